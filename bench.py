@@ -540,6 +540,26 @@ def bench_decode(args, model, eng, c, rank, world, device):
         dist.destroy_process_group()
 
 
+DUMP_SAMPLE = 1 << 22   # elements sampled from each of the parameter and gradient stores: 16 MB each
+
+
+def dump_outputs(out_dir, last, eng):
+    """What the last timed train step computed, as float32 .npy files: loss.npy and kld.npy (per caption, what train_step
+    returns), params_sample.npy and grads_sample.npy (the same seeded DUMP_SAMPLE positions of every parameter / gradient
+    element in state-dict order, without the stores' row padding), 32 MB in all at C2."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    loss, kld = last
+    arrays = {"loss": loss, "kld": kld}
+    for name, store in (("params_sample", eng.params), ("grads_sample", eng.grads)):
+        flat = torch.cat([v.reshape(-1) for v in store.views.values()])
+        idx = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        arrays[name] = flat[idx.to(flat.device)]
+        del flat
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -553,6 +573,9 @@ def main():
     ap.add_argument("--cbs-legs", default="all", choices=["all", "compiled"],
                     help="decode-cbs mode: all = compiled machines, the dense A/B and the selection step alone; compiled = the product path only")
     ap.add_argument("--dump-gemm", default="", help="write the per-shape GEMM timing table (roofline leg) to this file")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="train mode: after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): "
+                         "loss and kld per caption, and a fixed seeded sample of the updated parameters and of the gradients")
     ap.add_argument("--no-decode", action="store_true", help="skip the short decode leg of the default run")
     ap.add_argument("--dp-algo", default="rccl", choices=["auto", "rccl", "xgmi"],
                     help="gradient exchange at N > 1: rccl (default) = torch.distributed all-reduce; xgmi = direct reduce-scatter + "
@@ -567,6 +590,10 @@ def main():
                     help="only the timed train steps (no roofline / attention / decode / CPU legs): what the rocprofv3 passes run, "
                          "so that every profiled launch belongs to the C2 train step")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs and args.mode != "train":
+        ap.error("--dump-outputs: train mode only")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -625,15 +652,19 @@ def main():
     total_iters = 70000
 
     T_steps, Zdim = c["L"] + 1, c["Z"]
+    # a generator of the train steps' own: the decode legs before them draw from the default one once per search step, as many
+    # steps as their searches run, so with it the timed steps' inputs would depend on the decode's results and on which legs ran
+    eps_gen = torch.Generator(device=device)
+    eps_gen.manual_seed(5678 + rank)
 
     def step(i):
         feats, caps, senti, _ = batches[i % len(batches)]
         # the reparameterisation noise is DRAWN INSIDE the timed step, on the device (the reference draws it inside the step too,
         # per time step on the host: updown_cell.py:206); the pre-generated eps of `batches` serves the parity / roofline legs
-        eps = torch.randn(T_steps, c["B"], Zdim, device=device)
+        eps = torch.randn(T_steps, c["B"], Zdim, device=device, generator=eps_gen)
         lr = 0.015 * (1 - i / total_iters)
-        eng.train_step(feats, caps, senti, eps, lr=lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
-                       max_norm=12.5, decoder_frozen=False)
+        return eng.train_step(feats, caps, senti, eps, lr=lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
+                              max_norm=12.5, decoder_frozen=False)
 
     if args.timed_only or args.no_decode:   # no decode leg ran before: bring the GPU out of idle first (same count on every rank: the steps all-reduce)
         for i in range(args.prewarm):
@@ -648,7 +679,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -658,6 +689,8 @@ def main():
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, eng)
     dp_exposure = None
     if world > 1:
         eng.dp_profile = False

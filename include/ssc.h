@@ -132,7 +132,8 @@ int ssc_prep_tokens(const int64_t* caps, int B, int L, int pad, int boundary, in
 
 /* nn.Embedding forward (updown_captioner.py:430): out[i,:] = table[ids[i],:]  (n rows, E cols). */
 int ssc_embed_gather(const float* table, int ldt, const int64_t* ids, int n, int E, float* out, int ldo, void* stream);
-/* nn.Embedding backward: dtable[ids[i],:] += d[i,:] for ids[i] != pad (padding_idx row gets no grad). */
+/* nn.Embedding backward: dtable[ids[i],:] += d[i,:] for ids[i] != pad (padding_idx row gets no grad).  Deterministic: the rows
+   of one id are summed in ascending i and added to the table row once per 4096 positions. */
 int ssc_embed_scatter_add(float* dtable, int ldt, const int64_t* ids, int n, int E, const float* d, int ldd, int pad,
                           void* stream);
 

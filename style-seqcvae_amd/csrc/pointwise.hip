@@ -73,14 +73,82 @@ __global__ void embed_gather_kernel(const float* __restrict__ table, int ldt, co
   out[(size_t)i * ldo + e] = table[(size_t)ids[i] * ldt + e];
 }
 
-__global__ void embed_scatter_kernel(float* __restrict__ dt, int ldt, const int64_t* __restrict__ ids, int n, int E,
-                                     const float* __restrict__ d, int ldd, int pad) {
-  int i = blockIdx.y;
-  int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
-  int64_t id = ids[i];
-  if (id == pad) return;
-  atomicAdd(&dt[(size_t)id * ldt + e], d[(size_t)i * ldd + e]);
+// Deterministic: float atomics would add a token's rows in whatever order the blocks arrive, so the rounding (and, through the
+// next steps, the whole training run) would change from run to run.  Instead the blocks of a token's FIRST position sum the rows
+// of all its positions in ascending position order and add that sum with a plain store (once per kEmbedScatterChunk positions);
+// the blocks of its later positions exit.  The positions are listed in LDS first so that the sum keeps kEmbedScatterRows loads
+// in flight: a frequent token (the boundary token opens every caption) is not a chain of one load after another.
+constexpr int kEmbedScatterThreads = 256;
+constexpr int kEmbedScatterChunk = 4096;   // positions listed per pass
+constexpr int kEmbedScatterBatch = 8;    // ids loaded per thread before comparing
+constexpr int kEmbedScatterRows = 32;    // rows of d loaded per thread before adding
+__global__ void __launch_bounds__(kEmbedScatterThreads) embed_scatter_kernel(float* __restrict__ dt, int ldt,
+                                                                               const int64_t* __restrict__ ids, int n, int E,
+                                                                               const float* __restrict__ d, int ldd, int pad) {
+  __shared__ unsigned long long s_hit[kEmbedScatterChunk / SSC_WAVE];   // bit b of word w: ids[c0 + 64 w + b] == id
+  __shared__ int s_pos[kEmbedScatterChunk + kEmbedScatterRows];         // matching positions - c0, ascending
+  __shared__ int s_cnt;
+  const int i = blockIdx.y;
+  const int e = blockIdx.x * kEmbedScatterThreads + threadIdx.x;
+  const int64_t id = ids[i];
+  if (id == pad) return;   // (uniform over the block, as is the exit below)
+  // both scans over the ids below load kEmbedScatterBatch of them per thread before comparing: one memory latency per
+  // 2048 positions instead of one per 256
+  constexpr int kSpan = kEmbedScatterBatch * kEmbedScatterThreads;
+  bool earlier = false;
+  for (int j0 = threadIdx.x; j0 < i; j0 += kSpan) {
+    int64_t v[kEmbedScatterBatch];
+#pragma unroll
+    for (int u = 0; u < kEmbedScatterBatch; ++u) v[u] = ids[min(j0 + u * kEmbedScatterThreads, i - 1)];   // (clamped: no branch per load)
+#pragma unroll
+    for (int u = 0; u < kEmbedScatterBatch; ++u) earlier |= j0 + u * kEmbedScatterThreads < i && v[u] == id;
+  }
+  if (__syncthreads_or(earlier)) return;
+  const int lane = threadIdx.x % SSC_WAVE;
+  for (int c0 = i; c0 < n; c0 += kEmbedScatterChunk) {
+    const int cn = min(kEmbedScatterChunk, n - c0);
+    for (int k0 = 0; k0 < cn; k0 += kSpan) {   // (k0 is 0 or 2048: word (k0 + 256 u + 64 wave) / 64 < 64)
+      int64_t v[kEmbedScatterBatch];
+#pragma unroll
+      for (int u = 0; u < kEmbedScatterBatch; ++u) v[u] = ids[c0 + min(k0 + u * kEmbedScatterThreads + (int)threadIdx.x, cn - 1)];
+#pragma unroll
+      for (int u = 0; u < kEmbedScatterBatch; ++u) {
+        const unsigned long long hit = __ballot(k0 + u * kEmbedScatterThreads + (int)threadIdx.x < cn && v[u] == id);
+        if (lane == 0) s_hit[(k0 + u * kEmbedScatterThreads + threadIdx.x) / SSC_WAVE] = hit;
+      }
+    }
+    __syncthreads();
+    const int nw = (cn + SSC_WAVE - 1) / SSC_WAVE;
+    if (threadIdx.x < SSC_WAVE) {   // wave 0: word w's positions go behind those of words 0 .. w-1 (prefix sum over the lanes)
+      const unsigned long long m0 = lane < nw ? s_hit[lane] : 0ull;
+      const int c = __popcll(m0);
+      int incl = c;
+#pragma unroll
+      for (int o = 1; o < SSC_WAVE; o <<= 1) {
+        const int t = __shfl_up(incl, o, SSC_WAVE);
+        if (lane >= o) incl += t;
+      }
+      int q = incl - c;
+      for (unsigned long long m = m0; m; m &= m - 1) s_pos[q++] = lane * SSC_WAVE + __builtin_ctzll(m);
+      if (lane == SSC_WAVE - 1) s_cnt = incl;
+    }
+    __syncthreads();
+    const int cnt = s_cnt;
+    if (e < E) {
+      float s = 0.f;
+      for (int q0 = 0; q0 < cnt; q0 += kEmbedScatterRows) {
+        float v[kEmbedScatterRows];
+#pragma unroll
+        for (int u = 0; u < kEmbedScatterRows; ++u)
+          v[u] = q0 + u < cnt ? d[(size_t)(c0 + s_pos[q0 + u]) * ldd + e] : 0.f;
+#pragma unroll
+        for (int u = 0; u < kEmbedScatterRows; ++u)
+          if (q0 + u < cnt) s += v[u];
+      }
+      dt[(size_t)id * ldt + e] += s;
+    }
+    __syncthreads();   // (s_hit, s_pos and s_cnt are rewritten by the next chunk)
+  }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1262,8 +1330,8 @@ extern "C" int ssc_embed_gather(const float* table, int ldt, const int64_t* ids,
 extern "C" int ssc_embed_scatter_add(float* dtable, int ldt, const int64_t* ids, int n, int E, const float* d, int ldd,
                                      int pad, void* stream) {
   if (!dtable || !ids || !d || n <= 0 || E <= 0 || ldt < E || ldd < E) return SSC_EINVAL;
-  SSC_LAUNCH(embed_scatter_kernel, dim3(ssc_cdiv(E, 256), n), dim3(256), 0, S(stream), dtable, ldt, ids, n, E, d,
-                     ldd, pad);
+  SSC_LAUNCH(embed_scatter_kernel, dim3(ssc_cdiv(E, kEmbedScatterThreads), n), dim3(kEmbedScatterThreads), 0, S(stream), dtable,
+             ldt, ids, n, E, d, ldd, pad);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }
