@@ -661,6 +661,44 @@ size_t ssc_decode_search_workspace_bytes(const ssc_model_cfg* cfg, const ssc_sea
 int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Word-level sampling decoders (MultinomialSampler / TopKSampler / TopPSampler.sample_nodes,
+ * var_updown/var_updown/modules/beam_search.py:103-293, at one draw per row).  With log_probs = log_softmax(logits):
+ *   kind 0 multinomial(T): draw from softmax(log_probs / T)
+ *   kind 1 top-k(k, T):    keep the k largest log_probs (ties at the k-th place: lower index first), draw from softmax(kept / T)
+ *   kind 2 top-p(p, T):    sort log_softmax(log_probs / T) descending (ties: lower index first); a token is kept iff it is first or
+ *                          the tempered mass strictly ahead of it is < p (p = 0: the top token only; p >= 1: every token)
+ * The draw is Gumbel-max over the kept set: token = argmax_v logit_v / T + g_v (ties to the lower index), g_v = -log(-log(u_v)),
+ * u_v from Philox4x32-10 with key = seed and counter (v / 4, step, row id, 0), word v % 4, mapped to (0, 1) as
+ * (2 * (x >> 9) + 1) * 2^-24.  Reproducible bit for bit; no atomics in the choice.  The log-prob returned for a draw is the
+ * UNTEMPERED log_probs[token].  temperature > 0 (the runtime maps a top-k / top-p temperature of 0 to 1); 1 <= top_k <= V;
+ * 0 <= top_p <= 1.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int kind;            /* 0 multinomial, 1 top-k, 2 top-p */
+  int top_k;
+  float top_p;
+  float temperature;
+  uint64_t seed;
+} ssc_sampler_desc;
+/* One word per row from raw logits (rows, V) ld `ld`.  row_ids (rows) or NULL (row r): the batch entry of each row, the third
+ * Philox counter word.  last_pred (rows) or NULL: a row whose previous token is end_index has ended - it emits end_index at
+ * log-prob 0 and its logits are not read.  row_lp (rows) or NULL: the running caption log-prob, += the step log-prob.
+ * pred_out / lp_out (rows): the token and its untempered log-prob.  probs_out (rows, V) or NULL: the filtered, renormalised
+ * distribution of every row in vocabulary order (an ended row: one-hot at end_index). */
+int ssc_sample_rows(const float* logits, int ld, int rows, int V, const ssc_sampler_desc* s, const int64_t* row_ids, int step,
+                    const int64_t* last_pred, float* row_lp, int end_index, int64_t* pred_out, float* lp_out, float* probs_out,
+                    void* stream);
+/* The whole sampled decode of one diverse-decode call as ONE library call: the loop of ssc_decode_search with S = 1, beam = 1 and
+ * no machine (d->S = d->beam = 1, d->fsm = d->tables = d->mach = NULL; per_node is not used), ssc_sample_rows in place of the
+ * beam selection.  Batch entry b = (image, sample) is row b; step 0 feeds end_index (@@BOUNDARY@@).  d->skip_dead: ended rows
+ * are not stepped (ssc_decode_step_desc.row_lp).  d->early_stop / ctl / host_flag / host_flag_host: the protocol of
+ * ssc_beam_desc.ctl and ssc_decode_search (ctl[0] = number of columns; surplus queued steps are no-ops; bounded run-ahead).
+ * Out: d->predictions (B, max_steps) - columns >= ctl[0] hold end_index -, d->log_probs (B): each caption's summed log-prob. */
+size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
+int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ import torch  # noqa: E402
 from ssc_runtime.config import Config  # noqa: E402
 from ssc_runtime.data import SyntheticCaptionData, TensorFileData  # noqa: E402
 from ssc_runtime.inference import diverse_decode  # noqa: E402
+from ssc_runtime import sampling  # noqa: E402
 from ssc_runtime.vocab import Vocabulary  # noqa: E402
 from var_updown.models import UpDownCaptioner  # noqa: E402
 
@@ -74,7 +75,8 @@ def main():
         data = TensorFileData(_A.infer_tensors)
     cls = _LocalGlove if (_C.MODEL.EMBEDDING_SIZE in (300, 600) and _A.checkpoint_path) else UpDownCaptioner
     extra = {"mean_choice": {}} if _C.MODEL.SENTIMENT_VAE == 2 else {}   # (per-region attribute MEANS come with the data: data.obj)
-    model = cls.from_config(_C, vocabulary=vocabulary, device=device, **extra).to(device)
+    sampler = sampling.from_config(_C.MODEL)   # MODEL.DECODE_SAMPLER: None = beam search
+    model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
     model.eval()
@@ -82,6 +84,9 @@ def main():
     model._dec.weights_frozen = True   # the checkpoint's weights stay as they are for the whole run: weight-only tables are formed once
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
+    if sampler is not None and (_A.constraints_json or _A.boxes_json):
+        raise SystemExit(f"MODEL.DECODE_SAMPLER {_C.MODEL.DECODE_SAMPLER!r} does not take constraints: constrained sampling is "
+                         "not supported")
     boundary = vocabulary.get_token_index("@@BOUNDARY@@")
     predictions = []
     id2word = np.array([vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())], dtype=object)
@@ -138,7 +143,7 @@ def main():
             obj = data.obj[lo: lo + n_here, : feats.size(1)].to(device) if getattr(data, "obj", None) is not None else None
             pred, _ = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
-                                     obj_means=obj)
+                                     obj_means=obj, sampler=sampler)
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
             ids = pred.cpu().numpy()                                   # (images, n_z, steps)

@@ -1,0 +1,588 @@
+// Word-level sampling decoders: multinomial, top-k and top-p (nucleus) draws of one word per row, as a stand-alone row sampler
+// (ssc_sample_rows) and as the whole sampled decode of a diverse-decode call in one library call (ssc_decode_sample).
+// Reference: MultinomialSampler / TopKSampler / TopPSampler.sample_nodes (var_updown/var_updown/modules/beam_search.py:103-293)
+// at per_node_beam_size 1, driven like the one-state beam search of ssc_decode_search with beam 1.
+//
+// One workgroup per row.  The row's raw logits are read from HBM once: for V <= SAMPLE_LDS_MAX_V into LDS, after which every pass
+// (maximum, log-sum-exp, the radix selection of the cut, the draw) runs on LDS; longer rows take the same passes over global memory.
+// The cut of top-k / top-p is a radix select (8-bit digits, most significant first) on an order-preserving key of the value, with
+// per-bucket histograms of the count (top-k) or of the tempered probability mass in 2^-40 fixed point (top-p): integer LDS atomics
+// only, so every histogram - and therefore the kept set - is independent of the order the lanes arrive in.  Ties at the cut are
+// resolved by a second radix select on the index (lower index first).  The draw is Gumbel-max over the kept set with
+// counter-based Philox4x32-10 noise: bit-reproducible for a given seed, no float atomics, no order-dependent reduction.
+#include <math.h>
+#include <thread>
+
+#include "ssc_common.h"
+
+namespace {
+
+constexpr int SAMPLE_THREADS = 256;
+constexpr int SAMPLE_WAVES = SAMPLE_THREADS / 64;
+constexpr int SAMPLE_LDS_MAX_V = 32768;             // 128 KiB row in LDS (+ ~3 KiB of histograms) of the 160 KiB per CU
+constexpr double SAMPLE_MASS_ONE = 1099511627776.0;  // 2^40: fixed-point scale of the top-p masses
+
+inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011)
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+}
+// 32 random bits -> u in the open interval (0, 1): the odd multiples of 2^-24 below 1 (exact in fp32)
+__device__ __forceinline__ float sample_uniform(uint32_t x) { return (float)(((x >> 9) << 1) | 1u) * 5.9604644775390625e-08f; }
+__device__ __forceinline__ float sample_gumbel(uint32_t x) { return -logf(-logf(sample_uniform(x))); }
+
+// order-preserving key: a > b (floats, no NaN) <=> key(a) > key(b)
+__device__ __forceinline__ uint32_t sample_key(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+struct SampleShared {
+  uint32_t cnt[256];
+  unsigned long long mass[256];
+  float red[SAMPLE_WAVES];
+  float bestv[SAMPLE_WAVES];
+  int besti[SAMPLE_WAVES];
+  uint32_t sel_key;
+  int sel_found;
+  unsigned long long sel_ahead, sel_w;
+  uint32_t sel_cnt;
+};
+
+// block-wide max / sum in a fixed order (wave butterflies, then the waves in index order): the same result on every run
+__device__ __forceinline__ float block_max(float v, SampleShared& sh) {
+  v = ssc_wave_max(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh.red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh.red[0];
+  for (int w = 1; w < SAMPLE_WAVES; ++w) r = fmaxf(r, sh.red[w]);
+  return r;
+}
+__device__ __forceinline__ float block_sum(float v, SampleShared& sh) {
+  v = ssc_wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh.red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  float r = sh.red[0];
+  for (int w = 1; w < SAMPLE_WAVES; ++w) r += sh.red[w];
+  return r;
+}
+
+// the row, four consecutive entries at a time (entries >= V read as -inf)
+template <bool STAGED>
+struct RowView {
+  const float* g;   // global row
+  const float* s;   // LDS row (STAGED)
+  int V;
+  bool vec;         // global row 16-byte aligned with V % 4 == 0
+  __device__ __forceinline__ void get4(int j, float x[4]) const {
+    const int v = 4 * j;
+    if (STAGED) {
+      if (v + 3 < V) {
+        const float4 q = *reinterpret_cast<const float4*>(s + v);
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+        return;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x[c] = v + c < V ? s[v + c] : -INFINITY;
+    } else {
+      if (vec) {
+        const float4 q = *reinterpret_cast<const float4*>(g + v);
+        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+        return;
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x[c] = v + c < V ? g[v + c] : -INFINITY;
+    }
+  }
+  __device__ __forceinline__ float at(int v) const { return STAGED ? s[v] : g[v]; }
+};
+
+// One radix-select descent.  Every row entry v offers (active, key, weight); the entries are ranked by key DESCENDING.  Finds the
+// first entry, in that order, at which the running weight (inclusive) reaches `thr` - restricted to keys; the result is its key,
+// the weight strictly ahead of its key, and the count / weight of the entries that share its key.  found = 0: the total weight
+// stays below thr.  MASS = false: every active entry weighs 1.
+template <bool STAGED, bool MASS, typename F>
+__device__ void radix_descent(const RowView<STAGED>& row, F&& offer, unsigned long long thr, SampleShared& sh) {
+  const int lane = threadIdx.x & 63;
+  uint32_t prefix = 0;
+  unsigned long long ahead = 0;
+  const int nj = (row.V + 3) >> 2;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    const uint32_t hi_mask = shift == 24 ? 0u : ~((1u << (shift + 8)) - 1u);
+    for (int b = threadIdx.x; b < 256; b += SAMPLE_THREADS) { sh.cnt[b] = 0; sh.mass[b] = 0; }
+    __syncthreads();
+    for (int j0 = 0; j0 < nj; j0 += SAMPLE_THREADS) {   // (wave-uniform trip count: the ballots below see whole waves)
+      const int j = j0 + (int)threadIdx.x;
+      float x[4];
+      if (j < nj) row.get4(j, x);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int v = 4 * j + c;
+        bool act = false;
+        uint32_t key = 0;
+        unsigned long long w = 1;
+        if (j < nj && v < row.V) act = offer(v, x[c], key, w);
+        act = act && (key & hi_mask) == prefix;
+        const uint32_t bucket = (key >> shift) & 255u;
+        // the most frequent case - the lanes of a wave share their bucket (logits cluster in a few exponents) - as ONE atomic
+        // pair per wave: the first active lane's bucket is aggregated, the other lanes add their own
+        const unsigned long long am = __ballot(act);
+        if (am) {
+          const int leader = __ffsll((long long)am) - 1;
+          const uint32_t lb = __shfl(bucket, leader, 64);
+          const bool mine = act && bucket == lb;
+          const unsigned long long mm = __ballot(mine);
+          const unsigned long long ws = MASS ? wave_sum_u64(mine ? w : 0ull) : 0ull;
+          if (lane == leader) {
+            atomicAdd(&sh.cnt[lb], (uint32_t)__popcll(mm));
+            if (MASS) atomicAdd(&sh.mass[lb], ws);
+          }
+          if (act && !mine) {
+            atomicAdd(&sh.cnt[bucket], 1u);
+            if (MASS) atomicAdd(&sh.mass[bucket], w);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {   // wave 0: lane l holds buckets 255 - 4l ... 252 - 4l; exclusive scan of the weights, descending
+      unsigned long long wb[4];
+      uint32_t cb[4];
+      unsigned long long tot = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int b = 255 - 4 * lane - c;
+        cb[c] = sh.cnt[b];
+        wb[c] = MASS ? sh.mass[b] : (unsigned long long)cb[c];
+        tot += wb[c];
+      }
+      unsigned long long incl = tot;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long y = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += y;
+      }
+      unsigned long long a = ahead + (incl - tot);
+      int hit = -1;
+      unsigned long long hit_ahead = 0;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (hit < 0 && cb[c] > 0 && a + wb[c] >= thr) { hit = c; hit_ahead = a; }
+        a += wb[c];
+      }
+      const unsigned long long hm = __ballot(hit >= 0);
+      const int first = hm ? __ffsll((long long)hm) - 1 : -1;
+      if (lane == (first < 0 ? 0 : first)) {
+        sh.sel_found = first >= 0;
+        if (first >= 0) {
+          const int b = 255 - 4 * lane - hit;
+          sh.sel_key = prefix | ((uint32_t)b << shift);
+          sh.sel_ahead = hit_ahead;
+          sh.sel_w = wb[hit];
+          sh.sel_cnt = cb[hit];
+        }
+      }
+    }
+    __syncthreads();
+    if (!sh.sel_found) return;
+    prefix = sh.sel_key;
+    ahead = sh.sel_ahead;
+    __syncthreads();   // (sh.sel_* and the histograms are rewritten by the next pass)
+  }
+  // here sh.sel_key is the whole key of the cut, sh.sel_ahead the weight ahead of it, sh.sel_cnt / sh.sel_w its entries
+}
+
+struct SampleArgs {
+  const float* logits; size_t ld; int V;
+  int kind, top_k; float top_p, temperature;
+  uint32_t seed_lo, seed_hi;
+  const int64_t* row_ids; int step;
+  const int64_t* last_pred; float* row_lp; int end_index;
+  int64_t* pred_out; float* lp_out; float* probs_out;
+  int* ctl; int max_steps; int* host_flag;
+};
+
+template <bool STAGED>
+__global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(SampleArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float srow[];
+  __shared__ SampleShared sh;
+  const int r = blockIdx.x;
+  const int V = a.V;
+  const bool stopped = a.ctl && a.ctl[0] <= a.step;   // (written by an EARLIER launch of this stream: the search has ended)
+  const bool ended = stopped || (a.last_pred && a.last_pred[r] == a.end_index);   // workgroup-uniform
+  int64_t tok = a.end_index;
+  float lp = 0.f;
+  if (!ended) {
+    const float* g = a.logits + (size_t)r * a.ld;
+    RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
+    const int nj = (V + 3) >> 2;
+    // ---- stage the row (once from HBM) and its maximum ---------------------------------------------------------------------
+    float mx = -INFINITY;
+    if (STAGED) {
+      RowView<false> gv{g, nullptr, V, row.vec};
+      for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+        float x[4];
+        gv.get4(j, x);
+        if (4 * j + 3 < V) {
+          *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
+        } else {
+          for (int c = 0; c < 4; ++c)
+            if (4 * j + c < V) srow[4 * j + c] = x[c];
+        }
+        mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
+      }
+    } else {
+      for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+        float x[4];
+        row.get4(j, x);
+        mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
+      }
+    }
+    mx = block_max(mx, sh);   // (its barriers also publish srow)
+    const float T = a.temperature;
+    const bool topp = a.kind == 2 && a.top_p < 1.f;
+    // ---- untempered log-sum-exp (the step log-prob) and the tempered normaliser (top-p masses) -------------------------------
+    float s = 0.f, st = 0.f;
+    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+      float x[4];
+      row.get4(j, x);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        s += expf(x[c] - mx);
+        if (topp) st += expf((x[c] - mx) / T);
+      }
+    }
+    s = block_sum(s, sh);
+    const float lse = mx + logf(s);
+    float invz = 0.f;
+    if (topp) invz = 1.f / block_sum(st, sh);
+    // ---- the cut: kept <=> key > cut_key, or key == cut_key and v <= cut_idx ------------------------------------------------
+    uint32_t cut_key = 0;
+    int cut_idx = 0x7fffffff;   // (defaults: every entry kept)
+    const bool topk = a.kind == 1 && a.top_k < V;
+    if (topk || topp) {
+      unsigned long long thr;
+      bool found;
+      if (topk) {
+        thr = (unsigned long long)a.top_k;
+        radix_descent<STAGED, false>(row, [&](int, float x, uint32_t& key, unsigned long long& w) {
+          key = sample_key(x); w = 1; return true; }, thr, sh);
+      } else {
+        thr = (unsigned long long)llrint((double)a.top_p * SAMPLE_MASS_ONE);
+        radix_descent<STAGED, true>(row, [&](int, float x, uint32_t& key, unsigned long long& w) {
+          key = sample_key(x);
+          w = (unsigned long long)llrintf(expf((x - mx) / T) * invz * 1099511627776.0f);
+          return true; }, thr, sh);
+      }
+      found = sh.sel_found != 0;
+      if (found) {
+        cut_key = sh.sel_key;
+        const unsigned long long ahead = sh.sel_ahead, wt = sh.sel_w;
+        const uint32_t ct = sh.sel_cnt;
+        // entries tied at the cut share one weight; the n-th of them (lowest index first) is the cut
+        unsigned long long n;
+        if (topk) n = thr - ahead;
+        else {
+          const unsigned long long each = wt / ct;
+          n = (each == 0 || thr <= ahead) ? 1 : (thr - ahead + each - 1) / each;
+        }
+        n = n < 1 ? 1 : (n > ct ? ct : n);
+        __syncthreads();
+        if (n < ct) {
+          const uint32_t ck = cut_key;
+          radix_descent<STAGED, false>(row, [&](int v, float x, uint32_t& key, unsigned long long& w) {
+            key = ~(uint32_t)v; w = 1; return sample_key(x) == ck; }, n, sh);
+          cut_idx = (int)~sh.sel_key;
+        }
+        __syncthreads();
+      }
+    }
+    // ---- Gumbel-max over the kept set: argmax_v logit_v / T + g_v, ties to the lower index --------------------------------------
+    const uint32_t b = (uint32_t)(a.row_ids ? a.row_ids[r] : r);
+    float best = -INFINITY, zk = 0.f;
+    int besti = -1;
+    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+      float x[4];
+      row.get4(j, x);
+      uint32_t ctr[4] = {(uint32_t)j, (uint32_t)a.step, b, 0u};
+      philox4x32_10(ctr, a.seed_lo, a.seed_hi);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int v = 4 * j + c;
+        const uint32_t key = sample_key(x[c]);
+        const bool kept = v < V && (key > cut_key || (key == cut_key && v <= cut_idx));
+        if (kept) {
+          const float sc = x[c] / T + sample_gumbel(ctr[c]);
+          if (besti < 0 || sc > best) { best = sc; besti = v; }   // (v ascending within the thread: > keeps the lower index)
+          if (a.probs_out) zk += expf((x[c] - mx) / T);
+        }
+      }
+    }
+    // block argmax, ties to the lower index
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(best, o, 64);
+      const int oi = __shfl_xor(besti, o, 64);
+      if (oi >= 0 && (besti < 0 || ov > best || (ov == best && oi < besti))) { best = ov; besti = oi; }
+    }
+    __syncthreads();
+    if (lane == 0) { sh.bestv[threadIdx.x >> 6] = best; sh.besti[threadIdx.x >> 6] = besti; }
+    __syncthreads();
+    best = sh.bestv[0]; besti = sh.besti[0];
+    for (int w = 1; w < SAMPLE_WAVES; ++w) {
+      const float ov = sh.bestv[w];
+      const int oi = sh.besti[w];
+      if (oi >= 0 && (besti < 0 || ov > best || (ov == best && oi < besti))) { best = ov; besti = oi; }
+    }
+    tok = besti;
+    lp = row.at(besti) - lse;
+    if (a.probs_out) {   // the filtered, renormalised distribution in vocabulary order (tests, diagnostics)
+      zk = block_sum(zk, sh);
+      float* po = a.probs_out + (size_t)r * V;
+      for (int v = threadIdx.x; v < V; v += SAMPLE_THREADS) {
+        const float x = row.at(v);
+        const uint32_t key = sample_key(x);
+        const bool kept = key > cut_key || (key == cut_key && v <= cut_idx);
+        po[v] = kept ? expf((x - mx) / T) / zk : 0.f;
+      }
+    }
+  } else if (a.probs_out) {
+    float* po = a.probs_out + (size_t)r * V;
+    for (int v = threadIdx.x; v < V; v += SAMPLE_THREADS) po[v] = v == a.end_index ? 1.f : 0.f;
+  }
+  if (threadIdx.x == 0) {
+    a.pred_out[r] = tok;
+    a.lp_out[r] = lp;
+    if (a.row_lp) a.row_lp[r] += lp;
+  }
+  // early stop (the protocol of ssc_beam_desc.ctl, with the step as the column index): count the rows that have not ended; the last
+  // workgroup of the step notes an all-ended step in ctl[0] / host_flag[0] and its own completion in host_flag[1]
+  if (a.ctl && threadIdx.x == 0) {
+    int* cnt = a.ctl + 2 + a.step;
+    int* ticket = a.ctl + 2 + a.max_steps + a.step;
+    if (tok != a.end_index) atomicAdd(cnt, 1);
+    __threadfence();
+    const int done = atomicAdd(ticket, 1);
+    if (done == (int)gridDim.x - 1) {
+      if (!stopped) {
+        __threadfence();
+        if (atomicAdd(cnt, 0) == 0) {
+          atomicMin(a.ctl, a.step + 1);
+          if (a.host_flag) __hip_atomic_store(a.host_flag, a.step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+      }
+      if (a.host_flag) __hip_atomic_store(a.host_flag + 1, a.step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+}
+
+int sample_launch(SampleArgs a, int rows, hipStream_t st) {
+  if (a.V <= SAMPLE_LDS_MAX_V) {
+    const size_t lds = (size_t)((a.V + 3) & ~3) * 4;
+    if (lds > 64 * 1024 &&
+        hipFuncSetAttribute((const void*)sample_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+      return SSC_EHIP;
+    SSC_LAUNCH(sample_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
+  } else {
+    SSC_LAUNCH(sample_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
+  }
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+bool sampler_ok(const ssc_sampler_desc* s, int V) {
+  if (!s || V <= 0) return false;
+  if (!(s->temperature > 0.f) || !isfinite(s->temperature)) return false;
+  if (s->kind == 0) return true;
+  if (s->kind == 1) return s->top_k >= 1 && s->top_k <= V;
+  if (s->kind == 2) return s->top_p >= 0.f && s->top_p <= 1.f;
+  return false;
+}
+
+SampleArgs sample_args(const ssc_sampler_desc* s, const float* logits, size_t ld, int V) {
+  SampleArgs a{};
+  a.logits = logits; a.ld = ld; a.V = V;
+  a.kind = s->kind; a.top_k = s->top_k; a.top_p = s->top_p; a.temperature = s->temperature;
+  a.seed_lo = (uint32_t)(s->seed & 0xffffffffu); a.seed_hi = (uint32_t)(s->seed >> 32);
+  return a;
+}
+
+__global__ void sample_ctl_init_kernel(int* __restrict__ ctl, int n, int max_steps) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) ctl[i] = i == 0 ? max_steps : 0;
+}
+__global__ void sample_fill_i64_kernel(int64_t* __restrict__ p, int n, int64_t v) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+// preds (max_steps, B) -> out (B, max_steps); columns >= ctl[0] (steps the host never queued) hold end_index
+__global__ void sample_collect_kernel(const int64_t* __restrict__ preds, const int* __restrict__ ctl, int max_steps, int B,
+                                      int end_index, int64_t* __restrict__ out) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const int steps = ctl ? min(max(ctl[0], 1), max_steps) : max_steps;
+  for (int t = 0; t < max_steps; ++t) out[(size_t)b * max_steps + t] = t < steps ? preds[(size_t)t * B + b] : end_index;
+}
+
+struct SampleLayout {
+  size_t st[2][4];   // h1, c1, hd, cd: two generations of (B, H)
+  size_t tokens0;    // (B) int64 start tokens
+  size_t parent0;    // (B) int64 zeros: every row is its own parent (the beam-1 search's parent list)
+  size_t preds;      // (max_steps, B) int64
+  size_t lp;         // (B) running caption log-probs
+  size_t steplp;     // (B) the last step's log-probs
+  size_t alpha;      // (B, R)
+  size_t logits;     // (B, V)
+  size_t stepws, stepws_bytes;
+  size_t total;
+};
+
+SampleLayout sample_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  SampleLayout l;
+  const size_t B = (size_t)d->nimg * d->n_samples, H = cfg->H;
+  size_t o = 0;
+  for (int g = 0; g < 2; ++g)
+    for (int k = 0; k < 4; ++k) { l.st[g][k] = o; o += a256(B * H * 4); }
+  l.tokens0 = o; o += a256(B * 8);
+  l.parent0 = o; o += a256(B * 8);
+  l.preds = o; o += a256((size_t)d->max_steps * B * 8);
+  l.lp = o; o += a256(B * 4);
+  l.steplp = o; o += a256(B * 4);
+  l.alpha = o; o += a256(B * (size_t)d->R * 4);
+  l.logits = o; o += a256(B * (size_t)cfg->V * 4);
+  l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)B, d->R);
+  l.stepws = o; o += a256(l.stepws_bytes);
+  l.total = o;
+  return l;
+}
+
+bool sample_desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  if (!cfg || !d) return false;
+  if (d->nimg <= 0 || d->R <= 0 || d->n_samples <= 0 || d->max_steps <= 0 || d->end_index < 0 || d->end_index >= cfg->V) return false;
+  if (d->S != 1 || d->beam != 1 || d->fsm || d->tables || d->mach) return false;   // word sampling: one row per batch entry, no machine
+  const long B = (long)d->nimg * d->n_samples;
+  if (B > (1L << 24)) return false;
+  if (!d->feats || !d->imgbuf || !d->eps0 || (d->max_steps > 1 && !d->eps) || !d->predictions || !d->log_probs || !d->ctl) return false;
+  if (cfg->kld_mode == 2 ? !d->obj_atts : ((cfg->S || cfg->pm_scale != 0.f) && !d->sentiment)) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int ssc_sample_rows(const float* logits, int ld, int rows, int V, const ssc_sampler_desc* s, const int64_t* row_ids,
+                               int step, const int64_t* last_pred, float* row_lp, int end_index, int64_t* pred_out, float* lp_out,
+                               float* probs_out, void* stream) {
+  if (!logits || !pred_out || !lp_out || rows < 0 || ld < V || step < 0 || !sampler_ok(s, V)) return SSC_EINVAL;
+  if (last_pred && (end_index < 0 || end_index >= V)) return SSC_EINVAL;
+  if (rows == 0) return SSC_OK;
+  SampleArgs a = sample_args(s, logits, (size_t)ld, V);
+  a.row_ids = row_ids; a.step = step; a.last_pred = last_pred; a.row_lp = row_lp; a.end_index = end_index;
+  a.pred_out = pred_out; a.lp_out = lp_out; a.probs_out = probs_out;
+  return sample_launch(a, rows, (hipStream_t)stream);
+}
+
+extern "C" size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->max_steps <= 0 || d->R <= 0) return 0;
+  return sample_layout(cfg, d).total;
+}
+
+extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
+  if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
+  const SampleLayout l = sample_layout(cfg, d);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* W = (char*)workspace;
+  const int B = d->nimg * d->n_samples, H = cfg->H, V = cfg->V, Z = cfg->Z;
+  float* stt[2][4];
+  for (int g = 0; g < 2; ++g)
+    for (int k = 0; k < 4; ++k) stt[g][k] = (float*)(W + l.st[g][k]);
+  int64_t* tokens0 = (int64_t*)(W + l.tokens0);
+  int64_t* parent0 = (int64_t*)(W + l.parent0);
+  int64_t* preds = (int64_t*)(W + l.preds);
+  float* lp = (float*)(W + l.lp);
+  float* steplp = (float*)(W + l.steplp);
+  float* logits = (float*)(W + l.logits);
+  const int nctl = 2 + 2 * d->max_steps;
+  int* ctl = d->ctl;
+
+  SSC_LAUNCH(sample_ctl_init_kernel, dim3(ssc_cdiv(nctl, 256)), dim3(256), 0, st, ctl, nctl, d->max_steps);
+  SSC_CHECK_LAUNCH();
+  SSC_LAUNCH(sample_fill_i64_kernel, dim3(ssc_cdiv(B, 256)), dim3(256), 0, st, tokens0, B, (int64_t)d->end_index);
+  SSC_CHECK_LAUNCH();
+  if (hipMemsetAsync(parent0, 0, (size_t)B * 8, st) != hipSuccess) return SSC_EHIP;
+  if (hipMemsetAsync(lp, 0, (size_t)B * 4, st) != hipSuccess) return SSC_EHIP;
+  for (int k = 0; k < 4; ++k)   // zero start states (updown_cell.py:131-141)
+    if (hipMemsetAsync(stt[1][k], 0, (size_t)B * H * 4, st) != hipSuccess) return SSC_EHIP;
+
+  // the steps take the form the beam-1 search gives them (ssc_decode_search with S = beam = 1): same tables, same parent list
+  const bool table = d->R <= 128 && B >= 512 && d->n_samples >= 16 && ssc_decode_att_table_enabled();
+  ssc_decode_step_desc sd{};
+  sd.R = d->R; sd.feats = d->feats; sd.imgbuf = d->imgbuf; sd.alpha = (float*)(W + l.alpha); sd.log_probs = logits; sd.raw_logits = 1;
+  sd.obj_atts = d->obj_atts;
+  sd.G = B; sd.rows_per_image = d->n_samples; sd.tokens = tokens0; sd.sentiment = d->sentiment; sd.eps = d->eps0;
+  sd.h1 = stt[1][0]; sd.c1 = stt[1][1]; sd.hd = stt[1][2]; sd.cd = stt[1][3];
+  sd.h1_out = stt[0][0]; sd.c1_out = stt[0][1]; sd.hd_out = stt[0][2]; sd.cd_out = stt[0][3];
+  sd.att_table = table ? 2 : 0;
+  SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+  SampleArgs a = sample_args(s, logits, (size_t)V, V);
+  a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
+  a.ctl = d->early_stop ? ctl : nullptr; a.max_steps = d->max_steps; a.host_flag = d->early_stop ? d->host_flag : nullptr;
+  a.step = 0; a.last_pred = nullptr; a.pred_out = preds;
+  SSC_TRY(sample_launch(a, B, st));
+  // Early stop and the host's bounded run-ahead: as in ssc_decode_search (the sampler's last workgroup of step t notes t in
+  // host_flag[1]; step t is queued only once step t - RUN_AHEAD has completed).  Not under stream capture.
+  constexpr int RUN_AHEAD = 2;
+  bool bounded = false;
+  if (d->early_stop && d->host_flag_host) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
+    bounded = cs == hipStreamCaptureStatusNone;
+  }
+  auto wait_for_step = [&](int step) {
+    const volatile int* hf = (const volatile int*)d->host_flag_host;
+    for (unsigned spin = 1; hf[1] < step && hf[0] == 0; ++spin) {
+      if ((spin & 1023u) == 0 && hipStreamQuery(st) != hipErrorNotReady) { (void)hipGetLastError(); break; }
+      std::this_thread::yield();
+    }
+  };
+  int cur = 0;
+  sd.att_table = table ? 1 : 0;
+  sd.parent = parent0; sd.group = 1;
+  for (int t = 1; t < d->max_steps; ++t) {
+    if (bounded && t > RUN_AHEAD) wait_for_step(t - RUN_AHEAD);
+    if (d->early_stop && d->host_flag_host && *(volatile const int*)d->host_flag_host != 0) break;
+    const int64_t* last = preds + (size_t)(t - 1) * B;
+    sd.tokens = last; sd.eps = d->eps + (size_t)(t - 1) * B * Z;
+    sd.h1 = stt[cur][0]; sd.c1 = stt[cur][1]; sd.hd = stt[cur][2]; sd.cd = stt[cur][3];
+    sd.h1_out = stt[1 - cur][0]; sd.c1_out = stt[1 - cur][1]; sd.hd_out = stt[1 - cur][2]; sd.cd_out = stt[1 - cur][3];
+    sd.row_lp = d->skip_dead ? lp : nullptr; sd.end_index = d->end_index;   // ended rows are not stepped
+    SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+    a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
+    SSC_TRY(sample_launch(a, B, st));
+    cur = 1 - cur;
+  }
+  SSC_LAUNCH(sample_collect_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, st, preds, d->early_stop ? ctl : nullptr, d->max_steps, B,
+             d->end_index, d->predictions);
+  SSC_CHECK_LAUNCH();
+  if (hipMemcpyAsync(d->log_probs, lp, (size_t)B * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
+  return SSC_OK;
+}

@@ -63,6 +63,10 @@ def _defaults() -> dict:
             "LATENT_EMBEDDING": "glove", "PRIOR_STD": 1.0, "SIMPLE_VAE": True, "DO_USE_KLD_ANNEALING": False,
             "KLD_DECREASING": False, "KLD_INITIAL_WEIGHT": 2.0, "KLD_ANNEALING_PER_EPOCH": 0.25,
             "KLD_N_EPOCHS_BEFORE_RESET": 4,
+            # word-level sampling in place of beam search (ssc_runtime/sampling.py): "beam" (default), "multinomial", "top-k",
+            # "top-p" - the reference's MultinomialSampler / TopKSampler / TopPSampler (modules/beam_search.py:103-293); needs
+            # BEAM_SIZE 1 and no CBS
+            "DECODE_SAMPLER": "beam", "SAMPLER_TOP_K": 0, "SAMPLER_TOP_P": 1.0, "SAMPLER_TEMPERATURE": 1.0,
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,

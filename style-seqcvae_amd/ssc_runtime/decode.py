@@ -236,6 +236,52 @@ class DecodeEngine:
             _HOST_FLAGS.append(flag)
         return pred[:, :, :nsteps].contiguous().view(B, S, beam, nsteps), lps
 
+    def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
+               eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True):
+        """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
+        one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
+        64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
+        -> (predictions (B, steps) int64, log_probs (B,): each caption's summed untempered log-prob)."""
+        d = self.dims
+        B = ctx.nimg * n_samples
+        dev = self.device
+        sampler.check_vocab(d.V)
+        sd = _lib.SearchDesc()
+        sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
+        sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = 1, 1, 1, max_steps, end_index
+        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
+        sent = sentiment.reshape(B).to(dev, torch.float32).contiguous() if sentiment is not None else None
+        eps0 = eps0.to(dev, torch.float32).contiguous()
+        assert tuple(eps0.shape) == (B, d.Z), eps0.shape
+        if max_steps > 1:
+            eps = eps.to(dev, torch.float32).contiguous()
+            assert tuple(eps.shape) == (max_steps - 1, B, d.Z), (eps.shape, (max_steps - 1, B, d.Z))
+        sd.sentiment, sd.eps0, sd.eps = _lib.ptr(sent), _lib.ptr(eps0), _lib.ptr(eps) if max_steps > 1 else None
+        sd.obj_atts = _lib.ptr(ctx.obj)
+        sd.skip_dead = 1   # ended rows are not stepped
+        sd.early_stop = 1 if early_stop else 0
+        pred = torch.empty(B, max_steps, dtype=torch.int64, device=dev)
+        lps = torch.empty(B, dtype=torch.float32, device=dev)
+        ctl = torch.empty(2 + 2 * max_steps, dtype=torch.int32, device=dev)
+        sd.predictions, sd.log_probs, sd.ctl = _lib.ptr(pred), _lib.ptr(lps), _lib.ptr(ctl)
+        flag = None
+        if early_stop:
+            flag, flag_dev = _host_flag()
+            if flag_dev is not None:
+                sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
+        nbytes = self.lib.ssc_decode_sample_workspace_bytes(C.byref(self._cfg), C.byref(sd))
+        if self._sws is None or self._sws.numel() < nbytes:
+            self._sws = None   # (release before growing)
+            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        p = self._params()
+        sdesc = sampler.desc(seed)
+        self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), _lib.ptr(self._sws),
+                                   self._sws.numel(), _lib.stream_ptr())
+        nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call)
+        if flag is not None:
+            _HOST_FLAGS.append(flag)
+        return pred[:, :nsteps].contiguous(), lps
+
     def _step_from_embedding(self, ctx, token_embedding, states, sentiment, eps, prior_mean_out=None, prior_mean=None, prior_var=None):
         G = token_embedding.size(0)
         table = token_embedding.to(self.device, torch.float32).contiguous()

@@ -21,7 +21,8 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
                    max_steps: int, boundary_index: int, fsm: Optional[torch.Tensor] = None,
                    num_constraints: Optional[torch.Tensor] = None, min_constraints_to_satisfy: int = 0,
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
-                   skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None):
+                   skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
+                   sample_seed: Optional[int] = None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     fsm: None (trivial one-state machine, what MAX_GIVEN_CONSTRAINTS: 0 produces), or (nimg, S, S, V) uint8 - ONE machine per
     image, shared by its n_samples latent samples through an index list -, or (nimg*n_samples, S, S, V) (a copy per sample).
@@ -32,7 +33,17 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     logits (cbs_search(skip_dead=True)).  Every caption with a finite log-prob is the exact search's; should a selected caption
     have none (its constraints were not reachable within max_steps), the call is repeated exactly, with the same noise.
     compiled: the machines' CompiledFsm when the caller has it already.
-    obj_means (nimg, R, Z): per-region attribute means, SENTIMENT_VAE = 2 only (UpDownCaptioner.translate_obj_atts2obj_means)."""
+    obj_means (nimg, R, Z): per-region attribute means, SENTIMENT_VAE = 2 only (UpDownCaptioner.translate_obj_atts2obj_means).
+    sampler: None - beam search, as above -, or a word sampler of ssc_runtime.sampling (multinomial / top-k / top-p): every word
+    of every caption is then drawn on the device (DecodeEngine.sample, one library call); needs beam = 1 and fsm = None.
+    sample_seed: the 64-bit seed of the word draws; default: the call's one draw from the global generator (the seed of the
+    latent noise as well; with eps_steps given, one draw is made for the words), so a sampled call consumes the global random
+    state as a beam call does and sees the same latent noise as a beam-1 call."""
+    if sampler is not None:
+        if beam != 1:
+            raise ValueError(f"word sampling draws one word per row: beam must be 1, got {beam}")
+        if fsm is not None:
+            raise ValueError("word sampling does not take constraints (fsm): constrained sampling is not supported")
     dev = feats.device
     nimg = feats.size(0)
     d = dec.dims
@@ -47,7 +58,7 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     if not trivial and fsm.size(0) != B:
         assert fsm.size(0) == nimg, (fsm.shape, nimg, n_samples)
         mach = torch.arange(nimg, dtype=torch.int32, device=dev).repeat_interleave(n_samples)
-    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if eps_steps is None else None
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (eps_steps is None or (sampler is not None and sample_seed is None)) else None
     skip = bool(skip_dead) and (trivial or fsm.size(1) > 1)   # (trivial machine: only ended beams are left out of the steps)
     if not trivial and fsm.size(1) > 1 and compiled is None:
         from .decode import CompiledFsm
@@ -72,6 +83,11 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
             gen.manual_seed(seed)
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
+        if sampler is not None:
+            pred, lps = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
+                                   seed if sample_seed is None else sample_seed, early_stop=early_stop)
+            calls["k"] = pred.size(-1)
+            return pred.view(B, 1, 1, -1), lps.view(B, 1, 1)
         beams, lps = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
                                 fsm=None if trivial else fsm.contiguous(), compiled=compiled, mach=mach, skip_dead=skip_now,
                                 early_stop=early_stop)

@@ -134,6 +134,10 @@ class SearchDesc(C.Structure):
                 ("host_flag_host", vp)]
 
 
+class SamplerDesc(C.Structure):
+    _fields_ = [("kind", C.c_int), ("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("seed", C.c_uint64)]
+
+
 # name -> (restype, argtypes).  Every symbol include/ssc.h declares is listed; tests check they all resolve.
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -211,6 +215,9 @@ SYMBOLS = {
     "ssc_host_device_ptr": (_i, [vp, C.POINTER(vp)]),
     "ssc_decode_search_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_search": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), vp, _sz, vp]),
+    "ssc_sample_rows": (_i, [vp, _i, _i, _i, C.POINTER(SamplerDesc), vp, _i, vp, vp, _i, vp, vp, vp, vp]),
+    "ssc_decode_sample_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
+    "ssc_decode_sample": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), vp, _sz, vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)

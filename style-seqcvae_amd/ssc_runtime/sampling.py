@@ -1,0 +1,103 @@
+"""Word-level samplers for the diverse decode: multinomial, top-k and top-p (nucleus) draws of one word per row on the device
+(ssc_sample_rows / ssc_decode_sample, include/ssc.h).
+
+Reference: MultinomialSampler, TopKSampler, TopPSampler (var_updown/var_updown/modules/beam_search.py:103-293) - same constructor
+signatures and argument checks.  The reference draws with torch.multinomial; here the draw is Gumbel-max over the kept set with
+counter-based Philox4x32-10 noise keyed by a 64-bit seed: the same distribution, reproducible bit for bit.  One draw per row
+(beam 1, per_node_beam_size 1), so `with_replacement` has no effect.  Top-p keeps every token at p = 1 (the reference's fp32
+cumsum can fall short of 1 and drop tail tokens there).
+"""
+from . import lib as _lib
+
+KINDS = {"multinomial": 0, "top-k": 1, "top-p": 2}
+
+
+class Sampler:
+    kind = -1
+    name = ""
+
+    def desc(self, seed: int) -> "_lib.SamplerDesc":
+        """The C struct ssc_sampler_desc for a call with this 64-bit seed."""
+        d = _lib.SamplerDesc()
+        d.kind = self.kind
+        d.top_k = int(getattr(self, "k", 0))
+        d.top_p = float(getattr(self, "p", 1.0))
+        d.temperature = float(self.temperature)
+        d.seed = int(seed) & (2 ** 64 - 1)
+        return d
+
+    def check_vocab(self, V: int) -> None:
+        pass
+
+    def __repr__(self):
+        args = ", ".join(f"{k}={v!r}" for k, v in vars(self).items())
+        return f"{type(self).__name__}({args})"
+
+
+def _check_temperature(t) -> None:
+    if t < 0:
+        raise ValueError(f"temperature must not be negative, got {t}")
+
+
+class MultinomialSampler(Sampler):
+    """Draws from softmax(log_probs / temperature) (beam_search.py:103-141)."""
+    kind = 0
+    name = "multinomial"
+
+    def __init__(self, temperature: float = 1.0, with_replacement: bool = False) -> None:
+        _check_temperature(temperature)
+        if temperature <= 0:   # (the reference would divide by zero and draw from NaN)
+            raise ValueError(f"multinomial sampling needs temperature > 0, got {temperature}")
+        self.temperature = float(temperature)
+        self.with_replacement = with_replacement
+
+
+class TopKSampler(Sampler):
+    """Keeps the k largest log-probs (ties: lower index first), draws from softmax(kept / temperature) (beam_search.py:144-205).
+    A temperature of 0 means 1, as in the reference."""
+    kind = 1
+    name = "top-k"
+
+    def __init__(self, k: int = 1, temperature: float = 1.0, with_replacement: bool = False):
+        _check_temperature(temperature)
+        if int(k) != k or k < 1:
+            raise ValueError("k must be a postive integer no less than per_node_beam_size and no greater than vocabulary size")
+        self.k = int(k)
+        self.temperature = float(temperature or 1.0)
+        self.with_replacement = with_replacement
+
+    def check_vocab(self, V: int) -> None:
+        if not 1 <= self.k <= V:   # (beam_search.py:180-183)
+            raise ValueError("k must be a postive integer no less than per_node_beam_size and no greater than vocabulary size")
+
+
+class TopPSampler(Sampler):
+    """Keeps the smallest prefix of the tempered distribution, sorted descending (ties: lower index first), whose mass reaches p,
+    draws from it renormalised (beam_search.py:208-293).  A temperature of 0 means 1, as in the reference."""
+    kind = 2
+    name = "top-p"
+
+    def __init__(self, p: float = 0.9, temperature: float = 1.0, with_replacement: bool = False):
+        if p < 0.0 or p > 1.0:
+            raise ValueError("p must be a positive float no greater than 1.0")
+        _check_temperature(temperature)
+        self.p = float(p)
+        self.temperature = float(temperature or 1.0)
+        self.with_replacement = with_replacement
+
+
+def from_config(model_cfg):
+    """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE describe, or None for
+    "beam" (beam search, the default)."""
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    T = float(model_cfg.SAMPLER_TEMPERATURE)
+    if kind == "beam":
+        return None
+    if kind == "multinomial":
+        return MultinomialSampler(temperature=T)
+    if kind == "top-k":
+        return TopKSampler(k=int(model_cfg.SAMPLER_TOP_K), temperature=T)
+    if kind == "top-p":
+        return TopPSampler(p=float(model_cfg.SAMPLER_TOP_P), temperature=T)
+    raise ValueError(f"MODEL.DECODE_SAMPLER must be one of 'beam', 'multinomial', 'top-k', 'top-p', got {model_cfg.DECODE_SAMPLER!r} "
+                     "(the Gumbel / stochastic beam sampler is not supported)")

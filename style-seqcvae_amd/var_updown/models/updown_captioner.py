@@ -56,13 +56,19 @@ class UpDownCaptioner(nn.Module):
     def __init__(self, vocabulary, image_feature_size, embedding_size, hidden_size, attention_projection_size,
                  max_caption_length=20, beam_size=1, use_cbs=False, min_constraints_to_satisfy=2, z_space=150,
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
-                 sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None):
+                 sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
         is never defined, :89).  Here the caller supplies it: a dict of vectors, or use mean_choice_from_sentiglove /
-        mean_choice_from_senti_wordnet, which restate :80-86."""
+        mean_choice_from_senti_wordnet, which restate :80-86.
+        `sampler` (optional): a word sampler of ssc_runtime.sampling (MODEL.DECODE_SAMPLER) - the eval forward then draws every word
+        on the device (ssc_decode_sample) instead of running beam search; needs beam_size 1 and no CBS decode."""
         super().__init__()
+        if sampler is not None and beam_size != 1:
+            raise ValueError(f"MODEL.BEAM_SIZE must be 1 with MODEL.DECODE_SAMPLER {sampler.name!r} (word sampling draws one word per "
+                             f"row), got {beam_size}")
+        self.sampler = sampler
         self._vocabulary = vocabulary
         self.image_feature_size = image_feature_size
         self.embedding_size = embedding_size
@@ -141,7 +147,7 @@ class UpDownCaptioner(nn.Module):
                    prior_std=_C.MODEL.PRIOR_STD, simple_vae=_C.MODEL.SIMPLE_VAE, latent_embedding=_C.MODEL.LATENT_EMBEDDING,
                    sentiment_vae=_C.MODEL.SENTIMENT_VAE, senti_prior_multip=_C.MODEL.SENTI_PRIOR_MULTIP,
                    latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
-                   device=kwargs["device"], mean_choice=kwargs.get("mean_choice"))
+                   device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"))
 
     def _initialize_glove(self):
         """GloVe 42B (+ dependency embeddings for 600-d) rows for the vocabulary (updown_captioner.py:168-226).
@@ -280,6 +286,12 @@ class UpDownCaptioner(nn.Module):
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
         obj_means = self._obj_means(obj_atts, batch_size, num_boxes)   # (updown_captioner.py:246-247)
         step = functools.partial(self._decode_step, image_features, obj_means, sentiment=sentiment)
+        if self.sampler is not None:
+            if self._use_cbs and fsm is not None:
+                raise ValueError(f"MODEL.USE_CBS with a constraint machine cannot be combined with MODEL.DECODE_SAMPLER "
+                                 f"{self.sampler.name!r}: constrained sampling is not supported")
+            with torch.no_grad():
+                return {"predictions": self._sample_decode(image_features, obj_means, sentiment)}
         with torch.no_grad():
             if self._use_cbs and fsm is not None:
                 fsm_d = fsm.to(dev).to(torch.uint8)
@@ -292,6 +304,20 @@ class UpDownCaptioner(nn.Module):
                 beams, lps = self._beam_search.search(start_predictions, None, step, fsm_d)
                 best = beams[:, 0, 0, :]
         return {"predictions": best}
+
+    def _sample_decode(self, image_features, obj_means, sentiment):
+        """Eval forward with a word sampler: the whole decode in one library call (DecodeEngine.sample).  The latent noise is drawn
+        for every step up front from the same source as the beam path's (one (B, Z) draw per step); the word seed is one draw from
+        the global generator."""
+        B = image_features.size(0)
+        L = self._max_caption_length
+        dev = self._eng.device
+        ctx = self._image_context(image_features, obj_means)
+        eps = self._draw_eps(L, B, dev)
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        pred, _ = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed)
+        return pred
 
     def _image_context(self, image_features, obj_means=None):
         """Per-image terms (mask, averaged features, projected features, hoisted gate term) for the eval decode step, computed

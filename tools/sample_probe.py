@@ -1,0 +1,84 @@
+#!/usr/bin/env python3
+"""Time of the sampled decode (ssc_decode_sample) against the beam-1 and beam-5 searches (ssc_decode_search) at the bench's decode
+shape - 100 images x 20 latent samples per call, 36 x 2048 features, V 10 000, H 1200, max 20 steps, early stop off so every call
+runs all its steps -, and of the row sampler alone (sample_rows_kernel through ssc_sample_rows) on (G, V) logits, with its
+logits bytes / time against one HBM pass.
+    python tools/sample_probe.py [calls]
+Prints one JSON line."""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "style-seqcvae_amd"))
+sys.path.insert(0, ROOT)
+import torch
+
+import bench
+from ssc_runtime import lib as L
+from ssc_runtime import sampling
+from ssc_runtime.inference import diverse_decode
+from ssc_runtime.vocab import Vocabulary
+from var_updown.models import UpDownCaptioner
+
+
+def timed(fn, n):
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def main():
+    calls = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+    c = dict(bench.C2)
+    dev = torch.device("cuda", 0)
+    torch.manual_seed(0)
+    model = UpDownCaptioner(Vocabulary.synthetic(c["V"]), c["F"], c["E"], c["H"], c["A"], max_caption_length=c["L"], beam_size=5,
+                            z_space=c["Z"], sentiment_vae=1, senti_prior_multip=0.5, device=dev).to(dev).eval()
+    model._engine()
+    dec = model._dec
+    dec.weights_frozen = True
+    g = torch.Generator().manual_seed(4321)
+    images, n_z, steps = 100, 20, c["L"]
+    feats = torch.randn(images, c["R"], c["F"], generator=g).to(dev)
+    senti = torch.ones(images, device=dev)
+    out = {"images": images, "n_z": n_z, "max_steps": steps, "V": c["V"]}
+    t0 = time.perf_counter()
+    for name, beam, sampler in (("beam5", 5, None), ("beam1", 1, None), ("top_p_0.9", 1, sampling.TopPSampler(p=0.9)),
+                                ("top_k_40", 1, sampling.TopKSampler(k=40)), ("multinomial", 1, sampling.MultinomialSampler())):
+        ms = timed(lambda: diverse_decode(dec, feats, senti, n_z, beam, steps, 1, early_stop=False, sampler=sampler), calls)
+        out[name] = {"ms_per_call": ms, "us_per_step": ms * 1e3 / steps}
+    # the row sampler alone on (G, V) logits
+    lib = L.load()
+    G, V = images * n_z, c["V"]
+    logits = torch.randn(G, V, device=dev) * 3
+    pred = torch.empty(G, dtype=torch.int64, device=dev)
+    lp = torch.empty(G, dtype=torch.float32, device=dev)
+    out["row_kernel"] = {"G": G, "V": V}
+    for name, s in (("multinomial", sampling.MultinomialSampler()), ("top_k_40", sampling.TopKSampler(k=40)),
+                    ("top_p_0.9", sampling.TopPSampler(p=0.9))):
+        d = s.desc(7)
+
+        def run():
+            lib.ssc_sample_rows(L.ptr(logits), V, G, V, d, None, 1, None, None, 1, L.ptr(pred), L.ptr(lp), None, L.stream_ptr())
+        us = timed(run, 50) * 1e3
+        out["row_kernel"][name] = {"us": us, "GBps": G * V * 4 / us / 1e3}
+    # one HBM pass over the same bytes (a device copy reads and writes them: half its time is the read)
+    dst = torch.empty_like(logits)
+    us_copy = timed(lambda: dst.copy_(logits), 50) * 1e3
+    out["row_kernel"]["copy_read_write_us"] = us_copy
+    out["row_kernel"]["one_pass_GBps_from_copy"] = 2 * G * V * 4 / us_copy / 1e3
+    out["wall_s"] = time.perf_counter() - t0
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
