@@ -609,35 +609,30 @@ __device__ __forceinline__ void split4(const f32x4& v, u32x2& hi, u32x2& mid, u3
 // 2xFP16 (ssc_model_cfg.gemm_mode 3): 4 consecutive fp32 into TWO fp16 planes - ssc_split4_f16 (ssc_common.h)
 __device__ __forceinline__ void split4_f16(const f32x4& v, u32x2& hi, u32x2& lo) { ssc_split4_f16(v, hi, lo); }
 
-// WN = 32x32 MFMA tiles per wave along N: block tile 64 x (64*WN).  WN = 2 halves the A re-reads per streamed weight
-// byte (the CU-side load path, ~24 GB/s per CU, is what the skinny products saturate) at one workgroup per CU.
-// NBUF = LDS stages: 2 = one barrier per k-step (61 KB: two workgroups per CU); 1 = two barriers per k-step but half the
-// LDS (31 KB: four workgroups per CU) - each wave's in-order stream (loads, split, LDS stores, MFMAs) is what a single
-// workgroup is bound by, so more resident waves per SIMD matter more than the extra barrier.
-template <int PF, int WN, int NBUF>
+// PF = 2 k-steps prefetched in registers, one LDS stage (31 KB: four workgroups per CU) and so two barriers per k-step - each
+// wave's in-order stream (loads, split, LDS stores, MFMAs) is what a single workgroup is bound by, so more resident waves per
+// SIMD matter more than the extra barrier.  A 64x128 tile, two LDS stages and prefetch depths 1 and 4 measured slower
+// ("Negative results").
 __global__ __launch_bounds__(256) void gemm_x3_kernel(const KArgs a) {
-  constexpr int RB = 64 * WN;
-  constexpr int PLA = 64 * PL_ROW_B, PLB = RB * PL_ROW_B;   // bytes per plane
-  constexpr int STAGE_B = 3 * PLA + 3 * PLB;
-  __shared__ __attribute__((aligned(16))) unsigned char lds[NBUF * STAGE_B];
+  constexpr int PF = 2;
+  constexpr int PL = 64 * PL_ROW_B;   // bytes per plane (A and B tiles both 64 rows)
+  __shared__ __attribute__((aligned(16))) unsigned char lds[6 * PL];
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int half = lane >> 5, l31 = lane & 31;
   int bx, by;
   tile_order(blockIdx.y * gridDim.x + blockIdx.x, gridDim.x, gridDim.y, a.tile_gm, bx, by);
-  const int n0 = bx * RB, m0 = by * 64, z = blockIdx.z;
+  const int n0 = bx * 64, m0 = by * 64, z = blockIdx.z;
   const int s_lo = z * a.steps_per_split;
   int s_hi = s_lo + a.steps_per_split;
   if (s_hi > a.steps_total) s_hi = a.steps_total;
 
-  f32x16 acc[WN];
+  f32x16 acc;
 #pragma unroll
-  for (int ni = 0; ni < WN; ++ni)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[ni][i] = 0.f;
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 
-  typedef Stage<true, true, 64, RB, true> StageT;
+  typedef Stage<true, true, 64, 64, true> StageT;
   constexpr int NL = StageT::NLOADS;
   StageT st[PF];
   const int s_last = s_hi - 1;
@@ -654,8 +649,8 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const KArgs a) {
       split4(v, hi, mid, lo);
       unsigned char* p = base + row * PL_ROW_B + kq * 8;
       *reinterpret_cast<u32x2*>(p) = hi;
-      *reinterpret_cast<u32x2*>(p + PLA) = mid;
-      *reinterpret_cast<u32x2*>(p + 2 * PLA) = lo;
+      *reinterpret_cast<u32x2*>(p + PL) = mid;
+      *reinterpret_cast<u32x2*>(p + 2 * PL) = lo;
     }
 #pragma unroll
     for (int u = 0; u < StageT::NVB; ++u) {
@@ -665,16 +660,16 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const KArgs a) {
       if (!((x.okb >> u) & 1u)) v = f32x4{0.f, 0.f, 0.f, 0.f};
       u32x2 hi, mid, lo;
       split4(v, hi, mid, lo);
-      unsigned char* p = base + 3 * PLA + row * PL_ROW_B + kq * 8;
+      unsigned char* p = base + 3 * PL + row * PL_ROW_B + kq * 8;
       *reinterpret_cast<u32x2*>(p) = hi;
-      *reinterpret_cast<u32x2*>(p + PLB) = mid;
-      *reinterpret_cast<u32x2*>(p + 2 * PLB) = lo;
+      *reinterpret_cast<u32x2*>(p + PL) = mid;
+      *reinterpret_cast<u32x2*>(p + 2 * PL) = lo;
     }
   };
 
   Cursor cur;
   int s_ld = s_lo;
-  ThreadPtrs<true, true, 64, RB> tp;
+  ThreadPtrs<true, true, 64, 64> tp;
   auto issue_loads = [&](StageT& x) { x.load_ptrs(tp.pa, tp.pb, cur.k0, cur.K, cur.lda, cur.ldb, tid); };
   if (s_lo < s_hi) {
     cur.init(a, s_lo);
@@ -693,60 +688,37 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const KArgs a) {
   }
   __syncthreads();
 
-  auto compute = [&](int buf) {
-    const unsigned char* pa = lds + buf * STAGE_B + (wm * 32 + l31) * PL_ROW_B + half * 16;
-    const unsigned char* pb = lds + buf * STAGE_B + 3 * PLA + (wn * 32 * WN + l31) * PL_ROW_B + half * 16;
+  auto compute = [&]() {
+    const unsigned char* pa = lds + (wm * 32 + l31) * PL_ROW_B + half * 16;
+    const unsigned char* pb = lds + 3 * PL + (wn * 32 + l31) * PL_ROW_B + half * 16;
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
       bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pa + kk * 32));
-      bf16x8 am = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pa + PLA + kk * 32));
-      bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pa + 2 * PLA + kk * 32));
-#pragma unroll
-      for (int ni = 0; ni < WN; ++ni) {
-        const unsigned char* pbn = pb + ni * 32 * PL_ROW_B;
-        bf16x8 bh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pbn + kk * 32));
-        bf16x8 bm = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pbn + PLB + kk * 32));
-        bf16x8 bl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pbn + 2 * PLB + kk * 32));
-        // smallest partial products first
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc[ni], 0, 0, 0);
-        acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[ni], 0, 0, 0);
-      }
+      bf16x8 am = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pa + PL + kk * 32));
+      bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pa + 2 * PL + kk * 32));
+      bf16x8 bh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pb + kk * 32));
+      bf16x8 bm = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pb + PL + kk * 32));
+      bf16x8 bl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(pb + 2 * PL + kk * 32));
+      // smallest partial products first
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
     }
   };
 
-  constexpr int U = PF > 2 ? PF : 2;
-  // uniform sub-iterations (see gemm_kernel): only the MFMA work is skipped past the end of the k-range
-  for (int s = s_lo; s < s_hi; s += U) {
+  // uniform sub-iterations (see gemm_kernel): only the MFMA work is skipped past the end of the k-range; the store is
+  // unconditional (past the end it re-stores the clamped last tile, which nobody reads again)
+  for (int s = s_lo; s < s_hi; s += PF) {
 #pragma unroll
-    for (int j = 0; j < U; ++j) {
+    for (int j = 0; j < PF; ++j) {
       StageT& x = st[(j + 1) % PF];
-      const bool live = s + j < s_hi;
-      // One basic block: this step's MFMA chain and the NEXT tile's fp32 -> 3xbf16 split (VALU) + plane stores.  A wave
-      // issues in order and a dependent MFMA blocks everything behind it, so the split must sit BETWEEN the MFMAs to
-      // run in their shadow (sched_group_barrier below); the store is unconditional (past the end it re-stores the
-      // clamped last tile into the stage nobody reads again).
       x.template wait<(PF - 1) * NL>();
-      if constexpr (NBUF == 2) {
-        if (live) {
-          compute(j & 1);
-          put_planes(lds + ((j + 1) & 1) * STAGE_B, x);
-#pragma unroll
-          for (int q = 0; q < 12 * WN; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // 1 MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 7, 0);  // up to 7 VALU in its shadow
-          }
-        } else {
-          put_planes(lds + ((j + 1) & 1) * STAGE_B, x);
-        }
-      } else {
-        if (live) compute(0);
-        __syncthreads();  // every wave is done reading the single stage
-        put_planes(lds, x);
-      }
+      if (s + j < s_hi) compute();
+      __syncthreads();  // every wave is done reading the single stage
+      put_planes(lds, x);
       tp.step(a, cur, cur.advance(a, s_ld >= s_last), m0, n0, tid); s_ld = min(s_ld + 1, s_last);
       issue_loads(x);
       __syncthreads();
@@ -757,9 +729,11 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const KArgs a) {
   for (int j = 0; j < PF; ++j) st[j].template wait<0>();
 
   float* out = a.out + (size_t)z * a.slab_stride;
+  // (one 32-column tile per wave, written as a loop: hipcc then schedules the column arithmetic ahead of the k-loop's last
+  // barrier; the loop-free form costs 12 more instructions)
 #pragma unroll
-  for (int ni = 0; ni < WN; ++ni) {
-    const int col = n0 + (wn * WN + ni) * 32 + l31;
+  for (int ni = 0; ni < 1; ++ni) {
+    const int col = n0 + (wn + ni) * 32 + l31;
     if (col >= a.N) continue;
     const float bv = (a.bias != nullptr) ? a.bias[col] : 0.f;
     const int rbase = m0 + wm * 32 + 4 * half;
@@ -774,7 +748,7 @@ __global__ __launch_bounds__(256) void gemm_x3_kernel(const KArgs a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int row = rbase + (r & 3) + 8 * (r >> 2);
-      if (row < a.M) out[(size_t)row * a.ldo + col] = acc[ni][r] + bv + old[r];
+      if (row < a.M) out[(size_t)row * a.ldo + col] = acc[r] + bv + old[r];
     }
   }
 }
@@ -1136,8 +1110,8 @@ template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW, bool F
 __device__ __forceinline__ void x3w_body(const KArgs& a, const int blk_x, const int blk_y, const int blk_z, const int grid_x,
                                          const int grid_y, const int grid_z) {
   static_assert((TM == 128 && TN == 128) || (TM == 64 && TN == 256), "unsupported tile");
-  static_assert(PF >= 1 && PF <= 3, "prefetch depth");
-  constexpr int UNR = (PF == 3) ? 6 : 2;         // lcm(LDS stages, register sets)
+  static_assert(PF == 1 || PF == 2, "prefetch depth");
+  constexpr int UNR = 2;                         // lcm(LDS stages, register sets)
   // Device-side row lists (mcount / arows / crows) exist for the 128x128 form only: the minibatch kernels are never launched
   // with them, and their mere presence costs the k-loop a compiler-visible gather load + `s_waitcnt vmcnt(0)` at every
   // K-segment change (base_ptrs), which drains the hand-staged prefetch too.
@@ -1718,7 +1692,7 @@ struct KGroup {
   int first[SSC_GROUP_MAX + 1];
   int gx[SSC_GROUP_MAX], gy[SSC_GROUP_MAX], gz[SSC_GROUP_MAX];
 };
-template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW = 4, bool F16 = false>
+template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW, bool F16 = false>
 __global__ __launch_bounds__(256 + 64 * NPW, (F16 && NPW == 4) ? 4 : 1) void gemm_x3w_kernel(const KGroup g) {
   const int w = blockIdx.x;
   int p = 0;
@@ -1842,8 +1816,7 @@ gemm_fn pick_layout(const ssc_gemm_desc* d) {
   return gemm_kernel<false, true, WM, WN, PF, VEC>;
 }
 
-// tile choice: 128x128 (2x2 MFMA tiles per wave) when both dimensions are large, else 64x64 with a deeper prefetch
-// SSC_GEMM_MODE: "x3" (default) = 3xBF16 split kernel for NT products with 16 B/lane operands, "f32" = exact fp32 MFMA
+// Numerics.  SSC_GEMM_MODE: "x3" (default) = 3xBF16 split kernels, "f32" = exact fp32 MFMA
 int g_gemm_mode = -1;  // -1: take the default from the environment on first use
 }
 // A sequence-level call (ssc_train_fwd / _bwd, ssc_decode_*) runs under the numerics mode of ITS ssc_model_cfg (gemm_mode field):
@@ -1859,7 +1832,14 @@ inline int gemm_mode() {
   }
   return g_gemm_mode;
 }
-inline bool use_x3(const ssc_gemm_desc* d, bool vec) { return gemm_mode() == 1 && d->a_kc && d->b_kc && vec; }
+int g_gemm_f16 = ssc_env_int("SSC_GEMM_F16", 0);   // process default of the 2xFP16 form when no sequence-level call's cfg is in force
+// The numerics of one call, resolved once: exact fp32 MFMA, 3xBF16, or 3xBF16 with the 2xFP16 form for the wave-specialised
+// 128x128 NT kernel.  From the calling thread's sequence-level scope, else the process defaults (ssc_set_gemm_mode, "gemm_f16").
+enum class Num { F32, X3, X3_F16 };
+inline Num numerics() {
+  if (gemm_mode() != 1) return Num::F32;
+  return (ssc_tls_gemm_f16 >= 0 ? ssc_tls_gemm_f16 : g_gemm_f16) ? Num::X3_F16 : Num::X3;
+}
 // Tuning / diagnostic switches (include/ssc_debug.h: ssc_debug_set / ssc_debug_get; environment defaults in parentheses).
 // They select between kernel forms that compute the same product; none is part of the product ABI.
 // Large products (M, N >= 512): 0 = 64x64 kernels, 3 = always the 4-wave 128x128 3xBF16 kernel, 2 = always its wave-specialised
@@ -1871,22 +1851,27 @@ inline bool use_x3(const ssc_gemm_desc* d, bool vec) { return gemm_mode() == 1 &
 // decode of the fault ran clean with it twice (before and after the rebuild).  `ssc_debug_set("large_form", 3)` / SSC_X3B=3
 // selects the 4-wave kernel everywhere.
 int g_x3b = ssc_env_int("SSC_X3B", 1);
-int g_x3_nbuf = 1;  // single LDS stage: 31 KB per workgroup -> four resident workgroups per CU (rocprof r01: 37 vs 43 us)
-int g_x3_wide = 0;
-int g_x3_pf = 2;  // tuning hook: 1 = 64x128 block tile for skinny (M <= 64, N >= 1024) 3xBF16 products
-inline bool x3_wide(int M, int N) { return g_x3_wide && M <= 64 && N >= 1024; }
+int g_x3w_skinny = ssc_env_int("SSC_X3W_SKINNY", 1);  // 0 off, 1 NT and NN, 2 NN only
+// producer waves of the 2xFP16 kernel: 4 (default: two 8-wave workgroups per CU - 80 KB of LDS each - so that one's pipeline fill
+// and epilogue run under the other's k-loop: 10000 x 4800 x 2400 843 -> 750 us, same box) | 8 (one 12-wave workgroup per CU)
+int g_f16_npw = ssc_env_int("SSC_F16_NPW", 4);
 // 128x128 tiles from 65 rows on: a minibatch of 65-511 rows (C5: B = 128 per GPU) is MFMA-bound in 3xBF16, not HBM-bound - the
 // 64-wide kernels streamed the weights once per 64 rows (B = 128: 16.2 -> 14.3 ms per train step, B = 256: 27.0 -> 22.9 ms with
 // the wave-specialised 128x128 form, same box; 65-127 rows: one padded tile row still beats two 64-row passes, B = 96: 14.6 ->
-// 12.5 ms).  "big_min_m" (SSC_BIG_MIN_M) = 512 restores the earlier behaviour.
-int g_big_min_m = ssc_env_int("SSC_BIG_MIN_M", 65);
-inline bool big_tile(int M, int N) { return M >= g_big_min_m && N >= 512; }
+// 12.5 ms).
+constexpr int BIG_MIN_M = 65;
+inline bool big_tile(int M, int N) { return M >= BIG_MIN_M && N >= 512; }
 // M <= 64 with a wide N: 64x128 block tile (wave tile 32x64).  Every workgroup re-reads the whole A operand
 // (the minibatch activations, from L2) for its K-range, and the CU-side load path (~24 GB/s per CU) is what these
 // products run into first (rocprof r01: loads per CU saturate with A+B at BN=64), so halving the A re-reads per
 // streamed weight byte matters more than occupancy.
-int g_wide_min_n = 1024;
-inline bool wide_tile(int M, int N) { return M <= 64 && N >= g_wide_min_n; }
+constexpr int WIDE_MIN_N = 1024;
+inline bool wide_tile(int M, int N) { return M <= 64 && N >= WIDE_MIN_N; }
+// minibatch products on the wave-specialised 64x256 kernel from this width on: narrower ones do not fill the chip with
+// 256-column tiles (rocprof: slower than the 64-wide kernels)
+constexpr int X3W_MIN_N = 1024;
+inline bool x3w_skinny_shape(int M, int N, Num num) { return g_x3w_skinny && num != Num::F32 && M <= 64 && N >= X3W_MIN_N; }
+inline bool x3w_skinny_layout(const ssc_gemm_desc* d) { return g_x3w_skinny && d->a_kc && (g_x3w_skinny == 1 || !d->b_kc); }
 
 typedef void (*group_fn)(const KGroup);
 #ifdef SSC_X3W_AUDIT
@@ -1963,6 +1948,27 @@ inline void group_of_one(KGroup& g, const KArgs& k, dim3 grid) {
   }
 }
 
+// The wave-specialised kernels the launchers may run, each with its workgroup size (4 consumer waves + NPW producer waves) and
+// dynamic LDS.  x3w_prepare() raises the LDS limit of exactly these, so no form is launched without it.
+struct X3wForm { group_fn fn; int threads, lds; const char* what; };
+template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW, bool F16 = false>
+constexpr X3wForm x3w_form(const char* what) {
+  return {gemm_x3w_kernel<A_KC, B_KC, KG, TM, TN, PF, NPW, F16>, 256 + 64 * NPW, F16 ? x3w_lds_bytes_f16<TM, TN>() : x3w_lds_bytes<TM, TN>(), what};
+}
+enum { X3W_NT, X3W_NN, X3W_TN, X3W_TN_KG, X3W_NT_F16_4, X3W_NT_F16_8, X3W_SKINNY_NT, X3W_SKINNY_NN, X3W_FORMS };
+const X3wForm g_x3w[X3W_FORMS] = {
+    x3w_form<true, true, false, 128, 128, 2, 8>("128x128"), x3w_form<true, false, false, 128, 128, 2, 8>("128x128"),
+    x3w_form<false, false, false, 128, 128, 2, 8>("128x128"), x3w_form<false, false, true, 128, 128, 1, 8>("128x128"),
+    // 2xFP16: two planes per operand = 80 KB per workgroup; with 4 producer waves (8 waves per workgroup) TWO workgroups share a
+    // CU, so one's pipeline fill / epilogue runs under the other's k-loop (g_f16_npw = 4)
+    x3w_form<true, true, false, 128, 128, 2, 4, true>("128x128 f16"), x3w_form<true, true, false, 128, 128, 2, 8, true>("128x128 f16"),
+    x3w_form<true, true, false, 64, 256, 2, 8>("64x256"), x3w_form<true, false, false, 64, 256, 2, 8>("64x256"),
+};
+inline const X3wForm& x3w_big(bool a_kc, bool b_kc, bool kg) {   // layouts NT, NN, TN (+ k-row gather lists)
+  return g_x3w[(a_kc && b_kc) ? X3W_NT : a_kc ? X3W_NN : kg ? X3W_TN_KG : X3W_TN];
+}
+inline const X3wForm& x3w_skinny_form(bool b_kc) { return g_x3w[b_kc ? X3W_SKINNY_NT : X3W_SKINNY_NN]; }
+
 // the wave-specialised kernels need more than the default 64 KB of LDS per workgroup: raise the limit once
 int x3w_prepare() {
   // per DEVICE: the attribute belongs to the function's code object on the device it is set under - a process that drives two GPUs
@@ -1972,59 +1978,10 @@ int x3w_prepare() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return SSC_EHIP;
   bool& done = done_dev[dev];
   if (done) return SSC_OK;
-  group_fn big[8] = {gemm_x3w_kernel<true, true, false, 128, 128, 2>, gemm_x3w_kernel<true, false, false, 128, 128, 2>,
-                     gemm_x3w_kernel<false, false, true, 128, 128, 1>, gemm_x3w_kernel<false, false, false, 128, 128, 2>,
-                     gemm_x3w_kernel<true, true, false, 128, 128, 2, 8>, gemm_x3w_kernel<true, false, false, 128, 128, 2, 8>,
-                     gemm_x3w_kernel<false, false, true, 128, 128, 1, 8>, gemm_x3w_kernel<false, false, false, 128, 128, 2, 8>};
-  for (group_fn f : big)
-    if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, x3w_lds_bytes<128, 128>()) != hipSuccess) return SSC_EHIP;
-  if (hipFuncSetAttribute((const void*)gemm_x3w_kernel<true, true, false, 128, 128, 2, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          x3w_lds_bytes_f16<128, 128>()) != hipSuccess)
-    return SSC_EHIP;
-  if (hipFuncSetAttribute((const void*)gemm_x3w_kernel<true, true, false, 128, 128, 2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                          x3w_lds_bytes_f16<128, 128>()) != hipSuccess)
-    return SSC_EHIP;
-  group_fn skinny[6] = {gemm_x3w_kernel<true, true, false, 64, 256, 2>, gemm_x3w_kernel<true, false, false, 64, 256, 2>,
-                        gemm_x3w_kernel<true, true, false, 64, 256, 3>, gemm_x3w_kernel<true, false, false, 64, 256, 3>,
-                        gemm_x3w_kernel<true, true, false, 64, 256, 2, 8>, gemm_x3w_kernel<true, false, false, 64, 256, 2, 8>};
-  for (group_fn f : skinny)
-    if (hipFuncSetAttribute((const void*)f, hipFuncAttributeMaxDynamicSharedMemorySize, x3w_lds_bytes<64, 256>()) != hipSuccess) return SSC_EHIP;
+  for (const X3wForm& f : g_x3w)
+    if (hipFuncSetAttribute((const void*)f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, f.lds) != hipSuccess) return SSC_EHIP;
   done = true;
   return SSC_OK;
-}
-int g_f16_npw = ssc_env_int("SSC_F16_NPW", 4);   // producer waves of the 2xFP16 kernel: 4 (default: two 8-wave workgroups per CU - 80 KB of LDS each - so that one's pipeline fill and epilogue run under the other's k-loop: 10000 x 4800 x 2400 843 -> 750 us, same box) | 8 (one 12-wave workgroup per CU)
-int g_gemm_f16 = ssc_env_int("SSC_GEMM_F16", 0);   // process default of the 2xFP16 form when no sequence-level call's cfg is in force
-int g_x3w_skinny = ssc_env_int("SSC_X3W_SKINNY", 1);  // 0 off, 1 NT and NN, 2 NN only (hook -11 / -12 / -13)
-int g_x3w_min_n = ssc_env_int("SSC_X3W_MIN_N", 1024);   // narrower products do not fill the chip with 256-column tiles (rocprof: slower than the 64-wide kernels)
-int g_gemm_group = ssc_env_int("SSC_GEMM_GROUP", 1);   // grouped launches of independent minibatch products
-int g_dw_group = ssc_env_int("SSC_DW_GROUP", 1);       // grouped launches of the weight-gradient products (wave-specialised 128x128 form); 0 = one 4-wave launch per product
-// k-steps of operand tiles in flight in the producers' registers of the 64x256 kernels: 2 (default) | 3.  Three (120 staged
-// VGPRs, loop unrolled 6x) measured 2-6 % SLOWER on every gate product (40.5 -> 42.8 us at 64 x 4800 x 5648; train step 9.22 ->
-// 9.45 ms): the k-loop is not short of bytes in flight.
-int g_x3w_pf = ssc_env_int("SSC_X3W_PF", 2);
-int g_x3w_npw = ssc_env_int("SSC_X3W_NPW", 8);   // producer waves of the 64x256 kernels (4 | 8)
-int g_x3w_big_npw = ssc_env_int("SSC_X3W_BIG_NPW", 8);   // producer waves of the wave-specialised 128x128 kernels (4 | 8)
-inline int x3w_big_threads() { return g_x3w_big_npw == 8 ? 768 : 512; }
-inline group_fn x3w_big_fn(bool a_kc, bool b_kc, bool kg) {   // layouts NT, NN, TN (+ k-row gather lists)
-  if (g_x3w_big_npw == 8)
-    return (a_kc && b_kc) ? gemm_x3w_kernel<true, true, false, 128, 128, 2, 8>
-           : a_kc         ? gemm_x3w_kernel<true, false, false, 128, 128, 2, 8>
-           : kg           ? gemm_x3w_kernel<false, false, true, 128, 128, 1, 8>
-                          : gemm_x3w_kernel<false, false, false, 128, 128, 2, 8>;
-  return (a_kc && b_kc) ? gemm_x3w_kernel<true, true, false, 128, 128, 2>
-         : a_kc         ? gemm_x3w_kernel<true, false, false, 128, 128, 2>
-         : kg           ? gemm_x3w_kernel<false, false, true, 128, 128, 1>
-                        : gemm_x3w_kernel<false, false, false, 128, 128, 2>;
-}
-inline int x3w_skinny_threads() { return g_x3w_npw == 8 && g_x3w_pf != 3 ? 768 : 512; }
-inline group_fn x3w_skinny_fn(bool b_kc) {
-  if (x3w_skinny_threads() == 768) return b_kc ? gemm_x3w_kernel<true, true, false, 64, 256, 2, 8> : gemm_x3w_kernel<true, false, false, 64, 256, 2, 8>;
-  if (g_x3w_pf == 3) return b_kc ? gemm_x3w_kernel<true, true, false, 64, 256, 3> : gemm_x3w_kernel<true, false, false, 64, 256, 3>;
-  return b_kc ? gemm_x3w_kernel<true, true, false, 64, 256, 2> : gemm_x3w_kernel<true, false, false, 64, 256, 2>;
-}
-inline bool x3w_skinny_shape(int M, int N) { return g_x3w_skinny && gemm_mode() == 1 && M <= 64 && N >= g_x3w_min_n; }
-inline bool x3w_skinny(const ssc_gemm_desc* d, bool vec) {   // 2 = only where the weight matrix is [K][N] (backward dG W)
-  return vec && d->a_kc && x3w_skinny_shape(d->M, d->N) && (g_x3w_skinny == 1 || !d->b_kc);
 }
 
 // the wave-specialised kernels address an operand as (uniform 64-bit base) + (32-bit byte offset per lane)
@@ -2045,64 +2002,50 @@ inline bool x3w_span_ok(const ssc_gemm_desc* d) {
   }
   return true;
 }
-inline bool x3w_group_member(const ssc_gemm_desc* d, bool vec) {
-  return vec && d->a_kc && g_x3w_skinny && gemm_mode() == 1 && d->M <= 64 && d->N >= 64 && (g_x3w_skinny == 1 || !d->b_kc) &&
-         x3w_span_ok(d);
+inline bool vec_all(const KArgs& k) {   // every segment of both operands allows 16 B/lane loads
+  for (int i = 0; i < k.nseg; ++i)
+    if (!k.seg[i].avec || !k.seg[i].bvec) return false;
+  return true;
+}
+// may run on the wave-specialised kernel: 3xBF16 numerics, 16-byte operands, a layout it has (NT, NN, TN) and operand spans its
+// 32-bit offsets reach
+inline bool x3w_ok(const ssc_gemm_desc* d, const KArgs& k, Num num) {
+  return num != Num::F32 && vec_all(k) && (d->a_kc || !d->b_kc) && x3w_span_ok(d);
 }
 
-int launch(const ssc_gemm_desc* d, KArgs& k, int splits, hipStream_t st) {
-  k.steps_per_split = ssc_cdiv(k.steps_total, splits);
-  bool vec = true;  // every segment of both operands must allow 16 B/lane loads, else the 4 B/lane kernel runs
-  for (int i = 0; i < k.nseg; ++i) vec = vec && k.seg[i].avec && k.seg[i].bvec;
-  const bool compact = k.mcount || k.arows || k.crows || k.kcount || k.karows || k.kbrows;
-  if (compact) {  // device-side row compaction: gemm_x3b_kernel only
+// The kernel form of one product: a 4-wave kernel on one KArgs (256 threads, static LDS only) or a wave-specialised kernel on a
+// KGroup of one.
+struct Form {
+  gemm_fn fn = nullptr;
+  const X3wForm* x3w = nullptr;
+  dim3 grid;   // tiles along N, tiles along M, splits
+};
+// Decides the form of a product (pure: no HIP call, no global written), or refuses it with SSC_EINVAL / SSC_EALIGN.
+int plan(const ssc_gemm_desc* d, const KArgs& k, int splits, Num num, Form& f) {
+  const bool x3 = num != Num::F32, vec = vec_all(k);
+  const bool mlist = k.mcount || k.arows || k.crows, klist = k.kcount || k.karows || k.kbrows;
+  const bool compact = mlist || klist;
+  // records instead of C exist in the wave-specialised 128x128 NT form only: never fall through to a form that would store C
+  if (k.topk && !(x3 && vec && d->a_kc && d->b_kc && splits == 1 && !klist && x3w_span_ok(d))) return SSC_EINVAL;
+  if (compact) {   // device-side row compaction: the 128x128 3xBF16 kernels only
     if (!vec) return SSC_EALIGN;
-    if (gemm_mode() != 1 || (!d->a_kc && d->b_kc)) return SSC_EINVAL;
-    if ((k.kcount || k.karows || k.kbrows) && (k.nseg != 1 || d->a_kc || d->b_kc)) return SSC_EINVAL;
-    if ((k.mcount || k.arows || k.crows) && !d->a_kc) return SSC_EINVAL;
+    if (!x3 || (!d->a_kc && d->b_kc)) return SSC_EINVAL;
+    if (klist && (k.nseg != 1 || d->a_kc || d->b_kc)) return SSC_EINVAL;
+    if (mlist && !d->a_kc) return SSC_EINVAL;
   }
-  if (k.topk && !(gemm_mode() == 1 && vec && d->a_kc && d->b_kc && splits == 1 && x3w_span_ok(d) && !k.kcount && !k.karows && !k.kbrows))
-    return SSC_EINVAL;   // records instead of C exist in the wave-specialised 128x128 NT form only: never fall through to a form that would store C
-  if (x3w_skinny(d, vec) && !compact && !k.topk && x3w_span_ok(d)) {  // M = minibatch against a wide weight matrix: 64 x 256 wave-specialised tile
-    dim3 grid(ssc_cdiv(d->N, 256), ssc_cdiv(d->M, 64), splits);
-    ProfRec* rec = nullptr;
-    if (g_prof_on && g_prof && g_prof_n < PROF_MAX) {
-      rec = &g_prof[g_prof_n++];
-      rec->bytes = rec->flops = 0.0; rec->nmem = 0;
-      rec->kind = (d->a_kc ? 0 : 2) + (d->b_kc ? 0 : 1);
-      rec->M = d->M; rec->N = d->N; rec->splits = splits; rec->K = 0;
-      for (int i = 0; i < d->nseg; ++i) rec->K += d->seg[i].K;
-      prof_desc(rec, d, st);
-      (void)hipEventRecord(rec->e0, st);
-    }
-    SSC_TRY(x3w_prepare());
-    KGroup g1;
-    group_of_one(g1, k, grid);
-    SSC_AUDIT_BEGIN();
-    SSC_LAUNCH(x3w_skinny_fn(d->b_kc), dim3(g1.first[1]), dim3(x3w_skinny_threads()), (x3w_lds_bytes<64, 256>()), st, g1);
-    SSC_AUDIT_END(g1, true, d->b_kc != 0, "64x256", st);
-    if (rec) (void)hipEventRecord(rec->e1, st);
-    SSC_CHECK_LAUNCH();
+  // M = minibatch against a wide weight matrix: 64 x 256 wave-specialised tile
+  if (!compact && !k.topk && x3w_skinny_layout(d) && x3w_skinny_shape(d->M, d->N, num) && x3w_ok(d, k, num)) {
+    f.x3w = &x3w_skinny_form(d->b_kc);
+    f.grid = dim3(ssc_cdiv(d->N, 256), ssc_cdiv(d->M, 64), splits);
     return SSC_OK;
   }
-  if (gemm_mode() == 1 && vec && !(!d->a_kc && d->b_kc) && (compact || k.topk || (g_x3b && big_tile(d->M, d->N)))) {
-    dim3 grid(ssc_cdiv(d->N, 128), ssc_cdiv(d->M, 128), splits);
-    ProfRec* rec = nullptr;
-    if (g_prof_on && g_prof && g_prof_n < PROF_MAX) {
-      rec = &g_prof[g_prof_n++];
-      rec->bytes = rec->flops = 0.0; rec->nmem = 0;
-      rec->kind = (d->a_kc ? 0 : 2) + (d->b_kc ? 0 : 1);
-      rec->M = d->M; rec->N = d->N; rec->splits = splits; rec->K = 0;
-      for (int i = 0; i < d->nseg; ++i) rec->K += d->seg[i].K;
-      prof_desc(rec, d, st);
-      (void)hipEventRecord(rec->e0, st);
-    }
+  if (x3 && vec && (d->a_kc || !d->b_kc) && (compact || k.topk || (g_x3b && big_tile(d->M, d->N)))) {
+    f.grid = dim3(ssc_cdiv(d->N, 128), ssc_cdiv(d->M, 128), splits);
     const bool kg = k.karows || k.kbrows;
-    const bool kg_both = k.karows && k.kbrows;   // the wave-specialised gather kernel reads both lists unconditionally
     // Form: the 4-wave kernel keeps two workgroups per CU, which evens out small grids (380 tiles on 256 CUs); the
     // wave-specialised one runs ~13 % fewer cycles per k-step and wins once the grid is several rounds deep (decode:
     // 1520 tiles, +10 % tokens/s).  g_x3b: 1 = choose by grid size, 2 = always wave-specialised, 3 = always 4-wave.
-    const long wgs = (long)grid.x * grid.y * grid.z;
+    const long wgs = (long)f.grid.x * f.grid.y * f.grid.z;
     // (below 512 rows - one to four tile rows, split-K - the wave-specialised form wins at every grid size: 59 vs 71 us at 128 x 4800 x 5648)
     // (2xFP16 numerics requested and applicable: the wave-specialised form at every grid size - its F16 variant is 1.5x the 3xBF16
     // one, which outweighs what the 4-wave kernel gains on grids below three rounds)
@@ -2110,71 +2053,75 @@ int launch(const ssc_gemm_desc* d, KArgs& k, int splits, hipStream_t st) {
     // weight gradients 4800 x 5448 x 1344 with k-row lists 355 -> 266 us, vocabulary-head input gradient 328 -> 267 us, error against
     // float64 6-8e-7 of sum|a||b| with measured scales, as good as 3xBF16 - but 1.23-1.33x on 20 % of a step, minus the per-step
     // absmax passes over the gradient operands, is ~3 % of the train step: not taken, the training numerics stay 3xBF16.)
-    const bool f16 = (ssc_tls_gemm_f16 >= 0 ? ssc_tls_gemm_f16 : g_gemm_f16) && d->a_kc && d->b_kc && !kg && g_x3w_big_npw == 8 && g_x3b != 3;
-    if (k.topk && !(d->a_kc && d->b_kc && !kg && splits == 1 && x3w_span_ok(d))) return SSC_EINVAL;   // the records exist in this form's epilogue only
-    if ((k.topk || g_x3b == 2 || (g_x3b == 1 && (f16 || wgs >= 768 || (d->M < 512 && big_tile(d->M, d->N))))) && x3w_span_ok(d) && (!kg || kg_both)) {  // wave-specialised form: 12 waves, 120 KB of dynamic LDS
-      group_fn fn = x3w_big_fn(d->a_kc, d->b_kc, kg);
-      // 2xFP16: two planes per operand = 80 KB per workgroup; with 4 producer waves (8 waves per workgroup) TWO workgroups share a
-      // CU, so one's pipeline fill / epilogue runs under the other's k-loop (g_f16_npw = 4)
-      if (f16) fn = g_f16_npw == 4 ? gemm_x3w_kernel<true, true, false, 128, 128, 2, 4, true> : gemm_x3w_kernel<true, true, false, 128, 128, 2, 8, true>;
-      SSC_TRY(x3w_prepare());
-      KGroup g1;
-      group_of_one(g1, k, grid);
-      SSC_AUDIT_BEGIN();
-      if (f16) SSC_LAUNCH(fn, dim3(g1.first[1]), dim3(g_f16_npw == 4 ? 512 : 768), (x3w_lds_bytes_f16<128, 128>()), st, g1);
-      else SSC_LAUNCH(fn, dim3(g1.first[1]), dim3(x3w_big_threads()), (x3w_lds_bytes<128, 128>()), st, g1);
-      SSC_AUDIT_END(g1, d->a_kc != 0, d->b_kc != 0, "128x128", st);
-    } else
-    if (d->a_kc && d->b_kc) SSC_LAUNCH((gemm_x3b_kernel<true, true, false>), grid, dim3(256), 0, st, k);
-    else if (d->a_kc) SSC_LAUNCH((gemm_x3b_kernel<true, false, false>), grid, dim3(256), 0, st, k);
-    else if (kg) SSC_LAUNCH((gemm_x3b_kernel<false, false, true>), grid, dim3(256), 0, st, k);
-    else SSC_LAUNCH((gemm_x3b_kernel<false, false, false>), grid, dim3(256), 0, st, k);
-    if (rec) (void)hipEventRecord(rec->e1, st);
-    SSC_CHECK_LAUNCH();
-    return SSC_OK;
-  }
-  if (use_x3(d, vec)) {
-    const bool wide = x3_wide(d->M, d->N);
-    dim3 grid(ssc_cdiv(d->N, wide ? 128 : 64), ssc_cdiv(d->M, 64), splits);
-    ProfRec* rec = nullptr;
-    if (g_prof_on && g_prof && g_prof_n < PROF_MAX) {
-      rec = &g_prof[g_prof_n++];
-      rec->bytes = rec->flops = 0.0; rec->nmem = 0;
-      rec->kind = 0; rec->M = d->M; rec->N = d->N; rec->splits = splits; rec->K = 0;
-      for (int i = 0; i < d->nseg; ++i) rec->K += d->seg[i].K;
-      prof_desc(rec, d, st);
-      (void)hipEventRecord(rec->e0, st);
+    const bool f16 = num == Num::X3_F16 && d->a_kc && d->b_kc && !kg && g_x3b != 3;
+    const bool x3w = k.topk || g_x3b == 2 || (g_x3b == 1 && (f16 || wgs >= 768 || (d->M < 512 && big_tile(d->M, d->N))));
+    // (the wave-specialised gather kernel reads both k-row lists unconditionally)
+    if (x3w && x3w_span_ok(d) && (!kg || (k.karows && k.kbrows))) {
+      f.x3w = f16 ? &g_x3w[g_f16_npw == 4 ? X3W_NT_F16_4 : X3W_NT_F16_8] : &x3w_big(d->a_kc, d->b_kc, kg);
+      return SSC_OK;
     }
-    if (wide && g_x3_nbuf == 1) SSC_LAUNCH((gemm_x3_kernel<2, 2, 1>), grid, dim3(256), 0, st, k);
-    else if (wide) SSC_LAUNCH((gemm_x3_kernel<2, 2, 2>), grid, dim3(256), 0, st, k);
-    else if (g_x3_nbuf == 1 && g_x3_pf == 4) SSC_LAUNCH((gemm_x3_kernel<4, 1, 1>), grid, dim3(256), 0, st, k);
-    else if (g_x3_nbuf == 1 && g_x3_pf == 1) SSC_LAUNCH((gemm_x3_kernel<1, 1, 1>), grid, dim3(256), 0, st, k);
-    else if (g_x3_nbuf == 1) SSC_LAUNCH((gemm_x3_kernel<2, 1, 1>), grid, dim3(256), 0, st, k);
-    else SSC_LAUNCH((gemm_x3_kernel<2, 1, 2>), grid, dim3(256), 0, st, k);
-    if (rec) (void)hipEventRecord(rec->e1, st);
-    SSC_CHECK_LAUNCH();
+    f.fn = (d->a_kc && d->b_kc) ? gemm_x3b_kernel<true, true, false>
+           : d->a_kc            ? gemm_x3b_kernel<true, false, false>
+           : kg                 ? gemm_x3b_kernel<false, false, true>
+                                : gemm_x3b_kernel<false, false, false>;
     return SSC_OK;
   }
+  if (x3 && vec && d->a_kc && d->b_kc) {
+    f.fn = gemm_x3_kernel;
+    f.grid = dim3(ssc_cdiv(d->N, 64), ssc_cdiv(d->M, 64), splits);
+    return SSC_OK;
+  }
+  // exact fp32 - tile choice: 128x128 (2x2 MFMA tiles per wave) when both dimensions are large, else 64x64 with a deeper prefetch
   const bool big = big_tile(d->M, d->N);
   const bool wide = !big && vec && wide_tile(d->M, d->N);
-  const int bm = big ? 128 : 64, bn = (big || wide) ? 128 : 64;
-  dim3 grid(ssc_cdiv(d->N, bn), ssc_cdiv(d->M, bm), splits);
-  gemm_fn fn = big ? (vec ? pick_layout<2, 2, 1, true>(d) : pick_layout<2, 2, 1, false>(d))
-                   : wide ? pick_layout<1, 2, 2, true>(d)
-                          : (vec ? pick_layout<1, 1, 4, true>(d) : pick_layout<1, 1, 2, false>(d));
-  ProfRec* rec = nullptr;
-  if (g_prof_on && g_prof && g_prof_n < PROF_MAX) {
-    rec = &g_prof[g_prof_n++];
-      rec->bytes = rec->flops = 0.0; rec->nmem = 0;
-    rec->kind = (d->a_kc ? 0 : 2) + (d->b_kc ? 0 : 1);  // 0 NT, 1 NN, 3 TN
-    rec->M = d->M; rec->N = d->N; rec->splits = splits;
-    rec->K = 0;
-    for (int i = 0; i < d->nseg; ++i) rec->K += d->seg[i].K;
-      prof_desc(rec, d, st);
-    (void)hipEventRecord(rec->e0, st);
-  }
-  SSC_LAUNCH(fn, grid, dim3(256), 0, st, k);
+  f.grid = dim3(ssc_cdiv(d->N, (big || wide) ? 128 : 64), ssc_cdiv(d->M, big ? 128 : 64), splits);
+  f.fn = big ? (vec ? pick_layout<2, 2, 1, true>(d) : pick_layout<2, 2, 1, false>(d))
+             : wide ? pick_layout<1, 2, 2, true>(d)
+                    : (vec ? pick_layout<1, 1, 4, true>(d) : pick_layout<1, 1, 2, false>(d));
+  return SSC_OK;
+}
+
+// Opens the profiling record of one launch (nullptr while profiling is off).  kind 0 NT, 1 NN, 3 TN; a grouped launch adds its
+// members one by one and reports a nominal M, N and K.
+ProfRec* prof_open(const ssc_gemm_desc* const* d, int n, int M, int N, int K, int splits, hipStream_t st) {
+  if (!g_prof_on || !g_prof || g_prof_n >= PROF_MAX) return nullptr;
+  ProfRec* rec = &g_prof[g_prof_n++];
+  rec->bytes = rec->flops = 0.0; rec->nmem = 0;
+  rec->kind = (d[0]->a_kc ? 0 : 2) + (d[0]->b_kc ? 0 : 1);
+  rec->M = M; rec->N = N; rec->K = K; rec->splits = splits;
+  for (int i = 0; i < n; ++i) prof_desc(rec, d[i], st);
+  (void)hipEventRecord(rec->e0, st);
+  return rec;
+}
+inline void prof_close(ProfRec* rec, hipStream_t st) {
   if (rec) (void)hipEventRecord(rec->e1, st);
+}
+
+// The launch sequence of every wave-specialised launch (a single product is a group of one).
+int launch_x3w(const X3wForm& f, const KGroup& g, bool a_kc, bool b_kc, const char* what, ProfRec* rec, hipStream_t st) {
+  SSC_TRY(x3w_prepare());
+  SSC_AUDIT_BEGIN();
+  SSC_LAUNCH(f.fn, dim3(g.first[g.n]), dim3(f.threads), f.lds, st, g);
+  SSC_AUDIT_END(g, a_kc, b_kc, what, st);
+  prof_close(rec, st);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+int launch(const ssc_gemm_desc* d, KArgs& k, int splits, hipStream_t st) {
+  k.steps_per_split = ssc_cdiv(k.steps_total, splits);
+  Form f;
+  SSC_TRY(plan(d, k, splits, numerics(), f));
+  int K = 0;
+  for (int i = 0; i < d->nseg; ++i) K += d->seg[i].K;
+  ProfRec* rec = prof_open(&d, 1, d->M, d->N, K, splits, st);
+  if (f.x3w) {
+    KGroup g;
+    group_of_one(g, k, f.grid);
+    return launch_x3w(*f.x3w, g, d->a_kc != 0, d->b_kc != 0, f.x3w->what, rec, st);
+  }
+  SSC_LAUNCH(f.fn, f.grid, dim3(256), 0, st, k);
+  prof_close(rec, st);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }
@@ -2196,7 +2143,7 @@ int ssc_reduce_slabs(const float* slabs, int nslab, size_t stride, int M, int N,
 }
 
 extern "C" int ssc_gemm_auto_splits(int M, int N, int ksteps) {
-  if (x3w_skinny_shape(M, N)) {
+  if (x3w_skinny_shape(M, N, numerics())) {
     // one workgroup per CU: split K until the grid covers the chip once, at least 4 k-steps per workgroup
     const int tiles = ssc_cdiv(N, 256);
     int s = 256 / tiles;
@@ -2287,30 +2234,25 @@ int ssc_gemm_slabs_auto(const ssc_gemm_desc* d, float* slabs, size_t cap_floats,
 int ssc_gemm_slabs_group(const ssc_gemm_desc* const* d, int n, float* const* regions, const size_t* caps, int* nslab,
                          hipStream_t st) {
   if (!d || n < 1 || n > SSC_GROUP_MAX || !regions || !caps || !nslab) return SSC_EINVAL;
-  const bool group_on = g_gemm_group != 0;
+  const Num num = numerics();
   KGroup g;
-  bool ok = n >= 2 && group_on, any_wide = false;
+  bool ok = n >= 2, any_wide = false;
   long work = 0;
   // two classes of members: minibatches of up to 64 rows on the 64x256 kernels, and of 65-511 rows (MFMA-bound in 3xBF16: C5's
   // B = 128 per GPU) on the wave-specialised 128x128 kernels; a group is of one class
-  const bool mid = d[0] && d[0]->M > 64 && d[0]->M >= g_big_min_m;
+  const bool mid = d[0] && d[0]->M > 64 && d[0]->M >= BIG_MIN_M;
   const int tw = mid ? 128 : 256;
   for (int i = 0; i < n && ok; ++i) {
     SSC_TRY(build_args(d[i], g.a[i]));
-    KArgs& k = g.a[i];
-    bool vec = true;
-    for (int s = 0; s < k.nseg; ++s) vec = vec && k.seg[s].avec && k.seg[s].bvec;
+    const KArgs& k = g.a[i];
     const bool compact = k.mcount || k.arows || k.crows || k.kcount || k.karows || k.kbrows;
-    // a member needs the minibatch shape and 16 B/lane operands; a NARROW member (N < the 256-column kernels' minimum width,
-    // e.g. the 128-column dz product) may ride along in a group that has at least one wide member
-    if (mid) {
-      ok = !compact && vec && d[i]->a_kc && gemm_mode() == 1 && g_x3b != 0 && g_x3b != 3 && d[i]->M >= g_big_min_m && d[i]->M < 512 &&
-           d[i]->M == d[0]->M && d[i]->N >= 64 && x3w_span_ok(d[i]) && d[i]->b_kc == d[0]->b_kc && regions[i];
-      any_wide = any_wide || big_tile(d[i]->M, d[i]->N);
-    } else {
-      ok = !compact && x3w_group_member(d[i], vec) && d[i]->b_kc == d[0]->b_kc && regions[i];
-      any_wide = any_wide || x3w_skinny(d[i], vec);
-    }
+    // a member may run on the wave-specialised kernel and has the class's shape, the first member's layout and a region; a NARROW
+    // member (N < the 256-column kernels' minimum width, e.g. the 128-column dz product) may ride along in a group that has at
+    // least one wide member
+    const bool shape = mid ? g_x3b != 0 && g_x3b != 3 && d[i]->M >= BIG_MIN_M && d[i]->M < 512 && d[i]->M == d[0]->M
+                           : x3w_skinny_layout(d[i]) && d[i]->M <= 64;
+    ok = !compact && x3w_ok(d[i], k, num) && d[i]->a_kc && shape && d[i]->N >= 64 && d[i]->b_kc == d[0]->b_kc && regions[i];
+    any_wide = any_wide || (mid ? big_tile(d[i]->M, d[i]->N) : d[i]->N >= X3W_MIN_N);
     work += (long)ssc_cdiv(d[i]->N, tw) * ssc_cdiv(d[i]->M, mid ? 128 : 64) * k.steps_total;
   }
   ok = ok && any_wide;
@@ -2355,30 +2297,9 @@ int ssc_gemm_slabs_group(const ssc_gemm_desc* const* d, int n, float* const* reg
     if (d[i]->N > Nmax) Nmax = d[i]->N;
   }
   for (int i = n; i < SSC_GROUP_MAX; ++i) { g.first[i + 1] = g.first[n]; g.gx[i] = 1; g.gy[i] = 1; g.gz[i] = 1; }
-  SSC_TRY(x3w_prepare());
-  ProfRec* rec = nullptr;
-  if (g_prof_on && g_prof && g_prof_n < PROF_MAX) {  // one record for the group
-    rec = &g_prof[g_prof_n++];
-      rec->bytes = rec->flops = 0.0; rec->nmem = 0;
-    rec->kind = d[0]->b_kc ? 0 : 1;
-    rec->M = d[0]->M; rec->N = Nmax; rec->splits = nslab[0]; rec->K = Ksum;   // (N, K: nominal; bytes / flops are exact)
-    for (int i = 0; i < n; ++i) prof_desc(rec, d[i], st);
-    (void)hipEventRecord(rec->e0, st);
-  }
-  if (mid) {
-    SSC_AUDIT_BEGIN();
-    SSC_LAUNCH(x3w_big_fn(true, d[0]->b_kc != 0, false), dim3(g.first[n]), dim3(x3w_big_threads()), (x3w_lds_bytes<128, 128>()), st, g);
-    SSC_AUDIT_END(g, true, d[0]->b_kc != 0, "128x128 group", st);
-    if (rec) (void)hipEventRecord(rec->e1, st);
-    SSC_CHECK_LAUNCH();
-    return SSC_OK;
-  }
-  SSC_AUDIT_BEGIN();
-  SSC_LAUNCH(x3w_skinny_fn(d[0]->b_kc), dim3(g.first[n]), dim3(x3w_skinny_threads()), (x3w_lds_bytes<64, 256>()), st, g);
-  SSC_AUDIT_END(g, true, d[0]->b_kc != 0, "64x256 group", st);
-  if (rec) (void)hipEventRecord(rec->e1, st);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
+  ProfRec* rec = prof_open(d, n, d[0]->M, Nmax, Ksum, nslab[0], st);   // one record for the group (N, K: nominal; bytes / flops are exact)
+  if (mid) return launch_x3w(x3w_big(true, d[0]->b_kc != 0, false), g, true, d[0]->b_kc != 0, "128x128 group", rec, st);
+  return launch_x3w(x3w_skinny_form(d[0]->b_kc != 0), g, true, d[0]->b_kc != 0, "64x256 group", rec, st);
 }
 
 // n independent LARGE products C_i = A_i^T B_i (the weight gradients of one backward phase) with direct outputs: the
@@ -2387,24 +2308,23 @@ int ssc_gemm_slabs_group(const ssc_gemm_desc* const* d, int n, float* const* reg
 // workgroup per CU no longer loses to tile quantisation (380 tiles on 256 CUs) - the others one by one.
 int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, hipStream_t st) {
   if (!d || n < 1) return SSC_EINVAL;
-  const bool group_on = g_gemm_group != 0 && g_dw_group != 0;
+  const Num num = numerics();
   int i = 0;
   while (i < n) {
     KGroup g;
     int m = 0;
     bool kg0 = false;
     long Ksum = 0, MN = 0;
-    int j = i;
-    for (; j < n && m < SSC_GROUP_MAX; ++j) {
+    for (int j = i; j < n && m < SSC_GROUP_MAX; ++j) {
       const ssc_gemm_desc* dj = d[j];
       KArgs& k = g.a[m];
       SSC_TRY(build_args(dj, k));
       k.member = m;
-      const bool vec = k.nseg == 1 && k.seg[0].avec && k.seg[0].bvec;
       const bool kg = k.karows || k.kbrows;
-      const bool ok = group_on && gemm_mode() == 1 && vec && !dj->a_kc && !dj->b_kc && dj->C && dj->ldc >= dj->N && !k.mcount &&
-                      !k.arows && !k.crows && (kg ? (k.kcount && k.karows && k.kbrows) : !k.kcount) && (m == 0 || kg == kg0) &&
-                      x3w_span_ok(dj);
+      // a member may run on the wave-specialised kernel, is a single-segment TN product with a direct output, and has all three
+      // k-row lists exactly when the group's first member has them
+      const bool ok = x3w_ok(dj, k, num) && k.nseg == 1 && !dj->a_kc && !dj->b_kc && dj->C && dj->ldc >= dj->N && !k.mcount &&
+                      !k.arows && !k.crows && (kg ? (k.kcount && k.karows && k.kbrows) : !k.kcount) && (m == 0 || kg == kg0);
       if (!ok) break;
       kg0 = kg;
       k.steps_per_split = k.steps_total;
@@ -2419,21 +2339,8 @@ int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, hipStream_t st) {
       g.n = m;
       g.first[0] = 0;
       for (int q = m; q < SSC_GROUP_MAX; ++q) { g.first[q + 1] = g.first[m]; g.gx[q] = g.gy[q] = g.gz[q] = 1; }
-      SSC_TRY(x3w_prepare());
-      ProfRec* rec = nullptr;
-      if (g_prof_on && g_prof && g_prof_n < PROF_MAX) {  // one record: 2*K*sum(M_i N_i) flops
-        rec = &g_prof[g_prof_n++];
-      rec->bytes = rec->flops = 0.0; rec->nmem = 0;
-        rec->kind = 3;
-        rec->M = (int)(MN / d[i]->N); rec->N = d[i]->N; rec->splits = 1; rec->K = (int)Ksum;
-        for (int q = i; q < j; ++q) prof_desc(rec, d[q], st);
-        (void)hipEventRecord(rec->e0, st);
-      }
-      SSC_AUDIT_BEGIN();
-      SSC_LAUNCH(x3w_big_fn(false, false, kg0), dim3(g.first[m]), dim3(x3w_big_threads()), (x3w_lds_bytes<128, 128>()), st, g);
-      SSC_AUDIT_END(g, false, false, "128x128 TN group", st);
-      if (rec) (void)hipEventRecord(rec->e1, st);
-      SSC_CHECK_LAUNCH();
+      ProfRec* rec = prof_open(d + i, m, (int)(MN / d[i]->N), d[i]->N, (int)Ksum, 1, st);   // one record: 2*K*sum(M_i N_i) flops
+      SSC_TRY(launch_x3w(x3w_big(false, false, kg0), g, false, false, "128x128 TN group", rec, st));
       i += m;
     } else {  // a single eligible product gains nothing from the group form; ineligible ones take the usual path
       SSC_TRY(ssc_gemm(d[i], (void*)st));
@@ -2488,10 +2395,8 @@ extern "C" int ssc_gemm(const ssc_gemm_desc* d, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   KArgs k;
   SSC_TRY(build_args(d, k));
-  if (d->topk_part) {   // records instead of C: one pass, wave-specialised 128x128 NT form (launch() refuses anything else)
+  if (d->topk_part) {   // records instead of C: one pass, wave-specialised 128x128 NT form (plan() refuses anything else)
     k.out = nullptr; k.ldo = d->N; k.slab_stride = 0; k.bias = d->bias; k.accumulate = 0;
-    const bool vec_all = [&] { for (int i = 0; i < k.nseg; ++i) if (!k.seg[i].avec || !k.seg[i].bvec) return false; return true; }();
-    if (!vec_all || gemm_mode() != 1 || !d->a_kc || !d->b_kc) return SSC_EINVAL;
     return launch(d, k, 1, st);
   }
   if (!d->C || d->ldc < d->N) return SSC_EINVAL;
@@ -2586,18 +2491,8 @@ extern int ssc_g_img_mfma;   // pointwise.hip
 namespace {
 struct DebugKey { const char* name; int* var; };
 const DebugKey g_debug_keys[] = {
-    {"large_form", &g_x3b},          // large products (M, N >= 512): 0 = 64-wide kernels, 3 = 4-wave 128x128 3xBF16 kernel (default), 2 = its wave-specialised form, 1 = chosen by grid size   (SSC_X3B)
-    {"x3_wide", &g_x3_wide},         // 64x128 block tile for 3xBF16 products with M <= 64, N >= 1024 on the 4-wave kernel
-    {"x3_nbuf", &g_x3_nbuf},         // LDS stages of the 64-wide 3xBF16 kernel (1 | 2)
-    {"x3_pf", &g_x3_pf},             // register prefetch depth of the 64-wide 3xBF16 kernel (1 | 2 | 4)
+    {"large_form", &g_x3b},          // large products (M, N >= 512): 0 = 64-wide kernels, 1 = chosen by grid size (default), 2 = wave-specialised 128x128 form, 3 = 4-wave 128x128 3xBF16 kernel   (SSC_X3B)
     {"x3w_skinny", &g_x3w_skinny},   // minibatch products on the wave-specialised 64x256 kernel: 0 off, 1 NT and NN (default), 2 NN only   (SSC_X3W_SKINNY)
-    {"x3w_min_n", &g_x3w_min_n},     // ... from this output width on   (SSC_X3W_MIN_N)
-    {"wide_min_n", &g_wide_min_n},   // exact-fp32 kernels: 64x128 tile for M <= 64 from this width on
-    {"gemm_group", &g_gemm_group},   // grouped launches of independent minibatch products (0 | 1)   (SSC_GEMM_GROUP)
-    {"dw_group", &g_dw_group},       // grouped launches of the weight-gradient products (0 | 1)   (SSC_DW_GROUP)
-    {"x3w_big_npw", &g_x3w_big_npw}, // wave-specialised 128x128 kernels: producer waves (4 | 8)   (SSC_X3W_BIG_NPW)
-    {"x3w_npw", &g_x3w_npw},         // 64x256 kernels: producer waves per workgroup (4 | 8)   (SSC_X3W_NPW)
-    {"x3w_pf", &g_x3w_pf},           // 64x256 kernels: k-steps in flight in the producers' registers (2 | 3)   (SSC_X3W_PF)
     {"store_wt", &g_store_wt},       // wave-specialised kernels: write-through (sc1) output stores (0 | 1)   (SSC_STORE_WT)
     {"tile_gm", &g_tile_gm},         // tile rows per group of the tile order (8; 0 = row-major)   (SSC_TILE_GM)
     {"dec_dedup", &ssc_g_dec_dedup},           // decode: parent-state products on the distinct parents of a beam group (1 | 0)   (SSC_DEC_DEDUP)
@@ -2607,9 +2502,8 @@ const DebugKey g_debug_keys[] = {
     {"dec_planes", &ssc_g_dec_planes},         // decode: the 2xFP16 products of a large call read states and weights pre-split into fp16 pieces (1 | 0)   (SSC_DEC_PLANES)
     {"dec_parts", &ssc_g_dec_parts},           // decode: the vocabulary head of a one-state search leaves per-tile records instead of logits (1 | 0)   (SSC_DEC_PARTS)
     {"dec_att_table", &ssc_g_dec_att_table},   // decode: attended-feature term of the decoder gates from a per-image table (1 | 0)   (SSC_DEC_ATT_TABLE)
-    {"f16_npw", &g_f16_npw},         // 2xFP16 kernel: producer waves (8 | 4 = two workgroups per CU)   (SSC_F16_NPW)
-    {"gemm_f16", &g_gemm_f16},       // op-level products (ssc_gemm outside a sequence-level call): 1 = the wave-specialised 128x128 NT form takes the 2xFP16 split (what ssc_model_cfg.gemm_mode 3 selects per call)
-    {"big_min_m", &g_big_min_m},     // rows from which a product with N >= 512 takes 128x128 tiles (65; 512 = the behaviour until late in round 2)   (SSC_BIG_MIN_M)
+    {"f16_npw", &g_f16_npw},         // 2xFP16 kernel: producer waves (4 = two workgroups per CU (default) | 8)   (SSC_F16_NPW)
+    {"gemm_f16", &g_gemm_f16},       // op-level products (ssc_gemm outside a sequence-level call): 1 = the wave-specialised 128x128 NT form takes the 2xFP16 split (what ssc_model_cfg.gemm_mode 3 selects per call)   (SSC_GEMM_F16)
 };
 }  // namespace
 
@@ -2626,7 +2520,6 @@ extern "C" int ssc_debug_get(const char* key, int* value) {
   return SSC_EINVAL;
 }
 
-// diagnostic: resident workgroups per CU the runtime reports for the GEMM kernels (tools/, not used by the product path)
 #ifdef SSC_X3W_STAMP
 // diagnostics build only: device buffer of 256 u64 and the workgroup (flat blockIdx.x of the grouped launch) that fills it
 extern "C" int ssc_debug_stamp_setup(void* buf, int wg) {
@@ -2635,29 +2528,3 @@ extern "C" int ssc_debug_stamp_setup(void* buf, int wg) {
   return SSC_OK;
 }
 #endif
-
-extern "C" int ssc_debug_gemm_occupancy(int* out4) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_x3_kernel<2, 1, 2>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[0] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_x3_kernel<2, 1, 1>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[1] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_kernel<true, true, 1, 1, 4, true>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[2] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_kernel<true, false, 1, 2, 2, true>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[3] = n;
-  return SSC_OK;
-}
-
-extern "C" int ssc_debug_gemm_occupancy_x3b(int* out4) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_x3b_kernel<true, true, false>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[0] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_x3b_kernel<true, false, false>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[1] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_x3b_kernel<false, false, false>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[2] = n;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, gemm_x3b_kernel<false, false, true>, 256, 0) != hipSuccess) return SSC_EHIP;
-  out4[3] = n;
-  return SSC_OK;
-}

@@ -225,20 +225,6 @@ int flush_dw(const Ctx& c, DwBatch& q) {
     const bool al = ssc_aligned16(d.seg[0].A) && ssc_aligned16(d.seg[0].B) && !(d.seg[0].lda & 3) && !(d.seg[0].ldb & 3) && !(d.M & 3) && !(d.N & 3);
     if (!al) d.k_count = d.ka_rows = d.kb_rows = nullptr;
   }
-  int grouped = 1;
-  (void)ssc_debug_get("dw_group", &grouped);   // include/ssc_debug.h: 0 = one 4-wave launch per product (A/B switch)
-  if (!grouped) {
-    int rc1 = SSC_OK;
-    for (int i = 0; i < q.n && rc1 == SSC_OK; ++i) {
-      rc1 = ssc_gemm(&q.d[i], c.st);
-      if (rc1 == SSC_EINVAL || rc1 == SSC_EALIGN) {
-        q.d[i].k_count = q.d[i].ka_rows = q.d[i].kb_rows = nullptr;
-        rc1 = ssc_gemm(&q.d[i], c.st);
-      }
-    }
-    q.n = 0;
-    return rc1;
-  }
   int rc = ssc_gemm_dw_group(dp, q.n, c.st);
   if (rc == SSC_EINVAL || rc == SSC_EALIGN) {  // e.g. the exact-fp32 mode refuses compaction: whole sums instead
     for (int i = 0; i < q.n; ++i) q.d[i].k_count = q.d[i].ka_rows = q.d[i].kb_rows = nullptr;

@@ -228,8 +228,6 @@ DEBUG_SYMBOLS = {
     "ssc_prof_loop_ms": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ssc_debug_set": (_i, [C.c_char_p, _i]),
     "ssc_debug_get": (_i, [C.c_char_p, C.POINTER(C.c_int)]),
-    "ssc_debug_gemm_occupancy": (_i, [vp]),
-    "ssc_debug_gemm_occupancy_x3b": (_i, [vp]),
 }
 
 _lib = None

@@ -47,6 +47,13 @@ def test_debug_switches_by_name():
     lib.ssc_debug_set(b"large_form", prev)
     with pytest.raises(L.SscError, match="SSC_EINVAL"):
         lib.ssc_debug_set(b"no_such_switch", 1)
+    # switches of kernel forms that only ever measured slower were removed with those forms
+    for key in (b"x3_wide", b"x3_nbuf", b"x3_pf", b"x3w_pf", b"x3w_npw", b"x3w_big_npw", b"big_min_m", b"x3w_min_n",
+                b"wide_min_n", b"gemm_group", b"dw_group"):
+        with pytest.raises(L.SscError, match="SSC_EINVAL"):
+            lib.ssc_debug_set(key, 1)
+        with pytest.raises(L.SscError, match="SSC_EINVAL"):
+            lib.ssc_debug_get(key, C.byref(v))
 
 
 def test_struct_layouts_match_header_field_order():

@@ -1,5 +1,7 @@
 """GPU: exact-fp32 MFMA GEMM (ssc_gemm) against float64 matmul.  Tolerance: 2e-6 * sum|a||b| scale
 (fp32 accumulation over K), checked as max-abs <= 1e-4 for K <= 6000 with N(0,1)/sqrt(K)-scaled data."""
+import ctypes as C
+
 import pytest
 import torch
 
@@ -227,34 +229,39 @@ def test_large_products_split_bf16(kind, M, N, Ks, splits, form):
     """The 128x128 3xBF16 kernel (all three layouts; the m/n-contiguous operands go through the transposing LDS read)
     against float64: fp32-level accuracy, error <= 2e-6 * sum|a||b|."""
     a_kc, b_kc = {"NT": (1, 1), "NN": (1, 0), "TN": (0, 0)}[kind]
-    L.load().ssc_debug_set(b"large_form", form)   # 3: 4-wave 128x128 kernel (default), 2: its wave-specialised form
-    g = torch.Generator().manual_seed(M + N + len(Ks))
-    As = [(torch.randn((M, K) if a_kc else (K, M), generator=g) * torch.exp(torch.randn((M, K) if a_kc else (K, M), generator=g))).cuda() for K in Ks]
-    Bs = [(torch.randn((N, K) if b_kc else (K, N), generator=g) * torch.exp(torch.randn((N, K) if b_kc else (K, N), generator=g))).cuda() for K in Ks]
-    bias = torch.randn(N, generator=g).cuda()
-    out = torch.empty(M, N, device="cuda")
-    ws = torch.empty(8 * M * N, device="cuda")
-    gemm([(a, a.stride(0), b, b.stride(0), K) for a, b, K in zip(As, Bs, Ks)], M, N, a_kc, b_kc, out, bias=bias, splits=splits, ws=ws)
-    ref = bias.cpu().double()[None, :].repeat(M, 1)
-    mag = torch.zeros(M, N, dtype=torch.float64)
-    for a, b in zip(As, Bs):
-        ad, bd = a.cpu().double(), b.cpu().double()
-        ad = ad if a_kc else ad.T
-        bd = bd.T if b_kc else bd
-        ref += ad @ bd
-        mag += ad.abs() @ bd.abs()
-    err = ((out.cpu().double() - ref).abs() / mag.clamp_min(1e-30)).max().item()
-    assert err <= 2e-6, err
-    # exact on small integers (every partial product and sum is representable)
-    Ai = [torch.randint(-3, 4, a.shape, generator=g).float().cuda() for a in As]
-    Bi = [torch.randint(-3, 4, b.shape, generator=g).float().cuda() for b in Bs]
-    gemm([(a, a.stride(0), b, b.stride(0), K) for a, b, K in zip(Ai, Bi, Ks)], M, N, a_kc, b_kc, out, splits=splits, ws=ws)
-    refi = torch.zeros(M, N, dtype=torch.float64)
-    for a, b in zip(Ai, Bi):
-        ad, bd = a.cpu().double(), b.cpu().double()
-        refi += (ad if a_kc else ad.T) @ (bd.T if b_kc else bd)
-    assert torch.equal(out.cpu().double(), refi)
-    L.load().ssc_debug_set(b"large_form", 3)
+    lib = L.load()
+    prev = C.c_int(-1)
+    lib.ssc_debug_get(b"large_form", C.byref(prev))
+    lib.ssc_debug_set(b"large_form", form)   # 3: 4-wave 128x128 kernel, 2: its wave-specialised form
+    try:
+        g = torch.Generator().manual_seed(M + N + len(Ks))
+        As = [(torch.randn((M, K) if a_kc else (K, M), generator=g) * torch.exp(torch.randn((M, K) if a_kc else (K, M), generator=g))).cuda() for K in Ks]
+        Bs = [(torch.randn((N, K) if b_kc else (K, N), generator=g) * torch.exp(torch.randn((N, K) if b_kc else (K, N), generator=g))).cuda() for K in Ks]
+        bias = torch.randn(N, generator=g).cuda()
+        out = torch.empty(M, N, device="cuda")
+        ws = torch.empty(8 * M * N, device="cuda")
+        gemm([(a, a.stride(0), b, b.stride(0), K) for a, b, K in zip(As, Bs, Ks)], M, N, a_kc, b_kc, out, bias=bias, splits=splits, ws=ws)
+        ref = bias.cpu().double()[None, :].repeat(M, 1)
+        mag = torch.zeros(M, N, dtype=torch.float64)
+        for a, b in zip(As, Bs):
+            ad, bd = a.cpu().double(), b.cpu().double()
+            ad = ad if a_kc else ad.T
+            bd = bd.T if b_kc else bd
+            ref += ad @ bd
+            mag += ad.abs() @ bd.abs()
+        err = ((out.cpu().double() - ref).abs() / mag.clamp_min(1e-30)).max().item()
+        assert err <= 2e-6, err
+        # exact on small integers (every partial product and sum is representable)
+        Ai = [torch.randint(-3, 4, a.shape, generator=g).float().cuda() for a in As]
+        Bi = [torch.randint(-3, 4, b.shape, generator=g).float().cuda() for b in Bs]
+        gemm([(a, a.stride(0), b, b.stride(0), K) for a, b, K in zip(Ai, Bi, Ks)], M, N, a_kc, b_kc, out, splits=splits, ws=ws)
+        refi = torch.zeros(M, N, dtype=torch.float64)
+        for a, b in zip(Ai, Bi):
+            ad, bd = a.cpu().double(), b.cpu().double()
+            refi += (ad if a_kc else ad.T) @ (bd.T if b_kc else bd)
+        assert torch.equal(out.cpu().double(), refi)
+    finally:
+        lib.ssc_debug_set(b"large_form", prev.value)
 
 
 @pytest.mark.parametrize("form", [1, 2, 0])

@@ -17,11 +17,6 @@ DEFAULT = ["NT:64:4800:2048+1200+1200+1200", "NN:64:4448:4800+4800", "NN:64:1200
 
 
 def main():
-    import os as _os
-    from ssc_runtime import lib as _L
-    for env, key in (("SSC_X3_WIDE", b"x3_wide"), ("SSC_X3_PF", b"x3_pf"), ("SSC_X3_NBUF", b"x3_nbuf")):   # include/ssc_debug.h
-        if _os.environ.get(env):
-            _L.load().ssc_debug_set(key, int(_os.environ[env]))
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     shapes = sys.argv[2:] or DEFAULT
     for sh in shapes:
