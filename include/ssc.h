@@ -699,6 +699,44 @@ size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_sea
 int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Stochastic beam search (GumbelSampler driving BeamSearch._search, var_updown/var_updown/modules/beam_search.py:294-432,
+ * :592-768; Kool et al. 2019): `beam` = k distinct captions per batch entry, sampled without replacement with sequence-level
+ * probabilities.  lp = the untempered log_softmax of a row's logits, lpT = log_softmax(logits / T) (= lp at T = 1);
+ * gmax(phi, Tp): g_v = phi_v + Gumbel(u_v), Z = max_v g_v, G_v = Tp - softplus(Tp - g_v + log1p(-exp(g_v - Z))).
+ *   step 0: one row per entry, G = gmax(lp, 0) (untempered, target 0); the top k by G, re-ordered by lp descending.
+ *   step t >= 1: row (b, j) with running log-prob phi (ssc_beam_desc.last_lp) and state G_bj: G = gmax(phi + lpT, G_bj), the top
+ *     n = per_node tokens by G, each with the summed UNTEMPERED log-prob phi + lp[token].  Per entry, the top k of the k * n
+ *     candidates by G, sorted by summed log-prob descending (stable); back-pointer = candidate / n.
+ *   An ended beam (last token end_index) is one-hot at end_index: its one candidate is end_index with G = G_bj exactly and
+ *   log-prob phi; its logits are not read and it takes no noise.
+ *   Ties: equal G - lower token, lower candidate index; equal log-probs keep the G order.  G_v is strictly increasing in g_v, so
+ *   the top n by G are the top n by g (only the survivors are transformed; the order is the exact one).
+ * u_v: Philox4x32-10, key = seed, counter (v / 4, step, row, 0), word v % 4, mapped to (0, 1) as for ssc_sampler_desc; row = b at
+ * step 0, b * k + j after.  Limits: trivial machine only (dims.S = 1, fsm / tables / mach NULL), 1 <= per_node <= k <= 32,
+ * k <= V, B * k <= 2^24, temperature > 0 and finite - SSC_EINVAL beyond them.  A slot with no finite candidate emits end_index
+ * at -inf with the identity back-pointer.  ctl / host_flag: the early-stop protocol of ssc_beam_desc (step 0 included).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  float temperature;   /* T > 0: tempers the perturbed scores of steps >= 1 only (the reference's sample_nodes) */
+  uint64_t seed;
+} ssc_gumbel_desc;
+/* Step 0 from d->scores (B, V) ld d->ld (logits or log-probs: the row's log_softmax is taken).  Uses B, beam, dims.V,
+ * end_index, pred / lp_out (B, k), scratch_val (>= 2 * B * k floats), scratch_idx (>= B * k), ctl / max_steps / host_flag.
+ * g_out (B, k): the beams' G. */
+int ssc_beam_first_gumbel(const ssc_beam_desc* d, const ssc_gumbel_desc* s, float* g_out, void* stream);
+/* Step d->step_index >= 1 from d->scores (B * k, V): last_pred / last_lp (= phi) / g_last (B, k) -> pred / lp_out / g_out /
+ * backptr (B, k).  scratch_val >= 2 * B * k * per_node floats, scratch_idx >= B * k * per_node. */
+int ssc_beam_step_gumbel(const ssc_beam_desc* d, const ssc_gumbel_desc* s, const float* g_last, float* g_out, void* stream);
+/* The whole stochastic beam search of one diverse-decode call as ONE library call: the loop of ssc_decode_search with S = 1,
+ * beam k, per_node n and no machine (d->fsm = d->tables = d->mach = NULL), the Gumbel selection above in place of
+ * ssc_beam_first_fsm / ssc_beam_step_fsm; the same step forms (attention table, parent lists, un-gathered states, state planes),
+ * skip_dead, early stop and bounded run-ahead.  d->eps (max_steps - 1, B * k, Z).  Out: d->predictions (B, k, max_steps) -
+ * columns >= ctl[0] hold end_index -, d->log_probs (B, k) sorted descending: beam 0 is the best caption. */
+size_t ssc_decode_stochastic_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
+int ssc_decode_stochastic_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_gumbel_desc* s,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

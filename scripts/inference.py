@@ -75,7 +75,7 @@ def main():
         data = TensorFileData(_A.infer_tensors)
     cls = _LocalGlove if (_C.MODEL.EMBEDDING_SIZE in (300, 600) and _A.checkpoint_path) else UpDownCaptioner
     extra = {"mean_choice": {}} if _C.MODEL.SENTIMENT_VAE == 2 else {}   # (per-region attribute MEANS come with the data: data.obj)
-    sampler = sampling.from_config(_C.MODEL)   # MODEL.DECODE_SAMPLER: None = beam search
+    sampler = sampling.from_config(_C.MODEL)   # MODEL.DECODE_SAMPLER / STOCHASTIC_BEAM_SEARCH: None = beam search
     model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
@@ -85,8 +85,8 @@ def main():
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
     if sampler is not None and (_A.constraints_json or _A.boxes_json):
-        raise SystemExit(f"MODEL.DECODE_SAMPLER {_C.MODEL.DECODE_SAMPLER!r} does not take constraints: constrained sampling is "
-                         "not supported")
+        what = "MODEL.STOCHASTIC_BEAM_SEARCH" if sampler.beam_search else f"MODEL.DECODE_SAMPLER {_C.MODEL.DECODE_SAMPLER!r}"
+        raise SystemExit(f"{what} does not take constraints: constrained sampling is not supported")
     boundary = vocabulary.get_token_index("@@BOUNDARY@@")
     predictions = []
     id2word = np.array([vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())], dtype=object)

@@ -14,6 +14,7 @@
 #include <thread>
 
 #include "ssc_common.h"
+#include "ssc_philox.h"
 
 namespace {
 
@@ -23,21 +24,6 @@ constexpr int SAMPLE_LDS_MAX_V = 32768;             // 128 KiB row in LDS (+ ~3 
 constexpr double SAMPLE_MASS_ONE = 1099511627776.0;  // 2^40: fixed-point scale of the top-p masses
 
 inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC 2011)
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-}
-// 32 random bits -> u in the open interval (0, 1): the odd multiples of 2^-24 below 1 (exact in fp32)
-__device__ __forceinline__ float sample_uniform(uint32_t x) { return (float)(((x >> 9) << 1) | 1u) * 5.9604644775390625e-08f; }
-__device__ __forceinline__ float sample_gumbel(uint32_t x) { return -logf(-logf(sample_uniform(x))); }
 
 // order-preserving key: a > b (floats, no NaN) <=> key(a) > key(b)
 __device__ __forceinline__ uint32_t sample_key(float x) {

@@ -6,6 +6,8 @@
 // Reference: ConstrainedBeamSearch.search (updown-baseline/updown/modules/cbs.py:59-277) driving
 // UpDownCaptioner._decode_step in eval mode (var_updown/var_updown/models/updown_captioner.py:371-455), as the reference's
 // inference loop does per image and latent sample (var_updown/scripts/inference.py:117-189).
+#include <math.h>
+
 #include <algorithm>
 #include <thread>
 
@@ -16,11 +18,12 @@ namespace {
 inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The vocabulary head of the later steps leaves per-tile records instead of logits (ssc_decode_step_desc.topk_part) when the machine
-// is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.
-bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+// is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.  Never for the
+// stochastic beam search (gumbel): any token can win a Gumbel draw, so its selection reads the raw logits.
+bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d, bool gumbel) {
   const long G = (long)d->nimg * d->n_samples * d->S * d->beam;
-  return d->S == 1 && !d->fsm && !d->tables && d->per_node <= 2 && !cfg->tied && cfg->gemm_mode != 2 && cfg->H % 4 == 0 && G >= 512 &&
-         ssc_decode_parts_enabled();
+  return !gumbel && d->S == 1 && !d->fsm && !d->tables && d->per_node <= 2 && !cfg->tied && cfg->gemm_mode != 2 && cfg->H % 4 == 0 &&
+         G >= 512 && ssc_decode_parts_enabled();
 }
 
 struct SearchLayout {
@@ -32,7 +35,8 @@ struct SearchLayout {
   size_t backs;        // (max_steps-1, B, SB) int64
   size_t parent0;      // (B, SB) int64 zeros: every beam of the first expanded step descends from the one start row
   size_t lp[2];        // (B, S, beam) float
-  size_t sval, sidx;   // B*S*SB*per_node
+  size_t gs[2];        // gumbel: (B, beam) float, the beams' G (empty for beam search)
+  size_t sval, sidx;   // B*S*SB*per_node (gumbel: twice as many values - the candidates' G and log-probs)
   size_t alpha;        // (G, R)
   size_t logits;       // (G, V); (B, V) when the later steps leave records
   size_t parts;        // (G, ceil(V / 128), 6) records
@@ -41,7 +45,7 @@ struct SearchLayout {
   size_t total;
 };
 
-SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, bool gumbel) {
   SearchLayout l;
   const size_t B = (size_t)d->nimg * d->n_samples, SB = (size_t)d->S * d->beam, G = B * SB;
   const size_t H = cfg->H;
@@ -57,10 +61,11 @@ SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
   l.backs = o; o += a256((size_t)std::max(d->max_steps - 1, 1) * G * 8);
   l.parent0 = o; o += a256(G * 8);
   for (int g = 0; g < 2; ++g) { l.lp[g] = o; o += a256(G * 4); }
-  l.sval = o; o += a256(B * d->S * SB * d->per_node * 4);
+  for (int g = 0; g < 2; ++g) { l.gs[g] = o; o += a256(gumbel ? G * 4 : 0); }
+  l.sval = o; o += a256(B * d->S * SB * d->per_node * 4 * (gumbel ? 2 : 1));
   l.sidx = o; o += a256(B * d->S * SB * d->per_node * 8);
   l.alpha = o; o += a256(G * (size_t)d->R * 4);
-  const bool parts = search_uses_parts(cfg, d);
+  const bool parts = search_uses_parts(cfg, d, gumbel);
   l.logits = o; o += a256((parts ? B : G) * (size_t)cfg->V * 4);
   l.parts = o; o += a256(parts ? G * (size_t)ssc_cdiv(cfg->V, 128) * 6 * 4 : 0);
   l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)G, d->R);
@@ -104,17 +109,32 @@ extern "C" size_t ssc_decode_search_workspace_bytes(const ssc_model_cfg* cfg, co
   if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
       d->R <= 0)
     return 0;
-  return search_layout(cfg, d).total;
+  return search_layout(cfg, d, false).total;
 }
 
-extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-  SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
-  if (!p || !workspace || !desc_ok(cfg, d)) return SSC_EINVAL;
-  const SearchLayout l = search_layout(cfg, d);
-  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
-  hipStream_t st = (hipStream_t)stream;
-  char* W = (char*)workspace;
+namespace {
+
+// The selections the search loop below runs: beam search (the machine's top-k, ssc_beam_*_fsm / ssc_beam_step_parts) and the
+// stochastic beam search (Gumbel-top-k, sbs.hip).  first() selects step 0; step(a) a later step, reading the running state of
+// generation a and writing generation 1 - a.
+struct BeamSelect {
+  bool use_parts;
+  const float* parts;
+  int first(ssc_beam_desc* bd, hipStream_t st) const { return ssc_beam_first_fsm(bd, st); }
+  int step(ssc_beam_desc* bd, int, hipStream_t st) const {
+    return use_parts ? ssc_beam_step_parts(bd, parts, st) : ssc_beam_step_fsm(bd, st);
+  }
+};
+struct GumbelSelect {
+  const ssc_gumbel_desc* s;
+  float* g[2];
+  int first(ssc_beam_desc* bd, hipStream_t st) const { return ssc_beam_first_gumbel(bd, s, g[0], st); }
+  int step(ssc_beam_desc* bd, int a, hipStream_t st) const { return ssc_beam_step_gumbel(bd, s, g[a], g[1 - a], st); }
+};
+
+template <class Select>
+int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const SearchLayout& l, char* W,
+               const Select& sel, bool use_parts, hipStream_t st) {
   const int B = d->nimg * d->n_samples, S = d->S, beam = d->beam, SB = S * beam, G = B * SB, H = cfg->H, V = cfg->V, Z = cfg->Z;
   float* stt[2][4];
   for (int g = 0; g < 2; ++g)
@@ -127,8 +147,6 @@ extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, 
   float* lp[2] = {(float*)(W + l.lp[0]), (float*)(W + l.lp[1])};
   float* alpha = (float*)(W + l.alpha);
   float* logits = (float*)(W + l.logits);
-  float* parts = (float*)(W + l.parts);
-  const bool use_parts = search_uses_parts(cfg, d);
   const size_t plane = (size_t)G;
   const int nctl = 2 + 2 * d->max_steps;
 
@@ -162,7 +180,7 @@ extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, 
   bd.pred = preds; bd.lp_out = lp[0];
   bd.ctl = d->early_stop ? d->ctl : nullptr; bd.max_steps = d->max_steps; bd.host_flag = d->early_stop ? d->host_flag : nullptr;
   bd.scratch_val = (float*)(W + l.sval); bd.scratch_idx = (int64_t*)(W + l.sidx);
-  SSC_TRY(ssc_beam_first_fsm(&bd, st));
+  SSC_TRY(sel.first(&bd, st));
   // ---- enlarge the states to (B, S, beam) rows (cbs.py:152-155) --------------------------------------------------------------
   if (d->max_steps > 1) {
     for (int k = 0; k < 4; ++k) {
@@ -219,12 +237,11 @@ extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, 
       sd.h1_planes = ungathered ? W + l.pl[cur][0] : nullptr; sd.hd_planes = ungathered ? W + l.pl[cur][1] : nullptr;
     }
     sd.row_lp = d->skip_dead ? lp[a] : nullptr; sd.end_index = d->end_index;
-    if (use_parts) { sd.log_probs = nullptr; sd.topk_part = parts; }
+    if (use_parts) { sd.log_probs = nullptr; sd.topk_part = (float*)(W + l.parts); }
     SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
     bd.last_pred = last; bd.last_lp = lp[a]; bd.pred = preds + (size_t)t * plane; bd.lp_out = lp[1 - a];
     bd.backptr = backs + (size_t)(t - 1) * plane; bd.step_index = t;
-    if (use_parts) SSC_TRY(ssc_beam_step_parts(&bd, parts, st));
-    else SSC_TRY(ssc_beam_step_fsm(&bd, st));
+    SSC_TRY(sel.step(&bd, a, st));
     a = 1 - a;
     if (ung) {   // the next step reads these outputs through the back-pointers (ssc_decode_step_desc.ungathered)
       cur = 1 - cur;
@@ -241,4 +258,42 @@ extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, 
   }
   if (hipMemcpyAsync(d->log_probs, lp[a], (size_t)G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   return SSC_OK;
+}
+
+}  // namespace
+
+extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
+  if (!p || !workspace || !desc_ok(cfg, d)) return SSC_EINVAL;
+  const SearchLayout l = search_layout(cfg, d, false);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  char* W = (char*)workspace;
+  const bool use_parts = search_uses_parts(cfg, d, false);
+  return search_run(cfg, p, d, l, W, BeamSelect{use_parts, (const float*)(W + l.parts)}, use_parts, (hipStream_t)stream);
+}
+
+// the stochastic beam search: S = 1, no machine, the limits of ssc_beam_step_gumbel (k <= 32, per_node <= k, k <= V)
+static bool sbs_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_gumbel_desc* s) {
+  if (!desc_ok(cfg, d) || !s) return false;
+  if (d->S != 1 || d->fsm || d->tables || d->mach) return false;
+  if (d->beam > 32 || d->beam > cfg->V || d->per_node > d->beam) return false;
+  return s->temperature > 0.f && isfinite(s->temperature);
+}
+
+extern "C" size_t ssc_decode_stochastic_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
+      d->R <= 0)
+    return 0;
+  return search_layout(cfg, d, true).total;
+}
+
+extern "C" int ssc_decode_stochastic_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                          const ssc_gumbel_desc* s, void* workspace, size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);
+  if (!p || !workspace || !sbs_search_ok(cfg, d, s)) return SSC_EINVAL;
+  const SearchLayout l = search_layout(cfg, d, true);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  char* W = (char*)workspace;
+  return search_run(cfg, p, d, l, W, GumbelSelect{s, {(float*)(W + l.gs[0]), (float*)(W + l.gs[1])}}, false, (hipStream_t)stream);
 }

@@ -67,6 +67,9 @@ def _defaults() -> dict:
             # "top-p" - the reference's MultinomialSampler / TopKSampler / TopPSampler (modules/beam_search.py:103-293); needs
             # BEAM_SIZE 1 and no CBS
             "DECODE_SAMPLER": "beam", "SAMPLER_TOP_K": 0, "SAMPLER_TOP_P": 1.0, "SAMPLER_TEMPERATURE": 1.0,
+            # stochastic beam search (the reference's GumbelSampler, modules/beam_search.py:294-432): BEAM_SIZE captions sampled without
+            # replacement per latent sample; needs DECODE_SAMPLER "beam" and no CBS; SAMPLER_TEMPERATURE applies
+            "STOCHASTIC_BEAM_SEARCH": False,
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,

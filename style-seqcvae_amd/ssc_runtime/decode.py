@@ -282,6 +282,56 @@ class DecodeEngine:
             _HOST_FLAGS.append(flag)
         return pred[:, :nsteps].contiguous(), lps
 
+    def stochastic_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
+                        max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
+                        early_stop: bool = True, skip_dead: bool = True):
+        """The whole stochastic beam search of one call in ONE library call (ssc_decode_stochastic_beam): ctx.nimg images x n_samples
+        latent samples, batch entry b = (image, sample), `beam` captions per entry sampled without replacement by `sampler`
+        (sampling.GumbelSampler) with the 64-bit `seed`, per_node candidates per beam.  sentiment (B) or None; eps0 (B, Z),
+        eps (max_steps - 1, B*beam, Z): the noise of every step.
+        -> (predictions (B, beam, steps) int64, log_probs (B, beam): summed untempered log-probs, descending)."""
+        d = self.dims
+        B = ctx.nimg * n_samples
+        G = B * beam
+        dev = self.device
+        if not 1 <= per_node <= beam <= min(32, d.V):
+            raise ValueError(f"stochastic beam search needs 1 <= per_node <= beam <= min(32, V), got per_node {per_node}, beam {beam}")
+        sd = _lib.SearchDesc()
+        sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
+        sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = 1, beam, per_node, max_steps, end_index
+        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
+        sent = sentiment.reshape(B).to(dev, torch.float32).contiguous() if sentiment is not None else None
+        eps0 = eps0.to(dev, torch.float32).contiguous()
+        assert tuple(eps0.shape) == (B, d.Z), eps0.shape
+        if max_steps > 1:
+            eps = eps.to(dev, torch.float32).contiguous()
+            assert tuple(eps.shape) == (max_steps - 1, G, d.Z), (eps.shape, (max_steps - 1, G, d.Z))
+        sd.sentiment, sd.eps0, sd.eps = _lib.ptr(sent), _lib.ptr(eps0), _lib.ptr(eps) if max_steps > 1 else None
+        sd.obj_atts = _lib.ptr(ctx.obj)
+        sd.skip_dead = 1 if skip_dead else 0   # ended beams are not stepped
+        sd.early_stop = 1 if early_stop else 0
+        pred = torch.empty(B, beam, max_steps, dtype=torch.int64, device=dev)
+        lps = torch.empty(B, beam, dtype=torch.float32, device=dev)
+        ctl = torch.empty(2 + 2 * max_steps, dtype=torch.int32, device=dev)
+        sd.predictions, sd.log_probs, sd.ctl = _lib.ptr(pred), _lib.ptr(lps), _lib.ptr(ctl)
+        flag = None
+        if early_stop:
+            flag, flag_dev = _host_flag()
+            if flag_dev is not None:
+                sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
+        nbytes = self.lib.ssc_decode_stochastic_beam_workspace_bytes(C.byref(self._cfg), C.byref(sd))
+        if self._sws is None or self._sws.numel() < nbytes:
+            self._sws = None   # (release before growing)
+            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        p = self._params()
+        gdesc = sampler.desc(seed)
+        self.lib.ssc_decode_stochastic_beam(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(gdesc), _lib.ptr(self._sws),
+                                            self._sws.numel(), _lib.stream_ptr())
+        nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call)
+        if flag is not None:
+            _HOST_FLAGS.append(flag)
+        return pred[:, :, :nsteps].contiguous(), lps
+
     def _step_from_embedding(self, ctx, token_embedding, states, sentiment, eps, prior_mean_out=None, prior_mean=None, prior_var=None):
         G = token_embedding.size(0)
         table = token_embedding.to(self.device, torch.float32).contiguous()

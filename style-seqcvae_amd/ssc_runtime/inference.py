@@ -35,11 +35,16 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     compiled: the machines' CompiledFsm when the caller has it already.
     obj_means (nimg, R, Z): per-region attribute means, SENTIMENT_VAE = 2 only (UpDownCaptioner.translate_obj_atts2obj_means).
     sampler: None - beam search, as above -, or a word sampler of ssc_runtime.sampling (multinomial / top-k / top-p): every word
-    of every caption is then drawn on the device (DecodeEngine.sample, one library call); needs beam = 1 and fsm = None.
+    of every caption is then drawn on the device (DecodeEngine.sample, one library call); needs beam = 1 and fsm = None.  Or
+    sampling.GumbelSampler: the stochastic beam search (DecodeEngine.stochastic_beam) at any beam, per_node as for beam search;
+    beam 0 - the sampled caption with the highest log-prob - of every (image, sample) is returned; needs fsm = None.
     sample_seed: the 64-bit seed of the word draws; default: the call's one draw from the global generator (the seed of the
     latent noise as well; with eps_steps given, one draw is made for the words), so a sampled call consumes the global random
     state as a beam call does and sees the same latent noise as a beam-1 call."""
-    if sampler is not None:
+    gumbel = sampler is not None and sampler.beam_search
+    if gumbel and fsm is not None:
+        raise ValueError("the stochastic beam search does not take constraints (fsm): constrained sampling is not supported")
+    if sampler is not None and not gumbel:
         if beam != 1:
             raise ValueError(f"word sampling draws one word per row: beam must be 1, got {beam}")
         if fsm is not None:
@@ -83,6 +88,11 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
             gen.manual_seed(seed)
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
+        if gumbel:
+            beams, lps = dec.stochastic_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
+                                             seed if sample_seed is None else sample_seed, early_stop=early_stop, skip_dead=skip_now)
+            calls["k"] = beams.size(-1)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
         if sampler is not None:
             pred, lps = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
                                    seed if sample_seed is None else sample_seed, early_stop=early_stop)

@@ -138,6 +138,10 @@ class SamplerDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class GumbelDesc(C.Structure):
+    _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64)]
+
+
 # name -> (restype, argtypes).  Every symbol include/ssc.h declares is listed; tests check they all resolve.
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -218,6 +222,11 @@ SYMBOLS = {
     "ssc_sample_rows": (_i, [vp, _i, _i, _i, C.POINTER(SamplerDesc), vp, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_sample_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), vp, _sz, vp]),
+    "ssc_beam_first_gumbel": (_i, [C.POINTER(BeamDesc), C.POINTER(GumbelDesc), vp, vp]),
+    "ssc_beam_step_gumbel": (_i, [C.POINTER(BeamDesc), C.POINTER(GumbelDesc), vp, vp, vp]),
+    "ssc_decode_stochastic_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
+    "ssc_decode_stochastic_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(GumbelDesc), vp, _sz,
+                                        vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)

@@ -6,6 +6,9 @@ signatures and argument checks.  The reference draws with torch.multinomial; her
 counter-based Philox4x32-10 noise keyed by a 64-bit seed: the same distribution, reproducible bit for bit.  One draw per row
 (beam 1, per_node_beam_size 1), so `with_replacement` has no effect.  Top-p keeps every token at p = 1 (the reference's fp32
 cumsum can fall short of 1 and drop tail tokens there).
+
+GumbelSampler (beam_search.py:294-432) is the stochastic beam search: `beam` captions per batch entry without replacement, at any
+beam (DecodeEngine.stochastic_beam / ssc_decode_stochastic_beam).
 """
 from . import lib as _lib
 
@@ -15,6 +18,7 @@ KINDS = {"multinomial": 0, "top-k": 1, "top-p": 2}
 class Sampler:
     kind = -1
     name = ""
+    beam_search = False   # True: a sequence-level sampler that runs at any beam (GumbelSampler); False: a word sampler, beam 1 only
 
     def desc(self, seed: int) -> "_lib.SamplerDesc":
         """The C struct ssc_sampler_desc for a call with this 64-bit seed."""
@@ -86,13 +90,39 @@ class TopPSampler(Sampler):
         self.with_replacement = with_replacement
 
 
+class GumbelSampler(Sampler):
+    """Stochastic beam search (beam_search.py:294-432, Kool et al. 2019): the beam keeps `beam` distinct captions per batch entry,
+    sampled without replacement with sequence-level probabilities through the Gumbel-top-k trick (ssc_decode_stochastic_beam,
+    include/ssc.h).  temperature tempers the perturbed scores of the steps after the first, as in the reference."""
+    kind = -2
+    name = "gumbel"
+    beam_search = True
+
+    def __init__(self, temperature: float = 1.0):
+        if not temperature > 0:   # (the reference would divide by zero)
+            raise ValueError(f"the Gumbel sampler needs temperature > 0, got {temperature}")
+        self.temperature = float(temperature)
+
+    def desc(self, seed: int) -> "_lib.GumbelDesc":
+        """The C struct ssc_gumbel_desc for a call with this 64-bit seed."""
+        d = _lib.GumbelDesc()
+        d.temperature = float(self.temperature)
+        d.seed = int(seed) & (2 ** 64 - 1)
+        return d
+
+
 def from_config(model_cfg):
-    """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE describe, or None for
-    "beam" (beam search, the default)."""
+    """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / STOCHASTIC_BEAM_SEARCH
+    describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER "beam" gives
+    GumbelSampler(SAMPLER_TEMPERATURE)."""
     kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
     T = float(model_cfg.SAMPLER_TEMPERATURE)
+    sbs = bool(getattr(model_cfg, "STOCHASTIC_BEAM_SEARCH", False))
+    if sbs and kind != "beam":
+        raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
+                         "samplers draw one word per row; the stochastic beam search is a kind of beam search)")
     if kind == "beam":
-        return None
+        return GumbelSampler(temperature=T) if sbs else None
     if kind == "multinomial":
         return MultinomialSampler(temperature=T)
     if kind == "top-k":
@@ -100,4 +130,4 @@ def from_config(model_cfg):
     if kind == "top-p":
         return TopPSampler(p=float(model_cfg.SAMPLER_TOP_P), temperature=T)
     raise ValueError(f"MODEL.DECODE_SAMPLER must be one of 'beam', 'multinomial', 'top-k', 'top-p', got {model_cfg.DECODE_SAMPLER!r} "
-                     "(the Gumbel / stochastic beam sampler is not supported)")
+                     "(for the Gumbel / stochastic beam sampler set MODEL.STOCHASTIC_BEAM_SEARCH True with DECODE_SAMPLER 'beam')")

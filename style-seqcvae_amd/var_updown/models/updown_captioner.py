@@ -63,9 +63,11 @@ class UpDownCaptioner(nn.Module):
         is never defined, :89).  Here the caller supplies it: a dict of vectors, or use mean_choice_from_sentiglove /
         mean_choice_from_senti_wordnet, which restate :80-86.
         `sampler` (optional): a word sampler of ssc_runtime.sampling (MODEL.DECODE_SAMPLER) - the eval forward then draws every word
-        on the device (ssc_decode_sample) instead of running beam search; needs beam_size 1 and no CBS decode."""
+        on the device (ssc_decode_sample) instead of running beam search; needs beam_size 1 and no CBS decode.  Or
+        sampling.GumbelSampler (MODEL.STOCHASTIC_BEAM_SEARCH): the eval forward runs the stochastic beam search at beam_size with
+        per_node_beam_size beam_size // 2 (beam_size when that is 0) in one library call and returns beam 0; no CBS decode."""
         super().__init__()
-        if sampler is not None and beam_size != 1:
+        if sampler is not None and not sampler.beam_search and beam_size != 1:
             raise ValueError(f"MODEL.BEAM_SIZE must be 1 with MODEL.DECODE_SAMPLER {sampler.name!r} (word sampling draws one word per "
                              f"row), got {beam_size}")
         self.sampler = sampler
@@ -308,11 +310,20 @@ class UpDownCaptioner(nn.Module):
     def _sample_decode(self, image_features, obj_means, sentiment):
         """Eval forward with a word sampler: the whole decode in one library call (DecodeEngine.sample).  The latent noise is drawn
         for every step up front from the same source as the beam path's (one (B, Z) draw per step); the word seed is one draw from
-        the global generator."""
+        the global generator.  With the Gumbel sampler: the stochastic beam search (DecodeEngine.stochastic_beam), noise drawn as
+        the beam path draws it ((B, Z) for the first step, (B * beam, Z) for every later one), beam 0 returned."""
         B = image_features.size(0)
         L = self._max_caption_length
         dev = self._eng.device
         ctx = self._image_context(image_features, obj_means)
+        if self.sampler.beam_search:
+            k = self._beam_search.beam_size
+            eps0 = self._draw_eps(1, B, dev)[0]
+            eps = self._draw_eps(L - 1, B * k, dev) if L > 1 else None
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            sent = sentiment.reshape(B) if sentiment is not None else None
+            beams, _ = self._dec.stochastic_beam(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.sampler, seed)
+            return beams[:, 0, :]
         eps = self._draw_eps(L, B, dev)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         sent = sentiment.reshape(B) if sentiment is not None else None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Time of the sampled decode (ssc_decode_sample) against the beam-1 and beam-5 searches (ssc_decode_search) at the bench's decode
 shape - 100 images x 20 latent samples per call, 36 x 2048 features, V 10 000, H 1200, max 20 steps, early stop off so every call
-runs all its steps -, and of the row sampler alone (sample_rows_kernel through ssc_sample_rows) on (G, V) logits, with its
+runs all its steps -, the stochastic beam search at beam 5 (ssc_decode_stochastic_beam), and of the row sampler alone (sample_rows_kernel through ssc_sample_rows) on (G, V) logits, with its
 logits bytes / time against one HBM pass.
     python tools/sample_probe.py [calls]
 Prints one JSON line."""
@@ -53,7 +53,8 @@ def main():
     out = {"images": images, "n_z": n_z, "max_steps": steps, "V": c["V"]}
     t0 = time.perf_counter()
     for name, beam, sampler in (("beam5", 5, None), ("beam1", 1, None), ("top_p_0.9", 1, sampling.TopPSampler(p=0.9)),
-                                ("top_k_40", 1, sampling.TopKSampler(k=40)), ("multinomial", 1, sampling.MultinomialSampler())):
+                                ("top_k_40", 1, sampling.TopKSampler(k=40)), ("multinomial", 1, sampling.MultinomialSampler()),
+                                ("stochastic_beam5", 5, sampling.GumbelSampler())):
         ms = timed(lambda: diverse_decode(dec, feats, senti, n_z, beam, steps, 1, early_stop=False, sampler=sampler), calls)
         out[name] = {"ms_per_call": ms, "us_per_step": ms * 1e3 / steps}
     # the row sampler alone on (G, V) logits
@@ -71,6 +72,20 @@ def main():
             lib.ssc_sample_rows(L.ptr(logits), V, G, V, d, None, 1, None, None, 1, L.ptr(pred), L.ptr(lp), None, L.stream_ptr())
         us = timed(run, 50) * 1e3
         out["row_kernel"][name] = {"us": us, "GBps": G * V * 4 / us / 1e3}
+    # the stochastic beam search's selection alone (row kernel + merge, ssc_beam_step_gumbel) on (G * 5, V) logits, beam 5, per-node 2
+    Gs, k, n = G * 5, 5, 2
+    big = torch.randn(Gs, V, device=dev) * 3
+    bd = L.BeamDesc()
+    bd.scores, bd.ld, bd.raw_logits, bd.dims = L.ptr(big), V, 1, L.FsmDims(0, 1, V, 0, 1)
+    bd.B, bd.beam, bd.per_node, bd.end_index, bd.step_index = G, k, n, 1, 1
+    bufs = [torch.zeros(Gs, dtype=torch.int64, device=dev), torch.full((Gs,), -5.0, device=dev), torch.empty(Gs, dtype=torch.int64, device=dev),
+            torch.empty(Gs, device=dev), torch.empty(Gs, dtype=torch.int64, device=dev), torch.empty(2 * Gs * n, device=dev),
+            torch.empty(Gs * n, dtype=torch.int64, device=dev), torch.full((Gs,), -4.0, device=dev), torch.empty(Gs, device=dev)]
+    bd.last_pred, bd.last_lp, bd.pred, bd.lp_out, bd.backptr, bd.scratch_val, bd.scratch_idx = [L.ptr(b) for b in bufs[:7]]
+    gd = sampling.GumbelSampler().desc(7)
+    us = timed(lambda: lib.ssc_beam_step_gumbel(bd, gd, L.ptr(bufs[7]), L.ptr(bufs[8]), L.stream_ptr()), 20) * 1e3
+    out["row_kernel"]["stochastic_beam_step"] = {"G": Gs, "us": us, "GBps": Gs * V * 4 / us / 1e3}
+    del big
     # one HBM pass over the same bytes (a device copy reads and writes them: half its time is the read)
     dst = torch.empty_like(logits)
     us_copy = timed(lambda: dst.copy_(logits), 50) * 1e3
