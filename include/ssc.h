@@ -737,6 +737,38 @@ size_t ssc_decode_stochastic_beam_workspace_bytes(const ssc_model_cfg* cfg, cons
 int ssc_decode_stochastic_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_gumbel_desc* s,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Sampled-node beam search (BeamSearch._search driven by MultinomialSampler / TopKSampler / TopPSampler,
+ * var_updown/var_updown/modules/beam_search.py:103-293, :592-768): every live beam samples per_node = n candidate tokens from
+ * the filtered, tempered distribution of ssc_sampler_desc; the k * n candidates of a batch entry are merged deterministically.
+ * lp = the untempered log_softmax of a row's logits.
+ *   step 0: the word samplers keep sample_beams = torch.topk: ssc_beam_first_fsm with the trivial machine (ties: lower token).
+ *   step t >= 1, row (b, j) with running log-prob phi (ssc_beam_desc.last_lp): score s_v = logit_v / T + g_v over the kept set of
+ *     kind 0 / 1 / 2 (as ssc_sample_rows; top-p WITHOUT replacement also keeps the first n tokens of the sorted distribution).
+ *     Without replacement: the n tokens of largest s_v (Gumbel-top-n), in descending order (ties: lower token).  With replacement:
+ *     n independent Gumbel-max draws, draw d with noise word d, in draw order (duplicates allowed).  Each candidate carries the
+ *     summed UNTEMPERED log-prob phi + lp[token].  Per entry, the top k of the k * n candidates by summed log-prob, descending
+ *     (ties: lower candidate index = j * n + slot); back-pointer = candidate / n.
+ *   An ended beam (last token end_index) is one-hot at end_index: its logits are not read and it takes no noise.  Without
+ *   replacement its candidates are (end_index, phi), then (end_index, -inf); with replacement all n are (end_index, phi).
+ * g_v = -log(-log(u_v)), u_v: Philox4x32-10, key = seed, counter (v / 4, step, row, d), word v % 4, mapped to (0, 1) as for
+ * ssc_sampler_desc; row = b * k + j, d = the draw (0 without replacement).  At k = n = 1 a step is ssc_sample_rows on the same row
+ * id and step, bit for bit.  Limits: trivial machine only (dims.S = 1, fsm / tables / mach NULL), 1 <= k <= 32, 1 <= n <= 32,
+ * k, n <= V, top-k with n <= top_k <= V, B * k <= 2^24, temperature > 0 and finite - SSC_EINVAL beyond them.  A slot with no
+ * finite candidate emits end_index at -inf with the identity back-pointer.  ctl / host_flag: the early-stop protocol of
+ * ssc_beam_desc (step 0 included).
+ * ---------------------------------------------------------------------------------------------- */
+/* Step d->step_index >= 1 from raw logits d->scores (B * k, V) ld d->ld: last_pred / last_lp (B, k) -> pred / lp_out / backptr
+ * (B, k).  scratch_val >= B * k * per_node floats, scratch_idx >= B * k * per_node: the rows' candidates. */
+int ssc_beam_step_sampled(const ssc_beam_desc* d, const ssc_sampler_desc* s, int with_replacement, void* stream);
+/* The whole sampled-node beam search of one diverse-decode call as ONE library call: the loop of ssc_decode_search with S = 1,
+ * beam k, per_node n and no machine, ssc_beam_first_fsm for step 0 and the sampled step after it; the same step forms, skip_dead,
+ * early stop and bounded run-ahead.  d->eps (max_steps - 1, B * k, Z).  Out: d->predictions (B, k, max_steps) - columns >= ctl[0]
+ * hold end_index -, d->log_probs (B, k) sorted descending: beam 0 is the best caption. */
+size_t ssc_decode_sampled_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
+int ssc_decode_sampled_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                            int with_replacement, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

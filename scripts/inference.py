@@ -76,6 +76,7 @@ def main():
     cls = _LocalGlove if (_C.MODEL.EMBEDDING_SIZE in (300, 600) and _A.checkpoint_path) else UpDownCaptioner
     extra = {"mean_choice": {}} if _C.MODEL.SENTIMENT_VAE == 2 else {}   # (per-region attribute MEANS come with the data: data.obj)
     sampler = sampling.from_config(_C.MODEL)   # MODEL.DECODE_SAMPLER / STOCHASTIC_BEAM_SEARCH: None = beam search
+    sampled_beam = sampling.sampled_beam_from_config(_C.MODEL)   # MODEL.SAMPLED_BEAM_SEARCH: the word sampler at BEAM_SIZE
     model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
@@ -85,7 +86,8 @@ def main():
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
     if sampler is not None and (_A.constraints_json or _A.boxes_json):
-        what = "MODEL.STOCHASTIC_BEAM_SEARCH" if sampler.beam_search else f"MODEL.DECODE_SAMPLER {_C.MODEL.DECODE_SAMPLER!r}"
+        what = ("MODEL.STOCHASTIC_BEAM_SEARCH" if sampler.beam_search else "MODEL.SAMPLED_BEAM_SEARCH" if sampled_beam
+                else f"MODEL.DECODE_SAMPLER {_C.MODEL.DECODE_SAMPLER!r}")
         raise SystemExit(f"{what} does not take constraints: constrained sampling is not supported")
     boundary = vocabulary.get_token_index("@@BOUNDARY@@")
     predictions = []
@@ -143,7 +145,7 @@ def main():
             obj = data.obj[lo: lo + n_here, : feats.size(1)].to(device) if getattr(data, "obj", None) is not None else None
             pred, _ = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
-                                     obj_means=obj, sampler=sampler)
+                                     obj_means=obj, sampler=sampler, sampled_beam=sampled_beam)
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
             ids = pred.cpu().numpy()                                   # (images, n_z, steps)

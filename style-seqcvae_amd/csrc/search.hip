@@ -17,13 +17,17 @@ namespace {
 
 inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// The selection a search runs: beam search (the machine's top-k), the stochastic beam search (Gumbel-top-k, sbs.hip) or the
+// sampled-node beam search (a word sampler's draws per beam, sampled_beam.hip).
+enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED };
+
 // The vocabulary head of the later steps leaves per-tile records instead of logits (ssc_decode_step_desc.topk_part) when the machine
-// is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.  Never for the
-// stochastic beam search (gumbel): any token can win a Gumbel draw, so its selection reads the raw logits.
-bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d, bool gumbel) {
+// is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.  Beam search
+// only: any token can win a Gumbel draw or a sampler's draw, so those selections read the raw logits.
+bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d, SearchKind kind) {
   const long G = (long)d->nimg * d->n_samples * d->S * d->beam;
-  return !gumbel && d->S == 1 && !d->fsm && !d->tables && d->per_node <= 2 && !cfg->tied && cfg->gemm_mode != 2 && cfg->H % 4 == 0 &&
-         G >= 512 && ssc_decode_parts_enabled();
+  return kind == SEARCH_BEAM && d->S == 1 && !d->fsm && !d->tables && d->per_node <= 2 && !cfg->tied && cfg->gemm_mode != 2 &&
+         cfg->H % 4 == 0 && G >= 512 && ssc_decode_parts_enabled();
 }
 
 struct SearchLayout {
@@ -45,8 +49,9 @@ struct SearchLayout {
   size_t total;
 };
 
-SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, bool gumbel) {
+SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, SearchKind kind) {
   SearchLayout l;
+  const bool gumbel = kind == SEARCH_GUMBEL;
   const size_t B = (size_t)d->nimg * d->n_samples, SB = (size_t)d->S * d->beam, G = B * SB;
   const size_t H = cfg->H;
   size_t o = 0;
@@ -65,7 +70,7 @@ SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, b
   l.sval = o; o += a256(B * d->S * SB * d->per_node * 4 * (gumbel ? 2 : 1));
   l.sidx = o; o += a256(B * d->S * SB * d->per_node * 8);
   l.alpha = o; o += a256(G * (size_t)d->R * 4);
-  const bool parts = search_uses_parts(cfg, d, gumbel);
+  const bool parts = search_uses_parts(cfg, d, kind);
   l.logits = o; o += a256((parts ? B : G) * (size_t)cfg->V * 4);
   l.parts = o; o += a256(parts ? G * (size_t)ssc_cdiv(cfg->V, 128) * 6 * 4 : 0);
   l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)G, d->R);
@@ -109,14 +114,14 @@ extern "C" size_t ssc_decode_search_workspace_bytes(const ssc_model_cfg* cfg, co
   if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
       d->R <= 0)
     return 0;
-  return search_layout(cfg, d, false).total;
+  return search_layout(cfg, d, SEARCH_BEAM).total;
 }
 
 namespace {
 
-// The selections the search loop below runs: beam search (the machine's top-k, ssc_beam_*_fsm / ssc_beam_step_parts) and the
-// stochastic beam search (Gumbel-top-k, sbs.hip).  first() selects step 0; step(a) a later step, reading the running state of
-// generation a and writing generation 1 - a.
+// The selections the search loop below runs: beam search (the machine's top-k, ssc_beam_*_fsm / ssc_beam_step_parts), the
+// stochastic beam search (Gumbel-top-k, sbs.hip) and the sampled-node beam search (sampled_beam.hip).  first() selects step 0;
+// step(a) a later step, reading the running state of generation a and writing generation 1 - a.
 struct BeamSelect {
   bool use_parts;
   const float* parts;
@@ -130,6 +135,12 @@ struct GumbelSelect {
   float* g[2];
   int first(ssc_beam_desc* bd, hipStream_t st) const { return ssc_beam_first_gumbel(bd, s, g[0], st); }
   int step(ssc_beam_desc* bd, int a, hipStream_t st) const { return ssc_beam_step_gumbel(bd, s, g[a], g[1 - a], st); }
+};
+struct SampledSelect {   // step 0 is the word samplers' sample_beams: the plain top-k of the trivial machine
+  const ssc_sampler_desc* s;
+  int with_replacement;
+  int first(ssc_beam_desc* bd, hipStream_t st) const { return ssc_beam_first_fsm(bd, st); }
+  int step(ssc_beam_desc* bd, int, hipStream_t st) const { return ssc_beam_step_sampled(bd, s, with_replacement, st); }
 };
 
 template <class Select>
@@ -266,10 +277,10 @@ extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, 
                                  size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !desc_ok(cfg, d)) return SSC_EINVAL;
-  const SearchLayout l = search_layout(cfg, d, false);
+  const SearchLayout l = search_layout(cfg, d, SEARCH_BEAM);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   char* W = (char*)workspace;
-  const bool use_parts = search_uses_parts(cfg, d, false);
+  const bool use_parts = search_uses_parts(cfg, d, SEARCH_BEAM);
   return search_run(cfg, p, d, l, W, BeamSelect{use_parts, (const float*)(W + l.parts)}, use_parts, (hipStream_t)stream);
 }
 
@@ -285,15 +296,39 @@ extern "C" size_t ssc_decode_stochastic_beam_workspace_bytes(const ssc_model_cfg
   if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
       d->R <= 0)
     return 0;
-  return search_layout(cfg, d, true).total;
+  return search_layout(cfg, d, SEARCH_GUMBEL).total;
 }
 
 extern "C" int ssc_decode_stochastic_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
                                           const ssc_gumbel_desc* s, void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);
   if (!p || !workspace || !sbs_search_ok(cfg, d, s)) return SSC_EINVAL;
-  const SearchLayout l = search_layout(cfg, d, true);
+  const SearchLayout l = search_layout(cfg, d, SEARCH_GUMBEL);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   char* W = (char*)workspace;
   return search_run(cfg, p, d, l, W, GumbelSelect{s, {(float*)(W + l.gs[0]), (float*)(W + l.gs[1])}}, false, (hipStream_t)stream);
+}
+
+// the sampled-node beam search: S = 1, no machine, the limits of ssc_beam_step_sampled
+static bool snb_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_sampler_desc* s) {
+  if (!desc_ok(cfg, d) || !s) return false;
+  if (d->S != 1 || d->fsm || d->tables || d->mach) return false;
+  return ssc_sampled_beam_ok(d->nimg * d->n_samples, d->beam, d->per_node, cfg->V, s);
+}
+
+extern "C" size_t ssc_decode_sampled_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
+      d->R <= 0)
+    return 0;
+  return search_layout(cfg, d, SEARCH_SAMPLED).total;
+}
+
+extern "C" int ssc_decode_sampled_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                       const ssc_sampler_desc* s, int with_replacement, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+  SscGemmModeScope mode_scope(cfg);
+  if (!p || !workspace || !snb_search_ok(cfg, d, s)) return SSC_EINVAL;
+  const SearchLayout l = search_layout(cfg, d, SEARCH_SAMPLED);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  return search_run(cfg, p, d, l, (char*)workspace, SampledSelect{s, with_replacement}, false, (hipStream_t)stream);
 }

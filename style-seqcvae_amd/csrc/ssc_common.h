@@ -137,5 +137,8 @@ struct SscGemmModeScope {
   ~SscGemmModeScope() { ssc_tls_gemm_mode = prev; ssc_tls_gemm_f16 = prev16; }
 };
 int ssc_decode_parts_enabled();        // the "dec_parts" switch (decode.hip): vocabulary head records instead of logits
+// the limits of the sampled-node beam search (sampled_beam.hip, include/ssc.h: ssc_beam_step_sampled) for B entries of k beams,
+// n candidates per beam over V tokens
+bool ssc_sampled_beam_ok(int B, int k, int n, int V, const ssc_sampler_desc* s);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

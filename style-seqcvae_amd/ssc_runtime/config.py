@@ -70,6 +70,11 @@ def _defaults() -> dict:
             # stochastic beam search (the reference's GumbelSampler, modules/beam_search.py:294-432): BEAM_SIZE captions sampled without
             # replacement per latent sample; needs DECODE_SAMPLER "beam" and no CBS; SAMPLER_TEMPERATURE applies
             "STOCHASTIC_BEAM_SEARCH": False,
+            # sampled-node beam search (the reference's BeamSearch with a word sampler, modules/beam_search.py:592-768): every beam
+            # draws BEAM_SIZE // 2 (or BEAM_SIZE) candidate words from DECODE_SAMPLER, the BEAM_SIZE best by log-prob are kept; needs
+            # DECODE_SAMPLER multinomial / top-k / top-p, STOCHASTIC_BEAM_SEARCH False and no CBS.  SAMPLER_WITH_REPLACEMENT: the
+            # samplers' with_replacement (the draws of one beam may repeat a word)
+            "SAMPLED_BEAM_SEARCH": False, "SAMPLER_WITH_REPLACEMENT": False,
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,

@@ -290,12 +290,46 @@ class DecodeEngine:
         (sampling.GumbelSampler) with the 64-bit `seed`, per_node candidates per beam.  sentiment (B) or None; eps0 (B, Z),
         eps (max_steps - 1, B*beam, Z): the noise of every step.
         -> (predictions (B, beam, steps) int64, log_probs (B, beam): summed untempered log-probs, descending)."""
+        if not 1 <= per_node <= beam <= min(32, self.dims.V):
+            raise ValueError(f"stochastic beam search needs 1 <= per_node <= beam <= min(32, V), got per_node {per_node}, beam {beam}")
+        gdesc = sampler.desc(seed)
+        return self._beam_call(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                               self.lib.ssc_decode_stochastic_beam_workspace_bytes,
+                               lambda p, sd, ws: self.lib.ssc_decode_stochastic_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
+                                                                                     C.byref(gdesc), *ws))
+
+    def sampled_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
+                     max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
+                     early_stop: bool = True, skip_dead: bool = True):
+        """The whole sampled-node beam search of one call in ONE library call (ssc_decode_sampled_beam): the reference's BeamSearch
+        driven by a word sampler (ssc_runtime.sampling: multinomial / top-k / top-p) - step 0 takes the top `beam` tokens, every
+        later step draws per_node candidates per beam (with or without replacement, sampler.with_replacement) with the 64-bit
+        `seed` and keeps the `beam` best by summed log-prob.  ctx.nimg images x n_samples latent samples, batch entry
+        b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*beam, Z): the noise of every step.
+        -> (predictions (B, beam, steps) int64, log_probs (B, beam): summed untempered log-probs, descending - beam 0 the best)."""
+        V = self.dims.V
+        if sampler.beam_search:
+            raise ValueError("the sampled-node beam search takes a word sampler (multinomial / top-k / top-p); the Gumbel sampler "
+                             "runs as DecodeEngine.stochastic_beam")
+        if not (1 <= beam <= min(32, V) and 1 <= per_node <= min(32, V)):
+            raise ValueError(f"sampled beam search needs 1 <= beam, per_node <= min(32, V), got beam {beam}, per_node {per_node}")
+        if sampler.kind == 1 and not per_node <= sampler.k <= V:   # (beam_search.py:180-183)
+            raise ValueError("k must be a postive integer no less than per_node_beam_size and no greater than vocabulary size")
+        sdesc = sampler.desc(seed)
+        rep = 1 if sampler.with_replacement else 0
+        return self._beam_call(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                               self.lib.ssc_decode_sampled_beam_workspace_bytes,
+                               lambda p, sd, ws: self.lib.ssc_decode_sampled_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
+                                                                                  C.byref(sdesc), rep, *ws))
+
+    def _beam_call(self, ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                   workspace_bytes, call):
+        """The shared body of the one-call searches on the trivial machine: the search descriptor, outputs, host flag and
+        workspace; call(params, desc, (workspace, bytes, stream)) issues the library call."""
         d = self.dims
         B = ctx.nimg * n_samples
         G = B * beam
         dev = self.device
-        if not 1 <= per_node <= beam <= min(32, d.V):
-            raise ValueError(f"stochastic beam search needs 1 <= per_node <= beam <= min(32, V), got per_node {per_node}, beam {beam}")
         sd = _lib.SearchDesc()
         sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
         sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = 1, beam, per_node, max_steps, end_index
@@ -319,14 +353,12 @@ class DecodeEngine:
             flag, flag_dev = _host_flag()
             if flag_dev is not None:
                 sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
-        nbytes = self.lib.ssc_decode_stochastic_beam_workspace_bytes(C.byref(self._cfg), C.byref(sd))
+        nbytes = workspace_bytes(C.byref(self._cfg), C.byref(sd))
         if self._sws is None or self._sws.numel() < nbytes:
             self._sws = None   # (release before growing)
             self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         p = self._params()
-        gdesc = sampler.desc(seed)
-        self.lib.ssc_decode_stochastic_beam(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(gdesc), _lib.ptr(self._sws),
-                                            self._sws.numel(), _lib.stream_ptr())
+        call(p, sd, (_lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr()))
         nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call)
         if flag is not None:
             _HOST_FLAGS.append(flag)

@@ -22,7 +22,7 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
                    num_constraints: Optional[torch.Tensor] = None, min_constraints_to_satisfy: int = 0,
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
-                   sample_seed: Optional[int] = None):
+                   sample_seed: Optional[int] = None, sampled_beam: bool = False):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     fsm: None (trivial one-state machine, what MAX_GIVEN_CONSTRAINTS: 0 produces), or (nimg, S, S, V) uint8 - ONE machine per
     image, shared by its n_samples latent samples through an index list -, or (nimg*n_samples, S, S, V) (a copy per sample).
@@ -40,11 +40,20 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     beam 0 - the sampled caption with the highest log-prob - of every (image, sample) is returned; needs fsm = None.
     sample_seed: the 64-bit seed of the word draws; default: the call's one draw from the global generator (the seed of the
     latent noise as well; with eps_steps given, one draw is made for the words), so a sampled call consumes the global random
-    state as a beam call does and sees the same latent noise as a beam-1 call."""
+    state as a beam call does and sees the same latent noise as a beam-1 call.
+    sampled_beam: with a word sampler, run it as the reference's BeamSearch does (DecodeEngine.sampled_beam) at any beam: step 0
+    takes the top `beam` words, every later step draws per_node (default beam // 2, or beam) candidates per beam and keeps the
+    `beam` best by summed log-prob; beam 0 of every (image, sample) is returned; needs fsm = None."""
     gumbel = sampler is not None and sampler.beam_search
+    if sampled_beam:
+        if sampler is None or gumbel:
+            raise ValueError("sampled_beam needs a word sampler (multinomial / top-k / top-p)")
+        if fsm is not None:
+            raise ValueError("the sampled-node beam search does not take constraints (fsm): constrained sampling is not supported")
+    words = sampler is not None and not gumbel and not sampled_beam
     if gumbel and fsm is not None:
         raise ValueError("the stochastic beam search does not take constraints (fsm): constrained sampling is not supported")
-    if sampler is not None and not gumbel:
+    if words:
         if beam != 1:
             raise ValueError(f"word sampling draws one word per row: beam must be 1, got {beam}")
         if fsm is not None:
@@ -88,6 +97,11 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
             gen.manual_seed(seed)
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
+        if sampled_beam:
+            beams, lps = dec.sampled_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
+                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, skip_dead=skip_now)
+            calls["k"] = beams.size(-1)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
         if gumbel:
             beams, lps = dec.stochastic_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
                                              seed if sample_seed is None else sample_seed, early_stop=early_stop, skip_dead=skip_now)

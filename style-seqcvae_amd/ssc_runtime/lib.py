@@ -227,6 +227,10 @@ SYMBOLS = {
     "ssc_decode_stochastic_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_stochastic_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(GumbelDesc), vp, _sz,
                                         vp]),
+    "ssc_beam_step_sampled": (_i, [C.POINTER(BeamDesc), C.POINTER(SamplerDesc), _i, vp]),
+    "ssc_decode_sampled_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
+    "ssc_decode_sampled_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), _i, vp,
+                                     _sz, vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)

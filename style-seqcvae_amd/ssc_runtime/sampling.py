@@ -3,9 +3,11 @@
 
 Reference: MultinomialSampler, TopKSampler, TopPSampler (var_updown/var_updown/modules/beam_search.py:103-293) - same constructor
 signatures and argument checks.  The reference draws with torch.multinomial; here the draw is Gumbel-max over the kept set with
-counter-based Philox4x32-10 noise keyed by a 64-bit seed: the same distribution, reproducible bit for bit.  One draw per row
-(beam 1, per_node_beam_size 1), so `with_replacement` has no effect.  Top-p keeps every token at p = 1 (the reference's fp32
-cumsum can fall short of 1 and drop tail tokens there).
+counter-based Philox4x32-10 noise keyed by a 64-bit seed: the same distribution, reproducible bit for bit.  The word decode
+(DecodeEngine.sample / ssc_decode_sample) makes one draw per row (beam 1, per_node_beam_size 1), where `with_replacement` has no
+effect; the sampled-node beam search (DecodeEngine.sampled_beam / ssc_decode_sampled_beam, MODEL.SAMPLED_BEAM_SEARCH) draws
+per_node candidates per beam at any beam, with or without replacement as `with_replacement` says.  Top-p keeps every token at
+p = 1 (the reference's fp32 cumsum can fall short of 1 and drop tail tokens there).
 
 GumbelSampler (beam_search.py:294-432) is the stochastic beam search: `beam` captions per batch entry without replacement, at any
 beam (DecodeEngine.stochastic_beam / ssc_decode_stochastic_beam).
@@ -112,22 +114,39 @@ class GumbelSampler(Sampler):
 
 
 def from_config(model_cfg):
-    """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / STOCHASTIC_BEAM_SEARCH
-    describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER "beam" gives
-    GumbelSampler(SAMPLER_TEMPERATURE)."""
+    """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
+    STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
+    "beam" gives GumbelSampler(SAMPLER_TEMPERATURE).  Checks MODEL.SAMPLED_BEAM_SEARCH (sampled_beam_from_config)."""
     kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
     T = float(model_cfg.SAMPLER_TEMPERATURE)
     sbs = bool(getattr(model_cfg, "STOCHASTIC_BEAM_SEARCH", False))
+    rep = bool(getattr(model_cfg, "SAMPLER_WITH_REPLACEMENT", False))
+    sampled_beam_from_config(model_cfg)
     if sbs and kind != "beam":
         raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
                          "samplers draw one word per row; the stochastic beam search is a kind of beam search)")
     if kind == "beam":
         return GumbelSampler(temperature=T) if sbs else None
     if kind == "multinomial":
-        return MultinomialSampler(temperature=T)
+        return MultinomialSampler(temperature=T, with_replacement=rep)
     if kind == "top-k":
-        return TopKSampler(k=int(model_cfg.SAMPLER_TOP_K), temperature=T)
+        return TopKSampler(k=int(model_cfg.SAMPLER_TOP_K), temperature=T, with_replacement=rep)
     if kind == "top-p":
-        return TopPSampler(p=float(model_cfg.SAMPLER_TOP_P), temperature=T)
+        return TopPSampler(p=float(model_cfg.SAMPLER_TOP_P), temperature=T, with_replacement=rep)
     raise ValueError(f"MODEL.DECODE_SAMPLER must be one of 'beam', 'multinomial', 'top-k', 'top-p', got {model_cfg.DECODE_SAMPLER!r} "
                      "(for the Gumbel / stochastic beam sampler set MODEL.STOCHASTIC_BEAM_SEARCH True with DECODE_SAMPLER 'beam')")
+
+
+def sampled_beam_from_config(model_cfg) -> bool:
+    """MODEL.SAMPLED_BEAM_SEARCH: run the word sampler as the reference's BeamSearch does - per_node candidates per beam at
+    BEAM_SIZE (DecodeEngine.sampled_beam).  Needs DECODE_SAMPLER multinomial / top-k / top-p and STOCHASTIC_BEAM_SEARCH False."""
+    on = bool(getattr(model_cfg, "SAMPLED_BEAM_SEARCH", False))
+    if on:
+        kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+        if kind not in KINDS:
+            raise ValueError(f"MODEL.SAMPLED_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p', got "
+                             f"{model_cfg.DECODE_SAMPLER!r}")
+        if bool(getattr(model_cfg, "STOCHASTIC_BEAM_SEARCH", False)):
+            raise ValueError("MODEL.SAMPLED_BEAM_SEARCH and MODEL.STOCHASTIC_BEAM_SEARCH exclude each other (a word sampler's beam "
+                             "search or the Gumbel sampler's)")
+    return on

@@ -16,6 +16,7 @@ import torch
 from torch import nn
 
 from ssc_runtime import lib as _lib
+from ssc_runtime import sampling
 from ssc_runtime.cellops import cell_train_step
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.decoding import select_best_beam_with_constraints
@@ -56,7 +57,8 @@ class UpDownCaptioner(nn.Module):
     def __init__(self, vocabulary, image_feature_size, embedding_size, hidden_size, attention_projection_size,
                  max_caption_length=20, beam_size=1, use_cbs=False, min_constraints_to_satisfy=2, z_space=150,
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
-                 sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None):
+                 sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None,
+                 sampled_beam=False):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
@@ -65,12 +67,18 @@ class UpDownCaptioner(nn.Module):
         `sampler` (optional): a word sampler of ssc_runtime.sampling (MODEL.DECODE_SAMPLER) - the eval forward then draws every word
         on the device (ssc_decode_sample) instead of running beam search; needs beam_size 1 and no CBS decode.  Or
         sampling.GumbelSampler (MODEL.STOCHASTIC_BEAM_SEARCH): the eval forward runs the stochastic beam search at beam_size with
-        per_node_beam_size beam_size // 2 (beam_size when that is 0) in one library call and returns beam 0; no CBS decode."""
+        per_node_beam_size beam_size // 2 (beam_size when that is 0) in one library call and returns beam 0; no CBS decode.
+        `sampled_beam` (MODEL.SAMPLED_BEAM_SEARCH) with a word sampler: the eval forward runs the sampled-node beam search
+        (ssc_decode_sampled_beam: the reference's BeamSearch with that sampler) at beam_size, per_node_beam_size as above, and
+        returns beam 0."""
         super().__init__()
-        if sampler is not None and not sampler.beam_search and beam_size != 1:
+        if sampled_beam and (sampler is None or sampler.beam_search):
+            raise ValueError("MODEL.SAMPLED_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p'")
+        if sampler is not None and not sampler.beam_search and not sampled_beam and beam_size != 1:
             raise ValueError(f"MODEL.BEAM_SIZE must be 1 with MODEL.DECODE_SAMPLER {sampler.name!r} (word sampling draws one word per "
                              f"row), got {beam_size}")
         self.sampler = sampler
+        self.sampled_beam = bool(sampled_beam)
         self._vocabulary = vocabulary
         self.image_feature_size = image_feature_size
         self.embedding_size = embedding_size
@@ -139,7 +147,9 @@ class UpDownCaptioner(nn.Module):
     @classmethod
     def from_config(cls, config, **kwargs):
         """Instantiate from a Config (updown_captioner.py:141-166); extra kwargs such as cbs_simple are ignored as in
-        the reference.  mean_choice=... (SENTIMENT_VAE = 2) is handed to the constructor."""
+        the reference.  mean_choice=... (SENTIMENT_VAE = 2) is handed to the constructor.  MODEL.SAMPLED_BEAM_SEARCH is read only
+        with a sampler=... (the decode's); a model built without one (scripts/train.py) ignores it, as it ignores the other
+        decode keys."""
         _C = config
         return cls(vocabulary=kwargs.pop("vocabulary"), image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
                    embedding_size=_C.MODEL.EMBEDDING_SIZE, hidden_size=_C.MODEL.HIDDEN_SIZE,
@@ -149,7 +159,8 @@ class UpDownCaptioner(nn.Module):
                    prior_std=_C.MODEL.PRIOR_STD, simple_vae=_C.MODEL.SIMPLE_VAE, latent_embedding=_C.MODEL.LATENT_EMBEDDING,
                    sentiment_vae=_C.MODEL.SENTIMENT_VAE, senti_prior_multip=_C.MODEL.SENTI_PRIOR_MULTIP,
                    latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
-                   device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"))
+                   device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
+                   sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL))
 
     def _initialize_glove(self):
         """GloVe 42B (+ dependency embeddings for 600-d) rows for the vocabulary (updown_captioner.py:168-226).
@@ -311,18 +322,20 @@ class UpDownCaptioner(nn.Module):
         """Eval forward with a word sampler: the whole decode in one library call (DecodeEngine.sample).  The latent noise is drawn
         for every step up front from the same source as the beam path's (one (B, Z) draw per step); the word seed is one draw from
         the global generator.  With the Gumbel sampler: the stochastic beam search (DecodeEngine.stochastic_beam), noise drawn as
-        the beam path draws it ((B, Z) for the first step, (B * beam, Z) for every later one), beam 0 returned."""
+        the beam path draws it ((B, Z) for the first step, (B * beam, Z) for every later one), beam 0 returned; the sampled-node
+        beam search (sampled_beam, DecodeEngine.sampled_beam) likewise."""
         B = image_features.size(0)
         L = self._max_caption_length
         dev = self._eng.device
         ctx = self._image_context(image_features, obj_means)
-        if self.sampler.beam_search:
+        if self.sampler.beam_search or self.sampled_beam:
             k = self._beam_search.beam_size
             eps0 = self._draw_eps(1, B, dev)[0]
             eps = self._draw_eps(L - 1, B * k, dev) if L > 1 else None
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             sent = sentiment.reshape(B) if sentiment is not None else None
-            beams, _ = self._dec.stochastic_beam(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.sampler, seed)
+            run = self._dec.sampled_beam if self.sampled_beam else self._dec.stochastic_beam
+            beams, _ = run(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.sampler, seed)
             return beams[:, 0, :]
         eps = self._draw_eps(L, B, dev)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())

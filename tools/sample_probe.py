@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """Time of the sampled decode (ssc_decode_sample) against the beam-1 and beam-5 searches (ssc_decode_search) at the bench's decode
 shape - 100 images x 20 latent samples per call, 36 x 2048 features, V 10 000, H 1200, max 20 steps, early stop off so every call
-runs all its steps -, the stochastic beam search at beam 5 (ssc_decode_stochastic_beam), and of the row sampler alone (sample_rows_kernel through ssc_sample_rows) on (G, V) logits, with its
-logits bytes / time against one HBM pass.
+runs all its steps -, the stochastic beam search at beam 5 (ssc_decode_stochastic_beam), the sampled-node beam search at beam 5,
+per-node 2 for each word sampler with and without replacement (ssc_decode_sampled_beam), and of the selections alone
+(sample_rows_kernel through ssc_sample_rows, ssc_beam_step_gumbel, ssc_beam_step_sampled) on (G, V) logits, with their logits
+bytes / time against one HBM pass.
     python tools/sample_probe.py [calls]
 Prints one JSON line."""
 import json
@@ -57,6 +59,14 @@ def main():
                                 ("stochastic_beam5", 5, sampling.GumbelSampler())):
         ms = timed(lambda: diverse_decode(dec, feats, senti, n_z, beam, steps, 1, early_stop=False, sampler=sampler), calls)
         out[name] = {"ms_per_call": ms, "us_per_step": ms * 1e3 / steps}
+    for name, mk in (("multinomial", lambda r: sampling.MultinomialSampler(with_replacement=r)),
+                     ("top_k_40", lambda r: sampling.TopKSampler(k=40, with_replacement=r)),
+                     ("top_p_0.9", lambda r: sampling.TopPSampler(p=0.9, with_replacement=r))):
+        for r in (False, True):
+            sampler = mk(r)
+            ms = timed(lambda: diverse_decode(dec, feats, senti, n_z, 5, steps, 1, early_stop=False, sampler=sampler, sampled_beam=True),
+                       calls)
+            out[f"sampled_beam5_{name}_{'with' if r else 'without'}_replacement"] = {"ms_per_call": ms, "us_per_step": ms * 1e3 / steps}
     # the row sampler alone on (G, V) logits
     lib = L.load()
     G, V = images * n_z, c["V"]
@@ -85,6 +95,12 @@ def main():
     gd = sampling.GumbelSampler().desc(7)
     us = timed(lambda: lib.ssc_beam_step_gumbel(bd, gd, L.ptr(bufs[7]), L.ptr(bufs[8]), L.stream_ptr()), 20) * 1e3
     out["row_kernel"]["stochastic_beam_step"] = {"G": Gs, "us": us, "GBps": Gs * V * 4 / us / 1e3}
+    # the sampled-node beam search's selection alone (row kernel + merge, ssc_beam_step_sampled), same logits, beam 5, per-node 2
+    for name, s, r in (("multinomial", sampling.MultinomialSampler(), 0), ("multinomial_with_replacement", sampling.MultinomialSampler(), 1),
+                       ("top_k_40", sampling.TopKSampler(k=40), 0), ("top_p_0.9", sampling.TopPSampler(p=0.9), 0)):
+        sd = s.desc(7)
+        us = timed(lambda: lib.ssc_beam_step_sampled(bd, sd, r, L.stream_ptr()), 20) * 1e3
+        out["row_kernel"][f"sampled_beam_step_{name}"] = {"G": Gs, "us": us, "GBps": Gs * V * 4 / us / 1e3}
     del big
     # one HBM pass over the same bytes (a device copy reads and writes them: half its time is the read)
     dst = torch.empty_like(logits)
