@@ -2,6 +2,11 @@
 """Headline benchmark: captions/sec of one Style-SeqCVAE (var_updown) train step on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N=1 directly; N>1 under torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (+ decode legs, rooflines, exact-fp32 mode, C5, CPU baseline)
+
+A plain run sets up, brings the GPU out of idle, warms up, times the K steps, writes --dump-outputs and prints the result line;
+every other leg runs only with --full (after the timed steps and the dump, except the decode legs, which run before them on the
+random-init weights and leave the train step's inputs as they are).
 
 A "step" = one pass of the hot path over one minibatch per GPU: fused T-step forward + BPTT (HIP kernels behind
 libssc_hip.so) + RCCL all-reduce of the flat gradient buffer + clip_grad_norm + SGD(momentum, wd)
@@ -527,6 +532,141 @@ def measure_c5_train(device, steps=5, warmup=2):
             "roofline": roof}
 
 
+def train_roofline(eng, batches, c, device, dump_gemm):
+    """--full: in-situ hipEvent timing of every GEMM launch over 2 further steps (forward + backward, no update) and of the
+    T-step time loops alone -> the `roofline*` and `gemm_time_ms_per_step` entries of the result line."""
+    from ssc_runtime import lib as L
+    lib = L.load()
+    nprof = 2
+    B = c["B"]
+    # (a) the T-step time loops alone (hipEvent pair around the loop inside ssc_train_fwd / ssc_train_bwd; no other
+    #     instrumentation active): the fused attention+LSTM step of SURVEY 8(d) is loop time / T
+    import ctypes as _C
+    lib.ssc_prof_loop_enable(1)
+    fwd_loop_ms, bwd_loop_ms = [], []
+    for i in range(3):
+        feats, caps, senti, eps = batches[i % len(batches)]
+        eng.forward(feats, caps, senti, eps)
+        eng.backward(torch.full((B,), 1.0 / B, device=device), torch.full((B,), 1.0 / (B * 750.0), device=device))
+        f_ms, b_ms = _C.c_float(), _C.c_float()
+        lib.ssc_prof_loop_ms(_C.byref(f_ms), _C.byref(b_ms))
+        fwd_loop_ms.append(f_ms.value)
+        bwd_loop_ms.append(b_ms.value)
+    lib.ssc_prof_loop_enable(0)
+    # (b) a hipEvent pair around every GEMM launch of two further steps
+    lib.ssc_prof_enable(1)
+    for i in range(nprof):
+        feats, caps, senti, eps = batches[i % len(batches)]
+        eng.forward(feats, caps, senti, eps)
+        torch.cuda.synchronize()
+        eng.backward(torch.full((B,), 1.0 / B, device=device), torch.full((B,), 1.0 / (B * 750.0), device=device))
+    buf = torch.zeros(4096 * 8, dtype=torch.float32)
+    n = lib.ssc_prof_collect(buf.data_ptr(), 4096)
+    lib.ssc_prof_enable(0)
+    rec = buf[: n * 8].view(n, 8)   # kind, M, N, K, splits, ms, algorithmic bytes, flops (exact also for grouped launches)
+    names = {0: "gemm_kernel<NT> (forward: x W^T)", 1: "gemm_kernel<NN> (backward: dG W)", 3: "gemm_kernel<TN> (dW = dG^T X)"}
+    agg = {}
+    for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
+        a = agg.setdefault(int(kind), dict(ms=0.0, flops=0.0, bytes=0.0, n=0))
+        a["ms"] += msr
+        a["flops"] += rflops
+        a["bytes"] += rbytes
+        a["n"] += 1
+    if dump_gemm:
+        shapes = {}
+        for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
+            e = shapes.setdefault((int(kind), int(M), int(N), int(K), int(splits)), [0, 0.0, rbytes, rflops])
+            e[0] += 1
+            e[1] += msr
+        with open(dump_gemm, "w") as f:
+            f.write("kind,M,N,K,splits,calls_per_step,avg_us,total_ms_per_step,TFLOPs,algGBps\n")
+            for (kind, M, N, K, sp), (cnt, tot, rbytes, rflops) in sorted(shapes.items(), key=lambda kv: -kv[1][1]):
+                us = tot / cnt * 1e3
+                f.write(f"{names[kind][12:14]},{M},{N},{K},{sp},{cnt / nprof:.1f},{us:.1f},{tot / nprof:.3f},"
+                        f"{rflops / us / 1e6:.1f},{rbytes / us / 1e3:.0f}\n")
+    # Two regimes (DESIGN.md "GEMM"): the per-timestep MINIBATCH products (M = B rows against a wide weight matrix,
+    # forward x W^T and backward dG W) stream every weight once per launch -> HBM-bound; the LARGE products over the
+    # (t, b) rows (hoisted gate terms, vocabulary head, weight gradients) are bound by the bf16 matrix pipe, on which
+    # the 3xBF16 kernels spend six MFMA passes per fp32 product.
+    fam = {"minibatch": dict(ms=0.0, bytes=0.0, flops=0.0, n=0), "large": dict(ms=0.0, bytes=0.0, flops=0.0, n=0)}
+    for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
+        f = fam["minibatch" if M <= c["B"] else "large"]
+        f["ms"] += msr
+        f["bytes"] += rbytes          # algorithmic: every operand and the result once (summed over a group's members)
+        f["flops"] += rflops
+        f["n"] += 1
+    pm = {}
+    try:  # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/)
+        pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")))["kernels"]
+    except Exception:
+        pm = {}
+
+    def traffic_of(prefixes):
+        sel = [v for k, v in pm.items() if any(k.startswith(f) for f in prefixes)]
+        if not sel:
+            return None
+        return sum(v["hbm_bytes_per_launch"] * v["launches"] for v in sel) / max(1, sum(v["launches"] for v in sel))
+
+    mb, lg = fam["minibatch"], fam["large"]
+    total_gemm_ms = mb["ms"] + lg["ms"]
+    gbs = mb["bytes"] / (mb["ms"] * 1e-3) / 1e9
+    roof_mb = {"bound": "hbm", "kernel": "minibatch GEMMs (M = B: gemm_x3w_kernel<64x256>, gemm_x3_kernel<64x64>, gemm_kernel<64x64>)",
+               "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
+               "traffic": traffic_of(("gemm_x3w_kernel<NT,64x256", "gemm_x3w_kernel<NN,64x256", "gemm_x3_kernel", "gemm_kernel<NN,64x", "gemm_kernel<NT,64x")),
+               "algorithmic_bytes_per_launch": mb["bytes"] / max(1, mb["n"]), "launches_per_step": mb["n"] / nprof,
+               "avg_launch_us": mb["ms"] / max(1, mb["n"]) * 1e3, "share_of_gemm_time": mb["ms"] / total_gemm_ms}
+    tf6 = 6.0 * lg["flops"] / (lg["ms"] * 1e-3) / 1e12
+    roof_lg = {"bound": "mfma", "kernel": "large 3xBF16 GEMMs (128x128 tiles: wave-specialised gemm_x3w_kernel from 768 workgroups on "
+               "and for the grouped weight gradients, 4-wave gemm_x3b_kernel below; 6 bf16 MFMA passes per fp32 product; "
+               "TRUE flops: products with device-side row compaction are priced on the rows / k-rows they processed, the counts "
+               "read back behind each launch)",
+               "achieved": tf6, "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s", "frac": tf6 / MFMA_BF16_PEAK_TF,
+               "traffic": traffic_of(("gemm_x3b_kernel", "gemm_x3w_kernel<NT,128", "gemm_x3w_kernel<NN,128", "gemm_x3w_kernel<TN,128")),
+               "fp32_equivalent_TFLOPs": lg["flops"] / (lg["ms"] * 1e-3) / 1e12, "launches_per_step": lg["n"] / nprof,
+               "avg_launch_us": lg["ms"] / max(1, lg["n"]) * 1e3, "share_of_gemm_time": lg["ms"] / total_gemm_ms}
+    # the single dominant kernel: the wave-specialised 64x256 minibatch kernel in its two layouts (NT: forward x W^T,
+    # NN: backward dG W; N >= 1024) - algorithmic bytes per launch / average launch duration, both from the events
+    dom = {}
+    for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
+        if M <= c["B"] and N >= 1024 and int(kind) in (0, 1):
+            e = dom.setdefault(int(kind), dict(ms=0.0, bytes=0.0, n=0))
+            e["ms"] += msr
+            e["bytes"] += rbytes
+            e["n"] += 1
+    roof_dom = None
+    if dom:
+        kd = max(dom, key=lambda k: dom[k]["ms"])
+        e = dom[kd]
+        nm = "gemm_x3w_kernel<%s,64x256>" % ("NT" if kd == 0 else "NN")
+        g2 = e["bytes"] / (e["ms"] * 1e-3) / 1e9
+        roof_dom = {"bound": "hbm", "kernel": nm + (" (forward x W^T gate products)" if kd == 0 else " (backward dG W products)"),
+                    "achieved": g2, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": g2 / HBM_PEAK_GBS,
+                    "traffic": traffic_of((nm,)), "algorithmic_bytes_per_launch": e["bytes"] / e["n"],
+                    "launches_per_step": e["n"] / nprof, "avg_launch_us": e["ms"] / e["n"] * 1e3,
+                    "share_of_gemm_time": e["ms"] / total_gemm_ms}
+    roofline, roofline_other = (roof_mb, roof_lg) if mb["ms"] >= lg["ms"] else (roof_lg, roof_mb)
+    if roof_dom is not None and roofline is roof_mb:
+        roof_all_mb, roofline = roof_mb, roof_dom      # `roofline` = the dominant kernel; the family total stays beside it
+    else:
+        roof_all_mb = None
+    # the recurrent (per-timestep) gate GEMMs of the fused attention+LSTM step: NT launches with M == B, N == 4H
+    step_recs = [r for r in rec.tolist() if int(r[0]) == 0 and int(r[1]) == c["B"] and int(r[2]) == 4 * c["H"]]
+    T = c["L"] + 1
+    fused = fused_step_bytes(c)
+    fwd_step_us = sorted(fwd_loop_ms)[len(fwd_loop_ms) // 2] / T * 1e3   # the time loop alone, median of 3 calls
+    bwd_step_us = sorted(bwd_loop_ms)[len(bwd_loop_ms) // 2] / T * 1e3
+    roofline_step = {"bound": "hbm", "scope": "fused attention+LSTM step (SURVEY 8(d): rows #7-#11, excl. the vocabulary head "
+                     "and the hoisted per-sequence terms), forward: time of the T-step loop of ssc_train_fwd / T (hipEvent pair "
+                     "around the loop, no other instrumentation)", "achieved": fused / (fwd_step_us * 1e-6) / 1e9,
+                     "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": fused / (fwd_step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                     "algorithmic_bytes_per_step": fused, "us_per_step": fwd_step_us,
+                     "gate_gemm_us_per_step_with_event_overhead": sum(r[5] for r in step_recs) / nprof / T * 1e3,
+                     "bptt_us_per_step": bwd_step_us}
+    return {"roofline": roofline,
+            "roofline_large_gemm" if roofline_other is roof_lg else "roofline_minibatch_gemm": roofline_other,
+            "roofline_all_minibatch_gemms": roof_all_mb, "roofline_step": roofline_step,
+            "gemm_time_ms_per_step": {names[k]: agg[k]["ms"] / nprof for k in agg}}
+
 def bench_decode(args, model, eng, c, rank, world, device):
     import torch.distributed as dist
     if args.mode == "decode-cbs":
@@ -538,6 +678,26 @@ def bench_decode(args, model, eng, c, rank, world, device):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+GPU_WARM_S = 5.0   # untimed forward + backward work of a plain run before its warm-up steps
+
+
+def warm_gpu(eng, batches, B, device, seconds):
+    """Bring the GPU out of idle without changing what the timed steps compute: forward + backward passes of the train step
+    for `seconds` (the decode legs of --full do this for the steps behind them).  The backward overwrites the gradients and
+    neither touches the parameters, the momentum nor the generator of the steps' noise."""
+    gl = torch.full((B,), 1.0 / B, device=device)
+    gk = torch.full((B,), 1.0 / (B * 750.0), device=device)
+    t0 = time.perf_counter()
+    i = 0
+    while time.perf_counter() - t0 < seconds:
+        eng.forward(*batches[i % len(batches)])
+        eng.backward(gl, gk)
+        if i % 16 == 15:
+            torch.cuda.synchronize()
+        i += 1
+    torch.cuda.synchronize()
 
 
 DUMP_SAMPLE = 1 << 22   # elements sampled from each of the parameter and gradient stores: 16 MB each
@@ -565,18 +725,21 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="train mode: besides the headline, the decode legs, the rooflines, the exact-fp32 mode, the C5 train step and "
+                         "the CPU baseline (a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--batch", type=int, default=C2["B"])
     ap.add_argument("--mode", default="train", choices=["train", "decode", "decode-cbs"],
                     help="train: headline captions/sec (default); decode: C4 diverse-decode tokens/sec")
     ap.add_argument("--images", type=int, default=1000, help="decode mode: synthetic images in total")
     ap.add_argument("--cbs-legs", default="all", choices=["all", "compiled"],
                     help="decode-cbs mode: all = compiled machines, the dense A/B and the selection step alone; compiled = the product path only")
-    ap.add_argument("--dump-gemm", default="", help="write the per-shape GEMM timing table (roofline leg) to this file")
+    ap.add_argument("--dump-gemm", default="", help="--full: write the per-shape GEMM timing table (roofline leg) to this file")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="train mode: after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32): "
                          "loss and kld per caption, and a fixed seeded sample of the updated parameters and of the gradients")
-    ap.add_argument("--no-decode", action="store_true", help="skip the short decode leg of the default run")
+    ap.add_argument("--no-decode", action="store_true", help="--full: skip the decode legs that run before the train steps")
     ap.add_argument("--dp-algo", default="rccl", choices=["auto", "rccl", "xgmi"],
                     help="gradient exchange at N > 1: rccl (default) = torch.distributed all-reduce; xgmi = direct reduce-scatter + "
                          "all-gather over hipIpc peer mappings (csrc/collective.hip); auto = verify the direct path against RCCL at start-up "
@@ -584,8 +747,8 @@ def main():
                          "The direct path has never run across two devices in any record of this repository (no multi-GPU node was "
                          "available to the build), so it is opt-in until one such run exists")
     ap.add_argument("--prewarm", type=int, default=150,
-                    help="untimed extra train steps before the W warm-up steps when no decode leg ran first (a GPU coming out of "
-                         "idle needs > 1 s to reach its sustained state); 0 for the profiler passes")
+                    help="--timed-only and --full --no-decode: untimed extra train steps before the W warm-up steps (a GPU coming "
+                         "out of idle needs > 1 s to reach its sustained state); 0 for the profiler passes")
     ap.add_argument("--timed-only", action="store_true",
                     help="only the timed train steps (no roofline / attention / decode / CPU legs): what the rocprofv3 passes run, "
                          "so that every profiled launch belongs to the C2 train step")
@@ -594,6 +757,8 @@ def main():
         ap.error("--steps: at least one timed step")
     if args.dump_outputs and args.mode != "train":
         ap.error("--dump-outputs: train mode only")
+    if args.full and args.timed_only:
+        ap.error("--full and --timed-only exclude each other")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -623,7 +788,6 @@ def main():
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
 
-    from ssc_runtime import lib as L
     from ssc_runtime.vocab import Vocabulary
     from var_updown.models import UpDownCaptioner
 
@@ -642,11 +806,12 @@ def main():
     # (1000 images per rank = 20 beam-search calls of 5000 rows), reported in the same JSON line.  It runs FIRST, on the
     # random-init weights C4 is defined on (BOUNDARY is then rarely emitted, so the searches run their full
     # length; after a few SGD steps on synthetic captions the model emits BOUNDARY at once).
+    decode_legs = args.full and not args.no_decode
     dres = None
-    if not args.timed_only and not args.no_decode:
+    if decode_legs:
         dres = measure_decode(model, c, rank, world, device, 1000 * world, 5)   # C4: 1000 images per GPU (>= 5 calls and >= 2 s of warm-up: the leg runs first, on a GPU coming out of idle)
     cbs_res = None
-    if rank == 0 and world == 1 and not args.timed_only and not args.no_decode:
+    if rank == 0 and world == 1 and decode_legs:
         cbs_res = measure_decode_cbs(model, c, device)
     batches = [synth_batch(1234 + rank + 100 * i, c["B"], c["R"], c["F"], c["L"], c["V"], c["Z"], device) for i in range(4)]
     total_iters = 70000
@@ -666,10 +831,12 @@ def main():
         return eng.train_step(feats, caps, senti, eps, lr=lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
                               max_norm=12.5, decoder_frozen=False)
 
-    if args.timed_only or args.no_decode:   # no decode leg ran before: bring the GPU out of idle first (same count on every rank: the steps all-reduce)
+    if args.timed_only or (args.full and args.no_decode):   # no decode leg ran before: bring the GPU out of idle first (same count on every rank: the steps all-reduce)
         for i in range(args.prewarm):
             step(i)
         torch.cuda.synchronize()
+    elif not args.full:
+        warm_gpu(eng, batches, c["B"], device, GPU_WARM_S)
     for i in range(args.warmup):
         step(i)
     if world > 1:
@@ -732,145 +899,16 @@ def main():
     elif rank == 0:
         ms = elapsed / args.steps * 1e3
         value = world * c["B"] * args.steps / elapsed
-        # ---- roofline leg: in-situ hipEvent timing of every GEMM launch over 2 further steps -----------------------
-        lib = L.load()
-        nprof = 2
-        B = c["B"]
-        # (a) the T-step time loops alone (hipEvent pair around the loop inside ssc_train_fwd / ssc_train_bwd; no other
-        #     instrumentation active): the fused attention+LSTM step of SURVEY 8(d) is loop time / T
-        import ctypes as _C
-        lib.ssc_prof_loop_enable(1)
-        fwd_loop_ms, bwd_loop_ms = [], []
-        for i in range(3):
-            feats, caps, senti, eps = batches[i % len(batches)]
-            eng.forward(feats, caps, senti, eps)
-            eng.backward(torch.full((B,), 1.0 / B, device=device), torch.full((B,), 1.0 / (B * 750.0), device=device))
-            f_ms, b_ms = _C.c_float(), _C.c_float()
-            lib.ssc_prof_loop_ms(_C.byref(f_ms), _C.byref(b_ms))
-            fwd_loop_ms.append(f_ms.value)
-            bwd_loop_ms.append(b_ms.value)
-        lib.ssc_prof_loop_enable(0)
-        # (b) a hipEvent pair around every GEMM launch of two further steps
-        lib.ssc_prof_enable(1)
-        for i in range(nprof):
-            feats, caps, senti, eps = batches[i % len(batches)]
-            eng.forward(feats, caps, senti, eps)
-            torch.cuda.synchronize()
-            eng.backward(torch.full((B,), 1.0 / B, device=device), torch.full((B,), 1.0 / (B * 750.0), device=device))
-        buf = torch.zeros(4096 * 8, dtype=torch.float32)
-        n = lib.ssc_prof_collect(buf.data_ptr(), 4096)
-        lib.ssc_prof_enable(0)
-        rec = buf[: n * 8].view(n, 8)   # kind, M, N, K, splits, ms, algorithmic bytes, flops (exact also for grouped launches)
-        names = {0: "gemm_kernel<NT> (forward: x W^T)", 1: "gemm_kernel<NN> (backward: dG W)", 3: "gemm_kernel<TN> (dW = dG^T X)"}
-        agg = {}
-        for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
-            a = agg.setdefault(int(kind), dict(ms=0.0, flops=0.0, bytes=0.0, n=0))
-            a["ms"] += msr
-            a["flops"] += rflops
-            a["bytes"] += rbytes
-            a["n"] += 1
-        if args.dump_gemm:
-            shapes = {}
-            for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
-                e = shapes.setdefault((int(kind), int(M), int(N), int(K), int(splits)), [0, 0.0, rbytes, rflops])
-                e[0] += 1
-                e[1] += msr
-            with open(args.dump_gemm, "w") as f:
-                f.write("kind,M,N,K,splits,calls_per_step,avg_us,total_ms_per_step,TFLOPs,algGBps\n")
-                for (kind, M, N, K, sp), (cnt, tot, rbytes, rflops) in sorted(shapes.items(), key=lambda kv: -kv[1][1]):
-                    us = tot / cnt * 1e3
-                    f.write(f"{names[kind][12:14]},{M},{N},{K},{sp},{cnt / nprof:.1f},{us:.1f},{tot / nprof:.3f},"
-                            f"{rflops / us / 1e6:.1f},{rbytes / us / 1e3:.0f}\n")
-        # Two regimes (DESIGN.md "GEMM"): the per-timestep MINIBATCH products (M = B rows against a wide weight matrix,
-        # forward x W^T and backward dG W) stream every weight once per launch -> HBM-bound; the LARGE products over the
-        # (t, b) rows (hoisted gate terms, vocabulary head, weight gradients) are bound by the bf16 matrix pipe, on which
-        # the 3xBF16 kernels spend six MFMA passes per fp32 product.
-        fam = {"minibatch": dict(ms=0.0, bytes=0.0, flops=0.0, n=0), "large": dict(ms=0.0, bytes=0.0, flops=0.0, n=0)}
-        for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
-            f = fam["minibatch" if M <= c["B"] else "large"]
-            f["ms"] += msr
-            f["bytes"] += rbytes          # algorithmic: every operand and the result once (summed over a group's members)
-            f["flops"] += rflops
-            f["n"] += 1
-        pm = {}
-        try:  # HBM-side bytes per launch from the committed rocprofv3 PMC passes (profiles/)
-            pm = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")))["kernels"]
-        except Exception:
-            pm = {}
-
-        def traffic_of(prefixes):
-            sel = [v for k, v in pm.items() if any(k.startswith(f) for f in prefixes)]
-            if not sel:
-                return None
-            return sum(v["hbm_bytes_per_launch"] * v["launches"] for v in sel) / max(1, sum(v["launches"] for v in sel))
-
-        mb, lg = fam["minibatch"], fam["large"]
-        total_gemm_ms = mb["ms"] + lg["ms"]
-        gbs = mb["bytes"] / (mb["ms"] * 1e-3) / 1e9
-        roof_mb = {"bound": "hbm", "kernel": "minibatch GEMMs (M = B: gemm_x3w_kernel<64x256>, gemm_x3_kernel<64x64>, gemm_kernel<64x64>)",
-                   "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": gbs / HBM_PEAK_GBS,
-                   "traffic": traffic_of(("gemm_x3w_kernel<NT,64x256", "gemm_x3w_kernel<NN,64x256", "gemm_x3_kernel", "gemm_kernel<NN,64x", "gemm_kernel<NT,64x")),
-                   "algorithmic_bytes_per_launch": mb["bytes"] / max(1, mb["n"]), "launches_per_step": mb["n"] / nprof,
-                   "avg_launch_us": mb["ms"] / max(1, mb["n"]) * 1e3, "share_of_gemm_time": mb["ms"] / total_gemm_ms}
-        tf6 = 6.0 * lg["flops"] / (lg["ms"] * 1e-3) / 1e12
-        roof_lg = {"bound": "mfma", "kernel": "large 3xBF16 GEMMs (128x128 tiles: wave-specialised gemm_x3w_kernel from 768 workgroups on "
-                   "and for the grouped weight gradients, 4-wave gemm_x3b_kernel below; 6 bf16 MFMA passes per fp32 product; "
-                   "TRUE flops: products with device-side row compaction are priced on the rows / k-rows they processed, the counts "
-                   "read back behind each launch)",
-                   "achieved": tf6, "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s", "frac": tf6 / MFMA_BF16_PEAK_TF,
-                   "traffic": traffic_of(("gemm_x3b_kernel", "gemm_x3w_kernel<NT,128", "gemm_x3w_kernel<NN,128", "gemm_x3w_kernel<TN,128")),
-                   "fp32_equivalent_TFLOPs": lg["flops"] / (lg["ms"] * 1e-3) / 1e12, "launches_per_step": lg["n"] / nprof,
-                   "avg_launch_us": lg["ms"] / max(1, lg["n"]) * 1e3, "share_of_gemm_time": lg["ms"] / total_gemm_ms}
-        # the single dominant kernel: the wave-specialised 64x256 minibatch kernel in its two layouts (NT: forward x W^T,
-        # NN: backward dG W; N >= 1024) - algorithmic bytes per launch / average launch duration, both from the events
-        dom = {}
-        for kind, M, N, K, splits, msr, rbytes, rflops in rec.tolist():
-            if M <= c["B"] and N >= 1024 and int(kind) in (0, 1):
-                e = dom.setdefault(int(kind), dict(ms=0.0, bytes=0.0, n=0))
-                e["ms"] += msr
-                e["bytes"] += rbytes
-                e["n"] += 1
-        roof_dom = None
-        if dom:
-            kd = max(dom, key=lambda k: dom[k]["ms"])
-            e = dom[kd]
-            nm = "gemm_x3w_kernel<%s,64x256>" % ("NT" if kd == 0 else "NN")
-            g2 = e["bytes"] / (e["ms"] * 1e-3) / 1e9
-            roof_dom = {"bound": "hbm", "kernel": nm + (" (forward x W^T gate products)" if kd == 0 else " (backward dG W products)"),
-                        "achieved": g2, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": g2 / HBM_PEAK_GBS,
-                        "traffic": traffic_of((nm,)), "algorithmic_bytes_per_launch": e["bytes"] / e["n"],
-                        "launches_per_step": e["n"] / nprof, "avg_launch_us": e["ms"] / e["n"] * 1e3,
-                        "share_of_gemm_time": e["ms"] / total_gemm_ms}
-        roofline, roofline_other = (roof_mb, roof_lg) if mb["ms"] >= lg["ms"] else (roof_lg, roof_mb)
-        if roof_dom is not None and roofline is roof_mb:
-            roof_all_mb, roofline = roof_mb, roof_dom      # `roofline` = the dominant kernel; the family total stays beside it
-        else:
-            roof_all_mb = None
-        # the recurrent (per-timestep) gate GEMMs of the fused attention+LSTM step: NT launches with M == B, N == 4H
-        step_recs = [r for r in rec.tolist() if int(r[0]) == 0 and int(r[1]) == c["B"] and int(r[2]) == 4 * c["H"]]
-        T = c["L"] + 1
-        fused = fused_step_bytes(c)
-        fwd_step_us = sorted(fwd_loop_ms)[len(fwd_loop_ms) // 2] / T * 1e3   # the time loop alone, median of 3 calls
-        bwd_step_us = sorted(bwd_loop_ms)[len(bwd_loop_ms) // 2] / T * 1e3
-        roofline_step = {"bound": "hbm", "scope": "fused attention+LSTM step (SURVEY 8(d): rows #7-#11, excl. the vocabulary head "
-                         "and the hoisted per-sequence terms), forward: time of the T-step loop of ssc_train_fwd / T (hipEvent pair "
-                         "around the loop, no other instrumentation)", "achieved": fused / (fwd_step_us * 1e-6) / 1e9,
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": fused / (fwd_step_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                         "algorithmic_bytes_per_step": fused, "us_per_step": fwd_step_us,
-                         "gate_gemm_us_per_step_with_event_overhead": sum(r[5] for r in step_recs) / nprof / T * 1e3,
-                         "bptt_us_per_step": bwd_step_us}
         result = {"metric": "captions/sec (train step)", "value": value, "unit": "captions/s", "n_gpus": world,
                   "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "higher_is_better": True,
                   "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                   "config": {"workload": "C2 train step: fwd+bwd+allreduce+clip+SGD, B=%d/GPU, R=36, F=2048, L=20 (T=21), "
                                          "Z=128, V=10000, E=1000, H=1200, A=768, SENTIMENT_VAE=1" % c["B"],
                              "global_batch": world * c["B"], "parallelism": f"dp{world}", "loss_probe": loss_probe},
-                  "roofline": roofline,
-                  "roofline_large_gemm" if roofline_other is roof_lg else "roofline_minibatch_gemm": roofline_other,
-                  "roofline_all_minibatch_gemms": roof_all_mb,
-                  "roofline_step": roofline_step, "data_parallel": dp_exposure,
-                  "gemm_time_ms_per_step": {names[k]: agg[k]["ms"] / nprof for k in agg}}
-        result["attention_roofline"] = attention_roofline(device)
+                  "data_parallel": dp_exposure}
+        if args.full:
+            result.update(train_roofline(eng, batches, c, device, args.dump_gemm))
+            result["attention_roofline"] = attention_roofline(device)
     if rank == 0 and dres is not None:
         result["decode_tokens_per_s"] = dres["value"]
         result["decode"] = {k: dres[k] for k in ("metric", "value", "unit", "steps", "ms_per_step", "config", "roofline", "captions_per_s",
@@ -880,7 +918,7 @@ def main():
                                   "operand on the bf16 matrix cores (six partial products of order <= 2, fp32 accumulate: error ~ one "
                                   "fp32 rounding per product), everything else exact fp32; exact_fp32_mode = the same step with every "
                                   "product on v_mfma_f32_32x32x2_f32 (ssc_model_cfg.gemm_mode 2)")
-    if rank == 0 and world == 1 and result is not None and not args.timed_only:
+    if rank == 0 and world == 1 and result is not None and args.full:
         # the same train step with every product on the exact-fp32 matrix instruction (per-engine numerics mode)
         eng._cfg.gemm_mode = 2
         try:
@@ -901,7 +939,7 @@ def main():
     if rank == 0 and cbs_res is not None:
         result["decode_cbs"] = cbs_res
     if rank == 0 and not args.timed_only:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(c)
         print(json.dumps(result), flush=True)
     if world > 1:
