@@ -769,6 +769,51 @@ size_t ssc_decode_sampled_beam_workspace_bytes(const ssc_model_cfg* cfg, const s
 int ssc_decode_sampled_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
                             int with_replacement, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Diverse-caption evaluation (eval/eval.py:95-472 with the coco-caption scorers it calls): BLEU-1..4 (BleuScorer, option
+ * "closest"), ROUGE-L (Rouge, beta 1.2) and CIDEr-D (CiderScorer, sigma 6) of every candidate; distinct 1- / 2-grams of every
+ * image's N captions and of its top 5 by CIDEr (Div-n), and style-word counts.  The reductions over candidates (oracle argmax,
+ * corpus BLEU, means) are the caller's.  Exact: n-grams are compared by their full word tuples; fp64 scores, integer counts;
+ * integer atomics only; two calls on the same inputs are bit-identical, and equal captions of one image score bit-equal.
+ * Reference words are compact ids 1..W, W <= 65535; a reference holds 1..64 tokens.  Both calls read a device error flag back,
+ * so they synchronise `stream` (not capturable): every out-of-range id, length or offset gives SSC_EINVAL, nothing is indexed
+ * with it.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int I;                     /* images: the evaluated set (CIDEr-D's document frequencies and log I run over it) */
+  int nref;                  /* reference captions, >= I */
+  int ntok;                  /* tokens over all references */
+  int W;                     /* compact word ids 1..W */
+  const int* ref_offsets;    /* (I + 1): the references of image i are ref_offsets[i] .. ref_offsets[i + 1] - 1 (at least one) */
+  const int* tok_offsets;    /* (nref + 1): the tokens of reference r are tokens[tok_offsets[r] .. tok_offsets[r + 1]) */
+  const int* tokens;         /* (ntok): compact ids 1..W */
+  const uint8_t* style;      /* optional (W + 1): 1 = a style word */
+  void* state;               /* ssc_eval_refs_bytes(I, nref, ntok) bytes, written by ssc_eval_prepare_refs and read by ssc_eval_score */
+  size_t state_bytes;
+} ssc_eval_refs;
+
+typedef struct {
+  const int64_t* predictions; /* (P, N, steps): a row is cut at its first boundary_index, else kept whole; at most 64 tokens */
+  int P, N, steps;            /* 1 <= N <= 128 */
+  int boundary_index;
+  int V;                      /* prediction ids 0..V-1, V <= 65535 */
+  const int* id_map;          /* (V): compact id of prediction id v, 0 = in no reference (the vocabulary's UNK maps to 0) */
+  const uint8_t* style_ids;   /* optional (V): 1 = a style word (the same words as ssc_eval_refs.style) */
+  const int* ref_image;       /* (P): the prepared image of prediction image p, or -1: Div-n counts only */
+  double* scores;             /* (P, N, 6): B1, B2, B3, B4, ROUGE-L, CIDEr-D (0 where ref_image is -1) */
+  int* counts;                /* (P, N, 10): testlen, reflen, guess[4], correct[4] (BleuScorer's statistics) */
+  int* image_counts;          /* (P, 9): distinct 1-grams, distinct 2-grams, words of the N captions; the same of the top 5;
+                               * candidate style words, those of them the references hold, reference style words */
+  int* top5;                  /* (P, 5): sample indices by CIDEr-D, stable descending; -1 where N < 5 or ref_image is -1 */
+} ssc_eval_score_desc;
+
+size_t ssc_eval_refs_bytes(int I, int nref, int ntok);   /* 0 for arguments out of range */
+/* n-grams, tf, document frequencies, weights and norms of the references (three kernels). */
+int ssc_eval_prepare_refs(const ssc_eval_refs* r, void* stream);
+size_t ssc_eval_score_workspace_bytes(const ssc_eval_refs* r, const ssc_eval_score_desc* d);
+/* every candidate's scores and statistics, then every image's counts (two kernels) */
+int ssc_eval_score(const ssc_eval_refs* r, const ssc_eval_score_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,51 @@
+#!/usr/bin/env python3
+"""Diverse-caption evaluation on MI355X - counterpart of the reference's eval/eval.py: oracle and mean BLEU-1..4, ROUGE-L and
+CIDEr-D over the N captions per image of a predictions JSON (what scripts/inference.py writes), Div-1 / Div-2 over all captions
+and over the top 5 by CIDEr, and style precision / recall against a wordforms TSV.  METEOR is not computed."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "style-seqcvae_amd"))
+
+import torch  # noqa: E402
+
+from ssc_runtime.evaluation import (CaptionReferences, format_summary, load_predictions, load_references,  # noqa: E402
+                                    style_words_from_tsv)
+
+parser = argparse.ArgumentParser("Score diverse captions (oracle / mean BLEU, ROUGE-L, CIDEr-D, Div-n, style) on the GPU.")
+parser.add_argument("--predictions", required=True, help='[{"image_id", "caption"}, ...]: N captions per image, in file order')
+parser.add_argument("--references", required=True,
+                    help='COCO annotations {"annotations": [{"image_id", "caption"}, ...]} or {image_id: [captions]}')
+parser.add_argument("--style-wordforms", default="", help="wordforms TSV whose words are the style words (senti_prec / senti_rec)")
+parser.add_argument("--gpu-ids", default=[0], nargs="+", type=int)
+parser.add_argument("--output-json", default="", help="write the summary here")
+parser.add_argument("--top5-output", default="", help="write the 5 captions per image of highest CIDEr-D here (eval.py's filtered list)")
+
+
+def main():
+    a = parser.parse_args()
+    device = torch.device("cuda", a.gpu_ids[0])
+    torch.cuda.set_device(device)
+    style = style_words_from_tsv(a.style_wordforms) if a.style_wordforms else None
+    refs = CaptionReferences(load_references(a.references), style_words=style, device=device)
+    preds = load_predictions(a.predictions)
+    result = refs.score_captions(preds)
+    print("input:", a.predictions)
+    print("Total ref sentences:", sum(len(refs.tokens[i]) for i in result.image_ids))
+    s = result.summary()
+    for line in format_summary(s):
+        print(line)
+    if result.empty_images:
+        print(f"{result.empty_images} image(s) with only empty captions: Div-n 0")
+    if a.output_json:
+        json.dump(s, open(a.output_json, "w"), indent=1)
+    if a.top5_output:
+        out = [{"image_id": iid, "caption": preds[iid][int(n)]} for iid, row in zip(result.image_ids, result.top5) for n in row]
+        json.dump(out, open(a.top5_output, "w"))
+
+
+if __name__ == "__main__":
+    main()

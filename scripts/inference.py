@@ -46,6 +46,10 @@ parser.add_argument("--boxes-json", default="",
                          '"scores": [...]}}, filtered to constraints by ssc_runtime.constraints.ConstraintFilter '
                          "(updown-baseline/updown/utils/constraints.py:56-209); needs --hierarchy-json and --wordforms-tsv")
 parser.add_argument("--hierarchy-json", default="", help="Open Images class hierarchy (bbox_labels_600_hierarchy_readable.json)")
+parser.add_argument("--references", default="",
+                    help="score the decoded captions on the device right after decoding (ssc_runtime.evaluation, as scripts/evaluate.py "
+                         'prints): COCO annotations {"annotations": [{"image_id", "caption"}]} or {image_id: [captions]}')
+parser.add_argument("--style-wordforms", default="", help="with --references: wordforms TSV of the style words (senti_prec / senti_rec)")
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -111,6 +115,7 @@ def main():
         builder = FiniteStateMachineBuilder(vocabulary, _A.wordforms_tsv, None, max_given_constraints=kmax,
                                             max_words_per_constraint=_C.DATA.CBS.MAX_WORDS_PER_CONSTRAINT)
         # (one machine per IMAGE, shared by its N_Z samples and compiled on the device - ssc_fsm_compile -: a call is sized by its rows)
+    chunks = []   # (image ids, predictions on the device) of every chunk, for --references
     ROW_BUDGET = 40000   # rows (image, sample, state, beam) per decode step of a constrained call
     with torch.no_grad():
         lo = 0
@@ -148,6 +153,8 @@ def main():
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam)
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
+            if _A.references:
+                chunks.append(([int(x) for x in data.image_id[lo: lo + n_here]], pred))
             ids = pred.cpu().numpy()                                   # (images, n_z, steps)
             words = id2word[ids]
             is_end = ids == boundary
@@ -159,6 +166,15 @@ def main():
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
+    if _A.references:
+        from ssc_runtime.evaluation import CaptionReferences, format_summary, load_references, style_words_from_tsv
+        style = style_words_from_tsv(_A.style_wordforms) if _A.style_wordforms else None
+        refs = CaptionReferences(load_references(_A.references), style_words=style, device=device)
+        steps = max(p.size(-1) for _, p in chunks)
+        pred = torch.cat([torch.nn.functional.pad(p, (0, steps - p.size(-1)), value=boundary) for _, p in chunks])
+        result = refs.score(pred, boundary, vocabulary, image_ids=[i for ids, _ in chunks for i in ids])
+        for line in format_summary(result.summary()):
+            print(line)
 
 
 if __name__ == "__main__":

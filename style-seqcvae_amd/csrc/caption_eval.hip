@@ -1,0 +1,538 @@
+// Diverse-caption evaluation on the device: BLEU-1..4 (coco-caption BleuScorer, "closest"), ROUGE-L (coco-caption Rouge),
+// CIDEr-D (coco-caption CiderScorer, sigma 6) per candidate, Div-n and style counts per image (the reference's eval/eval.py).
+//
+// Words are compact ids 1..W (W <= 65535) of the reference words; an n-gram of order k <= 4 is one 64-bit key of k 16-bit ids
+// (field i = word i), so the order is the number of nonzero fields and two n-grams are equal iff their keys are.  A candidate's
+// own n-grams (its tf, Div-n) are compared on its original ids; words in no reference map to compact id 0 and never match.
+//
+// Reference preparation (once per reference set):
+//   ev_ref_ngrams  one wave per reference: its distinct n-grams sorted by key, with their tf (LDS, O(n^2 / 64) compares)
+//   ev_ref_df      one wave per image: the n-grams no earlier reference of the image holds go into an open-addressing table
+//                  (integer atomicCAS / atomicAdd only) - df = the number of images whose references hold the n-gram
+//   ev_ref_weights one wave per reference: w = tf (log I - log max(1, df)), per-order norms in a fixed order
+// Scoring (once per prediction tensor):
+//   ev_score       one wave per candidate: n-grams, tf, df lookups, CIDEr-D against each reference (binary search in the
+//                  reference's sorted keys, staged in LDS), BLEU clipping, ROUGE-L by bit-parallel LCS (lane = reference position)
+//   ev_image       one workgroup per image: distinct 1- / 2-grams of its N captions and of its top 5 by CIDEr (LDS hash sets),
+//                  style counts
+// Every sum over a candidate's n-grams runs in the same lane assignment and butterfly order whatever the candidate's position, so
+// equal captions of an image score bit-equal; no float atomics.  Bad ids / lengths / offsets raise a device flag (SSC_EINVAL) and
+// are clamped, never used as indices.
+#include "ssc_common.h"
+
+namespace {
+
+constexpr int EV_L = 64;                  // tokens per caption (references and candidates)
+constexpr int EV_NG = 4 * EV_L;           // n-gram slots per caption
+constexpr int EV_MAX_N = 128;             // samples per image
+constexpr int EV_DIV_SLOTS = 16384;       // LDS hash set of ev_image: >= 2 x EV_MAX_N x EV_L occurrences
+constexpr unsigned EV_EMPTY = 0xffffffffu;
+constexpr int EV_NSCORE = 6, EV_NCOUNT = 10, EV_NIMG = 9;
+
+struct EvLayout {
+  size_t key, hkey, w, norm, tf, nu, len, base, rstyle, hdf, flag, total;
+  unsigned long long T;
+};
+
+EvLayout ev_layout(int I, int nref, int ntok) {
+  EvLayout l;
+  const size_t S = 4 * (size_t)ntok;
+  unsigned long long T = 64;
+  while (T < 2 * S) T <<= 1;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o = ssc_round_up(o + bytes, 256); return at; };
+  l.key = take(S * 8); l.hkey = take(T * 8); l.w = take(S * 8); l.norm = take((size_t)nref * 4 * 8); l.tf = take(S * 4);
+  l.nu = take((size_t)nref * 4); l.len = take((size_t)nref * 4); l.base = take((size_t)nref * 4); l.rstyle = take((size_t)I * 4);
+  l.hdf = take(T * 4); l.flag = take(4);
+  l.total = o; l.T = T;
+  return l;
+}
+
+struct EvState {
+  unsigned long long* key; unsigned long long* hkey; double* w; double* norm; int* tf; int* nu; int* len; int* base; int* rstyle;
+  int* hdf; int* flag; unsigned long long mask;
+};
+
+EvState ev_state(const ssc_eval_refs* r) {
+  const EvLayout l = ev_layout(r->I, r->nref, r->ntok);
+  char* b = (char*)r->state;
+  return {(unsigned long long*)(b + l.key), (unsigned long long*)(b + l.hkey), (double*)(b + l.w), (double*)(b + l.norm),
+          (int*)(b + l.tf), (int*)(b + l.nu), (int*)(b + l.len), (int*)(b + l.base), (int*)(b + l.rstyle), (int*)(b + l.hdf),
+          (int*)(b + l.flag), l.T - 1};
+}
+
+__device__ __forceinline__ int ev_count(int L) {
+  int n = 0;
+#pragma unroll
+  for (int k = 1; k <= 4; ++k) n += L - k + 1 > 0 ? L - k + 1 : 0;
+  return n;
+}
+// slot j of a caption of L tokens -> order k (1..4) and start s: the orders' n-grams are laid out one after the other
+__device__ __forceinline__ void ev_split(int j, int L, int& k, int& s) {
+  k = 1;
+  int c = L;
+  while (j >= c && k < 4) { j -= c; ++k; c = L - k + 1; }
+  s = j;
+}
+__device__ __forceinline__ int ev_order(unsigned long long key) {
+  return (key >> 48) ? 4 : (key >> 32) ? 3 : (key >> 16) ? 2 : 1;
+}
+__device__ __forceinline__ unsigned long long ev_mix(unsigned long long k) {
+  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
+  return k;
+}
+__device__ __forceinline__ unsigned ev_mix32(unsigned k) {
+  k ^= k >> 16; k *= 0x7feb352dU; k ^= k >> 15; k *= 0x846ca68bU; k ^= k >> 16;
+  return k;
+}
+// index of `k` among the n sorted keys at `a`, or -1
+__device__ __forceinline__ int ev_find(const unsigned long long* a, int n, unsigned long long k) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (a[mid] < k) lo = mid + 1; else hi = mid;
+  }
+  return (lo < n && a[lo] == k) ? lo : -1;
+}
+__device__ __forceinline__ int ev_df(const unsigned long long* hkey, const int* hdf, unsigned long long mask, unsigned long long k) {
+  unsigned long long h = ev_mix(k) & mask;
+  for (unsigned long long p = 0; p <= mask; ++p) {
+    const unsigned long long s = hkey[h];
+    if (s == k) return hdf[h];
+    if (s == 0ull) return 0;
+    h = (h + 1) & mask;
+  }
+  return 0;
+}
+__device__ __forceinline__ double ev_wsum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int ev_isum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// ---- reference preparation ----------------------------------------------------------------------------------------------------
+
+__global__ __launch_bounds__(64) void ev_ref_ngrams(const int* tok_off, const int* tokens, int ntok, int W, EvState st) {
+  __shared__ int tk[EV_L];
+  __shared__ unsigned long long kk[EV_NG];
+  __shared__ int first[EV_NG];
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const int a = tok_off[r], b = tok_off[r + 1];
+  const int L = b - a;
+  if (a < 0 || b > ntok || L < 1 || L > EV_L) {
+    if (lane == 0) { st.flag[0] = 1; st.nu[r] = 0; st.len[r] = 0; st.base[r] = 0; }
+    return;
+  }
+  int t = 1;
+  if (lane < L) {
+    t = tokens[a + lane];
+    if (t < 1 || t > W) { st.flag[0] = 1; t = 1; }
+  }
+  tk[lane] = t;
+  __syncthreads();
+  const int n = ev_count(L);
+  for (int j = lane; j < n; j += 64) {
+    int k, s;
+    ev_split(j, L, k, s);
+    unsigned long long key = 0;
+    for (int i = 0; i < k; ++i) key |= (unsigned long long)tk[s + i] << (16 * i);
+    kk[j] = key;
+  }
+  __syncthreads();
+  for (int j = lane; j < n; j += 64) {
+    int f = 1;
+    for (int i = 0; i < j; ++i) f &= kk[i] != kk[j];
+    first[j] = f;
+  }
+  __syncthreads();
+  int mine = 0;
+  for (int j = lane; j < n; j += 64) {
+    if (!first[j]) continue;
+    ++mine;
+    int tf = 0, rank = 0;
+    for (int i = 0; i < n; ++i) {
+      tf += kk[i] == kk[j];
+      rank += first[i] && kk[i] < kk[j];
+    }
+    st.key[4 * (size_t)a + rank] = kk[j];   // rank < distinct count <= n <= 4 L: inside this reference's 4 L slots
+    st.tf[4 * (size_t)a + rank] = tf;
+  }
+  mine = ev_isum(mine);
+  if (lane == 0) { st.nu[r] = mine; st.len[r] = L; st.base[r] = a; }
+}
+
+__global__ __launch_bounds__(64) void ev_ref_df(const int* ref_off, int nref, const uint8_t* style, int W, EvState st) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const int lo = ref_off[i], hi = ref_off[i + 1];
+  if (lo < 0 || hi > nref || hi <= lo) {
+    if (lane == 0) { st.flag[0] = 1; st.rstyle[i] = 0; }
+    return;
+  }
+  int sty = 0;
+  for (int r = lo; r < hi; ++r) {
+    const size_t b = 4 * (size_t)st.base[r];
+    const int n = st.nu[r];
+    for (int e = lane; e < n; e += 64) {
+      const unsigned long long k = st.key[b + e];
+      bool dup = false;
+      for (int r2 = lo; r2 < r && !dup; ++r2) dup = ev_find(st.key + 4 * (size_t)st.base[r2], st.nu[r2], k) >= 0;
+      if (dup) continue;
+      unsigned long long h = ev_mix(k) & st.mask;
+      bool done = false;
+      for (unsigned long long p = 0; p <= st.mask && !done; ++p) {
+        const unsigned long long prev = atomicCAS(&st.hkey[h], 0ull, k);
+        if (prev == 0ull || prev == k) { atomicAdd(&st.hdf[h], 1); done = true; }
+        h = (h + 1) & st.mask;
+      }
+      if (!done) st.flag[0] = 1;
+      if (style && (k >> 16) == 0 && (int)k <= W && style[(int)k]) ++sty;
+    }
+  }
+  sty = ev_isum(sty);
+  if (lane == 0) st.rstyle[i] = sty;
+}
+
+__global__ __launch_bounds__(64) void ev_ref_weights(int I, EvState st) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const size_t b = 4 * (size_t)st.base[r];
+  const int n = st.nu[r];
+  const double rl = log((double)I);
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int e = lane; e < n; e += 64) {
+    const unsigned long long k = st.key[b + e];
+    const int df = ev_df(st.hkey, st.hdf, st.mask, k);
+    const double w = (double)st.tf[b + e] * (rl - log((double)(df > 1 ? df : 1)));
+    st.w[b + e] = w;
+    const int o = ev_order(k) - 1;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q == o) s[q] += w * w;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const double v = ev_wsum(s[q]);
+    if (lane == 0) st.norm[4 * (size_t)r + q] = sqrt(v);
+  }
+}
+
+// ---- scoring ------------------------------------------------------------------------------------------------------------------
+
+struct EvScoreArgs {
+  const int64_t* pred; int N, steps, boundary, V, I, nref, W;
+  const int* id_map; const uint8_t* style_ids; const int* ref_image; const int* ref_off; const int* tokens;
+  double* scores; int* counts; int* image_counts; int* top5; const uint8_t* style; int* flag;
+};
+
+__global__ __launch_bounds__(64) void ev_score(EvScoreArgs a, EvState st) {
+  __shared__ int ot[EV_L], ct[EV_L];
+  __shared__ unsigned long long sk[EV_NG];
+  __shared__ double sw[EV_NG];
+  __shared__ int stf[EV_NG];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int p = row / a.N;
+  const int64_t* pr = a.pred + (size_t)row * a.steps;
+  // length: the first boundary_index, else the full row
+  int L = a.steps;
+  for (int c0 = 0; c0 < a.steps; c0 += 64) {
+    const int c = c0 + lane;
+    const unsigned long long m = __ballot(c < a.steps && pr[c] == (int64_t)a.boundary);
+    if (m) { L = c0 + __builtin_ctzll(m); break; }
+  }
+  if (L > EV_L) { if (lane == 0) a.flag[0] = 1; L = EV_L; }
+  if (lane < L) {
+    int64_t v = pr[lane];
+    if (v < 0 || v >= a.V) { a.flag[0] = 1; v = 0; }
+    int c = a.id_map[v];
+    if (c < 0 || c > a.W) { a.flag[0] = 1; c = 0; }
+    ot[lane] = (int)v;
+    ct[lane] = c;
+  }
+  __syncthreads();
+  const int n = ev_count(L);
+  // this lane's n-grams: slots lane + 64 q; tf > 0 only at a distinct n-gram's first occurrence
+  int tfc[4], ordc[4], maxr[4];
+  unsigned long long ck[4];
+  double wc[4];
+  const int img = a.ref_image[p];
+  const bool scored = img >= 0 && img < a.I;
+  if (img < -1 || img >= a.I) { if (lane == 0) a.flag[0] = 1; }
+  const double rl = log((double)a.I);
+  double ns[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int j = lane + 64 * q;
+    tfc[q] = 0; ordc[q] = 0; ck[q] = 0; wc[q] = 0.0; maxr[q] = 0;
+    if (j >= n) continue;
+    int k, s;
+    ev_split(j, L, k, s);
+    ordc[q] = k;
+    int tf = 0;
+    bool first = true;
+    for (int s2 = 0; s2 + k <= L; ++s2) {
+      bool eq = true;
+      for (int i = 0; i < k; ++i) eq &= ot[s + i] == ot[s2 + i];
+      tf += eq;
+      if (eq && s2 < s) first = false;
+    }
+    if (!first) continue;
+    tfc[q] = tf;
+    unsigned long long key = 0;
+    for (int i = 0; i < k; ++i) key |= (unsigned long long)ct[s + i] << (16 * i);
+    bool any0 = false;
+    for (int i = 0; i < k; ++i) any0 |= ct[s + i] == 0;
+    ck[q] = any0 ? 0ull : key;
+    const int df = (scored && ck[q]) ? ev_df(st.hkey, st.hdf, st.mask, ck[q]) : 0;
+    const double w = (double)tf * (rl - log((double)(df > 1 ? df : 1)));
+    wc[q] = w;
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+      if (o == k - 1) ns[o] += w * w;
+  }
+  double normc[4];
+#pragma unroll
+  for (int o = 0; o < 4; ++o) normc[o] = sqrt(ev_wsum(ns[o]));
+  int* cnt = a.counts + (size_t)row * EV_NCOUNT;
+  double* sc = a.scores + (size_t)row * EV_NSCORE;
+  int lo = 0, hi = 0;
+  if (scored) {
+    lo = a.ref_off[img]; hi = a.ref_off[img + 1];
+    if (lo < 0 || hi > a.nref || hi <= lo) { if (lane == 0) a.flag[0] = 1; lo = hi = 0; }
+  }
+  double cid[4] = {0.0, 0.0, 0.0, 0.0};
+  double P = 0.0, Q = 0.0;
+  int bd = 0x7fffffff, bl = 0;
+  const int lenc = L > 1 ? L - 1 : 0;
+  for (int r = lo; r < hi; ++r) {
+    const size_t b = 4 * (size_t)st.base[r];
+    const int nr = min(st.nu[r], EV_NG), lr = min(st.len[r], EV_L);   // (<= 4 len and <= 64 as ev_ref_ngrams wrote them)
+    __syncthreads();   // the previous reference's LDS reads are done
+    for (int e = lane; e < nr; e += 64) { sk[e] = st.key[b + e]; sw[e] = st.w[b + e]; stf[e] = st.tf[b + e]; }
+    const int rt = lane < lr ? a.tokens[st.base[r] + lane] : -1;
+    __syncthreads();
+    double val[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      if (tfc[q] == 0 || ck[q] == 0ull) continue;
+      const int x = ev_find(sk, nr, ck[q]);
+      if (x < 0) continue;
+      const double wr = sw[x];
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+        if (o == ordc[q] - 1) val[o] += fmin(wc[q], wr) * wr;
+      maxr[q] = max(maxr[q], stf[x]);
+    }
+    const int lrl = lr > 1 ? lr - 1 : 0;
+    const double delta = (double)(lenc - lrl);
+    const double g = exp(-(delta * delta) / 72.0);
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      double v = ev_wsum(val[o]);
+      const double nr_o = st.norm[4 * (size_t)r + o];
+      if (normc[o] != 0.0 && nr_o != 0.0) v /= normc[o] * nr_o;
+      v *= g;
+      cid[o] += v;
+    }
+    // LCS(candidate, reference) by the bit-parallel recurrence V' = (V + (V & M)) | (V & ~M), bit = reference position
+    unsigned long long Vb = ~0ull;
+    for (int t = 0; t < L; ++t) {
+      const int c = ct[t];
+      const unsigned long long M = __ballot(c != 0 && rt == c);
+      Vb = (Vb + (Vb & M)) | (Vb & ~M);
+    }
+    const unsigned long long msk = lr >= 64 ? ~0ull : ((1ull << lr) - 1);
+    const int l = __popcll(~Vb & msk);
+    if (L > 0 && lr > 0) {
+      P = fmax(P, (double)l / (double)L);
+      Q = fmax(Q, (double)l / (double)lr);
+    }
+    const int d = lr > L ? lr - L : L - lr;
+    if (d < bd || (d == bd && lr < bl)) { bd = d; bl = lr; }
+  }
+  int corr[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int o = 0; o < 4; ++o)
+      if (o == ordc[q] - 1 && tfc[q] > 0) corr[o] += min(tfc[q], maxr[q]);
+#pragma unroll
+  for (int o = 0; o < 4; ++o) corr[o] = ev_isum(corr[o]);
+  if (lane == 0) {
+    const int reflen = hi > lo ? bl : 0;
+    int guess[4];
+    for (int o = 0; o < 4; ++o) guess[o] = L - o > 0 ? L - o : 0;
+    cnt[0] = L; cnt[1] = reflen;
+    for (int o = 0; o < 4; ++o) { cnt[2 + o] = guess[o]; cnt[6 + o] = corr[o]; }
+    if (hi > lo) {
+      double bleu[4], bb = 1.0;
+      for (int o = 0; o < 4; ++o) {
+        bb *= ((double)corr[o] + 1e-15) / ((double)guess[o] + 1e-9);
+        bleu[o] = pow(bb, 1.0 / (o + 1));
+      }
+      const double ratio = ((double)L + 1e-15) / ((double)reflen + 1e-9);
+      if (ratio < 1.0)
+        for (int o = 0; o < 4; ++o) bleu[o] *= exp(1.0 - 1.0 / ratio);
+      for (int o = 0; o < 4; ++o) sc[o] = bleu[o];
+      const double beta2 = 1.2 * 1.2;
+      sc[4] = (L > 0 && P != 0.0 && Q != 0.0) ? ((1.0 + beta2) * P * Q) / (Q + beta2 * P) : 0.0;
+      sc[5] = (((cid[0] + cid[1]) + cid[2]) + cid[3]) / 4.0 / (double)(hi - lo) * 10.0;
+    } else {
+      for (int o = 0; o < EV_NSCORE; ++o) sc[o] = 0.0;
+    }
+  }
+}
+
+// distinct n-grams (n = 1, 2) of the captions sel[0..ns) of prediction image p, over their original ids; with style != NULL the
+// new unigrams that are style words are counted (cs) and so are those its references hold (cm)
+__device__ void ev_distinct(const EvScoreArgs& a, const EvState& st, int p, const int* sel, int ns, const int* len, int order,
+                            unsigned* tab, int* cnt, int lo, int hi, bool style) {
+  for (int i = threadIdx.x; i < EV_DIV_SLOTS; i += blockDim.x) tab[i] = EV_EMPTY;
+  if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+  __syncthreads();
+  int nd = 0, cs = 0, cm = 0;
+  for (int x = threadIdx.x; x < ns * EV_L; x += blockDim.x) {
+    const int n = sel[x / EV_L], t = x % EV_L;
+    if (n < 0 || n >= a.N || t + order > len[n]) continue;
+    const int64_t* pr = a.pred + ((size_t)p * a.N + n) * a.steps;
+    const int64_t v0 = pr[t], v1 = order == 2 ? pr[t + 1] : 0;
+    if (v0 < 0 || v0 >= a.V || v1 < 0 || v1 >= a.V) continue;   // (flagged by ev_score)
+    const unsigned key = order == 1 ? (unsigned)v0 : (unsigned)v0 * 65536u + (unsigned)v1;
+    unsigned h = ev_mix32(key) & (EV_DIV_SLOTS - 1);
+    bool fresh = false;
+    for (int probe = 0; probe < EV_DIV_SLOTS; ++probe) {
+      const unsigned prev = atomicCAS(&tab[h], EV_EMPTY, key);
+      if (prev == EV_EMPTY) { fresh = true; break; }
+      if (prev == key) break;
+      h = (h + 1) & (EV_DIV_SLOTS - 1);
+    }
+    if (!fresh) continue;
+    ++nd;
+    if (style && a.style_ids[v0]) {
+      ++cs;
+      const int c = a.id_map[v0];
+      bool held = false;
+      if (c > 0 && c <= a.W)
+        for (int r = lo; r < hi && !held; ++r) held = ev_find(st.key + 4 * (size_t)st.base[r], st.nu[r], (unsigned long long)c) >= 0;
+      cm += held;
+    }
+  }
+  atomicAdd(&cnt[0], nd);
+  atomicAdd(&cnt[1], cs);
+  atomicAdd(&cnt[2], cm);
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void ev_image(EvScoreArgs a, EvState st) {
+  __shared__ unsigned tab[EV_DIV_SLOTS];
+  __shared__ int len[EV_MAX_N], sel[EV_MAX_N], top[5], cnt[3];
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int N = a.N;
+  for (int n = tid; n < N; n += blockDim.x) {
+    len[n] = a.counts[((size_t)p * N + n) * EV_NCOUNT];
+    sel[n] = n;
+  }
+  if (tid < 5) top[tid] = -1;
+  const int img = a.ref_image[p];
+  const bool scored = img >= 0 && img < a.I;
+  int lo = 0, hi = 0;
+  if (scored) {
+    lo = a.ref_off[img]; hi = a.ref_off[img + 1];
+    if (lo < 0 || hi > a.nref || hi <= lo) lo = hi = 0;   // (flagged by ev_score)
+  }
+  __syncthreads();
+  int* out = a.image_counts + (size_t)p * EV_NIMG;
+  int words = 0;
+  for (int n = 0; n < N; ++n) words += len[n];
+  ev_distinct(a, st, p, sel, N, len, 1, tab, cnt, lo, hi, scored && a.style_ids != nullptr);
+  if (tid == 0) { out[0] = cnt[0]; out[6] = cnt[1]; out[7] = cnt[2]; }
+  __syncthreads();
+  ev_distinct(a, st, p, sel, N, len, 2, tab, cnt, lo, hi, false);
+  if (tid == 0) { out[1] = cnt[0]; out[2] = words; out[8] = scored ? st.rstyle[img] : 0; }
+  if (scored && N >= 5) {
+    // top 5 by CIDEr, stable descending: rank = #{j : c_j > c_n, or c_j == c_n and j < n}
+    for (int n = tid; n < N; n += blockDim.x) {
+      const double c = a.scores[((size_t)p * N + n) * EV_NSCORE + 5];
+      int rank = 0;
+      for (int j = 0; j < N; ++j) {
+        const double cj = a.scores[((size_t)p * N + j) * EV_NSCORE + 5];
+        rank += cj > c || (cj == c && j < n);
+      }
+      if (rank < 5) top[rank] = n;
+    }
+    __syncthreads();
+    int w5 = 0;
+    for (int k = 0; k < 5; ++k) w5 += top[k] >= 0 ? len[top[k]] : 0;
+    ev_distinct(a, st, p, top, 5, len, 1, tab, cnt, lo, hi, false);
+    if (tid == 0) out[3] = cnt[0];
+    __syncthreads();
+    ev_distinct(a, st, p, top, 5, len, 2, tab, cnt, lo, hi, false);
+    if (tid == 0) { out[4] = cnt[0]; out[5] = w5; }
+  } else if (tid == 0) {
+    out[3] = out[4] = out[5] = 0;
+  }
+  if (tid < 5) a.top5[(size_t)p * 5 + tid] = top[tid];
+}
+
+bool ev_refs_ok(const ssc_eval_refs* r) {
+  return r && r->I >= 1 && r->I <= (1 << 24) && r->nref >= r->I && r->nref <= (1 << 26) && r->ntok >= r->nref &&
+         r->ntok <= (1 << 26) && r->W >= 1 && r->W <= 65535 && r->ref_offsets && r->tok_offsets && r->tokens && r->state;
+}
+
+int ev_read_flag(const int* flag, hipStream_t st) {
+  int h = 0;
+  if (hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return SSC_EHIP;
+  const hipError_t e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { ssc_tls_hip_error = (int)e; return SSC_EHIP; }
+  return h ? SSC_EINVAL : SSC_OK;
+}
+
+}  // namespace
+
+extern "C" size_t ssc_eval_refs_bytes(int I, int nref, int ntok) {
+  if (I < 1 || I > (1 << 24) || nref < I || nref > (1 << 26) || ntok < nref || ntok > (1 << 26)) return 0;
+  return ev_layout(I, nref, ntok).total;
+}
+
+extern "C" int ssc_eval_prepare_refs(const ssc_eval_refs* r, void* stream) {
+  if (!ev_refs_ok(r)) return SSC_EINVAL;
+  const EvLayout l = ev_layout(r->I, r->nref, r->ntok);
+  if (r->state_bytes < l.total) return SSC_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const EvState s = ev_state(r);
+  if (hipMemsetAsync(r->state, 0, l.total, st) != hipSuccess) return SSC_EHIP;
+  SSC_LAUNCH(ev_ref_ngrams, dim3(r->nref), dim3(64), 0, st, r->tok_offsets, r->tokens, r->ntok, r->W, s);
+  SSC_CHECK_LAUNCH();
+  SSC_LAUNCH(ev_ref_df, dim3(r->I), dim3(64), 0, st, r->ref_offsets, r->nref, r->style, r->W, s);
+  SSC_CHECK_LAUNCH();
+  SSC_LAUNCH(ev_ref_weights, dim3(r->nref), dim3(64), 0, st, r->I, s);
+  SSC_CHECK_LAUNCH();
+  return ev_read_flag(s.flag, st);
+}
+
+extern "C" size_t ssc_eval_score_workspace_bytes(const ssc_eval_refs* r, const ssc_eval_score_desc* d) {
+  (void)r; (void)d;
+  return 256;
+}
+
+extern "C" int ssc_eval_score(const ssc_eval_refs* r, const ssc_eval_score_desc* d, void* workspace, size_t workspace_bytes,
+                              void* stream) {
+  if (!ev_refs_ok(r) || !d) return SSC_EINVAL;
+  if (d->P < 1 || d->N < 1 || d->N > EV_MAX_N || d->steps < 1 || d->V < 1 || d->V > 65535 || (int64_t)d->P * d->N > (1 << 24) ||
+      !d->predictions || !d->id_map || !d->ref_image || !d->scores || !d->counts || !d->image_counts || !d->top5)
+    return SSC_EINVAL;
+  if (r->state_bytes < ev_layout(r->I, r->nref, r->ntok).total || !workspace || workspace_bytes < 256) return SSC_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const EvState s = ev_state(r);
+  EvScoreArgs a{d->predictions, d->N, d->steps, d->boundary_index, d->V, r->I, r->nref, r->W, d->id_map, d->style_ids, d->ref_image,
+                r->ref_offsets, r->tokens, d->scores, d->counts, d->image_counts, d->top5, r->style, (int*)workspace};
+  if (hipMemsetAsync(workspace, 0, sizeof(int), st) != hipSuccess) return SSC_EHIP;
+  SSC_LAUNCH(ev_score, dim3(d->P * d->N), dim3(64), 0, st, a, s);
+  SSC_CHECK_LAUNCH();
+  SSC_LAUNCH(ev_image, dim3(d->P), dim3(256), 0, st, a, s);
+  SSC_CHECK_LAUNCH();
+  return ev_read_flag(a.flag, st);
+}

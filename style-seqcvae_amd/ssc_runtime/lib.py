@@ -142,6 +142,16 @@ class GumbelDesc(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class EvalRefs(C.Structure):
+    _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
+                ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
+
+
+class EvalScoreDesc(C.Structure):
+    _fields_ = [("predictions", vp), ("P", C.c_int), ("N", C.c_int), ("steps", C.c_int), ("boundary_index", C.c_int), ("V", C.c_int),
+                ("id_map", vp), ("style_ids", vp), ("ref_image", vp), ("scores", vp), ("counts", vp), ("image_counts", vp), ("top5", vp)]
+
+
 # name -> (restype, argtypes).  Every symbol include/ssc.h declares is listed; tests check they all resolve.
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -231,6 +241,10 @@ SYMBOLS = {
     "ssc_decode_sampled_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sampled_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), _i, vp,
                                      _sz, vp]),
+    "ssc_eval_refs_bytes": (_sz, [_i, _i, _i]),
+    "ssc_eval_prepare_refs": (_i, [C.POINTER(EvalRefs), vp]),
+    "ssc_eval_score_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc)]),
+    "ssc_eval_score": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc), vp, _sz, vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)
