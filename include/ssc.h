@@ -814,6 +814,40 @@ size_t ssc_eval_score_workspace_bytes(const ssc_eval_refs* r, const ssc_eval_sco
 /* every candidate's scores and statistics, then every image's counts (two kernels) */
 int ssc_eval_score(const ssc_eval_refs* r, const ssc_eval_score_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Caption-SET diversity: the N captions of an image compared with each other (Wang & Chan, "Describing like humans", CVPR 2019;
+ * the numbers Seq-CVAE / COS-CVAE / POS / AG-CVAE report).  Per image p and sample i:
+ *   set_counts  BleuScorer's ten integers (testlen, reflen "closest", guess[4], correct[4]) of caption i against the other N - 1
+ *               captions of p as its references (by index: a duplicate at another index is a reference).  mBLEU-k is the caller's
+ *               reduction: corpus BLEU-k of the statistics summed over the images at sample index i, averaged over i.
+ *   kernel      K_ij = 1/4 sum_{n=1..4} cos(g_i^n, g_j^n), g_i^n = the caption's n-grams weighted tf (log I - log max(1, df)) with
+ *               the prepared references' df and I (no CIDEr-D clipping, no length Gaussian); a cosine with a zero vector is 0,
+ *               on the diagonal too.  Symmetric bit for bit, positive semi-definite up to rounding, entries in [0, 1].
+ *   eigenvalues of K, descending (cyclic Jacobi in fp64).  Self-CIDEr = -log(sqrt(l_1) / sum_i sqrt(l_i)) / log N is the caller's.
+ *   distinct    the number of distinct captions (token tuples) among the N; every empty caption is the same caption.
+ * A caption's n-grams are compared on its original ids 0..V-1 (id 0 is a word like any other); df is looked up through id_map
+ * as ssc_eval_score does.  Exact and deterministic as the calls above: integer counts, fp64, no float atomics, one summation
+ * order per pair whatever its position (equal captions give bit-equal rows), two calls bit-identical.  Reads a device flag
+ * back (synchronises `stream`): out-of-range ids, rows of more than 64 tokens or ref_image values give SSC_EINVAL.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const int64_t* predictions; /* (P, N, steps): as ssc_eval_score_desc */
+  int P, N, steps;            /* 2 <= N <= 128 */
+  int boundary_index;
+  int V;                      /* prediction ids 0..V-1, V <= 65535 */
+  const int* id_map;          /* (V): as ssc_eval_score_desc; may be NULL when refs is NULL */
+  const int* ref_image;       /* (P): the prepared image of prediction image p, or -1: no kernel / eigenvalues for it */
+  int* set_counts;            /* (P, N, 10) */
+  double* kernel;             /* optional (P, N, N): 0 where ref_image is -1 */
+  double* eigenvalues;        /* (P, N) descending; 0 where ref_image is -1 */
+  int* distinct;              /* (P) */
+} ssc_eval_set_desc;
+
+/* refs may be NULL when every ref_image is -1 (set_counts and distinct only). */
+size_t ssc_eval_set_workspace_bytes(const ssc_eval_refs* refs, const ssc_eval_set_desc* d);   /* 0 for arguments out of range */
+/* every caption's sorted n-grams and weights, every ordered pair of an image's captions, every image's eigenvalues (three kernels) */
+int ssc_eval_set(const ssc_eval_refs* refs, const ssc_eval_set_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Diverse-caption evaluation on MI355X - counterpart of the reference's eval/eval.py: oracle and mean BLEU-1..4, ROUGE-L and
 CIDEr-D over the N captions per image of a predictions JSON (what scripts/inference.py writes), Div-1 / Div-2 over all captions
-and over the top 5 by CIDEr, and style precision / recall against a wordforms TSV.  METEOR is not computed."""
+and over the top 5 by CIDEr, and style precision / recall against a wordforms TSV.  METEOR is not computed.  --set-diversity adds the caption-set numbers
+(each image's N captions against each other): mBLEU-1..4, Self-CIDEr and the share of distinct captions."""
 import argparse
 import json
 import os
@@ -22,6 +23,8 @@ parser.add_argument("--references", required=True,
 parser.add_argument("--style-wordforms", default="", help="wordforms TSV whose words are the style words (senti_prec / senti_rec)")
 parser.add_argument("--gpu-ids", default=[0], nargs="+", type=int)
 parser.add_argument("--output-json", default="", help="write the summary here")
+parser.add_argument("--set-diversity", action="store_true",
+                    help="also compare each image's captions with each other: mBLEU-1..4 (lower = more diverse), Self-CIDEr, unique")
 parser.add_argument("--top5-output", default="", help="write the 5 captions per image of highest CIDEr-D here (eval.py's filtered list)")
 
 
@@ -32,7 +35,7 @@ def main():
     style = style_words_from_tsv(a.style_wordforms) if a.style_wordforms else None
     refs = CaptionReferences(load_references(a.references), style_words=style, device=device)
     preds = load_predictions(a.predictions)
-    result = refs.score_captions(preds)
+    result = refs.score_captions(preds, set_diversity=a.set_diversity)
     print("input:", a.predictions)
     print("Total ref sentences:", sum(len(refs.tokens[i]) for i in result.image_ids))
     s = result.summary()
@@ -40,6 +43,8 @@ def main():
         print(line)
     if result.empty_images:
         print(f"{result.empty_images} image(s) with only empty captions: Div-n 0")
+    if result.degenerate_sets:
+        print(f"{result.degenerate_sets} image(s) whose captions hold no weighted n-gram: Self-CIDEr 0")
     if a.output_json:
         json.dump(s, open(a.output_json, "w"), indent=1)
     if a.top5_output:

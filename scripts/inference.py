@@ -50,6 +50,8 @@ parser.add_argument("--references", default="",
                     help="score the decoded captions on the device right after decoding (ssc_runtime.evaluation, as scripts/evaluate.py "
                          'prints): COCO annotations {"annotations": [{"image_id", "caption"}]} or {image_id: [captions]}')
 parser.add_argument("--style-wordforms", default="", help="with --references: wordforms TSV of the style words (senti_prec / senti_rec)")
+parser.add_argument("--set-diversity", action="store_true",
+                    help="with --references: also compare each image's captions with each other (mBLEU-1..4, Self-CIDEr, unique)")
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -172,9 +174,12 @@ def main():
         refs = CaptionReferences(load_references(_A.references), style_words=style, device=device)
         steps = max(p.size(-1) for _, p in chunks)
         pred = torch.cat([torch.nn.functional.pad(p, (0, steps - p.size(-1)), value=boundary) for _, p in chunks])
-        result = refs.score(pred, boundary, vocabulary, image_ids=[i for ids, _ in chunks for i in ids])
+        result = refs.score(pred, boundary, vocabulary, image_ids=[i for ids, _ in chunks for i in ids],
+                            set_diversity=_A.set_diversity)
         for line in format_summary(result.summary()):
             print(line)
+        if result.degenerate_sets:
+            print(f"{result.degenerate_sets} image(s) whose captions hold no weighted n-gram: Self-CIDEr 0")
 
 
 if __name__ == "__main__":

@@ -477,6 +477,354 @@ __global__ __launch_bounds__(256) void ev_image(EvScoreArgs a, EvState st) {
   if (tid < 5) a.top5[(size_t)p * 5 + tid] = top[tid];
 }
 
+// ---- caption-set diversity: the N captions of an image against each other ---------------------------------------------------
+//   es_caption  one wave per caption: its distinct n-grams over ORIGINAL ids (key field = id + 1, so id 0 is a word), sorted by
+//               key, with tf, the weight tf (log I - log max(1, df)) and the per-order norms - once per caption, in a workspace
+//               of S = (n-gram slots of min(steps, 64) tokens) entries per caption
+//   es_pair     one wave per (image, i): caption i's keys staged in LDS; against every j the n-grams both hold are found by binary
+//               search, ranked among themselves (ballot prefix), and their products summed in rank order - an order that depends on
+//               the set of shared n-grams alone, so K_ij == K_ji and equal captions give equal rows bit for bit; BLEU clipping
+//               maxima, the "closest" length and "an earlier caption equals this one" ride along
+//   es_eigen    one workgroup per image: K in LDS, cyclic Jacobi (round-robin pairing: N / 2 disjoint rotations at a time) in fp64
+//               until the largest off-diagonal entry is below 1e-15 max(1, largest diagonal entry); eigenvalues sorted descending
+
+constexpr int ES_THREADS = 256;
+constexpr int ES_MAX_SWEEPS = 30;
+
+struct EsLayout { size_t flag, key, w, tf, nu, len, norm, first, kmat, total; int S; };
+
+EsLayout es_layout(int P, int N, int steps, bool own_kmat) {
+  EsLayout l;
+  const int Lm = steps < EV_L ? steps : EV_L;
+  int S = 0;
+  for (int k = 1; k <= 4; ++k) S += Lm - k + 1 > 0 ? Lm - k + 1 : 0;
+  const size_t rows = (size_t)P * N;
+  size_t o = 0;
+  auto take = [&](size_t bytes) { size_t at = o; o = ssc_round_up(o + bytes, 256); return at; };
+  l.flag = take(4); l.key = take(rows * S * 8); l.w = take(rows * S * 8); l.tf = take(rows * S * 4); l.nu = take(rows * 4);
+  l.len = take(rows * 4); l.norm = take(rows * 4 * 8); l.first = take(rows * 4);
+  l.kmat = take(own_kmat ? rows * N * 8 : 0);
+  l.total = o; l.S = S;
+  return l;
+}
+
+struct EsArgs {
+  const int64_t* pred; int N, steps, boundary, V, I, W, S;
+  const int* id_map; const int* ref_image;
+  unsigned long long* key; double* w; int* tf; int* nu; int* len; double* norm; int* first;
+  int* counts; double* kmat; double* eig; int* distinct; int* flag;
+};
+
+// the prepared image of prediction image p, or -1; anything else raises the flag
+__device__ __forceinline__ int es_image(const EsArgs& a, int p) {
+  const int img = a.ref_image[p];
+  if (img < -1 || img >= a.I) { a.flag[0] = 1; return -1; }
+  return img;
+}
+
+__global__ __launch_bounds__(64) void es_caption(EsArgs a, EvState st) {
+  __shared__ int ot[EV_L], ct[EV_L];
+  __shared__ unsigned long long kk[EV_NG], ck[EV_NG], sk[EV_NG];
+  __shared__ double sw[EV_NG];
+  __shared__ int first[EV_NG];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int p = row / a.N;
+  const int64_t* pr = a.pred + (size_t)row * a.steps;
+  int L = a.steps;
+  for (int c0 = 0; c0 < a.steps; c0 += 64) {
+    const int c = c0 + lane;
+    const unsigned long long m = __ballot(c < a.steps && pr[c] == (int64_t)a.boundary);
+    if (m) { L = c0 + __builtin_ctzll(m); break; }
+  }
+  if (L > EV_L) { if (lane == 0) a.flag[0] = 1; L = EV_L; }
+  const bool scored = es_image(a, p) >= 0;
+  ot[lane] = 0; ct[lane] = 0;
+  if (lane < L) {
+    int64_t v = pr[lane];
+    if (v < 0 || v >= a.V) { a.flag[0] = 1; v = 0; }
+    int c = 0;
+    if (scored) {
+      c = a.id_map[v];
+      if (c < 0 || c > a.W) { a.flag[0] = 1; c = 0; }
+    }
+    ot[lane] = (int)v;
+    ct[lane] = c;
+  }
+  __syncthreads();
+  const int n = ev_count(L);   // <= a.S: L <= min(steps, 64)
+  for (int j = lane; j < n; j += 64) {
+    int k, s;
+    ev_split(j, L, k, s);
+    unsigned long long key = 0, c = 0;
+    bool any0 = false;
+    for (int i = 0; i < k; ++i) {
+      key |= (unsigned long long)(ot[s + i] + 1) << (16 * i);
+      c |= (unsigned long long)ct[s + i] << (16 * i);
+      any0 |= ct[s + i] == 0;
+    }
+    kk[j] = key;
+    ck[j] = any0 ? 0ull : c;
+  }
+  __syncthreads();
+  for (int j = lane; j < n; j += 64) {
+    int f = 1;
+    for (int i = 0; i < j; ++i) f &= kk[i] != kk[j];
+    first[j] = f;
+  }
+  __syncthreads();
+  const size_t b = (size_t)row * a.S;
+  const double rl = log((double)a.I);
+  int mine = 0;
+  for (int j = lane; j < n; j += 64) {
+    if (!first[j]) continue;
+    ++mine;
+    int tf = 0, rank = 0;
+    for (int i = 0; i < n; ++i) {
+      tf += kk[i] == kk[j];
+      rank += first[i] && kk[i] < kk[j];
+    }
+    const int df = (scored && ck[j]) ? ev_df(st.hkey, st.hdf, st.mask, ck[j]) : 0;
+    const double w = scored ? (double)tf * (rl - log((double)(df > 1 ? df : 1))) : 0.0;
+    sk[rank] = kk[j];   // rank < distinct count <= n <= S
+    sw[rank] = w;
+    a.key[b + rank] = kk[j];
+    a.w[b + rank] = w;
+    a.tf[b + rank] = tf;
+  }
+  mine = ev_isum(mine);
+  __syncthreads();
+  // per-order norms over the SORTED n-grams: the order depends on the caption's content alone
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int e = lane; e < mine; e += 64) {
+    const int o = ev_order(sk[e]) - 1;
+    const double w = sw[e];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q == o) s[q] += w * w;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const double v = ev_wsum(s[q]);
+    if (lane == 0) a.norm[4 * (size_t)row + q] = sqrt(v);
+  }
+  if (lane == 0) { a.nu[row] = mine; a.len[row] = L; }
+}
+
+__global__ __launch_bounds__(64) void es_pair(EsArgs a) {
+  __shared__ unsigned long long sk[EV_NG];
+  __shared__ double sw[EV_NG], sprod[EV_NG];
+  __shared__ int stf[EV_NG], smax[EV_NG], sord[EV_NG];
+  const int row = blockIdx.x, lane = threadIdx.x;
+  const int p = row / a.N, i = row - p * a.N;
+  const bool scored = a.ref_image[p] >= 0 && a.ref_image[p] < a.I;   // (out-of-range values were flagged by es_caption)
+  const int ni = min(a.nu[row], a.S), L = min(a.len[row], EV_L);
+  const size_t bi = (size_t)row * a.S;
+  for (int e = lane; e < EV_NG; e += 64) {
+    const bool in = e < ni;
+    sk[e] = in ? a.key[bi + e] : 0ull;
+    sw[e] = in ? a.w[bi + e] : 0.0;
+    stf[e] = in ? a.tf[bi + e] : 0;
+    smax[e] = 0;
+  }
+  const int64_t* pri = a.pred + (size_t)row * a.steps;
+  const int64_t mytok = lane < L ? pri[lane] : 0;
+  double normi[4];
+#pragma unroll
+  for (int o = 0; o < 4; ++o) normi[o] = a.norm[4 * (size_t)row + o];
+  __syncthreads();
+  int bd = 0x7fffffff, bl = 0;
+  bool dup = false;
+  for (int j = 0; j < a.N; ++j) {
+    const int rj = p * a.N + j;
+    const int nj = min(a.nu[rj], a.S), lj = min(a.len[rj], EV_L);
+    const size_t bj = (size_t)rj * a.S;
+    int common = 0;
+    for (int c0 = 0; c0 < nj; c0 += 64) {
+      const int e = c0 + lane;
+      int x = -1;
+      unsigned long long kj = 0;
+      if (e < nj) {
+        kj = a.key[bj + e];
+        x = ev_find(sk, ni, kj);
+      }
+      if (x >= 0 && j != i) smax[x] = max(smax[x], a.tf[bj + e]);   // one lane per x: the keys of caption j are distinct
+      if (scored) {
+        const unsigned long long m = __ballot(x >= 0);
+        if (x >= 0) {
+          const int r = common + __popcll(m & ((1ull << lane) - 1ull));   // rank among the shared n-grams, in key order
+          sprod[r] = sw[x] * a.w[bj + e];
+          sord[r] = ev_order(kj) - 1;
+        }
+        common += __popcll(m);
+      }
+    }
+    if (j != i) {
+      const int d = lj > L ? lj - L : L - lj;
+      if (d < bd || (d == bd && lj < bl)) { bd = d; bl = lj; }
+      if (j < i && lj == L && !dup) {
+        const int64_t* prj = a.pred + (size_t)rj * a.steps;
+        dup = __all(lane < L ? prj[lane] == mytok : true);
+      }
+    }
+    __syncthreads();
+    if (a.kmat) {
+      double kij = 0.0;
+      if (scored) {
+        double val[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int r = lane; r < common; r += 64) {
+          const int o = sord[r];
+          const double v = sprod[r];
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (q == o) val[q] += v;
+        }
+        double c[4];
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+          const double v = ev_wsum(val[o]);
+          const double nj_o = a.norm[4 * (size_t)rj + o];
+          c[o] = (normi[o] != 0.0 && nj_o != 0.0) ? v / (normi[o] * nj_o) : 0.0;
+        }
+        kij = (((c[0] + c[1]) + c[2]) + c[3]) * 0.25;
+      }
+      if (lane == 0) a.kmat[(size_t)row * a.N + j] = kij;
+    }
+    __syncthreads();   // sprod / sord / smax are free for the next caption
+  }
+  int corr[4] = {0, 0, 0, 0};
+  for (int e = lane; e < ni; e += 64) {
+    const int o = ev_order(sk[e]) - 1;
+    const int c = min(stf[e], smax[e]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (q == o) corr[q] += c;
+  }
+#pragma unroll
+  for (int o = 0; o < 4; ++o) corr[o] = ev_isum(corr[o]);
+  if (lane == 0) {
+    int* cnt = a.counts + (size_t)row * EV_NCOUNT;
+    cnt[0] = L; cnt[1] = bl;
+    for (int o = 0; o < 4; ++o) { cnt[2 + o] = L - o > 0 ? L - o : 0; cnt[6 + o] = corr[o]; }
+    a.first[row] = dup ? 0 : 1;
+  }
+}
+
+__global__ __launch_bounds__(ES_THREADS) void es_eigen(EsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double es_lds[];
+  const int N = a.N, LD = N | 1;        // odd leading dimension: a column walk touches every bank
+  double* A = es_lds;                   // [N][LD]
+  double* cs = A + (size_t)N * LD;      // [64] rotation cosines, then [64] sines
+  double* sn = cs + 64;
+  double* red = sn + 64;                // [ES_THREADS]
+  int* pp = (int*)(red + ES_THREADS);   // [64] the rotations' rows p < q
+  int* qq = pp + 64;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  if (tid == 0) {
+    int nd = 0;
+    for (int i = 0; i < N; ++i) nd += a.first[(size_t)p * N + i] != 0;
+    a.distinct[p] = nd;
+  }
+  const int img = a.ref_image[p];
+  if (img < 0 || img >= a.I) {   // workgroup-uniform
+    for (int i = tid; i < N; i += ES_THREADS) a.eig[(size_t)p * N + i] = 0.0;
+    return;
+  }
+  const double* K = a.kmat + (size_t)p * N * N;
+  for (int x = tid; x < N * N; x += ES_THREADS) A[(x / N) * LD + x % N] = K[x];
+  if (tid < 64) { cs[tid] = 1.0; sn[tid] = 0.0; pp[tid] = 0; qq[tid] = 0; }
+  __syncthreads();
+  const int m = N + (N & 1), half = m / 2;   // an odd N plays with a dummy index N that never rotates
+  for (int sweep = 0; sweep < ES_MAX_SWEEPS; ++sweep) {
+    double off = 0.0, dg = 0.0;
+    for (int x = tid; x < N * N; x += ES_THREADS) {
+      const int r = x / N, c = x - r * N;
+      const double v = fabs(A[r * LD + c]);
+      if (r == c) dg = fmax(dg, v); else off = fmax(off, v);
+    }
+    red[tid] = off;
+    __syncthreads();
+    for (int s = ES_THREADS / 2; s > 0; s >>= 1) {
+      if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+      __syncthreads();
+    }
+    off = red[0];
+    __syncthreads();
+    red[tid] = dg;
+    __syncthreads();
+    for (int s = ES_THREADS / 2; s > 0; s >>= 1) {
+      if (tid < s) red[tid] = fmax(red[tid], red[tid + s]);
+      __syncthreads();
+    }
+    dg = red[0];
+    __syncthreads();
+    if (off <= 1e-15 * fmax(1.0, dg)) break;   // workgroup-uniform
+    for (int step = 0; step < m - 1; ++step) {
+      if (tid < half) {
+        int u = tid == 0 ? step : (step + tid) % (m - 1);
+        int v = tid == 0 ? m - 1 : (step - tid + (m - 1)) % (m - 1);
+        if (u > v) { const int t = u; u = v; v = t; }
+        double c = 1.0, s = 0.0;
+        if (v < N) {
+          const double apq = A[u * LD + v];
+          if (apq != 0.0) {
+            const double theta = (A[v * LD + v] - A[u * LD + u]) / (2.0 * apq);
+            const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+            c = 1.0 / sqrt(t * t + 1.0);
+            s = t * c;
+          }
+        } else {
+          u = v = 0;
+        }
+        cs[tid] = c; sn[tid] = s; pp[tid] = u; qq[tid] = v;
+      }
+      __syncthreads();
+      for (int x = tid; x < half * N; x += ES_THREADS) {   // rows p, q of J^T A
+        const int k = x / N, col = x - k * N;
+        const double s = sn[k];
+        if (s == 0.0) continue;
+        const double c = cs[k];
+        double* ap = A + pp[k] * LD + col;
+        double* aq = A + qq[k] * LD + col;
+        const double x0 = *ap, x1 = *aq;
+        *ap = c * x0 - s * x1;
+        *aq = s * x0 + c * x1;
+      }
+      __syncthreads();
+      for (int x = tid; x < half * N; x += ES_THREADS) {   // columns p, q of (J^T A) J
+        const int k = x / N, r = x - k * N;
+        const double s = sn[k];
+        if (s == 0.0) continue;
+        const double c = cs[k];
+        double* ap = A + r * LD + pp[k];
+        double* aq = A + r * LD + qq[k];
+        const double x0 = *ap, x1 = *aq;
+        *ap = c * x0 - s * x1;
+        *aq = s * x0 + c * x1;
+      }
+      __syncthreads();
+      if (tid < half && sn[tid] != 0.0) { A[pp[tid] * LD + qq[tid]] = 0.0; A[qq[tid] * LD + pp[tid]] = 0.0; }   // the pivots, exactly
+      __syncthreads();
+    }
+  }
+  // descending, stable
+  for (int i = tid; i < N; i += ES_THREADS) {
+    const double d = A[i * LD + i];
+    int rank = 0;
+    for (int j = 0; j < N; ++j) {
+      const double dj = A[j * LD + j];
+      rank += dj > d || (dj == d && j < i);
+    }
+    a.eig[(size_t)p * N + rank] = d;
+  }
+}
+
+size_t es_eigen_lds(int N) { return ((size_t)N * (N | 1) + 128 + ES_THREADS) * sizeof(double) + 128 * sizeof(int); }
+
+bool es_desc_ok(const ssc_eval_set_desc* d) {
+  return d && d->P >= 1 && d->N >= 2 && d->N <= EV_MAX_N && d->steps >= 1 && d->V >= 1 && d->V <= 65535 &&
+         (int64_t)d->P * d->N <= (1 << 24) && d->predictions && d->ref_image && d->set_counts && d->eigenvalues && d->distinct;
+}
+
 bool ev_refs_ok(const ssc_eval_refs* r) {
   return r && r->I >= 1 && r->I <= (1 << 24) && r->nref >= r->I && r->nref <= (1 << 26) && r->ntok >= r->nref &&
          r->ntok <= (1 << 26) && r->W >= 1 && r->W <= 65535 && r->ref_offsets && r->tok_offsets && r->tokens && r->state;
@@ -533,6 +881,42 @@ extern "C" int ssc_eval_score(const ssc_eval_refs* r, const ssc_eval_score_desc*
   SSC_LAUNCH(ev_score, dim3(d->P * d->N), dim3(64), 0, st, a, s);
   SSC_CHECK_LAUNCH();
   SSC_LAUNCH(ev_image, dim3(d->P), dim3(256), 0, st, a, s);
+  SSC_CHECK_LAUNCH();
+  return ev_read_flag(a.flag, st);
+}
+
+extern "C" size_t ssc_eval_set_workspace_bytes(const ssc_eval_refs* r, const ssc_eval_set_desc* d) {
+  if (!es_desc_ok(d) || (r && (!ev_refs_ok(r) || !d->id_map))) return 0;
+  return es_layout(d->P, d->N, d->steps, r && !d->kernel).total;
+}
+
+extern "C" int ssc_eval_set(const ssc_eval_refs* r, const ssc_eval_set_desc* d, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+  if (!es_desc_ok(d) || (r && (!ev_refs_ok(r) || !d->id_map))) return SSC_EINVAL;
+  const EsLayout l = es_layout(d->P, d->N, d->steps, r && !d->kernel);
+  if (!workspace || workspace_bytes < l.total || (r && r->state_bytes < ev_layout(r->I, r->nref, r->ntok).total))
+    return SSC_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* b = (char*)workspace;
+  // without references no image has a kernel matrix: es_pair skips it, es_eigen writes zero eigenvalues
+  double* kmat = r ? (d->kernel ? d->kernel : (double*)(b + l.kmat)) : nullptr;
+  EsArgs a{d->predictions, d->N, d->steps, d->boundary_index, d->V, r ? r->I : 0, r ? r->W : 0, l.S, d->id_map, d->ref_image,
+           (unsigned long long*)(b + l.key), (double*)(b + l.w), (int*)(b + l.tf), (int*)(b + l.nu), (int*)(b + l.len),
+           (double*)(b + l.norm), (int*)(b + l.first), d->set_counts, kmat, d->eigenvalues, d->distinct,
+           (int*)(b + l.flag)};
+  EvState s{};
+  if (r) s = ev_state(r);
+  if (hipMemsetAsync(a.flag, 0, sizeof(int), st) != hipSuccess) return SSC_EHIP;
+  if (!r && d->kernel && hipMemsetAsync(d->kernel, 0, (size_t)d->P * d->N * d->N * sizeof(double), st) != hipSuccess) return SSC_EHIP;
+  SSC_LAUNCH(es_caption, dim3(d->P * d->N), dim3(64), 0, st, a, s);
+  SSC_CHECK_LAUNCH();
+  SSC_LAUNCH(es_pair, dim3(d->P * d->N), dim3(64), 0, st, a);
+  SSC_CHECK_LAUNCH();
+  const size_t lds = es_eigen_lds(d->N);
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)es_eigen, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return SSC_EHIP;
+  SSC_LAUNCH(es_eigen, dim3(d->P), dim3(ES_THREADS), lds, st, a);
   SSC_CHECK_LAUNCH();
   return ev_read_flag(a.flag, st);
 }

@@ -8,6 +8,10 @@ reductions (argmax, corpus BLEU sums, means) run here in float64.
     result = refs.score(predictions, boundary_index, vocabulary)        # (images, N, steps) int64 from diverse_decode
     result = refs.score_captions(json.load(open("predictions.json")))   # the JSON scripts/inference.py writes
     print("\\n".join(format_summary(result.summary())))
+
+Caption-SET diversity (the N captions of an image against each other: mBLEU-1..4, Self-CIDEr, the share of distinct captions) is
+one more library call (ssc_eval_set) on the same tensor, asked for with set_diversity=True; set_diversity(predictions, ...)
+gives mBLEU and Unique with no references at all.
 """
 import ctypes
 import json
@@ -87,15 +91,108 @@ def corpus_bleu(testlen, reflen, guess, correct) -> List[float]:
     return [float(x) for x in out]
 
 
+EIG_CUT = 1e-6   # eigenvalues of the Self-CIDEr kernel below EIG_CUT x the largest are taken as 0
+
+
+def mbleu(set_stats) -> List[float]:
+    """mBLEU-1..4 of set statistics (P, N, 10): corpus BLEU of the statistics summed over the images at sample index n, averaged
+    over n (the reduction of `mean B{k}`).  Lower = more diverse."""
+    st = np.asarray(set_stats, dtype=np.float64)
+    per = [corpus_bleu(st[:, n, 0].sum(), st[:, n, 1].sum(), st[:, n, 2:6].sum(0), st[:, n, 6:10].sum(0)) for n in range(st.shape[1])]
+    return [float(np.mean([b[k] for b in per])) for k in range(4)]
+
+
+def self_cider(eigenvalues):
+    """Self-CIDEr of one image from the eigenvalues of its caption kernel matrix: -log(sqrt(l_1) / sum sqrt(l_i)) / log N with the
+    eigenvalues below EIG_CUT l_1 set to 0.  Returns (value, degenerate): l_1 <= 0 (no caption has a weighted n-gram) gives 0."""
+    lam = np.sort(np.asarray(eigenvalues, dtype=np.float64))[::-1]
+    top = lam[0]
+    if not top > 0.0:
+        return 0.0, True
+    root = np.sqrt(np.where(lam < EIG_CUT * top, 0.0, lam))
+    return float(-np.log(root[0] / root.sum()) / np.log(len(lam))), False
+
+
+class SetDiversity:
+    """What ssc_eval_set wrote: set_stats (P, N, 10) int - BleuScorer's statistics of every caption against the other N - 1 of
+    its image -, distinct (P,) distinct captions per image, and for the images with references set_kernel (P, N, N) and
+    set_eigenvalues (P, N) descending (both 0 elsewhere)."""
+
+    def __init__(self, set_stats, distinct, kernel=None, eigenvalues=None, scored_rows=()):
+        self.set_stats, self.distinct, self.set_kernel, self.set_eigenvalues = set_stats, distinct, kernel, eigenvalues
+        self.scored_rows = list(scored_rows)
+        vals = [self_cider(eigenvalues[p]) for p in self.scored_rows]
+        self.self_cider_values = np.array([v for v, _ in vals], dtype=np.float64)
+        self.degenerate_sets = int(sum(d for _, d in vals))
+
+    def summary(self) -> Dict[str, float]:
+        s = {f"mBLEU-{k + 1}": v for k, v in enumerate(mbleu(self.set_stats))}
+        if self.scored_rows:
+            s["self-cider"] = float(np.mean(self.self_cider_values))
+        s["unique"] = float(np.mean(self.distinct / float(self.set_stats.shape[1])))
+        return s
+
+
+def _eval_set(pred: torch.Tensor, boundary_index: int, vocab_size: int, prep, id_map, ref_image, keep_kernel=True) -> SetDiversity:
+    """One ssc_eval_set call on (P, N, steps) int64 predictions on the device; prep None: no references (mBLEU / Unique only)."""
+    P, N, steps = pred.shape
+    if not 2 <= N <= MAX_SAMPLES:
+        raise ValueError(f"set diversity needs 2..{MAX_SAMPLES} captions per image, got N = {N}")
+    if not 1 <= vocab_size <= MAX_WORDS:
+        raise ValueError(f"{vocab_size} prediction ids: 1..{MAX_WORDS} are supported")
+    dev = pred.device
+    scored = prep is not None
+    counts = torch.empty(P, N, 10, dtype=torch.int32, device=dev)
+    kern = torch.empty(P, N, N, dtype=torch.float64, device=dev) if scored and keep_kernel else None
+    eig = torch.empty(P, N, dtype=torch.float64, device=dev)
+    dist = torch.empty(P, dtype=torch.int32, device=dev)
+    if ref_image is None:
+        ref_image = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    d = L.EvalSetDesc(L.ptr(pred), P, N, steps, int(boundary_index), int(vocab_size), L.ptr(id_map), L.ptr(ref_image), L.ptr(counts),
+                      L.ptr(kern), L.ptr(eig), L.ptr(dist))
+    lib = L.load()
+    rp = ctypes.byref(prep.desc) if scored else None
+    nbytes = lib.ssc_eval_set_workspace_bytes(rp, ctypes.byref(d))
+    if nbytes == 0:
+        raise ValueError(f"set diversity: arguments out of range ({P} images x {N} samples x {steps} steps)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib.ssc_eval_set(rp, ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
+    rows = [p for p, i in enumerate(ref_image.cpu().tolist()) if i >= 0] if scored else []
+    return SetDiversity(counts.cpu().numpy().astype(np.int64), dist.cpu().numpy().astype(np.int64),
+                        kern.cpu().numpy() if kern is not None else None, eig.cpu().numpy() if scored else None, rows)
+
+
+def set_diversity(predictions: torch.Tensor, boundary_index: int, vocab_size: int) -> SetDiversity:
+    """mBLEU-1..4 and Unique of (images, N, steps) int64 predictions on the device, ids 0..vocab_size-1, with no references:
+    set_diversity(pred, boundary, V).summary().  Self-CIDEr needs document frequencies: CaptionReferences.score(...,
+    set_diversity=True)."""
+    if predictions.dim() != 3 or predictions.dtype != torch.int64:
+        raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(predictions.shape)} {predictions.dtype}")
+    if not predictions.is_cuda:
+        raise ValueError("predictions must lie on the device")
+    return _eval_set(predictions.contiguous(), boundary_index, vocab_size, None, None, None)
+
+
 class EvalResult:
     """Per-candidate scores of the evaluated images (those with predictions and references, in prediction order) and the
     per-image counts, with eval.py's reductions.
       image_ids (I,); bleu (I, N, 4); rouge, cider (I, N); stats (I, N, 10) int: testlen, reflen, guess[4], correct[4]
       oracle: {"B1".."B4", "rouge", "cider"} -> (I,) best sample per image (argmax: lowest index on a tie)
       top5 (I, 5): samples by CIDEr, stable descending
-      empty_images: prediction images whose N captions are all empty (their Div-n is 0; eval.py divides by zero there)."""
+      empty_images: prediction images whose N captions are all empty (their Div-n is 0; eval.py divides by zero there).
+    With set_diversity=True also (None otherwise): set_stats (P, N, 10) and distinct (P,) over ALL prediction images, set_kernel
+    (P, N, N) and set_eigenvalues (P, N) (0 for images without references), self_cider_values (I,) per evaluated image,
+    degenerate_sets: evaluated images whose kernel matrix is 0 (Self-CIDEr 0)."""
 
-    def __init__(self, image_ids, scores, stats, image_counts, eval_rows, top5, has_style):
+    def __init__(self, image_ids, scores, stats, image_counts, eval_rows, top5, has_style, set_out: Optional[SetDiversity] = None):
+        self._set = set_out
+        self.set_stats = set_out.set_stats if set_out else None
+        self.set_kernel = set_out.set_kernel if set_out else None
+        self.set_eigenvalues = set_out.set_eigenvalues if set_out else None
+        self.distinct = set_out.distinct if set_out else None
+        self.self_cider_values = set_out.self_cider_values if set_out else None
+        self.degenerate_sets = set_out.degenerate_sets if set_out else None
         self.image_ids = [image_ids[p] for p in eval_rows]
         self.bleu = scores[eval_rows, :, :4]
         self.rouge = scores[eval_rows, :, 4]
@@ -141,6 +238,8 @@ class EvalResult:
             s["senti_prec"] = float(m / c) if c else float("nan")
             s["senti_rec"] = float(m / r) if r else float("nan")
             s["has_anp"] = float(np.mean(self.style_counts[:, 0] > 0))
+        if self._set is not None:
+            s.update(self._set.summary())
         return s
 
 
@@ -153,6 +252,13 @@ def format_summary(s: Dict[str, float]) -> List[str]:
     out += [f"top5 Div-1: {s['top5 Div-1']}", f"top5 Div-2: {s['top5 Div-2']}"]
     if "senti_prec" in s:
         out.append(f"senti_prec: {s['senti_prec']} senti_rec: {s['senti_rec']} has_anp: {s['has_anp']}")
+    # caption-set diversity (set_diversity=True): mBLEU x 100 as the BLEU lines; Self-CIDEr and Unique are shares in [0, 1]
+    for k in ("mBLEU-1", "mBLEU-2", "mBLEU-3", "mBLEU-4"):
+        if k in s:
+            out.append(f"{k}: {np.round(s[k] * 100.0, 2)}")
+    for k in ("self-cider", "unique"):
+        if k in s:
+            out.append(f"{k}: {np.round(s[k], 4)}")
     return out
 
 
@@ -222,7 +328,8 @@ class CaptionReferences:
             self._prepared[key] = _Prepared(self, ids, self.device)
         return self._prepared[key]
 
-    def _score_ids(self, pred: torch.Tensor, boundary_index: int, words: Sequence[str], image_ids: Sequence, unk: Optional[int]):
+    def _score_ids(self, pred: torch.Tensor, boundary_index: int, words: Sequence[str], image_ids: Sequence, unk: Optional[int],
+                   set_diversity: bool = False):
         if pred.dim() != 3 or pred.dtype != torch.int64:
             raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(pred.shape)} {pred.dtype}")
         P, N, steps = pred.shape
@@ -262,24 +369,33 @@ class CaptionReferences:
             lib.ssc_eval_score(ctypes.byref(prep.desc), ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
         rows = [p for p, i in enumerate(image_ids) if i in self.tokens]
         imgc = img.cpu().numpy().astype(np.int64)
+        set_out = _eval_set(pred, boundary_index, len(words), prep, id_map, ref_image) if set_diversity else None
         return EvalResult(list(image_ids), scores.cpu().numpy(), counts.cpu().numpy().astype(np.int64), imgc, rows,
-                          top5.cpu().numpy().astype(np.int64), self.style_words is not None)
+                          top5.cpu().numpy().astype(np.int64), self.style_words is not None, set_out)
 
-    def score(self, predictions: torch.Tensor, boundary_index: int, vocabulary, image_ids: Optional[Sequence] = None) -> EvalResult:
+    def score(self, predictions: torch.Tensor, boundary_index: int, vocabulary, image_ids: Optional[Sequence] = None,
+              set_diversity: bool = False) -> EvalResult:
         """predictions (images, N, steps) int64 on the device (diverse_decode's output); a row is cut at its first boundary_index.
         vocabulary: a Vocabulary (its @@UNKNOWN@@ matches nothing) or the list of words by id.  image_ids: one per prediction
-        image (default: this object's images, in order); images without references count toward Div-1 / Div-2 only."""
+        image (default: this object's images, in order); images without references count toward Div-1 / Div-2 only.
+        set_diversity: also compare each image's N captions with each other (one ssc_eval_set call): mBLEU-1..4, Self-CIDEr and
+        Unique in summary(); images without references count toward mBLEU and Unique only."""
+        if not isinstance(set_diversity, bool):
+            raise TypeError(f"set_diversity must be a bool, got {type(set_diversity).__name__}")
         if hasattr(vocabulary, "get_vocab_size"):
             words = [vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())]
         else:
             words = list(vocabulary)
         unk = words.index(UNKNOWN) if UNKNOWN in words else None
         ids = self.image_ids if image_ids is None else [_norm_id(i) for i in image_ids]
-        return self._score_ids(predictions, boundary_index, words, ids, unk)
+        return self._score_ids(predictions, boundary_index, words, ids, unk, set_diversity)
 
-    def score_captions(self, predictions) -> EvalResult:
+    def score_captions(self, predictions, set_diversity: bool = False) -> EvalResult:
         """Caption strings: [{"image_id", "caption"}, ...] (N per image in file order, as eval.py reads them) or
-        {image_id: [captions]}.  Captions are split on whitespace; every word is itself, including words no vocabulary holds."""
+        {image_id: [captions]}.  Captions are split on whitespace; every word is itself, including words no vocabulary holds.
+        set_diversity: as for score()."""
+        if not isinstance(set_diversity, bool):
+            raise TypeError(f"set_diversity must be a bool, got {type(set_diversity).__name__}")
         groups = load_predictions(predictions) if isinstance(predictions, (str, list)) else \
             OrderedDict((_norm_id(k), list(v)) for k, v in predictions.items())
         N = _samples_per_image(groups.values())
@@ -293,4 +409,4 @@ class CaptionReferences:
         for i, caps in enumerate(toks):
             for n, t in enumerate(caps):
                 arr[i, n, :len(t)] = [wid[w] for w in t]
-        return self._score_ids(torch.from_numpy(arr).to(self.device), 0, words, list(groups), None)
+        return self._score_ids(torch.from_numpy(arr).to(self.device), 0, words, list(groups), None, set_diversity)

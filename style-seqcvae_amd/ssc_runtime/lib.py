@@ -152,6 +152,11 @@ class EvalScoreDesc(C.Structure):
                 ("id_map", vp), ("style_ids", vp), ("ref_image", vp), ("scores", vp), ("counts", vp), ("image_counts", vp), ("top5", vp)]
 
 
+class EvalSetDesc(C.Structure):
+    _fields_ = [("predictions", vp), ("P", C.c_int), ("N", C.c_int), ("steps", C.c_int), ("boundary_index", C.c_int), ("V", C.c_int),
+                ("id_map", vp), ("ref_image", vp), ("set_counts", vp), ("kernel", vp), ("eigenvalues", vp), ("distinct", vp)]
+
+
 # name -> (restype, argtypes).  Every symbol include/ssc.h declares is listed; tests check they all resolve.
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -245,6 +250,8 @@ SYMBOLS = {
     "ssc_eval_prepare_refs": (_i, [C.POINTER(EvalRefs), vp]),
     "ssc_eval_score_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc)]),
     "ssc_eval_score": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc), vp, _sz, vp]),
+    "ssc_eval_set_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalSetDesc)]),
+    "ssc_eval_set": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalSetDesc), vp, _sz, vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)

@@ -2,6 +2,8 @@
 """Times the device caption evaluation (ssc_runtime.evaluation: ssc_eval_prepare_refs, ssc_eval_score) on a synthetic corpus of
 5 000 images x 20 samples x 5 references, captions of up to 20 words over a 10 000-word vocabulary, and the float64 CPU
 restatement (tests/captionevalref.py) on a slice of the same input for comparison.   python tools/eval_probe.py [--cpu-images K]
+With --set (default on) it also times the caption-set call ssc_eval_set (mBLEU / Self-CIDEr / Unique) on the same predictions and
+once at --set-samples captions per image, its host reduction, and the set restatement (tests/captionsetref.py) on the same slice.
 Both library calls read a device flag back, so wall-clock time around a call is its whole cost; the kernels' own time comes from
 events around the launches of a second call."""
 import argparse
@@ -26,6 +28,8 @@ p.add_argument("--length", type=int, default=20)
 p.add_argument("--vocab", type=int, default=10000)
 p.add_argument("--repeats", type=int, default=5)
 p.add_argument("--cpu-images", type=int, default=100, help="images of the CPU restatement's timed slice (0: skip)")
+p.add_argument("--set", type=int, default=1, help="1: also time ssc_eval_set (0: skip)")
+p.add_argument("--set-samples", type=int, default=100, help="captions per image of the second ssc_eval_set timing (0: skip)")
 a = p.parse_args()
 
 rng = np.random.default_rng(0)
@@ -105,3 +109,61 @@ if a.cpu_images:
     t = time.perf_counter() - t0
     print(f"CPU restatement (float64 Python, one thread): document frequencies {t_df * 1e3:.0f} ms; {K} images x {N} samples "
           f"scored in {t:.2f} s -> {t * I / K:.0f} s for all {I} images (linear extrapolation)")
+
+
+def time_set(pred_t, prep_desc, idm, refimg, label):
+    """ssc_eval_set alone: events around the call (3 kernels + flag read), the kernel matrix kept in the workspace."""
+    P_, N_, steps = pred_t.shape
+    cnt = torch.empty(P_, N_, 10, dtype=torch.int32, device=dev)
+    eig = torch.empty(P_, N_, dtype=torch.float64, device=dev)
+    dist = torch.empty(P_, dtype=torch.int32, device=dev)
+    sd = Lb.EvalSetDesc(Lb.ptr(pred_t), P_, N_, steps, 1, V, Lb.ptr(idm), Lb.ptr(refimg), Lb.ptr(cnt), None, Lb.ptr(eig), Lb.ptr(dist))
+    nbytes = lib.ssc_eval_set_workspace_bytes(ctypes.byref(prep_desc), ctypes.byref(sd))
+    wsp = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    lib.ssc_eval_set(ctypes.byref(prep_desc), ctypes.byref(sd), Lb.ptr(wsp), nbytes, Lb.stream_ptr())   # warm-up
+    ms = []
+    for _ in range(a.repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        lib.ssc_eval_set(ctypes.byref(prep_desc), ctypes.byref(sd), Lb.ptr(wsp), nbytes, Lb.stream_ptr())
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    print(f"ssc_eval_set alone, {label} ({P_} x {N_}, events, 3 kernels + flag read, workspace {nbytes / 2**20:.0f} MiB): "
+          f"median {np.median(ms):.2f} ms, min {np.min(ms):.2f} ms")
+
+
+if a.set:
+    from ssc_runtime import evaluation as E  # noqa: E402
+    time_set(pt, prepd.desc, id_map, ref_image, "the corpus above")
+    t0 = time.perf_counter()
+    res = cr.score(pt, 1, words, set_diversity=True)
+    t_all = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    sd_ = E.SetDiversity(res.set_stats, res.distinct, res.set_kernel, res.set_eigenvalues, range(I))
+    ss = sd_.summary()
+    print(f"score(set_diversity=True) (both calls, uploads, copies back incl. the kernel matrices): {t_all * 1e3:.1f} ms; "
+          f"host reduction of the set numbers (Self-CIDEr per image, mBLEU, unique): {(time.perf_counter() - t0) * 1e3:.1f} ms")
+    print({k: round(v, 6) for k, v in ss.items()}, "degenerate sets", sd_.degenerate_sets)
+    if a.set_samples:
+        Ns = a.set_samples
+        big = np.minimum(rng.zipf(1.3, size=(I, Ns, Lmax)), V - 3) + 1
+        lens = rng.integers(8, Lmax + 1, size=(I, Ns, 1))
+        big = np.where(np.arange(Lmax)[None, None, :] < lens, big, 1).astype(np.int64)
+        time_set(torch.from_numpy(big).to(dev), prepd.desc, id_map, ref_image, f"N = {Ns}")
+    if a.cpu_images:
+        import captionsetref as S
+        K = a.cpu_images
+        caps = [[[words[t] for t in list(row)[: list(row).index(1) if 1 in row else len(row)]] for row in pred[i]] for i in range(K)]
+        t0 = time.perf_counter()
+        df, n_img = S.reference_df([[r.split() for r in refs[i]] for i in ids])   # document frequencies over all images
+        t_df = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        st = np.stack([S.set_stats(c) for c in caps])
+        for c in caps:
+            S.self_cider(S.eigenvalues(S.kernel_matrix(c, df, n_img)))
+            S.distinct(c)
+        S.mbleu(st)
+        t = time.perf_counter() - t0
+        print(f"CPU set restatement (float64 Python, one thread): document frequencies {t_df * 1e3:.0f} ms; {K} images x {N} samples "
+              f"in {t:.2f} s -> {t * I / K:.0f} s for all {I} images (linear extrapolation)")
