@@ -770,6 +770,49 @@ int ssc_decode_sampled_beam(const ssc_model_cfg* cfg, const ssc_params* p, const
                             int with_replacement, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diverse beam search (Vijayakumar et al., "Diverse Beam Search", AAAI 2018: the "Div-BS" rows of the diverse-captioning papers).
+ * Deterministic: the k beams of a batch entry are `groups` = Gr groups of k' = k / Gr consecutive beams (beam g * k' + j), searched
+ * in order g = 0 .. Gr - 1 inside every step.  lp = the log_softmax of a row's logits exactly as ssc_beam_step_fsm takes it with
+ * raw_logits = 1 (bit-equal to ssc_log_softmax); with raw_logits = 0 the scores are log-probs as given.  c_g[v] = the number of
+ * beams of groups 0 .. g - 1 of this entry whose token selected AT THIS STEP is v (the forced END of an ended beam and an empty
+ * slot are not counted).
+ *   step t >= 1, live beam (g, j) with running TRUE log-prob phi (ssc_beam_desc.last_lp): r_v = lp_v - (strength * c_g[v]) (one
+ *     fp32 multiply, one fp32 subtract; c = 0 leaves lp_v untouched); its candidates are the n = per_node tokens of largest r_v,
+ *     descending (ties: lower token), each with the augmented sum a = phi + r_v and the true sum s = phi + lp_v.
+ *   An ended beam (last token end_index): one candidate, end_index, with a = s = phi exactly; its scores are not read.
+ *   Group merge: the k' candidates of largest a among the group's k' * n, descending (ties: lower candidate index j * n + slot);
+ *     output slot g * k' + i gets that candidate's token, back-pointer g * k' + j and the TRUE sum s: penalties steer a step's
+ *     choice and never accumulate.
+ *   step 0: one row per entry; every group takes the k' tokens of largest r_v of that row (phi = 0, ties: lower token).
+ * A slot with no finite candidate emits end_index at -inf with the identity back-pointer.  ctl / host_flag: the early-stop protocol
+ * of ssc_beam_desc (step 0 included).  Outputs are group-major and NOT sorted across groups: the best caption of an entry is the
+ * arg-max of its log-probs.  groups = 1 is ssc_beam_first_fsm / ssc_beam_step_fsm with the trivial machine, bit for bit;
+ * strength = 0 runs every group as a beam-k' search on its own rows.
+ * Limits: trivial machine only (dims.S = 1, fsm / tables / mach NULL), 1 <= k <= 32, 1 <= n <= 32, k, n <= V, k % groups == 0,
+ * B * k <= 2^24, strength >= 0 and finite - SSC_EINVAL beyond them.  No atomics in the choice: two calls on the same inputs are
+ * bit-identical.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int groups;       /* Gr >= 1, divides the beam */
+  float strength;   /* lambda >= 0: the Hamming penalty per earlier selection of a token at the same step */
+} ssc_diverse_desc;
+/* Step 0 from d->scores (B, V) ld d->ld.  Uses B, beam, dims.V, raw_logits, end_index, pred / lp_out (B, k), scratch_val
+ * (>= B * k floats) and scratch_idx (>= B * k): every row's k best (lp, token), ctl / max_steps / host_flag. */
+int ssc_beam_first_diverse(const ssc_beam_desc* d, const ssc_diverse_desc* s, void* stream);
+/* Step d->step_index >= 1 from d->scores (B * k, V): last_pred / last_lp (B, k) -> pred / lp_out / backptr (B, k).  With
+ * m = min(per_node + k - k / groups, V): scratch_val >= B * k * m floats, scratch_idx >= B * k * m - every live row's m best
+ * (lp, token), which hold its per_node best under any penalty of the other groups. */
+int ssc_beam_step_diverse(const ssc_beam_desc* d, const ssc_diverse_desc* s, void* stream);
+/* The whole diverse beam search of one diverse-decode call as ONE library call: the loop of ssc_decode_search with S = 1, beam k,
+ * per_node n and no machine (d->fsm = d->tables = d->mach = NULL), the two steps above in place of ssc_beam_first_fsm /
+ * ssc_beam_step_fsm on the raw logits; the same step forms (attention table, parent lists, un-gathered states, state planes),
+ * skip_dead, early stop and bounded run-ahead.  d->eps (max_steps - 1, B * k, Z).  Out: d->predictions (B, k, max_steps)
+ * group-major - columns >= ctl[0] hold end_index -, d->log_probs (B, k): the true summed log-probs, not sorted across groups. */
+size_t ssc_decode_diverse_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_diverse_desc* s);
+int ssc_decode_diverse_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_diverse_desc* s,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diverse-caption evaluation (eval/eval.py:95-472 with the coco-caption scorers it calls): BLEU-1..4 (BleuScorer, option
  * "closest"), ROUGE-L (Rouge, beta 1.2) and CIDEr-D (CiderScorer, sigma 6) of every candidate; distinct 1- / 2-grams of every
  * image's N captions and of its top 5 by CIDEr (Div-n), and style-word counts.  The reductions over candidates (oracle argmax,

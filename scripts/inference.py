@@ -83,7 +83,8 @@ def main():
     extra = {"mean_choice": {}} if _C.MODEL.SENTIMENT_VAE == 2 else {}   # (per-region attribute MEANS come with the data: data.obj)
     sampler = sampling.from_config(_C.MODEL)   # MODEL.DECODE_SAMPLER / STOCHASTIC_BEAM_SEARCH: None = beam search
     sampled_beam = sampling.sampled_beam_from_config(_C.MODEL)   # MODEL.SAMPLED_BEAM_SEARCH: the word sampler at BEAM_SIZE
-    model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, **extra).to(device)
+    diverse = sampling.diverse_beam_from_config(_C.MODEL)   # MODEL.DIVERSE_BEAM_SEARCH: groups of beams with a Hamming penalty
+    model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, diverse_beam=diverse, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
     model.eval()
@@ -95,6 +96,8 @@ def main():
         what = ("MODEL.STOCHASTIC_BEAM_SEARCH" if sampler.beam_search else "MODEL.SAMPLED_BEAM_SEARCH" if sampled_beam
                 else f"MODEL.DECODE_SAMPLER {_C.MODEL.DECODE_SAMPLER!r}")
         raise SystemExit(f"{what} does not take constraints: constrained sampling is not supported")
+    if diverse is not None and (_A.constraints_json or _A.boxes_json):
+        raise SystemExit("MODEL.DIVERSE_BEAM_SEARCH does not take constraints")
     boundary = vocabulary.get_token_index("@@BOUNDARY@@")
     predictions = []
     id2word = np.array([vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())], dtype=object)
@@ -150,9 +153,14 @@ def main():
                 ncons = torch.tensor([len(constraints.get(int(data.image_id[lo + i]), [])[:kmax]) for i in range(n_here)]
                                      ).repeat_interleave(n_z)
             obj = data.obj[lo: lo + n_here, : feats.size(1)].to(device) if getattr(data, "obj", None) is not None else None
-            pred, _ = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
-                                     num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
-                                     obj_means=obj, sampler=sampler, sampled_beam=sampled_beam)
+            if diverse is not None:   # every group's best caption: N_Z_SAMPLES * DIVERSE_BEAM_GROUPS captions per image
+                pred = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
+                                      diverse_beam=diverse, return_groups=True)[0]
+                pred = pred.reshape(pred.size(0), n_z * diverse.groups, pred.size(-1))
+            else:
+                pred, _ = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
+                                         num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
+                                         obj_means=obj, sampler=sampler, sampled_beam=sampled_beam)
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
             if _A.references:
@@ -163,7 +171,7 @@ def main():
             n_keep = np.where(is_end.any(-1), is_end.argmax(-1), ids.shape[-1])
             for i in range(ids.shape[0]):
                 image_id = int(data.image_id[lo + i])
-                for k in range(n_z):
+                for k in range(ids.shape[1]):
                     predictions.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))

@@ -18,12 +18,14 @@ namespace {
 inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The selection a search runs: beam search (the machine's top-k), the stochastic beam search (Gumbel-top-k, sbs.hip) or the
-// sampled-node beam search (a word sampler's draws per beam, sampled_beam.hip).
-enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED };
+// sampled-node beam search (a word sampler's draws per beam, sampled_beam.hip) or the diverse beam search (groups of beams with a
+// Hamming penalty, diverse_beam.hip).
+enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED, SEARCH_DIVERSE };
 
 // The vocabulary head of the later steps leaves per-tile records instead of logits (ssc_decode_step_desc.topk_part) when the machine
 // is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.  Beam search
-// only: any token can win a Gumbel draw or a sampler's draw, so those selections read the raw logits.
+// only: any token can win a Gumbel draw or a sampler's draw, and a penalised row needs more than its two best tokens, so those
+// selections read the raw logits.
 bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d, SearchKind kind) {
   const long G = (long)d->nimg * d->n_samples * d->S * d->beam;
   return kind == SEARCH_BEAM && d->S == 1 && !d->fsm && !d->tables && d->per_node <= 2 && !cfg->tied && cfg->gemm_mode != 2 &&
@@ -40,7 +42,8 @@ struct SearchLayout {
   size_t parent0;      // (B, SB) int64 zeros: every beam of the first expanded step descends from the one start row
   size_t lp[2];        // (B, S, beam) float
   size_t gs[2];        // gumbel: (B, beam) float, the beams' G (empty for beam search)
-  size_t sval, sidx;   // B*S*SB*per_node (gumbel: twice as many values - the candidates' G and log-probs)
+  size_t sval, sidx;   // B*S*SB*per_node (gumbel: twice as many values - the candidates' G and log-probs; diverse: the rows' lists,
+                       // `list` entries per row instead of per_node)
   size_t alpha;        // (G, R)
   size_t logits;       // (G, V); (B, V) when the later steps leave records
   size_t parts;        // (G, ceil(V / 128), 6) records
@@ -49,8 +52,9 @@ struct SearchLayout {
   size_t total;
 };
 
-SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, SearchKind kind) {
+SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, SearchKind kind, int list = 0) {
   SearchLayout l;
+  const size_t per_row = kind == SEARCH_DIVERSE ? (size_t)std::max(list, d->beam) : (size_t)d->per_node;
   const bool gumbel = kind == SEARCH_GUMBEL;
   const size_t B = (size_t)d->nimg * d->n_samples, SB = (size_t)d->S * d->beam, G = B * SB;
   const size_t H = cfg->H;
@@ -67,8 +71,8 @@ SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, S
   l.parent0 = o; o += a256(G * 8);
   for (int g = 0; g < 2; ++g) { l.lp[g] = o; o += a256(G * 4); }
   for (int g = 0; g < 2; ++g) { l.gs[g] = o; o += a256(gumbel ? G * 4 : 0); }
-  l.sval = o; o += a256(B * d->S * SB * d->per_node * 4 * (gumbel ? 2 : 1));
-  l.sidx = o; o += a256(B * d->S * SB * d->per_node * 8);
+  l.sval = o; o += a256(B * d->S * SB * per_row * 4 * (gumbel ? 2 : 1));
+  l.sidx = o; o += a256(B * d->S * SB * per_row * 8);
   l.alpha = o; o += a256(G * (size_t)d->R * 4);
   const bool parts = search_uses_parts(cfg, d, kind);
   l.logits = o; o += a256((parts ? B : G) * (size_t)cfg->V * 4);
@@ -120,7 +124,8 @@ extern "C" size_t ssc_decode_search_workspace_bytes(const ssc_model_cfg* cfg, co
 namespace {
 
 // The selections the search loop below runs: beam search (the machine's top-k, ssc_beam_*_fsm / ssc_beam_step_parts), the
-// stochastic beam search (Gumbel-top-k, sbs.hip) and the sampled-node beam search (sampled_beam.hip).  first() selects step 0;
+// stochastic beam search (Gumbel-top-k, sbs.hip), the sampled-node beam search (sampled_beam.hip) and the diverse beam search
+// (diverse_beam.hip).  first() selects step 0;
 // step(a) a later step, reading the running state of generation a and writing generation 1 - a.
 struct BeamSelect {
   bool use_parts;
@@ -141,6 +146,12 @@ struct SampledSelect {   // step 0 is the word samplers' sample_beams: the plain
   int with_replacement;
   int first(ssc_beam_desc* bd, hipStream_t st) const { return ssc_beam_first_fsm(bd, st); }
   int step(ssc_beam_desc* bd, int, hipStream_t st) const { return ssc_beam_step_sampled(bd, s, with_replacement, st); }
+};
+
+struct DiverseSelect {
+  const ssc_diverse_desc* s;
+  int first(ssc_beam_desc* bd, hipStream_t st) const { return ssc_beam_first_diverse(bd, s, st); }
+  int step(ssc_beam_desc* bd, int, hipStream_t st) const { return ssc_beam_step_diverse(bd, s, st); }
 };
 
 template <class Select>
@@ -331,4 +342,28 @@ extern "C" int ssc_decode_sampled_beam(const ssc_model_cfg* cfg, const ssc_param
   const SearchLayout l = search_layout(cfg, d, SEARCH_SAMPLED);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   return search_run(cfg, p, d, l, (char*)workspace, SampledSelect{s, with_replacement}, false, (hipStream_t)stream);
+}
+
+// the diverse beam search: S = 1, no machine, the limits of ssc_beam_step_diverse
+static bool dbs_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_diverse_desc* s) {
+  if (!desc_ok(cfg, d) || !s) return false;
+  if (d->S != 1 || d->fsm || d->tables || d->mach) return false;
+  return ssc_diverse_beam_ok(d->nimg * d->n_samples, d->beam, d->per_node, cfg->V, s);
+}
+
+extern "C" size_t ssc_decode_diverse_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
+                                                          const ssc_diverse_desc* s) {
+  if (!cfg || !d || !s || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
+      d->R <= 0 || s->groups < 1 || d->beam % s->groups != 0)
+    return 0;
+  return search_layout(cfg, d, SEARCH_DIVERSE, ssc_diverse_beam_list(d->beam, s->groups, d->per_node, cfg->V)).total;
+}
+
+extern "C" int ssc_decode_diverse_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                       const ssc_diverse_desc* s, void* workspace, size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);
+  if (!p || !workspace || !dbs_search_ok(cfg, d, s)) return SSC_EINVAL;
+  const SearchLayout l = search_layout(cfg, d, SEARCH_DIVERSE, ssc_diverse_beam_list(d->beam, s->groups, d->per_node, cfg->V));
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  return search_run(cfg, p, d, l, (char*)workspace, DiverseSelect{s}, false, (hipStream_t)stream);
 }

@@ -140,5 +140,9 @@ int ssc_decode_parts_enabled();        // the "dec_parts" switch (decode.hip): v
 // the limits of the sampled-node beam search (sampled_beam.hip, include/ssc.h: ssc_beam_step_sampled) for B entries of k beams,
 // n candidates per beam over V tokens
 bool ssc_sampled_beam_ok(int B, int k, int n, int V, const ssc_sampler_desc* s);
+// the limits of the diverse beam search (diverse_beam.hip, include/ssc.h: ssc_diverse_desc) for B entries of k beams, n candidates per
+// beam over V tokens; the entries of a row's list at a later step (n + k - k / groups, at most V)
+bool ssc_diverse_beam_ok(int B, int k, int n, int V, const ssc_diverse_desc* s);
+int ssc_diverse_beam_list(int k, int groups, int n, int V);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

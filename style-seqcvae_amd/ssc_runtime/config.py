@@ -75,6 +75,12 @@ def _defaults() -> dict:
             # DECODE_SAMPLER multinomial / top-k / top-p, STOCHASTIC_BEAM_SEARCH False and no CBS.  SAMPLER_WITH_REPLACEMENT: the
             # samplers' with_replacement (the draws of one beam may repeat a word)
             "SAMPLED_BEAM_SEARCH": False, "SAMPLER_WITH_REPLACEMENT": False,
+            # diverse beam search (Vijayakumar et al., AAAI 2018: the "Div-BS" baseline; ssc_runtime/sampling.py DiverseBeam): the
+            # BEAM_SIZE beams are DIVERSE_BEAM_GROUPS groups searched in order, a word the earlier groups chose at a step costs the
+            # later ones DIVERSE_BEAM_STRENGTH per choice; deterministic.  Needs DECODE_SAMPLER "beam", STOCHASTIC_BEAM_SEARCH and
+            # SAMPLED_BEAM_SEARCH False, no CBS and BEAM_SIZE % DIVERSE_BEAM_GROUPS == 0; scripts/inference.py then writes the best
+            # caption of every group (N_Z_SAMPLES * DIVERSE_BEAM_GROUPS per image)
+            "DIVERSE_BEAM_SEARCH": False, "DIVERSE_BEAM_GROUPS": 1, "DIVERSE_BEAM_STRENGTH": 0.5,
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,

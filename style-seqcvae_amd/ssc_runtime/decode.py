@@ -322,6 +322,25 @@ class DecodeEngine:
                                lambda p, sd, ws: self.lib.ssc_decode_sampled_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                   C.byref(sdesc), rep, *ws))
 
+    def diverse_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
+                     max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], diverse,
+                     early_stop: bool = True, skip_dead: bool = True):
+        """The whole diverse beam search of one call in ONE library call (ssc_decode_diverse_beam): `beam` beams per batch entry in
+        diverse.groups groups (sampling.DiverseBeam), searched in order inside every step with the Hamming penalty
+        diverse.strength; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples, batch entry
+        b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*beam, Z): the noise of every step.
+        -> (predictions (B, beam, steps) int64 group-major, log_probs (B, beam): true summed log-probs, NOT sorted across groups -
+        the best caption of an entry is the arg-max)."""
+        V = self.dims.V
+        if not (1 <= beam <= min(32, V) and 1 <= per_node <= min(32, V)):
+            raise ValueError(f"diverse beam search needs 1 <= beam, per_node <= min(32, V), got beam {beam}, per_node {per_node}")
+        diverse.check_beam(beam)
+        ddesc = diverse.desc()
+        return self._beam_call(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                               lambda cfg, sd: self.lib.ssc_decode_diverse_beam_workspace_bytes(cfg, sd, C.byref(ddesc)),
+                               lambda p, sd, ws: self.lib.ssc_decode_diverse_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
+                                                                                  C.byref(ddesc), *ws))
+
     def _beam_call(self, ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
                    workspace_bytes, call):
         """The shared body of the one-call searches on the trivial machine: the search descriptor, outputs, host flag and

@@ -22,7 +22,7 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
                    num_constraints: Optional[torch.Tensor] = None, min_constraints_to_satisfy: int = 0,
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
-                   sample_seed: Optional[int] = None, sampled_beam: bool = False):
+                   sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     fsm: None (trivial one-state machine, what MAX_GIVEN_CONSTRAINTS: 0 produces), or (nimg, S, S, V) uint8 - ONE machine per
     image, shared by its n_samples latent samples through an index list -, or (nimg*n_samples, S, S, V) (a copy per sample).
@@ -43,7 +43,21 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     state as a beam call does and sees the same latent noise as a beam-1 call.
     sampled_beam: with a word sampler, run it as the reference's BeamSearch does (DecodeEngine.sampled_beam) at any beam: step 0
     takes the top `beam` words, every later step draws per_node (default beam // 2, or beam) candidates per beam and keeps the
-    `beam` best by summed log-prob; beam 0 of every (image, sample) is returned; needs fsm = None."""
+    `beam` best by summed log-prob; beam 0 of every (image, sample) is returned; needs fsm = None.
+    diverse_beam: a sampling.DiverseBeam(groups, strength) - the deterministic diverse beam search (DecodeEngine.diverse_beam) at
+    `beam`, per_node by default the reference's rule on the group width (beam // groups // 2, or beam // groups); needs
+    sampler = None and fsm = None.  The caption with the highest log-prob of every (image, sample) is returned (ties: the lower
+    beam); with return_groups=True instead every group's best: (predictions (nimg, n_samples, groups, steps), steps, log_probs
+    (nimg, n_samples, groups))."""
+    if diverse_beam is not None:
+        if sampler is not None or sampled_beam:
+            raise ValueError("the diverse beam search is deterministic: it takes no sampler")
+        if fsm is not None:
+            raise ValueError("the diverse beam search does not take constraints (fsm)")
+        diverse_beam.check_beam(beam)
+        per_node = per_node or diverse_beam.per_node(beam)
+    elif return_groups:
+        raise ValueError("return_groups needs diverse_beam")
     gumbel = sampler is not None and sampler.beam_search
     if sampled_beam:
         if sampler is None or gumbel:
@@ -97,6 +111,11 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
             gen.manual_seed(seed)
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
+        if diverse_beam is not None:
+            beams, lps = dec.diverse_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, diverse_beam,
+                                          early_stop=early_stop, skip_dead=skip_now)
+            calls["k"] = beams.size(-1)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
         if sampled_beam:
             beams, lps = dec.sampled_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
                                           seed if sample_seed is None else sample_seed, early_stop=early_stop, skip_dead=skip_now)
@@ -119,6 +138,18 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
         return beams, lps
 
     beams, lps = search(skip)
+    if diverse_beam is not None:   # group-major, not sorted across groups: the arg-max inside each group, then over the entry
+        Gr = diverse_beam.groups
+        steps = beams.size(-1)
+        glp = lps.view(B, Gr, beam // Gr)
+        gi = glp.argmax(-1)   # (ties: the lower beam)
+        gbest = beams.view(B, Gr, beam // Gr, steps).gather(2, gi.view(B, Gr, 1, 1).expand(B, Gr, 1, steps)).squeeze(2)
+        gbest_lp = glp.gather(2, gi.unsqueeze(-1)).squeeze(-1)
+        if return_groups:
+            return gbest.view(nimg, n_samples, Gr, steps), calls["k"], gbest_lp.view(nimg, n_samples, Gr)
+        bi = gbest_lp.argmax(-1)
+        best = gbest.gather(1, bi.view(B, 1, 1).expand(B, 1, steps)).squeeze(1)
+        return best.view(nimg, n_samples, -1), calls["k"]
     if trivial or fsm.size(1) == 1:
         best = beams[:, 0, 0, :]
     else:

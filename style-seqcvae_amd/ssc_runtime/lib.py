@@ -142,6 +142,10 @@ class GumbelDesc(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class DiverseDesc(C.Structure):
+    _fields_ = [("groups", C.c_int), ("strength", C.c_float)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -246,6 +250,11 @@ SYMBOLS = {
     "ssc_decode_sampled_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sampled_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), _i, vp,
                                      _sz, vp]),
+    "ssc_beam_first_diverse": (_i, [C.POINTER(BeamDesc), C.POINTER(DiverseDesc), vp]),
+    "ssc_beam_step_diverse": (_i, [C.POINTER(BeamDesc), C.POINTER(DiverseDesc), vp]),
+    "ssc_decode_diverse_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(DiverseDesc)]),
+    "ssc_decode_diverse_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(DiverseDesc), vp, _sz,
+                                     vp]),
     "ssc_eval_refs_bytes": (_sz, [_i, _i, _i]),
     "ssc_eval_prepare_refs": (_i, [C.POINTER(EvalRefs), vp]),
     "ssc_eval_score_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc)]),

@@ -11,6 +11,9 @@ p = 1 (the reference's fp32 cumsum can fall short of 1 and drop tail tokens ther
 
 GumbelSampler (beam_search.py:294-432) is the stochastic beam search: `beam` captions per batch entry without replacement, at any
 beam (DecodeEngine.stochastic_beam / ssc_decode_stochastic_beam).
+
+DiverseBeam is no sampler: the deterministic diverse beam search (Vijayakumar et al., AAAI 2018; DecodeEngine.diverse_beam /
+ssc_decode_diverse_beam, MODEL.DIVERSE_BEAM_SEARCH), the "Div-BS" baseline the sampled decoders are compared with.
 """
 from . import lib as _lib
 
@@ -113,15 +116,78 @@ class GumbelSampler(Sampler):
         return d
 
 
+class DiverseBeam:
+    """Diverse beam search: the beam is `groups` groups of beam // groups beams searched in order; a word that beams of the
+    earlier groups selected at a step is ranked `strength` lower per selection for the later ones (Hamming diversity,
+    ssc_diverse_desc in include/ssc.h).  groups = 1 is beam search; strength = 0 runs the groups as independent searches."""
+
+    def __init__(self, groups: int = 1, strength: float = 0.5) -> None:
+        if int(groups) != groups or groups < 1:
+            raise ValueError(f"groups must be a positive integer, got {groups}")
+        if not (strength >= 0 and strength < float("inf")):
+            raise ValueError(f"strength must be finite and not negative, got {strength}")
+        self.groups = int(groups)
+        self.strength = float(strength)
+
+    def check_beam(self, beam: int) -> None:
+        if beam % self.groups != 0:
+            raise ValueError(f"the beam size ({beam}) must be a multiple of the number of groups ({self.groups})")
+
+    def per_node(self, beam: int) -> int:
+        """The reference's per-node rule (beam // 2, or beam) applied to the group width."""
+        kp = beam // self.groups
+        return kp // 2 or kp
+
+    def desc(self) -> "_lib.DiverseDesc":
+        """The C struct ssc_diverse_desc."""
+        d = _lib.DiverseDesc()
+        d.groups = self.groups
+        d.strength = self.strength
+        return d
+
+    def __repr__(self):
+        return f"DiverseBeam(groups={self.groups}, strength={self.strength})"
+
+
+def diverse_beam_from_config(model_cfg):
+    """MODEL.DIVERSE_BEAM_SEARCH / DIVERSE_BEAM_GROUPS / DIVERSE_BEAM_STRENGTH -> DiverseBeam, or None when off.  Needs
+    DECODE_SAMPLER "beam", STOCHASTIC_BEAM_SEARCH and SAMPLED_BEAM_SEARCH False, USE_CBS False and
+    BEAM_SIZE % DIVERSE_BEAM_GROUPS == 0."""
+    if not bool(getattr(model_cfg, "DIVERSE_BEAM_SEARCH", False)):
+        return None
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if kind != "beam":
+        raise ValueError(f"MODEL.DIVERSE_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the diverse "
+                         "beam search is deterministic)")
+    if bool(getattr(model_cfg, "STOCHASTIC_BEAM_SEARCH", False)):
+        raise ValueError("MODEL.DIVERSE_BEAM_SEARCH and MODEL.STOCHASTIC_BEAM_SEARCH exclude each other")
+    if bool(getattr(model_cfg, "SAMPLED_BEAM_SEARCH", False)):
+        raise ValueError("MODEL.DIVERSE_BEAM_SEARCH and MODEL.SAMPLED_BEAM_SEARCH exclude each other")
+    if bool(getattr(model_cfg, "USE_CBS", False)):
+        raise ValueError("MODEL.DIVERSE_BEAM_SEARCH does not take constraints: MODEL.USE_CBS must be False")
+    groups = int(getattr(model_cfg, "DIVERSE_BEAM_GROUPS", 1))
+    strength = float(getattr(model_cfg, "DIVERSE_BEAM_STRENGTH", 0.5))
+    if groups < 1:
+        raise ValueError(f"MODEL.DIVERSE_BEAM_GROUPS must be at least 1, got {groups}")
+    if not (strength >= 0 and strength < float("inf")):
+        raise ValueError(f"MODEL.DIVERSE_BEAM_STRENGTH must be finite and not negative, got {strength}")
+    beam = int(model_cfg.BEAM_SIZE)
+    if beam % groups != 0:
+        raise ValueError(f"MODEL.BEAM_SIZE ({beam}) must be a multiple of MODEL.DIVERSE_BEAM_GROUPS ({groups})")
+    return DiverseBeam(groups, strength)
+
+
 def from_config(model_cfg):
     """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
     STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
-    "beam" gives GumbelSampler(SAMPLER_TEMPERATURE).  Checks MODEL.SAMPLED_BEAM_SEARCH (sampled_beam_from_config)."""
+    "beam" gives GumbelSampler(SAMPLER_TEMPERATURE).  Checks MODEL.SAMPLED_BEAM_SEARCH (sampled_beam_from_config) and
+    MODEL.DIVERSE_BEAM_SEARCH (diverse_beam_from_config)."""
     kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
     T = float(model_cfg.SAMPLER_TEMPERATURE)
     sbs = bool(getattr(model_cfg, "STOCHASTIC_BEAM_SEARCH", False))
     rep = bool(getattr(model_cfg, "SAMPLER_WITH_REPLACEMENT", False))
     sampled_beam_from_config(model_cfg)
+    diverse_beam_from_config(model_cfg)
     if sbs and kind != "beam":
         raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
                          "samplers draw one word per row; the stochastic beam search is a kind of beam search)")

@@ -58,7 +58,7 @@ class UpDownCaptioner(nn.Module):
                  max_caption_length=20, beam_size=1, use_cbs=False, min_constraints_to_satisfy=2, z_space=150,
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
                  sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None,
-                 sampled_beam=False):
+                 sampled_beam=False, diverse_beam=None):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
@@ -70,8 +70,17 @@ class UpDownCaptioner(nn.Module):
         per_node_beam_size beam_size // 2 (beam_size when that is 0) in one library call and returns beam 0; no CBS decode.
         `sampled_beam` (MODEL.SAMPLED_BEAM_SEARCH) with a word sampler: the eval forward runs the sampled-node beam search
         (ssc_decode_sampled_beam: the reference's BeamSearch with that sampler) at beam_size, per_node_beam_size as above, and
-        returns beam 0."""
+        returns beam 0.
+        `diverse_beam` (MODEL.DIVERSE_BEAM_SEARCH): a sampling.DiverseBeam(groups, strength) - the eval forward runs the diverse beam
+        search (ssc_decode_diverse_beam) at beam_size in one library call and returns the caption with the highest log-prob; no
+        sampler, no CBS decode, beam_size a multiple of the groups."""
         super().__init__()
+        if diverse_beam is not None:
+            if sampler is not None:
+                raise ValueError("MODEL.DIVERSE_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam' without MODEL.STOCHASTIC_BEAM_SEARCH")
+            if beam_size % diverse_beam.groups != 0:
+                raise ValueError(f"MODEL.BEAM_SIZE ({beam_size}) must be a multiple of MODEL.DIVERSE_BEAM_GROUPS ({diverse_beam.groups})")
+        self.diverse_beam = diverse_beam
         if sampled_beam and (sampler is None or sampler.beam_search):
             raise ValueError("MODEL.SAMPLED_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p'")
         if sampler is not None and not sampler.beam_search and not sampled_beam and beam_size != 1:
@@ -149,7 +158,7 @@ class UpDownCaptioner(nn.Module):
         """Instantiate from a Config (updown_captioner.py:141-166); extra kwargs such as cbs_simple are ignored as in
         the reference.  mean_choice=... (SENTIMENT_VAE = 2) is handed to the constructor.  MODEL.SAMPLED_BEAM_SEARCH is read only
         with a sampler=... (the decode's); a model built without one (scripts/train.py) ignores it, as it ignores the other
-        decode keys."""
+        decode keys; diverse_beam=... (sampling.diverse_beam_from_config) likewise comes from the caller."""
         _C = config
         return cls(vocabulary=kwargs.pop("vocabulary"), image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
                    embedding_size=_C.MODEL.EMBEDDING_SIZE, hidden_size=_C.MODEL.HIDDEN_SIZE,
@@ -160,7 +169,8 @@ class UpDownCaptioner(nn.Module):
                    sentiment_vae=_C.MODEL.SENTIMENT_VAE, senti_prior_multip=_C.MODEL.SENTI_PRIOR_MULTIP,
                    latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
                    device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
-                   sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL))
+                   sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
+                   diverse_beam=kwargs.get("diverse_beam"))
 
     def _initialize_glove(self):
         """GloVe 42B (+ dependency embeddings for 600-d) rows for the vocabulary (updown_captioner.py:168-226).
@@ -305,6 +315,11 @@ class UpDownCaptioner(nn.Module):
                                  f"{self.sampler.name!r}: constrained sampling is not supported")
             with torch.no_grad():
                 return {"predictions": self._sample_decode(image_features, obj_means, sentiment)}
+        if self.diverse_beam is not None:
+            if self._use_cbs and fsm is not None:
+                raise ValueError("MODEL.USE_CBS with a constraint machine cannot be combined with MODEL.DIVERSE_BEAM_SEARCH")
+            with torch.no_grad():
+                return {"predictions": self._diverse_beam_decode(image_features, obj_means, sentiment)}
         with torch.no_grad():
             if self._use_cbs and fsm is not None:
                 fsm_d = fsm.to(dev).to(torch.uint8)
@@ -342,6 +357,22 @@ class UpDownCaptioner(nn.Module):
         sent = sentiment.reshape(B) if sentiment is not None else None
         pred, _ = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed)
         return pred
+
+    def _diverse_beam_decode(self, image_features, obj_means, sentiment):
+        """Eval forward with MODEL.DIVERSE_BEAM_SEARCH: the diverse beam search in one library call (DecodeEngine.diverse_beam), the
+        noise drawn as the beam path draws it; the caption with the highest log-prob of every image (ties: the lower beam)."""
+        B = image_features.size(0)
+        L = self._max_caption_length
+        dev = self._eng.device
+        ctx = self._image_context(image_features, obj_means)
+        k = self._beam_search.beam_size
+        eps0 = self._draw_eps(1, B, dev)[0]
+        eps = self._draw_eps(L - 1, B * k, dev) if L > 1 else None
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        beams, lps = self._dec.diverse_beam(ctx, sent, 1, k, self.diverse_beam.per_node(k), L, self._boundary_index, eps0, eps,
+                                            self.diverse_beam)
+        bi = lps.argmax(-1)
+        return beams.gather(1, bi.view(B, 1, 1).expand(B, 1, beams.size(-1))).squeeze(1)
 
     def _image_context(self, image_features, obj_means=None):
         """Per-image terms (mask, averaged features, projected features, hoisted gate term) for the eval decode step, computed

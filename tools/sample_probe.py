@@ -6,6 +6,10 @@ per-node 2 for each word sampler with and without replacement (ssc_decode_sample
 (sample_rows_kernel through ssc_sample_rows, ssc_beam_step_gumbel, ssc_beam_step_sampled) on (G, V) logits, with their logits
 bytes / time against one HBM pass.
     python tools/sample_probe.py [calls]
+    python tools/sample_probe.py diverse-beam [calls] [rounds]
+The diverse-beam leg alone: the time per call of ssc_decode_diverse_beam (k = 6 in 3 groups, per-node 1) next to ssc_decode_search
+(k = 6, per-node 3: the logits path) on the same inputs, in alternating rounds on the same device, and the two selections alone
+(ssc_beam_step_fsm, ssc_beam_step_diverse) on the same (G * 6, V) logits - their share of a step.
 Prints one JSON line."""
 import json
 import os
@@ -38,7 +42,62 @@ def timed(fn, n):
     return e0.elapsed_time(e1) / n
 
 
+def diverse_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, rounds):
+    """Alternating rounds of `calls` one-call searches each: beam search k 6 / per-node 3 and diverse beam search k 6 / 3 groups /
+    per-node 1, early stop off (all steps run), the same noise; then the selection kernels alone."""
+    dev = feats.device
+    k, B = 6, images * n_z
+    G = B * k
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    eps0 = torch.randn(B, c["Z"], device=dev, generator=gen)
+    eps = torch.randn(steps - 1, G, c["Z"], device=dev, generator=gen)
+    sent_b = senti.view(images, 1).expand(images, n_z).reshape(B).contiguous()
+    ctx = dec.prepare(feats)
+    div = sampling.DiverseBeam(3, 0.5)
+    run_beam = lambda: dec.search(ctx, sent_b, n_z, k, 3, steps, 1, eps0, eps, skip_dead=True, early_stop=False)
+    run_div = lambda: dec.diverse_beam(ctx, sent_b, n_z, k, 1, steps, 1, eps0, eps, div, skip_dead=True, early_stop=False)
+    out = {"images": images, "n_z": n_z, "beam": k, "max_steps": steps, "V": c["V"], "calls_per_round": calls,
+           "beam_search_ms": [], "diverse_beam_ms": []}
+    for _ in range(rounds):
+        out["beam_search_ms"].append(timed(run_beam, calls))
+        out["diverse_beam_ms"].append(timed(run_div, calls))
+    for key in ("beam_search_ms", "diverse_beam_ms"):
+        v = out[key]
+        out[key.replace("_ms", "")] = {"ms_per_call": sum(v) / len(v), "min": min(v), "max": max(v)}
+    # the selections alone on the same logits: step 1 of a search whose beams are all live
+    lib = L.load()
+    V = c["V"]
+    big = torch.randn(G, V, device=dev) * 3
+    bd = L.BeamDesc()
+    bd.scores, bd.ld, bd.raw_logits, bd.dims = L.ptr(big), V, 1, L.FsmDims(B, 1, V, 0, 1)
+    bd.B, bd.beam, bd.end_index, bd.step_index = B, k, 1, 1
+    m = 1 + k - k // 3
+    bufs = [torch.zeros(G, dtype=torch.int64, device=dev), torch.full((G,), -5.0, device=dev), torch.empty(G, dtype=torch.int64, device=dev),
+            torch.empty(G, device=dev), torch.empty(G, dtype=torch.int64, device=dev), torch.empty(G * max(m, 3), device=dev),
+            torch.empty(G * max(m, 3), dtype=torch.int64, device=dev)]
+    bd.last_pred, bd.last_lp, bd.pred, bd.lp_out, bd.backptr, bd.scratch_val, bd.scratch_idx = [L.ptr(b) for b in bufs]
+    dd = div.desc()
+
+    def beam_step():
+        bd.per_node = 3
+        lib.ssc_beam_step_fsm(bd, L.stream_ptr())
+
+    def div_step():
+        bd.per_node = 1
+        lib.ssc_beam_step_diverse(bd, dd, L.stream_ptr())
+    out["selection"] = {"G": G, "list": m}
+    for _ in range(rounds):
+        for name, fn in (("beam_step_us", beam_step), ("diverse_step_us", div_step)):
+            out["selection"].setdefault(name, []).append(timed(fn, 20) * 1e3)
+    out["selection"]["logits_bytes"] = G * V * 4
+    return out
+
+
 def main():
+    leg = len(sys.argv) > 1 and sys.argv[1] == "diverse-beam"
+    if leg:
+        del sys.argv[1]
     calls = int(sys.argv[1]) if len(sys.argv) > 1 else 5
     c = dict(bench.C2)
     dev = torch.device("cuda", 0)
@@ -52,6 +111,9 @@ def main():
     images, n_z, steps = 100, 20, c["L"]
     feats = torch.randn(images, c["R"], c["F"], generator=g).to(dev)
     senti = torch.ones(images, device=dev)
+    if leg:
+        print(json.dumps(diverse_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, int(sys.argv[2]) if len(sys.argv) > 2 else 3)))
+        return
     out = {"images": images, "n_z": n_z, "max_steps": steps, "V": c["V"]}
     t0 = time.perf_counter()
     for name, beam, sampler in (("beam5", 5, None), ("beam1", 1, None), ("top_p_0.9", 1, sampling.TopPSampler(p=0.9)),
