@@ -110,6 +110,13 @@ int ssc_split_f16(const float* x, int rows, int K, int ldx, const float* scale, 
 
 int ssc_gemm(const ssc_gemm_desc* d, void* stream);
 
+/* n <= 32 INDEPENDENT products C_i = A_i^T B_i with direct outputs (a_kc = b_kc = 0, one segment, splits ignored): the weight
+ * gradients of a train step.  Members with all three k-row lists (k_count, ka_rows, kb_rows - every member its own), 16-byte
+ * aligned operands and no bias run as ONE work list on a persistent grid (one workgroup per compute unit walks the tiles of
+ * every member); per output element the operations are those of the single product.  The other members go out as ssc_gemm
+ * would issue them (list-less eligible ones in grouped launches).  Errors as ssc_gemm. */
+int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, void* stream);
+
 /* Numerics of NT products (a_kc = b_kc = 1, 16-B aligned operands): mode 1 (default) splits every fp32 operand exactly
  * into three bf16 pieces and sums the six partial products of order <= 2 on v_mfma_f32_32x32x16_bf16 with fp32
  * accumulation (error ~ one fp32 rounding per product); mode 0 uses the exact-fp32 MFMA v_mfma_f32_32x32x2_f32.

@@ -35,6 +35,8 @@ int ssc_prof_loop_ms(float* fwd_loop_ms, float* bwd_loop_ms);
  *   "f16_npw"     producer waves of the 2xFP16 kernel: 4 (default: two workgroups per CU) | 8     (SSC_F16_NPW)
  *   "store_wt"    write-through (sc1) output stores of the wave-specialised kernels (1)            (SSC_STORE_WT)
  *   "tile_gm"     tile rows per group of the XCD-aware tile order (8; 0 = row-major)               (SSC_TILE_GM)
+ *   "dw_one_flush"  ssc_train_bwd issues the weight gradients of all phases as one work list (1) | 0 one launch per phase,
+ *                 as ssc_train_bwd_phases does                                                     (SSC_DW_ONE_FLUSH)
  *   decode (ssc_decode_step and the beam kernels; every form gives the same captions):
  *   "dec_att_table"  attended-feature term of the decoder gates from the per-image table (1)      (SSC_DEC_ATT_TABLE)
  *   "dec_dedup"      products fed only by the parent's states on the distinct parents (1)         (SSC_DEC_DEDUP)

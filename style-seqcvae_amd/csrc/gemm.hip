@@ -204,7 +204,8 @@ __device__ __forceinline__ void read_frag(float (&f)[4], const float* __restrict
   }
 }
 
-__device__ __forceinline__ void locate(const KArgs& a, int step, int& seg, int& k0) {
+template <class G>
+__device__ __forceinline__ void locate(const G& a, int step, int& seg, int& k0) {
   int rem = step;
   seg = 0;
 #pragma unroll 1
@@ -221,17 +222,20 @@ struct Cursor {
   const float* A;
   const float* B;
   int lda, ldb, K, k0, seg, left;  // left = k-steps remaining in this segment after the current one
-  __device__ __forceinline__ void fetch(const KArgs& g) {
+  template <class G>
+  __device__ __forceinline__ void fetch(const G& g) {
     A = g.seg[seg].A; B = g.seg[seg].B; lda = g.seg[seg].lda; ldb = g.seg[seg].ldb; K = g.seg[seg].K;
   }
-  __device__ __forceinline__ void init(const KArgs& g, int step) {
+  template <class G>
+  __device__ __forceinline__ void init(const G& g, int step) {
     locate(g, step, seg, k0);
     fetch(g);
     left = g.seg[seg].nsteps - 1 - k0 / BK;
   }
   // move to the next k-step unless `stay` (past the end of this workgroup's range: keep re-reading the last tile)
   // returns 0: stayed, 1: next k-step of the same segment, 2: first k-step of the next segment
-  __device__ __forceinline__ int advance(const KArgs& g, bool stay) {
+  template <class G>
+  __device__ __forceinline__ int advance(const G& g, bool stay) {
     if (stay) return 0;
     if (left > 0) {
       --left;
@@ -1085,7 +1089,8 @@ constexpr int X3W_STAMP_BYTES = 0;
 // this): every hand-issued operand load of the wave-specialised kernels reports the byte range it touches, relative to the
 // operand base of its K segment; the launch sites synchronise and compare the ranges with the spans the descriptors imply.
 #ifdef SSC_X3W_AUDIT
-__device__ long long g_audit[6][SSC_MAX_SEG][2][2];   // [group member][segment][A | B][lowest offset, highest offset + 16]
+constexpr int SSC_AUDIT_MEMBERS = 20;   // the longest member list of a launch (SSC_DW_MAX)
+__device__ long long g_audit[SSC_AUDIT_MEMBERS][SSC_MAX_SEG][2][2];   // [group member][segment][A | B][lowest offset, highest offset + 16]
 #define SSC_AUDIT_TOUCH(member, seg, op, off)                                       \
   do {                                                                              \
     atomicMin(&g_audit[(member)][(seg)][(op)][0], (long long)(off));                \
@@ -1106,9 +1111,9 @@ template <int TM, int TN> constexpr int x3w_lds_bytes_f16() { return 2 * 2 * (X3
 // F16: the operands are split into two fp16 planes and multiplied with THREE partial products (lo*hi, hi*lo, hi*hi) on
 // v_mfma_f32_32x32x16_f16 instead of three bf16 planes and six products - half the matrix-pipe work of a product that is bound by
 // it (the decode's 10000-row products: DESIGN.md).  LDS layout unchanged (plane 2 of each operand stays unused).
-template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW, bool F16 = false>
-__device__ __forceinline__ void x3w_body(const KArgs& a, const int blk_x, const int blk_y, const int blk_z, const int grid_x,
-                                         const int grid_y, const int grid_z) {
+template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW, bool F16 = false, class Args = KArgs>
+__device__ __forceinline__ void x3w_body(const Args& a, const int blk_x, const int blk_y, const int blk_z, const int grid_x,
+                                         const int grid_y, const int grid_z, const int thr) {   // thr: threadIdx.x
   static_assert((TM == 128 && TN == 128) || (TM == 64 && TN == 256), "unsupported tile");
   static_assert(PF == 1 || PF == 2, "prefetch depth");
   constexpr int UNR = 2;                         // lcm(LDS stages, register sets)
@@ -1131,9 +1136,9 @@ __device__ __forceinline__ void x3w_body(const KArgs& a, const int blk_x, const 
   // products 5-18 % SLOWER (10000 x 10000 x 1200, 2xFP16 form: 846 -> 1003 us): consecutive rows per wave stay.)
   auto kc_row = [&](int t, int u, int) __attribute__((always_inline)) -> int { return (t + NPT * u) >> 3; };
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-  const int wave = threadIdx.x >> 6;
+  const int wave = thr >> 6;
   const bool producer = wave >= 4;
-  const int tid = producer ? (int)threadIdx.x - 256 : (int)threadIdx.x;  // index within the role's threads
+  const int tid = producer ? thr - 256 : thr;  // index within the role's threads
   const int lane = tid & 63;
   int bx, by;
   const int Meff = (RL && a.mcount) ? min(a.M, *a.mcount) : a.M;  // uniform per launch
@@ -1567,7 +1572,7 @@ __device__ __forceinline__ void x3w_body(const KArgs& a, const int blk_x, const 
       // Vocabulary head of a decode step without the logits: per (row, this 128-column tile) the log-sum-exp partials and the two
       // best columns.  Four threads per tile row, 32 columns each, combined by shuffles; order: value descending, column ascending.
       const float* ct = reinterpret_cast<const float*>(lds);
-      const int t = (int)threadIdx.x;
+      const int t = thr;
       if (t < 512) {
         const int row = t >> 2, part = t & 3;
         const int grow = m0 + row;
@@ -1641,7 +1646,7 @@ __device__ __forceinline__ void x3w_body(const KArgs& a, const int blk_x, const 
     constexpr int CPR = TN / 4;  // float4 chunks per tile row
 #pragma unroll
     for (int i = 0; i < (TM * CPR + NTHR - 1) / NTHR; ++i) {
-      const int c = (int)threadIdx.x + NTHR * i;
+      const int c = thr + NTHR * i;
       if (TM * CPR % NTHR != 0 && c >= TM * CPR) break;
       const int row = c / CPR, col = 4 * (c % CPR);
       const int grow = m0 + row, gcol = n0 + col;
@@ -1671,9 +1676,9 @@ __device__ __forceinline__ void x3w_body(const KArgs& a, const int blk_x, const 
 #ifdef SSC_X3W_STAMP
   if (stamp_on && lane == 0) { stamp_lds[124] = __builtin_readcyclecounter(); stamp_lds[125] = wall_clock64(); }
   __syncthreads();
-  if ((int)blockIdx.x == g_stamp_wg && threadIdx.x < 256 && g_stamp_ptr)
-    g_stamp_ptr[threadIdx.x] = reinterpret_cast<const unsigned long long*>(lds + 2 * STAGE)[threadIdx.x];
-  if (g_stamp_wg == -2 && threadIdx.x == 0 && g_stamp_ptr && blockIdx.x < 1024) {
+  if ((int)blockIdx.x == g_stamp_wg && thr < 256 && g_stamp_ptr)
+    g_stamp_ptr[thr] = reinterpret_cast<const unsigned long long*>(lds + 2 * STAGE)[thr];
+  if (g_stamp_wg == -2 && thr == 0 && g_stamp_ptr && blockIdx.x < 1024) {
     g_stamp_ptr[2 * blockIdx.x] = stamp_entry;
     g_stamp_ptr[2 * blockIdx.x + 1] = wall_clock64();
   }
@@ -1702,7 +1707,77 @@ __global__ __launch_bounds__(256 + 64 * NPW, (F16 && NPW == 4) ? 4 : 1) void gem
   const int local = w - g.first[p];
   const int gx = g.gx[p], gy = g.gy[p], gz = g.gz[p];
   const int x = local % gx, yz = local / gx;
-  x3w_body<A_KC, B_KC, KG, TM, TN, PF, NPW, F16>(g.a[p], x, yz % gy, yz / gy, gx, gy, gz);
+  x3w_body<A_KC, B_KC, KG, TM, TN, PF, NPW, F16>(g.a[p], x, yz % gy, yz / gy, gx, gy, gz, (int)threadIdx.x);
+}
+
+// Launch form: a WORK LIST of up to SSC_DW_MAX independent TN products over gathered k-rows (the weight gradients of a train
+// step: C_i = A_i^T B_i over the live rows) walked by a PERSISTENT grid - one workgroup per CU (150 KB of LDS: the existing
+// occupancy), workgroup w runs tiles w, w + G, w + 2G, ... of the list, no workgroup waits for another.  Against one KGroup
+// launch per backward phase the partly filled last round of workgroups is paid once per step instead of once per launch.
+// A member is a compact record (the KArgs of a single-segment TN product has far fewer live fields than the 2 KB by-value
+// block of six KArgs); x3w_body reads it through KTnArgs, whose `seg` answers every index with the one segment, so the
+// cursor's indexed reads stay in scalar registers.  Per output element the sequence of operations is that of a group of one.
+constexpr int SSC_DW_MAX = 20;
+struct KTnMember {
+  const float* A;
+  const float* B;
+  float* C;
+  const int* kcount;   // every member its own lists (nothing assumes they are the same)
+  const int* karows;
+  const int* kbrows;
+  int lda, ldb, ldc, M, N, K, accumulate;
+  int first;           // index of the member's first tile in the list
+};
+struct KTnList {
+  KTnMember m[SSC_DW_MAX];
+  int n, total;        // members; tiles of all members
+  int tile_gm, store_wt;
+};
+struct KOneSeg {
+  KSeg s;
+  __device__ __forceinline__ const KSeg& operator[](int) const { return s; }
+};
+struct KTnArgs {   // the fields of KArgs x3w_body reads, for one member of a work list
+  KOneSeg seg;
+  int nseg, M, N;
+  float* out;
+  int ldo;
+  size_t slab_stride;
+  const float* bias;
+  int accumulate, steps_total, steps_per_split;
+  const int *mcount, *arows, *crows, *kcount, *karows, *kbrows;
+  int tile_gm, store_wt, member;
+  float* topk;
+  const float *a_scale, *b_scale;
+};
+template <int PF, int NPW>
+__global__ __launch_bounds__(256 + 64 * NPW, 1) void gemm_x3w_kernel_tn_list(const KTnList g) {
+  int p = 0;   // a workgroup's tiles ascend: so does their member
+  for (int t = blockIdx.x; t < g.total; t += gridDim.x) {   // workgroup-uniform; a workgroup without a tile leaves at once
+#pragma unroll 1
+    while (p + 1 < g.n && t >= g.m[p + 1].first) ++p;
+    const KTnMember& m = g.m[p];
+    // a fresh copy of the thread index per tile: the tile body's per-thread addresses are formed inside the iteration as in a
+    // launch of one tile per workgroup, instead of being hoisted and held in registers the k-loop needs
+    int thr = (int)threadIdx.x;
+    asm volatile("" : "+v"(thr));
+    __builtin_assume(thr >= 0 && thr < 256 + 64 * NPW);
+    KTnArgs a;
+    a.seg.s.A = m.A; a.seg.s.B = m.B; a.seg.s.lda = m.lda; a.seg.s.ldb = m.ldb; a.seg.s.K = m.K;
+    a.seg.s.nsteps = (m.K + BK - 1) / BK; a.seg.s.avec = a.seg.s.bvec = 1;
+    a.seg.s.A16 = a.seg.s.B16 = nullptr; a.seg.s.lda16 = a.seg.s.ldb16 = 0;
+    a.nseg = 1; a.M = m.M; a.N = m.N;
+    a.out = m.C; a.ldo = m.ldc; a.slab_stride = 0; a.bias = nullptr; a.accumulate = m.accumulate;
+    a.steps_total = a.steps_per_split = a.seg.s.nsteps;
+    a.mcount = a.arows = a.crows = nullptr;
+    a.kcount = m.kcount; a.karows = m.karows; a.kbrows = m.kbrows;
+    a.tile_gm = g.tile_gm; a.store_wt = g.store_wt; a.member = p;
+    a.topk = nullptr; a.a_scale = a.b_scale = nullptr;
+    const int gx = (m.N + 127) / 128, gy = (m.M + 127) / 128;
+    const int local = t - m.first;
+    x3w_body<false, false, true, 128, 128, PF, NPW>(a, local % gx, local / gx, 0, gx, gy, 1, thr);
+    __syncthreads();   // the epilogue's C tile leaves LDS before the next tile's operand planes arrive
+  }
 }
 
 __global__ void reduce_slabs_kernel(const float* __restrict__ slabs, int nslab, size_t slab_stride, int M, int N,
@@ -1875,11 +1950,11 @@ inline bool x3w_skinny_layout(const ssc_gemm_desc* d) { return g_x3w_skinny && d
 
 typedef void (*group_fn)(const KGroup);
 #ifdef SSC_X3W_AUDIT
-static_assert(SSC_GROUP_MAX == 6, "g_audit");
+static_assert(SSC_GROUP_MAX <= SSC_AUDIT_MEMBERS && SSC_DW_MAX <= SSC_AUDIT_MEMBERS, "g_audit");
 long g_audit_launches = 0, g_audit_records = 0, g_audit_violations = 0;
 struct AuditSummary { ~AuditSummary() { fprintf(stderr, "[x3w audit] %ld launches, %ld (member, segment, operand) ranges checked, %ld VIOLATIONS\n", g_audit_launches, g_audit_records, g_audit_violations); } } g_audit_summary;
 void audit_begin() {
-  long long init[6][SSC_MAX_SEG][2][2];
+  long long init[SSC_AUDIT_MEMBERS][SSC_MAX_SEG][2][2];
   for (auto& m : init) for (auto& sg : m) for (auto& op : sg) { op[0] = 0x7fffffffffffffffLL; op[1] = -0x7fffffffffffffffLL; }
   (void)hipMemcpyToSymbol(HIP_SYMBOL(g_audit), init, sizeof(init));
 }
@@ -1896,13 +1971,13 @@ long audit_rows(const int* list, const int* count, int nominal) {
   free(h);
   return mx;
 }
-void audit_end(const KGroup& g, bool a_kc, bool b_kc, const char* what, hipStream_t st) {
+void audit_end(const KArgs* ka, int n, bool a_kc, bool b_kc, const char* what, hipStream_t st) {
   (void)hipStreamSynchronize(st);
-  long long got[6][SSC_MAX_SEG][2][2];
+  long long got[SSC_AUDIT_MEMBERS][SSC_MAX_SEG][2][2];
   (void)hipMemcpyFromSymbol(got, HIP_SYMBOL(g_audit), sizeof(got));
   ++g_audit_launches;
-  for (int m = 0; m < g.n; ++m) {
-    const KArgs& k = g.a[m];
+  for (int m = 0; m < n; ++m) {
+    const KArgs& k = ka[m];
     for (int sg = 0; sg < k.nseg; ++sg) {
       const long K = k.kcount ? audit_rows(nullptr, k.kcount, k.seg[sg].K) : k.seg[sg].K;
       for (int op = 0; op < 2; ++op) {
@@ -1931,10 +2006,10 @@ void audit_end(const KGroup& g, bool a_kc, bool b_kc, const char* what, hipStrea
   }
 }
 #define SSC_AUDIT_BEGIN() audit_begin()
-#define SSC_AUDIT_END(g, a_kc, b_kc, what, st) audit_end(g, a_kc, b_kc, what, st)
+#define SSC_AUDIT_END(ka, n, a_kc, b_kc, what, st) audit_end(ka, n, a_kc, b_kc, what, st)
 #else
 #define SSC_AUDIT_BEGIN() do {} while (0)
-#define SSC_AUDIT_END(g, a_kc, b_kc, what, st) do {} while (0)
+#define SSC_AUDIT_END(ka, n, a_kc, b_kc, what, st) do {} while (0)
 #endif
 // a single product as a group of one
 inline void group_of_one(KGroup& g, const KArgs& k, dim3 grid) {
@@ -1969,6 +2044,12 @@ inline const X3wForm& x3w_big(bool a_kc, bool b_kc, bool kg) {   // layouts NT, 
 }
 inline const X3wForm& x3w_skinny_form(bool b_kc) { return g_x3w[b_kc ? X3W_SKINNY_NT : X3W_SKINNY_NN]; }
 
+// the persistent work-list form of the TN kernel with k-row lists (same tile, prefetch depth and producer waves as X3W_TN_KG)
+typedef void (*tn_list_fn)(const KTnList);
+const tn_list_fn g_tn_list_fn = gemm_x3w_kernel_tn_list<1, 8>;
+constexpr int TN_LIST_THREADS = 256 + 64 * 8, TN_LIST_LDS = x3w_lds_bytes<128, 128>();
+int g_cus[64] = {};   // compute units per device: the persistent grid
+
 // the wave-specialised kernels need more than the default 64 KB of LDS per workgroup: raise the limit once
 int x3w_prepare() {
   // per DEVICE: the attribute belongs to the function's code object on the device it is set under - a process that drives two GPUs
@@ -1980,6 +2061,8 @@ int x3w_prepare() {
   if (done) return SSC_OK;
   for (const X3wForm& f : g_x3w)
     if (hipFuncSetAttribute((const void*)f.fn, hipFuncAttributeMaxDynamicSharedMemorySize, f.lds) != hipSuccess) return SSC_EHIP;
+  if (hipFuncSetAttribute((const void*)g_tn_list_fn, hipFuncAttributeMaxDynamicSharedMemorySize, TN_LIST_LDS) != hipSuccess) return SSC_EHIP;
+  if (hipDeviceGetAttribute(&g_cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || g_cus[dev] < 1) return SSC_EHIP;
   done = true;
   return SSC_OK;
 }
@@ -2102,7 +2185,7 @@ int launch_x3w(const X3wForm& f, const KGroup& g, bool a_kc, bool b_kc, const ch
   SSC_TRY(x3w_prepare());
   SSC_AUDIT_BEGIN();
   SSC_LAUNCH(f.fn, dim3(g.first[g.n]), dim3(f.threads), f.lds, st, g);
-  SSC_AUDIT_END(g, a_kc, b_kc, what, st);
+  SSC_AUDIT_END(g.a, g.n, a_kc, b_kc, what, st);
   prof_close(rec, st);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
@@ -2302,47 +2385,108 @@ int ssc_gemm_slabs_group(const ssc_gemm_desc* const* d, int n, float* const* reg
   return launch_x3w(x3w_skinny_form(d[0]->b_kc != 0), g, true, d[0]->b_kc != 0, "64x256 group", rec, st);
 }
 
-// n independent LARGE products C_i = A_i^T B_i (the weight gradients of one backward phase) with direct outputs: the
-// eligible ones (3xBF16 mode, 16-B operands, m/n-contiguous single segment, all with or all without k-row gather lists)
-// go out as grouped launches of the wave-specialised 128x128 kernel - several rounds of workgroups per launch, so its one
-// workgroup per CU no longer loses to tile quantisation (380 tiles on 256 CUs) - the others one by one.
-int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, hipStream_t st) {
-  if (!d || n < 1) return SSC_EINVAL;
+// n independent LARGE products C_i = A_i^T B_i (the weight gradients of a train step, or of one backward phase) with direct
+// outputs.  The eligible ones with k-row gather lists (3xBF16 mode, 16-B operands, m/n-contiguous single segment, all three
+// lists, no bias) form ONE work list walked by a persistent grid (gemm_x3w_kernel_tn_list; more than SSC_DW_MAX of them: one
+// launch per SSC_DW_MAX).  Eligible ones without lists keep the grouped launch of the wave-specialised 128x128 kernel (their
+// k-loop has a deeper prefetch that the lists' own loads do not allow), the others go out one by one.
+namespace {
+int launch_tn_list(const ssc_gemm_desc* const* d, const KArgs* ka, int n, hipStream_t st) {
+  SSC_TRY(x3w_prepare());
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return SSC_EHIP;
+  // members with more k-steps first (the last round then holds the short tiles); equal ones in the caller's order
+  int ord[SSC_DW_MAX];
+  for (int i = 0; i < n; ++i) ord[i] = i;
+  for (int i = 1; i < n; ++i)
+    for (int j = i; j > 0 && ka[ord[j]].steps_total > ka[ord[j - 1]].steps_total; --j) { const int t = ord[j]; ord[j] = ord[j - 1]; ord[j - 1] = t; }
+  KTnList g;
+  memset(&g, 0, sizeof(g));
+  const ssc_gemm_desc* ds[SSC_DW_MAX];
+  KArgs audit[SSC_DW_MAX];
+  int first = 0;
+  long MN = 0;
+  for (int i = 0; i < n; ++i) {
+    const ssc_gemm_desc* di = d[ord[i]];
+    KTnMember& m = g.m[i];
+    m.A = di->seg[0].A; m.B = di->seg[0].B; m.C = di->C;
+    m.kcount = di->k_count; m.karows = di->ka_rows; m.kbrows = di->kb_rows;
+    m.lda = di->seg[0].lda; m.ldb = di->seg[0].ldb; m.ldc = di->ldc;
+    m.M = di->M; m.N = di->N; m.K = di->seg[0].K; m.accumulate = di->accumulate;
+    m.first = first;
+    first += ssc_cdiv(di->M, 128) * ssc_cdiv(di->N, 128);
+    MN += (long)di->M * di->N;
+    ds[i] = di;
+    audit[i] = ka[ord[i]];
+    audit[i].out = di->C; audit[i].ldo = di->ldc;
+  }
+  g.n = n; g.total = first;
+  g.tile_gm = g_tile_gm; g.store_wt = g_store_wt;
+  ProfRec* rec = prof_open(ds, n, (int)(MN / ds[0]->N), ds[0]->N, ds[0]->seg[0].K, 1, st);   // one record: 2*K*sum(M_i N_i) flops
+  SSC_AUDIT_BEGIN();
+  SSC_LAUNCH(g_tn_list_fn, dim3(first < g_cus[dev] ? first : g_cus[dev]), dim3(TN_LIST_THREADS), TN_LIST_LDS, st, g);
+  SSC_AUDIT_END(audit, n, false, false, "128x128 TN list", st);
+  (void)audit;
+  prof_close(rec, st);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+}  // namespace
+extern "C" int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  constexpr int NMAX = 32;
+  if (!d || n < 1 || n > NMAX) return SSC_EINVAL;
   const Num num = numerics();
+  // 2 = joins the work list, 1 = may join a group of list-less products, 0 = goes out alone
+  KArgs ka[NMAX];
+  int cls[NMAX];
+  for (int j = 0; j < n; ++j) {
+    const ssc_gemm_desc* dj = d[j];
+    KArgs& k = ka[j];
+    SSC_TRY(build_args(dj, k));
+    const bool kg = k.karows || k.kbrows;
+    // a member may run on the wave-specialised kernel and is a single-segment TN product with a direct output; it has all three
+    // k-row lists (and no bias: work list) or none of them (group)
+    const bool ok = x3w_ok(dj, k, num) && k.nseg == 1 && !dj->a_kc && !dj->b_kc && dj->C && dj->ldc >= dj->N && !k.mcount &&
+                    !k.arows && !k.crows && (kg ? (k.kcount && k.karows && k.kbrows && !dj->bias) : !k.kcount);
+    cls[j] = !ok ? 0 : kg ? 2 : 1;
+  }
+  // the work list: every member that qualifies, wherever it stands in the caller's order (the products are independent)
+  const ssc_gemm_desc* ld[SSC_DW_MAX];
+  KArgs lk[SSC_DW_MAX];
+  int ln = 0;
+  for (int j = 0; j < n; ++j) {
+    if (cls[j] != 2) continue;
+    ld[ln] = d[j]; lk[ln] = ka[j];
+    if (++ln == SSC_DW_MAX) { SSC_TRY(launch_tn_list(ld, lk, ln, st)); ln = 0; }
+  }
+  if (ln) SSC_TRY(launch_tn_list(ld, lk, ln, st));
   int i = 0;
   while (i < n) {
-    KGroup g;
+    if (cls[i] == 2) { ++i; continue; }
     int m = 0;
-    bool kg0 = false;
-    long Ksum = 0, MN = 0;
-    for (int j = i; j < n && m < SSC_GROUP_MAX; ++j) {
-      const ssc_gemm_desc* dj = d[j];
-      KArgs& k = g.a[m];
-      SSC_TRY(build_args(dj, k));
-      k.member = m;
-      const bool kg = k.karows || k.kbrows;
-      // a member may run on the wave-specialised kernel, is a single-segment TN product with a direct output, and has all three
-      // k-row lists exactly when the group's first member has them
-      const bool ok = x3w_ok(dj, k, num) && k.nseg == 1 && !dj->a_kc && !dj->b_kc && dj->C && dj->ldc >= dj->N && !k.mcount &&
-                      !k.arows && !k.crows && (kg ? (k.kcount && k.karows && k.kbrows) : !k.kcount) && (m == 0 || kg == kg0);
-      if (!ok) break;
-      kg0 = kg;
-      k.steps_per_split = k.steps_total;
-      k.out = dj->C; k.ldo = dj->ldc; k.slab_stride = 0; k.bias = dj->bias; k.accumulate = dj->accumulate;
-      g.gx[m] = ssc_cdiv(dj->N, 128); g.gy[m] = ssc_cdiv(dj->M, 128); g.gz[m] = 1;
-      if (m == 0) g.first[0] = 0;
-      g.first[m + 1] = g.first[m] + g.gx[m] * g.gy[m];
-      Ksum = dj->seg[0].K; MN += (long)dj->M * dj->N;
-      ++m;
-    }
+    while (cls[i] == 1 && i + m < n && cls[i + m] == 1 && m < SSC_GROUP_MAX) ++m;
     if (m >= 2) {
+      KGroup g;
       g.n = m;
       g.first[0] = 0;
+      long MN = 0;
+      for (int q = 0; q < m; ++q) {
+        const ssc_gemm_desc* dj = d[i + q];
+        KArgs& k = g.a[q];
+        k = ka[i + q];
+        k.member = q;
+        k.steps_per_split = k.steps_total;
+        k.out = dj->C; k.ldo = dj->ldc; k.slab_stride = 0; k.bias = dj->bias; k.accumulate = dj->accumulate;
+        g.gx[q] = ssc_cdiv(dj->N, 128); g.gy[q] = ssc_cdiv(dj->M, 128); g.gz[q] = 1;
+        g.first[q + 1] = g.first[q] + g.gx[q] * g.gy[q];
+        MN += (long)dj->M * dj->N;
+      }
       for (int q = m; q < SSC_GROUP_MAX; ++q) { g.first[q + 1] = g.first[m]; g.gx[q] = g.gy[q] = g.gz[q] = 1; }
-      ProfRec* rec = prof_open(d + i, m, (int)(MN / d[i]->N), d[i]->N, (int)Ksum, 1, st);   // one record: 2*K*sum(M_i N_i) flops
-      SSC_TRY(launch_x3w(x3w_big(false, false, kg0), g, false, false, "128x128 TN group", rec, st));
+      ProfRec* rec = prof_open(d + i, m, (int)(MN / d[i]->N), d[i]->N, d[i + m - 1]->seg[0].K, 1, st);   // one record: 2*K*sum(M_i N_i) flops
+      SSC_TRY(launch_x3w(x3w_big(false, false, false), g, false, false, "128x128 TN group", rec, st));
       i += m;
-    } else {  // a single eligible product gains nothing from the group form; ineligible ones take the usual path
+    } else {  // a single list-less product gains nothing from the group form; ineligible ones take the usual path
       SSC_TRY(ssc_gemm(d[i], (void*)st));
       ++i;
     }
@@ -2488,6 +2632,7 @@ extern "C" int ssc_set_gemm_mode(int mode) {
 // ---- include/ssc_debug.h -----------------------------------------------------------------------------------------
 extern int ssc_g_dec_att_table, ssc_g_dec_dedup, ssc_g_beam_reg, ssc_g_dec_ungathered, ssc_g_dec_parts, ssc_g_dec_planes;   // decode.hip
 extern int ssc_g_img_mfma;   // pointwise.hip
+extern int ssc_g_dw_one_flush;   // sequence.hip
 namespace {
 struct DebugKey { const char* name; int* var; };
 const DebugKey g_debug_keys[] = {
@@ -2495,6 +2640,7 @@ const DebugKey g_debug_keys[] = {
     {"x3w_skinny", &g_x3w_skinny},   // minibatch products on the wave-specialised 64x256 kernel: 0 off, 1 NT and NN (default), 2 NN only   (SSC_X3W_SKINNY)
     {"store_wt", &g_store_wt},       // wave-specialised kernels: write-through (sc1) output stores (0 | 1)   (SSC_STORE_WT)
     {"tile_gm", &g_tile_gm},         // tile rows per group of the tile order (8; 0 = row-major)   (SSC_TILE_GM)
+    {"dw_one_flush", &ssc_g_dw_one_flush},     // train backward in one call: the weight gradients of all phases as one work list (1 | 0 = one launch per phase)   (SSC_DW_ONE_FLUSH)
     {"dec_dedup", &ssc_g_dec_dedup},           // decode: parent-state products on the distinct parents of a beam group (1 | 0)   (SSC_DEC_DEDUP)
     {"beam_reg", &ssc_g_beam_reg},             // decode: beam selection with the vocabulary row in registers (1 | 0)              (SSC_BEAM_REG)
     {"img_mfma", &ssc_g_img_mfma},             // decode: the image cell's table contraction on the fp32 matrix cores (1 | 0 = VALU form)   (SSC_IMG_MFMA)

@@ -180,7 +180,7 @@ int gemm(const Ctx& c, bool a_kc, bool b_kc, std::initializer_list<Seg> segs, in
 //          gradient of the later steps through it (the LSTM backward is not masked by w).
 // When the operands do not qualify (alignment, fp32-MFMA mode) the product runs over all rows as before.
 //   gemm_rows: C[r] = A[r] . B for the listed rows r only (other rows of C are left as they are)
-//   gemm_dw:   C = A^T B summed over the live rows only
+//   queue_dw / flush_dw: C = A^T B summed over the live rows only
 int gemm_rows(const Ctx& c, bool b_kc, std::initializer_list<Seg> segs, int M, int N, float* C, int ldc, const float* bias = nullptr,
               bool live = false) {
   ssc_gemm_desc d;
@@ -198,10 +198,11 @@ int gemm_rows(const Ctx& c, bool b_kc, std::initializer_list<Seg> segs, int M, i
   }
   return ssc_gemm(&d, c.st);
 }
-// The weight-gradient products of a backward phase are independent of each other: they are queued and issued together
-// (ssc_gemm_dw_group: grouped launches of the wave-specialised kernel, several rounds of workgroups each).
+// The weight-gradient products of a backward phase - or, when one call runs every phase, of the whole step - are independent of
+// each other: they are queued and issued together (ssc_gemm_dw_group: one work list on a persistent grid of the wave-specialised
+// kernel, so that the partly filled last round of workgroups is paid once per flush).
 struct DwBatch {
-  static constexpr int MAX = 16;
+  static constexpr int MAX = 24;
   ssc_gemm_desc d[MAX];
   int n = 0;
 };
@@ -233,12 +234,6 @@ int flush_dw(const Ctx& c, DwBatch& q) {
   q.n = 0;
   return rc;
 }
-int gemm_dw(const Ctx& c, const float* A, int lda, const float* Bm, int ldb, int K, int M, int N, float* C, int ldc) {
-  DwBatch q;
-  SSC_TRY(queue_dw(c, q, A, lda, Bm, ldb, K, M, N, C, ldc));
-  return flush_dw(c, q);
-}
-
 // Workgroup 0: ascending list of the rows t*B+b whose target token is not padding (w = 1).  Workgroup 1: ascending list of
 // the rows that are not in the padding SUFFIX of their caption (w = 1 at step t or at a later step of caption b).
 // One workgroup per list, ordered block scan.
@@ -679,6 +674,9 @@ __global__ void repeat_kernel(const float* __restrict__ src, int n, int reps, fl
 }
 }  // namespace
 
+// ssc_debug_set("dw_one_flush"): 0 = ssc_train_bwd flushes the weight-gradient products once per phase, as ssc_train_bwd_phases does
+int ssc_g_dw_one_flush = ssc_env_int("SSC_DW_ONE_FLUSH", 1);
+
 // phases (bit mask): 1 = vocabulary head + BPTT time loop, or its halves 16 = vocabulary head (output-head gradients are final
 // after it) and 32 = BPTT time loop; 2 = embedding, attention-LSTM and attention-projection gradients, 4 = encoder-LSTM and
 // latent-head gradients, 8 = decoder-LSTM gradients; 2 = 64 (the embedding gradient alone) + 128 (attention-LSTM and attention
@@ -701,6 +699,12 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   int64_t* tok = (int64_t*)(W + l.tok);
   const size_t sH = (size_t)B * l.Hp;
   const float* hd_all = W + l.hd + sH;
+  // One call runs the phases 2b, 4 and 8: their weight-gradient products wait in ONE batch that is flushed once, ahead of the
+  // copies that read their results.  The output head's dW joins it when this call runs the head too: its operands - dlogits
+  // (l.logits), hd_all (l.hd) and, tied, l.dproj - are regions of their own (make_layout) that the BPTT loop never writes.
+  // A call of some phases only flushes per phase: a gradient range is final when its phase returns.
+  const bool one_flush = ssc_g_dw_one_flush && (phases & (128u | 4u | 8u)) == (128u | 4u | 8u);
+  DwBatch dwq;
   c.act_count = (const int*)(W + l.act); c.act_rows = c.act_count + 4;  // built by ssc_train_fwd of this minibatch
   c.live_count = (const int*)(W + l.live); c.live_rows = c.live_count + 4;
 
@@ -729,13 +733,17 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     SSC_TRY(head_tail_rows(dlog, l.Vp, p->emb, p->ld_emb, V4, V, TB, E, dP, l.Ep, st));
     SSC_TRY(ssc_tanh_bwd(dP, l.Ep, W + l.proj, l.Ep, TB, E, st));
     SSC_TRY(gemm_rows(c, false, {{dP, l.Ep, p->proj_w, p->ld_proj_w, E}}, TB, H, W + l.dhdv, l.Hp));
-    if (g->proj_w) SSC_TRY(gemm_dw(c, dP, l.Ep, hd_all, l.Hp, TB, E, H, g->proj_w, g->ld_proj_w));
+    if (g->proj_w) {
+      SSC_TRY(queue_dw(c, dwq, dP, l.Ep, hd_all, l.Hp, TB, E, H, g->proj_w, g->ld_proj_w));
+      if (!one_flush) SSC_TRY(flush_dw(c, dwq));
+    }
     if (g->proj_b) SSC_TRY(ssc_colsum2(dP, l.Ep, TB, E, nullptr, g->proj_b, 1, nullptr, 0, c.slabs, st));
   } else {
     SSC_TRY(gemm_rows(c, false, {{dlog, l.Vp, p->out_w, p->ld_out_w, V4}}, TB, H, W + l.dhdv, l.Hp));
     SSC_TRY(head_tail_rows(dlog, l.Vp, p->out_w, p->ld_out_w, V4, V, TB, H, W + l.dhdv, l.Hp, st));
     if (g->out_w) {
-      SSC_TRY(gemm_dw(c, dlog, l.Vp, hd_all, l.Hp, TB, V4, H, g->out_w, g->ld_out_w));
+      SSC_TRY(queue_dw(c, dwq, dlog, l.Vp, hd_all, l.Hp, TB, V4, H, g->out_w, g->ld_out_w));
+      if (!one_flush) SSC_TRY(flush_dw(c, dwq));
       SSC_TRY(head_tail_dw(dlog, l.Vp, hd_all, l.Hp, V4, V, TB, H, g->out_w, g->ld_out_w, st));
     }
     if (g->out_b) SSC_TRY(ssc_colsum2(dlog, l.Vp, TB, V, nullptr, g->out_b, 1, nullptr, 0, c.slabs, st));
@@ -907,9 +915,8 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     SSC_TRY(ssc_embed_scatter_add(g->emb, g->ld_emb, tok, TB, E, W + l.demb, l.Ep, cfg->pad, st));
   }
   }  // phase 2a
-  if (phases & 128u) {  // phase 2b: attention-LSTM and attention-projection gradients
-  {  // all weight-gradient products of this phase at once (grouped launches)
-    DwBatch q;
+  // all weight-gradient products of a phase are queued at once
+  auto queue_att = [&](DwBatch& q) -> int {
     if (g->att_w_ih) {
       float* gw = g->att_w_ih; int ld = g->ld_att_w_ih;
       SSC_TRY(queue_dw(c, q, dga, H4, W + l.emb, l.Ep, TB, H4, E, gw, ld));
@@ -919,7 +926,58 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
       SSC_TRY(queue_dw(c, q, dga, H4, h1_prev, l.Hp, TB, H4, H, g->att_w_hh, g->ld_att_w_hh));
     }
     if (g->wq) SSC_TRY(queue_dw(c, q, W + l.dq, l.Ap, h1_new, l.Hp, TB, A, H, g->wq, g->ld_wq));
-    SSC_TRY(flush_dw(c, q));
+    return SSC_OK;
+  };
+  auto queue_enc = [&](DwBatch& q) -> int {
+    if (g->enc_w_ih) {
+      float* gw = g->enc_w_ih; int ld = g->ld_enc_w_ih;
+      SSC_TRY(queue_dw(c, q, dge, H4, att, l.Fp, TB, H4, F, gw, ld));
+      SSC_TRY(queue_dw(c, q, dge, H4, h1_new, l.Hp, TB, H4, H, gw + F, ld));
+      SSC_TRY(queue_dw(c, q, dge, H4, hd_prev, l.Hp, TB, H4, H, gw + F + H, ld));
+    }
+    if (g->enc_w_hh) SSC_TRY(queue_dw(c, q, dge, H4, he_prev, l.Hp, TB, H4, H, g->enc_w_hh, g->ld_enc_w_hh));
+    // c-block (SENTIMENT_VAE = 2): dGe^T C over the padded Dp columns of the pooled history into the forward's aligned copy (free
+    // since the BPTT loop ended); its D real columns are copied into place below
+    if (g->enc_w_ih && l.D) SSC_TRY(queue_dw(c, q, dge, H4, W + l.pool, l.Dp, TB, H4, l.Dp, W + l.wc_e, l.Dp));
+    if (g->fc_mean_w && g->fc_lv_w && g->fc_lv_w == g->fc_mean_w + (size_t)Z * g->ld_fc_mean_w && g->ld_fc_lv_w == g->ld_fc_mean_w) {
+      // [dW_mu ; dW_lv] = (dmu | dlv)^T h_e as ONE (2Z x H) product: the two gradients are adjacent in the flat store, and 2Z keeps
+      // 16-byte rows where Z alone does not (the shipped Z_SPACE = 150 sent the two Z-row products to the scalar kernel)
+      SSC_TRY(queue_dw(c, q, W + l.dmulv, 2 * Z, he_new, l.Hp, TB, 2 * Z, H, g->fc_mean_w, g->ld_fc_mean_w));
+    } else {
+      if (g->fc_mean_w) SSC_TRY(queue_dw(c, q, W + l.dmulv, 2 * Z, he_new, l.Hp, TB, Z, H, g->fc_mean_w, g->ld_fc_mean_w));
+      if (g->fc_lv_w) SSC_TRY(queue_dw(c, q, W + l.dmulv + Z, 2 * Z, he_new, l.Hp, TB, Z, H, g->fc_lv_w, g->ld_fc_lv_w));
+    }
+    return SSC_OK;
+  };
+  auto queue_dec = [&](DwBatch& q) -> int {
+    if (g->dec_w_ih) {
+      float* gw = g->dec_w_ih; int ld = g->ld_dec_w_ih;
+      SSC_TRY(queue_dw(c, q, dgd, H4, att, l.Fp, TB, H4, F, gw, ld));
+      SSC_TRY(queue_dw(c, q, dgd, H4, h1_new, l.Hp, TB, H4, H, gw + F, ld));
+      SSC_TRY(queue_dw(c, q, dgd, H4, hd_prev, l.Hp, TB, H4, H, gw + F + H, ld));
+      if (l.Zp != Z) {
+        // Z no multiple of 4: the z-block product runs on the padded Zp columns of z (zero pads) into the forward's aligned
+        // z-block copy - free since the BPTT loop ended - and its Z real columns are copied into place below
+        SSC_TRY(queue_dw(c, q, dgd, H4, W + l.z, l.Zp, TB, H4, l.Zp, W + l.wz, l.Zp));
+      } else {
+        SSC_TRY(queue_dw(c, q, dgd, H4, W + l.z, l.Zp, TB, H4, Z, gw + zcol, ld));
+      }
+      if (l.D) SSC_TRY(queue_dw(c, q, dgd, H4, W + l.pool, l.Dp, TB, H4, l.Dp, W + l.wc_d, l.Dp));   // c-block, as for the encoder
+    } else if (g->dec_w_hh) {
+      SSC_TRY(queue_dw(c, q, dgd, H4, hd_prev, l.Hp, TB, H4, H, g->dec_w_hh, g->ld_dec_w_hh));
+    }
+    return SSC_OK;
+  };
+  if (one_flush) {
+    SSC_TRY(queue_att(dwq));
+    SSC_TRY(queue_enc(dwq));
+    SSC_TRY(queue_dec(dwq));
+    SSC_TRY(flush_dw(c, dwq));
+  }
+  if (phases & 128u) {  // phase 2b: attention-LSTM and attention-projection gradients
+  if (!one_flush) {
+    SSC_TRY(queue_att(dwq));
+    SSC_TRY(flush_dw(c, dwq));
   }
   // attention LSTM
   if (g->att_w_ih) {
@@ -946,27 +1004,9 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   if (g->wa) SSC_TRY(ssc_colsum(W + l.dwa, A, B, A, nullptr, g->wa, 1, 0, st));
   }  // phase 2b
   if (phases & 4u) {
-  {
-    DwBatch q;
-    if (g->enc_w_ih) {
-      float* gw = g->enc_w_ih; int ld = g->ld_enc_w_ih;
-      SSC_TRY(queue_dw(c, q, dge, H4, att, l.Fp, TB, H4, F, gw, ld));
-      SSC_TRY(queue_dw(c, q, dge, H4, h1_new, l.Hp, TB, H4, H, gw + F, ld));
-      SSC_TRY(queue_dw(c, q, dge, H4, hd_prev, l.Hp, TB, H4, H, gw + F + H, ld));
-    }
-    if (g->enc_w_hh) SSC_TRY(queue_dw(c, q, dge, H4, he_prev, l.Hp, TB, H4, H, g->enc_w_hh, g->ld_enc_w_hh));
-    // c-block (SENTIMENT_VAE = 2): dGe^T C over the padded Dp columns of the pooled history into the forward's aligned copy (free
-    // since the BPTT loop ended); its D real columns are copied into place below
-    if (g->enc_w_ih && l.D) SSC_TRY(queue_dw(c, q, dge, H4, W + l.pool, l.Dp, TB, H4, l.Dp, W + l.wc_e, l.Dp));
-    if (g->fc_mean_w && g->fc_lv_w && g->fc_lv_w == g->fc_mean_w + (size_t)Z * g->ld_fc_mean_w && g->ld_fc_lv_w == g->ld_fc_mean_w) {
-      // [dW_mu ; dW_lv] = (dmu | dlv)^T h_e as ONE (2Z x H) product: the two gradients are adjacent in the flat store, and 2Z keeps
-      // 16-byte rows where Z alone does not (the shipped Z_SPACE = 150 sent the two Z-row products to the scalar kernel)
-      SSC_TRY(queue_dw(c, q, W + l.dmulv, 2 * Z, he_new, l.Hp, TB, 2 * Z, H, g->fc_mean_w, g->ld_fc_mean_w));
-    } else {
-      if (g->fc_mean_w) SSC_TRY(queue_dw(c, q, W + l.dmulv, 2 * Z, he_new, l.Hp, TB, Z, H, g->fc_mean_w, g->ld_fc_mean_w));
-      if (g->fc_lv_w) SSC_TRY(queue_dw(c, q, W + l.dmulv + Z, 2 * Z, he_new, l.Hp, TB, Z, H, g->fc_lv_w, g->ld_fc_lv_w));
-    }
-    SSC_TRY(flush_dw(c, q));
+  if (!one_flush) {
+    SSC_TRY(queue_enc(dwq));
+    SSC_TRY(flush_dw(c, dwq));
   }
   // encoder LSTM
   if (g->enc_w_ih) {
@@ -988,25 +1028,9 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   if (g->fc_lv_b) SSC_TRY(ssc_colsum2(dmulv + Z, 2 * Z, TB, Z, nullptr, g->fc_lv_b, 1, nullptr, 0, c.slabs, st));
   }  // phase 4
   if (phases & 8u) {
-  {
-    DwBatch q;
-    if (g->dec_w_ih) {
-      float* gw = g->dec_w_ih; int ld = g->ld_dec_w_ih;
-      SSC_TRY(queue_dw(c, q, dgd, H4, att, l.Fp, TB, H4, F, gw, ld));
-      SSC_TRY(queue_dw(c, q, dgd, H4, h1_new, l.Hp, TB, H4, H, gw + F, ld));
-      SSC_TRY(queue_dw(c, q, dgd, H4, hd_prev, l.Hp, TB, H4, H, gw + F + H, ld));
-      if (l.Zp != Z) {
-        // Z no multiple of 4: the z-block product runs on the padded Zp columns of z (zero pads) into the forward's aligned
-        // z-block copy - free since the BPTT loop ended - and its Z real columns are copied into place below
-        SSC_TRY(queue_dw(c, q, dgd, H4, W + l.z, l.Zp, TB, H4, l.Zp, W + l.wz, l.Zp));
-      } else {
-        SSC_TRY(queue_dw(c, q, dgd, H4, W + l.z, l.Zp, TB, H4, Z, gw + zcol, ld));
-      }
-      if (l.D) SSC_TRY(queue_dw(c, q, dgd, H4, W + l.pool, l.Dp, TB, H4, l.Dp, W + l.wc_d, l.Dp));   // c-block, as for the encoder
-    } else if (g->dec_w_hh) {
-      SSC_TRY(queue_dw(c, q, dgd, H4, hd_prev, l.Hp, TB, H4, H, g->dec_w_hh, g->ld_dec_w_hh));
-    }
-    SSC_TRY(flush_dw(c, q));
+  if (!one_flush) {
+    SSC_TRY(queue_dec(dwq));
+    SSC_TRY(flush_dw(c, dwq));
   }
   // decoder LSTM (skipped while frozen: train.py:156-161)
   if (g->dec_w_ih && l.Zp != Z) {

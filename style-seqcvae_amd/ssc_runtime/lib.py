@@ -168,6 +168,7 @@ SYMBOLS = {
     "ssc_last_hip_error": (_i, []),
     "ssc_arch": (C.c_char_p, []),
     "ssc_gemm": (_i, [C.POINTER(GemmDesc), vp]),
+    "ssc_gemm_dw_group": (_i, [C.POINTER(C.POINTER(GemmDesc)), _i, vp]),
     "ssc_gemm_auto_splits": (_i, [_i, _i, _i]),
     "ssc_pow2_scale": (_i, [vp, _sz, _i, _sz, _i, vp, _i, vp, vp]),
     "ssc_split_f16": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp]),
