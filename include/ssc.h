@@ -898,6 +898,50 @@ size_t ssc_eval_set_workspace_bytes(const ssc_eval_refs* refs, const ssc_eval_se
 /* every caption's sorted n-grams and weights, every ordered pair of an image's captions, every image's eigenvalues (three kernels) */
 int ssc_eval_set(const ssc_eval_refs* refs, const ssc_eval_set_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Consensus re-ranking (Devlin et al. 2015, Mao et al. 2015; the "best-1 after consensus re-ranking" numbers of AG-CVAE /
+ * Seq-CVAE / COS-CVAE): for every query image the k nearest images of a bank of training images by cosine similarity of the
+ * pooled features (ssc_feat_prep's avg), then every candidate caption's mean CIDEr-D against the pooled references of those
+ * images, with the bank's document frequencies.  The similarities are an NT product of unit rows: ssc_gemm (a_kc = b_kc = 1) on a
+ * chunk of the bank at a time, followed by ssc_knn_merge on the same stream.
+ * ---------------------------------------------------------------------------------------------- */
+/* out row r = x row r / |x row r| (rows x F, leading dimensions ld / ldo >= F); a zero row stays zero.  One pass, fixed reduction
+ * order.  out may be x. */
+int ssc_l2_normalize_rows(const float* x, int rows, int F, int ld, float* out, int ldo, void* stream);
+
+/* Merges the (Q x Mc) chunk `sims` (ld >= Mc; column c is bank row bank_offset + c) into the running top-k lists best_sim /
+ * best_idx (Q, k), which the caller initialises to -inf / -1 and which stay sorted: similarity descending, equal similarities by
+ * bank index ascending; unused slots (-inf, -1) last.  exclude (optional, (Q)): a bank row the query skips, or -1.  k <= 128,
+ * Mc <= 2^22.  Exact selection (radix select on order-preserving keys, integer histograms): the lists after the last chunk are the
+ * k largest of the whole bank under that order whatever the chunking, bit for bit.  -0 counts as +0; a NaN as -inf. */
+int ssc_knn_merge(const float* sims, int ld, int Q, int Mc, int bank_offset, int k, const int* exclude, float* best_sim,
+                  int* best_idx, void* stream);
+
+typedef struct {
+  const int64_t* predictions; /* (P, N, steps): as ssc_eval_score_desc */
+  int P, N, steps;            /* 1 <= N <= 128 */
+  int boundary_index;
+  int V;                      /* prediction ids 0..V-1, V <= 65535 */
+  const int* id_map;          /* (V): as ssc_eval_score_desc */
+  const int* neighbours;      /* (P, k): prepared images of refs whose references form query p's pool, in this order; -1 = unused
+                               * slot; every query needs at least one valid entry (an image listed twice counts twice) */
+  int k;                      /* 1 <= k <= 128 */
+  double* scores;             /* (P, N): 10 / |R(p)| sum_{r in R(p)} sim(c, r), CiderScorer's per-reference similarity (CIDEr-D of
+                               * the candidate with the pool as its reference list and refs' document frequencies and log I) */
+  int* pool_refs;             /* (P): |R(p)| */
+  int* pick;                  /* (P): the sample of highest score, the lowest index on a tie */
+  int* order;                 /* (P, N): the samples by score, stable descending */
+} ssc_eval_consensus_desc;
+
+/* 0 for arguments out of range */
+size_t ssc_eval_consensus_workspace_bytes(const ssc_eval_refs* refs, const ssc_eval_consensus_desc* d);
+/* Every candidate's n-grams and weights once, then the references of the listed images in list order (one wave per candidate, fp64,
+ * one accumulation order: equal captions of a query score bit-equal, two calls are bit-identical); then every query's order (two
+ * kernels).  Reads a device flag back (synchronises `stream`): out-of-range ids, rows of more than 64 tokens, neighbour indices
+ * outside -1..I-1 and queries without a valid neighbour give SSC_EINVAL; nothing is indexed with them. */
+int ssc_eval_consensus(const ssc_eval_refs* refs, const ssc_eval_consensus_desc* d, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

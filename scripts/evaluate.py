@@ -2,7 +2,8 @@
 """Diverse-caption evaluation on MI355X - counterpart of the reference's eval/eval.py: oracle and mean BLEU-1..4, ROUGE-L and
 CIDEr-D over the N captions per image of a predictions JSON (what scripts/inference.py writes), Div-1 / Div-2 over all captions
 and over the top 5 by CIDEr, and style precision / recall against a wordforms TSV.  METEOR is not computed.  --set-diversity adds the caption-set numbers
-(each image's N captions against each other): mBLEU-1..4, Self-CIDEr and the share of distinct captions."""
+(each image's N captions against each other): mBLEU-1..4, Self-CIDEr and the share of distinct captions.  --consensus-bank adds best-1 after
+consensus re-ranking: every image's pick by mean CIDEr-D against the captions of its nearest bank images (features from --query-tensors)."""
 import argparse
 import json
 import os
@@ -26,6 +27,30 @@ parser.add_argument("--output-json", default="", help="write the summary here")
 parser.add_argument("--set-diversity", action="store_true",
                     help="also compare each image's captions with each other: mBLEU-1..4 (lower = more diverse), Self-CIDEr, unique")
 parser.add_argument("--top5-output", default="", help="write the 5 captions per image of highest CIDEr-D here (eval.py's filtered list)")
+parser.add_argument("--consensus-bank", default="", help="a bank of training images (scripts/build_consensus_bank.py): adds the consensus lines")
+parser.add_argument("--query-tensors", default="",
+                    help="with --consensus-bank: a tensor file (image_features or features + num_boxes, image_id) with the region "
+                         "features of every prediction image")
+parser.add_argument("--consensus-k", type=int, default=60, help="nearest bank images per prediction image")
+parser.add_argument("--consensus-output", default="", help="write the consensus pick of every image here")
+
+
+def consensus_of(a, preds, device):
+    from ssc_runtime.data import TensorFileData
+    from ssc_runtime.evaluation import ConsensusBank, pool_rows
+    if not a.query_tensors:
+        raise SystemExit("--consensus-bank needs --query-tensors (the prediction images' region features)")
+    data = TensorFileData(a.query_tensors)
+    row = {}
+    for r, iid in enumerate(data.image_id.tolist()):
+        row.setdefault(iid, r)
+    for iid in preds:
+        if iid not in row:
+            raise SystemExit(f"--query-tensors holds no features for prediction image {iid!r}")
+    bank = ConsensusBank.load(a.consensus_bank, device=device)
+    pooled = pool_rows(data, [row[iid] for iid in preds], device)
+    # an image that is itself in the bank is not its own neighbour
+    return bank.rerank_captions(preds, pooled, k=a.consensus_k, exclude_ids=list(preds))
 
 
 def main():
@@ -35,7 +60,10 @@ def main():
     style = style_words_from_tsv(a.style_wordforms) if a.style_wordforms else None
     refs = CaptionReferences(load_references(a.references), style_words=style, device=device)
     preds = load_predictions(a.predictions)
-    result = refs.score_captions(preds, set_diversity=a.set_diversity)
+    if a.consensus_output and not a.consensus_bank:
+        raise SystemExit("--consensus-output needs --consensus-bank")
+    cons = consensus_of(a, preds, device) if a.consensus_bank else None
+    result = refs.score_captions(preds, set_diversity=a.set_diversity, consensus=cons)
     print("input:", a.predictions)
     print("Total ref sentences:", sum(len(refs.tokens[i]) for i in result.image_ids))
     s = result.summary()
@@ -50,6 +78,9 @@ def main():
     if a.top5_output:
         out = [{"image_id": iid, "caption": preds[iid][int(n)]} for iid, row in zip(result.image_ids, result.top5) for n in row]
         json.dump(out, open(a.top5_output, "w"))
+    if a.consensus_output:
+        out = [{"image_id": iid, "caption": caps[int(n)]} for (iid, caps), n in zip(preds.items(), cons.pick)]
+        json.dump(out, open(a.consensus_output, "w"))
 
 
 if __name__ == "__main__":

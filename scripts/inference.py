@@ -52,6 +52,12 @@ parser.add_argument("--references", default="",
 parser.add_argument("--style-wordforms", default="", help="with --references: wordforms TSV of the style words (senti_prec / senti_rec)")
 parser.add_argument("--set-diversity", action="store_true",
                     help="with --references: also compare each image's captions with each other (mBLEU-1..4, Self-CIDEr, unique)")
+parser.add_argument("--consensus-bank", default="",
+                    help="consensus re-ranking: a bank of training images (scripts/build_consensus_bank.py); every image's captions are "
+                         "ranked by their mean CIDEr-D against the captions of its nearest bank images, no test reference involved")
+parser.add_argument("--consensus-k", type=int, default=60, help="with --consensus-bank: nearest bank images per decoded image")
+parser.add_argument("--consensus-output", default="",
+                    help='with --consensus-bank: write the picked caption of every image here ([{"image_id", "caption"}, ...])')
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -121,6 +127,12 @@ def main():
                                             max_words_per_constraint=_C.DATA.CBS.MAX_WORDS_PER_CONSTRAINT)
         # (one machine per IMAGE, shared by its N_Z samples and compiled on the device - ssc_fsm_compile -: a call is sized by its rows)
     chunks = []   # (image ids, predictions on the device) of every chunk, for --references
+    bank, consensus, best = None, [], []
+    if _A.consensus_bank:
+        from ssc_runtime.evaluation import ConsensusBank, ConsensusResult, pool_features
+        bank = ConsensusBank.load(_A.consensus_bank, device=device)
+    elif _A.consensus_output:
+        raise SystemExit("--consensus-output needs --consensus-bank")
     ROW_BUDGET = 40000   # rows (image, sample, state, beam) per decode step of a constrained call
     with torch.no_grad():
         lo = 0
@@ -173,9 +185,20 @@ def main():
                 image_id = int(data.image_id[lo + i])
                 for k in range(ids.shape[1]):
                     predictions.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
+            if bank is not None:
+                # an image that is itself in the bank is not its own neighbour
+                here = [int(x) for x in data.image_id[lo: lo + n_here]]
+                cons = bank.rerank(pred, boundary, vocabulary, pool_features(feats), k=_A.consensus_k, exclude_ids=here)
+                consensus.append(cons)
+                for i, image_id in enumerate(here):
+                    k = int(cons.pick[i])
+                    best.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
+    if _A.consensus_output:
+        json.dump(best, open(_A.consensus_output, "w", encoding="utf-8"))
+        print(f"wrote {len(best)} consensus captions to {_A.consensus_output}")
     if _A.references:
         from ssc_runtime.evaluation import CaptionReferences, format_summary, load_references, style_words_from_tsv
         style = style_words_from_tsv(_A.style_wordforms) if _A.style_wordforms else None
@@ -183,7 +206,7 @@ def main():
         steps = max(p.size(-1) for _, p in chunks)
         pred = torch.cat([torch.nn.functional.pad(p, (0, steps - p.size(-1)), value=boundary) for _, p in chunks])
         result = refs.score(pred, boundary, vocabulary, image_ids=[i for ids, _ in chunks for i in ids],
-                            set_diversity=_A.set_diversity)
+                            set_diversity=_A.set_diversity, consensus=ConsensusResult.concat(consensus) if consensus else None)
         for line in format_summary(result.summary()):
             print(line)
         if result.degenerate_sets:

@@ -18,102 +18,9 @@
 // Every sum over a candidate's n-grams runs in the same lane assignment and butterfly order whatever the candidate's position, so
 // equal captions of an image score bit-equal; no float atomics.  Bad ids / lengths / offsets raise a device flag (SSC_EINVAL) and
 // are clamped, never used as indices.
-#include "ssc_common.h"
+#include "caption_common.h"
 
 namespace {
-
-constexpr int EV_L = 64;                  // tokens per caption (references and candidates)
-constexpr int EV_NG = 4 * EV_L;           // n-gram slots per caption
-constexpr int EV_MAX_N = 128;             // samples per image
-constexpr int EV_DIV_SLOTS = 16384;       // LDS hash set of ev_image: >= 2 x EV_MAX_N x EV_L occurrences
-constexpr unsigned EV_EMPTY = 0xffffffffu;
-constexpr int EV_NSCORE = 6, EV_NCOUNT = 10, EV_NIMG = 9;
-
-struct EvLayout {
-  size_t key, hkey, w, norm, tf, nu, len, base, rstyle, hdf, flag, total;
-  unsigned long long T;
-};
-
-EvLayout ev_layout(int I, int nref, int ntok) {
-  EvLayout l;
-  const size_t S = 4 * (size_t)ntok;
-  unsigned long long T = 64;
-  while (T < 2 * S) T <<= 1;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o = ssc_round_up(o + bytes, 256); return at; };
-  l.key = take(S * 8); l.hkey = take(T * 8); l.w = take(S * 8); l.norm = take((size_t)nref * 4 * 8); l.tf = take(S * 4);
-  l.nu = take((size_t)nref * 4); l.len = take((size_t)nref * 4); l.base = take((size_t)nref * 4); l.rstyle = take((size_t)I * 4);
-  l.hdf = take(T * 4); l.flag = take(4);
-  l.total = o; l.T = T;
-  return l;
-}
-
-struct EvState {
-  unsigned long long* key; unsigned long long* hkey; double* w; double* norm; int* tf; int* nu; int* len; int* base; int* rstyle;
-  int* hdf; int* flag; unsigned long long mask;
-};
-
-EvState ev_state(const ssc_eval_refs* r) {
-  const EvLayout l = ev_layout(r->I, r->nref, r->ntok);
-  char* b = (char*)r->state;
-  return {(unsigned long long*)(b + l.key), (unsigned long long*)(b + l.hkey), (double*)(b + l.w), (double*)(b + l.norm),
-          (int*)(b + l.tf), (int*)(b + l.nu), (int*)(b + l.len), (int*)(b + l.base), (int*)(b + l.rstyle), (int*)(b + l.hdf),
-          (int*)(b + l.flag), l.T - 1};
-}
-
-__device__ __forceinline__ int ev_count(int L) {
-  int n = 0;
-#pragma unroll
-  for (int k = 1; k <= 4; ++k) n += L - k + 1 > 0 ? L - k + 1 : 0;
-  return n;
-}
-// slot j of a caption of L tokens -> order k (1..4) and start s: the orders' n-grams are laid out one after the other
-__device__ __forceinline__ void ev_split(int j, int L, int& k, int& s) {
-  k = 1;
-  int c = L;
-  while (j >= c && k < 4) { j -= c; ++k; c = L - k + 1; }
-  s = j;
-}
-__device__ __forceinline__ int ev_order(unsigned long long key) {
-  return (key >> 48) ? 4 : (key >> 32) ? 3 : (key >> 16) ? 2 : 1;
-}
-__device__ __forceinline__ unsigned long long ev_mix(unsigned long long k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-  return k;
-}
-__device__ __forceinline__ unsigned ev_mix32(unsigned k) {
-  k ^= k >> 16; k *= 0x7feb352dU; k ^= k >> 15; k *= 0x846ca68bU; k ^= k >> 16;
-  return k;
-}
-// index of `k` among the n sorted keys at `a`, or -1
-__device__ __forceinline__ int ev_find(const unsigned long long* a, int n, unsigned long long k) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (a[mid] < k) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && a[lo] == k) ? lo : -1;
-}
-__device__ __forceinline__ int ev_df(const unsigned long long* hkey, const int* hdf, unsigned long long mask, unsigned long long k) {
-  unsigned long long h = ev_mix(k) & mask;
-  for (unsigned long long p = 0; p <= mask; ++p) {
-    const unsigned long long s = hkey[h];
-    if (s == k) return hdf[h];
-    if (s == 0ull) return 0;
-    h = (h + 1) & mask;
-  }
-  return 0;
-}
-__device__ __forceinline__ double ev_wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int ev_isum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // ---- reference preparation ----------------------------------------------------------------------------------------------------
 
@@ -236,66 +143,14 @@ __global__ __launch_bounds__(64) void ev_score(EvScoreArgs a, EvState st) {
   const int row = blockIdx.x, lane = threadIdx.x;
   const int p = row / a.N;
   const int64_t* pr = a.pred + (size_t)row * a.steps;
-  // length: the first boundary_index, else the full row
-  int L = a.steps;
-  for (int c0 = 0; c0 < a.steps; c0 += 64) {
-    const int c = c0 + lane;
-    const unsigned long long m = __ballot(c < a.steps && pr[c] == (int64_t)a.boundary);
-    if (m) { L = c0 + __builtin_ctzll(m); break; }
-  }
-  if (L > EV_L) { if (lane == 0) a.flag[0] = 1; L = EV_L; }
-  if (lane < L) {
-    int64_t v = pr[lane];
-    if (v < 0 || v >= a.V) { a.flag[0] = 1; v = 0; }
-    int c = a.id_map[v];
-    if (c < 0 || c > a.W) { a.flag[0] = 1; c = 0; }
-    ot[lane] = (int)v;
-    ct[lane] = c;
-  }
-  __syncthreads();
-  const int n = ev_count(L);
-  // this lane's n-grams: slots lane + 64 q; tf > 0 only at a distinct n-gram's first occurrence
-  int tfc[4], ordc[4], maxr[4];
-  unsigned long long ck[4];
-  double wc[4];
   const int img = a.ref_image[p];
   const bool scored = img >= 0 && img < a.I;
   if (img < -1 || img >= a.I) { if (lane == 0) a.flag[0] = 1; }
-  const double rl = log((double)a.I);
-  double ns[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const int j = lane + 64 * q;
-    tfc[q] = 0; ordc[q] = 0; ck[q] = 0; wc[q] = 0.0; maxr[q] = 0;
-    if (j >= n) continue;
-    int k, s;
-    ev_split(j, L, k, s);
-    ordc[q] = k;
-    int tf = 0;
-    bool first = true;
-    for (int s2 = 0; s2 + k <= L; ++s2) {
-      bool eq = true;
-      for (int i = 0; i < k; ++i) eq &= ot[s + i] == ot[s2 + i];
-      tf += eq;
-      if (eq && s2 < s) first = false;
-    }
-    if (!first) continue;
-    tfc[q] = tf;
-    unsigned long long key = 0;
-    for (int i = 0; i < k; ++i) key |= (unsigned long long)ct[s + i] << (16 * i);
-    bool any0 = false;
-    for (int i = 0; i < k; ++i) any0 |= ct[s + i] == 0;
-    ck[q] = any0 ? 0ull : key;
-    const int df = (scored && ck[q]) ? ev_df(st.hkey, st.hdf, st.mask, ck[q]) : 0;
-    const double w = (double)tf * (rl - log((double)(df > 1 ? df : 1)));
-    wc[q] = w;
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-      if (o == k - 1) ns[o] += w * w;
-  }
-  double normc[4];
-#pragma unroll
-  for (int o = 0; o < 4; ++o) normc[o] = sqrt(ev_wsum(ns[o]));
+  // this lane's n-grams: slots lane + 64 q; tf > 0 only at a distinct n-gram's first occurrence
+  EvCand c;
+  ev_candidate(pr, a.steps, a.boundary, a.V, a.id_map, a.W, scored, a.I, st, a.flag, ot, ct, c);
+  const int L = c.L;
+  int maxr[4] = {0, 0, 0, 0};
   int* cnt = a.counts + (size_t)row * EV_NCOUNT;
   double* sc = a.scores + (size_t)row * EV_NSCORE;
   int lo = 0, hi = 0;
@@ -306,7 +161,6 @@ __global__ __launch_bounds__(64) void ev_score(EvScoreArgs a, EvState st) {
   double cid[4] = {0.0, 0.0, 0.0, 0.0};
   double P = 0.0, Q = 0.0;
   int bd = 0x7fffffff, bl = 0;
-  const int lenc = L > 1 ? L - 1 : 0;
   for (int r = lo; r < hi; ++r) {
     const size_t b = 4 * (size_t)st.base[r];
     const int nr = min(st.nu[r], EV_NG), lr = min(st.len[r], EV_L);   // (<= 4 len and <= 64 as ev_ref_ngrams wrote them)
@@ -314,34 +168,19 @@ __global__ __launch_bounds__(64) void ev_score(EvScoreArgs a, EvState st) {
     for (int e = lane; e < nr; e += 64) { sk[e] = st.key[b + e]; sw[e] = st.w[b + e]; stf[e] = st.tf[b + e]; }
     const int rt = lane < lr ? a.tokens[st.base[r] + lane] : -1;
     __syncthreads();
-    double val[4] = {0.0, 0.0, 0.0, 0.0};
+    double v[4];
+    int x[4];
+    ev_cider_ref(c, sk, sw, nr, lr, st.norm + 4 * (size_t)r, v, x);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      if (tfc[q] == 0 || ck[q] == 0ull) continue;
-      const int x = ev_find(sk, nr, ck[q]);
-      if (x < 0) continue;
-      const double wr = sw[x];
+    for (int q = 0; q < 4; ++q)
+      if (x[q] >= 0) maxr[q] = max(maxr[q], stf[x[q]]);
 #pragma unroll
-      for (int o = 0; o < 4; ++o)
-        if (o == ordc[q] - 1) val[o] += fmin(wc[q], wr) * wr;
-      maxr[q] = max(maxr[q], stf[x]);
-    }
-    const int lrl = lr > 1 ? lr - 1 : 0;
-    const double delta = (double)(lenc - lrl);
-    const double g = exp(-(delta * delta) / 72.0);
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      double v = ev_wsum(val[o]);
-      const double nr_o = st.norm[4 * (size_t)r + o];
-      if (normc[o] != 0.0 && nr_o != 0.0) v /= normc[o] * nr_o;
-      v *= g;
-      cid[o] += v;
-    }
+    for (int o = 0; o < 4; ++o) cid[o] += v[o];
     // LCS(candidate, reference) by the bit-parallel recurrence V' = (V + (V & M)) | (V & ~M), bit = reference position
     unsigned long long Vb = ~0ull;
     for (int t = 0; t < L; ++t) {
-      const int c = ct[t];
-      const unsigned long long M = __ballot(c != 0 && rt == c);
+      const int w = ct[t];
+      const unsigned long long M = __ballot(w != 0 && rt == w);
       Vb = (Vb + (Vb & M)) | (Vb & ~M);
     }
     const unsigned long long msk = lr >= 64 ? ~0ull : ((1ull << lr) - 1);
@@ -358,7 +197,7 @@ __global__ __launch_bounds__(64) void ev_score(EvScoreArgs a, EvState st) {
   for (int q = 0; q < 4; ++q)
 #pragma unroll
     for (int o = 0; o < 4; ++o)
-      if (o == ordc[q] - 1 && tfc[q] > 0) corr[o] += min(tfc[q], maxr[q]);
+      if (o == c.ordc[q] - 1 && c.tfc[q] > 0) corr[o] += min(c.tfc[q], maxr[q]);
 #pragma unroll
   for (int o = 0; o < 4; ++o) corr[o] = ev_isum(corr[o]);
   if (lane == 0) {
@@ -823,19 +662,6 @@ size_t es_eigen_lds(int N) { return ((size_t)N * (N | 1) + 128 + ES_THREADS) * s
 bool es_desc_ok(const ssc_eval_set_desc* d) {
   return d && d->P >= 1 && d->N >= 2 && d->N <= EV_MAX_N && d->steps >= 1 && d->V >= 1 && d->V <= 65535 &&
          (int64_t)d->P * d->N <= (1 << 24) && d->predictions && d->ref_image && d->set_counts && d->eigenvalues && d->distinct;
-}
-
-bool ev_refs_ok(const ssc_eval_refs* r) {
-  return r && r->I >= 1 && r->I <= (1 << 24) && r->nref >= r->I && r->nref <= (1 << 26) && r->ntok >= r->nref &&
-         r->ntok <= (1 << 26) && r->W >= 1 && r->W <= 65535 && r->ref_offsets && r->tok_offsets && r->tokens && r->state;
-}
-
-int ev_read_flag(const int* flag, hipStream_t st) {
-  int h = 0;
-  if (hipMemcpyAsync(&h, flag, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return SSC_EHIP;
-  const hipError_t e = hipStreamSynchronize(st);
-  if (e != hipSuccess) { ssc_tls_hip_error = (int)e; return SSC_EHIP; }
-  return h ? SSC_EINVAL : SSC_OK;
 }
 
 }  // namespace

@@ -12,6 +12,14 @@ reductions (argmax, corpus BLEU sums, means) run here in float64.
 Caption-SET diversity (the N captions of an image against each other: mBLEU-1..4, Self-CIDEr, the share of distinct captions) is
 one more library call (ssc_eval_set) on the same tensor, asked for with set_diversity=True; set_diversity(predictions, ...)
 gives mBLEU and Unique with no references at all.
+
+Consensus re-ranking (the papers' "best-1 after consensus re-ranking": the pick uses no test reference) needs a bank of training
+images - pooled features and captions:
+
+    bank = ConsensusBank.load("bank.pt")                                 # scripts/build_consensus_bank.py writes it
+    cons = bank.rerank(predictions, boundary_index, vocabulary, pooled_queries, k=60, exclude_ids=image_ids)
+    best = cons.pick                                                     # one sample index per image
+    result = refs.score(predictions, boundary_index, vocabulary, consensus=cons)   # adds the "consensus ..." numbers
 """
 import ctypes
 import json
@@ -185,8 +193,11 @@ class EvalResult:
     (P, N, N) and set_eigenvalues (P, N) (0 for images without references), self_cider_values (I,) per evaluated image,
     degenerate_sets: evaluated images whose kernel matrix is 0 (Self-CIDEr 0)."""
 
-    def __init__(self, image_ids, scores, stats, image_counts, eval_rows, top5, has_style, set_out: Optional[SetDiversity] = None):
+    def __init__(self, image_ids, scores, stats, image_counts, eval_rows, top5, has_style, set_out: Optional[SetDiversity] = None,
+                 consensus: Optional["ConsensusResult"] = None):
         self._set = set_out
+        # consensus_pick (I,): the consensus re-ranking's sample of every evaluated image (None without consensus=)
+        self.consensus_pick = np.asarray(consensus.pick, dtype=np.int64)[eval_rows] if consensus is not None else None
         self.set_stats = set_out.set_stats if set_out else None
         self.set_kernel = set_out.set_kernel if set_out else None
         self.set_eigenvalues = set_out.set_eigenvalues if set_out else None
@@ -240,6 +251,14 @@ class EvalResult:
             s["has_anp"] = float(np.mean(self.style_counts[:, 0] > 0))
         if self._set is not None:
             s.update(self._set.summary())
+        if self.consensus_pick is not None:
+            pick = self.consensus_pick
+            sel = st[rows, pick]
+            for k, b in enumerate(corpus_bleu(sel[:, 0].sum(), sel[:, 1].sum(), sel[:, 2:6].sum(0), sel[:, 6:10].sum(0))):
+                s[f"consensus B{k + 1}"] = b
+            s["consensus rouge"] = float(np.mean(self.rouge[rows, pick]))
+            s["consensus cider"] = float(np.mean(self.cider[rows, pick]))
+            s["consensus agreement"] = float(np.mean(pick == self.oracle["cider"]))
         return s
 
 
@@ -248,6 +267,12 @@ def format_summary(s: Dict[str, float]) -> List[str]:
     out = [f"Div-1: {s['Div-1']}", f"Div-2: {s['Div-2']}"]
     for k in ("B1", "B2", "B3", "B4", "mean B1", "mean B2", "mean B3", "mean B4", "rouge", "mean rouge", "cider", "mean cider"):
         out.append(f"{k}: {np.round(s[k] * 100.0, 2)}")
+    # best-1 after consensus re-ranking (consensus=): the picked caption of every image, scored like the oracle lines
+    for k in ("consensus B1", "consensus B2", "consensus B3", "consensus B4", "consensus rouge", "consensus cider"):
+        if k in s:
+            out.append(f"{k}: {np.round(s[k] * 100.0, 2)}")
+    if "consensus agreement" in s:
+        out.append(f"consensus agreement: {np.round(s['consensus agreement'], 4)}")
     out.append("meteor: not computed (METEOR needs Java and WordNet)")
     out += [f"top5 Div-1: {s['top5 Div-1']}", f"top5 Div-2: {s['top5 Div-2']}"]
     if "senti_prec" in s:
@@ -262,34 +287,64 @@ def format_summary(s: Dict[str, float]) -> List[str]:
     return out
 
 
+def _caption_ids(predictions):
+    """Caption strings ([{"image_id", "caption"}, ...] or {image_id: [captions]}) -> ({image_id: [captions]}, (images, N, steps) int64
+    ids with 0 after each caption, the words by id): captions split on whitespace, every word itself."""
+    groups = load_predictions(predictions) if isinstance(predictions, (str, list)) else \
+        OrderedDict((_norm_id(k), list(v)) for k, v in predictions.items())
+    N = _samples_per_image(groups.values())
+    toks = [[c.split() for c in caps] for caps in groups.values()]
+    longest = max((len(t) for caps in toks for t in caps), default=0)
+    if longest > MAX_TOKENS:
+        raise ValueError(f"a caption has {longest} words: at most {MAX_TOKENS} are supported")
+    words = [""] + sorted(set(w for caps in toks for t in caps for w in t))   # id 0: the end of a caption
+    wid = {w: i for i, w in enumerate(words)}
+    arr = np.zeros((len(toks), N, max(1, longest)), dtype=np.int64)
+    for i, caps in enumerate(toks):
+        for n, t in enumerate(caps):
+            arr[i, n, :len(t)] = [wid[w] for w in t]
+    return groups, arr, words
+
+
 class _Prepared:
     """The device state of one evaluated image set: its references as CSR arrays and what ssc_eval_prepare_refs wrote."""
 
     def __init__(self, refs: "CaptionReferences", ids: Sequence, device):
-        lib = L.load()
         ref_off, tok_off, toks = [0], [0], []
         for iid in ids:
             for r in refs.tokens[iid]:
                 toks += [refs.word_id[w] for w in r]
                 tok_off.append(len(toks))
             ref_off.append(len(tok_off) - 1)
-        self.I, self.nref, self.ntok = len(ids), len(tok_off) - 1, len(toks)
         self.index = {iid: i for i, iid in enumerate(ids)}
-        i32 = dict(dtype=torch.int32, device=device)
-        self.ref_off = torch.tensor(ref_off, **i32)
-        self.tok_off = torch.tensor(tok_off, **i32)
-        self.toks = torch.tensor(toks, **i32)
-        self.style = None
+        style = None
         if refs.style_words is not None:
-            flags = np.zeros(refs.W + 1, dtype=np.uint8)
+            style = np.zeros(refs.W + 1, dtype=np.uint8)
             for w, c in refs.word_id.items():
-                flags[c] = w in refs.style_words
-            self.style = torch.from_numpy(flags).to(device)
+                style[c] = w in refs.style_words
+        self._prepare(ref_off, tok_off, toks, refs.W, style, device)
+
+    @classmethod
+    def from_csr(cls, ref_off, tok_off, toks, W: int, device) -> "_Prepared":
+        """References given as compact ids 1..W in CSR form (image i holds references ref_off[i] .. ref_off[i + 1] - 1, reference r
+        the tokens toks[tok_off[r] : tok_off[r + 1]]): no strings, no tokeniser."""
+        self = cls.__new__(cls)
+        self.index = {i: i for i in range(len(ref_off) - 1)}
+        self._prepare(ref_off, tok_off, toks, W, None, device)
+        return self
+
+    def _prepare(self, ref_off, tok_off, toks, W, style, device):
+        lib = L.load()
+        self.I, self.nref, self.ntok = len(ref_off) - 1, len(tok_off) - 1, len(toks)
+        self.ref_off = torch.as_tensor(np.asarray(ref_off, dtype=np.int32)).to(device)
+        self.tok_off = torch.as_tensor(np.asarray(tok_off, dtype=np.int32)).to(device)
+        self.toks = torch.as_tensor(np.asarray(toks, dtype=np.int32)).to(device)
+        self.style = torch.from_numpy(style).to(device) if style is not None else None
         nbytes = lib.ssc_eval_refs_bytes(self.I, self.nref, self.ntok)
         if nbytes == 0:
             raise ValueError(f"reference set out of range: {self.I} images, {self.nref} captions, {self.ntok} tokens")
         self.state = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.desc = L.EvalRefs(self.I, self.nref, self.ntok, refs.W, L.ptr(self.ref_off), L.ptr(self.tok_off), L.ptr(self.toks),
+        self.desc = L.EvalRefs(self.I, self.nref, self.ntok, W, L.ptr(self.ref_off), L.ptr(self.tok_off), L.ptr(self.toks),
                                L.ptr(self.style), L.ptr(self.state), nbytes)
         with torch.cuda.device(device):
             lib.ssc_eval_prepare_refs(ctypes.byref(self.desc), L.stream_ptr())
@@ -329,7 +384,7 @@ class CaptionReferences:
         return self._prepared[key]
 
     def _score_ids(self, pred: torch.Tensor, boundary_index: int, words: Sequence[str], image_ids: Sequence, unk: Optional[int],
-                   set_diversity: bool = False):
+                   set_diversity: bool = False, consensus: Optional["ConsensusResult"] = None):
         if pred.dim() != 3 or pred.dtype != torch.int64:
             raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(pred.shape)} {pred.dtype}")
         P, N, steps = pred.shape
@@ -343,6 +398,11 @@ class CaptionReferences:
             raise ValueError(f"N = {N} captions per image: at most {MAX_SAMPLES} are supported")
         if len(words) > MAX_WORDS:
             raise ValueError(f"{len(words)} prediction ids: at most {MAX_WORDS} are supported")
+        if consensus is not None:
+            if not isinstance(consensus, ConsensusResult):
+                raise TypeError(f"consensus must be a ConsensusResult, got {type(consensus).__name__}")
+            if tuple(consensus.scores.shape) != (P, N):
+                raise ValueError(f"consensus holds {tuple(consensus.scores.shape)} scores for ({P}, {N}) predictions")
         ids = [i for i in image_ids if i in self.tokens]
         if not ids:
             raise ValueError("no prediction image has reference captions")
@@ -371,15 +431,18 @@ class CaptionReferences:
         imgc = img.cpu().numpy().astype(np.int64)
         set_out = _eval_set(pred, boundary_index, len(words), prep, id_map, ref_image) if set_diversity else None
         return EvalResult(list(image_ids), scores.cpu().numpy(), counts.cpu().numpy().astype(np.int64), imgc, rows,
-                          top5.cpu().numpy().astype(np.int64), self.style_words is not None, set_out)
+                          top5.cpu().numpy().astype(np.int64), self.style_words is not None, set_out, consensus)
 
     def score(self, predictions: torch.Tensor, boundary_index: int, vocabulary, image_ids: Optional[Sequence] = None,
-              set_diversity: bool = False) -> EvalResult:
+              set_diversity: bool = False, consensus: Optional["ConsensusResult"] = None) -> EvalResult:
         """predictions (images, N, steps) int64 on the device (diverse_decode's output); a row is cut at its first boundary_index.
         vocabulary: a Vocabulary (its @@UNKNOWN@@ matches nothing) or the list of words by id.  image_ids: one per prediction
         image (default: this object's images, in order); images without references count toward Div-1 / Div-2 only.
         set_diversity: also compare each image's N captions with each other (one ssc_eval_set call): mBLEU-1..4, Self-CIDEr and
-        Unique in summary(); images without references count toward mBLEU and Unique only."""
+        Unique in summary(); images without references count toward mBLEU and Unique only.
+        consensus: the ConsensusResult of ConsensusBank.rerank on the same predictions: summary() then also holds the picked
+        captions' corpus BLEU-1..4 (consensus B1..B4), mean ROUGE-L and CIDEr-D (consensus rouge / cider) and the share of images
+        whose pick is the CIDEr oracle's (consensus agreement)."""
         if not isinstance(set_diversity, bool):
             raise TypeError(f"set_diversity must be a bool, got {type(set_diversity).__name__}")
         if hasattr(vocabulary, "get_vocab_size"):
@@ -388,25 +451,265 @@ class CaptionReferences:
             words = list(vocabulary)
         unk = words.index(UNKNOWN) if UNKNOWN in words else None
         ids = self.image_ids if image_ids is None else [_norm_id(i) for i in image_ids]
-        return self._score_ids(predictions, boundary_index, words, ids, unk, set_diversity)
+        return self._score_ids(predictions, boundary_index, words, ids, unk, set_diversity, consensus)
 
-    def score_captions(self, predictions, set_diversity: bool = False) -> EvalResult:
+    def score_captions(self, predictions, set_diversity: bool = False, consensus: Optional["ConsensusResult"] = None) -> EvalResult:
         """Caption strings: [{"image_id", "caption"}, ...] (N per image in file order, as eval.py reads them) or
         {image_id: [captions]}.  Captions are split on whitespace; every word is itself, including words no vocabulary holds.
-        set_diversity: as for score()."""
+        set_diversity, consensus: as for score() (consensus: of ConsensusBank.rerank_captions on the same captions)."""
         if not isinstance(set_diversity, bool):
             raise TypeError(f"set_diversity must be a bool, got {type(set_diversity).__name__}")
-        groups = load_predictions(predictions) if isinstance(predictions, (str, list)) else \
-            OrderedDict((_norm_id(k), list(v)) for k, v in predictions.items())
-        N = _samples_per_image(groups.values())
-        toks = [[c.split() for c in caps] for caps in groups.values()]
-        longest = max((len(t) for caps in toks for t in caps), default=0)
-        if longest > MAX_TOKENS:
-            raise ValueError(f"a caption has {longest} words: at most {MAX_TOKENS} are supported")
-        words = [""] + sorted(set(w for caps in toks for t in caps for w in t))   # id 0: the end of a caption
-        wid = {w: i for i, w in enumerate(words)}
-        arr = np.zeros((len(toks), N, max(1, longest)), dtype=np.int64)
-        for i, caps in enumerate(toks):
-            for n, t in enumerate(caps):
-                arr[i, n, :len(t)] = [wid[w] for w in t]
-        return self._score_ids(torch.from_numpy(arr).to(self.device), 0, words, list(groups), None, set_diversity)
+        groups, arr, words = _caption_ids(predictions)
+        return self._score_ids(torch.from_numpy(arr).to(self.device), 0, words, list(groups), None, set_diversity, consensus)
+
+
+# ---- consensus re-ranking -------------------------------------------------------------------------------------------------------
+
+MAX_NEIGHBOURS = 128            # consensus.hip KNN_MAX_K
+SIM_BUFFER_BYTES = 64 << 20     # the (queries x bank chunk) similarity buffer stays below this
+MAX_CHUNK_ROWS = 1 << 22        # consensus.hip KNN_MAX_CHUNK
+
+
+def pool_features(feats: torch.Tensor) -> torch.Tensor:
+    """(B, R, F) region features on the device -> (B, F) masked means over the regions (ssc_feat_prep's avg: all-zero regions
+    are padding), the rows a ConsensusBank holds and is queried with."""
+    if feats.dim() != 3 or not feats.is_cuda:
+        raise ValueError(f"features must be (images, regions, F) on the device, got {tuple(feats.shape)} on {feats.device}")
+    feats = feats.contiguous().float()
+    B, R, F = feats.shape
+    mask = torch.empty(B, R, dtype=torch.float32, device=feats.device)
+    avg = torch.empty(B, F, dtype=torch.float32, device=feats.device)
+    with torch.cuda.device(feats.device):
+        L.load().ssc_feat_prep(L.ptr(feats), B, R, F, L.ptr(mask), L.ptr(avg), L.stream_ptr())
+    return avg
+
+
+def pool_rows(data, rows: Sequence[int], device, batch: int = 256) -> torch.Tensor:
+    """Pooled features (len(rows), F) float32 on the host of rows `rows` of a TensorFileData-like source (dense `feats` (N, R, F),
+    or ragged: every batch zero-padded to its largest region count), pooled on the device batch by batch."""
+    out = []
+    for lo in range(0, len(rows), batch):
+        sel = [int(r) for r in rows[lo: lo + batch]]
+        if getattr(data, "ragged", None) is None:
+            f = data.feats[sel]
+        else:
+            flat, nb, off = data.ragged
+            f = torch.zeros(len(sel), max(1, int(nb[sel].max())), flat.size(1))
+            for i, r in enumerate(sel):
+                f[i, : int(nb[r])] = flat[int(off[r]): int(off[r + 1])]
+        out.append(pool_features(f.to(device)).cpu())
+    return torch.cat(out)
+
+
+def _unit_rows(x: torch.Tensor, device) -> torch.Tensor:
+    """(rows, F) -> (rows, F rounded up to 4) float32 unit rows on the device (zero rows stay zero, the added columns are zero: the
+    product's operands are 16-byte aligned whatever F)."""
+    x = torch.as_tensor(x)
+    if x.dim() != 2 or x.size(0) < 1 or x.size(1) < 1:
+        raise ValueError(f"pooled features must be (rows, F), got {tuple(x.shape)}")
+    x = x.to(device=device, dtype=torch.float32).contiguous()
+    rows, F = x.shape
+    Fp = (F + 3) // 4 * 4
+    out = torch.zeros(rows, Fp, dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        L.load().ssc_l2_normalize_rows(L.ptr(x), rows, F, F, L.ptr(out), Fp, L.stream_ptr())
+    return out
+
+
+class ConsensusResult:
+    """What ConsensusBank.rerank found for P query images of N candidates: scores (P, N) float64 - a candidate's mean CIDEr-D x 10
+    against the pooled references of its image's neighbours -, pick (P,) the best sample (lowest index on a tie), order (P, N) the
+    samples by score (stable descending), neighbours (P, k) bank rows (-1 = unused) with neighbour_sims (P, k) (None when the lists
+    were given), pool_refs (P,) the pooled references per image."""
+
+    def __init__(self, scores, pick, order, neighbours, pool_refs, neighbour_sims=None):
+        self.scores, self.pick, self.order = scores, pick, order
+        self.neighbours, self.pool_refs, self.neighbour_sims = neighbours, pool_refs, neighbour_sims
+
+    @staticmethod
+    def concat(parts: Sequence["ConsensusResult"]) -> "ConsensusResult":
+        """The results of several calls (the same N and k) as one, in call order."""
+        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])   # noqa: E731
+        sims = cat("neighbour_sims") if all(r.neighbour_sims is not None for r in parts) else None
+        return ConsensusResult(cat("scores"), cat("pick"), cat("order"), cat("neighbours"), cat("pool_refs"), sims)
+
+
+class ConsensusBank:
+    """A bank of M training images for consensus re-ranking: pooled (M, F) features (masked means over regions: pool_features),
+    one image id per row and every image's reference captions (a list of M caption lists, or {image_id: [captions]}).  Holds the
+    unit-norm bank rows on the device and the captions as a CaptionReferences prepared over all M images, so CIDEr's document
+    frequencies and log I are the bank's."""
+
+    def __init__(self, pooled, image_ids: Sequence, references, device="cuda",
+                 tokenize: Callable[[str], List[str]] = simple_tokenize):
+        self.device = torch.device(device)
+        self.pooled = torch.as_tensor(pooled).detach().to("cpu", torch.float32)
+        ids = image_ids.tolist() if hasattr(image_ids, "tolist") else list(image_ids)
+        self.image_ids = [_norm_id(i) for i in ids]
+        M = len(self.image_ids)
+        if self.pooled.dim() != 2 or self.pooled.size(0) != M or M < 1:
+            raise ValueError(f"pooled must be (M, F) with one row per image id, got {tuple(self.pooled.shape)} for {M} ids")
+        if len(set(self.image_ids)) != M:
+            raise ValueError("an image id occurs twice in the bank")
+        if isinstance(references, dict):
+            references = {_norm_id(k): v for k, v in references.items()}
+            missing = [i for i in self.image_ids if i not in references]
+            if missing:
+                raise ValueError(f"bank image {missing[0]!r} has no reference captions")
+            caps = [list(references[i]) for i in self.image_ids]
+        else:
+            caps = [list(c) for c in references]
+        if len(caps) != M:
+            raise ValueError(f"{len(caps)} caption lists for {M} bank images")
+        self.captions = caps
+        self.index = {iid: j for j, iid in enumerate(self.image_ids)}
+        self.F = self.pooled.size(1)
+        self.bank = _unit_rows(self.pooled, self.device)
+        self.references = CaptionReferences(OrderedDict(zip(self.image_ids, caps)), tokenize=tokenize, device=self.device)
+        self.prep = self.references.prepared(self.image_ids)
+
+    def __len__(self):
+        return len(self.image_ids)
+
+    # -- file: plain tensors, lists and strings only (torch.load(weights_only=True) reads it) --
+    @staticmethod
+    def write_file(path: str, pooled, image_ids: Sequence, captions: Sequence[Sequence[str]]) -> None:
+        """The bank file: {"pooled": (M, F) float32, "image_id": (M,) int64 (a list of strings when an id is not an integer),
+        "captions": M lists of strings}."""
+        ids = image_ids.tolist() if hasattr(image_ids, "tolist") else list(image_ids)
+        pooled = torch.as_tensor(pooled).detach().to("cpu", torch.float32).contiguous()
+        caps = [[str(c) for c in cs] for cs in captions]
+        if pooled.dim() != 2 or pooled.size(0) != len(ids) or len(caps) != len(ids):
+            raise ValueError(f"bank file: {tuple(pooled.shape)} features, {len(ids)} ids, {len(caps)} caption lists")
+        image_id = torch.tensor(ids, dtype=torch.int64) if all(isinstance(i, int) for i in ids) else [str(i) for i in ids]
+        torch.save({"pooled": pooled, "image_id": image_id, "captions": caps}, path)
+
+    @staticmethod
+    def read_file(path: str):
+        """-> (pooled (M, F) float32, image ids, captions) of a bank file, read with weights_only=True."""
+        d = torch.load(path, map_location="cpu", weights_only=True)
+        for k in ("pooled", "image_id", "captions"):
+            if not isinstance(d, dict) or k not in d:
+                raise ValueError(f"{path}: not a consensus bank (no {k!r})")
+        ids = d["image_id"].tolist() if hasattr(d["image_id"], "tolist") else list(d["image_id"])
+        return d["pooled"].float(), ids, d["captions"]
+
+    def save(self, path: str) -> None:
+        self.write_file(path, self.pooled, self.image_ids, self.captions)
+
+    @classmethod
+    def load(cls, path: str, device="cuda", tokenize: Callable[[str], List[str]] = simple_tokenize) -> "ConsensusBank":
+        pooled, ids, caps = cls.read_file(path)
+        return cls(pooled, ids, caps, device=device, tokenize=tokenize)
+
+    # -- neighbours --
+    def _exclude_rows(self, exclude_ids, Q):
+        if exclude_ids is None:
+            return None
+        ex = exclude_ids.tolist() if hasattr(exclude_ids, "tolist") else list(exclude_ids)
+        if len(ex) != Q:
+            raise ValueError(f"{len(ex)} exclude ids for {Q} queries")
+        return torch.tensor([self.index.get(_norm_id(i), -1) for i in ex], dtype=torch.int32, device=self.device)
+
+    def neighbours(self, pooled_queries, k: int = 60, exclude_ids: Optional[Sequence] = None, chunk_rows: Optional[int] = None):
+        """The k nearest bank rows of every query row by cosine similarity -> (idx (Q, k) int32, sim (Q, k) float32) on the device,
+        similarity descending, ties to the lower bank row; slots past the bank's size hold (-1, -inf).  exclude_ids: one image id
+        per query; a query whose id is in the bank skips that row.  The similarities are ssc_gemm NT products of the unit rows,
+        one bank chunk at a time (chunk_rows: default the most that keeps the buffer below 64 MB), each merged by ssc_knn_merge."""
+        if not 1 <= int(k) <= MAX_NEIGHBOURS:
+            raise ValueError(f"k = {k}: 1..{MAX_NEIGHBOURS} neighbours are supported")
+        k = int(k)
+        q = torch.as_tensor(pooled_queries)
+        if q.dim() != 2 or q.size(1) != self.F:
+            raise ValueError(f"queries must be (Q, {self.F}), got {tuple(q.shape)}")
+        q = _unit_rows(q, self.device)
+        Q, Fp = q.shape
+        M = len(self)
+        excl = self._exclude_rows(exclude_ids, Q)
+        cap = min(MAX_CHUNK_ROWS, max(4, SIM_BUFFER_BYTES // (4 * Q) // 4 * 4))
+        rows = cap if chunk_rows is None else int(chunk_rows)
+        if not 1 <= rows <= cap:
+            raise ValueError(f"chunk_rows = {rows}: 1..{cap} rows fit the similarity buffer of {Q} queries")
+        rows = min(rows, M)
+        ld = (rows + 3) // 4 * 4
+        sims = torch.empty(Q, ld, dtype=torch.float32, device=self.device)
+        best_sim = torch.full((Q, k), float("-inf"), dtype=torch.float32, device=self.device)
+        best_idx = torch.full((Q, k), -1, dtype=torch.int32, device=self.device)
+        lib = L.load()
+        d = L.GemmDesc()
+        d.nseg, d.M, d.a_kc, d.b_kc, d.splits = 1, Q, 1, 1, 1   # one pass over K: an entry's value does not depend on the split count
+        d.seg[0].A, d.seg[0].lda, d.seg[0].ldb, d.seg[0].K = q.data_ptr(), Fp, Fp, Fp
+        d.C, d.ldc = sims.data_ptr(), ld
+        with torch.cuda.device(self.device):
+            st = L.stream_ptr()
+            for off in range(0, M, rows):
+                mc = min(rows, M - off)
+                d.N = mc
+                d.seg[0].B = self.bank.data_ptr() + 4 * off * Fp
+                lib.ssc_gemm(ctypes.byref(d), st)
+                lib.ssc_knn_merge(L.ptr(sims), ld, Q, mc, off, k, L.ptr(excl), L.ptr(best_sim), L.ptr(best_idx), st)
+        return best_idx, best_sim
+
+    # -- scores --
+    def _words(self, vocabulary):
+        if hasattr(vocabulary, "get_vocab_size"):
+            return [vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())]
+        return list(vocabulary)
+
+    def _rerank_ids(self, pred, boundary_index, words, unk, pooled_queries, k, exclude_ids, neighbours) -> ConsensusResult:
+        if pred.dim() != 3 or pred.dtype != torch.int64:
+            raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(pred.shape)} {pred.dtype}")
+        P, N, steps = pred.shape
+        if not 1 <= N <= MAX_SAMPLES:
+            raise ValueError(f"N = {N} captions per image: 1..{MAX_SAMPLES} are supported")
+        if not 1 <= len(words) <= MAX_WORDS:
+            raise ValueError(f"{len(words)} prediction ids: 1..{MAX_WORDS} are supported")
+        dev = self.device
+        sims = None
+        if neighbours is None:
+            if pooled_queries is None:
+                raise ValueError("rerank needs pooled_queries or neighbours")
+            nb, sims = self.neighbours(pooled_queries, k, exclude_ids)
+        else:
+            nb = torch.as_tensor(neighbours).to(device=dev, dtype=torch.int32).contiguous()
+        if nb.dim() != 2 or nb.size(0) != P or not 1 <= nb.size(1) <= MAX_NEIGHBOURS:
+            raise ValueError(f"neighbours must be ({P}, 1..{MAX_NEIGHBOURS}), got {tuple(nb.shape)}")
+        refs = self.references
+        id_map = np.array([refs.word_id.get(w, 0) for w in words], dtype=np.int32)
+        if unk is not None and 0 <= unk < len(words):
+            id_map[unk] = 0   # the vocabulary's @@UNKNOWN@@ matches nothing
+        id_map = torch.from_numpy(id_map).to(dev)
+        pred = pred.to(dev).contiguous()
+        scores = torch.empty(P, N, dtype=torch.float64, device=dev)
+        pool = torch.empty(P, dtype=torch.int32, device=dev)
+        pick = torch.empty(P, dtype=torch.int32, device=dev)
+        order = torch.empty(P, N, dtype=torch.int32, device=dev)
+        d = L.EvalConsensusDesc(L.ptr(pred), P, N, steps, int(boundary_index), len(words), L.ptr(id_map), L.ptr(nb), nb.size(1),
+                                L.ptr(scores), L.ptr(pool), L.ptr(pick), L.ptr(order))
+        lib = L.load()
+        nbytes = lib.ssc_eval_consensus_workspace_bytes(ctypes.byref(self.prep.desc), ctypes.byref(d))
+        if nbytes == 0:
+            raise ValueError(f"consensus: arguments out of range ({P} images x {N} samples x {steps} steps, k = {nb.size(1)})")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            lib.ssc_eval_consensus(ctypes.byref(self.prep.desc), ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
+        i64 = lambda t: t.cpu().numpy().astype(np.int64)   # noqa: E731
+        return ConsensusResult(scores.cpu().numpy(), i64(pick), i64(order), i64(nb), i64(pool),
+                               sims.cpu().numpy() if sims is not None else None)
+
+    def rerank(self, predictions: torch.Tensor, boundary_index: int, vocabulary, pooled_queries=None, k: int = 60,
+               exclude_ids: Optional[Sequence] = None, neighbours=None) -> ConsensusResult:
+        """Consensus re-ranking of (images, N, steps) int64 predictions (a row is cut at its first boundary_index): the k nearest
+        bank images of every image by its pooled features (P, F), then every candidate's mean CIDEr-D against those images'
+        captions.  vocabulary: as CaptionReferences.score.  exclude_ids: one image id per prediction image - an image that is
+        itself in the bank is not its own neighbour.  neighbours (P, k') int, bank rows or -1: use these lists instead of a search."""
+        words = self._words(vocabulary)
+        unk = words.index(UNKNOWN) if UNKNOWN in words else None
+        return self._rerank_ids(predictions, boundary_index, words, unk, pooled_queries, k, exclude_ids, neighbours)
+
+    def rerank_captions(self, predictions, pooled_queries=None, k: int = 60, exclude_ids: Optional[Sequence] = None,
+                        neighbours=None) -> ConsensusResult:
+        """The same for caption strings ([{"image_id", "caption"}, ...] or {image_id: [captions]}, as CaptionReferences.score_captions
+        reads them); pooled_queries: one row per image, in the captions' image order."""
+        _, arr, words = _caption_ids(predictions)
+        return self._rerank_ids(torch.from_numpy(arr).to(self.device), 0, words, None, pooled_queries, k, exclude_ids, neighbours)

@@ -161,6 +161,11 @@ class EvalSetDesc(C.Structure):
                 ("id_map", vp), ("ref_image", vp), ("set_counts", vp), ("kernel", vp), ("eigenvalues", vp), ("distinct", vp)]
 
 
+class EvalConsensusDesc(C.Structure):
+    _fields_ = [("predictions", vp), ("P", C.c_int), ("N", C.c_int), ("steps", C.c_int), ("boundary_index", C.c_int), ("V", C.c_int),
+                ("id_map", vp), ("neighbours", vp), ("k", C.c_int), ("scores", vp), ("pool_refs", vp), ("pick", vp), ("order", vp)]
+
+
 # name -> (restype, argtypes).  Every symbol include/ssc.h declares is listed; tests check they all resolve.
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -262,6 +267,10 @@ SYMBOLS = {
     "ssc_eval_score": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc), vp, _sz, vp]),
     "ssc_eval_set_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalSetDesc)]),
     "ssc_eval_set": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalSetDesc), vp, _sz, vp]),
+    "ssc_l2_normalize_rows": (_i, [vp, _i, _i, _i, vp, _i, vp]),
+    "ssc_knn_merge": (_i, [vp, _i, _i, _i, _i, _i, vp, vp, vp, vp]),
+    "ssc_eval_consensus_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc)]),
+    "ssc_eval_consensus": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc), vp, _sz, vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)
