@@ -707,6 +707,44 @@ int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_s
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scoring GIVEN captions under the model (teacher forcing): how likely is a caption that came from elsewhere - a ground-truth
+ * caption, another decoder's or another checkpoint's output.
+ * ---------------------------------------------------------------------------------------------- */
+/* The forced counterpart of ssc_sample_rows: per row of raw logits (rows, V) ld `ld`, lp = logits[target] - logsumexp(logits), the
+ * row read once.  An ENDED row - last_target[r] == end_index (last_target (rows), or NULL: no row has ended), or target[r] < 0 - is
+ * not read: lp_out = 0, rank_out = -1, row_lp unchanged.  An id >= V is never used as an index: lp_out = -inf, rank_out = -1, and
+ * row_lp, where given, becomes -inf (a caption that holds such an id has no finite log-prob).  row_lp (rows) or NULL: the running
+ * caption log-prob, += lp.  rank_out (rows) or NULL: the number of entries strictly greater than the target's logit plus the equal
+ * entries at a lower index - 0: the target is the arg-max.  No float atomics: the same bits on every run. */
+int ssc_score_rows(const float* logits, int ld, int rows, int V, const int64_t* target, const int64_t* last_target, int end_index,
+                   float* row_lp, float* lp_out, int* rank_out, void* stream);
+/* One scoring call = ONE entry point: nimg images x n_captions (C) captions x n_samples (N) latent samples, row g = (image, caption,
+ * sample), G = nimg * C * N rows of ssc_decode_step with rows_per_image = C * N, in the form the beam-1 drivers give the steps
+ * (ssc_decode_sample).  Step 0 feeds end_index (@@BOUNDARY@@) from zero states, step t feeds target t - 1; each step leaves raw
+ * logits and ssc_score_rows reads the target's log-prob from them.  max_len steps, known on the host: no early-stop protocol.
+ * From step 1 on ended and absent rows are not stepped (ssc_decode_step_desc.row_lp). */
+typedef struct {
+  int nimg, R, n_captions, n_samples, max_len, end_index;
+  const float* feats;            /* (nimg, R, F) */
+  const void* imgbuf;            /* from ssc_decode_prepare */
+  const float* sentiment;        /* (G) per row, or NULL */
+  const float* obj_atts;         /* cfg->kld_mode 2: (nimg, R, Z) per-region attribute means; else NULL */
+  const int64_t* targets;        /* (nimg, C, max_len): the caption's words, then end_index from the caption's end on (a caption with no
+                                  * end_index inside max_len is scored over max_len tokens).  A slot whose first entry is negative is
+                                  * ABSENT: log-prob 0, no tokens.  A negative id further on ends the caption there; an id >= V gives
+                                  * the caption the log-prob -inf.  Neither is ever used as an index */
+  const float* eps0;             /* (G, Z): noise of the first step */
+  const float* eps;              /* (max_len - 1, G, Z): noise of the later steps */
+  float* log_probs;              /* out (G): each (caption, sample)'s summed log-prob, the END included */
+  float* token_lp;               /* out (G, max_len), optional: the log-prob of every token; 0 after the caption's end */
+  int* token_rank;               /* out (G, max_len), optional: ssc_score_rows' rank of every token; -1 after the caption's end */
+  int* n_tokens;                 /* out (nimg, C): the scored tokens of every caption, the END included */
+} ssc_score_desc;
+size_t ssc_decode_score_workspace_bytes(const ssc_model_cfg* cfg, const ssc_score_desc* d);
+int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Stochastic beam search (GumbelSampler driving BeamSearch._search, var_updown/var_updown/modules/beam_search.py:294-432,
  * :592-768; Kool et al. 2019): `beam` = k distinct captions per batch entry, sampled without replacement with sequence-level
  * probabilities.  lp = the untempered log_softmax of a row's logits, lpT = log_softmax(logits / T) (= lp at T = 1);

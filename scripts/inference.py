@@ -16,7 +16,7 @@ import torch  # noqa: E402
 
 from ssc_runtime.config import Config  # noqa: E402
 from ssc_runtime.data import SyntheticCaptionData, TensorFileData  # noqa: E402
-from ssc_runtime.inference import diverse_decode  # noqa: E402
+from ssc_runtime.inference import diverse_decode, score_captions  # noqa: E402
 from ssc_runtime import sampling  # noqa: E402
 from ssc_runtime.vocab import Vocabulary  # noqa: E402
 from var_updown.models import UpDownCaptioner  # noqa: E402
@@ -58,6 +58,13 @@ parser.add_argument("--consensus-bank", default="",
 parser.add_argument("--consensus-k", type=int, default=60, help="with --consensus-bank: nearest bank images per decoded image")
 parser.add_argument("--consensus-output", default="",
                     help='with --consensus-bank: write the picked caption of every image here ([{"image_id", "caption"}, ...])')
+parser.add_argument("--likelihood-samples", type=int, default=0,
+                    help="likelihood re-ranking: score every image's decoded captions under M FRESH latent samples "
+                         "(ssc_runtime.inference.score_captions: log p(caption | image) ~ log mean_m p(caption | z^m, image)) and pick "
+                         "the likeliest - the model's own best-1, no reference involved; needs --likelihood-output")
+parser.add_argument("--likelihood-output", default="",
+                    help='with --likelihood-samples: per image {"image_id", "caption" (highest marginal), "caption_per_token" (highest '
+                         'marginal / n_tokens), "pick", "pick_per_token", "marginal": [...], "n_tokens": [...]}')
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -133,6 +140,9 @@ def main():
         bank = ConsensusBank.load(_A.consensus_bank, device=device)
     elif _A.consensus_output:
         raise SystemExit("--consensus-output needs --consensus-bank")
+    if bool(_A.likelihood_samples > 0) != bool(_A.likelihood_output) or _A.likelihood_samples < 0:
+        raise SystemExit("--likelihood-samples M (M >= 1) and --likelihood-output FILE go together")
+    likelihood, lik_pick, lik_pick_len = [], [], []
     ROW_BUDGET = 40000   # rows (image, sample, state, beam) per decode step of a constrained call
     with torch.no_grad():
         lo = 0
@@ -193,12 +203,27 @@ def main():
                 for i, image_id in enumerate(here):
                     k = int(cons.pick[i])
                     best.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
+            if _A.likelihood_samples:
+                # each caption under M fresh latent samples, not under the one sample that produced it
+                sc = score_captions(model._dec, feats, senti, pred, _A.likelihood_samples, boundary, "decoded", obj_means=obj)
+                marg = sc.marginal.double().cpu().numpy()
+                ntok = sc.n_tokens.cpu().numpy()
+                for i in range(ids.shape[0]):
+                    k, kl = int(marg[i].argmax()), int((marg[i] / np.maximum(ntok[i], 1)).argmax())
+                    lik_pick.append(k)
+                    lik_pick_len.append(kl)
+                    likelihood.append({"image_id": int(data.image_id[lo + i]), "caption": " ".join(words[i, k, : n_keep[i, k]]),
+                                       "caption_per_token": " ".join(words[i, kl, : n_keep[i, kl]]), "pick": k, "pick_per_token": kl,
+                                       "marginal": [float(x) for x in marg[i]], "n_tokens": [int(x) for x in ntok[i]]})
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
     if _A.consensus_output:
         json.dump(best, open(_A.consensus_output, "w", encoding="utf-8"))
         print(f"wrote {len(best)} consensus captions to {_A.consensus_output}")
+    if _A.likelihood_output:
+        json.dump(likelihood, open(_A.likelihood_output, "w", encoding="utf-8"))
+        print(f"wrote {len(likelihood)} likelihood picks to {_A.likelihood_output}")
     if _A.references:
         from ssc_runtime.evaluation import CaptionReferences, format_summary, load_references, style_words_from_tsv
         style = style_words_from_tsv(_A.style_wordforms) if _A.style_wordforms else None
@@ -209,6 +234,11 @@ def main():
                             set_diversity=_A.set_diversity, consensus=ConsensusResult.concat(consensus) if consensus else None)
         for line in format_summary(result.summary()):
             print(line)
+        if likelihood:   # best-1 by likelihood, next to the consensus lines: the pick by marginal and the pick by marginal per token
+            for name, pick in (("likelihood", lik_pick), ("likelihood/len", lik_pick_len)):
+                ps = result.pick_summary(pick, name)
+                print(f"{name} B4: {np.round(ps[name + ' B4'] * 100.0, 2)}")
+                print(f"{name} CIDEr: {np.round(ps[name + ' cider'] * 100.0, 2)}")
         if result.degenerate_sets:
             print(f"{result.degenerate_sets} image(s) whose captions hold no weighted n-gram: Self-CIDEr 0")
 

@@ -33,7 +33,13 @@ parser.add_argument("--config-override", default=[], nargs="*")
 parser.add_argument("--gpu-ids", required=True, nargs="+", type=int)
 parser.add_argument("--cpu-workers", type=int, default=0)
 parser.add_argument("--in-memory", action="store_true")
-parser.add_argument("--skip-validation", action="store_true")
+parser.add_argument("--skip-validation", action="store_true", help="no validation pass even with --val-tensors")
+parser.add_argument("--val-tensors", default="",
+                    help="held-out .pt file (as --train-tensors, dense image_features): its captions are scored under the model "
+                         "(teacher forcing, UpDownCaptioner.score_captions) and val_* scalars are appended to scalars.jsonl")
+parser.add_argument("--val-every", type=int, default=1000, help="with --val-tensors: validate every K iterations and at the last one")
+parser.add_argument("--val-samples", type=int, default=1, help="with --val-tensors: latent samples per caption")
+parser.add_argument("--val-images", type=int, default=0, help="with --val-tensors: score the first M images (0: all)")
 parser.add_argument("--serialization-dir", default="checkpoints/experiment")
 parser.add_argument("--checkpoint-every", default=10000, type=int)
 parser.add_argument("--start-from-checkpoint", default="")
@@ -52,12 +58,45 @@ parser.add_argument("--fused-optimizer", action="store_true",
                     help="clip + SGD in one HIP pass on the flat buffers instead of torch.optim.SGD")
 
 
+VAL_IMAGES_PER_CALL = 100
+
+
+def validate(model, val, n_images, n_samples, seed, iteration, device):
+    """Held-out likelihood of the captions of `val` under the model as it stands.  The noise comes from a generator of this pass's
+    own seeded by (seed, iteration) and the model's mode is left alone: neither the global random state nor anything the
+    training step reads is touched, so a run with validation trains exactly as the same run without it."""
+    from ssc_runtime.inference import CaptionScores
+    gen = torch.Generator(device=device)
+    gen.manual_seed((int(seed) * 1000003 + int(iteration)) % (2 ** 63))
+    Z = model.z_space
+    parts = []
+    for lo in range(0, n_images, VAL_IMAGES_PER_CALL):
+        hi = min(lo + VAL_IMAGES_PER_CALL, n_images)
+        caps = val.caps[lo:hi]
+        G = (hi - lo) * n_samples
+        eps = [torch.randn(G, Z, device=device, generator=gen) for _ in range(caps.size(1) + 1)]
+        feats = val.feats[lo:hi].to(device)
+        obj = val.obj[lo:hi, : feats.size(1)].to(device) if val.obj is not None else None
+        parts.append(model.score_captions(feats, caps, sentiment=val.senti[lo:hi, 0].to(device), obj_atts=obj, n_samples=n_samples,
+                                          want_ranks=True, eps_steps=eps))
+    s = CaptionScores.concat(parts).summary()
+    return {"val_nll_per_token": s["nll_per_token"], "val_perplexity": s["perplexity"],
+            "val_marginal_nll_per_token": s["marginal_nll_per_token"], "val_top1": s["top1"]}
+
+
 def main():
     _A = parser.parse_args()
     _C = Config(_A.config, _A.config_override)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+    validating = bool(_A.val_tensors) and not _A.skip_validation
+    if validating and world > 1:
+        # a pass on one rank alone stalls the peers' gradient exchange (ssc_runtime/xgmi.py); sharding it is not built
+        raise SystemExit("--val-tensors runs on one GPU only (WORLD_SIZE = 1): a validation pass on rank 0 alone would stall the "
+                         "other ranks' gradient exchange; train on several GPUs with --skip-validation and score checkpoints apart")
+    if validating and (_A.val_samples < 1 or _A.val_images < 0):
+        raise SystemExit("--val-samples must be at least 1 and --val-images at least 0")
     if -1 in _A.gpu_ids:
         raise SystemExit("--gpu-ids -1 (CPU) is not available: this build has no CPU path")
     gpu = _A.gpu_ids[local % len(_A.gpu_ids)]
@@ -87,6 +126,11 @@ def main():
             raise SystemExit("the h5 / nltk dataset readers are not built (h5py, nltk are not installable here): pass "
                              "--train-tensors file.pt (ssc_runtime/data.py: dense or ragged region features) or --synthetic N")
         data = TensorFileData(_A.train_tensors)
+    val = None
+    if validating:
+        val = TensorFileData(_A.val_tensors)
+        if val.feats is None:
+            raise SystemExit("--val-tensors needs dense image_features (N, R, F)")
     if _C.OPTIM.BATCH_SIZE % world:
         raise SystemExit("OPTIM.BATCH_SIZE (global) must be divisible by the number of ranks")
 
@@ -163,6 +207,12 @@ def main():
             log.flush()
             if iteration % 2000 == 0 or iteration == start_iteration:
                 print("{:6f}    {:6f}    {:6f}".format(rec["3loss"], rec["1reconstr_loss"], rec["2kld_loss"]))
+        last = iteration == _C.OPTIM.NUM_ITERATIONS or (_A.stop_after and iteration == _A.stop_after)
+        if val is not None and rank == 0 and (last or (_A.val_every > 0 and iteration % _A.val_every == 0)):
+            rec = {"iteration": iteration}
+            rec.update(validate(model, val, min(_A.val_images or len(val), len(val)), _A.val_samples, _C.RANDOM_SEED, iteration, device))
+            log.write(json.dumps(rec) + "\n")
+            log.flush()
         if rank == 0 and iteration % _A.checkpoint_every == 0:
             if _A.fused_optimizer:
                 osd = eng.optimizer_state_dict(named, lr, _C.OPTIM.MOMENTUM, _C.OPTIM.WEIGHT_DECAY, iteration)

@@ -1,0 +1,247 @@
+// Scoring given captions under the model: the forced counterpart of the word samplers.  ssc_score_rows returns, per row of raw
+// logits, the log-probability (and optionally the rank) of a GIVEN token; ssc_decode_score is the teacher-forced decode of a whole
+// scoring call - nimg images x C captions x N latent samples - in one library call: the step loop of ssc_decode_sample with the
+// given tokens fed in place of chosen ones and ssc_score_rows in place of the draw.
+//
+// One workgroup per row.  The row is read from HBM ONCE: every thread keeps a running (maximum, sum of exp(x - maximum)) pair over
+// its share of the row - 16-byte loads where the row is 16-byte aligned and V % 4 == 0, scalar loads otherwise - and counts the
+// entries that rank ahead of the target, whose logit is read first.  The pairs are combined in a fixed order (wave butterflies,
+// then the waves in index order): no float atomics, the same bits on every run.  The step log-prob is formed as
+// (x_target - max) - log(sum): the first difference is exact, so logits of magnitude 1e4 lose nothing to the subtraction.
+#include <math.h>
+
+#include "ssc_common.h"
+#include "ssc_radix.h"
+
+namespace {
+
+inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+constexpr int SCORE_THREADS = 256;
+constexpr int SCORE_WAVES = SCORE_THREADS / 64;
+
+struct ScoreArgs {
+  const float* logits; size_t ld; int V;
+  const int64_t* target; const int64_t* last_target; int end_index;
+  float* row_lp; float* lp_out; int* rank_out;
+  int lp_stride, rank_stride;   // lp_out / rank_out of row r at r * stride (the driver writes column t of its (G, L) outputs)
+};
+
+// (m, s) <- the pair of the union: s sums exp(x - m)
+__device__ __forceinline__ void score_merge(float& m, float& s, float om, float os) {
+  const float M = fmaxf(m, om);
+  if (M == -INFINITY) { m = M; s = 0.f; return; }
+  s = s * expf(m - M) + os * expf(om - M);
+  m = M;
+}
+
+__global__ __launch_bounds__(SCORE_THREADS) void score_rows_kernel(ScoreArgs a) {
+  __shared__ float sh_m[SCORE_WAVES], sh_s[SCORE_WAVES];
+  __shared__ int sh_c[SCORE_WAVES];
+  const int r = blockIdx.x;
+  const int V = a.V;
+  const int64_t tgt = a.target[r];
+  const size_t o = (size_t)r * a.lp_stride, ro = (size_t)r * a.rank_stride;
+  // workgroup-uniform: an ended row (its logits are not read), or an id that must not index the row
+  const bool ended = tgt < 0 || (a.last_target && a.last_target[r] == a.end_index);
+  if (ended || tgt >= V) {
+    if (threadIdx.x == 0) {
+      const float lp = ended ? 0.f : -INFINITY;
+      a.lp_out[o] = lp;
+      if (a.rank_out) a.rank_out[ro] = -1;
+      if (!ended && a.row_lp) a.row_lp[r] += lp;
+    }
+    return;
+  }
+  const float* g = a.logits + (size_t)r * a.ld;
+  const RowView<false> row{g, nullptr, V, ssc_aligned16_dev(g) && (V & 3) == 0};
+  const int t = (int)tgt;
+  const float xt = g[t];
+  const int nj = (V + 3) >> 2;
+  float m = -INFINITY, s = 0.f;
+  int ahead = 0;
+#pragma unroll 2
+  for (int j = threadIdx.x; j < nj; j += SCORE_THREADS) {
+    float x[4];
+    row.get4(j, x);   // (entries >= V read as -inf)
+    const float m4 = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ahead += (x[c] > xt || (x[c] == xt && 4 * j + c < t)) ? 1 : 0;
+    if (m4 == -INFINITY) continue;
+    if (m4 > m) { s *= expf(m - m4); m = m4; }
+    s += (expf(x[0] - m) + expf(x[1] - m)) + (expf(x[2] - m) + expf(x[3] - m));
+  }
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const float om = __shfl_xor(m, w, 64), os = __shfl_xor(s, w, 64);
+    score_merge(m, s, om, os);
+    ahead += __shfl_xor(ahead, w, 64);
+  }
+  if ((threadIdx.x & 63) == 0) { sh_m[threadIdx.x >> 6] = m; sh_s[threadIdx.x >> 6] = s; sh_c[threadIdx.x >> 6] = ahead; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < SCORE_WAVES; ++w) {
+      score_merge(m, s, sh_m[w], sh_s[w]);
+      ahead += sh_c[w];
+    }
+    const float lp = (xt - m) - logf(s);
+    a.lp_out[o] = lp;
+    if (a.rank_out) a.rank_out[ro] = ahead;
+    if (a.row_lp) a.row_lp[r] += lp;
+  }
+}
+
+int score_launch(const ScoreArgs& a, int rows, hipStream_t st) {
+  SSC_LAUNCH(score_rows_kernel, dim3(rows), dim3(SCORE_THREADS), 0, st, a);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+// targets (nimg, C, L) -> time-major rows g = (image, caption, sample): tgt (L, G) as given up to the caption's end - its first END,
+// negative id or id >= V - and -1 after it (an absent slot: -1 throughout), fed (L, G): the token fed at step t - END at step 0,
+// target t - 1 after, every id that cannot index the embedding replaced by END.  n_tokens (nimg, C): scored tokens.
+__global__ void score_prepare_kernel(const int64_t* __restrict__ targets, int NC, int N, int L, int V, int end_index,
+                                     int64_t* __restrict__ tgt, int64_t* __restrict__ fed, float* __restrict__ lp,
+                                     int* __restrict__ n_tokens) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  const int G = NC * N;
+  if (g >= G) return;
+  const int ic = g / N;
+  const int64_t* src = targets + (size_t)ic * L;
+  const bool absent = src[0] < 0;
+  int count = 0;
+  bool open = !absent;
+  fed[g] = end_index;
+  for (int t = 0; t < L; ++t) {
+    const int64_t x = open ? src[t] : -1;   // (nothing after a caption's end is scored or fed)
+    tgt[(size_t)t * G + g] = x;
+    if (t + 1 < L) fed[(size_t)(t + 1) * G + g] = (x < 0 || x >= V) ? end_index : x;
+    if (open) {
+      if (x >= 0) ++count;
+      if (x < 0 || x >= V || x == end_index) open = false;
+    }
+  }
+  lp[g] = 0.f;
+  if (g % N == 0) n_tokens[ic] = count;
+}
+
+struct ScoreLayout {
+  size_t st[2][4];   // h1, c1, hd, cd: two generations of (G, H)
+  size_t tgt;        // (L, G) int64
+  size_t fed;        // (L, G) int64
+  size_t parent0;    // (G) int64 zeros: every row is its own parent (the beam-1 search's parent list)
+  size_t lp;         // (G) running caption log-probs
+  size_t steplp;     // (G) the last step's log-probs (when the caller takes no token_lp)
+  size_t alpha;      // (G, R)
+  size_t logits;     // (G, V)
+  size_t stepws, stepws_bytes;
+  size_t total;
+};
+
+ScoreLayout score_layout(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
+  ScoreLayout l;
+  const size_t G = (size_t)d->nimg * d->n_captions * d->n_samples, H = cfg->H;
+  size_t o = 0;
+  for (int g = 0; g < 2; ++g)
+    for (int k = 0; k < 4; ++k) { l.st[g][k] = o; o += a256(G * H * 4); }
+  l.tgt = o; o += a256((size_t)d->max_len * G * 8);
+  l.fed = o; o += a256((size_t)d->max_len * G * 8);
+  l.parent0 = o; o += a256(G * 8);
+  l.lp = o; o += a256(G * 4);
+  l.steplp = o; o += a256(G * 4);
+  l.alpha = o; o += a256(G * (size_t)d->R * 4);
+  l.logits = o; o += a256(G * (size_t)cfg->V * 4);
+  l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)G, d->R);
+  l.stepws = o; o += a256(l.stepws_bytes);
+  l.total = o;
+  return l;
+}
+
+bool score_dims_ok(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
+  if (!cfg || !d) return false;
+  if (d->nimg <= 0 || d->R <= 0 || d->n_captions <= 0 || d->n_samples <= 0 || d->max_len <= 0) return false;
+  return (long)d->nimg * d->n_captions * d->n_samples <= (1L << 24);
+}
+
+bool score_desc_ok(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
+  if (!score_dims_ok(cfg, d) || d->end_index < 0 || d->end_index >= cfg->V) return false;
+  if (!d->feats || !d->imgbuf || !d->targets || !d->eps0 || (d->max_len > 1 && !d->eps) || !d->log_probs || !d->n_tokens) return false;
+  if (cfg->kld_mode == 2 ? !d->obj_atts : ((cfg->S || cfg->pm_scale != 0.f) && !d->sentiment)) return false;
+  return true;
+}
+
+}  // namespace
+
+extern "C" int ssc_score_rows(const float* logits, int ld, int rows, int V, const int64_t* target, const int64_t* last_target,
+                              int end_index, float* row_lp, float* lp_out, int* rank_out, void* stream) {
+  if (!logits || !target || !lp_out || rows < 0 || V <= 0 || ld < V || end_index < 0 || end_index >= V) return SSC_EINVAL;
+  if (rows == 0) return SSC_OK;
+  ScoreArgs a{};
+  a.logits = logits; a.ld = (size_t)ld; a.V = V; a.target = target; a.last_target = last_target; a.end_index = end_index;
+  a.row_lp = row_lp; a.lp_out = lp_out; a.rank_out = rank_out; a.lp_stride = a.rank_stride = 1;
+  return score_launch(a, rows, (hipStream_t)stream);
+}
+
+extern "C" size_t ssc_decode_score_workspace_bytes(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
+  if (!score_dims_ok(cfg, d)) return 0;
+  return score_layout(cfg, d).total;
+}
+
+extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d, void* workspace,
+                                size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
+  if (!p || !workspace || !score_desc_ok(cfg, d)) return SSC_EINVAL;
+  const ScoreLayout l = score_layout(cfg, d);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  char* W = (char*)workspace;
+  const int rpi = d->n_captions * d->n_samples, G = d->nimg * rpi, H = cfg->H, V = cfg->V, Z = cfg->Z, L = d->max_len;
+  float* stt[2][4];
+  for (int g = 0; g < 2; ++g)
+    for (int k = 0; k < 4; ++k) stt[g][k] = (float*)(W + l.st[g][k]);
+  int64_t* tgt = (int64_t*)(W + l.tgt);
+  int64_t* fed = (int64_t*)(W + l.fed);
+  int64_t* parent0 = (int64_t*)(W + l.parent0);
+  float* lp = (float*)(W + l.lp);
+  float* logits = (float*)(W + l.logits);
+
+  SSC_LAUNCH(score_prepare_kernel, dim3(ssc_cdiv(G, 256)), dim3(256), 0, st, d->targets, d->nimg * d->n_captions, d->n_samples, L, V,
+             d->end_index, tgt, fed, lp, d->n_tokens);
+  SSC_CHECK_LAUNCH();
+  if (hipMemsetAsync(parent0, 0, (size_t)G * 8, st) != hipSuccess) return SSC_EHIP;
+  for (int k = 0; k < 4; ++k)   // zero start states (updown_cell.py:131-141)
+    if (hipMemsetAsync(stt[1][k], 0, (size_t)G * H * 4, st) != hipSuccess) return SSC_EHIP;
+
+  // the steps take the form the beam-1 drivers give them (ssc_decode_sample): same tables, same parent list
+  const bool table = d->R <= 128 && G >= 512 && rpi >= 16 && ssc_decode_att_table_enabled();
+  ssc_decode_step_desc sd{};
+  sd.R = d->R; sd.feats = d->feats; sd.imgbuf = d->imgbuf; sd.alpha = (float*)(W + l.alpha); sd.log_probs = logits; sd.raw_logits = 1;
+  sd.obj_atts = d->obj_atts;
+  sd.G = G; sd.rows_per_image = rpi; sd.sentiment = d->sentiment;
+  ScoreArgs a{};
+  a.logits = logits; a.ld = (size_t)V; a.V = V; a.end_index = d->end_index; a.row_lp = lp;
+  a.lp_stride = d->token_lp ? L : 1; a.rank_stride = L;
+  int cur = 1;
+  for (int t = 0; t < L; ++t) {
+    sd.tokens = fed + (size_t)t * G;
+    sd.eps = t == 0 ? d->eps0 : d->eps + (size_t)(t - 1) * G * Z;
+    sd.h1 = stt[cur][0]; sd.c1 = stt[cur][1]; sd.hd = stt[cur][2]; sd.cd = stt[cur][3];
+    sd.h1_out = stt[1 - cur][0]; sd.c1_out = stt[1 - cur][1]; sd.hd_out = stt[1 - cur][2]; sd.cd_out = stt[1 - cur][3];
+    if (t == 0) {
+      sd.att_table = table ? 2 : 0;   // (every row's fed token is END here: no row may be skipped by it)
+    } else {
+      sd.att_table = table ? 1 : 0;
+      sd.parent = parent0; sd.group = 1;
+      sd.row_lp = lp; sd.end_index = d->end_index;   // ended and absent rows (fed token END) are not stepped
+    }
+    SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+    a.target = tgt + (size_t)t * G;
+    a.last_target = t == 0 ? nullptr : fed + (size_t)t * G;
+    a.lp_out = d->token_lp ? d->token_lp + t : (float*)(W + l.steplp);
+    a.rank_out = d->token_rank ? d->token_rank + t : nullptr;
+    SSC_TRY(score_launch(a, G, st));
+    cur = 1 - cur;
+  }
+  if (hipMemcpyAsync(d->log_probs, lp, (size_t)G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
+  return SSC_OK;
+}

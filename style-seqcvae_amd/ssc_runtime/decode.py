@@ -282,6 +282,43 @@ class DecodeEngine:
             _HOST_FLAGS.append(flag)
         return pred[:, :nsteps].contiguous(), lps
 
+    def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
+              eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False):
+        """The teacher-forced decode of GIVEN captions in ONE library call (ssc_decode_score): targets (nimg, C, L) int64 - the
+        caption's words, then end_index from its end on; a slot whose first entry is negative is absent - scored under n_samples
+        latent samples each, row g = (image, caption, sample), G = nimg * C * n_samples.  sentiment (G) per row or None; eps0
+        (G, Z), eps (L - 1, G, Z): the noise of every step.
+        -> (log_probs (G,), n_tokens (nimg, C) int32, token_lp (G, L) or None, token_rank (G, L) int32 or None)."""
+        d = self.dims
+        dev = self.device
+        assert targets.dim() == 3 and targets.size(0) == ctx.nimg, (targets.shape, ctx.nimg)
+        _, Cc, Lc = targets.shape
+        G = ctx.nimg * Cc * n_samples
+        targets = targets.to(dev, torch.int64).contiguous()
+        sd = _lib.ScoreDesc()
+        sd.nimg, sd.R, sd.n_captions, sd.n_samples, sd.max_len, sd.end_index = ctx.nimg, ctx.R, Cc, n_samples, Lc, end_index
+        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
+        sent = sentiment.reshape(G).to(dev, torch.float32).contiguous() if sentiment is not None else None
+        eps0 = eps0.to(dev, torch.float32).contiguous()
+        assert tuple(eps0.shape) == (G, d.Z), (eps0.shape, (G, d.Z))
+        if Lc > 1:
+            eps = eps.to(dev, torch.float32).contiguous()
+            assert tuple(eps.shape) == (Lc - 1, G, d.Z), (eps.shape, (Lc - 1, G, d.Z))
+        sd.sentiment, sd.obj_atts, sd.targets = _lib.ptr(sent), _lib.ptr(ctx.obj), _lib.ptr(targets)
+        sd.eps0, sd.eps = _lib.ptr(eps0), _lib.ptr(eps) if Lc > 1 else None
+        lps = torch.empty(G, dtype=torch.float32, device=dev)
+        ntok = torch.empty(ctx.nimg, Cc, dtype=torch.int32, device=dev)
+        tlp = torch.empty(G, Lc, dtype=torch.float32, device=dev) if want_tokens else None
+        trk = torch.empty(G, Lc, dtype=torch.int32, device=dev) if want_ranks else None
+        sd.log_probs, sd.n_tokens, sd.token_lp, sd.token_rank = _lib.ptr(lps), _lib.ptr(ntok), _lib.ptr(tlp), _lib.ptr(trk)
+        nbytes = self.lib.ssc_decode_score_workspace_bytes(C.byref(self._cfg), C.byref(sd))
+        if self._sws is None or self._sws.numel() < nbytes:
+            self._sws = None   # (release before growing)
+            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        p = self._params()
+        self.lib.ssc_decode_score(C.byref(self._cfg), C.byref(p), C.byref(sd), _lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr())
+        return lps, ntok, tlp, trk
+
     def stochastic_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                         max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
                         early_stop: bool = True, skip_dead: bool = True):

@@ -205,6 +205,7 @@ class EvalResult:
         self.self_cider_values = set_out.self_cider_values if set_out else None
         self.degenerate_sets = set_out.degenerate_sets if set_out else None
         self.image_ids = [image_ids[p] for p in eval_rows]
+        self.eval_rows = np.asarray(eval_rows, dtype=np.int64)   # rows of the predictions that were evaluated (have references)
         self.bleu = scores[eval_rows, :, :4]
         self.rouge = scores[eval_rows, :, 4]
         self.cider = scores[eval_rows, :, 5]
@@ -259,6 +260,21 @@ class EvalResult:
             s["consensus rouge"] = float(np.mean(self.rouge[rows, pick]))
             s["consensus cider"] = float(np.mean(self.cider[rows, pick]))
             s["consensus agreement"] = float(np.mean(pick == self.oracle["cider"]))
+        return s
+
+
+    def pick_summary(self, pick, name: str) -> Dict[str, float]:
+        """A best-1 choice made elsewhere (e.g. by likelihood, ssc_runtime.inference.score_captions), scored like the consensus
+        pick: pick (P,) - one sample per PREDICTION image, in the order of the predictions - -> {"<name> B1".."<name> B4",
+        "<name> rouge", "<name> cider", "<name> agreement"} over the evaluated images."""
+        pick = np.asarray(pick, dtype=np.int64)[self.eval_rows]
+        rows = np.arange(pick.shape[0])
+        sel = self.stats.astype(np.float64)[rows, pick]
+        s = {f"{name} B{k + 1}": b for k, b in enumerate(corpus_bleu(sel[:, 0].sum(), sel[:, 1].sum(), sel[:, 2:6].sum(0),
+                                                                      sel[:, 6:10].sum(0)))}
+        s[f"{name} rouge"] = float(np.mean(self.rouge[rows, pick]))
+        s[f"{name} cider"] = float(np.mean(self.cider[rows, pick]))
+        s[f"{name} agreement"] = float(np.mean(pick == self.oracle["cider"]))
         return s
 
 

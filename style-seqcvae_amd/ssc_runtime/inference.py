@@ -6,8 +6,10 @@ the batch entries of ONE constrained beam search (rows ordered image, sample, fs
 computed once per image and shared by its N_Z * beam rows; the result per (image, sample) equals the reference's
 per-call result given the same per-row noise.
 """
+import math
 import os
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import Dict, List, Optional
 
 import torch
 
@@ -166,3 +168,115 @@ def count_tokens(pred: torch.Tensor, boundary_index: int) -> int:
     steps = pred.size(-1)
     first = torch.where(is_end.any(-1), is_end.float().argmax(-1), torch.full(pred.shape[:-1], steps, device=pred.device))
     return int(first.sum().item())
+
+
+@dataclass
+class CaptionScores:
+    """What score_captions returns.  log_probs (nimg, C, N): log p(caption | z^n, image), the END included; n_tokens (nimg, C): the
+    scored tokens, the END included (0: an absent slot, whose log-probs are 0); marginal (nimg, C) = logsumexp_n log_probs - log N,
+    the Monte-Carlo estimate of log p(caption | image) with z^n drawn from the prior; token_lp (nimg, C, N, L) / token_rank
+    (nimg, C, N, L) int32 when asked for (0 / -1 after a caption's end; rank 0: the token was the model's arg-max)."""
+    log_probs: torch.Tensor
+    n_tokens: torch.Tensor
+    marginal: torch.Tensor
+    token_lp: Optional[torch.Tensor] = None
+    token_rank: Optional[torch.Tensor] = None
+
+    @staticmethod
+    def concat(parts: "List[CaptionScores]") -> "CaptionScores":
+        """The scores of several calls over different images as one (token arrays padded to the longest call: 0 / -1)."""
+        def cat(name, fill):
+            ts = [getattr(p, name) for p in parts]
+            if any(t is None for t in ts):
+                return None
+            L = max(t.size(-1) for t in ts)
+            return torch.cat([torch.nn.functional.pad(t, (0, L - t.size(-1)), value=fill) for t in ts])
+        return CaptionScores(torch.cat([p.log_probs for p in parts]), torch.cat([p.n_tokens for p in parts]),
+                             torch.cat([p.marginal for p in parts]), cat("token_lp", 0.0), cat("token_rank", -1))
+
+    def summary(self) -> Dict[str, float]:
+        """nll_per_token = -sum_c mean_n log_probs / sum_c n_tokens, perplexity = exp of it, marginal_nll_per_token =
+        -sum_c marginal / sum_c n_tokens; top1 / top5: the share of scored tokens of rank 0 / below 5 (with token_rank)."""
+        n = float(self.n_tokens.sum().item())
+        if n == 0:
+            raise ValueError("no caption was scored")
+        nll = -float(self.log_probs.double().mean(-1).sum().item()) / n
+        out = {"n_captions": int((self.n_tokens > 0).sum().item()), "n_tokens": int(n), "nll_per_token": nll,
+               "perplexity": math.exp(nll) if nll < 700 else math.inf,
+               "marginal_nll_per_token": -float(self.marginal.double().sum().item()) / n}
+        if self.token_rank is not None:
+            scored = self.token_rank >= 0
+            k = max(int(scored.sum().item()), 1)
+            out["top1"] = int((self.token_rank == 0).sum().item()) / k
+            out["top5"] = int((scored & (self.token_rank < 5)).sum().item()) / k
+        return out
+
+
+def score_captions(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[torch.Tensor], captions: torch.Tensor, n_samples: int,
+                   boundary_index: int, layout: str, eps_steps: Optional[List[torch.Tensor]] = None,
+                   obj_means: Optional[torch.Tensor] = None, pad_index: int = 0, want_tokens: bool = False,
+                   want_ranks: bool = False) -> CaptionScores:
+    """How likely are GIVEN captions under the model: feats (nimg, R, F), sentiment (nimg,) or None, captions (nimg, C, L) int64,
+    each scored under n_samples latent samples drawn from the prior (DecodeEngine.score, one library call).
+    layout - required, nothing is guessed: "padded" = the training layout (the words, then pad_index; no boundary tokens; a slot
+    that starts with pad_index is absent) - the END is appended here; "decoded" = what the decoders return (the words, then
+    boundary_index from the caption's end on; a slot whose first entry is negative is absent) - scored as emitted: a caption that
+    ran out of steps before its END has none.  The call is trimmed to the longest caption.  Ids outside the vocabulary raise
+    ValueError on the host, before anything is launched.
+    eps_steps: optional explicit noise per step [(nimg * C * n_samples, Z)], rows (image, caption, sample); default: a generator of
+    this call's own, seeded by ONE draw of the global CPU generator (as diverse_decode draws its noise).
+    obj_means (nimg, R, Z): per-region attribute means, SENTIMENT_VAE = 2 only."""
+    if layout not in ("padded", "decoded"):
+        raise ValueError(f"layout must be 'padded' (training layout) or 'decoded' (decoder output), got {layout!r}")
+    if captions.dim() != 3 or captions.size(0) != feats.size(0) or captions.size(2) < 1:
+        raise ValueError(f"captions must be (nimg, C, L) with nimg = {feats.size(0)}, got {tuple(captions.shape)}")
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1")
+    d = dec.dims
+    dev = feats.device
+    nimg, Cc, L0 = captions.shape
+    caps = captions.to("cpu", torch.int64)
+    end = boundary_index
+    steps = torch.arange(L0 + 1).view(1, 1, -1)
+    if layout == "padded":
+        is_pad = caps == pad_index
+        length = torch.where(is_pad.any(-1), is_pad.float().argmax(-1), torch.full((nimg, Cc), L0))   # words before the first pad
+        absent = length == 0
+        tg = torch.cat([caps, torch.full((nimg, Cc, 1), end, dtype=torch.int64)], -1)
+        tg = torch.where(steps >= length.unsqueeze(-1), torch.full_like(tg, end), tg)
+        n_scored = length + 1
+    else:
+        absent = caps[..., 0] < 0
+        is_end = caps == end
+        length = torch.where(is_end.any(-1), is_end.float().argmax(-1), torch.full((nimg, Cc), L0))
+        tg = torch.where(steps[..., :L0] >= length.unsqueeze(-1), torch.full_like(caps, end), caps)
+        n_scored = (length + 1).clamp(max=L0)
+    live = ~absent
+    if not bool(live.any()):
+        raise ValueError("every caption slot is absent")
+    words = tg[live]
+    if bool(((words < 0) | (words >= d.V)).any()):
+        bad = words[(words < 0) | (words >= d.V)]
+        raise ValueError(f"caption ids outside the vocabulary [0, {d.V}): e.g. {int(bad[0])}")
+    Lc = int(n_scored[live].max())
+    tg = tg[..., :Lc].clone()
+    tg[absent] = -1
+    G = nimg * Cc * n_samples
+    if eps_steps is not None:
+        if len(eps_steps) < Lc:
+            raise ValueError(f"eps_steps holds {len(eps_steps)} steps, the longest caption needs {Lc}")
+        eps0 = eps_steps[0].to(dev, torch.float32)
+        eps = torch.stack([e.to(dev, torch.float32) for e in eps_steps[1:Lc]]) if Lc > 1 else None
+    else:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(seed)
+        eps0 = torch.randn(G, d.Z, device=dev, generator=gen)
+        eps = torch.randn(max(Lc - 1, 1), G, d.Z, device=dev, generator=gen)[: Lc - 1] if Lc > 1 else None
+    ctx = dec.prepare(feats, obj_means)
+    sent_g = sentiment.reshape(nimg, 1).expand(nimg, Cc * n_samples).reshape(G) if sentiment is not None else None
+    lps, ntok, tlp, trk = dec.score(ctx, sent_g, tg.to(dev), n_samples, end, eps0, eps, want_tokens=want_tokens, want_ranks=want_ranks)
+    lps = lps.view(nimg, Cc, n_samples)
+    return CaptionScores(log_probs=lps, n_tokens=ntok, marginal=torch.logsumexp(lps, -1) - math.log(n_samples),
+                         token_lp=tlp.view(nimg, Cc, n_samples, Lc) if tlp is not None else None,
+                         token_rank=trk.view(nimg, Cc, n_samples, Lc) if trk is not None else None)

@@ -138,6 +138,12 @@ class SamplerDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("seed", C.c_uint64)]
 
 
+class ScoreDesc(C.Structure):
+    _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_captions", C.c_int), ("n_samples", C.c_int), ("max_len", C.c_int),
+                ("end_index", C.c_int), ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("obj_atts", vp), ("targets", vp),
+                ("eps0", vp), ("eps", vp), ("log_probs", vp), ("token_lp", vp), ("token_rank", vp), ("n_tokens", vp)]
+
+
 class GumbelDesc(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64)]
 
@@ -247,6 +253,9 @@ SYMBOLS = {
     "ssc_sample_rows": (_i, [vp, _i, _i, _i, C.POINTER(SamplerDesc), vp, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_sample_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), vp, _sz, vp]),
+    "ssc_score_rows": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
+    "ssc_decode_score_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(ScoreDesc)]),
+    "ssc_decode_score": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), vp, _sz, vp]),
     "ssc_beam_first_gumbel": (_i, [C.POINTER(BeamDesc), C.POINTER(GumbelDesc), vp, vp]),
     "ssc_beam_step_gumbel": (_i, [C.POINTER(BeamDesc), C.POINTER(GumbelDesc), vp, vp, vp]),
     "ssc_decode_stochastic_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),

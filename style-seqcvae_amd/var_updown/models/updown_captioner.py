@@ -151,6 +151,7 @@ class UpDownCaptioner(nn.Module):
         self._eng: Optional[TrainEngine] = None
         self._dec: Optional[DecodeEngine] = None
         self._ctx_cache = None
+        self.n_z_samples = 1           # latent samples per caption of score_captions (from_config: MODEL.N_Z_SAMPLES)
 
     # ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -160,17 +161,19 @@ class UpDownCaptioner(nn.Module):
         with a sampler=... (the decode's); a model built without one (scripts/train.py) ignores it, as it ignores the other
         decode keys; diverse_beam=... (sampling.diverse_beam_from_config) likewise comes from the caller."""
         _C = config
-        return cls(vocabulary=kwargs.pop("vocabulary"), image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
-                   embedding_size=_C.MODEL.EMBEDDING_SIZE, hidden_size=_C.MODEL.HIDDEN_SIZE,
-                   attention_projection_size=_C.MODEL.ATTENTION_PROJECTION_SIZE, beam_size=_C.MODEL.BEAM_SIZE,
-                   max_caption_length=_C.DATA.MAX_CAPTION_LENGTH, use_cbs=_C.MODEL.USE_CBS,
-                   min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY, z_space=_C.MODEL.Z_SPACE,
-                   prior_std=_C.MODEL.PRIOR_STD, simple_vae=_C.MODEL.SIMPLE_VAE, latent_embedding=_C.MODEL.LATENT_EMBEDDING,
-                   sentiment_vae=_C.MODEL.SENTIMENT_VAE, senti_prior_multip=_C.MODEL.SENTI_PRIOR_MULTIP,
-                   latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
-                   device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
-                   sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
-                   diverse_beam=kwargs.get("diverse_beam"))
+        model = cls(vocabulary=kwargs.pop("vocabulary"), image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
+                    embedding_size=_C.MODEL.EMBEDDING_SIZE, hidden_size=_C.MODEL.HIDDEN_SIZE,
+                    attention_projection_size=_C.MODEL.ATTENTION_PROJECTION_SIZE, beam_size=_C.MODEL.BEAM_SIZE,
+                    max_caption_length=_C.DATA.MAX_CAPTION_LENGTH, use_cbs=_C.MODEL.USE_CBS,
+                    min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY, z_space=_C.MODEL.Z_SPACE,
+                    prior_std=_C.MODEL.PRIOR_STD, simple_vae=_C.MODEL.SIMPLE_VAE, latent_embedding=_C.MODEL.LATENT_EMBEDDING,
+                    sentiment_vae=_C.MODEL.SENTIMENT_VAE, senti_prior_multip=_C.MODEL.SENTI_PRIOR_MULTIP,
+                    latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
+                    device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
+                    sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
+                    diverse_beam=kwargs.get("diverse_beam"))
+        model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
+        return model
 
     def _initialize_glove(self):
         """GloVe 42B (+ dependency embeddings for 600-d) rows for the vocabulary (updown_captioner.py:168-226).
@@ -332,6 +335,28 @@ class UpDownCaptioner(nn.Module):
                 beams, lps = self._beam_search.search(start_predictions, None, step, fsm_d)
                 best = beams[:, 0, 0, :]
         return {"predictions": best}
+
+    def score_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, obj_atts=None,
+                       n_samples: Optional[int] = None, layout: str = "padded", want_tokens: bool = False, want_ranks: bool = False,
+                       eps_steps=None):
+        """How likely are the given captions under the model as it stands: image_features (B, R, F), caption_tokens (B, L) or
+        (B, C, L) int64 - by default in the training layout (0-padded, no boundary tokens; layout="decoded": a decoder's output) -,
+        each scored under n_samples (default: MODEL.N_Z_SAMPLES) latent samples drawn from the prior, the pooled prior of
+        SENTIMENT_VAE = 2 included (obj_atts as in forward()).  eps_steps: the caller's own noise, one (B * C * n_samples, Z) tensor per
+        step (default: a generator of the call's own, seeded by one draw of the global CPU generator).  One library call, no autograd; the mode (train / eval) is left as
+        it is and plays no part.  -> ssc_runtime.inference.CaptionScores.
+        The image context is formed from the parameters as they are NOW, so the call is correct between optimizer steps - unless
+        the caller has set DecodeEngine.weights_frozen, which promises that they do not change."""
+        from ssc_runtime.inference import score_captions
+        self._engine()
+        B, R, _ = image_features.shape
+        caps = caption_tokens if caption_tokens.dim() == 3 else caption_tokens.unsqueeze(1)
+        obj_means = self._obj_means(obj_atts, B, R)
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        with torch.no_grad():
+            return score_captions(self._dec, image_features.to(self._eng.device, torch.float32), sent, caps,
+                                  n_samples or self.n_z_samples, self._boundary_index, layout, eps_steps=eps_steps, obj_means=obj_means,
+                                  want_tokens=want_tokens, want_ranks=want_ranks)
 
     def _sample_decode(self, image_features, obj_means, sentiment):
         """Eval forward with a word sampler: the whole decode in one library call (DecodeEngine.sample).  The latent noise is drawn
