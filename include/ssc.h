@@ -980,6 +980,41 @@ size_t ssc_eval_consensus_workspace_bytes(const ssc_eval_refs* refs, const ssc_e
 int ssc_eval_consensus(const ssc_eval_refs* refs, const ssc_eval_consensus_desc* d, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Self-critical sequence training (Rennie et al. 2017; Luo 2020): the step between the sampled decode (ssc_decode_sample), the
+ * per-caption reward (ssc_eval_score) and the train step (ssc_train_fwd / ssc_train_bwd).  P images x N samples, G = P * N rows,
+ * row g = p * N + i.  The sampled captions become the train step's `caps`; row g's reward is r_g = sum_k reward_weights[k] *
+ * scores[g][k] and its upstream gradients are gl_g = loss_scale * (r_g - b_g), gk_g = kld_scale.  Baseline b_g: 0 (baseline 0),
+ * the mean reward of the image's other N - 1 samples, (S_p - r_g) / (N - 1) with S_p summed in sample order (1), or the reward of
+ * the image's row of base_scores (2).  All of it in fp64, in column / sample order, rounded to fp32 once per output.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int P, N;                   /* 1 <= N <= 128 (as ssc_eval_score) */
+  int steps, L;               /* columns of predictions and of caps: L >= steps >= 1 */
+  int end_index;
+  const int64_t* predictions; /* (G, steps): as ssc_decode_sample leaves them */
+  const double* scores;       /* (P, N, 6): ssc_eval_score_desc.scores */
+  const double* base_scores;  /* (P, 6): the scores of one baseline caption per image; NULL unless baseline is 2 */
+  double reward_weights[6];   /* B1, B2, B3, B4, ROUGE-L, CIDEr-D */
+  int baseline;               /* 0 none, 1 leave-one-out (N >= 2), 2 given per image */
+  double loss_scale;          /* 1 / G for the mean over the rows */
+  double kld_scale;           /* 1 / (G * KLD_WEIGHT) */
+  int64_t* caps;              /* (G, L): the row's tokens before its first end_index (all `steps` tokens where it has none), then
+                               * 0.  Ids are copied as they are: an id 0 inside a caption is a 0 of the train step's caps */
+  int* lengths;               /* (G): the number of tokens kept */
+  float* reward;              /* (G): r */
+  float* advantage;           /* (G): r - b */
+  float* gl;                  /* (G) */
+  float* gk;                  /* (G) */
+  double* stats;              /* (4): mean r, mean b, mean |r - b|, share of rows with no end_index */
+} ssc_scst_desc;
+
+/* A pack kernel (one wave per row) and an advantage kernel (one workgroup per image, one more for the statistics).  Stream-ordered,
+ * no read-back (capturable), no atomics: two calls are bit-identical, and two samples of an image with bit-equal scores get
+ * bit-equal outputs (N = 2, leave-one-out: advantage exactly 0).  SSC_EINVAL and nothing written: a NULL pointer, N outside
+ * 1..128, L < steps, baseline 1 with N = 1, baseline 2 without base_scores. */
+int ssc_scst_prepare(const ssc_scst_desc* d, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

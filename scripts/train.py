@@ -56,6 +56,21 @@ parser.add_argument("--attribute-table", default="",
                          "SentiWordNet files (updown_captioner.py:79-93); only needed when obj_atts arrive as attribute strings")
 parser.add_argument("--fused-optimizer", action="store_true",
                     help="clip + SGD in one HIP pass on the flat buffers instead of torch.optim.SGD")
+parser.add_argument("--scst-references", default="",
+                    help="train with self-critical steps (ssc_runtime/scst.py) instead of cross-entropy ones: sampled captions rewarded "
+                         'against these references - COCO annotations {"annotations": [{"image_id", "caption"}]} or {image_id: [captions]}, '
+                         "as scripts/evaluate.py reads them; with --synthetic any value: the synthetic captions are the references.  "
+                         "Implies the fused optimiser; OPTIM.BATCH_SIZE counts images")
+parser.add_argument("--scst-samples", type=int, default=5, help="with --scst-references: captions sampled per image")
+parser.add_argument("--scst-baseline", default="loo", choices=["loo", "greedy", "none"],
+                    help="loo: the mean reward of the image's other samples; greedy: the reward of the arg-max caption at zero noise")
+parser.add_argument("--scst-sampler", default="multinomial", choices=["multinomial", "top-k", "top-p"],
+                    help="the word sampler of the rollout (MODEL.DECODE_SAMPLER's names)")
+parser.add_argument("--scst-temperature", type=float, default=1.0)
+parser.add_argument("--scst-top-k", type=int, default=40)
+parser.add_argument("--scst-top-p", type=float, default=0.9)
+parser.add_argument("--scst-reward", default="0,0,0,0,0,1", help="reward weights B1,B2,B3,B4,R,C (default: CIDEr-D alone)")
+parser.add_argument("--scst-max-steps", type=int, default=20, help="with --scst-references: longest sampled caption")
 
 
 VAL_IMAGES_PER_CALL = 100
@@ -82,6 +97,27 @@ def validate(model, val, n_images, n_samples, seed, iteration, device):
     s = CaptionScores.concat(parts).summary()
     return {"val_nll_per_token": s["nll_per_token"], "val_perplexity": s["perplexity"],
             "val_marginal_nll_per_token": s["marginal_nll_per_token"], "val_top1": s["top1"]}
+
+
+def scst_sampler(args):
+    """The word sampler the --scst-sampler / --scst-temperature / --scst-top-k / --scst-top-p flags describe."""
+    from ssc_runtime import sampling
+    if args.scst_sampler == "top-k":
+        return sampling.TopKSampler(k=args.scst_top_k, temperature=args.scst_temperature)
+    if args.scst_sampler == "top-p":
+        return sampling.TopPSampler(p=args.scst_top_p, temperature=args.scst_temperature)
+    return sampling.MultinomialSampler(temperature=args.scst_temperature)
+
+
+def scst_references(args, data, vocabulary):
+    """{image_id: [captions]} of --scst-references; with --synthetic the synthetic captions, spelled with the vocabulary's words."""
+    from ssc_runtime.evaluation import load_references
+    if not args.synthetic:
+        return load_references(args.scst_references)
+    refs = {}
+    for iid, cap in zip(data.image_id.tolist(), data.caps.tolist()):
+        refs.setdefault(iid, []).append(" ".join(vocabulary.get_token_from_index(t) for t in cap if t != 0))
+    return refs
 
 
 def main():
@@ -148,7 +184,7 @@ def main():
     # Learning rate: the reference's LambdaLR(1 - it / NUM_ITERATIONS) stepped once per iteration (train.py:132-134,176) gives
     # iteration i the rate LR * (1 - (i - 1) / N).  It is computed from the iteration number on BOTH paths, so a resumed run
     # continues the decay where it stopped (a fresh LambdaLR would restart at LR).
-    eng.dp_autograd = world > 1 and not _A.fused_optimizer
+    eng.dp_autograd = world > 1 and not (_A.fused_optimizer or _A.scst_references)
     named = list(model.named_parameters())
     start_iteration = 1
     if _A.start_from_checkpoint:
@@ -159,12 +195,19 @@ def main():
         model.load_state_dict(ckpt["model"])
         osd = ckpt.get("optimizer")
         if osd is not None:
-            if _A.fused_optimizer:
+            if _A.fused_optimizer or _A.scst_references:
                 eng.load_optimizer_state_dict(named, osd)
             else:
                 optimizer.load_state_dict({"state": osd["state"], "param_groups": osd["param_groups"]})
             start_iteration = int(osd.get("iteration", 0)) + 1   # correct resume (the reference restarts at 1: train.py:149)
     # batch i of a run is a function of (seed, i): a resumed run continues the data order where it stopped
+    scst = None
+    if _A.scst_references:
+        from ssc_runtime.evaluation import CaptionReferences
+        from ssc_runtime.scst import SelfCritical, parse_reward_weights, scst_seed
+        scst = SelfCritical(eng, model._dec, CaptionReferences(scst_references(_A, data, vocabulary), device=device), vocabulary,
+                            n_samples=_A.scst_samples, sampler=scst_sampler(_A), baseline=_A.scst_baseline,
+                            reward_weights=parse_reward_weights(_A.scst_reward), max_steps=_A.scst_max_steps)
     loader = cycle(data, _C.OPTIM.BATCH_SIZE // world, device, rank, world, seed=_C.RANDOM_SEED, start_batch=start_iteration - 1)
     log = open(os.path.join(_A.serialization_dir, "scalars.jsonl"), "a") if rank == 0 else None
 
@@ -181,7 +224,17 @@ def main():
         if _A.zero_eps:
             Bz, Lz = batch["caption_tokens"].shape
             model._eps_override = torch.zeros(Lz + 1, Bz, _C.MODEL.Z_SPACE, device=device)
-        if _A.fused_optimizer:
+        scst_stats = None
+        if scst is not None:
+            # rollout noise and word draws are a function of (RANDOM_SEED, iteration, rank): a resumed run draws what this one would
+            loss_b, kld_b, scst_stats = scst.step(batch["image_features"], batch["image_id"].tolist(), batch["sentiment"], lr=lr,
+                                                  kld_weight=_C.MODEL.KLD_WEIGHT, momentum=_C.OPTIM.MOMENTUM,
+                                                  weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
+                                                  decoder_frozen=not train_decoder, seed=scst_seed(_C.RANDOM_SEED, iteration, rank),
+                                                  obj_atts=batch.get("obj_atts"))
+            reconstr_loss, kld_loss = loss_b.mean(), kld_b.mean()
+            loss = reconstr_loss + kld_loss / _C.MODEL.KLD_WEIGHT
+        elif _A.fused_optimizer:
             B, L = batch["caption_tokens"].shape
             eps = model._draw_eps(L + 1, B, device)
             loss_b, kld_b = eng.train_step(batch["image_features"], batch["caption_tokens"], batch["sentiment"], eps, lr=lr,
@@ -203,6 +256,9 @@ def main():
         if rank == 0 and (iteration % 100 == 0 or iteration == start_iteration or _C.OPTIM.NUM_ITERATIONS <= 100):
             rec = {"iteration": iteration, "1reconstr_loss": float(reconstr_loss), "2kld_loss": float(kld_loss),
                    "3loss": float(loss), "4learning_rate": lr, "elapsed_s": time.time() - t0}
+            if scst_stats is not None:
+                st = scst_stats.tolist()
+                rec.update({"5reward": st[0], "6baseline": st[1], "7abs_advantage": st[2], "8no_end_share": st[3]})
             log.write(json.dumps(rec) + "\n")
             log.flush()
             if iteration % 2000 == 0 or iteration == start_iteration:
@@ -214,7 +270,7 @@ def main():
             log.write(json.dumps(rec) + "\n")
             log.flush()
         if rank == 0 and iteration % _A.checkpoint_every == 0:
-            if _A.fused_optimizer:
+            if _A.fused_optimizer or scst is not None:
                 osd = eng.optimizer_state_dict(named, lr, _C.OPTIM.MOMENTUM, _C.OPTIM.WEIGHT_DECAY, iteration)
             else:
                 osd = optimizer.state_dict()

@@ -553,6 +553,13 @@ class TrainEngine:
                               torch.full((B,), 1.0 / (B * kld_weight), dtype=torch.float32, device=self.device))
             self._upstream_key = key
         gl, gk = self._upstream
+        self.backward_update(gl, gk, lr, momentum, weight_decay, max_norm, decoder_frozen, group)
+        return loss, kld
+
+    def backward_update(self, gl, gk, lr, momentum=0.9, weight_decay=0.001, max_norm=12.5, decoder_frozen=False, group=None):
+        """What follows the forward in one iteration: the backward of the last forward() with the per-row upstream gradients
+        gl / gk (B,), the gradient all-reduce, clip + SGD.  train_step passes the constant vectors of the mean objective, the
+        self-critical step (ssc_runtime/scst.py) the advantage-weighted ones: one path for both."""
         import torch.distributed as dist
 
         skip = self.decoder_names if decoder_frozen else ()
@@ -564,4 +571,3 @@ class TrainEngine:
             world = self.allreduce_grads(group)
             sq_parts = None
         self.clip_sgd_step(lr, momentum, weight_decay, max_norm, decoder_frozen, gscale=1.0 / world, sq_norm=sq_parts)
-        return loss, kld

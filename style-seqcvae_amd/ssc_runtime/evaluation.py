@@ -322,6 +322,25 @@ def _caption_ids(predictions):
     return groups, arr, words
 
 
+def _eval_score(prep: "_Prepared", pred: torch.Tensor, boundary_index: int, vocab_size: int, id_map, style, ref_image):
+    """One ssc_eval_score call on device tensors: pred (P, N, steps) int64 contiguous, id_map (vocab_size) int32, style optional
+    (vocab_size) uint8, ref_image (P) int32.  -> (scores (P, N, 6) fp64, counts (P, N, 10), image_counts (P, 9), top5 (P, 5)) on the
+    device; nothing but the call's own error flag is read back."""
+    P, N, steps = pred.shape
+    dev = pred.device
+    scores = torch.empty(P, N, 6, dtype=torch.float64, device=dev)
+    counts = torch.empty(P, N, 10, dtype=torch.int32, device=dev)
+    img = torch.empty(P, 9, dtype=torch.int32, device=dev)
+    top5 = torch.empty(P, 5, dtype=torch.int32, device=dev)
+    d = L.EvalScoreDesc(L.ptr(pred), P, N, steps, int(boundary_index), int(vocab_size), L.ptr(id_map), L.ptr(style), L.ptr(ref_image),
+                        L.ptr(scores), L.ptr(counts), L.ptr(img), L.ptr(top5))
+    lib = L.load()
+    ws = torch.empty(lib.ssc_eval_score_workspace_bytes(ctypes.byref(prep.desc), ctypes.byref(d)), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib.ssc_eval_score(ctypes.byref(prep.desc), ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
+    return scores, counts, img, top5
+
+
 class _Prepared:
     """The device state of one evaluated image set: its references as CSR arrays and what ssc_eval_prepare_refs wrote."""
 
@@ -433,16 +452,7 @@ class CaptionReferences:
         id_map = torch.from_numpy(id_map).to(dev)
         ref_image = torch.tensor([prep.index.get(i, -1) for i in image_ids], dtype=torch.int32, device=dev)
         pred = pred.to(dev).contiguous()
-        scores = torch.empty(P, N, 6, dtype=torch.float64, device=dev)
-        counts = torch.empty(P, N, 10, dtype=torch.int32, device=dev)
-        img = torch.empty(P, 9, dtype=torch.int32, device=dev)
-        top5 = torch.empty(P, 5, dtype=torch.int32, device=dev)
-        d = L.EvalScoreDesc(L.ptr(pred), P, N, steps, int(boundary_index), len(words), L.ptr(id_map), L.ptr(style), L.ptr(ref_image),
-                            L.ptr(scores), L.ptr(counts), L.ptr(img), L.ptr(top5))
-        lib = L.load()
-        ws = torch.empty(lib.ssc_eval_score_workspace_bytes(ctypes.byref(prep.desc), ctypes.byref(d)), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            lib.ssc_eval_score(ctypes.byref(prep.desc), ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
+        scores, counts, img, top5 = _eval_score(prep, pred, boundary_index, len(words), id_map, style, ref_image)
         rows = [p for p, i in enumerate(image_ids) if i in self.tokens]
         imgc = img.cpu().numpy().astype(np.int64)
         set_out = _eval_set(pred, boundary_index, len(words), prep, id_map, ref_image) if set_diversity else None

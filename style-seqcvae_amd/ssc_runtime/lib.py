@@ -172,6 +172,13 @@ class EvalConsensusDesc(C.Structure):
                 ("id_map", vp), ("neighbours", vp), ("k", C.c_int), ("scores", vp), ("pool_refs", vp), ("pick", vp), ("order", vp)]
 
 
+class ScstDesc(C.Structure):
+    _fields_ = [("P", C.c_int), ("N", C.c_int), ("steps", C.c_int), ("L", C.c_int), ("end_index", C.c_int), ("predictions", vp),
+                ("scores", vp), ("base_scores", vp), ("reward_weights", C.c_double * 6), ("baseline", C.c_int),
+                ("loss_scale", C.c_double), ("kld_scale", C.c_double), ("caps", vp), ("lengths", vp), ("reward", vp),
+                ("advantage", vp), ("gl", vp), ("gk", vp), ("stats", vp)]
+
+
 # name -> (restype, argtypes).  Every symbol include/ssc.h declares is listed; tests check they all resolve.
 _i, _f, _sz = C.c_int, C.c_float, C.c_size_t
 SYMBOLS = {
@@ -280,6 +287,7 @@ SYMBOLS = {
     "ssc_knn_merge": (_i, [vp, _i, _i, _i, _i, _i, vp, vp, vp, vp]),
     "ssc_eval_consensus_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc)]),
     "ssc_eval_consensus": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc), vp, _sz, vp]),
+    "ssc_scst_prepare": (_i, [C.POINTER(ScstDesc), vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)

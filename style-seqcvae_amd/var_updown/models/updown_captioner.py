@@ -150,6 +150,7 @@ class UpDownCaptioner(nn.Module):
         self._eps_override = None      # test hook: explicit (T,B,Z) / list of (G,Z)
         self._eng: Optional[TrainEngine] = None
         self._dec: Optional[DecodeEngine] = None
+        self._scst = None   # (key, SelfCritical, its references) of the last scst_step
         self._ctx_cache = None
         self.n_z_samples = 1           # latent samples per caption of score_captions (from_config: MODEL.N_Z_SAMPLES)
 
@@ -357,6 +358,29 @@ class UpDownCaptioner(nn.Module):
             return score_captions(self._dec, image_features.to(self._eng.device, torch.float32), sent, caps,
                                   n_samples or self.n_z_samples, self._boundary_index, layout, eps_steps=eps_steps, obj_means=obj_means,
                                   want_tokens=want_tokens, want_ranks=want_ranks)
+
+    def scst_step(self, image_features: torch.Tensor, image_ids, sentiment=None, obj_atts=None, *, references, lr, seed,
+                  kld_weight: float = 750.0, momentum: float = 0.9, weight_decay: float = 0.001, max_norm: float = 12.5,
+                  decoder_frozen: bool = False, group=None, n_samples: int = 5, sampler=None, baseline: str = "loo",
+                  reward_weights=None, max_steps: Optional[int] = None):
+        """One self-critical training step (ssc_runtime.scst.SelfCritical.step) on the engines this module owns: n_samples captions
+        per image are sampled from the model as it stands, rewarded by CIDEr-D (reward_weights: B1, B2, B3, B4, ROUGE-L, CIDEr-D)
+        against `references` (a CaptionReferences keyed by image_ids), and the parameters are updated in place - clip + SGD on the
+        flat buffers, as scripts/train.py --fused-optimizer.  obj_atts as in forward().  max_steps defaults to the maximum caption
+        length.  -> (loss (B * n_samples,), kld (B * n_samples,), stats (4,) fp64: mean reward, mean baseline, mean |advantage|, share
+        of samples without an end)."""
+        from ssc_runtime.scst import CIDER_ONLY, SelfCritical
+        eng = self._engine()
+        B, R, _ = image_features.shape
+        weights = tuple(reward_weights) if reward_weights is not None else CIDER_ONLY
+        steps = int(max_steps or self._max_caption_length)
+        key = (id(references), n_samples, repr(sampler), baseline, weights, steps)
+        if self._scst is None or self._scst[0] != key or self._scst[1].eng is not eng:
+            self._scst = (key, SelfCritical(eng, self._dec, references, self._vocabulary, n_samples, sampler, baseline, weights, steps),
+                          references)
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        return self._scst[1].step(image_features, image_ids, sent, lr, kld_weight, momentum, weight_decay, max_norm, decoder_frozen,
+                                  group, seed, self._obj_means(obj_atts, B, R))
 
     def _sample_decode(self, image_features, obj_means, sentiment):
         """Eval forward with a word sampler: the whole decode in one library call (DecodeEngine.sample).  The latent noise is drawn
