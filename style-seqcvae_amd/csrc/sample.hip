@@ -10,16 +10,14 @@
 // only, so every histogram - and therefore the kept set - is independent of the order the lanes arrive in.  Ties at the cut are
 // resolved by a second radix select on the index (lower index first).  The draw is Gumbel-max over the kept set with
 // counter-based Philox4x32-10 noise: bit-reproducible for a given seed, no float atomics, no order-dependent reduction.
+// ssc_decode_sample's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
-#include <thread>
 
-#include "ssc_common.h"
+#include "decode_loop.h"
 #include "ssc_philox.h"
 #include "ssc_radix.h"
 
 namespace {
-
-inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct SampleArgs {
   const float* logits; size_t ld; int V;
@@ -238,14 +236,6 @@ SampleArgs sample_args(const ssc_sampler_desc* s, const float* logits, size_t ld
   return a;
 }
 
-__global__ void sample_ctl_init_kernel(int* __restrict__ ctl, int n, int max_steps) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) ctl[i] = i == 0 ? max_steps : 0;
-}
-__global__ void sample_fill_i64_kernel(int64_t* __restrict__ p, int n, int64_t v) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) p[i] = v;
-}
 // preds (max_steps, B) -> out (B, max_steps); columns >= ctl[0] (steps the host never queued) hold end_index
 __global__ void sample_collect_kernel(const int64_t* __restrict__ preds, const int* __restrict__ ctl, int max_steps, int B,
                                       int end_index, int64_t* __restrict__ out) {
@@ -256,7 +246,7 @@ __global__ void sample_collect_kernel(const int64_t* __restrict__ preds, const i
 }
 
 struct SampleLayout {
-  size_t st[2][4];   // h1, c1, hd, cd: two generations of (B, H)
+  SscStepStates states;   // (B, H) rows
   size_t tokens0;    // (B) int64 start tokens
   size_t parent0;    // (B) int64 zeros: every row is its own parent (the beam-1 search's parent list)
   size_t preds;      // (max_steps, B) int64
@@ -270,32 +260,28 @@ struct SampleLayout {
 
 SampleLayout sample_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
   SampleLayout l;
-  const size_t B = (size_t)d->nimg * d->n_samples, H = cfg->H;
+  const size_t B = (size_t)d->nimg * d->n_samples;
   size_t o = 0;
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 4; ++k) { l.st[g][k] = o; o += a256(B * H * 4); }
-  l.tokens0 = o; o += a256(B * 8);
-  l.parent0 = o; o += a256(B * 8);
-  l.preds = o; o += a256((size_t)d->max_steps * B * 8);
-  l.lp = o; o += a256(B * 4);
-  l.steplp = o; o += a256(B * 4);
-  l.alpha = o; o += a256(B * (size_t)d->R * 4);
-  l.logits = o; o += a256(B * (size_t)cfg->V * 4);
+  l.states.reserve(o, B, cfg->H);
+  l.tokens0 = ssc_ws_take(o, B * 8);
+  l.parent0 = ssc_ws_take(o, B * 8);
+  l.preds = ssc_ws_take(o, (size_t)d->max_steps * B * 8);
+  l.lp = ssc_ws_take(o, B * 4);
+  l.steplp = ssc_ws_take(o, B * 4);
+  l.alpha = ssc_ws_take(o, B * (size_t)d->R * 4);
+  l.logits = ssc_ws_take(o, B * (size_t)cfg->V * 4);
   l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)B, d->R);
-  l.stepws = o; o += a256(l.stepws_bytes);
+  l.stepws = ssc_ws_take(o, l.stepws_bytes);
   l.total = o;
   return l;
 }
 
 bool sample_desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!cfg || !d) return false;
-  if (d->nimg <= 0 || d->R <= 0 || d->n_samples <= 0 || d->max_steps <= 0 || d->end_index < 0 || d->end_index >= cfg->V) return false;
+  if (!ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return false;
   if (d->S != 1 || d->beam != 1 || d->fsm || d->tables || d->mach) return false;   // word sampling: one row per batch entry, no machine
   const long B = (long)d->nimg * d->n_samples;
   if (B > (1L << 24)) return false;
-  if (!d->feats || !d->imgbuf || !d->eps0 || (d->max_steps > 1 && !d->eps) || !d->predictions || !d->log_probs || !d->ctl) return false;
-  if (cfg->kld_mode == 2 ? !d->obj_atts : ((cfg->S || cfg->pm_scale != 0.f) && !d->sentiment)) return false;
-  return true;
+  return ssc_decode_inputs_ok(cfg, d, d->max_steps) && d->predictions && d->log_probs && d->ctl;
 }
 
 }  // namespace
@@ -313,7 +299,7 @@ extern "C" int ssc_sample_rows(const float* logits, int ld, int rows, int V, con
 }
 
 extern "C" size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->max_steps <= 0 || d->R <= 0) return 0;
+  if (!ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return 0;
   return sample_layout(cfg, d).total;
 }
 
@@ -325,69 +311,45 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* W = (char*)workspace;
-  const int B = d->nimg * d->n_samples, H = cfg->H, V = cfg->V, Z = cfg->Z;
-  float* stt[2][4];
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 4; ++k) stt[g][k] = (float*)(W + l.st[g][k]);
+  const int B = d->nimg * d->n_samples, V = cfg->V, Z = cfg->Z;
+  const SscStepStates& states = l.states;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
   int64_t* parent0 = (int64_t*)(W + l.parent0);
   int64_t* preds = (int64_t*)(W + l.preds);
   float* lp = (float*)(W + l.lp);
   float* steplp = (float*)(W + l.steplp);
   float* logits = (float*)(W + l.logits);
-  const int nctl = 2 + 2 * d->max_steps;
   int* ctl = d->ctl;
 
-  SSC_LAUNCH(sample_ctl_init_kernel, dim3(ssc_cdiv(nctl, 256)), dim3(256), 0, st, ctl, nctl, d->max_steps);
-  SSC_CHECK_LAUNCH();
-  SSC_LAUNCH(sample_fill_i64_kernel, dim3(ssc_cdiv(B, 256)), dim3(256), 0, st, tokens0, B, (int64_t)d->end_index);
-  SSC_CHECK_LAUNCH();
+  SSC_TRY(ssc_decode_start(ctl, d->max_steps, tokens0, B, d->end_index, st));
   if (hipMemsetAsync(parent0, 0, (size_t)B * 8, st) != hipSuccess) return SSC_EHIP;
   if (hipMemsetAsync(lp, 0, (size_t)B * 4, st) != hipSuccess) return SSC_EHIP;
-  for (int k = 0; k < 4; ++k)   // zero start states (updown_cell.py:131-141)
-    if (hipMemsetAsync(stt[1][k], 0, (size_t)B * H * 4, st) != hipSuccess) return SSC_EHIP;
+  SSC_TRY(states.zero(W, 1, B, st));
 
   // the steps take the form the beam-1 search gives them (ssc_decode_search with S = beam = 1): same tables, same parent list
-  const bool table = d->R <= 128 && B >= 512 && d->n_samples >= 16 && ssc_decode_att_table_enabled();
+  const bool want_table = ssc_att_table_wanted(d->R, B, d->n_samples);
+  SscAttTable table;
   ssc_decode_step_desc sd{};
   sd.R = d->R; sd.feats = d->feats; sd.imgbuf = d->imgbuf; sd.alpha = (float*)(W + l.alpha); sd.log_probs = logits; sd.raw_logits = 1;
   sd.obj_atts = d->obj_atts;
   sd.G = B; sd.rows_per_image = d->n_samples; sd.tokens = tokens0; sd.sentiment = d->sentiment; sd.eps = d->eps0;
-  sd.h1 = stt[1][0]; sd.c1 = stt[1][1]; sd.hd = stt[1][2]; sd.cd = stt[1][3];
-  sd.h1_out = stt[0][0]; sd.c1_out = stt[0][1]; sd.hd_out = stt[0][2]; sd.cd_out = stt[0][3];
-  sd.att_table = table ? 2 : 0;
+  states.bind(W, 1, &sd);
+  sd.att_table = table.next(want_table);
   SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
   a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
   a.ctl = d->early_stop ? ctl : nullptr; a.max_steps = d->max_steps; a.host_flag = d->early_stop ? d->host_flag : nullptr;
   a.step = 0; a.last_pred = nullptr; a.pred_out = preds;
   SSC_TRY(sample_launch(a, B, st));
-  // Early stop and the host's bounded run-ahead: as in ssc_decode_search (the sampler's last workgroup of step t notes t in
-  // host_flag[1]; step t is queued only once step t - RUN_AHEAD has completed).  Not under stream capture.
-  constexpr int RUN_AHEAD = 2;
-  bool bounded = false;
-  if (d->early_stop && d->host_flag_host) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    bounded = cs == hipStreamCaptureStatusNone;
-  }
-  auto wait_for_step = [&](int step) {
-    const volatile int* hf = (const volatile int*)d->host_flag_host;
-    for (unsigned spin = 1; hf[1] < step && hf[0] == 0; ++spin) {
-      if ((spin & 1023u) == 0 && hipStreamQuery(st) != hipErrorNotReady) { (void)hipGetLastError(); break; }
-      std::this_thread::yield();
-    }
-  };
+  const SscStepPacer pacer(d->early_stop, d->host_flag_host, st);   // (the sampler's last workgroup of a step notes it for the host)
   int cur = 0;
-  sd.att_table = table ? 1 : 0;
   sd.parent = parent0; sd.group = 1;
   for (int t = 1; t < d->max_steps; ++t) {
-    if (bounded && t > RUN_AHEAD) wait_for_step(t - RUN_AHEAD);
-    if (d->early_stop && d->host_flag_host && *(volatile const int*)d->host_flag_host != 0) break;
+    if (pacer.stop_before(t)) break;
     const int64_t* last = preds + (size_t)(t - 1) * B;
     sd.tokens = last; sd.eps = d->eps + (size_t)(t - 1) * B * Z;
-    sd.h1 = stt[cur][0]; sd.c1 = stt[cur][1]; sd.hd = stt[cur][2]; sd.cd = stt[cur][3];
-    sd.h1_out = stt[1 - cur][0]; sd.c1_out = stt[1 - cur][1]; sd.hd_out = stt[1 - cur][2]; sd.cd_out = stt[1 - cur][3];
+    states.bind(W, cur, &sd);
+    sd.att_table = table.next(want_table);
     sd.row_lp = d->skip_dead ? lp : nullptr; sd.end_index = d->end_index;   // ended rows are not stepped
     SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;

@@ -8,14 +8,13 @@
 // entries that rank ahead of the target, whose logit is read first.  The pairs are combined in a fixed order (wave butterflies,
 // then the waves in index order): no float atomics, the same bits on every run.  The step log-prob is formed as
 // (x_target - max) - log(sum): the first difference is exact, so logits of magnitude 1e4 lose nothing to the subtraction.
+// ssc_decode_score's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
 
-#include "ssc_common.h"
+#include "decode_loop.h"
 #include "ssc_radix.h"
 
 namespace {
-
-inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 constexpr int SCORE_THREADS = 256;
 constexpr int SCORE_WAVES = SCORE_THREADS / 64;
@@ -126,7 +125,7 @@ __global__ void score_prepare_kernel(const int64_t* __restrict__ targets, int NC
 }
 
 struct ScoreLayout {
-  size_t st[2][4];   // h1, c1, hd, cd: two generations of (G, H)
+  SscStepStates states;   // (G, H) rows
   size_t tgt;        // (L, G) int64
   size_t fed;        // (L, G) int64
   size_t parent0;    // (G) int64 zeros: every row is its own parent (the beam-1 search's parent list)
@@ -140,34 +139,29 @@ struct ScoreLayout {
 
 ScoreLayout score_layout(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
   ScoreLayout l;
-  const size_t G = (size_t)d->nimg * d->n_captions * d->n_samples, H = cfg->H;
+  const size_t G = (size_t)d->nimg * d->n_captions * d->n_samples;
   size_t o = 0;
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 4; ++k) { l.st[g][k] = o; o += a256(G * H * 4); }
-  l.tgt = o; o += a256((size_t)d->max_len * G * 8);
-  l.fed = o; o += a256((size_t)d->max_len * G * 8);
-  l.parent0 = o; o += a256(G * 8);
-  l.lp = o; o += a256(G * 4);
-  l.steplp = o; o += a256(G * 4);
-  l.alpha = o; o += a256(G * (size_t)d->R * 4);
-  l.logits = o; o += a256(G * (size_t)cfg->V * 4);
+  l.states.reserve(o, G, cfg->H);
+  l.tgt = ssc_ws_take(o, (size_t)d->max_len * G * 8);
+  l.fed = ssc_ws_take(o, (size_t)d->max_len * G * 8);
+  l.parent0 = ssc_ws_take(o, G * 8);
+  l.lp = ssc_ws_take(o, G * 4);
+  l.steplp = ssc_ws_take(o, G * 4);
+  l.alpha = ssc_ws_take(o, G * (size_t)d->R * 4);
+  l.logits = ssc_ws_take(o, G * (size_t)cfg->V * 4);
   l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)G, d->R);
-  l.stepws = o; o += a256(l.stepws_bytes);
+  l.stepws = ssc_ws_take(o, l.stepws_bytes);
   l.total = o;
   return l;
 }
 
 bool score_dims_ok(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
-  if (!cfg || !d) return false;
-  if (d->nimg <= 0 || d->R <= 0 || d->n_captions <= 0 || d->n_samples <= 0 || d->max_len <= 0) return false;
+  if (!ssc_decode_dims_ok(cfg, d, d ? d->max_len : 0) || d->n_captions <= 0) return false;
   return (long)d->nimg * d->n_captions * d->n_samples <= (1L << 24);
 }
 
 bool score_desc_ok(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
-  if (!score_dims_ok(cfg, d) || d->end_index < 0 || d->end_index >= cfg->V) return false;
-  if (!d->feats || !d->imgbuf || !d->targets || !d->eps0 || (d->max_len > 1 && !d->eps) || !d->log_probs || !d->n_tokens) return false;
-  if (cfg->kld_mode == 2 ? !d->obj_atts : ((cfg->S || cfg->pm_scale != 0.f) && !d->sentiment)) return false;
-  return true;
+  return score_dims_ok(cfg, d) && ssc_decode_inputs_ok(cfg, d, d->max_len) && d->targets && d->log_probs && d->n_tokens;
 }
 
 }  // namespace
@@ -195,10 +189,8 @@ extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, c
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* W = (char*)workspace;
-  const int rpi = d->n_captions * d->n_samples, G = d->nimg * rpi, H = cfg->H, V = cfg->V, Z = cfg->Z, L = d->max_len;
-  float* stt[2][4];
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 4; ++k) stt[g][k] = (float*)(W + l.st[g][k]);
+  const int rpi = d->n_captions * d->n_samples, G = d->nimg * rpi, V = cfg->V, Z = cfg->Z, L = d->max_len;
+  const SscStepStates& states = l.states;
   int64_t* tgt = (int64_t*)(W + l.tgt);
   int64_t* fed = (int64_t*)(W + l.fed);
   int64_t* parent0 = (int64_t*)(W + l.parent0);
@@ -209,11 +201,11 @@ extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, c
              d->end_index, tgt, fed, lp, d->n_tokens);
   SSC_CHECK_LAUNCH();
   if (hipMemsetAsync(parent0, 0, (size_t)G * 8, st) != hipSuccess) return SSC_EHIP;
-  for (int k = 0; k < 4; ++k)   // zero start states (updown_cell.py:131-141)
-    if (hipMemsetAsync(stt[1][k], 0, (size_t)G * H * 4, st) != hipSuccess) return SSC_EHIP;
+  SSC_TRY(states.zero(W, 1, G, st));
 
   // the steps take the form the beam-1 drivers give them (ssc_decode_sample): same tables, same parent list
-  const bool table = d->R <= 128 && G >= 512 && rpi >= 16 && ssc_decode_att_table_enabled();
+  const bool want_table = ssc_att_table_wanted(d->R, G, rpi);
+  SscAttTable table;
   ssc_decode_step_desc sd{};
   sd.R = d->R; sd.feats = d->feats; sd.imgbuf = d->imgbuf; sd.alpha = (float*)(W + l.alpha); sd.log_probs = logits; sd.raw_logits = 1;
   sd.obj_atts = d->obj_atts;
@@ -225,12 +217,9 @@ extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, c
   for (int t = 0; t < L; ++t) {
     sd.tokens = fed + (size_t)t * G;
     sd.eps = t == 0 ? d->eps0 : d->eps + (size_t)(t - 1) * G * Z;
-    sd.h1 = stt[cur][0]; sd.c1 = stt[cur][1]; sd.hd = stt[cur][2]; sd.cd = stt[cur][3];
-    sd.h1_out = stt[1 - cur][0]; sd.c1_out = stt[1 - cur][1]; sd.hd_out = stt[1 - cur][2]; sd.cd_out = stt[1 - cur][3];
-    if (t == 0) {
-      sd.att_table = table ? 2 : 0;   // (every row's fed token is END here: no row may be skipped by it)
-    } else {
-      sd.att_table = table ? 1 : 0;
+    states.bind(W, cur, &sd);
+    sd.att_table = table.next(want_table);
+    if (t > 0) {   // (at step 0 every row's fed token is END: no row may be skipped by it)
       sd.parent = parent0; sd.group = 1;
       sd.row_lp = lp; sd.end_index = d->end_index;   // ended and absent rows (fed token END) are not stepped
     }

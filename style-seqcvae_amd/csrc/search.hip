@@ -2,20 +2,18 @@
 // first step, state enlargement, then per step  decode step -> selection -> back-pointers  with the early-stop bookkeeping on the
 // device - launched from here like ssc_train_fwd launches the training time loop: no Python and no framework glue between the
 // steps (round 3's driver issued ~100 copy / fill / elementwise launches per call from torch around the ~25 library launches of a
-// step).
+// step).  The step states, the table decision, the early-stop pacing and the descriptor checks are the shared host driver of
+// decode_loop.h ("the one-call decodes' host driver").
 // Reference: ConstrainedBeamSearch.search (updown-baseline/updown/modules/cbs.py:59-277) driving
 // UpDownCaptioner._decode_step in eval mode (var_updown/var_updown/models/updown_captioner.py:371-455), as the reference's
 // inference loop does per image and latent sample (var_updown/scripts/inference.py:117-189).
 #include <math.h>
 
 #include <algorithm>
-#include <thread>
 
-#include "ssc_common.h"
+#include "decode_loop.h"
 
 namespace {
-
-inline size_t a256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // The selection a search runs: beam search (the machine's top-k), the stochastic beam search (Gumbel-top-k, sbs.hip) or the
 // sampled-node beam search (a word sampler's draws per beam, sampled_beam.hip) or the diverse beam search (groups of beams with a
@@ -33,8 +31,7 @@ bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d, Searc
 }
 
 struct SearchLayout {
-  size_t st[2][4];     // h1, c1, hd, cd: two generations of (G,H)
-  size_t pl[2][2];     // 2xFP16 numerics: the fp16 pieces of h1, hd - two generations of (G, Hk) words (ssc_decode_step_desc.h1_planes ...)
+  SscStepStates states;   // (G, H) rows; 2xFP16 numerics: with the fp16 pieces of h1, hd, (G, Hk) words
   size_t tokens0;      // (B) int64 start tokens
   size_t sent_rows;    // (G) float
   size_t preds;        // (max_steps, B, SB) int64
@@ -57,43 +54,40 @@ SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, S
   const size_t per_row = kind == SEARCH_DIVERSE ? (size_t)std::max(list, d->beam) : (size_t)d->per_node;
   const bool gumbel = kind == SEARCH_GUMBEL;
   const size_t B = (size_t)d->nimg * d->n_samples, SB = (size_t)d->S * d->beam, G = B * SB;
-  const size_t H = cfg->H;
   size_t o = 0;
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 4; ++k) { l.st[g][k] = o; o += a256(G * H * 4); }
   const size_t prow = cfg->gemm_mode == 3 && !cfg->tied && G >= 512 ? (size_t)ssc_decode_planes_ld(cfg) : 0;
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 2; ++k) { l.pl[g][k] = o; o += a256(G * prow * 4); }
-  l.tokens0 = o; o += a256(B * 8);
-  l.sent_rows = o; o += a256(G * 4);
-  l.preds = o; o += a256((size_t)d->max_steps * G * 8);
-  l.backs = o; o += a256((size_t)std::max(d->max_steps - 1, 1) * G * 8);
-  l.parent0 = o; o += a256(G * 8);
-  for (int g = 0; g < 2; ++g) { l.lp[g] = o; o += a256(G * 4); }
-  for (int g = 0; g < 2; ++g) { l.gs[g] = o; o += a256(gumbel ? G * 4 : 0); }
-  l.sval = o; o += a256(B * d->S * SB * per_row * 4 * (gumbel ? 2 : 1));
-  l.sidx = o; o += a256(B * d->S * SB * per_row * 8);
-  l.alpha = o; o += a256(G * (size_t)d->R * 4);
+  l.states.reserve(o, G, cfg->H, prow);
+  l.tokens0 = ssc_ws_take(o, B * 8);
+  l.sent_rows = ssc_ws_take(o, G * 4);
+  l.preds = ssc_ws_take(o, (size_t)d->max_steps * G * 8);
+  l.backs = ssc_ws_take(o, (size_t)std::max(d->max_steps - 1, 1) * G * 8);
+  l.parent0 = ssc_ws_take(o, G * 8);
+  for (int g = 0; g < 2; ++g) l.lp[g] = ssc_ws_take(o, G * 4);
+  for (int g = 0; g < 2; ++g) l.gs[g] = ssc_ws_take(o, gumbel ? G * 4 : 0);
+  l.sval = ssc_ws_take(o, B * d->S * SB * per_row * 4 * (gumbel ? 2 : 1));
+  l.sidx = ssc_ws_take(o, B * d->S * SB * per_row * 8);
+  l.alpha = ssc_ws_take(o, G * (size_t)d->R * 4);
   const bool parts = search_uses_parts(cfg, d, kind);
-  l.logits = o; o += a256((parts ? B : G) * (size_t)cfg->V * 4);
-  l.parts = o; o += a256(parts ? G * (size_t)ssc_cdiv(cfg->V, 128) * 6 * 4 : 0);
+  l.logits = ssc_ws_take(o, (parts ? B : G) * (size_t)cfg->V * 4);
+  l.parts = ssc_ws_take(o, parts ? G * (size_t)ssc_cdiv(cfg->V, 128) * 6 * 4 : 0);
   l.stepws_bytes = ssc_decode_step_workspace_bytes(cfg, (int)G, d->R);
-  l.stepws = o; o += a256(l.stepws_bytes);
+  l.stepws = ssc_ws_take(o, l.stepws_bytes);
   l.total = o;
   return l;
 }
 
+// the extents a search's workspace size depends on
+bool search_dims_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  return ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0) && d->S > 0 && d->beam > 0 && d->per_node > 0;
+}
+
 bool desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!cfg || !d) return false;
-  if (d->nimg <= 0 || d->R <= 0 || d->n_samples <= 0 || d->S <= 0 || d->S > 32 || d->beam <= 0 || d->per_node <= 0 ||
-      d->max_steps <= 0 || d->end_index < 0 || d->end_index >= cfg->V)
-    return false;
+  if (!search_dims_ok(cfg, d) || d->S > 32) return false;
   const long G = (long)d->nimg * d->n_samples * d->S * d->beam;
   if (G <= 0 || G > (1L << 24)) return false;
-  if (!d->feats || !d->imgbuf || !d->eps0 || (d->max_steps > 1 && !d->eps) || !d->predictions || !d->log_probs || !d->ctl) return false;
+  if (!ssc_decode_inputs_ok(cfg, d, d->max_steps) || !d->predictions || !d->log_probs || !d->ctl) return false;
   if (d->S > 1 && !d->fsm) return false;
   if (d->skip_dead && !d->tables && (d->S != 1 || d->fsm)) return false;   // (the one-state machine has no fill-only rows: skip_dead then only leaves ENDED beams out of the steps)
-  if (cfg->kld_mode == 2 ? !d->obj_atts : ((cfg->S || cfg->pm_scale != 0.f) && !d->sentiment)) return false;
   return true;
 }
 
@@ -114,10 +108,17 @@ __global__ void expand_rows_kernel(const float* __restrict__ src, int Wd, int re
 
 }  // namespace
 
+int ssc_decode_start(int* ctl, int max_steps, int64_t* tokens0, int B, int end_index, hipStream_t st) {
+  const int nctl = 2 + 2 * max_steps;
+  SSC_LAUNCH(ctl_init_kernel, dim3(ssc_cdiv(nctl, 256)), dim3(256), 0, st, ctl, nctl, max_steps);
+  SSC_CHECK_LAUNCH();
+  SSC_LAUNCH(fill_i64_kernel, dim3(ssc_cdiv(B, 256)), dim3(256), 0, st, tokens0, (size_t)B, (int64_t)end_index);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
 extern "C" size_t ssc_decode_search_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
-      d->R <= 0)
-    return 0;
+  if (!search_dims_ok(cfg, d)) return 0;
   return search_layout(cfg, d, SEARCH_BEAM).total;
 }
 
@@ -158,9 +159,7 @@ template <class Select>
 int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const SearchLayout& l, char* W,
                const Select& sel, bool use_parts, hipStream_t st) {
   const int B = d->nimg * d->n_samples, S = d->S, beam = d->beam, SB = S * beam, G = B * SB, H = cfg->H, V = cfg->V, Z = cfg->Z;
-  float* stt[2][4];
-  for (int g = 0; g < 2; ++g)
-    for (int k = 0; k < 4; ++k) stt[g][k] = (float*)(W + l.st[g][k]);
+  const SscStepStates& states = l.states;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
   float* sent_rows = (float*)(W + l.sent_rows);
   int64_t* preds = (int64_t*)(W + l.preds);
@@ -170,28 +169,20 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   float* alpha = (float*)(W + l.alpha);
   float* logits = (float*)(W + l.logits);
   const size_t plane = (size_t)G;
-  const int nctl = 2 + 2 * d->max_steps;
 
-  SSC_LAUNCH(ctl_init_kernel, dim3(ssc_cdiv(nctl, 256)), dim3(256), 0, st, d->ctl, nctl, d->max_steps);
-  SSC_CHECK_LAUNCH();
-  SSC_LAUNCH(fill_i64_kernel, dim3(ssc_cdiv(B, 256)), dim3(256), 0, st, tokens0, (size_t)B, (int64_t)d->end_index);
-  SSC_CHECK_LAUNCH();
+  SSC_TRY(ssc_decode_start(d->ctl, d->max_steps, tokens0, B, d->end_index, st));
   if (hipMemsetAsync(parent0, 0, (size_t)G * 8, st) != hipSuccess) return SSC_EHIP;
-  for (int k = 0; k < 4; ++k)   // zero start states (cbs.py: start_state None -> updown_cell.py:131-141)
-    if (hipMemsetAsync(stt[1][k], 0, (size_t)B * H * 4, st) != hipSuccess) return SSC_EHIP;
+  SSC_TRY(states.zero(W, 1, B, st));
 
-  // which form the steps take is decided once, from the extents (the decisions DecodeEngine.step makes per call)
-  auto table_mode = [&](int rows, int rpi) { return (d->R <= 128 && rows >= 512 && rpi >= 16 && ssc_decode_att_table_enabled()) ? 1 : 0; };
-  bool table_ready = false;
+  // which form the steps take is decided once per extent: the first step's B rows and the later steps' G rows each ask
+  SscAttTable table;
   ssc_decode_step_desc sd{};
   sd.R = d->R; sd.feats = d->feats; sd.imgbuf = d->imgbuf; sd.alpha = alpha; sd.log_probs = logits; sd.raw_logits = 1;
   sd.obj_atts = d->obj_atts;
   // ---- first step: one row per batch entry (cbs.py:127) ------------------------------------------------------------------
   sd.G = B; sd.rows_per_image = d->n_samples; sd.tokens = tokens0; sd.sentiment = d->sentiment; sd.eps = d->eps0;
-  sd.h1 = stt[1][0]; sd.c1 = stt[1][1]; sd.hd = stt[1][2]; sd.cd = stt[1][3];
-  sd.h1_out = stt[0][0]; sd.c1_out = stt[0][1]; sd.hd_out = stt[0][2]; sd.cd_out = stt[0][3];
-  sd.att_table = table_mode(B, d->n_samples) ? 2 : 0;
-  table_ready = sd.att_table != 0;
+  states.bind(W, 1, &sd);
+  sd.att_table = table.next(ssc_att_table_wanted(d->R, B, d->n_samples));
   SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
   ssc_beam_desc bd{};
   bd.scores = logits; bd.ld = V; bd.raw_logits = 1;
@@ -206,7 +197,8 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   // ---- enlarge the states to (B, S, beam) rows (cbs.py:152-155) --------------------------------------------------------------
   if (d->max_steps > 1) {
     for (int k = 0; k < 4; ++k) {
-      SSC_LAUNCH(expand_rows_kernel, dim3(ssc_cdiv(H, 256), G), dim3(256), 0, st, stt[0][k], H, SB, (size_t)G, stt[1][k]);
+      SSC_LAUNCH(expand_rows_kernel, dim3(ssc_cdiv(H, 256), G), dim3(256), 0, st, states.state(W, 0, k), H, SB, (size_t)G,
+                 states.state(W, 1, k));
       SSC_CHECK_LAUNCH();
     }
     if (d->sentiment) {
@@ -216,48 +208,21 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   }
   int cur = 1, a = 0;
   const int rpi = d->n_samples * SB;
-  const int tmode = table_mode(G, rpi);
+  const bool tmode = ssc_att_table_wanted(d->R, G, rpi);
   const bool ung = SB > 1 && ssc_decode_ungathered_ok(cfg, d->nimg, G, SB, tmode) != 0;
   bool ungathered = false;
   sd.G = G; sd.rows_per_image = rpi; sd.sentiment = d->sentiment ? sent_rows : nullptr; sd.group = SB;
   bd.skip_dead = d->skip_dead && d->tables ? 1 : 0;
-  // Early stop and the host's run-ahead.  The host queues a step in a fraction of the time the device needs for it, so a host that
-  // only polls the flag has long queued every step by the time the device writes it (measured: captions that all end at step 2 still
-  // cost all 20 steps).  The run-ahead is therefore bounded: step t is queued only once step t - RUN_AHEAD has completed - the last
-  // workgroup of a step's merge kernel notes the step in the second pinned word (ssc_beam_desc.host_flag[1]) and the host reads it;
-  // no event, no synchronisation call (an event per step cost 1.7 % of a search that never stops).  The device always has RUN_AHEAD
-  // steps of work queued, and at most that many surplus steps run.  Not under stream capture (a captured search queues every step).
-  constexpr int RUN_AHEAD = 2;
-  bool bounded = false;
-  if (d->early_stop && d->host_flag_host) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusNone; }
-    bounded = cs == hipStreamCaptureStatusNone;
-  }
-  auto wait_for_step = [&](int step) {   // until the device has completed `step` (or stopped, or the stream has drained: an error upstream)
-    const volatile int* hf = (const volatile int*)d->host_flag_host;
-    for (unsigned spin = 1; hf[1] < step && hf[0] == 0; ++spin) {
-      if ((spin & 1023u) == 0 && hipStreamQuery(st) != hipErrorNotReady) { (void)hipGetLastError(); break; }
-      std::this_thread::yield();
-    }
-  };
+  const SscStepPacer pacer(d->early_stop, d->host_flag_host, st);
   for (int t = 1; t < d->max_steps; ++t) {
-    // cbs.py:167: the device notes the step after which every beam had ended and turns later steps into no-ops (ssc_beam_desc.ctl);
-    // the host stops QUEUEING once it sees the flag the device wrote - a plain read of pinned memory
-    if (bounded && t > RUN_AHEAD) wait_for_step(t - RUN_AHEAD);
-    if (d->early_stop && d->host_flag_host && *(volatile const int*)d->host_flag_host != 0) break;
+    if (pacer.stop_before(t)) break;   // cbs.py:167
     const int64_t* last = preds + (size_t)(t - 1) * plane;
     sd.tokens = last; sd.eps = d->eps + (size_t)(t - 1) * G * Z;
-    sd.h1 = stt[cur][0]; sd.c1 = stt[cur][1]; sd.hd = stt[cur][2]; sd.cd = stt[cur][3];
-    sd.h1_out = stt[1 - cur][0]; sd.c1_out = stt[1 - cur][1]; sd.hd_out = stt[1 - cur][2]; sd.cd_out = stt[1 - cur][3];
+    states.bind(W, cur, &sd);
+    states.bind_planes(W, cur, ungathered, &sd);
     sd.parent = t == 1 ? parent0 : backs + (size_t)(t - 2) * plane;
-    sd.att_table = tmode ? (table_ready ? 1 : 2) : 0;
-    table_ready = table_ready || tmode;
+    sd.att_table = table.next(tmode);
     sd.ungathered = ungathered ? 1 : 0;
-    if (l.pl[1][0] != l.pl[0][0]) {   // the states' fp16 pieces travel with the un-gathered states (a re-ordered state is split again by its step)
-      sd.h1_planes_out = W + l.pl[1 - cur][0]; sd.hd_planes_out = W + l.pl[1 - cur][1];
-      sd.h1_planes = ungathered ? W + l.pl[cur][0] : nullptr; sd.hd_planes = ungathered ? W + l.pl[cur][1] : nullptr;
-    }
     sd.row_lp = d->skip_dead ? lp[a] : nullptr; sd.end_index = d->end_index;
     if (use_parts) { sd.log_probs = nullptr; sd.topk_part = (float*)(W + l.parts); }
     SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
@@ -270,7 +235,7 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
       ungathered = true;
     } else {     // cbs.py:236-250: re-order the states by back-pointer (into the generation the step has just consumed)
       for (int k = 0; k < 4; ++k)
-        SSC_TRY(ssc_gather_rows(stt[1 - cur][k], H, bd.backptr, B, SB, H, stt[cur][k], st));
+        SSC_TRY(ssc_gather_rows(states.state(W, 1 - cur, k), H, bd.backptr, B, SB, H, states.state(W, cur, k), st));
     }
   }
   if (d->early_stop) {
@@ -304,9 +269,7 @@ static bool sbs_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, co
 }
 
 extern "C" size_t ssc_decode_stochastic_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
-      d->R <= 0)
-    return 0;
+  if (!search_dims_ok(cfg, d)) return 0;
   return search_layout(cfg, d, SEARCH_GUMBEL).total;
 }
 
@@ -328,9 +291,7 @@ static bool snb_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, co
 }
 
 extern "C" size_t ssc_decode_sampled_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!cfg || !d || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
-      d->R <= 0)
-    return 0;
+  if (!search_dims_ok(cfg, d)) return 0;
   return search_layout(cfg, d, SEARCH_SAMPLED).total;
 }
 
@@ -353,9 +314,7 @@ static bool dbs_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, co
 
 extern "C" size_t ssc_decode_diverse_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
                                                           const ssc_diverse_desc* s) {
-  if (!cfg || !d || !s || d->nimg <= 0 || d->n_samples <= 0 || d->S <= 0 || d->beam <= 0 || d->per_node <= 0 || d->max_steps <= 0 ||
-      d->R <= 0 || s->groups < 1 || d->beam % s->groups != 0)
-    return 0;
+  if (!search_dims_ok(cfg, d) || !s || s->groups < 1 || d->beam % s->groups != 0) return 0;
   return search_layout(cfg, d, SEARCH_DIVERSE, ssc_diverse_beam_list(d->beam, s->groups, d->per_node, cfg->V)).total;
 }
 

@@ -120,6 +120,9 @@ int ssc_beam_merge(const float* sval, const int64_t* sidx, const float* last_lp,
                    int64_t* pred, float* lp_out, int64_t* backptr, int end_index, int* ctl, int step_index, int max_steps,
                    int* host_flag, hipStream_t st);
 int ssc_decode_att_table_enabled();   // the "dec_att_table" switch (decode.hip)
+// the start of a one-call decode with the early-stop protocol (search.hip): ctl[0] = max_steps, the counters behind it zero;
+// tokens0 (B) = end_index, the token the first step feeds
+int ssc_decode_start(int* ctl, int max_steps, int64_t* tokens0, int B, int end_index, hipStream_t st);
 
 // numerics mode of the calling thread's current sequence-level call (ssc_model_cfg.gemm_mode: 0 = the process default set by
 // ssc_set_gemm_mode, 1 = 3xBF16, 2 = exact-fp32 MFMA); -1 = none in force

@@ -50,7 +50,7 @@ class DecodeEngine:
         # Default off: the drop-in module's eval calls may be interleaved with training steps.
         self.weights_frozen = False
         self._last_ctx = None
-        self._sws = None   # workspace of search()
+        self._sws = None   # workspace of the one-call decodes
 
     def prepare(self, feats: torch.Tensor, obj_means: Optional[torch.Tensor] = None) -> ImageContext:
         """obj_means (nimg, R, Z): the per-region attribute means of SENTIMENT_VAE = 2 (kld_mode 2), else None."""
@@ -82,8 +82,11 @@ class DecodeEngine:
     ATT_TABLE_MIN_ROWS = 512
     ATT_TABLE_MIN_ROWS_PER_IMAGE = 16
 
+    def _att_table_fits(self, ctx: "ImageContext", G: int, rpi: int) -> bool:
+        return ctx.R <= 128 and G >= self.ATT_TABLE_MIN_ROWS and rpi >= self.ATT_TABLE_MIN_ROWS_PER_IMAGE
+
     def _att_table_mode(self, ctx: "ImageContext", G: int, rpi: int) -> int:
-        if ctx.R > 128 or G < self.ATT_TABLE_MIN_ROWS or rpi < self.ATT_TABLE_MIN_ROWS_PER_IMAGE:
+        if not self._att_table_fits(ctx, G, rpi):
             return 0
         on = C.c_int(1)   # ssc_debug_set("dec_att_table", 0): A/B switch of include/ssc_debug.h
         if self.lib._raw_ssc_debug_get(b"dec_att_table", C.byref(on)) != 0 or not on.value:
@@ -173,9 +176,65 @@ class DecodeEngine:
         if G % ctx.nimg != 0:
             return False
         # (same decision as step(): the table must be in use; it has been formed by the time a search re-orders beams)
-        att = 0 if (ctx.R > 128 or G < self.ATT_TABLE_MIN_ROWS or G // ctx.nimg < self.ATT_TABLE_MIN_ROWS_PER_IMAGE) else 1
+        att = 1 if self._att_table_fits(ctx, G, G // ctx.nimg) else 0
         return bool(self.lib._raw_ssc_decode_ungathered_ok(C.byref(self._cfg), ctx.nimg, G, group, att))
 
+
+    def _noise(self, sentiment, eps0, eps, first_rows: int, rows: int, steps: int):
+        """The caller's sentiment (first_rows), eps0 (first_rows, Z) and eps (steps - 1, rows, Z) as contiguous float32 on the device,
+        shape-checked; eps is None for a one-step call."""
+        dev, Z = self.device, self.dims.Z
+        sent = sentiment.reshape(first_rows).to(dev, torch.float32).contiguous() if sentiment is not None else None
+        eps0 = eps0.to(dev, torch.float32).contiguous()
+        assert tuple(eps0.shape) == (first_rows, Z), (eps0.shape, (first_rows, Z))
+        if steps <= 1:
+            return sent, eps0, None
+        eps = eps.to(dev, torch.float32).contiguous()
+        assert tuple(eps.shape) == (steps - 1, rows, Z), (eps.shape, (steps - 1, rows, Z))
+        return sent, eps0, eps
+
+    def _workspace(self, nbytes: int):
+        """-> (workspace, bytes, stream): the trailing arguments of a one-call decode; the workspace only ever grows."""
+        if self._sws is None or self._sws.numel() < nbytes:
+            self._sws = None   # (release before growing)
+            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        return _lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr()
+
+    def _one_call(self, ctx, sentiment, n_samples, S, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                  out_shape, workspace_bytes, call, machine=None):
+        """The shared body of the one-call decodes over a search descriptor: B = ctx.nimg * n_samples batch entries of S * beam
+        rows.  Fills the descriptor (machine(desc) adds a search's machine fields), checks the noise, allocates the outputs -
+        predictions out_shape + (max_steps,), log-probs out_shape -, takes the pinned early-stop flag, sizes the workspace with
+        workspace_bytes(cfg, desc) and issues call(params, desc, (workspace, bytes, stream)).
+        -> (predictions cut to the executed steps, log_probs); one wait at the end, for the number of steps."""
+        B = ctx.nimg * n_samples
+        dev = self.device
+        sd = _lib.SearchDesc()
+        sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
+        sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = S, beam, per_node, max_steps, end_index
+        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
+        sent, eps0, eps = self._noise(sentiment, eps0, eps, B, B * S * beam, max_steps)
+        sd.sentiment, sd.eps0, sd.eps = _lib.ptr(sent), _lib.ptr(eps0), _lib.ptr(eps)
+        sd.obj_atts = _lib.ptr(ctx.obj)
+        if machine is not None:
+            machine(sd)
+        sd.skip_dead = 1 if skip_dead else 0
+        sd.early_stop = 1 if early_stop else 0
+        pred = torch.empty(*out_shape, max_steps, dtype=torch.int64, device=dev)
+        lps = torch.empty(*out_shape, dtype=torch.float32, device=dev)
+        ctl = torch.empty(2 + 2 * max_steps, dtype=torch.int32, device=dev)
+        sd.predictions, sd.log_probs, sd.ctl = _lib.ptr(pred), _lib.ptr(lps), _lib.ptr(ctl)
+        flag = None
+        if early_stop:
+            flag, flag_dev = _host_flag()
+            if flag_dev is not None:
+                sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
+        ws = self._workspace(workspace_bytes(C.byref(self._cfg), C.byref(sd)))
+        call(self._params(), sd, ws)
+        nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call: its result is about to be read anyway)
+        if flag is not None:
+            _HOST_FLAGS.append(flag)
+        return pred[..., :nsteps].contiguous(), lps
 
     def search(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int, max_steps: int,
                end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
@@ -185,56 +244,29 @@ class DecodeEngine:
         latent samples, batch entry b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*S*beam, Z):
         the noise of every step, drawn by the caller.  fsm (M,S,S,V) / compiled / mach as in cbs_search.
         -> (predictions (B, S, beam, steps), log_probs (B, S, beam)); one wait at the end, for the number of steps."""
-        d = self.dims
         B = ctx.nimg * n_samples
         S = 1 if fsm is None else fsm.size(1)
-        G = B * S * beam
-        dev = self.device
         if fsm is not None:
             assert fsm.is_cuda and fsm.dtype == torch.uint8 and fsm.is_contiguous()
             assert mach is not None or fsm.size(0) == B
-        sd = _lib.SearchDesc()
-        sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
-        sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = S, beam, per_node, max_steps, end_index
-        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
-        sent = sentiment.reshape(B).to(dev, torch.float32).contiguous() if sentiment is not None else None
-        eps0 = eps0.to(dev, torch.float32).contiguous()
-        assert tuple(eps0.shape) == (B, d.Z), eps0.shape
-        if max_steps > 1:
-            eps = eps.to(dev, torch.float32).contiguous()
-            assert tuple(eps.shape) == (max_steps - 1, G, d.Z), (eps.shape, (max_steps - 1, G, d.Z))
-        sd.sentiment, sd.eps0, sd.eps = _lib.ptr(sent), _lib.ptr(eps0), _lib.ptr(eps) if max_steps > 1 else None
-        sd.obj_atts = _lib.ptr(ctx.obj)
         if mach is not None:   # one machine index per BATCH ENTRY (image, sample); the kernels index the machines with it unchecked
             assert fsm is not None and mach.numel() == B, (mach.shape, B)
             lo, hi = int(mach.min()), int(mach.max())
             assert 0 <= lo and hi < fsm.size(0), (lo, hi, fsm.size(0))
-        mach = mach.to(dev, torch.int32).contiguous() if mach is not None else None
-        sd.fsm, sd.mach = _lib.ptr(fsm), _lib.ptr(mach)
+            mach = mach.to(self.device, torch.int32).contiguous()
         if compiled is not None:
             assert compiled.dims.S == S and compiled.dims.P >= per_node
-            sd.tables, sd.dims = _lib.ptr(compiled.tables), compiled.dims
-        sd.skip_dead = 1 if (skip_dead and (compiled is not None or fsm is None)) else 0
-        sd.early_stop = 1 if early_stop else 0
-        pred = torch.empty(B, S * beam, max_steps, dtype=torch.int64, device=dev)
-        lps = torch.empty(B, S, beam, dtype=torch.float32, device=dev)
-        ctl = torch.empty(2 + 2 * max_steps, dtype=torch.int32, device=dev)
-        sd.predictions, sd.log_probs, sd.ctl = _lib.ptr(pred), _lib.ptr(lps), _lib.ptr(ctl)
-        flag = None
-        if early_stop:
-            flag, flag_dev = _host_flag()
-            if flag_dev is not None:
-                sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
-        nbytes = self.lib.ssc_decode_search_workspace_bytes(C.byref(self._cfg), C.byref(sd))
-        if self._sws is None or self._sws.numel() < nbytes:
-            self._sws = None   # (release before growing)
-            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        p = self._params()
-        self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), _lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr())
-        nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call: its result is about to be read anyway)
-        if flag is not None:
-            _HOST_FLAGS.append(flag)
-        return pred[:, :, :nsteps].contiguous().view(B, S, beam, nsteps), lps
+
+        def machine(sd):
+            sd.fsm, sd.mach = _lib.ptr(fsm), _lib.ptr(mach)
+            if compiled is not None:
+                sd.tables, sd.dims = _lib.ptr(compiled.tables), compiled.dims
+
+        return self._one_call(ctx, sentiment, n_samples, S, beam, per_node, max_steps, end_index, eps0, eps, early_stop,
+                              skip_dead and (compiled is not None or fsm is None), (B, S, beam),
+                              self.lib.ssc_decode_search_workspace_bytes,
+                              lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws),
+                              machine)
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True):
@@ -242,45 +274,13 @@ class DecodeEngine:
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
         -> (predictions (B, steps) int64, log_probs (B,): each caption's summed untempered log-prob)."""
-        d = self.dims
-        B = ctx.nimg * n_samples
-        dev = self.device
-        sampler.check_vocab(d.V)
-        sd = _lib.SearchDesc()
-        sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
-        sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = 1, 1, 1, max_steps, end_index
-        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
-        sent = sentiment.reshape(B).to(dev, torch.float32).contiguous() if sentiment is not None else None
-        eps0 = eps0.to(dev, torch.float32).contiguous()
-        assert tuple(eps0.shape) == (B, d.Z), eps0.shape
-        if max_steps > 1:
-            eps = eps.to(dev, torch.float32).contiguous()
-            assert tuple(eps.shape) == (max_steps - 1, B, d.Z), (eps.shape, (max_steps - 1, B, d.Z))
-        sd.sentiment, sd.eps0, sd.eps = _lib.ptr(sent), _lib.ptr(eps0), _lib.ptr(eps) if max_steps > 1 else None
-        sd.obj_atts = _lib.ptr(ctx.obj)
-        sd.skip_dead = 1   # ended rows are not stepped
-        sd.early_stop = 1 if early_stop else 0
-        pred = torch.empty(B, max_steps, dtype=torch.int64, device=dev)
-        lps = torch.empty(B, dtype=torch.float32, device=dev)
-        ctl = torch.empty(2 + 2 * max_steps, dtype=torch.int32, device=dev)
-        sd.predictions, sd.log_probs, sd.ctl = _lib.ptr(pred), _lib.ptr(lps), _lib.ptr(ctl)
-        flag = None
-        if early_stop:
-            flag, flag_dev = _host_flag()
-            if flag_dev is not None:
-                sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
-        nbytes = self.lib.ssc_decode_sample_workspace_bytes(C.byref(self._cfg), C.byref(sd))
-        if self._sws is None or self._sws.numel() < nbytes:
-            self._sws = None   # (release before growing)
-            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        p = self._params()
+        sampler.check_vocab(self.dims.V)
         sdesc = sampler.desc(seed)
-        self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), _lib.ptr(self._sws),
-                                   self._sws.numel(), _lib.stream_ptr())
-        nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call)
-        if flag is not None:
-            _HOST_FLAGS.append(flag)
-        return pred[:, :nsteps].contiguous(), lps
+        # skip_dead: ended rows are not stepped
+        return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, True,
+                              (ctx.nimg * n_samples,), self.lib.ssc_decode_sample_workspace_bytes,
+                              lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd),
+                                                                           C.byref(sdesc), *ws))
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
               eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False):
@@ -289,7 +289,6 @@ class DecodeEngine:
         latent samples each, row g = (image, caption, sample), G = nimg * C * n_samples.  sentiment (G) per row or None; eps0
         (G, Z), eps (L - 1, G, Z): the noise of every step.
         -> (log_probs (G,), n_tokens (nimg, C) int32, token_lp (G, L) or None, token_rank (G, L) int32 or None)."""
-        d = self.dims
         dev = self.device
         assert targets.dim() == 3 and targets.size(0) == ctx.nimg, (targets.shape, ctx.nimg)
         _, Cc, Lc = targets.shape
@@ -298,25 +297,17 @@ class DecodeEngine:
         sd = _lib.ScoreDesc()
         sd.nimg, sd.R, sd.n_captions, sd.n_samples, sd.max_len, sd.end_index = ctx.nimg, ctx.R, Cc, n_samples, Lc, end_index
         sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
-        sent = sentiment.reshape(G).to(dev, torch.float32).contiguous() if sentiment is not None else None
-        eps0 = eps0.to(dev, torch.float32).contiguous()
-        assert tuple(eps0.shape) == (G, d.Z), (eps0.shape, (G, d.Z))
-        if Lc > 1:
-            eps = eps.to(dev, torch.float32).contiguous()
-            assert tuple(eps.shape) == (Lc - 1, G, d.Z), (eps.shape, (Lc - 1, G, d.Z))
+        sent, eps0, eps = self._noise(sentiment, eps0, eps, G, G, Lc)
         sd.sentiment, sd.obj_atts, sd.targets = _lib.ptr(sent), _lib.ptr(ctx.obj), _lib.ptr(targets)
-        sd.eps0, sd.eps = _lib.ptr(eps0), _lib.ptr(eps) if Lc > 1 else None
+        sd.eps0, sd.eps = _lib.ptr(eps0), _lib.ptr(eps)
         lps = torch.empty(G, dtype=torch.float32, device=dev)
         ntok = torch.empty(ctx.nimg, Cc, dtype=torch.int32, device=dev)
         tlp = torch.empty(G, Lc, dtype=torch.float32, device=dev) if want_tokens else None
         trk = torch.empty(G, Lc, dtype=torch.int32, device=dev) if want_ranks else None
         sd.log_probs, sd.n_tokens, sd.token_lp, sd.token_rank = _lib.ptr(lps), _lib.ptr(ntok), _lib.ptr(tlp), _lib.ptr(trk)
-        nbytes = self.lib.ssc_decode_score_workspace_bytes(C.byref(self._cfg), C.byref(sd))
-        if self._sws is None or self._sws.numel() < nbytes:
-            self._sws = None   # (release before growing)
-            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        ws = self._workspace(self.lib.ssc_decode_score_workspace_bytes(C.byref(self._cfg), C.byref(sd)))
         p = self._params()
-        self.lib.ssc_decode_score(C.byref(self._cfg), C.byref(p), C.byref(sd), _lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr())
+        self.lib.ssc_decode_score(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws)
         return lps, ntok, tlp, trk
 
     def stochastic_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
@@ -330,7 +321,8 @@ class DecodeEngine:
         if not 1 <= per_node <= beam <= min(32, self.dims.V):
             raise ValueError(f"stochastic beam search needs 1 <= per_node <= beam <= min(32, V), got per_node {per_node}, beam {beam}")
         gdesc = sampler.desc(seed)
-        return self._beam_call(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+        return self._one_call(ctx, sentiment, n_samples, 1, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                              (ctx.nimg * n_samples, beam),
                                self.lib.ssc_decode_stochastic_beam_workspace_bytes,
                                lambda p, sd, ws: self.lib.ssc_decode_stochastic_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                      C.byref(gdesc), *ws))
@@ -354,7 +346,8 @@ class DecodeEngine:
             raise ValueError("k must be a postive integer no less than per_node_beam_size and no greater than vocabulary size")
         sdesc = sampler.desc(seed)
         rep = 1 if sampler.with_replacement else 0
-        return self._beam_call(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+        return self._one_call(ctx, sentiment, n_samples, 1, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                              (ctx.nimg * n_samples, beam),
                                self.lib.ssc_decode_sampled_beam_workspace_bytes,
                                lambda p, sd, ws: self.lib.ssc_decode_sampled_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                   C.byref(sdesc), rep, *ws))
@@ -373,52 +366,11 @@ class DecodeEngine:
             raise ValueError(f"diverse beam search needs 1 <= beam, per_node <= min(32, V), got beam {beam}, per_node {per_node}")
         diverse.check_beam(beam)
         ddesc = diverse.desc()
-        return self._beam_call(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+        return self._one_call(ctx, sentiment, n_samples, 1, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                              (ctx.nimg * n_samples, beam),
                                lambda cfg, sd: self.lib.ssc_decode_diverse_beam_workspace_bytes(cfg, sd, C.byref(ddesc)),
                                lambda p, sd, ws: self.lib.ssc_decode_diverse_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                   C.byref(ddesc), *ws))
-
-    def _beam_call(self, ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
-                   workspace_bytes, call):
-        """The shared body of the one-call searches on the trivial machine: the search descriptor, outputs, host flag and
-        workspace; call(params, desc, (workspace, bytes, stream)) issues the library call."""
-        d = self.dims
-        B = ctx.nimg * n_samples
-        G = B * beam
-        dev = self.device
-        sd = _lib.SearchDesc()
-        sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
-        sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = 1, beam, per_node, max_steps, end_index
-        sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
-        sent = sentiment.reshape(B).to(dev, torch.float32).contiguous() if sentiment is not None else None
-        eps0 = eps0.to(dev, torch.float32).contiguous()
-        assert tuple(eps0.shape) == (B, d.Z), eps0.shape
-        if max_steps > 1:
-            eps = eps.to(dev, torch.float32).contiguous()
-            assert tuple(eps.shape) == (max_steps - 1, G, d.Z), (eps.shape, (max_steps - 1, G, d.Z))
-        sd.sentiment, sd.eps0, sd.eps = _lib.ptr(sent), _lib.ptr(eps0), _lib.ptr(eps) if max_steps > 1 else None
-        sd.obj_atts = _lib.ptr(ctx.obj)
-        sd.skip_dead = 1 if skip_dead else 0   # ended beams are not stepped
-        sd.early_stop = 1 if early_stop else 0
-        pred = torch.empty(B, beam, max_steps, dtype=torch.int64, device=dev)
-        lps = torch.empty(B, beam, dtype=torch.float32, device=dev)
-        ctl = torch.empty(2 + 2 * max_steps, dtype=torch.int32, device=dev)
-        sd.predictions, sd.log_probs, sd.ctl = _lib.ptr(pred), _lib.ptr(lps), _lib.ptr(ctl)
-        flag = None
-        if early_stop:
-            flag, flag_dev = _host_flag()
-            if flag_dev is not None:
-                sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
-        nbytes = workspace_bytes(C.byref(self._cfg), C.byref(sd))
-        if self._sws is None or self._sws.numel() < nbytes:
-            self._sws = None   # (release before growing)
-            self._sws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        p = self._params()
-        call(p, sd, (_lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr()))
-        nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call)
-        if flag is not None:
-            _HOST_FLAGS.append(flag)
-        return pred[:, :, :nsteps].contiguous(), lps
 
     def _step_from_embedding(self, ctx, token_embedding, states, sentiment, eps, prior_mean_out=None, prior_mean=None, prior_var=None):
         G = token_embedding.size(0)

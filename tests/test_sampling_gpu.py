@@ -171,13 +171,14 @@ def inputs(cfg, nimg, ns, R, seed, steps=None):
     return feats, senti, eps0, eps
 
 
-@pytest.mark.parametrize("full", [False, True])
+@pytest.mark.parametrize("full", [False, True, "table"])
 def test_top1_sampling_equals_beam1_search(full):
     """TopKSampler(k=1) through ssc_decode_sample draws the argmax: the beam-1 search's captions (the steps are formed alike, so
     the logits are the same) and its caption log-probs within 1e-5 (+ one fp32 ulp of the sum).  Toy width and full width (H 1200, V 10 000, R 36, 8 images x
-    20 samples)."""
-    cfg, _, _, dec = model(full)
-    nimg, ns, R = (8, 20, 36) if full else (3, 4, 7)
+    20 samples); "table": toy width at 2 images x 256 samples - 512 rows, 256 per image, the smallest extents at which both calls
+    take the attended-feature-table form (formed by the call's first step, read by the later ones through the parent list)."""
+    cfg, _, _, dec = model(full is True)
+    nimg, ns, R = {False: (3, 4, 7), True: (8, 20, 36), "table": (2, 256, 7)}[full]
     L_ = cfg.max_caption_length
     feats, senti, eps0, eps = inputs(cfg, nimg, ns, R, seed=17)
     B = nimg * ns
