@@ -348,6 +348,27 @@ int ssc_sq_norm(const float* g, size_t n, float* scratch, float* out, void* stre
 int ssc_sgd_step(float* p, const float* g, float* buf, size_t n, const float* sqnorm, float gscale, float max_norm,
                  float lr, float momentum, float weight_decay, int first, void* stream);
 
+/* clip_grad_norm_ + torch.optim.Adam / AdamW (amsgrad = False, maximize = False) on flat buffers: update number `step` >= 1 of
+ * these n elements, m / v their first / second moment.  Per element, in fp32 and in this order (no fused multiply-add):
+ *   coef = min(1, max_norm / (sqrt(*sqnorm) * gscale + 1e-6)) * gscale            (as ssc_sgd_step)
+ *   d = g * coef
+ *   decoupled = 0 (Adam, L2 folded into the gradient):  d = d + weight_decay * p
+ *   decoupled = 1 (AdamW):                              p = p * (1 - lr * weight_decay)     (before anything else)
+ *   m = beta1 * m + (1 - beta1) * d
+ *   v = beta2 * v + ((1 - beta2) * d) * d
+ *   p = p - (lr / bc1) * (m / (sqrt(v) * (1 / sqrt(bc2)) + eps)),     bc1 = 1 - beta1^step, bc2 = 1 - beta2^step
+ * The host forms 1 - beta1, 1 - beta2, 1 - lr * weight_decay, lr / bc1 and 1 / sqrt(bc2) in double and hands them to the kernel
+ * rounded to float; sqrt and the division are the IEEE-rounded ones.  Elements with p = g = m = v = 0 (the padding columns of
+ * a flat parameter layout) stay exactly 0.
+ * One grid-stride stream over 16-byte loads and stores (reads p, g, m, v, writes p, m, v: 7 words per element).  Slices whose
+ * start is not 16-byte aligned are fine as long as the four pointers share one misalignment: a scalar head up to the first
+ * aligned element, the 16-byte bulk, a scalar tail; pointers that do not share it take the scalar path throughout.  No atomics:
+ * two calls on the same inputs are bit-identical.
+ * SSC_EINVAL and no launch: a NULL pointer, step < 1, a beta outside [0, 1), eps <= 0, lr < 0 or weight_decay < 0 (NaNs
+ * included); SSC_EALIGN: a pointer that is no multiple of 4.  n = 0: nothing to do, SSC_OK. */
+int ssc_adam_step(float* p, const float* g, float* m, float* v, size_t n, const float* sqnorm, float gscale, float max_norm,
+                  float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled, int step, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Model / sequence level: the T-step teacher-forced training forward and its BPTT
  * (UpDownCaptioner.forward training branch, updown_captioner.py:228-323; _decode_step :371-455;

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Train a Style-SeqCVAE captioner on MI355X - counterpart of the reference's var_updown/scripts/train.py:26-188 with
-the same flags, config keys, seeds, optimiser (SGD momentum/weight-decay, LambdaLR linear decay), decoder-LSTM freeze
+the same flags, config keys, seeds, optimiser (SGD momentum/weight-decay, LambdaLR linear decay; OPTIM.OPTIMIZER adam / adamw:
+Adam or AdamW behind the same clip and decay, on all three paths), decoder-LSTM freeze
 schedule, clip_grad_norm, scalar names and checkpoint layout ({"model": state_dict, "optimizer": ...}).
 
 One process per GPU: `python scripts/train.py --config cfg.yaml --gpu-ids 0` or, for N GPUs,
@@ -55,7 +56,12 @@ parser.add_argument("--attribute-table", default="",
                     help="SENTIMENT_VAE 2: json {attribute word: [Z_SPACE floats]} - the table the reference builds from its sentiment-GloVe / "
                          "SentiWordNet files (updown_captioner.py:79-93); only needed when obj_atts arrive as attribute strings")
 parser.add_argument("--fused-optimizer", action="store_true",
-                    help="clip + SGD in one HIP pass on the flat buffers instead of torch.optim.SGD")
+                    help="clip + SGD (OPTIM.OPTIMIZER adam / adamw: clip + Adam / AdamW) in one HIP pass on the flat buffers instead of "
+                         "torch.optim")
+# (absent from the namespace unless given: the namespace of a command line without it is what it was before the flag existed)
+parser.add_argument("--reset-optimizer", action="store_true", default=argparse.SUPPRESS,
+                    help="with --start-from-checkpoint: load the model only, drop the checkpoint's optimiser state and start at "
+                         "iteration 1 (the hand-over from cross-entropy training under SGD to self-critical training under Adam)")
 parser.add_argument("--scst-references", default="",
                     help="train with self-critical steps (ssc_runtime/scst.py) instead of cross-entropy ones: sampled captions rewarded "
                          'against these references - COCO annotations {"annotations": [{"image_id", "caption"}]} or {image_id: [captions]}, '
@@ -179,8 +185,16 @@ def main():
     model.eps_source = _A.eps_source
     model.train()
     eng = model._engine()
-    optimizer = torch.optim.SGD(model.parameters(), lr=_C.OPTIM.LR, momentum=_C.OPTIM.MOMENTUM,
-                                weight_decay=_C.OPTIM.WEIGHT_DECAY)
+    from ssc_runtime.engine import OptimSpec, check_optimizer_state_kind
+    kind = _C.OPTIM.OPTIMIZER
+    spec = None   # the fused paths' optimiser; None: SGD with OPTIM.MOMENTUM / WEIGHT_DECAY, as before the key existed
+    if kind == "sgd":
+        optimizer = torch.optim.SGD(model.parameters(), lr=_C.OPTIM.LR, momentum=_C.OPTIM.MOMENTUM,
+                                    weight_decay=_C.OPTIM.WEIGHT_DECAY)
+    else:
+        spec = OptimSpec(kind=kind, betas=tuple(_C.OPTIM.ADAM_BETAS), eps=_C.OPTIM.ADAM_EPS)
+        optimizer = (torch.optim.AdamW if kind == "adamw" else torch.optim.Adam)(
+            model.parameters(), lr=_C.OPTIM.LR, betas=spec.betas, eps=spec.eps, weight_decay=_C.OPTIM.WEIGHT_DECAY)
     # Learning rate: the reference's LambdaLR(1 - it / NUM_ITERATIONS) stepped once per iteration (train.py:132-134,176) gives
     # iteration i the rate LR * (1 - (i - 1) / N).  It is computed from the iteration number on BOTH paths, so a resumed run
     # continues the decay where it stopped (a fresh LambdaLR would restart at LR).
@@ -188,16 +202,20 @@ def main():
     named = list(model.named_parameters())
     start_iteration = 1
     if _A.start_from_checkpoint:
-        # Layout {"model": state_dict, "optimizer": SGD state_dict} as written by the reference's CheckpointManager
+        # Layout {"model": state_dict, "optimizer": SGD (or Adam / AdamW) state_dict} as written by the reference's CheckpointManager
         # (updown-baseline/updown/utils/checkpointing.py:81-112); the iteration rides inside the optimizer entry
         # (the reference's train.py:143-149 loads every other top-level key into the model).
         ckpt = torch.load(_A.start_from_checkpoint, map_location=device, weights_only=True)
         model.load_state_dict(ckpt["model"])
-        osd = ckpt.get("optimizer")
+        osd = None if getattr(_A, "reset_optimizer", False) else ckpt.get("optimizer")
         if osd is not None:
+            check_optimizer_state_kind(osd, kind)   # SGD state under an Adam kind (or the reverse): stop, naming both
             if _A.fused_optimizer or _A.scst_references:
-                eng.load_optimizer_state_dict(named, osd)
+                eng.load_optimizer_state_dict(named, osd, spec)
             else:
+                for st in osd["state"].values():   # torch.optim.Adam keeps its step counts on the host
+                    if "step" in st:
+                        st["step"] = st["step"].cpu()
                 optimizer.load_state_dict({"state": osd["state"], "param_groups": osd["param_groups"]})
             start_iteration = int(osd.get("iteration", 0)) + 1   # correct resume (the reference restarts at 1: train.py:149)
     # batch i of a run is a function of (seed, i): a resumed run continues the data order where it stopped
@@ -231,7 +249,7 @@ def main():
                                                   kld_weight=_C.MODEL.KLD_WEIGHT, momentum=_C.OPTIM.MOMENTUM,
                                                   weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
                                                   decoder_frozen=not train_decoder, seed=scst_seed(_C.RANDOM_SEED, iteration, rank),
-                                                  obj_atts=batch.get("obj_atts"))
+                                                  obj_atts=batch.get("obj_atts"), optim=spec)
             reconstr_loss, kld_loss = loss_b.mean(), kld_b.mean()
             loss = reconstr_loss + kld_loss / _C.MODEL.KLD_WEIGHT
         elif _A.fused_optimizer:
@@ -240,7 +258,7 @@ def main():
             loss_b, kld_b = eng.train_step(batch["image_features"], batch["caption_tokens"], batch["sentiment"], eps, lr=lr,
                                            kld_weight=_C.MODEL.KLD_WEIGHT, momentum=_C.OPTIM.MOMENTUM,
                                            weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
-                                           decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"))
+                                           decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec)
             reconstr_loss, kld_loss = loss_b.mean(), kld_b.mean()
             loss = reconstr_loss + kld_loss / _C.MODEL.KLD_WEIGHT
         else:
@@ -271,7 +289,7 @@ def main():
             log.flush()
         if rank == 0 and iteration % _A.checkpoint_every == 0:
             if _A.fused_optimizer or scst is not None:
-                osd = eng.optimizer_state_dict(named, lr, _C.OPTIM.MOMENTUM, _C.OPTIM.WEIGHT_DECAY, iteration)
+                osd = eng.optimizer_state_dict(named, lr, _C.OPTIM.MOMENTUM, _C.OPTIM.WEIGHT_DECAY, iteration, spec)
             else:
                 osd = optimizer.state_dict()
                 osd["iteration"] = iteration

@@ -1294,6 +1294,62 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// clip + Adam / AdamW on flat buffers (include/ssc.h states the arithmetic; -ffp-contract=off keeps it as written)
+// ---------------------------------------------------------------------------------------------
+struct AdamArgs {
+  float step_size;   // lr / (1 - beta1^step)
+  float rsqrt_bc2;   // 1 / sqrt(1 - beta2^step)
+  float beta1, omb1, beta2, omb2, eps, wd;
+  float decay;       // 1 - lr * wd (AdamW)
+};
+
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, float coef, const AdamArgs& a) {
+  float d = g * coef;
+  if (DECOUPLED) p = p * a.decay;
+  else d = d + a.wd * p;
+  m = a.beta1 * m + a.omb1 * d;
+  v = a.beta2 * v + a.omb2 * d * d;
+  p = p - a.step_size * (m / (sqrtf(v) * a.rsqrt_bc2 + a.eps));
+}
+
+// Elements [0, head) and [head + 4 * n4, n) go one by one, the n4 groups of four in between as 16-byte loads and stores
+// (p + head is 16-byte aligned in all four buffers; head = n, n4 = 0: the scalar path throughout).
+template <bool DECOUPLED>
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            size_t n, size_t head, size_t n4, const float* __restrict__ sqnorm, float gscale, float max_norm,
+                            AdamArgs a) {
+  float norm = sqrtf(*sqnorm) * gscale;
+  float coef = fminf(1.f, max_norm / (norm + 1e-6f)) * gscale;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  float4* p4 = reinterpret_cast<float4*>(p + head);
+  const float4* g4 = reinterpret_cast<const float4*>(g + head);
+  float4* m4 = reinterpret_cast<float4*>(m + head);
+  float4* v4 = reinterpret_cast<float4*>(v + head);
+  for (size_t k = i; k < n4; k += stride) {
+    float4 pv = p4[k], gv = g4[k], mv = m4[k], vv = v4[k];
+    adam_elem<DECOUPLED>(pv.x, gv.x, mv.x, vv.x, coef, a);
+    adam_elem<DECOUPLED>(pv.y, gv.y, mv.y, vv.y, coef, a);
+    adam_elem<DECOUPLED>(pv.z, gv.z, mv.z, vv.z, coef, a);
+    adam_elem<DECOUPLED>(pv.w, gv.w, mv.w, vv.w, coef, a);
+    p4[k] = pv;
+    m4[k] = mv;
+    v4[k] = vv;
+  }
+  const size_t tail = head + (n4 << 2);
+  const size_t ns = head + (n - tail);
+  for (size_t k = i; k < ns; k += stride) {
+    const size_t e = k < head ? k : tail + (k - head);
+    float pv = p[e], mv = m[e], vv = v[e];
+    adam_elem<DECOUPLED>(pv, g[e], mv, vv, coef, a);
+    p[e] = pv;
+    m[e] = mv;
+    v[e] = vv;
+  }
+}
+
 inline hipStream_t S(void* s) { return (hipStream_t)s; }
 
 }  // namespace
@@ -1638,6 +1694,45 @@ extern "C" int ssc_sgd_step(float* p, const float* g, float* buf, size_t n, cons
   if (blocks > 4096) blocks = 4096;
   SSC_LAUNCH(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), p, g, buf, n, sqnorm, gscale, max_norm,
                      lr, momentum, weight_decay, first);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+extern "C" int ssc_adam_step(float* p, const float* g, float* m, float* v, size_t n, const float* sqnorm, float gscale,
+                             float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int decoupled,
+                             int step, void* stream) {
+  if (!p || !g || !m || !v || !sqnorm || step < 1) return SSC_EINVAL;
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f) || !(eps > 0.f) || !(lr >= 0.f) || !(weight_decay >= 0.f))
+    return SSC_EINVAL;
+  const uintptr_t mis = (uintptr_t)p & 15u;
+  if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 3u) return SSC_EALIGN;
+  if (n == 0) return SSC_OK;
+  // the four slices of equally aligned buffers share one misalignment: scalar head up to the first 16-byte boundary, float4
+  // bulk, scalar tail; a direct caller's differently aligned pointers take the scalar path throughout
+  size_t head = n;
+  if (((uintptr_t)g & 15u) == mis && ((uintptr_t)m & 15u) == mis && ((uintptr_t)v & 15u) == mis) {
+    head = ((16u - mis) & 15u) >> 2;
+    if (head > n) head = n;
+  }
+  const size_t n4 = (n - head) >> 2;
+  AdamArgs a;
+  const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+  a.step_size = (float)((double)lr / bc1);
+  a.rsqrt_bc2 = (float)(1.0 / sqrt(bc2));
+  a.beta1 = beta1;
+  a.omb1 = (float)(1.0 - (double)beta1);
+  a.beta2 = beta2;
+  a.omb2 = (float)(1.0 - (double)beta2);
+  a.eps = eps;
+  a.wd = weight_decay;
+  a.decay = (float)(1.0 - (double)lr * (double)weight_decay);
+  const size_t work = n4 > n - (n4 << 2) ? n4 : n - (n4 << 2);
+  size_t blocks = (work + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (decoupled)
+    SSC_LAUNCH(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, S(stream), p, g, m, v, n, head, n4, sqnorm, gscale, max_norm, a);
+  else
+    SSC_LAUNCH(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, S(stream), p, g, m, v, n, head, n4, sqnorm, gscale, max_norm, a);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }

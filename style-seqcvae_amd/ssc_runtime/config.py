@@ -86,6 +86,10 @@ def _defaults() -> dict:
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,
             "LR_DECAY": 0.5, "LR_DECAY_START_EPOCH": 10, "WEIGHT_DECAY": 0.001, "CLIP_GRADIENTS": 12.5,
             "EPOCH_START_DECODER_TRAINING": 40000, "BEFORE_UPDATE_DECODER_EVERY": 30,
+            # the optimiser behind the gradient clip on every path of scripts/train.py: "sgd" (the reference's: MOMENTUM), "adam"
+            # (WEIGHT_DECAY as L2 in the gradient) or "adamw" (decoupled WEIGHT_DECAY) - what self-critical fine-tuning is run with,
+            # at an LR of 5e-5 or so.  LR, WEIGHT_DECAY, CLIP_GRADIENTS and the linear decay are shared by the kinds
+            "OPTIMIZER": "sgd", "ADAM_BETAS": [0.9, 0.999], "ADAM_EPS": 1e-8,
         },
     }
 
@@ -151,6 +155,14 @@ class Config(object):
                 f"found MODEL.EMBEDDING_SIZE {self._C.MODEL.EMBEDDING_SIZE}")
         assert self._C.MODEL.MIN_CONSTRAINTS_TO_SATISFY <= self._C.DATA.CBS.MAX_GIVEN_CONSTRAINTS, \
             "Satisfying more constraints than maximum specified is not possible."
+        o = self._C.OPTIM
+        if o.OPTIMIZER not in ("sgd", "adam", "adamw"):
+            raise ValueError(f'OPTIM.OPTIMIZER must be "sgd", "adam" or "adamw"; found {o.OPTIMIZER!r}')
+        betas = o.ADAM_BETAS
+        if len(betas) != 2 or not all(isinstance(b, (int, float)) and 0.0 <= b < 1.0 for b in betas):
+            raise ValueError(f"OPTIM.ADAM_BETAS must be two numbers in [0, 1); found {betas!r}")
+        if not o.ADAM_EPS > 0:
+            raise ValueError(f"OPTIM.ADAM_EPS must be positive; found {o.ADAM_EPS!r}")
 
     def __getattr__(self, attr: str):
         return getattr(self.__dict__["_C"], attr)

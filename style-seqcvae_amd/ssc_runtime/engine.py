@@ -108,6 +108,115 @@ def _r4(x):
     return (x + 3) // 4 * 4
 
 
+OPTIM_KINDS = ("sgd", "adam", "adamw")
+
+
+@dataclass
+class OptimSpec:
+    """Which optimiser follows the clip in a fused step (train_step, backward_update, SelfCritical.step, scst_step: `optim=`).
+    kind: "sgd" (momentum, L2) | "adam" (L2 folded into the gradient) | "adamw" (decoupled decay).  momentum / weight_decay left at
+    None take the call's own momentum / weight_decay arguments (OPTIM.MOMENTUM, OPTIM.WEIGHT_DECAY are shared by the kinds)."""
+    kind: str = "sgd"
+    momentum: Optional[float] = None
+    betas: Tuple[float, float] = (0.9, 0.999)
+    eps: float = 1e-8
+    weight_decay: Optional[float] = None
+
+    def __post_init__(self):
+        if self.kind not in OPTIM_KINDS:
+            raise ValueError(f"optimiser kind must be one of {list(OPTIM_KINDS)}, got {self.kind!r}")
+        self.betas = (float(self.betas[0]), float(self.betas[1]))
+
+    @property
+    def is_adam(self) -> bool:
+        return self.kind != "sgd"
+
+    def resolve(self, momentum, weight_decay):
+        """(momentum, weight_decay) of a call that passes these two next to this spec: the spec's own where it sets them."""
+        return (momentum if self.momentum is None else self.momentum,
+                weight_decay if self.weight_decay is None else self.weight_decay)
+
+
+def range_step_count(counts) -> int:
+    """The one Adam step count of a range of the flat layout from its parameters' counts.  A parameter with count 0 next to others
+    that agree never received a gradient under torch.optim (no state entry): it joins the range with zero moments, as a torch
+    SGD checkpoint's parameter without a momentum buffer does.  Two different non-zero counts cannot be carried by one counter."""
+    nonzero = sorted({int(c) for c in counts if c})
+    if len(nonzero) > 1:
+        raise ValueError(f"Adam state: the step counts {nonzero} differ within one range of the flat layout (the fused step keeps one "
+                         "count for the decoder LSTM and one for the rest); scripts/train.py --reset-optimizer starts without the state")
+    return nonzero[0] if nonzero else 0
+
+
+def optimizer_state_kind(sd: dict) -> Optional[str]:
+    """"sgd" / "adam" from the per-parameter entries of an optimiser state_dict (momentum_buffer versus exp_avg; Adam and AdamW
+    keep the same state), else from its param group, else None (nothing in it says)."""
+    for st in sd.get("state", {}).values():
+        if "exp_avg" in st:
+            return "adam"
+        if "momentum_buffer" in st:
+            return "sgd"
+    for grp in sd.get("param_groups", []):
+        if "betas" in grp:
+            return "adam"
+        if "momentum" in grp:
+            return "sgd"
+    return None
+
+
+def check_optimizer_state_kind(sd: dict, want: str):
+    """ValueError if `sd` holds the other optimiser family's state than `want` ("sgd" | "adam" | "adamw")."""
+    have = optimizer_state_kind(sd)
+    fam = "sgd" if want == "sgd" else "adam"
+    if have is not None and have != fam:
+        raise ValueError(f"the optimiser state is of kind {have!r} ({'exp_avg' if have == 'adam' else 'momentum_buffer'} entries) but the "
+                         f"optimiser is {want!r}: state of one kind cannot continue the other (scripts/train.py: --reset-optimizer "
+                         "drops it and starts at iteration 1)")
+
+
+def _unpadded(flat, offsets, shapes, name):
+    """The un-padded view of tensor `name` inside a flat buffer laid out as FlatStore lays it out."""
+    o, cnt = offsets[name]
+    shp = shapes[name]
+    if len(shp) == 2 and shp[0] > 1:
+        return flat[o:o + cnt].view(shp[0], _r4(shp[1]))[:, :shp[1]]
+    return flat[o:o + shp[-1]].view(*shp)
+
+
+def pack_adam_state(names, offsets, shapes, exp_avg, exp_avg_sq, steps, lr, spec: OptimSpec, weight_decay, iteration) -> dict:
+    """Flat moment buffers + a step count per name -> torch.optim.Adam's state_dict layout (`step` a float32 scalar tensor,
+    exp_avg / exp_avg_sq in the parameters' own shapes, indexed in `names` order); a name whose count is 0 has no entry.  Pure
+    tensor work: runs on any device."""
+    state = {}
+    for i, n in enumerate(names):
+        if steps.get(n, 0) > 0:
+            state[i] = {"step": torch.tensor(float(steps[n]), dtype=torch.float32),
+                        "exp_avg": _unpadded(exp_avg, offsets, shapes, n).detach().clone().contiguous(),
+                        "exp_avg_sq": _unpadded(exp_avg_sq, offsets, shapes, n).detach().clone().contiguous()}
+    group = {"lr": float(lr), "betas": tuple(spec.betas), "eps": float(spec.eps), "weight_decay": float(weight_decay),
+             "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+             "decoupled_weight_decay": spec.kind == "adamw", "params": list(range(len(names)))}
+    return {"state": state, "param_groups": [group], "iteration": int(iteration)}
+
+
+def unpack_adam_state(names, offsets, shapes, exp_avg, exp_avg_sq, sd: dict) -> "Dict[str, int]":
+    """Inverse of pack_adam_state (also reads what torch.optim.Adam / AdamW wrote): fills the flat buffers in place (zero where a
+    parameter has no entry) and returns the step count per name."""
+    check_optimizer_state_kind(sd, "adam")
+    exp_avg.zero_()
+    exp_avg_sq.zero_()
+    steps = {n: 0 for n in names}
+    for i, st in sd.get("state", {}).items():
+        n = names[int(i)]
+        if "exp_avg" not in st:
+            continue
+        for flat, key in ((exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+            dst = _unpadded(flat, offsets, shapes, n)
+            dst.copy_(st[key].to(dst.device, torch.float32).view_as(dst))
+        steps[n] = int(round(float(st["step"])))
+    return steps
+
+
 class FlatStore:
     """One flat fp32 device buffer holding every tensor of `shapes` (16-B aligned offsets, rows of 2-D
     weights padded to a multiple of 4 floats so that 16 B/lane loads stay legal), exposed as views."""
@@ -178,6 +287,9 @@ class TrainEngine:
         self.params = FlatStore(shapes, self.device)
         self.grads = FlatStore(shapes, self.device)
         self.momentum = None
+        self.exp_avg = None           # Adam / AdamW moments, flat as the parameters, zeroed on first use (clip_adam_step)
+        self.exp_avg_sq = None
+        self.adam_steps = [0, 0]      # updates taken so far by [everything but the decoder LSTM, the decoder LSTM]
         self._ws = None
         self._ws_key = None
         self._cfg = dims.cfg()
@@ -494,12 +606,60 @@ class TrainEngine:
         self.steps_done += 1
         return sq
 
-    def optimizer_state_dict(self, named_parameters, lr, momentum, weight_decay, iteration) -> dict:
+    def _adam_buffers(self):
+        if self.exp_avg is None:
+            self.exp_avg = torch.zeros_like(self.params.flat)
+            self.exp_avg_sq = torch.zeros_like(self.params.flat)
+
+    def clip_adam_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, max_norm=12.5,
+                       decoder_frozen=False, gscale=1.0, sq_norm=None):
+        """clip_grad_norm_(max_norm) + torch.optim.Adam (decoupled: AdamW) on the flat buffers: the twin of clip_sgd_step, same
+        ranges, same sq_norm / gscale, same return value.  torch counts the steps per parameter and does not count one for a
+        parameter without a gradient, so under the freeze schedule the decoder LSTM's count lags: two counters (adam_steps), one
+        ssc_adam_step call when they agree after this step's increments, else two split at the decoder range, both reading the
+        same squared norm.  The moments start at zero (torch's lazily created state)."""
+        self._adam_buffers()
+        lo, hi = self.trainable_range(decoder_frozen)
+        st = _lib.stream_ptr()
+        if sq_norm is not None:   # already summed range by range (backward_overlapped)
+            sq = sq_norm
+        else:
+            sq = self._scratch[1024:1025]
+            self.lib.ssc_sq_norm(_lib.ptr(self.grads.flat[lo:hi]), hi - lo, _lib.ptr(self._scratch), _lib.ptr(sq), st)
+        self.adam_steps[0] += 1
+        if not decoder_frozen:
+            self.adam_steps[1] += 1
+        if decoder_frozen or self.adam_steps[0] == self.adam_steps[1]:
+            calls = [(lo, hi, self.adam_steps[0])]
+        else:
+            mid = self.params.range_of(self.decoder_names)[0]
+            calls = [(lo, mid, self.adam_steps[0]), (mid, hi, self.adam_steps[1])]
+        for a, b, step in calls:
+            self.lib.ssc_adam_step(_lib.ptr(self.params.flat[a:b]), _lib.ptr(self.grads.flat[a:b]), _lib.ptr(self.exp_avg[a:b]),
+                                   _lib.ptr(self.exp_avg_sq[a:b]), b - a, _lib.ptr(sq), float(gscale), float(max_norm), float(lr),
+                                   float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(bool(decoupled)), step, st)
+        self.steps_done += 1
+        return sq
+
+    def _adam_step_counts(self, names) -> "Dict[str, int]":
+        dec, frozen = set(self.decoder_names), set(self.frozen_names)
+        return {n: 0 if n in frozen else self.adam_steps[1 if n in dec else 0] for n in names}
+
+    def optimizer_state_dict(self, named_parameters, lr, momentum, weight_decay, iteration, optim: Optional[OptimSpec] = None) -> dict:
         """The fused optimiser's state in torch.optim.SGD's state_dict layout (one momentum_buffer per parameter, indexed
         in `named_parameters` order = model.parameters() order), so that a checkpoint written on either path of
         scripts/train.py resumes on the other and `optimizer.load_state_dict` of the reference's train.py:142-151 accepts
-        it.  `iteration` rides along inside this entry: the reference loads every OTHER top-level key into the model."""
+        it.  `iteration` rides along inside this entry: the reference loads every OTHER top-level key into the model.
+        optim of an Adam kind: torch.optim.Adam's layout instead (pack_adam_state; a parameter that never took a step - the
+        frozen tied embedding, the decoder LSTM before its first update - has no entry)."""
         names = [n for n, _ in named_parameters]
+        if optim is not None and optim.is_adam:
+            self._adam_buffers()
+            wd = optim.resolve(momentum, weight_decay)[1]
+            return pack_adam_state(names, self.params.offsets, self.params.shapes, self.exp_avg, self.exp_avg_sq,
+                                   self._adam_step_counts(names), lr, optim, wd, iteration)
+        if optim is not None:
+            momentum, weight_decay = optim.resolve(momentum, weight_decay)
         state = {}
         if self.momentum is not None:
             for i, n in enumerate(names):
@@ -515,10 +675,20 @@ class TrainEngine:
                  "params": list(range(len(names)))}
         return {"state": state, "param_groups": [group], "iteration": int(iteration)}
 
-    def load_optimizer_state_dict(self, named_parameters, sd: dict):
+    def load_optimizer_state_dict(self, named_parameters, sd: dict, optim: Optional[OptimSpec] = None):
         """Inverse of optimizer_state_dict; also accepts a torch.optim.SGD state_dict (parameters without a buffer - never
-        updated so far - start from zero, torch's lazily created buffer)."""
+        updated so far - start from zero, torch's lazily created buffer) or, with optim of an Adam kind, torch.optim.Adam's /
+        AdamW's.  State of the other kind than `optim` (default: SGD) is a ValueError that names both."""
         names = [n for n, _ in named_parameters]
+        if optim is not None and optim.is_adam:
+            check_optimizer_state_kind(sd, optim.kind)
+            self._adam_buffers()
+            steps = unpack_adam_state(names, self.params.offsets, self.params.shapes, self.exp_avg, self.exp_avg_sq, sd)
+            dec, frozen = set(self.decoder_names), set(self.frozen_names)
+            for which, group in ((1, [n for n in names if n in dec]), (0, [n for n in names if n not in dec and n not in frozen])):
+                self.adam_steps[which] = range_step_count(steps[n] for n in group)
+            return
+        check_optimizer_state_kind(sd, "sgd")
         if self.momentum is None:
             self.momentum = torch.zeros_like(self.params.flat)
         self.momentum.zero_()
@@ -543,8 +713,9 @@ class TrainEngine:
         return dp.allreduce_flat(self.grads.flat, group=group, n_buckets=self.dp_buckets)
 
     def train_step(self, feats, caps, sentiment, eps, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
-                   max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None):
-        """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row."""
+                   max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None):
+        """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row.
+        optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above."""
         loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts)
         B = loss.numel()
         key = (B, float(kld_weight))
@@ -553,10 +724,11 @@ class TrainEngine:
                               torch.full((B,), 1.0 / (B * kld_weight), dtype=torch.float32, device=self.device))
             self._upstream_key = key
         gl, gk = self._upstream
-        self.backward_update(gl, gk, lr, momentum, weight_decay, max_norm, decoder_frozen, group)
+        self.backward_update(gl, gk, lr, momentum, weight_decay, max_norm, decoder_frozen, group, optim)
         return loss, kld
 
-    def backward_update(self, gl, gk, lr, momentum=0.9, weight_decay=0.001, max_norm=12.5, decoder_frozen=False, group=None):
+    def backward_update(self, gl, gk, lr, momentum=0.9, weight_decay=0.001, max_norm=12.5, decoder_frozen=False, group=None,
+                        optim: Optional[OptimSpec] = None):
         """What follows the forward in one iteration: the backward of the last forward() with the per-row upstream gradients
         gl / gk (B,), the gradient all-reduce, clip + SGD.  train_step passes the constant vectors of the mean objective, the
         self-critical step (ssc_runtime/scst.py) the advantage-weighted ones: one path for both."""
@@ -570,4 +742,12 @@ class TrainEngine:
             self.backward(gl, gk, skip=skip)
             world = self.allreduce_grads(group)
             sq_parts = None
-        self.clip_sgd_step(lr, momentum, weight_decay, max_norm, decoder_frozen, gscale=1.0 / world, sq_norm=sq_parts)
+        if optim is None:
+            self.clip_sgd_step(lr, momentum, weight_decay, max_norm, decoder_frozen, gscale=1.0 / world, sq_norm=sq_parts)
+            return
+        momentum, weight_decay = optim.resolve(momentum, weight_decay)
+        if optim.is_adam:
+            self.clip_adam_step(lr, optim.betas, optim.eps, weight_decay, optim.kind == "adamw", max_norm, decoder_frozen,
+                                gscale=1.0 / world, sq_norm=sq_parts)
+        else:
+            self.clip_sgd_step(lr, momentum, weight_decay, max_norm, decoder_frozen, gscale=1.0 / world, sq_norm=sq_parts)

@@ -224,6 +224,7 @@ SYMBOLS = {
     "ssc_fill": (_i, [vp, _sz, _f, vp]),
     "ssc_sq_norm": (_i, [vp, _sz, vp, vp, vp]),
     "ssc_sgd_step": (_i, [vp, vp, vp, _sz, vp, _f, _f, _f, _f, _f, _i, vp]),
+    "ssc_adam_step": (_i, [vp, vp, vp, vp, _sz, vp, _f, _f, _f, _f, _f, _f, _f, _i, _i, vp]),
     "ssc_train_workspace_bytes": (_sz, [C.POINTER(ModelCfg), _i, _i, _i]),
     "ssc_train_fwd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, vp]),
     "ssc_train_bwd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), vp]),

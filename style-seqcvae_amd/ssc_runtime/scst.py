@@ -199,10 +199,11 @@ class SelfCritical:
 
     # ---- step ---------------------------------------------------------------------------------------------
     def step(self, feats, image_ids, sentiment, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001, max_norm=12.5,
-             decoder_frozen=False, group=None, seed: int = 0, obj_atts=None):
+             decoder_frozen=False, group=None, seed: int = 0, obj_atts=None, optim=None):
         """A rollout, then the train step on its captions with its upstream gradients: forward, and the backward / all-reduce /
-        clip / SGD path TrainEngine.train_step takes.  -> (loss (G,), kld (G,), stats (4,) fp64 on the device)."""
+        clip / SGD path TrainEngine.train_step takes (optim: an engine.OptimSpec - Adam or AdamW behind the clip instead).
+        -> (loss (G,), kld (G,), stats (4,) fp64 on the device)."""
         ro = self.rollout(feats, image_ids, sentiment, seed, obj_atts, kld_weight)
         loss, kld = self.eng.forward(ro.feats, ro.caps, ro.sentiment, ro.train_eps, ro.obj_atts)
-        self.eng.backward_update(ro.gl, ro.gk, lr, momentum, weight_decay, max_norm, decoder_frozen, group)
+        self.eng.backward_update(ro.gl, ro.gk, lr, momentum, weight_decay, max_norm, decoder_frozen, group, optim)
         return loss, kld, ro.stats

@@ -362,11 +362,11 @@ class UpDownCaptioner(nn.Module):
     def scst_step(self, image_features: torch.Tensor, image_ids, sentiment=None, obj_atts=None, *, references, lr, seed,
                   kld_weight: float = 750.0, momentum: float = 0.9, weight_decay: float = 0.001, max_norm: float = 12.5,
                   decoder_frozen: bool = False, group=None, n_samples: int = 5, sampler=None, baseline: str = "loo",
-                  reward_weights=None, max_steps: Optional[int] = None):
+                  reward_weights=None, max_steps: Optional[int] = None, optim=None):
         """One self-critical training step (ssc_runtime.scst.SelfCritical.step) on the engines this module owns: n_samples captions
         per image are sampled from the model as it stands, rewarded by CIDEr-D (reward_weights: B1, B2, B3, B4, ROUGE-L, CIDEr-D)
         against `references` (a CaptionReferences keyed by image_ids), and the parameters are updated in place - clip + SGD on the
-        flat buffers, as scripts/train.py --fused-optimizer.  obj_atts as in forward().  max_steps defaults to the maximum caption
+        flat buffers, as scripts/train.py --fused-optimizer (optim: a ssc_runtime.engine.OptimSpec, clip + Adam / AdamW instead).  obj_atts as in forward().  max_steps defaults to the maximum caption
         length.  -> (loss (B * n_samples,), kld (B * n_samples,), stats (4,) fp64: mean reward, mean baseline, mean |advantage|, share
         of samples without an end)."""
         from ssc_runtime.scst import CIDER_ONLY, SelfCritical
@@ -380,7 +380,7 @@ class UpDownCaptioner(nn.Module):
                           references)
         sent = sentiment.reshape(B) if sentiment is not None else None
         return self._scst[1].step(image_features, image_ids, sent, lr, kld_weight, momentum, weight_decay, max_norm, decoder_frozen,
-                                  group, seed, self._obj_means(obj_atts, B, R))
+                                  group, seed, self._obj_means(obj_atts, B, R), optim)
 
     def _sample_decode(self, image_features, obj_means, sentiment):
         """Eval forward with a word sampler: the whole decode in one library call (DecodeEngine.sample).  The latent noise is drawn
