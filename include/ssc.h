@@ -152,6 +152,14 @@ int ssc_embed_scatter_add(float* dtable, int ldt, const int64_t* ids, int n, int
  *              + sent[b]*wcol[n*ldwcol]
  *   gates_out (B,4H) = activated (i,f,g,o);  c_out = f*c_prev + i*g;  h_out = o*tanh(c_out)
  * add1 is indexed by b / rows_per_add1 (decode: per-image hoisted term).  Any optional pointer may be 0.
+ * The four forward entry points share this descriptor; the optional fields each of them reads:
+ *                                       ssc_lstm_fwd   ssc_lstm_fwd_img   ssc_lstm_fwd_z / _p
+ *   rows, row_count                          yes              -                   -
+ *   slab_rows, c_prev_rows                   yes             yes                  -
+ *   slabs2, nslab2 (slab2_stride, _rows)     yes             yes                  -
+ *   h_planes (ld_hplanes, planes_scale)      yes        yes (H % 4 == 0)          -
+ * A field that is set for an entry point that does not read it is SSC_EINVAL (never silently ignored); add0, add0_rows, add1,
+ * the biases, the sentiment column, c_prev and gates_out are read by all four.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct {
   int B, H;

@@ -2631,7 +2631,7 @@ extern "C" int ssc_set_gemm_mode(int mode) {
 
 // ---- include/ssc_debug.h -----------------------------------------------------------------------------------------
 extern int ssc_g_dec_att_table, ssc_g_dec_dedup, ssc_g_beam_reg, ssc_g_dec_ungathered, ssc_g_dec_parts, ssc_g_dec_planes;   // decode.hip
-extern int ssc_g_img_mfma;   // pointwise.hip
+extern int ssc_g_img_mfma;   // lstm.hip
 extern int ssc_g_dw_one_flush;   // sequence.hip
 namespace {
 struct DebugKey { const char* name; int* var; };

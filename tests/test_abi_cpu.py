@@ -82,6 +82,30 @@ def test_bad_arguments_are_rejected_without_a_gpu():
     assert lib.ssc_gemm_auto_splits(64, 4800, 180) >= 1
 
 
+@pytest.mark.parametrize("field", ["rows", "slab_rows", "c_prev_rows", "slabs2"])
+def test_lstm_fwd_z_and_p_reject_descriptor_fields_their_kernels_do_not_read(field):
+    """ssc_lstm_fwd_z / ssc_lstm_fwd_p read none of the row lists, row indirections or the second slab list of ssc_lstm_fwd_desc
+    (include/ssc.h): a descriptor that is valid but for one of them is SSC_EINVAL (-1) before anything is launched or read."""
+    lib = L.load()
+    B, H, Z = 2, 4, 4
+    buf = (C.c_float * (B * 4 * H * 4))()          # host memory: never read, the check comes first
+    idx = (C.c_int * B)()
+    a = C.addressof(buf)
+    d = L.LstmFwdDesc()
+    d.B, d.H = B, H
+    d.slabs, d.nslab, d.slab_stride = a, 1, B * 4 * H
+    d.c_prev, d.ld_cprev = a, H
+    d.c_out, d.ld_cout, d.h_out, d.ld_hout = a, H, a, H
+    if field == "rows":
+        d.rows, d.row_count = C.addressof(idx), C.addressof(idx)
+    elif field == "slabs2":
+        d.slabs2, d.nslab2, d.slab2_stride = a, 1, B * 4 * H
+    else:
+        setattr(d, field, C.addressof(idx))
+    assert lib._raw_ssc_lstm_fwd_z(C.byref(d), a, Z, a, Z, Z, None) == -1
+    assert lib._raw_ssc_lstm_fwd_p(C.byref(d), a, H, 4, a, None) == -1
+
+
 def test_missing_extension_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(L, "_lib", None)
     monkeypatch.setattr(L, "LIB_PATH", str(tmp_path / "nope.so"))

@@ -235,7 +235,8 @@ def test_bare_updown_cell_matches_reference_cell(tag, sv, Z):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,H,Z,nslab", [(64, 1200, 128, 13), (5, 37, 13, 3), (70, 50, 6, 0)])
+@pytest.mark.parametrize("B,H,Z,nslab", [(64, 1200, 128, 13), (5, 37, 13, 3), (70, 50, 6, 0),
+                                         (5, 37, 13, 17), (3, 20, 6, 33)])   # (a second and a third 16-slab batch, tail masked)
 def test_lstm_fwd_z_equals_cell_with_precomputed_latent_block(B, H, Z, nslab):
     """ssc_lstm_fwd_z (decoder cell with the K = Z latent block z . Wz^T formed inside the kernel) against ssc_lstm_fwd fed the
     same block through add0, and against the LSTMCell pointwise formulas in float64 (updown_cell.py:211-229).  1e-5: the two
@@ -290,10 +291,83 @@ def test_lstm_fwd_z_equals_cell_with_precomputed_latent_block(B, H, Z, nslab):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("nslab,options", [(1, False), (4, False), (5, False), (8, False), (9, False), (17, False), (9, True)])
+def test_lstm_fwd_equals_float64(nslab, options):
+    """ssc_lstm_fwd against the LSTMCell pointwise formulas in float64 at ragged rows and units (B = 6, H = 37): every arm of the
+    slab-batch dispatch (1 / 4 / 8 / 16 in flight) and each of its boundaries, and once with every option of the descriptor
+    together - a row list of 4 of the 6 rows, slab_rows, c_prev_rows, a second slab list through slab2_rows, add0 through
+    add0_rows, add1, the sentiment column.  Rows that are not listed keep what the outputs held.  2e-6 on values of order 1, the
+    bound of the image cell's test (test_decode_gpu.py): fp32 sums of at most 25 terms and the library exp / tanh."""
+    import ctypes as C
+    from ssc_runtime import lib as L
+    lib = L.load()
+    B, H = 6, 37
+    H4 = 4 * H
+    g = torch.Generator().manual_seed(100 * nslab + options)
+    rnd = lambda *s: torch.randn(*s, generator=g).cuda()
+    slabs, c_prev, b_ih, b_hh = rnd(nslab, B, H4) * 0.3, rnd(B, H), rnd(H4) * 0.1, rnd(H4) * 0.1
+    fill = 7.0
+    h, c, gates = (torch.full((B, H), fill, device="cuda"), torch.full((B, H), fill, device="cuda"),
+                   torch.full((B, H4), fill, device="cuda"))
+    d = L.LstmFwdDesc()
+    d.B, d.H = B, H
+    d.slabs, d.nslab, d.slab_stride = slabs.data_ptr(), nslab, B * H4
+    d.b_ih, d.b_hh = b_ih.data_ptr(), b_hh.data_ptr()
+    d.c_prev, d.ld_cprev = c_prev.data_ptr(), H
+    d.gates_out = gates.data_ptr()
+    d.c_out, d.ld_cout, d.h_out, d.ld_hout = c.data_ptr(), H, h.data_ptr(), H
+    pre = slabs.double().sum(0) + b_ih.double() + b_hh.double()
+    cp = c_prev.double()
+    listed = torch.arange(B)
+    if options:
+        listed = torch.tensor([0, 2, 3, 5])
+        rows, cnt = listed.int().cuda(), torch.tensor([4], dtype=torch.int32, device="cuda")
+        srow = torch.randint(0, B, (B,), generator=g).int().cuda()
+        prow = torch.randint(0, B, (B,), generator=g).int().cuda()
+        slabs2, s2row = rnd(3, 4, H4) * 0.3, torch.randint(0, 4, (B,), generator=g).int().cuda()
+        add0, rows0 = rnd(5, H4) * 0.2, torch.randint(0, 5, (B,), generator=g).cuda()
+        add1 = rnd(3, H4) * 0.2                                    # one row per 2 rows of the batch
+        sent, wcol = torch.randint(-1, 2, (B,), generator=g).float().cuda(), rnd(H4) * 0.2
+        d.rows, d.row_count = rows.data_ptr(), cnt.data_ptr()
+        d.slab_rows, d.c_prev_rows = srow.data_ptr(), prow.data_ptr()
+        d.slabs2, d.nslab2, d.slab2_stride, d.slab2_rows = slabs2.data_ptr(), 3, 4 * H4, s2row.data_ptr()
+        d.add0, d.ld_add0, d.add0_rows = add0.data_ptr(), H4, rows0.data_ptr()
+        d.add1, d.ld_add1, d.rows_per_add1 = add1.data_ptr(), H4, 2
+        d.sent, d.wcol, d.ldwcol = sent.data_ptr(), wcol.data_ptr(), 1
+        pre = slabs.double().sum(0)[srow.long()] + slabs2.double().sum(0)[s2row.long()] + add0.double()[rows0] \
+            + add1.double().repeat_interleave(2, 0) + b_ih.double() + b_hh.double() + sent.double()[:, None] * wcol.double()
+        cp = c_prev.double()[prow.long()]
+    lib.ssc_lstm_fwd(C.byref(d), L.stream_ptr())
+    torch.cuda.synchronize()
+    i, f, gg, o = pre.split(H, dim=1)
+    cw = torch.sigmoid(f) * cp + torch.sigmoid(i) * torch.tanh(gg)
+    hw = torch.sigmoid(o) * torch.tanh(cw)
+    act = torch.cat([torch.sigmoid(i), torch.sigmoid(f), torch.tanh(gg), torch.sigmoid(o)], 1)
+    r = listed.cuda()
+    assert maxdiff(c[r], cw[r]) < 2e-6 and maxdiff(h[r], hw[r]) < 2e-6 and maxdiff(gates[r], act[r]) < 2e-6
+    other = torch.ones(B, dtype=torch.bool, device="cuda")
+    other[r] = False
+    assert bool((c[other] == fill).all()) and bool((h[other] == fill).all()) and bool((gates[other] == fill).all())
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("B,H,K,nA", [(64, 1200, 256, 5), (5, 37, 26, 0), (70, 50, 300, 9), (64, 1200, 768, 5)])
 def test_lstm_bwd_x_equals_cell_backward_with_precomputed_addend(B, H, K, nA):
     """ssc_lstm_bwd_x (LSTM cell backward with the addend dh += x . w formed inside the kernel; BPTT of the encoder LSTM with
     x = (dmu | dlv), w = [W_mu ; W_lv], updown_cell.py:196-197) against ssc_lstm_bwd fed the same product through dh2."""
+    _check_lstm_bwd_x(B, H, K, nA, 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("nA,nB", [(17, 3), (3, 17)])
+def test_lstm_bwd_x_with_both_slab_lists(nA, nB):
+    """The same with both split-K slab lists of dh given, one on either side of the 8 / 16 batch dispatch (17: a second batch with
+    a masked tail), at ragged rows and units; additionally against the backward formulas in float64 (2e-5 relative, the bound of
+    the test above)."""
+    _check_lstm_bwd_x(5, 37, 26, nA, nB)
+
+
+def _check_lstm_bwd_x(B, H, K, nA, nB):
     import ctypes as C
     from ssc_runtime import lib as L
     lib = L.load()
@@ -308,6 +382,7 @@ def test_lstm_bwd_x_equals_cell_backward_with_precomputed_addend(B, H, K, nA):
     c_prev, c_new = torch.randn(B, H, generator=g).to(dev), torch.randn(B, H, generator=g).to(dev)
     dh_in, dc_in = torch.randn(B, H, generator=g).to(dev), torch.randn(B, H, generator=g).to(dev)
     slabs = (torch.randn(max(nA, 1), B, H, generator=g) * 0.3).to(dev)
+    slabsB = (torch.randn(max(nB, 1), B, H, generator=g) * 0.3).to(dev) if nB else None
 
     def run(fused):
         dG, dcp = torch.empty(B, 4 * H, device=dev), torch.empty(B, H, device=dev)
@@ -320,6 +395,8 @@ def test_lstm_bwd_x_equals_cell_backward_with_precomputed_addend(B, H, K, nA):
         d.dG, d.dc_prev, d.ld_dcprev = dG.data_ptr(), dcp.data_ptr(), H
         if nA:
             d.slabsA, d.nA, d.strideA = slabs.data_ptr(), nA, B * H
+        if nB:
+            d.slabsB, d.nB, d.strideB = slabsB.data_ptr(), nB, B * H
         if fused:
             lib.ssc_lstm_bwd_x(C.byref(d), x.data_ptr(), K, w.data_ptr(), Hp, K, L.stream_ptr())
         else:
@@ -333,10 +410,19 @@ def test_lstm_bwd_x_equals_cell_backward_with_precomputed_addend(B, H, K, nA):
     for u, v in zip(a, b):
         assert torch.isfinite(u).all()
         assert (u - v).abs().max().item() < 2e-5 * max(1.0, float(v.abs().max()))
+    if nB:
+        dh = dh_in.double() + slabs[:nA].double().sum(0) + slabsB[:nB].double().sum(0) + x.double() @ w[:, :H].double()
+        i, f, gg, o = gates.double().split(H, dim=1)
+        tc = torch.tanh(c_new.double())
+        dc = dc_in.double() + dh * o * (1 - tc * tc)
+        dG = torch.cat([dc * gg * i * (1 - i), dc * c_prev.double() * f * (1 - f), dc * i * (1 - gg * gg), dh * tc * o * (1 - o)], 1)
+        for u, v in zip(a, (dG, dc * f)):
+            assert (u.double() - v).abs().max().item() < 2e-5 * max(1.0, float(v.abs().max()))
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,H,NP,nslab", [(64, 1200, 256, 12), (5, 37, 26, 3), (70, 50, 12, 0)])
+@pytest.mark.parametrize("B,H,NP,nslab", [(64, 1200, 256, 12), (5, 37, 26, 3), (70, 50, 12, 0),
+                                          (5, 37, 13, 17), (3, 20, 6, 33)])   # (a second and a third 16-slab batch, tail masked)
 def test_lstm_fwd_p_partial_products_sum_to_the_linear_layer(B, H, NP, nslab):
     """ssc_lstm_fwd_p = ssc_lstm_fwd + partial products of its h with an nn.Linear weight (NP x H): the ceil(H/16) slabs sum to
     h @ wp^T (fc_mean | fc_log_var after the encoder LSTM, updown_cell.py:196-197); cell outputs equal ssc_lstm_fwd's bit for bit."""

@@ -2,7 +2,7 @@
 used on one side of a select) into a branch with `s_waitcnt vmcnt(0)` at the join: a lane's loads then go out one at a time.
 Prints, per kernel, the number of global loads, the number of full waits that are followed by further global loads (serialisation
 points) and the longest run of loads issued back to back.
-  python tools/isa_loads.py style-seqcvae_amd/csrc/pointwise.hip [kernel-name-substring]  [--dump]
+  python tools/isa_loads.py style-seqcvae_amd/csrc/lstm.hip [kernel-name-substring]  [--dump]
 """
 import importlib.util
 import os
