@@ -328,6 +328,27 @@ int ssc_ce_fwd(const float* logits, int ldl, const int64_t* targets, const float
                int V, float* lse, float* loss, void* stream);
 int ssc_ce_bwd(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, const float* lse,
                const float* gl, int T, int B, int V, void* stream);
+/* Label-smoothed vocabulary cross-entropy: the same loss with torch.nn.functional.cross_entropy's label_smoothing = eps in
+ * [0, 1) on every row - the eps mass is uniform over ALL V classes, the target, the pad / unknown index and the boundary included:
+ *   row(eps) = lse - (1-eps) * logits[row,target] - (eps/V) * sum_v logits[row,v]
+ *   fwd: loss[b] = n_b * sum_t w*row(eps) / (n_b + 1e-13);   nll[b] (optional, may be NULL) = the same with row(0): the
+ *        unsmoothed loss of the same forward, at no extra pass.  `lse` must hold 3*T*B floats: [lse | w*row(eps) | w*row(0)]
+ *   bwd (in place): logits[row,:] <- (softmax - (1-eps) * onehot - eps/V) * gl[b] * w[row] * n_b/(n_b+1e-13)
+ * Rows with w = 0 are skipped as in ssc_ce_fwd / ssc_ce_bwd: their logits are never read (they may hold anything), the forward
+ * writes 0 into their three slots, the backward a zero row.  Columns V .. ldl-1 of a padded row are neither read nor written.
+ * The forward scans a row ONCE (one workgroup per row: running maximum, rescaled sum of exponentials and sum_v (x[v] -
+ * x[target]) together; row(eps) = (lse - x[target]) - (eps/V) * that sum, so no large lse - mean(x) difference is formed); the
+ * backward is one in-place stream.  Both move 16 bytes per lane when ldl % 4 == 0: a scalar head up to the first 16-byte
+ * boundary of the row (every row then shares the misalignment of `logits`), the 16-byte bulk, a scalar tail; any other ldl
+ * takes the scalar path throughout.  No atomics: two calls on the same inputs are bit-identical.
+ * eps = 0 launches the kernels of ssc_ce_fwd / ssc_ce_bwd: lse, loss and the gradient are bit-identical to theirs, the third
+ * block of `lse` is a copy of the second and nll equals loss.
+ * SSC_EINVAL and no launch, before anything touches memory: eps outside [0, 1) or NaN, a NULL pointer other than nll, T, B or
+ * V < 1, ldl < V; SSC_EALIGN: logits no multiple of 4. */
+int ssc_ce_fwd_smooth(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
+                      int V, float eps, float* lse, float* loss, float* nll, void* stream);
+int ssc_ce_bwd_smooth(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, const float* lse,
+                      const float* gl, int T, int B, int V, float eps, void* stream);
 /* row-wise log_softmax (updown_captioner.py:450, nn.LogSoftmax(dim=1)); in place allowed. */
 int ssc_log_softmax(const float* logits, int ldl, int rows, int V, float* out, int ldo, void* stream);
 
@@ -396,6 +417,9 @@ typedef struct {
   int gemm_mode;    /* numerics of the 16-byte aligned NT / NN / TN products issued by the sequence-level calls made with THIS cfg
                      * (ssc_train_*, ssc_decode_*): 0 = the process default (ssc_set_gemm_mode), 1 = 3xBF16 (three bf16 pieces per
                      * fp32 operand, six partial products on the bf16 matrix cores, fp32 accumulate), 2 = exact-fp32 MFMA */
+  float label_smoothing;  /* eps of the cross-entropy in ssc_train_fwd / ssc_train_bwd / ssc_train_bwd_phases (phase 16), see
+                           * ssc_ce_fwd_smooth: 0 = the plain masked NLL (the kernels of ssc_ce_fwd / ssc_ce_bwd); outside [0, 1):
+                           * SSC_EINVAL from those three calls.  The decode, score and self-critical paths ignore it */
 } ssc_model_cfg;
 
 /* Parameter (or gradient) table: device pointers + leading dimensions of 2-D weights. */
@@ -434,7 +458,9 @@ typedef struct {
 
 size_t ssc_train_workspace_bytes(const ssc_model_cfg* cfg, int B, int R, int L);
 
-/* forward: fills loss (B), kld (B); keeps activations in `workspace` for ssc_train_bwd. */
+/* forward: fills loss (B), kld (B); keeps activations in `workspace` for ssc_train_bwd.  With cfg->label_smoothing > 0 loss is
+ * the smoothed one; the unsmoothed loss of the same forward is kept in the workspace either way (ssc_train_workspace_view 12).
+ * The backward must be given the cfg of its forward. */
 int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
                   size_t workspace_bytes, float* loss, float* kld, void* stream);
 
@@ -454,7 +480,8 @@ int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* p, const ss
 
 /* read-back of saved per-step activations for tests: which = 0:h1 1:c1 2:h_enc 3:c_enc 4:h_dec 5:c_dec
  * (each (T+1,B,H), index 0 = initial zeros), 6: alpha (T,B,R), 7: mu (T,B,Zp), 8: lv (T,B,Zp), 9: logits (T*B,V),
- * 10: tokens (L+2,B) int64, 11: att (T,B,F).  Returns pointer into the workspace (and its ld) or 0. */
+ * 10: tokens (L+2,B) int64, 11: att (T,B,F), 12: nll (B): the unsmoothed loss_b of the last forward (= loss with
+ * label_smoothing 0).  Returns pointer into the workspace (and its ld) or 0. */
 void* ssc_train_workspace_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
 
 /* ------------------------------------------------------------------------------------------------

@@ -185,6 +185,10 @@ def main():
     model.eps_source = _A.eps_source
     model.train()
     eng = model._engine()
+    smoothing = model.label_smoothing   # OPTIM.LABEL_SMOOTHING: the cross-entropy steps; nll (the unsmoothed loss) is then logged too
+    if smoothing > 0 and _A.scst_references and rank == 0:
+        print(f"OPTIM.LABEL_SMOOTHING {smoothing} is ignored by the self-critical steps (--scst-references): the advantage-weighted "
+              "loss is no likelihood target")
     from ssc_runtime.engine import OptimSpec, check_optimizer_state_kind
     kind = _C.OPTIM.OPTIMIZER
     spec = None   # the fused paths' optimiser; None: SGD with OPTIM.MOMENTUM / WEIGHT_DECAY, as before the key existed
@@ -258,7 +262,8 @@ def main():
             loss_b, kld_b = eng.train_step(batch["image_features"], batch["caption_tokens"], batch["sentiment"], eps, lr=lr,
                                            kld_weight=_C.MODEL.KLD_WEIGHT, momentum=_C.OPTIM.MOMENTUM,
                                            weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
-                                           decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec)
+                                           decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec,
+                                           label_smoothing=smoothing)
             reconstr_loss, kld_loss = loss_b.mean(), kld_b.mean()
             loss = reconstr_loss + kld_loss / _C.MODEL.KLD_WEIGHT
         else:
@@ -274,6 +279,8 @@ def main():
         if rank == 0 and (iteration % 100 == 0 or iteration == start_iteration or _C.OPTIM.NUM_ITERATIONS <= 100):
             rec = {"iteration": iteration, "1reconstr_loss": float(reconstr_loss), "2kld_loss": float(kld_loss),
                    "3loss": float(loss), "4learning_rate": lr, "elapsed_s": time.time() - t0}
+            if smoothing > 0 and scst is None:
+                rec["nll"] = float(eng.nll().mean())   # the unsmoothed loss of the same forward (this rank's rows)
             if scst_stats is not None:
                 st = scst_stats.tolist()
                 rec.update({"5reward": st[0], "6baseline": st[1], "7abs_advantage": st[2], "8no_end_share": st[3]})

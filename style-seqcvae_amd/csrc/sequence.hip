@@ -35,7 +35,9 @@ struct Layout {
   size_t live;  // int32: same layout; rows (t, b) with w = 1 at step t OR ANY LATER step of caption b (see build_active_rows_kernel)
   size_t tok, w, nvalid, sent_all, wcol_e, wcol_d, mask, avg, pv, emb, ga_static, ga_avg;
   size_t h1, c1, he, ce, hd, cd, gates_a, gates_e, gates_d, q, attn_logits, alpha, att, mu, lv, z, mulv;
-  size_t slabs, slab_floats, logits, lse, proj;
+  size_t slabs, slab_floats, logits, lse, proj;   // lse: [lse | w*row(eps)]
+  size_t nllw0, nll;   // the [w*row(0)] block of ssc_ce_fwd_smooth and the (B) unsmoothed loss: behind everything else, so that no other
+                       // buffer's place depends on them
   size_t sl_q, sl_mulv, sl_gh1, sl_ghd, sl_ghd2, sl_ghe, sl_dqw, sl_dhe, sl_dz, small_floats, wsum_att, wsum_dec, wz;
   size_t sl_ga, sl_ge, sl_gd, gate_floats;   // split-K slab regions of the three gate products (forward)
   // backward
@@ -127,6 +129,8 @@ Layout make_layout(const ssc_model_cfg* c, int B, int R, int L) {
   l.dwa = l.take((size_t)B * l.A);
   l.demb = l.take(TB * l.Ep);
   l.dproj = l.take(l.tied ? TB * l.Ep : 0);
+  l.nllw0 = l.take(TB);
+  l.nll = l.take(B);
   return l;
 }
 
@@ -356,6 +360,7 @@ int check_cfg(const ssc_model_cfg* c, const ssc_params* p, const ssc_batch* b) {
   if (!c || !p || !b) return SSC_EINVAL;
   if (c->V <= 1 || c->E <= 0 || c->H <= 0 || c->A <= 0 || c->F <= 0 || c->Z <= 0) return SSC_EINVAL;
   if (c->kld_mode < 0 || c->kld_mode > 2) return SSC_EINVAL;
+  if (!(c->label_smoothing >= 0.f && c->label_smoothing < 1.f)) return SSC_EINVAL;   // NaN included
   // kld_mode 2 (SENTIMENT_VAE = 2): the conditioning block is the whole pooled attribute vector (S = Z) or its first entry (S = 1)
   if (c->kld_mode == 2 ? ((c->S != 1 && c->S != c->Z) || c->pm_scale != 0.f || !b->obj_atts) : (c->S != 0 && c->S != 1)) return SSC_EINVAL;
   if (b->B <= 0 || b->R <= 0 || b->L <= 0 || b->R > 256) return SSC_EINVAL;
@@ -424,6 +429,7 @@ extern "C" void* ssc_train_workspace_view(const ssc_model_cfg* cfg, int B, int R
     case 9: *ld = l.Vp; return w + l.logits;
     case 10: *ld = l.B; return w + l.tok;
     case 11: *ld = l.Fp; return w + l.att;
+    case 12: *ld = l.B; return w + l.nll;
     default: return nullptr;
   }
 }
@@ -609,7 +615,9 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
   } else {
     SSC_TRY(gemm_rows(c, true, {{hd_all, l.Hp, p->out_w, p->ld_out_w, H}}, TB, V, W + l.logits, l.Vp, p->out_b));
   }
-  SSC_TRY(ssc_ce_fwd(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, W + l.lse, loss, st));
+  // label_smoothing 0 launches the kernels of ssc_ce_fwd; the unsmoothed loss of this forward lands in l.nll either way
+  SSC_TRY(ssc_ce_fwd_smooth_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, W + l.lse,
+                                   W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st));
   return SSC_OK;
 }
 
@@ -710,7 +718,7 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
   if (phases & (1u | 16u)) {
   // ---- vocabulary head ------------------------------------------------------------------------------
-  SSC_TRY(ssc_ce_bwd(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, st));
+  SSC_TRY(ssc_ce_bwd_smooth(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, st));
   const float* dlog = W + l.logits;
   {  // every zero-initialised buffer of this phase in one launch
     FillList f;

@@ -119,6 +119,10 @@ int ssc_beam_rows_dense(bool norm, const float* lp, int ldlp, const uint8_t* fsm
 int ssc_beam_merge(const float* sval, const int64_t* sidx, const float* last_lp, int B, int S, int beam, int per_node,
                    int64_t* pred, float* lp_out, int64_t* backptr, int end_index, int* ctl, int step_index, int max_steps,
                    int* host_flag, hipStream_t st);
+// ssc_ce_fwd_smooth (pointwise.hip) with its three blocks given one by one: the train workspace keeps the [w*row(0)] block apart from
+// the first two, whose place - and with it every other buffer's - is what it was before the third block existed
+int ssc_ce_fwd_smooth_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
+                             int V, float eps, float* lse, float* nllw, float* nllw0, float* loss, float* nll, hipStream_t st);
 int ssc_decode_att_table_enabled();   // the "dec_att_table" switch (decode.hip)
 // the start of a one-call decode with the early-stop protocol (search.hip): ctl[0] = max_steps, the counters behind it zero;
 // tokens0 (B) = end_index, the token the first step feeds

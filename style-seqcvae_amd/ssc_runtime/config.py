@@ -90,6 +90,9 @@ def _defaults() -> dict:
             # (WEIGHT_DECAY as L2 in the gradient) or "adamw" (decoupled WEIGHT_DECAY) - what self-critical fine-tuning is run with,
             # at an LR of 5e-5 or so.  LR, WEIGHT_DECAY, CLIP_GRADIENTS and the linear decay are shared by the kinds
             "OPTIMIZER": "sgd", "ADAM_BETAS": [0.9, 0.999], "ADAM_EPS": 1e-8,
+            # label smoothing of the cross-entropy steps (torch.nn.functional.cross_entropy's label_smoothing: the mass is spread
+            # over all V classes), in [0, 1); 0 = the reference's plain masked NLL.  Self-critical steps and validation never smooth
+            "LABEL_SMOOTHING": 0.0,
         },
     }
 
@@ -163,6 +166,9 @@ class Config(object):
             raise ValueError(f"OPTIM.ADAM_BETAS must be two numbers in [0, 1); found {betas!r}")
         if not o.ADAM_EPS > 0:
             raise ValueError(f"OPTIM.ADAM_EPS must be positive; found {o.ADAM_EPS!r}")
+        ls = o.LABEL_SMOOTHING
+        if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not 0.0 <= ls < 1.0:
+            raise ValueError(f"OPTIM.LABEL_SMOOTHING must be a number in [0, 1); found {ls!r}")
 
     def __getattr__(self, attr: str):
         return getattr(self.__dict__["_C"], attr)

@@ -67,10 +67,13 @@ class ModelDims:
     pad: int = 0
     boundary: int = 1
     gemm_mode: int = 0    # numerics of this engine's products: 0 = process default (ssc_set_gemm_mode), 1 = 3xBF16, 2 = exact-fp32 MFMA
+    label_smoothing: float = 0.0   # eps of the cross-entropy (ssc_ce_fwd_smooth) in the cfg this builds; TrainEngine.forward /
+                                   # train_step set the field per call from their own label_smoothing argument
 
     def cfg(self) -> _lib.ModelCfg:
         return _lib.ModelCfg(self.V, self.E, self.H, self.A, self.F, self.Z, self.S, int(self.tied), self.kld_mode,
-                             float(self.pm_scale), float(self.prior_var), self.pad, self.boundary, int(self.gemm_mode))
+                             float(self.pm_scale), float(self.prior_var), self.pad, self.boundary, int(self.gemm_mode),
+                             check_label_smoothing(self.label_smoothing))
 
     def param_shapes(self) -> "Dict[str, Tuple[int, ...]]":
         V, E, H, A, F, Z, S = self.V, self.E, self.H, self.A, self.F, self.Z, self.S
@@ -106,6 +109,17 @@ class ModelDims:
 
 def _r4(x):
     return (x + 3) // 4 * 4
+
+
+def check_label_smoothing(x, name="label_smoothing") -> float:
+    """x as a float in [0, 1) (torch.nn.functional.cross_entropy's label_smoothing), else a ValueError that names `name`."""
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(x, bool) or not 0.0 <= v < 1.0:
+        raise ValueError(f"{name} must be a number in [0, 1); found {x!r}")
+    return v
 
 
 OPTIM_KINDS = ("sgd", "adam", "adamw")
@@ -371,8 +385,12 @@ class TrainEngine:
                         eps.data_ptr(), obj_atts.data_ptr() if obj_atts is not None else None)
         return bt, (sent, obj_atts)
 
-    def forward(self, feats, caps, sentiment, eps, obj_atts=None):
-        """-> (loss (B,), kld (B,)); keeps activations for backward().  obj_atts (B,R,S): per-region attribute means, kld_mode 2 only."""
+    def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0):
+        """-> (loss (B,), kld (B,)); keeps activations for backward().  obj_atts (B,R,S): per-region attribute means, kld_mode 2 only.
+        label_smoothing: eps of THIS call's cross-entropy (ssc_ce_fwd_smooth; 0 = the plain masked NLL, the kernels as they are
+        without it).  It stays in the engine's cfg until the next forward, so every backward of this forward - the phased one of
+        the data-parallel path included - differentiates the loss that was returned.  nll() is the unsmoothed loss either way."""
+        self._cfg.label_smoothing = check_label_smoothing(label_smoothing)
         bt, sent = self._batch(feats, caps, sentiment, eps, obj_atts)
         ws = self._workspace(bt.B, bt.R, bt.L)
         loss = torch.empty(bt.B, dtype=torch.float32, device=self.device)
@@ -555,6 +573,11 @@ class TrainEngine:
         self.lib.ssc_train_bwd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
                                _lib.ptr(gk), C.byref(g), _lib.stream_ptr())
 
+    def nll(self):
+        """(B,) unsmoothed loss_b of the last forward (= its loss when that ran with label_smoothing 0): a view of the workspace,
+        valid until the next forward."""
+        return self.workspace_view(12)
+
     def workspace_view(self, which, T1=None):
         """Saved activations of the last forward (test hook; see ssc_train_workspace_view)."""
         bt = self._keep[0]
@@ -574,6 +597,8 @@ class TrainEngine:
             return ws[off:off + T * B * ld.value].view(T, B, ld.value)[:, :, :d.V]
         if which == 11:
             return ws[off:off + T * B * ld.value].view(T, B, ld.value)[:, :, :d.F]
+        if which == 12:
+            return ws[off:off + B]
         raise ValueError(which)
 
     # ---- optimiser (train.py:126-134,173-176) ---------------------------------------------------------
@@ -713,10 +738,12 @@ class TrainEngine:
         return dp.allreduce_flat(self.grads.flat, group=group, n_buckets=self.dp_buckets)
 
     def train_step(self, feats, caps, sentiment, eps, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
-                   max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None):
+                   max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None,
+                   label_smoothing=0.0):
         """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row.
-        optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above."""
-        loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts)
+        optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above.
+        label_smoothing: as forward(); loss is then the smoothed one, nll() the unsmoothed."""
+        loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing)
         B = loss.numel()
         key = (B, float(kld_weight))
         if getattr(self, "_upstream_key", None) != key:   # d(mean loss + mean kld / KLD_WEIGHT) / d(loss_b, kld_b): constant per (B, weight)

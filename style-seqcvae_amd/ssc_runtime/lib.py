@@ -69,7 +69,8 @@ class LatentBwdDesc(C.Structure):
 class ModelCfg(C.Structure):
     _fields_ = [("V", C.c_int), ("E", C.c_int), ("H", C.c_int), ("A", C.c_int), ("F", C.c_int), ("Z", C.c_int),
                 ("S", C.c_int), ("tied", C.c_int), ("kld_mode", C.c_int), ("pm_scale", C.c_float),
-                ("prior_var", C.c_float), ("pad", C.c_int), ("boundary", C.c_int), ("gemm_mode", C.c_int)]
+                ("prior_var", C.c_float), ("pad", C.c_int), ("boundary", C.c_int), ("gemm_mode", C.c_int),
+                ("label_smoothing", C.c_float)]
 
 
 # (field, has_ld) in the exact order of ssc_params
@@ -215,6 +216,8 @@ SYMBOLS = {
     "ssc_latent_bwd": (_i, [C.POINTER(LatentBwdDesc), vp]),
     "ssc_ce_fwd": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, vp, vp, vp]),
     "ssc_ce_bwd": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, vp]),
+    "ssc_ce_fwd_smooth": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _f, vp, vp, vp, vp]),
+    "ssc_ce_bwd_smooth": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, _f, vp]),
     "ssc_log_softmax": (_i, [vp, _i, _i, _i, vp, _i, vp]),
     "ssc_colsum": (_i, [vp, _i, _i, _i, vp, vp, _i, _i, vp]),
     "ssc_colsum2": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, _i, vp, vp]),

@@ -20,7 +20,7 @@ from ssc_runtime import sampling
 from ssc_runtime.cellops import cell_train_step
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.decoding import select_best_beam_with_constraints
-from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine
+from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_label_smoothing
 
 from ..modules import ConstrainedBeamSearch, UpDownCell
 
@@ -29,8 +29,8 @@ class _SeqCVAETrainFn(torch.autograd.Function):
     """loss_b, kld_b = f(params; feats, caps, sentiment, eps) with the hand-derived BPTT as backward."""
 
     @staticmethod
-    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, *params):
-        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means)
+    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, *params):
+        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing)
         ctx.eng, ctx.names = eng, names
         ctx.version = eng.fwd_version
         return loss, kld
@@ -41,7 +41,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
         if eng.fwd_version != ctx.version:
             raise RuntimeError("UpDownCaptioner: backward() after a newer forward(); the activation workspace holds "
                                "only the latest forward")
-        need = ctx.needs_input_grad[7:]
+        need = ctx.needs_input_grad[8:]
         skip = [n for n, k in zip(ctx.names, need) if not k]
         eng.backward(gl, gk, skip=skip)
         if eng.dp_autograd:   # data parallel on the autograd path: ONE sum all-reduce of the flat gradient buffer, then the mean
@@ -50,7 +50,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
                 eng.grads.flat.mul_(1.0 / world)
         frozen = set(eng.frozen_names)
         grads = tuple(eng.grads.views[n].clone() if (k and n not in frozen) else None for n, k in zip(ctx.names, need))
-        return (None,) * 7 + grads
+        return (None,) * 8 + grads
 
 
 class UpDownCaptioner(nn.Module):
@@ -58,7 +58,7 @@ class UpDownCaptioner(nn.Module):
                  max_caption_length=20, beam_size=1, use_cbs=False, min_constraints_to_satisfy=2, z_space=150,
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
                  sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None,
-                 sampled_beam=False, diverse_beam=None):
+                 sampled_beam=False, diverse_beam=None, label_smoothing=0.0):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
@@ -73,8 +73,12 @@ class UpDownCaptioner(nn.Module):
         returns beam 0.
         `diverse_beam` (MODEL.DIVERSE_BEAM_SEARCH): a sampling.DiverseBeam(groups, strength) - the eval forward runs the diverse beam
         search (ssc_decode_diverse_beam) at beam_size in one library call and returns the caption with the highest log-prob; no
-        sampler, no CBS decode, beam_size a multiple of the groups."""
+        sampler, no CBS decode, beam_size a multiple of the groups.
+        `label_smoothing` (OPTIM.LABEL_SMOOTHING), in [0, 1): the cross-entropy of the training forward spreads this much of every
+        target's mass over all V classes (torch.nn.functional.cross_entropy's label_smoothing, ssc_ce_fwd_smooth); 0 = the
+        reference's plain masked NLL.  scst_step and score_captions never smooth."""
         super().__init__()
+        self.label_smoothing = check_label_smoothing(label_smoothing)
         if diverse_beam is not None:
             if sampler is not None:
                 raise ValueError("MODEL.DIVERSE_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam' without MODEL.STOCHASTIC_BEAM_SEARCH")
@@ -172,7 +176,7 @@ class UpDownCaptioner(nn.Module):
                     latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
                     device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
                     sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
-                    diverse_beam=kwargs.get("diverse_beam"))
+                    diverse_beam=kwargs.get("diverse_beam"), label_smoothing=_C.OPTIM.LABEL_SMOOTHING)
         model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
         return model
 
@@ -307,7 +311,8 @@ class UpDownCaptioner(nn.Module):
             sent = sentiment if sentiment is not None else None
             obj_means = self._obj_means(obj_atts, batch_size, num_boxes)
             loss, kld = _SeqCVAETrainFn.apply(eng, names, image_features.contiguous().float(),
-                                              caption_tokens.contiguous().long(), sent, eps, obj_means, *params)
+                                              caption_tokens.contiguous().long(), sent, eps, obj_means, self.label_smoothing,
+                                              *params)
             return {"loss": loss, "kld": kld}
         # eval branch (updown_captioner.py:324-366)
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
@@ -542,11 +547,14 @@ class UpDownCaptioner(nn.Module):
                                                              prior_var=pv if prior_var is not None else None)
         return new_states["h_decoder"], new_states, pm, pv.log(), pm, pv.log(), alpha
 
-    def _get_loss(self, logits: torch.Tensor, targets: torch.Tensor, target_mask: torch.Tensor) -> torch.Tensor:
+    def _get_loss(self, logits: torch.Tensor, targets: torch.Tensor, target_mask: torch.Tensor,
+                  label_smoothing: float = 0.0) -> torch.Tensor:
         """(batch,) summed masked negative log-likelihood of the targets (updown_captioner.py:457-466: target length times allennlp's
         per-sequence average) on the HIP path (ssc_ce_fwd: row-wise log-sum-exp + NLL, the kernel inside ssc_train_fwd).  logits
         (B, T, V), targets (B, T) int64, target_mask (B, T).  The training forward computes this inside its fused call; this is the
-        stand-alone entry the reference exposes.  No autograd."""
+        stand-alone entry the reference exposes.  label_smoothing in [0, 1): the smoothed loss instead (ssc_ce_fwd_smooth).
+        No autograd."""
+        label_smoothing = check_label_smoothing(label_smoothing)
         lib = _lib.load()
         dev = logits.device
         if dev.type != "cuda":
@@ -556,9 +564,10 @@ class UpDownCaptioner(nn.Module):
         tg = targets.to(dev, torch.int64).t().contiguous()
         w = target_mask.to(dev, torch.float32).t().contiguous()
         nvalid = w.sum(0).contiguous()
-        lse = torch.empty(2 * T * B, dtype=torch.float32, device=dev)
+        lse = torch.empty(3 * T * B, dtype=torch.float32, device=dev)
         loss = torch.empty(B, dtype=torch.float32, device=dev)
-        lib.ssc_ce_fwd(_lib.ptr(lg), V, _lib.ptr(tg), _lib.ptr(w), _lib.ptr(nvalid), T, B, V, _lib.ptr(lse), _lib.ptr(loss), _lib.stream_ptr())
+        lib.ssc_ce_fwd_smooth(_lib.ptr(lg), V, _lib.ptr(tg), _lib.ptr(w), _lib.ptr(nvalid), T, B, V, label_smoothing, _lib.ptr(lse),
+                              _lib.ptr(loss), None, _lib.stream_ptr())
         return loss
 
 
