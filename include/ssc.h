@@ -914,6 +914,69 @@ int ssc_decode_diverse_beam(const ssc_model_cfg* cfg, const ssc_params* p, const
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Beam search under the DECODE RULES: blocking of repeated n-grams, a minimum caption length, a list of tokens that are never
+ * emitted, and a length penalty in the ranking (what captioning code bases, fairseq and HF switch on before a best-1 caption is
+ * trusted).  Deterministic beam search with the trivial machine.  lp = the log_softmax of a row's logits exactly as
+ * ssc_beam_step_fsm takes it with raw_logits = 1 (bit-equal to ssc_log_softmax); with raw_logits = 0 the scores are used as given.
+ * A ban removes a token from a row's candidates AFTER the log-softmax: the log-probs of all other tokens are untouched and
+ * nothing is renormalised.  Every beam carries its true summed log-prob phi, its token history w_0 .. w_{t-1} (the tokens of
+ * steps 0 .. t - 1), its length len and its score.  With n = no_repeat_ngram, m = min_length and step t:
+ *   Banned tokens of a live row at step t >= 1: the suppress list; END if t < m; with n >= 1 every token v such that the n-gram
+ *     (w_{t-n+1}, .., w_{t-1}, v) already occurs in w_0 .. w_{t-1} (n = 1: every word already used; fewer than n - 1 tokens of
+ *     history: nothing).  END is never banned by the n-gram rule; a live history holds no END.
+ *   Live row: its candidates are the per_node unbanned tokens of largest lp, descending (ties: lower token), each with the sum
+ *     s = phi + lp[v] (one fp32 add), the length L = t + 1 and the key s / length_penalty[L - 1] (one IEEE fp32 division).
+ *   Ended row (last token END): one candidate, END, with s = phi and L = len of the beam; its key phi / length_penalty[len - 1]
+ *     has the bits of its score of the step before.  Its scores are not read.
+ *   Merge per batch entry: the k candidates of largest key among the k * per_node, descending (ties: lower candidate index
+ *     j * per_node + slot).  Slot i gets that candidate's token, the back-pointer j, the true sum s, len = L and score = key; its
+ *     history is the parent's first t tokens with the new token appended.
+ *   Step 0: one row per entry with an empty history; the suppress list and min_length apply.  The k best unbanned tokens, with
+ *     len = 1 and score = lp / length_penalty[0].
+ *   A slot with no finite candidate emits END at -inf with the identity back-pointer, the history of the beam in that slot plus
+ *     END, len = t + 1 and score -inf.
+ * ctl / host_flag: the early-stop protocol of ssc_beam_desc (step 0 included).  A step that finds the search already stopped emits
+ * END from the same beam and leaves phi, len and score as they were.  Outputs are sorted by key: beam 0 is the best caption under
+ * the length penalty.  With no_repeat_ngram = 0, min_length = 0, n_suppress = 0 and every penalty 1.0f a step is
+ * ssc_beam_first_fsm / ssc_beam_step_fsm with the trivial machine on the logits, bit for bit (x / 1.0f is x).
+ * The library knows no penalty formula: the caller fills the table (the runtime offers L ** alpha).
+ * Limits: trivial machine only (dims.S = 1, fsm / tables / mach NULL), 1 <= k, per_node <= 32, k, per_node <= V, B * k <= 2^24,
+ * 0 <= n <= 64, m >= 0, 0 <= n_suppress <= 8, every suppressed id in [0, V) and not end_index, every one of the 64 penalties
+ * finite and positive, 1 <= step_index <= 63 for the later step - SSC_EINVAL with no launch beyond them or with a NULL required
+ * pointer.  No float atomics: two calls on the same inputs are bit-identical.  d->scores is never written.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSC_RULES_MAX_LEN 64
+#define SSC_RULES_MAX_SUPPRESS 8
+typedef struct {
+  int no_repeat_ngram;   /* n: 0 = off, else 1..SSC_RULES_MAX_LEN */
+  int min_length;        /* m >= 0: END is banned at steps t < m (a caption has >= m words before END) */
+  int n_suppress; int suppress[SSC_RULES_MAX_SUPPRESS];   /* ids in [0, V), != end_index: never candidates */
+  float length_penalty[SSC_RULES_MAX_LEN];   /* entry L-1: the divisor of a caption of L tokens, END counted; > 0, finite;
+                                                all 1.0f = ranking by the raw sum */
+} ssc_rules_desc;
+typedef struct {          /* running per-beam state; two generations are the caller's */
+  const int* hist; const int* len;        /* in:  (B, k, ld_hist), (B, k); NULL at step 0 */
+  int* hist_out; int* len_out; float* score_out;   /* out: same shapes, (B, k) */
+  int ld_hist;            /* >= step_index + 1 */
+} ssc_rules_state;
+/* Step 0 from d->scores (B, V) ld d->ld.  Uses B, beam, dims.V, raw_logits, end_index, pred / lp_out (B, k), scratch_val
+ * (>= B * k floats) and scratch_idx (>= B * k): every row's k best unbanned (lp, token), ctl / max_steps / host_flag. */
+int ssc_beam_first_rules(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_rules_state* s, void* stream);
+/* Step d->step_index in 1..63 from d->scores (B * k, V): last_pred / last_lp (B, k) and the state's input generation -> pred /
+ * lp_out / backptr (B, k) and its output generation (a different one).  scratch_val >= B * k * per_node floats, scratch_idx
+ * >= B * k * per_node: every live row's per_node best unbanned (lp, token). */
+int ssc_beam_step_rules(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_rules_state* s, void* stream);
+/* The whole search of one diverse-decode call as ONE library call: the loop of ssc_decode_search with S = 1, beam k, per_node n and
+ * no machine (d->fsm = d->tables = d->mach = NULL), the two steps above in place of ssc_beam_first_fsm / ssc_beam_step_fsm on
+ * the raw logits (never the per-tile records: a ban can remove both records of a tile); the same step forms (attention table,
+ * parent lists, un-gathered states, state planes), skip_dead, early stop and bounded run-ahead.  max_steps <= 64.  d->eps
+ * (max_steps - 1, B * k, Z).  Out: d->predictions (B, k, max_steps) - columns >= ctl[0] hold end_index -, d->log_probs (B, k): the
+ * true summed log-probs, scores (B, k): the keys, descending along k, lengths (B, k): tokens of every caption, END counted. */
+size_t ssc_decode_rules_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
+int ssc_decode_rules_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_rules_desc* r,
+                          float* scores, int* lengths, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diverse-caption evaluation (eval/eval.py:95-472 with the coco-caption scorers it calls): BLEU-1..4 (BleuScorer, option
  * "closest"), ROUGE-L (Rouge, beta 1.2) and CIDEr-D (CiderScorer, sigma 6) of every candidate; distinct 1- / 2-grams of every
  * image's N captions and of its top 5 by CIDEr (Div-n), and style-word counts.  The reductions over candidates (oracle argmax,

@@ -97,6 +97,8 @@ def main():
     sampler = sampling.from_config(_C.MODEL)   # MODEL.DECODE_SAMPLER / STOCHASTIC_BEAM_SEARCH: None = beam search
     sampled_beam = sampling.sampled_beam_from_config(_C.MODEL)   # MODEL.SAMPLED_BEAM_SEARCH: the word sampler at BEAM_SIZE
     diverse = sampling.diverse_beam_from_config(_C.MODEL)   # MODEL.DIVERSE_BEAM_SEARCH: groups of beams with a Hamming penalty
+    # MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN: the beam search under decode rules
+    rules = sampling.decode_rules_from_config(_C.MODEL, vocabulary)
     model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, diverse_beam=diverse, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
@@ -111,6 +113,8 @@ def main():
         raise SystemExit(f"{what} does not take constraints: constrained sampling is not supported")
     if diverse is not None and (_A.constraints_json or _A.boxes_json):
         raise SystemExit("MODEL.DIVERSE_BEAM_SEARCH does not take constraints")
+    if rules is not None and (_A.constraints_json or _A.boxes_json):
+        raise SystemExit("MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN do not take constraints")
     boundary = vocabulary.get_token_index("@@BOUNDARY@@")
     predictions = []
     id2word = np.array([vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())], dtype=object)
@@ -182,7 +186,7 @@ def main():
             else:
                 pred, _ = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                          num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
-                                         obj_means=obj, sampler=sampler, sampled_beam=sampled_beam)
+                                         obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules)
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
             if _A.references:

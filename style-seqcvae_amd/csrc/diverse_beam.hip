@@ -29,7 +29,7 @@
 namespace {
 
 constexpr int DBS_MAX_BEAM = 32;   // k <= 32 (the counts, the merge's one wave), n <= 32: m = n + k - k' <= 63 lanes
-constexpr int DBS_REG_NV = 40;     // V <= 256 * 40: the row in registers (decode.hip: beam_row_topk_reg_kernel)
+constexpr int DBS_REG_NV = BEAM_ROW_NV;   // V <= 256 * 40: the row in registers
 
 struct DbsRowArgs {
   const float* scores; size_t ld; int V, m;
@@ -71,34 +71,7 @@ __global__ __launch_bounds__(256) void dbs_rows_kernel(DbsRowArgs a) {
   if (stopped || (a.last_pred && a.last_pred[r] == a.end_index)) return;   // workgroup-uniform: an ended beam never looks at its row
   const float* row = a.scores + (size_t)r * a.ld;
   float x[REG ? DBS_REG_NV : 1];
-  float lse = 0.f;
-  if (REG) {
-#pragma unroll
-    for (int u = 0; u < DBS_REG_NV; ++u) x[u] = row[min(t + u * 256, V - 1)];
-    if (NORM) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < DBS_REG_NV; ++u)
-        if (t + u * 256 < V) mx = fmaxf(mx, x[u]);
-      mx = dec_block_reduce(mx, shr, true);
-      float sum = 0.f;
-#pragma unroll
-      for (int u = 0; u < DBS_REG_NV; ++u)
-        if (t + u * 256 < V) sum += expf(x[u] - mx);
-      sum = dec_block_reduce(sum, shr, false);
-      lse = mx + logf(sum);
-#pragma unroll
-      for (int u = 0; u < DBS_REG_NV; ++u) x[u] -= lse;
-    }
-  } else if (NORM) {   // thread t owns v = t, t + 256, ...: the order of log_softmax_kernel
-    float mx = -INFINITY;
-    for (int v = t; v < V; v += 256) mx = fmaxf(mx, row[v]);
-    mx = dec_block_reduce(mx, shr, true);
-    float sum = 0.f;
-    for (int v = t; v < V; v += 256) sum += expf(row[v] - mx);
-    sum = dec_block_reduce(sum, shr, false);
-    lse = mx + logf(sum);
-  }
+  const float lse = beam_row_lse<NORM, REG>(row, V, x, shr);
   float* lval = a.lval + (size_t)r * m;
   int64_t* ltok = a.ltok + (size_t)r * m;
   Cand mine = dbs_own_best<NORM, REG>(x, row, lse, V, Cand{INFINITY, -1});
@@ -216,23 +189,8 @@ __global__ __launch_bounds__(64) void dbs_merge_kernel(DbsMergeArgs a) {
       __syncthreads();
     }
   }
-  if (a.ctl && lane == 0) {
-    int* cnt = a.ctl + 2 + a.step_index;
-    int* ticket = a.ctl + 2 + a.max_steps + a.step_index;
-    if (live) atomicAdd(cnt, live);
-    __threadfence();
-    const int done = atomicAdd(ticket, 1);
-    if (done == (int)gridDim.x - 1) {   // the last workgroup of this step
-      if (!stopped) {
-        __threadfence();
-        if (atomicAdd(cnt, 0) == 0) {
-          atomicMin(a.ctl, a.step_index + 1);
-          if (a.host_flag) __hip_atomic_store(a.host_flag, a.step_index + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-      // progress word: ssc_decode_diverse_beam queues step t only once step t - 2 has got here (its run-ahead bound)
-      if (a.host_flag) __hip_atomic_store(a.host_flag + 1, a.step_index, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+  if (a.ctl && lane == 0) {   // early stop: the protocol of ssc_beam_desc.ctl
+    beam_early_stop_tail(a.ctl, a.host_flag, a.step_index, a.max_steps, live, stopped);
   }
 }
 

@@ -17,13 +17,14 @@ namespace {
 
 // The selection a search runs: beam search (the machine's top-k), the stochastic beam search (Gumbel-top-k, sbs.hip) or the
 // sampled-node beam search (a word sampler's draws per beam, sampled_beam.hip) or the diverse beam search (groups of beams with a
-// Hamming penalty, diverse_beam.hip).
-enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED, SEARCH_DIVERSE };
+// Hamming penalty, diverse_beam.hip) or the beam search under the decode rules (n-gram blocking, minimum length, suppressed tokens,
+// length penalty: rules_beam.hip).
+enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED, SEARCH_DIVERSE, SEARCH_RULES };
 
 // The vocabulary head of the later steps leaves per-tile records instead of logits (ssc_decode_step_desc.topk_part) when the machine
 // is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.  Beam search
-// only: any token can win a Gumbel draw or a sampler's draw, and a penalised row needs more than its two best tokens, so those
-// selections read the raw logits.
+// only: any token can win a Gumbel draw or a sampler's draw, a penalised row needs more than its two best tokens, and a ban of
+// the decode rules can remove both records of a tile, so those selections read the raw logits.
 bool search_uses_parts(const ssc_model_cfg* cfg, const ssc_search_desc* d, SearchKind kind) {
   const long G = (long)d->nimg * d->n_samples * d->S * d->beam;
   return kind == SEARCH_BEAM && d->S == 1 && !d->fsm && !d->tables && d->per_node <= 2 && !cfg->tied && cfg->gemm_mode != 2 &&
@@ -39,6 +40,7 @@ struct SearchLayout {
   size_t parent0;      // (B, SB) int64 zeros: every beam of the first expanded step descends from the one start row
   size_t lp[2];        // (B, S, beam) float
   size_t gs[2];        // gumbel: (B, beam) float, the beams' G (empty for beam search)
+  size_t rhist[2], rlen[2], rscore[2];   // rules: (G, max_steps) int32 histories, (G) int32 lengths, (G) float scores (empty otherwise)
   size_t sval, sidx;   // B*S*SB*per_node (gumbel: twice as many values - the candidates' G and log-probs; diverse: the rows' lists,
                        // `list` entries per row instead of per_node)
   size_t alpha;        // (G, R)
@@ -64,6 +66,12 @@ SearchLayout search_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, S
   l.parent0 = ssc_ws_take(o, G * 8);
   for (int g = 0; g < 2; ++g) l.lp[g] = ssc_ws_take(o, G * 4);
   for (int g = 0; g < 2; ++g) l.gs[g] = ssc_ws_take(o, gumbel ? G * 4 : 0);
+  const bool rules = kind == SEARCH_RULES;
+  for (int g = 0; g < 2; ++g) {
+    l.rhist[g] = ssc_ws_take(o, rules ? G * (size_t)d->max_steps * 4 : 0);
+    l.rlen[g] = ssc_ws_take(o, rules ? G * 4 : 0);
+    l.rscore[g] = ssc_ws_take(o, rules ? G * 4 : 0);
+  }
   l.sval = ssc_ws_take(o, B * d->S * SB * per_row * 4 * (gumbel ? 2 : 1));
   l.sidx = ssc_ws_take(o, B * d->S * SB * per_row * 8);
   l.alpha = ssc_ws_take(o, G * (size_t)d->R * 4);
@@ -126,7 +134,7 @@ namespace {
 
 // The selections the search loop below runs: beam search (the machine's top-k, ssc_beam_*_fsm / ssc_beam_step_parts), the
 // stochastic beam search (Gumbel-top-k, sbs.hip), the sampled-node beam search (sampled_beam.hip) and the diverse beam search
-// (diverse_beam.hip).  first() selects step 0;
+// (diverse_beam.hip) and the beam search under the decode rules (rules_beam.hip).  first() selects step 0;
 // step(a) a later step, reading the running state of generation a and writing generation 1 - a.
 struct BeamSelect {
   bool use_parts;
@@ -155,9 +163,24 @@ struct DiverseSelect {
   int step(ssc_beam_desc* bd, int, hipStream_t st) const { return ssc_beam_step_diverse(bd, s, st); }
 };
 
+struct RulesSelect {   // generation a of the histories, lengths and scores goes with generation a of the log-probs
+  const ssc_rules_desc* r;
+  int* hist[2]; int* len[2]; float* score[2];
+  int ld_hist;
+  int first(ssc_beam_desc* bd, hipStream_t st) const {
+    const ssc_rules_state s{nullptr, nullptr, hist[0], len[0], score[0], ld_hist};
+    return ssc_beam_first_rules(bd, r, &s, st);
+  }
+  int step(ssc_beam_desc* bd, int a, hipStream_t st) const {
+    const ssc_rules_state s{hist[a], len[a], hist[1 - a], len[1 - a], score[1 - a], ld_hist};
+    return ssc_beam_step_rules(bd, r, &s, st);
+  }
+};
+
+// final_gen: the generation of the running per-beam state (lp, and a selection's own) that holds the search's last step
 template <class Select>
 int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const SearchLayout& l, char* W,
-               const Select& sel, bool use_parts, hipStream_t st) {
+               const Select& sel, bool use_parts, hipStream_t st, int* final_gen = nullptr) {
   const int B = d->nimg * d->n_samples, S = d->S, beam = d->beam, SB = S * beam, G = B * SB, H = cfg->H, V = cfg->V, Z = cfg->Z;
   const SscStepStates& states = l.states;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
@@ -244,6 +267,7 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
     SSC_TRY(ssc_beam_backtrace(preds, backs, d->max_steps, B, SB, d->predictions, st));
   }
   if (hipMemcpyAsync(d->log_probs, lp[a], (size_t)G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
+  if (final_gen) *final_gen = a;
   return SSC_OK;
 }
 
@@ -325,4 +349,34 @@ extern "C" int ssc_decode_diverse_beam(const ssc_model_cfg* cfg, const ssc_param
   const SearchLayout l = search_layout(cfg, d, SEARCH_DIVERSE, ssc_diverse_beam_list(d->beam, s->groups, d->per_node, cfg->V));
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   return search_run(cfg, p, d, l, (char*)workspace, DiverseSelect{s}, false, (hipStream_t)stream);
+}
+
+// the beam search under the decode rules: S = 1, no machine, the limits of ssc_beam_step_rules (every step index below 64)
+static bool rules_search_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_rules_desc* r) {
+  if (!desc_ok(cfg, d) || !r) return false;
+  if (d->S != 1 || d->fsm || d->tables || d->mach || d->max_steps > SSC_RULES_MAX_LEN) return false;
+  return ssc_rules_beam_ok(d->nimg * d->n_samples, d->beam, d->per_node, cfg->V, d->end_index, r);
+}
+
+extern "C" size_t ssc_decode_rules_beam_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  if (!search_dims_ok(cfg, d)) return 0;
+  return search_layout(cfg, d, SEARCH_RULES).total;
+}
+
+extern "C" int ssc_decode_rules_beam(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_rules_desc* r,
+                                     float* scores, int* lengths, void* workspace, size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);
+  if (!p || !workspace || !scores || !lengths || !rules_search_ok(cfg, d, r)) return SSC_EINVAL;
+  const SearchLayout l = search_layout(cfg, d, SEARCH_RULES);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  char* W = (char*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  RulesSelect sel{r, {(int*)(W + l.rhist[0]), (int*)(W + l.rhist[1])}, {(int*)(W + l.rlen[0]), (int*)(W + l.rlen[1])},
+                  {(float*)(W + l.rscore[0]), (float*)(W + l.rscore[1])}, d->max_steps};
+  int a = 0;
+  SSC_TRY(search_run(cfg, p, d, l, W, sel, false, st, &a));
+  const size_t G = (size_t)d->nimg * d->n_samples * d->beam;
+  if (hipMemcpyAsync(scores, sel.score[a], G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
+  if (hipMemcpyAsync(lengths, sel.len[a], G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
+  return SSC_OK;
 }

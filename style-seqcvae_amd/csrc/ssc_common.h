@@ -149,5 +149,6 @@ bool ssc_sampled_beam_ok(int B, int k, int n, int V, const ssc_sampler_desc* s);
 // beam over V tokens; the entries of a row's list at a later step (n + k - k / groups, at most V)
 bool ssc_diverse_beam_ok(int B, int k, int n, int V, const ssc_diverse_desc* s);
 int ssc_diverse_beam_list(int k, int groups, int n, int V);
+bool ssc_rules_beam_ok(int B, int k, int n, int V, int end_index, const ssc_rules_desc* r);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

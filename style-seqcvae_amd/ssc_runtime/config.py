@@ -81,6 +81,19 @@ def _defaults() -> dict:
             # SAMPLED_BEAM_SEARCH False, no CBS and BEAM_SIZE % DIVERSE_BEAM_GROUPS == 0; scripts/inference.py then writes the best
             # caption of every group (N_Z_SAMPLES * DIVERSE_BEAM_GROUPS per image)
             "DIVERSE_BEAM_SEARCH": False, "DIVERSE_BEAM_GROUPS": 1, "DIVERSE_BEAM_STRENGTH": 0.5,
+            # decode rules of the deterministic beam search (ssc_runtime/sampling.py DecodeRules; ssc_rules_desc): any non-default
+            # value selects the beam search under rules (one library call, beam 0 = the best caption under the length penalty).
+            # Needs DECODE_SAMPLER "beam", STOCHASTIC_ / SAMPLED_ / DIVERSE_BEAM_SEARCH False and no CBS.
+            # NO_REPEAT_NGRAM n: a word that would complete an n-gram the caption already holds is not a candidate (0 = off, 3 is
+            # the usual choice; at most 64)
+            "NO_REPEAT_NGRAM": 0,
+            # MIN_CAPTION_LENGTH m: the caption cannot end before it has m words
+            "MIN_CAPTION_LENGTH": 0,
+            # LENGTH_PENALTY_ALPHA a: beams are ranked by (summed log-prob) / length ** a, the boundary token counted (0 = the raw
+            # sum, which favours short captions; 1 = the mean log-prob per token)
+            "LENGTH_PENALTY_ALPHA": 0.0,
+            # SUPPRESS_UNKNOWN: @@UNKNOWN@@ is never emitted (its log-prob is not given to the other words)
+            "SUPPRESS_UNKNOWN": False,
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,
@@ -158,6 +171,23 @@ class Config(object):
                 f"found MODEL.EMBEDDING_SIZE {self._C.MODEL.EMBEDDING_SIZE}")
         assert self._C.MODEL.MIN_CONSTRAINTS_TO_SATISFY <= self._C.DATA.CBS.MAX_GIVEN_CONSTRAINTS, \
             "Satisfying more constraints than maximum specified is not possible."
+        m = self._C.MODEL
+        ngram, min_len, alpha = m.NO_REPEAT_NGRAM, m.MIN_CAPTION_LENGTH, m.LENGTH_PENALTY_ALPHA
+        if isinstance(ngram, bool) or not isinstance(ngram, int) or not 0 <= ngram <= 64:
+            raise ValueError(f"MODEL.NO_REPEAT_NGRAM must be an integer in 0..64; found {ngram!r}")
+        if isinstance(min_len, bool) or not isinstance(min_len, int) or min_len < 0:
+            raise ValueError(f"MODEL.MIN_CAPTION_LENGTH must be an integer and not negative; found {min_len!r}")
+        if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or alpha != alpha or abs(alpha) == float("inf"):
+            raise ValueError(f"MODEL.LENGTH_PENALTY_ALPHA must be a finite number; found {alpha!r}")
+        if not isinstance(m.SUPPRESS_UNKNOWN, bool):
+            raise ValueError(f"MODEL.SUPPRESS_UNKNOWN must be True or False; found {m.SUPPRESS_UNKNOWN!r}")
+        if ngram or min_len or alpha != 0 or m.SUPPRESS_UNKNOWN:   # the beam search under decode rules is selected
+            max_len = self._C.DATA.MAX_CAPTION_LENGTH
+            if min_len >= max_len:
+                raise ValueError(f"MODEL.MIN_CAPTION_LENGTH ({min_len}) must be below DATA.MAX_CAPTION_LENGTH ({max_len})")
+            if max_len > 64:
+                raise ValueError("the decode rules (MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / "
+                                 f"SUPPRESS_UNKNOWN) need DATA.MAX_CAPTION_LENGTH <= 64; found {max_len}")
         o = self._C.OPTIM
         if o.OPTIMIZER not in ("sgd", "adam", "adamw"):
             raise ValueError(f'OPTIM.OPTIMIZER must be "sgd", "adam" or "adamw"; found {o.OPTIMIZER!r}')

@@ -372,6 +372,32 @@ class DecodeEngine:
                                lambda p, sd, ws: self.lib.ssc_decode_diverse_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                   C.byref(ddesc), *ws))
 
+    def rules_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
+                   max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], rules,
+                   early_stop: bool = True, skip_dead: bool = True):
+        """The whole beam search under the decode rules of one call in ONE library call (ssc_decode_rules_beam): blocking of
+        repeated n-grams, a minimum length, suppressed tokens and a length penalty in the ranking (sampling.DecodeRules), applied
+        where the selection runs; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples,
+        batch entry b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*beam, Z): the noise of every
+        step.  -> (predictions (B, beam, steps) int64, log_probs (B, beam): the true summed log-probs, scores (B, beam): the sums
+        over the penalty of the captions' lengths, descending - beam 0 is the best caption -, lengths (B, beam) int32: the tokens
+        of every caption, the END counted)."""
+        V = self.dims.V
+        if not (1 <= beam <= min(32, V) and 1 <= per_node <= min(32, V)):
+            raise ValueError(f"the beam search under decode rules needs 1 <= beam, per_node <= min(32, V), got beam {beam}, "
+                             f"per_node {per_node}")
+        rules.check(V, end_index, max_steps)
+        rdesc = rules.desc()
+        B = ctx.nimg * n_samples
+        scores = torch.empty(B, beam, dtype=torch.float32, device=self.device)
+        lengths = torch.empty(B, beam, dtype=torch.int32, device=self.device)
+        pred, lps = self._one_call(ctx, sentiment, n_samples, 1, beam, per_node, max_steps, end_index, eps0, eps, early_stop,
+                                   skip_dead, (B, beam), self.lib.ssc_decode_rules_beam_workspace_bytes,
+                                   lambda p, sd, ws: self.lib.ssc_decode_rules_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
+                                                                                    C.byref(rdesc), _lib.ptr(scores),
+                                                                                    _lib.ptr(lengths), *ws))
+        return pred, lps, scores, lengths
+
     def _step_from_embedding(self, ctx, token_embedding, states, sentiment, eps, prior_mean_out=None, prior_mean=None, prior_var=None):
         G = token_embedding.size(0)
         table = token_embedding.to(self.device, torch.float32).contiguous()

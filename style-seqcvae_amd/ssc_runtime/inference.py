@@ -24,7 +24,8 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
                    num_constraints: Optional[torch.Tensor] = None, min_constraints_to_satisfy: int = 0,
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
-                   sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False):
+                   sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
+                   rules=None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     fsm: None (trivial one-state machine, what MAX_GIVEN_CONSTRAINTS: 0 produces), or (nimg, S, S, V) uint8 - ONE machine per
     image, shared by its n_samples latent samples through an index list -, or (nimg*n_samples, S, S, V) (a copy per sample).
@@ -50,7 +51,20 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     `beam`, per_node by default the reference's rule on the group width (beam // groups // 2, or beam // groups); needs
     sampler = None and fsm = None.  The caption with the highest log-prob of every (image, sample) is returned (ties: the lower
     beam); with return_groups=True instead every group's best: (predictions (nimg, n_samples, groups, steps), steps, log_probs
-    (nimg, n_samples, groups))."""
+    (nimg, n_samples, groups)).
+    rules: a sampling.DecodeRules - the beam search runs under them (DecodeEngine.rules_beam: n-gram blocking, minimum length,
+    suppressed tokens, length penalty); needs sampler = None, no diverse_beam and fsm = None.  Beam 0 - the best caption under the
+    length penalty - of every (image, sample) is returned.  None, or rules with every control off: the plain beam search."""
+    if rules is not None and not rules.active:
+        rules = None
+    if rules is not None:
+        if sampler is not None or sampled_beam:
+            raise ValueError("the decode rules belong to the deterministic beam search: they take no sampler")
+        if diverse_beam is not None:
+            raise ValueError("the decode rules cannot be combined with diverse_beam")
+        if fsm is not None:
+            raise ValueError("the beam search under decode rules does not take constraints (fsm)")
+        rules.check(dec.dims.V, boundary_index, max_steps)
     if diverse_beam is not None:
         if sampler is not None or sampled_beam:
             raise ValueError("the diverse beam search is deterministic: it takes no sampler")
@@ -113,6 +127,11 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
             gen.manual_seed(seed)
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
+        if rules is not None:
+            beams, lps, _, _ = dec.rules_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, rules,
+                                              early_stop=early_stop, skip_dead=skip_now)
+            calls["k"] = beams.size(-1)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
         if diverse_beam is not None:
             beams, lps = dec.diverse_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, diverse_beam,
                                           early_stop=early_stop, skip_dead=skip_now)

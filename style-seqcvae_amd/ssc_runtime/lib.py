@@ -153,6 +153,19 @@ class DiverseDesc(C.Structure):
     _fields_ = [("groups", C.c_int), ("strength", C.c_float)]
 
 
+SSC_RULES_MAX_LEN = 64
+SSC_RULES_MAX_SUPPRESS = 8
+
+
+class RulesDesc(C.Structure):
+    _fields_ = [("no_repeat_ngram", C.c_int), ("min_length", C.c_int), ("n_suppress", C.c_int),
+                ("suppress", C.c_int * SSC_RULES_MAX_SUPPRESS), ("length_penalty", C.c_float * SSC_RULES_MAX_LEN)]
+
+
+class RulesState(C.Structure):
+    _fields_ = [("hist", vp), ("len", vp), ("hist_out", vp), ("len_out", vp), ("score_out", vp), ("ld_hist", C.c_int)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -281,6 +294,11 @@ SYMBOLS = {
     "ssc_decode_diverse_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(DiverseDesc)]),
     "ssc_decode_diverse_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(DiverseDesc), vp, _sz,
                                      vp]),
+    "ssc_beam_first_rules": (_i, [C.POINTER(BeamDesc), C.POINTER(RulesDesc), C.POINTER(RulesState), vp]),
+    "ssc_beam_step_rules": (_i, [C.POINTER(BeamDesc), C.POINTER(RulesDesc), C.POINTER(RulesState), vp]),
+    "ssc_decode_rules_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
+    "ssc_decode_rules_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(RulesDesc), vp, vp, vp,
+                                   _sz, vp]),
     "ssc_eval_refs_bytes": (_sz, [_i, _i, _i]),
     "ssc_eval_prepare_refs": (_i, [C.POINTER(EvalRefs), vp]),
     "ssc_eval_score_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc)]),

@@ -14,7 +14,15 @@ beam (DecodeEngine.stochastic_beam / ssc_decode_stochastic_beam).
 
 DiverseBeam is no sampler: the deterministic diverse beam search (Vijayakumar et al., AAAI 2018; DecodeEngine.diverse_beam /
 ssc_decode_diverse_beam, MODEL.DIVERSE_BEAM_SEARCH), the "Div-BS" baseline the sampled decoders are compared with.
+
+DecodeRules is no sampler either: the controls a best-1 caption is decoded under - blocking of repeated n-grams, a minimum length,
+suppressed tokens and a length penalty in the ranking (DecodeEngine.rules_beam / ssc_decode_rules_beam, MODEL.NO_REPEAT_NGRAM /
+MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN), for the deterministic beam search.
 """
+import math
+
+import numpy as np
+
 from . import lib as _lib
 
 KINDS = {"multinomial": 0, "top-k": 1, "top-p": 2}
@@ -177,17 +185,109 @@ def diverse_beam_from_config(model_cfg):
     return DiverseBeam(groups, strength)
 
 
+class DecodeRules:
+    """The decode rules of the beam search (ssc_rules_desc in include/ssc.h): no_repeat_ngram n - a token that would complete an
+    n-gram the caption already holds is not a candidate (0: off; 3 is the usual choice) -, min_length - END is not a candidate before
+    that many words -, length_alpha - beams are ranked by their summed log-prob over length ** alpha, the END counted (0: the raw
+    sum) - and suppress: up to 8 token ids that are never emitted.  The log-probs themselves are never changed."""
+
+    def __init__(self, no_repeat_ngram: int = 0, min_length: int = 0, length_alpha: float = 0.0, suppress=()) -> None:
+        if isinstance(no_repeat_ngram, bool) or int(no_repeat_ngram) != no_repeat_ngram or not 0 <= no_repeat_ngram <= _lib.SSC_RULES_MAX_LEN:
+            raise ValueError(f"no_repeat_ngram must be an integer in 0..{_lib.SSC_RULES_MAX_LEN}, got {no_repeat_ngram!r}")
+        if isinstance(min_length, bool) or int(min_length) != min_length or min_length < 0:
+            raise ValueError(f"min_length must be an integer and not negative, got {min_length!r}")
+        if isinstance(length_alpha, bool) or not math.isfinite(length_alpha):
+            raise ValueError(f"length_alpha must be a finite number, got {length_alpha!r}")
+        suppress = tuple(suppress)
+        if len(suppress) > _lib.SSC_RULES_MAX_SUPPRESS:
+            raise ValueError(f"at most {_lib.SSC_RULES_MAX_SUPPRESS} tokens can be suppressed, got {len(suppress)}")
+        if any(isinstance(v, bool) or int(v) != v or v < 0 for v in suppress) or len(set(suppress)) != len(suppress):
+            raise ValueError(f"suppress must hold distinct token ids, none negative, got {suppress!r}")
+        self.no_repeat_ngram = int(no_repeat_ngram)
+        self.min_length = int(min_length)
+        self.length_alpha = float(length_alpha)
+        self.suppress = tuple(int(v) for v in suppress)
+
+    @property
+    def active(self) -> bool:
+        """False when every rule is off: the search is then the plain beam search."""
+        return bool(self.no_repeat_ngram or self.min_length or self.length_alpha != 0.0 or self.suppress)
+
+    def table(self) -> np.ndarray:
+        """(64,) float32: entry L - 1 = L ** length_alpha, formed in float64 and rounded once."""
+        with np.errstate(over="ignore"):   # (an alpha beyond float32's range gives inf: check() refuses it)
+            return (np.arange(1, _lib.SSC_RULES_MAX_LEN + 1, dtype=np.float64) ** self.length_alpha).astype(np.float32)
+
+    def check(self, V: int, end_index: int, max_steps: int) -> None:
+        if max_steps > _lib.SSC_RULES_MAX_LEN:
+            raise ValueError(f"the beam search under decode rules runs at most {_lib.SSC_RULES_MAX_LEN} steps, got {max_steps}")
+        for v in self.suppress:
+            if v >= V or v == end_index:
+                raise ValueError(f"a suppressed token must lie in [0, {V}) and must not be the boundary token {end_index}, got {v}")
+        t = self.table()
+        if not (np.isfinite(t).all() and (t > 0).all()):
+            raise ValueError(f"length_alpha {self.length_alpha} gives a penalty that is not finite and positive in float32")
+
+    def desc(self) -> "_lib.RulesDesc":
+        """The C struct ssc_rules_desc."""
+        d = _lib.RulesDesc()
+        d.no_repeat_ngram, d.min_length, d.n_suppress = self.no_repeat_ngram, self.min_length, len(self.suppress)
+        for i, v in enumerate(self.suppress):
+            d.suppress[i] = v
+        for i, v in enumerate(self.table()):
+            d.length_penalty[i] = float(v)
+        return d
+
+    def __repr__(self):
+        return (f"DecodeRules(no_repeat_ngram={self.no_repeat_ngram}, min_length={self.min_length}, length_alpha={self.length_alpha}, "
+                f"suppress={self.suppress})")
+
+
+def decode_rules_from_config(model_cfg, vocabulary=None):
+    """MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN -> DecodeRules, or None when every key
+    has its default (no new code path runs then).  The rules belong to the deterministic beam search: DECODE_SAMPLER "beam",
+    STOCHASTIC_BEAM_SEARCH, SAMPLED_BEAM_SEARCH and DIVERSE_BEAM_SEARCH False, USE_CBS False.  vocabulary: where @@UNKNOWN@@ is
+    looked up for SUPPRESS_UNKNOWN (None: only the keys are checked, and the id is left out)."""
+    n = getattr(model_cfg, "NO_REPEAT_NGRAM", 0)
+    m = getattr(model_cfg, "MIN_CAPTION_LENGTH", 0)
+    alpha = getattr(model_cfg, "LENGTH_PENALTY_ALPHA", 0.0)
+    unk = bool(getattr(model_cfg, "SUPPRESS_UNKNOWN", False))
+    set_keys = [k for k, on in (("NO_REPEAT_NGRAM", n != 0), ("MIN_CAPTION_LENGTH", m != 0), ("LENGTH_PENALTY_ALPHA", alpha != 0.0),
+                                ("SUPPRESS_UNKNOWN", unk)) if on]
+    if not set_keys:
+        return None
+    key = "MODEL." + set_keys[0]
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if kind != "beam":
+        raise ValueError(f"{key} needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the decode rules belong to the "
+                         "deterministic beam search)")
+    for other in ("STOCHASTIC_BEAM_SEARCH", "SAMPLED_BEAM_SEARCH", "DIVERSE_BEAM_SEARCH"):
+        if bool(getattr(model_cfg, other, False)):
+            raise ValueError(f"{key} and MODEL.{other} exclude each other (the decode rules belong to the deterministic beam search)")
+    if bool(getattr(model_cfg, "USE_CBS", False)):
+        raise ValueError(f"{key} does not take constraints: MODEL.USE_CBS must be False")
+    suppress = ()
+    if unk and vocabulary is not None:
+        from .vocab import UNKNOWN
+        suppress = (int(vocabulary.get_token_index(UNKNOWN)),)
+    try:
+        return DecodeRules(n, m, alpha, suppress)
+    except ValueError as e:
+        raise ValueError(f"MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA: {e}") from None
+
+
 def from_config(model_cfg):
     """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
     STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
     "beam" gives GumbelSampler(SAMPLER_TEMPERATURE).  Checks MODEL.SAMPLED_BEAM_SEARCH (sampled_beam_from_config) and
-    MODEL.DIVERSE_BEAM_SEARCH (diverse_beam_from_config)."""
+    MODEL.DIVERSE_BEAM_SEARCH (diverse_beam_from_config) and the decode-rule keys (decode_rules_from_config)."""
     kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
     T = float(model_cfg.SAMPLER_TEMPERATURE)
     sbs = bool(getattr(model_cfg, "STOCHASTIC_BEAM_SEARCH", False))
     rep = bool(getattr(model_cfg, "SAMPLER_WITH_REPLACEMENT", False))
     sampled_beam_from_config(model_cfg)
     diverse_beam_from_config(model_cfg)
+    decode_rules_from_config(model_cfg)
     if sbs and kind != "beam":
         raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
                          "samplers draw one word per row; the stochastic beam search is a kind of beam search)")

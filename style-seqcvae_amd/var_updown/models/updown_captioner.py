@@ -58,7 +58,7 @@ class UpDownCaptioner(nn.Module):
                  max_caption_length=20, beam_size=1, use_cbs=False, min_constraints_to_satisfy=2, z_space=150,
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
                  sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None,
-                 sampled_beam=False, diverse_beam=None, label_smoothing=0.0):
+                 sampled_beam=False, diverse_beam=None, label_smoothing=0.0, decode_rules=None):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
@@ -74,6 +74,10 @@ class UpDownCaptioner(nn.Module):
         `diverse_beam` (MODEL.DIVERSE_BEAM_SEARCH): a sampling.DiverseBeam(groups, strength) - the eval forward runs the diverse beam
         search (ssc_decode_diverse_beam) at beam_size in one library call and returns the caption with the highest log-prob; no
         sampler, no CBS decode, beam_size a multiple of the groups.
+        `decode_rules` (MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN): a
+        sampling.DecodeRules - the eval forward runs the beam search under them (ssc_decode_rules_beam) at beam_size in one library
+        call and returns beam 0, the best caption under the length penalty; no sampler, no diverse_beam, no CBS decode.  None, or
+        rules with every control off: the eval forward is what it is without them.
         `label_smoothing` (OPTIM.LABEL_SMOOTHING), in [0, 1): the cross-entropy of the training forward spreads this much of every
         target's mass over all V classes (torch.nn.functional.cross_entropy's label_smoothing, ssc_ce_fwd_smooth); 0 = the
         reference's plain masked NLL.  scst_step and score_captions never smooth."""
@@ -85,6 +89,17 @@ class UpDownCaptioner(nn.Module):
             if beam_size % diverse_beam.groups != 0:
                 raise ValueError(f"MODEL.BEAM_SIZE ({beam_size}) must be a multiple of MODEL.DIVERSE_BEAM_GROUPS ({diverse_beam.groups})")
         self.diverse_beam = diverse_beam
+        if decode_rules is not None and not decode_rules.active:
+            decode_rules = None
+        if decode_rules is not None:
+            if sampler is not None or sampled_beam:
+                raise ValueError("MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN need "
+                                 "MODEL.DECODE_SAMPLER 'beam' without MODEL.STOCHASTIC_BEAM_SEARCH")
+            if diverse_beam is not None:
+                raise ValueError("MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN and "
+                                 "MODEL.DIVERSE_BEAM_SEARCH exclude each other")
+            decode_rules.check(vocabulary.get_vocab_size(), vocabulary.get_token_index("@@BOUNDARY@@"), max_caption_length)
+        self.decode_rules = decode_rules
         if sampled_beam and (sampler is None or sampler.beam_search):
             raise ValueError("MODEL.SAMPLED_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p'")
         if sampler is not None and not sampler.beam_search and not sampled_beam and beam_size != 1:
@@ -164,9 +179,11 @@ class UpDownCaptioner(nn.Module):
         """Instantiate from a Config (updown_captioner.py:141-166); extra kwargs such as cbs_simple are ignored as in
         the reference.  mean_choice=... (SENTIMENT_VAE = 2) is handed to the constructor.  MODEL.SAMPLED_BEAM_SEARCH is read only
         with a sampler=... (the decode's); a model built without one (scripts/train.py) ignores it, as it ignores the other
-        decode keys; diverse_beam=... (sampling.diverse_beam_from_config) likewise comes from the caller."""
+        decode keys; diverse_beam=... (sampling.diverse_beam_from_config) likewise comes from the caller.  The decode rules
+        (sampling.decode_rules_from_config) are read here; with their keys at the defaults there are none."""
         _C = config
-        model = cls(vocabulary=kwargs.pop("vocabulary"), image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
+        vocabulary = kwargs.pop("vocabulary")
+        model = cls(vocabulary=vocabulary, image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
                     embedding_size=_C.MODEL.EMBEDDING_SIZE, hidden_size=_C.MODEL.HIDDEN_SIZE,
                     attention_projection_size=_C.MODEL.ATTENTION_PROJECTION_SIZE, beam_size=_C.MODEL.BEAM_SIZE,
                     max_caption_length=_C.DATA.MAX_CAPTION_LENGTH, use_cbs=_C.MODEL.USE_CBS,
@@ -176,7 +193,8 @@ class UpDownCaptioner(nn.Module):
                     latent_embedding_multip=_C.MODEL.LATENT_EMBEDDING_MULTIP, cbs_simple=_C.MODEL.CBS_SIMPLE,
                     device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
                     sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
-                    diverse_beam=kwargs.get("diverse_beam"), label_smoothing=_C.OPTIM.LABEL_SMOOTHING)
+                    diverse_beam=kwargs.get("diverse_beam"), label_smoothing=_C.OPTIM.LABEL_SMOOTHING,
+                    decode_rules=sampling.decode_rules_from_config(_C.MODEL, vocabulary))
         model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
         return model
 
@@ -329,6 +347,12 @@ class UpDownCaptioner(nn.Module):
                 raise ValueError("MODEL.USE_CBS with a constraint machine cannot be combined with MODEL.DIVERSE_BEAM_SEARCH")
             with torch.no_grad():
                 return {"predictions": self._diverse_beam_decode(image_features, obj_means, sentiment)}
+        if self.decode_rules is not None:
+            if self._use_cbs and fsm is not None:
+                raise ValueError("MODEL.USE_CBS with a constraint machine cannot be combined with the decode rules "
+                                 "(MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN)")
+            with torch.no_grad():
+                return {"predictions": self._rules_beam_decode(image_features, obj_means, sentiment)}
         with torch.no_grad():
             if self._use_cbs and fsm is not None:
                 fsm_d = fsm.to(dev).to(torch.uint8)
@@ -427,6 +451,20 @@ class UpDownCaptioner(nn.Module):
                                             self.diverse_beam)
         bi = lps.argmax(-1)
         return beams.gather(1, bi.view(B, 1, 1).expand(B, 1, beams.size(-1))).squeeze(1)
+
+    def _rules_beam_decode(self, image_features, obj_means, sentiment):
+        """Eval forward with decode rules: the beam search under them in one library call (DecodeEngine.rules_beam), the noise
+        drawn as the beam path draws it; beam 0 of every image - the best caption under the length penalty."""
+        B = image_features.size(0)
+        L = self._max_caption_length
+        dev = self._eng.device
+        ctx = self._image_context(image_features, obj_means)
+        k = self._beam_search.beam_size
+        eps0 = self._draw_eps(1, B, dev)[0]
+        eps = self._draw_eps(L - 1, B * k, dev) if L > 1 else None
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        beams, _, _, _ = self._dec.rules_beam(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.decode_rules)
+        return beams[:, 0, :]
 
     def _image_context(self, image_features, obj_means=None):
         """Per-image terms (mask, averaged features, projected features, hoisted gate term) for the eval decode step, computed

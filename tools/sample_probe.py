@@ -7,9 +7,13 @@ per-node 2 for each word sampler with and without replacement (ssc_decode_sample
 bytes / time against one HBM pass.
     python tools/sample_probe.py [calls]
     python tools/sample_probe.py diverse-beam [calls] [rounds]
+    python tools/sample_probe.py rules-beam [calls] [rounds]
 The diverse-beam leg alone: the time per call of ssc_decode_diverse_beam (k = 6 in 3 groups, per-node 1) next to ssc_decode_search
 (k = 6, per-node 3: the logits path) on the same inputs, in alternating rounds on the same device, and the two selections alone
 (ssc_beam_step_fsm, ssc_beam_step_diverse) on the same (G * 6, V) logits - their share of a step.
+The rules-beam leg alone, at C4's shapes (beam 5, per-node 2): the time per call of ssc_decode_search (at this size its later steps
+read per-tile records, not logits), of ssc_decode_rules_beam with every rule off and of ssc_decode_rules_beam with n = 3,
+alpha = 1, min_length = 5, suppress = [0] (both on the (G, V) logits), in alternating rounds on the same device and inputs.
 Prints one JSON line."""
 import json
 import os
@@ -94,8 +98,39 @@ def diverse_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, rounds):
     return out
 
 
+def rules_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, rounds):
+    """Alternating rounds of `calls` one-call searches each at beam 5 / per-node 2, early stop off (all steps run), the same noise:
+    the beam search, the search under rules with every rule off, and with n-gram blocking, a minimum length, a suppressed token
+    and a length penalty."""
+    dev = feats.device
+    k, n, B = 5, 2, images * n_z
+    G = B * k
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    eps0 = torch.randn(B, c["Z"], device=dev, generator=gen)
+    eps = torch.randn(steps - 1, G, c["Z"], device=dev, generator=gen)
+    sent_b = senti.view(images, 1).expand(images, n_z).reshape(B).contiguous()
+    ctx = dec.prepare(feats)
+    off = sampling.DecodeRules()
+    on = sampling.DecodeRules(no_repeat_ngram=3, min_length=5, length_alpha=1.0, suppress=(0,))
+    runs = (("beam_search", lambda: dec.search(ctx, sent_b, n_z, k, n, steps, 1, eps0, eps, skip_dead=True, early_stop=False)),
+            ("rules_off", lambda: dec.rules_beam(ctx, sent_b, n_z, k, n, steps, 1, eps0, eps, off, skip_dead=True, early_stop=False)),
+            ("rules_on", lambda: dec.rules_beam(ctx, sent_b, n_z, k, n, steps, 1, eps0, eps, on, skip_dead=True, early_stop=False)))
+    out = {"images": images, "n_z": n_z, "beam": k, "per_node": n, "rows_per_step": G, "max_steps": steps, "V": c["V"],
+           "calls_per_round": calls, "rounds_ms": {name: [] for name, _ in runs}}
+    for _ in range(rounds):
+        for name, fn in runs:
+            out["rounds_ms"][name].append(timed(fn, calls))
+    for name, _ in runs:
+        v = out["rounds_ms"][name]
+        out[name] = {"ms_per_call": sum(v) / len(v), "min": min(v), "max": max(v)}
+    base = out["beam_search"]["ms_per_call"]
+    out["ratio_to_beam_search"] = {name: out[name]["ms_per_call"] / base for name in ("rules_off", "rules_on")}
+    return out
+
+
 def main():
-    leg = len(sys.argv) > 1 and sys.argv[1] == "diverse-beam"
+    leg = len(sys.argv) > 1 and sys.argv[1] in ("diverse-beam", "rules-beam") and sys.argv[1]
     if leg:
         del sys.argv[1]
     calls = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -111,6 +146,9 @@ def main():
     images, n_z, steps = 100, 20, c["L"]
     feats = torch.randn(images, c["R"], c["F"], generator=g).to(dev)
     senti = torch.ones(images, device=dev)
+    if leg == "rules-beam":
+        print(json.dumps(rules_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, int(sys.argv[2]) if len(sys.argv) > 2 else 3)))
+        return
     if leg:
         print(json.dumps(diverse_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, int(sys.argv[2]) if len(sys.argv) > 2 else 3)))
         return
