@@ -801,6 +801,60 @@ int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_sc
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Posterior scoring of given captions: what the encoder branch q(z_t | x) = N(mu_tb, exp(lv_tb)) of the TRAIN forward says about a
+ * caption - the pieces of the ELBO and of the importance-weighted bound with q as the proposal (Burda et al. 2016).
+ * Rows r = t * B + b (step t of caption row b).  w (T*B): the train forward's step weight.  The generative prior is the one the
+ * eval decode samples: p(z_t) = N(pm_tb, prior_var), pm = the explicit `pm` where given (kld_mode 2: the pooled attribute means of
+ * the step), else pm_scale * sent[b] (0 without `sent`).  z = eps * exp(lv / 2) + mu as the forward stored it.  Per row b:
+ *   log_ratio[b]      = sum_t w_tb sum_j 1/2 (eps^2 + lv - log prior_var - (z - pm)^2 / prior_var)
+ *                     = sum_t w_tb [log p(z_t) - log q(z_t | x)]        (the 2 pi terms cancel; z - pm uses the STORED z)
+ *   kl[b]             = sum_t w_tb sum_j k_tbj, the training KL in the formula of kld_mode, as ssc_latent_fwd has it:
+ *                         0:    k = -1/2 (1 + lv - mu^2 - exp(lv))                 (against N(0, 1) whatever prior_var is)
+ *                         1, 2: k = -1/2 (1 + lv - log prior_var - ((mu - pm)^2 + exp(lv)) / (prior_var + 1e-5))
+ *   kl_dim[b, j]      = sum_t w_tb k_tbj          step_kl[t*B+b] = w_tb sum_j k_tbj
+ *   step_ratio[t*B+b] = the step's part of log_ratio
+ * One wave per caption row, lanes over j with a stride of 64, t sequential; the per-dimension sums stay in registers and the row
+ * scalars are one ssc_wave_sum of them: a fixed summation order, no float atomics, the same bits on every run.  A step with
+ * w == 0 is SKIPPED, not multiplied by zero: its rows of mu / lv / z / eps / pm are not read (they may hold anything), its step
+ * outputs are 0; a row without a live step gives 0 everywhere.  Columns j >= Z are never read.  Z <= 512.
+ * SSC_EINVAL and no launch: a NULL descriptor or required pointer, T, B or Z <= 0, Z > 512, ldz / ldeps / ldpm / ld < Z,
+ * prior_var <= 0 (NaN included), kld_mode outside 0..2, kld_mode 2 without pm. */
+typedef struct {
+  int T, B, Z;
+  const float* mu;               /* (T*B, ldz) */
+  const float* lv;               /* (T*B, ldz) */
+  const float* z;                /* (T*B, ldz) */
+  int ldz;
+  const float* eps;              /* (T*B, ldeps) */
+  int ldeps;
+  const float* w;                /* (T*B) */
+  const float* pm;               /* (T*B, ldpm) prior mean of every step, or NULL */
+  int ldpm;
+  int kld_mode;
+  const float* sent;             /* (B) or NULL */
+  float pm_scale, prior_var;
+  float* log_ratio;              /* out (B) */
+  float* kl;                     /* out (B) */
+  float* kl_dim;                 /* out (B, ld), optional */
+  int ld;
+  float* step_kl;                /* out (T*B), optional */
+  float* step_ratio;             /* out (T*B), optional */
+} ssc_posterior_rows_desc;
+int ssc_posterior_rows(const ssc_posterior_rows_desc* d, void* stream);
+/* The same for the forward that LAST ran in `workspace` (ssc_train_fwd with this cfg and a batch of these B, R, L): the descriptor
+ * is filled from that forward's mu, lv, z, step weights, pooled prior means (kld_mode 2) and batch->eps, then
+ *   log_w[b] = log_ratio[b] - nll[b]      (nll: the unsmoothed loss of that forward, ssc_train_workspace_view 12)
+ * = log p(x | z, image) + log p(z) - log q(z | x) at the sampled z: the log importance weight of row b.  kl equals the forward's
+ * kld.  log_w, log_ratio and kl (B) are required; kl_dim (B, ld), step_kl (T*B), step_ratio (T*B) may be NULL.  No state of its
+ * own; nothing in the workspace is written. */
+int ssc_train_posterior(const ssc_model_cfg* cfg, const ssc_batch* batch, void* workspace, size_t workspace_bytes, float* log_w,
+                        float* log_ratio, float* kl, float* kl_dim, int ld, float* step_kl, float* step_ratio, void* stream);
+/* read-back, for tests, of what ssc_train_posterior reads besides ssc_train_workspace_view's mu (7), lv (8) and nll (12):
+ * which = 0: the stored z (T,B,Zp), 1: the pooled prior means (T,B,Dp) of kld_mode 2 (else 0), 2: the step weights w (T,B).
+ * Returns pointer into the workspace (and its ld) or 0. */
+void* ssc_train_posterior_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
+
+/* ------------------------------------------------------------------------------------------------
  * Stochastic beam search (GumbelSampler driving BeamSearch._search, var_updown/var_updown/modules/beam_search.py:294-432,
  * :592-768; Kool et al. 2019): `beam` = k distinct captions per batch entry, sampled without replacement with sequence-level
  * probabilities.  lp = the untempered log_softmax of a row's logits, lpT = log_softmax(logits / T) (= lp at T = 1);

@@ -41,6 +41,11 @@ parser.add_argument("--val-tensors", default="",
 parser.add_argument("--val-every", type=int, default=1000, help="with --val-tensors: validate every K iterations and at the last one")
 parser.add_argument("--val-samples", type=int, default=1, help="with --val-tensors: latent samples per caption")
 parser.add_argument("--val-images", type=int, default=0, help="with --val-tensors: score the first M images (0: all)")
+# (absent from the namespace unless given, as --reset-optimizer: off, and today's output unchanged)
+parser.add_argument("--val-posterior-samples", type=int, default=argparse.SUPPRESS,
+                    help="with --val-tensors: also score the held-out captions under the POSTERIOR branch with K noise draws each "
+                         "(UpDownCaptioner.posterior_score_captions) and append val_elbo_nll_per_token, val_iwae_nll_per_token, "
+                         "val_kl_per_token, val_active_units; 0: off")
 parser.add_argument("--serialization-dir", default="checkpoints/experiment")
 parser.add_argument("--checkpoint-every", default=10000, type=int)
 parser.add_argument("--start-from-checkpoint", default="")
@@ -105,6 +110,31 @@ def validate(model, val, n_images, n_samples, seed, iteration, device):
             "val_marginal_nll_per_token": s["marginal_nll_per_token"], "val_top1": s["top1"]}
 
 
+POSTERIOR_TAG = 0x706F7374   # keeps the posterior pass's noise apart from the prior pass's of the same (seed, iteration)
+
+
+def validate_posterior(model, val, n_images, n_samples, seed, iteration, device):
+    """ELBO, importance-weighted bound and KL diagnostics of the captions of `val` under the posterior branch of the model as it
+    stands.  As validate(): a generator of this pass's own seeded by (seed, iteration) plus a tag, the model's mode left alone, a
+    forward on a workspace of its own - a run with it trains exactly as the same run without it."""
+    from ssc_runtime.inference import PosteriorScores
+    gen = torch.Generator(device=device)
+    gen.manual_seed(((int(seed) * 1000003 + int(iteration)) * 1000003 + POSTERIOR_TAG) % (2 ** 63))
+    Z = model.z_space
+    parts = []
+    for lo in range(0, n_images, VAL_IMAGES_PER_CALL):
+        hi = min(lo + VAL_IMAGES_PER_CALL, n_images)
+        caps = val.caps[lo:hi]
+        eps = torch.randn(caps.size(1) + 1, (hi - lo) * n_samples, Z, device=device, generator=gen)
+        feats = val.feats[lo:hi].to(device)
+        obj = val.obj[lo:hi, : feats.size(1)].to(device) if val.obj is not None else None
+        parts.append(model.posterior_score_captions(feats, caps, sentiment=val.senti[lo:hi, 0].to(device), obj_atts=obj,
+                                                    n_samples=n_samples, eps=eps))
+    s = PosteriorScores.concat(parts).summary()
+    return {"val_elbo_nll_per_token": s["elbo_nll_per_token"], "val_iwae_nll_per_token": s["iwae_nll_per_token"],
+            "val_kl_per_token": s["kl_per_token"], "val_active_units": s["active_units"]}
+
+
 def scst_sampler(args):
     """The word sampler the --scst-sampler / --scst-temperature / --scst-top-k / --scst-top-p flags describe."""
     from ssc_runtime import sampling
@@ -139,6 +169,9 @@ def main():
                          "other ranks' gradient exchange; train on several GPUs with --skip-validation and score checkpoints apart")
     if validating and (_A.val_samples < 1 or _A.val_images < 0):
         raise SystemExit("--val-samples must be at least 1 and --val-images at least 0")
+    posterior_samples = getattr(_A, "val_posterior_samples", 0)
+    if posterior_samples < 0:
+        raise SystemExit("--val-posterior-samples must be at least 0")
     if -1 in _A.gpu_ids:
         raise SystemExit("--gpu-ids -1 (CPU) is not available: this build has no CPU path")
     gpu = _A.gpu_ids[local % len(_A.gpu_ids)]
@@ -291,7 +324,10 @@ def main():
         last = iteration == _C.OPTIM.NUM_ITERATIONS or (_A.stop_after and iteration == _A.stop_after)
         if val is not None and rank == 0 and (last or (_A.val_every > 0 and iteration % _A.val_every == 0)):
             rec = {"iteration": iteration}
-            rec.update(validate(model, val, min(_A.val_images or len(val), len(val)), _A.val_samples, _C.RANDOM_SEED, iteration, device))
+            n_val = min(_A.val_images or len(val), len(val))
+            rec.update(validate(model, val, n_val, _A.val_samples, _C.RANDOM_SEED, iteration, device))
+            if posterior_samples > 0:
+                rec.update(validate_posterior(model, val, n_val, posterior_samples, _C.RANDOM_SEED, iteration, device))
             log.write(json.dumps(rec) + "\n")
             log.flush()
         if rank == 0 and iteration % _A.checkpoint_every == 0:

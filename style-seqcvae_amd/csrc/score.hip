@@ -9,6 +9,9 @@
 // then the waves in index order): no float atomics, the same bits on every run.  The step log-prob is formed as
 // (x_target - max) - log(sum): the first difference is exact, so logits of magnitude 1e4 lose nothing to the subtraction.
 // ssc_decode_score's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
+//
+// ssc_posterior_rows scores the POSTERIOR branch of a train forward: per caption row the log-density ratio log p(z) - log q(z | x) at
+// the sampled z and the training KL, split by latent dimension and by step.
 #include <math.h>
 
 #include "decode_loop.h"
@@ -164,7 +167,97 @@ bool score_desc_ok(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
   return score_dims_ok(cfg, d) && ssc_decode_inputs_ok(cfg, d, d->max_len) && d->targets && d->log_probs && d->n_tokens;
 }
 
+// ---- posterior rows (include/ssc.h: ssc_posterior_rows) ------------------------------------------------------------------------------
+// One wave per caption row b, lanes over the latent dimensions j = lane + 64 k (k < NJ), the steps in sequence.  Each lane keeps the
+// KL of its NJ dimensions summed over t (kl_dim) and one running sum of its log-ratio terms; the row scalars are ONE butterfly of
+// those at the end (the step outputs, where asked for, a butterfly per step): a fixed order, no atomics.  A step with w == 0 is
+// skipped before any of its rows is read.
+constexpr int POST_MAX_NJ = 8;
+
+template <int NJ>
+__global__ __launch_bounds__(64) void posterior_rows_kernel(const ssc_posterior_rows_desc d) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int Z = d.Z, B = d.B;
+  const float pv = d.prior_var, lpv = logf(pv), pvk = pv + 0.00001f;   // (pvk: the training KL's denominator, as latent_fwd_kernel)
+  const float pm_row = d.sent ? d.pm_scale * d.sent[b] : 0.f;
+  const bool steps = d.step_kl || d.step_ratio;   // (wave-uniform)
+  float kd[NJ];
+#pragma unroll
+  for (int k = 0; k < NJ; ++k) kd[k] = 0.f;
+  float racc = 0.f;
+  for (int t = 0; t < d.T; ++t) {
+    const size_t r = (size_t)t * B + b;
+    const float w = d.w[r];
+    if (w == 0.f) {   // (wave-uniform)
+      if (lane == 0) {
+        if (d.step_kl) d.step_kl[r] = 0.f;
+        if (d.step_ratio) d.step_ratio[r] = 0.f;
+      }
+      continue;
+    }
+    float sk = 0.f, sr = 0.f;
+#pragma unroll
+    for (int k = 0; k < NJ; ++k) {
+      const int j = lane + 64 * k;
+      if (j < Z) {
+        const float m = d.mu[r * d.ldz + j], l = d.lv[r * d.ldz + j], zz = d.z[r * d.ldz + j];
+        const float e = d.eps[r * d.ldeps + j];
+        const float pm = d.pm ? d.pm[r * d.ldpm + j] : pm_row;
+        const float dz = zz - pm;
+        const float rt = 0.5f * (e * e + l - lpv - dz * dz / pv);
+        float kt;
+        if (d.kld_mode == 0) {
+          kt = -0.5f * (1.f + l - m * m - expf(l));
+        } else {
+          const float dm = m - pm;
+          kt = -0.5f * (1.f + l - lpv - (dm * dm + expf(l)) / pvk);
+        }
+        kd[k] += w * kt;
+        racc += w * rt;
+        sk += kt;
+        sr += rt;
+      }
+    }
+    if (steps) {
+      sk = ssc_wave_sum(sk);
+      sr = ssc_wave_sum(sr);
+      if (lane == 0) {
+        if (d.step_kl) d.step_kl[r] = w * sk;
+        if (d.step_ratio) d.step_ratio[r] = w * sr;
+      }
+    }
+  }
+  float kacc = 0.f;
+#pragma unroll
+  for (int k = 0; k < NJ; ++k) {
+    const int j = lane + 64 * k;
+    if (d.kl_dim && j < Z) d.kl_dim[(size_t)b * d.ld + j] = kd[k];
+    kacc += kd[k];
+  }
+  kacc = ssc_wave_sum(kacc);
+  racc = ssc_wave_sum(racc);
+  if (lane == 0) {
+    d.kl[b] = kacc;
+    d.log_ratio[b] = racc;
+  }
+}
+
 }  // namespace
+
+extern "C" int ssc_posterior_rows(const ssc_posterior_rows_desc* d, void* stream) {
+  if (!d || !d->mu || !d->lv || !d->z || !d->eps || !d->w || !d->log_ratio || !d->kl) return SSC_EINVAL;
+  if (d->T <= 0 || d->B <= 0 || d->Z <= 0 || d->Z > 64 * POST_MAX_NJ || d->ldz < d->Z || d->ldeps < d->Z) return SSC_EINVAL;
+  if (!(d->prior_var > 0.f) || d->kld_mode < 0 || d->kld_mode > 2) return SSC_EINVAL;   // (NaN included)
+  if ((d->kld_mode == 2 && !d->pm) || (d->pm && d->ldpm < d->Z) || (d->kl_dim && d->ld < d->Z)) return SSC_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const int nj = ssc_cdiv(d->Z, 64);
+  if (nj <= 1) SSC_LAUNCH(posterior_rows_kernel<1>, dim3(d->B), dim3(64), 0, st, *d);
+  else if (nj == 2) SSC_LAUNCH(posterior_rows_kernel<2>, dim3(d->B), dim3(64), 0, st, *d);
+  else if (nj <= 4) SSC_LAUNCH(posterior_rows_kernel<4>, dim3(d->B), dim3(64), 0, st, *d);
+  else SSC_LAUNCH(posterior_rows_kernel<POST_MAX_NJ>, dim3(d->B), dim3(64), 0, st, *d);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
 
 extern "C" int ssc_score_rows(const float* logits, int ld, int rows, int V, const int64_t* target, const int64_t* last_target,
                               int end_index, float* row_lp, float* lp_out, int* rank_out, void* stream) {

@@ -621,6 +621,53 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
   return SSC_OK;
 }
 
+// ---- posterior scoring of the forward that last ran in this workspace (include/ssc.h: ssc_train_posterior) ------------------------------
+namespace {
+__global__ void posterior_log_w_kernel(const float* __restrict__ log_ratio, const float* __restrict__ nll, int B, float* __restrict__ log_w) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) log_w[b] = log_ratio[b] - nll[b];
+}
+}  // namespace
+
+extern "C" void* ssc_train_posterior_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld) {
+  if (!cfg || !workspace || B <= 0 || R <= 0 || L <= 0) return nullptr;
+  const Layout l = make_layout(cfg, B, R, L);
+  float* w = (float*)workspace;
+  int dummy;
+  if (!ld) ld = &dummy;
+  switch (which) {
+    case 0: *ld = l.Zp; return w + l.z;
+    case 1: *ld = l.Dp; return l.D ? w + l.pool : nullptr;
+    case 2: *ld = l.B; return w + l.w;
+    default: return nullptr;
+  }
+}
+
+extern "C" int ssc_train_posterior(const ssc_model_cfg* cfg, const ssc_batch* bt, void* workspace, size_t workspace_bytes, float* log_w,
+                                   float* log_ratio, float* kl, float* kl_dim, int ld, float* step_kl, float* step_ratio, void* stream) {
+  if (!cfg || !bt || !workspace || !log_w || !log_ratio || !kl) return SSC_EINVAL;
+  if (cfg->V <= 1 || cfg->E <= 0 || cfg->H <= 0 || cfg->A <= 0 || cfg->F <= 0 || cfg->Z <= 0) return SSC_EINVAL;
+  if (bt->B <= 0 || bt->R <= 0 || bt->L <= 0 || !bt->eps) return SSC_EINVAL;
+  if (cfg->pm_scale != 0.f && !bt->sentiment) return SSC_EINVAL;
+  const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
+  if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
+  const float* W = (const float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  ssc_posterior_rows_desc d{};
+  d.T = l.T; d.B = l.B; d.Z = l.Z;
+  d.mu = W + l.mu; d.lv = W + l.lv; d.z = W + l.z; d.ldz = l.Zp;
+  d.eps = bt->eps; d.ldeps = l.Z;
+  d.w = W + l.w;
+  if (l.D) { d.pm = W + l.pool; d.ldpm = l.Dp; }   // (kld_mode 2: the pooled prior mean of every step)
+  d.kld_mode = cfg->kld_mode; d.sent = cfg->pm_scale != 0.f ? bt->sentiment : nullptr;
+  d.pm_scale = cfg->pm_scale; d.prior_var = cfg->prior_var;
+  d.log_ratio = log_ratio; d.kl = kl; d.kl_dim = kl_dim; d.ld = ld; d.step_kl = step_kl; d.step_ratio = step_ratio;
+  SSC_TRY(ssc_posterior_rows(&d, stream));
+  SSC_LAUNCH(posterior_log_w_kernel, dim3(ssc_cdiv(l.B, 256)), dim3(256), 0, st, log_ratio, W + l.nll, l.B, log_w);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
 namespace {
 // ---- vocabulary sizes that are no multiple of 4 ------------------------------------------------------------------------------
 // The two backward products of the vocabulary head that run over V as a k- or m-extent (d(hidden) = dlogits . W over k = V;

@@ -308,6 +308,9 @@ class TrainEngine:
         self._ws_key = None
         self._cfg = dims.cfg()
         self._keep = None
+        self._post_ws = None          # posterior_forward's own workspace: the training forward's activations are never overwritten
+        self._post_ws_key = None
+        self._post = None
         self._scratch = torch.zeros(1024 + 16, dtype=torch.float32, device=self.device)
         names = list(shapes)
         self.decoder_names = [n for n in names if n.startswith(P_DEC)]
@@ -401,6 +404,51 @@ class TrainEngine:
         self._keep = (bt, feats, caps, sent, eps)
         self.fwd_version += 1
         return loss, kld
+
+    def posterior_forward(self, feats, caps, sentiment, eps, obj_atts=None):
+        """The posterior branch's view of given captions (include/ssc.h: ssc_train_posterior) -> (nll (B,), kld (B,), log_ratio (B,),
+        log_w (B,), kl_dim (B, Z), step_kl (T, B), step_ratio (T, B)): one ssc_train_fwd with label_smoothing 0 on a workspace of
+        this method's own and a copy of the cfg, then the log-density ratio log p(z) - log q(z | x) at the sampled z, the KL per
+        latent dimension and per step, and log_w = log_ratio - nll.  Nothing a later backward() reads is touched - _keep, the
+        training workspace, the cfg's label_smoothing, fwd_version: backward() after this call still differentiates the forward
+        the caller ran before it.  posterior_view(which) reads this forward's activations."""
+        cfg = _lib.ModelCfg.from_buffer_copy(self._cfg)
+        cfg.label_smoothing = 0.0
+        bt, keep = self._batch(feats, caps, sentiment, eps, obj_atts)
+        B, T, Z = bt.B, bt.L + 1, self.dims.Z
+        key = (B, bt.R, bt.L)
+        if self._post_ws_key != key:
+            nbytes = self.lib.ssc_train_workspace_bytes(C.byref(cfg), B, bt.R, bt.L)
+            self._post_ws = None   # (the old one is released before the new one is taken)
+            self._post_ws = torch.empty(nbytes // 4 + 64, dtype=torch.float32, device=self.device)
+            self._post_ws_key = key
+        ws = self._post_ws
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=self.device)
+        nll, kld, log_ratio, log_w, kl = new(B), new(B), new(B), new(B), new(B)
+        kl_dim, step_kl, step_ratio = new(B, Z), new(T, B), new(T, B)
+        p = self.params.c_struct()
+        st = _lib.stream_ptr()
+        self.lib.ssc_train_fwd(C.byref(cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(nll), _lib.ptr(kld), st)
+        self.lib.ssc_train_posterior(C.byref(cfg), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(log_w), _lib.ptr(log_ratio),
+                                     _lib.ptr(kl), _lib.ptr(kl_dim), Z, _lib.ptr(step_kl), _lib.ptr(step_ratio), st)
+        self._post = (bt, feats, caps, keep, eps, cfg)
+        return nll, kld, log_ratio, log_w, kl_dim, step_kl, step_ratio
+
+    def posterior_view(self, which):
+        """Activations of the last posterior_forward (test hook): "z" (T, B, Z) as the forward stored it, "pm" (T, B, Z) the pooled
+        prior means of kld_mode 2, "w" (T, B) the step weights (ssc_train_posterior_view); an int: workspace_view's numbering."""
+        bt, cfg, ws = self._post[0], self._post[5], self._post_ws
+        if isinstance(which, int):
+            return self._view(ws, bt, cfg, which)
+        ld = C.c_int(0)
+        p = self.lib.ssc_train_posterior_view(C.byref(cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), {"z": 0, "pm": 1, "w": 2}[which], C.byref(ld))
+        if not p:
+            raise ValueError(which)
+        off = (p - ws.data_ptr()) // 4
+        T, B = bt.L + 1, bt.B
+        if which == "w":
+            return ws[off:off + T * B].view(T, B)
+        return ws[off:off + T * B * ld.value].view(T, B, ld.value)[:, :, :self.dims.Z]
 
     # gradient ranges that are final after each backward phase (flat layout order: emb | att LSTM | attention |
     # enc LSTM | fc | output head | dec LSTM)
@@ -581,9 +629,11 @@ class TrainEngine:
     def workspace_view(self, which, T1=None):
         """Saved activations of the last forward (test hook; see ssc_train_workspace_view)."""
         bt = self._keep[0]
-        ws = self._workspace(bt.B, bt.R, bt.L)
+        return self._view(self._workspace(bt.B, bt.R, bt.L), bt, self._cfg, which)
+
+    def _view(self, ws, bt, cfg, which):
         ld = C.c_int(0)
-        p = self.lib.ssc_train_workspace_view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), which, C.byref(ld))
+        p = self.lib.ssc_train_workspace_view(C.byref(cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), which, C.byref(ld))
         off = (p - ws.data_ptr()) // 4
         T, B = bt.L + 1, bt.B
         d = self.dims

@@ -9,10 +9,11 @@ per-call result given the same per-row noise.
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
+from . import lib as _lib
 from .decode import DecodeEngine
 from .decoding import select_best_beam_simple_batched
 
@@ -299,3 +300,158 @@ def score_captions(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     return CaptionScores(log_probs=lps, n_tokens=ntok, marginal=torch.logsumexp(lps, -1) - math.log(n_samples),
                          token_lp=tlp.view(nimg, Cc, n_samples, Lc) if tlp is not None else None,
                          token_rank=trk.view(nimg, Cc, n_samples, Lc) if trk is not None else None)
+
+
+# ---- posterior scoring: ELBO and the importance-weighted bound -------------------------------------------------------------------------
+def plan_posterior_chunks(n_words, n_samples: int, max_rows: int = 256) -> "List[Tuple[List[int], int]]":
+    """The forwards of one posterior scoring call.  n_words: the words of every caption slot in slot order (image-major, flat; 0: an
+    absent slot, which is dropped).  -> [(slots, length)]: the slot numbers of a chunk, in order, and its longest caption; a chunk
+    runs len(slots) * n_samples rows (slot-major, then sample), at most max_rows; the samples of a caption are never split.  Pure."""
+    if n_samples < 1:
+        raise ValueError("n_samples must be at least 1")
+    if n_samples > max_rows:
+        raise ValueError(f"n_samples ({n_samples}) exceeds max_rows ({max_rows}): the samples of a caption stay in one forward")
+    per = max_rows // n_samples
+    present = [i for i, n in enumerate(n_words) if int(n) > 0]
+    chunks = []
+    for lo in range(0, len(present), per):
+        slots = present[lo: lo + per]
+        chunks.append((slots, max(int(n_words[i]) for i in slots)))
+    return chunks
+
+
+@dataclass
+class PosteriorScores:
+    """What posterior_score_captions returns (K = n_samples draws z^k ~ q(z | x) per caption; include/ssc.h: ssc_train_posterior).
+    (nimg, C, K): log_w = log p(x | z, image) + log p(z) - log q(z | x), nll = -log p(x | z, image), log_ratio = log p(z) - log q(z | x)
+    with p(z) the prior the eval decode samples, kld = the training KL in closed form (SENTIMENT_VAE 0: against N(0, 1) whatever
+    PRIOR_STD is).  (nimg, C): n_tokens (the END included; 0: an absent slot, zeros everywhere), elbo = mean_k log_w, iwae =
+    logsumexp_k log_w - log K (>= elbo; Burda et al. 2016), ess = exp(2 lse(log_w) - lse(2 log_w)) in [1, K].  kl_dim (Z) float64: the
+    training KL per latent dimension summed over every live (row, step), n_steps of them.  token_kl / token_ratio (nimg, C, K, L + 1)
+    with want_steps: the training KL / the log-ratio of every step (0 after the caption's end)."""
+    log_w: torch.Tensor
+    nll: torch.Tensor
+    log_ratio: torch.Tensor
+    kld: torch.Tensor
+    n_tokens: torch.Tensor
+    elbo: torch.Tensor
+    iwae: torch.Tensor
+    ess: torch.Tensor
+    kl_dim: torch.Tensor
+    n_steps: int
+    token_kl: Optional[torch.Tensor] = None
+    token_ratio: Optional[torch.Tensor] = None
+
+    @staticmethod
+    def reduce(log_w: torch.Tensor, present: torch.Tensor):
+        """(elbo, iwae, ess) over the last axis of log_w; zeros where `present` is False."""
+        K = log_w.size(-1)
+        lse = torch.logsumexp(log_w, -1)
+        elbo, iwae = log_w.mean(-1), lse - math.log(K)
+        ess = torch.exp(2 * lse - torch.logsumexp(2 * log_w, -1))
+        zero = torch.zeros_like(elbo)
+        return torch.where(present, elbo, zero), torch.where(present, iwae, zero), torch.where(present, ess, zero)
+
+    @staticmethod
+    def concat(parts: "List[PosteriorScores]") -> "PosteriorScores":
+        """The scores of several calls over different images as one (token arrays padded to the longest call with 0)."""
+        def cat(name):
+            ts = [getattr(p, name) for p in parts]
+            if any(t is None for t in ts):
+                return None
+            L = max(t.size(-1) for t in ts)
+            return torch.cat([torch.nn.functional.pad(t, (0, L - t.size(-1))) for t in ts])
+        simple = {n: torch.cat([getattr(p, n) for p in parts]) for n in ("log_w", "nll", "log_ratio", "kld", "n_tokens", "elbo", "iwae", "ess")}
+        return PosteriorScores(kl_dim=sum(p.kl_dim for p in parts), n_steps=sum(p.n_steps for p in parts), token_kl=cat("token_kl"),
+                               token_ratio=cat("token_ratio"), **simple)
+
+    def summary(self, active_threshold: float = 0.01) -> Dict[str, float]:
+        """Per scored token (n = sum n_tokens): elbo_nll_per_token = -sum_c elbo / n, iwae_nll_per_token = -sum_c iwae / n (<= the
+        former), recon_nll_per_token = sum_c mean_k nll / n, kl_per_token = sum_c mean_k kld / n (closed form, the training KL),
+        kl_mc_per_token = -sum_c mean_k log_ratio / n (one-sample estimate against the decode prior; elbo_nll = recon_nll + kl_mc);
+        ess_mean over the present captions; active_units = #{j: kl_dim[j] / n_steps > active_threshold nats}."""
+        n = float(self.n_tokens.sum().item())
+        if n == 0:
+            raise ValueError("no caption was scored")
+        present = self.n_tokens > 0
+        per = lambda t: float(t.double().mean(-1).sum().item()) / n
+        return {"n_captions": int(present.sum().item()), "n_tokens": int(n),
+                "elbo_nll_per_token": -float(self.elbo.double().sum().item()) / n,
+                "iwae_nll_per_token": -float(self.iwae.double().sum().item()) / n,
+                "recon_nll_per_token": per(self.nll), "kl_per_token": per(self.kld), "kl_mc_per_token": -per(self.log_ratio),
+                "ess_mean": float(self.ess.double()[present].mean().item()),
+                "active_units": int((self.kl_dim.double() / max(self.n_steps, 1) > active_threshold).sum().item())}
+
+
+def posterior_score_captions(eng, feats: torch.Tensor, sentiment: Optional[torch.Tensor], captions: torch.Tensor, n_samples: int, *,
+                             eps: Optional[torch.Tensor] = None, obj_means: Optional[torch.Tensor] = None, pad_index: int = 0,
+                             max_rows: int = 256, want_steps: bool = False) -> PosteriorScores:
+    """Given captions under the POSTERIOR branch of the model: eng a TrainEngine, feats (nimg, R, F), sentiment (nimg,) or None,
+    captions (nimg, C, L) int64 in the "padded" layout of score_captions (the words are those before the first pad_index, what
+    follows is set to pad; a slot that starts with pad_index is absent: zeros, n_tokens 0, not run).  Every present caption is run
+    through TrainEngine.posterior_forward under n_samples noise draws; the rows (image, caption, sample) of the present captions are
+    chunked into forwards of at most max_rows rows (plan_posterior_chunks), each trimmed to its longest caption.  The per-row image
+    terms are recomputed for every row of an image.  Ids outside [0, V) raise ValueError before anything is launched.
+    eps: optional explicit noise (L + 1, nimg * C * n_samples, Z) over ALL slots, rows (image, caption, sample); default: a
+    generator of this call's own, seeded by ONE draw of the global CPU generator.  obj_means (nimg, R, Z): SENTIMENT_VAE = 2 only."""
+    if captions.dim() != 3 or captions.size(0) != feats.size(0) or captions.size(2) < 1:
+        raise ValueError(f"captions must be (nimg, C, L) with nimg = {feats.size(0)}, got {tuple(captions.shape)}")
+    d = eng.dims
+    nimg, Cc, L0 = captions.shape
+    K = int(n_samples)
+    caps = captions.to("cpu", torch.int64)
+    is_pad = caps == pad_index
+    length = torch.where(is_pad.any(-1), is_pad.float().argmax(-1), torch.full((nimg, Cc), L0))   # words before the first pad
+    caps = torch.where(torch.arange(L0).view(1, 1, -1) >= length.unsqueeze(-1), torch.full_like(caps, pad_index), caps)
+    chunks = plan_posterior_chunks(length.view(-1).tolist(), K, max_rows)
+    if not chunks:
+        raise ValueError("every caption slot is absent")
+    words = caps[length > 0]
+    bad = (words < 0) | (words >= d.V)
+    if bool(bad.any()):
+        raise ValueError(f"caption ids outside the vocabulary [0, {d.V}): e.g. {int(words[bad][0])}")
+    dev = feats.device
+    G = nimg * Cc * K
+    T0 = L0 + 1
+    if eps is not None:
+        if tuple(eps.shape) != (T0, G, d.Z):
+            raise ValueError(f"eps must be (L + 1, nimg * C * n_samples, Z) = {(T0, G, d.Z)}, got {tuple(eps.shape)}")
+        eps = eps.to(dev, torch.float32)
+    else:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        gen = torch.Generator(device=dev)
+        gen.manual_seed(seed)
+        eps = torch.randn(T0, G, d.Z, device=dev, generator=gen)
+    flat = {n: torch.zeros(nimg * Cc, K, device=dev) for n in ("log_w", "nll", "log_ratio", "kld")}
+    tok = {n: torch.zeros(nimg * Cc, K, T0, device=dev) for n in (("token_kl", "token_ratio") if want_steps else ())}
+    kl_dim = torch.zeros(d.Z, dtype=torch.float64)
+    col = torch.empty(d.Z, device=dev)
+    caps_dev = caps.view(nimg * Cc, L0).to(dev)
+    for slots, Lc in chunks:
+        sl = torch.tensor(slots, device=dev)
+        rows = (sl.view(-1, 1) * K + torch.arange(K, device=dev).view(1, -1)).reshape(-1)   # rows of eps: (slot, sample)
+        img = (sl // Cc).repeat_interleave(K)
+        n = rows.numel()
+        out = eng.posterior_forward(feats.index_select(0, img).to(torch.float32).contiguous(),
+                                    caps_dev.index_select(0, sl).repeat_interleave(K, 0)[:, :Lc].contiguous(),
+                                    sentiment.reshape(nimg).to(dev, torch.float32).index_select(0, img) if sentiment is not None else None,
+                                    eps[: Lc + 1].index_select(1, rows).contiguous(),
+                                    obj_means.to(dev, torch.float32).index_select(0, img) if obj_means is not None else None)
+        nll, kld, log_ratio, log_w, kd, step_kl, step_ratio = out
+        for name, v in (("log_w", log_w), ("nll", nll), ("log_ratio", log_ratio), ("kld", kld)):
+            flat[name][sl] = v.view(-1, K)
+        if want_steps:
+            tok["token_kl"][sl, :, : Lc + 1] = step_kl.t().reshape(-1, K, Lc + 1)
+            tok["token_ratio"][sl, :, : Lc + 1] = step_ratio.t().reshape(-1, K, Lc + 1)
+        # the per-dimension total of the chunk's rows on the device, the chunks summed on the host in float64
+        eng.lib.ssc_colsum(_lib.ptr(kd), d.Z, n, d.Z, None, _lib.ptr(col), 1, 0, _lib.stream_ptr())
+        kl_dim += col.double().cpu()
+    n_tokens = torch.where(length > 0, length + 1, torch.zeros_like(length)).to(dev)
+    log_w = flat["log_w"].view(nimg, Cc, K)
+    elbo, iwae, ess = PosteriorScores.reduce(log_w, n_tokens > 0)
+    shape4 = lambda t: t.view(nimg, Cc, K, T0)
+    return PosteriorScores(log_w=log_w, nll=flat["nll"].view(nimg, Cc, K), log_ratio=flat["log_ratio"].view(nimg, Cc, K),
+                           kld=flat["kld"].view(nimg, Cc, K), n_tokens=n_tokens, elbo=elbo, iwae=iwae, ess=ess, kl_dim=kl_dim,
+                           n_steps=int(n_tokens.sum().item()) * K,
+                           token_kl=shape4(tok["token_kl"]) if want_steps else None,
+                           token_ratio=shape4(tok["token_ratio"]) if want_steps else None)

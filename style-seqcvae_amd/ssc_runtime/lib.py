@@ -145,6 +145,13 @@ class ScoreDesc(C.Structure):
                 ("eps0", vp), ("eps", vp), ("log_probs", vp), ("token_lp", vp), ("token_rank", vp), ("n_tokens", vp)]
 
 
+class PosteriorRowsDesc(C.Structure):
+    _fields_ = [("T", C.c_int), ("B", C.c_int), ("Z", C.c_int), ("mu", vp), ("lv", vp), ("z", vp), ("ldz", C.c_int), ("eps", vp),
+                ("ldeps", C.c_int), ("w", vp), ("pm", vp), ("ldpm", C.c_int), ("kld_mode", C.c_int), ("sent", vp),
+                ("pm_scale", C.c_float), ("prior_var", C.c_float), ("log_ratio", vp), ("kl", vp), ("kl_dim", vp), ("ld", C.c_int),
+                ("step_kl", vp), ("step_ratio", vp)]
+
+
 class GumbelDesc(C.Structure):
     _fields_ = [("temperature", C.c_float), ("seed", C.c_uint64)]
 
@@ -280,6 +287,9 @@ SYMBOLS = {
     "ssc_score_rows": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_score_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(ScoreDesc)]),
     "ssc_decode_score": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), vp, _sz, vp]),
+    "ssc_posterior_rows": (_i, [C.POINTER(PosteriorRowsDesc), vp]),
+    "ssc_train_posterior": (_i, [C.POINTER(ModelCfg), C.POINTER(Batch), vp, _sz, vp, vp, vp, vp, _i, vp, vp, vp]),
+    "ssc_train_posterior_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
     "ssc_beam_first_gumbel": (_i, [C.POINTER(BeamDesc), C.POINTER(GumbelDesc), vp, vp]),
     "ssc_beam_step_gumbel": (_i, [C.POINTER(BeamDesc), C.POINTER(GumbelDesc), vp, vp, vp]),
     "ssc_decode_stochastic_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),

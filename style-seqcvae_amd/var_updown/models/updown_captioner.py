@@ -388,6 +388,26 @@ class UpDownCaptioner(nn.Module):
                                   n_samples or self.n_z_samples, self._boundary_index, layout, eps_steps=eps_steps, obj_means=obj_means,
                                   want_tokens=want_tokens, want_ranks=want_ranks)
 
+    def posterior_score_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, obj_atts=None,
+                                 n_samples: int = 1, eps=None, want_steps: bool = False):
+        """The given captions under the POSTERIOR branch of the model as it stands (encoder LSTM, fc_mean, fc_log_var): the log
+        importance weights log p(x | z, image) + log p(z) - log q(z | x) of n_samples draws z ~ q(z | x) per caption, the ELBO, the
+        importance-weighted bound, and the training KL per caption, per step and per latent dimension.  image_features (B, R, F),
+        caption_tokens (B, L) or (B, C, L) int64 in the training layout (0-padded, no boundary tokens); obj_atts as in forward()
+        (SENTIMENT_VAE = 2).  eps: the caller's own noise (L + 1, B * C * n_samples, Z), rows (image, caption, sample); default: a
+        generator of the call's own, seeded by one draw of the global CPU generator.  No autograd; the parameters are read as they
+        are at the call; the mode (train / eval) is left as it is and plays no part; a backward() of an earlier training forward is
+        not disturbed.  -> ssc_runtime.inference.PosteriorScores."""
+        from ssc_runtime.inference import posterior_score_captions
+        eng = self._engine()
+        B, R, _ = image_features.shape
+        caps = caption_tokens if caption_tokens.dim() == 3 else caption_tokens.unsqueeze(1)
+        obj_means = self._obj_means(obj_atts, B, R)
+        sent = sentiment.reshape(B).to(eng.device, torch.float32) if sentiment is not None else None
+        with torch.no_grad():
+            return posterior_score_captions(eng, image_features.to(eng.device, torch.float32), sent, caps, n_samples, eps=eps,
+                                            obj_means=obj_means, pad_index=self._pad_index, want_steps=want_steps)
+
     def scst_step(self, image_features: torch.Tensor, image_ids, sentiment=None, obj_atts=None, *, references, lr, seed,
                   kld_weight: float = 750.0, momentum: float = 0.9, weight_decay: float = 0.001, max_norm: float = 12.5,
                   decoder_frozen: bool = False, group=None, n_samples: int = 5, sampler=None, baseline: str = "loo",
