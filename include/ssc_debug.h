@@ -35,6 +35,8 @@ int ssc_prof_loop_ms(float* fwd_loop_ms, float* bwd_loop_ms);
  *   "f16_npw"     producer waves of the 2xFP16 kernel: 4 (default: two workgroups per CU) | 8     (SSC_F16_NPW)
  *   "store_wt"    write-through (sc1) output stores of the wave-specialised kernels (1)            (SSC_STORE_WT)
  *   "tile_gm"     tile rows per group of the XCD-aware tile order (8; 0 = row-major)               (SSC_TILE_GM)
+ *   "stream_nt"   non-temporal loads and stores on data a train step touches once, a bit mask: 2 = the streams of ssc_sgd_step
+ *                 and ssc_sq_norm (default) | 0 = default cache policy; bit-identical results         (SSC_STREAM_NT)
  *   "dw_one_flush"  ssc_train_bwd issues the weight gradients of all phases as one work list (1) | 0 one launch per phase,
  *                 as ssc_train_bwd_phases does                                                     (SSC_DW_ONE_FLUSH)
  *   decode (ssc_decode_step and the beam kernels; every form gives the same captions):

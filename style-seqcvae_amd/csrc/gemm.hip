@@ -2633,6 +2633,7 @@ extern "C" int ssc_set_gemm_mode(int mode) {
 extern int ssc_g_dec_att_table, ssc_g_dec_dedup, ssc_g_beam_reg, ssc_g_dec_ungathered, ssc_g_dec_parts, ssc_g_dec_planes;   // decode.hip
 extern int ssc_g_img_mfma;   // lstm.hip
 extern int ssc_g_dw_one_flush;   // sequence.hip
+extern int ssc_g_stream_nt;      // pointwise.hip
 namespace {
 struct DebugKey { const char* name; int* var; };
 const DebugKey g_debug_keys[] = {
@@ -2649,6 +2650,7 @@ const DebugKey g_debug_keys[] = {
     {"dec_parts", &ssc_g_dec_parts},           // decode: the vocabulary head of a one-state search leaves per-tile records instead of logits (1 | 0)   (SSC_DEC_PARTS)
     {"dec_att_table", &ssc_g_dec_att_table},   // decode: attended-feature term of the decoder gates from a per-image table (1 | 0)   (SSC_DEC_ATT_TABLE)
     {"f16_npw", &g_f16_npw},         // 2xFP16 kernel: producer waves (4 = two workgroups per CU (default) | 8)   (SSC_F16_NPW)
+    {"stream_nt", &ssc_g_stream_nt}, // non-temporal loads and stores on the once-per-step streams, bit mask: 2 = ssc_sgd_step and ssc_sq_norm (default) | 0 off   (SSC_STREAM_NT)
     {"gemm_f16", &g_gemm_f16},       // op-level products (ssc_gemm outside a sequence-level call): 1 = the wave-specialised 128x128 NT form takes the 2xFP16 split (what ssc_model_cfg.gemm_mode 3 selects per call)   (SSC_GEMM_F16)
 };
 }  // namespace

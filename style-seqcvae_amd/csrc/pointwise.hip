@@ -604,6 +604,15 @@ __global__ void fill_kernel(float* __restrict__ p, size_t n, float v) {
 // ---------------------------------------------------------------------------------------------
 // clip + SGD on flat buffers
 // ---------------------------------------------------------------------------------------------
+// NT: the flat gradient / parameter / momentum buffers (0.45 GB each at C2's widths) are touched once per train step - with
+// non-temporal loads and stores they pass the caches by (ssc_g_stream_nt, bit 2; same arithmetic, same order, same bits).
+// C2 train step 8.17 -> 8.09 ms, sgd_kernel 431 -> 395 us, sq_norm_partial_kernel 99 -> 76 us.
+template <bool NT> __device__ __forceinline__ float stream_ld(const float* p) { return NT ? __builtin_nontemporal_load(p) : *p; }
+template <bool NT> __device__ __forceinline__ void stream_st(float* p, float v) {
+  if (NT) __builtin_nontemporal_store(v, p);
+  else *p = v;
+}
+template <bool NT>
 __global__ void sq_norm_partial_kernel(const float* __restrict__ g, size_t n, float* __restrict__ scratch) {
   __shared__ float sh[16];
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -611,15 +620,15 @@ __global__ void sq_norm_partial_kernel(const float* __restrict__ g, size_t n, fl
   float s = 0.f;
   if (ssc_aligned16_dev(g)) {  // 16 B/lane stream over the bulk, scalar tail
     const size_t n4 = n >> 2;
-    const float4* g4 = reinterpret_cast<const float4*>(g);
+    const ssc_f32x4* g4 = reinterpret_cast<const ssc_f32x4*>(g);
     for (size_t k = i; k < n4; k += stride) {
-      float4 v = g4[k];
+      const ssc_f32x4 v = NT ? __builtin_nontemporal_load(&g4[k]) : g4[k];
       s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
     }
-    for (size_t k = (n4 << 2) + i; k < n; k += stride) s += g[k] * g[k];
+    for (size_t k = (n4 << 2) + i; k < n; k += stride) { const float v = stream_ld<NT>(g + k); s += v * v; }
   } else {
     for (; i < n; i += stride) {
-      float v = g[i];
+      float v = stream_ld<NT>(g + i);
       s += v * v;
     }
   }
@@ -635,6 +644,7 @@ __global__ void sq_norm_final_kernel(const float* __restrict__ scratch, int nb, 
   if (threadIdx.x == 0) *out = s;
 }
 
+template <bool NT>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, size_t n,
                            const float* __restrict__ sqnorm, float gscale, float max_norm, float lr, float momentum,
                            float wd, int first) {
@@ -643,11 +653,11 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
-    float pv = p[i];
-    float dd = g[i] * coef + wd * pv;
-    float b = first ? dd : momentum * buf[i] + dd;
-    buf[i] = b;
-    p[i] = pv - lr * b;
+    float pv = stream_ld<NT>(p + i);
+    float dd = stream_ld<NT>(g + i) * coef + wd * pv;
+    float b = first ? dd : momentum * stream_ld<NT>(buf + i) + dd;
+    stream_st<NT>(buf + i, b);
+    stream_st<NT>(p + i, pv - lr * b);
   }
 }
 
@@ -973,10 +983,14 @@ extern "C" int ssc_fill(float* p, size_t n, float v, void* stream) {
   return SSC_OK;
 }
 
+// Non-temporal policy of the once-per-step streams, a bit mask: 2 = ssc_sgd_step and ssc_sq_norm.  (Bit 1, the weight loads of
+// the minibatch gate products, measured slower and is not built: DESIGN.md 6.)  Both policies are compiled forms chosen here.
+int ssc_g_stream_nt = ssc_env_int("SSC_STREAM_NT", 2);
 extern "C" int ssc_sq_norm(const float* g, size_t n, float* scratch, float* out, void* stream) {
   if (!g || !scratch || !out) return SSC_EINVAL;
   const int nb = 1024;
-  SSC_LAUNCH(sq_norm_partial_kernel, dim3(nb), dim3(256), 0, S(stream), g, n, scratch);
+  const auto partial = (ssc_g_stream_nt & 2) ? sq_norm_partial_kernel<true> : sq_norm_partial_kernel<false>;
+  SSC_LAUNCH(partial, dim3(nb), dim3(256), 0, S(stream), g, n, scratch);
   SSC_CHECK_LAUNCH();
   SSC_LAUNCH(sq_norm_final_kernel, dim3(1), dim3(256), 0, S(stream), scratch, nb, out);
   SSC_CHECK_LAUNCH();
@@ -989,7 +1003,8 @@ extern "C" int ssc_sgd_step(float* p, const float* g, float* buf, size_t n, cons
   if (n == 0) return SSC_OK;
   size_t blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  SSC_LAUNCH(sgd_kernel, dim3((unsigned)blocks), dim3(256), 0, S(stream), p, g, buf, n, sqnorm, gscale, max_norm,
+  const auto sgd = (ssc_g_stream_nt & 2) ? sgd_kernel<true> : sgd_kernel<false>;
+  SSC_LAUNCH(sgd, dim3((unsigned)blocks), dim3(256), 0, S(stream), p, g, buf, n, sqnorm, gscale, max_norm,
                      lr, momentum, weight_decay, first);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
