@@ -317,6 +317,42 @@ typedef struct {
 } ssc_latent_bwd_desc;
 int ssc_latent_bwd(const ssc_latent_bwd_desc* d, void* stream);
 
+/* Free bits on the KL of the latent head: a floor lambda >= 0 (nats) below which a KL term costs lambda and has no gradient.
+ * With k_tbj = the per-element closed-form KL of step t, row b, dimension j as ssc_latent_fwd forms it (-0.5 * its bracket, in the
+ * formula of kld_mode 0, 1 or 2), w_tb the step weight and S_bj = sum_t w_tb k_tbj:
+ *   mode 1 "element": kld_b = sum_t w_tb sum_j max(lambda, k_tbj)        gate g_tbj = [k_tbj > lambda]
+ *   mode 2 "step":    kld_b = sum_t w_tb max(lambda, sum_j k_tbj)        gate g_tb  = [sum_j k_tbj > lambda]
+ *   mode 3 "dim":     kld_b = sum_j (g_j ? S_bj : lambda)                gate g_j   = [K_j > lambda],  K_j = (1/B) sum_b S_bj
+ *                     (Kingma et al. 2016: the floor is on the minibatch mean of each dimension, mean_b kld_b = sum_j max(lambda, K_j)
+ *                     - B is the rows of THIS call, under data parallelism the rank's own minibatch)
+ * The comparison is strict: a term at or below the floor contributes lambda to the value and nothing to the gradient.
+ *   ssc_latent_fwd_fb: one step.  mu, lv and z are the bits of ssc_latent_fwd on the same descriptor (same slab summation order,
+ *     both kernel forms).  kld_raw[b] += w[b] * sum_j k_tbj in every mode (the bits ssc_latent_fwd adds to kld_acc).  Modes 1 and 2
+ *     add the floored step to d->kld_acc[b], mode 2 also writes gate_step[b] (1.0 or 0.0) for this step.  Mode 3 leaves d->kld_acc
+ *     alone and adds w[b] * k_tbj to dim_acc[b * lddim + j] (the lane that holds (b, j) owns the element), the caller zeroes
+ *     dim_acc before the first step and calls ssc_latent_fb_finish after the last.
+ *   ssc_latent_fb_finish (mode 3): K_j = (1/B) sum_b dim_acc[b, j] with b in index order -> kdim (Z), gate_dim[j] = K_j > lambda
+ *     (1.0 or 0.0), kld[b] = sum_j (gate ? dim_acc[b, j] : lambda), WRITTEN.  One launch.
+ *   ssc_latent_bwd_fb: ssc_latent_bwd with the KL part of dmu, dlv and dpm multiplied by the gate - mode 1 forms k_tbj again from
+ *     mu / lv with the device function the forward used, modes 2 and 3 read gate_step (B, this step's) / gate_dim (Z).  The
+ *     reparameterisation part (dz) is untouched, gk stays the gradient of the objective with respect to the returned kld_b.
+ * No atomics: two calls on the same inputs are bit-identical.
+ * SSC_EINVAL and no launch: what ssc_latent_fwd / ssc_latent_bwd refuse, a NULL fb, lambda negative, NaN or infinite, lambda > 0
+ * with a mode outside 1..3, kld_raw NULL (forward), gate_step NULL in mode 2, dim_acc NULL or lddim < Z (forward) or gate_dim NULL
+ * (backward) in mode 3.  lambda = 0 means off whatever the mode: the two calls launch the kernels of ssc_latent_fwd / ssc_latent_bwd,
+ * the fields of fb other than lambda are then not read or written. */
+typedef struct {
+  float lambda; int mode;
+  float* kld_raw;                /* forward: (B) raw KL accumulator */
+  float* gate_step;              /* mode 2: (B) gates of this step, written by the forward, read by the backward */
+  float* dim_acc; int lddim;     /* mode 3, forward: (B, lddim) accumulator of w k_tbj */
+  const float* gate_dim;         /* mode 3, backward: (Z) gates from ssc_latent_fb_finish */
+} ssc_free_bits;
+int ssc_latent_fwd_fb(const ssc_latent_fwd_desc* d, const ssc_free_bits* fb, void* stream);
+int ssc_latent_bwd_fb(const ssc_latent_bwd_desc* d, const ssc_free_bits* fb, void* stream);
+int ssc_latent_fb_finish(const float* dim_acc, int lddim, int B, int Z, float lambda, float* kdim, float* gate_dim, float* kld,
+                         void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Vocabulary cross-entropy: allennlp sequence_cross_entropy_with_logits(average=None) times the
  * target length (updown_captioner.py:457-466).  logits (T*B, V) time-major rows (row = t*B+b).
@@ -483,6 +519,29 @@ int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* p, const ss
  * 10: tokens (L+2,B) int64, 11: att (T,B,F), 12: nll (B): the unsmoothed loss_b of the last forward (= loss with
  * label_smoothing 0).  Returns pointer into the workspace (and its ld) or 0. */
 void* ssc_train_workspace_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
+
+/* The train step with a free-bits floor on the KL (see ssc_latent_fwd_fb): ssc_train_fwd / ssc_train_bwd / ssc_train_bwd_phases
+ * with lambda = free_bits (nats) and free_bits_mode 1 element, 2 step, 3 dim as two arguments of the call.  (The layout of
+ * ssc_model_cfg and the numbering of ssc_train_workspace_view are pinned, so the option travels beside the cfg and its buffers
+ * have a view of their own.)  free_bits 0 = off whatever the mode: the calls are then ssc_train_fwd / ssc_train_bwd /
+ * ssc_train_bwd_phases themselves - which are these with free_bits 0 -, the kernels of ssc_latent_fwd / ssc_latent_bwd run and
+ * every output keeps its bits.  With free_bits > 0 kld is the floored KL and the backward (the latent backward sits in phase 32)
+ * gates the KL gradient; a backward must be given the free_bits and free_bits_mode of its forward, as it must the cfg.  Mode 3
+ * costs one launch after the time loop (ssc_latent_fb_finish), B is the rows of the call.
+ * SSC_EINVAL and no launch: what the plain calls refuse, free_bits negative, NaN or infinite, a mode outside 1..3 while
+ * free_bits > 0.  The buffers are reserved at the end of the train workspace for any cfg and any option:
+ * ssc_train_workspace_bytes does not depend on them.
+ * ssc_train_free_bits_view: what a forward with free_bits > 0 left, which = 0: the raw KL (B), 1: K_j (Z; mode 3), 2: the step
+ * gates (T,B; mode 2), 3: the dimension gates (Z; mode 3), gates as 1.0 / 0.0.  Returns pointer into the workspace (and its ld) or 0. */
+int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
+                     size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream);
+int ssc_train_bwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
+                     size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
+                     int free_bits_mode, void* stream);
+int ssc_train_bwd_phases_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
+                            size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
+                            float free_bits, int free_bits_mode, void* stream);
+void* ssc_train_free_bits_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
 
 /* ------------------------------------------------------------------------------------------------
  * Data-parallel gradient exchange without RCCL: direct reduce-scatter + all-gather over peer-mapped buffers (hipIpc), all

@@ -222,6 +222,14 @@ def main():
     if smoothing > 0 and _A.scst_references and rank == 0:
         print(f"OPTIM.LABEL_SMOOTHING {smoothing} is ignored by the self-critical steps (--scst-references): the advantage-weighted "
               "loss is no likelihood target")
+    # OPTIM.KL_ANNEAL* / OPTIM.FREE_BITS*: the cross-entropy steps.  beta of iteration i (counted from 1) is kl_beta(i - 1, ...), a
+    # function of the iteration number alone, so a resumed run continues the schedule.  The floored KL enters the objective,
+    # 2kld_loss stays the raw KL of the same forward
+    from ssc_runtime.schedule import kl_beta_from_config
+    free_bits, free_bits_mode = model.free_bits, model.free_bits_mode
+    if (free_bits > 0 or _C.OPTIM.KL_ANNEAL != "none") and _A.scst_references and rank == 0:
+        print(f"OPTIM.KL_ANNEAL {_C.OPTIM.KL_ANNEAL} / OPTIM.FREE_BITS {free_bits} are ignored by the self-critical steps "
+              "(--scst-references): they take the KL as it is, with the constant MODEL.KLD_WEIGHT")
     from ssc_runtime.engine import OptimSpec, check_optimizer_state_kind
     kind = _C.OPTIM.OPTIMIZER
     spec = None   # the fused paths' optimiser; None: SGD with OPTIM.MOMENTUM / WEIGHT_DECAY, as before the key existed
@@ -280,6 +288,8 @@ def main():
             Bz, Lz = batch["caption_tokens"].shape
             model._eps_override = torch.zeros(Lz + 1, Bz, _C.MODEL.Z_SPACE, device=device)
         scst_stats = None
+        beta = 1.0 if scst is not None else kl_beta_from_config(_C.OPTIM, iteration - 1)
+        kld_free = None   # the floored KL that entered the objective (OPTIM.FREE_BITS > 0)
         if scst is not None:
             # rollout noise and word draws are a function of (RANDOM_SEED, iteration, rank): a resumed run draws what this one would
             loss_b, kld_b, scst_stats = scst.step(batch["image_features"], batch["image_id"].tolist(), batch["sentiment"], lr=lr,
@@ -296,14 +306,17 @@ def main():
                                            kld_weight=_C.MODEL.KLD_WEIGHT, momentum=_C.OPTIM.MOMENTUM,
                                            weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
                                            decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec,
-                                           label_smoothing=smoothing)
-            reconstr_loss, kld_loss = loss_b.mean(), kld_b.mean()
-            loss = reconstr_loss + kld_loss / _C.MODEL.KLD_WEIGHT
+                                           label_smoothing=smoothing, kl_beta=beta, free_bits=free_bits,
+                                           free_bits_mode=free_bits_mode)
+            reconstr_loss, kld_loss = loss_b.mean(), eng.kld_raw().mean()
+            kld_free = kld_b.mean() if free_bits > 0 else None
+            loss = reconstr_loss + beta * kld_b.mean() / _C.MODEL.KLD_WEIGHT
         else:
             optimizer.zero_grad()
             out = model(batch["image_features"], batch.get("obj_atts"), None, batch["caption_tokens"], batch["sentiment"])
-            reconstr_loss, kld_loss = out["loss"].mean(), out["kld"].mean()
-            loss = reconstr_loss + kld_loss / _C.MODEL.KLD_WEIGHT
+            reconstr_loss, kld_loss = out["loss"].mean(), eng.kld_raw().mean()
+            kld_free = out["kld"].mean() if free_bits > 0 else None
+            loss = reconstr_loss + beta * out["kld"].mean() / _C.MODEL.KLD_WEIGHT
             for group in optimizer.param_groups:
                 group["lr"] = lr
             loss.backward()   # world > 1: the flat gradient buffer is all-reduced once inside backward (eng.dp_autograd)
@@ -314,6 +327,12 @@ def main():
                    "3loss": float(loss), "4learning_rate": lr, "elapsed_s": time.time() - t0}
             if smoothing > 0 and scst is None:
                 rec["nll"] = float(eng.nll().mean())   # the unsmoothed loss of the same forward (this rank's rows)
+            if scst is None:
+                rec["kl_beta"] = beta
+                if kld_free is not None:
+                    rec["kld_free"] = float(kld_free)
+                    if free_bits_mode == "dim":   # latent dimensions whose minibatch mean KL is above the floor (this rank's rows)
+                        rec["active_dims"] = int(eng.free_bits_view("gate_dim").sum())
             if scst_stats is not None:
                 st = scst_stats.tolist()
                 rec.update({"5reward": st[0], "6baseline": st[1], "7abs_advantage": st[2], "8no_end_share": st[3]})

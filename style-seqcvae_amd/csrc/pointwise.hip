@@ -321,6 +321,195 @@ __global__ void latent_bwd_kernel(const ssc_latent_bwd_desc d) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// latent head with a free-bits floor on the KL (include/ssc.h: ssc_free_bits).  New kernels: lambda = 0 launches the ones above.
+// ---------------------------------------------------------------------------------------------
+// k_tbj = -0.5 * the bracket of latent_fwd_kernel (same expressions, same order: the sum over j of these is -0.5 times that
+// kernel's sum, exactly).  The forward and the mode-1 backward both form their gates from THIS function.
+__device__ __forceinline__ float latent_kl_elem(int kld_mode, float m, float l, float var, float pm, float lpv, float pvar) {
+  if (kld_mode == 0) return -0.5f * (1.f + l - m * m - var);
+  const float dm = m - pm;
+  return -0.5f * (1.f + l - lpv - (dm * dm + var) / (pvar + 0.00001f));
+}
+
+// what one (b, j) element adds: to the raw sum, to the floored sum (mode 1) and to the (B, lddim) accumulator (mode 3)
+template <int FB>
+__device__ __forceinline__ void latent_fb_elem(const ssc_free_bits& fb, float k, float wb, int b, int z, float& raw, float& flo) {
+  raw += k;
+  if (FB == 1) flo += k > fb.lambda ? k : fb.lambda;
+  if (FB == 3) fb.dim_acc[(size_t)b * fb.lddim + z] += wb * k;
+}
+
+// the row's sums (already reduced over j) into the accumulators
+template <int FB>
+__device__ __forceinline__ void latent_fb_row(const ssc_latent_fwd_desc& d, const ssc_free_bits& fb, int b, float wb, float raw, float flo) {
+  fb.kld_raw[b] += wb * raw;
+  if (FB == 1) d.kld_acc[b] += wb * flo;
+  if (FB == 2) {
+    const bool open = raw > fb.lambda;
+    d.kld_acc[b] += wb * (open ? raw : fb.lambda);
+    fb.gate_step[b] = open ? 1.f : 0.f;
+  }
+}
+
+template <int FB>
+__global__ void latent_fwd_fb_kernel(const ssc_latent_fwd_desc d, const ssc_free_bits fb) {
+  int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  int lane = threadIdx.x & 63;
+  if (b >= d.B) return;
+  const int Z = d.Z;
+  const float pm_row = d.sent ? d.pm_scale * d.sent[b] : 0.f;
+  const float pvar = d.prior_var, lpv = logf(pvar), wb = d.w[b];
+  float raw = 0.f, flo = 0.f;
+  for (int z = lane; z < Z; z += 64) {
+    float m = 0.f, l = 0.f;
+    for (int s0 = 0; s0 < d.nslab; s0 += 8) {   // (the slab order of latent_fwd_kernel)
+      float tm[8], tl[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const float* row = d.mulv + (size_t)min(s0 + u, d.nslab - 1) * d.slab_stride + (size_t)b * d.ldmulv;
+        tm[u] = row[z];
+        tl[u] = row[Z + z];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        m += (s0 + u < d.nslab) ? tm[u] : 0.f;
+        l += (s0 + u < d.nslab) ? tl[u] : 0.f;
+      }
+    }
+    m += d.bmu[z];
+    l += d.blv[z];
+    const float var = expf(l);
+    const float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
+    d.mu[(size_t)b * d.ldz + z] = m;
+    d.lv[(size_t)b * d.ldz + z] = l;
+    d.z[(size_t)b * d.ldz + z] = zz;
+    const float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : pm_row;
+    latent_fb_elem<FB>(fb, latent_kl_elem(d.kld_mode, m, l, var, pm, lpv, pvar), wb, b, z, raw, flo);
+  }
+  raw = ssc_wave_sum(raw);
+  if (FB == 1) flo = ssc_wave_sum(flo);
+  if (lane == 0) latent_fb_row<FB>(d, fb, b, wb, raw, flo);
+}
+
+// the many-slab form (latent_fwd_wide_kernel's parts and their order)
+template <int FB>
+__global__ __launch_bounds__(256) void latent_fwd_wide_fb_kernel(const ssc_latent_fwd_desc d, const ssc_free_bits fb) {
+  __shared__ float pm_[4][64], pl_[4][64], kr_[4], kf_[4];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int Z = d.Z;
+  const int ZW = (Z + 63) / 64;
+  const int SP = 4 / ZW;
+  const int zw = wave % ZW, part = wave / ZW;
+  const int z = zw * 64 + lane;
+  const int per = (d.nslab + SP - 1) / SP;
+  const int s_lo = part * per, s_hi = min(d.nslab, s_lo + per);
+  const float wb = d.w[b];
+  float m = 0.f, l = 0.f;
+  if (z < Z && ZW * SP == 4) {
+    for (int s0 = s_lo; s0 < s_hi; s0 += 16) {
+      float tm[16], tl[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        const float* row = d.mulv + (size_t)min(s0 + u, s_hi - 1) * d.slab_stride + (size_t)b * d.ldmulv;
+        tm[u] = row[z];
+        tl[u] = row[Z + z];
+      }
+#pragma unroll
+      for (int u = 0; u < 16; ++u) {
+        m += (s0 + u < s_hi) ? tm[u] : 0.f;
+        l += (s0 + u < s_hi) ? tl[u] : 0.f;
+      }
+    }
+  }
+  pm_[wave][lane] = m;
+  pl_[wave][lane] = l;
+  __syncthreads();
+  float raw = 0.f, flo = 0.f;
+  if (part == 0 && z < Z) {
+    for (int p = 1; p < SP; ++p) { m += pm_[p * ZW + zw][lane]; l += pl_[p * ZW + zw][lane]; }
+    const float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : (d.sent ? d.pm_scale * d.sent[b] : 0.f);
+    const float pvar = d.prior_var, lpv = logf(pvar);
+    m += d.bmu[z];
+    l += d.blv[z];
+    const float var = expf(l);
+    const float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
+    d.mu[(size_t)b * d.ldz + z] = m;
+    d.lv[(size_t)b * d.ldz + z] = l;
+    d.z[(size_t)b * d.ldz + z] = zz;
+    latent_fb_elem<FB>(fb, latent_kl_elem(d.kld_mode, m, l, var, pm, lpv, pvar), wb, b, z, raw, flo);
+  }
+  raw = ssc_wave_sum(raw);
+  if (FB == 1) flo = ssc_wave_sum(flo);
+  if (lane == 0) { kr_[wave] = raw; kf_[wave] = flo; }
+  __syncthreads();
+  if (tid == 0) {
+    float r = 0.f, f = 0.f;
+    for (int w2 = 0; w2 < ZW; ++w2) { r += kr_[w2]; f += kf_[w2]; }   // waves of part 0, in z order
+    latent_fb_row<FB>(d, fb, b, wb, r, f);
+  }
+}
+
+// mode 3 after the last step: one workgroup.  K_j over b in index order, the Z gates, then kld_b (one wave per row at a time)
+__global__ __launch_bounds__(256) void latent_fb_finish_kernel(const float* __restrict__ acc, int ld, int B, int Z, float lambda,
+                                                               float* __restrict__ kdim, float* gate, float* __restrict__ kld) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  for (int j = tid; j < Z; j += 256) {
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += acc[(size_t)b * ld + j];
+    const float k = s / (float)B;
+    kdim[j] = k;
+    gate[j] = k > lambda ? 1.f : 0.f;
+  }
+  __syncthreads();   // (the gates of this workgroup's own stores)
+  for (int b = wave; b < B; b += 4) {
+    float s = 0.f;
+    for (int j = lane; j < Z; j += 64) s += gate[j] != 0.f ? acc[(size_t)b * ld + j] : lambda;
+    s = ssc_wave_sum(s);
+    if (lane == 0) kld[b] = s;
+  }
+}
+
+template <int FB>
+__global__ void latent_bwd_fb_kernel(const ssc_latent_bwd_desc d, const ssc_free_bits fb) {
+  int b = blockIdx.y;
+  int z = blockIdx.x * blockDim.x + threadIdx.x;
+  if (z >= d.Z) return;
+  float k = d.gk[b] * d.w[b];
+  float m = d.mu[(size_t)b * d.ldz + z], l = d.lv[(size_t)b * d.ldz + z];
+  float dz = 0.f;
+  {
+    const int ns = d.nslab > 1 ? d.nslab : 1;
+    for (int s0 = 0; s0 < ns; s0 += 8) {
+      float t[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[u] = d.dz[(size_t)min(s0 + u, ns - 1) * d.slab_stride + (size_t)b * d.lddz + z];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) dz += (s0 + u < ns) ? t[u] : 0.f;
+    }
+  }
+  float e = d.eps[(size_t)b * d.ldeps + z];
+  float var = expf(l);
+  const float pm = d.kld_mode == 0 ? 0.f : (d.pm ? d.pm[(size_t)b * d.ldpm + z] : (d.sent ? d.pm_scale * d.sent[b] : 0.f));
+  bool open;
+  if (FB == 1) open = latent_kl_elem(d.kld_mode, m, l, var, pm, logf(d.prior_var), d.prior_var) > fb.lambda;
+  else if (FB == 2) open = fb.gate_step[b] != 0.f;
+  else open = fb.gate_dim[z] != 0.f;
+  k = open ? k : 0.f;   // a closed gate: the KL part is +0 times its factor, as with gk = 0
+  float dmu, dlv;
+  if (d.kld_mode == 0) {
+    dmu = dz + k * m;
+    dlv = dz * e * 0.5f * sqrtf(var) - 0.5f * k * (1.f - var);
+  } else {
+    float den = d.prior_var + 0.00001f;
+    dmu = dz + k * (m - pm) / den;
+    if (d.dpm) d.dpm[(size_t)b * d.lddpm + z] = -k * (m - pm) / den;
+    dlv = dz * e * 0.5f * sqrtf(var) - 0.5f * k * (1.f - var / den);
+  }
+  d.dmulv[(size_t)b * d.lddmulv + z] = dmu;
+  d.dmulv[(size_t)b * d.lddmulv + d.Z + z] = dlv;
+}
+
+// ---------------------------------------------------------------------------------------------
 // cross entropy over the vocabulary
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
@@ -795,6 +984,58 @@ extern "C" int ssc_latent_bwd(const ssc_latent_bwd_desc* d, void* stream) {
   if (!d || d->B <= 0 || d->Z <= 0 || !d->dz || !d->eps || !d->mu || !d->lv || !d->w || !d->gk || !d->dmulv)
     return SSC_EINVAL;
   SSC_LAUNCH(latent_bwd_kernel, dim3(ssc_cdiv(d->Z, 64), d->B), dim3(64), 0, S(stream), *d);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+// lambda is a finite number >= 0 and, when positive, the mode one of 1..3 (NaN fails the first comparison)
+static bool free_bits_ok(const ssc_free_bits* fb) {
+  if (!fb || !(fb->lambda >= 0.f) || !(fb->lambda <= 3.402823466e38f)) return false;
+  return fb->lambda == 0.f || (fb->mode >= 1 && fb->mode <= 3);
+}
+
+extern "C" int ssc_latent_fwd_fb(const ssc_latent_fwd_desc* d, const ssc_free_bits* fb, void* stream) {
+  if (!free_bits_ok(fb)) return SSC_EINVAL;
+  if (fb->lambda == 0.f) return ssc_latent_fwd(d, stream);
+  if (!d || d->B <= 0 || d->Z <= 0 || !d->mulv || d->nslab < 1 || !d->bmu || !d->blv || !d->eps || !d->w || !d->mu ||
+      !d->lv || !d->z || !d->kld_acc)
+    return SSC_EINVAL;
+  if (!fb->kld_raw || (fb->mode == 2 && !fb->gate_step) || (fb->mode == 3 && (!fb->dim_acc || fb->lddim < d->Z))) return SSC_EINVAL;
+  const int zw = (d->Z + 63) / 64;
+  const bool wide = d->nslab > 16 && (zw == 1 || zw == 2 || zw == 4);   // (the choice of ssc_latent_fwd)
+  const dim3 grid(wide ? d->B : ssc_cdiv(d->B, 4)), block(256);
+#define SSC_FB_FWD(FB) \
+  do { \
+    if (wide) SSC_LAUNCH(latent_fwd_wide_fb_kernel<FB>, grid, block, 0, S(stream), *d, *fb); \
+    else SSC_LAUNCH(latent_fwd_fb_kernel<FB>, grid, block, 0, S(stream), *d, *fb); \
+  } while (0)
+  if (fb->mode == 1) SSC_FB_FWD(1);
+  else if (fb->mode == 2) SSC_FB_FWD(2);
+  else SSC_FB_FWD(3);
+#undef SSC_FB_FWD
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+extern "C" int ssc_latent_fb_finish(const float* dim_acc, int lddim, int B, int Z, float lambda, float* kdim, float* gate_dim,
+                                    float* kld, void* stream) {
+  if (!dim_acc || !kdim || !gate_dim || !kld || B <= 0 || Z <= 0 || lddim < Z || !(lambda >= 0.f) || !(lambda <= 3.402823466e38f))
+    return SSC_EINVAL;
+  SSC_LAUNCH(latent_fb_finish_kernel, dim3(1), dim3(256), 0, S(stream), dim_acc, lddim, B, Z, lambda, kdim, gate_dim, kld);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+extern "C" int ssc_latent_bwd_fb(const ssc_latent_bwd_desc* d, const ssc_free_bits* fb, void* stream) {
+  if (!free_bits_ok(fb)) return SSC_EINVAL;
+  if (fb->lambda == 0.f) return ssc_latent_bwd(d, stream);
+  if (!d || d->B <= 0 || d->Z <= 0 || !d->dz || !d->eps || !d->mu || !d->lv || !d->w || !d->gk || !d->dmulv)
+    return SSC_EINVAL;
+  if ((fb->mode == 2 && !fb->gate_step) || (fb->mode == 3 && !fb->gate_dim)) return SSC_EINVAL;
+  const dim3 grid(ssc_cdiv(d->Z, 64), d->B), block(64);
+  if (fb->mode == 1) SSC_LAUNCH(latent_bwd_fb_kernel<1>, grid, block, 0, S(stream), *d, *fb);
+  else if (fb->mode == 2) SSC_LAUNCH(latent_bwd_fb_kernel<2>, grid, block, 0, S(stream), *d, *fb);
+  else SSC_LAUNCH(latent_bwd_fb_kernel<3>, grid, block, 0, S(stream), *d, *fb);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }

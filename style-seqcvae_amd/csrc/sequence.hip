@@ -38,6 +38,8 @@ struct Layout {
   size_t slabs, slab_floats, logits, lse, proj;   // lse: [lse | w*row(eps)]
   size_t nllw0, nll;   // the [w*row(0)] block of ssc_ce_fwd_smooth and the (B) unsmoothed loss: behind everything else, so that no other
                        // buffer's place depends on them
+  size_t kld_raw, fb_kdim, fb_gdim, fb_gstep, fb_acc;   // free bits (ssc_train_fwd_fb with free_bits > 0): the raw KL (B), K_j and the dimension gates (Z each),
+                                                        // the step gates (T*B), the (B, Zp) accumulator of mode 3.  Behind nll, reserved for any cfg
   size_t sl_q, sl_mulv, sl_gh1, sl_ghd, sl_ghd2, sl_ghe, sl_dqw, sl_dhe, sl_dz, small_floats, wsum_att, wsum_dec, wz;
   size_t sl_ga, sl_ge, sl_gd, gate_floats;   // split-K slab regions of the three gate products (forward)
   // backward
@@ -131,6 +133,10 @@ Layout make_layout(const ssc_model_cfg* c, int B, int R, int L) {
   l.dproj = l.take(l.tied ? TB * l.Ep : 0);
   l.nllw0 = l.take(TB);
   l.nll = l.take(B);
+  l.kld_raw = l.take(B);
+  l.fb_kdim = l.take(l.Z); l.fb_gdim = l.take(l.Z);
+  l.fb_gstep = l.take(TB);
+  l.fb_acc = l.take((size_t)B * l.Zp);
   return l;
 }
 
@@ -375,6 +381,13 @@ int check_cfg(const ssc_model_cfg* c, const ssc_params* p, const ssc_batch* b) {
 }
 
 // include/ssc_debug.h: hipEvent pair around the time loop of the last forward / backward call
+// the free-bits option of the _fb calls (include/ssc.h): lambda a finite number >= 0 and, while it is positive, a mode of 1..3
+int check_free_bits(float free_bits, int mode) {
+  if (!(free_bits >= 0.f) || !(free_bits <= 3.402823466e38f)) return SSC_EINVAL;   // negative, NaN, infinite
+  if (free_bits > 0.f && (mode < 1 || mode > 3)) return SSC_EINVAL;
+  return SSC_OK;
+}
+
 struct LoopProf {
   hipEvent_t e[4];
   bool created = false, on = false, fwd = false, bwd = false;
@@ -434,10 +447,31 @@ extern "C" void* ssc_train_workspace_view(const ssc_model_cfg* cfg, int B, int R
   }
 }
 
+extern "C" void* ssc_train_free_bits_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld) {
+  if (!cfg || !workspace || B <= 0 || R <= 0 || L <= 0) return nullptr;
+  const Layout l = make_layout(cfg, B, R, L);
+  float* w = (float*)workspace;
+  int dummy;
+  if (!ld) ld = &dummy;
+  switch (which) {
+    case 0: *ld = l.B; return w + l.kld_raw;
+    case 1: *ld = l.Z; return w + l.fb_kdim;
+    case 2: *ld = l.B; return w + l.fb_gstep;
+    case 3: *ld = l.Z; return w + l.fb_gdim;
+    default: return nullptr;
+  }
+}
+
 extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                              size_t workspace_bytes, float* loss, float* kld, void* stream) {
+  return ssc_train_fwd_fb(cfg, p, bt, workspace, workspace_bytes, loss, kld, 0.f, 0, stream);
+}
+
+extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
+  SSC_TRY(check_free_bits(free_bits, free_bits_mode));
   if (!workspace || !loss || !kld) return SSC_EINVAL;
   if (!ssc_aligned16(workspace)) return SSC_EALIGN;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
@@ -449,6 +483,7 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
   const int TB = T * B;
   int64_t* tok = (int64_t*)(W + l.tok);
   const size_t sH = (size_t)B * l.Hp;  // per-step stride of the state histories
+  const bool fb_on = free_bits > 0.f;   // a free-bits floor on the KL: the _fb kernels of the latent head, else today's
 
   // ---- per-sequence precompute --------------------------------------------------------------
   SSC_TRY(ssc_prep_tokens(bt->caps, B, l.L, cfg->pad, cfg->boundary, tok, W + l.w, W + l.nvalid, st));
@@ -468,6 +503,10 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
     FillList f;
     for (size_t off : {l.h1, l.c1, l.he, l.ce, l.hd, l.cd}) f.add(W + off, sH);
     f.add(kld, (size_t)B);
+    if (fb_on) {   // (free bits: the raw accumulator, and the per-dimension one of mode 3)
+      f.add(W + l.kld_raw, (size_t)B);
+      if (free_bits_mode == 3) f.add(W + l.fb_acc, (size_t)B * l.Zp);
+    }
     if (l.Zp != Z) {  // keep pad columns of z finite (they are never read as K, but are memcpy'd in tests)
       f.add(W + l.z, (size_t)TB * l.Zp); f.add(W + l.mu, (size_t)TB * l.Zp); f.add(W + l.lv, (size_t)TB * l.Zp);
     }
@@ -586,7 +625,15 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
       d.w = W + l.w + (size_t)t * B;
       d.mu = W + l.mu + (size_t)t * B * l.Zp; d.lv = W + l.lv + (size_t)t * B * l.Zp; d.z = zt; d.ldz = l.Zp;
       d.kld_acc = kld;
-      SSC_TRY(ssc_latent_fwd(&d, st));
+      if (fb_on) {
+        ssc_free_bits fb{};
+        fb.lambda = free_bits; fb.mode = free_bits_mode;
+        fb.kld_raw = W + l.kld_raw; fb.gate_step = W + l.fb_gstep + (size_t)t * B;
+        fb.dim_acc = W + l.fb_acc; fb.lddim = l.Zp;
+        SSC_TRY(ssc_latent_fwd_fb(&d, &fb, st));
+      } else {
+        SSC_TRY(ssc_latent_fwd(&d, st));
+      }
     }
     // (vi) decoder LSTM cell; its z block (K = Z, the only operand that waits for the latent head) is formed inside the kernel
     {
@@ -603,6 +650,9 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
   }
 
   if (g_loop.on) { (void)hipEventRecord(g_loop.e[1], st); g_loop.fwd = true; }
+  // free bits on the minibatch mean of each dimension: K_j, the Z gates and kld_b from the accumulator the steps filled
+  if (fb_on && free_bits_mode == 3)
+    SSC_TRY(ssc_latent_fb_finish(W + l.fb_acc, l.Zp, B, Z, free_bits, W + l.fb_kdim, W + l.fb_gdim, kld, st));
 
   // ---- vocabulary projection + CE over all steps (updown_captioner.py:444-445, 457-466) -----------
   const float* hd_all = W + l.hd + sH;  // rows t*B+b = h_dec after step t
@@ -740,9 +790,10 @@ int ssc_g_dw_one_flush = ssc_env_int("SSC_DW_ONE_FLUSH", 1);
 // (ssc_runtime/engine.py): the output head's 48 MB travel under the whole time loop.
 static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                           size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream,
-                          unsigned phases) {
+                          unsigned phases, float free_bits, int free_bits_mode) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
+  SSC_TRY(check_free_bits(free_bits, free_bits_mode));
   if (!workspace || !gl || !gk || !g) return SSC_EINVAL;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
@@ -867,7 +918,14 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
       if (l.D) { d.pm = W + l.pool + (size_t)t * B * l.Dp; d.ldpm = l.Dp; d.dpm = W + l.dpm; d.lddpm = l.Dp; }
       d.w = W + l.w + (size_t)t * B; d.gk = gk;
       d.dmulv = dmulv; d.lddmulv = 2 * Z;
-      SSC_TRY(ssc_latent_bwd(&d, st));
+      if (free_bits > 0.f) {   // the gates of this forward (mode 1 forms them again from mu / lv)
+        ssc_free_bits fb{};
+        fb.lambda = free_bits; fb.mode = free_bits_mode;
+        fb.gate_step = W + l.fb_gstep + (size_t)t * B; fb.gate_dim = W + l.fb_gdim;
+        SSC_TRY(ssc_latent_bwd_fb(&d, &fb, st));
+      } else {
+        SSC_TRY(ssc_latent_bwd(&d, st));
+      }
     }
     // 4-5. encoder LSTM: dhe = g_he' slabs + (dmu | dlv) [W_mu ; W_lv].  With the two fc weights adjacent in the flat store the
     // K = 2Z product is formed inside the cell kernel (ssc_lstm_bwd_x): no launch of its own on the dependency chain
@@ -1121,13 +1179,25 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
 extern "C" int ssc_train_bwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                              size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, 0.f, 0);
+}
+
+extern "C" int ssc_train_bwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
+                                int free_bits_mode, void* stream) {
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, free_bits, free_bits_mode);
 }
 
 extern "C" int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                     size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
                                     unsigned phases, void* stream) {
+  return ssc_train_bwd_phases_fb(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, 0.f, 0, stream);
+}
+
+extern "C" int ssc_train_bwd_phases_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                       size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
+                                       unsigned phases, float free_bits, int free_bits_mode, void* stream) {
   if (phases == 0 || phases > 255u) return SSC_EINVAL;
   if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode);
 }

@@ -106,6 +106,17 @@ def _defaults() -> dict:
             # label smoothing of the cross-entropy steps (torch.nn.functional.cross_entropy's label_smoothing: the mass is spread
             # over all V classes), in [0, 1); 0 = the reference's plain masked NLL.  Self-critical steps and validation never smooth
             "LABEL_SMOOTHING": 0.0,
+            # KL annealing of the cross-entropy steps (ssc_runtime/schedule.py: kl_beta): the KL term of the objective is multiplied
+            # by beta(iteration), a pure function of the iteration number.  "none": 1; "linear": from KL_ANNEAL_START to 1 over
+            # KL_ANNEAL_ITERS iterations; "cyclical" (Fu et al. 2019): the ramp restarts every KL_ANNEAL_ITERS iterations, rises over
+            # the first KL_ANNEAL_RATIO of a cycle and stays at 1 for the rest.  The reference's MODEL.KLD_* annealing keys above are
+            # read by nothing there or here
+            "KL_ANNEAL": "none", "KL_ANNEAL_ITERS": 10000, "KL_ANNEAL_RATIO": 0.5, "KL_ANNEAL_START": 0.0,
+            # free bits: a floor of FREE_BITS nats under the KL (0 = off).  FREE_BITS_MODE "element": every (step, dimension) term,
+            # "step": the KL of every step, "dim" (Kingma et al. 2016): the minibatch mean of every latent dimension, summed over the
+            # steps - the minibatch of one process.  A term at or below its floor has no gradient.  Self-critical steps and validation
+            # are never annealed or floored
+            "FREE_BITS": 0.0, "FREE_BITS_MODE": "dim",
         },
     }
 
@@ -199,6 +210,19 @@ class Config(object):
         ls = o.LABEL_SMOOTHING
         if isinstance(ls, bool) or not isinstance(ls, (int, float)) or not 0.0 <= ls < 1.0:
             raise ValueError(f"OPTIM.LABEL_SMOOTHING must be a number in [0, 1); found {ls!r}")
+        num = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool)
+        if o.KL_ANNEAL not in ("none", "linear", "cyclical"):
+            raise ValueError(f"OPTIM.KL_ANNEAL must be one of none | linear | cyclical; found {o.KL_ANNEAL!r}")
+        if isinstance(o.KL_ANNEAL_ITERS, bool) or not isinstance(o.KL_ANNEAL_ITERS, int) or o.KL_ANNEAL_ITERS < 1:
+            raise ValueError(f"OPTIM.KL_ANNEAL_ITERS must be an integer >= 1; found {o.KL_ANNEAL_ITERS!r}")
+        if not num(o.KL_ANNEAL_RATIO) or not 0.0 < o.KL_ANNEAL_RATIO <= 1.0:
+            raise ValueError(f"OPTIM.KL_ANNEAL_RATIO must be a number in (0, 1]; found {o.KL_ANNEAL_RATIO!r}")
+        if not num(o.KL_ANNEAL_START) or not 0.0 <= o.KL_ANNEAL_START <= 1.0:
+            raise ValueError(f"OPTIM.KL_ANNEAL_START must be a number in [0, 1]; found {o.KL_ANNEAL_START!r}")
+        if not num(o.FREE_BITS) or not 0.0 <= o.FREE_BITS < float("inf"):
+            raise ValueError(f"OPTIM.FREE_BITS must be a finite number >= 0; found {o.FREE_BITS!r}")
+        if o.FREE_BITS_MODE not in ("element", "step", "dim"):
+            raise ValueError(f"OPTIM.FREE_BITS_MODE must be one of element | step | dim; found {o.FREE_BITS_MODE!r}")
 
     def __getattr__(self, attr: str):
         return getattr(self.__dict__["_C"], attr)

@@ -122,6 +122,23 @@ def check_label_smoothing(x, name="label_smoothing") -> float:
     return v
 
 
+FREE_BITS_MODES = {"element": 1, "step": 2, "dim": 3}   # ssc_free_bits.mode / the free_bits_mode argument of ssc_train_fwd_fb
+
+
+def check_free_bits(x, mode="dim", name="free_bits") -> Tuple[float, int]:
+    """(lambda as a finite float >= 0, the mode's number in include/ssc.h), else a ValueError that names `name` / `name`_mode.
+    The mode is checked whatever lambda is: a misspelt mode does not wait for the day the floor is switched on."""
+    try:
+        v = float(x)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(x, bool) or not 0.0 <= v < float("inf"):
+        raise ValueError(f"{name} must be a finite number >= 0 (nats); found {x!r}")
+    if mode not in FREE_BITS_MODES:
+        raise ValueError(f"{name}_mode must be one of {' | '.join(FREE_BITS_MODES)}; found {mode!r}")
+    return v, FREE_BITS_MODES[mode]
+
+
 OPTIM_KINDS = ("sgd", "adam", "adamw")
 
 
@@ -308,6 +325,8 @@ class TrainEngine:
         self._ws_key = None
         self._cfg = dims.cfg()
         self._keep = None
+        self._kld = None              # the kld tensor the last forward returned (kld_raw() without a floor)
+        self._fb = (0.0, 3)           # (free_bits, free_bits_mode) of the last forward: every backward of it is given the same
         self._post_ws = None          # posterior_forward's own workspace: the training forward's activations are never overwritten
         self._post_ws_key = None
         self._post = None
@@ -388,26 +407,32 @@ class TrainEngine:
                         eps.data_ptr(), obj_atts.data_ptr() if obj_atts is not None else None)
         return bt, (sent, obj_atts)
 
-    def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0):
+    def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0, free_bits=0.0, free_bits_mode="dim"):
         """-> (loss (B,), kld (B,)); keeps activations for backward().  obj_atts (B,R,S): per-region attribute means, kld_mode 2 only.
         label_smoothing: eps of THIS call's cross-entropy (ssc_ce_fwd_smooth; 0 = the plain masked NLL, the kernels as they are
         without it).  It stays in the engine's cfg until the next forward, so every backward of this forward - the phased one of
-        the data-parallel path included - differentiates the loss that was returned.  nll() is the unsmoothed loss either way."""
+        the data-parallel path included - differentiates the loss that was returned.  nll() is the unsmoothed loss either way.
+        free_bits (nats) / free_bits_mode ("element" | "step" | "dim"): a floor on the KL of THIS call (include/ssc.h:
+        ssc_free_bits) - kld is then the floored KL, a term at or below the floor has no gradient in the backward, kld_raw() is the
+        KL without the floor.  0 = off: the kernels as they are without it.  "dim" floors the mean over the B rows of this call
+        of each latent dimension (under data parallelism: this rank's rows).  Kept beside the cfg until the next forward likewise."""
         self._cfg.label_smoothing = check_label_smoothing(label_smoothing)
+        self._fb = check_free_bits(free_bits, free_bits_mode)
         bt, sent = self._batch(feats, caps, sentiment, eps, obj_atts)
         ws = self._workspace(bt.B, bt.R, bt.L)
         loss = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         kld = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         p = self.params.c_struct()
-        self.lib.ssc_train_fwd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                               _lib.ptr(kld), _lib.stream_ptr())
+        self.lib.ssc_train_fwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                  _lib.ptr(kld), *self._fb, _lib.stream_ptr())
         self._keep = (bt, feats, caps, sent, eps)
+        self._kld = kld
         self.fwd_version += 1
         return loss, kld
 
     def posterior_forward(self, feats, caps, sentiment, eps, obj_atts=None):
         """The posterior branch's view of given captions (include/ssc.h: ssc_train_posterior) -> (nll (B,), kld (B,), log_ratio (B,),
-        log_w (B,), kl_dim (B, Z), step_kl (T, B), step_ratio (T, B)): one ssc_train_fwd with label_smoothing 0 on a workspace of
+        log_w (B,), kl_dim (B, Z), step_kl (T, B), step_ratio (T, B)): one ssc_train_fwd (label_smoothing 0; that entry has no free-bits floor) on a workspace of
         this method's own and a copy of the cfg, then the log-density ratio log p(z) - log q(z | x) at the sampled z, the KL per
         latent dimension and per step, and log_w = log_ratio - nll.  Nothing a later backward() reads is touched - _keep, the
         training workspace, the cfg's label_smoothing, fwd_version: backward() after this call still differentiates the forward
@@ -487,8 +512,8 @@ class TrainEngine:
         # only what the update will read travels: a frozen decoder LSTM / tied embedding keeps its (stale) gradient range at home
         t_lo, t_hi = self.trainable_range(bool(set(self.decoder_names) & skipset))
         for mask, rng in self.phase_ranges():
-            self.lib.ssc_train_bwd_phases(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
-                                          _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, _lib.stream_ptr())
+            self.lib.ssc_train_bwd_phases_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
+                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, _lib.stream_ptr())
             if rng is not None:
                 lo, hi = max(rng[0], t_lo), min(rng[1], t_hi)
                 if hi > lo and xg is not None:
@@ -604,8 +629,8 @@ class TrainEngine:
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
         for mask in masks:
-            self.lib.ssc_train_bwd_phases(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
-                                          _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, _lib.stream_ptr())
+            self.lib.ssc_train_bwd_phases_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
+                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, _lib.stream_ptr())
 
     def backward(self, gl, gk, skip: Sequence[str] = ()):
         """Writes d(sum_b gl_b loss_b + gk_b kld_b)/dparam into self.grads for every parameter not in `skip`
@@ -618,13 +643,35 @@ class TrainEngine:
         g = self.grads.c_struct(only=only)
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
-        self.lib.ssc_train_bwd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
-                               _lib.ptr(gk), C.byref(g), _lib.stream_ptr())
+        self.lib.ssc_train_bwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                  _lib.ptr(gk), C.byref(g), *self._fb, _lib.stream_ptr())
 
     def nll(self):
         """(B,) unsmoothed loss_b of the last forward (= its loss when that ran with label_smoothing 0): a view of the workspace,
         valid until the next forward."""
         return self.workspace_view(12)
+
+    def kld_raw(self):
+        """(B,) KL of the last forward without the free-bits floor: a view of the workspace, valid until the next forward - or,
+        when that forward ran with free_bits 0, the kld it returned."""
+        return self.free_bits_view("raw") if self._fb[0] > 0 else self._kld
+
+    def free_bits_view(self, which):
+        """Of the last forward with free_bits > 0 (ssc_train_free_bits_view): "raw" (B,) the KL without the floor, "kdim" (Z,) the
+        minibatch means K_j and "gate_dim" (Z,) their gates (mode "dim"), "gate_step" (T, B) the step gates (mode "step"); gates
+        are 1.0 / 0.0.  Views of the workspace, valid until the next forward."""
+        bt = self._keep[0]
+        ws = self._workspace(bt.B, bt.R, bt.L)
+        ld = C.c_int(0)
+        p = self.lib.ssc_train_free_bits_view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws),
+                                              {"raw": 0, "kdim": 1, "gate_step": 2, "gate_dim": 3}[which], C.byref(ld))
+        off = (p - ws.data_ptr()) // 4
+        T, B = bt.L + 1, bt.B
+        if which == "raw":
+            return ws[off:off + B]
+        if which == "gate_step":
+            return ws[off:off + T * B].view(T, B)
+        return ws[off:off + self.dims.Z]
 
     def workspace_view(self, which, T1=None):
         """Saved activations of the last forward (test hook; see ssc_train_workspace_view)."""
@@ -789,18 +836,28 @@ class TrainEngine:
 
     def train_step(self, feats, caps, sentiment, eps, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
                    max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None,
-                   label_smoothing=0.0):
+                   label_smoothing=0.0, kl_beta=1.0, free_bits=0.0, free_bits_mode="dim"):
         """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row.
         optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above.
-        label_smoothing: as forward(); loss is then the smoothed one, nll() the unsmoothed."""
-        loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing)
+        label_smoothing: as forward(); loss is then the smoothed one, nll() the unsmoothed.
+        kl_beta: the annealing weight of this iteration (ssc_runtime/schedule.py) - the objective is mean loss + kl_beta * mean kld /
+        kld_weight, so the upstream of kld_b is kl_beta / (B * kld_weight); 0 is legal: no KL gradient at all.
+        free_bits / free_bits_mode: as forward(); kld is then the floored KL, kld_raw() the raw one."""
+        kl_beta = float(kl_beta)
+        if not 0.0 <= kl_beta < float("inf"):
+            raise ValueError(f"kl_beta must be a finite number >= 0; found {kl_beta!r}")
+        loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing, free_bits, free_bits_mode)
         B = loss.numel()
         key = (B, float(kld_weight))
-        if getattr(self, "_upstream_key", None) != key:   # d(mean loss + mean kld / KLD_WEIGHT) / d(loss_b, kld_b): constant per (B, weight)
+        if getattr(self, "_upstream_key", None) != key:   # d(mean loss + beta mean kld / KLD_WEIGHT) / d(loss_b, kld_b): two (B,) buffers per (B, weight)
             self._upstream = (torch.full((B,), 1.0 / B, dtype=torch.float32, device=self.device),
                               torch.full((B,), 1.0 / (B * kld_weight), dtype=torch.float32, device=self.device))
             self._upstream_key = key
+            self._upstream_beta = 1.0
         gl, gk = self._upstream
+        if kl_beta != self._upstream_beta:   # a schedule moves beta every iteration: refill the same buffer (one launch, no allocation, no sync)
+            gk.fill_(kl_beta / (B * kld_weight))
+            self._upstream_beta = kl_beta
         self.backward_update(gl, gk, lr, momentum, weight_decay, max_norm, decoder_frozen, group, optim)
         return loss, kld
 

@@ -73,6 +73,11 @@ class ModelCfg(C.Structure):
                 ("label_smoothing", C.c_float)]
 
 
+class FreeBits(C.Structure):
+    _fields_ = [("lambda_", C.c_float), ("mode", C.c_int), ("kld_raw", vp), ("gate_step", vp), ("dim_acc", vp), ("lddim", C.c_int),
+                ("gate_dim", vp)]
+
+
 # (field, has_ld) in the exact order of ssc_params
 PARAM_FIELDS = [("emb", True), ("att_w_ih", True), ("att_w_hh", True), ("att_b_ih", False), ("att_b_hh", False),
                 ("wq", True), ("wv", True), ("wa", False), ("enc_w_ih", True), ("enc_w_hh", True), ("enc_b_ih", False),
@@ -234,6 +239,9 @@ SYMBOLS = {
     "ssc_latent_prior_sample": (_i, [vp, _i, vp, _f, _f, _i, _i, vp, _i, vp]),
     "ssc_latent_prior_sample_pm": (_i, [vp, _i, vp, _i, vp, _i, vp, _f, _f, _i, _i, vp, _i, vp]),
     "ssc_latent_bwd": (_i, [C.POINTER(LatentBwdDesc), vp]),
+    "ssc_latent_fwd_fb": (_i, [C.POINTER(LatentFwdDesc), C.POINTER(FreeBits), vp]),
+    "ssc_latent_bwd_fb": (_i, [C.POINTER(LatentBwdDesc), C.POINTER(FreeBits), vp]),
+    "ssc_latent_fb_finish": (_i, [vp, _i, _i, _i, _f, vp, vp, vp, vp]),
     "ssc_ce_fwd": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, vp, vp, vp]),
     "ssc_ce_bwd": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, vp]),
     "ssc_ce_fwd_smooth": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _f, vp, vp, vp, vp]),
@@ -254,6 +262,11 @@ SYMBOLS = {
     "ssc_train_bwd_phases": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
                                   C.c_uint, vp]),
     "ssc_train_workspace_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
+    "ssc_train_fwd_fb": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, _f, _i, vp]),
+    "ssc_train_bwd_fb": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), _f, _i, vp]),
+    "ssc_train_bwd_phases_fb": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
+                                     C.c_uint, _f, _i, vp]),
+    "ssc_train_free_bits_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
     "ssc_xgmi_enable_peer": (_i, [_i]),
     "ssc_xgmi_ipc_export": (_i, [vp, vp, C.POINTER(C.c_size_t)]),
     "ssc_xgmi_ipc_open": (_i, [vp, C.POINTER(vp)]),

@@ -20,7 +20,7 @@ from ssc_runtime import sampling
 from ssc_runtime.cellops import cell_train_step
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.decoding import select_best_beam_with_constraints
-from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_label_smoothing
+from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_free_bits, check_label_smoothing
 
 from ..modules import ConstrainedBeamSearch, UpDownCell
 
@@ -29,8 +29,8 @@ class _SeqCVAETrainFn(torch.autograd.Function):
     """loss_b, kld_b = f(params; feats, caps, sentiment, eps) with the hand-derived BPTT as backward."""
 
     @staticmethod
-    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, *params):
-        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing)
+    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *params):
+        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode)
         ctx.eng, ctx.names = eng, names
         ctx.version = eng.fwd_version
         return loss, kld
@@ -41,7 +41,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
         if eng.fwd_version != ctx.version:
             raise RuntimeError("UpDownCaptioner: backward() after a newer forward(); the activation workspace holds "
                                "only the latest forward")
-        need = ctx.needs_input_grad[8:]
+        need = ctx.needs_input_grad[10:]
         skip = [n for n, k in zip(ctx.names, need) if not k]
         eng.backward(gl, gk, skip=skip)
         if eng.dp_autograd:   # data parallel on the autograd path: ONE sum all-reduce of the flat gradient buffer, then the mean
@@ -50,7 +50,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
                 eng.grads.flat.mul_(1.0 / world)
         frozen = set(eng.frozen_names)
         grads = tuple(eng.grads.views[n].clone() if (k and n not in frozen) else None for n, k in zip(ctx.names, need))
-        return (None,) * 8 + grads
+        return (None,) * 10 + grads
 
 
 class UpDownCaptioner(nn.Module):
@@ -58,7 +58,8 @@ class UpDownCaptioner(nn.Module):
                  max_caption_length=20, beam_size=1, use_cbs=False, min_constraints_to_satisfy=2, z_space=150,
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
                  sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None,
-                 sampled_beam=False, diverse_beam=None, label_smoothing=0.0, decode_rules=None):
+                 sampled_beam=False, diverse_beam=None, label_smoothing=0.0, decode_rules=None, free_bits=0.0,
+                 free_bits_mode="dim"):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
@@ -80,9 +81,16 @@ class UpDownCaptioner(nn.Module):
         rules with every control off: the eval forward is what it is without them.
         `label_smoothing` (OPTIM.LABEL_SMOOTHING), in [0, 1): the cross-entropy of the training forward spreads this much of every
         target's mass over all V classes (torch.nn.functional.cross_entropy's label_smoothing, ssc_ce_fwd_smooth); 0 = the
-        reference's plain masked NLL.  scst_step and score_captions never smooth."""
+        reference's plain masked NLL.  scst_step and score_captions never smooth.
+        `free_bits` (OPTIM.FREE_BITS, nats) / `free_bits_mode` (OPTIM.FREE_BITS_MODE: "element" | "step" | "dim"): a floor under the KL
+        of the training forward (ssc_latent_fwd_fb) - out["kld"] is then the floored KL and a term at or below its floor has no
+        gradient; the KL without the floor is `_engine().kld_raw()`.  "dim" floors the mean over the rows of the call of every latent
+        dimension.  0 = off.  Any annealing weight is the caller's multiplier on out["kld"], as KLD_WEIGHT is.  scst_step,
+        score_captions and posterior_score_captions never floor."""
         super().__init__()
         self.label_smoothing = check_label_smoothing(label_smoothing)
+        self.free_bits = check_free_bits(free_bits, free_bits_mode)[0]
+        self.free_bits_mode = free_bits_mode
         if diverse_beam is not None:
             if sampler is not None:
                 raise ValueError("MODEL.DIVERSE_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam' without MODEL.STOCHASTIC_BEAM_SEARCH")
@@ -194,7 +202,8 @@ class UpDownCaptioner(nn.Module):
                     device=kwargs["device"], mean_choice=kwargs.get("mean_choice"), sampler=kwargs.get("sampler"),
                     sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
                     diverse_beam=kwargs.get("diverse_beam"), label_smoothing=_C.OPTIM.LABEL_SMOOTHING,
-                    decode_rules=sampling.decode_rules_from_config(_C.MODEL, vocabulary))
+                    decode_rules=sampling.decode_rules_from_config(_C.MODEL, vocabulary), free_bits=_C.OPTIM.FREE_BITS,
+                    free_bits_mode=_C.OPTIM.FREE_BITS_MODE)
         model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
         return model
 
@@ -330,7 +339,7 @@ class UpDownCaptioner(nn.Module):
             obj_means = self._obj_means(obj_atts, batch_size, num_boxes)
             loss, kld = _SeqCVAETrainFn.apply(eng, names, image_features.contiguous().float(),
                                               caption_tokens.contiguous().long(), sent, eps, obj_means, self.label_smoothing,
-                                              *params)
+                                              self.free_bits, self.free_bits_mode, *params)
             return {"loss": loss, "kld": kld}
         # eval branch (updown_captioner.py:324-366)
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
