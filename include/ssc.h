@@ -822,6 +822,67 @@ int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_s
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scheduled sampling in the cross-entropy train step (Bengio et al. 2015): with probability `prob` the attention LSTM's embedding
+ * input of a step is a word the model draws from its own logits of the previous step of the SAME forward, not the ground truth.
+ * tok is (L+2, B) time-major, w[t, b] = [tok[t+1, b] != pad].  The target of step t is tok[t+1], always: targets, weights, nvalid,
+ * the loss formula and the KL are what they are without it.  Only the input in[t, b] changes:
+ *   in[0, b] = tok[0, b] (the boundary token; step 0 never samples).
+ *   t >= 1: the row is ELIGIBLE iff w[t, b] == 1 and w[t-1, b] == 1 - the step has a target, and the previous step's logits row is
+ *     one the head projects.  A row that is not eligible is fed tok[t, b] (padded tails; the step after an in-caption @@UNKNOWN@@,
+ *     which is id 0, the pad index).
+ *   An eligible row FIRES iff u[t, b] < prob, u from Philox4x32-10 with key = sampler.seed and counter (0, t, b, 1), word 0, mapped
+ *     to (0, 1) as the samplers map it, (2 * (x >> 9) + 1) * 2^-24 (the word draws use a last counter word of 0: the two streams
+ *     never meet).  prob = 1 fires every eligible row, prob = 0 none.
+ *   A fired row is fed the token ssc_sample_rows draws from the logits row (t-1, b) of this forward with `sampler` (multinomial,
+ *     top-k or top-p, with temperature; top-k with k = 1 is the arg-max variant), step = t, row id b and the same seed.  The id is
+ *     fed as it is: a drawn boundary token or a drawn id 0 is treated as that id is anywhere else - id 0 gets the pad row of the
+ *     table and no embedding gradient.  (A logits row without one comparable entry - all NaN - has no draw: the row keeps tok[t, b].)
+ *   The drawn token is a constant: no gradient flows through the draw or the decision.
+ * The logits row cross-entropy reads for (t-1, b) is bit for bit the row the draw read: the head of step t-1 is computed once,
+ * inside the time loop, into the workspace's logits block, and nothing recomputes it after the loop.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  float prob;                 /* in [0, 1] */
+  ssc_sampler_desc sampler;   /* its seed is the one seed of the feature */
+} ssc_sched_sampling;
+/* The kernel of one step, one workgroup per row: logits (rows, V) ld `ld` are the previous step's, truth (rows) the ground-truth
+ * inputs tok[step], w_prev / w_cur (rows) the weights of steps step-1 / step, table (*, E) ld ldt the embedding table.  Out:
+ * tok_out (rows) the fed ids, fed_out (rows) 1.0 where the model's word was fed else 0.0, emb_out (rows, E) ld ldo the embedding
+ * row of every fed id, gathered in the same launch.  A row that does not fire never reads its logits.  Stream-ordered, no
+ * read-back.  SSC_EINVAL before any launch: prob outside [0, 1] or NaN, the sampler limits of ssc_sample_rows, a NULL pointer,
+ * ld < V, ldt < E, ldo < E, step < 1. */
+int ssc_sched_mix_rows(const float* logits, int ld, int rows, int V, const int64_t* truth, const float* w_prev, const float* w_cur,
+                       const float* table, int ldt, int E, int step, const ssc_sched_sampling* ss, int64_t* tok_out, float* fed_out,
+                       float* emb_out, int ldo, void* stream);
+/* ssc_train_fwd_fb with scheduled sampling.  ss == NULL or ss->prob == 0: it IS ssc_train_fwd_fb - the same launches, the same bits.
+ * Otherwise, for t >= 1, inside the time loop and in this order: the vocabulary head on h_dec of step t-1 (tied: its projection /
+ * tanh / emb^T chain), ssc_sched_mix_rows, the (B x E x 4H) block of emb_t W_ih^att[:, :E] for step t; after the loop only the last
+ * step's head remains.  Step 0 and everything that does not depend on the fed word stay hoisted.  The fed ids and the fed mask
+ * are kept in the workspace (ssc_train_sched_view 13 / 14), behind every other block; the workspace's embedding rows hold the
+ * fed words' rows.  The backward of such a forward is ssc_train_bwd_ss / ssc_train_bwd_phases_ss with fed_inputs = 1 (and, as ever,
+ * the cfg and the free-bits arguments of its forward).  Label smoothing, free bits and the caller's KL weight compose unchanged.
+ * SSC_EINVAL and no launch: what ssc_train_fwd_fb refuses; with ss != NULL, prob outside [0, 1] or NaN and the sampler limits.
+ * ssc_train_posterior, the scoring, decode and self-critical paths never sample. */
+int ssc_train_fwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                     float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_sched_sampling* ss, void* stream);
+/* read-back of what the last ssc_train_fwd_ss with prob > 0 left, numbered on from ssc_train_workspace_view (whose own numbering
+ * is pinned at 0..12, so - as the free-bits buffers - these have a view of their own): which = 13: the fed ids (T,B) int64,
+ * 14: 1.0 where such an id was the model's own word, else 0.0 (T,B) float; both undefined after any other forward.  Returns
+ * pointer into the workspace (and its ld) or 0. */
+void* ssc_train_sched_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
+/* ssc_train_bwd_fb / ssc_train_bwd_phases_fb told which inputs the forward fed (the layout of ssc_model_cfg is pinned, so this
+ * travels beside the cfg as the free-bits option does).  fed_inputs 0: they ARE those calls - the embedding gradient (phase 64) is
+ * scattered by the ground-truth inputs tok[:-1].  fed_inputs 1, after ssc_train_fwd_ss with prob > 0: it is scattered by the fed
+ * ids of the workspace (id 0 receives none); nothing else differs, the workspace's embedding and gate rows already hold the fed
+ * words' values.  SSC_EINVAL and no launch: what those calls refuse, fed_inputs outside {0, 1}. */
+int ssc_train_bwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                     const float* gl, const float* gk, const ssc_params* g, float free_bits, int free_bits_mode, int fed_inputs,
+                     void* stream);
+int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
+                            size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
+                            float free_bits, int free_bits_mode, int fed_inputs, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Scoring GIVEN captions under the model (teacher forcing): how likely is a caption that came from elsewhere - a ground-truth
  * caption, another decoder's or another checkpoint's output.
  * ---------------------------------------------------------------------------------------------- */

@@ -230,6 +230,15 @@ def main():
     if (free_bits > 0 or _C.OPTIM.KL_ANNEAL != "none") and _A.scst_references and rank == 0:
         print(f"OPTIM.KL_ANNEAL {_C.OPTIM.KL_ANNEAL} / OPTIM.FREE_BITS {free_bits} are ignored by the self-critical steps "
               "(--scst-references): they take the KL as it is, with the constant MODEL.KLD_WEIGHT")
+    # OPTIM.SCHEDULED_SAMPLING_*: the cross-entropy steps, on the fused and the autograd path.  The probability of iteration i
+    # (counted from 1) is ss_prob(i - 1, ...), as beta is; decisions and draws are seeded by (RANDOM_SEED, iteration, rank), so a
+    # resumed run draws what the uninterrupted run would have drawn
+    from ssc_runtime.schedule import ss_prob_from_config, ss_sampler_from_config, ss_seed
+    ss_configured = _C.OPTIM.SCHEDULED_SAMPLING_START >= 0
+    ss_sampler = ss_sampler_from_config(_C.OPTIM)
+    if ss_configured and _A.scst_references and rank == 0:
+        print(f"OPTIM.SCHEDULED_SAMPLING_START {_C.OPTIM.SCHEDULED_SAMPLING_START} is ignored by the self-critical steps "
+              "(--scst-references): their rollout already feeds the model its own words")
     from ssc_runtime.engine import OptimSpec, check_optimizer_state_kind
     kind = _C.OPTIM.OPTIMIZER
     spec = None   # the fused paths' optimiser; None: SGD with OPTIM.MOMENTUM / WEIGHT_DECAY, as before the key existed
@@ -290,6 +299,8 @@ def main():
         scst_stats = None
         beta = 1.0 if scst is not None else kl_beta_from_config(_C.OPTIM, iteration - 1)
         kld_free = None   # the floored KL that entered the objective (OPTIM.FREE_BITS > 0)
+        ss_p = ss_prob_from_config(_C.OPTIM, iteration - 1) if scst is None else 0.0
+        ss_args = dict(ss_prob=ss_p, ss_sampler=ss_sampler, ss_seed=ss_seed(_C.RANDOM_SEED, iteration, rank)) if ss_p > 0 else {}
         if scst is not None:
             # rollout noise and word draws are a function of (RANDOM_SEED, iteration, rank): a resumed run draws what this one would
             loss_b, kld_b, scst_stats = scst.step(batch["image_features"], batch["image_id"].tolist(), batch["sentiment"], lr=lr,
@@ -307,12 +318,14 @@ def main():
                                            weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
                                            decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec,
                                            label_smoothing=smoothing, kl_beta=beta, free_bits=free_bits,
-                                           free_bits_mode=free_bits_mode)
+                                           free_bits_mode=free_bits_mode, **ss_args)
             reconstr_loss, kld_loss = loss_b.mean(), eng.kld_raw().mean()
             kld_free = kld_b.mean() if free_bits > 0 else None
             loss = reconstr_loss + beta * kld_b.mean() / _C.MODEL.KLD_WEIGHT
         else:
             optimizer.zero_grad()
+            if ss_configured:
+                model.scheduled_sampling(ss_p, ss_args.get("ss_seed", 0), ss_sampler)
             out = model(batch["image_features"], batch.get("obj_atts"), None, batch["caption_tokens"], batch["sentiment"])
             reconstr_loss, kld_loss = out["loss"].mean(), eng.kld_raw().mean()
             kld_free = out["kld"].mean() if free_bits > 0 else None
@@ -333,6 +346,11 @@ def main():
                     rec["kld_free"] = float(kld_free)
                     if free_bits_mode == "dim":   # latent dimensions whose minibatch mean KL is above the floor (this rank's rows)
                         rec["active_dims"] = int(eng.free_bits_view("gate_dim").sum())
+            if ss_configured and scst is None:
+                rec["ss_prob"] = ss_p
+                # the share of the weighted positions (this rank's rows) the model's own word was fed at: read back here only
+                n_weighted = int((batch["caption_tokens"] != 0).sum()) + batch["caption_tokens"].size(0)
+                rec["ss_fed_share"] = float(eng.fed_mask().sum()) / max(n_weighted, 1)
             if scst_stats is not None:
                 st = scst_stats.tolist()
                 rec.update({"5reward": st[0], "6baseline": st[1], "7abs_advantage": st[2], "8no_end_share": st[3]})

@@ -10,12 +10,12 @@
 // only, so every histogram - and therefore the kept set - is independent of the order the lanes arrive in.  Ties at the cut are
 // resolved by a second radix select on the index (lower index first).  The draw is Gumbel-max over the kept set with
 // counter-based Philox4x32-10 noise: bit-reproducible for a given seed, no float atomics, no order-dependent reduction.
+// The draw of one row (sample_draw_row) lives in sample_draw.h: the scheduled-sampling mix kernel of the train step calls the same code.
 // ssc_decode_sample's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
 
 #include "decode_loop.h"
-#include "ssc_philox.h"
-#include "ssc_radix.h"
+#include "sample_draw.h"
 
 namespace {
 
@@ -41,130 +41,17 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(SampleArgs 
   float lp = 0.f;
   if (!ended) {
     const float* g = a.logits + (size_t)r * a.ld;
-    RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
-    const int nj = (V + 3) >> 2;
-    // ---- stage the row (once from HBM) and its maximum ---------------------------------------------------------------------
-    float mx = -INFINITY;
-    if (STAGED) {
-      RowView<false> gv{g, nullptr, V, row.vec};
-      for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-        float x[4];
-        gv.get4(j, x);
-        if (4 * j + 3 < V) {
-          *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
-        } else {
-          for (int c = 0; c < 4; ++c)
-            if (4 * j + c < V) srow[4 * j + c] = x[c];
-        }
-        mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-      }
-    } else {
-      for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-        float x[4];
-        row.get4(j, x);
-        mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-      }
-    }
-    mx = block_max(mx, sh);   // (its barriers also publish srow)
-    const float T = a.temperature;
-    const bool topp = a.kind == 2 && a.top_p < 1.f;
-    // ---- untempered log-sum-exp (the step log-prob) and the tempered normaliser (top-p masses) -------------------------------
-    float s = 0.f, st = 0.f;
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      row.get4(j, x);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        s += expf(x[c] - mx);
-        if (topp) st += expf((x[c] - mx) / T);
-      }
-    }
-    s = block_sum(s, sh);
-    const float lse = mx + logf(s);
-    float invz = 0.f;
-    if (topp) invz = 1.f / block_sum(st, sh);
-    // ---- the cut: kept <=> key > cut_key, or key == cut_key and v <= cut_idx ------------------------------------------------
-    // (the same code as sample_cut in ssc_radix.h, kept inline here because this kernel's ISA is held fixed: change both together)
-    uint32_t cut_key = 0;
-    int cut_idx = 0x7fffffff;   // (defaults: every entry kept)
-    const bool topk = a.kind == 1 && a.top_k < V;
-    if (topk || topp) {
-      unsigned long long thr;
-      bool found;
-      if (topk) {
-        thr = (unsigned long long)a.top_k;
-        radix_descent<STAGED, false>(row, [&](int, float x, uint32_t& key, unsigned long long& w) {
-          key = sample_key(x); w = 1; return true; }, thr, sh);
-      } else {
-        thr = (unsigned long long)llrint((double)a.top_p * SAMPLE_MASS_ONE);
-        radix_descent<STAGED, true>(row, [&](int, float x, uint32_t& key, unsigned long long& w) {
-          key = sample_key(x);
-          w = (unsigned long long)llrintf(expf((x - mx) / T) * invz * 1099511627776.0f);
-          return true; }, thr, sh);
-      }
-      found = sh.sel_found != 0;
-      if (found) {
-        cut_key = sh.sel_key;
-        const unsigned long long ahead = sh.sel_ahead, wt = sh.sel_w;
-        const uint32_t ct = sh.sel_cnt;
-        // entries tied at the cut share one weight; the n-th of them (lowest index first) is the cut
-        unsigned long long n;
-        if (topk) n = thr - ahead;
-        else {
-          const unsigned long long each = wt / ct;
-          n = (each == 0 || thr <= ahead) ? 1 : (thr - ahead + each - 1) / each;
-        }
-        n = n < 1 ? 1 : (n > ct ? ct : n);
-        __syncthreads();
-        if (n < ct) {
-          const uint32_t ck = cut_key;
-          radix_descent<STAGED, false>(row, [&](int v, float x, uint32_t& key, unsigned long long& w) {
-            key = ~(uint32_t)v; w = 1; return sample_key(x) == ck; }, n, sh);
-          cut_idx = (int)~sh.sel_key;
-        }
-        __syncthreads();
-      }
-    }
-    // ---- Gumbel-max over the kept set: argmax_v logit_v / T + g_v, ties to the lower index --------------------------------------
+    // the draw itself is shared with the scheduled-sampling mix kernel of the train step (sample_draw.h)
     const uint32_t b = (uint32_t)(a.row_ids ? a.row_ids[r] : r);
-    float best = -INFINITY, zk = 0.f;
-    int besti = -1;
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      row.get4(j, x);
-      uint32_t ctr[4] = {(uint32_t)j, (uint32_t)a.step, b, 0u};
-      philox4x32_10(ctr, a.seed_lo, a.seed_hi);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int v = 4 * j + c;
-        const uint32_t key = sample_key(x[c]);
-        const bool kept = v < V && (key > cut_key || (key == cut_key && v <= cut_idx));
-        if (kept) {
-          const float sc = x[c] / T + sample_gumbel(ctr[c]);
-          if (besti < 0 || sc > best) { best = sc; besti = v; }   // (v ascending within the thread: > keeps the lower index)
-          if (a.probs_out) zk += expf((x[c] - mx) / T);
-        }
-      }
-    }
-    // block argmax, ties to the lower index
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(besti, o, 64);
-      if (oi >= 0 && (besti < 0 || ov > best || (ov == best && oi < besti))) { best = ov; besti = oi; }
-    }
-    __syncthreads();
-    if (lane == 0) { sh.bestv[threadIdx.x >> 6] = best; sh.besti[threadIdx.x >> 6] = besti; }
-    __syncthreads();
-    best = sh.bestv[0]; besti = sh.besti[0];
-    for (int w = 1; w < SAMPLE_WAVES; ++w) {
-      const float ov = sh.bestv[w];
-      const int oi = sh.besti[w];
-      if (oi >= 0 && (besti < 0 || ov > best || (ov == best && oi < besti))) { best = ov; besti = oi; }
-    }
-    tok = besti;
-    lp = row.at(besti) - lse;
+    const SampleDraw dr = sample_draw_row<STAGED>(g, srow, V, a.kind, a.top_k, a.top_p, a.temperature, a.seed_lo, a.seed_hi, a.step, b,
+                                                  a.probs_out != nullptr, sh);
+    const RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
+    const float T = a.temperature, mx = dr.mx;
+    const uint32_t cut_key = dr.cut_key;
+    const int cut_idx = dr.cut_idx;
+    float zk = dr.zk;
+    tok = dr.tok;
+    lp = dr.lp;
     if (a.probs_out) {   // the filtered, renormalised distribution in vocabulary order (tests, diagnostics)
       zk = block_sum(zk, sh);
       float* po = a.probs_out + (size_t)r * V;
@@ -207,25 +94,14 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(SampleArgs 
 
 int sample_launch(SampleArgs a, int rows, hipStream_t st) {
   if (a.V <= SAMPLE_LDS_MAX_V) {
-    const size_t lds = (size_t)((a.V + 3) & ~3) * 4;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)sample_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SSC_EHIP;
+    size_t lds;
+    SSC_TRY(sample_row_lds(sample_rows_kernel<true>, a.V, &lds));
     SSC_LAUNCH(sample_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
   } else {
     SSC_LAUNCH(sample_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
   }
   SSC_CHECK_LAUNCH();
   return SSC_OK;
-}
-
-bool sampler_ok(const ssc_sampler_desc* s, int V) {
-  if (!s || V <= 0) return false;
-  if (!(s->temperature > 0.f) || !isfinite(s->temperature)) return false;
-  if (s->kind == 0) return true;
-  if (s->kind == 1) return s->top_k >= 1 && s->top_k <= V;
-  if (s->kind == 2) return s->top_p >= 0.f && s->top_p <= 1.f;
-  return false;
 }
 
 SampleArgs sample_args(const ssc_sampler_desc* s, const float* logits, size_t ld, int V) {

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <initializer_list>
 
+#include "sample_draw.h"
 #include "ssc_common.h"
 #include "ssc_debug.h"
 
@@ -40,6 +41,8 @@ struct Layout {
                        // buffer's place depends on them
   size_t kld_raw, fb_kdim, fb_gdim, fb_gstep, fb_acc;   // free bits (ssc_train_fwd_fb with free_bits > 0): the raw KL (B), K_j and the dimension gates (Z each),
                                                         // the step gates (T*B), the (B, Zp) accumulator of mode 3.  Behind nll, reserved for any cfg
+  size_t fed_ids, fed;   // scheduled sampling (ssc_train_fwd_ss with prob > 0): the ids the forward fed (T*B int64) and 1.0 where such an id was
+                         // the model's own word (T*B).  Behind the free-bits blocks, reserved for any cfg
   size_t sl_q, sl_mulv, sl_gh1, sl_ghd, sl_ghd2, sl_ghe, sl_dqw, sl_dhe, sl_dz, small_floats, wsum_att, wsum_dec, wz;
   size_t sl_ga, sl_ge, sl_gd, gate_floats;   // split-K slab regions of the three gate products (forward)
   // backward
@@ -137,6 +140,8 @@ Layout make_layout(const ssc_model_cfg* c, int B, int R, int L) {
   l.fb_kdim = l.take(l.Z); l.fb_gdim = l.take(l.Z);
   l.fb_gstep = l.take(TB);
   l.fb_acc = l.take((size_t)B * l.Zp);
+  l.fed_ids = l.take(2 * TB);
+  l.fed = l.take(TB);
   return l;
 }
 
@@ -462,17 +467,33 @@ extern "C" void* ssc_train_free_bits_view(const ssc_model_cfg* cfg, int B, int R
   }
 }
 
+extern "C" void* ssc_train_sched_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld) {
+  if (!cfg || !workspace || B <= 0 || R <= 0 || L <= 0) return nullptr;
+  const Layout l = make_layout(cfg, B, R, L);
+  float* w = (float*)workspace;
+  int dummy;
+  if (!ld) ld = &dummy;
+  switch (which) {
+    case 13: *ld = l.B; return w + l.fed_ids;
+    case 14: *ld = l.B; return w + l.fed;
+    default: return nullptr;
+  }
+}
+
 extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                              size_t workspace_bytes, float* loss, float* kld, void* stream) {
   return ssc_train_fwd_fb(cfg, p, bt, workspace, workspace_bytes, loss, kld, 0.f, 0, stream);
 }
 
-extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream) {
+// ss: scheduled sampling (include/ssc.h: ssc_train_fwd_ss); nullptr or prob 0 = teacher forcing, the launches as they are without it
+static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace, size_t workspace_bytes,
+                          float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_sched_sampling* ss, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
   SSC_TRY(check_free_bits(free_bits, free_bits_mode));
+  if (ss && (!(ss->prob >= 0.f && ss->prob <= 1.f) || !sampler_ok(&ss->sampler, cfg->V))) return SSC_EINVAL;   // NaN included
   if (!workspace || !loss || !kld) return SSC_EINVAL;
+  const bool ss_on = ss && ss->prob > 0.f;
   if (!ssc_aligned16(workspace)) return SSC_EALIGN;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
@@ -495,8 +516,13 @@ extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, c
   c.live_count = live; c.live_rows = live + 4;
   SSC_TRY(ssc_feat_prep(bt->feats, B, R, F, W + l.mask, W + l.avg, st));
   SSC_TRY(gemm(c, true, true, {{bt->feats, F, p->wv, p->ld_wv, F}}, B * R, A, W + l.pv, A));
-  SSC_TRY(ssc_embed_gather(p->emb, p->ld_emb, tok, TB, E, W + l.emb, l.Ep, st));
-  SSC_TRY(gemm(c, true, true, {{W + l.emb, l.Ep, p->att_w_ih, p->ld_att_w_ih, E}}, TB, H4, W + l.ga_static, H4));
+  // scheduled sampling: only step 0 (the boundary token) is known ahead of the loop; the rows of a later step are gathered by
+  // the mix kernel, and its block of ga_static follows it, inside the loop
+  const int hoisted = ss_on ? B : TB;
+  SSC_TRY(ssc_embed_gather(p->emb, p->ld_emb, tok, hoisted, E, W + l.emb, l.Ep, st));
+  SSC_TRY(gemm(c, true, true, {{W + l.emb, l.Ep, p->att_w_ih, p->ld_att_w_ih, E}}, hoisted, H4, W + l.ga_static, H4));
+  int64_t* fed_ids = (int64_t*)(W + l.fed_ids);
+  if (ss_on && hipMemcpyAsync(fed_ids, tok, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   SSC_TRY(gemm(c, true, true, {{W + l.avg, F, p->att_w_ih + E, p->ld_att_w_ih, F}}, B, H4, W + l.ga_avg, H4));
   // initial states (index 0 of every history), the KL accumulator, pad columns: one launch
   {
@@ -511,15 +537,39 @@ extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, c
       f.add(W + l.z, (size_t)TB * l.Zp); f.add(W + l.mu, (size_t)TB * l.Zp); f.add(W + l.lv, (size_t)TB * l.Zp);
     }
     if (cfg->tied) f.add(W + l.proj, (size_t)TB * l.Ep);  // padded rows stay finite through the tanh
+    if (ss_on) f.add(W + l.fed, (size_t)B);   // step 0 never samples
     SSC_TRY(fill_many(f, 0.f, st));
   }
   // (the rank-1 sentiment columns of W_ih^enc / W_ih^dec are made contiguous by prepare_weight_views)
   SSC_TRY(prepare_weight_views(l, p, W, st));
   const bool fc_adjacent = (p->fc_lv_w == p->fc_mean_w + (size_t)Z * p->ld_fc_mean_w) && p->ld_fc_lv_w == p->ld_fc_mean_w;
 
+  // scheduled sampling: the vocabulary head of ONE step (rows t*B .. t*B + B - 1 of h_dec -> the same rows of the logits block), all
+  // B rows of it: the draw of step t+1 reads these rows, cross-entropy reads the same bits after the loop
+  auto head_step = [&](int t) -> int {
+    const float* hd_t = W + l.hd + (size_t)(t + 1) * sH;
+    float* logits_t = W + l.logits + (size_t)t * B * l.Vp;
+    if (cfg->tied) {
+      float* proj_t = W + l.proj + (size_t)t * B * l.Ep;
+      SSC_TRY(gemm(c, true, true, {{hd_t, l.Hp, p->proj_w, p->ld_proj_w, H}}, B, E, proj_t, l.Ep));
+      SSC_TRY(ssc_bias_tanh(proj_t, l.Ep, B, E, p->proj_b, st));
+      return gemm(c, true, true, {{proj_t, l.Ep, p->emb, p->ld_emb, E}}, B, V, logits_t, l.Vp);
+    }
+    return gemm(c, true, true, {{hd_t, l.Hp, p->out_w, p->ld_out_w, H}}, B, V, logits_t, l.Vp, p->out_b);
+  };
+
   // ---- time loop ----------------------------------------------------------------------------------
   if (g_loop.on) { (void)hipEventRecord(g_loop.e[0], st); }
   for (int t = 0; t < T; ++t) {
+    if (ss_on && t > 0) {
+      // the word this step is fed: the head of step t-1, the decision and the draw, the fed word's embedding row and its gate block
+      SSC_TRY(head_step(t - 1));
+      float* emb_t = W + l.emb + (size_t)t * B * l.Ep;
+      SSC_TRY(ssc_sched_mix_rows(W + l.logits + (size_t)(t - 1) * B * l.Vp, l.Vp, B, V, tok + (size_t)t * B, W + l.w + (size_t)(t - 1) * B,
+                                 W + l.w + (size_t)t * B, p->emb, p->ld_emb, E, t, ss, fed_ids + (size_t)t * B, W + l.fed + (size_t)t * B,
+                                 emb_t, l.Ep, st));
+      SSC_TRY(gemm(c, true, true, {{emb_t, l.Ep, p->att_w_ih, p->ld_att_w_ih, E}}, B, H4, W + l.ga_static + (size_t)t * B * H4, H4));
+    }
     float* h1p = W + l.h1 + t * sH; float* h1n = h1p + sH;
     float* c1p = W + l.c1 + t * sH; float* c1n = c1p + sH;
     float* hep = W + l.he + t * sH; float* hen = hep + sH;
@@ -657,7 +707,9 @@ extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, c
   // ---- vocabulary projection + CE over all steps (updown_captioner.py:444-445, 457-466) -----------
   const float* hd_all = W + l.hd + sH;  // rows t*B+b = h_dec after step t
   // only the rows with a real target are projected (ssc_ce_fwd skips the others)
-  if (cfg->tied) {
+  if (ss_on) {
+    SSC_TRY(head_step(T - 1));   // every earlier step's rows were projected inside the loop
+  } else if (cfg->tied) {
     // (l.proj was zeroed with the initial states: padded rows stay finite through the tanh)
     SSC_TRY(gemm_rows(c, true, {{hd_all, l.Hp, p->proj_w, p->ld_proj_w, H}}, TB, E, W + l.proj, l.Ep));
     SSC_TRY(ssc_bias_tanh(W + l.proj, l.Ep, TB, E, p->proj_b, st));
@@ -669,6 +721,17 @@ extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, c
   SSC_TRY(ssc_ce_fwd_smooth_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, W + l.lse,
                                    W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st));
   return SSC_OK;
+}
+
+extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream) {
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, nullptr, stream);
+}
+
+extern "C" int ssc_train_fwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode,
+                                const ssc_sched_sampling* ss, void* stream) {
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, ss, stream);
 }
 
 // ---- posterior scoring of the forward that last ran in this workspace (include/ssc.h: ssc_train_posterior) ------------------------------
@@ -790,11 +853,11 @@ int ssc_g_dw_one_flush = ssc_env_int("SSC_DW_ONE_FLUSH", 1);
 // (ssc_runtime/engine.py): the output head's 48 MB travel under the whole time loop.
 static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                           size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream,
-                          unsigned phases, float free_bits, int free_bits_mode) {
+                          unsigned phases, float free_bits, int free_bits_mode, int fed_inputs = 0) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
   SSC_TRY(check_free_bits(free_bits, free_bits_mode));
-  if (!workspace || !gl || !gk || !g) return SSC_EINVAL;
+  if (!workspace || !gl || !gk || !g || (fed_inputs != 0 && fed_inputs != 1)) return SSC_EINVAL;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
@@ -1025,7 +1088,9 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     // zero the table gradient, then scatter-add rows by token id (padding_idx row gets none)
     if (hipMemset2DAsync(g->emb, (size_t)g->ld_emb * sizeof(float), 0, (size_t)E * sizeof(float), V, st) != hipSuccess)
       return SSC_EHIP;
-    SSC_TRY(ssc_embed_scatter_add(g->emb, g->ld_emb, tok, TB, E, W + l.demb, l.Ep, cfg->pad, st));
+    // (the rows are scattered by what the forward fed: the ground-truth inputs, or with scheduled sampling the fed ids)
+    SSC_TRY(ssc_embed_scatter_add(g->emb, g->ld_emb, fed_inputs ? (const int64_t*)(W + l.fed_ids) : tok, TB, E, W + l.demb, l.Ep,
+                                  cfg->pad, st));
   }
   }  // phase 2a
   // all weight-gradient products of a phase are queued at once
@@ -1197,7 +1262,19 @@ extern "C" int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* 
 extern "C" int ssc_train_bwd_phases_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                        size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
                                        unsigned phases, float free_bits, int free_bits_mode, void* stream) {
+  return ssc_train_bwd_phases_ss(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, free_bits, free_bits_mode, 0, stream);
+}
+
+extern "C" int ssc_train_bwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
+                                int free_bits_mode, int fed_inputs, void* stream) {
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, free_bits, free_bits_mode, fed_inputs);
+}
+
+extern "C" int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                       size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
+                                       unsigned phases, float free_bits, int free_bits_mode, int fed_inputs, void* stream) {
   if (phases == 0 || phases > 255u) return SSC_EINVAL;
   if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode, fed_inputs);
 }

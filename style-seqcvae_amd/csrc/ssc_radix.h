@@ -186,8 +186,8 @@ __device__ void radix_descent(const RowView<STAGED>& row, F&& offer, unsigned lo
 
 // The cut of a top-k (kind 1) / top-p (kind 2) row: kept <=> key > cut_key, or key == cut_key and v <= cut_idx.  mx is the
 // row's maximum, invz the inverse of its tempered normaliser sum_v exp((x_v - mx) / T) (read for top-p only).  Every thread
-// returns the same cut; kind 0, top_k >= V and top_p >= 1 keep every entry.  (sample_rows_kernel keeps this code inline: called
-// as a function it is laid out differently, and sample.hip's ISA is held fixed.)
+// returns the same cut; kind 0, top_k >= V and top_p >= 1 keep every entry.  (sample_draw_row in sample_draw.h, the draw of
+// sample_rows_kernel, keeps this code inline: called as a function it is laid out differently, and the samplers' ISA is held fixed.)
 template <bool STAGED>
 __device__ __forceinline__ void sample_cut(const RowView<STAGED>& row, int kind, int top_k, float top_p, float mx, float T,
                                            float invz, SampleShared& sh, uint32_t& cut_key, int& cut_idx) {

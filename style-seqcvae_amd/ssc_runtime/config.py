@@ -117,6 +117,13 @@ def _defaults() -> dict:
             # steps - the minibatch of one process.  A term at or below its floor has no gradient.  Self-critical steps and validation
             # are never annealed or floored
             "FREE_BITS": 0.0, "FREE_BITS_MODE": "dim",
+            # scheduled sampling of the cross-entropy steps (Bengio et al. 2015; ssc_runtime/schedule.py: ss_prob): from iteration
+            # SCHEDULED_SAMPLING_START on (-1 = off) a word the decoder is fed is, with a probability that rises by
+            # SCHEDULED_SAMPLING_INCREASE_PROB every SCHEDULED_SAMPLING_INCREASE_EVERY iterations up to SCHEDULED_SAMPLING_MAX_PROB,
+            # one the model draws from its own distribution of the previous step ("multinomial", at SCHEDULED_SAMPLING_TEMPERATURE)
+            # or its most likely word ("argmax").  Self-critical steps and validation never sample
+            "SCHEDULED_SAMPLING_START": -1, "SCHEDULED_SAMPLING_INCREASE_EVERY": 5000, "SCHEDULED_SAMPLING_INCREASE_PROB": 0.05,
+            "SCHEDULED_SAMPLING_MAX_PROB": 0.25, "SCHEDULED_SAMPLING_SAMPLER": "multinomial", "SCHEDULED_SAMPLING_TEMPERATURE": 1.0,
         },
     }
 
@@ -223,6 +230,18 @@ class Config(object):
             raise ValueError(f"OPTIM.FREE_BITS must be a finite number >= 0; found {o.FREE_BITS!r}")
         if o.FREE_BITS_MODE not in ("element", "step", "dim"):
             raise ValueError(f"OPTIM.FREE_BITS_MODE must be one of element | step | dim; found {o.FREE_BITS_MODE!r}")
+        integer = lambda x: isinstance(x, int) and not isinstance(x, bool)
+        if not integer(o.SCHEDULED_SAMPLING_START) or o.SCHEDULED_SAMPLING_START < -1:
+            raise ValueError(f"OPTIM.SCHEDULED_SAMPLING_START must be an iteration (an integer >= 0) or -1 for off; found {o.SCHEDULED_SAMPLING_START!r}")
+        if not integer(o.SCHEDULED_SAMPLING_INCREASE_EVERY) or o.SCHEDULED_SAMPLING_INCREASE_EVERY < 1:
+            raise ValueError(f"OPTIM.SCHEDULED_SAMPLING_INCREASE_EVERY must be an integer >= 1; found {o.SCHEDULED_SAMPLING_INCREASE_EVERY!r}")
+        for key in ("SCHEDULED_SAMPLING_INCREASE_PROB", "SCHEDULED_SAMPLING_MAX_PROB"):
+            if not num(o[key]) or not 0.0 <= o[key] <= 1.0:
+                raise ValueError(f"OPTIM.{key} must be a number in [0, 1]; found {o[key]!r}")
+        if o.SCHEDULED_SAMPLING_SAMPLER not in ("multinomial", "argmax"):
+            raise ValueError(f"OPTIM.SCHEDULED_SAMPLING_SAMPLER must be one of multinomial | argmax; found {o.SCHEDULED_SAMPLING_SAMPLER!r}")
+        if not num(o.SCHEDULED_SAMPLING_TEMPERATURE) or not 0.0 < o.SCHEDULED_SAMPLING_TEMPERATURE < float("inf"):
+            raise ValueError(f"OPTIM.SCHEDULED_SAMPLING_TEMPERATURE must be a finite number > 0; found {o.SCHEDULED_SAMPLING_TEMPERATURE!r}")
 
     def __getattr__(self, attr: str):
         return getattr(self.__dict__["_C"], attr)

@@ -122,6 +122,28 @@ def check_label_smoothing(x, name="label_smoothing") -> float:
     return v
 
 
+def check_sched_sampling(prob, sampler=None, seed=0) -> "Optional[_lib.SchedSampling]":
+    """ssc_sched_sampling for a forward, or None for prob 0 (teacher forcing: the call is then the one without it).  prob in [0, 1];
+    sampler: None (multinomial at temperature 1) or (kind, top_k, top_p, temperature) as ssc_sampler_desc has them - an object with
+    a word sampler of ssc_runtime/sampling.py (kind, k, p, temperature) will do -; seed: the one 64-bit seed of the decisions and the draws."""
+    try:
+        v = float(prob)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if isinstance(prob, bool) or not 0.0 <= v <= 1.0:
+        raise ValueError(f"ss_prob must be a number in [0, 1]; found {prob!r}")
+    if sampler is None:
+        sampler = (0, 0, 1.0, 1.0)
+    if not isinstance(sampler, (tuple, list)):
+        sampler = (sampler.kind, getattr(sampler, "k", 0), getattr(sampler, "p", 1.0), sampler.temperature)
+    kind, top_k, top_p, temperature = int(sampler[0]), int(sampler[1]), float(sampler[2]), float(sampler[3])
+    if kind not in (0, 1, 2) or not 0.0 < temperature < float("inf") or not 0.0 <= top_p <= 1.0 or (kind == 1 and top_k < 1):
+        raise ValueError(f"ss_sampler must be (kind 0 | 1 | 2, top_k >= 1 for kind 1, top_p in [0, 1], temperature > 0); found {sampler!r}")
+    if v == 0.0:
+        return None
+    return _lib.SchedSampling(v, _lib.SamplerDesc(kind, top_k, top_p, temperature, int(seed) & ((1 << 64) - 1)))
+
+
 FREE_BITS_MODES = {"element": 1, "step": 2, "dim": 3}   # ssc_free_bits.mode / the free_bits_mode argument of ssc_train_fwd_fb
 
 
@@ -327,6 +349,7 @@ class TrainEngine:
         self._keep = None
         self._kld = None              # the kld tensor the last forward returned (kld_raw() without a floor)
         self._fb = (0.0, 3)           # (free_bits, free_bits_mode) of the last forward: every backward of it is given the same
+        self._fed = 0                 # 1: the last forward sampled its inputs (ss_prob > 0) - every backward of it scatters by the fed ids
         self._post_ws = None          # posterior_forward's own workspace: the training forward's activations are never overwritten
         self._post_ws_key = None
         self._post = None
@@ -407,7 +430,8 @@ class TrainEngine:
                         eps.data_ptr(), obj_atts.data_ptr() if obj_atts is not None else None)
         return bt, (sent, obj_atts)
 
-    def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0, free_bits=0.0, free_bits_mode="dim"):
+    def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0, free_bits=0.0, free_bits_mode="dim",
+                ss_prob=0.0, ss_sampler=None, ss_seed=0):
         """-> (loss (B,), kld (B,)); keeps activations for backward().  obj_atts (B,R,S): per-region attribute means, kld_mode 2 only.
         label_smoothing: eps of THIS call's cross-entropy (ssc_ce_fwd_smooth; 0 = the plain masked NLL, the kernels as they are
         without it).  It stays in the engine's cfg until the next forward, so every backward of this forward - the phased one of
@@ -415,16 +439,26 @@ class TrainEngine:
         free_bits (nats) / free_bits_mode ("element" | "step" | "dim"): a floor on the KL of THIS call (include/ssc.h:
         ssc_free_bits) - kld is then the floored KL, a term at or below the floor has no gradient in the backward, kld_raw() is the
         KL without the floor.  0 = off: the kernels as they are without it.  "dim" floors the mean over the B rows of this call
-        of each latent dimension (under data parallelism: this rank's rows).  Kept beside the cfg until the next forward likewise."""
+        of each latent dimension (under data parallelism: this rank's rows).  Kept beside the cfg until the next forward likewise.
+        ss_prob / ss_sampler / ss_seed: scheduled sampling of THIS call (include/ssc.h: ssc_train_fwd_ss; check_sched_sampling) -
+        with probability ss_prob an eligible position is fed the word the model draws from its own logits of the previous step.
+        0 = off: ssc_train_fwd_fb as before.  input_tokens() / fed_mask() read what was fed; the engine remembers, until the next
+        forward, that every backward of this forward scatters the embedding gradient by the fed ids."""
         self._cfg.label_smoothing = check_label_smoothing(label_smoothing)
         self._fb = check_free_bits(free_bits, free_bits_mode)
+        ss = check_sched_sampling(ss_prob, ss_sampler, ss_seed)
+        self._fed = int(ss is not None)
         bt, sent = self._batch(feats, caps, sentiment, eps, obj_atts)
         ws = self._workspace(bt.B, bt.R, bt.L)
         loss = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         kld = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         p = self.params.c_struct()
-        self.lib.ssc_train_fwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                                  _lib.ptr(kld), *self._fb, _lib.stream_ptr())
+        if ss is None:
+            self.lib.ssc_train_fwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                      _lib.ptr(kld), *self._fb, _lib.stream_ptr())
+        else:
+            self.lib.ssc_train_fwd_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                      _lib.ptr(kld), *self._fb, C.byref(ss), _lib.stream_ptr())
         self._keep = (bt, feats, caps, sent, eps)
         self._kld = kld
         self.fwd_version += 1
@@ -512,8 +546,8 @@ class TrainEngine:
         # only what the update will read travels: a frozen decoder LSTM / tied embedding keeps its (stale) gradient range at home
         t_lo, t_hi = self.trainable_range(bool(set(self.decoder_names) & skipset))
         for mask, rng in self.phase_ranges():
-            self.lib.ssc_train_bwd_phases_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, _lib.stream_ptr())
+            self.lib.ssc_train_bwd_phases_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
+                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, self._fed, _lib.stream_ptr())
             if rng is not None:
                 lo, hi = max(rng[0], t_lo), min(rng[1], t_hi)
                 if hi > lo and xg is not None:
@@ -629,8 +663,8 @@ class TrainEngine:
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
         for mask in masks:
-            self.lib.ssc_train_bwd_phases_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, _lib.stream_ptr())
+            self.lib.ssc_train_bwd_phases_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
+                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, self._fed, _lib.stream_ptr())
 
     def backward(self, gl, gk, skip: Sequence[str] = ()):
         """Writes d(sum_b gl_b loss_b + gk_b kld_b)/dparam into self.grads for every parameter not in `skip`
@@ -643,13 +677,35 @@ class TrainEngine:
         g = self.grads.c_struct(only=only)
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
-        self.lib.ssc_train_bwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
-                                  _lib.ptr(gk), C.byref(g), *self._fb, _lib.stream_ptr())
+        self.lib.ssc_train_bwd_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                  _lib.ptr(gk), C.byref(g), *self._fb, self._fed, _lib.stream_ptr())
 
     def nll(self):
         """(B,) unsmoothed loss_b of the last forward (= its loss when that ran with label_smoothing 0): a view of the workspace,
         valid until the next forward."""
         return self.workspace_view(12)
+
+    def input_tokens(self):
+        """(T, B) int64: the ids the last forward fed to the attention LSTM - with scheduled sampling the fed ids block of the
+        workspace (a view, valid until the next forward), else the ground-truth inputs tok[:-1]."""
+        bt = self._keep[0]
+        T, B = bt.L + 1, bt.B
+        ws = self._workspace(bt.B, bt.R, bt.L)
+        view = self.lib.ssc_train_sched_view if self._fed else self.lib.ssc_train_workspace_view
+        p = view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), 13 if self._fed else 10, None)
+        off = (p - ws.data_ptr()) // 4
+        return ws[off:off + 2 * T * B].view(torch.int64).view(T, B)
+
+    def fed_mask(self):
+        """(T, B) bool: where the last forward fed the model's own word (all False without scheduled sampling)."""
+        bt = self._keep[0]
+        T, B = bt.L + 1, bt.B
+        if not self._fed:
+            return torch.zeros(T, B, dtype=torch.bool, device=self.device)
+        ws = self._workspace(bt.B, bt.R, bt.L)
+        p = self.lib.ssc_train_sched_view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), 14, None)
+        off = (p - ws.data_ptr()) // 4
+        return ws[off:off + T * B].view(T, B) != 0
 
     def kld_raw(self):
         """(B,) KL of the last forward without the free-bits floor: a view of the workspace, valid until the next forward - or,
@@ -836,17 +892,19 @@ class TrainEngine:
 
     def train_step(self, feats, caps, sentiment, eps, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
                    max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None,
-                   label_smoothing=0.0, kl_beta=1.0, free_bits=0.0, free_bits_mode="dim"):
+                   label_smoothing=0.0, kl_beta=1.0, free_bits=0.0, free_bits_mode="dim", ss_prob=0.0, ss_sampler=None, ss_seed=0):
         """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row.
         optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above.
         label_smoothing: as forward(); loss is then the smoothed one, nll() the unsmoothed.
         kl_beta: the annealing weight of this iteration (ssc_runtime/schedule.py) - the objective is mean loss + kl_beta * mean kld /
         kld_weight, so the upstream of kld_b is kl_beta / (B * kld_weight); 0 is legal: no KL gradient at all.
-        free_bits / free_bits_mode: as forward(); kld is then the floored KL, kld_raw() the raw one."""
+        free_bits / free_bits_mode: as forward(); kld is then the floored KL, kld_raw() the raw one.
+        ss_prob / ss_sampler / ss_seed: scheduled sampling, as forward()."""
         kl_beta = float(kl_beta)
         if not 0.0 <= kl_beta < float("inf"):
             raise ValueError(f"kl_beta must be a finite number >= 0; found {kl_beta!r}")
-        loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing, free_bits, free_bits_mode)
+        loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing, free_bits, free_bits_mode, ss_prob, ss_sampler,
+                                 ss_seed)
         B = loss.numel()
         key = (B, float(kld_weight))
         if getattr(self, "_upstream_key", None) != key:   # d(mean loss + beta mean kld / KLD_WEIGHT) / d(loss_b, kld_b): two (B,) buffers per (B, weight)

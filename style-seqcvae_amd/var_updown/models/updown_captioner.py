@@ -20,7 +20,7 @@ from ssc_runtime import sampling
 from ssc_runtime.cellops import cell_train_step
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.decoding import select_best_beam_with_constraints
-from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_free_bits, check_label_smoothing
+from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_free_bits, check_label_smoothing, check_sched_sampling
 
 from ..modules import ConstrainedBeamSearch, UpDownCell
 
@@ -29,8 +29,8 @@ class _SeqCVAETrainFn(torch.autograd.Function):
     """loss_b, kld_b = f(params; feats, caps, sentiment, eps) with the hand-derived BPTT as backward."""
 
     @staticmethod
-    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *params):
-        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode)
+    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, ss, *params):
+        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *ss)
         ctx.eng, ctx.names = eng, names
         ctx.version = eng.fwd_version
         return loss, kld
@@ -41,7 +41,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
         if eng.fwd_version != ctx.version:
             raise RuntimeError("UpDownCaptioner: backward() after a newer forward(); the activation workspace holds "
                                "only the latest forward")
-        need = ctx.needs_input_grad[10:]
+        need = ctx.needs_input_grad[11:]
         skip = [n for n, k in zip(ctx.names, need) if not k]
         eng.backward(gl, gk, skip=skip)
         if eng.dp_autograd:   # data parallel on the autograd path: ONE sum all-reduce of the flat gradient buffer, then the mean
@@ -50,7 +50,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
                 eng.grads.flat.mul_(1.0 / world)
         frozen = set(eng.frozen_names)
         grads = tuple(eng.grads.views[n].clone() if (k and n not in frozen) else None for n, k in zip(ctx.names, need))
-        return (None,) * 10 + grads
+        return (None,) * 11 + grads
 
 
 class UpDownCaptioner(nn.Module):
@@ -91,6 +91,7 @@ class UpDownCaptioner(nn.Module):
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.free_bits = check_free_bits(free_bits, free_bits_mode)[0]
         self.free_bits_mode = free_bits_mode
+        self._sched_sampling = (0.0, None, 0)   # scheduled_sampling(): off
         if diverse_beam is not None:
             if sampler is not None:
                 raise ValueError("MODEL.DIVERSE_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam' without MODEL.STOCHASTIC_BEAM_SEARCH")
@@ -339,7 +340,7 @@ class UpDownCaptioner(nn.Module):
             obj_means = self._obj_means(obj_atts, batch_size, num_boxes)
             loss, kld = _SeqCVAETrainFn.apply(eng, names, image_features.contiguous().float(),
                                               caption_tokens.contiguous().long(), sent, eps, obj_means, self.label_smoothing,
-                                              self.free_bits, self.free_bits_mode, *params)
+                                              self.free_bits, self.free_bits_mode, self._sched_sampling, *params)
             return {"loss": loss, "kld": kld}
         # eval branch (updown_captioner.py:324-366)
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
@@ -374,6 +375,15 @@ class UpDownCaptioner(nn.Module):
                 beams, lps = self._beam_search.search(start_predictions, None, step, fsm_d)
                 best = beams[:, 0, 0, :]
         return {"predictions": best}
+
+    def scheduled_sampling(self, prob, seed=0, sampler=None):
+        """Scheduled sampling of the NEXT training forwards (the autograd path; include/ssc.h: ssc_train_fwd_ss): with probability
+        `prob` an eligible position is fed the word the model draws from its own logits of the previous step, the draws and the
+        decisions seeded by `seed` (ssc_runtime.schedule.ss_seed for a resumable run: call this once per iteration).  sampler: None
+        (multinomial, temperature 1), a word sampler of ssc_runtime.sampling, or (kind, top_k, top_p, temperature).  prob 0 (the
+        default state) = off.  The eval forward, scst_step, score_captions and posterior_score_captions never sample."""
+        check_sched_sampling(prob, sampler, seed)
+        self._sched_sampling = (float(prob), sampler, int(seed))
 
     def score_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, obj_atts=None,
                        n_samples: Optional[int] = None, layout: str = "padded", want_tokens: bool = False, want_ranks: bool = False,
