@@ -93,6 +93,10 @@ typedef struct {
    * vocabulary head of a decode step then never writes its (rows, V) logits: ssc_beam_step_parts selects from the records.
    * NT products with 16-byte aligned operands under the 3xBF16 / 2xFP16 numerics only (SSC_EINVAL otherwise). */
   float* topk_part;
+  /* Optional, ssc_gemm_dw_group only (SSC_EINVAL elsewhere): a second destination (M x N, ld ldc2 >= N) that receives the values
+   * stored to C - two gradients that are the same product (an LSTM's W_hh and the recurrent block of its W_ih).  A work-list member
+   * stores both from its tile epilogue; any other member is followed by a copy. */
+  float* C2; int ldc2;
 } ssc_gemm_desc;
 
 /* out[0] = 2^(target_log2 - ceil(log2(max |x|))) over the rows x cols block x (ld), a power of two that brings the block's largest
@@ -128,7 +132,7 @@ int ssc_gemm_auto_splits(int M, int N, int ksteps); /* the split count ssc_gemm 
  * Per-sequence precompute
  * ---------------------------------------------------------------------------------------------- */
 /* region mask + masked mean: UpDownCell._average_image_features (updown_cell.py:233-270) +
- * allennlp masked_mean.  feats (B,R,F) -> mask (B,R) float {0,1}, avg (B,F). */
+ * allennlp masked_mean.  feats (B,R,F) -> mask (B,R) float {0,1}, avg (B,F).  One pass over feats; R <= 12288. */
 int ssc_feat_prep(const float* feats, int B, int R, int F, float* mask, float* avg, void* stream);
 
 /* boundary tokens + loss weights: allennlp add_sentence_boundary_token_ids as called at
@@ -136,6 +140,13 @@ int ssc_feat_prep(const float* feats, int B, int R, int F, float* mask, float* a
  * w_tm (T=L+1,B) float = [tokens[b,t+1] != pad], nvalid (B) float = sum_t w. */
 int ssc_prep_tokens(const int64_t* caps, int B, int L, int pad, int boundary, int64_t* tokens_tm, float* w_tm,
                     float* nvalid, void* stream);
+
+/* ssc_prep_tokens plus the two ascending row lists of the train step, in one launch: act = rows t*B+b with w = 1, live = rows
+ * with w = 1 at step t or at any later step of caption b.  Each list is int32 [count, 3 unused, rows ... (T*B entries)].
+ * ident (optional, B + 4 entries): the list of the rows 0 .. B-1 in the same layout - the k-row list of a product over the B rows
+ * of a per-row sum when it joins the work list of ssc_gemm_dw_group. */
+int ssc_prep_tokens_rows(const int64_t* caps, int B, int L, int pad, int boundary, int64_t* tokens_tm, float* w_tm,
+                         float* nvalid, int* act, int* live, int* ident, void* stream);
 
 /* nn.Embedding forward (updown_captioner.py:430): out[i,:] = table[ids[i],:]  (n rows, E cols). */
 int ssc_embed_gather(const float* table, int ldt, const int64_t* ids, int n, int E, float* out, int ldo, void* stream);

@@ -23,6 +23,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "ssc_common.h"
 #include "ssc_debug.h"
 
@@ -1111,6 +1113,7 @@ template <int TM, int TN> constexpr int x3w_lds_bytes_f16() { return 2 * 2 * (X3
 // F16: the operands are split into two fp16 planes and multiplied with THREE partial products (lo*hi, hi*lo, hi*hi) on
 // v_mfma_f32_32x32x16_f16 instead of three bf16 planes and six products - half the matrix-pipe work of a product that is bound by
 // it (the decode's 10000-row products: DESIGN.md).  LDS layout unchanged (plane 2 of each operand stays unused).
+struct KTnArgs;   // one member of a work list (below): the only argument form with a second destination
 template <bool A_KC, bool B_KC, bool KG, int TM, int TN, int PF, int NPW, bool F16 = false, class Args = KArgs>
 __device__ __forceinline__ void x3w_body(const Args& a, const int blk_x, const int blk_y, const int blk_z, const int grid_x,
                                          const int grid_y, const int grid_z, const int thr) {   // thr: threadIdx.x
@@ -1664,11 +1667,27 @@ __device__ __forceinline__ void x3w_body(const Args& a, const int blk_x, const i
         } else {
           *reinterpret_cast<float4*>(dst) = v;
         }
+        if constexpr (std::is_same_v<Args, KTnArgs>) {   // a work-list member's second destination: the same values once more
+          if (a.out2) {
+            float* dst2 = a.out2 + (size_t)grow * a.ldo2 + gcol;
+            if (!(a.ldo2 & 3) && !(reinterpret_cast<uintptr_t>(a.out2) & 15)) {
+              *reinterpret_cast<float4*>(dst2) = v;
+            } else {
+              dst2[0] = v.x; dst2[1] = v.y; dst2[2] = v.z; dst2[3] = v.w;
+            }
+          }
+        }
       } else {
         const float e[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          if (gcol + q < a.N) dst[q] = e[q] + (a.bias ? a.bias[gcol + q] : 0.f) + (a.accumulate ? dst[q] : 0.f);
+          if (gcol + q < a.N) {
+            const float r = e[q] + (a.bias ? a.bias[gcol + q] : 0.f) + (a.accumulate ? dst[q] : 0.f);
+            dst[q] = r;
+            if constexpr (std::is_same_v<Args, KTnArgs>) {
+              if (a.out2) a.out2[(size_t)grow * a.ldo2 + gcol + q] = r;
+            }
+          }
         }
       }
     }
@@ -1727,6 +1746,8 @@ struct KTnMember {
   const int* kbrows;
   int lda, ldb, ldc, M, N, K, accumulate;
   int first;           // index of the member's first tile in the list
+  float* C2;           // optional second destination of every C tile (ld ldc2)
+  int ldc2;
 };
 struct KTnList {
   KTnMember m[SSC_DW_MAX];
@@ -1749,6 +1770,8 @@ struct KTnArgs {   // the fields of KArgs x3w_body reads, for one member of a wo
   int tile_gm, store_wt, member;
   float* topk;
   const float *a_scale, *b_scale;
+  float* out2;
+  int ldo2;
 };
 template <int PF, int NPW>
 __global__ __launch_bounds__(256 + 64 * NPW, 1) void gemm_x3w_kernel_tn_list(const KTnList g) {
@@ -1773,6 +1796,7 @@ __global__ __launch_bounds__(256 + 64 * NPW, 1) void gemm_x3w_kernel_tn_list(con
     a.kcount = m.kcount; a.karows = m.karows; a.kbrows = m.kbrows;
     a.tile_gm = g.tile_gm; a.store_wt = g.store_wt; a.member = p;
     a.topk = nullptr; a.a_scale = a.b_scale = nullptr;
+    a.out2 = m.C2; a.ldo2 = m.ldc2;
     const int gx = (m.N + 127) / 128, gy = (m.M + 127) / 128;
     const int local = t - m.first;
     x3w_body<false, false, true, 128, 128, PF, NPW>(a, local % gx, local / gx, 0, gx, gy, 1, thr);
@@ -2413,6 +2437,7 @@ int launch_tn_list(const ssc_gemm_desc* const* d, const KArgs* ka, int n, hipStr
     m.kcount = di->k_count; m.karows = di->ka_rows; m.kbrows = di->kb_rows;
     m.lda = di->seg[0].lda; m.ldb = di->seg[0].ldb; m.ldc = di->ldc;
     m.M = di->M; m.N = di->N; m.K = di->seg[0].K; m.accumulate = di->accumulate;
+    m.C2 = di->C2; m.ldc2 = di->ldc2;
     m.first = first;
     first += ssc_cdiv(di->M, 128) * ssc_cdiv(di->N, 128);
     MN += (long)di->M * di->N;
@@ -2444,6 +2469,7 @@ extern "C" int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, void* str
     const ssc_gemm_desc* dj = d[j];
     KArgs& k = ka[j];
     SSC_TRY(build_args(dj, k));
+    if (dj->C2 && (dj->ldc2 < dj->N || !dj->C)) return SSC_EINVAL;
     const bool kg = k.karows || k.kbrows;
     // a member may run on the wave-specialised kernel and is a single-segment TN product with a direct output; it has all three
     // k-row lists (and no bias: work list) or none of them (group)
@@ -2487,10 +2513,18 @@ extern "C" int ssc_gemm_dw_group(const ssc_gemm_desc* const* d, int n, void* str
       SSC_TRY(launch_x3w(x3w_big(false, false, false), g, false, false, "128x128 TN group", rec, st));
       i += m;
     } else {  // a single list-less product gains nothing from the group form; ineligible ones take the usual path
-      SSC_TRY(ssc_gemm(d[i], (void*)st));
+      ssc_gemm_desc one = *d[i];
+      one.C2 = nullptr;
+      SSC_TRY(ssc_gemm(&one, (void*)st));
       ++i;
     }
   }
+  // a second destination outside the work list (whose tile epilogue stores it): a copy of the finished block
+  for (int j = 0; j < n; ++j)
+    if (d[j]->C2 && cls[j] != 2 &&
+        hipMemcpy2DAsync(d[j]->C2, (size_t)d[j]->ldc2 * sizeof(float), d[j]->C, (size_t)d[j]->ldc * sizeof(float),
+                         (size_t)d[j]->N * sizeof(float), d[j]->M, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return SSC_EHIP;
   return SSC_OK;
 }
 
@@ -2539,6 +2573,7 @@ extern "C" int ssc_gemm(const ssc_gemm_desc* d, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   KArgs k;
   SSC_TRY(build_args(d, k));
+  if (d->C2) return SSC_EINVAL;   // (ssc_gemm_dw_group only)
   if (d->topk_part) {   // records instead of C: one pass, wave-specialised 128x128 NT form (plan() refuses anything else)
     k.out = nullptr; k.ldo = d->N; k.slab_stride = 0; k.bias = d->bias; k.accumulate = 0;
     return launch(d, k, 1, st);
@@ -2642,7 +2677,7 @@ const DebugKey g_debug_keys[] = {
     {"store_wt", &g_store_wt},       // wave-specialised kernels: write-through (sc1) output stores (0 | 1)   (SSC_STORE_WT)
     {"tile_gm", &g_tile_gm},         // tile rows per group of the tile order (8; 0 = row-major)   (SSC_TILE_GM)
     {"dw_one_flush", &ssc_g_dw_one_flush},     // train backward in one call: the weight gradients of all phases as one work list (1 | 0 = one launch per phase)   (SSC_DW_ONE_FLUSH)
-    {"dec_dedup", &ssc_g_dec_dedup},           // decode: parent-state products on the distinct parents of a beam group (1 | 0)   (SSC_DEC_DEDUP)
+    {"dec_dedup", &ssc_g_dec_dedup},         // decode: parent-state products on the distinct parents of a beam group (1 | 0)   (SSC_DEC_DEDUP)
     {"beam_reg", &ssc_g_beam_reg},             // decode: beam selection with the vocabulary row in registers (1 | 0)              (SSC_BEAM_REG)
     {"img_mfma", &ssc_g_img_mfma},             // decode: the image cell's table contraction on the fp32 matrix cores (1 | 0 = VALU form)   (SSC_IMG_MFMA)
     {"dec_ungathered", &ssc_g_dec_ungathered}, // decode: states left in the previous step's row order, read through the parent lists (1 | 0)   (SSC_DEC_UNGATHERED)

@@ -16,31 +16,52 @@ namespace {
 // ---------------------------------------------------------------------------------------------
 // feat_prep: mask[b,r] = (sum_f |v| > 0) ; avg[b,f] = sum_r mask*v / max(sum_r mask, 1e-8)
 // ---------------------------------------------------------------------------------------------
-__global__ void feat_mask_kernel(const float* __restrict__ feats, int BR, int F, float* __restrict__ mask) {
-  int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
-  if (row >= BR) return;
-  const float* p = feats + (size_t)row * F;
-  float s = 0.f;
-  for (int f = lane; f < F; f += 64) s += fabsf(p[f]);
-  s = ssc_wave_sum(s);
-  if (lane == 0) mask[row] = s > 0.f ? 1.f : 0.f;
-}
-
-__global__ void feat_avg_kernel(const float* __restrict__ feats, const float* __restrict__ mask, int R, int F,
-                                float* __restrict__ avg) {
-  int b = blockIdx.y;
-  int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= F) return;
-  const float* p = feats + (size_t)b * R * F + f;
-  const float* m = mask + (size_t)b * R;
-  float s = 0.f, n = 0.f;
-  for (int r = 0; r < R; ++r) {
-    float mr = m[r];
-    s += mr * p[(size_t)r * F];
-    n += mr;
+// One workgroup per image, ONE pass over its (R, F) block.  Thread = column (1024 per sweep): it walks the R regions with eight
+// loads in flight and sums them in region order - a masked region is an all-zero row and adds exactly zero, so the sum needs no
+// mask and no multiply - and every wave flags the regions in which it met a non-zero entry (sum_f |v| > 0 <=> some v != 0).
+// Then the workgroup forms the mask and the count and divides the sums it left in avg.
+constexpr int kFeatPrepThreads = 1024;
+__global__ __launch_bounds__(kFeatPrepThreads) void feat_prep_kernel(const float* __restrict__ feats, int R, int F,
+                                                                     float* __restrict__ mask, float* avg) {
+  extern __shared__ int nz[];   // [R]
+  __shared__ float wave_n[kFeatPrepThreads / 64];
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+  const float* p = feats + (size_t)b * R * F;
+  for (int r = tid; r < R; r += kFeatPrepThreads) nz[r] = 0;
+  __syncthreads();
+  for (int f0 = 0; f0 < F; f0 += kFeatPrepThreads) {
+    const int f = f0 + tid;
+    const bool in = f < F;
+    const int fc = in ? f : F - 1;
+    float s = 0.f;
+    for (int r = 0; r < R; r += 8) {
+      float x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) x[u] = p[(size_t)min(r + u, R - 1) * F + fc];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (r + u < R) {
+          s += x[u];
+          const bool any = __ballot(in && fabsf(x[u]) > 0.f) != 0ull;
+          if (any && lane == 0) nz[r + u] = 1;   // (every writer stores the same value)
+        }
+    }
+    if (in) avg[(size_t)b * F + f] = s;
   }
-  avg[(size_t)b * F + f] = s / fmaxf(n, 1e-8f);
+  __syncthreads();
+  float n = 0.f;   // a count: exact in any order
+  for (int r = tid; r < R; r += kFeatPrepThreads) {
+    const float m = nz[r] ? 1.f : 0.f;
+    mask[(size_t)b * R + r] = m;
+    n += m;
+  }
+  n = ssc_wave_sum(n);
+  if (lane == 0) wave_n[tid >> 6] = n;
+  __syncthreads();
+  n = 0.f;
+  for (int q = 0; q < kFeatPrepThreads / 64; ++q) n += wave_n[q];
+  const float d = fmaxf(n, 1e-8f);
+  for (int f = tid; f < F; f += kFeatPrepThreads) avg[(size_t)b * F + f] = avg[(size_t)b * F + f] / d;   // this thread's own sums
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -754,9 +775,17 @@ __global__ void colsum_kernel(const float* __restrict__ X, int ldx, int rows, in
   int n = blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   float s = 0.f;
-  for (int r = 0; r < rows; ++r) {
-    float x = X[(size_t)r * ldx + n];
-    s += wrow ? wrow[r] * x : x;
+  for (int r = 0; r < rows; r += 8) {  // 8 row loads in flight, summed in row order
+    float x[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int rr = min(r + u, rows - 1);
+      x[u] = X[(size_t)rr * ldx + n];
+      if (wrow) x[u] = wrow[rr] * x[u];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (r + u < rows) s += x[u];
   }
   float* o = out + (size_t)n * out_stride;
   *o = accumulate ? *o + s : s;
@@ -913,10 +942,8 @@ inline hipStream_t S(void* s) { return (hipStream_t)s; }
 // =============================================================================================
 extern "C" int ssc_feat_prep(const float* feats, int B, int R, int F, float* mask, float* avg, void* stream) {
   if (!feats || !mask || !avg || B <= 0 || R <= 0 || F <= 0) return SSC_EINVAL;
-  int BR = B * R;
-  SSC_LAUNCH(feat_mask_kernel, dim3(ssc_cdiv(BR, 4)), dim3(256), 0, S(stream), feats, BR, F, mask);
-  SSC_CHECK_LAUNCH();
-  SSC_LAUNCH(feat_avg_kernel, dim3(ssc_cdiv(F, 256), B), dim3(256), 0, S(stream), feats, mask, R, F, avg);
+  if ((size_t)R * sizeof(int) > 48 * 1024) return SSC_EINVAL;   // the region flags of one image live in LDS
+  SSC_LAUNCH(feat_prep_kernel, dim3(B), dim3(kFeatPrepThreads), (size_t)R * sizeof(int), S(stream), feats, R, F, mask, avg);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }

@@ -12,6 +12,7 @@
 //  * torch.cat inputs never built: each K-segment of a gate GEMM reads its own source buffer;
 //  * vocabulary projection + CE over all T steps at once (M = T*B);
 //  * every weight gradient is one GEMM with K = T*B after the time loop.
+#include <climits>
 #include <cstdlib>
 #include <initializer_list>
 
@@ -41,6 +42,8 @@ struct Layout {
                        // buffer's place depends on them
   size_t kld_raw, fb_kdim, fb_gdim, fb_gstep, fb_acc;   // free bits (ssc_train_fwd_fb with free_bits > 0): the raw KL (B), K_j and the dimension gates (Z each),
                                                         // the step gates (T*B), the (B, Zp) accumulator of mode 3.  Behind nll, reserved for any cfg
+  size_t ident;   // int32, the layout of `live`: count B, rows 0 .. B-1 (the k-row list of a product over the B rows of a per-row sum).
+                  // Behind every other block, so that no offset moves
   size_t fed_ids, fed;   // scheduled sampling (ssc_train_fwd_ss with prob > 0): the ids the forward fed (T*B int64) and 1.0 where such an id was
                          // the model's own word (T*B).  Behind the free-bits blocks, reserved for any cfg
   size_t sl_q, sl_mulv, sl_gh1, sl_ghd, sl_ghd2, sl_ghe, sl_dqw, sl_dhe, sl_dz, small_floats, wsum_att, wsum_dec, wz;
@@ -142,6 +145,7 @@ Layout make_layout(const ssc_model_cfg* c, int B, int R, int L) {
   l.fb_acc = l.take((size_t)B * l.Zp);
   l.fed_ids = l.take(2 * TB);
   l.fed = l.take(TB);
+  l.ident = l.take((size_t)B + 4);
   return l;
 }
 
@@ -221,14 +225,18 @@ struct DwBatch {
   ssc_gemm_desc d[MAX];
   int n = 0;
 };
-int queue_dw(const Ctx& c, DwBatch& q, const float* A, int lda, const float* Bm, int ldb, int K, int M, int N, float* C, int ldc) {
+int queue_dw(const Ctx& c, DwBatch& q, const float* A, int lda, const float* Bm, int ldb, int K, int M, int N, float* C, int ldc,
+             const int* klist = nullptr, float* C2 = nullptr, int ldc2 = 0) {
+  // klist: a k-row list of the product's own (header + rows) instead of the live rows; C2: a second destination of the result
   if (q.n >= DwBatch::MAX) return SSC_EINVAL;
   ssc_gemm_desc& d = q.d[q.n++];
   fill_desc(d, false, false, {{A, lda, Bm, ldb, K}}, M, N);
   d.C = C; d.ldc = ldc;
+  d.C2 = C2; d.ldc2 = ldc2;
   d.splits = 0;
   d.workspace = c.slabs; d.workspace_floats = c.slab_floats;
-  if (c.live_rows) { d.k_count = c.live_count; d.ka_rows = c.live_rows; d.kb_rows = c.live_rows; }
+  if (klist) { d.k_count = klist; d.ka_rows = klist + 4; d.kb_rows = klist + 4; }
+  else if (c.live_rows) { d.k_count = c.live_count; d.ka_rows = c.live_rows; d.kb_rows = c.live_rows; }
   return SSC_OK;
 }
 int flush_dw(const Ctx& c, DwBatch& q) {
@@ -251,17 +259,14 @@ int flush_dw(const Ctx& c, DwBatch& q) {
 }
 // Workgroup 0: ascending list of the rows t*B+b whose target token is not padding (w = 1).  Workgroup 1: ascending list of
 // the rows that are not in the padding SUFFIX of their caption (w = 1 at step t or at a later step of caption b).
-// One workgroup per list, ordered block scan.
-__global__ __launch_bounds__(1024) void build_active_rows_kernel(const float* __restrict__ w, int n, int B, int* __restrict__ act,
-                                                                 int* __restrict__ live) {
-  __shared__ int part[1024];
+// One workgroup per list, ordered block scan.  wt(i) = row i has w != 0.
+template <class WT>
+__device__ __forceinline__ void ordered_row_list(WT wt, bool suffix, int n, int B, int* __restrict__ out, int* part) {
   const int tid = threadIdx.x;
-  const bool suffix = blockIdx.x == 1;
-  int* out = suffix ? live : act;
   auto flag = [&](int i) -> bool {
-    if (!suffix) return w[i] != 0.f;
+    if (!suffix) return wt(i);
     for (int r = i; r < n; r += B)   // same caption, this step and every later one
-      if (w[r] != 0.f) return true;
+      if (wt(r)) return true;
     return false;
   };
   const int per = (n + 1023) / 1024;
@@ -282,6 +287,54 @@ __global__ __launch_bounds__(1024) void build_active_rows_kernel(const float* __
   if (tid == 1023) out[0] = part[1023];
   // entries past the count are never read by a product; keep them in range anyway
   for (int i = part[1023] + tid; i < n; i += 1024) out[4 + i] = 0;
+}
+// Workgroup 2 (launched when the caller wants it): the list of the rows 0 .. B-1, same header.
+__device__ __forceinline__ void identity_row_list(int B, int* __restrict__ out) {
+  if (threadIdx.x == 0) out[0] = B;
+  for (int i = threadIdx.x; i < B; i += blockDim.x) out[4 + i] = i;
+}
+__global__ __launch_bounds__(1024) void build_active_rows_kernel(const float* __restrict__ w, int n, int B, int* __restrict__ act,
+                                                                 int* __restrict__ live, int* __restrict__ ident) {
+  __shared__ int part[1024];
+  if (blockIdx.x == 2) { identity_row_list(B, ident); return; }
+  const bool suffix = blockIdx.x == 1;
+  ordered_row_list([&](int i) { return w[i] != 0.f; }, suffix, n, B, suffix ? live : act, part);
+}
+// ssc_prep_tokens and the two row lists as ONE launch: a thread per row (t, b) forms the row's token and loss weight from the
+// caption itself (nothing is read back), both workgroups keep the weights in LDS for their list, workgroup 0 stores the
+// ssc_prep_tokens outputs.  The token at time-major position t+1 of caption b with nb real tokens: the closing boundary at
+// t = nb, the caption's token before it, its padding (then the extra 0 row) after it.
+constexpr int kPrepRowsMaxLds = 60 * 1024;   // one byte per row beside the scan's 4 KiB
+__global__ __launch_bounds__(1024) void prep_tokens_rows_kernel(const int64_t* __restrict__ caps, int B, int L, int pad, int boundary,
+                                                                int64_t* __restrict__ tok, float* __restrict__ w,
+                                                                float* __restrict__ nvalid, int* __restrict__ act,
+                                                                int* __restrict__ live, int* __restrict__ ident) {
+  extern __shared__ unsigned char wsh[];   // [n]
+  __shared__ int part[1024];
+  if (blockIdx.x == 2) { identity_row_list(B, ident); return; }
+  const int n = (L + 1) * B;
+  const bool first = blockIdx.x == 0;
+  for (int i = threadIdx.x; i < n; i += 1024) {
+    const int t = i / B, b = i - t * B;
+    const int64_t* cb = caps + (size_t)b * L;
+    int nb = 0;
+    for (int j = 0; j < L; ++j) nb += cb[j] != pad;
+    auto token = [&](int tt) -> int64_t { return tt == nb ? (int64_t)boundary : tt < L ? cb[tt] : (int64_t)0; };
+    const int64_t tk = token(t);
+    const bool on = tk != pad;
+    wsh[i] = on;
+    if (!first) continue;
+    tok[(size_t)(t + 1) * B + b] = tk;
+    w[i] = on ? 1.f : 0.f;
+    if (t == 0) {
+      tok[b] = boundary;
+      float nv = 0.f;
+      for (int tt = 0; tt <= L; ++tt) nv += token(tt) != pad ? 1.f : 0.f;
+      nvalid[b] = nv;
+    }
+  }
+  __syncthreads();
+  ordered_row_list([&](int i) { return wsh[i] != 0; }, !first, n, B, first ? act : live, part);
 }
 
 // GEMM that leaves its split-K slabs (M x N, ld N) in `region` for a fused epilogue / consumer
@@ -422,6 +475,25 @@ extern "C" int ssc_prof_loop_ms(float* fwd_loop_ms, float* bwd_loop_ms) {
   return SSC_OK;
 }
 
+extern "C" int ssc_prep_tokens_rows(const int64_t* caps, int B, int L, int pad, int boundary, int64_t* tokens_tm, float* w_tm,
+                                    float* nvalid, int* act, int* live, int* ident, void* stream) {
+  if (!caps || !tokens_tm || !w_tm || !nvalid || !act || !live || B <= 0 || L <= 0) return SSC_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)(L + 1) * B;
+  if (n > (size_t)INT_MAX) return SSC_EINVAL;
+  if (n <= (size_t)kPrepRowsMaxLds) {
+    SSC_LAUNCH(prep_tokens_rows_kernel, dim3(ident ? 3 : 2), dim3(1024), n, st, caps, B, L, pad, boundary, tokens_tm, w_tm, nvalid,
+               act, live, ident);
+    SSC_CHECK_LAUNCH();
+    return SSC_OK;
+  }
+  // more rows than one workgroup's LDS holds: the weights go through memory, two launches
+  SSC_TRY(ssc_prep_tokens(caps, B, L, pad, boundary, tokens_tm, w_tm, nvalid, stream));
+  SSC_LAUNCH(build_active_rows_kernel, dim3(ident ? 3 : 2), dim3(1024), 0, st, w_tm, (int)n, B, act, live, ident);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
 extern "C" size_t ssc_train_workspace_bytes(const ssc_model_cfg* cfg, int B, int R, int L) {
   if (!cfg || B <= 0 || R <= 0 || L <= 0) return 0;
   return make_layout(cfg, B, R, L).total * sizeof(float);
@@ -507,11 +579,9 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   const bool fb_on = free_bits > 0.f;   // a free-bits floor on the KL: the _fb kernels of the latent head, else today's
 
   // ---- per-sequence precompute --------------------------------------------------------------
-  SSC_TRY(ssc_prep_tokens(bt->caps, B, l.L, cfg->pad, cfg->boundary, tok, W + l.w, W + l.nvalid, st));
   int* act = (int*)(W + l.act);
   int* live = (int*)(W + l.live);
-  SSC_LAUNCH(build_active_rows_kernel, dim3(2), dim3(1024), 0, st, W + l.w, TB, B, act, live);
-  SSC_CHECK_LAUNCH();
+  SSC_TRY(ssc_prep_tokens_rows(bt->caps, B, l.L, cfg->pad, cfg->boundary, tok, W + l.w, W + l.nvalid, act, live, (int*)(W + l.ident), st));
   c.act_count = act; c.act_rows = act + 4;
   c.live_count = live; c.live_rows = live + 4;
   SSC_TRY(ssc_feat_prep(bt->feats, B, R, F, W + l.mask, W + l.avg, st));
@@ -1098,8 +1168,12 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     if (g->att_w_ih) {
       float* gw = g->att_w_ih; int ld = g->ld_att_w_ih;
       SSC_TRY(queue_dw(c, q, dga, H4, W + l.emb, l.Ep, TB, H4, E, gw, ld));
-      SSC_TRY(queue_dw(c, q, dga, H4, h1_prev, l.Hp, TB, H4, H, gw + E + F, ld));
+      // dW_hh^att = dGa^T H1_prev is the same product as the h1' block of dW_ih^att (both multiply h1'): a second destination
+      SSC_TRY(queue_dw(c, q, dga, H4, h1_prev, l.Hp, TB, H4, H, gw + E + F, ld, nullptr, g->att_w_hh, g->ld_att_w_hh));
       SSC_TRY(queue_dw(c, q, dga, H4, hd_prev, l.Hp, TB, H4, H, gw + E + F + H, ld));
+      // the averaged-feature block: avg is the same at every step, so dGa^T [avg ...] = (sum_t dGa)^T avg, a K = B product.  It
+      // rides in the work list under the identity list (its two-k-step tiles fill the last rounds), not in a launch of its own
+      SSC_TRY(queue_dw(c, q, W + l.dga_sum, H4, W + l.avg, F, B, H4, F, gw + E, ld, (const int*)(W + l.ident)));
     } else if (g->att_w_hh) {
       SSC_TRY(queue_dw(c, q, dga, H4, h1_prev, l.Hp, TB, H4, H, g->att_w_hh, g->ld_att_w_hh));
     }
@@ -1132,7 +1206,8 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
       float* gw = g->dec_w_ih; int ld = g->ld_dec_w_ih;
       SSC_TRY(queue_dw(c, q, dgd, H4, att, l.Fp, TB, H4, F, gw, ld));
       SSC_TRY(queue_dw(c, q, dgd, H4, h1_new, l.Hp, TB, H4, H, gw + F, ld));
-      SSC_TRY(queue_dw(c, q, dgd, H4, hd_prev, l.Hp, TB, H4, H, gw + F + H, ld));
+      // dW_hh^dec = dGd^T HD_prev is the same product as the hd' block of dW_ih^dec: a second destination
+      SSC_TRY(queue_dw(c, q, dgd, H4, hd_prev, l.Hp, TB, H4, H, gw + F + H, ld, nullptr, g->dec_w_hh, g->ld_dec_w_hh));
       if (l.Zp != Z) {
         // Z no multiple of 4: the z-block product runs on the padded Zp columns of z (zero pads) into the forward's aligned
         // z-block copy - free since the BPTT loop ended - and its Z real columns are copied into place below
@@ -1158,19 +1233,6 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     SSC_TRY(flush_dw(c, dwq));
   }
   // attention LSTM
-  if (g->att_w_ih) {
-    float* gw = g->att_w_ih; int ld = g->ld_att_w_ih;
-    SSC_TRY(gemm(c, false, false, {{W + l.dga_sum, H4, W + l.avg, F, B}}, H4, F, gw + E, ld));
-  }
-  if (g->att_w_hh) {
-    // dW_hh^att = dGa^T H1_prev is the same product as the h1' block of dW_ih^att (both multiply h1'): copy, do not recompute
-    if (g->att_w_ih) {
-      if (hipMemcpy2DAsync(g->att_w_hh, (size_t)g->ld_att_w_hh * sizeof(float), g->att_w_ih + E + F,
-                           (size_t)g->ld_att_w_ih * sizeof(float), (size_t)H * sizeof(float), H4, hipMemcpyDeviceToDevice,
-                           st) != hipSuccess)
-        return SSC_EHIP;
-    }
-  }
   if (g->att_b_ih && g->att_b_hh) {
     SSC_TRY(ssc_colsum2(dga, H4, TB, H4, nullptr, g->att_b_ih, 1, g->att_b_hh, 0, c.slabs, st));
   } else {
@@ -1202,8 +1264,12 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   }
   // latent heads
   const float* dmulv = W + l.dmulv;
-  if (g->fc_mean_b) SSC_TRY(ssc_colsum2(dmulv, 2 * Z, TB, Z, nullptr, g->fc_mean_b, 1, nullptr, 0, c.slabs, st));
-  if (g->fc_lv_b) SSC_TRY(ssc_colsum2(dmulv + Z, 2 * Z, TB, Z, nullptr, g->fc_lv_b, 1, nullptr, 0, c.slabs, st));
+  if (g->fc_mean_b && g->fc_lv_b == g->fc_mean_b + Z) {   // adjacent in the flat store, like the weights: one pass, same bits
+    SSC_TRY(ssc_colsum2(dmulv, 2 * Z, TB, 2 * Z, nullptr, g->fc_mean_b, 1, nullptr, 0, c.slabs, st));
+  } else {
+    if (g->fc_mean_b) SSC_TRY(ssc_colsum2(dmulv, 2 * Z, TB, Z, nullptr, g->fc_mean_b, 1, nullptr, 0, c.slabs, st));
+    if (g->fc_lv_b) SSC_TRY(ssc_colsum2(dmulv + Z, 2 * Z, TB, Z, nullptr, g->fc_lv_b, 1, nullptr, 0, c.slabs, st));
+  }
   }  // phase 4
   if (phases & 8u) {
   if (!one_flush) {
@@ -1222,15 +1288,6 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     if (l.D && hipMemcpy2DAsync(gw + F + 2 * H, (size_t)ld * sizeof(float), W + l.wc_d, (size_t)l.Dp * sizeof(float),
                                 (size_t)l.SC * sizeof(float), H4, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return SSC_EHIP;
-  }
-  if (g->dec_w_hh) {
-    // dW_hh^dec = dGd^T HD_prev is the same product as the hd' block of dW_ih^dec
-    if (g->dec_w_ih) {
-      if (hipMemcpy2DAsync(g->dec_w_hh, (size_t)g->ld_dec_w_hh * sizeof(float), g->dec_w_ih + F + H,
-                           (size_t)g->ld_dec_w_ih * sizeof(float), (size_t)H * sizeof(float), H4, hipMemcpyDeviceToDevice,
-                           st) != hipSuccess)
-        return SSC_EHIP;
-    }
   }
   if (g->dec_b_ih && g->dec_b_hh) {
     SSC_TRY(ssc_colsum2(dgd, H4, TB, H4, nullptr, g->dec_b_ih, 1, g->dec_b_hh, 0, c.slabs, st));

@@ -31,7 +31,8 @@ class GemmDesc(C.Structure):
     _fields_ = [("seg", GemmSeg * SSC_MAX_SEG), ("nseg", C.c_int), ("M", C.c_int), ("N", C.c_int), ("a_kc", C.c_int),
                 ("b_kc", C.c_int), ("C", vp), ("ldc", C.c_int), ("bias", vp), ("accumulate", C.c_int),
                 ("splits", C.c_int), ("workspace", vp), ("workspace_floats", C.c_size_t), ("m_count", vp), ("a_rows", vp),
-                ("c_rows", vp), ("k_count", vp), ("ka_rows", vp), ("kb_rows", vp), ("a_scale", vp), ("b_scale", vp), ("topk_part", vp)]
+                ("c_rows", vp), ("k_count", vp), ("ka_rows", vp), ("kb_rows", vp), ("a_scale", vp), ("b_scale", vp), ("topk_part", vp),
+                ("C2", vp), ("ldc2", C.c_int)]
 
 
 class LstmFwdDesc(C.Structure):
@@ -224,6 +225,7 @@ SYMBOLS = {
     "ssc_set_gemm_mode": (_i, [_i]),
     "ssc_feat_prep": (_i, [vp, _i, _i, _i, vp, vp, vp]),
     "ssc_prep_tokens": (_i, [vp, _i, _i, _i, _i, vp, vp, vp, vp]),
+    "ssc_prep_tokens_rows": (_i, [vp, _i, _i, _i, _i, vp, vp, vp, vp, vp, vp, vp]),
     "ssc_embed_gather": (_i, [vp, _i, vp, _i, _i, vp, _i, vp]),
     "ssc_embed_scatter_add": (_i, [vp, _i, vp, _i, _i, vp, _i, _i, vp]),
     "ssc_lstm_fwd": (_i, [C.POINTER(LstmFwdDesc), vp]),

@@ -11,6 +11,10 @@ sys.path.insert(0, __file__.rsplit("/", 2)[0] + "/profiles")
 from summarize import short  # noqa: E402
 
 
+# first kernel of a train step / of a beam-search call: the name in older traces -> the name since the one-launch precompute
+RENAMED = {"prep_tokens_kernel": "prep_tokens_rows_kernel", "feat_mask_kernel": "feat_prep_kernel"}
+
+
 def main():
     path = sys.argv[1]
     first = sys.argv[2] if len(sys.argv) > 2 else "prep_tokens_kernel"
@@ -20,6 +24,9 @@ def main():
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]))
     rows.sort()
     starts = [i for i, r in enumerate(rows) if first in r[2]]
+    if not starts and first in RENAMED:   # a collector script that still names the marker kernel of an older build
+        first = RENAMED[first]
+        starts = [i for i, r in enumerate(rows) if first in r[2]]
     if len(starts) < 2:
         print("need two occurrences of", first)
         return
