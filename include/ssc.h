@@ -757,6 +757,22 @@ int ssc_beam_backtrace_ctl(const int64_t* preds, const int64_t* backptrs, const 
 /* device-visible address of a pinned (hipHostMalloc / torch pin_memory) host word, for ssc_beam_desc.host_flag */
 int ssc_host_device_ptr(void* host_ptr, void** device_ptr);
 
+/* Attention trace of a one-call decode (ssc_search_desc.attn, ssc_score_desc.attn): which regions every word looked at.  With it set,
+ * step t's attention weights are written by the step itself to hist + t * rows * R instead of to the workspace block the next step
+ * overwrites (no copy, no launch), and one small kernel behind the call's last step writes anc.  `steps` is max_steps (max_len for
+ * ssc_decode_score), `rows` the row count of the later steps - B*S*beam for the searches, B for ssc_decode_sample, G for
+ * ssc_decode_score - and n_caps = rows.  A search's first step has B rows: they are the head of slab 0.  Both buffers are the
+ * caller's; neither the workspace layout nor *_workspace_bytes depend on it.  anc[q, t] is the row of slab t that holds the weights
+ * behind word t of returned caption q: for a search b*S*beam + a_{t-1} with a_{T-1} = q's beam, a_{t-1} = backptr[t-1][b, a_t]
+ * (word 0: b), for the two row decodes q itself.  It is -1 - the word read nothing, its slab row is unspecified - for t >= ctl[0],
+ * for t >= 1 when word t - 1 of the caption is end_index (a forced END; the first END itself keeps its attention, as token_lp keeps
+ * its log-prob), for every word of a beam whose final log-prob is <= -1e19, and in ssc_decode_score after a caption's end, for an
+ * absent slot and from a negative id on.  Read it with ssc_attn_gather. */
+typedef struct {
+  float* hist;   /* (steps, rows, R): step t's alpha, written by the step itself */
+  int*   anc;    /* (n_caps, steps) int32: the row of slab t whose alpha belongs to word t of caption q, or -1 */
+} ssc_attn_record;
+
 /* ------------------------------------------------------------------------------------------------
  * One diverse-decode call = ONE entry point: the whole constrained beam search over nimg images x n_samples latent
  * samples (batch entry b = (image, sample), rows (b, fsm state, beam)), every step launched from the library:
@@ -789,6 +805,9 @@ typedef struct {
                                   * [0] = the stop flag, [1] = the last step the device has completed */
   const int* host_flag_host;     /* the same words' host address: read between steps - the host stops queueing once [0] is set and
                                   * stays at most two steps ahead of [1] (plain memory reads, no event, no synchronisation call) */
+  const ssc_attn_record* attn;   /* optional attention trace (above); NULL: off - the same launches and the same bits as without the field.
+                                  * Set with a NULL hist or anc: SSC_EINVAL before any launch.  Honoured by ssc_decode_search, the
+                                  * stochastic, sampled-node, diverse and rules searches and ssc_decode_sample */
 } ssc_search_desc;
 size_t ssc_decode_search_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
 int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, void* workspace,
@@ -926,6 +945,7 @@ typedef struct {
   float* token_lp;               /* out (G, max_len), optional: the log-prob of every token; 0 after the caption's end */
   int* token_rank;               /* out (G, max_len), optional: ssc_score_rows' rank of every token; -1 after the caption's end */
   int* n_tokens;                 /* out (nimg, C): the scored tokens of every caption, the END included */
+  const ssc_attn_record* attn;   /* optional attention trace (ssc_attn_record: steps = max_len, rows = n_caps = G); NULL: off */
 } ssc_score_desc;
 size_t ssc_decode_score_workspace_bytes(const ssc_model_cfg* cfg, const ssc_score_desc* d);
 int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d, void* workspace, size_t workspace_bytes,
@@ -1318,6 +1338,30 @@ typedef struct {
  * bit-equal outputs (N = 2, leave-one-out: advantage exactly 0).  SSC_EINVAL and nothing written: a NULL pointer, N outside
  * 1..128, L < steps, baseline 1 with N = 1, baseline 2 without base_scores. */
 int ssc_scst_prepare(const ssc_scst_desc* d, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Reading an attention trace (ssc_attn_record): per selected caption and step the attention map of the word and its summary.
+ * A call of its own because the caller picks the captions it returns after the search (the best beam, a diverse group's arg-max):
+ * only those are gathered.  Row i of the outputs is caption q = sel[i] (sel NULL: q = i and n_sel must equal n_caps).  With
+ * a = anc[q, t]:
+ *   maps[i, t, 0:R]   a bit-for-bit copy of hist[t, a, :]; exact zeros - hist is NOT read - where a is outside [0, rows) (the -1 of
+ *                     ssc_attn_record) or q is outside [0, n_caps).  Columns [R, ld_maps) are left untouched.
+ *   top_region[i, t]  the arg-max of that row, ties to the lowest index; -1 on a zero row
+ *   top_weight[i, t]  the weight at the arg-max; 0 on a zero row
+ *   entropy[i, t]     -sum alpha ln alpha over alpha > 0, in nats; 0 on a zero row
+ * One wave per (caption, step) row, four rows per workgroup, lanes over R (16-byte accesses where R, ld_maps and the pointers allow);
+ * the arg-max and the entropy sum are wave butterflies in a fixed order: no atomics, the same bits on every call.  Stream-ordered.
+ * SSC_EINVAL before any launch: NULL d, hist or anc; every output NULL; ld_maps < R with maps set; a non-positive rows, R, steps,
+ * n_caps or n_sel; sel NULL with n_sel != n_caps.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* hist; int rows, R, steps;
+  const int* anc; int n_caps;
+  const int64_t* sel; int n_sel;      /* optional caption list; NULL: all, n_sel = n_caps */
+  float* maps; int ld_maps;           /* optional out (n_sel, steps, ld_maps >= R) */
+  int* top_region; float* top_weight; float* entropy;   /* optional out (n_sel, steps) */
+} ssc_attn_gather_desc;
+int ssc_attn_gather(const ssc_attn_gather_desc* d, void* stream);
 
 #ifdef __cplusplus
 }

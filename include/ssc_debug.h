@@ -51,6 +51,13 @@ int ssc_prof_loop_ms(float* fwd_loop_ms, float* bwd_loop_ms);
 int ssc_debug_set(const char* key, int value);
 int ssc_debug_get(const char* key, int* value);
 
+/* Test hook of the attention trace (ssc_attn_record): where a one-call decode keeps, in the workspace it has just run in, the words
+ * it chose and their ancestry - what the anc of its trace is derived from.  driver 0: the searches (ssc_decode_search and the
+ * stochastic, sampled-node, diverse and rules searches), 1: ssc_decode_sample.  which 0: the chosen words, (max_steps, rows) int64
+ * time-major; 1: the back-pointers, (max_steps - 1, rows) int64 (searches only).  cfg and desc are those of the call.  Returns a
+ * pointer into `workspace`, or 0 for a bad argument. */
+void* ssc_debug_decode_view(const void* cfg, const void* desc, void* workspace, int driver, int which);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,13 @@ parser.add_argument("--likelihood-samples", type=int, default=0,
 parser.add_argument("--likelihood-output", default="",
                     help='with --likelihood-samples: per image {"image_id", "caption" (highest marginal), "caption_per_token" (highest '
                          'marginal / n_tokens), "pick", "pick_per_token", "marginal": [...], "n_tokens": [...]}')
+parser.add_argument("--attention-output", default="",
+                    help="write the attention trace of every written caption to this .pt file (torch.save): a list, in the order of "
+                         'the predictions, of {"image_id", "sample", "tokens", "top_region", "top_weight", "entropy"} - one entry per '
+                         "word up to and including the caption's end: the region the word attended most, the weight there and the "
+                         "entropy of its attention in nats.  The predictions file is what it is without the flag")
+parser.add_argument("--attention-full", action="store_true",
+                    help='with --attention-output: every entry also holds "maps" (words, regions), the whole attention of every word')
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -147,6 +154,13 @@ def main():
     if bool(_A.likelihood_samples > 0) != bool(_A.likelihood_output) or _A.likelihood_samples < 0:
         raise SystemExit("--likelihood-samples M (M >= 1) and --likelihood-output FILE go together")
     likelihood, lik_pick, lik_pick_len = [], [], []
+    if _A.attention_full and not _A.attention_output:
+        raise SystemExit("--attention-full needs --attention-output")
+    attn_mode = ("full" if _A.attention_full else "summary") if _A.attention_output else (
+        None if _C.MODEL.DECODE_ATTENTION == "none" else _C.MODEL.DECODE_ATTENTION)
+    if attn_mode and not _A.attention_output:
+        raise SystemExit("MODEL.DECODE_ATTENTION needs --attention-output FILE to write the traces to")
+    traces = []
     ROW_BUDGET = 40000   # rows (image, sample, state, beam) per decode step of a constrained call
     with torch.no_grad():
         lo = 0
@@ -180,13 +194,16 @@ def main():
                                      ).repeat_interleave(n_z)
             obj = data.obj[lo: lo + n_here, : feats.size(1)].to(device) if getattr(data, "obj", None) is not None else None
             if diverse is not None:   # every group's best caption: N_Z_SAMPLES * DIVERSE_BEAM_GROUPS captions per image
-                pred = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
-                                      diverse_beam=diverse, return_groups=True)[0]
+                out = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
+                                     diverse_beam=diverse, return_groups=True, attention=attn_mode)
+                pred = out[0]
                 pred = pred.reshape(pred.size(0), n_z * diverse.groups, pred.size(-1))
             else:
-                pred, _ = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
-                                         num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
-                                         obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules)
+                out = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
+                                     num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
+                                     obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode)
+                pred = out[0]
+            trace = out[-1] if attn_mode else None
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
             if _A.references:
@@ -199,6 +216,16 @@ def main():
                 image_id = int(data.image_id[lo + i])
                 for k in range(ids.shape[1]):
                     predictions.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
+            if trace is not None:
+                # (images, captions per image, steps[, R]) like the predictions; every caption cut behind its end
+                tr = {n: getattr(trace, n).reshape(ids.shape[0], ids.shape[1], *getattr(trace, n).shape[-(2 if n == "maps" else 1):]).cpu()
+                      for n in ("top_region", "top_weight", "entropy", "maps") if getattr(trace, n) is not None}
+                for i in range(ids.shape[0]):
+                    for k in range(ids.shape[1]):
+                        n = min(int(n_keep[i, k]) + 1, ids.shape[-1])
+                        entry = {"image_id": int(data.image_id[lo + i]), "sample": k, "tokens": torch.from_numpy(ids[i, k, :n].copy())}
+                        entry.update({name: v[i, k, :n].clone() for name, v in tr.items()})
+                        traces.append(entry)
             if bank is not None:
                 # an image that is itself in the bank is not its own neighbour
                 here = [int(x) for x in data.image_id[lo: lo + n_here]]
@@ -222,6 +249,9 @@ def main():
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
+    if _A.attention_output:
+        torch.save(traces, _A.attention_output)
+        print(f"wrote {len(traces)} attention traces to {_A.attention_output}")
     if _A.consensus_output:
         json.dump(best, open(_A.consensus_output, "w", encoding="utf-8"))
         print(f"wrote {len(best)} consensus captions to {_A.consensus_output}")

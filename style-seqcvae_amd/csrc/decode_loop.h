@@ -101,6 +101,17 @@ struct SscStepPacer {
   }
 };
 
+// The attention trace of a call (ssc_attn_record, D::attn): off, or both of the caller's buffers ...
+template <class D>
+bool ssc_decode_attn_ok(const D* d) {
+  return !d->attn || (d->attn->hist && d->attn->anc);
+}
+// ... and where step t of `rows` rows writes its attention weights: its slab of the caller's history instead of the workspace
+// block every step overwrites.  The step writes them either way: recording is no copy and no launch.
+inline float* ssc_decode_alpha_at(const ssc_attn_record* attn, float* ws_alpha, int t, size_t rows, int R) {
+  return attn ? attn->hist + (size_t)t * rows * R : ws_alpha;
+}
+
 // What every driver checks of its descriptor D (ssc_search_desc, ssc_score_desc); `steps` is its max_steps / max_len.
 // ... the extents its workspace size depends on
 template <class D>
@@ -111,6 +122,6 @@ bool ssc_decode_dims_ok(const ssc_model_cfg* cfg, const D* d, int steps) {
 template <class D>
 bool ssc_decode_inputs_ok(const ssc_model_cfg* cfg, const D* d, int steps) {
   if (!d->feats || !d->imgbuf || !d->eps0 || (steps > 1 && !d->eps)) return false;
-  if (d->end_index < 0 || d->end_index >= cfg->V) return false;
+  if (d->end_index < 0 || d->end_index >= cfg->V || !ssc_decode_attn_ok(d)) return false;
   return !(cfg->kld_mode == 2 ? !d->obj_atts : ((cfg->S || cfg->pm_scale != 0.f) && !d->sentiment));
 }

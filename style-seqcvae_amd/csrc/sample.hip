@@ -162,6 +162,9 @@ bool sample_desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
 
 }  // namespace
 
+// include/ssc_debug.h, ssc_debug_decode_view: where ssc_decode_sample keeps its chosen words (max_steps, B)
+size_t ssc_sample_words_offset(const ssc_model_cfg* cfg, const ssc_search_desc* d) { return sample_layout(cfg, d).preds; }
+
 extern "C" int ssc_sample_rows(const float* logits, int ld, int rows, int V, const ssc_sampler_desc* s, const int64_t* row_ids,
                                int step, const int64_t* last_pred, float* row_lp, int end_index, int64_t* pred_out, float* lp_out,
                                float* probs_out, void* stream) {
@@ -211,6 +214,7 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
   sd.G = B; sd.rows_per_image = d->n_samples; sd.tokens = tokens0; sd.sentiment = d->sentiment; sd.eps = d->eps0;
   states.bind(W, 1, &sd);
   sd.att_table = table.next(want_table);
+  sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), 0, B, d->R);
   SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
   a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
@@ -226,6 +230,7 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
     sd.tokens = last; sd.eps = d->eps + (size_t)(t - 1) * B * Z;
     states.bind(W, cur, &sd);
     sd.att_table = table.next(want_table);
+    sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), t, B, d->R);
     sd.row_lp = d->skip_dead ? lp : nullptr; sd.end_index = d->end_index;   // ended rows are not stepped
     SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
@@ -235,6 +240,8 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
   SSC_LAUNCH(sample_collect_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, st, preds, d->early_stop ? ctl : nullptr, d->max_steps, B,
              d->end_index, d->predictions);
   SSC_CHECK_LAUNCH();
+  if (d->attn)   // the trace's ancestry is the identity: row b, until the row has ended or the call has stopped
+    SSC_TRY(ssc_attn_anc(preds, nullptr, d->early_stop ? ctl : nullptr, nullptr, d->max_steps, B, 1, d->end_index, d->attn->anc, st));
   if (hipMemcpyAsync(d->log_probs, lp, (size_t)B * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   return SSC_OK;
 }

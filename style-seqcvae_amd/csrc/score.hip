@@ -312,6 +312,7 @@ extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, c
     sd.eps = t == 0 ? d->eps0 : d->eps + (size_t)(t - 1) * G * Z;
     states.bind(W, cur, &sd);
     sd.att_table = table.next(want_table);
+    sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), t, G, d->R);
     if (t > 0) {   // (at step 0 every row's fed token is END: no row may be skipped by it)
       sd.parent = parent0; sd.group = 1;
       sd.row_lp = lp; sd.end_index = d->end_index;   // ended and absent rows (fed token END) are not stepped
@@ -324,6 +325,9 @@ extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, c
     SSC_TRY(score_launch(a, G, st));
     cur = 1 - cur;
   }
+  // the trace's ancestry is the identity wherever a target is scored: tgt holds -1 after a caption's end, for an absent slot and
+  // from a negative id on
+  if (d->attn) SSC_TRY(ssc_attn_anc(tgt, nullptr, nullptr, nullptr, L, G, 1, d->end_index, d->attn->anc, st));
   if (hipMemcpyAsync(d->log_probs, lp, (size_t)G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   return SSC_OK;
 }

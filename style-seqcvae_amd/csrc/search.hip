@@ -205,6 +205,7 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   // ---- first step: one row per batch entry (cbs.py:127) ------------------------------------------------------------------
   sd.G = B; sd.rows_per_image = d->n_samples; sd.tokens = tokens0; sd.sentiment = d->sentiment; sd.eps = d->eps0;
   states.bind(W, 1, &sd);
+  sd.alpha = ssc_decode_alpha_at(d->attn, alpha, 0, G, d->R);   // (a trace's slab 0: the B rows of this step are its head)
   sd.att_table = table.next(ssc_att_table_wanted(d->R, B, d->n_samples));
   SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
   ssc_beam_desc bd{};
@@ -245,6 +246,7 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
     states.bind_planes(W, cur, ungathered, &sd);
     sd.parent = t == 1 ? parent0 : backs + (size_t)(t - 2) * plane;
     sd.att_table = table.next(tmode);
+    sd.alpha = ssc_decode_alpha_at(d->attn, alpha, t, G, d->R);
     sd.ungathered = ungathered ? 1 : 0;
     sd.row_lp = d->skip_dead ? lp[a] : nullptr; sd.end_index = d->end_index;
     if (use_parts) { sd.log_probs = nullptr; sd.topk_part = (float*)(W + l.parts); }
@@ -266,6 +268,10 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   } else {
     SSC_TRY(ssc_beam_backtrace(preds, backs, d->max_steps, B, SB, d->predictions, st));
   }
+  // the trace's ancestry: the chain the back-trace has just walked.  Row g of step t is beam g after step t - 1's selection in the
+  // gathered and the un-gathered form alike (a step's outputs are in row order either way)
+  if (d->attn)
+    SSC_TRY(ssc_attn_anc(preds, backs, d->early_stop ? d->ctl : nullptr, lp[a], d->max_steps, B, SB, d->end_index, d->attn->anc, st));
   if (hipMemcpyAsync(d->log_probs, lp[a], (size_t)G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   if (final_gen) *final_gen = a;
   return SSC_OK;
@@ -379,4 +385,18 @@ extern "C" int ssc_decode_rules_beam(const ssc_model_cfg* cfg, const ssc_params*
   if (hipMemcpyAsync(scores, sel.score[a], G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   if (hipMemcpyAsync(lengths, sel.len[a], G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   return SSC_OK;
+}
+
+// include/ssc_debug.h: where the call that has just run in `workspace` keeps its chosen words and back-pointers.  Both lie in front of
+// every block whose size depends on the selection, so one layout serves the five searches.
+size_t ssc_sample_words_offset(const ssc_model_cfg* cfg, const ssc_search_desc* d);   // (sample.hip)
+extern "C" void* ssc_debug_decode_view(const void* cfg_, const void* desc, void* workspace, int driver, int which) {
+  const ssc_model_cfg* cfg = (const ssc_model_cfg*)cfg_;
+  const ssc_search_desc* d = (const ssc_search_desc*)desc;
+  if (!workspace || !ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return nullptr;
+  char* W = (char*)workspace;
+  if (driver == 1) return which == 0 ? W + ssc_sample_words_offset(cfg, d) : nullptr;
+  if (driver != 0 || !search_dims_ok(cfg, d)) return nullptr;
+  const SearchLayout l = search_layout(cfg, d, SEARCH_BEAM);
+  return which == 0 ? W + l.preds : which == 1 ? W + l.backs : nullptr;
 }

@@ -150,5 +150,9 @@ bool ssc_sampled_beam_ok(int B, int k, int n, int V, const ssc_sampler_desc* s);
 bool ssc_diverse_beam_ok(int B, int k, int n, int V, const ssc_diverse_desc* s);
 int ssc_diverse_beam_list(int k, int groups, int n, int V);
 bool ssc_rules_beam_ok(int B, int k, int n, int V, int end_index, const ssc_rules_desc* r);
+// the `anc` of an attention trace (attn_trace.hip, include/ssc.h: ssc_attn_record) from a call's chosen words (max_steps, B * SB)
+// time-major; backs (max_steps - 1, B * SB) or null: the identity; ctl or null: every step ran; lp (B * SB) or null: no dead beam
+int ssc_attn_anc(const int64_t* words, const int64_t* backs, const int* ctl, const float* lp, int max_steps, int B, int SB,
+                 int end_index, int* anc, hipStream_t st);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

@@ -94,6 +94,10 @@ def _defaults() -> dict:
             "LENGTH_PENALTY_ALPHA": 0.0,
             # SUPPRESS_UNKNOWN: @@UNKNOWN@@ is never emitted (its log-prob is not given to the other words)
             "SUPPRESS_UNKNOWN": False,
+            # attention traces of the eval decode (ssc_attn_record; DecodeEngine.attention): "none" (default), "summary" - per word
+            # of every returned caption the region it attended most, the weight there and the entropy of its attention - or "full"
+            # - the whole map over the regions as well.  Any decoder; the captions themselves do not change
+            "DECODE_ATTENTION": "none",
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,
@@ -206,6 +210,8 @@ class Config(object):
             if max_len > 64:
                 raise ValueError("the decode rules (MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / "
                                  f"SUPPRESS_UNKNOWN) need DATA.MAX_CAPTION_LENGTH <= 64; found {max_len}")
+        if m.DECODE_ATTENTION not in ("none", "summary", "full"):
+            raise ValueError(f"MODEL.DECODE_ATTENTION must be one of none | summary | full; found {m.DECODE_ATTENTION!r}")
         o = self._C.OPTIM
         if o.OPTIMIZER not in ("sgd", "adam", "adamw"):
             raise ValueError(f'OPTIM.OPTIMIZER must be "sgd", "adam" or "adamw"; found {o.OPTIMIZER!r}')

@@ -4,7 +4,7 @@ Reference: UpDownCaptioner._decode_step eval branch (var_updown/var_updown/model
 ConstrainedBeamSearch.search (updown-baseline/updown/modules/cbs.py:59-277).
 """
 import ctypes as C
-from typing import Callable, Dict, Optional, Tuple
+from typing import Callable, Dict, NamedTuple, Optional, Tuple
 
 import torch
 
@@ -23,6 +23,28 @@ class ImageContext:
         self.obj = obj   # SENTIMENT_VAE = 2: per-region attribute means (nimg, R, Z) of these images (updown_cell.py:160-163)
         self.nimg, self.R, _ = feats.shape
         self.att_table_ready = False   # the per-image attended-feature table is formed by the first step that uses it
+
+
+class AttentionRecord(NamedTuple):
+    """The attention trace a one-call decode leaves with attention=True (ssc_attn_record, include/ssc.h): hist (steps, rows, R) - step
+    t's attention weights in that step's row order - and anc (rows, steps) int32 - the row of slab t behind word t of returned
+    caption q, -1 where the word read nothing.  Captions are numbered as the call returns them, flattened.  Read it with
+    DecodeEngine.attention."""
+    hist: torch.Tensor
+    anc: torch.Tensor
+    rows: int
+    R: int
+    steps: int
+
+
+class AttentionTrace(NamedTuple):
+    """What DecodeEngine.attention reads from a record, per selected caption and step: maps (..., steps, R) - the word's attention
+    over the regions, exact zeros where it read nothing -, top_region (..., steps) int32 (-1 there), top_weight and entropy
+    (..., steps) in nats (0 there).  The parts not asked for are None."""
+    maps: Optional[torch.Tensor]
+    top_region: Optional[torch.Tensor]
+    top_weight: Optional[torch.Tensor]
+    entropy: Optional[torch.Tensor]
 
 
 class DecodeEngine:
@@ -200,13 +222,45 @@ class DecodeEngine:
             self._sws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return _lib.ptr(self._sws), self._sws.numel(), _lib.stream_ptr()
 
+    def _attn_record(self, steps: int, rows: int, R: int):
+        """-> (AttentionRecord over fresh buffers, its ssc_attn_record): the caller keeps both alive until the call is queued."""
+        rec = AttentionRecord(torch.empty(steps, rows, R, dtype=torch.float32, device=self.device),
+                              torch.empty(rows, steps, dtype=torch.int32, device=self.device), rows, R, steps)
+        return rec, _lib.AttnRecord(rec.hist.data_ptr(), rec.anc.data_ptr())
+
+    def attention(self, record: AttentionRecord, sel: Optional[torch.Tensor] = None, maps: bool = True,
+                  summary: bool = True) -> AttentionTrace:
+        """Read an attention record (ssc_attn_gather): for every caption of `sel` - int64 indices into the call's captions in the
+        order it returned them, flattened; any shape; None: all of them - and every step the attention map (maps=True) and / or its
+        arg-max region, the weight there and the entropy (summary=True).  An index outside the call's captions gives a zero row.
+        -> AttentionTrace with tensors of shape sel.shape + (steps,) (+ (R,) for the maps)."""
+        if not (maps or summary):
+            raise ValueError("DecodeEngine.attention: nothing asked for (maps and summary both off)")
+        dev = self.device
+        if sel is None:
+            shape, n, sel_t = (record.rows,), record.rows, None
+        else:
+            sel_t = sel.to(dev, torch.int64).contiguous()
+            shape, n = tuple(sel_t.shape), sel_t.numel()
+        steps, R = record.steps, record.R
+        m = torch.empty(*shape, steps, R, dtype=torch.float32, device=dev) if maps else None
+        top = torch.empty(*shape, steps, dtype=torch.int32, device=dev) if summary else None
+        wgt = torch.empty(*shape, steps, dtype=torch.float32, device=dev) if summary else None
+        ent = torch.empty(*shape, steps, dtype=torch.float32, device=dev) if summary else None
+        if n > 0:
+            d = _lib.AttnGatherDesc(record.hist.data_ptr(), record.rows, R, steps, record.anc.data_ptr(), record.rows,
+                                    _lib.ptr(sel_t), n, _lib.ptr(m), R, _lib.ptr(top), _lib.ptr(wgt), _lib.ptr(ent))
+            self.lib.ssc_attn_gather(C.byref(d), _lib.stream_ptr())
+        return AttentionTrace(m, top, wgt, ent)
+
     def _one_call(self, ctx, sentiment, n_samples, S, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
-                  out_shape, workspace_bytes, call, machine=None):
+                  out_shape, workspace_bytes, call, machine=None, attention=False):
         """The shared body of the one-call decodes over a search descriptor: B = ctx.nimg * n_samples batch entries of S * beam
         rows.  Fills the descriptor (machine(desc) adds a search's machine fields), checks the noise, allocates the outputs -
         predictions out_shape + (max_steps,), log-probs out_shape -, takes the pinned early-stop flag, sizes the workspace with
         workspace_bytes(cfg, desc) and issues call(params, desc, (workspace, bytes, stream)).
-        -> (predictions cut to the executed steps, log_probs); one wait at the end, for the number of steps."""
+        -> (predictions cut to the executed steps, log_probs[, AttentionRecord over max_steps steps with attention=True]); one wait
+        at the end, for the number of steps."""
         B = ctx.nimg * n_samples
         dev = self.device
         sd = _lib.SearchDesc()
@@ -229,21 +283,29 @@ class DecodeEngine:
             flag, flag_dev = _host_flag()
             if flag_dev is not None:
                 sd.host_flag, sd.host_flag_host = flag_dev, C.c_void_p(flag.data_ptr())
+        rec = arec = None
+        if attention:
+            rec, arec = self._attn_record(max_steps, B * S * beam, ctx.R)
+            sd.attn = C.pointer(arec)
         ws = self._workspace(workspace_bytes(C.byref(self._cfg), C.byref(sd)))
         call(self._params(), sd, ws)
         nsteps = int(ctl[0]) if early_stop else max_steps   # (the one wait of the call: its result is about to be read anyway)
         if flag is not None:
             _HOST_FLAGS.append(flag)
+        if attention:
+            return pred[..., :nsteps].contiguous(), lps, rec
         return pred[..., :nsteps].contiguous(), lps
 
     def search(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int, max_steps: int,
                end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
                compiled: Optional["CompiledFsm"] = None, mach: Optional[torch.Tensor] = None, skip_dead: bool = False,
-               early_stop: bool = True):
+               early_stop: bool = True, attention: bool = False):
         """The whole constrained beam search of one call in ONE library call (ssc_decode_search): ctx.nimg images x n_samples
         latent samples, batch entry b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*S*beam, Z):
         the noise of every step, drawn by the caller.  fsm (M,S,S,V) / compiled / mach as in cbs_search.
-        -> (predictions (B, S, beam, steps), log_probs (B, S, beam)); one wait at the end, for the number of steps."""
+        -> (predictions (B, S, beam, steps), log_probs (B, S, beam)); one wait at the end, for the number of steps.
+        attention=True (here and on every one-call decode below): additionally an AttentionRecord of the call's captions in the
+        order returned (caption q = the flattened index of the predictions' leading dimensions), for DecodeEngine.attention."""
         B = ctx.nimg * n_samples
         S = 1 if fsm is None else fsm.size(1)
         if fsm is not None:
@@ -266,10 +328,11 @@ class DecodeEngine:
                               skip_dead and (compiled is not None or fsm is None), (B, S, beam),
                               self.lib.ssc_decode_search_workspace_bytes,
                               lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws),
-                              machine)
+                              machine, attention=attention)
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
-               eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True):
+               eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
+               attention: bool = False):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
@@ -280,15 +343,17 @@ class DecodeEngine:
         return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, True,
                               (ctx.nimg * n_samples,), self.lib.ssc_decode_sample_workspace_bytes,
                               lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd),
-                                                                           C.byref(sdesc), *ws))
+                                                                           C.byref(sdesc), *ws), attention=attention)
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
-              eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False):
+              eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False,
+              attention: bool = False):
         """The teacher-forced decode of GIVEN captions in ONE library call (ssc_decode_score): targets (nimg, C, L) int64 - the
         caption's words, then end_index from its end on; a slot whose first entry is negative is absent - scored under n_samples
         latent samples each, row g = (image, caption, sample), G = nimg * C * n_samples.  sentiment (G) per row or None; eps0
         (G, Z), eps (L - 1, G, Z): the noise of every step.
-        -> (log_probs (G,), n_tokens (nimg, C) int32, token_lp (G, L) or None, token_rank (G, L) int32 or None)."""
+        -> (log_probs (G,), n_tokens (nimg, C) int32, token_lp (G, L) or None, token_rank (G, L) int32 or None[, AttentionRecord
+        of the G rows over L steps with attention=True])."""
         dev = self.device
         assert targets.dim() == 3 and targets.size(0) == ctx.nimg, (targets.shape, ctx.nimg)
         _, Cc, Lc = targets.shape
@@ -305,14 +370,20 @@ class DecodeEngine:
         tlp = torch.empty(G, Lc, dtype=torch.float32, device=dev) if want_tokens else None
         trk = torch.empty(G, Lc, dtype=torch.int32, device=dev) if want_ranks else None
         sd.log_probs, sd.n_tokens, sd.token_lp, sd.token_rank = _lib.ptr(lps), _lib.ptr(ntok), _lib.ptr(tlp), _lib.ptr(trk)
+        rec = arec = None
+        if attention:
+            rec, arec = self._attn_record(Lc, G, ctx.R)
+            sd.attn = C.pointer(arec)
         ws = self._workspace(self.lib.ssc_decode_score_workspace_bytes(C.byref(self._cfg), C.byref(sd)))
         p = self._params()
         self.lib.ssc_decode_score(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws)
+        if attention:
+            return lps, ntok, tlp, trk, rec
         return lps, ntok, tlp, trk
 
     def stochastic_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                         max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
-                        early_stop: bool = True, skip_dead: bool = True):
+                        early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
         """The whole stochastic beam search of one call in ONE library call (ssc_decode_stochastic_beam): ctx.nimg images x n_samples
         latent samples, batch entry b = (image, sample), `beam` captions per entry sampled without replacement by `sampler`
         (sampling.GumbelSampler) with the 64-bit `seed`, per_node candidates per beam.  sentiment (B) or None; eps0 (B, Z),
@@ -325,11 +396,12 @@ class DecodeEngine:
                               (ctx.nimg * n_samples, beam),
                                self.lib.ssc_decode_stochastic_beam_workspace_bytes,
                                lambda p, sd, ws: self.lib.ssc_decode_stochastic_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
-                                                                                     C.byref(gdesc), *ws))
+                                                                                     C.byref(gdesc), *ws),
+                              attention=attention)
 
     def sampled_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                      max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
-                     early_stop: bool = True, skip_dead: bool = True):
+                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
         """The whole sampled-node beam search of one call in ONE library call (ssc_decode_sampled_beam): the reference's BeamSearch
         driven by a word sampler (ssc_runtime.sampling: multinomial / top-k / top-p) - step 0 takes the top `beam` tokens, every
         later step draws per_node candidates per beam (with or without replacement, sampler.with_replacement) with the 64-bit
@@ -350,11 +422,12 @@ class DecodeEngine:
                               (ctx.nimg * n_samples, beam),
                                self.lib.ssc_decode_sampled_beam_workspace_bytes,
                                lambda p, sd, ws: self.lib.ssc_decode_sampled_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
-                                                                                  C.byref(sdesc), rep, *ws))
+                                                                                  C.byref(sdesc), rep, *ws),
+                              attention=attention)
 
     def diverse_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                      max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], diverse,
-                     early_stop: bool = True, skip_dead: bool = True):
+                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
         """The whole diverse beam search of one call in ONE library call (ssc_decode_diverse_beam): `beam` beams per batch entry in
         diverse.groups groups (sampling.DiverseBeam), searched in order inside every step with the Hamming penalty
         diverse.strength; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples, batch entry
@@ -370,11 +443,12 @@ class DecodeEngine:
                               (ctx.nimg * n_samples, beam),
                                lambda cfg, sd: self.lib.ssc_decode_diverse_beam_workspace_bytes(cfg, sd, C.byref(ddesc)),
                                lambda p, sd, ws: self.lib.ssc_decode_diverse_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
-                                                                                  C.byref(ddesc), *ws))
+                                                                                  C.byref(ddesc), *ws),
+                              attention=attention)
 
     def rules_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                    max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], rules,
-                   early_stop: bool = True, skip_dead: bool = True):
+                   early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
         """The whole beam search under the decode rules of one call in ONE library call (ssc_decode_rules_beam): blocking of
         repeated n-grams, a minimum length, suppressed tokens and a length penalty in the ranking (sampling.DecodeRules), applied
         where the selection runs; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples,
@@ -391,12 +465,12 @@ class DecodeEngine:
         B = ctx.nimg * n_samples
         scores = torch.empty(B, beam, dtype=torch.float32, device=self.device)
         lengths = torch.empty(B, beam, dtype=torch.int32, device=self.device)
-        pred, lps = self._one_call(ctx, sentiment, n_samples, 1, beam, per_node, max_steps, end_index, eps0, eps, early_stop,
-                                   skip_dead, (B, beam), self.lib.ssc_decode_rules_beam_workspace_bytes,
-                                   lambda p, sd, ws: self.lib.ssc_decode_rules_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
-                                                                                    C.byref(rdesc), _lib.ptr(scores),
-                                                                                    _lib.ptr(lengths), *ws))
-        return pred, lps, scores, lengths
+        out = self._one_call(ctx, sentiment, n_samples, 1, beam, per_node, max_steps, end_index, eps0, eps, early_stop,
+                             skip_dead, (B, beam), self.lib.ssc_decode_rules_beam_workspace_bytes,
+                             lambda p, sd, ws: self.lib.ssc_decode_rules_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
+                                                                              C.byref(rdesc), _lib.ptr(scores),
+                                                                              _lib.ptr(lengths), *ws), attention=attention)
+        return (out[0], out[1], scores, lengths) + tuple(out[2:])
 
     def _step_from_embedding(self, ctx, token_embedding, states, sentiment, eps, prior_mean_out=None, prior_mean=None, prior_var=None):
         G = token_embedding.size(0)

@@ -14,8 +14,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import lib as _lib
-from .decode import DecodeEngine
-from .decoding import select_best_beam_simple_batched
+from .decode import AttentionTrace, DecodeEngine
+from .decoding import select_best_beam_simple_batched, select_best_state_simple_batched
 
 
 
@@ -26,7 +26,7 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
-                   rules=None):
+                   rules=None, attention: Optional[str] = None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     fsm: None (trivial one-state machine, what MAX_GIVEN_CONSTRAINTS: 0 produces), or (nimg, S, S, V) uint8 - ONE machine per
     image, shared by its n_samples latent samples through an index list -, or (nimg*n_samples, S, S, V) (a copy per sample).
@@ -55,7 +55,14 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     (nimg, n_samples, groups)).
     rules: a sampling.DecodeRules - the beam search runs under them (DecodeEngine.rules_beam: n-gram blocking, minimum length,
     suppressed tokens, length penalty); needs sampler = None, no diverse_beam and fsm = None.  Beam 0 - the best caption under the
-    length penalty - of every (image, sample) is returned.  None, or rules with every control off: the plain beam search."""
+    length penalty - of every (image, sample) is returned.  None, or rules with every control off: the plain beam search.
+    attention: None, "summary" or "full" - with it the call additionally returns, as its last value, the AttentionTrace
+    (ssc_runtime.decode) of exactly the captions it returns, whatever the decoder: top_region / top_weight / entropy (nimg,
+    n_samples, steps) - with return_groups (nimg, n_samples, groups, steps) - and, under "full", maps (..., steps, R).  Words after
+    a caption's first END read nothing: region -1, zeros.  The captions, log-probs and the random state consumed do not change."""
+    if attention not in (None, "summary", "full"):
+        raise ValueError(f'attention must be None, "summary" or "full", got {attention!r}')
+    want_attn = attention is not None
     if rules is not None and not rules.active:
         rules = None
     if rules is not None:
@@ -129,37 +136,48 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
         if rules is not None:
-            beams, lps, _, _ = dec.rules_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, rules,
-                                              early_stop=early_stop, skip_dead=skip_now)
+            beams, lps, _, _, *rec = dec.rules_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, rules,
+                                                    early_stop=early_stop, skip_dead=skip_now, attention=want_attn)
             calls["k"] = beams.size(-1)
-            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if diverse_beam is not None:
-            beams, lps = dec.diverse_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, diverse_beam,
-                                          early_stop=early_stop, skip_dead=skip_now)
+            beams, lps, *rec = dec.diverse_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
+                                                diverse_beam, early_stop=early_stop, skip_dead=skip_now, attention=want_attn)
             calls["k"] = beams.size(-1)
-            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if sampled_beam:
-            beams, lps = dec.sampled_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
-                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, skip_dead=skip_now)
+            beams, lps, *rec = dec.sampled_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
+                                                seed if sample_seed is None else sample_seed, early_stop=early_stop,
+                                                skip_dead=skip_now, attention=want_attn)
             calls["k"] = beams.size(-1)
-            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if gumbel:
-            beams, lps = dec.stochastic_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
-                                             seed if sample_seed is None else sample_seed, early_stop=early_stop, skip_dead=skip_now)
+            beams, lps, *rec = dec.stochastic_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
+                                                   sampler, seed if sample_seed is None else sample_seed, early_stop=early_stop,
+                                                   skip_dead=skip_now, attention=want_attn)
             calls["k"] = beams.size(-1)
-            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam)
+            return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if sampler is not None:
-            pred, lps = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
-                                   seed if sample_seed is None else sample_seed, early_stop=early_stop)
+            pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
+                                         seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn)
             calls["k"] = pred.size(-1)
-            return pred.view(B, 1, 1, -1), lps.view(B, 1, 1)
-        beams, lps = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
-                                fsm=None if trivial else fsm.contiguous(), compiled=compiled, mach=mach, skip_dead=skip_now,
-                                early_stop=early_stop)
+            return pred.view(B, 1, 1, -1), lps.view(B, 1, 1), rec
+        beams, lps, *rec = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
+                                      fsm=None if trivial else fsm.contiguous(), compiled=compiled, mach=mach, skip_dead=skip_now,
+                                      early_stop=early_stop, attention=want_attn)
         calls["k"] = beams.size(-1)   # one step call per column (cbs.py:127,170)
-        return beams, lps
+        return beams, lps, rec
 
-    beams, lps = search(skip)
+    def trace(rec, sel, lead):
+        """-> () without attention, else (the AttentionTrace of captions `sel` of the call behind `rec`, shaped lead + (steps[, R])
+        and cut to the executed steps,)"""
+        if not want_attn:
+            return ()
+        tr = dec.attention(rec[0], sel.reshape(lead), maps=attention == "full", summary=True)
+        k = calls["k"]
+        return (type(tr)(*(None if x is None else x[:, :, :k] if len(lead) == 2 else x[:, :, :, :k] for x in tr)),)
+
+    beams, lps, rec = search(skip)
     if diverse_beam is not None:   # group-major, not sorted across groups: the arg-max inside each group, then over the entry
         Gr = diverse_beam.groups
         steps = beams.size(-1)
@@ -167,19 +185,26 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
         gi = glp.argmax(-1)   # (ties: the lower beam)
         gbest = beams.view(B, Gr, beam // Gr, steps).gather(2, gi.view(B, Gr, 1, 1).expand(B, Gr, 1, steps)).squeeze(2)
         gbest_lp = glp.gather(2, gi.unsqueeze(-1)).squeeze(-1)
+        # the call's caption number of every group's best: entry b, group g, beam gi inside it (group-major)
+        rows = torch.arange(B, device=dev).view(B, 1) * beam + torch.arange(Gr, device=dev).view(1, Gr) * (beam // Gr) + gi
         if return_groups:
-            return gbest.view(nimg, n_samples, Gr, steps), calls["k"], gbest_lp.view(nimg, n_samples, Gr)
+            return (gbest.view(nimg, n_samples, Gr, steps), calls["k"], gbest_lp.view(nimg, n_samples, Gr)) + \
+                trace(rec, rows, (nimg, n_samples, Gr))
         bi = gbest_lp.argmax(-1)
         best = gbest.gather(1, bi.view(B, 1, 1).expand(B, 1, steps)).squeeze(1)
-        return best.view(nimg, n_samples, -1), calls["k"]
+        return (best.view(nimg, n_samples, -1), calls["k"]) + trace(rec, rows.gather(1, bi.view(B, 1)), (nimg, n_samples))
+    state = torch.zeros(B, dtype=torch.long, device=dev)   # the machine state whose beam 0 is returned
     if trivial or fsm.size(1) == 1:
         best = beams[:, 0, 0, :]
     else:
         best, best_lp = select_best_beam_simple_batched(beams, lps, num_constraints, min_constraints_to_satisfy)
         if skip and bool((best_lp <= -1e19).any()):   # (one read of the device; the captions are about to be read anyway)
-            beams, lps = search(False)
+            beams, lps, rec = search(False)   # (and with it the trace: the repeat's record)
             best, _ = select_best_beam_simple_batched(beams, lps, num_constraints, min_constraints_to_satisfy)
-    return best.view(nimg, n_samples, -1), calls["k"]
+        if want_attn:
+            state = select_best_state_simple_batched(lps, num_constraints, min_constraints_to_satisfy)
+    sel = (torch.arange(B, device=dev) * S + state) * beam
+    return (best.view(nimg, n_samples, -1), calls["k"]) + trace(rec, sel, (nimg, n_samples))
 
 
 def count_tokens(pred: torch.Tensor, boundary_index: int) -> int:
@@ -201,10 +226,27 @@ class CaptionScores:
     marginal: torch.Tensor
     token_lp: Optional[torch.Tensor] = None
     token_rank: Optional[torch.Tensor] = None
+    attention: Optional[AttentionTrace] = None   # score_captions(attention=...): (nimg, C, N, L[, R]) per part
 
     @staticmethod
     def concat(parts: "List[CaptionScores]") -> "CaptionScores":
-        """The scores of several calls over different images as one (token arrays padded to the longest call: 0 / -1)."""
+        """The scores of several calls over different images as one (token arrays padded to the longest call: 0 / -1; the attention
+        trace padded as the steps after a caption's end are: region -1, zeros)."""
+        def cat_trace():
+            trs = [p.attention for p in parts]
+            if any(t is None for t in trs):
+                return None
+            L = max(t.top_region.size(3) for t in trs)
+            out = []
+            for name, fill in (("maps", 0.0), ("top_region", -1), ("top_weight", 0.0), ("entropy", 0.0)):
+                ts = [getattr(t, name) for t in trs]
+                if any(x is None for x in ts):
+                    out.append(None)
+                    continue
+                pad = lambda x: (0, 0, 0, L - x.size(3)) if name == "maps" else (0, L - x.size(3))
+                out.append(torch.cat([torch.nn.functional.pad(x, pad(x), value=fill) for x in ts]))
+            return AttentionTrace(*out)
+
         def cat(name, fill):
             ts = [getattr(p, name) for p in parts]
             if any(t is None for t in ts):
@@ -212,7 +254,7 @@ class CaptionScores:
             L = max(t.size(-1) for t in ts)
             return torch.cat([torch.nn.functional.pad(t, (0, L - t.size(-1)), value=fill) for t in ts])
         return CaptionScores(torch.cat([p.log_probs for p in parts]), torch.cat([p.n_tokens for p in parts]),
-                             torch.cat([p.marginal for p in parts]), cat("token_lp", 0.0), cat("token_rank", -1))
+                             torch.cat([p.marginal for p in parts]), cat("token_lp", 0.0), cat("token_rank", -1), cat_trace())
 
     def summary(self) -> Dict[str, float]:
         """nll_per_token = -sum_c mean_n log_probs / sum_c n_tokens, perplexity = exp of it, marginal_nll_per_token =
@@ -235,7 +277,7 @@ class CaptionScores:
 def score_captions(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[torch.Tensor], captions: torch.Tensor, n_samples: int,
                    boundary_index: int, layout: str, eps_steps: Optional[List[torch.Tensor]] = None,
                    obj_means: Optional[torch.Tensor] = None, pad_index: int = 0, want_tokens: bool = False,
-                   want_ranks: bool = False) -> CaptionScores:
+                   want_ranks: bool = False, attention: Optional[str] = None) -> CaptionScores:
     """How likely are GIVEN captions under the model: feats (nimg, R, F), sentiment (nimg,) or None, captions (nimg, C, L) int64,
     each scored under n_samples latent samples drawn from the prior (DecodeEngine.score, one library call).
     layout - required, nothing is guessed: "padded" = the training layout (the words, then pad_index; no boundary tokens; a slot
@@ -245,7 +287,11 @@ def score_captions(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
     ValueError on the host, before anything is launched.
     eps_steps: optional explicit noise per step [(nimg * C * n_samples, Z)], rows (image, caption, sample); default: a generator of
     this call's own, seeded by ONE draw of the global CPU generator (as diverse_decode draws its noise).
-    obj_means (nimg, R, Z): per-region attribute means, SENTIMENT_VAE = 2 only."""
+    obj_means (nimg, R, Z): per-region attribute means, SENTIMENT_VAE = 2 only.
+    attention: None, "summary" or "full": the scores then carry the AttentionTrace of every (caption, sample) - top_region /
+    top_weight / entropy (nimg, C, N, L) and, under "full", maps (nimg, C, N, L, R); zeros (region -1) after a caption's end."""
+    if attention not in (None, "summary", "full"):
+        raise ValueError(f'attention must be None, "summary" or "full", got {attention!r}')
     if layout not in ("padded", "decoded"):
         raise ValueError(f"layout must be 'padded' (training layout) or 'decoded' (decoder output), got {layout!r}")
     if captions.dim() != 3 or captions.size(0) != feats.size(0) or captions.size(2) < 1:
@@ -295,9 +341,14 @@ def score_captions(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
         eps = torch.randn(max(Lc - 1, 1), G, d.Z, device=dev, generator=gen)[: Lc - 1] if Lc > 1 else None
     ctx = dec.prepare(feats, obj_means)
     sent_g = sentiment.reshape(nimg, 1).expand(nimg, Cc * n_samples).reshape(G) if sentiment is not None else None
-    lps, ntok, tlp, trk = dec.score(ctx, sent_g, tg.to(dev), n_samples, end, eps0, eps, want_tokens=want_tokens, want_ranks=want_ranks)
+    lps, ntok, tlp, trk, *rec = dec.score(ctx, sent_g, tg.to(dev), n_samples, end, eps0, eps, want_tokens=want_tokens,
+                                          want_ranks=want_ranks, attention=attention is not None)
     lps = lps.view(nimg, Cc, n_samples)
-    return CaptionScores(log_probs=lps, n_tokens=ntok, marginal=torch.logsumexp(lps, -1) - math.log(n_samples),
+    tr = None
+    if rec:
+        sel = torch.arange(G, device=dev).view(nimg, Cc, n_samples)
+        tr = dec.attention(rec[0], sel, maps=attention == "full", summary=True)
+    return CaptionScores(attention=tr, log_probs=lps, n_tokens=ntok, marginal=torch.logsumexp(lps, -1) - math.log(n_samples),
                          token_lp=tlp.view(nimg, Cc, n_samples, Lc) if tlp is not None else None,
                          token_rank=trk.view(nimg, Cc, n_samples, Lc) if trk is not None else None)
 

@@ -133,12 +133,21 @@ class BeamDesc(C.Structure):
                 ("host_flag", vp)]
 
 
+class AttnRecord(C.Structure):
+    _fields_ = [("hist", vp), ("anc", vp)]
+
+
+class AttnGatherDesc(C.Structure):
+    _fields_ = [("hist", vp), ("rows", C.c_int), ("R", C.c_int), ("steps", C.c_int), ("anc", vp), ("n_caps", C.c_int), ("sel", vp),
+                ("n_sel", C.c_int), ("maps", vp), ("ld_maps", C.c_int), ("top_region", vp), ("top_weight", vp), ("entropy", vp)]
+
+
 class SearchDesc(C.Structure):
     _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_samples", C.c_int), ("S", C.c_int), ("beam", C.c_int), ("per_node", C.c_int),
                 ("max_steps", C.c_int), ("end_index", C.c_int), ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("eps0", vp),
                 ("eps", vp), ("obj_atts", vp), ("fsm", vp), ("tables", vp), ("dims", FsmDims), ("mach", vp), ("skip_dead", C.c_int),
                 ("early_stop", C.c_int), ("predictions", vp), ("log_probs", vp), ("ctl", vp), ("host_flag", vp),
-                ("host_flag_host", vp)]
+                ("host_flag_host", vp), ("attn", C.POINTER(AttnRecord))]
 
 
 class SamplerDesc(C.Structure):
@@ -152,7 +161,8 @@ class SchedSampling(C.Structure):
 class ScoreDesc(C.Structure):
     _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_captions", C.c_int), ("n_samples", C.c_int), ("max_len", C.c_int),
                 ("end_index", C.c_int), ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("obj_atts", vp), ("targets", vp),
-                ("eps0", vp), ("eps", vp), ("log_probs", vp), ("token_lp", vp), ("token_rank", vp), ("n_tokens", vp)]
+                ("eps0", vp), ("eps", vp), ("log_probs", vp), ("token_lp", vp), ("token_rank", vp), ("n_tokens", vp),
+                ("attn", C.POINTER(AttnRecord))]
 
 
 class PosteriorRowsDesc(C.Structure):
@@ -346,6 +356,7 @@ SYMBOLS = {
     "ssc_eval_consensus_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc)]),
     "ssc_eval_consensus": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc), vp, _sz, vp]),
     "ssc_scst_prepare": (_i, [C.POINTER(ScstDesc), vp]),
+    "ssc_attn_gather": (_i, [C.POINTER(AttnGatherDesc), vp]),
 }
 
 # include/ssc_debug.h (diagnostics / profiling / tuning switches: not part of the product ABI)
@@ -356,6 +367,7 @@ DEBUG_SYMBOLS = {
     "ssc_prof_loop_ms": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "ssc_debug_set": (_i, [C.c_char_p, _i]),
     "ssc_debug_get": (_i, [C.c_char_p, C.POINTER(C.c_int)]),
+    "ssc_debug_decode_view": (vp, [vp, vp, vp, _i, _i]),
 }
 
 _lib = None

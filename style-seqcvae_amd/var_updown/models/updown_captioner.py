@@ -181,6 +181,7 @@ class UpDownCaptioner(nn.Module):
         self._scst = None   # (key, SelfCritical, its references) of the last scst_step
         self._ctx_cache = None
         self.n_z_samples = 1           # latent samples per caption of score_captions (from_config: MODEL.N_Z_SAMPLES)
+        self._decode_attention = None  # decode_attention(): "summary" / "full" attention traces in the eval forward's output
 
     # ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -206,6 +207,7 @@ class UpDownCaptioner(nn.Module):
                     decode_rules=sampling.decode_rules_from_config(_C.MODEL, vocabulary), free_bits=_C.OPTIM.FREE_BITS,
                     free_bits_mode=_C.OPTIM.FREE_BITS_MODE)
         model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
+        model.decode_attention(_C.MODEL.DECODE_ATTENTION)
         return model
 
     def _initialize_glove(self):
@@ -351,18 +353,22 @@ class UpDownCaptioner(nn.Module):
                 raise ValueError(f"MODEL.USE_CBS with a constraint machine cannot be combined with MODEL.DECODE_SAMPLER "
                                  f"{self.sampler.name!r}: constrained sampling is not supported")
             with torch.no_grad():
-                return {"predictions": self._sample_decode(image_features, obj_means, sentiment)}
+                return self._sample_decode(image_features, obj_means, sentiment)
         if self.diverse_beam is not None:
             if self._use_cbs and fsm is not None:
                 raise ValueError("MODEL.USE_CBS with a constraint machine cannot be combined with MODEL.DIVERSE_BEAM_SEARCH")
             with torch.no_grad():
-                return {"predictions": self._diverse_beam_decode(image_features, obj_means, sentiment)}
+                return self._diverse_beam_decode(image_features, obj_means, sentiment)
         if self.decode_rules is not None:
             if self._use_cbs and fsm is not None:
                 raise ValueError("MODEL.USE_CBS with a constraint machine cannot be combined with the decode rules "
                                  "(MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN)")
             with torch.no_grad():
-                return {"predictions": self._rules_beam_decode(image_features, obj_means, sentiment)}
+                return self._rules_beam_decode(image_features, obj_means, sentiment)
+        if self._decode_attention is not None:
+            with torch.no_grad():
+                return self._traced_beam_decode(image_features, obj_means, sentiment, fsm if self._use_cbs else None,
+                                                num_constraints)
         with torch.no_grad():
             if self._use_cbs and fsm is not None:
                 fsm_d = fsm.to(dev).to(torch.uint8)
@@ -385,9 +391,62 @@ class UpDownCaptioner(nn.Module):
         check_sched_sampling(prob, sampler, seed)
         self._sched_sampling = (float(prob), sampler, int(seed))
 
+    def decode_attention(self, mode):
+        """Attention traces of the NEXT eval forwards (include/ssc.h: ssc_attn_record): "summary" - the output dict gains, per
+        image and word of the returned caption, attention_top_region (B, steps) int32 (the region the word attended most; -1 for
+        the words after the caption's END, which read nothing), attention_top_weight (the weight there) and attention_entropy
+        (nats) -, "full" - additionally attention (B, steps, R), the whole map -, or None / "none" (the default state): off, the
+        dict is what it is without.  Every decoder of the eval forward; the predictions are those of the same forward without it
+        given the same noise.  With it set the plain and the constrained beam search run as one library call
+        (DecodeEngine.search) with the noise of all steps drawn up front, as the sampled decodes draw theirs; constraints need
+        CBS_SIMPLE."""
+        if mode in (None, "none"):
+            self._decode_attention = None
+        elif mode in ("summary", "full"):
+            self._decode_attention = mode
+        else:
+            raise ValueError(f'decode_attention: mode must be None, "none", "summary" or "full", got {mode!r}')
+
+    def _traced(self, pred, rec, sel):
+        """The eval forward's output dict: predictions and, with decode_attention set, the trace of captions `sel` (B,) of `rec`."""
+        out = {"predictions": pred}
+        if rec:
+            n = pred.size(-1)
+            tr = self._dec.attention(rec[0], sel, maps=self._decode_attention == "full", summary=True)
+            out.update(attention_top_region=tr.top_region[:, :n], attention_top_weight=tr.top_weight[:, :n],
+                       attention_entropy=tr.entropy[:, :n])
+            if tr.maps is not None:
+                out["attention"] = tr.maps[:, :n]
+        return out
+
+    def _traced_beam_decode(self, image_features, obj_means, sentiment, fsm, num_constraints):
+        """Eval forward of the plain / constrained beam search with decode_attention set: the search in one library call
+        (DecodeEngine.search), the noise drawn as the step-by-step path draws it (one (rows, Z) draw per step)."""
+        from ssc_runtime.decoding import select_best_state_simple_batched
+        B = image_features.size(0)
+        L = self._max_caption_length
+        dev = self._eng.device
+        ctx = self._image_context(image_features, obj_means)
+        k, per = self._beam_search.beam_size, self._beam_search.per_node_beam_size
+        fsm_d = None
+        if fsm is not None:
+            if not self.cbs_simple:
+                raise ValueError("decode_attention with a constraint machine needs CBS_SIMPLE")
+            fsm_d = fsm.to(dev).to(torch.uint8).contiguous()
+        S = 1 if fsm_d is None else fsm_d.size(1)
+        eps0 = self._draw_eps(1, B, dev)[0]
+        eps = self._draw_eps(L - 1, B * S * k, dev) if L > 1 else None
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        beams, lps, rec = self._dec.search(ctx, sent, 1, k, per or k, L, self._boundary_index, eps0, eps, fsm=fsm_d, attention=True)
+        state = torch.zeros(B, dtype=torch.long, device=dev)
+        if fsm_d is not None and S > 1:
+            state = select_best_state_simple_batched(lps, num_constraints, self._min_constraints_to_satisfy)
+        rows = torch.arange(B, device=dev)
+        return self._traced(beams[rows, state, 0, :], [rec], (rows * S + state) * k)
+
     def score_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, obj_atts=None,
                        n_samples: Optional[int] = None, layout: str = "padded", want_tokens: bool = False, want_ranks: bool = False,
-                       eps_steps=None):
+                       eps_steps=None, attention: Optional[str] = None):
         """How likely are the given captions under the model as it stands: image_features (B, R, F), caption_tokens (B, L) or
         (B, C, L) int64 - by default in the training layout (0-padded, no boundary tokens; layout="decoded": a decoder's output) -,
         each scored under n_samples (default: MODEL.N_Z_SAMPLES) latent samples drawn from the prior, the pooled prior of
@@ -395,7 +454,8 @@ class UpDownCaptioner(nn.Module):
         step (default: a generator of the call's own, seeded by one draw of the global CPU generator).  One library call, no autograd; the mode (train / eval) is left as
         it is and plays no part.  -> ssc_runtime.inference.CaptionScores.
         The image context is formed from the parameters as they are NOW, so the call is correct between optimizer steps - unless
-        the caller has set DecodeEngine.weights_frozen, which promises that they do not change."""
+        the caller has set DecodeEngine.weights_frozen, which promises that they do not change.
+        attention: None, "summary" or "full" - CaptionScores.attention then holds every (caption, sample)'s trace."""
         from ssc_runtime.inference import score_captions
         self._engine()
         B, R, _ = image_features.shape
@@ -405,7 +465,7 @@ class UpDownCaptioner(nn.Module):
         with torch.no_grad():
             return score_captions(self._dec, image_features.to(self._eng.device, torch.float32), sent, caps,
                                   n_samples or self.n_z_samples, self._boundary_index, layout, eps_steps=eps_steps, obj_means=obj_means,
-                                  want_tokens=want_tokens, want_ranks=want_ranks)
+                                  want_tokens=want_tokens, want_ranks=want_ranks, attention=attention)
 
     def posterior_score_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, obj_atts=None,
                                  n_samples: int = 1, eps=None, want_steps: bool = False):
@@ -467,13 +527,15 @@ class UpDownCaptioner(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())
             sent = sentiment.reshape(B) if sentiment is not None else None
             run = self._dec.sampled_beam if self.sampled_beam else self._dec.stochastic_beam
-            beams, _ = run(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.sampler, seed)
-            return beams[:, 0, :]
+            beams, _, *rec = run(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.sampler, seed,
+                                 attention=self._decode_attention is not None)
+            return self._traced(beams[:, 0, :], rec, torch.arange(B, device=dev) * k)
         eps = self._draw_eps(L, B, dev)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         sent = sentiment.reshape(B) if sentiment is not None else None
-        pred, _ = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed)
-        return pred
+        pred, _, *rec = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed,
+                                         attention=self._decode_attention is not None)
+        return self._traced(pred, rec, torch.arange(B, device=dev))
 
     def _diverse_beam_decode(self, image_features, obj_means, sentiment):
         """Eval forward with MODEL.DIVERSE_BEAM_SEARCH: the diverse beam search in one library call (DecodeEngine.diverse_beam), the
@@ -486,10 +548,11 @@ class UpDownCaptioner(nn.Module):
         eps0 = self._draw_eps(1, B, dev)[0]
         eps = self._draw_eps(L - 1, B * k, dev) if L > 1 else None
         sent = sentiment.reshape(B) if sentiment is not None else None
-        beams, lps = self._dec.diverse_beam(ctx, sent, 1, k, self.diverse_beam.per_node(k), L, self._boundary_index, eps0, eps,
-                                            self.diverse_beam)
+        beams, lps, *rec = self._dec.diverse_beam(ctx, sent, 1, k, self.diverse_beam.per_node(k), L, self._boundary_index, eps0, eps,
+                                                  self.diverse_beam, attention=self._decode_attention is not None)
         bi = lps.argmax(-1)
-        return beams.gather(1, bi.view(B, 1, 1).expand(B, 1, beams.size(-1))).squeeze(1)
+        return self._traced(beams.gather(1, bi.view(B, 1, 1).expand(B, 1, beams.size(-1))).squeeze(1), rec,
+                            torch.arange(B, device=dev) * k + bi)
 
     def _rules_beam_decode(self, image_features, obj_means, sentiment):
         """Eval forward with decode rules: the beam search under them in one library call (DecodeEngine.rules_beam), the noise
@@ -502,8 +565,9 @@ class UpDownCaptioner(nn.Module):
         eps0 = self._draw_eps(1, B, dev)[0]
         eps = self._draw_eps(L - 1, B * k, dev) if L > 1 else None
         sent = sentiment.reshape(B) if sentiment is not None else None
-        beams, _, _, _ = self._dec.rules_beam(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.decode_rules)
-        return beams[:, 0, :]
+        beams, _, _, _, *rec = self._dec.rules_beam(ctx, sent, 1, k, k // 2 or k, L, self._boundary_index, eps0, eps, self.decode_rules,
+                                                    attention=self._decode_attention is not None)
+        return self._traced(beams[:, 0, :], rec, torch.arange(B, device=dev) * k)
 
     def _image_context(self, image_features, obj_means=None):
         """Per-image terms (mask, averaged features, projected features, hoisted gate term) for the eval decode step, computed
