@@ -814,6 +814,53 @@ int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_s
                       size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Ensemble decoding: ONE beam search over M parameter sets of one architecture (checkpoints of one configuration: seeds,
+ * cross-entropy / self-critical, SGD / Adam), the members' word distributions averaged at every step of the search.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSC_ENSEMBLE_MAX 8
+/* M (rows, V) matrices of raw logits -> one (rows, V) matrix of log-probs.  Per row g and member m, lp_m[v] = logits_m[g, v] - lse_m
+ * with lse_m formed exactly as ssc_log_softmax forms it (the same device function, the same summation order).
+ *   mode 0 "prob":    out[v] = mx_v + log sum_m exp(lp_m[v] + logw_m - mx_v), mx_v = max_m (lp_m[v] + logw_m), members in index
+ *                     order: the log of the weighted mean of the members' probabilities.  M = 1 (logw 0) is bit-equal to ssc_log_softmax
+ *   mode 1 "logprob": s[v] = sum_m w_m lp_m[v] (w_m = exp(logw_m), taken once on the host), out[v] = s[v] - logsumexp_v s (the
+ *                     log-softmax of s, in ssc_log_softmax's arithmetic): the normalised weighted geometric mean
+ * A member row that holds a NaN has a NaN log-sum-exp, as under ssc_log_softmax: the whole output row is NaN in both modes.
+ * A row with last_pred[g] == end_index or row_lp[g] <= -1e19 (either pointer may be NULL) is SKIPPED: neither read nor written -
+ * the rows ssc_decode_step_desc.row_lp leaves unspecified.  One workgroup per row, no atomics, bit-reproducible; out may not alias
+ * an input.  SSC_EINVAL before any launch for M outside 1 .. SSC_ENSEMBLE_MAX, a NULL member, V < 1, ld < V, ldo < V, a mode
+ * other than 0 / 1 or a non-finite logw. */
+typedef struct {
+  int M;                       /* members, 1 .. SSC_ENSEMBLE_MAX */
+  const float* const* logits;  /* host array of M device pointers, each (rows, V) raw logits, leading dimension ld */
+  int ld;
+  const float* logw;           /* host array (M): log of the members' weights, weights > 0 and summing to 1 (the caller normalises) */
+  int mode;                    /* 0 "prob", 1 "logprob" */
+} ssc_ensemble_rows_desc;
+int ssc_ensemble_combine_rows(const ssc_ensemble_rows_desc* e, int rows, int V, const int64_t* last_pred, const float* row_lp,
+                              int end_index, float* out, int ldo, void* stream);
+
+/* ssc_decode_search over M members.  Per step every member runs ssc_decode_step on its own two generations of states (its own
+ * fp16 pieces, attended-feature-table decision and step workspace) and leaves raw logits in its own (G, V) block; one
+ * ssc_ensemble_combine_rows (given the step's last_pred / row_lp under skip_dead) turns them into log-probs and the selection of
+ * ssc_decode_search reads those with raw_logits = 0; the back-pointers re-order (or are read through by) every member's states
+ * alike.  Shared by the members: features, noise (every member decodes the same latent sample), sentiment, obj_atts, the parent
+ * lists and row_lp.  Takes the ssc_search_desc of ssc_decode_search - any machine, mach, skip_dead, early_stop, every
+ * SENTIMENT_VAE - with d->imgbuf == imgbufs[0]; the records head (ssc_decode_step_desc.topk_part) is never used, and a set d->attn
+ * is SSC_EINVAL (no attention trace of an ensemble).  The stochastic, sampled-node, diverse and rules searches, ssc_decode_sample
+ * and ssc_decode_score take ONE parameter set. */
+typedef struct {
+  int M;                             /* members, 1 .. SSC_ENSEMBLE_MAX */
+  const ssc_params* const* params;   /* M parameter sets of ONE ssc_model_cfg (same architecture) */
+  const void* const* imgbufs;        /* M image buffers: ssc_decode_prepare of the SAME feats under each member's params.  Two members
+                                      * may share a buffer only if it was prepared under the params both of them use (not checked) */
+  const float* weights;              /* (M) > 0, any scale: normalised by the call; NULL: uniform */
+  int mode;                          /* as ssc_ensemble_rows_desc.mode */
+} ssc_ensemble_desc;
+size_t ssc_decode_search_ensemble_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_ensemble_desc* e);
+int ssc_decode_search_ensemble(const ssc_model_cfg* cfg, const ssc_ensemble_desc* e, const ssc_search_desc* d, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Word-level sampling decoders (MultinomialSampler / TopKSampler / TopPSampler.sample_nodes,
  * var_updown/var_updown/modules/beam_search.py:103-293, at one draw per row).  With log_probs = log_softmax(logits):
  *   kind 0 multinomial(T): draw from softmax(log_probs / T)

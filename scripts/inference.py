@@ -4,6 +4,7 @@ flags and JSON output ([{"image_id", "caption"}...], N_Z_SAMPLES captions per im
 decoded as ONE batched beam search per chunk instead of a per-image Python loop of N_Z_SAMPLES model calls."""
 import argparse
 import json
+import math
 import os
 import random
 import sys
@@ -19,7 +20,7 @@ from ssc_runtime.data import SyntheticCaptionData, TensorFileData  # noqa: E402
 from ssc_runtime.inference import diverse_decode, score_captions  # noqa: E402
 from ssc_runtime import sampling  # noqa: E402
 from ssc_runtime.vocab import Vocabulary  # noqa: E402
-from var_updown.models import UpDownCaptioner  # noqa: E402
+from var_updown.models import CaptionerEnsemble, UpDownCaptioner  # noqa: E402
 
 parser = argparse.ArgumentParser("Run diverse-decoding inference with a trained Style-SeqCVAE captioner (MI355X).")
 parser.add_argument("--config", required=True)
@@ -28,6 +29,13 @@ parser.add_argument("--gpu-ids", required=True, nargs="+", type=int)
 parser.add_argument("--cpu-workers", type=int, default=0)
 parser.add_argument("--in-memory", action="store_true")
 parser.add_argument("--checkpoint-path", default="", help="checkpoint with a 'model' state_dict; empty: random init")
+parser.add_argument("--ensemble-checkpoints", default=[], nargs="+", metavar="P",
+                    help="ensemble decoding: further checkpoints of the SAME configuration and vocabulary (--checkpoint-path is member "
+                         "0); one beam search over all members, their word distributions averaged at every step")
+parser.add_argument("--ensemble-weights", default=None, nargs="+", type=float,
+                    help="with --ensemble-checkpoints: one positive weight per member, member 0 first (any scale; default uniform)")
+parser.add_argument("--ensemble-mode", default=None, choices=["prob", "logprob"],
+                    help="with --ensemble-checkpoints: average the members' probabilities (prob, the default) or their log-probs")
 parser.add_argument("--output-path", default="predictions.json")
 parser.add_argument("--evalai-submit", action="store_true", help="accepted for flag parity; EvalAI is a network service")
 parser.add_argument("--infer-tensors", default="")
@@ -81,8 +89,32 @@ class _LocalGlove(UpDownCaptioner):
         return torch.zeros(self._vocabulary.get_vocab_size(), self.embedding_size)
 
 
+def check_ensemble_args(_A):
+    """The ensemble flags, checked before anything is loaded -> (weights or None, mode) for CaptionerEnsemble."""
+    if not _A.ensemble_checkpoints:
+        if _A.ensemble_weights is not None or _A.ensemble_mode is not None:
+            raise SystemExit("--ensemble-weights / --ensemble-mode need --ensemble-checkpoints")
+        return None, "prob"
+    if not _A.checkpoint_path:
+        raise SystemExit("--ensemble-checkpoints needs --checkpoint-path (member 0)")
+    n = 1 + len(_A.ensemble_checkpoints)
+    if n > 8:
+        raise SystemExit(f"--ensemble-checkpoints: at most 8 members in all, got {n}")
+    for p in [_A.checkpoint_path] + _A.ensemble_checkpoints:
+        if not os.path.isfile(p):
+            raise SystemExit(f"--ensemble-checkpoints: no such checkpoint {p!r}")
+    w = _A.ensemble_weights
+    if w is not None and (len(w) != n or any(not math.isfinite(x) or x <= 0 for x in w)):
+        raise SystemExit(f"--ensemble-weights: {n} positive finite weights wanted (member 0 first), got {w}")
+    for flag, what in (("attention_output", "--attention-output"), ("likelihood_samples", "--likelihood-samples")):
+        if getattr(_A, flag):
+            raise SystemExit(f"{what} is not available with --ensemble-checkpoints: an ensemble runs the beam search only")
+    return w, _A.ensemble_mode or "prob"
+
+
 def main():
     _A = parser.parse_args()
+    ens_weights, ens_mode = check_ensemble_args(_A)
     _C = Config(_A.config, _A.config_override)
     random.seed(_C.RANDOM_SEED)
     np.random.seed(_C.RANDOM_SEED)
@@ -111,7 +143,19 @@ def main():
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
     model.eval()
     model._engine()
-    model._dec.weights_frozen = True   # the checkpoint's weights stay as they are for the whole run: weight-only tables are formed once
+    dec = model._dec
+    if _A.ensemble_checkpoints:
+        if sampler is not None or diverse is not None or rules is not None or _C.MODEL.DECODE_ATTENTION != "none":
+            raise SystemExit("--ensemble-checkpoints runs the beam search only: no MODEL.DECODE_SAMPLER / STOCHASTIC_BEAM_SEARCH / "
+                             "DIVERSE_BEAM_SEARCH, no decode rules and no MODEL.DECODE_ATTENTION")
+        members = [model]
+        with torch.random.fork_rng(devices=[]):   # (the members' initialisation draws nothing from the run's random stream)
+            for path in _A.ensemble_checkpoints:
+                m = cls.from_config(_C, vocabulary=vocabulary, device=device, **extra).to(device)
+                m.load_state_dict(torch.load(path, map_location=device, weights_only=True)["model"])
+                members.append(m)
+        dec = CaptionerEnsemble(members, ens_weights, ens_mode).engine()
+    dec.weights_frozen = True   # the checkpoint's weights stay as they are for the whole run: weight-only tables are formed once
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
     if sampler is not None and (_A.constraints_json or _A.boxes_json):
@@ -194,12 +238,12 @@ def main():
                                      ).repeat_interleave(n_z)
             obj = data.obj[lo: lo + n_here, : feats.size(1)].to(device) if getattr(data, "obj", None) is not None else None
             if diverse is not None:   # every group's best caption: N_Z_SAMPLES * DIVERSE_BEAM_GROUPS captions per image
-                out = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
+                out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
                                      diverse_beam=diverse, return_groups=True, attention=attn_mode)
                 pred = out[0]
                 pred = pred.reshape(pred.size(0), n_z * diverse.groups, pred.size(-1))
             else:
-                out = diverse_decode(model._dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
+                out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode)
                 pred = out[0]

@@ -19,7 +19,8 @@ namespace {
 // sampled-node beam search (a word sampler's draws per beam, sampled_beam.hip) or the diverse beam search (groups of beams with a
 // Hamming penalty, diverse_beam.hip) or the beam search under the decode rules (n-gram blocking, minimum length, suppressed tokens,
 // length penalty: rules_beam.hip).
-enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED, SEARCH_DIVERSE, SEARCH_RULES };
+// SEARCH_ENSEMBLE: the beam search over several members (ssc_decode_search_ensemble): the layout of SEARCH_BEAM, never the records head.
+enum SearchKind { SEARCH_BEAM, SEARCH_GUMBEL, SEARCH_SAMPLED, SEARCH_DIVERSE, SEARCH_RULES, SEARCH_ENSEMBLE };
 
 // The vocabulary head of the later steps leaves per-tile records instead of logits (ssc_decode_step_desc.topk_part) when the machine
 // is the trivial one, at most two candidates per row are wanted and the head is one aligned 3xBF16 / 2xFP16 product.  Beam search
@@ -177,12 +178,33 @@ struct RulesSelect {   // generation a of the histories, lengths and scores goes
   }
 };
 
+// What a search steps: one member per parameter set, each with its image buffer, its two generations of states, its logits
+// block, its step workspace and its attended-feature-table decision.  The plain searches run a list of one over the blocks of
+// their SearchLayout (search_self); ssc_decode_search_ensemble runs up to SSC_ENSEMBLE_MAX.
+struct SearchMember {
+  const ssc_params* p;
+  const void* imgbuf;
+  SscStepStates states;
+  size_t logits, stepws;   // offsets into the workspace
+  SscAttTable table;
+};
+SearchMember search_self(const ssc_params* p, const ssc_search_desc* d, const SearchLayout& l) {
+  return SearchMember{p, d->imgbuf, l.states, l.logits, l.stepws, SscAttTable{}};
+}
+// Several members: where their logits are combined (ssc_ensemble_combine_rows) for the selection, which then reads log-probs.
+struct SearchCombine {
+  float logw[SSC_ENSEMBLE_MAX];
+  int mode;
+  size_t out;   // (G, V) block of the workspace
+};
+
 // final_gen: the generation of the running per-beam state (lp, and a selection's own) that holds the search's last step
+// mem / M: the members (a list of one issues the launches of a single-model search); comb: null for a single-model search, whose
+// selection normalises the one member's raw logits itself
 template <class Select>
-int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const SearchLayout& l, char* W,
-               const Select& sel, bool use_parts, hipStream_t st, int* final_gen = nullptr) {
+int search_run(const ssc_model_cfg* cfg, SearchMember* mem, int M, const SearchCombine* comb, const ssc_search_desc* d,
+               const SearchLayout& l, char* W, const Select& sel, bool use_parts, hipStream_t st, int* final_gen = nullptr) {
   const int B = d->nimg * d->n_samples, S = d->S, beam = d->beam, SB = S * beam, G = B * SB, H = cfg->H, V = cfg->V, Z = cfg->Z;
-  const SscStepStates& states = l.states;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
   float* sent_rows = (float*)(W + l.sent_rows);
   int64_t* preds = (int64_t*)(W + l.preds);
@@ -190,26 +212,33 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   int64_t* parent0 = (int64_t*)(W + l.parent0);
   float* lp[2] = {(float*)(W + l.lp[0]), (float*)(W + l.lp[1])};
   float* alpha = (float*)(W + l.alpha);
-  float* logits = (float*)(W + l.logits);
   const size_t plane = (size_t)G;
+  // the scores the selection reads: the one member's raw logits, or the members' combined log-probs
+  const float* scores = comb ? (const float*)(W + comb->out) : (const float*)(W + mem[0].logits);
+  const float* mlogits[SSC_ENSEMBLE_MAX];
+  for (int m = 0; m < M; ++m) mlogits[m] = (const float*)(W + mem[m].logits);
+  ssc_ensemble_rows_desc ed{M, mlogits, V, comb ? comb->logw : nullptr, comb ? comb->mode : 0};
 
   SSC_TRY(ssc_decode_start(d->ctl, d->max_steps, tokens0, B, d->end_index, st));
   if (hipMemsetAsync(parent0, 0, (size_t)G * 8, st) != hipSuccess) return SSC_EHIP;
-  SSC_TRY(states.zero(W, 1, B, st));
+  for (int m = 0; m < M; ++m) SSC_TRY(mem[m].states.zero(W, 1, B, st));
 
   // which form the steps take is decided once per extent: the first step's B rows and the later steps' G rows each ask
-  SscAttTable table;
   ssc_decode_step_desc sd{};
-  sd.R = d->R; sd.feats = d->feats; sd.imgbuf = d->imgbuf; sd.alpha = alpha; sd.log_probs = logits; sd.raw_logits = 1;
+  sd.R = d->R; sd.feats = d->feats; sd.alpha = alpha; sd.raw_logits = 1;
   sd.obj_atts = d->obj_atts;
   // ---- first step: one row per batch entry (cbs.py:127) ------------------------------------------------------------------
   sd.G = B; sd.rows_per_image = d->n_samples; sd.tokens = tokens0; sd.sentiment = d->sentiment; sd.eps = d->eps0;
-  states.bind(W, 1, &sd);
   sd.alpha = ssc_decode_alpha_at(d->attn, alpha, 0, G, d->R);   // (a trace's slab 0: the B rows of this step are its head)
-  sd.att_table = table.next(ssc_att_table_wanted(d->R, B, d->n_samples));
-  SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+  for (int m = 0; m < M; ++m) {
+    sd.imgbuf = mem[m].imgbuf; sd.log_probs = (float*)(W + mem[m].logits);
+    mem[m].states.bind(W, 1, &sd);
+    sd.att_table = mem[m].table.next(ssc_att_table_wanted(d->R, B, d->n_samples));
+    SSC_TRY(ssc_decode_step(cfg, mem[m].p, &sd, W + mem[m].stepws, l.stepws_bytes, st));
+  }
+  if (comb) SSC_TRY(ssc_ensemble_combine_rows(&ed, B, V, nullptr, nullptr, d->end_index, (float*)(W + comb->out), V, st));
   ssc_beam_desc bd{};
-  bd.scores = logits; bd.ld = V; bd.raw_logits = 1;
+  bd.scores = scores; bd.ld = V; bd.raw_logits = comb ? 0 : 1;
   bd.fsm = d->fsm; bd.tables = d->tables; bd.dims = d->dims; bd.mach = d->mach;
   if (!d->tables) { bd.dims.M = d->mach ? 0 : B; bd.dims.S = S; bd.dims.V = V; bd.dims.E = 0; bd.dims.P = 1; }
   if (bd.dims.S != S || bd.dims.V != V) return SSC_EINVAL;
@@ -220,11 +249,12 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
   SSC_TRY(sel.first(&bd, st));
   // ---- enlarge the states to (B, S, beam) rows (cbs.py:152-155) --------------------------------------------------------------
   if (d->max_steps > 1) {
-    for (int k = 0; k < 4; ++k) {
-      SSC_LAUNCH(expand_rows_kernel, dim3(ssc_cdiv(H, 256), G), dim3(256), 0, st, states.state(W, 0, k), H, SB, (size_t)G,
-                 states.state(W, 1, k));
-      SSC_CHECK_LAUNCH();
-    }
+    for (int m = 0; m < M; ++m)
+      for (int k = 0; k < 4; ++k) {
+        SSC_LAUNCH(expand_rows_kernel, dim3(ssc_cdiv(H, 256), G), dim3(256), 0, st, mem[m].states.state(W, 0, k), H, SB, (size_t)G,
+                   mem[m].states.state(W, 1, k));
+        SSC_CHECK_LAUNCH();
+      }
     if (d->sentiment) {
       SSC_LAUNCH(expand_rows_kernel, dim3(1, G), dim3(64), 0, st, d->sentiment, 1, SB, (size_t)G, sent_rows);
       SSC_CHECK_LAUNCH();
@@ -242,15 +272,21 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
     if (pacer.stop_before(t)) break;   // cbs.py:167
     const int64_t* last = preds + (size_t)(t - 1) * plane;
     sd.tokens = last; sd.eps = d->eps + (size_t)(t - 1) * G * Z;
-    states.bind(W, cur, &sd);
-    states.bind_planes(W, cur, ungathered, &sd);
     sd.parent = t == 1 ? parent0 : backs + (size_t)(t - 2) * plane;
-    sd.att_table = table.next(tmode);
     sd.alpha = ssc_decode_alpha_at(d->attn, alpha, t, G, d->R);
     sd.ungathered = ungathered ? 1 : 0;
     sd.row_lp = d->skip_dead ? lp[a] : nullptr; sd.end_index = d->end_index;
-    if (use_parts) { sd.log_probs = nullptr; sd.topk_part = (float*)(W + l.parts); }
-    SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+    for (int m = 0; m < M; ++m) {
+      sd.imgbuf = mem[m].imgbuf; sd.log_probs = (float*)(W + mem[m].logits);
+      mem[m].states.bind(W, cur, &sd);
+      mem[m].states.bind_planes(W, cur, ungathered, &sd);
+      sd.att_table = mem[m].table.next(tmode);
+      if (use_parts) { sd.log_probs = nullptr; sd.topk_part = (float*)(W + l.parts); }
+      SSC_TRY(ssc_decode_step(cfg, mem[m].p, &sd, W + mem[m].stepws, l.stepws_bytes, st));
+    }
+    if (comb)   // the rows the steps have left unspecified (row_lp) are not read and not written
+      SSC_TRY(ssc_ensemble_combine_rows(&ed, G, V, d->skip_dead ? last : nullptr, d->skip_dead ? lp[a] : nullptr, d->end_index,
+                                        (float*)(W + comb->out), V, st));
     bd.last_pred = last; bd.last_lp = lp[a]; bd.pred = preds + (size_t)t * plane; bd.lp_out = lp[1 - a];
     bd.backptr = backs + (size_t)(t - 1) * plane; bd.step_index = t;
     SSC_TRY(sel.step(&bd, a, st));
@@ -259,8 +295,9 @@ int search_run(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_d
       cur = 1 - cur;
       ungathered = true;
     } else {     // cbs.py:236-250: re-order the states by back-pointer (into the generation the step has just consumed)
-      for (int k = 0; k < 4; ++k)
-        SSC_TRY(ssc_gather_rows(states.state(W, 1 - cur, k), H, bd.backptr, B, SB, H, states.state(W, cur, k), st));
+      for (int m = 0; m < M; ++m)
+        for (int k = 0; k < 4; ++k)
+          SSC_TRY(ssc_gather_rows(mem[m].states.state(W, 1 - cur, k), H, bd.backptr, B, SB, H, mem[m].states.state(W, cur, k), st));
     }
   }
   if (d->early_stop) {
@@ -287,7 +324,76 @@ extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, 
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   char* W = (char*)workspace;
   const bool use_parts = search_uses_parts(cfg, d, SEARCH_BEAM);
-  return search_run(cfg, p, d, l, W, BeamSelect{use_parts, (const float*)(W + l.parts)}, use_parts, (hipStream_t)stream);
+  SearchMember self = search_self(p, d, l);
+  return search_run(cfg, &self, 1, nullptr, d, l, W, BeamSelect{use_parts, (const float*)(W + l.parts)}, use_parts,
+                    (hipStream_t)stream);
+}
+
+// ---- the beam search over several members (include/ssc.h: ssc_ensemble_desc) ------------------------------------------------------
+// Workspace: the SearchLayout of a beam search without the records head - member 0 steps in its states, logits and step-workspace
+// blocks, everything else in it (tokens, sentiment rows, words, back-pointers, parent lists, running log-probs, selection
+// scratch, alpha) is shared -, then per further member its states (two generations, with the fp16 pieces where the layout has
+// them), its (G, V) logits and its step workspace, then the (G, V) combined log-probs the selection reads.
+namespace {
+
+struct EnsembleLayout {
+  SearchLayout base;
+  SscStepStates states[SSC_ENSEMBLE_MAX];   // [0] = base.states
+  size_t logits[SSC_ENSEMBLE_MAX], stepws[SSC_ENSEMBLE_MAX];
+  size_t combined;
+  size_t total;
+};
+
+EnsembleLayout ensemble_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, int M) {
+  EnsembleLayout l;
+  l.base = search_layout(cfg, d, SEARCH_ENSEMBLE);
+  const size_t G = (size_t)d->nimg * d->n_samples * d->S * d->beam;
+  const size_t prow = l.base.states.has_planes() ? (size_t)ssc_decode_planes_ld(cfg) : 0;
+  size_t o = l.base.total;
+  l.states[0] = l.base.states; l.logits[0] = l.base.logits; l.stepws[0] = l.base.stepws;
+  for (int m = 1; m < M; ++m) {
+    l.states[m].reserve(o, G, cfg->H, prow);
+    l.logits[m] = ssc_ws_take(o, G * (size_t)cfg->V * 4);
+    l.stepws[m] = ssc_ws_take(o, l.base.stepws_bytes);
+  }
+  l.combined = ssc_ws_take(o, G * (size_t)cfg->V * 4);
+  l.total = o;
+  return l;
+}
+
+bool ensemble_members_ok(const ssc_ensemble_desc* e) {
+  return e && e->M >= 1 && e->M <= SSC_ENSEMBLE_MAX && (e->mode == 0 || e->mode == 1);
+}
+
+}  // namespace
+
+extern "C" size_t ssc_decode_search_ensemble_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
+                                                             const ssc_ensemble_desc* e) {
+  if (!search_dims_ok(cfg, d) || !ensemble_members_ok(e)) return 0;
+  return ensemble_layout(cfg, d, e->M).total;
+}
+
+extern "C" int ssc_decode_search_ensemble(const ssc_model_cfg* cfg, const ssc_ensemble_desc* e, const ssc_search_desc* d,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+  SscGemmModeScope mode_scope(cfg);
+  if (!workspace || !ensemble_members_ok(e) || !e->params || !e->imgbufs || !desc_ok(cfg, d) || d->attn) return SSC_EINVAL;
+  SearchCombine comb{};
+  double wsum = 0.0;
+  for (int m = 0; m < e->M; ++m) {
+    if (!e->params[m] || !e->imgbufs[m]) return SSC_EINVAL;
+    const float w = e->weights ? e->weights[m] : 1.f;
+    if (!(w > 0.f) || !isfinite(w)) return SSC_EINVAL;
+    wsum += (double)w;
+  }
+  if (d->imgbuf != e->imgbufs[0] || !isfinite(wsum)) return SSC_EINVAL;
+  for (int m = 0; m < e->M; ++m) comb.logw[m] = (float)log((double)(e->weights ? e->weights[m] : 1.f) / wsum);
+  comb.mode = e->mode;
+  const EnsembleLayout l = ensemble_layout(cfg, d, e->M);
+  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  comb.out = l.combined;
+  SearchMember mem[SSC_ENSEMBLE_MAX];
+  for (int m = 0; m < e->M; ++m) mem[m] = SearchMember{e->params[m], e->imgbufs[m], l.states[m], l.logits[m], l.stepws[m], SscAttTable{}};
+  return search_run(cfg, mem, e->M, &comb, d, l.base, (char*)workspace, BeamSelect{false, nullptr}, false, (hipStream_t)stream);
 }
 
 // the stochastic beam search: S = 1, no machine, the limits of ssc_beam_step_gumbel (k <= 32, per_node <= k, k <= V)
@@ -310,7 +416,9 @@ extern "C" int ssc_decode_stochastic_beam(const ssc_model_cfg* cfg, const ssc_pa
   const SearchLayout l = search_layout(cfg, d, SEARCH_GUMBEL);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   char* W = (char*)workspace;
-  return search_run(cfg, p, d, l, W, GumbelSelect{s, {(float*)(W + l.gs[0]), (float*)(W + l.gs[1])}}, false, (hipStream_t)stream);
+  SearchMember self = search_self(p, d, l);
+  return search_run(cfg, &self, 1, nullptr, d, l, W, GumbelSelect{s, {(float*)(W + l.gs[0]), (float*)(W + l.gs[1])}}, false,
+                    (hipStream_t)stream);
 }
 
 // the sampled-node beam search: S = 1, no machine, the limits of ssc_beam_step_sampled
@@ -332,7 +440,8 @@ extern "C" int ssc_decode_sampled_beam(const ssc_model_cfg* cfg, const ssc_param
   if (!p || !workspace || !snb_search_ok(cfg, d, s)) return SSC_EINVAL;
   const SearchLayout l = search_layout(cfg, d, SEARCH_SAMPLED);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
-  return search_run(cfg, p, d, l, (char*)workspace, SampledSelect{s, with_replacement}, false, (hipStream_t)stream);
+  SearchMember self = search_self(p, d, l);
+  return search_run(cfg, &self, 1, nullptr, d, l, (char*)workspace, SampledSelect{s, with_replacement}, false, (hipStream_t)stream);
 }
 
 // the diverse beam search: S = 1, no machine, the limits of ssc_beam_step_diverse
@@ -354,7 +463,8 @@ extern "C" int ssc_decode_diverse_beam(const ssc_model_cfg* cfg, const ssc_param
   if (!p || !workspace || !dbs_search_ok(cfg, d, s)) return SSC_EINVAL;
   const SearchLayout l = search_layout(cfg, d, SEARCH_DIVERSE, ssc_diverse_beam_list(d->beam, s->groups, d->per_node, cfg->V));
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
-  return search_run(cfg, p, d, l, (char*)workspace, DiverseSelect{s}, false, (hipStream_t)stream);
+  SearchMember self = search_self(p, d, l);
+  return search_run(cfg, &self, 1, nullptr, d, l, (char*)workspace, DiverseSelect{s}, false, (hipStream_t)stream);
 }
 
 // the beam search under the decode rules: S = 1, no machine, the limits of ssc_beam_step_rules (every step index below 64)
@@ -380,7 +490,8 @@ extern "C" int ssc_decode_rules_beam(const ssc_model_cfg* cfg, const ssc_params*
   RulesSelect sel{r, {(int*)(W + l.rhist[0]), (int*)(W + l.rhist[1])}, {(int*)(W + l.rlen[0]), (int*)(W + l.rlen[1])},
                   {(float*)(W + l.rscore[0]), (float*)(W + l.rscore[1])}, d->max_steps};
   int a = 0;
-  SSC_TRY(search_run(cfg, p, d, l, W, sel, false, st, &a));
+  SearchMember self = search_self(p, d, l);
+  SSC_TRY(search_run(cfg, &self, 1, nullptr, d, l, W, sel, false, st, &a));
   const size_t G = (size_t)d->nimg * d->n_samples * d->beam;
   if (hipMemcpyAsync(scores, sel.score[a], G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   if (hipMemcpyAsync(lengths, sel.len[a], G * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;

@@ -306,6 +306,14 @@ class DecodeEngine:
         -> (predictions (B, S, beam, steps), log_probs (B, S, beam)); one wait at the end, for the number of steps.
         attention=True (here and on every one-call decode below): additionally an AttentionRecord of the call's captions in the
         order returned (caption q = the flattened index of the predictions' leading dimensions), for DecodeEngine.attention."""
+        return self._search(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm, compiled, mach, skip_dead,
+                            early_stop, attention, self.lib.ssc_decode_search_workspace_bytes,
+                            lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws))
+
+    def _search(self, ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm, compiled, mach, skip_dead,
+                early_stop, attention, workspace_bytes, call):
+        """The body of search(): the machine's checks and descriptor fields around _one_call, for the entry point `call` and its
+        `workspace_bytes` (ssc_decode_search; ssc_decode_search_ensemble for EnsembleDecodeEngine.search)."""
         B = ctx.nimg * n_samples
         S = 1 if fsm is None else fsm.size(1)
         if fsm is not None:
@@ -325,9 +333,7 @@ class DecodeEngine:
                 sd.tables, sd.dims = _lib.ptr(compiled.tables), compiled.dims
 
         return self._one_call(ctx, sentiment, n_samples, S, beam, per_node, max_steps, end_index, eps0, eps, early_stop,
-                              skip_dead and (compiled is not None or fsm is None), (B, S, beam),
-                              self.lib.ssc_decode_search_workspace_bytes,
-                              lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws),
+                              skip_dead and (compiled is not None or fsm is None), (B, S, beam), workspace_bytes, call,
                               machine, attention=attention)
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
@@ -481,6 +487,117 @@ class DecodeEngine:
 
 
 DecodeEngine.step_from_embedding = DecodeEngine._step_from_embedding
+
+
+ENSEMBLE_MODES = {"prob": 0, "logprob": 1}
+
+
+def ensemble_weights(weights, n: int):
+    """The members' weights as the library takes them: n positive finite floats, normalised to sum 1 (None: uniform).
+    ValueError otherwise."""
+    import math
+    if weights is None:
+        return [1.0 / n] * n
+    w = [float(x) for x in weights]
+    if len(w) != n:
+        raise ValueError(f"ensemble: {len(w)} weights for {n} members")
+    if any(not math.isfinite(x) or x <= 0.0 for x in w):
+        raise ValueError(f"ensemble: weights must be positive and finite, got {w}")
+    total = sum(w)
+    return [x / total for x in w]
+
+
+class EnsembleContext:
+    """One ImageContext per member over the same features (EnsembleDecodeEngine.prepare)."""
+
+    def __init__(self, ctxs):
+        self.ctxs = list(ctxs)
+        self.feats, self.obj = self.ctxs[0].feats, self.ctxs[0].obj
+        self.nimg, self.R = self.ctxs[0].nimg, self.ctxs[0].R
+
+
+class EnsembleDecodeEngine:
+    """Ensemble decoding: one beam search over several DecodeEngines of one architecture (checkpoints of one configuration), the
+    members' word distributions averaged at every step (ssc_decode_search_ensemble).  mode "prob": the weighted mean of the
+    members' probabilities; "logprob": the normalised weighted mean of their log-probs.  weights: positive, any scale (None:
+    uniform).  Only the beam search runs over an ensemble; the other decodes name the feature they lack."""
+
+    def __init__(self, members, weights=None, mode: str = "prob"):
+        members = list(members)
+        if not 1 <= len(members) <= _lib.SSC_ENSEMBLE_MAX:
+            raise ValueError(f"ensemble: 1 .. {_lib.SSC_ENSEMBLE_MAX} members, got {len(members)}")
+        if mode not in ENSEMBLE_MODES:
+            raise ValueError(f"ensemble: unknown mode {mode!r} (one of {sorted(ENSEMBLE_MODES)})")
+        for m in members[1:]:
+            if m.dims != members[0].dims:
+                raise ValueError(f"ensemble: members of different architecture: {m.dims} != {members[0].dims}")
+            if m._cfg.gemm_mode != members[0]._cfg.gemm_mode or m.device != members[0].device:
+                raise ValueError("ensemble: members differ in their numerics mode or their device")
+        self.weights = ensemble_weights(weights, len(members))
+        self.members = members
+        self.mode = mode
+        self.dims = members[0].dims
+        self.device = members[0].device
+        self.lib = members[0].lib
+        self._cfg = members[0]._cfg
+
+    @property
+    def weights_frozen(self):
+        return all(m.weights_frozen for m in self.members)
+
+    @weights_frozen.setter
+    def weights_frozen(self, on):
+        for m in self.members:
+            m.weights_frozen = on
+
+    def prepare(self, feats: torch.Tensor, obj_means: Optional[torch.Tensor] = None) -> EnsembleContext:
+        return EnsembleContext([m.prepare(feats, obj_means) for m in self.members])
+
+    def search(self, ctx: EnsembleContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
+               max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
+               compiled: Optional["CompiledFsm"] = None, mach: Optional[torch.Tensor] = None, skip_dead: bool = False,
+               early_stop: bool = True, attention: bool = False):
+        """DecodeEngine.search over the ensemble: the same arguments (ctx from this engine's prepare), the same return value."""
+        if attention:
+            raise NotImplementedError("attention traces of an ensemble are not implemented (ensemble decoding runs the beam search only)")
+        if len(ctx.ctxs) != len(self.members):
+            raise ValueError("ensemble: the context was not prepared by this engine")
+        M = len(self.members)
+        structs = [m._params() for m in self.members]   # (kept alive until the call is queued)
+        params = (C.POINTER(_lib.Params) * M)(*[C.pointer(s) for s in structs])
+        imgbufs = (C.c_void_p * M)(*[c.buf.data_ptr() for c in ctx.ctxs])
+        weights = (C.c_float * M)(*self.weights)
+        ed = _lib.EnsembleDesc(M, params, imgbufs, weights, ENSEMBLE_MODES[self.mode])
+        lib, cfg = self.lib, C.byref(self._cfg)
+        # member 0 runs the shared body of the search: its descriptor carries imgbufs[0], as the library asks
+        return self.members[0]._search(ctx.ctxs[0], sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm,
+                                       compiled, mach, skip_dead, early_stop, False,
+                                       lambda c, sd: lib.ssc_decode_search_ensemble_workspace_bytes(c, sd, C.byref(ed)),
+                                       lambda p, sd, ws: lib.ssc_decode_search_ensemble(cfg, C.byref(ed), C.byref(sd), *ws))
+
+    def _unsupported(self, what):
+        raise NotImplementedError(f"{what} over an ensemble is not implemented (ensemble decoding runs the beam search only)")
+
+    def sample(self, *a, **k):
+        self._unsupported("the sampled decode (sample)")
+
+    def score(self, *a, **k):
+        self._unsupported("caption scoring (score)")
+
+    def stochastic_beam(self, *a, **k):
+        self._unsupported("the stochastic beam search (stochastic_beam)")
+
+    def sampled_beam(self, *a, **k):
+        self._unsupported("the sampled-node beam search (sampled_beam)")
+
+    def diverse_beam(self, *a, **k):
+        self._unsupported("the diverse beam search (diverse_beam)")
+
+    def rules_beam(self, *a, **k):
+        self._unsupported("the beam search under decode rules (rules_beam)")
+
+    def attention(self, *a, **k):
+        self._unsupported("the attention trace (attention)")
 
 
 class CompiledFsm:

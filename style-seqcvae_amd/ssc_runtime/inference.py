@@ -9,18 +9,18 @@ per-call result given the same per-row noise.
 import math
 import os
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Tuple, Union
 
 import torch
 
 from . import lib as _lib
-from .decode import AttentionTrace, DecodeEngine
+from .decode import AttentionTrace, DecodeEngine, EnsembleDecodeEngine
 from .decoding import select_best_beam_simple_batched, select_best_state_simple_batched
 
 
 
 
-def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[torch.Tensor], n_samples: int, beam: int,
+def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.Tensor, sentiment: Optional[torch.Tensor], n_samples: int, beam: int,
                    max_steps: int, boundary_index: int, fsm: Optional[torch.Tensor] = None,
                    num_constraints: Optional[torch.Tensor] = None, min_constraints_to_satisfy: int = 0,
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
@@ -28,6 +28,9 @@ def diverse_decode(dec: DecodeEngine, feats: torch.Tensor, sentiment: Optional[t
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
                    rules=None, attention: Optional[str] = None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
+    dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
+    over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
+    single engine and raise NotImplementedError with an ensemble.
     fsm: None (trivial one-state machine, what MAX_GIVEN_CONSTRAINTS: 0 produces), or (nimg, S, S, V) uint8 - ONE machine per
     image, shared by its n_samples latent samples through an index list -, or (nimg*n_samples, S, S, V) (a copy per sample).
     eps_steps: optional explicit noise per step call [(rows_k, Z)]; default: a generator of this call's own, seeded by ONE draw

@@ -150,6 +150,18 @@ class SearchDesc(C.Structure):
                 ("host_flag_host", vp), ("attn", C.POINTER(AttnRecord))]
 
 
+SSC_ENSEMBLE_MAX = 8
+
+
+class EnsembleRowsDesc(C.Structure):
+    _fields_ = [("M", C.c_int), ("logits", C.POINTER(vp)), ("ld", C.c_int), ("logw", c_float_p), ("mode", C.c_int)]
+
+
+class EnsembleDesc(C.Structure):
+    _fields_ = [("M", C.c_int), ("params", C.POINTER(C.POINTER(Params))), ("imgbufs", C.POINTER(vp)), ("weights", c_float_p),
+                ("mode", C.c_int)]
+
+
 class SamplerDesc(C.Structure):
     _fields_ = [("kind", C.c_int), ("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float), ("seed", C.c_uint64)]
 
@@ -310,6 +322,9 @@ SYMBOLS = {
     "ssc_host_device_ptr": (_i, [vp, C.POINTER(vp)]),
     "ssc_decode_search_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_search": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), vp, _sz, vp]),
+    "ssc_ensemble_combine_rows": (_i, [C.POINTER(EnsembleRowsDesc), _i, _i, vp, vp, _i, vp, _i, vp]),
+    "ssc_decode_search_ensemble_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(EnsembleDesc)]),
+    "ssc_decode_search_ensemble": (_i, [C.POINTER(ModelCfg), C.POINTER(EnsembleDesc), C.POINTER(SearchDesc), vp, _sz, vp]),
     "ssc_sample_rows": (_i, [vp, _i, _i, _i, C.POINTER(SamplerDesc), vp, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_sample_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), vp, _sz, vp]),

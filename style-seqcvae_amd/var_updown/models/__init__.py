@@ -1,3 +1,4 @@
+from .ensemble import CaptionerEnsemble
 from .updown_captioner import UpDownCaptioner
 
-__all__ = ["UpDownCaptioner"]
+__all__ = ["CaptionerEnsemble", "UpDownCaptioner"]
