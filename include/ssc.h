@@ -960,6 +960,61 @@ int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_params* p, const
                             float free_bits, int free_bits_mode, int fed_inputs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Knowledge distillation in the cross-entropy train step (Hinton et al. 2015; Kim & Rush 2016, word-level): the student's rows
+ * are trained against a teacher's per-word distribution beside the (label-smoothed) hard targets.  Rows, weights w, counts n_b
+ * and targets are those of ssc_ce_fwd_smooth.  Per row with w != 0, x the student's logits row, s the teacher's scores row (raw
+ * logits or log-probs: only differences within a row matter), tau the temperature, alpha the mixing weight:
+ *   q      = softmax(s / tau)                                 (an entry s[v] = -inf has q[v] = 0)
+ *   p_tau  = softmax(x / tau)
+ *   kd_row = tau^2 * sum_{v: q[v] > 0} q[v] * (log q[v] - log p_tau[v])       (tau^2 KL(q || p_tau) >= 0)
+ *   row    = (1 - alpha) * row(eps) + alpha * kd_row          row(eps): the label-smoothed row of ssc_ce_fwd_smooth
+ *   loss_b = n_b * sum_t w*row / (n_b + 1e-13)
+ *   kd_b   = n_b * sum_t w*kd_row / (n_b + 1e-13)             (reported beside the loss, not weighted by alpha)
+ *   bwd (in place): x[v] <- ((1 - alpha) * (softmax(x)[v] - (1-eps)[v==y] - eps/V) + alpha * tau * (p_tau[v] - q[v]))
+ *                            * gl_b * w * n_b/(n_b + 1e-13)
+ * The teacher is a constant (no gradient flows into it); nll, the unsmoothed hard loss of the same forward, is what it is without
+ * distillation.  Rows with w = 0 are never read in either matrix: their slots are written as 0, the backward writes a zero row.
+ * kd_row is formed relative to the rows' maxima - sum_v q[v] ((s[v]-max s) - (x[v]-max x))/tau - (log sum exp((s-max s)/tau) -
+ * log sum exp((x-max x)/tau)), q[v] = 0 terms skipped -, so no large quantities cancel and a teacher that is a bit copy of the
+ * student gives exactly 0.  A teacher row with a NaN gives a NaN loss for its caption; a student entry at -inf under positive
+ * teacher mass gives +inf.  One workgroup per row; the forward reads each row from HBM once (a second scan finds it in L2), the
+ * backward is one in-place stream; 16 bytes per lane when ldl % 4 == ldt % 4 == 0 and the two matrices share one misalignment,
+ * else element by element; columns V .. ld-1 are never touched.  No atomics: two calls on the same inputs are bit-identical.
+ * kd == NULL or alpha == 0: the calls ARE ssc_ce_fwd_smooth / ssc_ce_bwd_smooth (ssc_train_fwd_fb / ssc_train_bwd_fb /
+ * ssc_train_bwd_phases_fb) - the same launches, the same bits, and no buffer of kd is read or written.
+ * SSC_EINVAL and no launch, before anything touches memory: what the plain calls refuse; alpha outside [0, 1] or NaN; a
+ * temperature <= 0, NaN or infinite; with alpha > 0 a NULL teacher or rows, ldt < V, or a teacher range that overlaps the logits
+ * range.  SSC_EALIGN: a pointer that is no multiple of 4.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* teacher; int ldt;   /* (T*B, V) scores, ldt >= V; must not overlap the student's logits */
+  float alpha;                     /* in [0, 1] */
+  float temperature;               /* > 0, finite */
+  float* rows;                     /* caller-owned, 3*T*B floats: [lse(x/tau) | lse(s/tau) | w*kd_row], written by the forward, read by the backward */
+  float* kd;                       /* (B) or NULL: kd_b */
+} ssc_distill;
+/* `lse` holds 3*T*B floats, [lse | w*row | w*row(0)], as for ssc_ce_fwd_smooth; the backward is given the kd of its forward. */
+int ssc_ce_fwd_distill(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
+                       int V, float eps, const ssc_distill* kd, float* lse, float* loss, float* nll, void* stream);
+int ssc_ce_bwd_distill(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, const float* lse,
+                       const float* gl, int T, int B, int V, float eps, const ssc_distill* kd, void* stream);
+/* ssc_train_fwd_fb / ssc_train_bwd_fb / ssc_train_bwd_phases_fb with the descriptor beside the cfg (whose layout is pinned, as
+ * the numbering of ssc_train_workspace_view is; the scratch is the caller's, so ssc_train_workspace_bytes does not change).
+ * Only the two cross-entropy calls of the step change - the forward's after the vocabulary head, the backward's at the start of
+ * phase 16; a backward must be given the kd of its forward, with `rows` as that forward left it.  Label smoothing, free bits and
+ * the caller's KL weight compose unchanged.  Distillation does not compose with scheduled sampling (the student would be fed its
+ * own words while the teacher was fed the ground truth): there is no entry that takes both.  The self-critical, posterior,
+ * scoring and decode paths never distil. */
+int ssc_train_fwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                     float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_distill* kd, void* stream);
+int ssc_train_bwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                     const float* gl, const float* gk, const ssc_params* g, float free_bits, int free_bits_mode,
+                     const ssc_distill* kd, void* stream);
+int ssc_train_bwd_phases_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
+                            size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
+                            float free_bits, int free_bits_mode, const ssc_distill* kd, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Scoring GIVEN captions under the model (teacher forcing): how likely is a caption that came from elsewhere - a ground-truth
  * caption, another decoder's or another checkpoint's output.
  * ---------------------------------------------------------------------------------------------- */

@@ -82,6 +82,13 @@ parser.add_argument("--scst-top-k", type=int, default=40)
 parser.add_argument("--scst-top-p", type=float, default=0.9)
 parser.add_argument("--scst-reward", default="0,0,0,0,0,1", help="reward weights B1,B2,B3,B4,R,C (default: CIDEr-D alone)")
 parser.add_argument("--scst-max-steps", type=int, default=20, help="with --scst-references: longest sampled caption")
+# (absent from the namespace unless given, as --reset-optimizer)
+parser.add_argument("--distill-checkpoints", nargs="+", default=argparse.SUPPRESS,
+                    help="knowledge distillation: 1..8 teacher checkpoints of this configuration (as this script writes them); the "
+                         "cross-entropy steps then train against their per-word distributions with OPTIM.DISTILL_ALPHA (> 0) at "
+                         "OPTIM.DISTILL_TEMPERATURE, several teachers combined as OPTIM.DISTILL_MODE says.  Loaded once, frozen")
+parser.add_argument("--distill-weights", nargs="+", type=float, default=argparse.SUPPRESS,
+                    help="with --distill-checkpoints: one positive weight per teacher (default: uniform)")
 
 
 VAL_IMAGES_PER_CALL = 100
@@ -156,9 +163,34 @@ def scst_references(args, data, vocabulary):
     return refs
 
 
+def distill_plan(_A, _C):
+    """(checkpoint paths, weights or None, alpha, temperature, mode) of a distilling run, None for one that does not distil; the
+    flags' and keys' errors as SystemExit, before anything is loaded."""
+    paths = getattr(_A, "distill_checkpoints", None)
+    weights = getattr(_A, "distill_weights", None)
+    alpha = _C.OPTIM.DISTILL_ALPHA
+    if paths is None:
+        if weights is not None:
+            raise SystemExit("--distill-weights needs --distill-checkpoints")
+        if alpha > 0:
+            raise SystemExit(f"OPTIM.DISTILL_ALPHA {alpha} needs teachers: pass --distill-checkpoints")
+        return None
+    if not 1 <= len(paths) <= 8:
+        raise SystemExit(f"--distill-checkpoints takes 1 to 8 checkpoints; found {len(paths)}")
+    if weights is not None and (len(weights) != len(paths) or any(not 0.0 < w < float("inf") for w in weights)):
+        raise SystemExit(f"--distill-weights takes one positive finite weight per teacher ({len(paths)}); found {weights}")
+    if not alpha > 0:
+        raise SystemExit("--distill-checkpoints needs OPTIM.DISTILL_ALPHA > 0 (the weight of the teachers' term in the loss)")
+    if _C.OPTIM.SCHEDULED_SAMPLING_START >= 0:
+        raise SystemExit("--distill-checkpoints (distillation) cannot be combined with a configured scheduled sampling "
+                         "(OPTIM.SCHEDULED_SAMPLING_START >= 0): the teachers' distributions are those of the ground-truth inputs")
+    return list(paths), (list(weights) if weights is not None else None), alpha, _C.OPTIM.DISTILL_TEMPERATURE, _C.OPTIM.DISTILL_MODE
+
+
 def main():
     _A = parser.parse_args()
     _C = Config(_A.config, _A.config_override)
+    plan = distill_plan(_A, _C)
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -239,6 +271,22 @@ def main():
     if ss_configured and _A.scst_references and rank == 0:
         print(f"OPTIM.SCHEDULED_SAMPLING_START {_C.OPTIM.SCHEDULED_SAMPLING_START} is ignored by the self-critical steps "
               "(--scst-references): their rollout already feeds the model its own words")
+    # --distill-checkpoints / OPTIM.DISTILL_*: the cross-entropy steps, on the fused and the autograd path.  One set of frozen
+    # teachers per rank, loaded once; every step they run their forwards on the step's minibatch and noise ahead of the student's
+    teacher = None
+    if plan is not None and _A.scst_references:
+        if rank == 0:
+            print(f"--distill-checkpoints / OPTIM.DISTILL_ALPHA {plan[2]} are ignored by the self-critical steps (--scst-references): "
+                  "the advantage-weighted loss is no likelihood target")
+    elif plan is not None:
+        from ssc_runtime.distill import DistillTeacher
+        paths, weights, kd_alpha, kd_tau, kd_mode = plan
+        members = []
+        for path in paths:
+            sd = torch.load(path, map_location=device, weights_only=True)["model"]
+            members.append(({k: v for k, v in sd.items()}, eng.dims))
+        teacher = DistillTeacher(members, weights, kd_mode, student_dims=eng.dims, device=device)
+        model.distill(teacher, kd_alpha, kd_tau)   # (the autograd path; the fused path passes distill= itself)
     from ssc_runtime.engine import OptimSpec, check_optimizer_state_kind
     kind = _C.OPTIM.OPTIMIZER
     spec = None   # the fused paths' optimiser; None: SGD with OPTIM.MOMENTUM / WEIGHT_DECAY, as before the key existed
@@ -313,12 +361,16 @@ def main():
         elif _A.fused_optimizer:
             B, L = batch["caption_tokens"].shape
             eps = model._draw_eps(L + 1, B, device)
+            kd_args = {}
+            if teacher is not None:
+                kd_args["distill"] = teacher.distill(batch["image_features"], batch["caption_tokens"], batch["sentiment"], eps, kd_alpha,
+                                                     kd_tau, batch.get("obj_atts"))
             loss_b, kld_b = eng.train_step(batch["image_features"], batch["caption_tokens"], batch["sentiment"], eps, lr=lr,
                                            kld_weight=_C.MODEL.KLD_WEIGHT, momentum=_C.OPTIM.MOMENTUM,
                                            weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
                                            decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec,
                                            label_smoothing=smoothing, kl_beta=beta, free_bits=free_bits,
-                                           free_bits_mode=free_bits_mode, **ss_args)
+                                           free_bits_mode=free_bits_mode, **ss_args, **kd_args)
             reconstr_loss, kld_loss = loss_b.mean(), eng.kld_raw().mean()
             kld_free = kld_b.mean() if free_bits > 0 else None
             loss = reconstr_loss + beta * kld_b.mean() / _C.MODEL.KLD_WEIGHT
@@ -338,7 +390,9 @@ def main():
         if rank == 0 and (iteration % 100 == 0 or iteration == start_iteration or _C.OPTIM.NUM_ITERATIONS <= 100):
             rec = {"iteration": iteration, "1reconstr_loss": float(reconstr_loss), "2kld_loss": float(kld_loss),
                    "3loss": float(loss), "4learning_rate": lr, "elapsed_s": time.time() - t0}
-            if smoothing > 0 and scst is None:
+            if teacher is not None:
+                rec["kd"] = float(eng.kd().mean())     # tau^2 KL(teacher || student) of the same forward (this rank's rows)
+            if (smoothing > 0 or teacher is not None) and scst is None:
                 rec["nll"] = float(eng.nll().mean())   # the unsmoothed loss of the same forward (this rank's rows)
             if scst is None:
                 rec["kl_beta"] = beta

@@ -558,11 +558,15 @@ extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, cons
 }
 
 // ss: scheduled sampling (include/ssc.h: ssc_train_fwd_ss); nullptr or prob 0 = teacher forcing, the launches as they are without it
+// kd: distillation (include/ssc.h: ssc_train_fwd_kd); nullptr or alpha 0 = the cross-entropy as it is without it.  Never both.
 static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace, size_t workspace_bytes,
-                          float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_sched_sampling* ss, void* stream) {
+                          float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_sched_sampling* ss,
+                          const ssc_distill* kd, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
   SSC_TRY(check_free_bits(free_bits, free_bits_mode));
+  bool kd_on;
+  SSC_TRY(ssc_distill_check(kd, nullptr, 0, 0, cfg->V, &kd_on));
   if (ss && (!(ss->prob >= 0.f && ss->prob <= 1.f) || !sampler_ok(&ss->sampler, cfg->V))) return SSC_EINVAL;   // NaN included
   if (!workspace || !loss || !kld) return SSC_EINVAL;
   const bool ss_on = ss && ss->prob > 0.f;
@@ -570,6 +574,8 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
+  // (the teacher's rows may not meet the logits block the backward overwrites: checked here, ahead of the first launch)
+  if (kd_on) SSC_TRY(ssc_distill_check(kd, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -788,6 +794,9 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     SSC_TRY(gemm_rows(c, true, {{hd_all, l.Hp, p->out_w, p->ld_out_w, H}}, TB, V, W + l.logits, l.Vp, p->out_b));
   }
   // label_smoothing 0 launches the kernels of ssc_ce_fwd; the unsmoothed loss of this forward lands in l.nll either way
+  if (kd_on)   // the soft targets of a teacher beside the (smoothed) hard loss: distill.hip
+    return ssc_ce_fwd_distill_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, kd, W + l.lse,
+                                     W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
   SSC_TRY(ssc_ce_fwd_smooth_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, W + l.lse,
                                    W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st));
   return SSC_OK;
@@ -795,13 +804,19 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
 extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                 size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, nullptr, stream);
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, nullptr, nullptr, stream);
+}
+
+extern "C" int ssc_train_fwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode,
+                                const ssc_distill* kd, void* stream) {
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, nullptr, kd, stream);
 }
 
 extern "C" int ssc_train_fwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                 size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode,
                                 const ssc_sched_sampling* ss, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, ss, stream);
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, ss, nullptr, stream);
 }
 
 // ---- posterior scoring of the forward that last ran in this workspace (include/ssc.h: ssc_train_posterior) ------------------------------
@@ -923,14 +938,18 @@ int ssc_g_dw_one_flush = ssc_env_int("SSC_DW_ONE_FLUSH", 1);
 // (ssc_runtime/engine.py): the output head's 48 MB travel under the whole time loop.
 static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                           size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream,
-                          unsigned phases, float free_bits, int free_bits_mode, int fed_inputs = 0) {
+                          unsigned phases, float free_bits, int free_bits_mode, int fed_inputs = 0,
+                          const ssc_distill* kd = nullptr) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
   SSC_TRY(check_free_bits(free_bits, free_bits_mode));
+  bool kd_on;
+  SSC_TRY(ssc_distill_check(kd, nullptr, 0, 0, cfg->V, &kd_on));
   if (!workspace || !gl || !gk || !g || (fed_inputs != 0 && fed_inputs != 1)) return SSC_EINVAL;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
+  if (kd_on) SSC_TRY(ssc_distill_check(kd, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -949,7 +968,10 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
   if (phases & (1u | 16u)) {
   // ---- vocabulary head ------------------------------------------------------------------------------
-  SSC_TRY(ssc_ce_bwd_smooth(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, st));
+  if (kd_on)   // (the forward of this minibatch left the rows' log-sum-exps in kd->rows)
+    SSC_TRY(ssc_ce_bwd_distill(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, kd, st));
+  else
+    SSC_TRY(ssc_ce_bwd_smooth(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, st));
   const float* dlog = W + l.logits;
   {  // every zero-initialised buffer of this phase in one launch
     FillList f;
@@ -1334,4 +1356,18 @@ extern "C" int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_param
   if (phases == 0 || phases > 255u) return SSC_EINVAL;
   if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
   return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode, fed_inputs);
+}
+
+extern "C" int ssc_train_bwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
+                                int free_bits_mode, const ssc_distill* kd, void* stream) {
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, free_bits, free_bits_mode, 0, kd);
+}
+
+extern "C" int ssc_train_bwd_phases_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                       size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
+                                       unsigned phases, float free_bits, int free_bits_mode, const ssc_distill* kd, void* stream) {
+  if (phases == 0 || phases > 255u) return SSC_EINVAL;
+  if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode, 0, kd);
 }

@@ -123,6 +123,12 @@ int ssc_beam_merge(const float* sval, const int64_t* sidx, const float* last_lp,
 // the first two, whose place - and with it every other buffer's - is what it was before the third block existed
 int ssc_ce_fwd_smooth_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
                              int V, float eps, float* lse, float* nllw, float* nllw0, float* loss, float* nll, hipStream_t st);
+// distillation (distill.hip, include/ssc.h: ssc_distill): the descriptor's refusals - *on = kd != NULL and alpha > 0; logits NULL
+// leaves the overlap test to a later call -, and ssc_ce_fwd_distill with its three blocks given one by one
+int ssc_distill_check(const ssc_distill* kd, const float* logits, int ldl, size_t rows, int V, bool* on);
+int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
+                              int V, float eps, const ssc_distill* kd, float* lse, float* nllw, float* nllw0, float* loss, float* nll,
+                              hipStream_t st);
 int ssc_decode_att_table_enabled();   // the "dec_att_table" switch (decode.hip)
 // the start of a one-call decode with the early-stop protocol (search.hip): ctl[0] = max_steps, the counters behind it zero;
 // tokens0 (B) = end_index, the token the first step feeds

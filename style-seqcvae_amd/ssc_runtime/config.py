@@ -128,6 +128,13 @@ def _defaults() -> dict:
             # or its most likely word ("argmax").  Self-critical steps and validation never sample
             "SCHEDULED_SAMPLING_START": -1, "SCHEDULED_SAMPLING_INCREASE_EVERY": 5000, "SCHEDULED_SAMPLING_INCREASE_PROB": 0.05,
             "SCHEDULED_SAMPLING_MAX_PROB": 0.25, "SCHEDULED_SAMPLING_SAMPLER": "multinomial", "SCHEDULED_SAMPLING_TEMPERATURE": 1.0,
+            # knowledge distillation of the cross-entropy steps (Hinton et al. 2015; word-level: Kim & Rush 2016): with teacher
+            # checkpoints given to scripts/train.py (--distill-checkpoints) the loss of a word is (1 - DISTILL_ALPHA) * the
+            # (smoothed) hard loss + DISTILL_ALPHA * DISTILL_TEMPERATURE^2 * KL(teacher || student) at that temperature; 0 = off.
+            # DISTILL_MODE: how several teachers are combined, "prob" (the mean of their probabilities) or "logprob" (the normalised
+            # mean of their log-probs), as in ensemble decoding.  Not together with scheduled sampling; self-critical steps and
+            # validation never distil
+            "DISTILL_ALPHA": 0.0, "DISTILL_TEMPERATURE": 1.0, "DISTILL_MODE": "prob",
         },
     }
 
@@ -248,6 +255,12 @@ class Config(object):
             raise ValueError(f"OPTIM.SCHEDULED_SAMPLING_SAMPLER must be one of multinomial | argmax; found {o.SCHEDULED_SAMPLING_SAMPLER!r}")
         if not num(o.SCHEDULED_SAMPLING_TEMPERATURE) or not 0.0 < o.SCHEDULED_SAMPLING_TEMPERATURE < float("inf"):
             raise ValueError(f"OPTIM.SCHEDULED_SAMPLING_TEMPERATURE must be a finite number > 0; found {o.SCHEDULED_SAMPLING_TEMPERATURE!r}")
+        if not num(o.DISTILL_ALPHA) or not 0.0 <= o.DISTILL_ALPHA <= 1.0:
+            raise ValueError(f"OPTIM.DISTILL_ALPHA must be a number in [0, 1]; found {o.DISTILL_ALPHA!r}")
+        if not num(o.DISTILL_TEMPERATURE) or not 0.0 < o.DISTILL_TEMPERATURE < float("inf"):
+            raise ValueError(f"OPTIM.DISTILL_TEMPERATURE must be a finite number > 0; found {o.DISTILL_TEMPERATURE!r}")
+        if o.DISTILL_MODE not in ("prob", "logprob"):
+            raise ValueError(f"OPTIM.DISTILL_MODE must be one of prob | logprob; found {o.DISTILL_MODE!r}")
 
     def __getattr__(self, attr: str):
         return getattr(self.__dict__["_C"], attr)

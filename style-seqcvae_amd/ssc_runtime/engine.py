@@ -144,6 +144,47 @@ def check_sched_sampling(prob, sampler=None, seed=0) -> "Optional[_lib.SchedSamp
     return _lib.SchedSampling(v, _lib.SamplerDesc(kind, top_k, top_p, temperature, int(seed) & ((1 << 64) - 1)))
 
 
+def check_distill(alpha, temperature=1.0) -> Tuple[float, float]:
+    """(alpha in [0, 1], temperature > 0 and finite) as floats - the mixing weight and the temperature of ssc_distill (include/ssc.h)
+    -, else a ValueError that names distill_alpha / distill_temperature."""
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError):
+        a = float("nan")
+    if isinstance(alpha, bool) or not 0.0 <= a <= 1.0:
+        raise ValueError(f"distill_alpha must be a number in [0, 1]; found {alpha!r}")
+    try:
+        t = float(temperature)
+    except (TypeError, ValueError):
+        t = float("nan")
+    if isinstance(temperature, bool) or not 0.0 < t < float("inf"):
+        raise ValueError(f"distill_temperature must be a finite number > 0; found {temperature!r}")
+    return a, t
+
+
+@dataclass
+class Distill:
+    """The soft targets of ONE forward (TrainEngine.forward / train_step: `distill=`): scores (T*B, >= V) float32 on the engine's
+    device - a teacher's raw logits or log-probs of the same rows, time-major, leading dimension ld (DistillTeacher.scores makes
+    them) -, the mixing weight alpha and the temperature.  alpha 0 = off: the forward is the one without it."""
+    scores: torch.Tensor
+    ld: int
+    alpha: float
+    temperature: float = 1.0
+
+    def __post_init__(self):
+        self.alpha, self.temperature = check_distill(self.alpha, self.temperature)
+        self.ld = int(self.ld)
+
+
+def check_distill_sampling(alpha, ss_prob):
+    """Distillation and scheduled sampling do not compose (the student would be fed its own words while the teacher was fed the
+    ground truth: the two rows would describe different histories): a ValueError that names both."""
+    if float(alpha) > 0.0 and float(ss_prob) > 0.0:
+        raise ValueError(f"distillation (distill_alpha = {alpha}) and scheduled sampling (ss_prob = {ss_prob}) cannot be used "
+                         "in one forward: the teacher's rows are those of the ground-truth inputs")
+
+
 FREE_BITS_MODES = {"element": 1, "step": 2, "dim": 3}   # ssc_free_bits.mode / the free_bits_mode argument of ssc_train_fwd_fb
 
 
@@ -349,6 +390,9 @@ class TrainEngine:
         self._keep = None
         self._kld = None              # the kld tensor the last forward returned (kld_raw() without a floor)
         self._fb = (0.0, 3)           # (free_bits, free_bits_mode) of the last forward: every backward of it is given the same
+        self._kd = None               # the ssc_distill of the last forward (None: it did not distil) - every backward of it is given the same
+        self._kd_keep = None          # (the scores tensor it points into)
+        self._kd_scratch = None       # 3*T*B + B floats: the descriptor's rows blocks and kd_b
         self._fed = 0                 # 1: the last forward sampled its inputs (ss_prob > 0) - every backward of it scatters by the fed ids
         self._post_ws = None          # posterior_forward's own workspace: the training forward's activations are never overwritten
         self._post_ws_key = None
@@ -431,7 +475,7 @@ class TrainEngine:
         return bt, (sent, obj_atts)
 
     def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0, free_bits=0.0, free_bits_mode="dim",
-                ss_prob=0.0, ss_sampler=None, ss_seed=0):
+                ss_prob=0.0, ss_sampler=None, ss_seed=0, distill: "Optional[Distill]" = None):
         """-> (loss (B,), kld (B,)); keeps activations for backward().  obj_atts (B,R,S): per-region attribute means, kld_mode 2 only.
         label_smoothing: eps of THIS call's cross-entropy (ssc_ce_fwd_smooth; 0 = the plain masked NLL, the kernels as they are
         without it).  It stays in the engine's cfg until the next forward, so every backward of this forward - the phased one of
@@ -443,17 +487,26 @@ class TrainEngine:
         ss_prob / ss_sampler / ss_seed: scheduled sampling of THIS call (include/ssc.h: ssc_train_fwd_ss; check_sched_sampling) -
         with probability ss_prob an eligible position is fed the word the model draws from its own logits of the previous step.
         0 = off: ssc_train_fwd_fb as before.  input_tokens() / fed_mask() read what was fed; the engine remembers, until the next
-        forward, that every backward of this forward scatters the embedding gradient by the fed ids."""
+        forward, that every backward of this forward scatters the embedding gradient by the fed ids.
+        distill: the soft targets of THIS call (Distill; include/ssc.h: ssc_distill) - loss is then (1 - alpha) * the (smoothed)
+        hard loss + alpha * tau^2 KL(teacher || student) per row, kd() the KL term alone, nll() unchanged.  None or alpha 0 = off:
+        ssc_train_fwd_fb as before.  Kept beside the cfg until the next forward, as the options above are.  Not together with
+        ss_prob > 0 (ValueError)."""
+        check_distill_sampling(distill.alpha if distill is not None else 0.0, ss_prob)
         self._cfg.label_smoothing = check_label_smoothing(label_smoothing)
         self._fb = check_free_bits(free_bits, free_bits_mode)
         ss = check_sched_sampling(ss_prob, ss_sampler, ss_seed)
         self._fed = int(ss is not None)
         bt, sent = self._batch(feats, caps, sentiment, eps, obj_atts)
+        self._kd, self._kd_keep = self._distill_desc(distill, (bt.L + 1) * bt.B, bt.B), distill
         ws = self._workspace(bt.B, bt.R, bt.L)
         loss = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         kld = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         p = self.params.c_struct()
-        if ss is None:
+        if self._kd is not None:
+            self.lib.ssc_train_fwd_kd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                      _lib.ptr(kld), *self._fb, C.byref(self._kd), _lib.stream_ptr())
+        elif ss is None:
             self.lib.ssc_train_fwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
                                       _lib.ptr(kld), *self._fb, _lib.stream_ptr())
         else:
@@ -463,6 +516,39 @@ class TrainEngine:
         self._kld = kld
         self.fwd_version += 1
         return loss, kld
+
+    def _distill_desc(self, distill, rows, B) -> "Optional[_lib.Distill]":
+        """ssc_distill of a forward over `rows` = T*B rows, or None where it does not distil; the scratch is the engine's."""
+        if distill is None or distill.alpha == 0.0:
+            return None
+        t = distill.scores
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == self.params.flat.device):
+            raise ValueError("distill.scores must be a float32 tensor on the engine's device")
+        have = t.untyped_storage().nbytes() // 4 - t.storage_offset()   # (scores may be a view of padded rows: what lies behind its first element)
+        if distill.ld < self.dims.V or have < (rows - 1) * distill.ld + self.dims.V:
+            raise ValueError(f"distill.scores holds {have} floats at ld {distill.ld}: fewer than the {rows} rows of V = {self.dims.V} of this forward")
+        n = 3 * rows + B
+        if self._kd_scratch is None or self._kd_scratch.numel() != n:
+            self._kd_scratch = torch.zeros(n, dtype=torch.float32, device=self.device)
+        sc = self._kd_scratch
+        return _lib.Distill(t.data_ptr(), distill.ld, distill.alpha, distill.temperature, sc.data_ptr(), sc[3 * rows:].data_ptr())
+
+    def kd(self):
+        """(B,) kd_b of the last forward - n_b sum_t w tau^2 KL(teacher || student) / (n_b + 1e-13), not weighted by alpha -: a view of
+        the engine's scratch, valid until the next distilled forward; zeros when the last forward did not distil."""
+        B = self._keep[0].B
+        if self._kd is None:
+            return torch.zeros(B, dtype=torch.float32, device=self.device)
+        return self._kd_scratch[self._kd_scratch.numel() - B:]
+
+    def _bwd_phases(self, p, bt, ws, gl, gk, g, mask):
+        """One ssc_train_bwd_phases call of the last forward, with the options that forward kept beside the cfg."""
+        if self._kd is not None:
+            self.lib.ssc_train_bwd_phases_kd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                             _lib.ptr(gk), C.byref(g), mask, *self._fb, C.byref(self._kd), _lib.stream_ptr())
+        else:
+            self.lib.ssc_train_bwd_phases_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                             _lib.ptr(gk), C.byref(g), mask, *self._fb, self._fed, _lib.stream_ptr())
 
     def posterior_forward(self, feats, caps, sentiment, eps, obj_atts=None):
         """The posterior branch's view of given captions (include/ssc.h: ssc_train_posterior) -> (nll (B,), kld (B,), log_ratio (B,),
@@ -546,8 +632,7 @@ class TrainEngine:
         # only what the update will read travels: a frozen decoder LSTM / tied embedding keeps its (stale) gradient range at home
         t_lo, t_hi = self.trainable_range(bool(set(self.decoder_names) & skipset))
         for mask, rng in self.phase_ranges():
-            self.lib.ssc_train_bwd_phases_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, self._fed, _lib.stream_ptr())
+            self._bwd_phases(p, bt, ws, gl, gk, g, mask)
             if rng is not None:
                 lo, hi = max(rng[0], t_lo), min(rng[1], t_hi)
                 if hi > lo and xg is not None:
@@ -663,8 +748,7 @@ class TrainEngine:
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
         for mask in masks:
-            self.lib.ssc_train_bwd_phases_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4,
-                                             _lib.ptr(gl), _lib.ptr(gk), C.byref(g), mask, *self._fb, self._fed, _lib.stream_ptr())
+            self._bwd_phases(p, bt, ws, gl, gk, g, mask)
 
     def backward(self, gl, gk, skip: Sequence[str] = ()):
         """Writes d(sum_b gl_b loss_b + gk_b kld_b)/dparam into self.grads for every parameter not in `skip`
@@ -677,6 +761,10 @@ class TrainEngine:
         g = self.grads.c_struct(only=only)
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
+        if self._kd is not None:
+            self.lib.ssc_train_bwd_kd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                      _lib.ptr(gk), C.byref(g), *self._fb, C.byref(self._kd), _lib.stream_ptr())
+            return
         self.lib.ssc_train_bwd_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
                                   _lib.ptr(gk), C.byref(g), *self._fb, self._fed, _lib.stream_ptr())
 
@@ -892,19 +980,21 @@ class TrainEngine:
 
     def train_step(self, feats, caps, sentiment, eps, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
                    max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None,
-                   label_smoothing=0.0, kl_beta=1.0, free_bits=0.0, free_bits_mode="dim", ss_prob=0.0, ss_sampler=None, ss_seed=0):
+                   label_smoothing=0.0, kl_beta=1.0, free_bits=0.0, free_bits_mode="dim", ss_prob=0.0, ss_sampler=None, ss_seed=0,
+                   distill: "Optional[Distill]" = None):
         """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row.
         optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above.
         label_smoothing: as forward(); loss is then the smoothed one, nll() the unsmoothed.
         kl_beta: the annealing weight of this iteration (ssc_runtime/schedule.py) - the objective is mean loss + kl_beta * mean kld /
         kld_weight, so the upstream of kld_b is kl_beta / (B * kld_weight); 0 is legal: no KL gradient at all.
         free_bits / free_bits_mode: as forward(); kld is then the floored KL, kld_raw() the raw one.
-        ss_prob / ss_sampler / ss_seed: scheduled sampling, as forward()."""
+        ss_prob / ss_sampler / ss_seed: scheduled sampling, as forward().
+        distill: soft targets, as forward(); loss is then the mixed one, kd() the KL term, nll() the hard loss."""
         kl_beta = float(kl_beta)
         if not 0.0 <= kl_beta < float("inf"):
             raise ValueError(f"kl_beta must be a finite number >= 0; found {kl_beta!r}")
         loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing, free_bits, free_bits_mode, ss_prob, ss_sampler,
-                                 ss_seed)
+                                 ss_seed, distill)
         B = loss.numel()
         key = (B, float(kld_weight))
         if getattr(self, "_upstream_key", None) != key:   # d(mean loss + beta mean kld / KLD_WEIGHT) / d(loss_b, kld_b): two (B,) buffers per (B, weight)

@@ -170,6 +170,10 @@ class SchedSampling(C.Structure):
     _fields_ = [("prob", C.c_float), ("sampler", SamplerDesc)]
 
 
+class Distill(C.Structure):
+    _fields_ = [("teacher", vp), ("ldt", C.c_int), ("alpha", C.c_float), ("temperature", C.c_float), ("rows", vp), ("kd", vp)]
+
+
 class ScoreDesc(C.Structure):
     _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_captions", C.c_int), ("n_samples", C.c_int), ("max_len", C.c_int),
                 ("end_index", C.c_int), ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("obj_atts", vp), ("targets", vp),
@@ -335,6 +339,13 @@ SYMBOLS = {
     "ssc_train_bwd_ss": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), _f, _i, _i, vp]),
     "ssc_train_bwd_phases_ss": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
                                      C.c_uint, _f, _i, _i, vp]),
+    "ssc_ce_fwd_distill": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Distill), vp, vp, vp, vp]),
+    "ssc_ce_bwd_distill": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Distill), vp]),
+    "ssc_train_fwd_kd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, _f, _i, C.POINTER(Distill), vp]),
+    "ssc_train_bwd_kd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), _f, _i,
+                              C.POINTER(Distill), vp]),
+    "ssc_train_bwd_phases_kd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
+                                     C.c_uint, _f, _i, C.POINTER(Distill), vp]),
     "ssc_score_rows": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_score_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(ScoreDesc)]),
     "ssc_decode_score": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), vp, _sz, vp]),

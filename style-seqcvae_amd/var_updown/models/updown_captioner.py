@@ -21,6 +21,7 @@ from ssc_runtime.cellops import cell_train_step
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.decoding import select_best_beam_with_constraints
 from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_free_bits, check_label_smoothing, check_sched_sampling
+from ssc_runtime.engine import check_distill, check_distill_sampling
 
 from ..modules import ConstrainedBeamSearch, UpDownCell
 
@@ -29,8 +30,8 @@ class _SeqCVAETrainFn(torch.autograd.Function):
     """loss_b, kld_b = f(params; feats, caps, sentiment, eps) with the hand-derived BPTT as backward."""
 
     @staticmethod
-    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, ss, *params):
-        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *ss)
+    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, ss, distill, *params):
+        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *ss, distill=distill)
         ctx.eng, ctx.names = eng, names
         ctx.version = eng.fwd_version
         return loss, kld
@@ -41,7 +42,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
         if eng.fwd_version != ctx.version:
             raise RuntimeError("UpDownCaptioner: backward() after a newer forward(); the activation workspace holds "
                                "only the latest forward")
-        need = ctx.needs_input_grad[11:]
+        need = ctx.needs_input_grad[12:]
         skip = [n for n, k in zip(ctx.names, need) if not k]
         eng.backward(gl, gk, skip=skip)
         if eng.dp_autograd:   # data parallel on the autograd path: ONE sum all-reduce of the flat gradient buffer, then the mean
@@ -50,7 +51,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
                 eng.grads.flat.mul_(1.0 / world)
         frozen = set(eng.frozen_names)
         grads = tuple(eng.grads.views[n].clone() if (k and n not in frozen) else None for n, k in zip(ctx.names, need))
-        return (None,) * 11 + grads
+        return (None,) * 12 + grads
 
 
 class UpDownCaptioner(nn.Module):
@@ -92,6 +93,7 @@ class UpDownCaptioner(nn.Module):
         self.free_bits = check_free_bits(free_bits, free_bits_mode)[0]
         self.free_bits_mode = free_bits_mode
         self._sched_sampling = (0.0, None, 0)   # scheduled_sampling(): off
+        self._distill = None                    # distill(): off
         if diverse_beam is not None:
             if sampler is not None:
                 raise ValueError("MODEL.DIVERSE_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam' without MODEL.STOCHASTIC_BEAM_SEARCH")
@@ -340,9 +342,16 @@ class UpDownCaptioner(nn.Module):
             params = [self._named()[n] for n in names]
             sent = sentiment if sentiment is not None else None
             obj_means = self._obj_means(obj_atts, batch_size, num_boxes)
-            loss, kld = _SeqCVAETrainFn.apply(eng, names, image_features.contiguous().float(),
-                                              caption_tokens.contiguous().long(), sent, eps, obj_means, self.label_smoothing,
-                                              self.free_bits, self.free_bits_mode, self._sched_sampling, *params)
+            feats, caps = image_features.contiguous().float(), caption_tokens.contiguous().long()
+            kd = None
+            if self._distill is not None:   # the teachers' forwards on this minibatch and this noise, ahead of the student's
+                teacher, alpha, temperature = self._distill
+                check_distill_sampling(alpha, self._sched_sampling[0])
+                kd = teacher.distill(feats, caps, sent, eps, alpha, temperature, obj_means)
+            loss, kld = _SeqCVAETrainFn.apply(eng, names, feats, caps, sent, eps, obj_means, self.label_smoothing,
+                                              self.free_bits, self.free_bits_mode, self._sched_sampling, kd, *params)
+            if kd is not None:
+                return {"loss": loss, "kld": kld, "kd": eng.kd().clone()}
             return {"loss": loss, "kld": kld}
         # eval branch (updown_captioner.py:324-366)
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
@@ -390,6 +399,20 @@ class UpDownCaptioner(nn.Module):
         default state) = off.  The eval forward, scst_step, score_captions and posterior_score_captions never sample."""
         check_sched_sampling(prob, sampler, seed)
         self._sched_sampling = (float(prob), sampler, int(seed))
+
+    def distill(self, teacher, alpha, temperature=1.0):
+        """Knowledge distillation of the NEXT training forwards (the autograd path; include/ssc.h: ssc_distill): `teacher` (an
+        ssc_runtime.distill.DistillTeacher of this captioner's architecture and vocabulary) runs its members' forwards on every
+        minibatch and the same noise, and loss becomes (1 - alpha) * the (smoothed) hard loss + alpha * temperature^2 KL(teacher ||
+        student) per word; the output dict gains "kd", the KL term alone.  teacher None or alpha 0 (the default state) = off.  Not
+        together with scheduled_sampling (ValueError at the forward).  The eval forward, scst_step, score_captions and
+        posterior_score_captions never distil."""
+        if teacher is None:
+            self._distill = None
+            return
+        alpha, temperature = check_distill(alpha, temperature)
+        teacher.check_student(self._dims())
+        self._distill = (teacher, alpha, temperature) if alpha > 0.0 else None
 
     def decode_attention(self, mode):
         """Attention traces of the NEXT eval forwards (include/ssc.h: ssc_attn_record): "summary" - the output dict gains, per
