@@ -1054,6 +1054,53 @@ int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_sc
                      void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent-guided decoding: decode under a caption's posterior instead of the configured prior.  A guide gives every batch entry of a
+ * one-call decode - b = (image, sample) for the search and the sampled decode, row g = (image, caption, sample) for scoring - and every
+ * step t < min(steps, len[b]) the distribution its latent is drawn from: reconstruction (the stored z path of a posterior forward,
+ * var NULL), style transfer (an exemplar's path on another image), interpolation (a mix of two paths), sampling around an exemplar.
+ * Decode step t - step 0 feeds @@BOUNDARY@@ - uses slab t: the train forward's step index.  The guide is a z, not a prior mean:
+ * SIMPLE_VAE's zeroing of the prior mean does not apply to it.
+ *   guided row r of entry b = r / rows_per_entry:  z[r, j] = eps[r, j] * sqrtf(var[t, b, j]) + mean[t, b, j]   (the expression of
+ *     ssc_latent_prior_sample_pm: a decode driven step by step with the guide expanded to (rows, Z) gives the same bits);
+ *     var NULL: z = mean, and eps is NOT read for guided (t, b).  A negative variance gives NaN.
+ *   unguided row (t >= steps, or t >= len[b]):  what ssc_latent_prior_sample gives, eps * sqrtf(cfg->prior_var) + pm_scale * sent[r].
+ * Pad columns Z .. round4(Z) of z are zeroed; columns >= Z of mean / var are never read.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int steps;           /* slabs in mean / var */
+  const float* mean;   /* (steps, B, ld) */
+  const float* var;    /* (steps, B, ld), or NULL: 0 - z = mean and eps is NOT read for guided (t, b) */
+  int ld;              /* >= Z */
+  const int* len;      /* (B), or NULL: every entry is guided for all `steps` */
+} ssc_latent_guide;
+/* The latent launch of one decode step under a guide: `rows` rows in entries of rows_per_entry consecutive rows (B = rows /
+ * rows_per_entry entries: 1 row per entry in a search's first step, S * beam in its later steps, 1 in the sampled decode and in
+ * scoring).  eps (rows, ldeps), sent (rows) or NULL, z (rows, ldz), ldeps, ldz >= Z.  g NULL or t >= g->steps: exactly the launch
+ * of ssc_latent_prior_sample.  16-byte accesses on each operand whose leading dimension and base allow them, scalar accesses
+ * otherwise; the result does not depend on which are taken.  No atomics.  SSC_EINVAL and no launch: a NULL eps or z, rows, Z or
+ * rows_per_entry < 1, rows no multiple of rows_per_entry, t < 0, steps < 1, a NULL mean, ld, ldeps or ldz < Z, a pointer that is
+ * not 4-byte aligned. */
+int ssc_latent_guide_rows(const ssc_latent_guide* g, int t, int rows, int rows_per_entry, int Z, const float* eps, int ldeps,
+                          const float* sent, float pm_scale, float prior_var, float* z, int ldz, void* stream);
+/* The one-call decodes under a guide: ssc_decode_search, ssc_decode_sample and ssc_decode_score with step t's z block drawn by
+ * ssc_latent_guide_rows - one launch in place of one launch; every machine, mach, skip_dead, early_stop, attention traces and
+ * every numerics mode as without a guide, and the same *_workspace_bytes.  guide NULL: the unguided call - the same launches, the
+ * same bits.  B of the guide: nimg * n_samples (search, sample), nimg * n_captions * n_samples (score).  SSC_EINVAL before any
+ * launch: what the unguided call refuses; steps < 1, a NULL mean, ld < cfg->Z, a mean, var or len that is not 4-byte aligned,
+ * cfg->kld_mode == 2 (SENTIMENT_VAE = 2: the pooled prior mean there also conditions the LSTMs). */
+int ssc_decode_search_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_latent_guide* guide,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                             const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream);
+int ssc_decode_score_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d, const ssc_latent_guide* guide,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* Comparing captions: per pair q of pred (n, Lp) and ref (n, Lr) int64, the length of each the tokens before its first end_index
+ * or negative id, out (n, 5) int32 = { n_pred, n_ref, equal positions below min(n_pred, n_ref), exact (0 / 1: equal lengths, every
+ * position equal), word-level Levenshtein distance }.  One thread per pair, integer arithmetic, no atomics: two calls give the same
+ * bits.  SSC_EINVAL and no launch: a NULL pointer, n < 0, Lp or Lr outside [1, 128], end_index < 0.  n = 0: nothing to do. */
+int ssc_caption_match(const int64_t* pred, int Lp, const int64_t* ref, int Lr, int n, int end_index, int* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Posterior scoring of given captions: what the encoder branch q(z_t | x) = N(mu_tb, exp(lv_tb)) of the TRAIN forward says about a
  * caption - the pieces of the ELBO and of the importance-weighted bound with q as the proposal (Burda et al. 2016).
  * Rows r = t * B + b (step t of caption row b).  w (T*B): the train forward's step weight.  The generative prior is the one the

@@ -80,6 +80,14 @@ parser.add_argument("--attention-output", default="",
                          "entropy of its attention in nats.  The predictions file is what it is without the flag")
 parser.add_argument("--attention-full", action="store_true",
                     help='with --attention-output: every entry also holds "maps" (words, regions), the whole attention of every word')
+parser.add_argument("--exemplar-tensors", default="",
+                    help="latent-guided decoding: a .pt file (torch.save) {\"image_id\": [...], \"captions\": (N, L) int64, 0-padded} with "
+                         "ONE exemplar caption per image.  Each is encoded on that image's own features by the posterior branch and the "
+                         "image's captions are decoded under the exemplar's latent path instead of the prior (beam search, constrained "
+                         "or not, and word sampling).  The predictions file has its usual layout")
+parser.add_argument("--exemplar-jitter", type=float, default=None,
+                    help="with --exemplar-tensors: sample AROUND the exemplar's path - standard deviation J times the posterior's "
+                         "(default 0: every latent sample of an image decodes the path itself)")
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -112,9 +120,39 @@ def check_ensemble_args(_A):
     return w, _A.ensemble_mode or "prob"
 
 
+def check_exemplar_args(_A):
+    """The exemplar flags, checked before anything is loaded -> the jitter (0.0 without --exemplar-jitter)."""
+    if not _A.exemplar_tensors:
+        if _A.exemplar_jitter is not None:
+            raise SystemExit("--exemplar-jitter needs --exemplar-tensors")
+        return 0.0
+    if not os.path.isfile(_A.exemplar_tensors):
+        raise SystemExit(f"--exemplar-tensors: no such file {_A.exemplar_tensors!r}")
+    j = 0.0 if _A.exemplar_jitter is None else _A.exemplar_jitter
+    if not math.isfinite(j) or j < 0:
+        raise SystemExit(f"--exemplar-jitter: a finite standard-deviation factor >= 0 wanted, got {j}")
+    if _A.ensemble_checkpoints:
+        raise SystemExit("--exemplar-tensors is not available with --ensemble-checkpoints: latent guides steer a single model")
+    return j
+
+
+def load_exemplars(path, max_len):
+    """-> {image_id: caption row (L,) int64} of an --exemplar-tensors file"""
+    blob = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(blob, dict) or "image_id" not in blob or "captions" not in blob:
+        raise SystemExit('--exemplar-tensors: a dict {"image_id": [...], "captions": (N, L) int64} wanted')
+    caps = torch.as_tensor(blob["captions"]).to(torch.int64)
+    ids = [int(x) for x in blob["image_id"]]
+    if caps.dim() != 2 or caps.size(0) != len(ids) or caps.size(1) < 1 or caps.size(1) > max_len:
+        raise SystemExit(f"--exemplar-tensors: captions must be (N, L) with N = {len(ids)} image ids and 1 <= L <= DATA.MAX_CAPTION_LENGTH "
+                         f"= {max_len}, got {tuple(caps.shape)}")
+    return {i: caps[k] for k, i in enumerate(ids)}
+
+
 def main():
     _A = parser.parse_args()
     ens_weights, ens_mode = check_ensemble_args(_A)
+    jitter = check_exemplar_args(_A)
     _C = Config(_A.config, _A.config_override)
     random.seed(_C.RANDOM_SEED)
     np.random.seed(_C.RANDOM_SEED)
@@ -166,6 +204,18 @@ def main():
         raise SystemExit("MODEL.DIVERSE_BEAM_SEARCH does not take constraints")
     if rules is not None and (_A.constraints_json or _A.boxes_json):
         raise SystemExit("MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN do not take constraints")
+    exemplars = None
+    if _A.exemplar_tensors:
+        if (sampler is not None and (sampler.beam_search or sampled_beam)) or diverse is not None or rules is not None:
+            raise SystemExit("--exemplar-tensors steers the beam search (constrained or not) and word sampling: no "
+                             "MODEL.STOCHASTIC_BEAM_SEARCH / SAMPLED_BEAM_SEARCH / DIVERSE_BEAM_SEARCH and no decode rules")
+        if _C.MODEL.SENTIMENT_VAE == 2 and not _C.MODEL.SIMPLE_VAE:
+            raise SystemExit("--exemplar-tensors is not available with MODEL.SENTIMENT_VAE 2")
+        exemplars = load_exemplars(_A.exemplar_tensors, _C.DATA.MAX_CAPTION_LENGTH)
+        V = vocabulary.get_vocab_size()
+        for i, c in exemplars.items():
+            if bool(((c < 0) | (c >= V)).any()) or int(c[0]) == 0:
+                raise SystemExit(f"--exemplar-tensors: the caption of image {i} is empty or holds ids outside the vocabulary [0, {V})")
     boundary = vocabulary.get_token_index("@@BOUNDARY@@")
     predictions = []
     id2word = np.array([vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())], dtype=object)
@@ -237,6 +287,15 @@ def main():
                 ncons = torch.tensor([len(constraints.get(int(data.image_id[lo + i]), [])[:kmax]) for i in range(n_here)]
                                      ).repeat_interleave(n_z)
             obj = data.obj[lo: lo + n_here, : feats.size(1)].to(device) if getattr(data, "obj", None) is not None else None
+            guide = None
+            if exemplars is not None:   # every image's exemplar, encoded on the image's own features: the path its samples decode
+                from ssc_runtime.guide import LatentGuide, encode_captions
+                here = [int(x) for x in data.image_id[lo: lo + n_here]]
+                missing = [i for i in here if i not in exemplars]
+                if missing:
+                    raise SystemExit(f"--exemplar-tensors holds no caption for image {missing[0]} ({len(missing)} images of this call)")
+                caps = torch.stack([exemplars[i] for i in here]).to(device)
+                guide = LatentGuide.from_encoding(encode_captions(model._eng, feats, caps, senti), jitter=jitter, repeat=n_z)
             if diverse is not None:   # every group's best caption: N_Z_SAMPLES * DIVERSE_BEAM_GROUPS captions per image
                 out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
                                      diverse_beam=diverse, return_groups=True, attention=attn_mode)
@@ -245,7 +304,8 @@ def main():
             else:
                 out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
-                                     obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode)
+                                     obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode,
+                                     guide=guide)
                 pred = out[0]
             trace = out[-1] if attn_mode else None
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the

@@ -46,6 +46,10 @@ parser.add_argument("--val-posterior-samples", type=int, default=argparse.SUPPRE
                     help="with --val-tensors: also score the held-out captions under the POSTERIOR branch with K noise draws each "
                          "(UpDownCaptioner.posterior_score_captions) and append val_elbo_nll_per_token, val_iwae_nll_per_token, "
                          "val_kl_per_token, val_active_units; 0: off")
+parser.add_argument("--val-reconstruction", action="store_true", default=argparse.SUPPRESS,
+                    help="with --val-tensors: also decode every held-out caption back from its own posterior latent path "
+                         "(UpDownCaptioner.reconstruct_captions, beam search under a latent guide) and append val_recon_token_accuracy, "
+                         "val_recon_exact_rate, val_recon_wer: how much of a caption its latents carry")
 parser.add_argument("--serialization-dir", default="checkpoints/experiment")
 parser.add_argument("--checkpoint-every", default=10000, type=int)
 parser.add_argument("--start-from-checkpoint", default="")
@@ -187,6 +191,22 @@ def distill_plan(_A, _C):
     return list(paths), (list(weights) if weights is not None else None), alpha, _C.OPTIM.DISTILL_TEMPERATURE, _C.OPTIM.DISTILL_MODE
 
 
+def validate_reconstruction(model, val, n_images, device):
+    """Reconstruction of the captions of `val` through z with the model as it stands: the mean path of the posterior branch (no
+    noise), the beam search under it, the words compared on the device.  Deterministic; draws nothing from any random stream, the
+    model's mode left alone, a forward on a workspace of its own - a run with it trains exactly as the same run without it."""
+    from ssc_runtime.guide import match_summary
+    parts = []
+    for lo in range(0, n_images, VAL_IMAGES_PER_CALL):
+        hi = min(lo + VAL_IMAGES_PER_CALL, n_images)
+        caps = val.caps[lo:hi]
+        caps = caps[:, 0] if caps.dim() == 3 else caps   # (the first caption of every image)
+        rec = model.reconstruct_captions(val.feats[lo:hi].to(device), caps, sentiment=val.senti[lo:hi, 0].to(device), prior_samples=0)
+        parts.append(rec.match)
+    s = match_summary(torch.cat(parts))
+    return {"val_recon_token_accuracy": s["token_accuracy"], "val_recon_exact_rate": s["exact_rate"], "val_recon_wer": s["wer"]}
+
+
 def main():
     _A = parser.parse_args()
     _C = Config(_A.config, _A.config_override)
@@ -204,6 +224,9 @@ def main():
     posterior_samples = getattr(_A, "val_posterior_samples", 0)
     if posterior_samples < 0:
         raise SystemExit("--val-posterior-samples must be at least 0")
+    reconstruction = getattr(_A, "val_reconstruction", False)
+    if reconstruction and not _A.val_tensors:
+        raise SystemExit("--val-reconstruction needs --val-tensors")
     if -1 in _A.gpu_ids:
         raise SystemExit("--gpu-ids -1 (CPU) is not available: this build has no CPU path")
     gpu = _A.gpu_ids[local % len(_A.gpu_ids)]
@@ -419,6 +442,8 @@ def main():
             rec.update(validate(model, val, n_val, _A.val_samples, _C.RANDOM_SEED, iteration, device))
             if posterior_samples > 0:
                 rec.update(validate_posterior(model, val, n_val, posterior_samples, _C.RANDOM_SEED, iteration, device))
+            if reconstruction:
+                rec.update(validate_reconstruction(model, val, n_val, device))
             log.write(json.dumps(rec) + "\n")
             log.flush()
         if rank == 0 and iteration % _A.checkpoint_every == 0:

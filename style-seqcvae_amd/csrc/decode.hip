@@ -587,6 +587,12 @@ extern "C" int ssc_decode_ungathered_ok(const ssc_model_cfg* cfg, int nimg, int 
 
 extern "C" int ssc_decode_step(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_decode_step_desc* d, void* workspace,
                                size_t workspace_bytes, void* stream) {
+  return ssc_decode_step_guided(cfg, p, d, nullptr, workspace, workspace_bytes, stream);
+}
+
+// the step with its z block from a latent guide (ssc_common.h: SscStepGuide); sg null: the step of ssc_decode_step
+int ssc_decode_step_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_decode_step_desc* d, const SscStepGuide* sg,
+                           void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!cfg || !p || !d || !workspace) return SSC_EINVAL;
   const int G = d->G, R = d->R, rpi = d->rows_per_image;
@@ -712,6 +718,9 @@ extern "C" int ssc_decode_step(const ssc_model_cfg* cfg, const ssc_params* p, co
     if (d->prior_mean_out && hipMemcpy2DAsync(d->prior_mean_out, (size_t)Z * sizeof(float), W + l.pm, (size_t)l.Zp * sizeof(float),
                                               (size_t)Z * sizeof(float), G, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return SSC_EHIP;
+  } else if (sg && sg->guide && sg->t < sg->guide->steps) {   // the call's latent guide: a z per entry, not a prior mean
+    SSC_TRY(ssc_latent_guide_rows(sg->guide, sg->t, G, sg->rows_per_entry, Z, d->eps, Z, cfg->pm_scale != 0.f ? d->sentiment : nullptr,
+                                  cfg->pm_scale, cfg->prior_var, W + l.z, l.Zp, st));
   } else if (d->prior_mean || d->prior_var) {   // the caller's own prior (updown_captioner.py:371-381)
     SSC_TRY(ssc_latent_prior_sample_pm(d->eps, Z, d->prior_mean, Z, d->prior_var, Z, cfg->pm_scale != 0.f ? d->sentiment : nullptr,
                                        cfg->pm_scale, cfg->prior_var, G, Z, W + l.z, l.Zp, st));

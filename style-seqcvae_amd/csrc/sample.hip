@@ -184,8 +184,16 @@ extern "C" size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, co
 
 extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
                                  void* workspace, size_t workspace_bytes, void* stream) {
+  return ssc_decode_sample_guided(cfg, p, d, s, nullptr, workspace, workspace_bytes, stream);
+}
+
+// guide (or null): step t's z block from slab t of the call's latent guide, one entry per row
+extern "C" int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                        const ssc_sampler_desc* s, const ssc_latent_guide* guide, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
+  if (guide && !ssc_latent_guide_ok(cfg, guide)) return SSC_EINVAL;
   const SampleLayout l = sample_layout(cfg, d);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -215,7 +223,8 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
   states.bind(W, 1, &sd);
   sd.att_table = table.next(want_table);
   sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), 0, B, d->R);
-  SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+  SscStepGuide sg{guide, 0, 1};
+  SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
   a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
   a.ctl = d->early_stop ? ctl : nullptr; a.max_steps = d->max_steps; a.host_flag = d->early_stop ? d->host_flag : nullptr;
@@ -232,7 +241,8 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
     sd.att_table = table.next(want_table);
     sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), t, B, d->R);
     sd.row_lp = d->skip_dead ? lp : nullptr; sd.end_index = d->end_index;   // ended rows are not stepped
-    SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+    sg.t = t;
+    SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
     SSC_TRY(sample_launch(a, B, st));
     cur = 1 - cur;

@@ -276,8 +276,14 @@ extern "C" size_t ssc_decode_score_workspace_bytes(const ssc_model_cfg* cfg, con
 
 extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d, void* workspace,
                                 size_t workspace_bytes, void* stream) {
+  return ssc_decode_score_guided(cfg, p, d, nullptr, workspace, workspace_bytes, stream);
+}
+
+// guide (or null): step t's z block from slab t of the call's latent guide, one entry per row g = (image, caption, sample)
+extern "C" int ssc_decode_score_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d,
+                                       const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
-  if (!p || !workspace || !score_desc_ok(cfg, d)) return SSC_EINVAL;
+  if (!p || !workspace || !score_desc_ok(cfg, d) || (guide && !ssc_latent_guide_ok(cfg, guide))) return SSC_EINVAL;
   const ScoreLayout l = score_layout(cfg, d);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -317,7 +323,8 @@ extern "C" int ssc_decode_score(const ssc_model_cfg* cfg, const ssc_params* p, c
       sd.parent = parent0; sd.group = 1;
       sd.row_lp = lp; sd.end_index = d->end_index;   // ended and absent rows (fed token END) are not stepped
     }
-    SSC_TRY(ssc_decode_step(cfg, p, &sd, W + l.stepws, l.stepws_bytes, st));
+    const SscStepGuide sg{guide, t, 1};
+    SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
     a.target = tgt + (size_t)t * G;
     a.last_target = t == 0 ? nullptr : fed + (size_t)t * G;
     a.lp_out = d->token_lp ? d->token_lp + t : (float*)(W + l.steplp);

@@ -201,9 +201,12 @@ struct SearchCombine {
 // final_gen: the generation of the running per-beam state (lp, and a selection's own) that holds the search's last step
 // mem / M: the members (a list of one issues the launches of a single-model search); comb: null for a single-model search, whose
 // selection normalises the one member's raw logits itself
+// guide: the call's latent guide (ssc_decode_search_guided) or null - step t's z block then comes from its slab t, one entry per
+// batch entry: one row in the first step, S * beam rows in the later ones
 template <class Select>
 int search_run(const ssc_model_cfg* cfg, SearchMember* mem, int M, const SearchCombine* comb, const ssc_search_desc* d,
-               const SearchLayout& l, char* W, const Select& sel, bool use_parts, hipStream_t st, int* final_gen = nullptr) {
+               const SearchLayout& l, char* W, const Select& sel, bool use_parts, hipStream_t st, int* final_gen = nullptr,
+               const ssc_latent_guide* guide = nullptr) {
   const int B = d->nimg * d->n_samples, S = d->S, beam = d->beam, SB = S * beam, G = B * SB, H = cfg->H, V = cfg->V, Z = cfg->Z;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
   float* sent_rows = (float*)(W + l.sent_rows);
@@ -234,7 +237,8 @@ int search_run(const ssc_model_cfg* cfg, SearchMember* mem, int M, const SearchC
     sd.imgbuf = mem[m].imgbuf; sd.log_probs = (float*)(W + mem[m].logits);
     mem[m].states.bind(W, 1, &sd);
     sd.att_table = mem[m].table.next(ssc_att_table_wanted(d->R, B, d->n_samples));
-    SSC_TRY(ssc_decode_step(cfg, mem[m].p, &sd, W + mem[m].stepws, l.stepws_bytes, st));
+    const SscStepGuide sg{guide, 0, 1};
+    SSC_TRY(ssc_decode_step_guided(cfg, mem[m].p, &sd, &sg, W + mem[m].stepws, l.stepws_bytes, st));
   }
   if (comb) SSC_TRY(ssc_ensemble_combine_rows(&ed, B, V, nullptr, nullptr, d->end_index, (float*)(W + comb->out), V, st));
   ssc_beam_desc bd{};
@@ -282,7 +286,8 @@ int search_run(const ssc_model_cfg* cfg, SearchMember* mem, int M, const SearchC
       mem[m].states.bind_planes(W, cur, ungathered, &sd);
       sd.att_table = mem[m].table.next(tmode);
       if (use_parts) { sd.log_probs = nullptr; sd.topk_part = (float*)(W + l.parts); }
-      SSC_TRY(ssc_decode_step(cfg, mem[m].p, &sd, W + mem[m].stepws, l.stepws_bytes, st));
+      const SscStepGuide sg{guide, t, SB};
+      SSC_TRY(ssc_decode_step_guided(cfg, mem[m].p, &sd, &sg, W + mem[m].stepws, l.stepws_bytes, st));
     }
     if (comb)   // the rows the steps have left unspecified (row_lp) are not read and not written
       SSC_TRY(ssc_ensemble_combine_rows(&ed, G, V, d->skip_dead ? last : nullptr, d->skip_dead ? lp[a] : nullptr, d->end_index,
@@ -318,15 +323,20 @@ int search_run(const ssc_model_cfg* cfg, SearchMember* mem, int M, const SearchC
 
 extern "C" int ssc_decode_search(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, void* workspace,
                                  size_t workspace_bytes, void* stream) {
+  return ssc_decode_search_guided(cfg, p, d, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ssc_decode_search_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                        const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
-  if (!p || !workspace || !desc_ok(cfg, d)) return SSC_EINVAL;
+  if (!p || !workspace || !desc_ok(cfg, d) || (guide && !ssc_latent_guide_ok(cfg, guide))) return SSC_EINVAL;
   const SearchLayout l = search_layout(cfg, d, SEARCH_BEAM);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   char* W = (char*)workspace;
   const bool use_parts = search_uses_parts(cfg, d, SEARCH_BEAM);
   SearchMember self = search_self(p, d, l);
   return search_run(cfg, &self, 1, nullptr, d, l, W, BeamSelect{use_parts, (const float*)(W + l.parts)}, use_parts,
-                    (hipStream_t)stream);
+                    (hipStream_t)stream, nullptr, guide);
 }
 
 // ---- the beam search over several members (include/ssc.h: ssc_ensemble_desc) ------------------------------------------------------

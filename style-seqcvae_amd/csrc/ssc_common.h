@@ -160,5 +160,16 @@ bool ssc_rules_beam_ok(int B, int k, int n, int V, int end_index, const ssc_rule
 // time-major; backs (max_steps - 1, B * SB) or null: the identity; ctl or null: every step ran; lp (B * SB) or null: no dead beam
 int ssc_attn_anc(const int64_t* words, const int64_t* backs, const int* ctl, const float* lp, int max_steps, int B, int SB,
                  int end_index, int* anc, hipStream_t st);
+// Latent-guided decoding (latent_guide.hip, include/ssc.h: ssc_latent_guide).  What a one-call decode hands a step: the call's guide,
+// the step index t (slab t of the guide) and the rows of one guide entry at this step.  ssc_decode_step_guided is ssc_decode_step
+// with the step's z block drawn by ssc_latent_guide_rows; sg null, sg->guide null or t >= steps: the launches of ssc_decode_step.
+struct SscStepGuide {
+  const ssc_latent_guide* guide;
+  int t, rows_per_entry;
+};
+// what the guided entry points check of a guide before any launch (NULL is refused: the caller passes it only where one is set)
+bool ssc_latent_guide_ok(const ssc_model_cfg* cfg, const ssc_latent_guide* g);
+int ssc_decode_step_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_decode_step_desc* d, const SscStepGuide* sg,
+                           void* workspace, size_t workspace_bytes, void* stream);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

@@ -296,19 +296,33 @@ class DecodeEngine:
             return pred[..., :nsteps].contiguous(), lps, rec
         return pred[..., :nsteps].contiguous(), lps
 
+    def _guide_desc(self, guide, B: int):
+        """-> (ssc_latent_guide, the tensors behind it) of a LatentGuide (ssc_runtime.guide) for a call of B entries, refused on the
+        host where the library would refuse it."""
+        if self.dims.kld_mode == 2:
+            raise NotImplementedError("latent guides (guide=) are not implemented for SENTIMENT_VAE = 2: the pooled prior mean there also "
+                                      "conditions the LSTMs")
+        return guide.desc(self.device, B, self.dims.Z)
+
     def search(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int, max_steps: int,
                end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
                compiled: Optional["CompiledFsm"] = None, mach: Optional[torch.Tensor] = None, skip_dead: bool = False,
-               early_stop: bool = True, attention: bool = False):
+               early_stop: bool = True, attention: bool = False, guide=None):
         """The whole constrained beam search of one call in ONE library call (ssc_decode_search): ctx.nimg images x n_samples
         latent samples, batch entry b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*S*beam, Z):
         the noise of every step, drawn by the caller.  fsm (M,S,S,V) / compiled / mach as in cbs_search.
         -> (predictions (B, S, beam, steps), log_probs (B, S, beam)); one wait at the end, for the number of steps.
         attention=True (here and on every one-call decode below): additionally an AttentionRecord of the call's captions in the
-        order returned (caption q = the flattened index of the predictions' leading dimensions), for DecodeEngine.attention."""
+        order returned (caption q = the flattened index of the predictions' leading dimensions), for DecodeEngine.attention.
+        guide: a LatentGuide (ssc_runtime.guide) over the B entries, or None - step t's latent of entry b is then drawn around
+        guide.mean[t, b] instead of the prior (ssc_decode_search_guided); eps0 / eps are still the noise (unread where the guide has
+        no variance)."""
+        call = lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws)
+        if guide is not None:
+            gd, _keep = self._guide_desc(guide, ctx.nimg * n_samples)
+            call = lambda p, sd, ws: self.lib.ssc_decode_search_guided(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(gd), *ws)
         return self._search(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm, compiled, mach, skip_dead,
-                            early_stop, attention, self.lib.ssc_decode_search_workspace_bytes,
-                            lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws))
+                            early_stop, attention, self.lib.ssc_decode_search_workspace_bytes, call)
 
     def _search(self, ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm, compiled, mach, skip_dead,
                 early_stop, attention, workspace_bytes, call):
@@ -338,28 +352,33 @@ class DecodeEngine:
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
-               attention: bool = False):
+               attention: bool = False, guide=None):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
-        -> (predictions (B, steps) int64, log_probs (B,): each caption's summed untempered log-prob)."""
+        -> (predictions (B, steps) int64, log_probs (B,): each caption's summed untempered log-prob).
+        guide: a LatentGuide over the B entries, or None (ssc_decode_sample_guided; see search)."""
         sampler.check_vocab(self.dims.V)
         sdesc = sampler.desc(seed)
+        call = lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), *ws)
+        if guide is not None:
+            gd, _keep = self._guide_desc(guide, ctx.nimg * n_samples)
+            call = lambda p, sd, ws: self.lib.ssc_decode_sample_guided(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
+                                                                       C.byref(gd), *ws)
         # skip_dead: ended rows are not stepped
         return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, True,
-                              (ctx.nimg * n_samples,), self.lib.ssc_decode_sample_workspace_bytes,
-                              lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd),
-                                                                           C.byref(sdesc), *ws), attention=attention)
+                              (ctx.nimg * n_samples,), self.lib.ssc_decode_sample_workspace_bytes, call, attention=attention)
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
               eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False,
-              attention: bool = False):
+              attention: bool = False, guide=None):
         """The teacher-forced decode of GIVEN captions in ONE library call (ssc_decode_score): targets (nimg, C, L) int64 - the
         caption's words, then end_index from its end on; a slot whose first entry is negative is absent - scored under n_samples
         latent samples each, row g = (image, caption, sample), G = nimg * C * n_samples.  sentiment (G) per row or None; eps0
         (G, Z), eps (L - 1, G, Z): the noise of every step.
         -> (log_probs (G,), n_tokens (nimg, C) int32, token_lp (G, L) or None, token_rank (G, L) int32 or None[, AttentionRecord
-        of the G rows over L steps with attention=True])."""
+        of the G rows over L steps with attention=True]).
+        guide: a LatentGuide over the G rows, or None (ssc_decode_score_guided; see search)."""
         dev = self.device
         assert targets.dim() == 3 and targets.size(0) == ctx.nimg, (targets.shape, ctx.nimg)
         _, Cc, Lc = targets.shape
@@ -382,19 +401,25 @@ class DecodeEngine:
             sd.attn = C.pointer(arec)
         ws = self._workspace(self.lib.ssc_decode_score_workspace_bytes(C.byref(self._cfg), C.byref(sd)))
         p = self._params()
-        self.lib.ssc_decode_score(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws)
+        if guide is not None:
+            gd, _keep = self._guide_desc(guide, G)
+            self.lib.ssc_decode_score_guided(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(gd), *ws)
+        else:
+            self.lib.ssc_decode_score(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws)
         if attention:
             return lps, ntok, tlp, trk, rec
         return lps, ntok, tlp, trk
 
     def stochastic_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                         max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
-                        early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
+                        early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
         """The whole stochastic beam search of one call in ONE library call (ssc_decode_stochastic_beam): ctx.nimg images x n_samples
         latent samples, batch entry b = (image, sample), `beam` captions per entry sampled without replacement by `sampler`
         (sampling.GumbelSampler) with the 64-bit `seed`, per_node candidates per beam.  sentiment (B) or None; eps0 (B, Z),
         eps (max_steps - 1, B*beam, Z): the noise of every step.
         -> (predictions (B, beam, steps) int64, log_probs (B, beam): summed untempered log-probs, descending)."""
+        if guide is not None:
+            _guide_unsupported('the stochastic beam search (stochastic_beam)')
         if not 1 <= per_node <= beam <= min(32, self.dims.V):
             raise ValueError(f"stochastic beam search needs 1 <= per_node <= beam <= min(32, V), got per_node {per_node}, beam {beam}")
         gdesc = sampler.desc(seed)
@@ -407,13 +432,15 @@ class DecodeEngine:
 
     def sampled_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                      max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
-                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
+                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
         """The whole sampled-node beam search of one call in ONE library call (ssc_decode_sampled_beam): the reference's BeamSearch
         driven by a word sampler (ssc_runtime.sampling: multinomial / top-k / top-p) - step 0 takes the top `beam` tokens, every
         later step draws per_node candidates per beam (with or without replacement, sampler.with_replacement) with the 64-bit
         `seed` and keeps the `beam` best by summed log-prob.  ctx.nimg images x n_samples latent samples, batch entry
         b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*beam, Z): the noise of every step.
         -> (predictions (B, beam, steps) int64, log_probs (B, beam): summed untempered log-probs, descending - beam 0 the best)."""
+        if guide is not None:
+            _guide_unsupported('the sampled-node beam search (sampled_beam)')
         V = self.dims.V
         if sampler.beam_search:
             raise ValueError("the sampled-node beam search takes a word sampler (multinomial / top-k / top-p); the Gumbel sampler "
@@ -433,13 +460,15 @@ class DecodeEngine:
 
     def diverse_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                      max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], diverse,
-                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
+                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
         """The whole diverse beam search of one call in ONE library call (ssc_decode_diverse_beam): `beam` beams per batch entry in
         diverse.groups groups (sampling.DiverseBeam), searched in order inside every step with the Hamming penalty
         diverse.strength; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples, batch entry
         b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*beam, Z): the noise of every step.
         -> (predictions (B, beam, steps) int64 group-major, log_probs (B, beam): true summed log-probs, NOT sorted across groups -
         the best caption of an entry is the arg-max)."""
+        if guide is not None:
+            _guide_unsupported('the diverse beam search (diverse_beam)')
         V = self.dims.V
         if not (1 <= beam <= min(32, V) and 1 <= per_node <= min(32, V)):
             raise ValueError(f"diverse beam search needs 1 <= beam, per_node <= min(32, V), got beam {beam}, per_node {per_node}")
@@ -454,7 +483,7 @@ class DecodeEngine:
 
     def rules_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                    max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], rules,
-                   early_stop: bool = True, skip_dead: bool = True, attention: bool = False):
+                   early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
         """The whole beam search under the decode rules of one call in ONE library call (ssc_decode_rules_beam): blocking of
         repeated n-grams, a minimum length, suppressed tokens and a length penalty in the ranking (sampling.DecodeRules), applied
         where the selection runs; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples,
@@ -462,6 +491,8 @@ class DecodeEngine:
         step.  -> (predictions (B, beam, steps) int64, log_probs (B, beam): the true summed log-probs, scores (B, beam): the sums
         over the penalty of the captions' lengths, descending - beam 0 is the best caption -, lengths (B, beam) int32: the tokens
         of every caption, the END counted)."""
+        if guide is not None:
+            _guide_unsupported('the beam search under decode rules (rules_beam)')
         V = self.dims.V
         if not (1 <= beam <= min(32, V) and 1 <= per_node <= min(32, V)):
             raise ValueError(f"the beam search under decode rules needs 1 <= beam, per_node <= min(32, V), got beam {beam}, "
@@ -487,6 +518,11 @@ class DecodeEngine:
 
 
 DecodeEngine.step_from_embedding = DecodeEngine._step_from_embedding
+
+
+def _guide_unsupported(what):
+    from .guide import guide_unsupported
+    guide_unsupported(what)
 
 
 ENSEMBLE_MODES = {"prob": 0, "logprob": 1}
@@ -556,8 +592,10 @@ class EnsembleDecodeEngine:
     def search(self, ctx: EnsembleContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
                compiled: Optional["CompiledFsm"] = None, mach: Optional[torch.Tensor] = None, skip_dead: bool = False,
-               early_stop: bool = True, attention: bool = False):
+               early_stop: bool = True, attention: bool = False, guide=None):
         """DecodeEngine.search over the ensemble: the same arguments (ctx from this engine's prepare), the same return value."""
+        if guide is not None:
+            _guide_unsupported("an ensemble (EnsembleDecodeEngine)")
         if attention:
             raise NotImplementedError("attention traces of an ensemble are not implemented (ensemble decoding runs the beam search only)")
         if len(ctx.ctxs) != len(self.members):

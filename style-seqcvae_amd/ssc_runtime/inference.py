@@ -26,7 +26,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
-                   rules=None, attention: Optional[str] = None):
+                   rules=None, attention: Optional[str] = None, guide=None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -62,7 +62,22 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     attention: None, "summary" or "full" - with it the call additionally returns, as its last value, the AttentionTrace
     (ssc_runtime.decode) of exactly the captions it returns, whatever the decoder: top_region / top_weight / entropy (nimg,
     n_samples, steps) - with return_groups (nimg, n_samples, groups, steps) - and, under "full", maps (..., steps, R).  Words after
-    a caption's first END read nothing: region -1, zeros.  The captions, log-probs and the random state consumed do not change."""
+    a caption's first END read nothing: region -1, zeros.  The captions, log-probs and the random state consumed do not change.
+    guide: a LatentGuide (ssc_runtime.guide) over the nimg * n_samples entries (image, sample), or None - the latents are then
+    drawn around the guide's path instead of the prior, for the beam search (with or without fsm) and for word sampling; every
+    other decoder and an ensemble raise NotImplementedError naming the feature."""
+    if guide is not None:
+        from .guide import guide_unsupported
+        if isinstance(dec, EnsembleDecodeEngine):
+            guide_unsupported("an ensemble (EnsembleDecodeEngine)")
+        if rules is not None and rules.active:
+            guide_unsupported("the beam search under decode rules (rules)")
+        if diverse_beam is not None:
+            guide_unsupported("the diverse beam search (diverse_beam)")
+        if sampled_beam:
+            guide_unsupported("the sampled-node beam search (sampled_beam)")
+        if sampler is not None and sampler.beam_search:
+            guide_unsupported("the stochastic beam search (GumbelSampler)")
     if attention not in (None, "summary", "full"):
         raise ValueError(f'attention must be None, "summary" or "full", got {attention!r}')
     want_attn = attention is not None
@@ -123,6 +138,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     S = 1 if trivial else fsm.size(1)
     G = B * S * beam
 
+    gkw = {"guide": guide} if guide is not None else {}   # (an unguided call is made exactly as before)
+
     def search(skip_now):
         # the noise of ALL steps is drawn up front - from the caller's list, or from a generator of this call's own seeded by ONE draw
         # of the global generator: the search may stop early (or, polled late, a few steps after it could have), and what the
@@ -162,12 +179,13 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
             return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if sampler is not None:
             pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
-                                         seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn)
+                                         seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn,
+                                         **gkw)
             calls["k"] = pred.size(-1)
             return pred.view(B, 1, 1, -1), lps.view(B, 1, 1), rec
         beams, lps, *rec = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
                                       fsm=None if trivial else fsm.contiguous(), compiled=compiled, mach=mach, skip_dead=skip_now,
-                                      early_stop=early_stop, attention=want_attn)
+                                      early_stop=early_stop, attention=want_attn, **gkw)
         calls["k"] = beams.size(-1)   # one step call per column (cbs.py:127,170)
         return beams, lps, rec
 

@@ -181,6 +181,10 @@ class ScoreDesc(C.Structure):
                 ("attn", C.POINTER(AttnRecord))]
 
 
+class LatentGuideDesc(C.Structure):
+    _fields_ = [("steps", C.c_int), ("mean", vp), ("var", vp), ("ld", C.c_int), ("len", vp)]
+
+
 class PosteriorRowsDesc(C.Structure):
     _fields_ = [("T", C.c_int), ("B", C.c_int), ("Z", C.c_int), ("mu", vp), ("lv", vp), ("z", vp), ("ldz", C.c_int), ("eps", vp),
                 ("ldeps", C.c_int), ("w", vp), ("pm", vp), ("ldpm", C.c_int), ("kld_mode", C.c_int), ("sent", vp),
@@ -349,6 +353,14 @@ SYMBOLS = {
     "ssc_score_rows": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_score_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(ScoreDesc)]),
     "ssc_decode_score": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), vp, _sz, vp]),
+    "ssc_latent_guide_rows": (_i, [C.POINTER(LatentGuideDesc), _i, _i, _i, _i, vp, _i, vp, _f, _f, vp, _i, vp]),
+    "ssc_decode_search_guided": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(LatentGuideDesc), vp, _sz,
+                                      vp]),
+    "ssc_decode_sample_guided": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                      C.POINTER(LatentGuideDesc), vp, _sz, vp]),
+    "ssc_decode_score_guided": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), C.POINTER(LatentGuideDesc), vp, _sz,
+                                     vp]),
+    "ssc_caption_match": (_i, [vp, _i, vp, _i, _i, _i, vp, vp]),
     "ssc_posterior_rows": (_i, [C.POINTER(PosteriorRowsDesc), vp]),
     "ssc_train_posterior": (_i, [C.POINTER(ModelCfg), C.POINTER(Batch), vp, _sz, vp, vp, vp, vp, _i, vp, vp, vp]),
     "ssc_train_posterior_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),

@@ -184,6 +184,7 @@ class UpDownCaptioner(nn.Module):
         self._ctx_cache = None
         self.n_z_samples = 1           # latent samples per caption of score_captions (from_config: MODEL.N_Z_SAMPLES)
         self._decode_attention = None  # decode_attention(): "summary" / "full" attention traces in the eval forward's output
+        self._decode_guide = None      # decode_guide(): a LatentGuide the NEXT eval forwards draw their latents around
 
     # ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -357,6 +358,14 @@ class UpDownCaptioner(nn.Module):
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
         obj_means = self._obj_means(obj_atts, batch_size, num_boxes)   # (updown_captioner.py:246-247)
         step = functools.partial(self._decode_step, image_features, obj_means, sentiment=sentiment)
+        if self._decode_guide is not None:
+            from ssc_runtime.guide import guide_unsupported
+            if self.sampler is not None and (self.sampler.beam_search or self.sampled_beam):
+                guide_unsupported("the stochastic and the sampled-node beam search (MODEL.DECODE_SAMPLER with a beam)")
+            if self.diverse_beam is not None:
+                guide_unsupported("the diverse beam search (MODEL.DIVERSE_BEAM_SEARCH)")
+            if self.decode_rules is not None:
+                guide_unsupported("the beam search under decode rules")
         if self.sampler is not None:
             if self._use_cbs and fsm is not None:
                 raise ValueError(f"MODEL.USE_CBS with a constraint machine cannot be combined with MODEL.DECODE_SAMPLER "
@@ -374,7 +383,7 @@ class UpDownCaptioner(nn.Module):
                                  "(MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN)")
             with torch.no_grad():
                 return self._rules_beam_decode(image_features, obj_means, sentiment)
-        if self._decode_attention is not None:
+        if self._decode_attention is not None or self._decode_guide is not None:
             with torch.no_grad():
                 return self._traced_beam_decode(image_features, obj_means, sentiment, fsm if self._use_cbs else None,
                                                 num_constraints)
@@ -430,6 +439,37 @@ class UpDownCaptioner(nn.Module):
         else:
             raise ValueError(f'decode_attention: mode must be None, "none", "summary" or "full", got {mode!r}')
 
+    def decode_guide(self, guide):
+        """A latent guide for the NEXT eval forwards (ssc_runtime.guide.LatentGuide over the B images of the forward, one entry per
+        image; include/ssc.h: ssc_latent_guide): the latent of step t of image b is drawn around guide.mean[t, b] instead of the
+        prior - reconstruction, style transfer from an exemplar caption, interpolation.  None (the default state): off.  The plain
+        and the constrained beam search then run as one library call (DecodeEngine.search) with the noise of all steps drawn up
+        front, as under decode_attention (constraints need CBS_SIMPLE); word sampling takes the guide as well; every other decoder
+        raises NotImplementedError naming the feature.  The guide must match the batch of every forward it is set for."""
+        if guide is not None:
+            from ssc_runtime.guide import LatentGuide
+            if not isinstance(guide, LatentGuide):
+                raise ValueError(f"decode_guide: a ssc_runtime.guide.LatentGuide or None, got {type(guide).__name__}")
+            if guide.Z != self.z_space:
+                raise ValueError(f"decode_guide: the guide has Z = {guide.Z}, the model {self.z_space}")
+        self._decode_guide = guide
+
+    def reconstruct_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, beam: Optional[int] = None,
+                             eps=None, prior_samples: int = 4, prior_seed: Optional[int] = None):
+        """Reconstruction through z with the model as it stands: every caption (B, L) int64 in the training layout is encoded on its
+        own image by the posterior branch (eps (L + 1, B, Z): its noise; None: the mean path), decoded back by the beam search under
+        its own z path, compared with the given words (token accuracy, exact rate, word error rate) and scored teacher-forced
+        under the path and under prior_samples prior samples (0: not under the prior - the call then draws nothing).  No autograd; a backward() of an earlier training forward is not disturbed.
+        -> ssc_runtime.guide.Reconstruction.  Not for SENTIMENT_VAE = 2."""
+        from ssc_runtime.guide import reconstruct_captions
+        eng = self._engine()
+        B = image_features.size(0)
+        sent = sentiment.reshape(B) if sentiment is not None else None
+        with torch.no_grad():
+            return reconstruct_captions(eng, self._dec, image_features.to(eng.device, torch.float32), sent, caption_tokens,
+                                        int(beam or self._beam_search.beam_size), self._boundary_index, eps=eps,
+                                        prior_samples=prior_samples, pad_index=self._pad_index, prior_seed=prior_seed)
+
     def _traced(self, pred, rec, sel):
         """The eval forward's output dict: predictions and, with decode_attention set, the trace of captions `sel` (B,) of `rec`."""
         out = {"predictions": pred}
@@ -443,8 +483,8 @@ class UpDownCaptioner(nn.Module):
         return out
 
     def _traced_beam_decode(self, image_features, obj_means, sentiment, fsm, num_constraints):
-        """Eval forward of the plain / constrained beam search with decode_attention set: the search in one library call
-        (DecodeEngine.search), the noise drawn as the step-by-step path draws it (one (rows, Z) draw per step)."""
+        """Eval forward of the plain / constrained beam search with decode_attention or decode_guide set: the search in one library
+        call (DecodeEngine.search), the noise drawn as the step-by-step path draws it (one (rows, Z) draw per step)."""
         from ssc_runtime.decoding import select_best_state_simple_batched
         B = image_features.size(0)
         L = self._max_caption_length
@@ -454,18 +494,19 @@ class UpDownCaptioner(nn.Module):
         fsm_d = None
         if fsm is not None:
             if not self.cbs_simple:
-                raise ValueError("decode_attention with a constraint machine needs CBS_SIMPLE")
+                raise ValueError("decode_attention / decode_guide with a constraint machine needs CBS_SIMPLE")
             fsm_d = fsm.to(dev).to(torch.uint8).contiguous()
         S = 1 if fsm_d is None else fsm_d.size(1)
         eps0 = self._draw_eps(1, B, dev)[0]
         eps = self._draw_eps(L - 1, B * S * k, dev) if L > 1 else None
         sent = sentiment.reshape(B) if sentiment is not None else None
-        beams, lps, rec = self._dec.search(ctx, sent, 1, k, per or k, L, self._boundary_index, eps0, eps, fsm=fsm_d, attention=True)
+        beams, lps, *rec = self._dec.search(ctx, sent, 1, k, per or k, L, self._boundary_index, eps0, eps, fsm=fsm_d,
+                                            attention=self._decode_attention is not None, guide=self._decode_guide)
         state = torch.zeros(B, dtype=torch.long, device=dev)
         if fsm_d is not None and S > 1:
             state = select_best_state_simple_batched(lps, num_constraints, self._min_constraints_to_satisfy)
         rows = torch.arange(B, device=dev)
-        return self._traced(beams[rows, state, 0, :], [rec], (rows * S + state) * k)
+        return self._traced(beams[rows, state, 0, :], rec, (rows * S + state) * k)
 
     def score_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, obj_atts=None,
                        n_samples: Optional[int] = None, layout: str = "padded", want_tokens: bool = False, want_ranks: bool = False,
@@ -557,7 +598,7 @@ class UpDownCaptioner(nn.Module):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         sent = sentiment.reshape(B) if sentiment is not None else None
         pred, _, *rec = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed,
-                                         attention=self._decode_attention is not None)
+                                         attention=self._decode_attention is not None, guide=self._decode_guide)
         return self._traced(pred, rec, torch.arange(B, device=dev))
 
     def _diverse_beam_decode(self, image_features, obj_means, sentiment):
