@@ -531,27 +531,17 @@ int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* p, const ss
  * label_smoothing 0).  Returns pointer into the workspace (and its ld) or 0. */
 void* ssc_train_workspace_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
 
-/* The train step with a free-bits floor on the KL (see ssc_latent_fwd_fb): ssc_train_fwd / ssc_train_bwd / ssc_train_bwd_phases
- * with lambda = free_bits (nats) and free_bits_mode 1 element, 2 step, 3 dim as two arguments of the call.  (The layout of
- * ssc_model_cfg and the numbering of ssc_train_workspace_view are pinned, so the option travels beside the cfg and its buffers
- * have a view of their own.)  free_bits 0 = off whatever the mode: the calls are then ssc_train_fwd / ssc_train_bwd /
- * ssc_train_bwd_phases themselves - which are these with free_bits 0 -, the kernels of ssc_latent_fwd / ssc_latent_bwd run and
- * every output keeps its bits.  With free_bits > 0 kld is the floored KL and the backward (the latent backward sits in phase 32)
- * gates the KL gradient; a backward must be given the free_bits and free_bits_mode of its forward, as it must the cfg.  Mode 3
- * costs one launch after the time loop (ssc_latent_fb_finish), B is the rows of the call.
+/* The train step with a free-bits floor on the KL (see ssc_latent_fwd_fb): ssc_train_fwd_opts / ssc_train_bwd_opts (below) with
+ * lambda = opts->free_bits (nats) and opts->free_bits_mode 1 element, 2 step, 3 dim.  free_bits 0 = off whatever the mode: the
+ * kernels of ssc_latent_fwd / ssc_latent_bwd run and every output keeps its bits.  With free_bits > 0 kld is the floored KL and
+ * the backward (the latent backward sits in phase 32) gates the KL gradient.  Mode 3 costs one launch after the time loop
+ * (ssc_latent_fb_finish), B is the rows of the call.
  * SSC_EINVAL and no launch: what the plain calls refuse, free_bits negative, NaN or infinite, a mode outside 1..3 while
  * free_bits > 0.  The buffers are reserved at the end of the train workspace for any cfg and any option:
- * ssc_train_workspace_bytes does not depend on them.
+ * ssc_train_workspace_bytes does not depend on them; the numbering of ssc_train_workspace_view is pinned, so they have a view of
+ * their own.
  * ssc_train_free_bits_view: what a forward with free_bits > 0 left, which = 0: the raw KL (B), 1: K_j (Z; mode 3), 2: the step
  * gates (T,B; mode 2), 3: the dimension gates (Z; mode 3), gates as 1.0 / 0.0.  Returns pointer into the workspace (and its ld) or 0. */
-int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
-                     size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream);
-int ssc_train_bwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
-                     size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
-                     int free_bits_mode, void* stream);
-int ssc_train_bwd_phases_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
-                            size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
-                            float free_bits, int free_bits_mode, void* stream);
 void* ssc_train_free_bits_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
 
 /* ------------------------------------------------------------------------------------------------
@@ -931,33 +921,24 @@ typedef struct {
 int ssc_sched_mix_rows(const float* logits, int ld, int rows, int V, const int64_t* truth, const float* w_prev, const float* w_cur,
                        const float* table, int ldt, int E, int step, const ssc_sched_sampling* ss, int64_t* tok_out, float* fed_out,
                        float* emb_out, int ldo, void* stream);
-/* ssc_train_fwd_fb with scheduled sampling.  ss == NULL or ss->prob == 0: it IS ssc_train_fwd_fb - the same launches, the same bits.
+/* The train step with scheduled sampling: ssc_train_fwd_opts (below) with opts->sched.  sched == NULL or prob == 0: teacher
+ * forcing - the same launches, the same bits.
  * Otherwise, for t >= 1, inside the time loop and in this order: the vocabulary head on h_dec of step t-1 (tied: its projection /
  * tanh / emb^T chain), ssc_sched_mix_rows, the (B x E x 4H) block of emb_t W_ih^att[:, :E] for step t; after the loop only the last
  * step's head remains.  Step 0 and everything that does not depend on the fed word stay hoisted.  The fed ids and the fed mask
  * are kept in the workspace (ssc_train_sched_view 13 / 14), behind every other block; the workspace's embedding rows hold the
- * fed words' rows.  The backward of such a forward is ssc_train_bwd_ss / ssc_train_bwd_phases_ss with fed_inputs = 1 (and, as ever,
- * the cfg and the free-bits arguments of its forward).  Label smoothing, free bits and the caller's KL weight compose unchanged.
- * SSC_EINVAL and no launch: what ssc_train_fwd_fb refuses; with ss != NULL, prob outside [0, 1] or NaN and the sampler limits.
+ * fed words' rows.  The backward of such a forward (ssc_train_bwd_opts with the same opts) scatters the embedding gradient
+ * (phase 64) by the fed ids of the workspace (id 0 receives none), not by the ground-truth inputs tok[:-1]; nothing else differs,
+ * the workspace's embedding and gate rows already hold the fed words' values.  Label smoothing, free bits and the caller's KL
+ * weight compose unchanged.
+ * SSC_EINVAL and no launch, from the forward and the backward alike: what the plain calls refuse; with sched != NULL, prob
+ * outside [0, 1] or NaN and the sampler limits.
  * ssc_train_posterior, the scoring, decode and self-critical paths never sample. */
-int ssc_train_fwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
-                     float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_sched_sampling* ss, void* stream);
-/* read-back of what the last ssc_train_fwd_ss with prob > 0 left, numbered on from ssc_train_workspace_view (whose own numbering
+/* read-back of what the last forward with sched->prob > 0 left, numbered on from ssc_train_workspace_view (whose own numbering
  * is pinned at 0..12, so - as the free-bits buffers - these have a view of their own): which = 13: the fed ids (T,B) int64,
  * 14: 1.0 where such an id was the model's own word, else 0.0 (T,B) float; both undefined after any other forward.  Returns
  * pointer into the workspace (and its ld) or 0. */
 void* ssc_train_sched_view(const ssc_model_cfg* cfg, int B, int R, int L, void* workspace, int which, int* ld);
-/* ssc_train_bwd_fb / ssc_train_bwd_phases_fb told which inputs the forward fed (the layout of ssc_model_cfg is pinned, so this
- * travels beside the cfg as the free-bits option does).  fed_inputs 0: they ARE those calls - the embedding gradient (phase 64) is
- * scattered by the ground-truth inputs tok[:-1].  fed_inputs 1, after ssc_train_fwd_ss with prob > 0: it is scattered by the fed
- * ids of the workspace (id 0 receives none); nothing else differs, the workspace's embedding and gate rows already hold the fed
- * words' values.  SSC_EINVAL and no launch: what those calls refuse, fed_inputs outside {0, 1}. */
-int ssc_train_bwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
-                     const float* gl, const float* gk, const ssc_params* g, float free_bits, int free_bits_mode, int fed_inputs,
-                     void* stream);
-int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
-                            size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
-                            float free_bits, int free_bits_mode, int fed_inputs, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Knowledge distillation in the cross-entropy train step (Hinton et al. 2015; Kim & Rush 2016, word-level): the student's rows
@@ -980,8 +961,8 @@ int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_params* p, const
  * teacher mass gives +inf.  One workgroup per row; the forward reads each row from HBM once (a second scan finds it in L2), the
  * backward is one in-place stream; 16 bytes per lane when ldl % 4 == ldt % 4 == 0 and the two matrices share one misalignment,
  * else element by element; columns V .. ld-1 are never touched.  No atomics: two calls on the same inputs are bit-identical.
- * kd == NULL or alpha == 0: the calls ARE ssc_ce_fwd_smooth / ssc_ce_bwd_smooth (ssc_train_fwd_fb / ssc_train_bwd_fb /
- * ssc_train_bwd_phases_fb) - the same launches, the same bits, and no buffer of kd is read or written.
+ * kd == NULL or alpha == 0: the calls ARE ssc_ce_fwd_smooth / ssc_ce_bwd_smooth (in the train step: the cross-entropy as it is
+ * without opts->distill) - the same launches, the same bits, and no buffer of kd is read or written.
  * SSC_EINVAL and no launch, before anything touches memory: what the plain calls refuse; alpha outside [0, 1] or NaN; a
  * temperature <= 0, NaN or infinite; with alpha > 0 a NULL teacher or rows, ldt < V, or a teacher range that overlaps the logits
  * range.  SSC_EALIGN: a pointer that is no multiple of 4.
@@ -998,21 +979,33 @@ int ssc_ce_fwd_distill(const float* logits, int ldl, const int64_t* targets, con
                        int V, float eps, const ssc_distill* kd, float* lse, float* loss, float* nll, void* stream);
 int ssc_ce_bwd_distill(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, const float* lse,
                        const float* gl, int T, int B, int V, float eps, const ssc_distill* kd, void* stream);
-/* ssc_train_fwd_fb / ssc_train_bwd_fb / ssc_train_bwd_phases_fb with the descriptor beside the cfg (whose layout is pinned, as
- * the numbering of ssc_train_workspace_view is; the scratch is the caller's, so ssc_train_workspace_bytes does not change).
- * Only the two cross-entropy calls of the step change - the forward's after the vocabulary head, the backward's at the start of
- * phase 16; a backward must be given the kd of its forward, with `rows` as that forward left it.  Label smoothing, free bits and
- * the caller's KL weight compose unchanged.  Distillation does not compose with scheduled sampling (the student would be fed its
- * own words while the teacher was fed the ground truth): there is no entry that takes both.  The self-critical, posterior,
- * scoring and decode paths never distil. */
-int ssc_train_fwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
-                     float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_distill* kd, void* stream);
-int ssc_train_bwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
-                     const float* gl, const float* gk, const ssc_params* g, float free_bits, int free_bits_mode,
-                     const ssc_distill* kd, void* stream);
-int ssc_train_bwd_phases_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace,
-                            size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
-                            float free_bits, int free_bits_mode, const ssc_distill* kd, void* stream);
+/* The train step with distillation: ssc_train_fwd_opts / ssc_train_bwd_opts (below) with opts->distill; the scratch is the
+ * caller's, so ssc_train_workspace_bytes does not change.  Only the two cross-entropy calls of the step change - the forward's
+ * after the vocabulary head, the backward's at the start of phase 16; the backward reads `rows` as its forward left it.  Label
+ * smoothing, free bits and the caller's KL weight compose unchanged.  Distillation does not compose with scheduled sampling (the
+ * student would be fed its own words while the teacher was fed the ground truth): both on is SSC_EINVAL.  The self-critical,
+ * posterior, scoring and decode paths never distil. */
+
+/* ------------------------------------------------------------------------------------------------
+ * The options of one train step.  The layout of ssc_model_cfg is pinned, so an option travels beside the cfg, in this
+ * descriptor - free bits (ssc_latent_fwd_fb), scheduled sampling and distillation (above) today; the next option is a field here,
+ * never an entry of its own.  opts == NULL or every option off: the calls ARE ssc_train_fwd / ssc_train_bwd_phases - the same
+ * launches, the same bits (those are these with opts NULL, ssc_train_bwd with phases 15 besides).  One rule for the backward: it
+ * is given the cfg and the opts of its forward, with every buffer the opts point to as that forward left it.
+ * phases: the mask of ssc_train_bwd_phases; 15 is the whole backward; 0 or > 255 is SSC_EINVAL.
+ * SSC_EINVAL and no launch, from both entries: what the plain calls and each option's block refuse; sched on (prob > 0) together
+ * with distill on (alpha > 0).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  float free_bits; int free_bits_mode;   /* lambda in nats and 1 element | 2 step | 3 dim; free_bits 0 = off whatever the mode */
+  const ssc_sched_sampling* sched;       /* NULL or prob 0 = teacher forcing */
+  const ssc_distill* distill;            /* NULL or alpha 0 = off */
+} ssc_train_opts;
+int ssc_train_fwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                       float* loss, float* kld, const ssc_train_opts* opts, void* stream);
+int ssc_train_bwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                       const float* gl, const float* gk, const ssc_params* g, unsigned phases, const ssc_train_opts* opts,
+                       void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Scoring GIVEN captions under the model (teacher forcing): how likely is a caption that came from elsewhere - a ground-truth

@@ -1,7 +1,7 @@
 // Scheduled sampling of the cross-entropy train step (Bengio et al. 2015; include/ssc.h: ssc_sched_sampling): the kernel that
 // decides, per row of one time step, whether the attention LSTM is fed the ground-truth word or a word the model draws from its own
 // logits of the previous step, and gathers the embedding row of the word that is fed - one launch per step inside the time loop of
-// ssc_train_fwd_ss (sequence.hip).
+// ssc_train_fwd_opts (sequence.hip).
 //
 // One workgroup per row.  The decision is one Philox4x32-10 block of counter (0, step, row, 1): its last word keeps the stream
 // apart from the word draws' (last word 0).  A row that fires draws with sample_draw_row (sample_draw.h) - the code of

@@ -40,11 +40,11 @@ struct Layout {
   size_t slabs, slab_floats, logits, lse, proj;   // lse: [lse | w*row(eps)]
   size_t nllw0, nll;   // the [w*row(0)] block of ssc_ce_fwd_smooth and the (B) unsmoothed loss: behind everything else, so that no other
                        // buffer's place depends on them
-  size_t kld_raw, fb_kdim, fb_gdim, fb_gstep, fb_acc;   // free bits (ssc_train_fwd_fb with free_bits > 0): the raw KL (B), K_j and the dimension gates (Z each),
+  size_t kld_raw, fb_kdim, fb_gdim, fb_gstep, fb_acc;   // free bits (ssc_train_fwd_opts with free_bits > 0): the raw KL (B), K_j and the dimension gates (Z each),
                                                         // the step gates (T*B), the (B, Zp) accumulator of mode 3.  Behind nll, reserved for any cfg
   size_t ident;   // int32, the layout of `live`: count B, rows 0 .. B-1 (the k-row list of a product over the B rows of a per-row sum).
                   // Behind every other block, so that no offset moves
-  size_t fed_ids, fed;   // scheduled sampling (ssc_train_fwd_ss with prob > 0): the ids the forward fed (T*B int64) and 1.0 where such an id was
+  size_t fed_ids, fed;   // scheduled sampling (ssc_train_fwd_opts with sched->prob > 0): the ids the forward fed (T*B int64) and 1.0 where such an id was
                          // the model's own word (T*B).  Behind the free-bits blocks, reserved for any cfg
   size_t sl_q, sl_mulv, sl_gh1, sl_ghd, sl_ghd2, sl_ghe, sl_dqw, sl_dhe, sl_dz, small_floats, wsum_att, wsum_dec, wz;
   size_t sl_ga, sl_ge, sl_gd, gate_floats;   // split-K slab regions of the three gate products (forward)
@@ -438,14 +438,28 @@ int check_cfg(const ssc_model_cfg* c, const ssc_params* p, const ssc_batch* b) {
   return SSC_OK;
 }
 
-// include/ssc_debug.h: hipEvent pair around the time loop of the last forward / backward call
-// the free-bits option of the _fb calls (include/ssc.h): lambda a finite number >= 0 and, while it is positive, a mode of 1..3
-int check_free_bits(float free_bits, int mode) {
-  if (!(free_bits >= 0.f) || !(free_bits <= 3.402823466e38f)) return SSC_EINVAL;   // negative, NaN, infinite
-  if (free_bits > 0.f && (mode < 1 || mode > 3)) return SSC_EINVAL;
+// The options of a train step (include/ssc.h: ssc_train_opts), checked against the cfg and resolved: the one place the forward and
+// its backward validate them, so a new option is a field of ssc_train_opts and a line here.  opts NULL = every option off.  Of
+// ssc_distill_check this is the first, memory-free stage; the overlap with the logits block is checked where the layout is known.
+struct TrainOpts {
+  ssc_train_opts o{};
+  bool fb_on = false, ss_on = false, kd_on = false;
+};
+int resolve_train_opts(const ssc_train_opts* opts, const ssc_model_cfg* cfg, TrainOpts* r) {
+  if (opts) r->o = *opts;
+  const ssc_train_opts& o = r->o;
+  // free bits: lambda a finite number >= 0 and, while it is positive, a mode of 1..3
+  if (!(o.free_bits >= 0.f) || !(o.free_bits <= 3.402823466e38f)) return SSC_EINVAL;   // negative, NaN, infinite
+  if (o.free_bits > 0.f && (o.free_bits_mode < 1 || o.free_bits_mode > 3)) return SSC_EINVAL;
+  SSC_TRY(ssc_distill_check(o.distill, nullptr, 0, 0, cfg->V, &r->kd_on));
+  if (o.sched && (!(o.sched->prob >= 0.f && o.sched->prob <= 1.f) || !sampler_ok(&o.sched->sampler, cfg->V))) return SSC_EINVAL;   // NaN included
+  r->fb_on = o.free_bits > 0.f;
+  r->ss_on = o.sched && o.sched->prob > 0.f;
+  if (r->ss_on && r->kd_on) return SSC_EINVAL;   // the student would be fed its own words while the teacher was fed the ground truth
   return SSC_OK;
 }
 
+// include/ssc_debug.h: hipEvent pair around the time loop of the last forward / backward call
 struct LoopProf {
   hipEvent_t e[4];
   bool created = false, on = false, fwd = false, bwd = false;
@@ -552,37 +566,30 @@ extern "C" void* ssc_train_sched_view(const ssc_model_cfg* cfg, int B, int R, in
   }
 }
 
-extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                             size_t workspace_bytes, float* loss, float* kld, void* stream) {
-  return ssc_train_fwd_fb(cfg, p, bt, workspace, workspace_bytes, loss, kld, 0.f, 0, stream);
-}
-
-// ss: scheduled sampling (include/ssc.h: ssc_train_fwd_ss); nullptr or prob 0 = teacher forcing, the launches as they are without it
-// kd: distillation (include/ssc.h: ssc_train_fwd_kd); nullptr or alpha 0 = the cross-entropy as it is without it.  Never both.
+// opts (include/ssc.h: ssc_train_opts): sched off = teacher forcing, distill off = the cross-entropy as it is without it, free
+// bits off = the plain latent head; each with the launches as they are without the option
 static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace, size_t workspace_bytes,
-                          float* loss, float* kld, float free_bits, int free_bits_mode, const ssc_sched_sampling* ss,
-                          const ssc_distill* kd, void* stream) {
+                          float* loss, float* kld, const ssc_train_opts* opts, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
-  SSC_TRY(check_free_bits(free_bits, free_bits_mode));
-  bool kd_on;
-  SSC_TRY(ssc_distill_check(kd, nullptr, 0, 0, cfg->V, &kd_on));
-  if (ss && (!(ss->prob >= 0.f && ss->prob <= 1.f) || !sampler_ok(&ss->sampler, cfg->V))) return SSC_EINVAL;   // NaN included
+  TrainOpts ro;
+  SSC_TRY(resolve_train_opts(opts, cfg, &ro));
+  const ssc_train_opts& o = ro.o;
+  const bool fb_on = ro.fb_on, ss_on = ro.ss_on;   // (fb_on: a free-bits floor on the KL, the _fb kernels of the latent head)
+  bool kd_on = ro.kd_on;
   if (!workspace || !loss || !kld) return SSC_EINVAL;
-  const bool ss_on = ss && ss->prob > 0.f;
   if (!ssc_aligned16(workspace)) return SSC_EALIGN;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
   // (the teacher's rows may not meet the logits block the backward overwrites: checked here, ahead of the first launch)
-  if (kd_on) SSC_TRY(ssc_distill_check(kd, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
+  if (kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
   const int TB = T * B;
   int64_t* tok = (int64_t*)(W + l.tok);
   const size_t sH = (size_t)B * l.Hp;  // per-step stride of the state histories
-  const bool fb_on = free_bits > 0.f;   // a free-bits floor on the KL: the _fb kernels of the latent head, else today's
 
   // ---- per-sequence precompute --------------------------------------------------------------
   int* act = (int*)(W + l.act);
@@ -607,7 +614,7 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     f.add(kld, (size_t)B);
     if (fb_on) {   // (free bits: the raw accumulator, and the per-dimension one of mode 3)
       f.add(W + l.kld_raw, (size_t)B);
-      if (free_bits_mode == 3) f.add(W + l.fb_acc, (size_t)B * l.Zp);
+      if (o.free_bits_mode == 3) f.add(W + l.fb_acc, (size_t)B * l.Zp);
     }
     if (l.Zp != Z) {  // keep pad columns of z finite (they are never read as K, but are memcpy'd in tests)
       f.add(W + l.z, (size_t)TB * l.Zp); f.add(W + l.mu, (size_t)TB * l.Zp); f.add(W + l.lv, (size_t)TB * l.Zp);
@@ -642,7 +649,7 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
       SSC_TRY(head_step(t - 1));
       float* emb_t = W + l.emb + (size_t)t * B * l.Ep;
       SSC_TRY(ssc_sched_mix_rows(W + l.logits + (size_t)(t - 1) * B * l.Vp, l.Vp, B, V, tok + (size_t)t * B, W + l.w + (size_t)(t - 1) * B,
-                                 W + l.w + (size_t)t * B, p->emb, p->ld_emb, E, t, ss, fed_ids + (size_t)t * B, W + l.fed + (size_t)t * B,
+                                 W + l.w + (size_t)t * B, p->emb, p->ld_emb, E, t, o.sched, fed_ids + (size_t)t * B, W + l.fed + (size_t)t * B,
                                  emb_t, l.Ep, st));
       SSC_TRY(gemm(c, true, true, {{emb_t, l.Ep, p->att_w_ih, p->ld_att_w_ih, E}}, B, H4, W + l.ga_static + (size_t)t * B * H4, H4));
     }
@@ -753,7 +760,7 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
       d.kld_acc = kld;
       if (fb_on) {
         ssc_free_bits fb{};
-        fb.lambda = free_bits; fb.mode = free_bits_mode;
+        fb.lambda = o.free_bits; fb.mode = o.free_bits_mode;
         fb.kld_raw = W + l.kld_raw; fb.gate_step = W + l.fb_gstep + (size_t)t * B;
         fb.dim_acc = W + l.fb_acc; fb.lddim = l.Zp;
         SSC_TRY(ssc_latent_fwd_fb(&d, &fb, st));
@@ -777,8 +784,8 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
   if (g_loop.on) { (void)hipEventRecord(g_loop.e[1], st); g_loop.fwd = true; }
   // free bits on the minibatch mean of each dimension: K_j, the Z gates and kld_b from the accumulator the steps filled
-  if (fb_on && free_bits_mode == 3)
-    SSC_TRY(ssc_latent_fb_finish(W + l.fb_acc, l.Zp, B, Z, free_bits, W + l.fb_kdim, W + l.fb_gdim, kld, st));
+  if (fb_on && o.free_bits_mode == 3)
+    SSC_TRY(ssc_latent_fb_finish(W + l.fb_acc, l.Zp, B, Z, o.free_bits, W + l.fb_kdim, W + l.fb_gdim, kld, st));
 
   // ---- vocabulary projection + CE over all steps (updown_captioner.py:444-445, 457-466) -----------
   const float* hd_all = W + l.hd + sH;  // rows t*B+b = h_dec after step t
@@ -795,28 +802,21 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   }
   // label_smoothing 0 launches the kernels of ssc_ce_fwd; the unsmoothed loss of this forward lands in l.nll either way
   if (kd_on)   // the soft targets of a teacher beside the (smoothed) hard loss: distill.hip
-    return ssc_ce_fwd_distill_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, kd, W + l.lse,
+    return ssc_ce_fwd_distill_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, o.distill, W + l.lse,
                                      W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
   SSC_TRY(ssc_ce_fwd_smooth_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, W + l.lse,
                                    W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st));
   return SSC_OK;
 }
 
-extern "C" int ssc_train_fwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, nullptr, nullptr, stream);
+extern "C" int ssc_train_fwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                  size_t workspace_bytes, float* loss, float* kld, const ssc_train_opts* opts, void* stream) {
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, opts, stream);
 }
 
-extern "C" int ssc_train_fwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode,
-                                const ssc_distill* kd, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, nullptr, kd, stream);
-}
-
-extern "C" int ssc_train_fwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, float* loss, float* kld, float free_bits, int free_bits_mode,
-                                const ssc_sched_sampling* ss, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, free_bits, free_bits_mode, ss, nullptr, stream);
+extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                             size_t workspace_bytes, float* loss, float* kld, void* stream) {
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, nullptr, stream);
 }
 
 // ---- posterior scoring of the forward that last ran in this workspace (include/ssc.h: ssc_train_posterior) ------------------------------
@@ -937,19 +937,21 @@ int ssc_g_dw_one_flush = ssc_env_int("SSC_DW_ONE_FLUSH", 1);
 // them lets the caller start the all-reduce of a finished gradient range while the next phase computes
 // (ssc_runtime/engine.py): the output head's 48 MB travel under the whole time loop.
 static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                          size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream,
-                          unsigned phases, float free_bits, int free_bits_mode, int fed_inputs = 0,
-                          const ssc_distill* kd = nullptr) {
+                          size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
+                          const ssc_train_opts* opts, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
-  SSC_TRY(check_free_bits(free_bits, free_bits_mode));
-  bool kd_on;
-  SSC_TRY(ssc_distill_check(kd, nullptr, 0, 0, cfg->V, &kd_on));
-  if (!workspace || !gl || !gk || !g || (fed_inputs != 0 && fed_inputs != 1)) return SSC_EINVAL;
+  TrainOpts ro;   // the opts of the forward: its gates (free bits), its fed ids (sched on), its teacher and row sums (distill)
+  SSC_TRY(resolve_train_opts(opts, cfg, &ro));
+  const ssc_train_opts& o = ro.o;
+  bool kd_on = ro.kd_on;
+  if (phases == 0 || phases > 255u) return SSC_EINVAL;
+  if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
+  if (!workspace || !gl || !gk || !g) return SSC_EINVAL;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
-  if (kd_on) SSC_TRY(ssc_distill_check(kd, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
+  if (kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -969,7 +971,7 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   if (phases & (1u | 16u)) {
   // ---- vocabulary head ------------------------------------------------------------------------------
   if (kd_on)   // (the forward of this minibatch left the rows' log-sum-exps in kd->rows)
-    SSC_TRY(ssc_ce_bwd_distill(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, kd, st));
+    SSC_TRY(ssc_ce_bwd_distill(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, o.distill, st));
   else
     SSC_TRY(ssc_ce_bwd_smooth(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, st));
   const float* dlog = W + l.logits;
@@ -1073,9 +1075,9 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
       if (l.D) { d.pm = W + l.pool + (size_t)t * B * l.Dp; d.ldpm = l.Dp; d.dpm = W + l.dpm; d.lddpm = l.Dp; }
       d.w = W + l.w + (size_t)t * B; d.gk = gk;
       d.dmulv = dmulv; d.lddmulv = 2 * Z;
-      if (free_bits > 0.f) {   // the gates of this forward (mode 1 forms them again from mu / lv)
+      if (ro.fb_on) {   // the gates of this forward (mode 1 forms them again from mu / lv)
         ssc_free_bits fb{};
-        fb.lambda = free_bits; fb.mode = free_bits_mode;
+        fb.lambda = o.free_bits; fb.mode = o.free_bits_mode;
         fb.gate_step = W + l.fb_gstep + (size_t)t * B; fb.gate_dim = W + l.fb_gdim;
         SSC_TRY(ssc_latent_bwd_fb(&d, &fb, st));
       } else {
@@ -1181,7 +1183,7 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
     if (hipMemset2DAsync(g->emb, (size_t)g->ld_emb * sizeof(float), 0, (size_t)E * sizeof(float), V, st) != hipSuccess)
       return SSC_EHIP;
     // (the rows are scattered by what the forward fed: the ground-truth inputs, or with scheduled sampling the fed ids)
-    SSC_TRY(ssc_embed_scatter_add(g->emb, g->ld_emb, fed_inputs ? (const int64_t*)(W + l.fed_ids) : tok, TB, E, W + l.demb, l.Ep,
+    SSC_TRY(ssc_embed_scatter_add(g->emb, g->ld_emb, ro.ss_on ? (const int64_t*)(W + l.fed_ids) : tok, TB, E, W + l.demb, l.Ep,
                                   cfg->pad, st));
   }
   }  // phase 2a
@@ -1321,53 +1323,19 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   return SSC_OK;
 }
 
-extern "C" int ssc_train_bwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                             size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, 0.f, 0);
+extern "C" int ssc_train_bwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                  size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
+                                  const ssc_train_opts* opts, void* stream) {
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, opts, stream);
 }
 
-extern "C" int ssc_train_bwd_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
-                                int free_bits_mode, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, free_bits, free_bits_mode);
+extern "C" int ssc_train_bwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                             size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream) {
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, 15u, nullptr, stream);
 }
 
 extern "C" int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                     size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
                                     unsigned phases, void* stream) {
-  return ssc_train_bwd_phases_fb(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, 0.f, 0, stream);
-}
-
-extern "C" int ssc_train_bwd_phases_fb(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                       size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
-                                       unsigned phases, float free_bits, int free_bits_mode, void* stream) {
-  return ssc_train_bwd_phases_ss(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, free_bits, free_bits_mode, 0, stream);
-}
-
-extern "C" int ssc_train_bwd_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
-                                int free_bits_mode, int fed_inputs, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, free_bits, free_bits_mode, fed_inputs);
-}
-
-extern "C" int ssc_train_bwd_phases_ss(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                       size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
-                                       unsigned phases, float free_bits, int free_bits_mode, int fed_inputs, void* stream) {
-  if (phases == 0 || phases > 255u) return SSC_EINVAL;
-  if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode, fed_inputs);
-}
-
-extern "C" int ssc_train_bwd_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, float free_bits,
-                                int free_bits_mode, const ssc_distill* kd, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, 15u | 64u | 128u, free_bits, free_bits_mode, 0, kd);
-}
-
-extern "C" int ssc_train_bwd_phases_kd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
-                                       size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
-                                       unsigned phases, float free_bits, int free_bits_mode, const ssc_distill* kd, void* stream) {
-  if (phases == 0 || phases > 255u) return SSC_EINVAL;
-  if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, stream, phases, free_bits, free_bits_mode, 0, kd);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, nullptr, stream);
 }

@@ -7,7 +7,7 @@ var_updown/scripts/train.py:154-176.
 """
 import ctypes as C
 from dataclasses import dataclass
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -185,7 +185,7 @@ def check_distill_sampling(alpha, ss_prob):
                          "in one forward: the teacher's rows are those of the ground-truth inputs")
 
 
-FREE_BITS_MODES = {"element": 1, "step": 2, "dim": 3}   # ssc_free_bits.mode / the free_bits_mode argument of ssc_train_fwd_fb
+FREE_BITS_MODES = {"element": 1, "step": 2, "dim": 3}   # ssc_free_bits.mode / ssc_train_opts.free_bits_mode
 
 
 def check_free_bits(x, mode="dim", name="free_bits") -> Tuple[float, int]:
@@ -200,6 +200,15 @@ def check_free_bits(x, mode="dim", name="free_bits") -> Tuple[float, int]:
     if mode not in FREE_BITS_MODES:
         raise ValueError(f"{name}_mode must be one of {' | '.join(FREE_BITS_MODES)}; found {mode!r}")
     return v, FREE_BITS_MODES[mode]
+
+
+class _FwdOpts(NamedTuple):
+    """The ssc_train_opts of one forward (c) and what it points into - the ssc_sched_sampling, the ssc_distill and the teacher's
+    scores tensor, each None where the option is off -, referenced until the last backward of that forward."""
+    c: _lib.TrainOpts
+    sched: Optional[_lib.SchedSampling]
+    distill: Optional[_lib.Distill]
+    scores: Optional[Distill]
 
 
 OPTIM_KINDS = ("sgd", "adam", "adamw")
@@ -389,11 +398,8 @@ class TrainEngine:
         self._cfg = dims.cfg()
         self._keep = None
         self._kld = None              # the kld tensor the last forward returned (kld_raw() without a floor)
-        self._fb = (0.0, 3)           # (free_bits, free_bits_mode) of the last forward: every backward of it is given the same
-        self._kd = None               # the ssc_distill of the last forward (None: it did not distil) - every backward of it is given the same
-        self._kd_keep = None          # (the scores tensor it points into)
+        self._opts = _FwdOpts(_lib.TrainOpts(), None, None, None)   # the options of the last forward: every backward of it is given the same
         self._kd_scratch = None       # 3*T*B + B floats: the descriptor's rows blocks and kd_b
-        self._fed = 0                 # 1: the last forward sampled its inputs (ss_prob > 0) - every backward of it scatters by the fed ids
         self._post_ws = None          # posterior_forward's own workspace: the training forward's activations are never overwritten
         self._post_ws_key = None
         self._post = None
@@ -484,34 +490,28 @@ class TrainEngine:
         ssc_free_bits) - kld is then the floored KL, a term at or below the floor has no gradient in the backward, kld_raw() is the
         KL without the floor.  0 = off: the kernels as they are without it.  "dim" floors the mean over the B rows of this call
         of each latent dimension (under data parallelism: this rank's rows).  Kept beside the cfg until the next forward likewise.
-        ss_prob / ss_sampler / ss_seed: scheduled sampling of THIS call (include/ssc.h: ssc_train_fwd_ss; check_sched_sampling) -
+        ss_prob / ss_sampler / ss_seed: scheduled sampling of THIS call (include/ssc.h: ssc_sched_sampling; check_sched_sampling) -
         with probability ss_prob an eligible position is fed the word the model draws from its own logits of the previous step.
-        0 = off: ssc_train_fwd_fb as before.  input_tokens() / fed_mask() read what was fed; the engine remembers, until the next
+        0 = off: teacher forcing as before.  input_tokens() / fed_mask() read what was fed; the engine remembers, until the next
         forward, that every backward of this forward scatters the embedding gradient by the fed ids.
         distill: the soft targets of THIS call (Distill; include/ssc.h: ssc_distill) - loss is then (1 - alpha) * the (smoothed)
         hard loss + alpha * tau^2 KL(teacher || student) per row, kd() the KL term alone, nll() unchanged.  None or alpha 0 = off:
-        ssc_train_fwd_fb as before.  Kept beside the cfg until the next forward, as the options above are.  Not together with
+        the cross-entropy as before.  Kept beside the cfg until the next forward, as the options above are.  Not together with
         ss_prob > 0 (ValueError)."""
         check_distill_sampling(distill.alpha if distill is not None else 0.0, ss_prob)
         self._cfg.label_smoothing = check_label_smoothing(label_smoothing)
-        self._fb = check_free_bits(free_bits, free_bits_mode)
+        fb = check_free_bits(free_bits, free_bits_mode)
         ss = check_sched_sampling(ss_prob, ss_sampler, ss_seed)
-        self._fed = int(ss is not None)
         bt, sent = self._batch(feats, caps, sentiment, eps, obj_atts)
-        self._kd, self._kd_keep = self._distill_desc(distill, (bt.L + 1) * bt.B, bt.B), distill
+        kd = self._distill_desc(distill, (bt.L + 1) * bt.B, bt.B)
+        self._opts = _FwdOpts(_lib.TrainOpts(*fb, C.pointer(ss) if ss is not None else None, C.pointer(kd) if kd is not None else None),
+                              ss, kd, distill)
         ws = self._workspace(bt.B, bt.R, bt.L)
         loss = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         kld = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         p = self.params.c_struct()
-        if self._kd is not None:
-            self.lib.ssc_train_fwd_kd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                                      _lib.ptr(kld), *self._fb, C.byref(self._kd), _lib.stream_ptr())
-        elif ss is None:
-            self.lib.ssc_train_fwd_fb(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                                      _lib.ptr(kld), *self._fb, _lib.stream_ptr())
-        else:
-            self.lib.ssc_train_fwd_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                                      _lib.ptr(kld), *self._fb, C.byref(ss), _lib.stream_ptr())
+        self.lib.ssc_train_fwd_opts(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                    _lib.ptr(kld), C.byref(self._opts.c), _lib.stream_ptr())
         self._keep = (bt, feats, caps, sent, eps)
         self._kld = kld
         self.fwd_version += 1
@@ -537,18 +537,14 @@ class TrainEngine:
         """(B,) kd_b of the last forward - n_b sum_t w tau^2 KL(teacher || student) / (n_b + 1e-13), not weighted by alpha -: a view of
         the engine's scratch, valid until the next distilled forward; zeros when the last forward did not distil."""
         B = self._keep[0].B
-        if self._kd is None:
+        if self._opts.distill is None:
             return torch.zeros(B, dtype=torch.float32, device=self.device)
         return self._kd_scratch[self._kd_scratch.numel() - B:]
 
     def _bwd_phases(self, p, bt, ws, gl, gk, g, mask):
-        """One ssc_train_bwd_phases call of the last forward, with the options that forward kept beside the cfg."""
-        if self._kd is not None:
-            self.lib.ssc_train_bwd_phases_kd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
-                                             _lib.ptr(gk), C.byref(g), mask, *self._fb, C.byref(self._kd), _lib.stream_ptr())
-        else:
-            self.lib.ssc_train_bwd_phases_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
-                                             _lib.ptr(gk), C.byref(g), mask, *self._fb, self._fed, _lib.stream_ptr())
+        """One ssc_train_bwd_opts call of the last forward (mask 15: its whole backward), with the cfg and the options of that forward."""
+        self.lib.ssc_train_bwd_opts(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                    _lib.ptr(gk), C.byref(g), mask, C.byref(self._opts.c), _lib.stream_ptr())
 
     def posterior_forward(self, feats, caps, sentiment, eps, obj_atts=None):
         """The posterior branch's view of given captions (include/ssc.h: ssc_train_posterior) -> (nll (B,), kld (B,), log_ratio (B,),
@@ -761,12 +757,7 @@ class TrainEngine:
         g = self.grads.c_struct(only=only)
         gl = gl.to(torch.float32).contiguous()
         gk = gk.to(torch.float32).contiguous()
-        if self._kd is not None:
-            self.lib.ssc_train_bwd_kd(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
-                                      _lib.ptr(gk), C.byref(g), *self._fb, C.byref(self._kd), _lib.stream_ptr())
-            return
-        self.lib.ssc_train_bwd_ss(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
-                                  _lib.ptr(gk), C.byref(g), *self._fb, self._fed, _lib.stream_ptr())
+        self._bwd_phases(p, bt, ws, gl, gk, g, 15)
 
     def nll(self):
         """(B,) unsmoothed loss_b of the last forward (= its loss when that ran with label_smoothing 0): a view of the workspace,
@@ -779,8 +770,9 @@ class TrainEngine:
         bt = self._keep[0]
         T, B = bt.L + 1, bt.B
         ws = self._workspace(bt.B, bt.R, bt.L)
-        view = self.lib.ssc_train_sched_view if self._fed else self.lib.ssc_train_workspace_view
-        p = view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), 13 if self._fed else 10, None)
+        fed = self._opts.sched is not None
+        view = self.lib.ssc_train_sched_view if fed else self.lib.ssc_train_workspace_view
+        p = view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), 13 if fed else 10, None)
         off = (p - ws.data_ptr()) // 4
         return ws[off:off + 2 * T * B].view(torch.int64).view(T, B)
 
@@ -788,7 +780,7 @@ class TrainEngine:
         """(T, B) bool: where the last forward fed the model's own word (all False without scheduled sampling)."""
         bt = self._keep[0]
         T, B = bt.L + 1, bt.B
-        if not self._fed:
+        if self._opts.sched is None:
             return torch.zeros(T, B, dtype=torch.bool, device=self.device)
         ws = self._workspace(bt.B, bt.R, bt.L)
         p = self.lib.ssc_train_sched_view(C.byref(self._cfg), bt.B, bt.R, bt.L, _lib.ptr(ws), 14, None)
@@ -798,7 +790,7 @@ class TrainEngine:
     def kld_raw(self):
         """(B,) KL of the last forward without the free-bits floor: a view of the workspace, valid until the next forward - or,
         when that forward ran with free_bits 0, the kld it returned."""
-        return self.free_bits_view("raw") if self._fb[0] > 0 else self._kld
+        return self.free_bits_view("raw") if self._opts.c.free_bits > 0 else self._kld
 
     def free_bits_view(self, which):
         """Of the last forward with free_bits > 0 (ssc_train_free_bits_view): "raw" (B,) the KL without the floor, "kdim" (Z,) the

@@ -174,6 +174,11 @@ class Distill(C.Structure):
     _fields_ = [("teacher", vp), ("ldt", C.c_int), ("alpha", C.c_float), ("temperature", C.c_float), ("rows", vp), ("kd", vp)]
 
 
+class TrainOpts(C.Structure):
+    _fields_ = [("free_bits", C.c_float), ("free_bits_mode", C.c_int), ("sched", C.POINTER(SchedSampling)),
+                ("distill", C.POINTER(Distill))]
+
+
 class ScoreDesc(C.Structure):
     _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_captions", C.c_int), ("n_samples", C.c_int), ("max_len", C.c_int),
                 ("end_index", C.c_int), ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("obj_atts", vp), ("targets", vp),
@@ -297,11 +302,10 @@ SYMBOLS = {
     "ssc_train_bwd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), vp]),
     "ssc_train_bwd_phases": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
                                   C.c_uint, vp]),
+    "ssc_train_fwd_opts": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(TrainOpts), vp]),
+    "ssc_train_bwd_opts": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
+                                C.c_uint, C.POINTER(TrainOpts), vp]),
     "ssc_train_workspace_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
-    "ssc_train_fwd_fb": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, _f, _i, vp]),
-    "ssc_train_bwd_fb": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), _f, _i, vp]),
-    "ssc_train_bwd_phases_fb": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
-                                     C.c_uint, _f, _i, vp]),
     "ssc_train_free_bits_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
     "ssc_xgmi_enable_peer": (_i, [_i]),
     "ssc_xgmi_ipc_export": (_i, [vp, vp, C.POINTER(C.c_size_t)]),
@@ -337,19 +341,9 @@ SYMBOLS = {
     "ssc_decode_sample_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc), vp, _sz, vp]),
     "ssc_sched_mix_rows": (_i, [vp, _i, _i, _i, vp, vp, vp, vp, _i, _i, _i, C.POINTER(SchedSampling), vp, vp, vp, _i, vp]),
-    "ssc_train_fwd_ss": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, _f, _i, C.POINTER(SchedSampling),
-                              vp]),
     "ssc_train_sched_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
-    "ssc_train_bwd_ss": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), _f, _i, _i, vp]),
-    "ssc_train_bwd_phases_ss": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
-                                     C.c_uint, _f, _i, _i, vp]),
     "ssc_ce_fwd_distill": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Distill), vp, vp, vp, vp]),
     "ssc_ce_bwd_distill": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Distill), vp]),
-    "ssc_train_fwd_kd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, _f, _i, C.POINTER(Distill), vp]),
-    "ssc_train_bwd_kd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params), _f, _i,
-                              C.POINTER(Distill), vp]),
-    "ssc_train_bwd_phases_kd": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
-                                     C.c_uint, _f, _i, C.POINTER(Distill), vp]),
     "ssc_score_rows": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_score_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(ScoreDesc)]),
     "ssc_decode_score": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), vp, _sz, vp]),

@@ -401,7 +401,7 @@ class UpDownCaptioner(nn.Module):
         return {"predictions": best}
 
     def scheduled_sampling(self, prob, seed=0, sampler=None):
-        """Scheduled sampling of the NEXT training forwards (the autograd path; include/ssc.h: ssc_train_fwd_ss): with probability
+        """Scheduled sampling of the NEXT training forwards (the autograd path; include/ssc.h: ssc_sched_sampling): with probability
         `prob` an eligible position is fed the word the model draws from its own logits of the previous step, the draws and the
         decisions seeded by `seed` (ssc_runtime.schedule.ss_seed for a resumable run: call this once per iteration).  sampler: None
         (multinomial, temperature 1), a word sampler of ssc_runtime.sampling, or (kind, top_k, top_p, temperature).  prob 0 (the

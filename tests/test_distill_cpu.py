@@ -114,7 +114,7 @@ def test_skipped_rows_are_never_read_by_the_reference():
 
 
 # ---- 2. the C ABI ----------------------------------------------------------------------------------------------------------------
-NEW = ("ssc_ce_fwd_distill", "ssc_ce_bwd_distill", "ssc_train_fwd_kd", "ssc_train_bwd_kd", "ssc_train_bwd_phases_kd")
+NEW = ("ssc_ce_fwd_distill", "ssc_ce_bwd_distill", "ssc_train_fwd_opts", "ssc_train_bwd_opts")
 
 
 def test_new_symbols_and_struct_mirror_the_header():
@@ -128,9 +128,8 @@ def test_new_symbols_and_struct_mirror_the_header():
         assert decl[:decl.index(");")].count(",") + 1 == len(L.SYMBOLS[name][1]), name
     assert len(L.SYMBOLS["ssc_ce_fwd_distill"][1]) == len(L.SYMBOLS["ssc_ce_fwd_smooth"][1]) + 1
     assert len(L.SYMBOLS["ssc_ce_bwd_distill"][1]) == len(L.SYMBOLS["ssc_ce_bwd_smooth"][1]) + 1
-    for a, b in (("ssc_train_fwd_kd", "ssc_train_fwd_fb"), ("ssc_train_bwd_kd", "ssc_train_bwd_fb"),
-                 ("ssc_train_bwd_phases_kd", "ssc_train_bwd_phases_fb")):
-        assert len(L.SYMBOLS[a][1]) == len(L.SYMBOLS[b][1]) + 1
+    # the descriptor travels as a field of ssc_train_opts (its layout: tests/test_free_bits_cpu.py), a pointer to this struct
+    assert dict(L.TrainOpts._fields_)["distill"] is C.POINTER(L.Distill) and L.TrainOpts.distill.offset == 16
     body = flat[:flat.index("} ssc_distill;")]
     body = body[body.rindex("typedef struct {"):]
     fields = re.findall(r"(?:const float\*|float\*|float|int)\s+(\w+);", body)
@@ -207,13 +206,13 @@ def test_train_entries_refuse_bad_distill_arguments():
         setattr(p, name, 4 if typ is C.c_int else a)
     bt = L.Batch(2, 3, 4, a, a, a, a, None)
     cfg = L.ModelCfg(10, 4, 4, 4, 4, 4, 0, 0, 0, 0.0, 1.0, 0, 1, 0)
-    ref = lambda kd: C.byref(kd) if kd is not None else None
+    ref = lambda kd, fb=0.0, mode=0: C.byref(L.TrainOpts(fb, mode, None, C.pointer(kd) if kd is not None else None))
     calls = {
-        "fwd": lambda kd, fb=0.0, mode=0: lib._raw_ssc_train_fwd_kd(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, fb, mode, ref(kd), None),
-        "bwd": lambda kd, fb=0.0, mode=0: lib._raw_ssc_train_bwd_kd(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), fb, mode,
-                                                                    ref(kd), None),
-        "phases": lambda kd, fb=0.0, mode=0: lib._raw_ssc_train_bwd_phases_kd(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p),
-                                                                              16, fb, mode, ref(kd), None),
+        "fwd": lambda kd, fb=0.0, mode=0: lib._raw_ssc_train_fwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, ref(kd, fb, mode), None),
+        "bwd": lambda kd, fb=0.0, mode=0: lib._raw_ssc_train_bwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), 15,
+                                                                      ref(kd, fb, mode), None),
+        "phases": lambda kd, fb=0.0, mode=0: lib._raw_ssc_train_bwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), 16,
+                                                                         ref(kd, fb, mode), None),
     }
     for name, call in calls.items():
         assert call(None) == -4 and call(_kd(a, a, ldt=10)) == -4 and call(_kd(None, None, alpha=0.0)) == -4, name
@@ -224,12 +223,12 @@ def test_train_entries_refuse_bad_distill_arguments():
             assert call(_kd(a, a, ldt=10, tau=tau)) == -1 and call(_kd(a, a, ldt=10, tau=tau, alpha=0.0)) == -1, (name, tau)
         assert call(_kd(None, a, ldt=10)) == -1 and call(_kd(a, None, ldt=10)) == -1 and call(_kd(a, a, ldt=9)) == -1, name
         assert call(_kd(a + 2, a, ldt=10)) == -2 and call(_kd(a, a + 1, ldt=10)) == -2, name
-        assert call(_kd(a, a, ldt=10), 0.1, 0) == -1 and call(_kd(a, a, ldt=10), 0.1, 3) == -4     # the free-bits checks are the _fb call's
+        assert call(_kd(a, a, ldt=10), 0.1, 0) == -1 and call(_kd(a, a, ldt=10), 0.1, 3) == -4     # the free-bits checks are the same helper's
     bad_cfg = L.ModelCfg(10, 4, 4, 4, 4, 4, 0, 0, 0, 0.0, 1.0, 0, 1, 0, 1.5)
-    assert lib._raw_ssc_train_fwd_kd(C.byref(bad_cfg), C.byref(p), C.byref(bt), a, 16, a, a, 0.0, 0, ref(_kd(a, a, ldt=10)), None) == -1
+    assert lib._raw_ssc_train_fwd_opts(C.byref(bad_cfg), C.byref(p), C.byref(bt), a, 16, a, a, ref(_kd(a, a, ldt=10)), None) == -1
     for phases in (0, 256):
-        assert lib._raw_ssc_train_bwd_phases_kd(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), phases, 0.0, 0,
-                                                ref(_kd(a, a, ldt=10)), None) == -1
+        assert lib._raw_ssc_train_bwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), phases,
+                                           ref(_kd(a, a, ldt=10)), None) == -1
 
 
 # ---- 3. the runtime --------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,7 @@
 float64 restatement (tests/distillref.py) computed from the same fp32 inputs, at row widths on every path of the kernels (scalar
 throughout, 16-byte bulk with and without a tail, misaligned first rows, a teacher matrix laid out as the student's and otherwise),
 with skipped rows full of NaN in both matrices, poisoned pad columns, teacher entries at -inf and a student row spread over +-80.
-Train step: ssc_train_fwd_kd / ssc_train_bwd_kd against the CPU oracle, whose per-step logits stay in the autograd graph and are
+Train step: ssc_train_fwd_opts / ssc_train_bwd_opts (the descriptor in ssc_train_opts) against the CPU oracle, whose per-step logits stay in the autograd graph and are
 turned into the distilled loss by distillref; the teachers are oracle parameter sets of other seeds run on the same noise.  Then the
 fused step, DistillTeacher, the module and scripts/train.py.
 Tolerances are the project's own (tests/test_train_gpu.py): loss and kd 1e-4 + 1e-5 max|ref|, gradients 1e-4 max(scale, 1e-3) + 2e-6."""

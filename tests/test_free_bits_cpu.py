@@ -1,6 +1,6 @@
 """CPU: KL annealing and free bits - the schedule (ssc_runtime/schedule.py), the OPTIM.KL_ANNEAL* / OPTIM.FREE_BITS* config keys, the
 float64 reference of the GPU tests (tests/freebitsref.py) against autograd and the oracle, and the C ABI of ssc_latent_fwd_fb /
-ssc_latent_bwd_fb / ssc_latent_fb_finish and the ssc_train_*_fb calls that carry the option beside the cfg: exported, mirrored in ctypes, and refusing bad
+ssc_latent_bwd_fb / ssc_latent_fb_finish and the ssc_train_*_opts calls that carry the option beside the cfg: exported, mirrored in ctypes, and refusing bad
 arguments before anything touches memory (no GPU here)."""
 import ctypes as C
 import os
@@ -105,7 +105,8 @@ def test_captioner_takes_the_values_and_the_engine_checks_them():
 # ---- ABI --------------------------------------------------------------------------------------------------------------------
 def test_structs_follow_the_header_and_the_option_travels_beside_the_cfg():
     """ssc_model_cfg keeps its layout (tests/test_label_smoothing_cpu.py pins its last field and the workspace views): the floor
-    is an argument pair of the ssc_train_*_fb calls and its buffers have a view of their own."""
+    is a field pair of ssc_train_opts, the one descriptor of ssc_train_fwd_opts / ssc_train_bwd_opts, and its buffers have a view
+    of their own."""
     text = open(os.path.join(ROOT, "include", "ssc.h")).read()
     body = text[text.index("typedef struct {\n  int V, E, H, A, F, Z;"):text.index("} ssc_model_cfg;")]
     names = [n.strip() for line in re.findall(r"(?:int|float)\s+([\w, ]+);", body) for n in line.split(",")]
@@ -125,11 +126,25 @@ def test_structs_follow_the_header_and_the_option_travels_beside_the_cfg():
     assert not lib.ssc_train_free_bits_view(C.byref(cfg), 2, 3, 4, C.addressof(buf), -1, C.byref(ld))
     assert not lib.ssc_train_free_bits_view(C.byref(cfg), 0, 3, 4, C.addressof(buf), 0, C.byref(ld))
     cdll = C.CDLL(L.LIB_PATH)
-    for name in ("ssc_latent_fwd_fb", "ssc_latent_bwd_fb", "ssc_latent_fb_finish", "ssc_train_fwd_fb", "ssc_train_bwd_fb",
-                 "ssc_train_bwd_phases_fb", "ssc_train_free_bits_view"):
+    for name in ("ssc_latent_fwd_fb", "ssc_latent_bwd_fb", "ssc_latent_fb_finish", "ssc_train_fwd_opts", "ssc_train_bwd_opts",
+                 "ssc_train_free_bits_view"):
         assert hasattr(cdll, name) and name in L.SYMBOLS
-    for name in ("ssc_train_fwd", "ssc_train_bwd", "ssc_train_bwd_phases"):      # the plain call + (float, int)
-        assert len(L.SYMBOLS[name + "_fb"][1]) == len(L.SYMBOLS[name][1]) + 2
+    # the descriptor: the header's fields in the header's order, 24 bytes; the two entries take what their SYMBOLS rows say
+    flat = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    body = flat[:flat.index("} ssc_train_opts;")]
+    body = body[body.rindex("typedef struct {"):]
+    names = re.findall(r"(?:float|int|const ssc_sched_sampling\*|const ssc_distill\*)\s+(\w+);", body)
+    assert names == [f for f, _ in L.TrainOpts._fields_] == ["free_bits", "free_bits_mode", "sched", "distill"]
+    assert C.sizeof(L.TrainOpts) == 24 and L.TrainOpts.sched.offset == 8 and L.TrainOpts.distill.offset == 16
+    for name in ("ssc_train_fwd_opts", "ssc_train_bwd_opts"):
+        decl = flat[flat.index("int " + name + "("):]
+        assert decl[:decl.index(");")].count(",") + 1 == len(L.SYMBOLS[name][1]), name
+    assert len(L.SYMBOLS["ssc_train_fwd_opts"][1]) == len(L.SYMBOLS["ssc_train_fwd"][1]) + 1          # the plain call + opts
+    assert len(L.SYMBOLS["ssc_train_bwd_opts"][1]) == len(L.SYMBOLS["ssc_train_bwd_phases"][1]) + 1
+    # the entries that carried one option each are gone: not declared, not exported, not bound
+    for name in ("ssc_train_fwd_fb", "ssc_train_fwd_ss", "ssc_train_fwd_kd", "ssc_train_bwd_fb", "ssc_train_bwd_ss", "ssc_train_bwd_kd",
+                 "ssc_train_bwd_phases_fb", "ssc_train_bwd_phases_ss", "ssc_train_bwd_phases_kd"):
+        assert name not in text and not hasattr(cdll, name) and name not in L.SYMBOLS, name
     assert lib.ssc_version() == 4
 
 
@@ -202,12 +217,11 @@ def test_train_forward_refuses_a_bad_floor():
     cfg = L.ModelCfg(10, 4, 4, 4, 4, 4, 0, 0, 0, 0.0, 1.0, 0, 1, 0)
 
     def fwd(free_bits, mode):
-        return lib._raw_ssc_train_fwd_fb(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, free_bits, mode, None)
+        return lib._raw_ssc_train_fwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(L.TrainOpts(free_bits, mode)), None)
 
-    def bwd(free_bits, mode, phases=None):
-        if phases is None:
-            return lib._raw_ssc_train_bwd_fb(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), free_bits, mode, None)
-        return lib._raw_ssc_train_bwd_phases_fb(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), phases, free_bits, mode, None)
+    def bwd(free_bits, mode, phases=15):
+        return lib._raw_ssc_train_bwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), phases,
+                                           C.byref(L.TrainOpts(free_bits, mode)), None)
 
     for call in (fwd, bwd, lambda x, m: bwd(x, m, 32)):
         assert call(0.0, 0) == -4 and call(0.0, 7) == -4                         # off: the mode is not read
@@ -217,7 +231,9 @@ def test_train_forward_refuses_a_bad_floor():
             assert call(0.1, mode) == -1
         for lam in (-0.1, float("nan"), float("inf")):
             assert call(lam, 3) == -1
-    # the plain entries are the same calls without a floor
+    # the plain entries are the same calls without a floor, as is a NULL descriptor
+    assert lib._raw_ssc_train_fwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, None, None) == -4
+    assert lib._raw_ssc_train_bwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), 15, None, None) == -4
     assert lib._raw_ssc_train_fwd(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, None) == -4
     assert lib._raw_ssc_train_bwd(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), None) == -4
 

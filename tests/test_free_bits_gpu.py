@@ -1,6 +1,6 @@
 """GPU: KL annealing and the free-bits floor of the train step.  Kernel level: ssc_latent_fwd_fb / ssc_latent_fb_finish /
 ssc_latent_bwd_fb against the float64 reference (tests/freebitsref.py) from the same fp32 inputs, at the shapes that cross every
-boundary of the two forward forms.  Train step: ssc_train_fwd_fb / ssc_train_bwd_fb against the CPU oracle, whose
+boundary of the two forward forms.  Train step: ssc_train_fwd_opts / ssc_train_bwd_opts (the floor in ssc_train_opts) against the CPU oracle, whose
 per-step mean / log_var / prior_mean stay in the autograd graph and become the floored KL through freebitsref; off and saturated
 floors, determinism, the phased backward, the module and its neighbours, scripts/train.py.
 

@@ -1,6 +1,6 @@
 """CPU: scheduled sampling - the restated forward (tests/schedsampref.py) against the oracle, the schedule and the seed
-(ssc_runtime/schedule.py), the OPTIM.SCHEDULED_SAMPLING_* config keys, and the C ABI of ssc_sched_mix_rows / ssc_train_fwd_ss /
-ssc_train_bwd_ss / ssc_train_bwd_phases_ss: exported, mirrored in ctypes, and refusing bad arguments before anything is launched
+(ssc_runtime/schedule.py), the OPTIM.SCHEDULED_SAMPLING_* config keys, and the C ABI of ssc_sched_mix_rows and of
+ssc_train_fwd_opts / ssc_train_bwd_opts with a `sched` descriptor: exported, mirrored in ctypes, and refusing bad arguments before anything is launched
 (no GPU here)."""
 import ctypes as C
 import os
@@ -174,16 +174,15 @@ def test_struct_layouts_and_bindings_mirror_the_header():
     assert C.sizeof(L.SchedSampling) == 8 + C.sizeof(L.SamplerDesc) and L.SchedSampling.sampler.offset == 8   # (the seed is 8-byte aligned)
     assert L.ModelCfg._fields_[-1] == ("label_smoothing", C.c_float)            # the cfg did not grow
     cdll = C.CDLL(L.LIB_PATH)
-    for name in ("ssc_sched_mix_rows", "ssc_train_fwd_ss", "ssc_train_bwd_ss", "ssc_train_bwd_phases_ss", "ssc_train_sched_view"):
+    for name in ("ssc_sched_mix_rows", "ssc_train_fwd_opts", "ssc_train_bwd_opts", "ssc_train_sched_view"):
         assert hasattr(cdll, name) and name in L.SYMBOLS
     flat = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    for name in ("ssc_sched_mix_rows", "ssc_train_fwd_ss", "ssc_train_bwd_ss", "ssc_train_bwd_phases_ss"):
+    for name in ("ssc_sched_mix_rows", "ssc_train_fwd_opts", "ssc_train_bwd_opts"):
         decl = flat[flat.index("int " + name + "("):]
         nargs = decl[:decl.index(");")].count(",") + 1
         assert nargs == len(L.SYMBOLS[name][1]), name
-    assert len(L.SYMBOLS["ssc_train_fwd_ss"][1]) == len(L.SYMBOLS["ssc_train_fwd_fb"][1]) + 1
-    assert len(L.SYMBOLS["ssc_train_bwd_ss"][1]) == len(L.SYMBOLS["ssc_train_bwd_fb"][1]) + 1
-    assert len(L.SYMBOLS["ssc_train_bwd_phases_ss"][1]) == len(L.SYMBOLS["ssc_train_bwd_phases_fb"][1]) + 1
+    # the descriptor travels as a field of ssc_train_opts (its layout: tests/test_free_bits_cpu.py), a pointer to this struct
+    assert dict(L.TrainOpts._fields_)["sched"] is C.POINTER(L.SchedSampling) and L.TrainOpts.sched.offset == 8
     lib = L.load()
     assert lib.ssc_version() == 4
     # the two new blocks sit behind every other one: views 13 / 14 of ssc_train_sched_view, offsets larger than any other view's
@@ -259,20 +258,35 @@ def test_train_entries_refuse_bad_sampling_arguments():
     bt = L.Batch(2, 3, 4, a, a, a, a, None)
     cfg = L.ModelCfg(10, 4, 4, 4, 4, 4, 0, 0, 0, 0.0, 1.0, 0, 1, 0)
 
-    def fwd(ss, free_bits=0.0, mode=0):
-        return lib._raw_ssc_train_fwd_ss(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, free_bits, mode,
-                                         C.byref(ss) if ss is not None else None, None)
+    def opts(ss, free_bits=0.0, mode=0, kd=None):
+        return C.byref(L.TrainOpts(free_bits, mode, C.pointer(ss) if ss is not None else None, C.pointer(kd) if kd is not None else None))
+
+    def fwd(ss, free_bits=0.0, mode=0, kd=None):
+        return lib._raw_ssc_train_fwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, opts(ss, free_bits, mode, kd), None)
+
+    def bwd(ss, phases=15, free_bits=0.0, mode=0, kd=None):
+        return lib._raw_ssc_train_bwd_opts(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), phases,
+                                           opts(ss, free_bits, mode, kd), None)
 
     assert fwd(None) == -4 and fwd(_ss(0.0)) == -4 and fwd(_ss(0.25)) == -4 and fwd(_ss(1.0)) == -4
     assert fwd(_ss(0.5, kind=1, top_k=1)) == -4 and fwd(_ss(0.5, kind=1, top_k=10)) == -4 and fwd(_ss(0.5, kind=2, top_p=0.9)) == -4
     for prob in (-0.1, 1.5, float("nan")):
         assert fwd(_ss(prob)) == -1
     assert fwd(_ss(0.5, kind=1, top_k=11)) == -1 and fwd(_ss(0.5, kind=3)) == -1 and fwd(_ss(0.5, temperature=0.0)) == -1
-    assert fwd(_ss(0.5), 0.1, 0) == -1 and fwd(_ss(0.5), 0.1, 3) == -4         # the free-bits checks are the _fb call's
-    bwd = lambda fed, phases=None: (
-        lib._raw_ssc_train_bwd_ss(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), 0.0, 0, fed, None) if phases is None else
-        lib._raw_ssc_train_bwd_phases_ss(C.byref(cfg), C.byref(p), C.byref(bt), a, 16, a, a, C.byref(p), phases, 0.0, 0, fed, None))
-    for phases in (None, 64, 2):
-        assert bwd(0, phases) == -4 and bwd(1, phases) == -4
-        assert bwd(2, phases) == -1 and bwd(-1, phases) == -1
-    assert bwd(1, 0) == -1 and bwd(1, 256) == -1
+    assert fwd(_ss(0.5), 0.1, 0) == -1 and fwd(_ss(0.5), 0.1, 3) == -4         # the free-bits checks are the same helper's
+    # the backward is given the opts of its forward ("the forward fed its own words" is sched->prob > 0) and refuses every
+    # descriptor the forward refuses, whatever the phases
+    for phases in (15, 64, 2):
+        assert bwd(None, phases) == -4 and bwd(_ss(0.0), phases) == -4 and bwd(_ss(0.5), phases) == -4 and bwd(_ss(1.0), phases) == -4
+        assert bwd(_ss(0.5, kind=1, top_k=10), phases) == -4 and bwd(_ss(0.5, kind=2, top_p=0.9), phases) == -4
+        for prob in (-0.1, 1.5, float("nan")):
+            assert bwd(_ss(prob), phases) == -1, prob
+        assert bwd(_ss(0.5, kind=3), phases) == -1 and bwd(_ss(0.5, kind=1, top_k=11), phases) == -1
+        assert bwd(_ss(0.5, temperature=0.0), phases) == -1
+        assert bwd(_ss(0.5), phases, 0.1, 0) == -1 and bwd(_ss(0.5), phases, 0.1, 3) == -4
+    assert bwd(_ss(0.5), 0) == -1 and bwd(_ss(0.5), 256) == -1
+    # scheduled sampling on together with distillation on: refused by both entries; either one off is in order
+    kd = lambda alpha: L.Distill(a, 10, alpha, 2.0, a, None)
+    for call in (fwd, bwd):
+        assert call(_ss(0.5), kd=kd(0.5)) == -1 and call(_ss(1.0), kd=kd(1.0)) == -1
+        assert call(_ss(0.0), kd=kd(0.5)) == -4 and call(_ss(0.5), kd=kd(0.0)) == -4 and call(None, kd=kd(0.5)) == -4

@@ -474,6 +474,78 @@ def test_phased_backward_equals_the_one_call_backward(masks):
     assert not bad, bad
 
 
+def test_opts_entries_are_the_plain_calls_when_off_and_compose_the_options():
+    """ssc_train_fwd_opts / ssc_train_bwd_opts (include/ssc.h: ssc_train_opts) through the ctypes table, on an engine's own
+    parameter, gradient and workspace buffers.  Options off - a NULL descriptor, a zeroed one, one whose every option is present
+    but off - is ssc_train_fwd / ssc_train_bwd BIT FOR BIT.  Options on together (label smoothing in the cfg, a free-bits floor
+    and distillation in the descriptor): the one-call backward (phases 15) and the phased one leave the same bits."""
+    import ctypes as C
+    from ssc_runtime import lib as L
+    lib = L.load()
+    cfg = oracle.OracleConfig(vocab_size=60, image_feature_size=36, embedding_size=20, hidden_size=28,
+                              attention_projection_size=12, z_space=8, max_caption_length=4, sentiment_vae=1,
+                              senti_prior_multip=0.5)
+    eng = engine_from(cfg, oracle.init_params(cfg, seed=23))
+    gen = torch.Generator().manual_seed(8)
+    B, R, Lc, V = 3, 5, 4, 60
+    T = Lc + 1
+    feats = dev(torch.randn(B, R, 36, generator=gen))
+    caps = torch.zeros(B, Lc, dtype=torch.long)
+    caps[0] = torch.randint(2, V, (Lc,), generator=gen)            # fills L
+    caps[1, :2] = torch.randint(2, V, (2,), generator=gen)         # a padded tail
+    caps[2, :3] = torch.randint(2, V, (3,), generator=gen)
+    caps = dev(caps)
+    senti = dev(torch.tensor([[1.0], [0.0], [-1.0]]))
+    eps = dev(torch.randn(T, B, 8, generator=gen))
+    gl = torch.full((B,), 1.0 / B, device="cuda")
+    gk = torch.full((B,), 1.0 / (B * 750.0), device="cuda")
+    bt, keep = eng._batch(feats, caps, senti, eps)
+    ws = eng._workspace(B, R, Lc)
+    p, g = eng.params.c_struct(), eng.grads.c_struct()
+    head = (C.byref(eng._cfg), C.byref(p), C.byref(bt), L.ptr(ws), ws.numel() * 4)
+
+    def run(fwd, bwds):
+        """One forward, then the backward as the given calls -> (loss, kld, every gradient)."""
+        loss, kld = torch.empty(B, device="cuda"), torch.empty(B, device="cuda")
+        fwd(L.ptr(loss), L.ptr(kld))
+        eng.grads.flat.fill_(float("nan"))
+        for bwd in bwds:
+            bwd()
+        torch.cuda.synchronize()
+        got = {n: v.clone() for n, v in eng.grads.views.items()}
+        assert torch.isfinite(loss).all() and torch.isfinite(kld).all() and all(torch.isfinite(v).all() for v in got.values())
+        return loss, kld, got
+
+    def via_opts(opts, masks=(15,)):
+        ref = C.byref(opts) if opts is not None else None
+        return run(lambda lo, kl: lib.ssc_train_fwd_opts(*head, lo, kl, ref, L.stream_ptr()),
+                   [lambda m=m: lib.ssc_train_bwd_opts(*head, L.ptr(gl), L.ptr(gk), C.byref(g), m, ref, L.stream_ptr()) for m in masks])
+
+    def same(a, b, what):
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]), what
+        bad = [n for n in a[2] if not torch.equal(a[2][n], b[2][n])]
+        assert not bad, (what, bad)
+
+    # ---- options off is the plain call
+    plain = run(lambda lo, kl: lib.ssc_train_fwd(*head, lo, kl, L.stream_ptr()),
+                [lambda: lib.ssc_train_bwd(*head, L.ptr(gl), L.ptr(gk), C.byref(g), L.stream_ptr())])
+    sched_off = L.SchedSampling(0.0, L.SamplerDesc(0, 0, 1.0, 1.0, 7))
+    distill_off = L.Distill(None, 0, 0.0, 1.0, None, None)
+    same(plain, via_opts(None), "opts NULL")
+    same(plain, via_opts(L.TrainOpts()), "opts zeroed")
+    same(plain, via_opts(L.TrainOpts(0.0, 3, C.pointer(sched_off), C.pointer(distill_off))), "every option present and off")
+
+    # ---- options compose through the one entry: smoothing + free bits + distillation, one call against the phases
+    eng._cfg.label_smoothing = 0.1
+    teacher = torch.randn(T * B, V, generator=gen).cuda()           # held outside the workspace
+    rows, kd_b = torch.zeros(3 * T * B, device="cuda"), torch.zeros(B, device="cuda")
+    distill = L.Distill(teacher.data_ptr(), V, 0.5, 2.0, rows.data_ptr(), kd_b.data_ptr())
+    opts = L.TrainOpts(0.05, 3, None, C.pointer(distill))
+    one = via_opts(opts)
+    assert not torch.equal(one[0], plain[0])                        # (the options did change the step)
+    same(one, via_opts(opts, (16, 32, 2, 4, 8)), "phases 16, 32, 2, 4, 8")
+
+
 @pytest.mark.parametrize("n,E", [(1344, 1000), (700, 37), (5, 300), (9000, 40)])
 def test_embedding_scatter_sums_each_token_in_position_order(n, E):
     """ssc_embed_scatter_add (the embedding gradient of the train step) is deterministic: a token's rows are summed in ascending
