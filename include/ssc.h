@@ -1324,6 +1324,66 @@ int ssc_decode_rules_beam(const ssc_model_cfg* cfg, const ssc_params* p, const s
                           float* scores, int* lengths, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Logit rules for the word samplers (ssc_sample_rows / ssc_decode_sample): a word bias, repetition / presence / frequency
+ * penalties, and bans - blocked n-grams, a minimum length, suppressed tokens.  The decode rules above ban a token AFTER the
+ * log-softmax and renormalise nothing: right for ranking beams, wrong for a sampler, which needs the edited distribution.  These
+ * rules edit the RAW logits of a row in place, in front of the draw; they are a second mechanism with names of their own and share
+ * only the two limits SSC_RULES_MAX_LEN / SSC_RULES_MAX_SUPPRESS with ssc_rules_desc.
+ * A live row r at step t has the history w_0 .. w_{t-1}: the tokens it emitted at steps 0 .. t - 1 (the BOUNDARY fed at step 0 is
+ * not counted).  Its logits x[0 .. V) are edited in this order, every arithmetic step one fp32 operation:
+ *   1. Bias:      x[v] = x[v] + bias[bias_row[r]][v] for every v < V.  An entry of -inf is a ban of any size.  +inf and NaN are
+ *                 the caller's error (the library cannot see device memory; the runtime refuses them on the host).
+ *   2. Penalties: for every distinct token c of the history, occurring n_c times:
+ *                   first x[c] = x[c] > 0 ? x[c] / theta : x[c] * theta           (repetition_penalty theta)
+ *                   then  x[c] = x[c] - (presence + frequency * (float)n_c)       (one multiplication, one addition, one subtraction)
+ *   3. Bans (x[v] = -inf): the suppress list; END while t < min_length; with n = no_repeat_ngram >= 1 every v such that the
+ *                 n-gram (w_{t-n+1}, .., w_{t-1}, v) already occurs in the history - the wording of ssc_rules_desc: n = 1 bans every
+ *                 used word, fewer than n - 1 tokens of history bans nothing, END is never banned by this rule.
+ * A row whose last token is END (t >= 1 and w_{t-1} == end_index) has ended: it is neither read nor written.  Columns V .. ld - 1
+ * are never touched; the bias matrix is never written.  A history id outside [0, V) is skipped: never indexed with (it still
+ * takes part in the n-gram comparison as a value).  ssc_sample_rows then draws from the edited row, unchanged: the log-prob it
+ * returns and sums is the untempered log-softmax of the EDITED row - of the distribution the word was drawn from
+ * (ssc_decode_score gives the model's own likelihood of the result).  A banned token has a perturbed score of -inf and is never
+ * drawn while one entry of the row is finite.  So that the rules alone cannot empty a row, V > t + n_suppress + 1 is required;
+ * emptying a row through the bias is the caller's responsibility.
+ * Two kernel forms, chosen on the host.  With a bias one workgroup per row streams the row once (16-byte accesses where both rows
+ * allow them, scalar ones otherwise; the sum does not depend on which), then makes the sparse edits.  Without a bias no thread
+ * walks the row: one wave per row touches at most t + n_suppress + 1 elements.  No atomics: two calls on equal inputs are
+ * bit-identical.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int no_repeat_ngram;        /* n: 0 = off, else 1..SSC_RULES_MAX_LEN */
+  int min_length;             /* m >= 0: END is banned at steps t < m */
+  int n_suppress; int suppress[SSC_RULES_MAX_SUPPRESS];   /* ids in [0, V), != end_index */
+  float repetition_penalty;   /* theta > 0, finite; 1 = off */
+  float presence_penalty;     /* finite; 0 = off */
+  float frequency_penalty;    /* finite; 0 = off */
+  const float* bias; int ld_bias; int n_bias;   /* (n_bias, V), ld_bias >= V; NULL = none */
+  const int* bias_row;        /* (rows): the bias row of each logits row; NULL = row 0 for all;
+                                 a value outside [0, n_bias) = no bias for that row (never indexed) */
+} ssc_logit_rules;
+/* The edit of `rows` rows of raw logits (rows, V) ld `ld` at step t.  Token j of row i is hist[j * ld_hist + i] - the
+ * (max_steps, B) block the sampled decode keeps; hist may be NULL at t = 0.  SSC_EINVAL before any launch: a NULL logits or r, a
+ * NULL hist at t >= 1, rows < 0, V < 1, ld < V, ld_hist < rows, t outside 0 .. SSC_RULES_MAX_LEN - 1, end_index outside [0, V),
+ * a field beyond its limits above, a suppressed id outside [0, V) or equal to end_index, a bias with ld_bias < V or n_bias < 1,
+ * V <= t + n_suppress + 1.  SSC_EALIGN: logits, hist, bias or bias_row no multiple of 4.  Every control off and no bias: SSC_OK
+ * with no launch. */
+int ssc_logit_rules_rows(float* logits, int ld, int rows, int V, const ssc_logit_rules* r, const int64_t* hist, int ld_hist, int t,
+                         int end_index, void* stream);
+/* ssc_decode_sample_guided with one ssc_logit_rules_rows launch between each step's decode step and its draw, step 0 included:
+ * the history is the call's own block of chosen words, so the workspace is that of ssc_decode_sample.  bias_row (B) is indexed by
+ * batch entry b = (image, sample).  rules NULL or inactive (every control off, no bias): the launches and the bits of
+ * ssc_decode_sample_guided, which is this call with rules = NULL.  Composes unchanged with a guide, an attention trace,
+ * skip_dead, early_stop and every numerics mode: only the contents of the logits block change.  d->log_probs sums the log-probs
+ * under the edited distributions.  SSC_EINVAL before any launch: what ssc_decode_sample_guided refuses; a field of `rules` beyond
+ * its limits (as above, with V = cfg->V); active rules with max_steps > SSC_RULES_MAX_LEN or V <= max_steps + n_suppress.
+ * SSC_EALIGN: bias or bias_row no multiple of 4. */
+size_t ssc_decode_sample_rules_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
+int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                            const ssc_logit_rules* rules, const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Diverse-caption evaluation (eval/eval.py:95-472 with the coco-caption scorers it calls): BLEU-1..4 (BleuScorer, option
  * "closest"), ROUGE-L (Rouge, beta 1.2) and CIDEr-D (CiderScorer, sigma 6) of every candidate; distinct 1- / 2-grams of every
  * image's N captions and of its top 5 by CIDEr (Div-n), and style-word counts.  The reductions over candidates (oracle argmax,

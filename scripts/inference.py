@@ -88,6 +88,11 @@ parser.add_argument("--exemplar-tensors", default="",
 parser.add_argument("--exemplar-jitter", type=float, default=None,
                     help="with --exemplar-tensors: sample AROUND the exemplar's path - standard deviation J times the posterior's "
                          "(default 0: every latent sample of an image decodes the path itself)")
+parser.add_argument("--word-bias", default="",
+                    help='logit bias for word sampling: a JSON file {word: bias} - the bias is added to that word\'s raw logit at every '
+                         'step of every image, in front of the draw ("-inf" bans the word; a word outside the vocabulary is an error). '
+                         "Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without SAMPLED_BEAM_SEARCH; composes with the "
+                         "MODEL.SAMPLER_* logit rules")
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -136,6 +141,47 @@ def check_exemplar_args(_A):
     return j
 
 
+def check_word_bias_args(_A, model_cfg=None):
+    """--word-bias, checked before anything is loaded; with model_cfg (the MODEL node) also that the run samples words."""
+    if not _A.word_bias:
+        return
+    if not os.path.isfile(_A.word_bias):
+        raise SystemExit(f"--word-bias: no such file {_A.word_bias!r}")
+    if _A.ensemble_checkpoints:
+        raise SystemExit("--word-bias is not available with --ensemble-checkpoints: an ensemble runs the beam search only")
+    if model_cfg is not None:
+        kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+        if kind not in sampling.KINDS or model_cfg.SAMPLED_BEAM_SEARCH or model_cfg.STOCHASTIC_BEAM_SEARCH:
+            raise SystemExit("--word-bias needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                             f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
+
+
+def load_word_bias(path, vocabulary):
+    """-> (V,) float32 bias row of a --word-bias file {word: bias}; "-inf" bans a word"""
+    try:
+        blob = json.load(open(path, encoding="utf-8"))
+    except ValueError as e:
+        raise SystemExit(f"--word-bias: {path!r} is not JSON ({e})")
+    if not isinstance(blob, dict) or not blob:
+        raise SystemExit('--word-bias: a non-empty JSON object {word: bias} wanted')
+    row = torch.zeros(vocabulary.get_vocab_size(), dtype=torch.float32)
+    boundary = vocabulary.get_token_index("@@BOUNDARY@@")
+    for word, value in blob.items():
+        idx = vocabulary.get_token_index(word)
+        if vocabulary.get_token_from_index(idx) != word:   # (an unknown word maps to @@UNKNOWN@@)
+            raise SystemExit(f"--word-bias: the word {word!r} is not in the vocabulary")
+        try:
+            v = float(value)
+        except (TypeError, ValueError):
+            raise SystemExit(f"--word-bias: the bias of {word!r} must be a number or \"-inf\", got {value!r}")
+        if isinstance(value, bool) or v != v or v == float("inf"):
+            raise SystemExit(f"--word-bias: the bias of {word!r} must be finite or \"-inf\", got {value!r}")
+        if idx == boundary and v == float("-inf"):
+            raise SystemExit("--word-bias: @@BOUNDARY@@ cannot be banned (no caption could end)")
+        row[idx] = v
+    return row
+
+
 def load_exemplars(path, max_len):
     """-> {image_id: caption row (L,) int64} of an --exemplar-tensors file"""
     blob = torch.load(path, map_location="cpu", weights_only=True)
@@ -153,7 +199,9 @@ def main():
     _A = parser.parse_args()
     ens_weights, ens_mode = check_ensemble_args(_A)
     jitter = check_exemplar_args(_A)
+    check_word_bias_args(_A)
     _C = Config(_A.config, _A.config_override)
+    check_word_bias_args(_A, _C.MODEL)
     random.seed(_C.RANDOM_SEED)
     np.random.seed(_C.RANDOM_SEED)
     torch.manual_seed(_C.RANDOM_SEED)
@@ -176,6 +224,14 @@ def main():
     diverse = sampling.diverse_beam_from_config(_C.MODEL)   # MODEL.DIVERSE_BEAM_SEARCH: groups of beams with a Hamming penalty
     # MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN: the beam search under decode rules
     rules = sampling.decode_rules_from_config(_C.MODEL, vocabulary)
+    # MODEL.SAMPLER_NO_REPEAT_NGRAM / SAMPLER_MIN_LENGTH / ... and --word-bias: the logit rules of the word-sampled decode
+    logit_rules = sampling.logit_rules_from_config(_C.MODEL, vocabulary)
+    if _A.word_bias:
+        kw = {} if logit_rules is None else dict(no_repeat_ngram=logit_rules.no_repeat_ngram, min_length=logit_rules.min_length,
+                                                 suppress=logit_rules.suppress, repetition_penalty=logit_rules.repetition_penalty,
+                                                 presence_penalty=logit_rules.presence_penalty,
+                                                 frequency_penalty=logit_rules.frequency_penalty)
+        logit_rules = sampling.LogitRules(bias=load_word_bias(_A.word_bias, vocabulary).to(device), **kw)
     model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, diverse_beam=diverse, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
@@ -305,7 +361,7 @@ def main():
                 out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode,
-                                     guide=guide)
+                                     guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}))
                 pred = out[0]
             trace = out[-1] if attn_mode else None
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the

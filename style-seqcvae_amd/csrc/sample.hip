@@ -191,9 +191,25 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
 extern "C" int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
                                         const ssc_sampler_desc* s, const ssc_latent_guide* guide, void* workspace,
                                         size_t workspace_bytes, void* stream) {
+  return ssc_decode_sample_rules(cfg, p, d, s, nullptr, guide, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t ssc_decode_sample_rules_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  return ssc_decode_sample_workspace_bytes(cfg, d);   // the history is the call's own block of chosen words
+}
+
+// rules (or null): the logit rules of include/ssc.h, one launch between each step's decode step and its draw
+extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                       const ssc_sampler_desc* s, const ssc_logit_rules* rules, const ssc_latent_guide* guide,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
   if (guide && !ssc_latent_guide_ok(cfg, guide)) return SSC_EINVAL;
+  bool ruled = false;
+  if (rules) {
+    SSC_TRY(ssc_logit_rules_check(rules, cfg->V, d->end_index, &ruled));
+    if (ruled && (d->max_steps > SSC_RULES_MAX_LEN || (long)cfg->V <= (long)d->max_steps + rules->n_suppress)) return SSC_EINVAL;
+  }
   const SampleLayout l = sample_layout(cfg, d);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
@@ -225,6 +241,7 @@ extern "C" int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_para
   sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), 0, B, d->R);
   SscStepGuide sg{guide, 0, 1};
   SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
+  if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, 0, d->end_index, st));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
   a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
   a.ctl = d->early_stop ? ctl : nullptr; a.max_steps = d->max_steps; a.host_flag = d->early_stop ? d->host_flag : nullptr;
@@ -243,6 +260,7 @@ extern "C" int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_para
     sd.row_lp = d->skip_dead ? lp : nullptr; sd.end_index = d->end_index;   // ended rows are not stepped
     sg.t = t;
     SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
+    if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, t, d->end_index, st));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
     SSC_TRY(sample_launch(a, B, st));
     cur = 1 - cur;

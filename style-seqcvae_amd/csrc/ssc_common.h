@@ -171,5 +171,11 @@ struct SscStepGuide {
 bool ssc_latent_guide_ok(const ssc_model_cfg* cfg, const ssc_latent_guide* g);
 int ssc_decode_step_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_decode_step_desc* d, const SscStepGuide* sg,
                            void* workspace, size_t workspace_bytes, void* stream);
+// Logit rules for the word samplers (logit_rules.hip, include/ssc.h: ssc_logit_rules).  ssc_logit_rules_check: the refusals that
+// depend on the fields and V alone (SSC_OK with *active = whether any control is on or a bias is set); ssc_logit_rules_launch: the
+// edit of one step from checked rules - what ssc_decode_sample_rules issues per step.
+int ssc_logit_rules_check(const ssc_logit_rules* r, int V, int end_index, bool* active);
+int ssc_logit_rules_launch(float* logits, int ld, int rows, int V, const ssc_logit_rules* r, const int64_t* hist, int ld_hist, int t,
+                           int end_index, hipStream_t st);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

@@ -94,6 +94,15 @@ def _defaults() -> dict:
             "LENGTH_PENALTY_ALPHA": 0.0,
             # SUPPRESS_UNKNOWN: @@UNKNOWN@@ is never emitted (its log-prob is not given to the other words)
             "SUPPRESS_UNKNOWN": False,
+            # logit rules of the word samplers (ssc_runtime/sampling.py LogitRules; ssc_logit_rules): the raw logits of every step
+            # are edited in front of the draw, so the sampler draws from the edited distribution.  A second mechanism, apart from
+            # the decode rules above.  Any non-default value needs DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and
+            # STOCHASTIC_BEAM_SEARCH False.  SAMPLER_NO_REPEAT_NGRAM n (0 = off, at most 64) and SAMPLER_MIN_LENGTH m as above;
+            # SAMPLER_SUPPRESS_UNKNOWN: @@UNKNOWN@@ is never drawn; SAMPLER_REPETITION_PENALTY theta > 0 (1 = off): the logit of a
+            # word the caption holds is divided by theta where positive, multiplied where not; SAMPLER_PRESENCE_PENALTY /
+            # SAMPLER_FREQUENCY_PENALTY (0 = off): presence + frequency * count is taken off such a logit
+            "SAMPLER_NO_REPEAT_NGRAM": 0, "SAMPLER_MIN_LENGTH": 0, "SAMPLER_SUPPRESS_UNKNOWN": False,
+            "SAMPLER_REPETITION_PENALTY": 1.0, "SAMPLER_PRESENCE_PENALTY": 0.0, "SAMPLER_FREQUENCY_PENALTY": 0.0,
             # attention traces of the eval decode (ssc_attn_record; DecodeEngine.attention): "none" (default), "summary" - per word
             # of every returned caption the region it attended most, the weight there and the entropy of its attention - or "full"
             # - the whole map over the regions as well.  Any decoder; the captions themselves do not change
@@ -217,6 +226,26 @@ class Config(object):
             if max_len > 64:
                 raise ValueError("the decode rules (MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / "
                                  f"SUPPRESS_UNKNOWN) need DATA.MAX_CAPTION_LENGTH <= 64; found {max_len}")
+        s_ngram, s_min = m.SAMPLER_NO_REPEAT_NGRAM, m.SAMPLER_MIN_LENGTH
+        if isinstance(s_ngram, bool) or not isinstance(s_ngram, int) or not 0 <= s_ngram <= 64:
+            raise ValueError(f"MODEL.SAMPLER_NO_REPEAT_NGRAM must be an integer in 0..64; found {s_ngram!r}")
+        if isinstance(s_min, bool) or not isinstance(s_min, int) or s_min < 0:
+            raise ValueError(f"MODEL.SAMPLER_MIN_LENGTH must be an integer and not negative; found {s_min!r}")
+        if not isinstance(m.SAMPLER_SUPPRESS_UNKNOWN, bool):
+            raise ValueError(f"MODEL.SAMPLER_SUPPRESS_UNKNOWN must be True or False; found {m.SAMPLER_SUPPRESS_UNKNOWN!r}")
+        for key in ("SAMPLER_REPETITION_PENALTY", "SAMPLER_PRESENCE_PENALTY", "SAMPLER_FREQUENCY_PENALTY"):
+            v = getattr(m, key)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or abs(v) == float("inf"):
+                raise ValueError(f"MODEL.{key} must be a finite number; found {v!r}")
+        if not m.SAMPLER_REPETITION_PENALTY > 0:
+            raise ValueError(f"MODEL.SAMPLER_REPETITION_PENALTY must be positive; found {m.SAMPLER_REPETITION_PENALTY!r}")
+        if (s_ngram or s_min or m.SAMPLER_SUPPRESS_UNKNOWN or m.SAMPLER_REPETITION_PENALTY != 1 or m.SAMPLER_PRESENCE_PENALTY != 0
+                or m.SAMPLER_FREQUENCY_PENALTY != 0):   # the sampled decode under logit rules is selected
+            max_len = self._C.DATA.MAX_CAPTION_LENGTH
+            if s_min >= max_len:
+                raise ValueError(f"MODEL.SAMPLER_MIN_LENGTH ({s_min}) must be below DATA.MAX_CAPTION_LENGTH ({max_len})")
+            if max_len > 64:
+                raise ValueError(f"the logit rules (MODEL.SAMPLER_NO_REPEAT_NGRAM ...) need DATA.MAX_CAPTION_LENGTH <= 64; found {max_len}")
         if m.DECODE_ATTENTION not in ("none", "summary", "full"):
             raise ValueError(f"MODEL.DECODE_ATTENTION must be one of none | summary | full; found {m.DECODE_ATTENTION!r}")
         o = self._C.OPTIM

@@ -352,22 +352,33 @@ class DecodeEngine:
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
-               attention: bool = False, guide=None):
+               attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
         -> (predictions (B, steps) int64, log_probs (B,): each caption's summed untempered log-prob).
-        guide: a LatentGuide over the B entries, or None (ssc_decode_sample_guided; see search)."""
+        guide: a LatentGuide over the B entries, or None (ssc_decode_sample_guided; see search).
+        logit_rules: a sampling.LogitRules, or None - every step's raw logits are edited in front of the draw
+        (ssc_decode_sample_rules: word bias, repetition / presence / frequency penalties, n-gram / length / token bans) and the
+        log-probs are those under the edited distributions; None or inactive rules take the entry point of a call without them.
+        skip_dead (default on): ended rows are not stepped; the captions do not depend on it."""
         sampler.check_vocab(self.dims.V)
         sdesc = sampler.desc(seed)
         call = lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), *ws)
+        gd = None
         if guide is not None:
             gd, _keep = self._guide_desc(guide, ctx.nimg * n_samples)
             call = lambda p, sd, ws: self.lib.ssc_decode_sample_guided(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
                                                                        C.byref(gd), *ws)
-        # skip_dead: ended rows are not stepped
-        return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, True,
-                              (ctx.nimg * n_samples,), self.lib.ssc_decode_sample_workspace_bytes, call, attention=attention)
+        workspace_bytes = self.lib.ssc_decode_sample_workspace_bytes
+        if logit_rules is not None and logit_rules.active:
+            logit_rules.check(self.dims.V, end_index, max_steps, ctx.nimg)
+            rd, _keep_rules = logit_rules.desc(n_samples)
+            call = lambda p, sd, ws: self.lib.ssc_decode_sample_rules(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
+                                                                      C.byref(rd), C.byref(gd) if gd is not None else None, *ws)
+            workspace_bytes = self.lib.ssc_decode_sample_rules_workspace_bytes
+        return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention)
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
               eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False,

@@ -26,7 +26,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
-                   rules=None, attention: Optional[str] = None, guide=None):
+                   rules=None, attention: Optional[str] = None, guide=None, logit_rules=None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -65,7 +65,19 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     a caption's first END read nothing: region -1, zeros.  The captions, log-probs and the random state consumed do not change.
     guide: a LatentGuide (ssc_runtime.guide) over the nimg * n_samples entries (image, sample), or None - the latents are then
     drawn around the guide's path instead of the prior, for the beam search (with or without fsm) and for word sampling; every
-    other decoder and an ensemble raise NotImplementedError naming the feature."""
+    other decoder and an ensemble raise NotImplementedError naming the feature.
+    logit_rules: a sampling.LogitRules - with a word sampler the raw logits of every step are edited in front of the draw
+    (DecodeEngine.sample(logit_rules=): word bias, repetition / presence / frequency penalties, n-gram / length / token bans);
+    ValueError with any other decoder, NotImplementedError with an ensemble.  None, or rules with every control off: the plain
+    sampled decode.  (`rules` stays the beam search's and keeps refusing a sampler.)"""
+    if logit_rules is not None and not logit_rules.active:
+        logit_rules = None
+    if logit_rules is not None:
+        if isinstance(dec, EnsembleDecodeEngine):
+            raise NotImplementedError("logit rules (logit_rules) are not implemented for an ensemble (EnsembleDecodeEngine)")
+        if sampler is None or sampler.beam_search or sampled_beam:
+            raise ValueError("the logit rules belong to the word samplers: logit_rules needs a multinomial / top-k / top-p sampler "
+                             "without sampled_beam (the beam search takes rules=)")
     if guide is not None:
         from .guide import guide_unsupported
         if isinstance(dec, EnsembleDecodeEngine):
@@ -139,6 +151,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     G = B * S * beam
 
     gkw = {"guide": guide} if guide is not None else {}   # (an unguided call is made exactly as before)
+    rkw = {"logit_rules": logit_rules} if logit_rules is not None else {}
 
     def search(skip_now):
         # the noise of ALL steps is drawn up front - from the caller's list, or from a generator of this call's own seeded by ONE draw
@@ -180,7 +193,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         if sampler is not None:
             pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn,
-                                         **gkw)
+                                         **gkw, **rkw)
             calls["k"] = pred.size(-1)
             return pred.view(B, 1, 1, -1), lps.view(B, 1, 1), rec
         beams, lps, *rec = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,

@@ -218,6 +218,12 @@ class RulesState(C.Structure):
     _fields_ = [("hist", vp), ("len", vp), ("hist_out", vp), ("len_out", vp), ("score_out", vp), ("ld_hist", C.c_int)]
 
 
+class LogitRules(C.Structure):
+    _fields_ = [("no_repeat_ngram", C.c_int), ("min_length", C.c_int), ("n_suppress", C.c_int),
+                ("suppress", C.c_int * SSC_RULES_MAX_SUPPRESS), ("repetition_penalty", C.c_float), ("presence_penalty", C.c_float),
+                ("frequency_penalty", C.c_float), ("bias", vp), ("ld_bias", C.c_int), ("n_bias", C.c_int), ("bias_row", vp)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -377,6 +383,10 @@ SYMBOLS = {
     "ssc_decode_rules_beam_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_rules_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(RulesDesc), vp, vp, vp,
                                    _sz, vp]),
+    "ssc_logit_rules_rows": (_i, [vp, _i, _i, _i, C.POINTER(LogitRules), vp, _i, _i, _i, vp]),
+    "ssc_decode_sample_rules_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
+    "ssc_decode_sample_rules": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                     C.POINTER(LogitRules), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
     "ssc_eval_refs_bytes": (_sz, [_i, _i, _i]),
     "ssc_eval_prepare_refs": (_i, [C.POINTER(EvalRefs), vp]),
     "ssc_eval_score_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc)]),

@@ -18,6 +18,11 @@ ssc_decode_diverse_beam, MODEL.DIVERSE_BEAM_SEARCH), the "Div-BS" baseline the s
 DecodeRules is no sampler either: the controls a best-1 caption is decoded under - blocking of repeated n-grams, a minimum length,
 suppressed tokens and a length penalty in the ranking (DecodeEngine.rules_beam / ssc_decode_rules_beam, MODEL.NO_REPEAT_NGRAM /
 MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN), for the deterministic beam search.
+
+LogitRules are the word samplers' own controls, a second and separate mechanism: the raw logits of every sampled step are edited in
+front of the draw - a word bias, repetition / presence / frequency penalties, blocked n-grams, a minimum length, suppressed tokens
+(DecodeEngine.sample(logit_rules=) / ssc_decode_sample_rules, MODEL.SAMPLER_NO_REPEAT_NGRAM and its kin) - so that the sampler
+draws from the edited distribution, where DecodeRules ban after the log-softmax and renormalise nothing.
 """
 import math
 
@@ -276,6 +281,132 @@ def decode_rules_from_config(model_cfg, vocabulary=None):
         raise ValueError(f"MODEL.NO_REPEAT_NGRAM / MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA: {e}") from None
 
 
+class LogitRules:
+    """The logit rules of the word samplers (ssc_logit_rules in include/ssc.h): the raw logits of every step are edited in front of
+    the draw - first `bias` is added, then the words the caption already holds are penalised (repetition_penalty theta: a positive
+    logit is divided by theta, any other multiplied; presence_penalty + frequency_penalty * count is then taken off), then tokens
+    are banned (no_repeat_ngram n, min_length, suppress: as DecodeRules words them).  The sampler draws from the edited
+    distribution and reports the log-prob under it.  bias: a float32 device tensor (V,), (1, V) - one row for all - or (nimg, V) -
+    one row per image; -inf bans a word, +inf and NaN are refused."""
+
+    def __init__(self, no_repeat_ngram: int = 0, min_length: int = 0, suppress=(), repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, bias=None) -> None:
+        if isinstance(no_repeat_ngram, bool) or int(no_repeat_ngram) != no_repeat_ngram or not 0 <= no_repeat_ngram <= _lib.SSC_RULES_MAX_LEN:
+            raise ValueError(f"no_repeat_ngram must be an integer in 0..{_lib.SSC_RULES_MAX_LEN}, got {no_repeat_ngram!r}")
+        if isinstance(min_length, bool) or int(min_length) != min_length or min_length < 0:
+            raise ValueError(f"min_length must be an integer and not negative, got {min_length!r}")
+        suppress = tuple(suppress)
+        if len(suppress) > _lib.SSC_RULES_MAX_SUPPRESS:
+            raise ValueError(f"at most {_lib.SSC_RULES_MAX_SUPPRESS} tokens can be suppressed, got {len(suppress)}")
+        if any(isinstance(v, bool) or int(v) != v or v < 0 for v in suppress) or len(set(suppress)) != len(suppress):
+            raise ValueError(f"suppress must hold distinct token ids, none negative, got {suppress!r}")
+        for name, v in (("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
+                        ("frequency_penalty", frequency_penalty)):
+            if isinstance(v, bool) or not math.isfinite(v) or abs(v) > float(np.finfo(np.float32).max):
+                raise ValueError(f"{name} must be a finite number, got {v!r}")
+        if not float(np.float32(repetition_penalty)) > 0:
+            raise ValueError(f"repetition_penalty must be positive, got {repetition_penalty!r}")
+        if bias is not None:
+            import torch
+            if not (isinstance(bias, torch.Tensor) and bias.dtype == torch.float32 and bias.dim() in (1, 2) and bias.numel() > 0):
+                raise ValueError("bias must be a float32 tensor of shape (V,), (1, V) or (nimg, V)")
+            bias = bias.reshape(1, -1) if bias.dim() == 1 else bias
+        self.no_repeat_ngram = int(no_repeat_ngram)
+        self.min_length = int(min_length)
+        self.suppress = tuple(int(v) for v in suppress)
+        self.repetition_penalty = float(repetition_penalty)
+        self.presence_penalty = float(presence_penalty)
+        self.frequency_penalty = float(frequency_penalty)
+        self.bias = bias
+
+    @property
+    def active(self) -> bool:
+        """False when every control is off and there is no bias: the decode is then the plain sampled decode."""
+        return bool(self.no_repeat_ngram or self.min_length or self.suppress or np.float32(self.repetition_penalty) != 1
+                    or np.float32(self.presence_penalty) != 0 or np.float32(self.frequency_penalty) != 0 or self.bias is not None)
+
+    def check(self, V: int, end_index: int, max_steps: int, nimg: int) -> None:
+        """The limits of ssc_decode_sample_rules for a call over nimg images, and the bias's contents (one read-back)."""
+        if not self.active:
+            return
+        if max_steps > _lib.SSC_RULES_MAX_LEN:
+            raise ValueError(f"the sampled decode under logit rules runs at most {_lib.SSC_RULES_MAX_LEN} steps, got {max_steps}")
+        for v in self.suppress:
+            if v >= V or v == end_index:
+                raise ValueError(f"a suppressed token must lie in [0, {V}) and must not be the boundary token {end_index}, got {v}")
+        if V <= max_steps + len(self.suppress):
+            raise ValueError(f"the logit rules need a vocabulary above max_steps + suppressed tokens = {max_steps + len(self.suppress)}"
+                             f", got {V} (the rules alone must not empty a row)")
+        if self.bias is not None:
+            b = self.bias
+            if not b.is_cuda:
+                raise ValueError("bias must be a device tensor")
+            if b.size(1) != V or b.size(0) not in (1, nimg):
+                raise ValueError(f"bias must have shape ({V},), (1, {V}) or ({nimg}, {V}), got {tuple(b.shape)}")
+            import torch
+            if bool((torch.isnan(b) | (b == float("inf"))).any()):
+                raise ValueError("bias holds NaN or +inf (-inf bans a word; +inf and NaN are refused)")
+
+    def desc(self, n_samples: int):
+        """-> (the C struct ssc_logit_rules for a call of n_samples entries per image, the tensors behind it: keep them until the
+        call is queued).  bias_row is the image index of every entry b = (image, sample); NULL with one shared row."""
+        d = _lib.LogitRules()
+        d.no_repeat_ngram, d.min_length, d.n_suppress = self.no_repeat_ngram, self.min_length, len(self.suppress)
+        for i, v in enumerate(self.suppress):
+            d.suppress[i] = v
+        d.repetition_penalty, d.presence_penalty, d.frequency_penalty = (self.repetition_penalty, self.presence_penalty,
+                                                                         self.frequency_penalty)
+        keep = []
+        if self.bias is not None:
+            import torch
+            b = self.bias.contiguous()
+            keep.append(b)
+            d.bias, d.ld_bias, d.n_bias = b.data_ptr(), b.size(1), b.size(0)
+            if b.size(0) > 1:
+                rows = torch.arange(b.size(0), dtype=torch.int32, device=b.device).repeat_interleave(int(n_samples)).contiguous()
+                keep.append(rows)
+                d.bias_row = rows.data_ptr()
+        return d, keep
+
+    def __repr__(self):
+        return (f"LogitRules(no_repeat_ngram={self.no_repeat_ngram}, min_length={self.min_length}, suppress={self.suppress}, "
+                f"repetition_penalty={self.repetition_penalty}, presence_penalty={self.presence_penalty}, "
+                f"frequency_penalty={self.frequency_penalty}, bias={None if self.bias is None else tuple(self.bias.shape)})")
+
+
+_LOGIT_RULE_KEYS = (("SAMPLER_NO_REPEAT_NGRAM", 0), ("SAMPLER_MIN_LENGTH", 0), ("SAMPLER_SUPPRESS_UNKNOWN", False),
+                    ("SAMPLER_REPETITION_PENALTY", 1.0), ("SAMPLER_PRESENCE_PENALTY", 0.0), ("SAMPLER_FREQUENCY_PENALTY", 0.0))
+
+
+def logit_rules_from_config(model_cfg, vocabulary=None):
+    """MODEL.SAMPLER_NO_REPEAT_NGRAM / SAMPLER_MIN_LENGTH / SAMPLER_SUPPRESS_UNKNOWN / SAMPLER_REPETITION_PENALTY /
+    SAMPLER_PRESENCE_PENALTY / SAMPLER_FREQUENCY_PENALTY -> LogitRules, or None when every key has its default (no new code path
+    runs then).  The rules belong to the word samplers: DECODE_SAMPLER multinomial / top-k / top-p, SAMPLED_BEAM_SEARCH and
+    STOCHASTIC_BEAM_SEARCH False.  vocabulary: where @@UNKNOWN@@ is looked up for SAMPLER_SUPPRESS_UNKNOWN (None: only the keys
+    are checked, and the id is left out)."""
+    vals = {k: getattr(model_cfg, k, dflt) for k, dflt in _LOGIT_RULE_KEYS}
+    set_keys = [k for k, dflt in _LOGIT_RULE_KEYS if vals[k] != dflt]
+    if not set_keys:
+        return None
+    key = "MODEL." + set_keys[0]
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if kind not in KINDS:
+        raise ValueError(f"{key} needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p', got {model_cfg.DECODE_SAMPLER!r} (the "
+                         "logit rules belong to the word samplers; the beam search has MODEL.NO_REPEAT_NGRAM and its kin)")
+    for other in ("SAMPLED_BEAM_SEARCH", "STOCHASTIC_BEAM_SEARCH"):
+        if bool(getattr(model_cfg, other, False)):
+            raise ValueError(f"{key} and MODEL.{other} exclude each other (the logit rules belong to the word-sampled decode)")
+    suppress = ()
+    if vals["SAMPLER_SUPPRESS_UNKNOWN"] and vocabulary is not None:
+        from .vocab import UNKNOWN
+        suppress = (int(vocabulary.get_token_index(UNKNOWN)),)
+    try:
+        return LogitRules(vals["SAMPLER_NO_REPEAT_NGRAM"], vals["SAMPLER_MIN_LENGTH"], suppress, vals["SAMPLER_REPETITION_PENALTY"],
+                          vals["SAMPLER_PRESENCE_PENALTY"], vals["SAMPLER_FREQUENCY_PENALTY"])
+    except ValueError as e:
+        raise ValueError(f"MODEL.SAMPLER_NO_REPEAT_NGRAM / SAMPLER_MIN_LENGTH / SAMPLER_*_PENALTY: {e}") from None
+
+
 def from_config(model_cfg):
     """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
     STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
@@ -288,6 +419,7 @@ def from_config(model_cfg):
     sampled_beam_from_config(model_cfg)
     diverse_beam_from_config(model_cfg)
     decode_rules_from_config(model_cfg)
+    logit_rules_from_config(model_cfg)
     if sbs and kind != "beam":
         raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
                          "samplers draw one word per row; the stochastic beam search is a kind of beam search)")

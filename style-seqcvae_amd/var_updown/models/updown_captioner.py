@@ -185,6 +185,7 @@ class UpDownCaptioner(nn.Module):
         self.n_z_samples = 1           # latent samples per caption of score_captions (from_config: MODEL.N_Z_SAMPLES)
         self._decode_attention = None  # decode_attention(): "summary" / "full" attention traces in the eval forward's output
         self._decode_guide = None      # decode_guide(): a LatentGuide the NEXT eval forwards draw their latents around
+        self._logit_rules = None       # logit_rules(): sampling.LogitRules the NEXT eval forwards of a word sampler draw under
 
     # ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -193,7 +194,9 @@ class UpDownCaptioner(nn.Module):
         the reference.  mean_choice=... (SENTIMENT_VAE = 2) is handed to the constructor.  MODEL.SAMPLED_BEAM_SEARCH is read only
         with a sampler=... (the decode's); a model built without one (scripts/train.py) ignores it, as it ignores the other
         decode keys; diverse_beam=... (sampling.diverse_beam_from_config) likewise comes from the caller.  The decode rules
-        (sampling.decode_rules_from_config) are read here; with their keys at the defaults there are none."""
+        (sampling.decode_rules_from_config) are read here; with their keys at the defaults there are none.  The logit rules of the
+        word samplers (MODEL.SAMPLER_NO_REPEAT_NGRAM and its kin, sampling.logit_rules_from_config) are read only with a word
+        sampler=... that is not run as a sampled-node beam search: a model built without one never reads them."""
         _C = config
         vocabulary = kwargs.pop("vocabulary")
         model = cls(vocabulary=vocabulary, image_feature_size=_C.MODEL.IMAGE_FEATURE_SIZE,
@@ -211,6 +214,8 @@ class UpDownCaptioner(nn.Module):
                     free_bits_mode=_C.OPTIM.FREE_BITS_MODE)
         model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
         model.decode_attention(_C.MODEL.DECODE_ATTENTION)
+        if model.sampler is not None and not model.sampler.beam_search and not model.sampled_beam:
+            model.logit_rules(sampling.logit_rules_from_config(_C.MODEL, vocabulary))
         return model
 
     def _initialize_glove(self):
@@ -454,6 +459,25 @@ class UpDownCaptioner(nn.Module):
                 raise ValueError(f"decode_guide: the guide has Z = {guide.Z}, the model {self.z_space}")
         self._decode_guide = guide
 
+    def logit_rules(self, rules):
+        """Logit rules for the NEXT eval forwards of a word sampler (ssc_runtime.sampling.LogitRules; include/ssc.h:
+        ssc_logit_rules): every step's raw logits are edited in front of the draw - a word bias (one row, or one per image of the
+        forward), repetition / presence / frequency penalties, blocked n-grams, a minimum length, suppressed tokens.  None (the
+        default state), or rules with every control off: off, the forward is what it is without.  ValueError without a word
+        sampler (the beam search has decode_rules).  Training forwards, scst_step, score_captions and every beam search never read
+        them."""
+        if rules is not None:
+            if not isinstance(rules, sampling.LogitRules):
+                raise ValueError(f"logit_rules: a ssc_runtime.sampling.LogitRules or None, got {type(rules).__name__}")
+            if self.sampler is None or self.sampler.beam_search or self.sampled_beam:
+                raise ValueError("logit_rules needs a word sampler (MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                                 "MODEL.SAMPLED_BEAM_SEARCH): the logit rules belong to the word-sampled decode")
+            rules.check(self._vocabulary.get_vocab_size(), self._boundary_index, self._max_caption_length,
+                        rules.bias.size(0) if rules.bias is not None else 1)
+            if not rules.active:
+                rules = None
+        self._logit_rules = rules
+
     def reconstruct_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, beam: Optional[int] = None,
                              eps=None, prior_samples: int = 4, prior_seed: Optional[int] = None):
         """Reconstruction through z with the model as it stands: every caption (B, L) int64 in the training layout is encoded on its
@@ -598,7 +622,8 @@ class UpDownCaptioner(nn.Module):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         sent = sentiment.reshape(B) if sentiment is not None else None
         pred, _, *rec = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed,
-                                         attention=self._decode_attention is not None, guide=self._decode_guide)
+                                         attention=self._decode_attention is not None, guide=self._decode_guide,
+                                         **({"logit_rules": self._logit_rules} if self._logit_rules is not None else {}))
         return self._traced(pred, rec, torch.arange(B, device=dev))
 
     def _diverse_beam_decode(self, image_features, obj_means, sentiment):

@@ -8,12 +8,17 @@ bytes / time against one HBM pass.
     python tools/sample_probe.py [calls]
     python tools/sample_probe.py diverse-beam [calls] [rounds]
     python tools/sample_probe.py rules-beam [calls] [rounds]
+    python tools/sample_probe.py word-rules [calls] [rounds]
 The diverse-beam leg alone: the time per call of ssc_decode_diverse_beam (k = 6 in 3 groups, per-node 1) next to ssc_decode_search
 (k = 6, per-node 3: the logits path) on the same inputs, in alternating rounds on the same device, and the two selections alone
 (ssc_beam_step_fsm, ssc_beam_step_diverse) on the same (G * 6, V) logits - their share of a step.
 The rules-beam leg alone, at C4's shapes (beam 5, per-node 2): the time per call of ssc_decode_search (at this size its later steps
 read per-tile records, not logits), of ssc_decode_rules_beam with every rule off and of ssc_decode_rules_beam with n = 3,
 alpha = 1, min_length = 5, suppress = [0] (both on the (G, V) logits), in alternating rounds on the same device and inputs.
+The word-rules leg alone, at C4's word-sampling call (2000 rows, top-p 0.9): the time per call of ssc_decode_sample, of the same call
+under logit rules without a bias (n = 3, min_length = 5, theta = 1.2, presence 0.2, frequency 0.1, suppress = [0]: the sparse
+kernel) and with a per-image bias as well (the streaming kernel), in alternating rounds on the same device and inputs; then the
+bias kernel alone on (2000, V) logits next to a device copy that moves the same bytes (3 x rows x V x 4: two reads, one write).
 Prints one JSON line."""
 import json
 import os
@@ -129,8 +134,52 @@ def rules_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, rounds):
     return out
 
 
+def word_rules_leg(dec, feats, senti, images, n_z, steps, c, calls, rounds):
+    """Alternating rounds of `calls` one-call sampled decodes each (top-p 0.9, early stop off, the same noise and seed): without
+    rules, under rules without a bias, under rules with a per-image bias; then the bias kernel alone against a copy."""
+    import ctypes as C
+    dev = feats.device
+    B, V = images * n_z, c["V"]
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1)
+    eps0 = torch.randn(B, c["Z"], device=dev, generator=gen)
+    eps = torch.randn(steps - 1, B, c["Z"], device=dev, generator=gen)
+    sent_b = senti.view(images, 1).expand(images, n_z).reshape(B).contiguous()
+    ctx = dec.prepare(feats)
+    smp = sampling.TopPSampler(p=0.9)
+    kw = dict(no_repeat_ngram=3, min_length=5, suppress=(0,), repetition_penalty=1.2, presence_penalty=0.2, frequency_penalty=0.1)
+    sparse = sampling.LogitRules(**kw)
+    biased = sampling.LogitRules(bias=torch.randn(images, V, device=dev, generator=gen), **kw)
+    run = lambda lr: (lambda: dec.sample(ctx, sent_b, n_z, steps, 1, eps0, eps, smp, 7, early_stop=False, logit_rules=lr))
+    runs = (("sample", run(None)), ("rules_no_bias", run(sparse)), ("rules_image_bias", run(biased)))
+    out = {"images": images, "n_z": n_z, "rows": B, "max_steps": steps, "V": V, "calls_per_round": calls,
+           "rounds_ms": {name: [] for name, _ in runs}}
+    for _ in range(rounds):
+        for name, fn in runs:
+            out["rounds_ms"][name].append(timed(fn, calls))
+    for name, _ in runs:
+        v = sorted(out["rounds_ms"][name])
+        out[name] = {"median_ms_per_call": v[len(v) // 2], "min": v[0], "max": v[-1]}
+    base = out["sample"]["median_ms_per_call"]
+    out["ratio_to_sample"] = {name: out[name]["median_ms_per_call"] / base for name in ("rules_no_bias", "rules_image_bias")}
+    # the bias kernel alone (step 0: no history) against a copy of the same bytes - x and the bias read, x written
+    lib = L.load()
+    logits = torch.randn(B, V, device=dev) * 3
+    full = torch.randn(B, V, device=dev)
+    rd, _keep = sampling.LogitRules(bias=full).desc(1)
+    rows = torch.arange(B, dtype=torch.int32, device=dev)
+    rd.bias_row = rows.data_ptr()
+    us = timed(lambda: lib.ssc_logit_rules_rows(L.ptr(logits), V, B, V, C.byref(rd), None, B, 0, 1, L.stream_ptr()), 50) * 1e3
+    dst = torch.empty(3 * B * V // 2, device=dev)
+    src = torch.randn(3 * B * V // 2, device=dev)
+    us_copy = timed(lambda: dst.copy_(src), 50) * 1e3
+    out["bias_kernel"] = {"rows": B, "V": V, "bytes": 3 * B * V * 4, "us": us, "GBps": 3 * B * V * 4 / us / 1e3,
+                          "copy_same_bytes_us": us_copy, "ratio_to_copy": us / us_copy}
+    return out
+
+
 def main():
-    leg = len(sys.argv) > 1 and sys.argv[1] in ("diverse-beam", "rules-beam") and sys.argv[1]
+    leg = len(sys.argv) > 1 and sys.argv[1] in ("diverse-beam", "rules-beam", "word-rules") and sys.argv[1]
     if leg:
         del sys.argv[1]
     calls = int(sys.argv[1]) if len(sys.argv) > 1 else 5
@@ -146,6 +195,9 @@ def main():
     images, n_z, steps = 100, 20, c["L"]
     feats = torch.randn(images, c["R"], c["F"], generator=g).to(dev)
     senti = torch.ones(images, device=dev)
+    if leg == "word-rules":
+        print(json.dumps(word_rules_leg(dec, feats, senti, images, n_z, steps, c, calls, int(sys.argv[2]) if len(sys.argv) > 2 else 3)))
+        return
     if leg == "rules-beam":
         print(json.dumps(rules_beam_leg(dec, feats, senti, images, n_z, steps, c, calls, int(sys.argv[2]) if len(sys.argv) > 2 else 3)))
         return
