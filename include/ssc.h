@@ -1507,6 +1507,53 @@ int ssc_eval_consensus(const ssc_eval_refs* refs, const ssc_eval_consensus_desc*
                        void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Diverse subset selection: from the N candidate captions of every image the k that are good AND different from each other,
+ * chosen from a similarity kernel K (ssc_eval_set_desc.kernel) and a per-candidate quality q (consensus scores, caption
+ * log-probs) with no test reference.  Everything is fp64; every argmax resolves ties to the lowest candidate index; every sum
+ * runs over j (or over the components of a vector) ascending.  K is read as a symmetric matrix: K_ij is taken from row j.
+ * q^ is the quality the rules use: q itself (normalize 0) or (q - min) / (max - min) over the image's eligible candidates
+ * (normalize 1; all equal: 0); with quality NULL q^ = 0.  n_e = the image's eligible candidates.
+ *   MBR (1)   s_i = (sum_{j != i, eligible} K_ij) / (n_e - 1), 0 with n_e = 1: the candidate closest to all others (minimum Bayes
+ *             risk under the kernel).  picks = the k eligible candidates of highest s_i, stable descending; gains = s_i.
+ *   MMR (2)   maximal marginal relevance: the first pick is argmax q^_i (gain lambda q^_i), each later one
+ *             argmax_{i not in S} lambda q^_i - (1 - lambda) max_{j in S} K_ij; gains = that objective.
+ *   DPP (3)   greedy MAP inference of the determinantal point process L_ij = r_i K_ij r_j, r_i = exp(theta q^_i) (Chen, Zhang &
+ *             Zhou, NeurIPS 2018).  d_i^2 = L_ii and an empty vector c_i per candidate; at each step j = argmax_{i not in S}
+ *             d_i^2; the rule stops when d_j^2 < min_gain or d_j^2 is not greater than 0; otherwise j is picked and for every
+ *             i not in S: e_i = (L_ji - <c_j, c_i>) / d_j, c_i gets e_i appended, d_i^2 -= e_i^2.  gains = d_j^2 at the pick
+ *             (= det L_{S + j} / det L_S): a duplicate of a picked caption (K_ij = K_jj, equal q) is left with gain 0 up to
+ *             rounding and a candidate with a zero diagonal is never picked by the rule.
+ *   fallback  the slots a rule left open (DPP after its stop) are filled with the remaining eligible candidates by q^, stable
+ *             descending (quality NULL: by index); their gain is reported as 0.  Slots beyond n_e hold -1 (gain 0).
+ * n_primary = the picks the rule itself made (MBR, MMR: min(k, n_e)).
+ * One wave per image; each lane owns candidates lane and lane + 64; (value, index) butterflies for the argmax; the DPP vectors
+ * lie component-major (k x N per image) in LDS for k <= 16 and in the workspace beyond, each lane touching only its own two
+ * columns.  No atomics: two calls on the same inputs are bit-identical, images with bit-equal inputs get bit-equal outputs.
+ * SSC_EINVAL before any launch: a NULL descriptor, P < 1, P * N > 2^24, N outside 1..128, k outside 1..N, a method outside
+ * 1..3, normalize outside {0, 1}, NULL picks, gains, n_primary or kernel, a NULL quality for MMR or for DPP with theta != 0,
+ * lambda outside [0, 1] or NaN, theta < 0 or not finite, min_gain < 0 or NaN (the three are checked whatever the method), a
+ * NULL workspace or one smaller than ssc_eval_select_workspace_bytes.  The call reads one device flag back (synchronises
+ * `stream`): a non-finite quality of an eligible candidate, a non-finite K_ij of two eligible candidates or a quality range
+ * max - min that overflows give SSC_EINVAL; that image's picks are all -1 (gains 0, n_primary 0), the other images' are valid.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int P, N, k;               /* 1 <= k <= N <= 128 */
+  int method;                /* 1 MBR | 2 MMR | 3 greedy DPP */
+  const double* kernel;      /* (P, N, N) similarity, as ssc_eval_set_desc.kernel leaves it (symmetric, entries in [0,1]) */
+  const double* quality;     /* (P, N) finite; may be NULL for MBR and for DPP with theta == 0 */
+  int normalize;             /* 1: per image q^ = (q - min) / (max - min), all equal -> 0; 0: q^ = q */
+  double lambda;             /* MMR trade-off in [0, 1] */
+  double theta;              /* DPP quality weight >= 0 */
+  double min_gain;           /* DPP: stop the primary rule when the best remaining gain is < min_gain (>= 0) */
+  const uint8_t* eligible;   /* optional (P, N): 0 = never pick this candidate (an empty caption, a filtered one) */
+  int* picks;                /* (P, k) candidate indices in pick order; -1 when fewer than k are eligible */
+  double* gains;             /* (P, k) the rule's value of each pick at the time it was picked (0 for fallback picks and -1 slots) */
+  int* n_primary;            /* (P) how many picks the rule itself made before the fallback filled up */
+} ssc_eval_select_desc;
+size_t ssc_eval_select_workspace_bytes(const ssc_eval_select_desc* d);   /* 0 for arguments out of range */
+int ssc_eval_select(const ssc_eval_select_desc* d, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Self-critical sequence training (Rennie et al. 2017; Luo 2020): the step between the sampled decode (ssc_decode_sample), the
  * per-caption reward (ssc_eval_score) and the train step (ssc_train_fwd / ssc_train_bwd).  P images x N samples, G = P * N rows,
  * row g = p * N + i.  The sampled captions become the train step's `caps`; row g's reward is r_g = sum_k reward_weights[k] *

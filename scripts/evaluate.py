@@ -3,7 +3,9 @@
 CIDEr-D over the N captions per image of a predictions JSON (what scripts/inference.py writes), Div-1 / Div-2 over all captions
 and over the top 5 by CIDEr, and style precision / recall against a wordforms TSV.  METEOR is not computed.  --set-diversity adds the caption-set numbers
 (each image's N captions against each other): mBLEU-1..4, Self-CIDEr and the share of distinct captions.  --consensus-bank adds best-1 after
-consensus re-ranking: every image's pick by mean CIDEr-D against the captions of its nearest bank images (features from --query-tensors)."""
+consensus re-ranking: every image's pick by mean CIDEr-D against the captions of its nearest bank images (features from --query-tensors).
+--select-k K keeps K captions per image that are good and different from each other (MBR / MMR / greedy DPP on the caption kernel with the
+bank's document frequencies, the consensus scores as quality: no test reference is involved) and reports that subset's own numbers."""
 import argparse
 import json
 import os
@@ -33,6 +35,17 @@ parser.add_argument("--query-tensors", default="",
                          "features of every prediction image")
 parser.add_argument("--consensus-k", type=int, default=60, help="nearest bank images per prediction image")
 parser.add_argument("--consensus-output", default="", help="write the consensus pick of every image here")
+parser.add_argument("--select-k", type=int, default=0,
+                    help="with --consensus-bank: keep K captions per image that are good and different from each other; adds the "
+                         "'select subset' lines")
+parser.add_argument("--select-method", default="dpp", choices=["dpp", "mmr", "mbr"],
+                    help="greedy DPP MAP (quality x diversity), maximal marginal relevance, or minimum Bayes risk under the caption kernel")
+parser.add_argument("--select-quality", default="consensus", choices=["consensus", "logprob"],
+                    help="the per-caption quality: the consensus scores (a predictions file holds no log-probs: logprob is "
+                         "scripts/inference.py's)")
+parser.add_argument("--select-lambda", type=float, default=0.5, help="mmr: weight of the quality against the similarity to a pick")
+parser.add_argument("--select-theta", type=float, default=1.0, help="dpp: weight of the quality")
+parser.add_argument("--select-output", default="", help="write the K captions per image here, in pick order (a predictions file)")
 
 
 def consensus_of(a, preds, device):
@@ -50,7 +63,7 @@ def consensus_of(a, preds, device):
     bank = ConsensusBank.load(a.consensus_bank, device=device)
     pooled = pool_rows(data, [row[iid] for iid in preds], device)
     # an image that is itself in the bank is not its own neighbour
-    return bank.rerank_captions(preds, pooled, k=a.consensus_k, exclude_ids=list(preds))
+    return bank, bank.rerank_captions(preds, pooled, k=a.consensus_k, exclude_ids=list(preds))
 
 
 def main():
@@ -62,11 +75,23 @@ def main():
     preds = load_predictions(a.predictions)
     if a.consensus_output and not a.consensus_bank:
         raise SystemExit("--consensus-output needs --consensus-bank")
-    cons = consensus_of(a, preds, device) if a.consensus_bank else None
+    if a.select_k < 0 or (a.select_output and not a.select_k):
+        raise SystemExit("--select-output needs --select-k K (K >= 1)")
+    if a.select_k and a.select_quality == "logprob":
+        raise SystemExit("--select-quality logprob: a predictions file holds no log-probs (scripts/inference.py --select-k has them)")
+    if a.select_k and not a.consensus_bank:
+        raise SystemExit("--select-quality consensus needs --consensus-bank")
+    bank, cons = consensus_of(a, preds, device) if a.consensus_bank else (None, None)
     result = refs.score_captions(preds, set_diversity=a.set_diversity, consensus=cons)
+    selection = None
+    if a.select_k:
+        selection = bank.select_captions(preds, quality="consensus", consensus=cons, k=a.select_k, method=a.select_method,
+                                         lam=a.select_lambda, theta=a.select_theta)
     print("input:", a.predictions)
     print("Total ref sentences:", sum(len(refs.tokens[i]) for i in result.image_ids))
     s = result.summary()
+    if selection is not None:
+        s.update(result.subset_summary(selection, "select"))
     for line in format_summary(s):
         print(line)
     if result.empty_images:
@@ -81,6 +106,9 @@ def main():
     if a.consensus_output:
         out = [{"image_id": iid, "caption": caps[int(n)]} for (iid, caps), n in zip(preds.items(), cons.pick)]
         json.dump(out, open(a.consensus_output, "w"))
+    if a.select_output:
+        out = [{"image_id": iid, "caption": c} for iid, caps in selection.captions(preds).items() for c in caps]
+        json.dump(out, open(a.select_output, "w"))
 
 
 if __name__ == "__main__":

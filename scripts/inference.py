@@ -66,6 +66,20 @@ parser.add_argument("--consensus-bank", default="",
 parser.add_argument("--consensus-k", type=int, default=60, help="with --consensus-bank: nearest bank images per decoded image")
 parser.add_argument("--consensus-output", default="",
                     help='with --consensus-bank: write the picked caption of every image here ([{"image_id", "caption"}, ...])')
+parser.add_argument("--select-k", type=int, default=0,
+                    help="keep K captions per image that are good and different from each other (ssc_runtime.evaluation.select_captions "
+                         "on the caption kernel of the image's decoded captions); needs --select-output")
+parser.add_argument("--select-method", default="dpp", choices=["dpp", "mmr", "mbr"],
+                    help="greedy DPP MAP (quality x diversity), maximal marginal relevance, or minimum Bayes risk under the caption kernel")
+parser.add_argument("--select-quality", default="consensus", choices=["consensus", "logprob"],
+                    help="the per-caption quality: the consensus scores (needs --consensus-bank) or the captions' log-probs under the "
+                         "model (the groups' own with MODEL.DIVERSE_BEAM_SEARCH, else the marginal of ssc_runtime.inference.score_captions "
+                         "over max(1, --likelihood-samples) latent samples, which draws from the run's random stream); the kernel's document frequencies are the bank's, or "
+                         "without a bank those of --references")
+parser.add_argument("--select-lambda", type=float, default=0.5, help="mmr: weight of the quality against the similarity to a pick")
+parser.add_argument("--select-theta", type=float, default=1.0, help="dpp: weight of the quality")
+parser.add_argument("--select-output", default="",
+                    help='with --select-k: write the K captions per image here, in pick order ([{"image_id", "caption"}, ...])')
 parser.add_argument("--likelihood-samples", type=int, default=0,
                     help="likelihood re-ranking: score every image's decoded captions under M FRESH latent samples "
                          "(ssc_runtime.inference.score_captions: log p(caption | image) ~ log mean_m p(caption | z^m, image)) and pick "
@@ -301,6 +315,17 @@ def main():
         bank = ConsensusBank.load(_A.consensus_bank, device=device)
     elif _A.consensus_output:
         raise SystemExit("--consensus-output needs --consensus-bank")
+    if bool(_A.select_k > 0) != bool(_A.select_output) or _A.select_k < 0:
+        raise SystemExit("--select-k K (K >= 1) and --select-output FILE go together")
+    select_refs, selections, selected = None, [], []
+    if _A.select_k:
+        if _A.select_quality == "consensus" and bank is None:
+            raise SystemExit("--select-quality consensus needs --consensus-bank")
+        if bank is None:
+            if not _A.references:
+                raise SystemExit("--select-k needs --consensus-bank or --references (the document frequencies of the caption kernel)")
+            from ssc_runtime.evaluation import CaptionReferences, load_references
+            select_refs = CaptionReferences(load_references(_A.references), device=device)
     if bool(_A.likelihood_samples > 0) != bool(_A.likelihood_output) or _A.likelihood_samples < 0:
         raise SystemExit("--likelihood-samples M (M >= 1) and --likelihood-output FILE go together")
     likelihood, lik_pick, lik_pick_len = [], [], []
@@ -394,6 +419,7 @@ def main():
                 for i, image_id in enumerate(here):
                     k = int(cons.pick[i])
                     best.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
+            sc = None
             if _A.likelihood_samples:
                 # each caption under M fresh latent samples, not under the one sample that produced it
                 sc = score_captions(model._dec, feats, senti, pred, _A.likelihood_samples, boundary, "decoded", obj_means=obj)
@@ -406,6 +432,25 @@ def main():
                     likelihood.append({"image_id": int(data.image_id[lo + i]), "caption": " ".join(words[i, k, : n_keep[i, k]]),
                                        "caption_per_token": " ".join(words[i, kl, : n_keep[i, kl]]), "pick": k, "pick_per_token": kl,
                                        "marginal": [float(x) for x in marg[i]], "n_tokens": [int(x) for x in ntok[i]]})
+            if _A.select_k:
+                here = [int(x) for x in data.image_id[lo: lo + n_here]]
+                logprob = None
+                if _A.select_quality == "logprob":
+                    if diverse is not None:
+                        logprob = out[2].reshape(pred.size(0), pred.size(1))
+                    else:
+                        if sc is None:
+                            sc = score_captions(model._dec, feats, senti, pred, 1, boundary, "decoded", obj_means=obj)
+                        logprob = sc.marginal
+                kw = dict(quality=_A.select_quality, consensus=consensus[-1] if bank is not None else None, logprob=logprob,
+                          k=min(_A.select_k, pred.size(1)), method=_A.select_method, lam=_A.select_lambda, theta=_A.select_theta)
+                if bank is not None:
+                    sel = bank.select(pred, boundary, vocabulary, **kw)
+                else:
+                    sel = select_refs.select(pred, boundary, vocabulary, image_ids=here, **kw)
+                selections.append(sel)
+                for i, image_id in enumerate(here):
+                    selected += [{"image_id": image_id, "caption": " ".join(words[i, n, : n_keep[i, n]])} for n in sel.picks[i] if n >= 0]
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
@@ -415,6 +460,9 @@ def main():
     if _A.consensus_output:
         json.dump(best, open(_A.consensus_output, "w", encoding="utf-8"))
         print(f"wrote {len(best)} consensus captions to {_A.consensus_output}")
+    if _A.select_output:
+        json.dump(selected, open(_A.select_output, "w", encoding="utf-8"))
+        print(f"wrote {len(selected)} selected captions ({_A.select_method}, k = {_A.select_k}) to {_A.select_output}")
     if _A.likelihood_output:
         json.dump(likelihood, open(_A.likelihood_output, "w", encoding="utf-8"))
         print(f"wrote {len(likelihood)} likelihood picks to {_A.likelihood_output}")
@@ -426,7 +474,11 @@ def main():
         pred = torch.cat([torch.nn.functional.pad(p, (0, steps - p.size(-1)), value=boundary) for _, p in chunks])
         result = refs.score(pred, boundary, vocabulary, image_ids=[i for ids, _ in chunks for i in ids],
                             set_diversity=_A.set_diversity, consensus=ConsensusResult.concat(consensus) if consensus else None)
-        for line in format_summary(result.summary()):
+        summ = result.summary()
+        if selections:
+            from ssc_runtime.evaluation import CaptionSelection
+            summ.update(result.subset_summary(CaptionSelection.concat(selections), "select"))
+        for line in format_summary(summ):
             print(line)
         if likelihood:   # best-1 by likelihood, next to the consensus lines: the pick by marginal and the pick by marginal per token
             for name, pick in (("likelihood", lik_pick), ("likelihood/len", lik_pick_len)):

@@ -20,6 +20,13 @@ images - pooled features and captions:
     cons = bank.rerank(predictions, boundary_index, vocabulary, pooled_queries, k=60, exclude_ids=image_ids)
     best = cons.pick                                                     # one sample index per image
     result = refs.score(predictions, boundary_index, vocabulary, consensus=cons)   # adds the "consensus ..." numbers
+
+Diverse subset selection (the k captions of an image to show: good AND different from each other, chosen with no test reference)
+is one more library call (ssc_eval_select: MBR, MMR or the greedy MAP of a DPP) on the caption kernel and a quality per candidate:
+
+    sel = bank.select(predictions, boundary_index, vocabulary, quality="consensus", consensus=cons, k=5, method="dpp")
+    kept = sel.gather(predictions, boundary_index)                       # (images, k, steps), in pick order
+    summary = {**result.summary(), **result.subset_summary(sel, "select")}
 """
 import ctypes
 import json
@@ -141,8 +148,9 @@ class SetDiversity:
         return s
 
 
-def _eval_set(pred: torch.Tensor, boundary_index: int, vocab_size: int, prep, id_map, ref_image, keep_kernel=True) -> SetDiversity:
-    """One ssc_eval_set call on (P, N, steps) int64 predictions on the device; prep None: no references (mBLEU / Unique only)."""
+def _eval_set_call(pred: torch.Tensor, boundary_index: int, vocab_size: int, prep, id_map, ref_image, keep_kernel=True):
+    """One ssc_eval_set call on (P, N, steps) int64 predictions on the device; prep None: no references (mBLEU / Unique only).
+    -> (set_counts, distinct, kernel or None, eigenvalues, ref_image) on the device."""
     P, N, steps = pred.shape
     if not 2 <= N <= MAX_SAMPLES:
         raise ValueError(f"set diversity needs 2..{MAX_SAMPLES} captions per image, got N = {N}")
@@ -166,6 +174,13 @@ def _eval_set(pred: torch.Tensor, boundary_index: int, vocab_size: int, prep, id
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         lib.ssc_eval_set(rp, ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
+    return counts, dist, kern, eig, ref_image
+
+
+def _eval_set(pred: torch.Tensor, boundary_index: int, vocab_size: int, prep, id_map, ref_image, keep_kernel=True) -> SetDiversity:
+    """_eval_set_call with its outputs copied to the host."""
+    scored = prep is not None
+    counts, dist, kern, eig, ref_image = _eval_set_call(pred, boundary_index, vocab_size, prep, id_map, ref_image, keep_kernel)
     rows = [p for p, i in enumerate(ref_image.cpu().tolist()) if i >= 0] if scored else []
     return SetDiversity(counts.cpu().numpy().astype(np.int64), dist.cpu().numpy().astype(np.int64),
                         kern.cpu().numpy() if kern is not None else None, eig.cpu().numpy() if scored else None, rows)
@@ -182,6 +197,125 @@ def set_diversity(predictions: torch.Tensor, boundary_index: int, vocab_size: in
     return _eval_set(predictions.contiguous(), boundary_index, vocab_size, None, None, None)
 
 
+# ---- diverse subset selection ---------------------------------------------------------------------------------------------------
+
+SELECT_METHODS = {"mbr": 1, "mmr": 2, "dpp": 3}
+
+
+class CaptionSelection:
+    """What ssc_eval_select chose for P images: picks (P, k) int64 candidate indices in pick order (-1: fewer than k candidates
+    were eligible), gains (P, k) float64 the rule's value of every pick when it was made (0 for fallback picks and -1 slots),
+    n_primary (P,) the picks the rule itself made before the fallback by quality filled up; method, k."""
+
+    def __init__(self, picks, gains, n_primary, method: str):
+        self.picks, self.gains, self.n_primary, self.method = picks, gains, n_primary, method
+        self.k = int(picks.shape[1])
+
+    def gather(self, predictions: torch.Tensor, boundary_index: int = 0) -> torch.Tensor:
+        """(P, N, steps) predictions -> (P, k, steps) the picked rows in pick order, on the predictions' device; a -1 slot becomes an
+        empty caption (a row of boundary_index)."""
+        if predictions.dim() != 3 or predictions.size(0) != self.picks.shape[0]:
+            raise ValueError(f"predictions must be ({self.picks.shape[0]}, N, steps), got {tuple(predictions.shape)}")
+        idx = torch.from_numpy(np.ascontiguousarray(self.picks)).to(predictions.device)
+        if int(idx.max()) >= predictions.size(1):
+            raise ValueError(f"a pick names candidate {int(idx.max())} of {predictions.size(1)}")
+        rows = predictions.gather(1, idx.clamp(min=0).unsqueeze(-1).expand(-1, -1, predictions.size(2)))
+        return torch.where((idx < 0).unsqueeze(-1), torch.full_like(rows, int(boundary_index)), rows)
+
+    def captions(self, groups) -> "OrderedDict[Any, List[str]]":
+        """{image_id: [N captions]} in the selection's image order -> {image_id: [the picked captions in pick order]}."""
+        if len(groups) != self.picks.shape[0]:
+            raise ValueError(f"{len(groups)} images for a selection over {self.picks.shape[0]}")
+        return OrderedDict((iid, [caps[int(n)] for n in row if n >= 0]) for (iid, caps), row in zip(groups.items(), self.picks))
+
+    @staticmethod
+    def concat(parts: Sequence["CaptionSelection"]) -> "CaptionSelection":
+        """The selections of several calls (the same method and k) as one, in call order."""
+        cat = lambda name: np.concatenate([getattr(r, name) for r in parts])   # noqa: E731
+        return CaptionSelection(cat("picks"), cat("gains"), cat("n_primary"), parts[0].method)
+
+
+def select_captions(kernel, quality=None, k: int = 5, method: str = "dpp", lam: float = 0.5, theta: float = 1.0,
+                    min_gain: float = 1e-10, normalize: bool = True, eligible=None) -> CaptionSelection:
+    """From the N candidates of every image the k that are good and different from each other (one ssc_eval_select call).
+    kernel (P, N, N) float64 on the device: the caption similarity ssc_eval_set leaves (SetDiversity.set_kernel, or what
+    CaptionReferences.select / ConsensusBank.select build themselves).  quality (P, N): consensus scores, caption log-probs, ...;
+    None for "mbr", and for "dpp" with theta = 0.  method: "mbr" - the candidates closest to all others; "mmr" - lam x quality
+    against (1 - lam) x the largest similarity to a pick; "dpp" - the greedy MAP of the DPP exp(theta q^_i) K_ij exp(theta q^_j),
+    which stops at gains below min_gain (duplicates of a pick) and fills the rest by quality.  normalize: the rules see every
+    image's quality scaled to [0, 1].  eligible (P, N): 0 / False = never pick (an empty or filtered caption)."""
+    if method not in SELECT_METHODS:
+        raise ValueError(f"method {method!r}: one of {sorted(SELECT_METHODS)}")
+    kern = torch.as_tensor(kernel)
+    if kern.dim() != 3 or kern.size(1) != kern.size(2) or kern.dtype != torch.float64:
+        raise ValueError(f"kernel must be (images, N, N) float64, got {tuple(kern.shape)} {kern.dtype}")
+    P, N, _ = kern.shape
+    if not 1 <= N <= MAX_SAMPLES or not 1 <= int(k) <= N:
+        raise ValueError(f"k = {k} of N = {N} candidates: 1 <= k <= N <= {MAX_SAMPLES} is supported")
+    if quality is None and (method == "mmr" or (method == "dpp" and theta != 0)):
+        raise ValueError(f"method {method!r} needs a quality per candidate" + (" (or theta = 0)" if method == "dpp" else ""))
+    for name, t in (("quality", quality), ("eligible", eligible)):
+        if t is not None and tuple(torch.as_tensor(t).shape) != (P, N):
+            raise ValueError(f"{name} must be ({P}, {N}), got {tuple(torch.as_tensor(t).shape)}")
+    kern = (kern if kern.is_cuda else kern.cuda()).contiguous()
+    dev = kern.device
+    qual = elig = None
+    if quality is not None:
+        qual = torch.as_tensor(quality).to(device=dev, dtype=torch.float64).contiguous()
+    if eligible is not None:
+        elig = (torch.as_tensor(eligible).to(dev) != 0).to(torch.uint8).contiguous()
+    k = int(k)
+    picks = torch.empty(P, k, dtype=torch.int32, device=dev)
+    gains = torch.empty(P, k, dtype=torch.float64, device=dev)
+    nprim = torch.empty(P, dtype=torch.int32, device=dev)
+    d = L.EvalSelectDesc(P, N, k, SELECT_METHODS[method], L.ptr(kern), L.ptr(qual), int(bool(normalize)), float(lam), float(theta),
+                         float(min_gain), L.ptr(elig), L.ptr(picks), L.ptr(gains), L.ptr(nprim))
+    lib = L.load()
+    nbytes = lib.ssc_eval_select_workspace_bytes(ctypes.byref(d))
+    if nbytes == 0:
+        raise ValueError(f"selection: arguments out of range (lam = {lam}, theta = {theta}, min_gain = {min_gain}, {P} images)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        lib.ssc_eval_select(ctypes.byref(d), L.ptr(ws), ws.numel(), L.stream_ptr())
+    return CaptionSelection(picks.cpu().numpy().astype(np.int64), gains.cpu().numpy(), nprim.cpu().numpy().astype(np.int64), method)
+
+
+def _select_quality(quality, consensus, logprob, P, N):
+    """The (P, N) quality a select() call names: "consensus" - the ConsensusResult's scores; "logprob" - the given log-probs; a
+    tensor - itself; None."""
+    if isinstance(quality, str):
+        if quality == "consensus":
+            if not isinstance(consensus, ConsensusResult):
+                raise ValueError('quality="consensus" needs consensus=ConsensusResult (ConsensusBank.rerank on the same predictions)')
+            quality = consensus.scores
+        elif quality == "logprob":
+            if logprob is None:
+                raise ValueError('quality="logprob" needs logprob=(images, N) caption log-probs')
+            quality = logprob
+        else:
+            raise ValueError(f'quality {quality!r}: "consensus", "logprob", a tensor or None')
+    if quality is not None and tuple(quality.shape) != (P, N):
+        raise ValueError(f"quality holds {tuple(quality.shape)} values for ({P}, {N}) predictions")
+    return quality
+
+
+def _select_on_kernel(pred, boundary_index, vocab_size, prep, id_map, ref_image, quality, eligible, kw) -> CaptionSelection:
+    """The caption kernel of (P, N, steps) predictions on the device (ssc_eval_set) and the selection on it; empty captions are not
+    eligible.  N = 1: the kernel is not needed (the one candidate, if it is not empty).  prep None (no image has references): the
+    zero kernel every image without references gets."""
+    P, N, _ = pred.shape
+    if N >= 2 and prep is not None:
+        kern = _eval_set_call(pred, boundary_index, vocab_size, prep, id_map, ref_image)[2]
+    elif N >= 2:
+        kern = torch.zeros(P, N, N, dtype=torch.float64, device=pred.device)
+    else:
+        kern = torch.ones(P, 1, 1, dtype=torch.float64, device=pred.device)
+    elig = pred[:, :, 0] != int(boundary_index)
+    if eligible is not None:
+        elig = elig & (torch.as_tensor(eligible).to(pred.device) != 0)
+    return select_captions(kern, quality, eligible=elig, **kw)
+
+
 class EvalResult:
     """Per-candidate scores of the evaluated images (those with predictions and references, in prediction order) and the
     per-image counts, with eval.py's reductions.
@@ -196,6 +330,7 @@ class EvalResult:
     def __init__(self, image_ids, scores, stats, image_counts, eval_rows, top5, has_style, set_out: Optional[SetDiversity] = None,
                  consensus: Optional["ConsensusResult"] = None):
         self._set = set_out
+        self._ctx = None   # (references, predictions on the device, boundary, words, image ids, unk): what subset_summary scores again
         # consensus_pick (I,): the consensus re-ranking's sample of every evaluated image (None without consensus=)
         self.consensus_pick = np.asarray(consensus.pick, dtype=np.int64)[eval_rows] if consensus is not None else None
         self.set_stats = set_out.set_stats if set_out else None
@@ -278,6 +413,31 @@ class EvalResult:
         return s
 
 
+    def subset_summary(self, selection: "CaptionSelection", name: str) -> Dict[str, float]:
+        """The k captions per image a selection kept (select_captions, CaptionReferences.select, ConsensusBank.select on the SAME
+        predictions), evaluated as a caption set of their own: the gathered (P, k, steps) predictions go through the score call and,
+        for k >= 2, the set call again.  -> {"<name> subset Div-1", "... Div-2", "... distinct" (mean distinct captions per image),
+        "... unique", "... mBLEU-1".."... mBLEU-4", "... self-cider", "... oracle cider", "... mean cider", "... oracle B4",
+        "... mean B4"}; a -1 slot counts as an empty caption."""
+        if self._ctx is None:
+            raise ValueError("subset_summary needs a result of CaptionReferences.score / score_captions")
+        refs, pred, boundary, words, image_ids, unk = self._ctx
+        if selection.picks.shape[0] != pred.size(0):
+            raise ValueError(f"the selection holds {selection.picks.shape[0]} images, the predictions {pred.size(0)}")
+        sub = refs._score_ids(selection.gather(pred, boundary), boundary, words, image_ids, unk, set_diversity=selection.k >= 2,
+                              _min_n=1)
+        s = sub.summary()
+        out = {f"{name} subset Div-1": s["Div-1"], f"{name} subset Div-2": s["Div-2"]}
+        if sub.distinct is not None:
+            out[f"{name} subset distinct"] = float(np.mean(sub.distinct))
+            for key in ("unique", "mBLEU-1", "mBLEU-2", "mBLEU-3", "mBLEU-4", "self-cider"):
+                if key in s:
+                    out[f"{name} subset {key}"] = s[key]
+        out[f"{name} subset oracle cider"], out[f"{name} subset mean cider"] = s["cider"], s["mean cider"]
+        out[f"{name} subset oracle B4"], out[f"{name} subset mean B4"] = s["B4"], s["mean B4"]
+        return out
+
+
 def format_summary(s: Dict[str, float]) -> List[str]:
     """The lines eval.py prints: BLEU / ROUGE-L / CIDEr x 100 rounded to 2 decimals; METEOR is not computed."""
     out = [f"Div-1: {s['Div-1']}", f"Div-2: {s['Div-2']}"]
@@ -300,6 +460,12 @@ def format_summary(s: Dict[str, float]) -> List[str]:
     for k in ("self-cider", "unique"):
         if k in s:
             out.append(f"{k}: {np.round(s[k], 4)}")
+    # a selected subset (EvalResult.subset_summary): BLEU / CIDEr / mBLEU x 100 as above, the shares and counts as they are
+    for k in s:
+        if " subset " in k:
+            scaled = k.rsplit(" subset ", 1)[1] in ("mBLEU-1", "mBLEU-2", "mBLEU-3", "mBLEU-4", "oracle cider", "mean cider",
+                                                    "oracle B4", "mean B4")
+            out.append(f"{k}: {np.round(s[k] * 100.0, 2) if scaled else np.round(s[k], 4)}")
     return out
 
 
@@ -419,7 +585,7 @@ class CaptionReferences:
         return self._prepared[key]
 
     def _score_ids(self, pred: torch.Tensor, boundary_index: int, words: Sequence[str], image_ids: Sequence, unk: Optional[int],
-                   set_diversity: bool = False, consensus: Optional["ConsensusResult"] = None):
+                   set_diversity: bool = False, consensus: Optional["ConsensusResult"] = None, _min_n: int = 5):
         if pred.dim() != 3 or pred.dtype != torch.int64:
             raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(pred.shape)} {pred.dtype}")
         P, N, steps = pred.shape
@@ -427,7 +593,7 @@ class CaptionReferences:
             raise ValueError(f"{len(image_ids)} image ids for {P} prediction images")
         if len(set(image_ids)) != P:
             raise ValueError("an image id occurs twice among the predictions")
-        if N < 5:
+        if N < _min_n:
             raise ValueError(f"top-5 Div-n needs at least 5 captions per image, got N = {N}")
         if N > MAX_SAMPLES:
             raise ValueError(f"N = {N} captions per image: at most {MAX_SAMPLES} are supported")
@@ -456,8 +622,48 @@ class CaptionReferences:
         rows = [p for p, i in enumerate(image_ids) if i in self.tokens]
         imgc = img.cpu().numpy().astype(np.int64)
         set_out = _eval_set(pred, boundary_index, len(words), prep, id_map, ref_image) if set_diversity else None
-        return EvalResult(list(image_ids), scores.cpu().numpy(), counts.cpu().numpy().astype(np.int64), imgc, rows,
-                          top5.cpu().numpy().astype(np.int64), self.style_words is not None, set_out, consensus)
+        res = EvalResult(list(image_ids), scores.cpu().numpy(), counts.cpu().numpy().astype(np.int64), imgc, rows,
+                         top5.cpu().numpy().astype(np.int64), self.style_words is not None, set_out, consensus)
+        res._ctx = (self, pred, boundary_index, list(words), list(image_ids), unk)
+        return res
+
+    def _select_ids(self, pred: torch.Tensor, boundary_index: int, words: Sequence[str], image_ids: Sequence, unk: Optional[int],
+                    quality, consensus, logprob, eligible, kw) -> "CaptionSelection":
+        if pred.dim() != 3 or pred.dtype != torch.int64:
+            raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(pred.shape)} {pred.dtype}")
+        P, N, _ = pred.shape
+        if len(image_ids) != P:
+            raise ValueError(f"{len(image_ids)} image ids for {P} prediction images")
+        ids = [i for i in image_ids if i in self.tokens]
+        prep = id_map = ref_image = None
+        if ids:   # (a call whose images all lack references still selects: by the quality alone)
+            prep = self.prepared(ids)
+            id_map = np.array([self.word_id.get(w, 0) for w in words], dtype=np.int32)
+            if unk is not None and 0 <= unk < len(words):
+                id_map[unk] = 0   # the vocabulary's @@UNKNOWN@@ matches nothing
+            id_map = torch.from_numpy(id_map).to(self.device)
+            ref_image = torch.tensor([prep.index.get(i, -1) for i in image_ids], dtype=torch.int32, device=self.device)
+        quality = _select_quality(quality, consensus, logprob, P, N)
+        return _select_on_kernel(pred.to(self.device).contiguous(), boundary_index, len(words), prep, id_map, ref_image, quality,
+                                 eligible, kw)
+
+    def select(self, predictions: torch.Tensor, boundary_index: int, vocabulary, image_ids: Optional[Sequence] = None,
+               quality="consensus", consensus: Optional["ConsensusResult"] = None, logprob=None, eligible=None,
+               **kw) -> "CaptionSelection":
+        """The k captions per image to keep: the caption kernel of the predictions (ssc_eval_set with these references' document
+        frequencies - only the frequencies: no caption is compared with a reference) and select_captions on it, all on the device.
+        predictions, boundary_index, vocabulary, image_ids: as for score(); an image without references has a zero kernel (a DPP
+        then falls back to the quality order).  quality: "consensus" (the scores of consensus=, a ConsensusResult on the same
+        predictions), "logprob" (logprob=, (images, N) caption log-probs), a (images, N) tensor, or None.  Empty captions are never
+        picked; eligible (images, N) excludes more.  **kw: k, method, lam, theta, min_gain, normalize of select_captions."""
+        if hasattr(vocabulary, "get_vocab_size"):
+            words = [vocabulary.get_token_from_index(i) for i in range(vocabulary.get_vocab_size())]
+        else:
+            words = list(vocabulary)
+        unk = words.index(UNKNOWN) if UNKNOWN in words else None
+        ids = self.image_ids if image_ids is None else [_norm_id(i) for i in image_ids]
+        return self._select_ids(predictions, boundary_index, words, ids, unk, quality, consensus, logprob, eligible, kw)
+
 
     def score(self, predictions: torch.Tensor, boundary_index: int, vocabulary, image_ids: Optional[Sequence] = None,
               set_diversity: bool = False, consensus: Optional["ConsensusResult"] = None) -> EvalResult:
@@ -732,6 +938,35 @@ class ConsensusBank:
         words = self._words(vocabulary)
         unk = words.index(UNKNOWN) if UNKNOWN in words else None
         return self._rerank_ids(predictions, boundary_index, words, unk, pooled_queries, k, exclude_ids, neighbours)
+
+    def _select_ids(self, pred, boundary_index, words, unk, quality, consensus, logprob, eligible, kw) -> "CaptionSelection":
+        if pred.dim() != 3 or pred.dtype != torch.int64:
+            raise ValueError(f"predictions must be (images, N, steps) int64, got {tuple(pred.shape)} {pred.dtype}")
+        P, N, _ = pred.shape
+        refs = self.references
+        id_map = np.array([refs.word_id.get(w, 0) for w in words], dtype=np.int32)
+        if unk is not None and 0 <= unk < len(words):
+            id_map[unk] = 0   # the vocabulary's @@UNKNOWN@@ matches nothing
+        id_map = torch.from_numpy(id_map).to(self.device)
+        # (any prepared image: the kernel reads the set's document frequencies and log I, not the image's references)
+        ref_image = torch.zeros(P, dtype=torch.int32, device=self.device)
+        quality = _select_quality(quality, consensus, logprob, P, N)
+        return _select_on_kernel(pred.to(self.device).contiguous(), boundary_index, len(words), self.prep, id_map, ref_image,
+                                 quality, eligible, kw)
+
+    def select(self, predictions: torch.Tensor, boundary_index: int, vocabulary, quality="consensus",
+               consensus: Optional[ConsensusResult] = None, logprob=None, eligible=None, **kw) -> "CaptionSelection":
+        """CaptionReferences.select with the BANK's document frequencies: the k captions per image to keep, chosen with no test
+        reference at all.  quality="consensus": the scores of consensus= (this bank's rerank on the same predictions)."""
+        words = self._words(vocabulary)
+        unk = words.index(UNKNOWN) if UNKNOWN in words else None
+        return self._select_ids(predictions, boundary_index, words, unk, quality, consensus, logprob, eligible, kw)
+
+    def select_captions(self, predictions, quality="consensus", consensus: Optional[ConsensusResult] = None, logprob=None,
+                        eligible=None, **kw) -> "CaptionSelection":
+        """select() for caption strings, read as rerank_captions reads them."""
+        _, arr, words = _caption_ids(predictions)
+        return self._select_ids(torch.from_numpy(arr).to(self.device), 0, words, None, quality, consensus, logprob, eligible, kw)
 
     def rerank_captions(self, predictions, pooled_queries=None, k: int = 60, exclude_ids: Optional[Sequence] = None,
                         neighbours=None) -> ConsensusResult:

@@ -244,6 +244,13 @@ class EvalConsensusDesc(C.Structure):
                 ("id_map", vp), ("neighbours", vp), ("k", C.c_int), ("scores", vp), ("pool_refs", vp), ("pick", vp), ("order", vp)]
 
 
+class EvalSelectDesc(C.Structure):
+    # ("lambda" is a Python keyword: the field is set positionally, through setattr or through **{"lambda": x})
+    _fields_ = [("P", C.c_int), ("N", C.c_int), ("k", C.c_int), ("method", C.c_int), ("kernel", vp), ("quality", vp),
+                ("normalize", C.c_int), ("lambda", C.c_double), ("theta", C.c_double), ("min_gain", C.c_double), ("eligible", vp),
+                ("picks", vp), ("gains", vp), ("n_primary", vp)]
+
+
 class ScstDesc(C.Structure):
     _fields_ = [("P", C.c_int), ("N", C.c_int), ("steps", C.c_int), ("L", C.c_int), ("end_index", C.c_int), ("predictions", vp),
                 ("scores", vp), ("base_scores", vp), ("reward_weights", C.c_double * 6), ("baseline", C.c_int),
@@ -397,6 +404,8 @@ SYMBOLS = {
     "ssc_knn_merge": (_i, [vp, _i, _i, _i, _i, _i, vp, vp, vp, vp]),
     "ssc_eval_consensus_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc)]),
     "ssc_eval_consensus": (_i, [C.POINTER(EvalRefs), C.POINTER(EvalConsensusDesc), vp, _sz, vp]),
+    "ssc_eval_select_workspace_bytes": (_sz, [C.POINTER(EvalSelectDesc)]),
+    "ssc_eval_select": (_i, [C.POINTER(EvalSelectDesc), vp, _sz, vp]),
     "ssc_scst_prepare": (_i, [C.POINTER(ScstDesc), vp]),
     "ssc_attn_gather": (_i, [C.POINTER(AttnGatherDesc), vp]),
 }
