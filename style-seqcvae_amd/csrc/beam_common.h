@@ -61,17 +61,7 @@ __device__ __forceinline__ float dec_block_reduce1(float v, float (*sh)[4], int 
   return r;
 }
 
-// block reduction with exactly the arithmetic of log_softmax_kernel (256 threads, strided partials, this order)
-__device__ __forceinline__ float dec_block_reduce(float v, float* sh, bool is_max) {
-  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  v = is_max ? ssc_wave_max(v) : ssc_wave_sum(v);
-  __syncthreads();
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
+// (the two-barrier float reduction is ssc_block_reduce of ssc_common.h: the function log_softmax_kernel itself calls)
 
 // ---- pieces of the selections that take a whole row per workgroup of 256 (diverse_beam.hip, rules_beam.hip) ---------------------
 
@@ -92,12 +82,12 @@ __device__ __forceinline__ float beam_row_lse(const float* __restrict__ row, int
 #pragma unroll
       for (int u = 0; u < BEAM_ROW_NV; ++u)
         if (t + u * 256 < V) mx = fmaxf(mx, x[u]);
-      mx = dec_block_reduce(mx, shr, true);
+      mx = ssc_block_reduce(mx, shr, true);
       float sum = 0.f;
 #pragma unroll
       for (int u = 0; u < BEAM_ROW_NV; ++u)
         if (t + u * 256 < V) sum += expf(x[u] - mx);
-      sum = dec_block_reduce(sum, shr, false);
+      sum = ssc_block_reduce(sum, shr, false);
       lse = mx + logf(sum);
 #pragma unroll
       for (int u = 0; u < BEAM_ROW_NV; ++u) x[u] -= lse;
@@ -105,10 +95,10 @@ __device__ __forceinline__ float beam_row_lse(const float* __restrict__ row, int
   } else if (NORM) {   // thread t owns v = t, t + 256, ...: the order of log_softmax_kernel
     float mx = -INFINITY;
     for (int v = t; v < V; v += 256) mx = fmaxf(mx, row[v]);
-    mx = dec_block_reduce(mx, shr, true);
+    mx = ssc_block_reduce(mx, shr, true);
     float sum = 0.f;
     for (int v = t; v < V; v += 256) sum += expf(row[v] - mx);
-    sum = dec_block_reduce(sum, shr, false);
+    sum = ssc_block_reduce(sum, shr, false);
     lse = mx + logf(sum);
   }
   return lse;

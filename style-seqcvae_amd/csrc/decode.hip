@@ -174,7 +174,7 @@ int gemm_slabs(hipStream_t st, float* ws, size_t ws_floats, std::initializer_lis
 // pass k finds the best candidate strictly after the previous pick in that order).
 // ---------------------------------------------------------------------------------------------------
 // NORM: `lp` holds un-normalised logits; the row's log-sum-exp is taken here with exactly the arithmetic of
-// log_softmax_kernel (256 threads, strided partial maxima / sums, block_reduce order), so lp[v] - lse is bit-identical to
+// log_softmax_kernel (256 threads, strided partial maxima / sums, ssc_block_reduce order), so lp[v] - lse is bit-identical to
 // what ssc_log_softmax would have stored.  The row is staged in LDS when it fits (`staged`), so HBM sees it once.
 template <bool NORM>
 __device__ __forceinline__ const float* row_prepare(const float* __restrict__ row, int V, bool staged, float* srow, float* shr,
@@ -197,11 +197,11 @@ __device__ __forceinline__ const float* row_prepare(const float* __restrict__ ro
       }
     }
   }
-  mx = dec_block_reduce(mx, shr, true);   // (its barriers also publish srow)
+  mx = ssc_block_reduce(mx, shr, true);   // (its barriers also publish srow)
   const float* src = staged ? srow : row;
   float s = 0.f;
   for (int v = threadIdx.x; v < V; v += blockDim.x) s += expf(src[v] - mx);
-  s = dec_block_reduce(s, shr, false);
+  s = ssc_block_reduce(s, shr, false);
   lse = mx + logf(s);
   return src;
 }
@@ -303,12 +303,12 @@ __global__ __launch_bounds__(256) void beam_row_topk_reg_kernel(const float* __r
 #pragma unroll
       for (int u = 0; u < BEAM_REG_NV; ++u)
         if (t + u * 256 < V) mx = fmaxf(mx, x[u]);
-      mx = dec_block_reduce(mx, shr, true);
+      mx = ssc_block_reduce(mx, shr, true);
       float sum = 0.f;
 #pragma unroll
       for (int u = 0; u < BEAM_REG_NV; ++u)
         if (t + u * 256 < V) sum += expf(x[u] - mx);
-      sum = dec_block_reduce(sum, shr, false);
+      sum = ssc_block_reduce(sum, shr, false);
       lse = mx + logf(sum);
     }
     if (NORM) {

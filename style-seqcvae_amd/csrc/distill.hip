@@ -19,17 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ float kd_block_reduce(float v, float* sh, bool is_max) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = is_max ? ssc_wave_max(v) : ssc_wave_sum(v);
-  __syncthreads();
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < 4; ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
-
 // f(x[v], s[v]) over the row pair: elements [0, head) and [head + 4 * n4, V) one by one, the n4 groups of four in between as
 // 16-byte loads (head = V, n4 = 0: the scalar path throughout)
 template <class F>
@@ -43,7 +32,7 @@ __device__ __forceinline__ void kd_scan(const float* __restrict__ x, const float
   }
   const int tail = head + (n4 << 2), ns = head + (V - tail);
   for (int k = threadIdx.x; k < ns; k += 256) {
-    const int v = k < head ? k : tail + (k - head);
+    const int v = ssc_row_split_col(k, head, tail);
     f(x[v], s[v]);
   }
 }
@@ -80,8 +69,8 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(const KdFwdArgs a) {
     ms = fmaxf(ms, sv);
     d += xv - r;
   });
-  const float Mx = kd_block_reduce(mx, sh, true), Ms = kd_block_reduce(ms, sh, true);
-  d = kd_block_reduce(d, sh, false);
+  const float Mx = ssc_block_reduce(mx, sh, true), Ms = ssc_block_reduce(ms, sh, true);
+  d = ssc_block_reduce(d, sh, false);
   const float it = a.inv_tau;
   float sx = 0.f, sxt = 0.f, ss = 0.f, acc = 0.f;
   kd_scan(x, s, a.V, a.head, a.n4, [&](float xv, float sv) {
@@ -92,10 +81,10 @@ __global__ __launch_bounds__(256) void kd_fwd_kernel(const KdFwdArgs a) {
     ss += es;
     if (es > 0.f) acc += es * (TAU1 ? ds - dx : (ds - dx) * it);   // q[v] = 0 contributes nothing (never 0 * inf)
   });
-  sx = kd_block_reduce(sx, sh, false);
-  sxt = TAU1 ? sx : kd_block_reduce(sxt, sh, false);
-  ss = kd_block_reduce(ss, sh, false);
-  acc = kd_block_reduce(acc, sh, false);
+  sx = ssc_block_reduce(sx, sh, false);
+  sxt = TAU1 ? sx : ssc_block_reduce(sxt, sh, false);
+  ss = ssc_block_reduce(ss, sh, false);
+  acc = ssc_block_reduce(acc, sh, false);
   if (threadIdx.x == 0) {
     const float l = Mx + logf(sx);
     const float lsxt = logf(sxt), lss = logf(ss);
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(256) void kd_bwd_kernel(const KdBwdArgs a) {
   const int head = a.head, n4 = a.n4, tail = head + (n4 << 2), ns = head + (a.V - tail);
   if (coef == 0.f) {  // never reads either row: a padded target's rows may hold anything
     for (int i = threadIdx.x; i < n4; i += 256) p4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = threadIdx.x; k < ns; k += 256) p[k < head ? k : tail + (k - head)] = 0.f;
+    for (int k = threadIdx.x; k < ns; k += 256) p[ssc_row_split_col(k, head, tail)] = 0.f;
     return;
   }
   const float* s = a.teacher + (size_t)row * a.ldt;
@@ -191,23 +180,9 @@ __global__ __launch_bounds__(256) void kd_bwd_kernel(const KdBwdArgs a) {
     p4[i] = x;
   }
   for (int k = threadIdx.x; k < ns; k += 256) {
-    const int v = k < head ? k : tail + (k - head);
+    const int v = ssc_row_split_col(k, head, tail);
     p[v] = one(p[v], s[v], v);
   }
-}
-
-inline bool kd_eps_ok(float eps) { return eps >= 0.f && eps < 1.f; }   // false for NaN
-
-// how the kernels walk a row pair (see kd_scan): 16-byte accesses only where both rows of every pair share one misalignment
-inline void kd_row_split(const float* logits, int ldl, const float* teacher, int ldt, int V, int* head, int* n4) {
-  *head = V;
-  *n4 = 0;
-  if ((ldl & 3) != 0 || (ldt & 3) != 0) return;
-  if (((uintptr_t)logits & 15u) != ((uintptr_t)teacher & 15u)) return;
-  const int h = (int)(((16u - (unsigned)((uintptr_t)logits & 15u)) & 15u) >> 2);
-  if (h >= V) return;
-  *head = h;
-  *n4 = (V - h) >> 2;
 }
 
 // the [first, first + (rows-1) * ld + V) float ranges of the two matrices may not meet
@@ -240,7 +215,7 @@ int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targe
                               int V, float eps, const ssc_distill* kd, float* lse, float* nllw, float* nllw0, float* loss, float* nll,
                               hipStream_t st) {
   if (!logits || !targets || !w || !nvalid || !lse || !nllw || !nllw0 || !loss || T <= 0 || B <= 0 || V <= 0 || ldl < V ||
-      !kd_eps_ok(eps))
+      !ssc_ce_eps_ok(eps))
     return SSC_EINVAL;
   if (((uintptr_t)logits & 3u) != 0) return SSC_EALIGN;
   bool on;
@@ -250,7 +225,7 @@ int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targe
   KdFwdArgs a{};
   a.logits = logits; a.ldl = ldl; a.teacher = kd->teacher; a.ldt = kd->ldt; a.targets = targets; a.w = w;
   a.V = V; a.rows = rows;
-  kd_row_split(logits, ldl, kd->teacher, kd->ldt, V, &a.head, &a.n4);
+  ssc_row_split(logits, ldl, kd->teacher, kd->ldt, V, &a.head, &a.n4);
   a.eps_over_v = (float)((double)eps / V); a.alpha = kd->alpha; a.tau = kd->temperature; a.inv_tau = 1.f / kd->temperature;
   a.lse = lse; a.nllw = nllw; a.nllw0 = nllw0; a.kdrows = kd->rows;
   if (kd->temperature == 1.f) SSC_LAUNCH(kd_fwd_kernel<true>, dim3(rows), dim3(256), 0, st, a);
@@ -274,7 +249,7 @@ extern "C" int ssc_ce_fwd_distill(const float* logits, int ldl, const int64_t* t
 extern "C" int ssc_ce_bwd_distill(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid,
                                   const float* lse, const float* gl, int T, int B, int V, float eps, const ssc_distill* kd,
                                   void* stream) {
-  if (!logits || !targets || !w || !nvalid || !lse || !gl || T <= 0 || B <= 0 || V <= 0 || ldl < V || !kd_eps_ok(eps))
+  if (!logits || !targets || !w || !nvalid || !lse || !gl || T <= 0 || B <= 0 || V <= 0 || ldl < V || !ssc_ce_eps_ok(eps))
     return SSC_EINVAL;
   if (((uintptr_t)logits & 3u) != 0) return SSC_EALIGN;
   bool on;
@@ -284,7 +259,7 @@ extern "C" int ssc_ce_bwd_distill(float* logits, int ldl, const int64_t* targets
   a.logits = logits; a.ldl = ldl; a.teacher = kd->teacher; a.ldt = kd->ldt; a.targets = targets;
   a.w = w; a.nvalid = nvalid; a.lse = lse; a.kdrows = kd->rows; a.gl = gl;
   a.B = B; a.V = V; a.rows = T * B;
-  kd_row_split(logits, ldl, kd->teacher, kd->ldt, V, &a.head, &a.n4);
+  ssc_row_split(logits, ldl, kd->teacher, kd->ldt, V, &a.head, &a.n4);
   a.keep = 1.f - eps; a.eps_over_v = (float)((double)eps / V); a.alpha = kd->alpha; a.inv_tau = 1.f / kd->temperature;
   a.atau = kd->alpha * kd->temperature;
   if (kd->temperature == 1.f) SSC_LAUNCH(kd_bwd_kernel<true>, dim3(T * B), dim3(256), 0, (hipStream_t)stream, a);

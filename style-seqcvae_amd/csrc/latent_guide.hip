@@ -5,7 +5,7 @@
 // ssc_latent_guide_rows is the decode step's latent launch (ssc_latent_prior_sample's place): row r belongs to entry
 // b = r / rows_per_entry; a guided entry gets z = eps * sqrtf(var[t, b]) + mean[t, b] - the expression of
 // latent_prior_sample_pm_kernel (pointwise.hip), so a decode driven step by step with (rows, Z) operands gives the same bits -, an
-// unguided one the expression of latent_prior_sample_kernel.  One thread per (row, four columns); whether an entry is guided is read
+// unguided one the expression of latent_prior_sample_pm_kernel.  One thread per (row, four columns); whether an entry is guided is read
 // once per thread and is the same for every thread of a row.  Each of the three operands (eps, the guide, z) is touched with 16-byte
 // accesses where its leading dimension and base allow and with scalar accesses otherwise; the arithmetic is the same either way
 // (-ffp-contract=off), so the bits do not depend on the path.  Columns >= Z of the inputs are never read; with var NULL a guided
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void latent_guide_rows_kernel(const GuideRowsA
 #pragma unroll
     for (int u = 0; u < 4; ++u) zz[u] = e[u] * a.sd + pm;
   }
-  // pad columns Z .. round4(Z) of a 16-byte padded row are zeroed, as latent_prior_sample_kernel zeroes them
+  // pad columns Z .. round4(Z) of a 16-byte padded row are zeroed, as latent_prior_sample_pm_kernel zeroes them
 #pragma unroll
   for (int u = 0; u < 4; ++u)
     if (c + u >= Z) zz[u] = 0.f;

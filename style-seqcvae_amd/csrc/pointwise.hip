@@ -3,6 +3,7 @@
 // axis and 64-lane shuffle reductions.  Reference citations are on the C entry points in ssc.h.
 #include <algorithm>
 
+#include "latent_common.h"
 #include "ssc_common.h"
 
 thread_local int ssc_tls_hip_error = 0;
@@ -171,198 +172,61 @@ __global__ void __launch_bounds__(kEmbedScatterThreads) embed_scatter_kernel(flo
 }
 
 // ---------------------------------------------------------------------------------------------
-// latent head
+// latent head: mu / log_var / z / KL of one step and its backward, plain (FB = 0) or with a free-bits floor on the KL
+// (FB = 1..3, the modes of include/ssc.h: ssc_free_bits).  Every form is built from the pieces below, so mu / lv / z and the raw KL
+// are the same bits in all of them; latent_fb_elem and latent_fb_row are the only place where the modes differ.
 // ---------------------------------------------------------------------------------------------
-__global__ void latent_fwd_kernel(const ssc_latent_fwd_desc d) {
-  int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
-  if (b >= d.B) return;
-  const int Z = d.Z;
-  const float pm_row = d.sent ? d.pm_scale * d.sent[b] : 0.f;
-  float pvar = d.prior_var;
-  float lpv = logf(pvar);
-  float acc = 0.f;
-  for (int z = lane; z < Z; z += 64) {
-    float m = 0.f, l = 0.f;
-    for (int s0 = 0; s0 < d.nslab; s0 += 8) {
-      float tm[8], tl[8];
+// m, l += slabs [s_lo, s_hi) of element (b, z) in index order, U loads of each in flight: the loads of a round are clamped to the
+// last valid slab and all issued before the adds, a term past the range is added as 0
+template <int U>
+__device__ __forceinline__ void latent_sum_slabs(const ssc_latent_fwd_desc& d, int b, int z, int s_lo, int s_hi, float& m, float& l) {
+  for (int s0 = s_lo; s0 < s_hi; s0 += U) {
+    float tm[U], tl[U];
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float* row = d.mulv + (size_t)min(s0 + u, d.nslab - 1) * d.slab_stride + (size_t)b * d.ldmulv;
-        tm[u] = row[z];
-        tl[u] = row[Z + z];
-      }
+    for (int u = 0; u < U; ++u) {
+      const float* row = d.mulv + (size_t)min(s0 + u, s_hi - 1) * d.slab_stride + (size_t)b * d.ldmulv;
+      tm[u] = row[z];
+      tl[u] = row[d.Z + z];
+    }
 #pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        m += (s0 + u < d.nslab) ? tm[u] : 0.f;
-        l += (s0 + u < d.nslab) ? tl[u] : 0.f;
-      }
+    for (int u = 0; u < U; ++u) {
+      m += (s0 + u < s_hi) ? tm[u] : 0.f;
+      l += (s0 + u < s_hi) ? tl[u] : 0.f;
     }
-    m += d.bmu[z];
-    l += d.blv[z];
-    float var = expf(l);
-    float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
-    d.mu[(size_t)b * d.ldz + z] = m;
-    d.lv[(size_t)b * d.ldz + z] = l;
-    d.z[(size_t)b * d.ldz + z] = zz;
-    if (d.kld_mode == 0) {
-      acc += 1.f + l - m * m - var;
-    } else {
-      const float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : pm_row;
-      float dm = m - pm;
-      acc += 1.f + l - lpv - (dm * dm + var) / (pvar + 0.00001f);
-    }
-  }
-  acc = ssc_wave_sum(acc);
-  if (lane == 0) d.kld_acc[b] += d.w[b] * (-0.5f * acc);
-}
-
-__global__ void latent_prior_sample_kernel(const float* __restrict__ eps, int ldeps, const float* __restrict__ sent,
-                                           float pm_scale, float sd, int G, int Z, float* __restrict__ z, int ldz) {
-  int g = blockIdx.y;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Z) {   // pad columns of a 16-byte padded row are zeroed (the row is a K-segment of r4(Z) columns in the decode step)
-    if (i < ((Z + 3) & ~3) && i < ldz) z[(size_t)g * ldz + i] = 0.f;
-    return;
-  }
-  float pm = sent ? pm_scale * sent[g] : 0.f;
-  z[(size_t)g * ldz + i] = eps[(size_t)g * ldeps + i] * sd + pm;
-}
-
-// the same with a per-row, per-dimension prior mean (SENTIMENT_VAE = 2: the attention-pooled attribute means, updown_cell.py:160-163)
-// ... and, optionally, a per-element prior variance (a caller of _decode_step that hands its own prior, updown_captioner.py:371-381)
-__global__ void latent_prior_sample_pm_kernel(const float* __restrict__ eps, int ldeps, const float* __restrict__ pm, int ldpm,
-                                              const float* __restrict__ pv, int ldpv, const float* __restrict__ sent, float pm_scale,
-                                              float sd, int G, int Z, float* __restrict__ z, int ldz) {
-  int g = blockIdx.y;
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= Z) {
-    if (i < ((Z + 3) & ~3) && i < ldz) z[(size_t)g * ldz + i] = 0.f;
-    return;
-  }
-  const float m = pm ? pm[(size_t)g * ldpm + i] : (sent ? pm_scale * sent[g] : 0.f);
-  const float s = pv ? sqrtf(pv[(size_t)g * ldpv + i]) : sd;
-  z[(size_t)g * ldz + i] = eps[(size_t)g * ldeps + i] * s + m;
-}
-
-// latent_fwd_kernel for MANY partial slabs (the cdiv(H,16) partial products of lstm_fwd_p_kernel): one 256-thread workgroup per
-// row; the slab list is split into 256 / (64 ceil(Z/64)) contiguous parts that are summed in parallel (each in index order) and
-// combined in part order - fixed summation order, four times the loads in flight of the wave-per-row form.  Z <= 256.
-__global__ __launch_bounds__(256) void latent_fwd_wide_kernel(const ssc_latent_fwd_desc d) {
-  __shared__ float pm_[4][64], pl_[4][64], kl_[4];
-  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int Z = d.Z;
-  const int ZW = (Z + 63) / 64;            // waves per full z range (1, 2 or 4)
-  const int SP = 4 / ZW;                   // slab parts
-  const int zw = wave % ZW, part = wave / ZW;
-  const int z = zw * 64 + lane;
-  const int per = (d.nslab + SP - 1) / SP;
-  const int s_lo = part * per, s_hi = min(d.nslab, s_lo + per);
-  float m = 0.f, l = 0.f;
-  if (z < Z && ZW * SP == 4) {
-    for (int s0 = s_lo; s0 < s_hi; s0 += 16) {
-      float tm[16], tl[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const float* row = d.mulv + (size_t)min(s0 + u, s_hi - 1) * d.slab_stride + (size_t)b * d.ldmulv;
-        tm[u] = row[z];
-        tl[u] = row[Z + z];
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        m += (s0 + u < s_hi) ? tm[u] : 0.f;
-        l += (s0 + u < s_hi) ? tl[u] : 0.f;
-      }
-    }
-  }
-  pm_[wave][lane] = m;
-  pl_[wave][lane] = l;
-  __syncthreads();
-  float acc = 0.f;
-  if (part == 0 && z < Z) {
-    for (int p = 1; p < SP; ++p) { m += pm_[p * ZW + zw][lane]; l += pl_[p * ZW + zw][lane]; }
-    const float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : (d.sent ? d.pm_scale * d.sent[b] : 0.f);
-    const float pvar = d.prior_var, lpv = logf(pvar);
-    m += d.bmu[z];
-    l += d.blv[z];
-    const float var = expf(l);
-    const float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
-    d.mu[(size_t)b * d.ldz + z] = m;
-    d.lv[(size_t)b * d.ldz + z] = l;
-    d.z[(size_t)b * d.ldz + z] = zz;
-    if (d.kld_mode == 0) {
-      acc = 1.f + l - m * m - var;
-    } else {
-      const float dm = m - pm;
-      acc = 1.f + l - lpv - (dm * dm + var) / (pvar + 0.00001f);
-    }
-  }
-  acc = ssc_wave_sum(acc);
-  if (lane == 0) kl_[wave] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    float a = 0.f;
-    for (int w2 = 0; w2 < ZW; ++w2) a += kl_[w2];   // waves of part 0, in z order
-    d.kld_acc[b] += d.w[b] * (-0.5f * a);
   }
 }
 
-__global__ void latent_bwd_kernel(const ssc_latent_bwd_desc d) {
-  int b = blockIdx.y;
-  int z = blockIdx.x * blockDim.x + threadIdx.x;
-  if (z >= d.Z) return;
-  float k = d.gk[b] * d.w[b];
-  float m = d.mu[(size_t)b * d.ldz + z], l = d.lv[(size_t)b * d.ldz + z];
-  float dz = 0.f;
-  {
-    const int ns = d.nslab > 1 ? d.nslab : 1;
-    for (int s0 = 0; s0 < ns; s0 += 8) {
-      float t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = d.dz[(size_t)min(s0 + u, ns - 1) * d.slab_stride + (size_t)b * d.lddz + z];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) dz += (s0 + u < ns) ? t[u] : 0.f;
-    }
-  }
-  float e = d.eps[(size_t)b * d.ldeps + z];
-  float var = expf(l);
-  float dmu, dlv;
-  if (d.kld_mode == 0) {
-    dmu = dz + k * m;
-    dlv = dz * e * 0.5f * sqrtf(var) - 0.5f * k * (1.f - var);
-  } else {
-    float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : (d.sent ? d.pm_scale * d.sent[b] : 0.f);
-    float den = d.prior_var + 0.00001f;
-    dmu = dz + k * (m - pm) / den;
-    if (d.dpm) d.dpm[(size_t)b * d.lddpm + z] = -k * (m - pm) / den;
-    dlv = dz * e * 0.5f * sqrtf(var) - 0.5f * k * (1.f - var / den);
-  }
-  d.dmulv[(size_t)b * d.lddmulv + z] = dmu;
-  d.dmulv[(size_t)b * d.lddmulv + d.Z + z] = dlv;
-}
-
-// ---------------------------------------------------------------------------------------------
-// latent head with a free-bits floor on the KL (include/ssc.h: ssc_free_bits).  New kernels: lambda = 0 launches the ones above.
-// ---------------------------------------------------------------------------------------------
-// k_tbj = -0.5 * the bracket of latent_fwd_kernel (same expressions, same order: the sum over j of these is -0.5 times that
-// kernel's sum, exactly).  The forward and the mode-1 backward both form their gates from THIS function.
-__device__ __forceinline__ float latent_kl_elem(int kld_mode, float m, float l, float var, float pm, float lpv, float pvar) {
-  if (kld_mode == 0) return -0.5f * (1.f + l - m * m - var);
-  const float dm = m - pm;
-  return -0.5f * (1.f + l - lpv - (dm * dm + var) / (pvar + 0.00001f));
+// the summed (m, l) of element (b, z): biases, the sample, the three stores; returns the element's KL k_tbj
+__device__ __forceinline__ float latent_finish_elem(const ssc_latent_fwd_desc& d, int b, int z, float m, float l) {
+  const float pm = latent_prior_mean(d.pm, d.ldpm, d.sent, d.pm_scale, b, z);   // (before the stores: no load may be moved across them)
+  m += d.bmu[z];
+  l += d.blv[z];
+  const float var = expf(l);
+  const float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
+  d.mu[(size_t)b * d.ldz + z] = m;
+  d.lv[(size_t)b * d.ldz + z] = l;
+  d.z[(size_t)b * d.ldz + z] = zz;
+  return latent_kl_elem(d.kld_mode, m, l, var, pm, logf(d.prior_var), d.prior_var);
 }
 
 // what one (b, j) element adds: to the raw sum, to the floored sum (mode 1) and to the (B, lddim) accumulator (mode 3)
 template <int FB>
-__device__ __forceinline__ void latent_fb_elem(const ssc_free_bits& fb, float k, float wb, int b, int z, float& raw, float& flo) {
+__device__ __forceinline__ void latent_fb_elem(const ssc_latent_fwd_desc& d, const ssc_free_bits& fb, float k, int b, int z, float& raw,
+                                               float& flo) {
   raw += k;
   if (FB == 1) flo += k > fb.lambda ? k : fb.lambda;
-  if (FB == 3) fb.dim_acc[(size_t)b * fb.lddim + z] += wb * k;
+  if (FB == 3) fb.dim_acc[(size_t)b * fb.lddim + z] += d.w[b] * k;
 }
 
-// the row's sums (already reduced over j) into the accumulators
+// the row's sums (already reduced over j) into the accumulators; FB = 0 touches no field of fb.  (The step weight is read where
+// it is used, by the one lane that writes the row: read ahead of the slab loads it would hold them back by a memory round trip.)
 template <int FB>
-__device__ __forceinline__ void latent_fb_row(const ssc_latent_fwd_desc& d, const ssc_free_bits& fb, int b, float wb, float raw, float flo) {
+__device__ __forceinline__ void latent_fb_row(const ssc_latent_fwd_desc& d, const ssc_free_bits& fb, int b, float raw, float flo) {
+  const float wb = d.w[b];
+  if (FB == 0) {
+    d.kld_acc[b] += wb * raw;
+    return;
+  }
   fb.kld_raw[b] += wb * raw;
   if (FB == 1) d.kld_acc[b] += wb * flo;
   if (FB == 2) {
@@ -372,102 +236,78 @@ __device__ __forceinline__ void latent_fb_row(const ssc_latent_fwd_desc& d, cons
   }
 }
 
+// one wave per row, four rows per workgroup
 template <int FB>
-__global__ void latent_fwd_fb_kernel(const ssc_latent_fwd_desc d, const ssc_free_bits fb) {
-  int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  int lane = threadIdx.x & 63;
+__global__ void latent_fwd_kernel(const ssc_latent_fwd_desc d, const ssc_free_bits fb) {
+  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (b >= d.B) return;
-  const int Z = d.Z;
-  const float pm_row = d.sent ? d.pm_scale * d.sent[b] : 0.f;
-  const float pvar = d.prior_var, lpv = logf(pvar), wb = d.w[b];
   float raw = 0.f, flo = 0.f;
-  for (int z = lane; z < Z; z += 64) {
+  for (int z = lane; z < d.Z; z += 64) {
     float m = 0.f, l = 0.f;
-    for (int s0 = 0; s0 < d.nslab; s0 += 8) {   // (the slab order of latent_fwd_kernel)
-      float tm[8], tl[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const float* row = d.mulv + (size_t)min(s0 + u, d.nslab - 1) * d.slab_stride + (size_t)b * d.ldmulv;
-        tm[u] = row[z];
-        tl[u] = row[Z + z];
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        m += (s0 + u < d.nslab) ? tm[u] : 0.f;
-        l += (s0 + u < d.nslab) ? tl[u] : 0.f;
-      }
-    }
-    m += d.bmu[z];
-    l += d.blv[z];
-    const float var = expf(l);
-    const float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
-    d.mu[(size_t)b * d.ldz + z] = m;
-    d.lv[(size_t)b * d.ldz + z] = l;
-    d.z[(size_t)b * d.ldz + z] = zz;
-    const float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : pm_row;
-    latent_fb_elem<FB>(fb, latent_kl_elem(d.kld_mode, m, l, var, pm, lpv, pvar), wb, b, z, raw, flo);
+    latent_sum_slabs<8>(d, b, z, 0, d.nslab, m, l);
+    latent_fb_elem<FB>(d, fb, latent_finish_elem(d, b, z, m, l), b, z, raw, flo);
   }
   raw = ssc_wave_sum(raw);
   if (FB == 1) flo = ssc_wave_sum(flo);
-  if (lane == 0) latent_fb_row<FB>(d, fb, b, wb, raw, flo);
+  if (lane == 0) latent_fb_row<FB>(d, fb, b, raw, flo);
 }
 
-// the many-slab form (latent_fwd_wide_kernel's parts and their order)
+// The form for MANY partial slabs (the cdiv(H,16) partial products of lstm_fwd_p_kernel): one 256-thread workgroup per row; the
+// slab list is split into 256 / (64 ceil(Z/64)) contiguous parts that are summed in parallel (each in index order) and combined in
+// part order - fixed summation order, four times the loads in flight of the wave-per-row form.  Z <= 256.
 template <int FB>
-__global__ __launch_bounds__(256) void latent_fwd_wide_fb_kernel(const ssc_latent_fwd_desc d, const ssc_free_bits fb) {
+__global__ __launch_bounds__(256) void latent_fwd_wide_kernel(const ssc_latent_fwd_desc d, const ssc_free_bits fb) {
   __shared__ float pm_[4][64], pl_[4][64], kr_[4], kf_[4];
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int Z = d.Z;
-  const int ZW = (Z + 63) / 64;
-  const int SP = 4 / ZW;
+  const int ZW = (Z + 63) / 64;            // waves per full z range (1, 2 or 4)
+  const int SP = 4 / ZW;                   // slab parts
   const int zw = wave % ZW, part = wave / ZW;
   const int z = zw * 64 + lane;
   const int per = (d.nslab + SP - 1) / SP;
   const int s_lo = part * per, s_hi = min(d.nslab, s_lo + per);
-  const float wb = d.w[b];
   float m = 0.f, l = 0.f;
-  if (z < Z && ZW * SP == 4) {
-    for (int s0 = s_lo; s0 < s_hi; s0 += 16) {
-      float tm[16], tl[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        const float* row = d.mulv + (size_t)min(s0 + u, s_hi - 1) * d.slab_stride + (size_t)b * d.ldmulv;
-        tm[u] = row[z];
-        tl[u] = row[Z + z];
-      }
-#pragma unroll
-      for (int u = 0; u < 16; ++u) {
-        m += (s0 + u < s_hi) ? tm[u] : 0.f;
-        l += (s0 + u < s_hi) ? tl[u] : 0.f;
-      }
-    }
-  }
+  if (z < Z && ZW * SP == 4) latent_sum_slabs<16>(d, b, z, s_lo, s_hi, m, l);
   pm_[wave][lane] = m;
   pl_[wave][lane] = l;
   __syncthreads();
   float raw = 0.f, flo = 0.f;
   if (part == 0 && z < Z) {
     for (int p = 1; p < SP; ++p) { m += pm_[p * ZW + zw][lane]; l += pl_[p * ZW + zw][lane]; }
-    const float pm = d.pm ? d.pm[(size_t)b * d.ldpm + z] : (d.sent ? d.pm_scale * d.sent[b] : 0.f);
-    const float pvar = d.prior_var, lpv = logf(pvar);
-    m += d.bmu[z];
-    l += d.blv[z];
-    const float var = expf(l);
-    const float zz = d.eps[(size_t)b * d.ldeps + z] * sqrtf(var) + m;
-    d.mu[(size_t)b * d.ldz + z] = m;
-    d.lv[(size_t)b * d.ldz + z] = l;
-    d.z[(size_t)b * d.ldz + z] = zz;
-    latent_fb_elem<FB>(fb, latent_kl_elem(d.kld_mode, m, l, var, pm, lpv, pvar), wb, b, z, raw, flo);
+    latent_fb_elem<FB>(d, fb, latent_finish_elem(d, b, z, m, l), b, z, raw, flo);
   }
   raw = ssc_wave_sum(raw);
   if (FB == 1) flo = ssc_wave_sum(flo);
-  if (lane == 0) { kr_[wave] = raw; kf_[wave] = flo; }
+  if (lane == 0) {
+    kr_[wave] = raw;
+    if (FB == 1) kf_[wave] = flo;
+  }
   __syncthreads();
   if (tid == 0) {
     float r = 0.f, f = 0.f;
-    for (int w2 = 0; w2 < ZW; ++w2) { r += kr_[w2]; f += kf_[w2]; }   // waves of part 0, in z order
-    latent_fb_row<FB>(d, fb, b, wb, r, f);
+    for (int w2 = 0; w2 < ZW; ++w2) {   // waves of part 0, in z order
+      r += kr_[w2];
+      if (FB == 1) f += kf_[w2];
+    }
+    latent_fb_row<FB>(d, fb, b, r, f);
   }
+}
+
+// z = eps * sd + prior mean, per row g; pm: a per-row, per-dimension prior mean (SENTIMENT_VAE = 2: the attention-pooled attribute
+// means, updown_cell.py:160-163), pv: a per-element prior variance in place of sd^2 (a caller of _decode_step that hands its own
+// prior, updown_captioner.py:371-381); both optional
+__global__ void latent_prior_sample_pm_kernel(const float* __restrict__ eps, int ldeps, const float* __restrict__ pm, int ldpm,
+                                              const float* __restrict__ pv, int ldpv, const float* __restrict__ sent, float pm_scale,
+                                              float sd, int G, int Z, float* __restrict__ z, int ldz) {
+  int g = blockIdx.y;
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Z) {   // pad columns of a 16-byte padded row are zeroed (the row is a K-segment of r4(Z) columns in the decode step)
+    if (i < ((Z + 3) & ~3) && i < ldz) z[(size_t)g * ldz + i] = 0.f;
+    return;
+  }
+  const float m = latent_prior_mean(pm, ldpm, sent, pm_scale, g, i);
+  const float s = pv ? sqrtf(pv[(size_t)g * ldpv + i]) : sd;
+  z[(size_t)g * ldz + i] = eps[(size_t)g * ldeps + i] * s + m;
 }
 
 // mode 3 after the last step: one workgroup.  K_j over b in index order, the Z gates, then kld_b (one wave per row at a time)
@@ -490,32 +330,38 @@ __global__ __launch_bounds__(256) void latent_fb_finish_kernel(const float* __re
   }
 }
 
+// dz += the split-K slabs of the producing GEMM in index order, eight loads in flight
+__device__ __forceinline__ void latent_bwd_sum_slabs(const float* slabs, int n, size_t stride, size_t cell, float& dz) {
+  for (int s0 = 0; s0 < n; s0 += 8) {
+    float t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = slabs[(size_t)min(s0 + u, n - 1) * stride + cell];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) dz += (s0 + u < n) ? t[u] : 0.f;
+  }
+}
+
+// FB = 1..3: the KL part of dmu, dlv and dpm is multiplied by the element's gate (mode 1 forms it again from mu / lv with the
+// forward's latent_kl_elem, modes 2 and 3 read it); FB = 0 leaves k alone
 template <int FB>
-__global__ void latent_bwd_fb_kernel(const ssc_latent_bwd_desc d, const ssc_free_bits fb) {
+__global__ void latent_bwd_kernel(const ssc_latent_bwd_desc d, const ssc_free_bits fb) {
   int b = blockIdx.y;
   int z = blockIdx.x * blockDim.x + threadIdx.x;
   if (z >= d.Z) return;
   float k = d.gk[b] * d.w[b];
   float m = d.mu[(size_t)b * d.ldz + z], l = d.lv[(size_t)b * d.ldz + z];
   float dz = 0.f;
-  {
-    const int ns = d.nslab > 1 ? d.nslab : 1;
-    for (int s0 = 0; s0 < ns; s0 += 8) {
-      float t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = d.dz[(size_t)min(s0 + u, ns - 1) * d.slab_stride + (size_t)b * d.lddz + z];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) dz += (s0 + u < ns) ? t[u] : 0.f;
-    }
-  }
+  latent_bwd_sum_slabs(d.dz, d.nslab > 1 ? d.nslab : 1, d.slab_stride, (size_t)b * d.lddz + z, dz);
   float e = d.eps[(size_t)b * d.ldeps + z];
   float var = expf(l);
-  const float pm = d.kld_mode == 0 ? 0.f : (d.pm ? d.pm[(size_t)b * d.ldpm + z] : (d.sent ? d.pm_scale * d.sent[b] : 0.f));
-  bool open;
-  if (FB == 1) open = latent_kl_elem(d.kld_mode, m, l, var, pm, logf(d.prior_var), d.prior_var) > fb.lambda;
-  else if (FB == 2) open = fb.gate_step[b] != 0.f;
-  else open = fb.gate_dim[z] != 0.f;
-  k = open ? k : 0.f;   // a closed gate: the KL part is +0 times its factor, as with gk = 0
+  const float pm = d.kld_mode == 0 ? 0.f : latent_prior_mean(d.pm, d.ldpm, d.sent, d.pm_scale, b, z);
+  if (FB != 0) {
+    bool open;
+    if (FB == 1) open = latent_kl_elem(d.kld_mode, m, l, var, pm, logf(d.prior_var), d.prior_var) > fb.lambda;
+    else if (FB == 2) open = fb.gate_step[b] != 0.f;
+    else open = fb.gate_dim[z] != 0.f;
+    k = open ? k : 0.f;   // a closed gate: the KL part is +0 times its factor, as with gk = 0
+  }
   float dmu, dlv;
   if (d.kld_mode == 0) {
     dmu = dz + k * m;
@@ -530,20 +376,10 @@ __global__ void latent_bwd_fb_kernel(const ssc_latent_bwd_desc d, const ssc_free
   d.dmulv[(size_t)b * d.lddmulv + d.Z + z] = dlv;
 }
 
+
 // ---------------------------------------------------------------------------------------------
 // cross entropy over the vocabulary
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_reduce(float v, float* sh, bool is_max) {
-  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  v = is_max ? ssc_wave_max(v) : ssc_wave_sum(v);
-  __syncthreads();
-  if (lane == 0) sh[wv] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
-  return r;
-}
-
 __global__ void ce_fwd_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ targets,
                               const float* __restrict__ w, int V, float* __restrict__ lse, float* __restrict__ nllw) {
   __shared__ float sh[16];
@@ -555,10 +391,10 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, int ldl, const i
   const float* p = logits + (size_t)row * ldl;
   float mx = -INFINITY;
   for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, p[v]);
-  mx = block_reduce(mx, sh, true);
+  mx = ssc_block_reduce(mx, sh, true);
   float s = 0.f;
   for (int v = threadIdx.x; v < V; v += blockDim.x) s += expf(p[v] - mx);
-  s = block_reduce(s, sh, false);
+  s = ssc_block_reduce(s, sh, false);
   if (threadIdx.x == 0) {
     float l = mx + logf(s);
     lse[row] = l;
@@ -656,10 +492,10 @@ __global__ __launch_bounds__(256) void ce_fwd_smooth_kernel(const float* __restr
     d += ((x.x - r) + (x.y - r)) + ((x.z - r) + (x.w - r));
   }
   const int tail = head + (n4 << 2), ns = head + (V - tail);
-  for (int k = threadIdx.x; k < ns; k += 256) ce_online(p[k < head ? k : tail + (k - head)], r, m, s, d);
-  const float M = block_reduce(m, sh, true);
-  s = block_reduce(s * expf(m - M), sh, false);   // a thread without elements: m = -inf, s = 0 -> 0
-  d = block_reduce(d, sh, false);
+  for (int k = threadIdx.x; k < ns; k += 256) ce_online(p[ssc_row_split_col(k, head, tail)], r, m, s, d);
+  const float M = ssc_block_reduce(m, sh, true);
+  s = ssc_block_reduce(s * expf(m - M), sh, false);   // a thread without elements: m = -inf, s = 0 -> 0
+  d = ssc_block_reduce(d, sh, false);
   if (threadIdx.x == 0) {
     const float l = M + logf(s);
     const float nll = l - r;
@@ -683,7 +519,7 @@ __global__ __launch_bounds__(256) void ce_bwd_smooth_kernel(float* __restrict__ 
   const int tail = head + (n4 << 2), ns = head + (V - tail);
   if (coef == 0.f) {  // never reads the row: a padded target's logits may hold anything
     for (int i = threadIdx.x; i < n4; i += 256) p4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = threadIdx.x; k < ns; k += 256) p[k < head ? k : tail + (k - head)] = 0.f;
+    for (int k = threadIdx.x; k < ns; k += 256) p[ssc_row_split_col(k, head, tail)] = 0.f;
     return;
   }
   const float l = lse[row];
@@ -699,7 +535,7 @@ __global__ __launch_bounds__(256) void ce_bwd_smooth_kernel(float* __restrict__ 
     p4[i] = x;
   }
   for (int k = threadIdx.x; k < ns; k += 256) {
-    const int v = k < head ? k : tail + (k - head);
+    const int v = ssc_row_split_col(k, head, tail);
     p[v] = (expf(p[v] - l) - (v == tgt ? keep : 0.f) - eps_over_v) * coef;
   }
 }
@@ -711,10 +547,10 @@ __global__ void log_softmax_kernel(const float* __restrict__ logits, int ldl, in
   float* o = out + (size_t)row * ldo;
   float mx = -INFINITY;
   for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, p[v]);
-  mx = block_reduce(mx, sh, true);
+  mx = ssc_block_reduce(mx, sh, true);
   float s = 0.f;
   for (int v = threadIdx.x; v < V; v += blockDim.x) s += expf(p[v] - mx);
-  s = block_reduce(s, sh, false);
+  s = ssc_block_reduce(s, sh, false);
   float l = mx + logf(s);
   for (int v = threadIdx.x; v < V; v += blockDim.x) o[v] = p[v] - l;
 }
@@ -850,7 +686,7 @@ __global__ void sq_norm_partial_kernel(const float* __restrict__ g, size_t n, fl
       s += v * v;
     }
   }
-  s = block_reduce(s, sh, false);
+  s = ssc_block_reduce(s, sh, false);
   if (threadIdx.x == 0) scratch[blockIdx.x] = s;
 }
 
@@ -858,7 +694,7 @@ __global__ void sq_norm_final_kernel(const float* __restrict__ scratch, int nb, 
   __shared__ float sh[16];
   float s = 0.f;
   for (int i = threadIdx.x; i < nb; i += blockDim.x) s += scratch[i];
-  s = block_reduce(s, sh, false);
+  s = ssc_block_reduce(s, sh, false);
   if (threadIdx.x == 0) *out = s;
 }
 
@@ -975,24 +811,88 @@ extern "C" int ssc_embed_scatter_add(float* dtable, int ldt, const int64_t* ids,
   return SSC_OK;
 }
 
-extern "C" int ssc_latent_fwd(const ssc_latent_fwd_desc* d, void* stream) {
-  if (!d || d->B <= 0 || d->Z <= 0 || !d->mulv || d->nslab < 1 || !d->bmu || !d->blv || !d->eps || !d->w || !d->mu ||
-      !d->lv || !d->z || !d->kld_acc)
-    return SSC_EINVAL;
-  const int zw = (d->Z + 63) / 64;
-  if (d->nslab > 16 && (zw == 1 || zw == 2 || zw == 4))
-    SSC_LAUNCH(latent_fwd_wide_kernel, dim3(d->B), dim3(256), 0, S(stream), *d);
+// lambda is a finite number >= 0 and, when positive, the mode one of 1..3 (NaN fails the first comparison)
+static bool free_bits_ok(const ssc_free_bits* fb) {
+  if (!fb || !(fb->lambda >= 0.f) || !(fb->lambda <= 3.402823466e38f)) return false;
+  return fb->lambda == 0.f || (fb->mode >= 1 && fb->mode <= 3);
+}
+// the kernels' template argument: 0 (lambda = 0: the plain kernels, no other field of fb is read or written) or the mode
+static int free_bits_form(const ssc_free_bits* fb) { return fb->lambda == 0.f ? 0 : fb->mode; }
+
+static bool latent_fwd_ok(const ssc_latent_fwd_desc* d) {
+  return d && d->B > 0 && d->Z > 0 && d->mulv && d->nslab >= 1 && d->bmu && d->blv && d->eps && d->w && d->mu && d->lv && d->z &&
+         d->kld_acc;
+}
+static bool latent_bwd_ok(const ssc_latent_bwd_desc* d) {
+  return d && d->B > 0 && d->Z > 0 && d->dz && d->eps && d->mu && d->lv && d->w && d->gk && d->dmulv;
+}
+
+template <int FB>
+static void latent_fwd_form(const ssc_latent_fwd_desc& d, const ssc_free_bits& fb, hipStream_t st) {
+  const int zw = (d.Z + 63) / 64;
+  if (d.nslab > 16 && (zw == 1 || zw == 2 || zw == 4))
+    SSC_LAUNCH(latent_fwd_wide_kernel<FB>, dim3(d.B), dim3(256), 0, st, d, fb);
   else
-    SSC_LAUNCH(latent_fwd_kernel, dim3(ssc_cdiv(d->B, 4)), dim3(256), 0, S(stream), *d);
+    SSC_LAUNCH(latent_fwd_kernel<FB>, dim3(ssc_cdiv(d.B, 4)), dim3(256), 0, st, d, fb);
+}
+static int latent_fwd_launch(const ssc_latent_fwd_desc& d, const ssc_free_bits& fb, int form, hipStream_t st) {
+  if (form == 0) latent_fwd_form<0>(d, fb, st);
+  else if (form == 1) latent_fwd_form<1>(d, fb, st);
+  else if (form == 2) latent_fwd_form<2>(d, fb, st);
+  else latent_fwd_form<3>(d, fb, st);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+static int latent_bwd_launch(const ssc_latent_bwd_desc& d, const ssc_free_bits& fb, int form, hipStream_t st) {
+  const dim3 grid(ssc_cdiv(d.Z, 64), d.B), block(64);
+  if (form == 0) SSC_LAUNCH(latent_bwd_kernel<0>, grid, block, 0, st, d, fb);
+  else if (form == 1) SSC_LAUNCH(latent_bwd_kernel<1>, grid, block, 0, st, d, fb);
+  else if (form == 2) SSC_LAUNCH(latent_bwd_kernel<2>, grid, block, 0, st, d, fb);
+  else SSC_LAUNCH(latent_bwd_kernel<3>, grid, block, 0, st, d, fb);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }
 
+extern "C" int ssc_latent_fwd(const ssc_latent_fwd_desc* d, void* stream) {
+  if (!latent_fwd_ok(d)) return SSC_EINVAL;
+  return latent_fwd_launch(*d, ssc_free_bits{}, 0, S(stream));
+}
+
+extern "C" int ssc_latent_fwd_fb(const ssc_latent_fwd_desc* d, const ssc_free_bits* fb, void* stream) {
+  if (!free_bits_ok(fb) || !latent_fwd_ok(d)) return SSC_EINVAL;
+  const int form = free_bits_form(fb);
+  if (form != 0 && (!fb->kld_raw || (form == 2 && !fb->gate_step) || (form == 3 && (!fb->dim_acc || fb->lddim < d->Z))))
+    return SSC_EINVAL;
+  return latent_fwd_launch(*d, *fb, form, S(stream));
+}
+
+extern "C" int ssc_latent_fb_finish(const float* dim_acc, int lddim, int B, int Z, float lambda, float* kdim, float* gate_dim,
+                                    float* kld, void* stream) {
+  if (!dim_acc || !kdim || !gate_dim || !kld || B <= 0 || Z <= 0 || lddim < Z || !(lambda >= 0.f) || !(lambda <= 3.402823466e38f))
+    return SSC_EINVAL;
+  SSC_LAUNCH(latent_fb_finish_kernel, dim3(1), dim3(256), 0, S(stream), dim_acc, lddim, B, Z, lambda, kdim, gate_dim, kld);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
+extern "C" int ssc_latent_bwd(const ssc_latent_bwd_desc* d, void* stream) {
+  if (!latent_bwd_ok(d)) return SSC_EINVAL;
+  return latent_bwd_launch(*d, ssc_free_bits{}, 0, S(stream));
+}
+
+extern "C" int ssc_latent_bwd_fb(const ssc_latent_bwd_desc* d, const ssc_free_bits* fb, void* stream) {
+  if (!free_bits_ok(fb) || !latent_bwd_ok(d)) return SSC_EINVAL;
+  const int form = free_bits_form(fb);
+  if ((form == 2 && !fb->gate_step) || (form == 3 && !fb->gate_dim)) return SSC_EINVAL;
+  return latent_bwd_launch(*d, *fb, form, S(stream));
+}
+
+// the _pm kernel without a per-element mean or variance: the same expression, the same zeroed pad columns
 extern "C" int ssc_latent_prior_sample(const float* eps, int ldeps, const float* sent, float pm_scale, float prior_var,
                                        int G, int Z, float* z, int ldz, void* stream) {
   if (!eps || !z || G <= 0 || Z <= 0) return SSC_EINVAL;
-  SSC_LAUNCH(latent_prior_sample_kernel, dim3(ssc_cdiv((Z + 3) & ~3, 64), G), dim3(64), 0, S(stream), eps, ldeps, sent,
-                     pm_scale, sqrtf(prior_var), G, Z, z, ldz);
+  SSC_LAUNCH(latent_prior_sample_pm_kernel, dim3(ssc_cdiv((Z + 3) & ~3, 64), G), dim3(64), 0, S(stream), eps, ldeps,
+             (const float*)nullptr, 0, (const float*)nullptr, 0, sent, pm_scale, sqrtf(prior_var), G, Z, z, ldz);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }
@@ -1007,65 +907,6 @@ extern "C" int ssc_latent_prior_sample_pm(const float* eps, int ldeps, const flo
   return SSC_OK;
 }
 
-extern "C" int ssc_latent_bwd(const ssc_latent_bwd_desc* d, void* stream) {
-  if (!d || d->B <= 0 || d->Z <= 0 || !d->dz || !d->eps || !d->mu || !d->lv || !d->w || !d->gk || !d->dmulv)
-    return SSC_EINVAL;
-  SSC_LAUNCH(latent_bwd_kernel, dim3(ssc_cdiv(d->Z, 64), d->B), dim3(64), 0, S(stream), *d);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-// lambda is a finite number >= 0 and, when positive, the mode one of 1..3 (NaN fails the first comparison)
-static bool free_bits_ok(const ssc_free_bits* fb) {
-  if (!fb || !(fb->lambda >= 0.f) || !(fb->lambda <= 3.402823466e38f)) return false;
-  return fb->lambda == 0.f || (fb->mode >= 1 && fb->mode <= 3);
-}
-
-extern "C" int ssc_latent_fwd_fb(const ssc_latent_fwd_desc* d, const ssc_free_bits* fb, void* stream) {
-  if (!free_bits_ok(fb)) return SSC_EINVAL;
-  if (fb->lambda == 0.f) return ssc_latent_fwd(d, stream);
-  if (!d || d->B <= 0 || d->Z <= 0 || !d->mulv || d->nslab < 1 || !d->bmu || !d->blv || !d->eps || !d->w || !d->mu ||
-      !d->lv || !d->z || !d->kld_acc)
-    return SSC_EINVAL;
-  if (!fb->kld_raw || (fb->mode == 2 && !fb->gate_step) || (fb->mode == 3 && (!fb->dim_acc || fb->lddim < d->Z))) return SSC_EINVAL;
-  const int zw = (d->Z + 63) / 64;
-  const bool wide = d->nslab > 16 && (zw == 1 || zw == 2 || zw == 4);   // (the choice of ssc_latent_fwd)
-  const dim3 grid(wide ? d->B : ssc_cdiv(d->B, 4)), block(256);
-#define SSC_FB_FWD(FB) \
-  do { \
-    if (wide) SSC_LAUNCH(latent_fwd_wide_fb_kernel<FB>, grid, block, 0, S(stream), *d, *fb); \
-    else SSC_LAUNCH(latent_fwd_fb_kernel<FB>, grid, block, 0, S(stream), *d, *fb); \
-  } while (0)
-  if (fb->mode == 1) SSC_FB_FWD(1);
-  else if (fb->mode == 2) SSC_FB_FWD(2);
-  else SSC_FB_FWD(3);
-#undef SSC_FB_FWD
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-extern "C" int ssc_latent_fb_finish(const float* dim_acc, int lddim, int B, int Z, float lambda, float* kdim, float* gate_dim,
-                                    float* kld, void* stream) {
-  if (!dim_acc || !kdim || !gate_dim || !kld || B <= 0 || Z <= 0 || lddim < Z || !(lambda >= 0.f) || !(lambda <= 3.402823466e38f))
-    return SSC_EINVAL;
-  SSC_LAUNCH(latent_fb_finish_kernel, dim3(1), dim3(256), 0, S(stream), dim_acc, lddim, B, Z, lambda, kdim, gate_dim, kld);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-extern "C" int ssc_latent_bwd_fb(const ssc_latent_bwd_desc* d, const ssc_free_bits* fb, void* stream) {
-  if (!free_bits_ok(fb)) return SSC_EINVAL;
-  if (fb->lambda == 0.f) return ssc_latent_bwd(d, stream);
-  if (!d || d->B <= 0 || d->Z <= 0 || !d->dz || !d->eps || !d->mu || !d->lv || !d->w || !d->gk || !d->dmulv)
-    return SSC_EINVAL;
-  if ((fb->mode == 2 && !fb->gate_step) || (fb->mode == 3 && !fb->gate_dim)) return SSC_EINVAL;
-  const dim3 grid(ssc_cdiv(d->Z, 64), d->B), block(64);
-  if (fb->mode == 1) SSC_LAUNCH(latent_bwd_fb_kernel<1>, grid, block, 0, S(stream), *d, *fb);
-  else if (fb->mode == 2) SSC_LAUNCH(latent_bwd_fb_kernel<2>, grid, block, 0, S(stream), *d, *fb);
-  else SSC_LAUNCH(latent_bwd_fb_kernel<3>, grid, block, 0, S(stream), *d, *fb);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
 
 // lse must hold 2*T*B floats: [lse | w*nll]
 extern "C" int ssc_ce_fwd(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T,
@@ -1088,25 +929,11 @@ extern "C" int ssc_ce_bwd(float* logits, int ldl, const int64_t* targets, const 
   return SSC_OK;
 }
 
-namespace {
-inline bool ce_eps_ok(float eps) { return eps >= 0.f && eps < 1.f; }   // false for NaN
-// how the smoothing kernels walk a row (see ce_online): with 16-byte rows every row shares the first row's misalignment
-inline void ce_row_split(const float* logits, int ldl, int V, int* head, int* n4) {
-  *head = V;
-  *n4 = 0;
-  if ((ldl & 3) != 0) return;
-  const int h = (int)(((16u - (unsigned)((uintptr_t)logits & 15u)) & 15u) >> 2);
-  if (h >= V) return;
-  *head = h;
-  *n4 = (V - h) >> 2;
-}
-}  // namespace
-
 // the three blocks [lse], [w*row(eps)], [w*row(0)] (T*B floats each) given one by one
 int ssc_ce_fwd_smooth_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
                              int V, float eps, float* lse, float* nllw, float* nllw0, float* loss, float* nll, hipStream_t st) {
   if (!logits || !targets || !w || !nvalid || !lse || !nllw || !nllw0 || !loss || T <= 0 || B <= 0 || V <= 0 || ldl < V ||
-      !ce_eps_ok(eps))
+      !ssc_ce_eps_ok(eps))
     return SSC_EINVAL;
   if (((uintptr_t)logits & 3u) != 0) return SSC_EALIGN;
   const int rows = T * B;
@@ -1115,7 +942,7 @@ int ssc_ce_fwd_smooth_blocks(const float* logits, int ldl, const int64_t* target
     SSC_CHECK_LAUNCH();
   } else {
     int head, n4;
-    ce_row_split(logits, ldl, V, &head, &n4);
+    ssc_row_split(logits, ldl, nullptr, 0, V, &head, &n4);
     SSC_LAUNCH(ce_fwd_smooth_kernel, dim3(rows), dim3(256), 0, st, logits, ldl, targets, w, V, head, n4,
                (float)((double)eps / V), lse, nllw, nllw0);
     SSC_CHECK_LAUNCH();
@@ -1136,14 +963,14 @@ extern "C" int ssc_ce_fwd_smooth(const float* logits, int ldl, const int64_t* ta
 
 extern "C" int ssc_ce_bwd_smooth(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid,
                                  const float* lse, const float* gl, int T, int B, int V, float eps, void* stream) {
-  if (!logits || !targets || !w || !nvalid || !lse || !gl || T <= 0 || B <= 0 || V <= 0 || ldl < V || !ce_eps_ok(eps))
+  if (!logits || !targets || !w || !nvalid || !lse || !gl || T <= 0 || B <= 0 || V <= 0 || ldl < V || !ssc_ce_eps_ok(eps))
     return SSC_EINVAL;
   if (((uintptr_t)logits & 3u) != 0) return SSC_EALIGN;
   if (eps == 0.f) {
     SSC_LAUNCH(ce_bwd_kernel, dim3(T * B), dim3(256), 0, S(stream), logits, ldl, targets, w, nvalid, lse, gl, B, V);
   } else {
     int head, n4;
-    ce_row_split(logits, ldl, V, &head, &n4);
+    ssc_row_split(logits, ldl, nullptr, 0, V, &head, &n4);
     SSC_LAUNCH(ce_bwd_smooth_kernel, dim3(T * B), dim3(256), 0, S(stream), logits, ldl, targets, w, nvalid, lse, gl, B, V, head,
                n4, 1.f - eps, (float)((double)eps / V));
   }

@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include "decode_loop.h"
+#include "latent_common.h"
 #include "ssc_radix.h"
 
 namespace {
@@ -178,8 +179,7 @@ template <int NJ>
 __global__ __launch_bounds__(64) void posterior_rows_kernel(const ssc_posterior_rows_desc d) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int Z = d.Z, B = d.B;
-  const float pv = d.prior_var, lpv = logf(pv), pvk = pv + 0.00001f;   // (pvk: the training KL's denominator, as latent_fwd_kernel)
-  const float pm_row = d.sent ? d.pm_scale * d.sent[b] : 0.f;
+  const float pv = d.prior_var, lpv = logf(pv);
   const bool steps = d.step_kl || d.step_ratio;   // (wave-uniform)
   float kd[NJ];
 #pragma unroll
@@ -195,6 +195,7 @@ __global__ __launch_bounds__(64) void posterior_rows_kernel(const ssc_posterior_
       }
       continue;
     }
+    const float* pm_t = d.pm ? d.pm + (size_t)t * B * d.ldpm : nullptr;   // (this step's (B, ldpm) block)
     float sk = 0.f, sr = 0.f;
 #pragma unroll
     for (int k = 0; k < NJ; ++k) {
@@ -202,16 +203,10 @@ __global__ __launch_bounds__(64) void posterior_rows_kernel(const ssc_posterior_
       if (j < Z) {
         const float m = d.mu[r * d.ldz + j], l = d.lv[r * d.ldz + j], zz = d.z[r * d.ldz + j];
         const float e = d.eps[r * d.ldeps + j];
-        const float pm = d.pm ? d.pm[r * d.ldpm + j] : pm_row;
+        const float pm = latent_prior_mean(pm_t, d.ldpm, d.sent, d.pm_scale, b, j);
         const float dz = zz - pm;
         const float rt = 0.5f * (e * e + l - lpv - dz * dz / pv);
-        float kt;
-        if (d.kld_mode == 0) {
-          kt = -0.5f * (1.f + l - m * m - expf(l));
-        } else {
-          const float dm = m - pm;
-          kt = -0.5f * (1.f + l - lpv - (dm * dm + expf(l)) / pvk);
-        }
+        const float kt = latent_kl_elem(d.kld_mode, m, l, expf(l), pm, lpv, pv);   // (the training KL: the forward's function)
         kd[k] += w * kt;
         racc += w * rt;
         sk += kt;

@@ -60,6 +60,37 @@ __device__ __forceinline__ float ssc_wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+// the sum or maximum of v over the workgroup (a multiple of 64 threads, sh: one float per wave), the same in every thread: wave
+// butterflies, then the waves in index order.  Two barriers, so calls may follow one another on the same sh.
+__device__ __forceinline__ float ssc_block_reduce(float v, float* sh, bool is_max) {
+  int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  v = is_max ? ssc_wave_max(v) : ssc_wave_sum(v);
+  __syncthreads();
+  if (lane == 0) sh[wv] = v;
+  __syncthreads();
+  float r = sh[0];
+  for (int i = 1; i < nw; ++i) r = is_max ? fmaxf(r, sh[i]) : r + sh[i];
+  return r;
+}
+
+// How the cross-entropy kernels that stream a row (pointwise.hip: label smoothing, distill.hip: with a teacher's row b beside it)
+// walk it: elements [0, head) and [head + 4 * n4, V) one by one, the n4 groups of four in between as 16-byte accesses.  With
+// leading dimensions that are multiples of 4 every row shares the first row's misalignment; a second matrix must share it too.
+// head = V, n4 = 0 is the scalar path throughout.
+static inline void ssc_row_split(const float* a, int lda, const float* b, int ldb, int V, int* head, int* n4) {
+  *head = V;
+  *n4 = 0;
+  if ((lda & 3) != 0) return;
+  if (b && ((ldb & 3) != 0 || ((uintptr_t)a & 15u) != ((uintptr_t)b & 15u))) return;
+  const int h = (int)(((16u - (unsigned)((uintptr_t)a & 15u)) & 15u) >> 2);
+  if (h >= V) return;
+  *head = h;
+  *n4 = (V - h) >> 2;
+}
+// the column of the k-th element of a split row's scalar part (k < head + V - tail, tail = head + 4 * n4)
+__device__ __forceinline__ int ssc_row_split_col(int k, int head, int tail) { return k < head ? k : tail + (k - head); }
+static inline bool ssc_ce_eps_ok(float eps) { return eps >= 0.f && eps < 1.f; }   // the label-smoothing weight; false for NaN
+
 __device__ __forceinline__ float ssc_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 // tanh x = 1 - 2 / (1 + e^{2x}) on the hardware exp2 / rcp (v_exp_f32, v_rcp_f32: ~1 ulp each): absolute error < 3e-7 everywhere,
 // exact limits (+-1) for large |x|.  Used where a kernel is bound by its tanh count (attention logits: G*R*A per step - 138 M

@@ -73,9 +73,10 @@ def floor_for(k, w, mode, select=None):
 # ---- 1. kernels -------------------------------------------------------------------------------------------------------------
 T_K = 4
 # (B, Z, nslab, kld_mode, per-element prior mean and its gradient): a lane round; the 8-slab unroll; rows that do not fill the
-# block's four waves; the many-slab form at one wave per row width and at four; a width that form declines
+# block's four waves; the many-slab form at one wave per row width and at four; a width that form declines; that form at two waves
+# per row width, where each of its two parts of 20 slabs completes a full round of 16 loads and then a remainder
 KSHAPES = [(1, 5, 1, 0, False), (3, 64, 3, 1, False), (5, 100, 9, 1, False), (2, 64, 17, 0, False), (4, 200, 20, 2, True),
-           (4, 150, 20, 2, False)]
+           (4, 150, 20, 2, False), (3, 128, 40, 1, False)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -113,7 +114,8 @@ def kcase(B, Z, nslab, kmode, has_pm, mode):
     dzs = dz.double().sum(1)[..., :Z]
     want_dmu = dzs + dmu_k
     want_dlv = dzs * eps.double() * 0.5 * (0.5 * l).exp() + dlv_k
-    return dict(B=B, Z=Z, nslab=nslab, kmode=kmode, has_pm=has_pm, mode=mode, w=w, sent=sent, pm=pm, prior_var=prior_var, bmu=bmu,
+    return dict(B=B, Z=Z, nslab=nslab, kmode=kmode, has_pm=has_pm, mode=mode, w=w, sent=sent, pm=pm, prior_var=prior_var,
+                prior_mean=prior_mean, bmu=bmu,
                 blv=blv, slabs=slabs, eps=eps, m=m, l=l, z=z, k=k, lam=lam, kld=kld, raw=fr.raw(k, w), gate=gate, K=K, dz=dz, gk=gk,
                 dmu=want_dmu, dlv=want_dlv, dpm=dpm_k)
 
@@ -241,6 +243,33 @@ def test_kernels_with_lambda_zero_are_the_plain_kernels(B, Z, nslab, kmode, has_
     for name in ("mu", "lv", "z", "kld", "dmulv", "dpm"):
         assert torch.equal(bits(a[name]), bits(b[name])), name
     assert bool((a["raw"] == 0).all()) and bool(torch.isnan(a["gate_step"]).all())      # nothing of the struct is written
+
+
+@pytest.mark.parametrize("B,Z,nslab,kmode,has_pm", KSHAPES)
+def test_plain_kernels_match_float64(B, Z, nslab, kmode, has_pm):
+    """ssc_latent_fwd / ssc_latent_bwd against the reference with every gate open: the raw KL and its whole gradient."""
+    c = kcase(B, Z, nslab, kmode, has_pm, 1)
+    out = run_kernels(c, 0.0, plain=True)
+    for name in ("mu", "lv", "z"):
+        assert bool((out[name][:, :, Z:] == POISON).all()), name
+        assert maxdiff(out[name][:, :, :Z], c[{"mu": "m", "lv": "l", "z": "z"}[name]]) <= 1e-5
+    every = torch.ones(T_K, B, Z, dtype=torch.bool)
+    dmu_k, dlv_k, dpm_k = fr.dlatent(c["m"], c["l"], c["prior_mean"], c["prior_var"], kmode, c["w"], c["gk"], every)
+    dzs = c["dz"].double().sum(1)[..., :Z]
+    want_dmu, want_dlv = dzs + dmu_k, dzs * c["eps"].double() * 0.5 * (0.5 * c["l"]).exp() + dlv_k
+    dm, dl = out["dmulv"][:, :, :Z].cpu(), out["dmulv"][:, :, Z:2 * Z].cpu()
+    print(f"B={B} Z={Z} nslab={nslab} kld_mode={kmode} plain: kld err {maxdiff(out['kld'], c['raw']):.3e} (tol {kl_tol(c['raw']):.3e}), "
+          f"dmu err {maxdiff(dm, want_dmu):.3e} (tol {grad_tol(want_dmu):.3e}), dlv err {maxdiff(dl, want_dlv):.3e} "
+          f"(tol {grad_tol(want_dlv):.3e})")
+    assert maxdiff(out["kld"], c["raw"]) <= kl_tol(c["raw"])
+    assert maxdiff(dm, want_dmu) <= grad_tol(want_dmu)
+    assert maxdiff(dl, want_dlv) <= grad_tol(want_dlv)
+    assert bool((out["dmulv"][:, :, 2 * Z:] == POISON).all())
+    if has_pm:
+        print(f"  dpm err {maxdiff(out['dpm'][:, :, :Z], dpm_k):.3e} (tol {grad_tol(dpm_k):.3e})")
+        assert maxdiff(out["dpm"][:, :, :Z], dpm_k) <= grad_tol(dpm_k)
+        assert bool((out["dpm"][:, :, Z:] == POISON).all())
+    assert bool((out["raw"] == 0).all()) and bool(torch.isnan(out["gate_step"]).all())  # (the plain entries take no struct)
 
 
 # ---- 2. train step ----------------------------------------------------------------------------------------------------------
