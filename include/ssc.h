@@ -246,6 +246,7 @@ int ssc_lstm_bwd_x(const ssc_lstm_bwd_desc* d, const float* x, int ldx, const fl
  * (attention.py:78-95) + allennlp masked_softmax + the weighted sum (updown_cell.py:156-158).
  *   logit[g,r] = wa . tanh(q[g] + pv[img(g),r]);  alpha = masked_softmax(logit, mask[img(g)])
  *   att[g,:]  = sum_r alpha[g,r] feats[img(g),r,:]          img(g) = g / rows_per_image
+ * Every entry but ssc_attn_logits takes G <= 65535 (the rows are the grid's second dimension): SSC_EINVAL and no launch beyond.
  * ---------------------------------------------------------------------------------------------- */
 int ssc_attn_logits(const float* q, int ldq, const float* pv, const float* wa, int G, int R, int A, int rows_per_image,
                     float* logits, void* stream);
@@ -412,6 +413,7 @@ int ssc_colsum2(const float* X, int ldx, int rows, int N, const float* wrow, flo
 /* dst[i] = src[i*stride]: one weight column made contiguous (the rank-1 sentiment column, updown_cell.py:181-184) */
 int ssc_copy_strided(const float* src, size_t stride, int n, float* dst, void* stream);
 /* y = tanh(x + bias) (tied output projection, updown_captioner.py:115-117) and its backward dy*(1-y^2) */
+/* both: SSC_EINVAL and no launch for a leading dimension below N or rows > 65535 (rows are the grid's second dimension) */
 int ssc_bias_tanh(float* x, int ldx, int rows, int N, const float* bias, void* stream);
 int ssc_tanh_bwd(float* dy, int lddy, const float* y, int ldy, int rows, int N, void* stream);
 int ssc_fill(float* p, size_t n, float v, void* stream);

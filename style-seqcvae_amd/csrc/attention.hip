@@ -150,6 +150,7 @@ __device__ __forceinline__ void wave_masked_softmax(const float* __restrict__ l,
 }
 
 constexpr int MAXR_LANE = 4;  // R <= 256
+constexpr int ATTN_MAXG = 65535;  // rows g ride on gridDim.y in the apply, pool and backward kernels: more is SSC_EINVAL, not an invalid grid
 
 // One wave per (row, 256-float feature chunk).  (A four-wave form - regions split over the waves of a 256-thread workgroup,
 // partial sums through LDS - was measured in round 2: no gain at the train shape, 6.4 us either way, and 93 vs 60 us at the
@@ -380,7 +381,7 @@ extern "C" int ssc_attn_logits(const float* q, int ldq, const float* pv, const f
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st) {
   if (!q || !pv || !wa || !mask || !alpha || !logits || !rows || !row_count || G <= 0 || R <= 0 || A <= 0 || A > ATTN_MAXA ||
-      rows_per_image <= 0 || ldq < A || R > 64 * MAXR_LANE)
+      rows_per_image <= 0 || ldq < A || R > 64 * MAXR_LANE || G > ATTN_MAXG)
     return SSC_EINVAL;
   SSC_LAUNCH(attn_logits_kernel, dim3(G * ssc_cdiv(R, ATTN_RG)), dim3(256), 0, st, q, ldq, 1, (size_t)0, (float*)nullptr, 0, pv, wa,
              G, R, A, rows_per_image, logits, rows, row_count);
@@ -395,7 +396,7 @@ extern "C" int ssc_attn_fwd(const float* q, int ldq, const float* pv, const floa
                             const float* feats, int G, int R, int A, int F, int rows_per_image, float* logits,
                             float* alpha, float* att, int ldatt, void* stream) {
   if (!mask || !feats || !alpha || !att || !logits || F <= 0 || ldatt < F) return SSC_EINVAL;
-  if (R > 64 * MAXR_LANE) return SSC_EINVAL;
+  if (R > 64 * MAXR_LANE || G > ATTN_MAXG) return SSC_EINVAL;
   SSC_TRY(ssc_attn_logits(q, ldq, pv, wa, G, R, A, rows_per_image, logits, stream));
   SSC_LAUNCH(attn_apply_kernel, dim3(ssc_cdiv(F, 256), G), dim3(64), 0, (hipStream_t)stream, logits, mask, feats,
                      G, R, F, rows_per_image, alpha, att, ldatt, (const float*)nullptr, 0, (float*)nullptr, 0);
@@ -405,7 +406,7 @@ extern "C" int ssc_attn_fwd(const float* q, int ldq, const float* pv, const floa
 
 extern "C" int ssc_attn_weights(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                                 int rows_per_image, float* logits, float* alpha, void* stream) {
-  if (!mask || !alpha || !logits || R > 64 * MAXR_LANE) return SSC_EINVAL;
+  if (!mask || !alpha || !logits || R > 64 * MAXR_LANE || G > ATTN_MAXG) return SSC_EINVAL;
   SSC_TRY(ssc_attn_logits(q, ldq, pv, wa, G, R, A, rows_per_image, logits, stream));
   SSC_LAUNCH(attn_apply_kernel, dim3(1, G), dim3(64), 0, (hipStream_t)stream, logits, mask, (const float*)nullptr, G, R, 4,
              rows_per_image, alpha, (float*)nullptr, 0, (const float*)nullptr, 0, (float*)nullptr, 0);
@@ -418,7 +419,7 @@ extern "C" int ssc_attn_fwd_pool(const float* q, int ldq, const float* pv, const
                                  float* alpha, float* att, int ldatt, const float* obj, int D, float* pool, int ldpool,
                                  void* stream) {
   if (!mask || !feats || !alpha || !att || !logits || F <= 0 || ldatt < F) return SSC_EINVAL;
-  if (!obj || !pool || D <= 0 || ldpool < D || R > 64 * MAXR_LANE) return SSC_EINVAL;
+  if (!obj || !pool || D <= 0 || ldpool < D || R > 64 * MAXR_LANE || G > ATTN_MAXG) return SSC_EINVAL;
   SSC_TRY(ssc_attn_logits(q, ldq, pv, wa, G, R, A, rows_per_image, logits, stream));
   SSC_LAUNCH(attn_apply_kernel, dim3(ssc_cdiv(F, 256) + ssc_cdiv(ldpool, 256), G), dim3(64), 0, (hipStream_t)stream, logits, mask,
              feats, G, R, F, rows_per_image, alpha, att, ldatt, obj, D, pool, ldpool);
@@ -428,7 +429,7 @@ extern "C" int ssc_attn_fwd_pool(const float* q, int ldq, const float* pv, const
 
 extern "C" int ssc_attn_pool(const float* alpha, const float* x, int G, int R, int D, int rows_per_image, float* out, int ldo,
                              void* stream) {
-  if (!alpha || !x || !out || G <= 0 || R <= 0 || D <= 0 || rows_per_image <= 0 || ldo < D) return SSC_EINVAL;
+  if (!alpha || !x || !out || G <= 0 || G > ATTN_MAXG || R <= 0 || D <= 0 || rows_per_image <= 0 || ldo < D) return SSC_EINVAL;
   SSC_LAUNCH(attn_pool_kernel, dim3(ssc_cdiv((D + 3) & ~3, 128), G), dim3(128), 0, (hipStream_t)stream, alpha, x, G, R, D, rows_per_image,
              out, ldo);
   SSC_CHECK_LAUNCH();
@@ -442,7 +443,8 @@ int ssc_attn_fwd_qslabs(const float* qslabs, int nslab, size_t slab_stride, floa
                         const float* obj, int D, float* pool, int ldpool) {
   if (!qslabs || nslab < 1 || !q_out || !pv || !wa || !mask || !feats || !alpha || !att || !logits) return SSC_EINVAL;
   if (obj && (!pool || D <= 0 || ldpool < D)) return SSC_EINVAL;
-  if (G <= 0 || R <= 0 || A <= 0 || A > ATTN_MAXA || F <= 0 || ldatt < F || ldqo < A || R > 64 * MAXR_LANE) return SSC_EINVAL;
+  if (G <= 0 || G > ATTN_MAXG || R <= 0 || A <= 0 || A > ATTN_MAXA || F <= 0 || ldatt < F || ldqo < A || R > 64 * MAXR_LANE)
+    return SSC_EINVAL;
   SSC_LAUNCH(attn_logits_kernel, dim3(G * ssc_cdiv(R, ATTN_RG)), dim3(256), 0, st, qslabs, A, nslab, slab_stride, q_out,
                      ldqo, pv, wa, G, R, A, rows_per_image, logits, (const int*)nullptr, (const int*)nullptr);
   SSC_CHECK_LAUNCH();
@@ -464,7 +466,8 @@ extern "C" int ssc_attn_bwd_pool(const float* datt, int lddatt, const float* q, 
                                  float* dpv_acc, float* dwa_acc, float* scratch_dalpha, const float* obj, int D,
                                  const float* dpool_a, int lddpa, int Da, const float* dpool_b, int lddpb, void* stream) {
   if (!datt || !q || !pv || !wa || !alpha || !feats || !dq || !dpv_acc || !dwa_acc || !scratch_dalpha) return SSC_EINVAL;
-  if (G <= 0 || R <= 0 || A <= 0 || F <= 0 || R > 64 * MAXR_LANE || lddatt < F || ldq < A || lddq < A) return SSC_EINVAL;
+  if (G <= 0 || G > ATTN_MAXG || R <= 0 || A <= 0 || F <= 0 || R > 64 * MAXR_LANE || lddatt < F || ldq < A || lddq < A)
+    return SSC_EINVAL;
   if (obj && (!dpool_a || D <= 0 || Da < 0 || Da > D || lddpa < Da || (dpool_b && lddpb < D))) return SSC_EINVAL;
   SSC_LAUNCH(attn_dalpha_kernel, dim3(ssc_cdiv(G * R, 4)), dim3(256), 0, (hipStream_t)stream, datt, lddatt, feats,
                      G, R, F, scratch_dalpha, obj, D, dpool_a, lddpa, Da, dpool_b, lddpb);

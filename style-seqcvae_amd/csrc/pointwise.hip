@@ -1054,15 +1054,17 @@ extern "C" int ssc_copy_strided(const float* src, size_t stride, int n, float* d
   return SSC_OK;
 }
 
+// rows ride on gridDim.y, which the runtime limits to 65535: more is refused here, not handed on as an invalid grid
+static constexpr int kMaxGridY = 65535;
 extern "C" int ssc_bias_tanh(float* x, int ldx, int rows, int N, const float* bias, void* stream) {
-  if (!x || rows <= 0 || N <= 0 || ldx < N) return SSC_EINVAL;
+  if (!x || rows <= 0 || rows > kMaxGridY || N <= 0 || ldx < N) return SSC_EINVAL;
   SSC_LAUNCH(bias_tanh_kernel, dim3(ssc_cdiv(N, 256), rows), dim3(256), 0, S(stream), x, ldx, N, bias);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }
 
 extern "C" int ssc_tanh_bwd(float* dy, int lddy, const float* y, int ldy, int rows, int N, void* stream) {
-  if (!dy || !y || rows <= 0 || N <= 0) return SSC_EINVAL;
+  if (!dy || !y || rows <= 0 || rows > kMaxGridY || N <= 0 || lddy < N || ldy < N) return SSC_EINVAL;
   SSC_LAUNCH(tanh_bwd_kernel, dim3(ssc_cdiv(N, 256), rows), dim3(256), 0, S(stream), dy, lddy, y, ldy, N);
   SSC_CHECK_LAUNCH();
   return SSC_OK;

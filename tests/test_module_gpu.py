@@ -421,6 +421,51 @@ def _check_lstm_bwd_x(B, H, K, nA, nB):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("B,H", [(5, 37), (70, 50)])
+def test_lstm_bwd_second_addend_and_running_sum_equal_float64(B, H):
+    """ssc_lstm_bwd with dh2 set (rows ld H + 3 apart) and dgsum starting from random values, against the backward formulas in
+    float64: dG and dc_prev at the 2e-5 relative bound of the tests above; dgsum moves by dG to within the one rounding of its
+    fp32 add, |after - (before + dG)| <= 2^-24 |before + dG|."""
+    import ctypes as C
+    from ssc_runtime import lib as L
+    lib = L.load()
+    g = torch.Generator().manual_seed(B * 1000 + H + 7)
+    dev = "cuda"
+    gates = torch.rand(B, 4 * H, generator=g).to(dev)
+    c_prev, c_new = torch.randn(B, H, generator=g).to(dev), torch.randn(B, H, generator=g).to(dev)
+    dh_in, dc_in = torch.randn(B, H, generator=g).to(dev), torch.randn(B, H, generator=g).to(dev)
+    dh2 = torch.full((B, H + 3), float("nan"))
+    dh2[:, :H] = torch.randn(B, H, generator=g)
+    dh2 = dh2.to(dev)
+    before = torch.randn(B, 4 * H, generator=g).to(dev)
+    dgsum = before.clone()
+    dG, dcp = torch.full((B, 4 * H), float("nan"), device=dev), torch.full((B, H), float("nan"), device=dev)
+    d = L.LstmBwdDesc()
+    d.B, d.H = B, H
+    d.dh, d.ld_dh = dh_in.data_ptr(), H
+    d.dh2, d.ld_dh2 = dh2.data_ptr(), H + 3
+    d.dc_in, d.ld_dcin = dc_in.data_ptr(), H
+    d.gates = gates.data_ptr()
+    d.c_prev, d.ld_cprev, d.c_new, d.ld_cnew = c_prev.data_ptr(), H, c_new.data_ptr(), H
+    d.dG, d.dc_prev, d.ld_dcprev = dG.data_ptr(), dcp.data_ptr(), H
+    d.dgsum = dgsum.data_ptr()
+    lib.ssc_lstm_bwd(C.byref(d), L.stream_ptr())
+    torch.cuda.synchronize()
+    dh = dh_in.double() + dh2[:, :H].double()
+    i, f, gg, o = gates.double().split(H, dim=1)
+    tc = torch.tanh(c_new.double())
+    dc = dc_in.double() + dh * o * (1 - tc * tc)
+    want = torch.cat([dc * gg * i * (1 - i), dc * c_prev.double() * f * (1 - f), dc * i * (1 - gg * gg), dh * tc * o * (1 - o)], 1)
+    for name, u, v in (("dG", dG, want), ("dc_prev", dcp, dc * f)):
+        err, bound = (u.double() - v).abs().max().item(), 2e-5 * max(1.0, float(v.abs().max()))
+        print(f"lstm_bwd B={B} H={H} {name}: error / bound {err / bound:.3f}")
+        assert torch.isfinite(u).all() and err < bound
+    moved = before.double() + dG.double()
+    assert ((dgsum.double() - moved).abs() <= 2.0 ** -24 * moved.abs()).all()
+    assert not torch.equal(dgsum, before)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("B,H,NP,nslab", [(64, 1200, 256, 12), (5, 37, 26, 3), (70, 50, 12, 0),
                                           (5, 37, 13, 17), (3, 20, 6, 33)])   # (a second and a third 16-slab batch, tail masked)
 def test_lstm_fwd_p_partial_products_sum_to_the_linear_layer(B, H, NP, nslab):
