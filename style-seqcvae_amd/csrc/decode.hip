@@ -224,8 +224,7 @@ __global__ __launch_bounds__(256) void beam_first_kernel(const float* __restrict
     Cand best{-INFINITY, -1};
     for (int v = threadIdx.x; v < V; v += blockDim.x) {
       float x = (!m || m[v]) ? (NORM ? row[v] - lse : row[v]) : -INFINITY;
-      bool after_prev = (prev.i < 0) || (x < prev.v) || (x == prev.v && v > prev.i);
-      if (after_prev && (best.i < 0 || better(x, v, best))) best = Cand{x, v};
+      if (after(x, v, prev) && (best.i < 0 || better(x, v, best))) best = Cand{x, v};
     }
     best = block_best(best, sh);
     if (threadIdx.x == 0) {
@@ -263,8 +262,7 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restr
       if (m && !m[v]) x = -1e20f;
       else if (ended) x = v == end_index ? 0.f : -INFINITY;
       else x = NORM ? row[v] - lse : row[v];
-      bool after_prev = (prev.i < 0) || (x < prev.v) || (x == prev.v && v > prev.i);
-      if (after_prev && (best.i < 0 || better(x, v, best))) best = Cand{x, v};
+      if (after(x, v, prev) && (best.i < 0 || better(x, v, best))) best = Cand{x, v};
     }
     best = block_best(best, sh);
     if (threadIdx.x == 0) {
@@ -275,11 +273,10 @@ __global__ __launch_bounds__(256) void beam_row_topk_kernel(const float* __restr
   }
 }
 
-// The same selection with the row in REGISTERS (V <= 256 * BEAM_REG_NV): thread t holds v = t, t + 256, ... - the assignment of
-// row_prepare, so the maxima, the sums (same per-thread order, same block reduction) and therefore lse and lp[v] - lse are
-// bit-identical to it.  One memory round trip per row (all loads of a thread in flight at once), no LDS row: the staged form
-// took five dependent load batches, four passes over a 40 KB LDS row and three workgroups per CU (160 us for 5000 x 10000).
-constexpr int BEAM_REG_NV = 40;
+// The same selection with the row in REGISTERS (V <= 256 * BEAM_ROW_NV; beam_row_lse of beam_common.h): thread t holds
+// v = t, t + 256, ... - the assignment of row_prepare, so the maxima, the sums (same per-thread order, same block reduction) and
+// therefore lse and lp[v] - lse are bit-identical to it.  One memory round trip per row, no LDS row: the staged form took five
+// dependent load batches, four passes over a 40 KB LDS row and three workgroups per CU (160 us for 5000 x 10000).
 template <bool NORM>
 __global__ __launch_bounds__(256) void beam_row_topk_reg_kernel(const float* __restrict__ lp, int ldlp,
                                                                 const uint8_t* __restrict__ fsm, const int* __restrict__ mach,
@@ -293,52 +290,26 @@ __global__ __launch_bounds__(256) void beam_row_topk_reg_kernel(const float* __r
   const uint8_t* m = fsm ? fsm + (((size_t)(mach ? mach[b] : b) * S + s) * S + i) * V : nullptr;
   const bool ended = last_pred[g] == end_index;   // workgroup-uniform; an ended beam never looks at its row
   const float* row = lp + (size_t)g * ldlp;
-  float x[BEAM_REG_NV];
-  float lse = 0.f;
+  float x[BEAM_ROW_NV];
   if (!ended) {
-#pragma unroll
-    for (int u = 0; u < BEAM_REG_NV; ++u) x[u] = row[min(t + u * 256, V - 1)];
-    if (NORM) {
-      float mx = -INFINITY;
-#pragma unroll
-      for (int u = 0; u < BEAM_REG_NV; ++u)
-        if (t + u * 256 < V) mx = fmaxf(mx, x[u]);
-      mx = ssc_block_reduce(mx, shr, true);
-      float sum = 0.f;
-#pragma unroll
-      for (int u = 0; u < BEAM_REG_NV; ++u)
-        if (t + u * 256 < V) sum += expf(x[u] - mx);
-      sum = ssc_block_reduce(sum, shr, false);
-      lse = mx + logf(sum);
-    }
-    if (NORM) {
-#pragma unroll
-      for (int u = 0; u < BEAM_REG_NV; ++u) x[u] -= lse;
-    }
+    beam_row_lse<NORM, true>(row, V, x, beam_reduce2(shr));
   } else {
 #pragma unroll
-    for (int u = 0; u < BEAM_REG_NV; ++u) x[u] = t + u * 256 == end_index ? 0.f : -INFINITY;
+    for (int u = 0; u < BEAM_ROW_NV; ++u) x[u] = t + u * 256 == end_index ? 0.f : -INFINITY;
   }
   if (m) {   // (uniform; the mask bytes of a thread all in flight at once)
-    uint8_t mk[BEAM_REG_NV];
+    uint8_t mk[BEAM_ROW_NV];
 #pragma unroll
-    for (int u = 0; u < BEAM_REG_NV; ++u) mk[u] = m[min(t + u * 256, V - 1)];
+    for (int u = 0; u < BEAM_ROW_NV; ++u) mk[u] = m[min(t + u * 256, V - 1)];
 #pragma unroll
-    for (int u = 0; u < BEAM_REG_NV; ++u)
+    for (int u = 0; u < BEAM_ROW_NV; ++u)
       if (!mk[u]) x[u] = -1e20f;
   }
   const size_t base = ((((size_t)b * S + i) * S + s) * beam + k) * per_node;   // scratch layout (b, i, s, k, n)
   Cand prev{INFINITY, -1};
   for (int n = 0; n < per_node; ++n) {
-    Cand best{-INFINITY, -1};
-#pragma unroll
-    for (int u = 0; u < BEAM_REG_NV; ++u) {
-      const int v = t + u * 256;
-      const float y = x[u];
-      const bool after_prev = (prev.i < 0) || (y < prev.v) || (y == prev.v && v > prev.i);
-      if (v < V && after_prev && (best.i < 0 || better(y, v, best))) best = Cand{y, v};
-    }
-    best = block_best(best, sh);
+    // (every token is kept: the mask is already folded into x)
+    const Cand best = block_best(beam_own_best<NORM, true>(x, row, 0.f, V, prev, [](int, int) { return true; }), sh);
     if (t == 0) {
       sval[base + n] = best.v;
       sidx[base + n] = best.i;
@@ -814,7 +785,7 @@ int ssc_beam_rows_dense(bool norm, const float* lp, int ldlp, const uint8_t* fsm
                         hipStream_t st) {
   const int staged = norm && (size_t)V * sizeof(float) <= BEAM_STAGE_MAX;
   const size_t lds = staged ? (size_t)V * sizeof(float) : 0;
-  if (V <= 256 * BEAM_REG_NV && ssc_g_beam_reg) {
+  if (V <= 256 * BEAM_ROW_NV && ssc_g_beam_reg) {
     if (norm)
       SSC_LAUNCH(beam_row_topk_reg_kernel<true>, dim3(B * S * beam, S), dim3(256), 0, st, lp, ldlp, fsm, mach, last_pred, S, V, beam,
                  per_node, end_index, scratch_val, scratch_idx);

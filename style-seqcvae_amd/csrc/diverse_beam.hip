@@ -9,14 +9,13 @@
 // and the beams of the other groups select at most P = k - k' distinct tokens.  So the n best tokens of a row under the penalised
 // score r lie among its m = n + P best tokens under lp (value descending, token ascending): of those m at most P are penalised, at
 // least n unpenalised ones remain, and each of them ranks before every token outside the list both before and after the penalty.
-//   (A) rows kernel, one workgroup per live row, independent of groups: the log-sum-exp with the arithmetic of log_softmax_kernel
-//       (thread t owns tokens t, t + 256, ...: bit-identical to ssc_beam_step_fsm) and the row's top m by lp, left in scratch as
-//       (lp, token).  V <= 256 * 40: the row lives in registers, one memory round trip.  Every thread keeps its best token; a round
-//       is one block argmax, after which only the winner's thread looks at its tokens again.  Ended rows are not read.
+//   (A) rows kernel, one workgroup per live row, independent of groups: beam_list_rows_kernel of beam_common.h without the rules -
+//       the log-sum-exp every search shares (bit-identical to ssc_beam_step_fsm) and the row's top m by lp, left in scratch as
+//       (lp, token).  Ended rows are not read.
 //   (B) merge kernel, one wave per batch entry, the groups in order over those short lists: lane e holds entry e of a row
 //       (m <= 63), subtracts lambda * count (the counts of <= 32 distinct tokens live in LDS), ranks the entries by counting and
 //       leaves the n best as candidates; k' rounds of a wave argmax over the group's k' * n candidates; the chosen tokens join
-//       the counts.  Early stop: the protocol of ssc_beam_desc.ctl, as beam_merge_kernel (fsm.hip) follows it.
+//       the counts.  Early stop: the protocol of ssc_beam_desc.ctl (beam_early_stop_tail).
 // No atomics in the choice: two calls on the same inputs are bit-identical.  A slot that finds no finite candidate emits end_index
 // at -inf with the identity back-pointer, never index -1.
 #include <math.h>
@@ -28,61 +27,6 @@
 
 namespace {
 
-constexpr int DBS_MAX_BEAM = 32;   // k <= 32 (the counts, the merge's one wave), n <= 32: m = n + k - k' <= 63 lanes
-constexpr int DBS_REG_NV = BEAM_ROW_NV;   // V <= 256 * 40: the row in registers
-
-struct DbsRowArgs {
-  const float* scores; size_t ld; int V, m;
-  const int64_t* last_pred;   // (rows) or NULL (step 0: every row is live)
-  int end_index;
-  const int* ctl; int step;
-  float* lval; int64_t* ltok;   // (rows, m): the row's m best (lp, token), descending
-};
-
-// thread t's best token strictly after `prev` in the (value descending, token ascending) order
-template <bool NORM, bool REG>
-__device__ __forceinline__ Cand dbs_own_best(const float (&x)[REG ? DBS_REG_NV : 1], const float* __restrict__ row, float lse, int V,
-                                             const Cand& prev) {
-  const int t = threadIdx.x;
-  Cand best{-INFINITY, -1};
-  if (REG) {
-#pragma unroll
-    for (int u = 0; u < DBS_REG_NV; ++u) {
-      const int v = t + u * 256;
-      const float y = x[u];
-      if (v < V && after(y, v, prev) && (best.i < 0 || better(y, v, best))) best = Cand{y, v};
-    }
-  } else {
-    for (int v = t; v < V; v += 256) {
-      const float y = NORM ? row[v] - lse : row[v];
-      if (after(y, v, prev) && (best.i < 0 || better(y, v, best))) best = Cand{y, v};
-    }
-  }
-  return best;
-}
-
-template <bool NORM, bool REG>
-__global__ __launch_bounds__(256) void dbs_rows_kernel(DbsRowArgs a) {
-  __shared__ Cand sh2[2][4];
-  __shared__ float shr[16];
-  const int r = blockIdx.x, t = threadIdx.x;
-  const int V = a.V, m = a.m;
-  const bool stopped = a.ctl && a.last_pred && a.ctl[0] <= a.step;   // (written by an EARLIER launch of this stream)
-  if (stopped || (a.last_pred && a.last_pred[r] == a.end_index)) return;   // workgroup-uniform: an ended beam never looks at its row
-  const float* row = a.scores + (size_t)r * a.ld;
-  float x[REG ? DBS_REG_NV : 1];
-  const float lse = beam_row_lse<NORM, REG>(row, V, x, shr);
-  float* lval = a.lval + (size_t)r * m;
-  int64_t* ltok = a.ltok + (size_t)r * m;
-  Cand mine = dbs_own_best<NORM, REG>(x, row, lse, V, Cand{INFINITY, -1});
-  int par = 0;
-  for (int i = 0; i < m; ++i) {
-    const Cand w = block_best1(mine, sh2, par); par ^= 1;
-    if (t == 0) { lval[i] = w.i >= 0 ? w.v : -INFINITY; ltok[i] = w.i; }   // (w.i < 0: NaN scores only - the merge leaves such an entry out)
-    if (w.i >= 0 && (w.i & 255) == t) mine = dbs_own_best<NORM, REG>(x, row, lse, V, w);   // the owner of token w.i: its best after w
-  }
-}
-
 struct DbsMergeArgs {
   const float* lval; const int64_t* ltok; int m;
   int k, groups, n; float strength;
@@ -93,9 +37,10 @@ struct DbsMergeArgs {
 };
 
 __global__ __launch_bounds__(64) void dbs_merge_kernel(DbsMergeArgs a) {
-  __shared__ float ca[DBS_MAX_BEAM * DBS_MAX_BEAM], cs[DBS_MAX_BEAM * DBS_MAX_BEAM];   // a group's candidates: augmented sum, true sum,
-  __shared__ int ctk[DBS_MAX_BEAM * DBS_MAX_BEAM];                                      // token
-  __shared__ int ptok[DBS_MAX_BEAM], pcnt[DBS_MAX_BEAM];   // the tokens selected at this step so far, and by how many beams
+  // k <= 32 (the counts, this one wave), n <= 32: m = n + k - k' <= 63 lanes
+  __shared__ float ca[BEAM_LIST_MAX * BEAM_LIST_MAX], cs[BEAM_LIST_MAX * BEAM_LIST_MAX];   // a group's candidates: augmented sum, true sum,
+  __shared__ int ctk[BEAM_LIST_MAX * BEAM_LIST_MAX];                                        // token
+  __shared__ int ptok[BEAM_LIST_MAX], pcnt[BEAM_LIST_MAX];   // the tokens selected at this step so far, and by how many beams
   const int b = blockIdx.x, lane = threadIdx.x;
   const int k = a.k, Gr = a.groups, kp = k / Gr, m = a.m;
   const bool first = a.last_pred == nullptr;
@@ -156,12 +101,7 @@ __global__ __launch_bounds__(64) void dbs_merge_kernel(DbsMergeArgs a) {
       // the group's k' best candidates by augmented sum, descending (ties: lower candidate index)
       Cand prev{INFINITY, -1};
       for (int i = 0; i < kp; ++i) {
-        Cand best{-INFINITY, -1};
-        for (int c = lane; c < C; c += 64) {
-          const float x = ca[c];
-          if (x > -INFINITY && after(x, c, prev) && (best.i < 0 || better(x, c, best))) best = Cand{x, c};   // (finite only: NaN and -inf are never taken)
-        }
-        best = wave_best(best);
+        const Cand best = beam_next_key(ca, C, prev);
         const int c = best.i;
         const int tok = c >= 0 ? ctk[c] : a.end_index;
         if (c >= 0) prev = best;
@@ -194,19 +134,6 @@ __global__ __launch_bounds__(64) void dbs_merge_kernel(DbsMergeArgs a) {
   }
 }
 
-int dbs_rows_launch(const DbsRowArgs& a, bool norm, int rows, hipStream_t st) {
-  const bool reg = a.V <= 256 * DBS_REG_NV;
-#define SSC_DBS_ROWS(NORM_, REG_) SSC_LAUNCH((dbs_rows_kernel<NORM_, REG_>), dim3(rows), dim3(256), 0, st, a)
-  if (reg) {
-    if (norm) SSC_DBS_ROWS(true, true); else SSC_DBS_ROWS(false, true);
-  } else {
-    if (norm) SSC_DBS_ROWS(true, false); else SSC_DBS_ROWS(false, false);
-  }
-#undef SSC_DBS_ROWS
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
 // the limits of both entries (include/ssc.h): trivial machine, the group split, scratch for the lists
 bool dbs_desc_ok(const ssc_beam_desc* d, const ssc_diverse_desc* s, int per_node) {
   if (!d || !s || !d->scores || !d->pred || !d->lp_out || !d->scratch_val || !d->scratch_idx) return false;
@@ -219,8 +146,7 @@ bool dbs_desc_ok(const ssc_beam_desc* d, const ssc_diverse_desc* s, int per_node
 
 // trivial machine aside (checked by the callers): 1 <= k, n <= 32, k, n <= V, k % groups == 0, B * k <= 2^24, 0 <= strength finite
 bool ssc_diverse_beam_ok(int B, int k, int n, int V, const ssc_diverse_desc* s) {
-  if (!s || B <= 0 || V <= 0 || k < 1 || k > DBS_MAX_BEAM || n < 1 || n > DBS_MAX_BEAM || k > V || n > V) return false;
-  if ((long)B * k > (1L << 24)) return false;
+  if (!s || !beam_list_dims_ok(B, k, n, V)) return false;
   if (s->groups < 1 || k % s->groups != 0) return false;
   return s->strength >= 0.f && isfinite(s->strength);
 }
@@ -234,10 +160,10 @@ extern "C" int ssc_beam_first_diverse(const ssc_beam_desc* d, const ssc_diverse_
   hipStream_t st = (hipStream_t)stream;
   const int B = d->B, k = d->beam;
   // step 0: one row per entry; its k best tokens hold every group's k' best under the penalty (m = k' + (k - k'))
-  DbsRowArgs a{};
+  BeamListRowArgs a{};
   a.scores = d->scores; a.ld = (size_t)d->ld; a.V = d->dims.V; a.m = k; a.end_index = d->end_index;
   a.lval = d->scratch_val; a.ltok = d->scratch_idx;
-  SSC_TRY(dbs_rows_launch(a, d->raw_logits != 0, B, st));
+  SSC_TRY(beam_list_rows_launch<false>(a, d->raw_logits != 0, B, st));
   DbsMergeArgs g{};
   g.lval = d->scratch_val; g.ltok = d->scratch_idx; g.m = k; g.k = k; g.groups = s->groups; g.n = k / s->groups;
   g.strength = s->strength; g.pred = d->pred; g.lp_out = d->lp_out; g.end_index = d->end_index;
@@ -253,11 +179,11 @@ extern "C" int ssc_beam_step_diverse(const ssc_beam_desc* d, const ssc_diverse_d
   hipStream_t st = (hipStream_t)stream;
   const int B = d->B, k = d->beam, n = d->per_node;
   const int m = ssc_diverse_beam_list(k, s->groups, n, d->dims.V);
-  DbsRowArgs a{};
+  BeamListRowArgs a{};
   a.scores = d->scores; a.ld = (size_t)d->ld; a.V = d->dims.V; a.m = m; a.last_pred = d->last_pred; a.end_index = d->end_index;
   a.ctl = d->ctl; a.step = d->step_index;
   a.lval = d->scratch_val; a.ltok = d->scratch_idx;
-  SSC_TRY(dbs_rows_launch(a, d->raw_logits != 0, B * k, st));
+  SSC_TRY(beam_list_rows_launch<false>(a, d->raw_logits != 0, B * k, st));
   DbsMergeArgs g{};
   g.lval = d->scratch_val; g.ltok = d->scratch_idx; g.m = m; g.k = k; g.groups = s->groups; g.n = n; g.strength = s->strength;
   g.last_pred = d->last_pred; g.last_lp = d->last_lp; g.pred = d->pred; g.lp_out = d->lp_out; g.backptr = d->backptr;

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void ens_combine_kernel(const EnsArgs a) {
   float lse[SSC_ENSEMBLE_MAX];   // (beam_row_lse leaves the row's value with every thread)
 #pragma unroll
   for (int m = 0; m < SSC_ENSEMBLE_MAX; ++m)
-    lse[m] = m < a.M ? beam_row_lse<true, false>(a.logits[m] + (size_t)g * a.ld, V, none, shr) : 0.f;
+    lse[m] = m < a.M ? beam_row_lse<true, false>(a.logits[m] + (size_t)g * a.ld, V, none, beam_reduce2(shr)) : 0.f;
   float* o = a.out + (size_t)g * a.ldo;
   const int n4 = a.vec ? V >> 2 : 0;
   for (int i = t; i < n4; i += 256) {
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void ens_combine_kernel(const EnsArgs a) {
   }
   if (MODE == 1) {   // out = s - logsumexp_v s: the log-softmax of the row just written, whatever the rows' alignment
     __syncthreads();   // (the workgroup's stores of s, before other threads of it read them)
-    const float l = beam_row_lse<true, false>(o, V, none, shr);   // (its reductions' barriers: every read of s is done)
+    const float l = beam_row_lse<true, false>(o, V, none, beam_reduce2(shr));   // (its reductions' barriers: every read of s is done)
     for (int i = t; i < n4; i += 256) {
       float4 r = reinterpret_cast<const float4*>(o)[i];
       r.x -= l; r.y -= l; r.z -= l; r.w -= l;

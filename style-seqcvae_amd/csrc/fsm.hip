@@ -157,11 +157,9 @@ __global__ __launch_bounds__(256) void fsm_compile_kernel(const uint8_t* __restr
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // later steps, part A, one workgroup per source row g = (b, s, k): the masked top-`per_node` for EVERY target state
-// (cbs.py:177-209).  REG: V <= 256 * ROW_NV, the row lives in registers (decode.hip: beam_row_topk_reg_kernel - same ownership,
-// same log-sum-exp arithmetic, so x is the same bits).
+// (cbs.py:177-209).  REG: V <= 256 * BEAM_ROW_NV, the row lives in registers (beam_row_lse of beam_common.h, as in decode.hip's
+// beam_row_topk_reg_kernel: x is the same bits).
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int ROW_NV = 40;
-
 template <bool NORM, bool REG>
 __global__ __launch_bounds__(256) void beam_row_fsm_kernel(const float* __restrict__ lp, int ldlp, FsmT T,
                                                            const uint8_t* __restrict__ fsm, const int* __restrict__ mach,
@@ -181,40 +179,18 @@ __global__ __launch_bounds__(256) void beam_row_fsm_kernel(const float* __restri
   const bool junk = skip_dead && !ended && last_lp[g] <= -1e19f;         // no finite beam here: scored as all-zero log-probs
   const float* row = lp + (size_t)g * ldlp;
   const int U = (V + 255) >> 8;
-  float x[REG ? ROW_NV : 1];
+  float x[REG ? BEAM_ROW_NV : 1];
   float lse = 0.f;
   // ---- the row ----------------------------------------------------------------------------------------------------------
-  if (REG) {
-    if (!ended && !junk) {
+  if (!ended && !junk) {
+    lse = beam_row_lse<NORM, REG>(row, V, x, [&](float v, bool is_max) {
+      const float r = dec_block_reduce1(v, shr2, par, is_max);
+      par ^= 1;
+      return r;
+    });
+  } else if (REG) {
 #pragma unroll
-      for (int u = 0; u < ROW_NV; ++u) x[u] = row[min(t + u * 256, V - 1)];
-      if (NORM) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int u = 0; u < ROW_NV; ++u)
-          if (t + u * 256 < V) mx = fmaxf(mx, x[u]);
-        mx = dec_block_reduce1(mx, shr2, par, true); par ^= 1;
-        float sum = 0.f;
-#pragma unroll
-        for (int u = 0; u < ROW_NV; ++u)
-          if (t + u * 256 < V) sum += expf(x[u] - mx);
-        sum = dec_block_reduce1(sum, shr2, par, false); par ^= 1;
-        lse = mx + logf(sum);
-#pragma unroll
-        for (int u = 0; u < ROW_NV; ++u) x[u] -= lse;
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < ROW_NV; ++u) x[u] = junk ? 0.f : (t + u * 256 == end_index ? 0.f : -INFINITY);
-    }
-  } else if (NORM && !ended && !junk) {   // thread t owns v = t, t + 256, ...: the order of log_softmax_kernel
-    float mx = -INFINITY;
-    for (int v = t; v < V; v += 256) mx = fmaxf(mx, row[v]);
-    mx = dec_block_reduce1(mx, shr2, par, true); par ^= 1;
-    float sum = 0.f;
-    for (int v = t; v < V; v += 256) sum += expf(row[v] - mx);
-    sum = dec_block_reduce1(sum, shr2, par, false); par ^= 1;
-    lse = mx + logf(sum);
+    for (int u = 0; u < BEAM_ROW_NV; ++u) x[u] = junk ? 0.f : (t + u * 256 == end_index ? 0.f : -INFINITY);
   }
   auto xval = [&](int v) -> float {   // the cleaned log-prob of token v (cbs.py:177-186), any token
     if (ended) return v == end_index ? 0.f : -INFINITY;
@@ -269,14 +245,8 @@ __global__ __launch_bounds__(256) void beam_row_fsm_kernel(const float* __restri
     Cand prev{INFINITY, -1};
     for (int n = 0; n < per_node; ++n) {
       Cand best{-INFINITY, -1};
-      if (REG) {
-#pragma unroll
-        for (int u = 0; u < ROW_NV; ++u) {
-          const int v = t + u * 256;
-          const bool exc = u < 32 ? ((w0 >> u) & 1u) : ((w1 >> (u - 32)) & 1u);
-          const float y = x[u];
-          if (v < V && !exc && after(y, v, prev) && (best.i < 0 || better(y, v, best))) best = Cand{y, v};
-        }
+      if constexpr (REG) {   // (not an exception: the thread's bit u is clear)
+        best = beam_own_best<NORM, true>(x, row, lse, V, prev, [&](int u, int) { return !((u < 32 ? w0 >> u : w1 >> (u - 32)) & 1u); });
       } else {
         for (int u = 0; u < U; ++u) {
           const int v = t + u * 256;
@@ -414,23 +384,7 @@ __global__ __launch_bounds__(64) void beam_merge_kernel(const float* __restrict_
     }
   }
   if (ctl && lane == 0) {
-    int* cnt = ctl + 2 + step_index;
-    int* ticket = ctl + 2 + max_steps + step_index;
-    if (not_ended) atomicAdd(cnt, not_ended);
-    __threadfence();
-    const int done = atomicAdd(ticket, 1);
-    if (done == (int)gridDim.x - 1) {   // the last workgroup of this step
-      if (!stopped) {
-        __threadfence();
-        const int left = atomicAdd(cnt, 0);
-        if (left == 0) {
-          atomicMin(ctl, step_index + 1);
-          if (host_flag) __hip_atomic_store(host_flag, step_index + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-      // progress word: the host of ssc_decode_search queues step t only once step t - 2 has got here (its run-ahead bound)
-      if (host_flag) __hip_atomic_store(host_flag + 1, step_index, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    beam_early_stop_tail(ctl, host_flag, step_index, max_steps, not_ended, stopped);
   }
 }
 
@@ -526,7 +480,7 @@ extern "C" int ssc_beam_step_fsm(const ssc_beam_desc* d, void* stream) {
 #define SSC_ROW_FSM(NORM_, REG_)                                                                                            \
   SSC_LAUNCH((beam_row_fsm_kernel<NORM_, REG_>), grid, blk, lds, st, d->scores, d->ld, T, d->fsm, d->mach, d->last_pred,     \
              d->last_lp, S, V, beam, per_node, d->end_index, d->skip_dead, d->scratch_val, d->scratch_idx)
-    if (V <= 256 * ROW_NV) {
+    if (V <= 256 * BEAM_ROW_NV) {
       if (norm) SSC_ROW_FSM(true, true); else SSC_ROW_FSM(false, true);
     } else {
       if (norm) SSC_ROW_FSM(true, false); else SSC_ROW_FSM(false, false);

@@ -4,12 +4,10 @@
 // ssc_beam_first_rules / ssc_beam_step_rules are the stand-alone steps, ssc_decode_rules_beam (search.hip) runs them inside the
 // one-call search loop.  The rules live where the selection lives: the host never sees a step of a one-call search, and blocking
 // needs every beam's history at every step.
-//   (A) rows kernel, one workgroup of 256 per live row.  One wave forms the row's ban list in LDS first (at most 63 + 8 + 1 tokens:
-//       lane i compares the (n-1)-gram at history position i with the history's last n - 1 tokens and bans the token that followed
-//       it; then the suppress list; then END below the minimum length).  Then the log-sum-exp of diverse_beam.hip's rows kernel
-//       (beam_row_lse: bit-equal to ssc_log_softmax) and per_node rounds of a block argmax in which a banned token never becomes a
-//       thread's candidate: a value is tested against the list only when it would replace the thread's current best, which is
-//       rare.  The scores are never written and nothing is renormalised.  V <= 256 * 40: the row lives in registers.
+//   (A) rows kernel, one workgroup of 256 per live row: beam_list_rows_kernel of beam_common.h with the rules.  One wave forms the
+//       row's ban list in LDS first (beam_ban_list: at most 63 + 8 + 1 tokens), then the log-sum-exp every search shares (bit-equal
+//       to ssc_log_softmax) and per_node rounds of a block argmax in which a banned token never becomes a thread's candidate.  The
+//       scores are never written and nothing is renormalised.
 //   (B) merge kernel, one wave per batch entry: the keys of the k * per_node candidates in LDS, k rounds of a wave argmax (ties:
 //       lower candidate index), then the lanes copy the parents' history rows into the other generation and append the tokens.
 //       Early stop: the protocol of ssc_beam_desc.ctl (beam_early_stop_tail).
@@ -21,107 +19,6 @@
 #include "ssc_common.h"
 
 namespace {
-
-constexpr int RULES_MAX_BEAM = 32;                                            // k, per_node <= 32: the merge's one wave, its LDS
-constexpr int RULES_MAX_BAN = SSC_RULES_MAX_LEN + SSC_RULES_MAX_SUPPRESS + 1;   // n-gram bans (one per history position), suppress list, END
-
-struct RulesRowArgs {
-  const float* scores; size_t ld; int V, m;   // m: candidates per row (per_node; step 0: k)
-  const int64_t* last_pred;                   // (rows) or NULL (step 0: every row is live)
-  const int* hist; int ld_hist;               // (rows, ld_hist): tokens 0 .. step - 1 of every row; not read at step 0
-  int end_index;
-  const int* ctl; int step;
-  int ngram, min_length, n_suppress;
-  int suppress[SSC_RULES_MAX_SUPPRESS];
-  float* lval; int64_t* ltok;   // (rows, m): the row's m best unbanned (lp, token), descending
-};
-
-__device__ __forceinline__ bool rules_banned(const int* ban, int nb, int v) {
-  for (int q = 0; q < nb; ++q)
-    if (ban[q] == v) return true;
-  return false;
-}
-
-// thread t's best unbanned token strictly after `prev` in the (value descending, token ascending) order
-template <bool NORM, bool REG>
-__device__ __forceinline__ Cand rules_own_best(const float (&x)[REG ? BEAM_ROW_NV : 1], const float* __restrict__ row, float lse, int V,
-                                               const Cand& prev, const int* ban, int nb) {
-  const int t = threadIdx.x;
-  Cand best{-INFINITY, -1};
-  if (REG) {
-#pragma unroll
-    for (int u = 0; u < BEAM_ROW_NV; ++u) {
-      const int v = t + u * 256;
-      const float y = x[u];
-      if (v < V && after(y, v, prev) && (best.i < 0 || better(y, v, best)) && !rules_banned(ban, nb, v)) best = Cand{y, v};
-    }
-  } else {
-    for (int v = t; v < V; v += 256) {
-      const float y = NORM ? row[v] - lse : row[v];
-      if (after(y, v, prev) && (best.i < 0 || better(y, v, best)) && !rules_banned(ban, nb, v)) best = Cand{y, v};
-    }
-  }
-  return best;
-}
-
-template <bool NORM, bool REG>
-__global__ __launch_bounds__(256) void rules_rows_kernel(RulesRowArgs a) {
-  __shared__ Cand sh2[2][4];
-  __shared__ float shr[16];
-  __shared__ int hs[SSC_RULES_MAX_LEN];
-  __shared__ int ban[RULES_MAX_BAN];
-  __shared__ int nban;
-  const int r = blockIdx.x, t = threadIdx.x;
-  const int V = a.V, m = a.m;
-  const bool stopped = a.ctl && a.last_pred && a.ctl[0] <= a.step;   // (written by an EARLIER launch of this stream)
-  if (stopped || (a.last_pred && a.last_pred[r] == a.end_index)) return;   // workgroup-uniform: an ended beam never looks at its row
-  // ---- the row's ban list (wave 0) ----------------------------------------------------------------------------------------------
-  const int T = a.last_pred ? min(a.step, SSC_RULES_MAX_LEN - 1) : 0;   // tokens of history
-  const bool grams = a.ngram >= 1 && T >= a.ngram;   // (workgroup-uniform; fewer than n tokens of history: no n-gram to repeat)
-  if (grams) {
-    if (t < SSC_RULES_MAX_LEN) hs[t] = t < T ? a.hist[(size_t)r * a.ld_hist + t] : -1;
-    __syncthreads();
-  }
-  if (t < 64) {
-    const int n = a.ngram;
-    int nb = 0;
-    if (grams) {
-      // the n-gram that starts at position t ends inside the history; its first n - 1 tokens against the history's last n - 1
-      bool hit = t + n <= T;
-      if (hit) {
-        for (int q = 0; q < n - 1; ++q) hit = hit && hs[t + q] == hs[T - (n - 1) + q];
-      }
-      const int tok = hit ? hs[t + n - 1] : -1;
-      hit = hit && tok != a.end_index && tok >= 0;   // (END is never banned by this rule)
-      const unsigned long long mask = __ballot(hit);
-      if (hit) ban[__popcll(mask & ((1ull << t) - 1ull))] = tok;
-      nb = __popcll(mask);
-    }
-    if (t == 0) {
-#pragma unroll
-      for (int q = 0; q < SSC_RULES_MAX_SUPPRESS; ++q)
-        if (q < a.n_suppress) ban[nb + q] = a.suppress[q];
-      nb += a.n_suppress;
-      if (a.step < a.min_length) ban[nb++] = a.end_index;
-      nban = nb;
-    }
-  }
-  __syncthreads();
-  const int nb = nban;
-  // ---- the row's m best unbanned tokens -------------------------------------------------------------------------------------------
-  const float* row = a.scores + (size_t)r * a.ld;
-  float x[REG ? BEAM_ROW_NV : 1];
-  const float lse = beam_row_lse<NORM, REG>(row, V, x, shr);
-  float* lval = a.lval + (size_t)r * m;
-  int64_t* ltok = a.ltok + (size_t)r * m;
-  Cand mine = rules_own_best<NORM, REG>(x, row, lse, V, Cand{INFINITY, -1}, ban, nb);
-  int par = 0;
-  for (int i = 0; i < m; ++i) {
-    const Cand w = block_best1(mine, sh2, par); par ^= 1;
-    if (t == 0) { lval[i] = w.i >= 0 ? w.v : -INFINITY; ltok[i] = w.i; }   // (w.i < 0: fewer than m unbanned tokens - the merge leaves such an entry out)
-    if (w.i >= 0 && (w.i & 255) == t) mine = rules_own_best<NORM, REG>(x, row, lse, V, w, ban, nb);   // the owner of token w.i: its best after w
-  }
-}
 
 struct RulesMergeArgs {
   const float* lval; const int64_t* ltok;
@@ -136,10 +33,10 @@ struct RulesMergeArgs {
 };
 
 __global__ __launch_bounds__(64) void rules_merge_kernel(RulesMergeArgs a) {
-  __shared__ float ckey[RULES_MAX_BEAM * RULES_MAX_BEAM], csum[RULES_MAX_BEAM * RULES_MAX_BEAM];   // the candidates: key, true sum,
-  __shared__ int ctk[RULES_MAX_BEAM * RULES_MAX_BEAM];                                             // token
+  __shared__ float ckey[BEAM_LIST_MAX * BEAM_LIST_MAX], csum[BEAM_LIST_MAX * BEAM_LIST_MAX];   // the candidates: key, true sum,
+  __shared__ int ctk[BEAM_LIST_MAX * BEAM_LIST_MAX];                                           // token
   __shared__ float tab[SSC_RULES_MAX_LEN];
-  __shared__ int opar[RULES_MAX_BEAM], otok[RULES_MAX_BEAM];   // the selected slots' parents and tokens, for the histories
+  __shared__ int opar[BEAM_LIST_MAX], otok[BEAM_LIST_MAX];   // the selected slots' parents and tokens, for the histories
   const int b = blockIdx.x, lane = threadIdx.x;
   const int k = a.k, t = a.step_index;
   const bool first = a.last_pred == nullptr;
@@ -193,12 +90,7 @@ __global__ __launch_bounds__(64) void rules_merge_kernel(RulesMergeArgs a) {
     // the k best candidates by key, descending (ties: lower candidate index)
     Cand prev{INFINITY, -1};
     for (int i = 0; i < k; ++i) {
-      Cand best{-INFINITY, -1};
-      for (int c = lane; c < C; c += 64) {
-        const float x = ckey[c];
-        if (x > -INFINITY && after(x, c, prev) && (best.i < 0 || better(x, c, best))) best = Cand{x, c};   // (finite only: NaN and -inf are never taken)
-      }
-      best = wave_best(best);
+      const Cand best = beam_next_key(ckey, C, prev);
       const int c = best.i;
       if (c >= 0) prev = best;
       if (lane == 0) {
@@ -229,19 +121,6 @@ __global__ __launch_bounds__(64) void rules_merge_kernel(RulesMergeArgs a) {
   }
 }
 
-int rules_rows_launch(const RulesRowArgs& a, bool norm, int rows, hipStream_t st) {
-  const bool reg = a.V <= 256 * BEAM_ROW_NV;
-#define SSC_RULES_ROWS(NORM_, REG_) SSC_LAUNCH((rules_rows_kernel<NORM_, REG_>), dim3(rows), dim3(256), 0, st, a)
-  if (reg) {
-    if (norm) SSC_RULES_ROWS(true, true); else SSC_RULES_ROWS(false, true);
-  } else {
-    if (norm) SSC_RULES_ROWS(true, false); else SSC_RULES_ROWS(false, false);
-  }
-#undef SSC_RULES_ROWS
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
 // the limits of both entries (include/ssc.h): trivial machine, the rules, the state's outputs, scratch for the lists
 bool rules_desc_ok(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_rules_state* s, int per_node) {
   if (!d || !r || !s || !d->scores || !d->pred || !d->lp_out || !d->scratch_val || !d->scratch_idx) return false;
@@ -250,7 +129,7 @@ bool rules_desc_ok(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_ru
   return ssc_rules_beam_ok(d->B, d->beam, per_node, d->dims.V, d->end_index, r);
 }
 
-void rules_fill(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_rules_state* s, int m, RulesRowArgs* a, RulesMergeArgs* g) {
+void rules_fill(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_rules_state* s, int m, BeamListRowArgs* a, RulesMergeArgs* g) {
   a->scores = d->scores; a->ld = (size_t)d->ld; a->V = d->dims.V; a->m = m; a->end_index = d->end_index;
   a->ngram = r->no_repeat_ngram; a->min_length = r->min_length; a->n_suppress = r->n_suppress;
   for (int q = 0; q < SSC_RULES_MAX_SUPPRESS; ++q) a->suppress[q] = q < r->n_suppress ? r->suppress[q] : -1;
@@ -267,8 +146,7 @@ void rules_fill(const ssc_beam_desc* d, const ssc_rules_desc* r, const ssc_rules
 // trivial machine aside (checked by the callers): 1 <= k, n <= 32, k, n <= V, B * k <= 2^24, end_index in [0, V), and the rules'
 // own ranges (include/ssc.h: ssc_rules_desc)
 bool ssc_rules_beam_ok(int B, int k, int n, int V, int end_index, const ssc_rules_desc* r) {
-  if (!r || B <= 0 || V <= 0 || k < 1 || k > RULES_MAX_BEAM || n < 1 || n > RULES_MAX_BEAM || k > V || n > V) return false;
-  if ((long)B * k > (1L << 24)) return false;
+  if (!r || !beam_list_dims_ok(B, k, n, V)) return false;
   if (end_index < 0 || end_index >= V) return false;
   if (r->no_repeat_ngram < 0 || r->no_repeat_ngram > SSC_RULES_MAX_LEN || r->min_length < 0) return false;
   if (r->n_suppress < 0 || r->n_suppress > SSC_RULES_MAX_SUPPRESS) return false;
@@ -284,10 +162,10 @@ extern "C" int ssc_beam_first_rules(const ssc_beam_desc* d, const ssc_rules_desc
   if (d->ctl && d->max_steps <= 0) return SSC_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   // step 0: one row per entry with an empty history; its k best unbanned tokens
-  RulesRowArgs a{};
+  BeamListRowArgs a{};
   RulesMergeArgs g{};
   rules_fill(d, r, s, d->beam, &a, &g);
-  SSC_TRY(rules_rows_launch(a, d->raw_logits != 0, d->B, st));
+  SSC_TRY(beam_list_rows_launch<true>(a, d->raw_logits != 0, d->B, st));
   g.step_index = 0;
   SSC_LAUNCH(rules_merge_kernel, dim3(d->B), dim3(64), 0, st, g);
   SSC_CHECK_LAUNCH();
@@ -300,11 +178,11 @@ extern "C" int ssc_beam_step_rules(const ssc_beam_desc* d, const ssc_rules_desc*
   if (d->step_index < 1 || d->step_index > SSC_RULES_MAX_LEN - 1 || s->ld_hist < d->step_index + 1) return SSC_EINVAL;
   if (d->ctl && (d->max_steps <= 0 || d->step_index >= d->max_steps)) return SSC_EINVAL;
   hipStream_t st = (hipStream_t)stream;
-  RulesRowArgs a{};
+  BeamListRowArgs a{};
   RulesMergeArgs g{};
   rules_fill(d, r, s, d->per_node, &a, &g);
   a.last_pred = d->last_pred; a.hist = s->hist; a.ld_hist = s->ld_hist; a.ctl = d->ctl; a.step = d->step_index;
-  SSC_TRY(rules_rows_launch(a, d->raw_logits != 0, d->B * d->beam, st));
+  SSC_TRY(beam_list_rows_launch<true>(a, d->raw_logits != 0, d->B * d->beam, st));
   g.last_pred = d->last_pred; g.last_lp = d->last_lp; g.hist = s->hist; g.len = s->len; g.backptr = d->backptr;
   g.step_index = d->step_index;
   SSC_LAUNCH(rules_merge_kernel, dim3(d->B), dim3(64), 0, st, g);
