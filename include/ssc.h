@@ -773,6 +773,20 @@ typedef struct {
  * and sample.  Noise is handed in for all steps (the reference draws (rows, Z) per step, updown_cell.py:206), so the
  * random state a call consumes does not depend on where the search stops.
  * ---------------------------------------------------------------------------------------------- */
+/* Where a one-call decode starts (ssc_search_desc.start): the arguments start_predictions / start_state of
+ * ConstrainedBeamSearch.search (cbs.py:59).  The driver copies the four blocks into the generation of states its first step reads
+ * (in place of zeroing it) and `tokens` into the first step's fed tokens (in place of filling them with end_index); nothing else
+ * in its loop changes.  The first step never treats its fed token as "ended", even where it is end_index.  What the search
+ * returns is the CONTINUATION: a constraint machine starts in its start state (constraint words that led to the start state do
+ * not count), the decode rules' and the logit rules' histories, minimum length, length penalty and penalties, the samplers' step
+ * counter and max_steps all start at the search's own step 0, and log_probs sums the continuation only (ssc_prefix_join adds a
+ * prefix).  ssc_decode_prime makes one from a forced prefix.  Honoured by ssc_decode_search, the stochastic, sampled-node, diverse
+ * and rules searches and ssc_decode_sample / _sample_rules.  SSC_EINVAL before any launch: a NULL member; `start` together with a
+ * latent guide (ssc_decode_*_guided, ssc_decode_sample_rules) or with an ensemble (ssc_decode_search_ensemble). */
+typedef struct {
+  const float* h1; const float* c1; const float* hd; const float* cd;   /* (B, H) each, ld H: the states the FIRST step reads */
+  const int64_t* tokens;                                                /* (B): the word the first step is fed; an id outside [0, V) is fed as end_index, never used as an index */
+} ssc_start_state;
 typedef struct {
   int nimg, R, n_samples;        /* image context (ssc_decode_prepare over nimg images of R regions); B = nimg * n_samples */
   int S, beam, per_node, max_steps, end_index;
@@ -797,6 +811,8 @@ typedef struct {
                                   * [0] = the stop flag, [1] = the last step the device has completed */
   const int* host_flag_host;     /* the same words' host address: read between steps - the host stops queueing once [0] is set and
                                   * stays at most two steps ahead of [1] (plain memory reads, no event, no synchronisation call) */
+  const ssc_start_state* start;  /* optional start state and start token (above); NULL: zero states and end_index, as without the field -
+                                  * the same launches, the same bits.  (In front of attn, which stays the descriptor's last field) */
   const ssc_attn_record* attn;   /* optional attention trace (above); NULL: off - the same launches and the same bits as without the field.
                                   * Set with a NULL hist or anc: SSC_EINVAL before any launch.  Honoured by ssc_decode_search, the
                                   * stochastic, sampled-node, diverse and rules searches and ssc_decode_sample */
@@ -1384,6 +1400,48 @@ size_t ssc_decode_sample_rules_workspace_bytes(const ssc_model_cfg* cfg, const s
 int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
                             const ssc_logit_rules* rules, const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Prompted decoding: start the one-call decodes from a forced prefix ("a happy ...").  ssc_decode_prime teacher-forces the prefix
+ * on the B = nimg * n_samples rows of a call - the loop of ssc_decode_score, leaving STATES instead of only scores -, its outputs
+ * are an ssc_start_state for any search or sampled decode over the same B entries, and ssc_prefix_join puts prefix and
+ * continuation together.  The prefix costs max_len steps of B rows, before a search enlarges to B * S * beam rows.
+ * ---------------------------------------------------------------------------------------------- */
+/* Row b = (image, sample).  len_b = the number of leading ids of prefix[b, :] that lie in [0, V) and are not end_index: the first
+ * other id (-1 padding, an id >= V, end_index) ends the prefix and is never used as an index.  Step t < max_len feeds the rows with
+ * len_b > t end_index (t = 0: from zero states) or prefix[b, t-1] and scores them against prefix[b, t] (ssc_score_rows):
+ * log_probs[b] += log p(prefix[b, t]), token_lp[b, t] likewise.  After step t every row with len_b == t + 1 is CAPTURED: the
+ * step's four output states go to h1 / c1 / hd / cd and tokens[b] = prefix[b, t].  A row with len_b == 0 gets zero states,
+ * tokens[b] = end_index, log_probs 0: the start of an unprefixed call.  Rows with len_b <= t are not stepped from step 1 on
+ * (ssc_decode_step_desc.row_lp); nothing of theirs is read afterwards.  token_lp is 0 from column len_b on.  max_len steps, known
+ * on the host.  Every SENTIMENT_VAE, every numerics mode.  SSC_EINVAL before any launch: a NULL required pointer, an extent < 1,
+ * B > 2^24, end_index outside [0, V), what the configuration's prior needs (sentiment / obj_atts) missing. */
+typedef struct {
+  int nimg, R, n_samples, max_len, end_index;
+  const float* feats;            /* (nimg, R, F) */
+  const void* imgbuf;            /* from ssc_decode_prepare */
+  const float* sentiment;        /* (B) or NULL */
+  const float* obj_atts;         /* cfg->kld_mode 2: (nimg, R, Z); else NULL */
+  const int64_t* prefix;         /* (B, max_len) int64 */
+  const float* eps;              /* (max_len, B, Z): noise of step t at eps + t * B * Z */
+  float* h1; float* c1; float* hd; float* cd;   /* out (B, H) each */
+  int64_t* tokens;               /* out (B) */
+  int* lengths;                  /* out (B) int32: len_b */
+  float* log_probs;              /* out (B): the prefix's summed log-prob */
+  float* token_lp;               /* out (B, max_len), optional */
+} ssc_prime_desc;
+size_t ssc_decode_prime_workspace_bytes(const ssc_model_cfg* cfg, const ssc_prime_desc* d);
+int ssc_decode_prime(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_prime_desc* d, void* workspace, size_t workspace_bytes,
+                     void* stream);
+/* Prefix + continuation.  prefix (B, Lp) and lengths (B) as ssc_decode_prime took and left them, predictions (B, Q, steps) and
+ * log_probs (B, Q) a search's (Q = S * beam; 1 for the sampled decode), ctl the search's or NULL: columns >= ctl[0] are read as
+ * end_index.  captions (B, Q, Lp + steps): caption q of entry b is prefix[b, :len_b], then the search's words, then end_index to the
+ * end.  total (B, Q) = prefix_lp[b] + log_probs[b, q]; a log_probs value <= -1e19 (a beam that does not exist) stays as it is.
+ * One small kernel, no atomics, the same bits on every run.  SSC_EINVAL and no launch: a NULL pointer other than ctl, B, Q, Lp or
+ * steps < 1, B * Q > 2^24, end_index < 0. */
+int ssc_prefix_join(const int64_t* prefix, const int* lengths, int Lp, const int64_t* predictions, const int* ctl, int steps,
+                    const float* log_probs, const float* prefix_lp, int B, int Q, int end_index, int64_t* captions, float* total,
+                    void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Diverse-caption evaluation (eval/eval.py:95-472 with the coco-caption scorers it calls): BLEU-1..4 (BleuScorer, option

@@ -107,6 +107,14 @@ parser.add_argument("--word-bias", default="",
                          'step of every image, in front of the draw ("-inf" bans the word; a word outside the vocabulary is an error). '
                          "Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without SAMPLED_BEAM_SEARCH; composes with the "
                          "MODEL.SAMPLER_* logit rules")
+parser.add_argument("--prefix", default="",
+                    help='prompted decoding: words every caption starts with, e.g. --prefix "a happy" - one prompt for every image '
+                         "(default: MODEL.DECODE_PREFIX).  The prompt is teacher-forced, the configured decoder continues from it; "
+                         "constraints, rules and DATA.MAX_CAPTION_LENGTH apply to the continuation.  A word outside the vocabulary "
+                         "is an error")
+parser.add_argument("--prefix-json", default="",
+                    help='prompted decoding with a prompt per image: a JSON file {image_id: "words"}.  Images without an entry get no '
+                         "prompt; prompts of different lengths share one call")
 
 
 class _LocalGlove(UpDownCaptioner):
@@ -170,6 +178,36 @@ def check_word_bias_args(_A, model_cfg=None):
                              f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
 
 
+def check_prefix_args(_A):
+    """--prefix / --prefix-json, checked before anything is loaded -> {image_id: "words"} of --prefix-json, or None."""
+    if not _A.prefix and not _A.prefix_json:
+        return None
+    if _A.prefix and _A.prefix_json:
+        raise SystemExit("--prefix and --prefix-json exclude each other")
+    if _A.prefix and not _A.prefix.split():
+        raise SystemExit("--prefix: at least one word wanted")
+    for flag, what, why in (("ensemble_checkpoints", "--ensemble-checkpoints", "every member would need its own primed states"),
+                            ("exemplar_tensors", "--exemplar-tensors", "a latent guide's steps are those of a caption decoded from "
+                                                                        "@@BOUNDARY@@"),
+                            ("attention_output", "--attention-output", "the trace would not cover the prefix words")):
+        if getattr(_A, flag):
+            raise SystemExit(f"--prefix / --prefix-json is not available with {what}: {why}")
+    if not _A.prefix_json:
+        return None
+    if not os.path.isfile(_A.prefix_json):
+        raise SystemExit(f"--prefix-json: no such file {_A.prefix_json!r}")
+    try:
+        blob = json.load(open(_A.prefix_json, encoding="utf-8"))
+    except ValueError as e:
+        raise SystemExit(f"--prefix-json: {_A.prefix_json!r} is not JSON ({e})")
+    if not isinstance(blob, dict) or not blob or not all(isinstance(v, str) for v in blob.values()):
+        raise SystemExit('--prefix-json: a non-empty JSON object {image_id: "words"} wanted')
+    try:
+        return {int(k): v for k, v in blob.items()}
+    except ValueError:
+        raise SystemExit("--prefix-json: the keys must be image ids (integers)")
+
+
 def load_word_bias(path, vocabulary):
     """-> (V,) float32 bias row of a --word-bias file {word: bias}; "-inf" bans a word"""
     try:
@@ -211,11 +249,19 @@ def load_exemplars(path, max_len):
 
 def main():
     _A = parser.parse_args()
+    prompts = check_prefix_args(_A)
     ens_weights, ens_mode = check_ensemble_args(_A)
     jitter = check_exemplar_args(_A)
     check_word_bias_args(_A)
     _C = Config(_A.config, _A.config_override)
     check_word_bias_args(_A, _C.MODEL)
+    prompt = _A.prefix or ("" if prompts is not None else str(_C.MODEL.DECODE_PREFIX).strip())
+    if (prompt or prompts is not None) and not _A.prefix and not _A.prefix_json:   # (MODEL.DECODE_PREFIX: the flags' refusals apply)
+        _A.prefix = prompt
+        check_prefix_args(_A)
+    if (prompt or prompts is not None) and _C.MODEL.DECODE_ATTENTION != "none":
+        raise SystemExit("--prefix / --prefix-json cannot be combined with MODEL.DECODE_ATTENTION: the trace would not cover the "
+                         "prefix words")
     random.seed(_C.RANDOM_SEED)
     np.random.seed(_C.RANDOM_SEED)
     torch.manual_seed(_C.RANDOM_SEED)
@@ -246,6 +292,15 @@ def main():
                                                  presence_penalty=logit_rules.presence_penalty,
                                                  frequency_penalty=logit_rules.frequency_penalty)
         logit_rules = sampling.LogitRules(bias=load_word_bias(_A.word_bias, vocabulary).to(device), **kw)
+    # --prefix / --prefix-json / MODEL.DECODE_PREFIX: every image's prompt as word ids, padded to the longest (-1)
+    prefix_ids = None
+    if prompt or prompts is not None:
+        from ssc_runtime.prefix import DecodePrefix
+        try:
+            per_image = [prompt if prompts is None else prompts.get(int(i), "") for i in data.image_id]
+            prefix_ids = DecodePrefix.from_words(vocabulary, per_image).ids
+        except ValueError as e:
+            raise SystemExit(f"--prefix / --prefix-json: {e}")
     model = cls.from_config(_C, vocabulary=vocabulary, device=device, sampler=sampler, diverse_beam=diverse, **extra).to(device)
     if _A.checkpoint_path:
         model.load_state_dict(torch.load(_A.checkpoint_path, map_location=device, weights_only=True)["model"])
@@ -377,16 +432,20 @@ def main():
                     raise SystemExit(f"--exemplar-tensors holds no caption for image {missing[0]} ({len(missing)} images of this call)")
                 caps = torch.stack([exemplars[i] for i in here]).to(device)
                 guide = LatentGuide.from_encoding(encode_captions(model._eng, feats, caps, senti), jitter=jitter, repeat=n_z)
+            pkw = {}   # (a call without a prefix is made exactly as before)
+            if prefix_ids is not None:
+                from ssc_runtime.prefix import DecodePrefix
+                pkw = {"prefix": DecodePrefix(prefix_ids[lo: lo + n_here])}
             if diverse is not None:   # every group's best caption: N_Z_SAMPLES * DIVERSE_BEAM_GROUPS captions per image
                 out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, obj_means=obj,
-                                     diverse_beam=diverse, return_groups=True, attention=attn_mode)
+                                     diverse_beam=diverse, return_groups=True, attention=attn_mode, **pkw)
                 pred = out[0]
                 pred = pred.reshape(pred.size(0), n_z * diverse.groups, pred.size(-1))
             else:
                 out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode,
-                                     guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}))
+                                     guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}), **pkw)
                 pred = out[0]
             trace = out[-1] if attn_mode else None
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the

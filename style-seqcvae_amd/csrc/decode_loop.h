@@ -50,6 +50,24 @@ struct SscStepStates {
   }
 };
 
+// Where a call starts (ssc_search_desc.start, include/ssc.h: ssc_start_state).  What the drivers refuse before any launch: a NULL
+// member, and a start state together with what it is not combined with - `alone` is false where the call has a latent guide or
+// runs an ensemble.
+inline bool ssc_decode_start_ok(const ssc_start_state* s, bool alone = true) {
+  return !s || (alone && s->h1 && s->c1 && s->hd && s->cd && s->tokens);
+}
+// ... and the states the first step reads: generation `gen` zeroed (no start state: the launches of a call without the field) or
+// the caller's four blocks copied into it.  The fed tokens are ssc_decode_start's.
+inline int ssc_decode_start_states(const ssc_start_state* s, const SscStepStates& states, char* W, int gen, size_t rows,
+                                   hipStream_t stream) {
+  if (!s) return states.zero(W, gen, rows, stream);
+  const float* src[4] = {s->h1, s->c1, s->hd, s->cd};
+  for (int k = 0; k < 4; ++k)
+    if (hipMemcpyAsync(states.state(W, gen, k), src[k], rows * states.H * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+      return SSC_EHIP;
+  return SSC_OK;
+}
+
 // The attended-feature term of the gates from the per-image table (ssc_decode_step_desc.att_table): the decision
 // DecodeEngine.step makes per call, here once per call and extent.
 inline bool ssc_att_table_wanted(int R, int rows, int rows_per_image) {
@@ -100,6 +118,15 @@ struct SscStepPacer {
     return flag && flag[0] != 0;
   }
 };
+
+// The rows a TEACHER-FORCED step leaves out (ssc_decode_score, ssc_decode_prime), decided here for both: at step 0 every row's fed
+// token is END, so no row may be skipped by it; from step 1 on a row whose fed token is END - its caption or prefix has ended, or
+// the slot is absent - is not stepped (ssc_decode_step_desc.row_lp), under the beam-1 parent list `parent0`.
+inline void ssc_forced_step_rows(ssc_decode_step_desc* sd, int t, const int64_t* parent0, const float* lp, int end_index) {
+  if (t == 0) return;
+  sd->parent = parent0; sd->group = 1;
+  sd->row_lp = lp; sd->end_index = end_index;
+}
 
 // The attention trace of a call (ssc_attn_record, D::attn): off, or both of the caller's buffers ...
 template <class D>

@@ -157,7 +157,7 @@ bool sample_desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
   if (d->S != 1 || d->beam != 1 || d->fsm || d->tables || d->mach) return false;   // word sampling: one row per batch entry, no machine
   const long B = (long)d->nimg * d->n_samples;
   if (B > (1L << 24)) return false;
-  return ssc_decode_inputs_ok(cfg, d, d->max_steps) && d->predictions && d->log_probs && d->ctl;
+  return ssc_decode_inputs_ok(cfg, d, d->max_steps) && d->predictions && d->log_probs && d->ctl && ssc_decode_start_ok(d->start);
 }
 
 }  // namespace
@@ -205,6 +205,7 @@ extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_param
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
   if (guide && !ssc_latent_guide_ok(cfg, guide)) return SSC_EINVAL;
+  if (!ssc_decode_start_ok(d->start, !guide)) return SSC_EINVAL;   // (no start state under a guide)
   bool ruled = false;
   if (rules) {
     SSC_TRY(ssc_logit_rules_check(rules, cfg->V, d->end_index, &ruled));
@@ -224,10 +225,11 @@ extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_param
   float* logits = (float*)(W + l.logits);
   int* ctl = d->ctl;
 
-  SSC_TRY(ssc_decode_start(ctl, d->max_steps, tokens0, B, d->end_index, st));
+  // where the call starts: zero states and @@BOUNDARY@@, or the caller's start state
+  SSC_TRY(ssc_decode_start(ctl, d->max_steps, tokens0, B, d->end_index, d->start ? d->start->tokens : nullptr, V, st));
   if (hipMemsetAsync(parent0, 0, (size_t)B * 8, st) != hipSuccess) return SSC_EHIP;
   if (hipMemsetAsync(lp, 0, (size_t)B * 4, st) != hipSuccess) return SSC_EHIP;
-  SSC_TRY(states.zero(W, 1, B, st));
+  SSC_TRY(ssc_decode_start_states(d->start, states, W, 1, B, st));
 
   // the steps take the form the beam-1 search gives them (ssc_decode_search with S = beam = 1): same tables, same parent list
   const bool want_table = ssc_att_table_wanted(d->R, B, d->n_samples);

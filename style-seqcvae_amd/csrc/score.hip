@@ -264,6 +264,15 @@ extern "C" int ssc_score_rows(const float* logits, int ld, int rows, int V, cons
   return score_launch(a, rows, (hipStream_t)stream);
 }
 
+// ssc_common.h: ssc_score_rows with lp_out of row r at r * lp_stride - column t of a driver's (rows, L) output (ssc_decode_prime)
+int ssc_score_rows_at(const float* logits, int ld, int rows, int V, const int64_t* target, const int64_t* last_target, int end_index,
+                      float* row_lp, float* lp_out, int lp_stride, hipStream_t st) {
+  ScoreArgs a{};
+  a.logits = logits; a.ld = (size_t)ld; a.V = V; a.target = target; a.last_target = last_target; a.end_index = end_index;
+  a.row_lp = row_lp; a.lp_out = lp_out; a.lp_stride = lp_stride; a.rank_stride = 1;
+  return score_launch(a, rows, st);
+}
+
 extern "C" size_t ssc_decode_score_workspace_bytes(const ssc_model_cfg* cfg, const ssc_score_desc* d) {
   if (!score_dims_ok(cfg, d)) return 0;
   return score_layout(cfg, d).total;
@@ -314,10 +323,7 @@ extern "C" int ssc_decode_score_guided(const ssc_model_cfg* cfg, const ssc_param
     states.bind(W, cur, &sd);
     sd.att_table = table.next(want_table);
     sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), t, G, d->R);
-    if (t > 0) {   // (at step 0 every row's fed token is END: no row may be skipped by it)
-      sd.parent = parent0; sd.group = 1;
-      sd.row_lp = lp; sd.end_index = d->end_index;   // ended and absent rows (fed token END) are not stepped
-    }
+    ssc_forced_step_rows(&sd, t, parent0, lp, d->end_index);   // ended and absent rows (fed token END) are not stepped
     const SscStepGuide sg{guide, t, 1};
     SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
     a.target = tgt + (size_t)t * G;

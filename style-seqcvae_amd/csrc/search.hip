@@ -96,6 +96,7 @@ bool desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
   if (G <= 0 || G > (1L << 24)) return false;
   if (!ssc_decode_inputs_ok(cfg, d, d->max_steps) || !d->predictions || !d->log_probs || !d->ctl) return false;
   if (d->S > 1 && !d->fsm) return false;
+  if (!ssc_decode_start_ok(d->start)) return false;
   if (d->skip_dead && !d->tables && (d->S != 1 || d->fsm)) return false;   // (the one-state machine has no fill-only rows: skip_dead then only leaves ENDED beams out of the steps)
   return true;
 }
@@ -103,6 +104,14 @@ bool desc_ok(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
 __global__ void fill_i64_kernel(int64_t* __restrict__ p, size_t n, int64_t v) {
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
+}
+// a start state's tokens: the caller's, an id that cannot index the embedding replaced by END
+__global__ void start_tokens_kernel(const int64_t* __restrict__ src, int n, int V, int end_index, int64_t* __restrict__ dst) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) {
+    const int64_t x = src[i];
+    dst[i] = x >= 0 && x < V ? x : (int64_t)end_index;
+  }
 }
 __global__ void ctl_init_kernel(int* __restrict__ ctl, int n, int max_steps) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -117,10 +126,16 @@ __global__ void expand_rows_kernel(const float* __restrict__ src, int Wd, int re
 
 }  // namespace
 
-int ssc_decode_start(int* ctl, int max_steps, int64_t* tokens0, int B, int end_index, hipStream_t st) {
+int ssc_decode_start(int* ctl, int max_steps, int64_t* tokens0, int B, int end_index, const int64_t* start_tokens, int V,
+                     hipStream_t st) {
   const int nctl = 2 + 2 * max_steps;
   SSC_LAUNCH(ctl_init_kernel, dim3(ssc_cdiv(nctl, 256)), dim3(256), 0, st, ctl, nctl, max_steps);
   SSC_CHECK_LAUNCH();
+  if (start_tokens) {
+    SSC_LAUNCH(start_tokens_kernel, dim3(ssc_cdiv(B, 256)), dim3(256), 0, st, start_tokens, B, V, end_index, tokens0);
+    SSC_CHECK_LAUNCH();
+    return SSC_OK;
+  }
   SSC_LAUNCH(fill_i64_kernel, dim3(ssc_cdiv(B, 256)), dim3(256), 0, st, tokens0, (size_t)B, (int64_t)end_index);
   SSC_CHECK_LAUNCH();
   return SSC_OK;
@@ -222,9 +237,10 @@ int search_run(const ssc_model_cfg* cfg, SearchMember* mem, int M, const SearchC
   for (int m = 0; m < M; ++m) mlogits[m] = (const float*)(W + mem[m].logits);
   ssc_ensemble_rows_desc ed{M, mlogits, V, comb ? comb->logw : nullptr, comb ? comb->mode : 0};
 
-  SSC_TRY(ssc_decode_start(d->ctl, d->max_steps, tokens0, B, d->end_index, st));
+  // where the call starts: zero states and @@BOUNDARY@@, or the caller's start state (never with several members)
+  SSC_TRY(ssc_decode_start(d->ctl, d->max_steps, tokens0, B, d->end_index, d->start ? d->start->tokens : nullptr, V, st));
   if (hipMemsetAsync(parent0, 0, (size_t)G * 8, st) != hipSuccess) return SSC_EHIP;
-  for (int m = 0; m < M; ++m) SSC_TRY(mem[m].states.zero(W, 1, B, st));
+  for (int m = 0; m < M; ++m) SSC_TRY(ssc_decode_start_states(d->start, mem[m].states, W, 1, B, st));
 
   // which form the steps take is decided once per extent: the first step's B rows and the later steps' G rows each ask
   ssc_decode_step_desc sd{};
@@ -330,6 +346,7 @@ extern "C" int ssc_decode_search_guided(const ssc_model_cfg* cfg, const ssc_para
                                         const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !desc_ok(cfg, d) || (guide && !ssc_latent_guide_ok(cfg, guide))) return SSC_EINVAL;
+  if (!ssc_decode_start_ok(d->start, !guide)) return SSC_EINVAL;   // (no start state under a guide)
   const SearchLayout l = search_layout(cfg, d, SEARCH_BEAM);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   char* W = (char*)workspace;
@@ -387,6 +404,7 @@ extern "C" int ssc_decode_search_ensemble(const ssc_model_cfg* cfg, const ssc_en
                                           void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);
   if (!workspace || !ensemble_members_ok(e) || !e->params || !e->imgbufs || !desc_ok(cfg, d) || d->attn) return SSC_EINVAL;
+  if (!ssc_decode_start_ok(d->start, false)) return SSC_EINVAL;   // (no start state of an ensemble)
   SearchCombine comb{};
   double wsum = 0.0;
   for (int m = 0; m < e->M; ++m) {

@@ -162,8 +162,14 @@ int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targe
                               hipStream_t st);
 int ssc_decode_att_table_enabled();   // the "dec_att_table" switch (decode.hip)
 // the start of a one-call decode with the early-stop protocol (search.hip): ctl[0] = max_steps, the counters behind it zero;
-// tokens0 (B) = end_index, the token the first step feeds
-int ssc_decode_start(int* ctl, int max_steps, int64_t* tokens0, int B, int end_index, hipStream_t st);
+// tokens0 (B) = end_index, the token the first step feeds - or, with a start state (ssc_start_state), its tokens, an id outside
+// [0, V) replaced by end_index (never used as an index)
+int ssc_decode_start(int* ctl, int max_steps, int64_t* tokens0, int B, int end_index, const int64_t* start_tokens, int V,
+                     hipStream_t st);
+
+// ssc_score_rows (score.hip) with lp_out of row r at r * lp_stride: what a teacher-forced driver issues per step
+int ssc_score_rows_at(const float* logits, int ld, int rows, int V, const int64_t* target, const int64_t* last_target, int end_index,
+                      float* row_lp, float* lp_out, int lp_stride, hipStream_t st);
 
 // numerics mode of the calling thread's current sequence-level call (ssc_model_cfg.gemm_mode: 0 = the process default set by
 // ssc_set_gemm_mode, 1 = 3xBF16, 2 = exact-fp32 MFMA); -1 = none in force

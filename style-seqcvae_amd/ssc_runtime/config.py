@@ -107,6 +107,10 @@ def _defaults() -> dict:
             # of every returned caption the region it attended most, the weight there and the entropy of its attention - or "full"
             # - the whole map over the regions as well.  Any decoder; the captions themselves do not change
             "DECODE_ATTENTION": "none",
+            # prompted decoding (ssc_start_state, ssc_decode_prime; UpDownCaptioner.decode_prefix): words every caption of the eval
+            # decode starts with, e.g. "a happy"; "" (default): off.  Any decoder continues from the prompt; constraints, rules and
+            # MAX_CAPTION_LENGTH apply to the continuation.  Not together with DECODE_ATTENTION
+            "DECODE_PREFIX": "",
         },
         "OPTIM": {
             "BATCH_SIZE": 150, "NUM_ITERATIONS": 70000, "LR": 0.015, "MOMENTUM": 0.9, "LR_DECAY_EVERY_N": 7,
@@ -248,6 +252,10 @@ class Config(object):
                 raise ValueError(f"the logit rules (MODEL.SAMPLER_NO_REPEAT_NGRAM ...) need DATA.MAX_CAPTION_LENGTH <= 64; found {max_len}")
         if m.DECODE_ATTENTION not in ("none", "summary", "full"):
             raise ValueError(f"MODEL.DECODE_ATTENTION must be one of none | summary | full; found {m.DECODE_ATTENTION!r}")
+        if not isinstance(m.DECODE_PREFIX, str):
+            raise ValueError(f"MODEL.DECODE_PREFIX must be a string of words; found {m.DECODE_PREFIX!r}")
+        if m.DECODE_PREFIX.strip() and m.DECODE_ATTENTION != "none":
+            raise ValueError("MODEL.DECODE_PREFIX cannot be combined with MODEL.DECODE_ATTENTION: the trace would not cover the prefix words")
         o = self._C.OPTIM
         if o.OPTIMIZER not in ("sgd", "adam", "adamw"):
             raise ValueError(f'OPTIM.OPTIMIZER must be "sgd", "adam" or "adamw"; found {o.OPTIMIZER!r}')

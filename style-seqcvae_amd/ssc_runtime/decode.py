@@ -254,16 +254,20 @@ class DecodeEngine:
         return AttentionTrace(m, top, wgt, ent)
 
     def _one_call(self, ctx, sentiment, n_samples, S, beam, per_node, max_steps, end_index, eps0, eps, early_stop, skip_dead,
-                  out_shape, workspace_bytes, call, machine=None, attention=False):
+                  out_shape, workspace_bytes, call, machine=None, attention=False, start=None):
         """The shared body of the one-call decodes over a search descriptor: B = ctx.nimg * n_samples batch entries of S * beam
         rows.  Fills the descriptor (machine(desc) adds a search's machine fields), checks the noise, allocates the outputs -
         predictions out_shape + (max_steps,), log-probs out_shape -, takes the pinned early-stop flag, sizes the workspace with
         workspace_bytes(cfg, desc) and issues call(params, desc, (workspace, bytes, stream)).
         -> (predictions cut to the executed steps, log_probs[, AttentionRecord over max_steps steps with attention=True]); one wait
-        at the end, for the number of steps."""
+        at the end, for the number of steps.  start: a StartState (ssc_runtime.prefix, DecodeEngine.prime) over the B entries, or
+        None - the call then starts from its states and its tokens (ssc_search_desc.start) and returns the continuation."""
         B = ctx.nimg * n_samples
         dev = self.device
         sd = _lib.SearchDesc()
+        if start is not None:
+            sdesc, _keep_start = start.desc(dev, B, self.dims.H)
+            sd.start = C.pointer(sdesc)
         sd.nimg, sd.R, sd.n_samples = ctx.nimg, ctx.R, n_samples
         sd.S, sd.beam, sd.per_node, sd.max_steps, sd.end_index = S, beam, per_node, max_steps, end_index
         sd.feats, sd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
@@ -307,7 +311,7 @@ class DecodeEngine:
     def search(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int, max_steps: int,
                end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
                compiled: Optional["CompiledFsm"] = None, mach: Optional[torch.Tensor] = None, skip_dead: bool = False,
-               early_stop: bool = True, attention: bool = False, guide=None):
+               early_stop: bool = True, attention: bool = False, guide=None, start=None):
         """The whole constrained beam search of one call in ONE library call (ssc_decode_search): ctx.nimg images x n_samples
         latent samples, batch entry b = (image, sample).  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B*S*beam, Z):
         the noise of every step, drawn by the caller.  fsm (M,S,S,V) / compiled / mach as in cbs_search.
@@ -316,16 +320,21 @@ class DecodeEngine:
         order returned (caption q = the flattened index of the predictions' leading dimensions), for DecodeEngine.attention.
         guide: a LatentGuide (ssc_runtime.guide) over the B entries, or None - step t's latent of entry b is then drawn around
         guide.mean[t, b] instead of the prior (ssc_decode_search_guided); eps0 / eps are still the noise (unread where the guide has
-        no variance)."""
+        no variance).
+        start: a StartState (DecodeEngine.prime), or None - the search starts from its states and tokens instead of zero states and
+        @@BOUNDARY@@ and returns the CONTINUATION: the machine starts in its start state, max_steps bounds the continuation, the
+        log-probs are the continuation's (here and on every decode below; ssc_runtime.prefix.join_prefix adds the prefix).  Not
+        together with a guide."""
+        _start_check(start, guide)
         call = lambda p, sd, ws: self.lib.ssc_decode_search(C.byref(self._cfg), C.byref(p), C.byref(sd), *ws)
         if guide is not None:
             gd, _keep = self._guide_desc(guide, ctx.nimg * n_samples)
             call = lambda p, sd, ws: self.lib.ssc_decode_search_guided(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(gd), *ws)
         return self._search(ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm, compiled, mach, skip_dead,
-                            early_stop, attention, self.lib.ssc_decode_search_workspace_bytes, call)
+                            early_stop, attention, self.lib.ssc_decode_search_workspace_bytes, call, start=start)
 
     def _search(self, ctx, sentiment, n_samples, beam, per_node, max_steps, end_index, eps0, eps, fsm, compiled, mach, skip_dead,
-                early_stop, attention, workspace_bytes, call):
+                early_stop, attention, workspace_bytes, call, start=None):
         """The body of search(): the machine's checks and descriptor fields around _one_call, for the entry point `call` and its
         `workspace_bytes` (ssc_decode_search; ssc_decode_search_ensemble for EnsembleDecodeEngine.search)."""
         B = ctx.nimg * n_samples
@@ -348,11 +357,11 @@ class DecodeEngine:
 
         return self._one_call(ctx, sentiment, n_samples, S, beam, per_node, max_steps, end_index, eps0, eps, early_stop,
                               skip_dead and (compiled is not None or fsm is None), (B, S, beam), workspace_bytes, call,
-                              machine, attention=attention)
+                              machine, attention=attention, start=start)
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
-               attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True):
+               attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
@@ -362,6 +371,7 @@ class DecodeEngine:
         (ssc_decode_sample_rules: word bias, repetition / presence / frequency penalties, n-gram / length / token bans) and the
         log-probs are those under the edited distributions; None or inactive rules take the entry point of a call without them.
         skip_dead (default on): ended rows are not stepped; the captions do not depend on it."""
+        _start_check(start, guide)
         sampler.check_vocab(self.dims.V)
         sdesc = sampler.desc(seed)
         call = lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), *ws)
@@ -378,7 +388,7 @@ class DecodeEngine:
                                                                       C.byref(rd), C.byref(gd) if gd is not None else None, *ws)
             workspace_bytes = self.lib.ssc_decode_sample_rules_workspace_bytes
         return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
-                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention)
+                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
               eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False,
@@ -421,9 +431,47 @@ class DecodeEngine:
             return lps, ntok, tlp, trk, rec
         return lps, ntok, tlp, trk
 
+    def prime(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, prefix, end_index: int, eps: torch.Tensor,
+              want_tokens: bool = False):
+        """Teacher-force a prefix on the B = ctx.nimg * n_samples rows of a call in ONE library call (ssc_decode_prime) and return
+        the StartState (ssc_runtime.prefix) the searches and the sampled decode take as start=.  prefix: a DecodePrefix or an
+        int64 tensor, (nimg, Lp) - expanded over the samples - or (B, Lp), padded with -1; a row's prefix ends at its first id
+        outside [0, V) or equal to end_index.  sentiment (B) or None; eps (Lp, B, Z): the noise of the prefix's steps.  A row
+        without a prefix gets the start of an unprefixed call (zero states, end_index, log-prob 0).
+        want_tokens: the StartState carries token_lp (B, Lp)."""
+        from .prefix import DecodePrefix, StartState
+        dev, d = self.device, self.dims
+        B = ctx.nimg * n_samples
+        ids = prefix.ids if isinstance(prefix, DecodePrefix) else DecodePrefix(prefix).ids
+        if ids.size(0) == ctx.nimg and n_samples > 1:
+            ids = ids.repeat_interleave(n_samples, 0)
+        if ids.size(0) != B:
+            raise ValueError(f"prime: the prefix has {ids.size(0)} rows; this call has {ctx.nimg} images and {B} entries")
+        ids = ids.to(dev, torch.int64).contiguous()
+        Lp = ids.size(1)
+        eps = eps.to(dev, torch.float32).contiguous()
+        if tuple(eps.shape) != (Lp, B, d.Z):
+            raise ValueError(f"prime: eps must be (Lp, B, Z) = {(Lp, B, d.Z)}, got {tuple(eps.shape)}")
+        sent = sentiment.reshape(B).to(dev, torch.float32).contiguous() if sentiment is not None else None
+        pd = _lib.PrimeDesc()
+        pd.nimg, pd.R, pd.n_samples, pd.max_len, pd.end_index = ctx.nimg, ctx.R, n_samples, Lp, end_index
+        pd.feats, pd.imgbuf = ctx.feats.data_ptr(), ctx.buf.data_ptr()
+        pd.sentiment, pd.obj_atts, pd.prefix, pd.eps = _lib.ptr(sent), _lib.ptr(ctx.obj), _lib.ptr(ids), _lib.ptr(eps)
+        st = [torch.empty(B, d.H, dtype=torch.float32, device=dev) for _ in range(4)]
+        tok = torch.empty(B, dtype=torch.int64, device=dev)
+        lens = torch.empty(B, dtype=torch.int32, device=dev)
+        lps = torch.empty(B, dtype=torch.float32, device=dev)
+        tlp = torch.empty(B, Lp, dtype=torch.float32, device=dev) if want_tokens else None
+        pd.h1, pd.c1, pd.hd, pd.cd = [_lib.ptr(t) for t in st]
+        pd.tokens, pd.lengths, pd.log_probs, pd.token_lp = _lib.ptr(tok), _lib.ptr(lens), _lib.ptr(lps), _lib.ptr(tlp)
+        ws = self._workspace(self.lib.ssc_decode_prime_workspace_bytes(C.byref(self._cfg), C.byref(pd)))
+        p = self._params()
+        self.lib.ssc_decode_prime(C.byref(self._cfg), C.byref(p), C.byref(pd), *ws)
+        return StartState(st[0], st[1], st[2], st[3], tok, lens, lps, tlp)
+
     def stochastic_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                         max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
-                        early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
+                        early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None, start=None):
         """The whole stochastic beam search of one call in ONE library call (ssc_decode_stochastic_beam): ctx.nimg images x n_samples
         latent samples, batch entry b = (image, sample), `beam` captions per entry sampled without replacement by `sampler`
         (sampling.GumbelSampler) with the 64-bit `seed`, per_node candidates per beam.  sentiment (B) or None; eps0 (B, Z),
@@ -439,11 +487,11 @@ class DecodeEngine:
                                self.lib.ssc_decode_stochastic_beam_workspace_bytes,
                                lambda p, sd, ws: self.lib.ssc_decode_stochastic_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                      C.byref(gdesc), *ws),
-                              attention=attention)
+                              attention=attention, start=start)
 
     def sampled_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                      max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int,
-                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
+                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None, start=None):
         """The whole sampled-node beam search of one call in ONE library call (ssc_decode_sampled_beam): the reference's BeamSearch
         driven by a word sampler (ssc_runtime.sampling: multinomial / top-k / top-p) - step 0 takes the top `beam` tokens, every
         later step draws per_node candidates per beam (with or without replacement, sampler.with_replacement) with the 64-bit
@@ -467,11 +515,11 @@ class DecodeEngine:
                                self.lib.ssc_decode_sampled_beam_workspace_bytes,
                                lambda p, sd, ws: self.lib.ssc_decode_sampled_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                   C.byref(sdesc), rep, *ws),
-                              attention=attention)
+                              attention=attention, start=start)
 
     def diverse_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                      max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], diverse,
-                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
+                     early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None, start=None):
         """The whole diverse beam search of one call in ONE library call (ssc_decode_diverse_beam): `beam` beams per batch entry in
         diverse.groups groups (sampling.DiverseBeam), searched in order inside every step with the Hamming penalty
         diverse.strength; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples, batch entry
@@ -490,11 +538,11 @@ class DecodeEngine:
                                lambda cfg, sd: self.lib.ssc_decode_diverse_beam_workspace_bytes(cfg, sd, C.byref(ddesc)),
                                lambda p, sd, ws: self.lib.ssc_decode_diverse_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                                   C.byref(ddesc), *ws),
-                              attention=attention)
+                              attention=attention, start=start)
 
     def rules_beam(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                    max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], rules,
-                   early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None):
+                   early_stop: bool = True, skip_dead: bool = True, attention: bool = False, guide=None, start=None):
         """The whole beam search under the decode rules of one call in ONE library call (ssc_decode_rules_beam): blocking of
         repeated n-grams, a minimum length, suppressed tokens and a length penalty in the ranking (sampling.DecodeRules), applied
         where the selection runs; per_node candidates per beam.  Deterministic.  ctx.nimg images x n_samples latent samples,
@@ -517,7 +565,8 @@ class DecodeEngine:
                              skip_dead, (B, beam), self.lib.ssc_decode_rules_beam_workspace_bytes,
                              lambda p, sd, ws: self.lib.ssc_decode_rules_beam(C.byref(self._cfg), C.byref(p), C.byref(sd),
                                                                               C.byref(rdesc), _lib.ptr(scores),
-                                                                              _lib.ptr(lengths), *ws), attention=attention)
+                                                                              _lib.ptr(lengths), *ws), attention=attention,
+                             start=start)
         return (out[0], out[1], scores, lengths) + tuple(out[2:])
 
     def _step_from_embedding(self, ctx, token_embedding, states, sentiment, eps, prior_mean_out=None, prior_mean=None, prior_var=None):
@@ -534,6 +583,13 @@ DecodeEngine.step_from_embedding = DecodeEngine._step_from_embedding
 def _guide_unsupported(what):
     from .guide import guide_unsupported
     guide_unsupported(what)
+
+
+def _start_check(start, guide):
+    """A start state and a latent guide are not combined (include/ssc.h: ssc_start_state)."""
+    if start is not None and guide is not None:
+        raise NotImplementedError("a start state (start=) together with a latent guide (guide=) is not implemented: a guide's slab t "
+                                  "is the step of a caption decoded from @@BOUNDARY@@")
 
 
 ENSEMBLE_MODES = {"prob": 0, "logprob": 1}
@@ -603,8 +659,11 @@ class EnsembleDecodeEngine:
     def search(self, ctx: EnsembleContext, sentiment: Optional[torch.Tensor], n_samples: int, beam: int, per_node: int,
                max_steps: int, end_index: int, eps0: torch.Tensor, eps: Optional[torch.Tensor], fsm: Optional[torch.Tensor] = None,
                compiled: Optional["CompiledFsm"] = None, mach: Optional[torch.Tensor] = None, skip_dead: bool = False,
-               early_stop: bool = True, attention: bool = False, guide=None):
+               early_stop: bool = True, attention: bool = False, guide=None, start=None):
         """DecodeEngine.search over the ensemble: the same arguments (ctx from this engine's prepare), the same return value."""
+        if start is not None:
+            raise NotImplementedError("a start state (start=) over an ensemble (EnsembleDecodeEngine) is not implemented: every member "
+                                      "would need its own primed states")
         if guide is not None:
             _guide_unsupported("an ensemble (EnsembleDecodeEngine)")
         if attention:

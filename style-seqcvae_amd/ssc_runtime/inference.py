@@ -26,7 +26,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    eps_steps: Optional[List[torch.Tensor]] = None, early_stop: bool = True, per_node: Optional[int] = None,
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
-                   rules=None, attention: Optional[str] = None, guide=None, logit_rules=None):
+                   rules=None, attention: Optional[str] = None, guide=None, logit_rules=None, prefix=None,
+                   prefix_eps: Optional[torch.Tensor] = None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -69,7 +70,25 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     logit_rules: a sampling.LogitRules - with a word sampler the raw logits of every step are edited in front of the draw
     (DecodeEngine.sample(logit_rules=): word bias, repetition / presence / frequency penalties, n-gram / length / token bans);
     ValueError with any other decoder, NotImplementedError with an ensemble.  None, or rules with every control off: the plain
-    sampled decode.  (`rules` stays the beam search's and keeps refusing a sampler.)"""
+    sampled decode.  (`rules` stays the beam search's and keeps refusing a sampler.)
+    prefix: a DecodePrefix (ssc_runtime.prefix) with one row per image - or per (image, sample) entry -, or None.  With it every
+    caption starts with its image's prompt: the prompt is teacher-forced on the nimg * n_samples rows (DecodeEngine.prime), whichever
+    decoder was chosen continues from there (start=) and the call returns the FULL captions (nimg, n_samples, Lp + steps) - the
+    prompt's words, the continuation, then @@BOUNDARY@@ - with return_groups the grouped form, its log-probs the prompt's included.
+    The second value stays the number of SEARCH steps executed; max_steps bounds the continuation.  The machine of a constrained
+    search starts in its start state after the prompt (constraint words inside the prompt do not count), and the rules and logit
+    rules see the continuation only.  An image whose row holds no word decodes as without a prefix.
+    prefix_eps (Lp, nimg * n_samples, Z): the noise of the prompt's steps; default: drawn from the call's own generator AFTER the
+    noise of the search, so that the search sees the noise of the same call without a prefix.  NotImplementedError together with
+    attention=, guide= or an ensemble."""
+    if prefix is not None:
+        from .prefix import prefix_unsupported
+        if isinstance(dec, EnsembleDecodeEngine):
+            prefix_unsupported("an ensemble (EnsembleDecodeEngine)")
+        if guide is not None:
+            prefix_unsupported("latent guides (guide=)")
+        if attention is not None:
+            prefix_unsupported("attention traces (attention=): the trace would not cover the prefix words")
     if logit_rules is not None and not logit_rules.active:
         logit_rules = None
     if logit_rules is not None:
@@ -151,6 +170,39 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     G = B * S * beam
 
     gkw = {"guide": guide} if guide is not None else {}   # (an unguided call is made exactly as before)
+    primed = {}   # with a prefix: "ids" (B, Lp), "start" the StartState - formed by the first search, reused by a repeat
+    pseed = None
+    if prefix is not None and prefix_eps is None and eps_steps is not None:
+        pseed = int(torch.randint(0, 2 ** 62, (1,)).item())   # (the prefix noise of a call whose search noise is the caller's)
+
+    def prime(gen):
+        """-> the start= of this call's decoder: {} without a prefix"""
+        if prefix is None:
+            return {}
+        if not primed:
+            from .prefix import DecodePrefix
+            ids = (prefix if isinstance(prefix, DecodePrefix) else DecodePrefix(prefix)).ids
+            if ids.size(0) == nimg:
+                ids = ids.repeat_interleave(n_samples, 0)
+            if ids.size(0) != B:
+                raise ValueError(f"the prefix has {ids.size(0)} rows for {nimg} images x {n_samples} samples")
+            if prefix_eps is not None:
+                peps = prefix_eps
+            else:
+                if gen is None:
+                    gen = torch.Generator(device=dev)
+                    gen.manual_seed(pseed)
+                peps = torch.randn(ids.size(1), B, d.Z, device=dev, generator=gen)
+            primed["ids"] = ids.to(dev)
+            primed["start"] = dec.prime(ctx, sent_b, n_samples, primed["ids"], boundary_index, peps)
+        return {"start": primed["start"]}
+
+    def joined(beams, lps):
+        """-> (the full captions of a prefixed call, their log-probs); the search's own without a prefix"""
+        if prefix is None:
+            return beams, lps
+        from .prefix import join_prefix
+        return join_prefix(primed["ids"], primed["start"], beams, lps, boundary_index)
     rkw = {"logit_rules": logit_rules} if logit_rules is not None else {}
 
     def search(skip_now):
@@ -163,42 +215,44 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
             eps = torch.zeros(max(max_steps - 1, 1), G, d.Z, device=dev)
             if rest:
                 eps[: len(rest)] = torch.stack(rest)
+            skw = prime(None)
         else:
             gen = torch.Generator(device=dev)
             gen.manual_seed(seed)
             eps0 = torch.randn(B, d.Z, device=dev, generator=gen)
             eps = torch.randn(max(max_steps - 1, 1), G, d.Z, device=dev, generator=gen)
+            skw = prime(gen)
         if rules is not None:
             beams, lps, _, _, *rec = dec.rules_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, rules,
-                                                    early_stop=early_stop, skip_dead=skip_now, attention=want_attn)
+                                                    early_stop=early_stop, skip_dead=skip_now, attention=want_attn, **skw)
             calls["k"] = beams.size(-1)
             return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if diverse_beam is not None:
             beams, lps, *rec = dec.diverse_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
-                                                diverse_beam, early_stop=early_stop, skip_dead=skip_now, attention=want_attn)
+                                                diverse_beam, early_stop=early_stop, skip_dead=skip_now, attention=want_attn, **skw)
             calls["k"] = beams.size(-1)
             return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if sampled_beam:
             beams, lps, *rec = dec.sampled_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps, sampler,
                                                 seed if sample_seed is None else sample_seed, early_stop=early_stop,
-                                                skip_dead=skip_now, attention=want_attn)
+                                                skip_dead=skip_now, attention=want_attn, **skw)
             calls["k"] = beams.size(-1)
             return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if gumbel:
             beams, lps, *rec = dec.stochastic_beam(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
                                                    sampler, seed if sample_seed is None else sample_seed, early_stop=early_stop,
-                                                   skip_dead=skip_now, attention=want_attn)
+                                                   skip_dead=skip_now, attention=want_attn, **skw)
             calls["k"] = beams.size(-1)
             return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if sampler is not None:
             pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn,
-                                         **gkw, **rkw)
+                                         **gkw, **rkw, **skw)
             calls["k"] = pred.size(-1)
             return pred.view(B, 1, 1, -1), lps.view(B, 1, 1), rec
         beams, lps, *rec = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
                                       fsm=None if trivial else fsm.contiguous(), compiled=compiled, mach=mach, skip_dead=skip_now,
-                                      early_stop=early_stop, attention=want_attn, **gkw)
+                                      early_stop=early_stop, attention=want_attn, **gkw, **skw)
         calls["k"] = beams.size(-1)   # one step call per column (cbs.py:127,170)
         return beams, lps, rec
 
@@ -212,13 +266,14 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         return (type(tr)(*(None if x is None else x[:, :, :k] if len(lead) == 2 else x[:, :, :, :k] for x in tr)),)
 
     beams, lps, rec = search(skip)
+    beams, total = joined(beams, lps)   # (the selections below go by the search's own log-probs: the prefix's is the same for an entry's beams)
     if diverse_beam is not None:   # group-major, not sorted across groups: the arg-max inside each group, then over the entry
         Gr = diverse_beam.groups
         steps = beams.size(-1)
         glp = lps.view(B, Gr, beam // Gr)
         gi = glp.argmax(-1)   # (ties: the lower beam)
         gbest = beams.view(B, Gr, beam // Gr, steps).gather(2, gi.view(B, Gr, 1, 1).expand(B, Gr, 1, steps)).squeeze(2)
-        gbest_lp = glp.gather(2, gi.unsqueeze(-1)).squeeze(-1)
+        gbest_lp = total.view(B, Gr, beam // Gr).gather(2, gi.unsqueeze(-1)).squeeze(-1)
         # the call's caption number of every group's best: entry b, group g, beam gi inside it (group-major)
         rows = torch.arange(B, device=dev).view(B, 1) * beam + torch.arange(Gr, device=dev).view(1, Gr) * (beam // Gr) + gi
         if return_groups:
@@ -233,7 +288,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     else:
         best, best_lp = select_best_beam_simple_batched(beams, lps, num_constraints, min_constraints_to_satisfy)
         if skip and bool((best_lp <= -1e19).any()):   # (one read of the device; the captions are about to be read anyway)
-            beams, lps, rec = search(False)   # (and with it the trace: the repeat's record)
+            beams, lps, rec = search(False)   # (and with it the trace: the repeat's record; a prefix's start state is reused)
+            beams, total = joined(beams, lps)
             best, _ = select_best_beam_simple_batched(beams, lps, num_constraints, min_constraints_to_satisfy)
         if want_attn:
             state = select_best_state_simple_batched(lps, num_constraints, min_constraints_to_satisfy)

@@ -142,12 +142,23 @@ class AttnGatherDesc(C.Structure):
                 ("n_sel", C.c_int), ("maps", vp), ("ld_maps", C.c_int), ("top_region", vp), ("top_weight", vp), ("entropy", vp)]
 
 
+class StartState(C.Structure):
+    _fields_ = [("h1", vp), ("c1", vp), ("hd", vp), ("cd", vp), ("tokens", vp)]
+
+
 class SearchDesc(C.Structure):
     _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_samples", C.c_int), ("S", C.c_int), ("beam", C.c_int), ("per_node", C.c_int),
                 ("max_steps", C.c_int), ("end_index", C.c_int), ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("eps0", vp),
                 ("eps", vp), ("obj_atts", vp), ("fsm", vp), ("tables", vp), ("dims", FsmDims), ("mach", vp), ("skip_dead", C.c_int),
                 ("early_stop", C.c_int), ("predictions", vp), ("log_probs", vp), ("ctl", vp), ("host_flag", vp),
-                ("host_flag_host", vp), ("attn", C.POINTER(AttnRecord))]
+                ("host_flag_host", vp), ("start", C.POINTER(StartState)), ("attn", C.POINTER(AttnRecord))]
+
+
+class PrimeDesc(C.Structure):
+    _fields_ = [("nimg", C.c_int), ("R", C.c_int), ("n_samples", C.c_int), ("max_len", C.c_int), ("end_index", C.c_int),
+                ("feats", vp), ("imgbuf", vp), ("sentiment", vp), ("obj_atts", vp), ("prefix", vp), ("eps", vp),
+                ("h1", vp), ("c1", vp), ("hd", vp), ("cd", vp), ("tokens", vp), ("lengths", vp), ("log_probs", vp),
+                ("token_lp", vp)]
 
 
 SSC_ENSEMBLE_MAX = 8
@@ -394,6 +405,9 @@ SYMBOLS = {
     "ssc_decode_sample_rules_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample_rules": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
                                      C.POINTER(LogitRules), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
+    "ssc_decode_prime_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(PrimeDesc)]),
+    "ssc_decode_prime": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(PrimeDesc), vp, _sz, vp]),
+    "ssc_prefix_join": (_i, [vp, vp, _i, vp, vp, _i, vp, vp, _i, _i, _i, vp, vp, vp]),
     "ssc_eval_refs_bytes": (_sz, [_i, _i, _i]),
     "ssc_eval_prepare_refs": (_i, [C.POINTER(EvalRefs), vp]),
     "ssc_eval_score_workspace_bytes": (_sz, [C.POINTER(EvalRefs), C.POINTER(EvalScoreDesc)]),

@@ -186,6 +186,7 @@ class UpDownCaptioner(nn.Module):
         self._decode_attention = None  # decode_attention(): "summary" / "full" attention traces in the eval forward's output
         self._decode_guide = None      # decode_guide(): a LatentGuide the NEXT eval forwards draw their latents around
         self._logit_rules = None       # logit_rules(): sampling.LogitRules the NEXT eval forwards of a word sampler draw under
+        self._decode_prefix = None     # decode_prefix(): a DecodePrefix every caption of the NEXT eval forwards starts with
 
     # ------------------------------------------------------------------------------------------------------
     @classmethod
@@ -216,6 +217,9 @@ class UpDownCaptioner(nn.Module):
         model.decode_attention(_C.MODEL.DECODE_ATTENTION)
         if model.sampler is not None and not model.sampler.beam_search and not model.sampled_beam:
             model.logit_rules(sampling.logit_rules_from_config(_C.MODEL, vocabulary))
+        if str(_C.MODEL.DECODE_PREFIX).strip():
+            from ssc_runtime.prefix import DecodePrefix
+            model.decode_prefix(DecodePrefix.from_words(vocabulary, str(_C.MODEL.DECODE_PREFIX)))
         return model
 
     def _initialize_glove(self):
@@ -363,6 +367,9 @@ class UpDownCaptioner(nn.Module):
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
         obj_means = self._obj_means(obj_atts, batch_size, num_boxes)   # (updown_captioner.py:246-247)
         step = functools.partial(self._decode_step, image_features, obj_means, sentiment=sentiment)
+        if self._decode_prefix is not None:
+            with torch.no_grad():
+                return self._prefixed_decode(image_features, obj_means, sentiment, fsm if self._use_cbs else None, num_constraints)
         if self._decode_guide is not None:
             from ssc_runtime.guide import guide_unsupported
             if self.sampler is not None and (self.sampler.beam_search or self.sampled_beam):
@@ -458,6 +465,59 @@ class UpDownCaptioner(nn.Module):
             if guide.Z != self.z_space:
                 raise ValueError(f"decode_guide: the guide has Z = {guide.Z}, the model {self.z_space}")
         self._decode_guide = guide
+
+    def decode_prefix(self, prefix):
+        """A prompt for the NEXT eval forwards (ssc_runtime.prefix.DecodePrefix with one row - the same prompt for every image - or
+        one row per image of the forward; include/ssc.h: ssc_start_state, ssc_decode_prime): every returned caption starts with its
+        prompt's words, the configured decoder - beam search, plain or constrained (CBS_SIMPLE), a word sampler, the stochastic,
+        sampled-node and diverse beam searches, the beam search under decode rules - continues from there, and "predictions" is
+        (B, Lp + steps).  None (the default state): off, the forward is what it is without.  The machine of a constrained search
+        starts in its start state after the prompt, rules and logit rules see the continuation only, MAX_CAPTION_LENGTH bounds the
+        continuation.  The decode runs as ssc_runtime.inference.diverse_decode(prefix=...) with one latent sample per image and the
+        noise of a generator seeded by one draw of the global one.  NotImplementedError at the forward together with
+        decode_attention or decode_guide."""
+        if prefix is not None:
+            from ssc_runtime.prefix import DecodePrefix
+            if not isinstance(prefix, DecodePrefix):
+                raise ValueError(f"decode_prefix: a ssc_runtime.prefix.DecodePrefix or None, got {type(prefix).__name__}")
+            V = self._vocabulary.get_vocab_size()
+            ids = prefix.ids
+            if bool(((ids >= V) | (ids == self._boundary_index)).any()):
+                raise ValueError(f"decode_prefix: the prefix holds @@BOUNDARY@@ or an id outside the vocabulary of {V}")
+        self._decode_prefix = prefix
+
+    def _prefixed_decode(self, image_features, obj_means, sentiment, fsm, num_constraints):
+        """Eval forward with decode_prefix set: whichever decoder is configured, through inference.diverse_decode(prefix=...)."""
+        from ssc_runtime.inference import diverse_decode
+        from ssc_runtime.prefix import DecodePrefix, prefix_unsupported
+        if self._decode_attention is not None:
+            prefix_unsupported("attention traces (decode_attention): the trace would not cover the prefix words")
+        if self._decode_guide is not None:
+            prefix_unsupported("latent guides (decode_guide)")
+        B = image_features.size(0)
+        dev = self._eng.device
+        ids = self._decode_prefix.ids
+        if ids.size(0) == 1 and B > 1:
+            ids = ids.expand(B, ids.size(1))
+        if ids.size(0) != B:
+            raise ValueError(f"decode_prefix: the prefix has {ids.size(0)} rows, the forward {B} images")
+        fsm_d = None
+        if fsm is not None:
+            if not self.cbs_simple:
+                raise ValueError("decode_prefix with a constraint machine needs CBS_SIMPLE")
+            fsm_d = fsm.to(dev).to(torch.uint8).contiguous()
+        words = self.sampler is not None and not self.sampler.beam_search and not self.sampled_beam
+        k = 1 if words else self._beam_search.beam_size
+        per = None if (words or self.diverse_beam is not None or self.sampler is not None or self.decode_rules is not None) \
+            else (self._beam_search.per_node_beam_size or None)
+        out = diverse_decode(self._dec, image_features.to(dev).float().contiguous(),
+                             sentiment.reshape(B).to(dev) if sentiment is not None else None, 1, k, self._max_caption_length,
+                             self._boundary_index, fsm=fsm_d, num_constraints=num_constraints,
+                             min_constraints_to_satisfy=self._min_constraints_to_satisfy, per_node=per, obj_means=obj_means,
+                             sampler=self.sampler, sampled_beam=bool(self.sampled_beam and self.sampler is not None),
+                             diverse_beam=self.diverse_beam, rules=self.decode_rules,
+                             logit_rules=self._logit_rules if words else None, prefix=DecodePrefix(ids))
+        return {"predictions": out[0][:, 0, :]}
 
     def logit_rules(self, rules):
         """Logit rules for the NEXT eval forwards of a word sampler (ssc_runtime.sampling.LogitRules; include/ssc.h:
