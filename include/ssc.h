@@ -655,7 +655,8 @@ int ssc_decode_step(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_dec
  *   ssc_beam_step  : one later step (:170-234): ended beams forced to end_index, per target state i the
  *                    masked (-1e20) top-`per_node` per row, + running log-prob, top-`beam` over S*beam*per_node;
  *                    backpointer = idx / per_node (floor).  Ties resolve to the lowest index.
- *   ssc_gather_rows: state re-ordering by backpointer (:236-250).
+ *   ssc_gather_rows: state re-ordering by backpointer (:236-250).  SSC_EINVAL and no launch for B * rows_per_batch > 65535
+ *                    (the rows are the grid's second dimension) and for src == dst.
  * fsm (B,S,S,V) uint8, or NULL with S = 1 for the trivial one-state machine (every transition allowed; what
  * MAX_GIVEN_CONSTRAINTS: 0 produces).  Row order (batch, fsm_state, beam).
  * ---------------------------------------------------------------------------------------------- */
@@ -741,7 +742,8 @@ int ssc_beam_step_fsm(const ssc_beam_desc* d, void* stream);
  * ssc_gemm_desc.topk_part left (rows B*beam, ceil(V / 128) tiles of 6 floats each) instead of from the (rows, V) logits: the
  * row's log-sum-exp is combined from the tiles' partials, its best tokens from the tiles' best two.  Same selections as
  * ssc_beam_step_fsm on the logits unless two candidates collide after the subtraction of the log-sum-exp (which here is
- * summed in tile order); log-probs agree to rounding (~1e-6).  d->scores is not read. */
+ * summed in tile order); log-probs agree to rounding (~1e-6).  d->scores is not read.  SSC_EINVAL and no launch for S != 1, a
+ * machine, tables, per_node > 2 or per_node > V (as ssc_beam_step_fsm: a row has no more candidates than tokens). */
 int ssc_beam_step_parts(const ssc_beam_desc* d, const float* parts, void* stream);
 /* back-trace with the step count taken from ctl[0] on the device: out (B,SB,max_steps); columns >= ctl[0] are filled with end_index */
 int ssc_beam_backtrace_ctl(const int64_t* preds, const int64_t* backptrs, const int* ctl, int max_steps, int B, int SB,

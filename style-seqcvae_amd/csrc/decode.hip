@@ -846,6 +846,7 @@ extern "C" int ssc_beam_step_logits(const float* logits, int ldlp, const uint8_t
 extern "C" int ssc_gather_rows(const float* src, int ld, const int64_t* backptr, int B, int rows_per_batch, int Wd,
                                float* dst, void* stream) {
   if (!src || !backptr || !dst || B <= 0 || rows_per_batch <= 0 || Wd <= 0 || ld < Wd || src == dst) return SSC_EINVAL;
+  if ((long)B * rows_per_batch > 65535) return SSC_EINVAL;   // (the rows are the grid's second dimension)
   SSC_LAUNCH(gather_rows_kernel, dim3(ssc_cdiv(Wd, 256), B * rows_per_batch), dim3(256), 0, (hipStream_t)stream, src,
                      ld, backptr, rows_per_batch, Wd, dst);
   SSC_CHECK_LAUNCH();

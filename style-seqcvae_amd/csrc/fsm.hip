@@ -500,7 +500,7 @@ extern "C" int ssc_beam_step_parts(const ssc_beam_desc* d, const float* parts, v
   if (!d || !parts || !d->last_pred || !d->last_lp || !d->pred || !d->lp_out || !d->backptr || !d->scratch_val || !d->scratch_idx)
     return SSC_EINVAL;
   const int B = d->B, V = d->dims.V, beam = d->beam, per_node = d->per_node;
-  if (d->dims.S != 1 || d->fsm || d->tables || B <= 0 || V <= 0 || beam <= 0 || per_node <= 0 || per_node > 2 || d->end_index < 0 ||
+  if (d->dims.S != 1 || d->fsm || d->tables || B <= 0 || V <= 0 || beam <= 0 || per_node <= 0 || per_node > 2 || per_node > V || d->end_index < 0 ||
       d->end_index >= V || beam > beam * per_node)
     return SSC_EINVAL;
   if (d->ctl && (d->max_steps <= 0 || d->step_index <= 0 || d->step_index >= d->max_steps)) return SSC_EINVAL;
