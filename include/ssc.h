@@ -1007,6 +1007,49 @@ int ssc_ce_bwd_distill(float* logits, int ldl, const int64_t* targets, const flo
  * posterior, scoring and decode paths never distil. */
 
 /* ------------------------------------------------------------------------------------------------
+ * Token-level unlikelihood training in the cross-entropy train step (Welleck et al. 2020, "Neural Text Generation with
+ * Unlikelihood Training"): beside the (label-smoothed) likelihood of its target, a row lowers the probability of the words its
+ * caption has already used.  Rows, weights w, counts n_b, targets y and eps are those of ssc_ce_fwd_smooth; rows are time-major,
+ * row = t*B + b.  Per row with w != 0, x the logits row, alpha the weight, delta = min_one_minus:
+ *   C(t,b) = the distinct ids y[s,b] over s < t with w[s,b] != 0, minus y[t,b]        (the candidates; step 0 has none; a context
+ *            position with w = 0 - padding, an in-caption unknown - contributes none; no id is special-cased beyond that)
+ *   p      = softmax(x),  om_c = 1 - p[c], formed as -expm1f(x[c] - lse)
+ *   ul_row = - sum_{c in C} log(max(om_c, delta))            (a clamped candidate contributes -log(delta) and no gradient)
+ *   g_c    = p[c] / om_c where om_c > delta, else 0;  G = sum_c g_c
+ *   row    = row(eps) + alpha * ul_row                        row(eps): the label-smoothed row of ssc_ce_fwd_smooth
+ *   loss_b = n_b * sum_t w*row / (n_b + 1e-13)
+ *   ul_b   = n_b * sum_t w*ul_row / (n_b + 1e-13)             (reported beside the loss, not weighted by alpha)
+ *   bwd (in place): x[v] <- (softmax(x)[v] - (1-eps)[v==y] - eps/V - alpha*G*softmax(x)[v] + alpha*g_v [v in C])
+ *                            * gl_b * w * n_b/(n_b + 1e-13)
+ * nll, the unsmoothed hard loss of the same forward, is what it is without the option.  Rows with w = 0 are never read: their
+ * slots are written as 0, the backward writes a zero row.  Columns V .. ld-1 are never touched.  One workgroup per row, one lane per
+ * context position (hence T <= 256); the forward scans the row once as ssc_ce_fwd_smooth does and then gathers the candidates'
+ * logits, the backward gathers them before its in-place stream and patches them after it; 16 bytes per lane when ldl % 4 == 0.
+ * No atomics, every sum in a fixed order: two calls on the same inputs are bit-identical.
+ * ul == NULL or alpha == 0: the calls ARE ssc_ce_fwd_smooth / ssc_ce_bwd_smooth (in the train step: the cross-entropy as it is
+ * without the descriptor) - the same launches, the same bits, and no buffer of the descriptor is read or written.
+ * SSC_EINVAL and no launch, before anything touches memory: what the smoothed calls refuse; alpha negative, NaN or infinite;
+ * min_one_minus outside (0, 1) or NaN; with alpha > 0 a NULL rows or T > 256.  SSC_EALIGN: rows or ul no multiple of 4.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  float alpha;            /* >= 0, finite; 0 = off */
+  float min_one_minus;    /* delta, in (0, 1); the host's default is 1e-5, the clamp of fairseq's implementation */
+  float* rows;            /* caller-owned, 2*T*B floats: [G | w*ul_row], written by the forward, read by the backward */
+  float* ul;              /* (B) or NULL: ul_b */
+} ssc_unlikelihood;
+/* `lse` holds 3*T*B floats, [lse | w*row | w*row(0)], as for ssc_ce_fwd_smooth; the backward is given the descriptor of its forward. */
+int ssc_ce_fwd_unlike(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
+                      int V, float eps, const ssc_unlikelihood* ul, float* lse, float* loss, float* nll, void* stream);
+int ssc_ce_bwd_unlike(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, const float* lse,
+                      const float* gl, int T, int B, int V, float eps, const ssc_unlikelihood* ul, void* stream);
+/* The train step with unlikelihood training: ssc_train_fwd_unlike / ssc_train_bwd_unlike (behind ssc_train_opts, below); the
+ * scratch is the caller's, so ssc_train_workspace_bytes does not change.  Only the two cross-entropy calls of the step change - the
+ * forward's after the vocabulary head, the backward's at the start of phase 16; the backward reads `rows` as its forward left it.
+ * Label smoothing, free bits, the caller's KL weight and scheduled sampling compose unchanged (under scheduled sampling the
+ * candidates are the ground-truth targets, as the loss's targets are).  It does not compose with distillation: both on (alpha of
+ * both > 0) is SSC_EINVAL.  The self-critical, posterior, scoring and decode paths never apply it. */
+
+/* ------------------------------------------------------------------------------------------------
  * The options of one train step.  The layout of ssc_model_cfg is pinned, so an option travels beside the cfg, in this
  * descriptor - free bits (ssc_latent_fwd_fb), scheduled sampling and distillation (above) today; the next option is a field here,
  * never an entry of its own.  opts == NULL or every option off: the calls ARE ssc_train_fwd / ssc_train_bwd_phases - the same
@@ -1026,6 +1069,18 @@ int ssc_train_fwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_
 int ssc_train_bwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
                        const float* gl, const float* gk, const ssc_params* g, unsigned phases, const ssc_train_opts* opts,
                        void* stream);
+/* The same two entries with an ssc_unlikelihood (above) beside the opts.  While ssc_version() is 4 the 24 bytes of ssc_train_opts
+ * are as pinned as ssc_model_cfg is - a caller built against them hands the library exactly those, so a field behind `distill`
+ * would be read out of that caller's memory -, so this descriptor is an argument of its own; when the version next moves it becomes
+ * a field of ssc_train_opts and these entries go.  ul == NULL or alpha == 0: the calls ARE ssc_train_fwd_opts / ssc_train_bwd_opts.
+ * The backward is given the ul of its forward, `rows` as that forward left it.  SSC_EINVAL and no launch, from both entries: what
+ * those refuse and what ssc_unlikelihood's block refuses (T = L + 1 > 256 with alpha > 0 among it); distill on (alpha > 0) together
+ * with unlikelihood on (alpha > 0). */
+int ssc_train_fwd_unlike(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                         float* loss, float* kld, const ssc_train_opts* opts, const ssc_unlikelihood* ul, void* stream);
+int ssc_train_bwd_unlike(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* batch, void* workspace, size_t workspace_bytes,
+                         const float* gl, const float* gk, const ssc_params* g, unsigned phases, const ssc_train_opts* opts,
+                         const ssc_unlikelihood* ul, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Scoring GIVEN captions under the model (teacher forcing): how likely is a caption that came from elsewhere - a ground-truth

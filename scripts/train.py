@@ -310,6 +310,12 @@ def main():
             members.append(({k: v for k, v in sd.items()}, eng.dims))
         teacher = DistillTeacher(members, weights, kd_mode, student_dims=eng.dims, device=device)
         model.distill(teacher, kd_alpha, kd_tau)   # (the autograd path; the fused path passes distill= itself)
+    # OPTIM.UNLIKELIHOOD_ALPHA: the cross-entropy steps, on the fused and the autograd path (the module carries it there); ul, the
+    # unweighted term of the same forward, is then logged beside nll
+    unlikelihood = model.unlikelihood
+    if unlikelihood > 0 and _A.scst_references and rank == 0:
+        print(f"OPTIM.UNLIKELIHOOD_ALPHA {unlikelihood} is ignored by the self-critical steps (--scst-references): the "
+              "advantage-weighted loss is no likelihood target")
     from ssc_runtime.engine import OptimSpec, check_optimizer_state_kind
     kind = _C.OPTIM.OPTIMIZER
     spec = None   # the fused paths' optimiser; None: SGD with OPTIM.MOMENTUM / WEIGHT_DECAY, as before the key existed
@@ -393,7 +399,8 @@ def main():
                                            weight_decay=_C.OPTIM.WEIGHT_DECAY, max_norm=_C.OPTIM.CLIP_GRADIENTS,
                                            decoder_frozen=not train_decoder, obj_atts=batch.get("obj_atts"), optim=spec,
                                            label_smoothing=smoothing, kl_beta=beta, free_bits=free_bits,
-                                           free_bits_mode=free_bits_mode, **ss_args, **kd_args)
+                                           free_bits_mode=free_bits_mode, unlikelihood=unlikelihood,
+                                           unlikelihood_clamp=model.unlikelihood_clamp, **ss_args, **kd_args)
             reconstr_loss, kld_loss = loss_b.mean(), eng.kld_raw().mean()
             kld_free = kld_b.mean() if free_bits > 0 else None
             loss = reconstr_loss + beta * kld_b.mean() / _C.MODEL.KLD_WEIGHT
@@ -415,7 +422,9 @@ def main():
                    "3loss": float(loss), "4learning_rate": lr, "elapsed_s": time.time() - t0}
             if teacher is not None:
                 rec["kd"] = float(eng.kd().mean())     # tau^2 KL(teacher || student) of the same forward (this rank's rows)
-            if (smoothing > 0 or teacher is not None) and scst is None:
+            if unlikelihood > 0 and scst is None:
+                rec["ul"] = float(eng.ul().mean())     # - sum log(1 - p[repeated word]) of the same forward (this rank's rows), unweighted
+            if (smoothing > 0 or teacher is not None or unlikelihood > 0) and scst is None:
                 rec["nll"] = float(eng.nll().mean())   # the unsmoothed loss of the same forward (this rank's rows)
             if scst is None:
                 rec["kl_beta"] = beta

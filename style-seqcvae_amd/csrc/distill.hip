@@ -209,6 +209,15 @@ int ssc_distill_check(const ssc_distill* kd, const float* logits, int ldl, size_
   return SSC_OK;
 }
 
+// kd_loss_kernel over the blocks [w*row], [w*row(0)] and a third [w*term] (T*B floats each): loss (B), nll (B, optional) and the
+// term's per-caption sums (B, optional) - the third block is distillation's w*kd_row or unlikelihood training's w*ul_row
+int ssc_ce_loss3(const float* nllw, const float* nllw0, const float* termw, const float* nvalid, int T, int B, float* loss, float* nll,
+                 float* term, hipStream_t st) {
+  SSC_LAUNCH(kd_loss_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, st, nllw, nllw0, termw, nvalid, T, B, loss, nll, term);
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
+}
+
 // ssc_ce_fwd_distill with the three blocks of `lse` given one by one (the train workspace keeps the third apart, see
 // ssc_ce_fwd_smooth_blocks)
 int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
@@ -231,10 +240,7 @@ int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targe
   if (kd->temperature == 1.f) SSC_LAUNCH(kd_fwd_kernel<true>, dim3(rows), dim3(256), 0, st, a);
   else SSC_LAUNCH(kd_fwd_kernel<false>, dim3(rows), dim3(256), 0, st, a);
   SSC_CHECK_LAUNCH();
-  SSC_LAUNCH(kd_loss_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, st, nllw, nllw0, kd->rows + 2 * (size_t)rows, nvalid, T, B, loss, nll,
-             kd->kd);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
+  return ssc_ce_loss3(nllw, nllw0, kd->rows + 2 * (size_t)rows, nvalid, T, B, loss, nll, kd->kd, st);
 }
 
 // lse must hold 3*T*B floats: [lse | w*row | w*row(0)]

@@ -443,19 +443,23 @@ int check_cfg(const ssc_model_cfg* c, const ssc_params* p, const ssc_batch* b) {
 // ssc_distill_check this is the first, memory-free stage; the overlap with the logits block is checked where the layout is known.
 struct TrainOpts {
   ssc_train_opts o{};
-  bool fb_on = false, ss_on = false, kd_on = false;
+  const ssc_unlikelihood* ul = nullptr;   // beside the opts (ssc_train_fwd_unlike / ssc_train_bwd_unlike): their 24 bytes are pinned
+  bool fb_on = false, ss_on = false, kd_on = false, ul_on = false;
 };
-int resolve_train_opts(const ssc_train_opts* opts, const ssc_model_cfg* cfg, TrainOpts* r) {
+int resolve_train_opts(const ssc_train_opts* opts, const ssc_unlikelihood* ul, const ssc_model_cfg* cfg, TrainOpts* r) {
   if (opts) r->o = *opts;
+  r->ul = ul;
   const ssc_train_opts& o = r->o;
   // free bits: lambda a finite number >= 0 and, while it is positive, a mode of 1..3
   if (!(o.free_bits >= 0.f) || !(o.free_bits <= 3.402823466e38f)) return SSC_EINVAL;   // negative, NaN, infinite
   if (o.free_bits > 0.f && (o.free_bits_mode < 1 || o.free_bits_mode > 3)) return SSC_EINVAL;
   SSC_TRY(ssc_distill_check(o.distill, nullptr, 0, 0, cfg->V, &r->kd_on));
+  SSC_TRY(ssc_unlike_check(r->ul, 0, &r->ul_on));   // (the limit on the steps: where the layout is known)
   if (o.sched && (!(o.sched->prob >= 0.f && o.sched->prob <= 1.f) || !sampler_ok(&o.sched->sampler, cfg->V))) return SSC_EINVAL;   // NaN included
   r->fb_on = o.free_bits > 0.f;
   r->ss_on = o.sched && o.sched->prob > 0.f;
   if (r->ss_on && r->kd_on) return SSC_EINVAL;   // the student would be fed its own words while the teacher was fed the ground truth
+  if (r->kd_on && r->ul_on) return SSC_EINVAL;   // one cross-entropy kernel per step: the two terms are not composed
   return SSC_OK;
 }
 
@@ -566,17 +570,17 @@ extern "C" void* ssc_train_sched_view(const ssc_model_cfg* cfg, int B, int R, in
   }
 }
 
-// opts (include/ssc.h: ssc_train_opts): sched off = teacher forcing, distill off = the cross-entropy as it is without it, free
+// opts (include/ssc.h: ssc_train_opts) and ul beside them: sched off = teacher forcing, distill / ul off = the cross-entropy as it is without it, free
 // bits off = the plain latent head; each with the launches as they are without the option
 static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace, size_t workspace_bytes,
-                          float* loss, float* kld, const ssc_train_opts* opts, void* stream) {
+                          float* loss, float* kld, const ssc_train_opts* opts, const ssc_unlikelihood* ul, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
   TrainOpts ro;
-  SSC_TRY(resolve_train_opts(opts, cfg, &ro));
+  SSC_TRY(resolve_train_opts(opts, ul, cfg, &ro));
   const ssc_train_opts& o = ro.o;
   const bool fb_on = ro.fb_on, ss_on = ro.ss_on;   // (fb_on: a free-bits floor on the KL, the _fb kernels of the latent head)
-  bool kd_on = ro.kd_on;
+  bool kd_on = ro.kd_on, ul_on = ro.ul_on;
   if (!workspace || !loss || !kld) return SSC_EINVAL;
   if (!ssc_aligned16(workspace)) return SSC_EALIGN;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
@@ -584,6 +588,7 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   float* W = (float*)workspace;
   // (the teacher's rows may not meet the logits block the backward overwrites: checked here, ahead of the first launch)
   if (kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
+  if (ul_on) SSC_TRY(ssc_unlike_check(ro.ul, l.T, &ul_on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -804,6 +809,9 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   if (kd_on)   // the soft targets of a teacher beside the (smoothed) hard loss: distill.hip
     return ssc_ce_fwd_distill_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, o.distill, W + l.lse,
                                      W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
+  if (ul_on)   // the words the caption has already used are pushed down beside the (smoothed) hard loss: unlikelihood.hip
+    return ssc_ce_fwd_unlike_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, ro.ul,
+                                    W + l.lse, W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
   SSC_TRY(ssc_ce_fwd_smooth_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, W + l.lse,
                                    W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st));
   return SSC_OK;
@@ -811,12 +819,18 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
 extern "C" int ssc_train_fwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                   size_t workspace_bytes, float* loss, float* kld, const ssc_train_opts* opts, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, opts, stream);
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, opts, nullptr, stream);
+}
+
+extern "C" int ssc_train_fwd_unlike(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                    size_t workspace_bytes, float* loss, float* kld, const ssc_train_opts* opts,
+                                    const ssc_unlikelihood* ul, void* stream) {
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, opts, ul, stream);
 }
 
 extern "C" int ssc_train_fwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                              size_t workspace_bytes, float* loss, float* kld, void* stream) {
-  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, nullptr, stream);
+  return train_fwd_impl(cfg, p, bt, workspace, workspace_bytes, loss, kld, nullptr, nullptr, stream);
 }
 
 // ---- posterior scoring of the forward that last ran in this workspace (include/ssc.h: ssc_train_posterior) ------------------------------
@@ -938,13 +952,13 @@ int ssc_g_dw_one_flush = ssc_env_int("SSC_DW_ONE_FLUSH", 1);
 // (ssc_runtime/engine.py): the output head's 48 MB travel under the whole time loop.
 static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                           size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
-                          const ssc_train_opts* opts, void* stream) {
+                          const ssc_train_opts* opts, const ssc_unlikelihood* ul, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   SSC_TRY(check_cfg(cfg, p, bt));
-  TrainOpts ro;   // the opts of the forward: its gates (free bits), its fed ids (sched on), its teacher and row sums (distill)
-  SSC_TRY(resolve_train_opts(opts, cfg, &ro));
+  TrainOpts ro;   // the opts of the forward: its gates (free bits), its fed ids (sched on), its teacher and row sums (distill), its rows' G (unlikelihood)
+  SSC_TRY(resolve_train_opts(opts, ul, cfg, &ro));
   const ssc_train_opts& o = ro.o;
-  bool kd_on = ro.kd_on;
+  bool kd_on = ro.kd_on, ul_on = ro.ul_on;
   if (phases == 0 || phases > 255u) return SSC_EINVAL;
   if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
   if (!workspace || !gl || !gk || !g) return SSC_EINVAL;
@@ -952,6 +966,7 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
   if (kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
+  if (ul_on) SSC_TRY(ssc_unlike_check(ro.ul, l.T, &ul_on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -972,6 +987,8 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   // ---- vocabulary head ------------------------------------------------------------------------------
   if (kd_on)   // (the forward of this minibatch left the rows' log-sum-exps in kd->rows)
     SSC_TRY(ssc_ce_bwd_distill(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, o.distill, st));
+  else if (ul_on)   // (the forward of this minibatch left the rows' G in ul->rows)
+    SSC_TRY(ssc_ce_bwd_unlike(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, ro.ul, st));
   else
     SSC_TRY(ssc_ce_bwd_smooth(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, st));
   const float* dlog = W + l.logits;
@@ -1326,16 +1343,22 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 extern "C" int ssc_train_bwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                   size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
                                   const ssc_train_opts* opts, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, opts, stream);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, opts, nullptr, stream);
+}
+
+extern "C" int ssc_train_bwd_unlike(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
+                                    size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, unsigned phases,
+                                    const ssc_train_opts* opts, const ssc_unlikelihood* ul, void* stream) {
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, opts, ul, stream);
 }
 
 extern "C" int ssc_train_bwd(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                              size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, 15u, nullptr, stream);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, 15u, nullptr, nullptr, stream);
 }
 
 extern "C" int ssc_train_bwd_phases(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
                                     size_t workspace_bytes, const float* gl, const float* gk, const ssc_params* g,
                                     unsigned phases, void* stream) {
-  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, nullptr, stream);
+  return train_bwd_impl(cfg, p, bt, workspace, workspace_bytes, gl, gk, g, phases, nullptr, nullptr, stream);
 }

@@ -160,6 +160,15 @@ int ssc_distill_check(const ssc_distill* kd, const float* logits, int ldl, size_
 int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
                               int V, float eps, const ssc_distill* kd, float* lse, float* nllw, float* nllw0, float* loss, float* nll,
                               hipStream_t st);
+// the per-caption sums of three row blocks in one launch (distill.hip: kd_loss_kernel), shared by distillation and unlikelihood training
+int ssc_ce_loss3(const float* nllw, const float* nllw0, const float* termw, const float* nvalid, int T, int B, float* loss, float* nll,
+                 float* term, hipStream_t st);
+// unlikelihood training (unlikelihood.hip, include/ssc.h: ssc_unlikelihood): the descriptor's refusals - *on = ul != NULL and
+// alpha > 0; T = 0 leaves the limit on the steps to a later call -, and ssc_ce_fwd_unlike with its three blocks given one by one
+int ssc_unlike_check(const ssc_unlikelihood* ul, int T, bool* on);
+int ssc_ce_fwd_unlike_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
+                             int V, float eps, const ssc_unlikelihood* ul, float* lse, float* nllw, float* nllw0, float* loss,
+                             float* nll, hipStream_t st);
 int ssc_decode_att_table_enabled();   // the "dec_att_table" switch (decode.hip)
 // the start of a one-call decode with the early-stop protocol (search.hip): ctl[0] = max_steps, the counters behind it zero;
 // tokens0 (B) = end_index, the token the first step feeds - or, with a start state (ssc_start_state), its tokens, an id outside

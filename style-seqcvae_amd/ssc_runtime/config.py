@@ -148,6 +148,11 @@ def _defaults() -> dict:
             # mean of their log-probs), as in ensemble decoding.  Not together with scheduled sampling; self-critical steps and
             # validation never distil
             "DISTILL_ALPHA": 0.0, "DISTILL_TEMPERATURE": 1.0, "DISTILL_MODE": "prob",
+            # token-level unlikelihood training of the cross-entropy steps (Welleck et al. 2020): a word's loss gains
+            # UNLIKELIHOOD_ALPHA * (- sum log(1 - p[c])) over the words c its caption has already used, the word's own target left
+            # out - the training-side remedy for repetition; a finite number >= 0, 0 = off.  Not together with DISTILL_ALPHA > 0;
+            # self-critical steps and validation never apply it
+            "UNLIKELIHOOD_ALPHA": 0.0,
         },
     }
 
@@ -298,6 +303,11 @@ class Config(object):
             raise ValueError(f"OPTIM.DISTILL_TEMPERATURE must be a finite number > 0; found {o.DISTILL_TEMPERATURE!r}")
         if o.DISTILL_MODE not in ("prob", "logprob"):
             raise ValueError(f"OPTIM.DISTILL_MODE must be one of prob | logprob; found {o.DISTILL_MODE!r}")
+        if not num(o.UNLIKELIHOOD_ALPHA) or not 0.0 <= o.UNLIKELIHOOD_ALPHA < float("inf"):
+            raise ValueError(f"OPTIM.UNLIKELIHOOD_ALPHA must be a finite number >= 0; found {o.UNLIKELIHOOD_ALPHA!r}")
+        if o.UNLIKELIHOOD_ALPHA > 0 and o.DISTILL_ALPHA > 0:
+            raise ValueError(f"OPTIM.UNLIKELIHOOD_ALPHA {o.UNLIKELIHOOD_ALPHA} and OPTIM.DISTILL_ALPHA {o.DISTILL_ALPHA} cannot both be "
+                             "positive: unlikelihood training and distillation do not compose")
 
     def __getattr__(self, attr: str):
         return getattr(self.__dict__["_C"], attr)

@@ -185,6 +185,34 @@ def check_distill_sampling(alpha, ss_prob):
                          "in one forward: the teacher's rows are those of the ground-truth inputs")
 
 
+def check_unlikelihood(alpha, min_one_minus=1e-5) -> Tuple[float, float]:
+    """(alpha a finite number >= 0, min_one_minus in (0, 1)) as floats - the weight and the clamp of ssc_unlikelihood (include/ssc.h)
+    -, else a ValueError that names unlikelihood / unlikelihood_clamp."""
+    try:
+        a = float(alpha)
+    except (TypeError, ValueError):
+        a = float("nan")
+    if isinstance(alpha, bool) or not 0.0 <= a < float("inf"):
+        raise ValueError(f"unlikelihood must be a finite number >= 0; found {alpha!r}")
+    try:
+        d = float(min_one_minus)
+    except (TypeError, ValueError):
+        d = float("nan")
+    if isinstance(min_one_minus, bool) or not 0.0 < d < 1.0:
+        raise ValueError(f"unlikelihood_clamp must be a number in (0, 1); found {min_one_minus!r}")
+    return a, d
+
+
+def check_unlikelihood_distill(unlikelihood, distill_alpha):
+    """Unlikelihood training and distillation do not compose (include/ssc.h: ssc_train_fwd_unlike): a ValueError that names both."""
+    if float(unlikelihood) > 0.0 and float(distill_alpha) > 0.0:
+        raise ValueError(f"unlikelihood training (unlikelihood = {unlikelihood}) and distillation (distill_alpha = {distill_alpha}) "
+                         "cannot be used in one forward")
+
+
+UNLIKELIHOOD_MAX_STEPS = 256   # ssc_ce_fwd_unlike: one lane of a workgroup per context position
+
+
 FREE_BITS_MODES = {"element": 1, "step": 2, "dim": 3}   # ssc_free_bits.mode / ssc_train_opts.free_bits_mode
 
 
@@ -204,11 +232,13 @@ def check_free_bits(x, mode="dim", name="free_bits") -> Tuple[float, int]:
 
 class _FwdOpts(NamedTuple):
     """The ssc_train_opts of one forward (c) and what it points into - the ssc_sched_sampling, the ssc_distill and the teacher's
-    scores tensor, each None where the option is off -, referenced until the last backward of that forward."""
+    scores tensor -, and the ssc_unlikelihood that travels beside it; each None where the option is off, referenced until the last
+    backward of that forward."""
     c: _lib.TrainOpts
     sched: Optional[_lib.SchedSampling]
     distill: Optional[_lib.Distill]
     scores: Optional[Distill]
+    unlikelihood: Optional[_lib.Unlikelihood] = None
 
 
 OPTIM_KINDS = ("sgd", "adam", "adamw")
@@ -400,6 +430,7 @@ class TrainEngine:
         self._kld = None              # the kld tensor the last forward returned (kld_raw() without a floor)
         self._opts = _FwdOpts(_lib.TrainOpts(), None, None, None)   # the options of the last forward: every backward of it is given the same
         self._kd_scratch = None       # 3*T*B + B floats: the descriptor's rows blocks and kd_b
+        self._ul_scratch = None       # 2*T*B + B floats: ssc_unlikelihood's rows blocks and ul_b
         self._post_ws = None          # posterior_forward's own workspace: the training forward's activations are never overwritten
         self._post_ws_key = None
         self._post = None
@@ -481,7 +512,7 @@ class TrainEngine:
         return bt, (sent, obj_atts)
 
     def forward(self, feats, caps, sentiment, eps, obj_atts=None, label_smoothing=0.0, free_bits=0.0, free_bits_mode="dim",
-                ss_prob=0.0, ss_sampler=None, ss_seed=0, distill: "Optional[Distill]" = None):
+                ss_prob=0.0, ss_sampler=None, ss_seed=0, distill: "Optional[Distill]" = None, unlikelihood=0.0, unlikelihood_clamp=1e-5):
         """-> (loss (B,), kld (B,)); keeps activations for backward().  obj_atts (B,R,S): per-region attribute means, kld_mode 2 only.
         label_smoothing: eps of THIS call's cross-entropy (ssc_ce_fwd_smooth; 0 = the plain masked NLL, the kernels as they are
         without it).  It stays in the engine's cfg until the next forward, so every backward of this forward - the phased one of
@@ -497,21 +528,32 @@ class TrainEngine:
         distill: the soft targets of THIS call (Distill; include/ssc.h: ssc_distill) - loss is then (1 - alpha) * the (smoothed)
         hard loss + alpha * tau^2 KL(teacher || student) per row, kd() the KL term alone, nll() unchanged.  None or alpha 0 = off:
         the cross-entropy as before.  Kept beside the cfg until the next forward, as the options above are.  Not together with
-        ss_prob > 0 (ValueError)."""
+        ss_prob > 0 (ValueError).
+        unlikelihood / unlikelihood_clamp: token-level unlikelihood training of THIS call (include/ssc.h: ssc_unlikelihood) - each row
+        adds unlikelihood * (- sum over the caption's earlier words c, the row's own target left out, of log max(1 - p[c],
+        unlikelihood_clamp)) to its (smoothed) loss; ul() is that term alone, nll() unchanged.  0 = off: the cross-entropy as before.
+        Kept beside the cfg until the next forward, as the options above are.  Composes with everything but distill (ValueError)."""
         check_distill_sampling(distill.alpha if distill is not None else 0.0, ss_prob)
+        ul_alpha, ul_clamp = check_unlikelihood(unlikelihood, unlikelihood_clamp)
+        check_unlikelihood_distill(ul_alpha, distill.alpha if distill is not None else 0.0)
         self._cfg.label_smoothing = check_label_smoothing(label_smoothing)
         fb = check_free_bits(free_bits, free_bits_mode)
         ss = check_sched_sampling(ss_prob, ss_sampler, ss_seed)
         bt, sent = self._batch(feats, caps, sentiment, eps, obj_atts)
         kd = self._distill_desc(distill, (bt.L + 1) * bt.B, bt.B)
+        ul = self._unlikelihood_desc(ul_alpha, ul_clamp, bt.L + 1, bt.B)
         self._opts = _FwdOpts(_lib.TrainOpts(*fb, C.pointer(ss) if ss is not None else None, C.pointer(kd) if kd is not None else None),
-                              ss, kd, distill)
+                              ss, kd, distill, ul)
         ws = self._workspace(bt.B, bt.R, bt.L)
         loss = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         kld = torch.empty(bt.B, dtype=torch.float32, device=self.device)
         p = self.params.c_struct()
-        self.lib.ssc_train_fwd_opts(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
-                                    _lib.ptr(kld), C.byref(self._opts.c), _lib.stream_ptr())
+        if ul is not None:   # (the descriptor travels beside the opts: include/ssc.h, ssc_train_fwd_unlike)
+            self.lib.ssc_train_fwd_unlike(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                          _lib.ptr(kld), C.byref(self._opts.c), C.byref(ul), _lib.stream_ptr())
+        else:
+            self.lib.ssc_train_fwd_opts(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(loss),
+                                        _lib.ptr(kld), C.byref(self._opts.c), _lib.stream_ptr())
         self._keep = (bt, feats, caps, sent, eps)
         self._kld = kld
         self.fwd_version += 1
@@ -541,8 +583,35 @@ class TrainEngine:
             return torch.zeros(B, dtype=torch.float32, device=self.device)
         return self._kd_scratch[self._kd_scratch.numel() - B:]
 
+    def _unlikelihood_desc(self, alpha, clamp, T, B) -> "Optional[_lib.Unlikelihood]":
+        """ssc_unlikelihood of a forward over T steps of B captions, or None where the term is off; the scratch is the engine's."""
+        if alpha == 0.0:
+            return None
+        if T > UNLIKELIHOOD_MAX_STEPS:
+            raise ValueError(f"unlikelihood training handles captions of at most {UNLIKELIHOOD_MAX_STEPS} steps; found {T}")
+        rows = T * B
+        n = 2 * rows + B
+        if self._ul_scratch is None or self._ul_scratch.numel() != n:
+            self._ul_scratch = torch.zeros(n, dtype=torch.float32, device=self.device)
+        sc = self._ul_scratch
+        return _lib.Unlikelihood(alpha, clamp, sc.data_ptr(), sc[2 * rows:].data_ptr())
+
+    def ul(self):
+        """(B,) ul_b of the last forward - n_b sum_t w ul_row / (n_b + 1e-13), not weighted by alpha -: a view of the engine's
+        scratch, valid until the next forward with the term on; zeros when the last forward had it off."""
+        B = self._keep[0].B
+        if self._opts.unlikelihood is None:
+            return torch.zeros(B, dtype=torch.float32, device=self.device)
+        return self._ul_scratch[self._ul_scratch.numel() - B:]
+
     def _bwd_phases(self, p, bt, ws, gl, gk, g, mask):
-        """One ssc_train_bwd_opts call of the last forward (mask 15: its whole backward), with the cfg and the options of that forward."""
+        """One ssc_train_bwd_opts call of the last forward (mask 15: its whole backward), with the cfg and the options of that forward
+        (ssc_train_bwd_unlike where that forward had the unlikelihood term on)."""
+        ul = self._opts.unlikelihood
+        if ul is not None:
+            self.lib.ssc_train_bwd_unlike(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
+                                          _lib.ptr(gk), C.byref(g), mask, C.byref(self._opts.c), C.byref(ul), _lib.stream_ptr())
+            return
         self.lib.ssc_train_bwd_opts(C.byref(self._cfg), C.byref(p), C.byref(bt), _lib.ptr(ws), ws.numel() * 4, _lib.ptr(gl),
                                     _lib.ptr(gk), C.byref(g), mask, C.byref(self._opts.c), _lib.stream_ptr())
 
@@ -973,7 +1042,7 @@ class TrainEngine:
     def train_step(self, feats, caps, sentiment, eps, lr, kld_weight=750.0, momentum=0.9, weight_decay=0.001,
                    max_norm=12.5, decoder_frozen=False, group=None, obj_atts=None, optim: Optional[OptimSpec] = None,
                    label_smoothing=0.0, kl_beta=1.0, free_bits=0.0, free_bits_mode="dim", ss_prob=0.0, ss_sampler=None, ss_seed=0,
-                   distill: "Optional[Distill]" = None):
+                   distill: "Optional[Distill]" = None, unlikelihood=0.0, unlikelihood_clamp=1e-5):
         """fwd + bwd + (all-reduce) + clip + SGD: one iteration of train.py:154-176.  Returns (loss, kld) per row.
         optim: another optimiser behind the clip (OptimSpec); None = SGD with the arguments above.
         label_smoothing: as forward(); loss is then the smoothed one, nll() the unsmoothed.
@@ -981,12 +1050,13 @@ class TrainEngine:
         kld_weight, so the upstream of kld_b is kl_beta / (B * kld_weight); 0 is legal: no KL gradient at all.
         free_bits / free_bits_mode: as forward(); kld is then the floored KL, kld_raw() the raw one.
         ss_prob / ss_sampler / ss_seed: scheduled sampling, as forward().
-        distill: soft targets, as forward(); loss is then the mixed one, kd() the KL term, nll() the hard loss."""
+        distill: soft targets, as forward(); loss is then the mixed one, kd() the KL term, nll() the hard loss.
+        unlikelihood / unlikelihood_clamp: as forward(); loss then carries the weighted term, ul() the term alone."""
         kl_beta = float(kl_beta)
         if not 0.0 <= kl_beta < float("inf"):
             raise ValueError(f"kl_beta must be a finite number >= 0; found {kl_beta!r}")
         loss, kld = self.forward(feats, caps, sentiment, eps, obj_atts, label_smoothing, free_bits, free_bits_mode, ss_prob, ss_sampler,
-                                 ss_seed, distill)
+                                 ss_seed, distill, unlikelihood, unlikelihood_clamp)
         B = loss.numel()
         key = (B, float(kld_weight))
         if getattr(self, "_upstream_key", None) != key:   # d(mean loss + beta mean kld / KLD_WEIGHT) / d(loss_b, kld_b): two (B,) buffers per (B, weight)

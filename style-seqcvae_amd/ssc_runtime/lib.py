@@ -185,6 +185,10 @@ class Distill(C.Structure):
     _fields_ = [("teacher", vp), ("ldt", C.c_int), ("alpha", C.c_float), ("temperature", C.c_float), ("rows", vp), ("kd", vp)]
 
 
+class Unlikelihood(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("min_one_minus", C.c_float), ("rows", vp), ("ul", vp)]
+
+
 class TrainOpts(C.Structure):
     _fields_ = [("free_bits", C.c_float), ("free_bits_mode", C.c_int), ("sched", C.POINTER(SchedSampling)),
                 ("distill", C.POINTER(Distill))]
@@ -329,6 +333,10 @@ SYMBOLS = {
     "ssc_train_fwd_opts": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(TrainOpts), vp]),
     "ssc_train_bwd_opts": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
                                 C.c_uint, C.POINTER(TrainOpts), vp]),
+    "ssc_train_fwd_unlike": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(TrainOpts),
+                                  C.POINTER(Unlikelihood), vp]),
+    "ssc_train_bwd_unlike": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(Batch), vp, _sz, vp, vp, C.POINTER(Params),
+                                  C.c_uint, C.POINTER(TrainOpts), C.POINTER(Unlikelihood), vp]),
     "ssc_train_workspace_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
     "ssc_train_free_bits_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
     "ssc_xgmi_enable_peer": (_i, [_i]),
@@ -368,6 +376,8 @@ SYMBOLS = {
     "ssc_train_sched_view": (vp, [C.POINTER(ModelCfg), _i, _i, _i, vp, _i, C.POINTER(C.c_int)]),
     "ssc_ce_fwd_distill": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Distill), vp, vp, vp, vp]),
     "ssc_ce_bwd_distill": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Distill), vp]),
+    "ssc_ce_fwd_unlike": (_i, [vp, _i, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Unlikelihood), vp, vp, vp, vp]),
+    "ssc_ce_bwd_unlike": (_i, [vp, _i, vp, vp, vp, vp, vp, _i, _i, _i, _f, C.POINTER(Unlikelihood), vp]),
     "ssc_score_rows": (_i, [vp, _i, _i, _i, vp, vp, _i, vp, vp, vp, vp]),
     "ssc_decode_score_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(ScoreDesc)]),
     "ssc_decode_score": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), vp, _sz, vp]),

@@ -21,7 +21,7 @@ from ssc_runtime.cellops import cell_train_step
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.decoding import select_best_beam_with_constraints
 from ssc_runtime.engine import FIELD_OF, ModelDims, TrainEngine, check_free_bits, check_label_smoothing, check_sched_sampling
-from ssc_runtime.engine import check_distill, check_distill_sampling
+from ssc_runtime.engine import check_distill, check_distill_sampling, check_unlikelihood, check_unlikelihood_distill
 
 from ..modules import ConstrainedBeamSearch, UpDownCell
 
@@ -30,8 +30,10 @@ class _SeqCVAETrainFn(torch.autograd.Function):
     """loss_b, kld_b = f(params; feats, caps, sentiment, eps) with the hand-derived BPTT as backward."""
 
     @staticmethod
-    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, ss, distill, *params):
-        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *ss, distill=distill)
+    def forward(ctx, eng, names, feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, ss, distill, unlikelihood,
+                *params):
+        loss, kld = eng.forward(feats, caps, sentiment, eps, obj_means, label_smoothing, free_bits, free_bits_mode, *ss, distill=distill,
+                                unlikelihood=unlikelihood[0], unlikelihood_clamp=unlikelihood[1])
         ctx.eng, ctx.names = eng, names
         ctx.version = eng.fwd_version
         return loss, kld
@@ -42,7 +44,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
         if eng.fwd_version != ctx.version:
             raise RuntimeError("UpDownCaptioner: backward() after a newer forward(); the activation workspace holds "
                                "only the latest forward")
-        need = ctx.needs_input_grad[12:]
+        need = ctx.needs_input_grad[13:]
         skip = [n for n, k in zip(ctx.names, need) if not k]
         eng.backward(gl, gk, skip=skip)
         if eng.dp_autograd:   # data parallel on the autograd path: ONE sum all-reduce of the flat gradient buffer, then the mean
@@ -51,7 +53,7 @@ class _SeqCVAETrainFn(torch.autograd.Function):
                 eng.grads.flat.mul_(1.0 / world)
         frozen = set(eng.frozen_names)
         grads = tuple(eng.grads.views[n].clone() if (k and n not in frozen) else None for n, k in zip(ctx.names, need))
-        return (None,) * 12 + grads
+        return (None,) * 13 + grads
 
 
 class UpDownCaptioner(nn.Module):
@@ -60,7 +62,7 @@ class UpDownCaptioner(nn.Module):
                  prior_std=None, simple_vae=False, latent_embedding=None, latent_embedding_multip=1,
                  sentiment_vae=False, senti_prior_multip=1, cbs_simple=False, device=None, mean_choice=None, sampler=None,
                  sampled_beam=False, diverse_beam=None, label_smoothing=0.0, decode_rules=None, free_bits=0.0,
-                 free_bits_mode="dim"):
+                 free_bits_mode="dim", unlikelihood=0.0, unlikelihood_clamp=1e-5):
         """Same parameters as the reference (updown_captioner.py:21-41) plus `mean_choice` (SENTIMENT_VAE = 2 only): the attribute
         word -> z_space-vector table the reference builds from files at hard-coded paths (`/path/to/sentiglove10.pkl`,
         `/path/to/wordform_swd_scores.json`, updown_captioner.py:79-93) - and cannot finish building as shipped (`self.senti_glove_5`
@@ -87,8 +89,14 @@ class UpDownCaptioner(nn.Module):
         of the training forward (ssc_latent_fwd_fb) - out["kld"] is then the floored KL and a term at or below its floor has no
         gradient; the KL without the floor is `_engine().kld_raw()`.  "dim" floors the mean over the rows of the call of every latent
         dimension.  0 = off.  Any annealing weight is the caller's multiplier on out["kld"], as KLD_WEIGHT is.  scst_step,
-        score_captions and posterior_score_captions never floor."""
+        score_captions and posterior_score_captions never floor.
+        `unlikelihood` (OPTIM.UNLIKELIHOOD_ALPHA, a finite number >= 0) / `unlikelihood_clamp` (in (0, 1)): token-level unlikelihood
+        training of the training forward (Welleck et al. 2020; ssc_ce_fwd_unlike) - every word adds `unlikelihood` times
+        - sum log max(1 - p[c], unlikelihood_clamp) over the words c its caption has already used (its own target left out) to its
+        loss; out["ul"] is that term alone, unweighted.  0 = off.  Not together with distill().  scst_step, score_captions and
+        posterior_score_captions never apply it."""
         super().__init__()
+        self.unlikelihood, self.unlikelihood_clamp = check_unlikelihood(unlikelihood, unlikelihood_clamp)
         self.label_smoothing = check_label_smoothing(label_smoothing)
         self.free_bits = check_free_bits(free_bits, free_bits_mode)[0]
         self.free_bits_mode = free_bits_mode
@@ -212,7 +220,7 @@ class UpDownCaptioner(nn.Module):
                     sampled_beam=kwargs.get("sampler") is not None and sampling.sampled_beam_from_config(_C.MODEL),
                     diverse_beam=kwargs.get("diverse_beam"), label_smoothing=_C.OPTIM.LABEL_SMOOTHING,
                     decode_rules=sampling.decode_rules_from_config(_C.MODEL, vocabulary), free_bits=_C.OPTIM.FREE_BITS,
-                    free_bits_mode=_C.OPTIM.FREE_BITS_MODE)
+                    free_bits_mode=_C.OPTIM.FREE_BITS_MODE, unlikelihood=_C.OPTIM.UNLIKELIHOOD_ALPHA)
         model.n_z_samples = max(1, int(_C.MODEL.N_Z_SAMPLES))   # default latent sample count of score_captions
         model.decode_attention(_C.MODEL.DECODE_ATTENTION)
         if model.sampler is not None and not model.sampler.beam_search and not model.sampled_beam:
@@ -357,11 +365,15 @@ class UpDownCaptioner(nn.Module):
             if self._distill is not None:   # the teachers' forwards on this minibatch and this noise, ahead of the student's
                 teacher, alpha, temperature = self._distill
                 check_distill_sampling(alpha, self._sched_sampling[0])
+                check_unlikelihood_distill(self.unlikelihood, alpha)
                 kd = teacher.distill(feats, caps, sent, eps, alpha, temperature, obj_means)
             loss, kld = _SeqCVAETrainFn.apply(eng, names, feats, caps, sent, eps, obj_means, self.label_smoothing,
-                                              self.free_bits, self.free_bits_mode, self._sched_sampling, kd, *params)
+                                              self.free_bits, self.free_bits_mode, self._sched_sampling, kd,
+                                              (self.unlikelihood, self.unlikelihood_clamp), *params)
             if kd is not None:
                 return {"loss": loss, "kld": kld, "kd": eng.kd().clone()}
+            if self.unlikelihood > 0:
+                return {"loss": loss, "kld": kld, "ul": eng.ul().clone()}
             return {"loss": loss, "kld": kld}
         # eval branch (updown_captioner.py:324-366)
         start_predictions = torch.full((batch_size,), self._boundary_index, dtype=torch.long, device=dev)
