@@ -1459,6 +1459,53 @@ int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Truncation for the word samplers: cuts that adapt to each step's entropy - locally typical sampling (Meister et al. 2022), min-p
+ * (Nguyen et al. 2024), eta and epsilon sampling (Hewitt et al. 2022).  Like the logit rules, a truncation edits the RAW logits of
+ * a row in place, in front of the unchanged draw: ssc_sample_rows then draws from the edited row and its log-prob is the
+ * untempered log-softmax of the EDITED row.  ssc_sampler_desc and the samplers are untouched; ssc_version() stays 4.
+ * With T the sampler's temperature, over the finite entries of x[0 .. V): q = softmax(x / T), s_v = -log q_v,
+ * H = -sum_v q_v log q_v (nats).  The kinds:
+ *   0  off.
+ *   1  typical(tau), tau in (0, 1]: the entries in ascending order of d_v = |s_v - H|, equal d by the lower index first; v is kept
+ *      iff it is first in that order or the mass q strictly ahead of it is < tau - the rule of top-p, on another order.  Masses in
+ *      2^-40 fixed point; entries that share the cut's d are taken to share one mass (top-p's rule, exact for equal logits).
+ *      tau = 1 keeps every finite entry.
+ *   2  min-p(m), m in (0, 1]: kept iff (x_v - max x) / T >= log m, i.e. q_v >= m max_u q_u.  Every maximal entry is kept.
+ *   3  eta(eps), eps in (0, 1): eta = min(eps, sqrt(eps) exp(-H)); kept iff log q_v >= log eta, or v is the lowest-index maximum.
+ *   4  epsilon(eps), eps in (0, 1): kept iff log q_v >= log eps, or v is the lowest-index maximum.
+ * A dropped entry becomes -inf, a kept one keeps its bits.  An entry that arrives as -inf (a ban of the logit rules) stays dropped
+ * and weighs nothing in Z and H.  A row without a finite entry is left as it is (statistics 0); NaN and +inf are the caller's
+ * error (the call still ends and stays inside the row).  A row whose last token is END (last_pred[r] == end_index) is neither read
+ * nor written (statistics 0); columns V .. ld - 1 are never touched.  One workgroup per row, the row staged in LDS for
+ * V <= 32768 and walked in global memory above; 16-byte accesses where the row is 16-byte aligned with V % 4 == 0, scalar ones
+ * otherwise - the result does not depend on which.  Reductions in a fixed order, integer histograms: two calls on equal inputs are
+ * bit-identical.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  int kind;          /* 0 off, 1 typical, 2 min-p, 3 eta, 4 epsilon */
+  float value;       /* tau / m in (0, 1]; eps in (0, 1) */
+  float* entropy;    /* per row: H in nats, or NULL */
+  int* kept;         /* per row: the number of entries left finite, or NULL */
+} ssc_truncation;
+/* The edit of `rows` rows of raw logits (rows, V) ld `ld`; entropy / kept: (rows) or NULL.  last_pred (rows) or NULL: the rows'
+ * previous tokens.  SSC_EINVAL before any launch: a NULL logits or tr, kind outside 0 .. 4, a value outside its range or NaN
+ * (kind 0 reads none), temperature <= 0 or not finite, rows < 0, V < 1, ld < V, end_index outside [0, V) with a last_pred.
+ * SSC_EALIGN: logits, last_pred, entropy or kept no multiple of 4.  kind 0: SSC_OK with no launch. */
+int ssc_truncate_rows(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature, const int64_t* last_pred,
+                      int end_index, void* stream);
+/* ssc_decode_sample_rules with one ssc_truncate_rows launch per step, step 0 included, between the rules' edit and the draw:
+ * per step the logit rules, then the truncation, then the sampler's own top-k / top-p, all on the distribution tempered by
+ * s->temperature; last_pred is the previous step's words.  Here trunc->entropy / trunc->kept are (max_steps, B) blocks or NULL:
+ * step t writes slab t, slabs of steps never queued (early_stop) are not written.  trunc NULL or kind 0: the launches and the
+ * bits of ssc_decode_sample_rules, which is this call with trunc = NULL.  The workspace is that of ssc_decode_sample.
+ * d->log_probs sums the log-probs under the edited distributions.  SSC_EINVAL before any launch: what ssc_decode_sample_rules
+ * refuses; kind outside 0 .. 4; a value outside its range.  SSC_EALIGN: entropy or kept no multiple of 4. */
+size_t ssc_decode_sample_trunc_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
+int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                            const ssc_logit_rules* rules, const ssc_truncation* trunc, const ssc_latent_guide* guide,
+                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Prompted decoding: start the one-call decodes from a forced prefix ("a happy ...").  ssc_decode_prime teacher-forces the prefix
  * on the B = nimg * n_samples rows of a call - the loop of ssc_decode_score, leaving STATES instead of only scores -, its outputs
  * are an ssc_start_state for any search or sampled decode over the same B entries, and ssc_prefix_join puts prefix and

@@ -107,6 +107,11 @@ parser.add_argument("--word-bias", default="",
                          'step of every image, in front of the draw ("-inf" bans the word; a word outside the vocabulary is an error). '
                          "Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without SAMPLED_BEAM_SEARCH; composes with the "
                          "MODEL.SAMPLER_* logit rules")
+parser.add_argument("--truncation", default="",
+                    help="truncation for word sampling: KIND[:VALUE] with KIND typical | min-p | eta | epsilon, e.g. --truncation "
+                         "typical:0.9 (default: MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE) - every step's distribution is cut "
+                         "between the logit rules and the draw.  Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without "
+                         "SAMPLED_BEAM_SEARCH")
 parser.add_argument("--prefix", default="",
                     help='prompted decoding: words every caption starts with, e.g. --prefix "a happy" - one prompt for every image '
                          "(default: MODEL.DECODE_PREFIX).  The prompt is teacher-forced, the configured decoder continues from it; "
@@ -176,6 +181,28 @@ def check_word_bias_args(_A, model_cfg=None):
         if kind not in sampling.KINDS or model_cfg.SAMPLED_BEAM_SEARCH or model_cfg.STOCHASTIC_BEAM_SEARCH:
             raise SystemExit("--word-bias needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
                              f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
+
+
+def check_truncation_args(_A, model_cfg=None):
+    """--truncation KIND[:VALUE], checked before anything is loaded -> its sampling.Truncation, or None without the flag; with
+    model_cfg (the MODEL node) also that the run samples words."""
+    if not _A.truncation:
+        return None
+    name, _, value = _A.truncation.partition(":")
+    try:
+        tr = sampling.truncation_from_name(name, float(value) if value.strip() else None)
+    except ValueError as e:
+        raise SystemExit(f"--truncation: {e}")
+    if tr is None:
+        return None
+    if _A.ensemble_checkpoints:
+        raise SystemExit("--truncation is not available with --ensemble-checkpoints: an ensemble runs the beam search only")
+    if model_cfg is not None:
+        kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+        if kind not in sampling.KINDS or model_cfg.SAMPLED_BEAM_SEARCH or model_cfg.STOCHASTIC_BEAM_SEARCH:
+            raise SystemExit("--truncation needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                             f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
+    return tr
 
 
 def check_prefix_args(_A):
@@ -253,8 +280,10 @@ def main():
     ens_weights, ens_mode = check_ensemble_args(_A)
     jitter = check_exemplar_args(_A)
     check_word_bias_args(_A)
+    check_truncation_args(_A)
     _C = Config(_A.config, _A.config_override)
     check_word_bias_args(_A, _C.MODEL)
+    truncation = check_truncation_args(_A, _C.MODEL)
     prompt = _A.prefix or ("" if prompts is not None else str(_C.MODEL.DECODE_PREFIX).strip())
     if (prompt or prompts is not None) and not _A.prefix and not _A.prefix_json:   # (MODEL.DECODE_PREFIX: the flags' refusals apply)
         _A.prefix = prompt
@@ -292,6 +321,9 @@ def main():
                                                  presence_penalty=logit_rules.presence_penalty,
                                                  frequency_penalty=logit_rules.frequency_penalty)
         logit_rules = sampling.LogitRules(bias=load_word_bias(_A.word_bias, vocabulary).to(device), **kw)
+    # --truncation, else MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE: the cut of the word-sampled decode's distribution
+    if not _A.truncation:
+        truncation = sampling.truncation_from_config(_C.MODEL)
     # --prefix / --prefix-json / MODEL.DECODE_PREFIX: every image's prompt as word ids, padded to the longest (-1)
     prefix_ids = None
     if prompt or prompts is not None:
@@ -445,7 +477,8 @@ def main():
                 out = diverse_decode(dec, feats, senti, n_z, beam, _C.DATA.MAX_CAPTION_LENGTH, boundary, fsm=fsm,
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode,
-                                     guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}), **pkw)
+                                     guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}),
+                                     **({"truncation": truncation} if truncation is not None else {}), **pkw)
                 pred = out[0]
             trace = out[-1] if attn_mode else None
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the

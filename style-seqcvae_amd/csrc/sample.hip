@@ -11,6 +11,8 @@
 // resolved by a second radix select on the index (lower index first).  The draw is Gumbel-max over the kept set with
 // counter-based Philox4x32-10 noise: bit-reproducible for a given seed, no float atomics, no order-dependent reduction.
 // The draw of one row (sample_draw_row) lives in sample_draw.h: the scheduled-sampling mix kernel of the train step calls the same code.
+// The edits of the raw logits in front of the draw - the logit rules (logit_rules.hip) and the truncation (truncation.hip) - are launches
+// of their own between a step's decode step and its draw (ssc_decode_sample_trunc); the draw itself does not know of them.
 // ssc_decode_sample's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
 
@@ -202,6 +204,18 @@ extern "C" size_t ssc_decode_sample_rules_workspace_bytes(const ssc_model_cfg* c
 extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
                                        const ssc_sampler_desc* s, const ssc_logit_rules* rules, const ssc_latent_guide* guide,
                                        void* workspace, size_t workspace_bytes, void* stream) {
+  return ssc_decode_sample_trunc(cfg, p, d, s, rules, nullptr, guide, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t ssc_decode_sample_trunc_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  return ssc_decode_sample_workspace_bytes(cfg, d);   // the edit is in place and keeps nothing between the steps
+}
+
+// trunc (or null): the truncation of include/ssc.h, one launch between each step's logit rules and its draw; step t's statistics go
+// to slab t of trunc->entropy / trunc->kept
+extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                       const ssc_sampler_desc* s, const ssc_logit_rules* rules, const ssc_truncation* trunc,
+                                       const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
   if (guide && !ssc_latent_guide_ok(cfg, guide)) return SSC_EINVAL;
@@ -211,11 +225,19 @@ extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_param
     SSC_TRY(ssc_logit_rules_check(rules, cfg->V, d->end_index, &ruled));
     if (ruled && (d->max_steps > SSC_RULES_MAX_LEN || (long)cfg->V <= (long)d->max_steps + rules->n_suppress)) return SSC_EINVAL;
   }
+  bool cut = false;
+  if (trunc) SSC_TRY(ssc_truncation_check(trunc, s->temperature, &cut));
   const SampleLayout l = sample_layout(cfg, d);
   if (workspace_bytes < l.total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* W = (char*)workspace;
   const int B = d->nimg * d->n_samples, V = cfg->V, Z = cfg->Z;
+  // step t's truncation: the statistics of slab t
+  auto truncate = [&](int t, const int64_t* last) {
+    return ssc_truncation_launch((float*)(W + l.logits), V, B, V, trunc, s->temperature,
+                                 trunc->entropy ? trunc->entropy + (size_t)t * B : nullptr,
+                                 trunc->kept ? trunc->kept + (size_t)t * B : nullptr, last, d->end_index, st);
+  };
   const SscStepStates& states = l.states;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
   int64_t* parent0 = (int64_t*)(W + l.parent0);
@@ -244,6 +266,7 @@ extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_param
   SscStepGuide sg{guide, 0, 1};
   SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
   if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, 0, d->end_index, st));
+  if (cut) SSC_TRY(truncate(0, nullptr));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
   a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
   a.ctl = d->early_stop ? ctl : nullptr; a.max_steps = d->max_steps; a.host_flag = d->early_stop ? d->host_flag : nullptr;
@@ -263,6 +286,7 @@ extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_param
     sg.t = t;
     SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
     if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, t, d->end_index, st));
+    if (cut) SSC_TRY(truncate(t, last));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
     SSC_TRY(sample_launch(a, B, st));
     cur = 1 - cur;

@@ -223,5 +223,11 @@ int ssc_decode_step_guided(const ssc_model_cfg* cfg, const ssc_params* p, const 
 int ssc_logit_rules_check(const ssc_logit_rules* r, int V, int end_index, bool* active);
 int ssc_logit_rules_launch(float* logits, int ld, int rows, int V, const ssc_logit_rules* r, const int64_t* hist, int ld_hist, int t,
                            int end_index, hipStream_t st);
+// Truncation for the word samplers (truncation.hip, include/ssc.h: ssc_truncation).  ssc_truncation_check: the refusals that depend
+// on the fields and the temperature alone (SSC_OK with *active = kind != 0); ssc_truncation_launch: the edit of one step from a
+// checked descriptor, its statistics going to `entropy` / `kept` (rows, or null) - what ssc_decode_sample_trunc issues per step.
+int ssc_truncation_check(const ssc_truncation* tr, float temperature, bool* active);
+int ssc_truncation_launch(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature, float* entropy, int* kept,
+                          const int64_t* last_pred, int end_index, hipStream_t st);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

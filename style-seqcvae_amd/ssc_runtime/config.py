@@ -103,6 +103,13 @@ def _defaults() -> dict:
             # SAMPLER_FREQUENCY_PENALTY (0 = off): presence + frequency * count is taken off such a logit
             "SAMPLER_NO_REPEAT_NGRAM": 0, "SAMPLER_MIN_LENGTH": 0, "SAMPLER_SUPPRESS_UNKNOWN": False,
             "SAMPLER_REPETITION_PENALTY": 1.0, "SAMPLER_PRESENCE_PENALTY": 0.0, "SAMPLER_FREQUENCY_PENALTY": 0.0,
+            # truncation of the word samplers (ssc_runtime/sampling.py Truncation; ssc_truncation): a cut that adapts to each step's
+            # entropy, made on the raw logits between the logit rules and the draw.  "none" (default), "typical" (locally typical
+            # sampling: the words whose surprise is closest to the entropy, up to a mass of VALUE, default 0.9), "min-p" (at least
+            # VALUE times the top word's probability, default 0.05), "eta" / "epsilon" (probability at least
+            # min(VALUE, sqrt(VALUE) exp(-entropy)) / VALUE, default 3e-4).  SAMPLER_TRUNCATION_VALUE 0 = the kind's default.  Needs
+            # DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
+            "SAMPLER_TRUNCATION": "none", "SAMPLER_TRUNCATION_VALUE": 0.0,
             # attention traces of the eval decode (ssc_attn_record; DecodeEngine.attention): "none" (default), "summary" - per word
             # of every returned caption the region it attended most, the weight there and the entropy of its attention - or "full"
             # - the whole map over the regions as well.  Any decoder; the captions themselves do not change
@@ -255,6 +262,15 @@ class Config(object):
                 raise ValueError(f"MODEL.SAMPLER_MIN_LENGTH ({s_min}) must be below DATA.MAX_CAPTION_LENGTH ({max_len})")
             if max_len > 64:
                 raise ValueError(f"the logit rules (MODEL.SAMPLER_NO_REPEAT_NGRAM ...) need DATA.MAX_CAPTION_LENGTH <= 64; found {max_len}")
+        if m.SAMPLER_TRUNCATION not in ("none", "typical", "min-p", "eta", "epsilon"):
+            raise ValueError(f"MODEL.SAMPLER_TRUNCATION must be one of none | typical | min-p | eta | epsilon; found {m.SAMPLER_TRUNCATION!r}")
+        tv = m.SAMPLER_TRUNCATION_VALUE
+        if isinstance(tv, bool) or not isinstance(tv, (int, float)) or tv != tv:
+            raise ValueError(f"MODEL.SAMPLER_TRUNCATION_VALUE must be a number; found {tv!r}")
+        hi_ok = tv <= 1 if m.SAMPLER_TRUNCATION in ("typical", "min-p") else tv < 1
+        if m.SAMPLER_TRUNCATION != "none" and not (0 <= tv and hi_ok):   # (0: the kind's default)
+            raise ValueError(f"MODEL.SAMPLER_TRUNCATION_VALUE must lie in (0, 1] for typical / min-p and in (0, 1) for eta / epsilon, "
+                             f"or be 0 for the kind's default; found {tv!r}")
         if m.DECODE_ATTENTION not in ("none", "summary", "full"):
             raise ValueError(f"MODEL.DECODE_ATTENTION must be one of none | summary | full; found {m.DECODE_ATTENTION!r}")
         if not isinstance(m.DECODE_PREFIX, str):

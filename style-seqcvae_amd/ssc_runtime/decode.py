@@ -361,7 +361,8 @@ class DecodeEngine:
 
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
-               attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None):
+               attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None, truncation=None,
+               truncation_stats: bool = False):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
@@ -370,8 +371,17 @@ class DecodeEngine:
         logit_rules: a sampling.LogitRules, or None - every step's raw logits are edited in front of the draw
         (ssc_decode_sample_rules: word bias, repetition / presence / frequency penalties, n-gram / length / token bans) and the
         log-probs are those under the edited distributions; None or inactive rules take the entry point of a call without them.
+        truncation: a sampling.Truncation, or None - every step's raw logits are cut between the logit rules and the draw
+        (ssc_decode_sample_trunc: typical, min-p, eta or epsilon truncation of the distribution tempered by the sampler's
+        temperature); None or an inactive one issues the call without it.  truncation_stats=True (with an active truncation):
+        the result is followed by (entropy (B, steps) float32 in nats, kept (B, steps) int32 - the entries left finite), zero
+        for ended rows and in the columns past the stop.
         skip_dead (default on): ended rows are not stepped; the captions do not depend on it."""
         _start_check(start, guide)
+        if truncation is not None and not truncation.active:
+            truncation = None
+        if truncation_stats and truncation is None:
+            raise ValueError("DecodeEngine.sample: truncation_stats needs an active truncation")
         sampler.check_vocab(self.dims.V)
         sdesc = sampler.desc(seed)
         call = lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), *ws)
@@ -387,8 +397,25 @@ class DecodeEngine:
             call = lambda p, sd, ws: self.lib.ssc_decode_sample_rules(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
                                                                       C.byref(rd), C.byref(gd) if gd is not None else None, *ws)
             workspace_bytes = self.lib.ssc_decode_sample_rules_workspace_bytes
-        return self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
-                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
+        ent = kept = None
+        if truncation is not None:
+            if not (logit_rules is not None and logit_rules.active):
+                rd = None
+            B = ctx.nimg * n_samples
+            if truncation_stats:   # (max_steps, B) blocks; slabs of steps never queued stay zero
+                ent = torch.zeros(max_steps, B, dtype=torch.float32, device=self.device)
+                kept = torch.zeros(max_steps, B, dtype=torch.int32, device=self.device)
+            td = truncation.desc(ent, kept)
+            call = lambda p, sd, ws: self.lib.ssc_decode_sample_trunc(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
+                                                                      C.byref(rd) if rd is not None else None, C.byref(td),
+                                                                      C.byref(gd) if gd is not None else None, *ws)
+            workspace_bytes = self.lib.ssc_decode_sample_trunc_workspace_bytes
+        out = self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
+                             (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
+        if truncation_stats:
+            steps = out[0].size(-1)
+            out = tuple(out) + ((ent[:steps].t().contiguous(), kept[:steps].t().contiguous()),)
+        return out
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,
               eps0: torch.Tensor, eps: Optional[torch.Tensor], want_tokens: bool = False, want_ranks: bool = False,

@@ -27,7 +27,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
                    rules=None, attention: Optional[str] = None, guide=None, logit_rules=None, prefix=None,
-                   prefix_eps: Optional[torch.Tensor] = None):
+                   prefix_eps: Optional[torch.Tensor] = None, truncation=None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -71,6 +71,10 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     (DecodeEngine.sample(logit_rules=): word bias, repetition / presence / frequency penalties, n-gram / length / token bans);
     ValueError with any other decoder, NotImplementedError with an ensemble.  None, or rules with every control off: the plain
     sampled decode.  (`rules` stays the beam search's and keeps refusing a sampler.)
+    truncation: a sampling.Truncation (typical / min-p / eta / epsilon) - with a word sampler every step's distribution is cut
+    between the logit rules and the draw (DecodeEngine.sample(truncation=)); ValueError naming the decoder with any other one,
+    NotImplementedError with an ensemble.  None or an inactive one: the call without it.  Composes with logit_rules, guide, prefix
+    and attention.
     prefix: a DecodePrefix (ssc_runtime.prefix) with one row per image - or per (image, sample) entry -, or None.  With it every
     caption starts with its image's prompt: the prompt is teacher-forced on the nimg * n_samples rows (DecodeEngine.prime), whichever
     decoder was chosen continues from there (start=) and the call returns the FULL captions (nimg, n_samples, Lp + steps) - the
@@ -97,6 +101,19 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         if sampler is None or sampler.beam_search or sampled_beam:
             raise ValueError("the logit rules belong to the word samplers: logit_rules needs a multinomial / top-k / top-p sampler "
                              "without sampled_beam (the beam search takes rules=)")
+    if truncation is not None and not truncation.active:
+        truncation = None
+    if truncation is not None:
+        if isinstance(dec, EnsembleDecodeEngine):
+            raise NotImplementedError("truncation (truncation=) is not implemented for an ensemble (EnsembleDecodeEngine)")
+        other = ("the beam search under decode rules (rules)" if rules is not None and rules.active else
+                 "the diverse beam search (diverse_beam)" if diverse_beam is not None else
+                 "the sampled-node beam search (sampled_beam)" if sampled_beam else
+                 "the stochastic beam search (GumbelSampler)" if sampler is not None and sampler.beam_search else
+                 "the beam search" if sampler is None else None)
+        if other is not None:
+            raise ValueError(f"the truncation belongs to the word samplers: truncation= needs a multinomial / top-k / top-p sampler, "
+                             f"not {other}")
     if guide is not None:
         from .guide import guide_unsupported
         if isinstance(dec, EnsembleDecodeEngine):
@@ -204,6 +221,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         from .prefix import join_prefix
         return join_prefix(primed["ids"], primed["start"], beams, lps, boundary_index)
     rkw = {"logit_rules": logit_rules} if logit_rules is not None else {}
+    if truncation is not None:
+        rkw["truncation"] = truncation
 
     def search(skip_now):
         # the noise of ALL steps is drawn up front - from the caller's list, or from a generator of this call's own seeded by ONE draw

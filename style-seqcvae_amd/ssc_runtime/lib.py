@@ -239,6 +239,10 @@ class LogitRules(C.Structure):
                 ("frequency_penalty", C.c_float), ("bias", vp), ("ld_bias", C.c_int), ("n_bias", C.c_int), ("bias_row", vp)]
 
 
+class Truncation(C.Structure):
+    _fields_ = [("kind", C.c_int), ("value", C.c_float), ("entropy", vp), ("kept", vp)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -415,6 +419,10 @@ SYMBOLS = {
     "ssc_decode_sample_rules_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample_rules": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
                                      C.POINTER(LogitRules), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
+    "ssc_truncate_rows": (_i, [vp, _i, _i, _i, C.POINTER(Truncation), _f, vp, _i, vp]),
+    "ssc_decode_sample_trunc_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
+    "ssc_decode_sample_trunc": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                     C.POINTER(LogitRules), C.POINTER(Truncation), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
     "ssc_decode_prime_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(PrimeDesc)]),
     "ssc_decode_prime": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(PrimeDesc), vp, _sz, vp]),
     "ssc_prefix_join": (_i, [vp, vp, _i, vp, vp, _i, vp, vp, _i, _i, _i, vp, vp, vp]),

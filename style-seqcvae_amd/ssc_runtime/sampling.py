@@ -23,6 +23,10 @@ LogitRules are the word samplers' own controls, a second and separate mechanism:
 front of the draw - a word bias, repetition / presence / frequency penalties, blocked n-grams, a minimum length, suppressed tokens
 (DecodeEngine.sample(logit_rules=) / ssc_decode_sample_rules, MODEL.SAMPLER_NO_REPEAT_NGRAM and its kin) - so that the sampler
 draws from the edited distribution, where DecodeRules ban after the log-softmax and renormalise nothing.
+
+Truncation is the word samplers' entropy-adaptive cut - locally typical, min-p, eta and epsilon sampling - made the same way: one
+more edit of the raw logits between the logit rules and the draw (DecodeEngine.sample(truncation=) / ssc_decode_sample_trunc,
+MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE).  The samplers themselves are unchanged.
 """
 import math
 
@@ -407,6 +411,113 @@ def logit_rules_from_config(model_cfg, vocabulary=None):
         raise ValueError(f"MODEL.SAMPLER_NO_REPEAT_NGRAM / SAMPLER_MIN_LENGTH / SAMPLER_*_PENALTY: {e}") from None
 
 
+TRUNCATION_KINDS = {"none": 0, "typical": 1, "min-p": 2, "eta": 3, "epsilon": 4}
+
+
+class Truncation:
+    """A truncation of the word samplers' distribution (ssc_truncation in include/ssc.h): a cut that adapts to each step's entropy,
+    made on the raw logits of every step between the logit rules and the draw (DecodeEngine.sample(truncation=) /
+    ssc_decode_sample_trunc), so that the sampler - multinomial, top-k or top-p - draws from the cut distribution, tempered by the
+    sampler's temperature, and reports the log-prob under it.  kind: 0 off, 1 typical, 2 min-p, 3 eta, 4 epsilon; value: the mass
+    tau / the ratio m in (0, 1], or epsilon in (0, 1)."""
+    name = "none"
+
+    def __init__(self, kind: int = 0, value: float = 0.0) -> None:
+        if isinstance(kind, bool) or int(kind) != kind or not 0 <= kind <= 4:
+            raise ValueError(f"the truncation kind must be an integer in 0..4, got {kind!r}")
+        kind = int(kind)
+        try:
+            value = float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"the truncation value must be a number, got {value!r}") from None
+        name = [n for n, k in TRUNCATION_KINDS.items() if k == kind][0]
+        if kind in (1, 2) and not (0.0 < value <= 1.0):   # (false for NaN)
+            raise ValueError(f"{name} truncation needs a value in (0, 1], got {value}")
+        if kind in (3, 4) and not (0.0 < value < 1.0):
+            raise ValueError(f"{name} truncation needs an epsilon in (0, 1), got {value}")
+        self.kind = kind
+        self.value = value
+        self.name = name
+
+    @property
+    def active(self) -> bool:
+        return self.kind != 0
+
+    def desc(self, entropy=None, kept=None) -> "_lib.Truncation":
+        """The C struct ssc_truncation; entropy / kept: the statistics tensors of the call, or None."""
+        d = _lib.Truncation()
+        d.kind, d.value = self.kind, self.value
+        d.entropy = entropy.data_ptr() if entropy is not None else None
+        d.kept = kept.data_ptr() if kept is not None else None
+        return d
+
+    def __repr__(self):
+        return f"{type(self).__name__}({self.name}, {self.value})"
+
+
+class TypicalTruncation(Truncation):
+    """Locally typical sampling (Meister et al. 2022): the words whose surprise is closest to the step's entropy, up to `mass`."""
+
+    def __init__(self, mass: float = 0.9) -> None:
+        super().__init__(1, mass)
+
+
+class MinPTruncation(Truncation):
+    """Min-p (Nguyen et al. 2024): the words at least `min_p` times as probable as the most probable one."""
+
+    def __init__(self, min_p: float = 0.05) -> None:
+        super().__init__(2, min_p)
+
+
+class EtaTruncation(Truncation):
+    """Eta sampling (Hewitt et al. 2022): the words with probability at least min(epsilon, sqrt(epsilon) * exp(-entropy))."""
+
+    def __init__(self, epsilon: float = 3e-4) -> None:
+        super().__init__(3, epsilon)
+
+
+class EpsilonTruncation(Truncation):
+    """Epsilon sampling (Hewitt et al. 2022): the words with probability at least `epsilon`."""
+
+    def __init__(self, epsilon: float = 3e-4) -> None:
+        super().__init__(4, epsilon)
+
+
+_TRUNCATION_CLASSES = {"typical": TypicalTruncation, "min-p": MinPTruncation, "eta": EtaTruncation, "epsilon": EpsilonTruncation}
+
+
+def truncation_from_name(name: str, value=None):
+    """"typical" / "min-p" / "eta" / "epsilon" (+ a value, None: the kind's default) -> its Truncation; "none" -> None."""
+    key = str(name).strip().lower()
+    if key == "none":
+        return None
+    if key not in _TRUNCATION_CLASSES:
+        raise ValueError(f"the truncation must be one of none | typical | min-p | eta | epsilon, got {name!r}")
+    return _TRUNCATION_CLASSES[key]() if value is None else _TRUNCATION_CLASSES[key](value)
+
+
+def truncation_from_config(model_cfg):
+    """MODEL.SAMPLER_TRUNCATION (none | typical | min-p | eta | epsilon) / SAMPLER_TRUNCATION_VALUE (0 = the kind's default) ->
+    Truncation, or None when off (no new code path runs then).  The truncation belongs to the word samplers: DECODE_SAMPLER
+    multinomial / top-k / top-p, SAMPLED_BEAM_SEARCH and STOCHASTIC_BEAM_SEARCH False."""
+    name = str(getattr(model_cfg, "SAMPLER_TRUNCATION", "none")).strip().lower()
+    value = float(getattr(model_cfg, "SAMPLER_TRUNCATION_VALUE", 0.0))
+    if name == "none":
+        return None
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if kind not in KINDS:
+        raise ValueError(f"MODEL.SAMPLER_TRUNCATION needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p', got "
+                         f"{model_cfg.DECODE_SAMPLER!r} (the truncation belongs to the word samplers)")
+    for other in ("SAMPLED_BEAM_SEARCH", "STOCHASTIC_BEAM_SEARCH"):
+        if bool(getattr(model_cfg, other, False)):
+            raise ValueError(f"MODEL.SAMPLER_TRUNCATION and MODEL.{other} exclude each other (the truncation belongs to the "
+                             "word-sampled decode)")
+    try:
+        return truncation_from_name(name, None if value == 0 else value)
+    except ValueError as e:
+        raise ValueError(f"MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE: {e}") from None
+
+
 def from_config(model_cfg):
     """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
     STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
@@ -420,6 +531,7 @@ def from_config(model_cfg):
     diverse_beam_from_config(model_cfg)
     decode_rules_from_config(model_cfg)
     logit_rules_from_config(model_cfg)
+    truncation_from_config(model_cfg)
     if sbs and kind != "beam":
         raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
                          "samplers draw one word per row; the stochastic beam search is a kind of beam search)")

@@ -194,6 +194,7 @@ class UpDownCaptioner(nn.Module):
         self._decode_attention = None  # decode_attention(): "summary" / "full" attention traces in the eval forward's output
         self._decode_guide = None      # decode_guide(): a LatentGuide the NEXT eval forwards draw their latents around
         self._logit_rules = None       # logit_rules(): sampling.LogitRules the NEXT eval forwards of a word sampler draw under
+        self._truncation = None        # truncation(): sampling.Truncation the NEXT eval forwards of a word sampler cut their steps with
         self._decode_prefix = None     # decode_prefix(): a DecodePrefix every caption of the NEXT eval forwards starts with
 
     # ------------------------------------------------------------------------------------------------------
@@ -225,6 +226,7 @@ class UpDownCaptioner(nn.Module):
         model.decode_attention(_C.MODEL.DECODE_ATTENTION)
         if model.sampler is not None and not model.sampler.beam_search and not model.sampled_beam:
             model.logit_rules(sampling.logit_rules_from_config(_C.MODEL, vocabulary))
+            model.truncation(sampling.truncation_from_config(_C.MODEL))
         if str(_C.MODEL.DECODE_PREFIX).strip():
             from ssc_runtime.prefix import DecodePrefix
             model.decode_prefix(DecodePrefix.from_words(vocabulary, str(_C.MODEL.DECODE_PREFIX)))
@@ -528,7 +530,8 @@ class UpDownCaptioner(nn.Module):
                              min_constraints_to_satisfy=self._min_constraints_to_satisfy, per_node=per, obj_means=obj_means,
                              sampler=self.sampler, sampled_beam=bool(self.sampled_beam and self.sampler is not None),
                              diverse_beam=self.diverse_beam, rules=self.decode_rules,
-                             logit_rules=self._logit_rules if words else None, prefix=DecodePrefix(ids))
+                             logit_rules=self._logit_rules if words else None, prefix=DecodePrefix(ids),
+                             **({"truncation": self._truncation} if words and self._truncation is not None else {}))
         return {"predictions": out[0][:, 0, :]}
 
     def logit_rules(self, rules):
@@ -549,6 +552,21 @@ class UpDownCaptioner(nn.Module):
             if not rules.active:
                 rules = None
         self._logit_rules = rules
+
+    def truncation(self, truncation):
+        """A truncation for the NEXT eval forwards of a word sampler (ssc_runtime.sampling.Truncation; include/ssc.h:
+        ssc_truncation): every step's distribution is cut - typical, min-p, eta or epsilon - between the logit rules and the draw.
+        None (the default state) or an inactive one: off, the forward is what it is without.  ValueError without a word sampler.
+        Training forwards, scst_step, score_captions and every beam search never read it."""
+        if truncation is not None:
+            if not isinstance(truncation, sampling.Truncation):
+                raise ValueError(f"truncation takes a ssc_runtime.sampling.Truncation or None, got {type(truncation).__name__}")
+            if self.sampler is None or self.sampler.beam_search or self.sampled_beam:
+                raise ValueError("truncation needs a word sampler (MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                                 "MODEL.SAMPLED_BEAM_SEARCH): the truncation belongs to the word-sampled decode")
+            if not truncation.active:
+                truncation = None
+        self._truncation = truncation
 
     def reconstruct_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, beam: Optional[int] = None,
                              eps=None, prior_samples: int = 4, prior_seed: Optional[int] = None):
@@ -695,7 +713,8 @@ class UpDownCaptioner(nn.Module):
         sent = sentiment.reshape(B) if sentiment is not None else None
         pred, _, *rec = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed,
                                          attention=self._decode_attention is not None, guide=self._decode_guide,
-                                         **({"logit_rules": self._logit_rules} if self._logit_rules is not None else {}))
+                                         **({"logit_rules": self._logit_rules} if self._logit_rules is not None else {}),
+                                         **({"truncation": self._truncation} if self._truncation is not None else {}))
         return self._traced(pred, rec, torch.arange(B, device=dev))
 
     def _diverse_beam_decode(self, image_features, obj_means, sentiment):
