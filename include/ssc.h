@@ -1506,6 +1506,69 @@ int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_params* p, const
                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Contrastive decoding for the word samplers (Li et al. 2023; with a degraded image as the amateur: visual contrastive decoding,
+ * Leng et al. 2023): a second, AMATEUR stream is decoded in lock-step with the normal EXPERT stream, fed the same words, and the
+ * expert's raw logits are contrasted with the amateur's in front of the draw - what the image, the latent, the style or the later
+ * checkpoint contributes to the next word is sampled more.  With lp_e = log_softmax(x_e), lp_a = log_softmax(x_a) (untempered),
+ * m = max_u lp_e[u] and logb = log(beta), every live row becomes, in place over the expert's,
+ *     y[v] = lp_e[v] + alpha * (lp_e[v] - lp_a[v])    if beta == 0 or lp_e[v] >= logb + m   (the plausibility cut)
+ *     y[v] = -inf                                     otherwise
+ * Each log-sum-exp is formed as ssc_log_softmax forms it (the same device function, the same summation order): x - lse is bit-equal
+ * to ssc_log_softmax.  logb is taken once on the host (log in double, rounded to fp32), logb + m is one fp32 addition; the edit is
+ * one subtraction, one multiplication and one addition, never an fma; alpha == 0 stores lp_e itself.  Every maximal expert entry is
+ * kept.  Downstream y is a row of RAW logits: the logit rules, the truncation and the draw - at the sampler's temperature - are
+ * unchanged, and the log-prob a draw reports is the log-softmax of the edited row.
+ * A row whose last token is END (last_pred[r] == end_index) is neither read nor written (statistics 0); columns V .. ld - 1 of
+ * either row are never touched; the amateur's rows are never written and may not overlap the expert's.  NaN or +-inf in either row
+ * is the caller's error (the call still ends and stays inside the rows).  amateur may be NULL iff alpha == 0: the plausibility cut
+ * alone.  kept (rows) or NULL: the entries left finite; divergence (rows) or NULL: KL(p_e || p_a) = sum_v p_e[v] (lp_e[v] - lp_a[v])
+ * in nats over all V entries - how much the word depended on what the amateur lacks; 0 without an amateur.
+ * One workgroup per row; each row is read from HBM once, the later passes find it in L2 (no row is staged in LDS, so no bound on
+ * V); 16-byte accesses where both rows are 16-byte aligned with V % 4 == 0, scalar ones otherwise - the result does not depend on
+ * which.  Reductions in a fixed order, no atomics: two calls on equal inputs are bit-identical.
+ * SSC_EINVAL before any launch: a NULL logits, a NULL amateur with alpha != 0, alpha < 0 or not finite, beta outside [0, 1) or NaN,
+ * rows < 0, V < 1, ld < V, ld_amateur < V with an amateur, end_index outside [0, V) with a last_pred.  SSC_EALIGN: logits, amateur,
+ * last_pred, kept or divergence no multiple of 4.  alpha == 0 && beta == 0: SSC_OK with no launch.
+ * ---------------------------------------------------------------------------------------------- */
+int ssc_contrast_rows(float* logits, int ld, const float* amateur, int ld_amateur, int rows, int V, float alpha, float beta,
+                      const int64_t* last_pred, int end_index, int* kept, float* divergence, void* stream);
+/* The amateur of a contrastive sampled decode.  A NULL member is the expert's own: an amateur differs from the expert in what is
+ * set - its parameter set (a weak checkpoint), its image context (degraded features), its sentiment, its noise (zero noise: z at
+ * the prior mean), its attribute means, or whether it follows the call's latent guide. */
+typedef struct {
+  float alpha, beta;             /* as ssc_contrast_rows; both 0: off */
+  const ssc_params* params;      /* the amateur's parameter set (of the call's ssc_model_cfg); NULL: the expert's */
+  const float* feats;            /* (nimg, R, F) the amateur's features, and ... */
+  const void* imgbuf;            /* ... ssc_decode_prepare of them under the amateur's params.  Both or neither (SSC_EINVAL); NULL: the
+                                  * expert's context.  params without them: SSC_EINVAL (the expert's buffer was prepared under the
+                                  * expert's params) */
+  const float* sentiment;        /* (B), or NULL: the expert's */
+  const float* eps0;             /* (B, Z), or NULL: the expert's.  Zero noise gives z at the prior mean */
+  const float* eps;              /* (max_steps - 1, B, Z), or NULL: the expert's */
+  const float* obj_atts;         /* cfg->kld_mode 2: (nimg, R, Z), or NULL: the expert's */
+  int guide_mode;                /* with a latent guide: 0 - the amateur follows the guide too (with its own noise where the guide has a
+                                  * variance); 1 - the amateur ignores it and decodes under its prior with its noise */
+  const ssc_start_state* start;  /* the amateur's start state: only the four state blocks are read, the fed tokens are the expert's
+                                  * (tokens may be NULL).  Required iff d->start is set (SSC_EINVAL); not read with alpha == 0 */
+  int* kept;                     /* (max_steps, B) or NULL: step t writes slab t with ssc_contrast_rows' kept; slabs of steps never ... */
+  float* divergence;             /* ... queued (early_stop) are not written.  (max_steps, B) or NULL: ssc_contrast_rows' divergence */
+} ssc_contrast;
+/* ssc_decode_sample_trunc with an amateur stream.  Per step, for a live row: the expert's decode step; the amateur's decode step,
+ * fed the same tokens, on its own two generations of states, its own alpha scratch, logits block, attended-feature-table decision
+ * and step workspace (as a member of ssc_decode_search_ensemble has), sharing row_lp / skip_dead with the expert; one
+ * ssc_contrast_rows launch; the logit rules; the truncation; the draw.  Everything runs on `stream`.  With alpha == 0 the amateur is
+ * not stepped and the workspace is that of ssc_decode_sample.  The attention trace records the expert; early stop, the pacer, ctl
+ * and host_flag are untouched.  contrast NULL, or alpha == 0 && beta == 0: the launches and the bits of ssc_decode_sample_trunc,
+ * which is this call with contrast = NULL.  d->log_probs sums the log-probs under the edited distributions.
+ * SSC_EINVAL before any launch: what ssc_decode_sample_trunc refuses; alpha or beta outside their ranges; feats without imgbuf or
+ * imgbuf without feats; params without them; guide_mode outside 0 / 1; with alpha != 0 a start on one side only or with a NULL
+ * state block.  SSC_EALIGN: kept or divergence no multiple of 4. */
+size_t ssc_decode_sample_contrast_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_contrast* contrast);
+int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                               const ssc_contrast* contrast, const ssc_logit_rules* rules, const ssc_truncation* trunc,
+                               const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Prompted decoding: start the one-call decodes from a forced prefix ("a happy ...").  ssc_decode_prime teacher-forces the prefix
  * on the B = nimg * n_samples rows of a call - the loop of ssc_decode_score, leaving STATES instead of only scores -, its outputs
  * are an ssc_start_state for any search or sampled decode over the same B entries, and ssc_prefix_join puts prefix and

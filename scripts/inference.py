@@ -19,6 +19,7 @@ from ssc_runtime.config import Config  # noqa: E402
 from ssc_runtime.data import SyntheticCaptionData, TensorFileData  # noqa: E402
 from ssc_runtime.inference import diverse_decode, score_captions  # noqa: E402
 from ssc_runtime import sampling  # noqa: E402
+from ssc_runtime.contrast import AMATEURS  # noqa: E402
 from ssc_runtime.vocab import Vocabulary  # noqa: E402
 from var_updown.models import CaptionerEnsemble, UpDownCaptioner  # noqa: E402
 
@@ -112,6 +113,20 @@ parser.add_argument("--truncation", default="",
                          "typical:0.9 (default: MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE) - every step's distribution is cut "
                          "between the logit rules and the draw.  Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without "
                          "SAMPLED_BEAM_SEARCH")
+parser.add_argument("--contrast", default="",
+                    help="contrastive decoding for word sampling: ALPHA[:BETA], e.g. --contrast 1:0.1 (default: MODEL.CONTRAST_ALPHA / "
+                         "CONTRAST_BETA; ALPHA 0 = off) - an amateur stream is decoded in lock-step and every step's logits become "
+                         "lp + ALPHA (lp - lp_amateur) on the words at least BETA times as probable as the top word.  Needs "
+                         "MODEL.DECODE_SAMPLER multinomial / top-k / top-p without SAMPLED_BEAM_SEARCH")
+parser.add_argument("--contrast-amateur", default="",
+                    help="the amateur of --contrast: mean-features | noise-features | prior-mean | neutral-sentiment (default: "
+                         "MODEL.CONTRAST_AMATEUR)")
+parser.add_argument("--contrast-checkpoint", default="",
+                    help="the amateur's weights: a checkpoint of the SAME configuration and vocabulary (e.g. an early one); with it the "
+                         "amateur kind applies only where --contrast-amateur is given")
+parser.add_argument("--contrast-output", default="",
+                    help="with an active contrast: write per returned caption the KL of the expert's word distribution from the "
+                         "amateur's at every word, in nats (JSON: image_id, caption, divergence)")
 parser.add_argument("--prefix", default="",
                     help='prompted decoding: words every caption starts with, e.g. --prefix "a happy" - one prompt for every image '
                          "(default: MODEL.DECODE_PREFIX).  The prompt is teacher-forced, the configured decoder continues from it; "
@@ -205,6 +220,49 @@ def check_truncation_args(_A, model_cfg=None):
     return tr
 
 
+def check_contrast_args(_A, model_cfg=None):
+    """--contrast ALPHA[:BETA] / --contrast-amateur / --contrast-checkpoint / --contrast-output, checked before anything is loaded
+    -> (alpha, beta, amateur kind or None) of the flags, None for what a flag does not give; with model_cfg (the MODEL node) the
+    keys fill the gaps and the result is (alpha, beta, kind), or None when the contrast is off - and it is checked that the run
+    samples words."""
+    alpha = beta = None
+    if _A.contrast:
+        a, _, b = _A.contrast.partition(":")
+        try:
+            alpha, beta = float(a), (float(b) if b.strip() else None)
+        except ValueError:
+            raise SystemExit(f"--contrast: ALPHA[:BETA] wanted, two numbers, got {_A.contrast!r}")
+        if not (0 <= alpha < float("inf")):
+            raise SystemExit(f"--contrast: ALPHA must be finite and >= 0, got {alpha!r}")
+        if beta is not None and not (0 <= beta < 1):
+            raise SystemExit(f"--contrast: BETA must lie in [0, 1), got {beta!r}")
+    kind = _A.contrast_amateur or None
+    if kind is not None and kind not in AMATEURS:
+        raise SystemExit(f"--contrast-amateur: one of {' | '.join(AMATEURS)} wanted, got {kind!r}")
+    if _A.contrast_checkpoint and not os.path.exists(_A.contrast_checkpoint):
+        raise SystemExit(f"--contrast-checkpoint: no such checkpoint {_A.contrast_checkpoint!r}")
+    if model_cfg is None:
+        return alpha, beta, kind
+    alpha = float(model_cfg.CONTRAST_ALPHA) if alpha is None else alpha
+    cut_alone = alpha == 0 and beta is not None and beta != 0   # (--contrast 0:BETA; ALPHA 0 is off whatever the keys' BETA)
+    beta = float(model_cfg.CONTRAST_BETA) if beta is None else beta
+    if alpha == 0 and not cut_alone:
+        for flag, name in ((_A.contrast_amateur, "--contrast-amateur"), (_A.contrast_checkpoint, "--contrast-checkpoint"),
+                           (_A.contrast_output, "--contrast-output")):
+            if flag and not _A.contrast:
+                raise SystemExit(f"{name} needs an active contrast: --contrast ALPHA[:BETA] or MODEL.CONTRAST_ALPHA")
+        return None
+    if _A.ensemble_checkpoints:
+        raise SystemExit("--contrast is not available with --ensemble-checkpoints: an ensemble runs the beam search only")
+    sk = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if sk not in sampling.KINDS or model_cfg.SAMPLED_BEAM_SEARCH or model_cfg.STOCHASTIC_BEAM_SEARCH:
+        raise SystemExit("--contrast needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                         f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
+    if kind is None and not _A.contrast_checkpoint:
+        kind = str(model_cfg.CONTRAST_AMATEUR)
+    return alpha, beta, kind
+
+
 def check_prefix_args(_A):
     """--prefix / --prefix-json, checked before anything is loaded -> {image_id: "words"} of --prefix-json, or None."""
     if not _A.prefix and not _A.prefix_json:
@@ -281,9 +339,11 @@ def main():
     jitter = check_exemplar_args(_A)
     check_word_bias_args(_A)
     check_truncation_args(_A)
+    check_contrast_args(_A)
     _C = Config(_A.config, _A.config_override)
     check_word_bias_args(_A, _C.MODEL)
     truncation = check_truncation_args(_A, _C.MODEL)
+    contrast_args = check_contrast_args(_A, _C.MODEL)
     prompt = _A.prefix or ("" if prompts is not None else str(_C.MODEL.DECODE_PREFIX).strip())
     if (prompt or prompts is not None) and not _A.prefix and not _A.prefix_json:   # (MODEL.DECODE_PREFIX: the flags' refusals apply)
         _A.prefix = prompt
@@ -351,6 +411,24 @@ def main():
                 members.append(m)
         dec = CaptionerEnsemble(members, ens_weights, ens_mode).engine()
     dec.weights_frozen = True   # the checkpoint's weights stay as they are for the whole run: weight-only tables are formed once
+    # --contrast / MODEL.CONTRAST_*: the amateur of the word-sampled decode - a kind, the weights of --contrast-checkpoint, or both
+    contrast = None
+    model.contrast(None)   # (the run's own decode below is handed the contrast itself)
+    if contrast_args is not None:
+        from ssc_runtime.contrast import Contrast, contrast_from_name
+        c_alpha, c_beta, c_kind = contrast_args
+        amateur_engine = None
+        if _A.contrast_checkpoint:
+            with torch.random.fork_rng(devices=[]):   # (the amateur's initialisation draws nothing from the run's random stream)
+                am = cls.from_config(_C, vocabulary=vocabulary, device=device, **extra).to(device)
+                am.load_state_dict(torch.load(_A.contrast_checkpoint, map_location=device, weights_only=True)["model"])
+            am.eval()
+            am._engine()
+            amateur_engine = am._dec
+            amateur_engine.weights_frozen = True
+        contrast = (contrast_from_name(c_alpha, c_beta, c_kind, float(_C.MODEL.CONTRAST_NOISE), engine=amateur_engine)
+                    if c_kind is not None else Contrast(c_alpha, c_beta, engine=amateur_engine))
+    divergences = []   # --contrast-output: one record per returned caption
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
     if sampler is not None and (_A.constraints_json or _A.boxes_json):
@@ -478,8 +556,11 @@ def main():
                                      num_constraints=ncons, min_constraints_to_satisfy=_C.MODEL.MIN_CONSTRAINTS_TO_SATISFY,
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode,
                                      guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}),
-                                     **({"truncation": truncation} if truncation is not None else {}), **pkw)
+                                     **({"truncation": truncation} if truncation is not None else {}),
+                                     **({"contrast": contrast, "contrast_stats": True} if contrast is not None else {}), **pkw)
                 pred = out[0]
+                if contrast is not None:
+                    out, c_div = out[:-1], out[-1][1].cpu().numpy()   # (images, n_z, steps of the continuation)
             trace = out[-1] if attn_mode else None
             # ids -> words, cut at the first @@BOUNDARY@@ (inference.py:180-182): one table lookup for the whole chunk - the
             # per-token Python calls this replaces took as long as the chunk's 20 decode steps on the GPU
@@ -493,6 +574,10 @@ def main():
                 image_id = int(data.image_id[lo + i])
                 for k in range(ids.shape[1]):
                     predictions.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
+                    if contrast is not None and _A.contrast_output:   # the caption's words and its END, less a prefix's words
+                        n_div = max(1, min(int(n_keep[i, k]) + 1 - (ids.shape[-1] - c_div.shape[-1]), c_div.shape[-1]))
+                        divergences.append({"image_id": image_id, "caption": predictions[-1]["caption"],
+                                            "divergence": [float(v) for v in c_div[i, k, :n_div]]})
             if trace is not None:
                 # (images, captions per image, steps[, R]) like the predictions; every caption cut behind its end
                 tr = {n: getattr(trace, n).reshape(ids.shape[0], ids.shape[1], *getattr(trace, n).shape[-(2 if n == "maps" else 1):]).cpu()
@@ -545,6 +630,8 @@ def main():
                     selected += [{"image_id": image_id, "caption": " ".join(words[i, n, : n_keep[i, n]])} for n in sel.picks[i] if n >= 0]
             lo += n_here
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
+    if contrast is not None and _A.contrast_output:
+        json.dump(divergences, open(_A.contrast_output, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
     if _A.attention_output:
         torch.save(traces, _A.attention_output)

@@ -216,10 +216,64 @@ extern "C" size_t ssc_decode_sample_trunc_workspace_bytes(const ssc_model_cfg* c
 extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
                                        const ssc_sampler_desc* s, const ssc_logit_rules* rules, const ssc_truncation* trunc,
                                        const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream) {
+  return ssc_decode_sample_contrast(cfg, p, d, s, nullptr, rules, trunc, guide, workspace, workspace_bytes, stream);
+}
+
+namespace {
+
+// The amateur stream of a contrastive call (ssc_contrast, include/ssc.h), behind the expert's blocks: what an ensemble member has of
+// its own - two generations of states, alpha scratch, a logits block and a step workspace.  An amateur is stepped iff alpha != 0.
+struct AmateurLayout {
+  SscStepStates states;
+  size_t alpha, logits, stepws, stepws_bytes;
+};
+inline bool contrast_steps_amateur(const ssc_contrast* c) { return c && c->alpha != 0.f; }
+size_t contrast_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, const SampleLayout& l, AmateurLayout* am) {
+  const size_t B = (size_t)d->nimg * d->n_samples;
+  size_t o = l.total;
+  am->states.reserve(o, B, cfg->H);
+  am->alpha = ssc_ws_take(o, B * (size_t)d->R * 4);
+  am->logits = ssc_ws_take(o, B * (size_t)cfg->V * 4);
+  am->stepws_bytes = l.stepws_bytes;
+  am->stepws = ssc_ws_take(o, am->stepws_bytes);
+  return o;
+}
+
+}  // namespace
+
+extern "C" size_t ssc_decode_sample_contrast_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
+                                                             const ssc_contrast* contrast) {
+  if (!ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return 0;
+  const SampleLayout l = sample_layout(cfg, d);
+  if (!contrast_steps_amateur(contrast)) return l.total;
+  AmateurLayout am;
+  return contrast_layout(cfg, d, l, &am);
+}
+
+// contrast (or null): the amateur stream and the contrast of include/ssc.h - per step the amateur's decode step behind the expert's,
+// then one ssc_contrast_rows launch in front of the logit rules; step t's statistics go to slab t of contrast->kept / ->divergence
+extern "C" int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                          const ssc_sampler_desc* s, const ssc_contrast* contrast, const ssc_logit_rules* rules,
+                                          const ssc_truncation* trunc, const ssc_latent_guide* guide, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
   if (guide && !ssc_latent_guide_ok(cfg, guide)) return SSC_EINVAL;
   if (!ssc_decode_start_ok(d->start, !guide)) return SSC_EINVAL;   // (no start state under a guide)
+  bool contrasted = false;
+  if (contrast) {
+    const int rc = ssc_contrast_check(contrast->alpha, contrast->beta, contrast->kept, contrast->divergence, &contrasted);
+    if (rc == SSC_EINVAL) return rc;
+    if ((contrast->feats != nullptr) != (contrast->imgbuf != nullptr) || (contrast->params && !contrast->imgbuf)) return SSC_EINVAL;
+    if (contrast->guide_mode != 0 && contrast->guide_mode != 1) return SSC_EINVAL;
+    if (contrast_steps_amateur(contrast)) {   // (an amateur that is not stepped reads no start state)
+      if ((contrast->start != nullptr) != (d->start != nullptr)) return SSC_EINVAL;
+      const ssc_start_state* cs = contrast->start;
+      if (cs && !(cs->h1 && cs->c1 && cs->hd && cs->cd)) return SSC_EINVAL;   // (its tokens are not read: the expert's are fed)
+    }
+    SSC_TRY(rc);
+  }
+  const bool amateur = contrasted && contrast_steps_amateur(contrast);
   bool ruled = false;
   if (rules) {
     SSC_TRY(ssc_logit_rules_check(rules, cfg->V, d->end_index, &ruled));
@@ -228,10 +282,18 @@ extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_param
   bool cut = false;
   if (trunc) SSC_TRY(ssc_truncation_check(trunc, s->temperature, &cut));
   const SampleLayout l = sample_layout(cfg, d);
-  if (workspace_bytes < l.total) return SSC_EWORKSPACE;
+  AmateurLayout am{};
+  const size_t total = amateur ? contrast_layout(cfg, d, l, &am) : l.total;
+  if (workspace_bytes < total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* W = (char*)workspace;
   const int B = d->nimg * d->n_samples, V = cfg->V, Z = cfg->Z;
+  // step t's contrast: the expert's logits edited in place against the amateur's, the statistics of slab t
+  auto contrast_step = [&](int t, const int64_t* last) {
+    return ssc_contrast_launch((float*)(W + l.logits), V, amateur ? (const float*)(W + am.logits) : nullptr, V, B, V, contrast->alpha,
+                               contrast->beta, contrast->kept ? contrast->kept + (size_t)t * B : nullptr,
+                               contrast->divergence ? contrast->divergence + (size_t)t * B : nullptr, last, d->end_index, st);
+  };
   // step t's truncation: the statistics of slab t
   auto truncate = [&](int t, const int64_t* last) {
     return ssc_truncation_launch((float*)(W + l.logits), V, B, V, trunc, s->temperature,
@@ -252,6 +314,7 @@ extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_param
   if (hipMemsetAsync(parent0, 0, (size_t)B * 8, st) != hipSuccess) return SSC_EHIP;
   if (hipMemsetAsync(lp, 0, (size_t)B * 4, st) != hipSuccess) return SSC_EHIP;
   SSC_TRY(ssc_decode_start_states(d->start, states, W, 1, B, st));
+  if (amateur) SSC_TRY(ssc_decode_start_states(contrast->start, am.states, W, 1, B, st));
 
   // the steps take the form the beam-1 search gives them (ssc_decode_search with S = beam = 1): same tables, same parent list
   const bool want_table = ssc_att_table_wanted(d->R, B, d->n_samples);
@@ -265,6 +328,25 @@ extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_param
   sd.alpha = ssc_decode_alpha_at(d->attn, (float*)(W + l.alpha), 0, B, d->R);
   SscStepGuide sg{guide, 0, 1};
   SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
+  // the amateur's step: the expert's descriptor - the same fed tokens, parent list and skipped rows - over its own context, noise,
+  // states and blocks; its attention weights stay in its scratch (the trace records the expert)
+  const ssc_params* pa = amateur && contrast->params ? contrast->params : p;
+  SscAttTable table_a;
+  SscStepGuide sga{amateur && contrast->guide_mode == 0 ? guide : nullptr, 0, 1};
+  const float* eps_a = amateur && contrast->eps ? contrast->eps : d->eps;
+  auto amateur_step = [&](int gen) {
+    ssc_decode_step_desc sa = sd;
+    if (contrast->imgbuf) { sa.feats = contrast->feats; sa.imgbuf = contrast->imgbuf; }
+    if (contrast->sentiment) sa.sentiment = contrast->sentiment;
+    if (contrast->obj_atts) sa.obj_atts = contrast->obj_atts;
+    sa.eps = sga.t == 0 ? (contrast->eps0 ? contrast->eps0 : d->eps0) : eps_a + (size_t)(sga.t - 1) * B * Z;
+    sa.alpha = (float*)(W + am.alpha); sa.log_probs = (float*)(W + am.logits);
+    am.states.bind(W, gen, &sa);
+    sa.att_table = table_a.next(want_table);
+    return ssc_decode_step_guided(cfg, pa, &sa, &sga, W + am.stepws, am.stepws_bytes, st);
+  };
+  if (amateur) SSC_TRY(amateur_step(1));
+  if (contrasted) SSC_TRY(contrast_step(0, nullptr));
   if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, 0, d->end_index, st));
   if (cut) SSC_TRY(truncate(0, nullptr));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
@@ -285,6 +367,9 @@ extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_param
     sd.row_lp = d->skip_dead ? lp : nullptr; sd.end_index = d->end_index;   // ended rows are not stepped
     sg.t = t;
     SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
+    sga.t = t;
+    if (amateur) SSC_TRY(amateur_step(cur));
+    if (contrasted) SSC_TRY(contrast_step(t, last));
     if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, t, d->end_index, st));
     if (cut) SSC_TRY(truncate(t, last));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;

@@ -229,5 +229,11 @@ int ssc_logit_rules_launch(float* logits, int ld, int rows, int V, const ssc_log
 int ssc_truncation_check(const ssc_truncation* tr, float temperature, bool* active);
 int ssc_truncation_launch(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature, float* entropy, int* kept,
                           const int64_t* last_pred, int end_index, hipStream_t st);
+// Contrastive decoding for the word samplers (contrast.hip, include/ssc.h: ssc_contrast_rows, ssc_contrast).  ssc_contrast_check: the
+// refusals that depend on the knobs and the statistics pointers alone (SSC_OK with *active = alpha != 0 || beta != 0);
+// ssc_contrast_launch: the edit of one step from checked knobs - what ssc_decode_sample_contrast issues per step.
+int ssc_contrast_check(float alpha, float beta, const int* kept, const float* divergence, bool* active);
+int ssc_contrast_launch(float* logits, int ld, const float* amateur, int lda, int rows, int V, float alpha, float beta, int* kept,
+                        float* divergence, const int64_t* last_pred, int end_index, hipStream_t st);
 int ssc_attn_weights_rows(const float* q, int ldq, const float* pv, const float* wa, const float* mask, int G, int R, int A,
                           int rows_per_image, float* logits, float* alpha, const int* rows, const int* row_count, hipStream_t st);

@@ -110,6 +110,13 @@ def _defaults() -> dict:
             # min(VALUE, sqrt(VALUE) exp(-entropy)) / VALUE, default 3e-4).  SAMPLER_TRUNCATION_VALUE 0 = the kind's default.  Needs
             # DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
             "SAMPLER_TRUNCATION": "none", "SAMPLER_TRUNCATION_VALUE": 0.0,
+            # contrastive decoding of the word samplers (ssc_runtime/contrast.py Contrast; ssc_contrast): an amateur stream is decoded
+            # in lock-step with the normal one and every step's logits become lp + CONTRAST_ALPHA (lp - lp_amateur) on the words
+            # whose probability is at least CONTRAST_BETA times the top word's.  CONTRAST_ALPHA 0 (default): off.  CONTRAST_AMATEUR:
+            # "mean-features" (every region replaced by the image's mean region), "noise-features" (the features under noise of
+            # level CONTRAST_NOISE in (0, 1]), "prior-mean" (z at the prior mean), "neutral-sentiment" (sentiment 0).  Needs
+            # DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
+            "CONTRAST_ALPHA": 0.0, "CONTRAST_BETA": 0.1, "CONTRAST_AMATEUR": "mean-features", "CONTRAST_NOISE": 0.5,
             # attention traces of the eval decode (ssc_attn_record; DecodeEngine.attention): "none" (default), "summary" - per word
             # of every returned caption the region it attended most, the weight there and the entropy of its attention - or "full"
             # - the whole map over the regions as well.  Any decoder; the captions themselves do not change
@@ -271,6 +278,14 @@ class Config(object):
         if m.SAMPLER_TRUNCATION != "none" and not (0 <= tv and hi_ok):   # (0: the kind's default)
             raise ValueError(f"MODEL.SAMPLER_TRUNCATION_VALUE must lie in (0, 1] for typical / min-p and in (0, 1) for eta / epsilon, "
                              f"or be 0 for the kind's default; found {tv!r}")
+        for key, ok, what in (("CONTRAST_ALPHA", lambda v: 0 <= v < float("inf"), "a finite number >= 0 (0 = off)"),
+                              ("CONTRAST_BETA", lambda v: 0 <= v < 1, "in [0, 1)"), ("CONTRAST_NOISE", lambda v: 0 < v <= 1, "in (0, 1]")):
+            cv = getattr(m, key)
+            if isinstance(cv, bool) or not isinstance(cv, (int, float)) or cv != cv or not ok(cv):
+                raise ValueError(f"MODEL.{key} must be {what}; found {cv!r}")
+        if m.CONTRAST_AMATEUR not in ("mean-features", "noise-features", "prior-mean", "neutral-sentiment"):
+            raise ValueError("MODEL.CONTRAST_AMATEUR must be one of mean-features | noise-features | prior-mean | neutral-sentiment; "
+                             f"found {m.CONTRAST_AMATEUR!r}")
         if m.DECODE_ATTENTION not in ("none", "summary", "full"):
             raise ValueError(f"MODEL.DECODE_ATTENTION must be one of none | summary | full; found {m.DECODE_ATTENTION!r}")
         if not isinstance(m.DECODE_PREFIX, str):

@@ -362,7 +362,7 @@ class DecodeEngine:
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
                attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None, truncation=None,
-               truncation_stats: bool = False):
+               truncation_stats: bool = False, contrast=None, contrast_stats: bool = False):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
@@ -376,8 +376,18 @@ class DecodeEngine:
         temperature); None or an inactive one issues the call without it.  truncation_stats=True (with an active truncation):
         the result is followed by (entropy (B, steps) float32 in nats, kept (B, steps) int32 - the entries left finite), zero
         for ended rows and in the columns past the stop.
+        contrast: a contrast.Contrast, or None - contrastive decoding (ssc_decode_sample_contrast): an amateur stream is decoded in
+        lock-step with this one, fed the same words, and every step's raw logits are contrasted with the amateur's in front of the
+        logit rules; None or an inactive one issues the call without it.  With start= the Contrast carries the amateur's own
+        StartState (Contrast.start).  contrast_stats=True (with an active contrast): the result is followed - behind the
+        truncation's statistics - by (kept (B, steps) int32 - the words left plausible -, divergence (B, steps) float32 - the KL
+        of the expert's word distribution from the amateur's, in nats), zero for ended rows and in the columns past the stop.
         skip_dead (default on): ended rows are not stepped; the captions do not depend on it."""
         _start_check(start, guide)
+        if contrast is not None and not contrast.active:
+            contrast = None
+        if contrast_stats and contrast is None:
+            raise ValueError("DecodeEngine.sample: contrast_stats needs an active contrast")
         if truncation is not None and not truncation.active:
             truncation = None
         if truncation_stats and truncation is None:
@@ -410,11 +420,29 @@ class DecodeEngine:
                                                                       C.byref(rd) if rd is not None else None, C.byref(td),
                                                                       C.byref(gd) if gd is not None else None, *ws)
             workspace_bytes = self.lib.ssc_decode_sample_trunc_workspace_bytes
+        ckept = cdiv = None
+        if contrast is not None:
+            if not (logit_rules is not None and logit_rules.active):
+                rd = None
+            if truncation is None:
+                td = None
+            B = ctx.nimg * n_samples
+            if contrast_stats:   # (max_steps, B) blocks; slabs of steps never queued stay zero
+                ckept = torch.zeros(max_steps, B, dtype=torch.int32, device=self.device)
+                cdiv = torch.zeros(max_steps, B, dtype=torch.float32, device=self.device)
+            cd, _keep_contrast = contrast.desc(self, ctx, n_samples, max_steps, start is not None, ckept, cdiv)
+            call = lambda p, sd, ws: self.lib.ssc_decode_sample_contrast(
+                C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), C.byref(cd), C.byref(rd) if rd is not None else None,
+                C.byref(td) if td is not None else None, C.byref(gd) if gd is not None else None, *ws)
+            workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_contrast_workspace_bytes(cfg, sd, C.byref(cd))
         out = self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
         if truncation_stats:
             steps = out[0].size(-1)
             out = tuple(out) + ((ent[:steps].t().contiguous(), kept[:steps].t().contiguous()),)
+        if contrast_stats:
+            steps = out[0].size(-1)
+            out = tuple(out) + ((ckept[:steps].t().contiguous(), cdiv[:steps].t().contiguous()),)
         return out
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,

@@ -27,7 +27,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
                    rules=None, attention: Optional[str] = None, guide=None, logit_rules=None, prefix=None,
-                   prefix_eps: Optional[torch.Tensor] = None, truncation=None):
+                   prefix_eps: Optional[torch.Tensor] = None, truncation=None, contrast=None, contrast_stats: bool = False):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -75,6 +75,13 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     between the logit rules and the draw (DecodeEngine.sample(truncation=)); ValueError naming the decoder with any other one,
     NotImplementedError with an ensemble.  None or an inactive one: the call without it.  Composes with logit_rules, guide, prefix
     and attention.
+    contrast: a contrast.Contrast - contrastive decoding with a word sampler (DecodeEngine.sample(contrast=)): an amateur stream -
+    degraded features, z at the prior mean, a neutral sentiment, no exemplar or a weak checkpoint - is decoded in lock-step and every
+    step's logits are contrasted with it in front of the logit rules.  The amateur's image context is prepared here ("noise:g"
+    features from a generator seeded by the call's one draw of the global generator); with prefix= both streams are primed on the
+    same prefix noise.  ValueError naming the decoder with any other one, NotImplementedError with an ensemble.  None or an inactive
+    one: the call without it.  Greedy contrastive decoding is the top-k sampler with k = 1.  contrast_stats=True: the result is
+    followed by (kept, divergence) of shape (nimg, n_samples, steps) - over the continuation with a prefix.
     prefix: a DecodePrefix (ssc_runtime.prefix) with one row per image - or per (image, sample) entry -, or None.  With it every
     caption starts with its image's prompt: the prompt is teacher-forced on the nimg * n_samples rows (DecodeEngine.prime), whichever
     decoder was chosen continues from there (start=) and the call returns the FULL captions (nimg, n_samples, Lp + steps) - the
@@ -113,6 +120,21 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                  "the beam search" if sampler is None else None)
         if other is not None:
             raise ValueError(f"the truncation belongs to the word samplers: truncation= needs a multinomial / top-k / top-p sampler, "
+                             f"not {other}")
+    if contrast is not None and not contrast.active:
+        contrast = None
+    if contrast_stats and contrast is None:
+        raise ValueError("contrast_stats needs an active contrast")
+    if contrast is not None:
+        if isinstance(dec, EnsembleDecodeEngine):
+            raise NotImplementedError("contrastive decoding (contrast=) is not implemented for an ensemble (EnsembleDecodeEngine)")
+        other = ("the beam search under decode rules (rules)" if rules is not None and rules.active else
+                 "the diverse beam search (diverse_beam)" if diverse_beam is not None else
+                 "the sampled-node beam search (sampled_beam)" if sampled_beam else
+                 "the stochastic beam search (GumbelSampler)" if sampler is not None and sampler.beam_search else
+                 "the beam search" if sampler is None else None)
+        if other is not None:
+            raise ValueError(f"the contrast belongs to the word samplers: contrast= needs a multinomial / top-k / top-p sampler, "
                              f"not {other}")
     if guide is not None:
         from .guide import guide_unsupported
@@ -212,6 +234,14 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                 peps = torch.randn(ids.size(1), B, d.Z, device=dev, generator=gen)
             primed["ids"] = ids.to(dev)
             primed["start"] = dec.prime(ctx, sent_b, n_samples, primed["ids"], boundary_index, peps)
+            if contrast is not None and contrast.steps_amateur:   # the amateur reads the same prompt under the same noise
+                a_sent = sent_b
+                if contrast.sentiment is not None:
+                    a_sent = torch.as_tensor(contrast.sentiment, dtype=torch.float32, device=dev)
+                    a_sent = (a_sent.reshape(1).expand(B) if a_sent.numel() == 1 else
+                              a_sent.reshape(nimg, 1).expand(nimg, n_samples).reshape(B) if a_sent.numel() == nimg else a_sent.reshape(B))
+                contrast.start = (contrast.engine or dec).prime(contrast.ctx if contrast.ctx is not None else ctx, a_sent, n_samples,
+                                                                primed["ids"], boundary_index, peps)
         return {"start": primed["start"]}
 
     def joined(beams, lps):
@@ -223,6 +253,15 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     rkw = {"logit_rules": logit_rules} if logit_rules is not None else {}
     if truncation is not None:
         rkw["truncation"] = truncation
+    stats = {}
+    if contrast is not None:
+        cgen = torch.Generator(device=dev)
+        cgen.manual_seed(seed if seed is not None else sample_seed)   # (no draw of the call's own: the caller gave the draws' seed)
+        contrast.prepare(dec, ctx.feats, ctx.obj, generator=cgen)
+        contrast.start = None
+        rkw["contrast"] = contrast
+        if contrast_stats:
+            rkw["contrast_stats"] = True
 
     def search(skip_now):
         # the noise of ALL steps is drawn up front - from the caller's list, or from a generator of this call's own seeded by ONE draw
@@ -267,6 +306,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
             pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn,
                                          **gkw, **rkw, **skw)
+            if contrast_stats:
+                stats["kept"], stats["divergence"] = rec.pop()
             calls["k"] = pred.size(-1)
             return pred.view(B, 1, 1, -1), lps.view(B, 1, 1), rec
         beams, lps, *rec = dec.search(ctx, sent_b, n_samples, beam, per_node, max_steps, boundary_index, eps0, eps,
@@ -313,7 +354,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         if want_attn:
             state = select_best_state_simple_batched(lps, num_constraints, min_constraints_to_satisfy)
     sel = (torch.arange(B, device=dev) * S + state) * beam
-    return (best.view(nimg, n_samples, -1), calls["k"]) + trace(rec, sel, (nimg, n_samples))
+    cstats = ((stats["kept"].view(nimg, n_samples, -1), stats["divergence"].view(nimg, n_samples, -1)),) if contrast_stats else ()
+    return (best.view(nimg, n_samples, -1), calls["k"]) + trace(rec, sel, (nimg, n_samples)) + cstats
 
 
 def count_tokens(pred: torch.Tensor, boundary_index: int) -> int:

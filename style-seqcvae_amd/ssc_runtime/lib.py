@@ -243,6 +243,12 @@ class Truncation(C.Structure):
     _fields_ = [("kind", C.c_int), ("value", C.c_float), ("entropy", vp), ("kept", vp)]
 
 
+class Contrast(C.Structure):
+    _fields_ = [("alpha", C.c_float), ("beta", C.c_float), ("params", vp), ("feats", vp), ("imgbuf", vp), ("sentiment", vp),
+                ("eps0", vp), ("eps", vp), ("obj_atts", vp), ("guide_mode", C.c_int), ("start", C.POINTER(StartState)), ("kept", vp),
+                ("divergence", vp)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -423,6 +429,11 @@ SYMBOLS = {
     "ssc_decode_sample_trunc_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
     "ssc_decode_sample_trunc": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
                                      C.POINTER(LogitRules), C.POINTER(Truncation), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
+    "ssc_contrast_rows": (_i, [vp, _i, vp, _i, _i, _i, _f, _f, vp, _i, vp, vp, vp]),
+    "ssc_decode_sample_contrast_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(Contrast)]),
+    "ssc_decode_sample_contrast": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                        C.POINTER(Contrast), C.POINTER(LogitRules), C.POINTER(Truncation),
+                                        C.POINTER(LatentGuideDesc), vp, _sz, vp]),
     "ssc_decode_prime_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(PrimeDesc)]),
     "ssc_decode_prime": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(PrimeDesc), vp, _sz, vp]),
     "ssc_prefix_join": (_i, [vp, vp, _i, vp, vp, _i, vp, vp, _i, _i, _i, vp, vp, vp]),

@@ -532,6 +532,8 @@ def from_config(model_cfg):
     decode_rules_from_config(model_cfg)
     logit_rules_from_config(model_cfg)
     truncation_from_config(model_cfg)
+    from .contrast import contrast_from_config
+    contrast_from_config(model_cfg)
     if sbs and kind != "beam":
         raise ValueError(f"MODEL.STOCHASTIC_BEAM_SEARCH needs MODEL.DECODE_SAMPLER 'beam', got {model_cfg.DECODE_SAMPLER!r} (the word "
                          "samplers draw one word per row; the stochastic beam search is a kind of beam search)")

@@ -195,6 +195,7 @@ class UpDownCaptioner(nn.Module):
         self._decode_guide = None      # decode_guide(): a LatentGuide the NEXT eval forwards draw their latents around
         self._logit_rules = None       # logit_rules(): sampling.LogitRules the NEXT eval forwards of a word sampler draw under
         self._truncation = None        # truncation(): sampling.Truncation the NEXT eval forwards of a word sampler cut their steps with
+        self._contrast = None          # contrast(): contrast.Contrast the NEXT eval forwards of a word sampler decode against an amateur with
         self._decode_prefix = None     # decode_prefix(): a DecodePrefix every caption of the NEXT eval forwards starts with
 
     # ------------------------------------------------------------------------------------------------------
@@ -227,6 +228,8 @@ class UpDownCaptioner(nn.Module):
         if model.sampler is not None and not model.sampler.beam_search and not model.sampled_beam:
             model.logit_rules(sampling.logit_rules_from_config(_C.MODEL, vocabulary))
             model.truncation(sampling.truncation_from_config(_C.MODEL))
+            from ssc_runtime.contrast import contrast_from_config
+            model.contrast(contrast_from_config(_C.MODEL))
         if str(_C.MODEL.DECODE_PREFIX).strip():
             from ssc_runtime.prefix import DecodePrefix
             model.decode_prefix(DecodePrefix.from_words(vocabulary, str(_C.MODEL.DECODE_PREFIX)))
@@ -531,7 +534,8 @@ class UpDownCaptioner(nn.Module):
                              sampler=self.sampler, sampled_beam=bool(self.sampled_beam and self.sampler is not None),
                              diverse_beam=self.diverse_beam, rules=self.decode_rules,
                              logit_rules=self._logit_rules if words else None, prefix=DecodePrefix(ids),
-                             **({"truncation": self._truncation} if words and self._truncation is not None else {}))
+                             **({"truncation": self._truncation} if words and self._truncation is not None else {}),
+                             **({"contrast": self._contrast} if words and self._contrast is not None else {}))
         return {"predictions": out[0][:, 0, :]}
 
     def logit_rules(self, rules):
@@ -567,6 +571,23 @@ class UpDownCaptioner(nn.Module):
             if not truncation.active:
                 truncation = None
         self._truncation = truncation
+
+    def contrast(self, contrast):
+        """A contrast for the NEXT eval forwards of a word sampler (ssc_runtime.contrast.Contrast; include/ssc.h: ssc_contrast):
+        an amateur stream - degraded features, z at the prior mean, a neutral sentiment, a weak checkpoint - is decoded in lock-step
+        and every step's logits are contrasted with it in front of the logit rules.  None (the default state) or an inactive one:
+        off, the forward is what it is without.  ValueError without a word sampler.  Training forwards, scst_step, score_captions and
+        every beam search never read it."""
+        if contrast is not None:
+            from ssc_runtime.contrast import Contrast
+            if not isinstance(contrast, Contrast):
+                raise ValueError(f"contrast takes a ssc_runtime.contrast.Contrast or None, got {type(contrast).__name__}")
+            if self.sampler is None or self.sampler.beam_search or self.sampled_beam:
+                raise ValueError("contrast needs a word sampler (MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                                 "MODEL.SAMPLED_BEAM_SEARCH): the contrast belongs to the word-sampled decode")
+            if not contrast.active:
+                contrast = None
+        self._contrast = contrast
 
     def reconstruct_captions(self, image_features: torch.Tensor, caption_tokens: torch.Tensor, sentiment=None, beam: Optional[int] = None,
                              eps=None, prior_samples: int = 4, prior_seed: Optional[int] = None):
@@ -714,7 +735,8 @@ class UpDownCaptioner(nn.Module):
         pred, _, *rec = self._dec.sample(ctx, sent, 1, L, self._boundary_index, eps[0], eps[1:] if L > 1 else None, self.sampler, seed,
                                          attention=self._decode_attention is not None, guide=self._decode_guide,
                                          **({"logit_rules": self._logit_rules} if self._logit_rules is not None else {}),
-                                         **({"truncation": self._truncation} if self._truncation is not None else {}))
+                                         **({"truncation": self._truncation} if self._truncation is not None else {}),
+                                         **({"contrast": self._contrast} if self._contrast is not None else {}))
         return self._traced(pred, rec, torch.arange(B, device=dev))
 
     def _diverse_beam_decode(self, image_features, obj_means, sentiment):
