@@ -783,8 +783,8 @@ typedef struct {
  * not count), the decode rules' and the logit rules' histories, minimum length, length penalty and penalties, the samplers' step
  * counter and max_steps all start at the search's own step 0, and log_probs sums the continuation only (ssc_prefix_join adds a
  * prefix).  ssc_decode_prime makes one from a forced prefix.  Honoured by ssc_decode_search, the stochastic, sampled-node, diverse
- * and rules searches and ssc_decode_sample / _sample_rules.  SSC_EINVAL before any launch: a NULL member; `start` together with a
- * latent guide (ssc_decode_*_guided, ssc_decode_sample_rules) or with an ensemble (ssc_decode_search_ensemble). */
+ * and rules searches and ssc_decode_sample / ssc_decode_sample_opts.  SSC_EINVAL before any launch: a NULL member; `start` together
+ * with a latent guide (ssc_decode_*_guided, ssc_sample_opts.guide) or with an ensemble (ssc_decode_search_ensemble). */
 typedef struct {
   const float* h1; const float* c1; const float* hd; const float* cd;   /* (B, H) each, ld H: the states the FIRST step reads */
   const int64_t* tokens;                                                /* (B): the word the first step is fed; an id outside [0, V) is fed as end_index, never used as an index */
@@ -903,7 +903,8 @@ int ssc_sample_rows(const float* logits, int ld, int rows, int V, const ssc_samp
  * beam selection.  Batch entry b = (image, sample) is row b; step 0 feeds end_index (@@BOUNDARY@@).  d->skip_dead: ended rows
  * are not stepped (ssc_decode_step_desc.row_lp).  d->early_stop / ctl / host_flag / host_flag_host: the protocol of
  * ssc_beam_desc.ctl and ssc_decode_search (ctl[0] = number of columns; surplus queued steps are no-ops; bounded run-ahead).
- * Out: d->predictions (B, max_steps) - columns >= ctl[0] hold end_index -, d->log_probs (B): each caption's summed log-prob. */
+ * Out: d->predictions (B, max_steps) - columns >= ctl[0] hold end_index -, d->log_probs (B): each caption's summed log-prob.
+ * These two ARE ssc_decode_sample_opts_workspace_bytes / ssc_decode_sample_opts (ssc_sample_opts, below) with opts NULL. */
 size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
 int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
                       void* workspace, size_t workspace_bytes, void* stream);
@@ -1150,16 +1151,15 @@ typedef struct {
  * not 4-byte aligned. */
 int ssc_latent_guide_rows(const ssc_latent_guide* g, int t, int rows, int rows_per_entry, int Z, const float* eps, int ldeps,
                           const float* sent, float pm_scale, float prior_var, float* z, int ldz, void* stream);
-/* The one-call decodes under a guide: ssc_decode_search, ssc_decode_sample and ssc_decode_score with step t's z block drawn by
- * ssc_latent_guide_rows - one launch in place of one launch; every machine, mach, skip_dead, early_stop, attention traces and
- * every numerics mode as without a guide, and the same *_workspace_bytes.  guide NULL: the unguided call - the same launches, the
- * same bits.  B of the guide: nimg * n_samples (search, sample), nimg * n_captions * n_samples (score).  SSC_EINVAL before any
- * launch: what the unguided call refuses; steps < 1, a NULL mean, ld < cfg->Z, a mean, var or len that is not 4-byte aligned,
- * cfg->kld_mode == 2 (SENTIMENT_VAE = 2: the pooled prior mean there also conditions the LSTMs). */
+/* The one-call decodes under a guide: ssc_decode_search and ssc_decode_score through the two entries below, the sampled decode
+ * through the `guide` field of its ssc_sample_opts (further below) - step t's z block drawn by ssc_latent_guide_rows, one launch in
+ * place of one launch; every machine, mach, skip_dead, early_stop, attention traces and every numerics mode as without a guide,
+ * and the same *_workspace_bytes.  guide NULL: the unguided call - the same launches, the same bits.  B of the guide:
+ * nimg * n_samples (search, sample), nimg * n_captions * n_samples (score).  SSC_EINVAL before any launch: what the unguided call
+ * refuses; steps < 1, a NULL mean, ld < cfg->Z, a mean, var or len that is not 4-byte aligned, cfg->kld_mode == 2
+ * (SENTIMENT_VAE = 2: the pooled prior mean there also conditions the LSTMs). */
 int ssc_decode_search_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_latent_guide* guide,
                              void* workspace, size_t workspace_bytes, void* stream);
-int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
-                             const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream);
 int ssc_decode_score_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_score_desc* d, const ssc_latent_guide* guide,
                             void* workspace, size_t workspace_bytes, void* stream);
 /* Comparing captions: per pair q of pred (n, Lp) and ref (n, Lr) int64, the length of each the tokens before its first end_index
@@ -1445,18 +1445,13 @@ typedef struct {
  * with no launch. */
 int ssc_logit_rules_rows(float* logits, int ld, int rows, int V, const ssc_logit_rules* r, const int64_t* hist, int ld_hist, int t,
                          int end_index, void* stream);
-/* ssc_decode_sample_guided with one ssc_logit_rules_rows launch between each step's decode step and its draw, step 0 included:
- * the history is the call's own block of chosen words, so the workspace is that of ssc_decode_sample.  bias_row (B) is indexed by
- * batch entry b = (image, sample).  rules NULL or inactive (every control off, no bias): the launches and the bits of
- * ssc_decode_sample_guided, which is this call with rules = NULL.  Composes unchanged with a guide, an attention trace,
- * skip_dead, early_stop and every numerics mode: only the contents of the logits block change.  d->log_probs sums the log-probs
- * under the edited distributions.  SSC_EINVAL before any launch: what ssc_decode_sample_guided refuses; a field of `rules` beyond
- * its limits (as above, with V = cfg->V); active rules with max_steps > SSC_RULES_MAX_LEN or V <= max_steps + n_suppress.
- * SSC_EALIGN: bias or bias_row no multiple of 4. */
-size_t ssc_decode_sample_rules_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
-int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
-                            const ssc_logit_rules* rules, const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes,
-                            void* stream);
+/* As the `rules` field of ssc_sample_opts (below): one ssc_logit_rules_rows launch per step of the sampled decode, step 0 included.
+ * The history is the call's own block of chosen words, so the workspace does not grow.  bias_row (B) is indexed by batch entry
+ * b = (image, sample).  rules NULL or inactive (every control off, no bias): the launches and the bits of the call without them.
+ * Composes unchanged with a guide, an attention trace, skip_dead, early_stop and every numerics mode: only the contents of the
+ * logits block change.  d->log_probs sums the log-probs under the edited distributions.  SSC_EINVAL before any launch: a field of
+ * `rules` beyond its limits (as above, with V = cfg->V); active rules with max_steps > SSC_RULES_MAX_LEN or
+ * V <= max_steps + n_suppress.  SSC_EALIGN: bias or bias_row no multiple of 4. */
 
 /* ------------------------------------------------------------------------------------------------
  * Truncation for the word samplers: cuts that adapt to each step's entropy - locally typical sampling (Meister et al. 2022), min-p
@@ -1493,17 +1488,13 @@ typedef struct {
  * SSC_EALIGN: logits, last_pred, entropy or kept no multiple of 4.  kind 0: SSC_OK with no launch. */
 int ssc_truncate_rows(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature, const int64_t* last_pred,
                       int end_index, void* stream);
-/* ssc_decode_sample_rules with one ssc_truncate_rows launch per step, step 0 included, between the rules' edit and the draw:
- * per step the logit rules, then the truncation, then the sampler's own top-k / top-p, all on the distribution tempered by
- * s->temperature; last_pred is the previous step's words.  Here trunc->entropy / trunc->kept are (max_steps, B) blocks or NULL:
- * step t writes slab t, slabs of steps never queued (early_stop) are not written.  trunc NULL or kind 0: the launches and the
- * bits of ssc_decode_sample_rules, which is this call with trunc = NULL.  The workspace is that of ssc_decode_sample.
- * d->log_probs sums the log-probs under the edited distributions.  SSC_EINVAL before any launch: what ssc_decode_sample_rules
- * refuses; kind outside 0 .. 4; a value outside its range.  SSC_EALIGN: entropy or kept no multiple of 4. */
-size_t ssc_decode_sample_trunc_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d);
-int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
-                            const ssc_logit_rules* rules, const ssc_truncation* trunc, const ssc_latent_guide* guide,
-                            void* workspace, size_t workspace_bytes, void* stream);
+/* As the `trunc` field of ssc_sample_opts (below): one ssc_truncate_rows launch per step of the sampled decode, step 0 included;
+ * the truncation and then the sampler's own top-k / top-p both act on the distribution tempered by s->temperature; last_pred is the
+ * previous step's words.  There trunc->entropy / trunc->kept are (max_steps, B) blocks or NULL: step t writes slab t, slabs of steps
+ * never queued (early_stop) are not written.  trunc NULL or kind 0: the launches and the bits of the call without it.  The edit is
+ * in place and keeps nothing between the steps, so the workspace does not grow.  d->log_probs sums the log-probs under the edited
+ * distributions.  SSC_EINVAL before any launch: kind outside 0 .. 4; a value outside its range.  SSC_EALIGN: entropy or kept no
+ * multiple of 4. */
 
 /* ------------------------------------------------------------------------------------------------
  * Contrastive decoding for the word samplers (Li et al. 2023; with a degraded image as the amateur: visual contrastive decoding,
@@ -1553,20 +1544,40 @@ typedef struct {
   int* kept;                     /* (max_steps, B) or NULL: step t writes slab t with ssc_contrast_rows' kept; slabs of steps never ... */
   float* divergence;             /* ... queued (early_stop) are not written.  (max_steps, B) or NULL: ssc_contrast_rows' divergence */
 } ssc_contrast;
-/* ssc_decode_sample_trunc with an amateur stream.  Per step, for a live row: the expert's decode step; the amateur's decode step,
- * fed the same tokens, on its own two generations of states, its own alpha scratch, logits block, attended-feature-table decision
- * and step workspace (as a member of ssc_decode_search_ensemble has), sharing row_lp / skip_dead with the expert; one
- * ssc_contrast_rows launch; the logit rules; the truncation; the draw.  Everything runs on `stream`.  With alpha == 0 the amateur is
- * not stepped and the workspace is that of ssc_decode_sample.  The attention trace records the expert; early stop, the pacer, ctl
- * and host_flag are untouched.  contrast NULL, or alpha == 0 && beta == 0: the launches and the bits of ssc_decode_sample_trunc,
- * which is this call with contrast = NULL.  d->log_probs sums the log-probs under the edited distributions.
- * SSC_EINVAL before any launch: what ssc_decode_sample_trunc refuses; alpha or beta outside their ranges; feats without imgbuf or
- * imgbuf without feats; params without them; guide_mode outside 0 / 1; with alpha != 0 a start on one side only or with a NULL
- * state block.  SSC_EALIGN: kept or divergence no multiple of 4. */
-size_t ssc_decode_sample_contrast_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_contrast* contrast);
-int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
-                               const ssc_contrast* contrast, const ssc_logit_rules* rules, const ssc_truncation* trunc,
-                               const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream);
+/* As the `contrast` field of ssc_sample_opts (below): the sampled decode with an amateur stream.  Per step the amateur's decode step
+ * is fed the expert's tokens, on its own two generations of states, its own alpha scratch, logits block, attended-feature-table
+ * decision and step workspace (as a member of ssc_decode_search_ensemble has), sharing row_lp / skip_dead with the expert; then one
+ * ssc_contrast_rows launch.  Everything runs on `stream`.  With alpha == 0 the amateur is not stepped and the workspace does not
+ * grow.  The attention trace records the expert; early stop, the pacer, ctl and host_flag are untouched.  contrast NULL, or
+ * alpha == 0 && beta == 0: the launches and the bits of the call without it.  d->log_probs sums the log-probs under the edited
+ * distributions.  SSC_EINVAL before any launch: alpha or beta outside their ranges; feats without imgbuf or imgbuf without feats;
+ * params without them; guide_mode outside 0 / 1; with alpha != 0 a start on one side only or with a NULL state block.  SSC_EALIGN:
+ * kept or divergence no multiple of 4. */
+
+/* ------------------------------------------------------------------------------------------------
+ * The options of one sampled decode: the latent guide, the logit rules, the truncation and the contrast (their blocks above), beside
+ * the search and sampler descriptors.  The next option is a field appended here - no entry of its own, no move of ssc_version().
+ * Per step, for a live row, in this order: the expert's decode step (its z block from slab t of the guide); the amateur's decode
+ * step; the contrast; the logit rules; the truncation; the draw.
+ * The `bytes` rule: `bytes` is sizeof(ssc_sample_opts) as the CALLER was built.  A field is read only if it lies wholly inside the
+ * first `bytes` bytes; otherwise it is NULL.  So a caller built before an option existed keeps working against a later library.
+ * SSC_EINVAL before anything else is read: bytes < sizeof(size_t); bytes no multiple of the pointer size; bytes above this library's
+ * sizeof(ssc_sample_opts) - such a caller knows an option this library would silently drop.
+ * opts NULL, or every field NULL or off: the calls ARE ssc_decode_sample_workspace_bytes / ssc_decode_sample - the same launches, the
+ * same bits.  ssc_decode_sample_opts_workspace_bytes grows over the plain call's only by an amateur that is stepped (contrast
+ * alpha != 0); it is 0 for a `bytes` it refuses.  SSC_EINVAL before any launch: what ssc_decode_sample and each option's block
+ * refuse; a start state (d->start) together with a guide.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  size_t bytes;                     /* sizeof(ssc_sample_opts) as the caller was built */
+  const ssc_latent_guide* guide;    /* NULL: the prior */
+  const ssc_logit_rules*  rules;    /* NULL or every control off: no edit */
+  const ssc_truncation*   trunc;    /* NULL or kind 0: no cut */
+  const ssc_contrast*     contrast; /* NULL or alpha == beta == 0: no amateur, no contrast */
+} ssc_sample_opts;
+size_t ssc_decode_sample_opts_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_sample_opts* opts);
+int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                           const ssc_sample_opts* opts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Prompted decoding: start the one-call decodes from a forced prefix ("a happy ...").  ssc_decode_prime teacher-forces the prefix

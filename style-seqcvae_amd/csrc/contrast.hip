@@ -2,7 +2,7 @@
 // row - the same words decoded from a degraded image, a neutral latent or a weaker checkpoint - become, in place over the expert's,
 //   y[v] = lp_e[v] + alpha * (lp_e[v] - lp_a[v])   where beta == 0 or lp_e[v] >= log(beta) + max_u lp_e[u],   -inf elsewhere
 // (Li et al. 2023), a row of raw logits for the logit rules, the truncation and the unchanged draw behind it.  ssc_contrast_rows is
-// the stand-alone edit of one step; ssc_decode_sample_contrast (sample.hip) issues it between each step's two decode steps and its
+// the stand-alone edit of one step; ssc_decode_sample_opts (sample.hip) issues it between each step's two decode steps and its
 // logit rules.
 // One workgroup of 256 per row, as log_softmax_kernel and ssc_ensemble_combine_rows.  The passes of a live row:
 //   1. the expert's log-sum-exp by beam_row_lse (beam_common.h): the arithmetic and the thread ownership of log_softmax_kernel, so

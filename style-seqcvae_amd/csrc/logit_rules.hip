@@ -1,7 +1,7 @@
 // Logit rules for the word samplers (ssc_logit_rules, include/ssc.h): a word bias, repetition / presence / frequency penalties and
 // bans (blocked n-grams, a minimum length, suppressed tokens), applied to the RAW logits of a row in front of the draw, so that the
 // sampler draws from - and reports the log-prob under - the edited distribution.  ssc_logit_rules_rows is the stand-alone edit of
-// one step; ssc_decode_sample_rules (sample.hip) issues it between each step's decode step and its draw.
+// one step; ssc_decode_sample_opts (sample.hip) issues it between each step's decode step and its draw.
 // Two forms, chosen on the host:
 //   (A) with a bias, one workgroup of 256 per row streams the row once, x += bias: 16 bytes per lane where both rows share one
 //       misalignment and both leading dimensions are multiples of 4 (scalar head / float4 bulk / scalar tail, as distill.hip's

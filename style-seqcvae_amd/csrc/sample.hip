@@ -12,7 +12,7 @@
 // counter-based Philox4x32-10 noise: bit-reproducible for a given seed, no float atomics, no order-dependent reduction.
 // The draw of one row (sample_draw_row) lives in sample_draw.h: the scheduled-sampling mix kernel of the train step calls the same code.
 // The edits of the raw logits in front of the draw - the logit rules (logit_rules.hip) and the truncation (truncation.hip) - are launches
-// of their own between a step's decode step and its draw (ssc_decode_sample_trunc); the draw itself does not know of them.
+// of their own between a step's decode step and its draw (ssc_decode_sample_opts); the draw itself does not know of them.
 // ssc_decode_sample's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
 
@@ -179,46 +179,6 @@ extern "C" int ssc_sample_rows(const float* logits, int ld, int rows, int V, con
   return sample_launch(a, rows, (hipStream_t)stream);
 }
 
-extern "C" size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  if (!ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return 0;
-  return sample_layout(cfg, d).total;
-}
-
-extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
-                                 void* workspace, size_t workspace_bytes, void* stream) {
-  return ssc_decode_sample_guided(cfg, p, d, s, nullptr, workspace, workspace_bytes, stream);
-}
-
-// guide (or null): step t's z block from slab t of the call's latent guide, one entry per row
-extern "C" int ssc_decode_sample_guided(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
-                                        const ssc_sampler_desc* s, const ssc_latent_guide* guide, void* workspace,
-                                        size_t workspace_bytes, void* stream) {
-  return ssc_decode_sample_rules(cfg, p, d, s, nullptr, guide, workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t ssc_decode_sample_rules_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  return ssc_decode_sample_workspace_bytes(cfg, d);   // the history is the call's own block of chosen words
-}
-
-// rules (or null): the logit rules of include/ssc.h, one launch between each step's decode step and its draw
-extern "C" int ssc_decode_sample_rules(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
-                                       const ssc_sampler_desc* s, const ssc_logit_rules* rules, const ssc_latent_guide* guide,
-                                       void* workspace, size_t workspace_bytes, void* stream) {
-  return ssc_decode_sample_trunc(cfg, p, d, s, rules, nullptr, guide, workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t ssc_decode_sample_trunc_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
-  return ssc_decode_sample_workspace_bytes(cfg, d);   // the edit is in place and keeps nothing between the steps
-}
-
-// trunc (or null): the truncation of include/ssc.h, one launch between each step's logit rules and its draw; step t's statistics go
-// to slab t of trunc->entropy / trunc->kept
-extern "C" int ssc_decode_sample_trunc(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
-                                       const ssc_sampler_desc* s, const ssc_logit_rules* rules, const ssc_truncation* trunc,
-                                       const ssc_latent_guide* guide, void* workspace, size_t workspace_bytes, void* stream) {
-  return ssc_decode_sample_contrast(cfg, p, d, s, nullptr, rules, trunc, guide, workspace, workspace_bytes, stream);
-}
-
 namespace {
 
 // The amateur stream of a contrastive call (ssc_contrast, include/ssc.h), behind the expert's blocks: what an ensemble member has of
@@ -239,23 +199,52 @@ size_t contrast_layout(const ssc_model_cfg* cfg, const ssc_search_desc* d, const
   return o;
 }
 
+// the fields of a caller's ssc_sample_opts that lie inside its `bytes` (include/ssc.h: the `bytes` rule), the others null; opts null:
+// every field null.  false: a size this library refuses.  Every field behind `bytes` is one pointer, so a whole number of pointers
+// holds whole fields.
+static_assert(sizeof(ssc_sample_opts) == 5 * sizeof(void*), "ssc_sample_opts: the size and four pointers (a later option: one more)");
+bool sample_opts_read(const ssc_sample_opts* opts, ssc_sample_opts* o) {
+  *o = ssc_sample_opts{};
+  if (!opts) return true;
+  const size_t n = opts->bytes;
+  if (n < sizeof(size_t) || n % sizeof(void*) != 0 || n > sizeof(ssc_sample_opts)) return false;
+  memcpy(o, opts, n);
+  return true;
+}
+
 }  // namespace
 
-extern "C" size_t ssc_decode_sample_contrast_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
-                                                             const ssc_contrast* contrast) {
-  if (!ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return 0;
+extern "C" size_t ssc_decode_sample_opts_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
+                                                         const ssc_sample_opts* opts) {
+  ssc_sample_opts o;
+  if (!sample_opts_read(opts, &o) || !ssc_decode_dims_ok(cfg, d, d ? d->max_steps : 0)) return 0;
   const SampleLayout l = sample_layout(cfg, d);
-  if (!contrast_steps_amateur(contrast)) return l.total;
+  if (!contrast_steps_amateur(o.contrast)) return l.total;
   AmateurLayout am;
   return contrast_layout(cfg, d, l, &am);
 }
 
-// contrast (or null): the amateur stream and the contrast of include/ssc.h - per step the amateur's decode step behind the expert's,
-// then one ssc_contrast_rows launch in front of the logit rules; step t's statistics go to slab t of contrast->kept / ->divergence
-extern "C" int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
-                                          const ssc_sampler_desc* s, const ssc_contrast* contrast, const ssc_logit_rules* rules,
-                                          const ssc_truncation* trunc, const ssc_latent_guide* guide, void* workspace,
-                                          size_t workspace_bytes, void* stream) {
+extern "C" size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
+  return ssc_decode_sample_opts_workspace_bytes(cfg, d, nullptr);
+}
+
+extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+  return ssc_decode_sample_opts(cfg, p, d, s, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The sampled decode under its options (include/ssc.h, ssc_sample_opts).  Per step: the expert's decode step (its z block from slab t
+// of the guide), the amateur's decode step, the contrast, the logit rules, the truncation, the draw; step t's statistics go to slab t
+// of contrast->kept / ->divergence and trunc->entropy / ->kept.
+extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                      const ssc_sampler_desc* s, const ssc_sample_opts* opts, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  ssc_sample_opts o;
+  if (!sample_opts_read(opts, &o)) return SSC_EINVAL;
+  const ssc_latent_guide* guide = o.guide;
+  const ssc_logit_rules* rules = o.rules;
+  const ssc_truncation* trunc = o.trunc;
+  const ssc_contrast* contrast = o.contrast;
   SscGemmModeScope mode_scope(cfg);   // the numerics mode of this cfg, for every product the call issues
   if (!p || !workspace || !sample_desc_ok(cfg, d) || !sampler_ok(s, cfg->V)) return SSC_EINVAL;
   if (guide && !ssc_latent_guide_ok(cfg, guide)) return SSC_EINVAL;
@@ -288,18 +277,6 @@ extern "C" int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_pa
   hipStream_t st = (hipStream_t)stream;
   char* W = (char*)workspace;
   const int B = d->nimg * d->n_samples, V = cfg->V, Z = cfg->Z;
-  // step t's contrast: the expert's logits edited in place against the amateur's, the statistics of slab t
-  auto contrast_step = [&](int t, const int64_t* last) {
-    return ssc_contrast_launch((float*)(W + l.logits), V, amateur ? (const float*)(W + am.logits) : nullptr, V, B, V, contrast->alpha,
-                               contrast->beta, contrast->kept ? contrast->kept + (size_t)t * B : nullptr,
-                               contrast->divergence ? contrast->divergence + (size_t)t * B : nullptr, last, d->end_index, st);
-  };
-  // step t's truncation: the statistics of slab t
-  auto truncate = [&](int t, const int64_t* last) {
-    return ssc_truncation_launch((float*)(W + l.logits), V, B, V, trunc, s->temperature,
-                                 trunc->entropy ? trunc->entropy + (size_t)t * B : nullptr,
-                                 trunc->kept ? trunc->kept + (size_t)t * B : nullptr, last, d->end_index, st);
-  };
   const SscStepStates& states = l.states;
   int64_t* tokens0 = (int64_t*)(W + l.tokens0);
   int64_t* parent0 = (int64_t*)(W + l.parent0);
@@ -346,14 +323,24 @@ extern "C" int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_pa
     return ssc_decode_step_guided(cfg, pa, &sa, &sga, W + am.stepws, am.stepws_bytes, st);
   };
   if (amateur) SSC_TRY(amateur_step(1));
-  if (contrasted) SSC_TRY(contrast_step(0, nullptr));
-  if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, 0, d->end_index, st));
-  if (cut) SSC_TRY(truncate(0, nullptr));
   SampleArgs a = sample_args(s, logits, (size_t)V, V);
   a.end_index = d->end_index; a.row_lp = lp; a.lp_out = steplp;
   a.ctl = d->early_stop ? ctl : nullptr; a.max_steps = d->max_steps; a.host_flag = d->early_stop ? d->host_flag : nullptr;
-  a.step = 0; a.last_pred = nullptr; a.pred_out = preds;
-  SSC_TRY(sample_launch(a, B, st));
+  // the tail of step t, behind its decode steps: the edits of the expert's logits in place - the contrast against the amateur's, the
+  // logit rules, the truncation, their statistics going to slab t - and the draw; last: the previous step's words (null at step 0)
+  auto edit_and_draw = [&](int t, const int64_t* last) -> int {
+    if (contrasted)
+      SSC_TRY(ssc_contrast_launch(logits, V, amateur ? (const float*)(W + am.logits) : nullptr, V, B, V, contrast->alpha, contrast->beta,
+                                  contrast->kept ? contrast->kept + (size_t)t * B : nullptr,
+                                  contrast->divergence ? contrast->divergence + (size_t)t * B : nullptr, last, d->end_index, st));
+    if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, t, d->end_index, st));
+    if (cut)
+      SSC_TRY(ssc_truncation_launch(logits, V, B, V, trunc, s->temperature, trunc->entropy ? trunc->entropy + (size_t)t * B : nullptr,
+                                    trunc->kept ? trunc->kept + (size_t)t * B : nullptr, last, d->end_index, st));
+    a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
+    return sample_launch(a, B, st);
+  };
+  SSC_TRY(edit_and_draw(0, nullptr));
   const SscStepPacer pacer(d->early_stop, d->host_flag_host, st);   // (the sampler's last workgroup of a step notes it for the host)
   int cur = 0;
   sd.parent = parent0; sd.group = 1;
@@ -369,11 +356,7 @@ extern "C" int ssc_decode_sample_contrast(const ssc_model_cfg* cfg, const ssc_pa
     SSC_TRY(ssc_decode_step_guided(cfg, p, &sd, &sg, W + l.stepws, l.stepws_bytes, st));
     sga.t = t;
     if (amateur) SSC_TRY(amateur_step(cur));
-    if (contrasted) SSC_TRY(contrast_step(t, last));
-    if (ruled) SSC_TRY(ssc_logit_rules_launch(logits, V, B, V, rules, preds, B, t, d->end_index, st));
-    if (cut) SSC_TRY(truncate(t, last));
-    a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
-    SSC_TRY(sample_launch(a, B, st));
+    SSC_TRY(edit_and_draw(t, last));
     cur = 1 - cur;
   }
   SSC_LAUNCH(sample_collect_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, st, preds, d->early_stop ? ctl : nullptr, d->max_steps, B,

@@ -219,19 +219,20 @@ int ssc_decode_step_guided(const ssc_model_cfg* cfg, const ssc_params* p, const 
                            void* workspace, size_t workspace_bytes, void* stream);
 // Logit rules for the word samplers (logit_rules.hip, include/ssc.h: ssc_logit_rules).  ssc_logit_rules_check: the refusals that
 // depend on the fields and V alone (SSC_OK with *active = whether any control is on or a bias is set); ssc_logit_rules_launch: the
-// edit of one step from checked rules - what ssc_decode_sample_rules issues per step.
+// edit of one step from checked rules - what ssc_decode_sample_opts issues per step for its `rules`.
 int ssc_logit_rules_check(const ssc_logit_rules* r, int V, int end_index, bool* active);
 int ssc_logit_rules_launch(float* logits, int ld, int rows, int V, const ssc_logit_rules* r, const int64_t* hist, int ld_hist, int t,
                            int end_index, hipStream_t st);
 // Truncation for the word samplers (truncation.hip, include/ssc.h: ssc_truncation).  ssc_truncation_check: the refusals that depend
 // on the fields and the temperature alone (SSC_OK with *active = kind != 0); ssc_truncation_launch: the edit of one step from a
-// checked descriptor, its statistics going to `entropy` / `kept` (rows, or null) - what ssc_decode_sample_trunc issues per step.
+// checked descriptor, its statistics going to `entropy` / `kept` (rows, or null) - what ssc_decode_sample_opts issues per step for its
+// `trunc`.
 int ssc_truncation_check(const ssc_truncation* tr, float temperature, bool* active);
 int ssc_truncation_launch(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature, float* entropy, int* kept,
                           const int64_t* last_pred, int end_index, hipStream_t st);
 // Contrastive decoding for the word samplers (contrast.hip, include/ssc.h: ssc_contrast_rows, ssc_contrast).  ssc_contrast_check: the
 // refusals that depend on the knobs and the statistics pointers alone (SSC_OK with *active = alpha != 0 || beta != 0);
-// ssc_contrast_launch: the edit of one step from checked knobs - what ssc_decode_sample_contrast issues per step.
+// ssc_contrast_launch: the edit of one step from checked knobs - what ssc_decode_sample_opts issues per step for its `contrast`.
 int ssc_contrast_check(float alpha, float beta, const int* kept, const float* divergence, bool* active);
 int ssc_contrast_launch(float* logits, int ld, const float* amateur, int lda, int rows, int V, float alpha, float beta, int* kept,
                         float* divergence, const int64_t* last_pred, int end_index, hipStream_t st);

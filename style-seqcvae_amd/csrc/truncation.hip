@@ -1,6 +1,6 @@
 // Entropy-adaptive truncation for the word samplers (ssc_truncation, include/ssc.h): locally typical, min-p, eta and epsilon cuts
 // of a row of RAW logits in front of the unchanged draw, so that the sampler draws from - and reports the log-prob under - the cut
-// distribution.  ssc_truncate_rows is the stand-alone edit of one step; ssc_decode_sample_trunc (sample.hip) issues it between each
+// distribution.  ssc_truncate_rows is the stand-alone edit of one step; ssc_decode_sample_opts (sample.hip) issues it between each
 // step's logit rules and its draw.
 // One workgroup of SAMPLE_THREADS per row, two forms as for the samplers (ssc_radix.h): the row staged in LDS once for
 // V <= SAMPLE_LDS_MAX_V, every pass over global memory above that.  The passes of a live row:

@@ -2,7 +2,7 @@
 
 A second, *amateur* stream is decoded in lock-step with the normal *expert* stream, fed the same words, and every step's raw logits
 become  lp_e + alpha * (lp_e - lp_a)  on the expert's plausible words (lp_e >= log(beta) + max lp_e), -inf elsewhere, in front of the
-logit rules, the truncation and the unchanged draw (DecodeEngine.sample(contrast=) / ssc_decode_sample_contrast).  What the amateur
+logit rules, the truncation and the unchanged draw (DecodeEngine.sample(contrast=) / ssc_sample_opts.contrast).  What the amateur
 lacks is what the decode gets more of:
 
     Contrast(1.0, features="mean")            the image: every region replaced by the image's mean region - the language prior

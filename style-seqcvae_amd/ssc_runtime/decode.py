@@ -363,20 +363,20 @@ class DecodeEngine:
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
                attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None, truncation=None,
                truncation_stats: bool = False, contrast=None, contrast_stats: bool = False):
-        """The whole sampled decode of one call in ONE library call (ssc_decode_sample): ctx.nimg images x n_samples latent samples,
+        """The whole sampled decode of one call in ONE library call (ssc_decode_sample_opts): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
         -> (predictions (B, steps) int64, log_probs (B,): each caption's summed untempered log-prob).
-        guide: a LatentGuide over the B entries, or None (ssc_decode_sample_guided; see search).
+        guide: a LatentGuide over the B entries, or None (ssc_sample_opts.guide; see search).
         logit_rules: a sampling.LogitRules, or None - every step's raw logits are edited in front of the draw
-        (ssc_decode_sample_rules: word bias, repetition / presence / frequency penalties, n-gram / length / token bans) and the
-        log-probs are those under the edited distributions; None or inactive rules take the entry point of a call without them.
+        (ssc_sample_opts.rules: word bias, repetition / presence / frequency penalties, n-gram / length / token bans) and the
+        log-probs are those under the edited distributions; None or inactive rules leave the field NULL.
         truncation: a sampling.Truncation, or None - every step's raw logits are cut between the logit rules and the draw
-        (ssc_decode_sample_trunc: typical, min-p, eta or epsilon truncation of the distribution tempered by the sampler's
+        (ssc_sample_opts.trunc: typical, min-p, eta or epsilon truncation of the distribution tempered by the sampler's
         temperature); None or an inactive one issues the call without it.  truncation_stats=True (with an active truncation):
         the result is followed by (entropy (B, steps) float32 in nats, kept (B, steps) int32 - the entries left finite), zero
         for ended rows and in the columns past the stop.
-        contrast: a contrast.Contrast, or None - contrastive decoding (ssc_decode_sample_contrast): an amateur stream is decoded in
+        contrast: a contrast.Contrast, or None - contrastive decoding (ssc_sample_opts.contrast): an amateur stream is decoded in
         lock-step with this one, fed the same words, and every step's raw logits are contrasted with the amateur's in front of the
         logit rules; None or an inactive one issues the call without it.  With start= the Contrast carries the amateur's own
         StartState (Contrast.start).  contrast_stats=True (with an active contrast): the result is followed - behind the
@@ -394,47 +394,38 @@ class DecodeEngine:
             raise ValueError("DecodeEngine.sample: truncation_stats needs an active truncation")
         sampler.check_vocab(self.dims.V)
         sdesc = sampler.desc(seed)
-        call = lambda p, sd, ws: self.lib.ssc_decode_sample(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), *ws)
-        gd = None
+        B = ctx.nimg * n_samples
+        # one descriptor for the call's options; every object behind a field stays alive in `keep` until the call has returned
+        opts = _lib.SampleOpts(bytes=C.sizeof(_lib.SampleOpts))
+        keep = []
         if guide is not None:
-            gd, _keep = self._guide_desc(guide, ctx.nimg * n_samples)
-            call = lambda p, sd, ws: self.lib.ssc_decode_sample_guided(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
-                                                                       C.byref(gd), *ws)
-        workspace_bytes = self.lib.ssc_decode_sample_workspace_bytes
+            gd, _keep = self._guide_desc(guide, B)
+            opts.guide = C.pointer(gd)
+            keep += [gd, _keep]
         if logit_rules is not None and logit_rules.active:
             logit_rules.check(self.dims.V, end_index, max_steps, ctx.nimg)
-            rd, _keep_rules = logit_rules.desc(n_samples)
-            call = lambda p, sd, ws: self.lib.ssc_decode_sample_rules(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
-                                                                      C.byref(rd), C.byref(gd) if gd is not None else None, *ws)
-            workspace_bytes = self.lib.ssc_decode_sample_rules_workspace_bytes
+            rd, _keep = logit_rules.desc(n_samples)
+            opts.rules = C.pointer(rd)
+            keep += [rd, _keep]
         ent = kept = None
         if truncation is not None:
-            if not (logit_rules is not None and logit_rules.active):
-                rd = None
-            B = ctx.nimg * n_samples
             if truncation_stats:   # (max_steps, B) blocks; slabs of steps never queued stay zero
                 ent = torch.zeros(max_steps, B, dtype=torch.float32, device=self.device)
                 kept = torch.zeros(max_steps, B, dtype=torch.int32, device=self.device)
             td = truncation.desc(ent, kept)
-            call = lambda p, sd, ws: self.lib.ssc_decode_sample_trunc(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
-                                                                      C.byref(rd) if rd is not None else None, C.byref(td),
-                                                                      C.byref(gd) if gd is not None else None, *ws)
-            workspace_bytes = self.lib.ssc_decode_sample_trunc_workspace_bytes
+            opts.trunc = C.pointer(td)
+            keep.append(td)
         ckept = cdiv = None
         if contrast is not None:
-            if not (logit_rules is not None and logit_rules.active):
-                rd = None
-            if truncation is None:
-                td = None
-            B = ctx.nimg * n_samples
             if contrast_stats:   # (max_steps, B) blocks; slabs of steps never queued stay zero
                 ckept = torch.zeros(max_steps, B, dtype=torch.int32, device=self.device)
                 cdiv = torch.zeros(max_steps, B, dtype=torch.float32, device=self.device)
-            cd, _keep_contrast = contrast.desc(self, ctx, n_samples, max_steps, start is not None, ckept, cdiv)
-            call = lambda p, sd, ws: self.lib.ssc_decode_sample_contrast(
-                C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc), C.byref(cd), C.byref(rd) if rd is not None else None,
-                C.byref(td) if td is not None else None, C.byref(gd) if gd is not None else None, *ws)
-            workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_contrast_workspace_bytes(cfg, sd, C.byref(cd))
+            cd, _keep = contrast.desc(self, ctx, n_samples, max_steps, start is not None, ckept, cdiv)
+            opts.contrast = C.pointer(cd)
+            keep += [cd, _keep]
+        call = lambda p, sd, ws: self.lib.ssc_decode_sample_opts(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
+                                                                 C.byref(opts), *ws)
+        workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_opts_workspace_bytes(cfg, sd, C.byref(opts))
         out = self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
         if truncation_stats:

@@ -249,6 +249,12 @@ class Contrast(C.Structure):
                 ("divergence", vp)]
 
 
+class SampleOpts(C.Structure):
+    """ssc_sample_opts: `bytes` is sizeof(SampleOpts); a field behind it is not read (include/ssc.h, the `bytes` rule)."""
+    _fields_ = [("bytes", C.c_size_t), ("guide", C.POINTER(LatentGuideDesc)), ("rules", C.POINTER(LogitRules)),
+                ("trunc", C.POINTER(Truncation)), ("contrast", C.POINTER(Contrast))]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -394,8 +400,6 @@ SYMBOLS = {
     "ssc_latent_guide_rows": (_i, [C.POINTER(LatentGuideDesc), _i, _i, _i, _i, vp, _i, vp, _f, _f, vp, _i, vp]),
     "ssc_decode_search_guided": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(LatentGuideDesc), vp, _sz,
                                       vp]),
-    "ssc_decode_sample_guided": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
-                                      C.POINTER(LatentGuideDesc), vp, _sz, vp]),
     "ssc_decode_score_guided": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(ScoreDesc), C.POINTER(LatentGuideDesc), vp, _sz,
                                      vp]),
     "ssc_caption_match": (_i, [vp, _i, vp, _i, _i, _i, vp, vp]),
@@ -422,18 +426,11 @@ SYMBOLS = {
     "ssc_decode_rules_beam": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(RulesDesc), vp, vp, vp,
                                    _sz, vp]),
     "ssc_logit_rules_rows": (_i, [vp, _i, _i, _i, C.POINTER(LogitRules), vp, _i, _i, _i, vp]),
-    "ssc_decode_sample_rules_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
-    "ssc_decode_sample_rules": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
-                                     C.POINTER(LogitRules), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
     "ssc_truncate_rows": (_i, [vp, _i, _i, _i, C.POINTER(Truncation), _f, vp, _i, vp]),
-    "ssc_decode_sample_trunc_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc)]),
-    "ssc_decode_sample_trunc": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
-                                     C.POINTER(LogitRules), C.POINTER(Truncation), C.POINTER(LatentGuideDesc), vp, _sz, vp]),
     "ssc_contrast_rows": (_i, [vp, _i, vp, _i, _i, _i, _f, _f, vp, _i, vp, vp, vp]),
-    "ssc_decode_sample_contrast_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(Contrast)]),
-    "ssc_decode_sample_contrast": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
-                                        C.POINTER(Contrast), C.POINTER(LogitRules), C.POINTER(Truncation),
-                                        C.POINTER(LatentGuideDesc), vp, _sz, vp]),
+    "ssc_decode_sample_opts_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(SampleOpts)]),
+    "ssc_decode_sample_opts": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                    C.POINTER(SampleOpts), vp, _sz, vp]),
     "ssc_decode_prime_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(PrimeDesc)]),
     "ssc_decode_prime": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(PrimeDesc), vp, _sz, vp]),
     "ssc_prefix_join": (_i, [vp, vp, _i, vp, vp, _i, vp, vp, _i, _i, _i, vp, vp, vp]),

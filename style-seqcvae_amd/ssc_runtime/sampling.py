@@ -21,11 +21,11 @@ MIN_CAPTION_LENGTH / LENGTH_PENALTY_ALPHA / SUPPRESS_UNKNOWN), for the determini
 
 LogitRules are the word samplers' own controls, a second and separate mechanism: the raw logits of every sampled step are edited in
 front of the draw - a word bias, repetition / presence / frequency penalties, blocked n-grams, a minimum length, suppressed tokens
-(DecodeEngine.sample(logit_rules=) / ssc_decode_sample_rules, MODEL.SAMPLER_NO_REPEAT_NGRAM and its kin) - so that the sampler
+(DecodeEngine.sample(logit_rules=) / ssc_sample_opts.rules, MODEL.SAMPLER_NO_REPEAT_NGRAM and its kin) - so that the sampler
 draws from the edited distribution, where DecodeRules ban after the log-softmax and renormalise nothing.
 
 Truncation is the word samplers' entropy-adaptive cut - locally typical, min-p, eta and epsilon sampling - made the same way: one
-more edit of the raw logits between the logit rules and the draw (DecodeEngine.sample(truncation=) / ssc_decode_sample_trunc,
+more edit of the raw logits between the logit rules and the draw (DecodeEngine.sample(truncation=) / ssc_sample_opts.trunc,
 MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE).  The samplers themselves are unchanged.
 """
 import math
@@ -330,7 +330,7 @@ class LogitRules:
                     or np.float32(self.presence_penalty) != 0 or np.float32(self.frequency_penalty) != 0 or self.bias is not None)
 
     def check(self, V: int, end_index: int, max_steps: int, nimg: int) -> None:
-        """The limits of ssc_decode_sample_rules for a call over nimg images, and the bias's contents (one read-back)."""
+        """The limits of ssc_decode_sample_opts' rules for a call over nimg images, and the bias's contents (one read-back)."""
         if not self.active:
             return
         if max_steps > _lib.SSC_RULES_MAX_LEN:
@@ -417,7 +417,7 @@ TRUNCATION_KINDS = {"none": 0, "typical": 1, "min-p": 2, "eta": 3, "epsilon": 4}
 class Truncation:
     """A truncation of the word samplers' distribution (ssc_truncation in include/ssc.h): a cut that adapts to each step's entropy,
     made on the raw logits of every step between the logit rules and the draw (DecodeEngine.sample(truncation=) /
-    ssc_decode_sample_trunc), so that the sampler - multinomial, top-k or top-p - draws from the cut distribution, tempered by the
+    ssc_sample_opts.trunc), so that the sampler - multinomial, top-k or top-p - draws from the cut distribution, tempered by the
     sampler's temperature, and reports the log-prob under it.  kind: 0 off, 1 typical, 2 min-p, 3 eta, 4 epsilon; value: the mass
     tau / the ratio m in (0, 1], or epsilon in (0, 1)."""
     name = "none"

@@ -147,6 +147,21 @@ def search_desc(a, beam=4, per_node=2):
     return d
 
 
+def sample_opts(guide=None, rules=None, trunc=None, contrast=None, nbytes=None):
+    """-> an ssc_sample_opts over the given descriptors (ctypes structures, or None: a NULL field); bytes = its own size unless given."""
+    o = L.SampleOpts(bytes=C.sizeof(L.SampleOpts) if nbytes is None else nbytes)
+    for field, desc in (("guide", guide), ("rules", rules), ("trunc", trunc), ("contrast", contrast)):
+        if desc is not None:
+            setattr(o, field, C.pointer(desc))
+    return o
+
+
+# the per-feature entries of the sampled decode that ssc_sample_opts / ssc_decode_sample_opts replaced
+RETIRED_SAMPLE_ENTRIES = ("ssc_decode_sample_guided", "ssc_decode_sample_rules", "ssc_decode_sample_rules_workspace_bytes",
+                          "ssc_decode_sample_trunc", "ssc_decode_sample_trunc_workspace_bytes", "ssc_decode_sample_contrast",
+                          "ssc_decode_sample_contrast_workspace_bytes")
+
+
 def score_desc(a):
     d = L.ScoreDesc()
     d.nimg, d.R, d.n_captions, d.n_samples, d.max_len, d.end_index = 2, 5, 3, 2, 6, 1

@@ -18,7 +18,7 @@ from ssc_runtime.decode import DecodeEngine, EnsembleDecodeEngine
 from ssc_runtime.engine import ModelDims
 from ssc_runtime.inference import diverse_decode
 from ssc_runtime.vocab import Vocabulary
-from test_attention_trace_cpu import CFG, header, model_cfg, search_desc, struct_fields
+from test_attention_trace_cpu import CFG, RETIRED_SAMPLE_ENTRIES, header, model_cfg, sample_opts, search_desc, struct_fields
 from truncationref import D_BAND
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -217,9 +217,15 @@ def test_bindings_mirror_the_header():
     assert struct_fields("ssc_contrast") == names == ["alpha", "beta", "params", "feats", "imgbuf", "sentiment", "eps0", "eps", "obj_atts",
                                                       "guide_mode", "start", "kept", "divergence"]
     assert C.sizeof(L.Contrast) == 96
-    for name in ("ssc_contrast_rows", "ssc_decode_sample_contrast_workspace_bytes", "ssc_decode_sample_contrast"):
+    for name in ("ssc_contrast_rows", "ssc_decode_sample_opts_workspace_bytes", "ssc_decode_sample_opts"):
         assert name in L.SYMBOLS and name + "(" in header()
-    assert len(L.SYMBOLS["ssc_contrast_rows"][1]) == 13 and len(L.SYMBOLS["ssc_decode_sample_contrast"][1]) == 11
+    assert len(L.SYMBOLS["ssc_contrast_rows"][1]) == 13
+    # the sampled decode's options are one descriptor - the header's field order, the size and four pointers - behind one entry
+    assert struct_fields("ssc_sample_opts") == [f for f, _ in L.SampleOpts._fields_] == ["bytes", "guide", "rules", "trunc", "contrast"]
+    assert C.sizeof(L.SampleOpts) == 5 * C.sizeof(C.c_void_p) and L.SampleOpts._fields_[4][1] is C.POINTER(L.Contrast)
+    cdll = C.CDLL(L.LIB_PATH)
+    for name in RETIRED_SAMPLE_ENTRIES:
+        assert name not in L.SYMBOLS and not hasattr(cdll, name) and name + "(" not in header(), name
     assert L.SYMBOLS["ssc_contrast_rows"][1][6] is C.c_float and L.SYMBOLS["ssc_contrast_rows"][1][7] is C.c_float
     assert L.load().ssc_version() == 4
     # the pinned structs keep their sizes
@@ -280,8 +286,9 @@ def test_decode_refuses_a_bad_contrast_before_any_launch():
     d = search_desc(a, beam=1, per_node=1)
     c_, dd = C.byref(cfg), C.byref(d)
     n0 = lib.ssc_decode_sample_workspace_bytes(c_, dd)
-    size = lambda c: lib.ssc_decode_sample_contrast_workspace_bytes(c_, dd, C.byref(c) if c is not None else None)
+    size = lambda c: lib.ssc_decode_sample_opts_workspace_bytes(c_, dd, C.byref(sample_opts(contrast=c)))
     assert n0 > 0 and size(None) == n0 == size(contrast(0.0, 0.0)) == size(contrast(0.0, 0.5))
+    assert lib.ssc_decode_sample_opts_workspace_bytes(c_, dd, None) == n0
     n = size(contrast())
     B, H, V, Rr = 6, CFG["H"], CFG["V"], 5
     assert n >= n0 + 4 * (8 * B * H + B * Rr + B * V) + lib.ssc_decode_step_workspace_bytes(c_, B, Rr)
@@ -290,8 +297,8 @@ def test_decode_refuses_a_bad_contrast_before_any_launch():
 
     def call(c, nbytes, smp=None, rules=None, trunc=None, guide=None):
         smp = smp or L.SamplerDesc(0, 0, 1.0, 1.0, 3)
-        return lib._raw_ssc_decode_sample_contrast(c_, C.byref(p), dd, C.byref(smp), C.byref(c) if c is not None else None, rules, trunc,
-                                                   guide, a, nbytes, None)
+        return lib._raw_ssc_decode_sample_opts(c_, C.byref(p), dd, C.byref(smp), C.byref(sample_opts(guide, rules, trunc, c)), a, nbytes,
+                                               None)
 
     assert call(None, n0 - 1) == -4 and call(contrast(0.0, 0.0), n0 - 1) == -4 and call(contrast(0.0, 0.5), n0 - 1) == -4
     for al, be in GOOD_KNOBS:
@@ -318,23 +325,23 @@ def test_decode_refuses_a_bad_contrast_before_any_launch():
     assert call(contrast(start=C.pointer(st)), n - 1) == -4 and call(contrast(start=C.pointer(no_tokens)), n - 1) == -4
     assert call(contrast(0.0, 0.5), n0 - 1) == -4           # (an amateur that is not stepped reads no start state)
     d.start = None
-    # everything ssc_decode_sample_trunc refuses stays refused: a bad sampler, bad rules, a bad truncation, a bad guide, a bad descriptor
+    # everything the call refuses without a contrast stays refused: a bad sampler, bad rules, a bad truncation, a bad guide, a bad descriptor
     assert call(contrast(), n, smp=L.SamplerDesc(0, 0, 1.0, 0.0, 3)) == -1
     bad_rules = L.LogitRules()
     bad_rules.repetition_penalty = 0.0
-    assert call(contrast(), n, rules=C.byref(bad_rules)) == -1
-    assert call(contrast(), n, trunc=C.byref(L.Truncation(1, 1.5, None, None))) == -1
-    assert call(contrast(), n - 1, trunc=C.byref(L.Truncation(2, 0.05, None, None))) == -4
-    assert call(contrast(), n, guide=C.byref(L.LatentGuideDesc(0, a, a, 4, a))) == -1
-    assert call(contrast(guide_mode=1), n - 1, guide=C.byref(L.LatentGuideDesc(3, a, a, 4, a))) == -4
+    assert call(contrast(), n, rules=bad_rules) == -1
+    assert call(contrast(), n, trunc=L.Truncation(1, 1.5, None, None)) == -1
+    assert call(contrast(), n - 1, trunc=L.Truncation(2, 0.05, None, None)) == -4
+    assert call(contrast(), n, guide=L.LatentGuideDesc(0, a, a, 4, a)) == -1
+    assert call(contrast(guide_mode=1), n - 1, guide=L.LatentGuideDesc(3, a, a, 4, a)) == -4
     d.feats = None
     assert call(contrast(), n) == -1
     d.feats = a
     d.beam = 2
     assert call(contrast(), n) == -1
     d.beam = 1
-    # ssc_decode_sample_trunc is the call with a NULL contrast: the same refusals and the same workspace
-    assert lib._raw_ssc_decode_sample_trunc(c_, C.byref(p), dd, C.byref(L.SamplerDesc(0, 0, 1.0, 1.0, 3)), None, None, None, a, n0 - 1, None) == -4
+    # NULL opts are the call with a NULL contrast: the same refusals and the same workspace
+    assert lib._raw_ssc_decode_sample_opts(c_, C.byref(p), dd, C.byref(L.SamplerDesc(0, 0, 1.0, 1.0, 3)), None, a, n0 - 1, None) == -4
 
 
 # ---- the runtime --------------------------------------------------------------------------------------------------------------------------

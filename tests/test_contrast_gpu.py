@@ -1,6 +1,6 @@
 """GPU: contrastive decoding for the word samplers (include/ssc.h: ssc_contrast_rows, ssc_contrast).  The row kernel against the
 float64 restatement (tests/contrastref.py) on inputs the restatement calls decidable; the sampled decode with an amateur stream
-(ssc_decode_sample_contrast, DecodeEngine.sample(contrast=)) against the same decode driven step by step over two DecodeEngine.step
+(ssc_sample_opts.contrast, DecodeEngine.sample(contrast=)) against the same decode driven step by step over two DecodeEngine.step
 streams, against the call without it and against the CPU oracle; what the plausibility cut does to the draws; diverse_decode, the
 module and scripts/inference.py."""
 import ctypes as C
@@ -178,13 +178,13 @@ def make_contrast(kind, variant, alpha=ALPHA, beta=BETA, **kw):
 
 
 class ForcedOff(Contrast):
-    """A contrast with both knobs at 0 that DecodeEngine.sample hands to ssc_decode_sample_contrast all the same"""
+    """A contrast with both knobs at 0 that DecodeEngine.sample hands to ssc_decode_sample_opts (as its contrast) all the same"""
     active = True
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_off_path_is_the_call_without_a_contrast(variant):
-    """contrast=None, an inactive Contrast and a descriptor with both knobs at 0 handed to ssc_decode_sample_contrast itself give
+    """contrast=None, an inactive Contrast and a descriptor with both knobs at 0 handed to ssc_decode_sample_opts itself give
     the predictions and the log-probs of the call without the argument, bit for bit - alone, under active logit rules and under a
     truncation."""
     cfg, _, _, dec = medium(variant)

@@ -16,7 +16,7 @@ from ssc_runtime.decode import DecodeEngine, EnsembleDecodeEngine
 from ssc_runtime.engine import ModelDims
 from ssc_runtime.guide import Encoding, LatentGuide, caption_match, match_summary
 from ssc_runtime.inference import diverse_decode
-from test_attention_trace_cpu import model_cfg, score_desc, search_desc, struct_fields
+from test_attention_trace_cpu import model_cfg, sample_opts, score_desc, search_desc, struct_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 END = 1
@@ -158,7 +158,7 @@ def test_lerp():
 
 
 # ---- bindings against the header -------------------------------------------------------------------------------------------------------
-NEW = ("ssc_latent_guide_rows", "ssc_caption_match", "ssc_decode_search_guided", "ssc_decode_sample_guided", "ssc_decode_score_guided")
+NEW = ("ssc_latent_guide_rows", "ssc_caption_match", "ssc_decode_search_guided", "ssc_decode_sample_opts", "ssc_decode_score_guided")
 
 
 def test_bindings_mirror_the_header():
@@ -169,9 +169,14 @@ def test_bindings_mirror_the_header():
     for name in NEW:
         assert name in L.SYMBOLS and hasattr(cdll, name), name
     # the guided calls are the plain ones plus the guide, in front of the workspace
-    for plain in ("ssc_decode_search", "ssc_decode_sample", "ssc_decode_score"):
+    for plain in ("ssc_decode_search", "ssc_decode_score"):
         args, gargs = L.SYMBOLS[plain][1], L.SYMBOLS[plain + "_guided"][1]
         assert gargs[:-3] == args[:-3] + [C.POINTER(L.LatentGuideDesc)] and gargs[-3:] == args[-3:]
+    # the sampled decode takes it as the first field behind the size of its options, which travel in the same place
+    args, oargs = L.SYMBOLS["ssc_decode_sample"][1], L.SYMBOLS["ssc_decode_sample_opts"][1]
+    assert oargs[:-3] == args[:-3] + [C.POINTER(L.SampleOpts)] and oargs[-3:] == args[-3:]
+    assert struct_fields("ssc_sample_opts") == [f for f, _ in L.SampleOpts._fields_] and C.sizeof(L.SampleOpts) == 5 * C.sizeof(C.c_void_p)
+    assert L.SampleOpts._fields_[1] == ("guide", C.POINTER(L.LatentGuideDesc))
     # the descriptors did not grow: the guide travels beside them
     assert struct_fields("ssc_search_desc")[-1] == "attn" and struct_fields("ssc_score_desc")[-1] == "attn"
     assert lib.ssc_version() == 4
@@ -226,18 +231,19 @@ def test_caption_match_refusals():
 
 
 def guided_calls(lib, a):
-    """-> [(name, descriptor, bytes(cfg, desc), call(cfg, desc, guide or None, workspace_bytes))]"""
+    """-> [(name, descriptor, bytes(cfg, desc), call(cfg, desc, guide (a LatentGuideDesc) or None, workspace_bytes))]"""
     smp = L.SamplerDesc(0, 0, 1.0, 1.0, 3)
     p = L.Params()
     ref = C.byref
+    gref = lambda g: ref(g) if g is not None else None
     return [("search", search_desc(a), lib.ssc_decode_search_workspace_bytes,
-             lambda c, d, g, n: lib._raw_ssc_decode_search_guided(c, ref(p), d, g, a, n, None)),
+             lambda c, d, g, n: lib._raw_ssc_decode_search_guided(c, ref(p), d, gref(g), a, n, None)),
             ("search-beam1", search_desc(a, beam=1, per_node=1), lib.ssc_decode_search_workspace_bytes,
-             lambda c, d, g, n: lib._raw_ssc_decode_search_guided(c, ref(p), d, g, a, n, None)),
+             lambda c, d, g, n: lib._raw_ssc_decode_search_guided(c, ref(p), d, gref(g), a, n, None)),
             ("sample", search_desc(a, beam=1, per_node=1), lib.ssc_decode_sample_workspace_bytes,
-             lambda c, d, g, n: lib._raw_ssc_decode_sample_guided(c, ref(p), d, ref(smp), g, a, n, None)),
+             lambda c, d, g, n: lib._raw_ssc_decode_sample_opts(c, ref(p), d, ref(smp), ref(sample_opts(guide=g)), a, n, None)),
             ("score", score_desc(a), lib.ssc_decode_score_workspace_bytes,
-             lambda c, d, g, n: lib._raw_ssc_decode_score_guided(c, ref(p), d, g, a, n, None))]
+             lambda c, d, g, n: lib._raw_ssc_decode_score_guided(c, ref(p), d, gref(g), a, n, None))]
 
 
 def test_guided_decodes_refuse_a_bad_guide_before_any_launch_and_cost_no_workspace():
@@ -253,21 +259,21 @@ def test_guided_decodes_refuse_a_bad_guide_before_any_launch_and_cost_no_workspa
         assert n > 0, name
         assert call(C.byref(cfg), C.byref(d), None, n - 1) == -4, name
         for good in (guide_desc(a), guide_desc(a, var=None), guide_desc(a, len=None), guide_desc(a, ld=7, steps=1), guide_desc(a, steps=100)):
-            assert call(C.byref(cfg), C.byref(d), C.byref(good), n - 1) == -4, name
+            assert call(C.byref(cfg), C.byref(d), good, n - 1) == -4, name
         for kw in BAD_GUIDES:
             g = bad_guide(a, kw)
-            assert call(C.byref(cfg), C.byref(d), C.byref(g), n - 1) == -1, (name, kw)
-            assert call(C.byref(cfg), C.byref(d), C.byref(g), n) == -1, (name, kw)
+            assert call(C.byref(cfg), C.byref(d), g, n - 1) == -1, (name, kw)
+            assert call(C.byref(cfg), C.byref(d), g, n) == -1, (name, kw)
         # SENTIMENT_VAE = 2: out of scope, with every other input of that configuration in place
         sv2 = model_cfg()
         sv2.kld_mode, sv2.S = 2, 1
         d.obj_atts = a
         assert call(C.byref(sv2), C.byref(d), None, 0) == -4, name
-        assert call(C.byref(sv2), C.byref(d), C.byref(guide_desc(a)), 1 << 40) == -1, name
+        assert call(C.byref(sv2), C.byref(d), guide_desc(a), 1 << 40) == -1, name
         d.obj_atts = None
         # what the unguided call refuses stays refused
         d.feats = None
-        assert call(C.byref(cfg), C.byref(d), C.byref(guide_desc(a)), n) == -1, name
+        assert call(C.byref(cfg), C.byref(d), guide_desc(a), n) == -1, name
 
 
 # ---- the runtime's refusals ------------------------------------------------------------------------------------------------------------

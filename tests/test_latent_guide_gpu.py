@@ -189,7 +189,9 @@ def test_caption_match_against_the_dynamic_programme(n, L_):
 
 # ---- the decodes -----------------------------------------------------------------------------------------------------------------------
 class NullGuided:
-    """The library with the three plain one-call decodes re-routed to their guided entry points with a NULL guide."""
+    """The library with the plain search and scoring calls re-routed to their guided entry points with a NULL guide.  The sampled
+    decode takes its guide in ssc_sample_opts and DecodeEngine.sample always goes through ssc_decode_sample_opts, so there the two
+    sides are swapped: the engine's call is the one with a NULL guide in its opts, the re-routed one is the plain entry point."""
 
     def __init__(self, lib):
         self._lib = lib
@@ -198,8 +200,11 @@ class NullGuided:
         lib = self._lib
         if name in ("ssc_decode_search", "ssc_decode_score"):
             return lambda cfg, p, sd, *ws: getattr(lib, name + "_guided")(cfg, p, sd, None, *ws)
-        if name == "ssc_decode_sample":
-            return lambda cfg, p, sd, s, *ws: lib.ssc_decode_sample_guided(cfg, p, sd, s, None, *ws)
+        if name == "ssc_decode_sample_opts":
+            def plain(cfg, p, sd, s, opts, *ws):
+                assert opts._obj.bytes == C.sizeof(L.SampleOpts) and not opts._obj.guide
+                return lib.ssc_decode_sample(cfg, p, sd, s, *ws)
+            return plain
         return getattr(lib, name)
 
 

@@ -20,7 +20,7 @@ from ssc_runtime.decode import DecodeEngine, EnsembleDecodeEngine
 from ssc_runtime.engine import ModelDims
 from ssc_runtime.inference import diverse_decode
 from ssc_runtime.vocab import Vocabulary
-from test_attention_trace_cpu import CFG, header, model_cfg, search_desc, struct_fields
+from test_attention_trace_cpu import CFG, header, model_cfg, sample_opts, search_desc, struct_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 END = 1
@@ -181,9 +181,12 @@ def test_bindings_mirror_the_header():
     assert C.sizeof(L.LogitRules) == 80
     r = L.LogitRules()
     assert not r.bias and not r.bias_row and r.no_repeat_ngram == 0
-    for name in ("ssc_logit_rules_rows", "ssc_decode_sample_rules_workspace_bytes", "ssc_decode_sample_rules"):
+    for name in ("ssc_logit_rules_rows", "ssc_decode_sample_opts_workspace_bytes", "ssc_decode_sample_opts"):
         assert name in L.SYMBOLS and name + "(" in header()
-    assert len(L.SYMBOLS["ssc_logit_rules_rows"][1]) == 10 and len(L.SYMBOLS["ssc_decode_sample_rules"][1]) == 9
+    assert len(L.SYMBOLS["ssc_logit_rules_rows"][1]) == 10
+    # the rules are the third field of the sampled decode's options (the size and four pointers)
+    assert struct_fields("ssc_sample_opts") == [f for f, _ in L.SampleOpts._fields_] and C.sizeof(L.SampleOpts) == 5 * C.sizeof(C.c_void_p)
+    assert L.SampleOpts._fields_[2] == ("rules", C.POINTER(L.LogitRules))
     assert L.load().ssc_version() == 4
     # the pinned structs keep their sizes
     assert (C.sizeof(L.SamplerDesc), C.sizeof(L.RulesDesc)) == (24, 12 + 4 * 8 + 4 * 64)
@@ -247,7 +250,8 @@ def test_rows_refuses_bad_arguments_before_any_launch():
 def sample_rules_call(lib, a):
     smp = L.SamplerDesc(0, 0, 1.0, 1.0, 3)
     p = L.Params()
-    return lambda c, d, r, g, n: lib._raw_ssc_decode_sample_rules(c, C.byref(p), d, C.byref(smp), r, g, a, n, None)
+    return lambda c, d, r, g, n: lib._raw_ssc_decode_sample_opts(c, C.byref(p), d, C.byref(smp), C.byref(sample_opts(guide=g, rules=r)), a,
+                                                                 n, None)
 
 
 def test_decode_refuses_bad_rules_before_any_launch_and_costs_no_workspace():
@@ -259,7 +263,7 @@ def test_decode_refuses_bad_rules_before_any_launch_and_costs_no_workspace():
     a = C.addressof(buf)
     cfg = model_cfg()
     d = search_desc(a, beam=1, per_node=1)
-    n = lib.ssc_decode_sample_rules_workspace_bytes(C.byref(cfg), C.byref(d))
+    n = lib.ssc_decode_sample_opts_workspace_bytes(C.byref(cfg), C.byref(d), C.byref(sample_opts(rules=rules_desc())))
     assert n > 0 and n == lib.ssc_decode_sample_workspace_bytes(C.byref(cfg), C.byref(d))
     call = sample_rules_call(lib, a)
     c, dd = C.byref(cfg), C.byref(d)
@@ -267,33 +271,33 @@ def test_decode_refuses_bad_rules_before_any_launch_and_costs_no_workspace():
     off = L.LogitRules()
     off.repetition_penalty = 1.0
     for good in (off, rules_desc(), rules_desc(a), rules_desc(a, bias_row=None), rules_desc(suppress=(0, 2, 3))):
-        assert call(c, dd, C.byref(good), None, n - 1) == -4
+        assert call(c, dd, good, None, n - 1) == -4
     for kw in BAD_FIELDS:
         for r in (rules_desc(**kw), rules_desc(a, **kw)):
-            assert call(c, dd, C.byref(r), None, n - 1) == -1, kw
-            assert call(c, dd, C.byref(r), None, n) == -1, kw
+            assert call(c, dd, r, None, n - 1) == -1, kw
+            assert call(c, dd, r, None, n) == -1, kw
     for kw in BAD_BIAS:
-        assert call(c, dd, C.byref(rules_desc(a, **kw)), None, n) == -1, kw
-    assert call(c, dd, C.byref(rules_desc(a, bias=a + 2)), None, n) == -2
-    assert call(c, dd, C.byref(rules_desc(a, bias_row=a + 1)), None, n) == -2
+        assert call(c, dd, rules_desc(a, **kw), None, n) == -1, kw
+    assert call(c, dd, rules_desc(a, bias=a + 2), None, n) == -2
+    assert call(c, dd, rules_desc(a, bias_row=a + 1), None, n) == -2
     # active rules: at most SSC_RULES_MAX_LEN steps, and a vocabulary the rules alone cannot empty
     d.max_steps = 65
-    assert call(c, dd, C.byref(rules_desc()), None, 1 << 40) == -1
-    assert call(c, dd, C.byref(off), None, 0) == -4            # inactive rules do not limit the steps
+    assert call(c, dd, rules_desc(), None, 1 << 40) == -1
+    assert call(c, dd, off, None, 0) == -4            # inactive rules do not limit the steps
     d.max_steps = 46
-    assert call(c, dd, C.byref(rules_desc(suppress=(0, 2, 3, 4))), None, 1 << 40) == -1    # V = 50 <= 46 + 4
-    assert call(c, dd, C.byref(rules_desc(suppress=(0, 2, 3))), None, 0) == -4
+    assert call(c, dd, rules_desc(suppress=(0, 2, 3, 4)), None, 1 << 40) == -1    # V = 50 <= 46 + 4
+    assert call(c, dd, rules_desc(suppress=(0, 2, 3)), None, 0) == -4
     d.max_steps = 6
     # what the unruled call refuses stays refused
     d.feats = None
-    assert call(c, dd, C.byref(rules_desc()), None, n) == -1
+    assert call(c, dd, rules_desc(), None, n) == -1
     d.feats = a
     d.beam = 2
-    assert call(c, dd, C.byref(rules_desc()), None, n) == -1
+    assert call(c, dd, rules_desc(), None, n) == -1
     d.beam = 1
     bad_guide = L.LatentGuideDesc(0, a, a, 4, a)
-    assert call(c, dd, C.byref(rules_desc()), C.byref(bad_guide), n) == -1
-    assert call(c, dd, C.byref(rules_desc()), C.byref(L.LatentGuideDesc(3, a, a, 4, a)), n - 1) == -4
+    assert call(c, dd, rules_desc(), bad_guide, n) == -1
+    assert call(c, dd, rules_desc(), L.LatentGuideDesc(3, a, a, 4, a), n - 1) == -4
     assert CFG["V"] == 50
 
 

@@ -1,5 +1,5 @@
 """GPU: the logit rules of the word samplers (include/ssc.h: ssc_logit_rules).  The kernel (ssc_logit_rules_rows) bit for bit against
-the NumPy restatement (tests/logitrulesref.py); the sampled decode under rules (ssc_decode_sample_rules, DecodeEngine.sample) against
+the NumPy restatement (tests/logitrulesref.py); the sampled decode under rules (ssc_sample_opts.rules, DecodeEngine.sample) against
 the same decode driven step by step, against the rules themselves and against the CPU oracle; the module and scripts/inference.py."""
 import ctypes as C
 import json
@@ -208,7 +208,7 @@ NIMG, NS = 3, 2
 
 
 class ForcedRules(sampling.LogitRules):
-    """Inactive rules that DecodeEngine.sample hands to ssc_decode_sample_rules all the same"""
+    """Inactive rules that DecodeEngine.sample hands to ssc_decode_sample_opts (as its rules) all the same"""
     active = True
 
 
@@ -259,7 +259,7 @@ def padded(pred, steps, end):
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_off_path_is_the_plain_sampled_decode(variant):
-    """logit_rules=None and rules with every control off - handed to DecodeEngine.sample, and handed to ssc_decode_sample_rules
+    """logit_rules=None and rules with every control off - handed to DecodeEngine.sample, and handed to ssc_decode_sample_opts
     itself - give the predictions and the log-probs of the call without the argument, bit for bit."""
     cfg, _, _, dec = medium(variant)
     feats, sent_b, eps0, eps = decode_inputs(cfg)

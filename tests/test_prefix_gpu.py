@@ -610,8 +610,10 @@ def test_refusals():
     sd1 = raw_search_desc(dec, ctx, c, good, outs)
     sd1.beam = 1
     smp = sampling.TopKSampler(k=3).desc(1)
-    assert lib._raw_ssc_decode_sample_guided(cfgp, C.byref(p), C.byref(sd1), C.byref(smp), C.byref(gd), *ws) == -1
-    assert lib._raw_ssc_decode_sample_rules(cfgp, C.byref(p), C.byref(sd1), C.byref(smp), None, C.byref(gd), *ws) == -1
+    opts = L.SampleOpts(bytes=C.sizeof(L.SampleOpts), guide=C.pointer(gd))   # (rules, trunc and contrast NULL)
+    assert lib._raw_ssc_decode_sample_opts(cfgp, C.byref(p), C.byref(sd1), C.byref(smp), C.byref(opts), *ws) == -1
+    opts.bytes = L.SampleOpts.rules.offset                                   # (a caller that knows of the guide alone)
+    assert lib._raw_ssc_decode_sample_opts(cfgp, C.byref(p), C.byref(sd1), C.byref(smp), C.byref(opts), *ws) == -1
     params = (C.POINTER(L.Params) * 1)(C.pointer(p))
     imgbufs = (C.c_void_p * 1)(ctx.buf.data_ptr())
     ed = L.EnsembleDesc(1, params, imgbufs, None, 0)

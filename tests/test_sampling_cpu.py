@@ -9,6 +9,7 @@ import samplerref as S
 from ssc_runtime import lib as L
 from ssc_runtime import sampling
 from ssc_runtime.config import Config
+from test_attention_trace_cpu import model_cfg, sample_opts, search_desc
 
 
 def test_sampler_argument_checks():
@@ -74,6 +75,39 @@ def test_sample_calls_reject_bad_arguments_without_a_gpu():
     with pytest.raises(L.SscError, match="SSC_EINVAL"):
         lib.ssc_decode_sample(C.byref(cfg), C.byref(L.Params()), C.byref(sd), C.byref(sampling.MultinomialSampler().desc(1)),
                               C.c_void_p(16), 1 << 30, None)
+
+
+def test_sample_opts_bytes_rule_without_a_gpu():
+    """ssc_sample_opts.bytes (include/ssc.h): a size below sizeof(size_t), no multiple of the pointer size or above the library's own
+    is SSC_EINVAL (-1) whatever else the call holds; a field is read only if it lies wholly inside `bytes` - a bad contrast is refused
+    inside the size and not read behind it, where the call then wants the plain call's workspace (one byte short: SSC_EWORKSPACE, -4).
+    ssc_decode_sample_opts_workspace_bytes is the plain call's without an amateur and grows by the amateur's blocks with one."""
+    lib = L.load()
+    buf = (C.c_float * 64)()
+    a = C.addressof(buf)   # (never read: every check comes before the launch)
+    cfg, d, p, smp = model_cfg(), search_desc(a, beam=1, per_node=1), L.Params(), L.SamplerDesc(0, 0, 1.0, 1.0, 3)
+    c_, dd = C.byref(cfg), C.byref(d)
+    size = lambda o: lib.ssc_decode_sample_opts_workspace_bytes(c_, dd, C.byref(o) if o is not None else None)
+    call = lambda o, n: lib._raw_ssc_decode_sample_opts(c_, C.byref(p), dd, C.byref(smp), C.byref(o) if o is not None else None, a, n, None)
+    full, word = C.sizeof(L.SampleOpts), C.sizeof(C.c_size_t)
+    assert full == 5 * C.sizeof(C.c_void_p) and L.SampleOpts.contrast.offset == full - C.sizeof(C.c_void_p)
+    n0 = lib.ssc_decode_sample_workspace_bytes(c_, dd)
+    assert n0 > 0 and size(None) == size(sample_opts()) == size(sample_opts(nbytes=word)) == n0
+    assert call(None, n0 - 1) == call(sample_opts(), n0 - 1) == call(sample_opts(nbytes=word), n0 - 1) == -4
+    for nbytes in (0, 4, 12, full + 8):
+        assert call(sample_opts(nbytes=nbytes), n0) == -1 and call(sample_opts(nbytes=nbytes), n0 - 1) == -1, nbytes
+        assert size(sample_opts(nbytes=nbytes)) == 0, nbytes
+    bad = L.Contrast()
+    bad.alpha, bad.beta = -1.0, 0.1
+    assert call(sample_opts(contrast=bad), n0) == -1 and call(sample_opts(contrast=bad), n0 - 1) == -1
+    cut = sample_opts(contrast=bad, nbytes=L.SampleOpts.contrast.offset)
+    assert call(cut, n0 - 1) == -4 and size(cut) == n0
+    # an amateur that is stepped: the number the contrast's own workspace function gave before this entry replaced it, read off the
+    # commit before for this shape - V 50, H 8, R 5, B = 2 x 3, 6 steps
+    good = L.Contrast()
+    good.alpha, good.beta = 1.0, 0.1
+    assert n0 == 67115776 and size(sample_opts(contrast=good)) == 134230016
+    assert size(sample_opts(contrast=good, nbytes=L.SampleOpts.contrast.offset)) == n0
 
 
 def test_filter_restatement_matches_the_reference_distributions():

@@ -1,6 +1,7 @@
 """GPU: the word samplers (ssc_sample_rows, ssc_decode_sample, DecodeEngine.sample, diverse_decode(sampler=...), the module's
 eval forward and scripts/inference.py with MODEL.DECODE_SAMPLER) against the reference's own distributions
 (tests/golden/g17_samplers.npz), the NumPy restatement of the draw (tests/samplerref.py), the beam-1 search and the CPU oracle."""
+import ctypes as C
 import json
 import math
 import os
@@ -19,6 +20,7 @@ from ssc_runtime import lib as L
 from ssc_runtime import sampling
 from ssc_runtime.decode import DecodeEngine
 from ssc_runtime.inference import diverse_decode
+from test_attention_trace_gpu import R_, STEPS, VARIANTS, entry_inputs, medium
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -271,6 +273,48 @@ def test_end_handling_and_early_stop():
                            early_stop=False)
     assert full.shape == (nimg * ns, cfg.max_caption_length) and (full == cfg.boundary_index).all()
     assert torch.equal(lp, lp2)
+
+
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_sample_opts_off_paths_are_the_plain_call(variant):
+    """The medium model, 3 images x 2 samples, the three samplers: ssc_decode_sample, ssc_decode_sample_opts with opts NULL, with
+    four NULL fields, with bytes = sizeof(size_t), and with all three off descriptors present (rules with every control off, a kind-0
+    truncation, a contrast with alpha = beta = 0) give the same predictions and the same log-probs, bit for bit.  So does an active
+    min-p truncation behind `bytes` - a field that is not wholly inside the caller's size is not read -, which changes the log-probs
+    once `bytes` covers it."""
+    cfg, _, _, dec = medium(variant)
+    nimg, ns = 3, 2
+    feats, senti, eps0, eps = entry_inputs(cfg, nimg, ns, R_, 17, STEPS)
+    sent_b = senti.view(nimg, 1).expand(nimg, ns).reshape(-1).cuda() if senti is not None else None
+    ctx = dec.prepare(feats.cuda())
+    lib, cfgp = dec.lib, C.byref(dec._cfg)
+    Opts, full = L.SampleOpts, C.sizeof(L.SampleOpts)
+    off_rules, _keep = sampling.LogitRules().desc(ns)
+    off_trunc, off_contrast = sampling.Truncation().desc(), L.Contrast()
+    minp = sampling.MinPTruncation(0.3).desc()
+    bits = lambda x: x.view(torch.int32)
+
+    def run(sdesc, opts, plain=False):
+        o = C.byref(opts) if opts is not None else None
+        if plain:
+            nbytes, call = lib.ssc_decode_sample_workspace_bytes, lambda p, sd, ws: lib.ssc_decode_sample(cfgp, C.byref(p), C.byref(sd), C.byref(sdesc), *ws)
+        else:
+            nbytes = lambda c, sd: lib.ssc_decode_sample_opts_workspace_bytes(c, sd, o)
+            call = lambda p, sd, ws: lib.ssc_decode_sample_opts(cfgp, C.byref(p), C.byref(sd), C.byref(sdesc), o, *ws)
+        return dec._one_call(ctx, sent_b, ns, 1, 1, 1, STEPS, cfg.boundary_index, eps0.cuda(), eps.cuda(), True, True, (nimg * ns,), nbytes, call)
+
+    for smp in (sampling.MultinomialSampler(1.0), sampling.TopKSampler(k=3), sampling.TopPSampler(p=0.9, temperature=1.2)):
+        sdesc = smp.desc(13)
+        pred0, lp0 = run(sdesc, None, plain=True)
+        cases = {"opts NULL": None, "four NULL fields": Opts(bytes=full), "bytes = sizeof(size_t)": Opts(bytes=C.sizeof(C.c_size_t)),
+                 "three off descriptors": Opts(bytes=full, rules=C.pointer(off_rules), trunc=C.pointer(off_trunc),
+                                               contrast=C.pointer(off_contrast)),
+                 "min-p behind bytes": Opts(bytes=Opts.trunc.offset, trunc=C.pointer(minp))}
+        for name, opts in cases.items():
+            pred, lp = run(sdesc, opts)
+            assert torch.equal(pred, pred0) and torch.equal(bits(lp), bits(lp0)), (variant, smp, name)
+        _, lp_cut = run(sdesc, Opts(bytes=full, trunc=C.pointer(minp)))
+        assert not torch.equal(bits(lp_cut), bits(lp0)), (variant, smp)   # (the same descriptor, once it is read)
 
 
 MODULE_SCRIPT = r"""

@@ -18,7 +18,7 @@ from ssc_runtime.decode import DecodeEngine, EnsembleDecodeEngine
 from ssc_runtime.engine import ModelDims
 from ssc_runtime.inference import diverse_decode
 from ssc_runtime.vocab import Vocabulary
-from test_attention_trace_cpu import CFG, header, model_cfg, search_desc, struct_fields
+from test_attention_trace_cpu import CFG, header, model_cfg, sample_opts, search_desc, struct_fields
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 END = 1
@@ -262,9 +262,12 @@ def test_a_model_reads_the_keys_with_a_word_sampler_only():
 def test_bindings_mirror_the_header():
     assert struct_fields("ssc_truncation") == [f for f, _ in L.Truncation._fields_] == ["kind", "value", "entropy", "kept"]
     assert C.sizeof(L.Truncation) == 24
-    for name in ("ssc_truncate_rows", "ssc_decode_sample_trunc_workspace_bytes", "ssc_decode_sample_trunc"):
+    for name in ("ssc_truncate_rows", "ssc_decode_sample_opts_workspace_bytes", "ssc_decode_sample_opts"):
         assert name in L.SYMBOLS and name + "(" in header()
-    assert len(L.SYMBOLS["ssc_truncate_rows"][1]) == 9 and len(L.SYMBOLS["ssc_decode_sample_trunc"][1]) == 10
+    assert len(L.SYMBOLS["ssc_truncate_rows"][1]) == 9
+    # the truncation is the fourth field of the sampled decode's options (the size and four pointers)
+    assert struct_fields("ssc_sample_opts") == [f for f, _ in L.SampleOpts._fields_] and C.sizeof(L.SampleOpts) == 5 * C.sizeof(C.c_void_p)
+    assert L.SampleOpts._fields_[3] == ("trunc", C.POINTER(L.Truncation))
     assert L.SYMBOLS["ssc_truncate_rows"][1][5] is C.c_float
     assert L.load().ssc_version() == 4
     # the pinned structs keep their sizes
@@ -316,15 +319,14 @@ def test_decode_refuses_a_bad_truncation_before_any_launch_and_costs_no_workspac
     a = C.addressof(buf)
     cfg = model_cfg()
     d = search_desc(a, beam=1, per_node=1)
-    n = lib.ssc_decode_sample_trunc_workspace_bytes(C.byref(cfg), C.byref(d))
+    n = lib.ssc_decode_sample_opts_workspace_bytes(C.byref(cfg), C.byref(d), C.byref(sample_opts(trunc=trunc())))
     assert n > 0 and n == lib.ssc_decode_sample_workspace_bytes(C.byref(cfg), C.byref(d))
     p = L.Params()
     c, dd = C.byref(cfg), C.byref(d)
 
     def call(t, nbytes, smp=None, rules=None, guide=None):
         smp = smp or L.SamplerDesc(0, 0, 1.0, 1.0, 3)
-        return lib._raw_ssc_decode_sample_trunc(c, C.byref(p), dd, C.byref(smp), rules, C.byref(t) if t is not None else None, guide, a,
-                                                nbytes, None)
+        return lib._raw_ssc_decode_sample_opts(c, C.byref(p), dd, C.byref(smp), C.byref(sample_opts(guide, rules, t)), a, nbytes, None)
 
     assert call(None, n - 1) == -4 and call(trunc(0, 0.0), n - 1) == -4
     for k, v in GOOD_VALUES:
@@ -332,17 +334,17 @@ def test_decode_refuses_a_bad_truncation_before_any_launch_and_costs_no_workspac
     for k, v in BAD_VALUES:
         assert call(trunc(k, v), n - 1) == -1 and call(trunc(k, v), n) == -1, (k, v)
     assert call(trunc(entropy=a + 2), n) == -2 and call(trunc(kept=a + 1), n) == -2
-    # everything ssc_decode_sample_rules refuses stays refused: a bad sampler, bad rules, a bad guide, a bad descriptor
+    # everything the call refuses without a truncation stays refused: a bad sampler, bad rules, a bad guide, a bad descriptor
     assert call(trunc(), n, smp=L.SamplerDesc(0, 0, 1.0, 0.0, 3)) == -1       # temperature 0
     assert call(trunc(), n, smp=L.SamplerDesc(3, 0, 1.0, 1.0, 3)) == -1       # sampler kind 3 does not exist
     bad_rules = L.LogitRules()
     bad_rules.repetition_penalty = 0.0
-    assert call(trunc(), n, rules=C.byref(bad_rules)) == -1
+    assert call(trunc(), n, rules=bad_rules) == -1
     good_rules = L.LogitRules()
     good_rules.no_repeat_ngram, good_rules.repetition_penalty = 2, 1.3
-    assert call(trunc(), n - 1, rules=C.byref(good_rules)) == -4
-    assert call(trunc(), n, guide=C.byref(L.LatentGuideDesc(0, a, a, 4, a))) == -1
-    assert call(trunc(), n - 1, guide=C.byref(L.LatentGuideDesc(3, a, a, 4, a))) == -4
+    assert call(trunc(), n - 1, rules=good_rules) == -4
+    assert call(trunc(), n, guide=L.LatentGuideDesc(0, a, a, 4, a)) == -1
+    assert call(trunc(), n - 1, guide=L.LatentGuideDesc(3, a, a, 4, a)) == -4
     d.feats = None
     assert call(trunc(), n) == -1
     d.feats = a

@@ -1,6 +1,6 @@
 """GPU: the truncation of the word samplers (include/ssc.h: ssc_truncation).  The kernel (ssc_truncate_rows) against the float64
 restatement (tests/truncationref.py) on inputs the restatement calls decidable; the distribution the draw is then made from; the
-sampled decode under a truncation (ssc_decode_sample_trunc, DecodeEngine.sample) against the call without it, against the same
+sampled decode under a truncation (ssc_sample_opts.trunc, DecodeEngine.sample) against the call without it, against the same
 decode driven step by step and against the CPU oracle; diverse_decode, the module and scripts/inference.py."""
 import ctypes as C
 import functools
@@ -212,15 +212,15 @@ NIMG, NS = 3, 2
 
 
 class ForcedOff(sampling.Truncation):
-    """A kind-0 truncation that DecodeEngine.sample hands to ssc_decode_sample_trunc all the same"""
+    """A kind-0 truncation that DecodeEngine.sample hands to ssc_decode_sample_opts (as its trunc) all the same"""
     active = True
 
 
 @pytest.mark.parametrize("variant", list(VARIANTS))
 def test_off_path_is_the_call_without_a_truncation(variant):
-    """truncation=None and kind 0 - handed to DecodeEngine.sample, and handed to ssc_decode_sample_trunc itself - give the predictions
-    and the log-probs of the call without the argument, bit for bit; so does ssc_decode_sample_trunc under active logit rules
-    against ssc_decode_sample_rules."""
+    """truncation=None and kind 0 - handed to DecodeEngine.sample, and handed to ssc_decode_sample_opts itself - give the predictions
+    and the log-probs of the call without the argument, bit for bit; so does the kind-0 descriptor under active logit rules against
+    the call with those rules alone."""
     cfg, _, _, dec = medium(variant)
     feats, sent_b, eps0, eps = decode_inputs(cfg)
     ctx = dec.prepare(feats)
