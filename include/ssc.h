@@ -1556,7 +1556,9 @@ typedef struct {
 
 /* ------------------------------------------------------------------------------------------------
  * The options of one sampled decode: the latent guide, the logit rules, the truncation and the contrast (their blocks above), beside
- * the search and sampler descriptors.  The next option is a field appended here - no entry of its own, no move of ssc_version().
+ * the search and sampler descriptors.  While ssc_version() is 4 the five pointers of this struct are fixed (its size is part of what
+ * version 4 promises), so a later option travels BESIDE it, as ssc_unlikelihood travels beside ssc_train_opts: ssc_mirostat and
+ * ssc_decode_sample_mirostat, below.  At the next move of ssc_version() such descriptors become fields appended here.
  * Per step, for a live row, in this order: the expert's decode step (its z block from slab t of the guide); the amateur's decode
  * step; the contrast; the logit rules; the truncation; the draw.
  * The `bytes` rule: `bytes` is sizeof(ssc_sample_opts) as the CALLER was built.  A field is read only if it lies wholly inside the
@@ -1578,6 +1580,65 @@ typedef struct {
 size_t ssc_decode_sample_opts_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_sample_opts* opts);
 int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
                            const ssc_sample_opts* opts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Mirostat for the word samplers (Basu et al., ICLR 2021, algorithm 2, "Mirostat 2.0"): the surprise of the generated words is held
+ * at a target tau by feedback.  Every word whose surprise exceeds a running threshold mu is cut; after each draw mu moves by the
+ * error between the drawn word's surprise and tau.  The one edit of the sampled decode with STATE: mu is a value per row carried
+ * from step to step.  All quantities are in nats, as `entropy` and `divergence` are.  Like the truncation, the cut edits the RAW
+ * logits of a row in place in front of the unchanged draw; ssc_sampler_desc and the samplers are untouched; ssc_version() stays 4.
+ * With T the sampler's temperature and the row x[0 .. V) as it arrives (behind the contrast, the logit rules and the truncation),
+ * over its finite entries, formed as ssc_truncate_rows forms them: mx = max x, a_v = (x_v - mx) / T, logz = log sum_v exp(a_v),
+ * first = the lowest index with x_v == mx.
+ *   The CUT, given the row's mu (ssc_mirostat_rows): thr = logz - mu (one fp32 subtraction); v is kept iff a_v >= thr or v == first -
+ *   surprise -log q_v <= mu, or the top word.  A dropped entry becomes -inf, a kept one keeps its bits; an entry that arrives as
+ *   -inf stays dropped and weighs nothing.  Per row: kept (the entries left finite, or NULL) and norm[0][r] = mx, norm[1][r] = logz
+ *   (`norm` is 2 * rows floats).
+ *   The UPDATE, after the draw of token w (ssc_mirostat_update): s = logz - (x_w - mx) / T, e = s - tau, mu' = mu - eta * e; each
+ *   one fp32 operation, never an fma.  s is the surprise under the tempered distribution BEFORE Mirostat's own cut - the choice of
+ *   the authors' reference implementation, not the surprise under the renormalised, cut distribution.  x_w is read from the edited
+ *   row: a drawn word is a kept word and still holds its bits.  Per row: mu' and surprise = s (or NULL).  mu_out may be mu_in.
+ * Rows that pass through: a row whose last token is END (last_pred[r] == end_index) is neither read nor written; so is a row
+ * without a finite entry, and at the update a row with x_w == -inf or with pred[r] outside [0, V) (the host cannot see it: the
+ * device checks it).  For these kept = 0, surprise = 0, mu' = mu, and norm is left alone.  Columns V .. ld - 1 are never touched.
+ * NaN and +inf are the caller's error (the calls still end and stay inside the rows): every trip count depends on V alone, every
+ * index is a loop index or a checked token id.  One workgroup per row for the cut, the row staged in LDS for V <= 32768 and walked
+ * in global memory above; 16-byte accesses where the row is 16-byte aligned with V % 4 == 0, scalar ones otherwise - the result
+ * does not depend on which; one thread per row for the update.  Reductions in a fixed order, no atomics: two calls on equal inputs
+ * are bit-identical.
+ * SSC_EINVAL before any launch: a NULL logits, mu_in, norm (and, at the update, pred or mu_out); rows < 0, V < 1, ld < V;
+ * temperature <= 0 or not finite; end_index outside [0, V) with a last_pred; at the update tau < 0 or eta < 0 or either not finite.
+ * SSC_EALIGN: any block that is no multiple of 4.  rows == 0: SSC_OK with no launch.
+ * ---------------------------------------------------------------------------------------------- */
+int ssc_mirostat_rows(float* logits, int ld, int rows, int V, float temperature, const float* mu_in, const int64_t* last_pred,
+                      int end_index, int* kept, float* norm, void* stream);
+int ssc_mirostat_update(const float* logits, int ld, int rows, int V, float temperature, float tau, float eta, const float* norm,
+                        const int64_t* pred, const int64_t* last_pred, int end_index, const float* mu_in, float* mu_out,
+                        float* surprise, void* stream);
+/* Mirostat in the sampled decode: the descriptor travels BESIDE ssc_sample_opts (see there). */
+typedef struct {
+  float tau;         /* the surprise target in nats; 0: off (no other field is read) */
+  float eta;         /* the learning rate of mu, >= 0; 0: a fixed surprise cut at mu0 */
+  float mu0;         /* every row's mu at the first step (the paper: 2 tau) */
+  float* mu;         /* (max_steps + 1, B), required: the call fills slab 0 with mu0, step t cuts with slab t and writes slab t + 1 */
+  float* surprise;   /* (max_steps, B) or NULL: step t writes slab t with ssc_mirostat_update's surprise */
+  int* kept;         /* (max_steps, B) or NULL: step t writes slab t with ssc_mirostat_rows' kept */
+} ssc_mirostat;
+/* ssc_decode_sample_opts_workspace_bytes / ssc_decode_sample_opts with one argument more.  With m NULL or m->tau == 0 they ARE those
+ * calls: the same launches, the same bits, the same workspace size.  Otherwise, per step and for a live row, in this order: the
+ * decode steps, the contrast, the logit rules, the truncation, the Mirostat cut (ssc_mirostat_rows with slab t of mu), the draw,
+ * the Mirostat update (ssc_mirostat_update, slab t -> slab t + 1); last_pred is the previous step's words, the temperature is
+ * s->temperature.  Slabs of steps never queued (early_stop) are not written.  The workspace grows by the cut's `norm` alone: 2 B
+ * floats rounded up to 256 bytes, appended behind everything else - no existing offset moves.  Under d->start (a prompt) the control
+ * starts at mu0 at the continuation's first step.  skip_dead, early_stop, the pacer, ctl, the attention trace, the guide, the rules,
+ * the truncation and the contrast (amateur included) are untouched; d->log_probs sums the log-probs under the edited rows.
+ * SSC_EINVAL before any launch: what ssc_decode_sample_opts refuses; tau < 0, NaN or infinite; with tau > 0: eta < 0 or not finite,
+ * mu0 not finite, a NULL mu.  SSC_EALIGN: mu, surprise or kept no multiple of 4. */
+size_t ssc_decode_sample_mirostat_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_sample_opts* opts,
+                                                  const ssc_mirostat* m);
+int ssc_decode_sample_mirostat(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                               const ssc_sample_opts* opts, const ssc_mirostat* m, void* workspace, size_t workspace_bytes,
+                               void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Prompted decoding: start the one-call decodes from a forced prefix ("a happy ...").  ssc_decode_prime teacher-forces the prefix

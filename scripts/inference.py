@@ -113,6 +113,14 @@ parser.add_argument("--truncation", default="",
                          "typical:0.9 (default: MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE) - every step's distribution is cut "
                          "between the logit rules and the draw.  Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without "
                          "SAMPLED_BEAM_SEARCH")
+parser.add_argument("--mirostat", default="",
+                    help="Mirostat 2.0 for word sampling: TAU[:ETA], the surprise target in bits and the learning rate, e.g. --mirostat "
+                         "3:0.1 (default: MODEL.SAMPLER_MIROSTAT_TAU / SAMPLER_MIROSTAT_ETA; TAU 0 = off) - words more surprising than a "
+                         "running threshold are cut behind the truncation, and the threshold follows the drawn words' surprise.  Needs "
+                         "MODEL.DECODE_SAMPLER multinomial / top-k / top-p without SAMPLED_BEAM_SEARCH")
+parser.add_argument("--mirostat-output", default="",
+                    help="with an active Mirostat: write per returned caption the threshold mu and the drawn word's surprise at every "
+                         "word, in bits (JSON: image_id, caption, mu, surprise)")
 parser.add_argument("--contrast", default="",
                     help="contrastive decoding for word sampling: ALPHA[:BETA], e.g. --contrast 1:0.1 (default: MODEL.CONTRAST_ALPHA / "
                          "CONTRAST_BETA; ALPHA 0 = off) - an amateur stream is decoded in lock-step and every step's logits become "
@@ -218,6 +226,41 @@ def check_truncation_args(_A, model_cfg=None):
             raise SystemExit("--truncation needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
                              f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
     return tr
+
+
+def check_mirostat_args(_A, model_cfg=None):
+    """--mirostat TAU[:ETA] / --mirostat-output, checked before anything is loaded -> its sampling.Mirostat, or None without the flag
+    (or with TAU 0); with model_cfg (the MODEL node) the keys stand in for a missing flag and it is checked that the run samples
+    words."""
+    m = None
+    if _A.mirostat:
+        t, _, e = _A.mirostat.partition(":")
+        try:
+            tau, eta = float(t), (float(e) if e.strip() else None)
+        except ValueError:
+            raise SystemExit(f"--mirostat: TAU[:ETA] wanted, two numbers, got {_A.mirostat!r}")
+        if eta is None:
+            eta = float(model_cfg.SAMPLER_MIROSTAT_ETA) if model_cfg is not None else 0.1
+        try:
+            m = sampling.Mirostat(tau, eta)
+        except ValueError as err:
+            raise SystemExit(f"--mirostat: {err}")
+    elif model_cfg is not None and float(model_cfg.SAMPLER_MIROSTAT_TAU) != 0:
+        m = sampling.Mirostat(float(model_cfg.SAMPLER_MIROSTAT_TAU), float(model_cfg.SAMPLER_MIROSTAT_ETA))
+    if m is not None and not m.active:
+        m = None
+    if m is None:
+        if _A.mirostat_output and (model_cfg is not None or _A.mirostat):
+            raise SystemExit("--mirostat-output needs an active Mirostat: --mirostat TAU[:ETA] or MODEL.SAMPLER_MIROSTAT_TAU")
+        return None
+    if _A.ensemble_checkpoints:
+        raise SystemExit("--mirostat is not available with --ensemble-checkpoints: an ensemble runs the beam search only")
+    if model_cfg is not None:
+        kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+        if kind not in sampling.KINDS or model_cfg.SAMPLED_BEAM_SEARCH or model_cfg.STOCHASTIC_BEAM_SEARCH:
+            raise SystemExit("--mirostat needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                             f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
+    return m
 
 
 def check_contrast_args(_A, model_cfg=None):
@@ -340,10 +383,12 @@ def main():
     check_word_bias_args(_A)
     check_truncation_args(_A)
     check_contrast_args(_A)
+    check_mirostat_args(_A)
     _C = Config(_A.config, _A.config_override)
     check_word_bias_args(_A, _C.MODEL)
     truncation = check_truncation_args(_A, _C.MODEL)
     contrast_args = check_contrast_args(_A, _C.MODEL)
+    mirostat = check_mirostat_args(_A, _C.MODEL)   # --mirostat, else MODEL.SAMPLER_MIROSTAT_TAU / SAMPLER_MIROSTAT_ETA
     prompt = _A.prefix or ("" if prompts is not None else str(_C.MODEL.DECODE_PREFIX).strip())
     if (prompt or prompts is not None) and not _A.prefix and not _A.prefix_json:   # (MODEL.DECODE_PREFIX: the flags' refusals apply)
         _A.prefix = prompt
@@ -429,6 +474,8 @@ def main():
         contrast = (contrast_from_name(c_alpha, c_beta, c_kind, float(_C.MODEL.CONTRAST_NOISE), engine=amateur_engine)
                     if c_kind is not None else Contrast(c_alpha, c_beta, engine=amateur_engine))
     divergences = []   # --contrast-output: one record per returned caption
+    miro_traces = []   # --mirostat-output: one record per returned caption
+    model.mirostat(None)   # (the run's own decode below is handed the Mirostat itself)
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
     if sampler is not None and (_A.constraints_json or _A.boxes_json):
@@ -557,8 +604,12 @@ def main():
                                      obj_means=obj, sampler=sampler, sampled_beam=sampled_beam, rules=rules, attention=attn_mode,
                                      guide=guide, **({"logit_rules": logit_rules} if logit_rules is not None else {}),
                                      **({"truncation": truncation} if truncation is not None else {}),
-                                     **({"contrast": contrast, "contrast_stats": True} if contrast is not None else {}), **pkw)
+                                     **({"contrast": contrast, "contrast_stats": True} if contrast is not None else {}),
+                                     **({"mirostat": mirostat, "mirostat_stats": bool(_A.mirostat_output)} if mirostat is not None else {}),
+                                     **pkw)
                 pred = out[0]
+                if mirostat is not None and _A.mirostat_output:
+                    out, (m_mu, m_sur) = out[:-1], (out[-1][0].cpu().numpy(), out[-1][1].cpu().numpy())   # (images, n_z, steps)
                 if contrast is not None:
                     out, c_div = out[:-1], out[-1][1].cpu().numpy()   # (images, n_z, steps of the continuation)
             trace = out[-1] if attn_mode else None
@@ -574,6 +625,11 @@ def main():
                 image_id = int(data.image_id[lo + i])
                 for k in range(ids.shape[1]):
                     predictions.append({"image_id": image_id, "caption": " ".join(words[i, k, : n_keep[i, k]])})
+                    if mirostat is not None and _A.mirostat_output and diverse is None:   # the caption's words and its END, less a prefix's
+                        n_m = max(1, min(int(n_keep[i, k]) + 1 - (ids.shape[-1] - m_mu.shape[-1]), m_mu.shape[-1]))
+                        miro_traces.append({"image_id": image_id, "caption": predictions[-1]["caption"],
+                                            "mu": [float(v) for v in m_mu[i, k, :n_m]],
+                                            "surprise": [float(v) for v in m_sur[i, k, :n_m]]})
                     if contrast is not None and _A.contrast_output:   # the caption's words and its END, less a prefix's words
                         n_div = max(1, min(int(n_keep[i, k]) + 1 - (ids.shape[-1] - c_div.shape[-1]), c_div.shape[-1]))
                         divergences.append({"image_id": image_id, "caption": predictions[-1]["caption"],
@@ -632,6 +688,8 @@ def main():
     json.dump(predictions, open(_A.output_path, "w", encoding="utf-8"))
     if contrast is not None and _A.contrast_output:
         json.dump(divergences, open(_A.contrast_output, "w", encoding="utf-8"))
+    if mirostat is not None and _A.mirostat_output:
+        json.dump(miro_traces, open(_A.mirostat_output, "w", encoding="utf-8"))
     print(f"wrote {len(predictions)} captions to {_A.output_path}")
     if _A.attention_output:
         torch.save(traces, _A.attention_output)

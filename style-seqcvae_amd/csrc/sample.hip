@@ -12,7 +12,9 @@
 // counter-based Philox4x32-10 noise: bit-reproducible for a given seed, no float atomics, no order-dependent reduction.
 // The draw of one row (sample_draw_row) lives in sample_draw.h: the scheduled-sampling mix kernel of the train step calls the same code.
 // The edits of the raw logits in front of the draw - the logit rules (logit_rules.hip) and the truncation (truncation.hip) - are launches
-// of their own between a step's decode step and its draw (ssc_decode_sample_opts); the draw itself does not know of them.
+// of their own between a step's decode step and its draw (ssc_decode_sample_opts); the draw itself does not know of them.  Mirostat
+// (mirostat.hip) adds a cut in front of and an update behind the draw, with a value per row carried between the steps
+// (ssc_decode_sample_mirostat).
 // ssc_decode_sample's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
 
@@ -224,6 +226,16 @@ extern "C" size_t ssc_decode_sample_opts_workspace_bytes(const ssc_model_cfg* cf
   return contrast_layout(cfg, d, l, &am);
 }
 
+// Mirostat's (include/ssc.h, ssc_mirostat) share of the workspace: the cut's norm, 2 B floats, behind everything else
+inline size_t mirostat_norm_bytes(const ssc_search_desc* d) { return ((size_t)d->nimg * d->n_samples * 2 * 4 + 255) & ~(size_t)255; }
+
+extern "C" size_t ssc_decode_sample_mirostat_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
+                                                             const ssc_sample_opts* opts, const ssc_mirostat* m) {
+  const size_t base = ssc_decode_sample_opts_workspace_bytes(cfg, d, opts);
+  if (base == 0 || !m || m->tau == 0.f) return base;
+  return ((base + 255) & ~(size_t)255) + mirostat_norm_bytes(d);
+}
+
 extern "C" size_t ssc_decode_sample_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d) {
   return ssc_decode_sample_opts_workspace_bytes(cfg, d, nullptr);
 }
@@ -235,10 +247,11 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
 
 // The sampled decode under its options (include/ssc.h, ssc_sample_opts).  Per step: the expert's decode step (its z block from slab t
 // of the guide), the amateur's decode step, the contrast, the logit rules, the truncation, the draw; step t's statistics go to slab t
-// of contrast->kept / ->divergence and trunc->entropy / ->kept.
-extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
-                                      const ssc_sampler_desc* s, const ssc_sample_opts* opts, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+// of contrast->kept / ->divergence and trunc->entropy / ->kept.  Under an active Mirostat (m, may be null) the cut follows the
+// truncation with slab t of m->mu and the update follows the draw, slab t -> slab t + 1.
+namespace {
+int sample_decode(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                  const ssc_sample_opts* opts, const ssc_mirostat* m, void* workspace, size_t workspace_bytes, void* stream) {
   ssc_sample_opts o;
   if (!sample_opts_read(opts, &o)) return SSC_EINVAL;
   const ssc_latent_guide* guide = o.guide;
@@ -270,9 +283,16 @@ extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params
   }
   bool cut = false;
   if (trunc) SSC_TRY(ssc_truncation_check(trunc, s->temperature, &cut));
+  bool miro = false;
+  SSC_TRY(ssc_mirostat_check(m, s->temperature, &miro));
   const SampleLayout l = sample_layout(cfg, d);
   AmateurLayout am{};
-  const size_t total = amateur ? contrast_layout(cfg, d, l, &am) : l.total;
+  size_t total = amateur ? contrast_layout(cfg, d, l, &am) : l.total;
+  size_t norm_at = 0;
+  if (miro) {   // (the cut's norm behind everything else: no existing offset moves)
+    norm_at = (total + 255) & ~(size_t)255;
+    total = norm_at + mirostat_norm_bytes(d);
+  }
   if (workspace_bytes < total) return SSC_EWORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   char* W = (char*)workspace;
@@ -292,6 +312,8 @@ extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params
   if (hipMemsetAsync(lp, 0, (size_t)B * 4, st) != hipSuccess) return SSC_EHIP;
   SSC_TRY(ssc_decode_start_states(d->start, states, W, 1, B, st));
   if (amateur) SSC_TRY(ssc_decode_start_states(contrast->start, am.states, W, 1, B, st));
+  float* norm = miro ? (float*)(W + norm_at) : nullptr;
+  if (miro) SSC_TRY(ssc_mirostat_fill(m->mu, B, m->mu0, st));   // (slab 0; under d->start too: the control starts at the continuation)
 
   // the steps take the form the beam-1 search gives them (ssc_decode_search with S = beam = 1): same tables, same parent list
   const bool want_table = ssc_att_table_wanted(d->R, B, d->n_samples);
@@ -338,7 +360,13 @@ extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params
       SSC_TRY(ssc_truncation_launch(logits, V, B, V, trunc, s->temperature, trunc->entropy ? trunc->entropy + (size_t)t * B : nullptr,
                                     trunc->kept ? trunc->kept + (size_t)t * B : nullptr, last, d->end_index, st));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
-    return sample_launch(a, B, st);
+    if (!miro) return sample_launch(a, B, st);
+    float* mu = m->mu + (size_t)t * B;
+    SSC_TRY(ssc_mirostat_rows_launch(logits, V, B, V, s->temperature, mu, last, d->end_index, m->kept ? m->kept + (size_t)t * B : nullptr,
+                                     norm, st));
+    SSC_TRY(sample_launch(a, B, st));
+    return ssc_mirostat_update_launch(logits, V, B, V, s->temperature, m->tau, m->eta, norm, a.pred_out, last, d->end_index, mu, mu + B,
+                                      m->surprise ? m->surprise + (size_t)t * B : nullptr, st);
   };
   SSC_TRY(edit_and_draw(0, nullptr));
   const SscStepPacer pacer(d->early_stop, d->host_flag_host, st);   // (the sampler's last workgroup of a step notes it for the host)
@@ -366,4 +394,17 @@ extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params
     SSC_TRY(ssc_attn_anc(preds, nullptr, d->early_stop ? ctl : nullptr, nullptr, d->max_steps, B, 1, d->end_index, d->attn->anc, st));
   if (hipMemcpyAsync(d->log_probs, lp, (size_t)B * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return SSC_EHIP;
   return SSC_OK;
+}
+}  // namespace
+
+extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                      const ssc_sampler_desc* s, const ssc_sample_opts* opts, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+  return sample_decode(cfg, p, d, s, opts, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ssc_decode_sample_mirostat(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                          const ssc_sampler_desc* s, const ssc_sample_opts* opts, const ssc_mirostat* m, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  return sample_decode(cfg, p, d, s, opts, m, workspace, workspace_bytes, stream);
 }

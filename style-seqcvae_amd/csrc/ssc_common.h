@@ -230,6 +230,16 @@ int ssc_logit_rules_launch(float* logits, int ld, int rows, int V, const ssc_log
 int ssc_truncation_check(const ssc_truncation* tr, float temperature, bool* active);
 int ssc_truncation_launch(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature, float* entropy, int* kept,
                           const int64_t* last_pred, int end_index, hipStream_t st);
+// Mirostat for the word samplers (mirostat.hip, include/ssc.h: ssc_mirostat).  ssc_mirostat_check: the refusals that depend on the
+// fields and the temperature alone (SSC_OK with *active = m && tau != 0); ssc_mirostat_fill: n floats of mu set to mu0; the two
+// launches: the cut in front of and the update behind one step's draw - what ssc_decode_sample_mirostat issues per step.
+int ssc_mirostat_check(const ssc_mirostat* m, float temperature, bool* active);
+int ssc_mirostat_fill(float* mu, int n, float mu0, hipStream_t st);
+int ssc_mirostat_rows_launch(float* logits, int ld, int rows, int V, float temperature, const float* mu, const int64_t* last_pred,
+                             int end_index, int* kept, float* norm, hipStream_t st);
+int ssc_mirostat_update_launch(const float* logits, int ld, int rows, int V, float temperature, float tau, float eta, const float* norm,
+                               const int64_t* pred, const int64_t* last_pred, int end_index, const float* mu_in, float* mu_out,
+                               float* surprise, hipStream_t st);
 // Contrastive decoding for the word samplers (contrast.hip, include/ssc.h: ssc_contrast_rows, ssc_contrast).  ssc_contrast_check: the
 // refusals that depend on the knobs and the statistics pointers alone (SSC_OK with *active = alpha != 0 || beta != 0);
 // ssc_contrast_launch: the edit of one step from checked knobs - what ssc_decode_sample_opts issues per step for its `contrast`.

@@ -110,6 +110,11 @@ def _defaults() -> dict:
             # min(VALUE, sqrt(VALUE) exp(-entropy)) / VALUE, default 3e-4).  SAMPLER_TRUNCATION_VALUE 0 = the kind's default.  Needs
             # DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
             "SAMPLER_TRUNCATION": "none", "SAMPLER_TRUNCATION_VALUE": 0.0,
+            # Mirostat 2.0 for the word samplers (ssc_runtime/sampling.py Mirostat; ssc_mirostat): the surprise of the drawn words
+            # is held at SAMPLER_MIROSTAT_TAU bits (0, the default: off) - words more surprising than a running threshold mu are
+            # cut behind the truncation, and after each draw mu moves by SAMPLER_MIROSTAT_ETA times the error; mu starts at
+            # 2 TAU.  Needs DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
+            "SAMPLER_MIROSTAT_TAU": 0.0, "SAMPLER_MIROSTAT_ETA": 0.1,
             # contrastive decoding of the word samplers (ssc_runtime/contrast.py Contrast; ssc_contrast): an amateur stream is decoded
             # in lock-step with the normal one and every step's logits become lp + CONTRAST_ALPHA (lp - lp_amateur) on the words
             # whose probability is at least CONTRAST_BETA times the top word's.  CONTRAST_ALPHA 0 (default): off.  CONTRAST_AMATEUR:
@@ -278,6 +283,10 @@ class Config(object):
         if m.SAMPLER_TRUNCATION != "none" and not (0 <= tv and hi_ok):   # (0: the kind's default)
             raise ValueError(f"MODEL.SAMPLER_TRUNCATION_VALUE must lie in (0, 1] for typical / min-p and in (0, 1) for eta / epsilon, "
                              f"or be 0 for the kind's default; found {tv!r}")
+        for key, what in (("SAMPLER_MIROSTAT_TAU", "a finite number of bits >= 0 (0 = off)"), ("SAMPLER_MIROSTAT_ETA", "a finite number >= 0")):
+            mv = getattr(m, key)
+            if isinstance(mv, bool) or not isinstance(mv, (int, float)) or not 0 <= mv < float("inf"):   # (false for NaN)
+                raise ValueError(f"MODEL.{key} must be {what}; found {mv!r}")
         for key, ok, what in (("CONTRAST_ALPHA", lambda v: 0 <= v < float("inf"), "a finite number >= 0 (0 = off)"),
                               ("CONTRAST_BETA", lambda v: 0 <= v < 1, "in [0, 1)"), ("CONTRAST_NOISE", lambda v: 0 < v <= 1, "in (0, 1]")):
             cv = getattr(m, key)

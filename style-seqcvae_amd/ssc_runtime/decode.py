@@ -362,7 +362,8 @@ class DecodeEngine:
     def sample(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], n_samples: int, max_steps: int, end_index: int,
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
                attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None, truncation=None,
-               truncation_stats: bool = False, contrast=None, contrast_stats: bool = False):
+               truncation_stats: bool = False, contrast=None, contrast_stats: bool = False, mirostat=None,
+               mirostat_stats: bool = False):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample_opts): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
@@ -382,8 +383,18 @@ class DecodeEngine:
         StartState (Contrast.start).  contrast_stats=True (with an active contrast): the result is followed - behind the
         truncation's statistics - by (kept (B, steps) int32 - the words left plausible -, divergence (B, steps) float32 - the KL
         of the expert's word distribution from the amateur's, in nats), zero for ended rows and in the columns past the stop.
+        mirostat: a sampling.Mirostat, or None - the surprise of the drawn words is held at its target by feedback
+        (ssc_decode_sample_mirostat: a cut behind the truncation with the row's running threshold mu, an update of mu behind the
+        draw); None or an inactive one issues ssc_decode_sample_opts as before.  mirostat_stats=True (with an active Mirostat): the
+        result is followed - behind the other statistics - by (mu (B, steps) float32 - the threshold step t cut with -, surprise
+        (B, steps) float32 - the drawn word's surprise under the tempered distribution in front of the cut -, kept (B, steps) int32),
+        mu and surprise in the object's unit; surprise and kept are zero for ended rows, all three in the columns past the stop.
         skip_dead (default on): ended rows are not stepped; the captions do not depend on it."""
         _start_check(start, guide)
+        if mirostat is not None and not mirostat.active:
+            mirostat = None
+        if mirostat_stats and mirostat is None:
+            raise ValueError("DecodeEngine.sample: mirostat_stats needs an active mirostat")
         if contrast is not None and not contrast.active:
             contrast = None
         if contrast_stats and contrast is None:
@@ -426,6 +437,14 @@ class DecodeEngine:
         call = lambda p, sd, ws: self.lib.ssc_decode_sample_opts(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
                                                                  C.byref(opts), *ws)
         workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_opts_workspace_bytes(cfg, sd, C.byref(opts))
+        if mirostat is not None:   # the descriptor beside the opts; mu (max_steps + 1, B); slabs of steps never queued stay zero
+            mmu = torch.zeros(max_steps + 1, B, dtype=torch.float32, device=self.device)
+            msur = torch.zeros(max_steps, B, dtype=torch.float32, device=self.device) if mirostat_stats else None
+            mkept = torch.zeros(max_steps, B, dtype=torch.int32, device=self.device) if mirostat_stats else None
+            md = mirostat.desc(mmu, msur, mkept)
+            call = lambda p, sd, ws: self.lib.ssc_decode_sample_mirostat(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
+                                                                         C.byref(opts), C.byref(md), *ws)
+            workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_mirostat_workspace_bytes(cfg, sd, C.byref(opts), C.byref(md))
         out = self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
         if truncation_stats:
@@ -434,6 +453,10 @@ class DecodeEngine:
         if contrast_stats:
             steps = out[0].size(-1)
             out = tuple(out) + ((ckept[:steps].t().contiguous(), cdiv[:steps].t().contiguous()),)
+        if mirostat_stats:
+            steps = out[0].size(-1)
+            out = tuple(out) + ((mirostat.from_nats(mmu[:steps].t().contiguous()), mirostat.from_nats(msur[:steps].t().contiguous()),
+                                 mkept[:steps].t().contiguous()),)
         return out
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,

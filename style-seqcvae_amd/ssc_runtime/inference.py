@@ -27,7 +27,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    skip_dead: bool = True, compiled=None, obj_means: Optional[torch.Tensor] = None, sampler=None,
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
                    rules=None, attention: Optional[str] = None, guide=None, logit_rules=None, prefix=None,
-                   prefix_eps: Optional[torch.Tensor] = None, truncation=None, contrast=None, contrast_stats: bool = False):
+                   prefix_eps: Optional[torch.Tensor] = None, truncation=None, contrast=None, contrast_stats: bool = False, mirostat=None,
+                   mirostat_stats: bool = False):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -82,6 +83,11 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     same prefix noise.  ValueError naming the decoder with any other one, NotImplementedError with an ensemble.  None or an inactive
     one: the call without it.  Greedy contrastive decoding is the top-k sampler with k = 1.  contrast_stats=True: the result is
     followed by (kept, divergence) of shape (nimg, n_samples, steps) - over the continuation with a prefix.
+    mirostat: a sampling.Mirostat - with a word sampler the surprise of every caption's words is held at its target by feedback
+    (DecodeEngine.sample(mirostat=): a cut behind the truncation, an update behind the draw); ValueError naming the decoder with any
+    other one, NotImplementedError with an ensemble.  None or an inactive one: the call without it.  Composes with logit_rules,
+    truncation, contrast, guide, prefix (the control starts at the continuation) and attention.  mirostat_stats=True: the result is
+    followed - behind the contrast's statistics - by (mu, surprise, kept) of shape (nimg, n_samples, steps), in the object's unit.
     prefix: a DecodePrefix (ssc_runtime.prefix) with one row per image - or per (image, sample) entry -, or None.  With it every
     caption starts with its image's prompt: the prompt is teacher-forced on the nimg * n_samples rows (DecodeEngine.prime), whichever
     decoder was chosen continues from there (start=) and the call returns the FULL captions (nimg, n_samples, Lp + steps) - the
@@ -120,6 +126,21 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                  "the beam search" if sampler is None else None)
         if other is not None:
             raise ValueError(f"the truncation belongs to the word samplers: truncation= needs a multinomial / top-k / top-p sampler, "
+                             f"not {other}")
+    if mirostat is not None and not mirostat.active:
+        mirostat = None
+    if mirostat_stats and mirostat is None:
+        raise ValueError("mirostat_stats needs an active mirostat")
+    if mirostat is not None:
+        if isinstance(dec, EnsembleDecodeEngine):
+            raise NotImplementedError("Mirostat (mirostat=) is not implemented for an ensemble (EnsembleDecodeEngine)")
+        other = ("the beam search under decode rules (rules)" if rules is not None and rules.active else
+                 "the diverse beam search (diverse_beam)" if diverse_beam is not None else
+                 "the sampled-node beam search (sampled_beam)" if sampled_beam else
+                 "the stochastic beam search (GumbelSampler)" if sampler is not None and sampler.beam_search else
+                 "the beam search" if sampler is None else None)
+        if other is not None:
+            raise ValueError(f"Mirostat belongs to the word samplers: mirostat= needs a multinomial / top-k / top-p sampler, "
                              f"not {other}")
     if contrast is not None and not contrast.active:
         contrast = None
@@ -253,6 +274,10 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     rkw = {"logit_rules": logit_rules} if logit_rules is not None else {}
     if truncation is not None:
         rkw["truncation"] = truncation
+    if mirostat is not None:
+        rkw["mirostat"] = mirostat
+        if mirostat_stats:
+            rkw["mirostat_stats"] = True
     stats = {}
     if contrast is not None:
         cgen = torch.Generator(device=dev)
@@ -306,6 +331,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
             pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn,
                                          **gkw, **rkw, **skw)
+            if mirostat_stats:   # (the last of the statistics DecodeEngine.sample appends)
+                stats["mirostat"] = rec.pop()
             if contrast_stats:
                 stats["kept"], stats["divergence"] = rec.pop()
             calls["k"] = pred.size(-1)
@@ -355,7 +382,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
             state = select_best_state_simple_batched(lps, num_constraints, min_constraints_to_satisfy)
     sel = (torch.arange(B, device=dev) * S + state) * beam
     cstats = ((stats["kept"].view(nimg, n_samples, -1), stats["divergence"].view(nimg, n_samples, -1)),) if contrast_stats else ()
-    return (best.view(nimg, n_samples, -1), calls["k"]) + trace(rec, sel, (nimg, n_samples)) + cstats
+    mstats = (tuple(x.view(nimg, n_samples, -1) for x in stats["mirostat"]),) if mirostat_stats else ()
+    return (best.view(nimg, n_samples, -1), calls["k"]) + trace(rec, sel, (nimg, n_samples)) + cstats + mstats
 
 
 def count_tokens(pred: torch.Tensor, boundary_index: int) -> int:

@@ -255,6 +255,11 @@ class SampleOpts(C.Structure):
                 ("trunc", C.POINTER(Truncation)), ("contrast", C.POINTER(Contrast))]
 
 
+class Mirostat(C.Structure):
+    """ssc_mirostat: travels beside SampleOpts (ssc_decode_sample_mirostat); tau == 0 is off."""
+    _fields_ = [("tau", C.c_float), ("eta", C.c_float), ("mu0", C.c_float), ("mu", vp), ("surprise", vp), ("kept", vp)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -431,6 +436,12 @@ SYMBOLS = {
     "ssc_decode_sample_opts_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(SampleOpts)]),
     "ssc_decode_sample_opts": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
                                     C.POINTER(SampleOpts), vp, _sz, vp]),
+    "ssc_mirostat_rows": (_i, [vp, _i, _i, _i, _f, vp, vp, _i, vp, vp, vp]),
+    "ssc_mirostat_update": (_i, [vp, _i, _i, _i, _f, _f, _f, vp, vp, vp, _i, vp, vp, vp, vp]),
+    "ssc_decode_sample_mirostat_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(SampleOpts),
+                                                         C.POINTER(Mirostat)]),
+    "ssc_decode_sample_mirostat": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                        C.POINTER(SampleOpts), C.POINTER(Mirostat), vp, _sz, vp]),
     "ssc_decode_prime_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(PrimeDesc)]),
     "ssc_decode_prime": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(PrimeDesc), vp, _sz, vp]),
     "ssc_prefix_join": (_i, [vp, vp, _i, vp, vp, _i, vp, vp, _i, _i, _i, vp, vp, vp]),

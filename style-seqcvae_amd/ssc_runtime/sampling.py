@@ -27,6 +27,9 @@ draws from the edited distribution, where DecodeRules ban after the log-softmax 
 Truncation is the word samplers' entropy-adaptive cut - locally typical, min-p, eta and epsilon sampling - made the same way: one
 more edit of the raw logits between the logit rules and the draw (DecodeEngine.sample(truncation=) / ssc_sample_opts.trunc,
 MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE).  The samplers themselves are unchanged.
+
+Mirostat is the one control with state: a surprise target held by feedback, a cut behind the truncation and an update behind the draw
+(DecodeEngine.sample(mirostat=) / ssc_decode_sample_mirostat, MODEL.SAMPLER_MIROSTAT_TAU / SAMPLER_MIROSTAT_ETA).
 """
 import math
 
@@ -518,6 +521,97 @@ def truncation_from_config(model_cfg):
         raise ValueError(f"MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE: {e}") from None
 
 
+LN2 = math.log(2.0)
+MIROSTAT_UNITS = {"bits": LN2, "nats": 1.0}
+
+
+class Mirostat:
+    """Mirostat 2.0 for the word samplers (ssc_mirostat in include/ssc.h; Basu et al., ICLR 2021): the surprise of the drawn words is
+    held at the target `tau` by feedback - every word whose surprise exceeds a running threshold mu is cut in front of the draw, and
+    after the draw mu moves by eta times the error between the drawn word's surprise and tau (DecodeEngine.sample(mirostat=) /
+    ssc_decode_sample_mirostat).  mu0: every caption's mu at its first word, None: 2 tau (the paper's start).  unit: "bits" (the
+    paper's, the default) or "nats" - what tau, mu0 and the returned statistics are in; the device works in nats, the conversion is
+    made once here (ln 2 in double, rounded to fp32).  tau = 0: off; eta = 0: a fixed surprise cut at mu0."""
+
+    def __init__(self, tau: float = 3.0, eta: float = 0.1, mu0=None, unit: str = "bits") -> None:
+        if unit not in MIROSTAT_UNITS:
+            raise ValueError(f"the Mirostat unit must be 'bits' or 'nats', got {unit!r}")
+        try:
+            tau, eta = float(tau), float(eta)
+            mu0 = 2.0 * tau if mu0 is None else float(mu0)
+        except (TypeError, ValueError):
+            raise ValueError(f"the Mirostat tau, eta and mu0 must be numbers, got {tau!r}, {eta!r}, {mu0!r}") from None
+        if not (tau >= 0.0 and math.isfinite(tau)):   # (false for NaN)
+            raise ValueError(f"the Mirostat target tau must be finite and >= 0 (0: off), got {tau}")
+        if not (eta >= 0.0 and math.isfinite(eta)):
+            raise ValueError(f"the Mirostat learning rate eta must be finite and >= 0, got {eta}")
+        if not math.isfinite(mu0):
+            raise ValueError(f"the Mirostat start mu0 must be finite, got {mu0}")
+        self.tau, self.eta, self.mu0, self.unit = tau, eta, mu0, unit
+
+    @property
+    def scale(self) -> float:
+        """nats per unit"""
+        return MIROSTAT_UNITS[self.unit]
+
+    @property
+    def tau_nats(self) -> float:
+        return _f32(self.tau * self.scale)
+
+    @property
+    def mu0_nats(self) -> float:
+        return _f32(self.mu0 * self.scale)
+
+    @property
+    def active(self) -> bool:
+        return self.tau_nats != 0.0
+
+    def from_nats(self, t):
+        """A tensor of device statistics (nats) in this object's unit."""
+        return t if self.unit == "nats" else t / self.scale
+
+    def desc(self, mu=None, surprise=None, kept=None) -> "_lib.Mirostat":
+        """The C struct ssc_mirostat (nats); mu / surprise / kept: the blocks of the call, or None."""
+        d = _lib.Mirostat()
+        d.tau, d.eta, d.mu0 = self.tau_nats, self.eta, self.mu0_nats
+        d.mu = mu.data_ptr() if mu is not None else None
+        d.surprise = surprise.data_ptr() if surprise is not None else None
+        d.kept = kept.data_ptr() if kept is not None else None
+        return d
+
+    def __repr__(self):
+        return f"{type(self).__name__}(tau={self.tau}, eta={self.eta}, mu0={self.mu0}, unit={self.unit!r})"
+
+
+def _f32(v: float) -> float:
+    """v rounded to fp32 (what the C struct will hold)"""
+    import ctypes
+    return ctypes.c_float(v).value
+
+
+def mirostat_from_config(model_cfg):
+    """MODEL.SAMPLER_MIROSTAT_TAU (bits, 0 = off) / SAMPLER_MIROSTAT_ETA -> Mirostat, or None when off (no new code path runs then).
+    Mirostat belongs to the word samplers: DECODE_SAMPLER multinomial / top-k / top-p, SAMPLED_BEAM_SEARCH and
+    STOCHASTIC_BEAM_SEARCH False."""
+    tau = float(getattr(model_cfg, "SAMPLER_MIROSTAT_TAU", 0.0))
+    eta = float(getattr(model_cfg, "SAMPLER_MIROSTAT_ETA", 0.1))
+    if tau == 0.0:
+        return None
+    try:
+        m = Mirostat(tau, eta)
+    except ValueError as e:
+        raise ValueError(f"MODEL.SAMPLER_MIROSTAT_TAU / SAMPLER_MIROSTAT_ETA: {e}") from None
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if kind not in KINDS:
+        raise ValueError(f"MODEL.SAMPLER_MIROSTAT_TAU needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p', got "
+                         f"{model_cfg.DECODE_SAMPLER!r} (Mirostat belongs to the word samplers)")
+    for other in ("SAMPLED_BEAM_SEARCH", "STOCHASTIC_BEAM_SEARCH"):
+        if bool(getattr(model_cfg, other, False)):
+            raise ValueError(f"MODEL.SAMPLER_MIROSTAT_TAU and MODEL.{other} exclude each other (Mirostat belongs to the word-sampled "
+                             "decode)")
+    return m
+
+
 def from_config(model_cfg):
     """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
     STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
@@ -532,6 +626,7 @@ def from_config(model_cfg):
     decode_rules_from_config(model_cfg)
     logit_rules_from_config(model_cfg)
     truncation_from_config(model_cfg)
+    mirostat_from_config(model_cfg)
     from .contrast import contrast_from_config
     contrast_from_config(model_cfg)
     if sbs and kind != "beam":

@@ -195,7 +195,8 @@ class UpDownCaptioner(nn.Module):
         self._decode_guide = None      # decode_guide(): a LatentGuide the NEXT eval forwards draw their latents around
         self._logit_rules = None       # logit_rules(): sampling.LogitRules the NEXT eval forwards of a word sampler draw under
         self._truncation = None        # truncation(): sampling.Truncation the NEXT eval forwards of a word sampler cut their steps with
-        self._contrast = None          # contrast(): contrast.Contrast the NEXT eval forwards of a word sampler decode against an amateur with
+        self._mirostat = None          # mirostat(): sampling.Mirostat the NEXT eval forwards of a word sampler hold their surprise with
+        self._contrast = None          # contrast():contrast.Contrast the NEXT eval forwards of a word sampler decode against an amateur with
         self._decode_prefix = None     # decode_prefix(): a DecodePrefix every caption of the NEXT eval forwards starts with
 
     # ------------------------------------------------------------------------------------------------------
@@ -228,6 +229,7 @@ class UpDownCaptioner(nn.Module):
         if model.sampler is not None and not model.sampler.beam_search and not model.sampled_beam:
             model.logit_rules(sampling.logit_rules_from_config(_C.MODEL, vocabulary))
             model.truncation(sampling.truncation_from_config(_C.MODEL))
+            model.mirostat(sampling.mirostat_from_config(_C.MODEL))
             from ssc_runtime.contrast import contrast_from_config
             model.contrast(contrast_from_config(_C.MODEL))
         if str(_C.MODEL.DECODE_PREFIX).strip():
@@ -535,6 +537,7 @@ class UpDownCaptioner(nn.Module):
                              diverse_beam=self.diverse_beam, rules=self.decode_rules,
                              logit_rules=self._logit_rules if words else None, prefix=DecodePrefix(ids),
                              **({"truncation": self._truncation} if words and self._truncation is not None else {}),
+                             **({"mirostat": self._mirostat} if words and self._mirostat is not None else {}),
                              **({"contrast": self._contrast} if words and self._contrast is not None else {}))
         return {"predictions": out[0][:, 0, :]}
 
@@ -571,6 +574,21 @@ class UpDownCaptioner(nn.Module):
             if not truncation.active:
                 truncation = None
         self._truncation = truncation
+
+    def mirostat(self, mirostat):
+        """A Mirostat for the NEXT eval forwards of a word sampler (ssc_runtime.sampling.Mirostat; include/ssc.h: ssc_mirostat):
+        the surprise of every caption's words is held at the target - a cut behind the truncation, an update behind the draw.
+        None (the default state) or an inactive one: off, the forward is what it is without.  ValueError without a word sampler.
+        Training forwards, scst_step, score_captions and every beam search never read it."""
+        if mirostat is not None:
+            if not isinstance(mirostat, sampling.Mirostat):
+                raise ValueError(f"mirostat takes a ssc_runtime.sampling.Mirostat or None, got {type(mirostat).__name__}")
+            if self.sampler is None or self.sampler.beam_search or self.sampled_beam:
+                raise ValueError("mirostat needs a word sampler (MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                                 "MODEL.SAMPLED_BEAM_SEARCH): Mirostat belongs to the word-sampled decode")
+            if not mirostat.active:
+                mirostat = None
+        self._mirostat = mirostat
 
     def contrast(self, contrast):
         """A contrast for the NEXT eval forwards of a word sampler (ssc_runtime.contrast.Contrast; include/ssc.h: ssc_contrast):
@@ -736,6 +754,7 @@ class UpDownCaptioner(nn.Module):
                                          attention=self._decode_attention is not None, guide=self._decode_guide,
                                          **({"logit_rules": self._logit_rules} if self._logit_rules is not None else {}),
                                          **({"truncation": self._truncation} if self._truncation is not None else {}),
+                                         **({"mirostat": self._mirostat} if self._mirostat is not None else {}),
                                          **({"contrast": self._contrast} if self._contrast is not None else {}))
         return self._traced(pred, rec, torch.arange(B, device=dev))
 
