@@ -123,13 +123,11 @@ __global__ __launch_bounds__(256) void contrast_rows_kernel(const ContrastArgs a
   }
 }
 
-inline bool finite_f(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }   // false for NaN
-
 }  // namespace
 
 int ssc_contrast_check(float alpha, float beta, const int* kept, const float* divergence, bool* active) {
   *active = false;
-  if (!(alpha >= 0.f) || !finite_f(alpha)) return SSC_EINVAL;   // (false for NaN)
+  if (!(alpha >= 0.f) || !ssc_finite_f(alpha)) return SSC_EINVAL;   // (false for NaN)
   if (!(beta >= 0.f && beta < 1.f)) return SSC_EINVAL;
   if (((uintptr_t)kept & 3u) != 0 || ((uintptr_t)divergence & 3u) != 0) return SSC_EALIGN;
   *active = alpha != 0.f || beta != 0.f;

@@ -135,8 +135,6 @@ inline void logit_rules_split(const float* logits, int ld, const float* bias, in
   *n4 = (V - h) >> 2;
 }
 
-inline bool finite_f(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }   // false for NaN
-
 }  // namespace
 
 int ssc_logit_rules_check(const ssc_logit_rules* r, int V, int end_index, bool* active) {
@@ -146,8 +144,8 @@ int ssc_logit_rules_check(const ssc_logit_rules* r, int V, int end_index, bool* 
   if (r->n_suppress < 0 || r->n_suppress > SSC_RULES_MAX_SUPPRESS) return SSC_EINVAL;
   for (int q = 0; q < r->n_suppress; ++q)
     if (r->suppress[q] < 0 || r->suppress[q] >= V || r->suppress[q] == end_index) return SSC_EINVAL;
-  if (!(r->repetition_penalty > 0.f) || !finite_f(r->repetition_penalty)) return SSC_EINVAL;
-  if (!finite_f(r->presence_penalty) || !finite_f(r->frequency_penalty)) return SSC_EINVAL;
+  if (!(r->repetition_penalty > 0.f) || !ssc_finite_f(r->repetition_penalty)) return SSC_EINVAL;
+  if (!ssc_finite_f(r->presence_penalty) || !ssc_finite_f(r->frequency_penalty)) return SSC_EINVAL;
   if (r->bias && (r->ld_bias < V || r->n_bias < 1)) return SSC_EINVAL;
   if (((uintptr_t)r->bias & 3u) != 0 || (r->bias && ((uintptr_t)r->bias_row & 3u) != 0)) return SSC_EALIGN;
   *active = r->no_repeat_ngram >= 1 || r->min_length > 0 || r->n_suppress > 0 || r->repetition_penalty != 1.f ||

@@ -6,19 +6,22 @@
 //   ssc_mirostat_update  the UPDATE behind the draw: mu' = mu - eta (s - tau), s the drawn word's surprise under the tempered
 //                        distribution BEFORE the cut - the authors' reference implementation's choice, not the renormalised one.
 // ssc_decode_sample_mirostat (sample.hip) issues the two around each step's draw; the draw itself does not know of them.
-// The cut has the shape of the truncation's kinds 2 to 4 (truncation.hip): one workgroup of SAMPLE_THREADS per row, the row staged in
-// LDS once for V <= SAMPLE_LDS_MAX_V, every pass over global memory above that.  The passes of a live row:
-//   1. the maximum mx (and, STAGED, the copy into LDS);
-//   2. with a_v = (x_v - mx) / T over the finite entries: Z = sum exp(a_v), log Z, and the lowest index at which x_v == mx;
-//   3. the write pass: kept <=> a_v >= log Z - mu or v == first; a dropped entry becomes -inf, a kept one is stored back with the bits
+// The cut is the truncation's kinds 2 to 4 (truncation.hip) with a threshold per row, built from the same row passes of ssc_radix.h:
+// one workgroup of SAMPLE_THREADS per row, the row staged in LDS once for V <= SAMPLE_LDS_MAX_V, every pass over global memory above
+// that.  The passes of a live row:
+//   1. row_stage_max: the maximum mx (and, STAGED, the copy into LDS);
+//   2. row_tempered_sums, with a_v = (x_v - mx) / T over the finite entries: Z = sum exp(a_v) (no entropy sum), and the lowest index
+//      at which x_v == mx; then log Z;
+//   3. row_write_kept: kept <=> a_v >= log Z - mu or v == first; a dropped entry becomes -inf, a kept one is stored back with the bits
 //      it had; the kept entries are counted.  mx and log Z go to `norm` for the update, which then reads ONE word of the row.
+// What is the kernel's own: the threshold, the `norm` store, and which statistics a row that is not edited zeroes (`kept` alone).
 // Every reduction runs in a fixed order (wave butterflies, then the waves in index order), no atomics: two calls on equal inputs are
 // bit-identical.  An entry of -inf stays dropped and weighs nothing; a row without a finite entry is left as it is; a row whose last
 // token is END is neither read nor written; columns V .. ld - 1 are never touched.  16-byte accesses where the row is 16-byte aligned
 // with V % 4 == 0, scalar ones otherwise: per element the same operations either way.
 #include <math.h>
 
-#include "sample_draw.h"
+#include "ssc_radix.h"
 
 namespace {
 
@@ -29,28 +32,6 @@ struct MirostatArgs {
   const int64_t* last_pred; int end_index;
   int* kept; float* norm;
 };
-
-// block-wide integer min / sum in a fixed order (the samplers' besti words carry the waves' parts)
-__device__ __forceinline__ int miro_block_min_int(int v, SampleShared& sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh.besti[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = sh.besti[0];
-  for (int w = 1; w < SAMPLE_WAVES; ++w) r = min(r, sh.besti[w]);
-  return r;
-}
-__device__ __forceinline__ int miro_block_sum_int(int v, SampleShared& sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh.besti[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = sh.besti[0];
-  for (int w = 1; w < SAMPLE_WAVES; ++w) r += sh.besti[w];
-  return r;
-}
 
 template <bool STAGED>
 __global__ __launch_bounds__(SAMPLE_THREADS) void mirostat_rows_kernel(MirostatArgs a) {
@@ -63,80 +44,23 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void mirostat_rows_kernel(MirostatA
     return;
   }
   float* g = a.logits + (size_t)r * a.ld;
-  const bool vec = ssc_aligned16_dev(g) && (V & 3) == 0;
-  const RowView<STAGED> row{g, srow, V, vec};
-  const int nj = (V + 3) >> 2;
+  const RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
   const float T = a.temperature;
   // ---- 1. stage the row (once from HBM) and its maximum --------------------------------------------------------------------
-  float mx = -INFINITY;
-  if (STAGED) {
-    const RowView<false> gv{g, nullptr, V, vec};
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      gv.get4(j, x);
-      if (4 * j + 3 < V) {
-        *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-        for (int c = 0; c < 4; ++c)
-          if (4 * j + c < V) srow[4 * j + c] = x[c];
-      }
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  } else {
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      row.get4(j, x);
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  }
-  mx = block_max(mx, sh);   // (its barriers also publish srow)
-  if (!(mx > -INFINITY)) {  // no finite entry (workgroup-uniform): the row is left as it is
+  const float mx = row_stage_max(row, srow, sh);
+  if (!(mx > -INFINITY)) {  // no finite entry (workgroup-uniform): the row is left as it is, and so is its norm
     if (threadIdx.x == 0 && a.kept) a.kept[r] = 0;
     return;
   }
   // ---- 2. the tempered normaliser over the finite entries and the lowest-index maximum ---------------------------------------
-  float z = 0.f;
-  int first = 0x7fffffff;
-  for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-    float x[4];
-    row.get4(j, x);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (x[c] > -INFINITY) {   // (-inf, and the columns past V, weigh nothing)
-        z += expf((x[c] - mx) / T);
-        if (x[c] == mx) first = min(first, 4 * j + c);
-      }
-    }
-  }
-  z = block_sum(z, sh);
-  const float logz = logf(z);
-  first = miro_block_min_int(first, sh);
+  const RowSums sums = row_tempered_sums<STAGED, false>(row, mx, T, true, sh);
+  const float logz = logf(sums.z);
+  const int first = sums.first;
   // ---- 3. the cut: surprise log Z - a_v <= mu, or the top word ----------------------------------------------------------------
   const float thr = logz - a.mu[r];
-  int nkept = 0;
-  for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-    float x[4];
-    row.get4(j, x);
-    bool drop[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int v = 4 * j + c;
-      bool keep = false;
-      if (v < V && x[c] > -INFINITY) keep = (x[c] - mx) / T >= thr || v == first;
-      drop[c] = !keep;
-      nkept += keep ? 1 : 0;
-    }
-    if (vec) {
-      *reinterpret_cast<float4*>(g + 4 * j) = make_float4(drop[0] ? -INFINITY : x[0], drop[1] ? -INFINITY : x[1],
-                                                          drop[2] ? -INFINITY : x[2], drop[3] ? -INFINITY : x[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (4 * j + c < V && drop[c]) g[4 * j + c] = -INFINITY;
-    }
-  }
+  int nkept = row_write_kept(row, g, [&](int v, float x) { return ((x - mx) / T >= thr) | (v == first); });
   if (a.kept) {   // (a kernel argument: workgroup-uniform)
-    nkept = miro_block_sum_int(nkept, sh);
+    nkept = block_sum_int(nkept, sh);
     if (threadIdx.x == 0) a.kept[r] = nkept;
   }
   if (threadIdx.x == 0) {
@@ -183,17 +107,15 @@ __global__ __launch_bounds__(256) void mirostat_fill_kernel(float* __restrict__ 
   if (i < n) mu[i] = v;
 }
 
-inline bool finite_f(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }   // false for NaN
-
 }  // namespace
 
 int ssc_mirostat_check(const ssc_mirostat* m, float temperature, bool* active) {
   *active = false;
   if (!m) return SSC_OK;
-  if (!(m->tau >= 0.f) || !finite_f(m->tau)) return SSC_EINVAL;   // (false for NaN)
+  if (!(m->tau >= 0.f) || !ssc_finite_f(m->tau)) return SSC_EINVAL;   // (false for NaN)
   if (m->tau == 0.f) return SSC_OK;                                // off: nothing else is read
-  if (!(m->eta >= 0.f) || !finite_f(m->eta) || !finite_f(m->mu0)) return SSC_EINVAL;
-  if (!(temperature > 0.f) || !finite_f(temperature)) return SSC_EINVAL;
+  if (!(m->eta >= 0.f) || !ssc_finite_f(m->eta) || !ssc_finite_f(m->mu0)) return SSC_EINVAL;
+  if (!(temperature > 0.f) || !ssc_finite_f(temperature)) return SSC_EINVAL;
   if (!m->mu) return SSC_EINVAL;
   if (((uintptr_t)m->mu & 3u) != 0 || ((uintptr_t)m->surprise & 3u) != 0 || ((uintptr_t)m->kept & 3u) != 0) return SSC_EALIGN;
   *active = true;
@@ -214,15 +136,7 @@ int ssc_mirostat_rows_launch(float* logits, int ld, int rows, int V, float tempe
   a.temperature = temperature; a.mu = mu;
   a.last_pred = last_pred; a.end_index = end_index;
   a.kept = kept; a.norm = norm;
-  if (V <= SAMPLE_LDS_MAX_V) {
-    size_t lds;
-    SSC_TRY(sample_row_lds(mirostat_rows_kernel<true>, V, &lds));
-    SSC_LAUNCH(mirostat_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
-  } else {
-    SSC_LAUNCH(mirostat_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
-  }
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
+  return sample_row_launch(mirostat_rows_kernel<true>, mirostat_rows_kernel<false>, V, rows, st, a);
 }
 
 int ssc_mirostat_update_launch(const float* logits, int ld, int rows, int V, float temperature, float tau, float eta, const float* norm,
@@ -241,7 +155,7 @@ int ssc_mirostat_update_launch(const float* logits, int ld, int rows, int V, flo
 extern "C" int ssc_mirostat_rows(float* logits, int ld, int rows, int V, float temperature, const float* mu_in, const int64_t* last_pred,
                                  int end_index, int* kept, float* norm, void* stream) {
   if (!logits || !mu_in || !norm || rows < 0 || V < 1 || ld < V) return SSC_EINVAL;
-  if (!(temperature > 0.f) || !finite_f(temperature)) return SSC_EINVAL;
+  if (!(temperature > 0.f) || !ssc_finite_f(temperature)) return SSC_EINVAL;
   if (last_pred && (end_index < 0 || end_index >= V)) return SSC_EINVAL;
   if (((uintptr_t)logits & 3u) != 0 || ((uintptr_t)mu_in & 3u) != 0 || ((uintptr_t)last_pred & 3u) != 0 || ((uintptr_t)kept & 3u) != 0 ||
       ((uintptr_t)norm & 3u) != 0)
@@ -254,8 +168,8 @@ extern "C" int ssc_mirostat_update(const float* logits, int ld, int rows, int V,
                                    const float* norm, const int64_t* pred, const int64_t* last_pred, int end_index, const float* mu_in,
                                    float* mu_out, float* surprise, void* stream) {
   if (!logits || !norm || !pred || !mu_in || !mu_out || rows < 0 || V < 1 || ld < V) return SSC_EINVAL;
-  if (!(temperature > 0.f) || !finite_f(temperature)) return SSC_EINVAL;
-  if (!(tau >= 0.f) || !finite_f(tau) || !(eta >= 0.f) || !finite_f(eta)) return SSC_EINVAL;
+  if (!(temperature > 0.f) || !ssc_finite_f(temperature)) return SSC_EINVAL;
+  if (!(tau >= 0.f) || !ssc_finite_f(tau) || !(eta >= 0.f) || !ssc_finite_f(eta)) return SSC_EINVAL;
   if (last_pred && (end_index < 0 || end_index >= V)) return SSC_EINVAL;
   if (((uintptr_t)logits & 3u) != 0 || ((uintptr_t)norm & 3u) != 0 || ((uintptr_t)pred & 3u) != 0 || ((uintptr_t)last_pred & 3u) != 0 ||
       ((uintptr_t)mu_in & 3u) != 0 || ((uintptr_t)mu_out & 3u) != 0 || ((uintptr_t)surprise & 3u) != 0)

@@ -97,15 +97,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(SampleArgs 
 }
 
 int sample_launch(SampleArgs a, int rows, hipStream_t st) {
-  if (a.V <= SAMPLE_LDS_MAX_V) {
-    size_t lds;
-    SSC_TRY(sample_row_lds(sample_rows_kernel<true>, a.V, &lds));
-    SSC_LAUNCH(sample_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
-  } else {
-    SSC_LAUNCH(sample_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
-  }
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
+  return sample_row_launch(sample_rows_kernel<true>, sample_rows_kernel<false>, a.V, rows, st, a);
 }
 
 SampleArgs sample_args(const ssc_sampler_desc* s, const float* logits, size_t ld, int V) {

@@ -1,8 +1,9 @@
 // The word draw of one row of raw logits, shared by the word samplers (sample.hip: sample_rows_kernel) and the scheduled-sampling
-// mix kernel of the train step (sched_sampling.hip): stage the row, its maximum and log-sum-exp, the top-k / top-p cut, and the
-// Gumbel-max draw over the kept set with Philox4x32-10 noise of counter (v / 4, step, row, 0).  One definition: a kernel that calls
-// sample_draw_row draws ssc_sample_rows' token for the same row, sampler, step, row id and seed.  Also the limits of
-// ssc_sampler_desc every entry point that takes one checks before a launch (sampler_ok).
+// mix kernel of the train step (sched_sampling.hip): the row staged with its maximum (row_stage_max of ssc_radix.h), its
+// log-sum-exp, the top-k / top-p cut, and the Gumbel-max draw over the kept set with Philox4x32-10 noise of counter
+// (v / 4, step, row, 0).  One definition: a kernel that calls sample_draw_row draws ssc_sample_rows' token for the same row, sampler,
+// step, row id and seed.  Also the limits of ssc_sampler_desc every entry point that takes one checks before a launch (sampler_ok);
+// the launch of the two kernel forms is ssc_radix.h's sample_row_launch.
 #pragma once
 #include <math.h>
 
@@ -18,15 +19,6 @@ inline bool sampler_ok(const ssc_sampler_desc* s, int V) {
   if (s->kind == 1) return s->top_k >= 1 && s->top_k <= V;
   if (s->kind == 2) return s->top_p >= 0.f && s->top_p <= 1.f;
   return false;
-}
-
-// dynamic LDS of a kernel that stages its row (V <= SAMPLE_LDS_MAX_V), raised past the 64 KiB default where the row needs it
-template <typename K>
-inline int sample_row_lds(K kernel, int V, size_t* lds) {
-  *lds = (size_t)((V + 3) & ~3) * 4;
-  if (*lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
-    return SSC_EHIP;
-  return SSC_OK;
 }
 
 struct SampleDraw {
@@ -47,28 +39,7 @@ __device__ __forceinline__ SampleDraw sample_draw_row(const float* g, float* sro
   RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
   const int nj = (V + 3) >> 2;
   // ---- stage the row (once from HBM) and its maximum ---------------------------------------------------------------------
-  float mx = -INFINITY;
-  if (STAGED) {
-    RowView<false> gv{g, nullptr, V, row.vec};
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      gv.get4(j, x);
-      if (4 * j + 3 < V) {
-        *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-        for (int c = 0; c < 4; ++c)
-          if (4 * j + c < V) srow[4 * j + c] = x[c];
-      }
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  } else {
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      row.get4(j, x);
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  }
-  mx = block_max(mx, sh);   // (its barriers also publish srow)
+  const float mx = row_stage_max(row, srow, sh);
   const bool topp = kind == 2 && top_p < 1.f;
   // ---- untempered log-sum-exp (the step log-prob) and the tempered normaliser (top-p masses) -------------------------------
   float s = 0.f, st = 0.f;

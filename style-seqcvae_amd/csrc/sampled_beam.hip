@@ -90,28 +90,7 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void snb_rows_kernel(SnbRowArgs a) 
   RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
   const int nj = (V + 3) >> 2;
   // ---- stage the row (once from HBM) and its maximum (as sample_rows_kernel) -----------------------------------------------
-  float mx = -INFINITY;
-  if (STAGED) {
-    RowView<false> gv{g, nullptr, V, row.vec};
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      gv.get4(j, x);
-      if (4 * j + 3 < V) {
-        *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-        for (int c = 0; c < 4; ++c)
-          if (4 * j + c < V) srow[4 * j + c] = x[c];
-      }
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  } else {
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      row.get4(j, x);
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  }
-  mx = block_max(mx, sh);   // (its barriers also publish srow)
+  const float mx = row_stage_max(row, srow, sh);
   const float T = a.temperature;
   const bool topp = a.kind == 2 && a.top_p < 1.f;
   // ---- untempered log-sum-exp (the step log-prob) and the tempered normaliser (top-p masses) ---------------------------------
@@ -287,20 +266,6 @@ __global__ __launch_bounds__(64) void snb_merge_kernel(const float* __restrict__
   }
 }
 
-int snb_rows_launch(const SnbRowArgs& a, int rows, hipStream_t st) {
-  if (a.V <= SAMPLE_LDS_MAX_V) {
-    const size_t lds = (size_t)((a.V + 3) & ~3) * 4;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute((const void*)snb_rows_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return SSC_EHIP;
-    SSC_LAUNCH(snb_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
-  } else {
-    SSC_LAUNCH(snb_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
-  }
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
 }  // namespace
 
 // trivial machine aside (checked by the callers): 1 <= k, n <= 32, k, n <= V, B * k <= 2^24, T > 0 finite, a known kind, top-k with
@@ -332,7 +297,7 @@ extern "C" int ssc_beam_step_sampled(const ssc_beam_desc* d, const ssc_sampler_d
   a.seed_lo = (uint32_t)(s->seed & 0xffffffffu); a.seed_hi = (uint32_t)(s->seed >> 32); a.step = d->step_index;
   a.last_pred = d->last_pred; a.phi = d->last_lp; a.end_index = d->end_index; a.ctl = d->ctl;
   a.clp = d->scratch_val; a.ctok = d->scratch_idx;
-  SSC_TRY(snb_rows_launch(a, B * k, st));
+  SSC_TRY(sample_row_launch(snb_rows_kernel<true>, snb_rows_kernel<false>, a.V, B * k, st, a));
   SSC_LAUNCH(snb_merge_kernel, dim3(B), dim3(64), 0, st, d->scratch_val, d->scratch_idx, n, k, d->last_lp, d->pred, d->lp_out,
              d->backptr, d->end_index, d->ctl, d->step_index, d->max_steps, d->host_flag);
   SSC_CHECK_LAUNCH();

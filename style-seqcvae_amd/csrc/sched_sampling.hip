@@ -78,14 +78,5 @@ extern "C" int ssc_sched_mix_rows(const float* logits, int ld, int rows, int V, 
   a.truth = truth; a.w_prev = w_prev; a.w_cur = w_cur;
   a.table = table; a.ldt = ldt; a.E = E;
   a.tok_out = tok_out; a.fed_out = fed_out; a.emb_out = emb_out; a.ldo = ldo;
-  hipStream_t st = (hipStream_t)stream;
-  if (V <= SAMPLE_LDS_MAX_V) {
-    size_t lds;
-    SSC_TRY(sample_row_lds(sched_mix_rows_kernel<true>, V, &lds));
-    SSC_LAUNCH(sched_mix_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
-  } else {
-    SSC_LAUNCH(sched_mix_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
-  }
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
+  return sample_row_launch(sched_mix_rows_kernel<true>, sched_mix_rows_kernel<false>, V, rows, (hipStream_t)stream, a);
 }

@@ -46,6 +46,7 @@ static inline int ssc_env_int(const char* name, int dflt) {
 static inline bool ssc_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
 static inline int ssc_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline size_t ssc_round_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
+static inline bool ssc_finite_f(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }   // false for NaN
 
 #define SSC_WAVE 64
 __device__ __forceinline__ bool ssc_aligned16_dev(const void* p) { return (((uintptr_t)p) & 15u) == 0; }

@@ -1,6 +1,9 @@
-// Row-statistics helpers shared by the word samplers (sample.hip) and the sampled-node beam search (sampled_beam.hip): the
-// order-preserving key of a logit, the row view (LDS-staged or global), block reductions in a fixed order, and the radix select
-// with integer-only LDS histograms that finds the top-k / top-p cut (ties at the cut: lower index first).
+// Row-pass helpers shared by the word samplers (sample.hip, sched_sampling.hip through sample_draw.h), the sampled-node beam search
+// (sampled_beam.hip) and the cuts in front of the draw (truncation.hip, mirostat.hip): the order-preserving key of a logit, the row
+// view (LDS-staged or global), block reductions in a fixed order, the row passes every one of these kernels is built from - stage
+// the row and take its maximum (row_stage_max), the tempered sums (row_tempered_sums), the write pass of a cut (row_write_kept) -,
+// the radix select with integer-only LDS histograms that finds the top-k / top-p cut (ties at the cut: lower index first), and the
+// host side of the two kernel forms: the LDS row's size and the launch that chooses between them (sample_row_launch).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -58,6 +61,27 @@ __device__ __forceinline__ float block_sum(float v, SampleShared& sh) {
   for (int w = 1; w < SAMPLE_WAVES; ++w) r += sh.red[w];
   return r;
 }
+// block-wide integer min / sum in the same fixed order (the samplers' besti words carry the waves' parts)
+__device__ __forceinline__ int block_min_int(int v, SampleShared& sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh.besti[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int r = sh.besti[0];
+  for (int w = 1; w < SAMPLE_WAVES; ++w) r = min(r, sh.besti[w]);
+  return r;
+}
+__device__ __forceinline__ int block_sum_int(int v, SampleShared& sh) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) sh.besti[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int r = sh.besti[0];
+  for (int w = 1; w < SAMPLE_WAVES; ++w) r += sh.besti[w];
+  return r;
+}
 
 // the row, four consecutive entries at a time (entries >= V read as -inf)
 template <bool STAGED>
@@ -88,6 +112,98 @@ struct RowView {
   }
   __device__ __forceinline__ float at(int v) const { return STAGED ? s[v] : g[v]; }
 };
+
+// The first pass of a row kernel: the row's maximum, the same in every thread, and - STAGED - the row's one read from HBM into srow
+// ((V + 3) & ~3 floats of LDS, row.s); the global form reads the row once per pass instead.
+template <bool STAGED>
+__device__ __forceinline__ float row_stage_max(const RowView<STAGED>& row, float* srow, SampleShared& sh) {
+  const int V = row.V;
+  const int nj = (V + 3) >> 2;
+  float mx = -INFINITY;
+  if (STAGED) {
+    const RowView<false> gv{row.g, nullptr, V, row.vec};
+    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+      float x[4];
+      gv.get4(j, x);
+      if (4 * j + 3 < V) {
+        *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
+      } else {
+        for (int c = 0; c < 4; ++c)
+          if (4 * j + c < V) srow[4 * j + c] = x[c];
+      }
+      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
+    }
+  } else {
+    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+      float x[4];
+      row.get4(j, x);
+      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
+    }
+  }
+  return block_max(mx, sh);   // (its barriers also publish srow)
+}
+
+// The tempered sums of a live row with maximum mx, over its finite entries (-inf, and the columns past V, weigh nothing and are
+// never multiplied), a_v = (x_v - mx) / T: z = sum exp(a_v); ENTROPY: s1 = sum a_v exp(a_v) (else 0); want_first (workgroup-uniform):
+// the lowest index at which x_v == mx (else 0x7fffffff).  The same in every thread.
+struct RowSums { float z, s1; int first; };
+template <bool STAGED, bool ENTROPY>
+__device__ __forceinline__ RowSums row_tempered_sums(const RowView<STAGED>& row, float mx, float T, bool want_first, SampleShared& sh) {
+  const int nj = (row.V + 3) >> 2;
+  RowSums o{0.f, 0.f, 0x7fffffff};
+  for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+    float x[4];
+    row.get4(j, x);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (x[c] > -INFINITY) {
+        const float av = (x[c] - mx) / T;
+        const float e = expf(av);
+        o.z += e;
+        if (ENTROPY) o.s1 += e * av;
+        if (want_first && x[c] == mx) o.first = min(o.first, 4 * j + c);
+      }
+    }
+  }
+  o.z = block_sum(o.z, sh);
+  if (ENTROPY) o.s1 = block_sum(o.s1, sh);
+  if (want_first) o.first = block_min_int(o.first, sh);
+  return o;
+}
+
+// The write pass of a cut over the row at g (the row of `row`, writable): keep(v, x) is asked for every v < V with a finite x; a
+// dropped entry becomes -inf.  With row.vec a kept entry is stored back with the bits it had (16-byte stores), without it only the
+// dropped entries are stored: per element the same result.  Returns the thread's count of kept entries (block_sum_int it).
+// (A predicate that joins two comparisons joins them with |: behind this call a || compiles to a divergent branch per element,
+// measured at 1 to 4 % of the cut kernels' time.)
+template <bool STAGED, typename F>
+__device__ __forceinline__ int row_write_kept(const RowView<STAGED>& row, float* g, F&& keep) {
+  const int V = row.V;
+  const int nj = (V + 3) >> 2;
+  int nkept = 0;
+  for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
+    float x[4];
+    row.get4(j, x);
+    bool drop[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int v = 4 * j + c;
+      bool k = false;
+      if (v < V && x[c] > -INFINITY) k = keep(v, x[c]);
+      drop[c] = !k;
+      nkept += k ? 1 : 0;
+    }
+    if (row.vec) {
+      *reinterpret_cast<float4*>(g + 4 * j) = make_float4(drop[0] ? -INFINITY : x[0], drop[1] ? -INFINITY : x[1],
+                                                          drop[2] ? -INFINITY : x[2], drop[3] ? -INFINITY : x[3]);
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (4 * j + c < V && drop[c]) g[4 * j + c] = -INFINITY;
+    }
+  }
+  return nkept;
+}
 
 // One radix-select descent.  Every row entry v offers (active, key, weight); the entries are ranked by key DESCENDING.  Finds the
 // first entry, in that order, at which the running weight (inclusive) reaches `thr` - restricted to keys; the result is its key,
@@ -232,6 +348,29 @@ __device__ __forceinline__ void sample_cut(const RowView<STAGED>& row, int kind,
       __syncthreads();
     }
   }
+}
+
+// dynamic LDS of a kernel that stages its row (V <= SAMPLE_LDS_MAX_V), raised past the 64 KiB default where the row needs it
+template <typename K>
+inline int sample_row_lds(K kernel, int V, size_t* lds) {
+  *lds = (size_t)((V + 3) & ~3) * 4;
+  if (*lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds) != hipSuccess)
+    return SSC_EHIP;
+  return SSC_OK;
+}
+
+// the launch of a row kernel, one workgroup of SAMPLE_THREADS per row: its LDS form for V <= SAMPLE_LDS_MAX_V, its global form above
+template <typename A>
+inline int sample_row_launch(void (*lds_form)(A), void (*global_form)(A), int V, int rows, hipStream_t st, const A& a) {
+  if (V <= SAMPLE_LDS_MAX_V) {
+    size_t lds;
+    SSC_TRY(sample_row_lds(lds_form, V, &lds));
+    SSC_LAUNCH(lds_form, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
+  } else {
+    SSC_LAUNCH(global_form, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
+  }
+  SSC_CHECK_LAUNCH();
+  return SSC_OK;
 }
 
 }  // namespace

@@ -2,14 +2,17 @@
 // of a row of RAW logits in front of the unchanged draw, so that the sampler draws from - and reports the log-prob under - the cut
 // distribution.  ssc_truncate_rows is the stand-alone edit of one step; ssc_decode_sample_opts (sample.hip) issues it between each
 // step's logit rules and its draw.
-// One workgroup of SAMPLE_THREADS per row, two forms as for the samplers (ssc_radix.h): the row staged in LDS once for
-// V <= SAMPLE_LDS_MAX_V, every pass over global memory above that.  The passes of a live row:
-//   1. the maximum mx (and, STAGED, the copy into LDS);
-//   2. with a_v = (x_v - mx) / T over the finite entries: Z = sum exp(a_v), S = sum a_v exp(a_v); log Z, H = log Z - S / Z;
-//      kinds 3 and 4 also the lowest index at which x_v == mx;
-//   3. kind 1 only: the radix select of ssc_radix.h on the key of d_v = |(log Z - a_v) - H|, ASCENDING (the key is complemented),
-//      weighted by the 2^-40 fixed-point masses of top-p; ties at the cut by a second select on the index (lower index first);
-//   4. the write pass: a dropped entry becomes -inf, a kept one is stored back with the bits it had; the kept entries are counted.
+// One workgroup of SAMPLE_THREADS per row, two forms as for the samplers: the row staged in LDS once for V <= SAMPLE_LDS_MAX_V, every
+// pass over global memory above that.  The passes of a live row; 1, 2 and 4 are the row passes of ssc_radix.h, which the Mirostat
+// cut (mirostat.hip) shares:
+//   1. row_stage_max: the maximum mx (and, STAGED, the copy into LDS);
+//   2. row_tempered_sums, with a_v = (x_v - mx) / T over the finite entries: Z = sum exp(a_v), S = sum a_v exp(a_v), kinds 3 and 4
+//      also the lowest index at which x_v == mx; then log Z, H = log Z - S / Z;
+//   3. the kernel's own: the threshold of kinds 2 to 4, or, kind 1, the radix select of ssc_radix.h on the key of
+//      d_v = |(log Z - a_v) - H|, ASCENDING (the key is complemented), weighted by the 2^-40 fixed-point masses of top-p; ties at the
+//      cut by a second select on the index (lower index first);
+//   4. row_write_kept under the kind's predicate: a dropped entry becomes -inf, a kept one is stored back with the bits it had; the
+//      kept entries are counted.
 // Kinds 2 to 4 compare a_v with one threshold and need no select.  Every reduction runs in a fixed order (wave butterflies, then the
 // waves in index order) and the histograms of the select are integer: two calls on equal inputs are bit-identical.  An entry of
 // -inf (a ban of the logit rules) stays dropped, weighs nothing and never meets a product; a row without a finite entry is left
@@ -17,7 +20,7 @@
 // where the row is 16-byte aligned with V % 4 == 0, scalar ones otherwise: per element the same operations either way.
 #include <math.h>
 
-#include "sample_draw.h"
+#include "ssc_radix.h"
 
 namespace {
 
@@ -27,28 +30,6 @@ struct TruncArgs {
   const int64_t* last_pred; int end_index;
   float* entropy; int* kept;
 };
-
-// block-wide integer min / sum in a fixed order (the samplers' besti words carry the waves' parts)
-__device__ __forceinline__ int block_min_int(int v, SampleShared& sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh.besti[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = sh.besti[0];
-  for (int w = 1; w < SAMPLE_WAVES; ++w) r = min(r, sh.besti[w]);
-  return r;
-}
-__device__ __forceinline__ int block_sum_int(int v, SampleShared& sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh.besti[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int r = sh.besti[0];
-  for (int w = 1; w < SAMPLE_WAVES; ++w) r += sh.besti[w];
-  return r;
-}
 
 // the typical order's key of a finite entry: descending key <=> ascending d = |s_v - H|, s_v = log Z - a_v (d >= 0: its bits order it)
 __device__ __forceinline__ uint32_t typical_key(float x, float mx, float T, float logz, float H) {
@@ -63,71 +44,23 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void truncate_rows_kernel(TruncArgs
   __shared__ SampleShared sh;
   const int r = blockIdx.x;
   const int V = a.V;
-  if (a.last_pred && a.last_pred[r] == a.end_index) {   // workgroup-uniform: an ended row is neither read nor written
+  const auto leave = [&] {   // the statistics of a row that is not edited
     if (threadIdx.x == 0) {
       if (a.entropy) a.entropy[r] = 0.f;
       if (a.kept) a.kept[r] = 0;
     }
-    return;
-  }
+  };
+  if (a.last_pred && a.last_pred[r] == a.end_index) return leave();   // workgroup-uniform: an ended row is neither read nor written
   float* g = a.logits + (size_t)r * a.ld;
-  const bool vec = ssc_aligned16_dev(g) && (V & 3) == 0;
-  const RowView<STAGED> row{g, srow, V, vec};
-  const int nj = (V + 3) >> 2;
+  const RowView<STAGED> row{g, srow, V, ssc_aligned16_dev(g) && (V & 3) == 0};
   const float T = a.temperature;
   // ---- 1. stage the row (once from HBM) and its maximum --------------------------------------------------------------------
-  float mx = -INFINITY;
-  if (STAGED) {
-    const RowView<false> gv{g, nullptr, V, vec};
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      gv.get4(j, x);
-      if (4 * j + 3 < V) {
-        *reinterpret_cast<float4*>(srow + 4 * j) = make_float4(x[0], x[1], x[2], x[3]);
-      } else {
-        for (int c = 0; c < 4; ++c)
-          if (4 * j + c < V) srow[4 * j + c] = x[c];
-      }
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  } else {
-    for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-      float x[4];
-      row.get4(j, x);
-      mx = fmaxf(fmaxf(mx, fmaxf(x[0], x[1])), fmaxf(x[2], x[3]));
-    }
-  }
-  mx = block_max(mx, sh);   // (its barriers also publish srow)
-  if (!(mx > -INFINITY)) {  // no finite entry (workgroup-uniform): the row is left as it is
-    if (threadIdx.x == 0) {
-      if (a.entropy) a.entropy[r] = 0.f;
-      if (a.kept) a.kept[r] = 0;
-    }
-    return;
-  }
-  // ---- 2. the tempered normaliser and the entropy over the finite entries ---------------------------------------------------
-  const bool want_first = a.kind >= 3;
-  float z = 0.f, s1 = 0.f;
-  int first = 0x7fffffff;
-  for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-    float x[4];
-    row.get4(j, x);
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      if (x[c] > -INFINITY) {   // (-inf, and the columns past V, weigh nothing and are never multiplied)
-        const float av = (x[c] - mx) / T;
-        const float e = expf(av);
-        z += e;
-        s1 += e * av;
-        if (want_first && x[c] == mx) first = min(first, 4 * j + c);
-      }
-    }
-  }
-  z = block_sum(z, sh);
-  s1 = block_sum(s1, sh);
-  const float logz = logf(z);
-  const float H = logz - s1 / z;
-  if (want_first) first = block_min_int(first, sh);
+  const float mx = row_stage_max(row, srow, sh);
+  if (!(mx > -INFINITY)) return leave();   // no finite entry (workgroup-uniform): the row is left as it is
+  // ---- 2. the tempered normaliser and the entropy over the finite entries; kinds 3 and 4: the lowest-index maximum -------------
+  const RowSums sums = row_tempered_sums<STAGED, true>(row, mx, T, a.kind >= 3, sh);
+  const float z = sums.z, logz = logf(z), H = logz - sums.s1 / z;
+  const int first = sums.first;
   // ---- 3. the cut ------------------------------------------------------------------------------------------------------------
   // kinds 2 to 4: kept <=> a_v >= thr_a (or v == first); kind 1: kept <=> key > cut_key, or key == cut_key and v <= cut_idx
   float thr_a = -INFINITY;
@@ -168,35 +101,13 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void truncate_rows_kernel(TruncArgs
   }
   // ---- 4. the write pass -------------------------------------------------------------------------------------------------------
   const int kind = a.kind;
-  int nkept = 0;
-  for (int j = threadIdx.x; j < nj; j += SAMPLE_THREADS) {
-    float x[4];
-    row.get4(j, x);
-    bool drop[4];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const int v = 4 * j + c;
-      bool keep = false;
-      if (v < V && x[c] > -INFINITY) {
-        if (kind == 1) {
-          const uint32_t key = typical_key(x[c], mx, T, logz, H);
-          keep = key > cut_key || (key == cut_key && v <= cut_idx);
-        } else {
-          keep = (x[c] - mx) / T >= thr_a || v == first;   // (first stays 0x7fffffff for kind 2)
-        }
-      }
-      drop[c] = !keep;
-      nkept += keep ? 1 : 0;
+  int nkept = row_write_kept(row, g, [&](int v, float x) -> bool {
+    if (kind == 1) {
+      const uint32_t key = typical_key(x, mx, T, logz, H);
+      return key > cut_key || (key == cut_key && v <= cut_idx);
     }
-    if (vec) {
-      *reinterpret_cast<float4*>(g + 4 * j) = make_float4(drop[0] ? -INFINITY : x[0], drop[1] ? -INFINITY : x[1],
-                                                          drop[2] ? -INFINITY : x[2], drop[3] ? -INFINITY : x[3]);
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-        if (4 * j + c < V && drop[c]) g[4 * j + c] = -INFINITY;
-    }
-  }
+    return ((x - mx) / T >= thr_a) | (v == first);   // (first stays 0x7fffffff for kind 2)
+  });
   if (a.kept) {   // (a kernel argument: workgroup-uniform)
     nkept = block_sum_int(nkept, sh);
     if (threadIdx.x == 0) a.kept[r] = nkept;
@@ -204,14 +115,12 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void truncate_rows_kernel(TruncArgs
   if (a.entropy && threadIdx.x == 0) a.entropy[r] = H;
 }
 
-inline bool finite_f(float v) { return v >= -3.402823466e38f && v <= 3.402823466e38f; }   // false for NaN
-
 }  // namespace
 
 int ssc_truncation_check(const ssc_truncation* tr, float temperature, bool* active) {
   *active = false;
   if (!tr || tr->kind < 0 || tr->kind > 4) return SSC_EINVAL;
-  if (!(temperature > 0.f) || !finite_f(temperature)) return SSC_EINVAL;
+  if (!(temperature > 0.f) || !ssc_finite_f(temperature)) return SSC_EINVAL;
   if (tr->kind == 1 || tr->kind == 2) {
     if (!(tr->value > 0.f && tr->value <= 1.f)) return SSC_EINVAL;   // (false for NaN)
   } else if (tr->kind != 0) {
@@ -229,15 +138,7 @@ int ssc_truncation_launch(float* logits, int ld, int rows, int V, const ssc_trun
   a.kind = tr->kind; a.value = tr->value; a.temperature = temperature;
   a.last_pred = last_pred; a.end_index = end_index;
   a.entropy = entropy; a.kept = kept;
-  if (V <= SAMPLE_LDS_MAX_V) {
-    size_t lds;
-    SSC_TRY(sample_row_lds(truncate_rows_kernel<true>, V, &lds));
-    SSC_LAUNCH(truncate_rows_kernel<true>, dim3(rows), dim3(SAMPLE_THREADS), lds, st, a);
-  } else {
-    SSC_LAUNCH(truncate_rows_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
-  }
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
+  return sample_row_launch(truncate_rows_kernel<true>, truncate_rows_kernel<false>, V, rows, st, a);
 }
 
 extern "C" int ssc_truncate_rows(float* logits, int ld, int rows, int V, const ssc_truncation* tr, float temperature,
