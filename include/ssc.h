@@ -1641,6 +1641,68 @@ int ssc_decode_sample_mirostat(const ssc_model_cfg* cfg, const ssc_params* p, co
                                void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Arithmetic sampling for the word samplers (Vilnis et al., ICML 2023, "Arithmetic Sampling: Parallel Diverse Decoding for Large
+ * Language Models"): every caption decodes along a CODE POINT in [0, 1) by inverse CDF in vocabulary order, the code renormalised
+ * into the chosen word's interval after every step.  Each caption is on its own an exact draw from the sampler's distribution; the
+ * N codes of an image form a randomly shifted lattice, so the set is stratified - fewer repeated captions, lower-variance estimates
+ * over the N samples - while the rows stay independent of each other.  It replaces only the DRAW of the sampled decode: every edit
+ * in front of it (guide, contrast, logit rules, truncation, the Mirostat cut) works as before; ssc_sampler_desc is read as the
+ * samplers read it, except the seed, which only ssc_arith_codes uses; ssc_version() stays 4.  Like Mirostat it carries one value
+ * per row from step to step.  A code is a uint64 c, meaning c / 2^64.  The arithmetic that decides a word is exact integer
+ * arithmetic, so device and a host restatement (tests/arithref.py) agree bit for bit.
+ * For a live row x[0 .. V), as it arrives behind all edits, with the sampler s (kind, top_k, top_p, temperature T):
+ *   1. mx, the untempered log-sum-exp lse and the top-k / top-p cut are formed exactly as ssc_sample_rows forms them: the kept set
+ *      is the set ssc_sample_rows keeps.
+ *   2. The MASS of a kept entry is w_v = llrintf(expf((x_v - mx) / T) * 2^40) in fp32, that of a cut or -inf entry 0; the top entry
+ *      has w = 2^40 exactly.  W = sum_v w_v in 64-bit integers, which does not depend on the summation order.  An entry whose mass
+ *      rounds to 0 - a probability below 2^-41 of the top word's - CANNOT BE DRAWN.
+ *   3. With (t, lo) the high and low 64 bits of the 128-bit product c * W, the token is the unique v, in vocabulary order, with
+ *      cum(v) <= t < cum(v) + w_v, cum(v) = sum_{u < v} w_u.
+ *   4. The new code is c' = floor(((t - cum(v)) * 2^64 + lo) / w_v), below 2^64 because t - cum(v) < w_v.
+ *   5. The returned log-prob is the untempered x_v - lse, as for ssc_sample_rows; row_lp (or NULL) accumulates it.
+ * Rows that pass through, with c' = c: a row whose last token is END (last_pred[r] == end_index) emits end_index at log-prob 0 and
+ * its logits are not read; a row with W == 0 (no finite entry) yields what ssc_sample_rows yields for it - the lowest-index kept
+ * entry, log-prob x_v - lse.  mass_out ((rows, V) int64, or NULL; for tests and diagnostics, like probs_out) receives the w_v - for
+ * an ended row 2^40 at end_index and 0 elsewhere.  code_out may be code_in.  NaN and +inf are the caller's error (the call still
+ * ends and stays inside its rows): a mass that is no positive number counts as 0, every trip count depends on V alone, every index
+ * is a loop index; if no lane claims t, the lowest-index maximum is emitted and the code passes through.  One workgroup per row,
+ * the row staged in LDS for V <= 32768 and walked in global memory above; the walk of step 3 is a 64-bit prefix scan in tiles in
+ * vocabulary order, the division of step 4 a shift-subtract loop of one thread.  No float atomics, no order-dependent float
+ * reduction decides anything: two calls on equal inputs are bit-identical.
+ * The codes of a call (ssc_arith_codes): for image i with N = n_samples, row i N + j starts at c = u_i + floor(j 2^64 / N) (mod 2^64);
+ * u_i = word 0 + 2^32 * word 1 of Philox4x32-10 with key = seed and counter (0, 0, i, 0x41524954).  The last counter word ("ARIT")
+ * is used by no other stream of the library: the word draws and the stochastic beam use 0, the scheduled-sampling coin 1, the
+ * sampled-node beam its draw index 0 .. 31.
+ * SSC_EINVAL before any launch: a NULL logits, code_in, pred_out, lp_out or code_out; rows < 0, V < 1, ld < V; a sampler the word
+ * samplers refuse; end_index outside [0, V) with a last_pred; for ssc_arith_codes a NULL code_out, nimg < 0, n_samples outside
+ * [1, 2^24] or more than 2^31 rows.  SSC_EALIGN: a code (or mass) block that is no multiple of 8.  rows == 0 (nimg == 0): SSC_OK
+ * with no launch.
+ * ---------------------------------------------------------------------------------------------- */
+int ssc_arith_codes(uint64_t seed, int nimg, int n_samples, uint64_t* code_out, void* stream);
+int ssc_arith_rows(const float* logits, int ld, int rows, int V, const ssc_sampler_desc* s, const uint64_t* code_in,
+                   const int64_t* last_pred, float* row_lp, int end_index, int64_t* pred_out, float* lp_out, uint64_t* code_out,
+                   int64_t* mass_out, void* stream);
+/* Arithmetic sampling in the sampled decode: the descriptor travels BESIDE ssc_sample_opts, as ssc_mirostat does. */
+typedef struct {
+  int mode;         /* 0: off (no other field is read); 1: the call fills slab 0 with ssc_arith_codes(s->seed, nimg, n_samples);
+                       2: the caller has filled slab 0 */
+  uint64_t* code;   /* (max_steps + 1, B), required when on: step t draws with slab t and writes slab t + 1 */
+} ssc_arith;
+/* ssc_decode_sample_mirostat_workspace_bytes / ssc_decode_sample_mirostat with one argument more.  With a NULL or a->mode == 0 they
+ * ARE those calls: the same launches, the same bits, the same workspace size.  Otherwise the draw launch of every step is
+ * ssc_arith_rows' kernel - last_pred the previous step's words, row_lp the running caption log-probs -, carrying the early-stop
+ * protocol of the sampler's own draw kernel.  Everything else is untouched: skip_dead, early_stop, ctl / host_flag, the pacer, the
+ * attention trace, the guide, the contrast with its amateur, the rules, the truncation, the Mirostat cut and update, d->start.
+ * Under d->start (a prompt) the codes start at the continuation's first step.  Slabs of steps never queued (early_stop) are not
+ * written.  The workspace does not grow.  SSC_EINVAL before any launch: what ssc_decode_sample_mirostat refuses; a mode outside
+ * 0 .. 2; with mode 1 or 2 a NULL code.  SSC_EALIGN: code no multiple of 8. */
+size_t ssc_decode_sample_arith_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d, const ssc_sample_opts* opts,
+                                               const ssc_mirostat* m, const ssc_arith* a);
+int ssc_decode_sample_arith(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
+                            const ssc_sample_opts* opts, const ssc_mirostat* m, const ssc_arith* a, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Prompted decoding: start the one-call decodes from a forced prefix ("a happy ...").  ssc_decode_prime teacher-forces the prefix
  * on the B = nimg * n_samples rows of a call - the loop of ssc_decode_score, leaving STATES instead of only scores -, its outputs
  * are an ssc_start_state for any search or sampled decode over the same B entries, and ssc_prefix_join puts prefix and

@@ -121,6 +121,14 @@ parser.add_argument("--mirostat", default="",
 parser.add_argument("--mirostat-output", default="",
                     help="with an active Mirostat: write per returned caption the threshold mu and the drawn word's surprise at every "
                          "word, in bits (JSON: image_id, caption, mu, surprise)")
+parser.add_argument("--arithmetic", action="store_true",
+                    help="arithmetic sampling for word sampling (default: MODEL.SAMPLER_ARITHMETIC): every word is drawn by inverse CDF "
+                         "along a code point per caption, the codes of an image a randomly shifted lattice - the captions of an image "
+                         "are stratified instead of independent.  Needs MODEL.DECODE_SAMPLER multinomial / top-k / top-p without "
+                         "SAMPLED_BEAM_SEARCH")
+parser.add_argument("--arithmetic-share-latent", action="store_true",
+                    help="with arithmetic sampling: the latent samples of an image share the noise of its first one, so its captions "
+                         "differ by their codes alone (default: MODEL.SAMPLER_ARITHMETIC_SHARE_LATENT)")
 parser.add_argument("--contrast", default="",
                     help="contrastive decoding for word sampling: ALPHA[:BETA], e.g. --contrast 1:0.1 (default: MODEL.CONTRAST_ALPHA / "
                          "CONTRAST_BETA; ALPHA 0 = off) - an amateur stream is decoded in lock-step and every step's logits become "
@@ -263,6 +271,25 @@ def check_mirostat_args(_A, model_cfg=None):
     return m
 
 
+def check_arithmetic_args(_A, model_cfg=None):
+    """--arithmetic / --arithmetic-share-latent, checked before anything is loaded -> its sampling.Arithmetic, or None without the
+    flag; with model_cfg (the MODEL node) the keys stand in for a missing flag and it is checked that the run samples words."""
+    on = _A.arithmetic or (model_cfg is not None and bool(model_cfg.SAMPLER_ARITHMETIC))
+    share = _A.arithmetic_share_latent or (model_cfg is not None and bool(model_cfg.SAMPLER_ARITHMETIC_SHARE_LATENT))
+    if not on:
+        if _A.arithmetic_share_latent and model_cfg is not None:   # (before the config is read the key may still turn it on)
+            raise SystemExit("--arithmetic-share-latent needs arithmetic sampling: --arithmetic or MODEL.SAMPLER_ARITHMETIC")
+        return None
+    if _A.ensemble_checkpoints:
+        raise SystemExit("--arithmetic is not available with --ensemble-checkpoints: an ensemble runs the beam search only")
+    if model_cfg is not None:
+        kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+        if kind not in sampling.KINDS or model_cfg.SAMPLED_BEAM_SEARCH or model_cfg.STOCHASTIC_BEAM_SEARCH:
+            raise SystemExit("--arithmetic needs a word sampler: MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                             f"MODEL.SAMPLED_BEAM_SEARCH / STOCHASTIC_BEAM_SEARCH, got {model_cfg.DECODE_SAMPLER!r}")
+    return sampling.Arithmetic("lattice", share_latent=bool(share))
+
+
 def check_contrast_args(_A, model_cfg=None):
     """--contrast ALPHA[:BETA] / --contrast-amateur / --contrast-checkpoint / --contrast-output, checked before anything is loaded
     -> (alpha, beta, amateur kind or None) of the flags, None for what a flag does not give; with model_cfg (the MODEL node) the
@@ -384,11 +411,13 @@ def main():
     check_truncation_args(_A)
     check_contrast_args(_A)
     check_mirostat_args(_A)
+    check_arithmetic_args(_A)
     _C = Config(_A.config, _A.config_override)
     check_word_bias_args(_A, _C.MODEL)
     truncation = check_truncation_args(_A, _C.MODEL)
     contrast_args = check_contrast_args(_A, _C.MODEL)
     mirostat = check_mirostat_args(_A, _C.MODEL)   # --mirostat, else MODEL.SAMPLER_MIROSTAT_TAU / SAMPLER_MIROSTAT_ETA
+    arithmetic = check_arithmetic_args(_A, _C.MODEL)   # --arithmetic, else MODEL.SAMPLER_ARITHMETIC / SAMPLER_ARITHMETIC_SHARE_LATENT
     prompt = _A.prefix or ("" if prompts is not None else str(_C.MODEL.DECODE_PREFIX).strip())
     if (prompt or prompts is not None) and not _A.prefix and not _A.prefix_json:   # (MODEL.DECODE_PREFIX: the flags' refusals apply)
         _A.prefix = prompt
@@ -476,6 +505,7 @@ def main():
     divergences = []   # --contrast-output: one record per returned caption
     miro_traces = []   # --mirostat-output: one record per returned caption
     model.mirostat(None)   # (the run's own decode below is handed the Mirostat itself)
+    model.arithmetic(None)
     n_z = max(1, _C.MODEL.N_Z_SAMPLES)
     beam = _C.MODEL.BEAM_SIZE
     if sampler is not None and (_A.constraints_json or _A.boxes_json):
@@ -606,6 +636,7 @@ def main():
                                      **({"truncation": truncation} if truncation is not None else {}),
                                      **({"contrast": contrast, "contrast_stats": True} if contrast is not None else {}),
                                      **({"mirostat": mirostat, "mirostat_stats": bool(_A.mirostat_output)} if mirostat is not None else {}),
+                                     **({"arithmetic": arithmetic} if arithmetic is not None else {}),
                                      **pkw)
                 pred = out[0]
                 if mirostat is not None and _A.mirostat_output:

@@ -14,7 +14,8 @@
 // The edits of the raw logits in front of the draw - the logit rules (logit_rules.hip) and the truncation (truncation.hip) - are launches
 // of their own between a step's decode step and its draw (ssc_decode_sample_opts); the draw itself does not know of them.  Mirostat
 // (mirostat.hip) adds a cut in front of and an update behind the draw, with a value per row carried between the steps
-// (ssc_decode_sample_mirostat).
+// (ssc_decode_sample_mirostat).  Arithmetic sampling (arith.hip) replaces the draw's launch by its own, with a code per row carried
+// between the steps (ssc_decode_sample_arith).
 // ssc_decode_sample's host loop is built from the shared driver of decode_loop.h ("the one-call decodes' host driver").
 #include <math.h>
 
@@ -75,25 +76,8 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_rows_kernel(SampleArgs 
     a.lp_out[r] = lp;
     if (a.row_lp) a.row_lp[r] += lp;
   }
-  // early stop (the protocol of ssc_beam_desc.ctl, with the step as the column index): count the rows that have not ended; the last
-  // workgroup of the step notes an all-ended step in ctl[0] / host_flag[0] and its own completion in host_flag[1]
-  if (a.ctl && threadIdx.x == 0) {
-    int* cnt = a.ctl + 2 + a.step;
-    int* ticket = a.ctl + 2 + a.max_steps + a.step;
-    if (tok != a.end_index) atomicAdd(cnt, 1);
-    __threadfence();
-    const int done = atomicAdd(ticket, 1);
-    if (done == (int)gridDim.x - 1) {
-      if (!stopped) {
-        __threadfence();
-        if (atomicAdd(cnt, 0) == 0) {
-          atomicMin(a.ctl, a.step + 1);
-          if (a.host_flag) __hip_atomic_store(a.host_flag, a.step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-      }
-      if (a.host_flag) __hip_atomic_store(a.host_flag + 1, a.step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  // early stop: sample_step_done of sample_draw.h, shared with the arithmetic draw (arith.hip)
+  if (a.ctl && threadIdx.x == 0) sample_step_done(a.ctl, a.max_steps, a.host_flag, a.step, stopped, tok != a.end_index);
 }
 
 int sample_launch(SampleArgs a, int rows, hipStream_t st) {
@@ -240,10 +224,12 @@ extern "C" int ssc_decode_sample(const ssc_model_cfg* cfg, const ssc_params* p, 
 // The sampled decode under its options (include/ssc.h, ssc_sample_opts).  Per step: the expert's decode step (its z block from slab t
 // of the guide), the amateur's decode step, the contrast, the logit rules, the truncation, the draw; step t's statistics go to slab t
 // of contrast->kept / ->divergence and trunc->entropy / ->kept.  Under an active Mirostat (m, may be null) the cut follows the
-// truncation with slab t of m->mu and the update follows the draw, slab t -> slab t + 1.
+// truncation with slab t of m->mu and the update follows the draw, slab t -> slab t + 1.  Under an active arithmetic descriptor (ar,
+// may be null) the draw of step t is ssc_arith_rows with slab t of ar->code, writing slab t + 1.
 namespace {
 int sample_decode(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d, const ssc_sampler_desc* s,
-                  const ssc_sample_opts* opts, const ssc_mirostat* m, void* workspace, size_t workspace_bytes, void* stream) {
+                  const ssc_sample_opts* opts, const ssc_mirostat* m, const ssc_arith* ar, void* workspace, size_t workspace_bytes,
+                  void* stream) {
   ssc_sample_opts o;
   if (!sample_opts_read(opts, &o)) return SSC_EINVAL;
   const ssc_latent_guide* guide = o.guide;
@@ -277,6 +263,8 @@ int sample_decode(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_searc
   if (trunc) SSC_TRY(ssc_truncation_check(trunc, s->temperature, &cut));
   bool miro = false;
   SSC_TRY(ssc_mirostat_check(m, s->temperature, &miro));
+  bool arith = false;
+  SSC_TRY(ssc_arith_check(ar, &arith));
   const SampleLayout l = sample_layout(cfg, d);
   AmateurLayout am{};
   size_t total = amateur ? contrast_layout(cfg, d, l, &am) : l.total;
@@ -306,6 +294,7 @@ int sample_decode(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_searc
   if (amateur) SSC_TRY(ssc_decode_start_states(contrast->start, am.states, W, 1, B, st));
   float* norm = miro ? (float*)(W + norm_at) : nullptr;
   if (miro) SSC_TRY(ssc_mirostat_fill(m->mu, B, m->mu0, st));   // (slab 0; under d->start too: the control starts at the continuation)
+  if (arith && ar->mode == 1) SSC_TRY(ssc_arith_codes_launch(s->seed, d->nimg, d->n_samples, ar->code, st));   // (slab 0, likewise)
 
   // the steps take the form the beam-1 search gives them (ssc_decode_search with S = beam = 1): same tables, same parent list
   const bool want_table = ssc_att_table_wanted(d->R, B, d->n_samples);
@@ -352,11 +341,18 @@ int sample_decode(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_searc
       SSC_TRY(ssc_truncation_launch(logits, V, B, V, trunc, s->temperature, trunc->entropy ? trunc->entropy + (size_t)t * B : nullptr,
                                     trunc->kept ? trunc->kept + (size_t)t * B : nullptr, last, d->end_index, st));
     a.step = t; a.last_pred = last; a.pred_out = preds + (size_t)t * B;
-    if (!miro) return sample_launch(a, B, st);
+    // the draw: the sampler's own, or the arithmetic one along the rows' codes, slab t -> slab t + 1
+    auto draw = [&]() -> int {
+      if (!arith) return sample_launch(a, B, st);
+      uint64_t* code = ar->code + (size_t)t * B;
+      return ssc_arith_rows_launch(logits, V, B, V, s, code, last, lp, d->end_index, a.pred_out, steplp, code + B, nullptr, t, a.ctl,
+                                   a.max_steps, a.host_flag, st);
+    };
+    if (!miro) return draw();
     float* mu = m->mu + (size_t)t * B;
     SSC_TRY(ssc_mirostat_rows_launch(logits, V, B, V, s->temperature, mu, last, d->end_index, m->kept ? m->kept + (size_t)t * B : nullptr,
                                      norm, st));
-    SSC_TRY(sample_launch(a, B, st));
+    SSC_TRY(draw());
     return ssc_mirostat_update_launch(logits, V, B, V, s->temperature, m->tau, m->eta, norm, a.pred_out, last, d->end_index, mu, mu + B,
                                       m->surprise ? m->surprise + (size_t)t * B : nullptr, st);
   };
@@ -392,11 +388,24 @@ int sample_decode(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_searc
 extern "C" int ssc_decode_sample_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
                                       const ssc_sampler_desc* s, const ssc_sample_opts* opts, void* workspace, size_t workspace_bytes,
                                       void* stream) {
-  return sample_decode(cfg, p, d, s, opts, nullptr, workspace, workspace_bytes, stream);
+  return sample_decode(cfg, p, d, s, opts, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ssc_decode_sample_mirostat(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
                                           const ssc_sampler_desc* s, const ssc_sample_opts* opts, const ssc_mirostat* m, void* workspace,
                                           size_t workspace_bytes, void* stream) {
-  return sample_decode(cfg, p, d, s, opts, m, workspace, workspace_bytes, stream);
+  return sample_decode(cfg, p, d, s, opts, m, nullptr, workspace, workspace_bytes, stream);
+}
+
+// the arithmetic draw needs no workspace of its own: its codes live in the caller's block
+extern "C" size_t ssc_decode_sample_arith_workspace_bytes(const ssc_model_cfg* cfg, const ssc_search_desc* d,
+                                                          const ssc_sample_opts* opts, const ssc_mirostat* m, const ssc_arith* a) {
+  (void)a;
+  return ssc_decode_sample_mirostat_workspace_bytes(cfg, d, opts, m);
+}
+
+extern "C" int ssc_decode_sample_arith(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_search_desc* d,
+                                       const ssc_sampler_desc* s, const ssc_sample_opts* opts, const ssc_mirostat* m, const ssc_arith* a,
+                                       void* workspace, size_t workspace_bytes, void* stream) {
+  return sample_decode(cfg, p, d, s, opts, m, a, workspace, workspace_bytes, stream);
 }

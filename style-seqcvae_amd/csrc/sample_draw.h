@@ -21,6 +21,27 @@ inline bool sampler_ok(const ssc_sampler_desc* s, int V) {
   return false;
 }
 
+// The early stop of a sampled decode's draw kernels (the protocol of ssc_beam_desc.ctl, with the step as the column index), called
+// by ONE thread per workgroup behind the row's writes: count the rows that have not ended (`live`); the last workgroup of the step
+// notes an all-ended step in ctl[0] / host_flag[0] and its own completion in host_flag[1].  stopped: ctl[0] <= step at entry.
+__device__ __forceinline__ void sample_step_done(int* ctl, int max_steps, int* host_flag, int step, bool stopped, bool live) {
+  int* cnt = ctl + 2 + step;
+  int* ticket = ctl + 2 + max_steps + step;
+  if (live) atomicAdd(cnt, 1);
+  __threadfence();
+  const int done = atomicAdd(ticket, 1);
+  if (done == (int)gridDim.x - 1) {
+    if (!stopped) {
+      __threadfence();
+      if (atomicAdd(cnt, 0) == 0) {
+        atomicMin(ctl, step + 1);
+        if (host_flag) __hip_atomic_store(host_flag, step + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+    }
+    if (host_flag) __hip_atomic_store(host_flag + 1, step, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
 struct SampleDraw {
   int tok;            // the drawn token (-1: no entry of the row is comparable - every logit NaN)
   float lp;           // its untempered log-probability

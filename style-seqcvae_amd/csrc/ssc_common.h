@@ -241,6 +241,15 @@ int ssc_mirostat_rows_launch(float* logits, int ld, int rows, int V, float tempe
 int ssc_mirostat_update_launch(const float* logits, int ld, int rows, int V, float temperature, float tau, float eta, const float* norm,
                                const int64_t* pred, const int64_t* last_pred, int end_index, const float* mu_in, float* mu_out,
                                float* surprise, hipStream_t st);
+// Arithmetic sampling for the word samplers (arith.hip, include/ssc.h: ssc_arith).  ssc_arith_check: the refusals that depend on the
+// descriptor alone (SSC_OK with *active = a && mode != 0); ssc_arith_codes_launch: the lattice of a call; ssc_arith_rows_launch: the
+// draw of one step from checked arguments, with the early-stop words of the decode (ctl null: none) - what ssc_decode_sample_arith
+// issues per step in place of the sampler's draw.
+int ssc_arith_check(const ssc_arith* a, bool* active);
+int ssc_arith_codes_launch(uint64_t seed, int nimg, int n_samples, uint64_t* code_out, hipStream_t st);
+int ssc_arith_rows_launch(const float* logits, int ld, int rows, int V, const ssc_sampler_desc* s, const uint64_t* code_in,
+                          const int64_t* last_pred, float* row_lp, int end_index, int64_t* pred_out, float* lp_out, uint64_t* code_out,
+                          int64_t* mass_out, int step, int* ctl, int max_steps, int* host_flag, hipStream_t st);
 // Contrastive decoding for the word samplers (contrast.hip, include/ssc.h: ssc_contrast_rows, ssc_contrast).  ssc_contrast_check: the
 // refusals that depend on the knobs and the statistics pointers alone (SSC_OK with *active = alpha != 0 || beta != 0);
 // ssc_contrast_launch: the edit of one step from checked knobs - what ssc_decode_sample_opts issues per step for its `contrast`.

@@ -1,5 +1,7 @@
 // Counter-based Philox4x32-10 noise shared by the device samplers (sample.hip: word sampling, sbs.hip: stochastic beam search).
 // Counter (v / 4, step, row, 0), key = the 64-bit seed, word v % 4 for token v; tests/samplerref.py restates it on the host.
+// The last counter word names the stream: 0 the word draws, 1 the scheduled-sampling coin, 0 .. 31 the sampled-node beam's draw
+// index, 0x41524954 the lattice shifts of arithmetic sampling (arith.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

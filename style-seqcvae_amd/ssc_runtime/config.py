@@ -115,6 +115,12 @@ def _defaults() -> dict:
             # cut behind the truncation, and after each draw mu moves by SAMPLER_MIROSTAT_ETA times the error; mu starts at
             # 2 TAU.  Needs DECODE_SAMPLER multinomial / top-k / top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
             "SAMPLER_MIROSTAT_TAU": 0.0, "SAMPLER_MIROSTAT_ETA": 0.1,
+            # arithmetic sampling for the word samplers (ssc_runtime/sampling.py Arithmetic; ssc_arith): the draw of every step is
+            # made by inverse CDF along a code point per caption, the codes of an image a randomly shifted lattice - the captions of
+            # an image are stratified instead of independent.  SAMPLER_ARITHMETIC_SHARE_LATENT: the samples of an image also share
+            # the latent noise of its first sample, so they differ by their codes alone.  Needs DECODE_SAMPLER multinomial / top-k /
+            # top-p with SAMPLED_ and STOCHASTIC_BEAM_SEARCH False
+            "SAMPLER_ARITHMETIC": False, "SAMPLER_ARITHMETIC_SHARE_LATENT": False,
             # contrastive decoding of the word samplers (ssc_runtime/contrast.py Contrast; ssc_contrast): an amateur stream is decoded
             # in lock-step with the normal one and every step's logits become lp + CONTRAST_ALPHA (lp - lp_amateur) on the words
             # whose probability is at least CONTRAST_BETA times the top word's.  CONTRAST_ALPHA 0 (default): off.  CONTRAST_AMATEUR:
@@ -287,6 +293,11 @@ class Config(object):
             mv = getattr(m, key)
             if isinstance(mv, bool) or not isinstance(mv, (int, float)) or not 0 <= mv < float("inf"):   # (false for NaN)
                 raise ValueError(f"MODEL.{key} must be {what}; found {mv!r}")
+        for key in ("SAMPLER_ARITHMETIC", "SAMPLER_ARITHMETIC_SHARE_LATENT"):
+            if not isinstance(getattr(m, key), bool):
+                raise ValueError(f"MODEL.{key} must be True or False; found {getattr(m, key)!r}")
+        if m.SAMPLER_ARITHMETIC_SHARE_LATENT and not m.SAMPLER_ARITHMETIC:
+            raise ValueError("MODEL.SAMPLER_ARITHMETIC_SHARE_LATENT needs MODEL.SAMPLER_ARITHMETIC True")
         for key, ok, what in (("CONTRAST_ALPHA", lambda v: 0 <= v < float("inf"), "a finite number >= 0 (0 = off)"),
                               ("CONTRAST_BETA", lambda v: 0 <= v < 1, "in [0, 1)"), ("CONTRAST_NOISE", lambda v: 0 < v <= 1, "in (0, 1]")):
             cv = getattr(m, key)

@@ -363,7 +363,7 @@ class DecodeEngine:
                eps0: torch.Tensor, eps: Optional[torch.Tensor], sampler, seed: int, early_stop: bool = True,
                attention: bool = False, guide=None, logit_rules=None, skip_dead: bool = True, start=None, truncation=None,
                truncation_stats: bool = False, contrast=None, contrast_stats: bool = False, mirostat=None,
-               mirostat_stats: bool = False):
+               mirostat_stats: bool = False, arithmetic=None, arithmetic_codes: bool = False):
         """The whole sampled decode of one call in ONE library call (ssc_decode_sample_opts): ctx.nimg images x n_samples latent samples,
         one row per batch entry b = (image, sample), one word per row and step drawn by `sampler` (ssc_runtime.sampling) with the
         64-bit `seed`.  sentiment (B) or None; eps0 (B, Z), eps (max_steps - 1, B, Z): the noise of every step.
@@ -389,8 +389,15 @@ class DecodeEngine:
         result is followed - behind the other statistics - by (mu (B, steps) float32 - the threshold step t cut with -, surprise
         (B, steps) float32 - the drawn word's surprise under the tempered distribution in front of the cut -, kept (B, steps) int32),
         mu and surprise in the object's unit; surprise and kept are zero for ended rows, all three in the columns past the stop.
+        arithmetic: a sampling.Arithmetic, or None - the draw of every step is made by inverse CDF along a code point per row
+        (ssc_decode_sample_arith), the codes a randomly shifted lattice per image that `seed` decides, or the object's own; None
+        issues the call of before.  arithmetic_codes=True (with an arithmetic): the result is followed - behind the other
+        statistics - by the codes (B, steps + 1) int64 holding the uint64 bits: column t is the code step t drew with, column
+        t + 1 the code it left; zero past the stop.
         skip_dead (default on): ended rows are not stepped; the captions do not depend on it."""
         _start_check(start, guide)
+        if arithmetic_codes and arithmetic is None:
+            raise ValueError("DecodeEngine.sample: arithmetic_codes needs an arithmetic")
         if mirostat is not None and not mirostat.active:
             mirostat = None
         if mirostat_stats and mirostat is None:
@@ -445,6 +452,14 @@ class DecodeEngine:
             call = lambda p, sd, ws: self.lib.ssc_decode_sample_mirostat(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
                                                                          C.byref(opts), C.byref(md), *ws)
             workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_mirostat_workspace_bytes(cfg, sd, C.byref(opts), C.byref(md))
+        if arithmetic is not None:   # the descriptor beside the opts and Mirostat's (NULL when off); code (max_steps + 1, B)
+            acode = torch.zeros(max_steps + 1, B, dtype=torch.int64, device=self.device)
+            ad = arithmetic.desc(acode)
+            mref = C.byref(md) if mirostat is not None else None
+            aref = C.byref(ad) if ad is not None else None
+            call = lambda p, sd, ws: self.lib.ssc_decode_sample_arith(C.byref(self._cfg), C.byref(p), C.byref(sd), C.byref(sdesc),
+                                                                      C.byref(opts), mref, aref, *ws)
+            workspace_bytes = lambda cfg, sd: self.lib.ssc_decode_sample_arith_workspace_bytes(cfg, sd, C.byref(opts), mref, aref)
         out = self._one_call(ctx, sentiment, n_samples, 1, 1, 1, max_steps, end_index, eps0, eps, early_stop, skip_dead,
                              (ctx.nimg * n_samples,), workspace_bytes, call, attention=attention, start=start)
         if truncation_stats:
@@ -457,6 +472,9 @@ class DecodeEngine:
             steps = out[0].size(-1)
             out = tuple(out) + ((mirostat.from_nats(mmu[:steps].t().contiguous()), mirostat.from_nats(msur[:steps].t().contiguous()),
                                  mkept[:steps].t().contiguous()),)
+        if arithmetic_codes:
+            steps = out[0].size(-1)
+            out = tuple(out) + (acode[:steps + 1].t().contiguous(),)
         return out
 
     def score(self, ctx: ImageContext, sentiment: Optional[torch.Tensor], targets: torch.Tensor, n_samples: int, end_index: int,

@@ -28,7 +28,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                    sample_seed: Optional[int] = None, sampled_beam: bool = False, diverse_beam=None, return_groups: bool = False,
                    rules=None, attention: Optional[str] = None, guide=None, logit_rules=None, prefix=None,
                    prefix_eps: Optional[torch.Tensor] = None, truncation=None, contrast=None, contrast_stats: bool = False, mirostat=None,
-                   mirostat_stats: bool = False):
+                   mirostat_stats: bool = False, arithmetic=None):
     """feats (nimg,R,F), sentiment (nimg,) or None -> predictions (nimg, n_samples, steps) int64 on device.
     dec: a DecodeEngine, or an EnsembleDecodeEngine (ssc_runtime.decode) - the beam search, plain or constrained (fsm), then runs
     over the ensemble's members in one call; the sampled / stochastic / diverse / rules decodes and attention traces belong to a
@@ -88,6 +88,12 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     other one, NotImplementedError with an ensemble.  None or an inactive one: the call without it.  Composes with logit_rules,
     truncation, contrast, guide, prefix (the control starts at the continuation) and attention.  mirostat_stats=True: the result is
     followed - behind the contrast's statistics - by (mu, surprise, kept) of shape (nimg, n_samples, steps), in the object's unit.
+    arithmetic: a sampling.Arithmetic - with a word sampler every step's draw is made by inverse CDF along a code point per caption
+    (DecodeEngine.sample(arithmetic=)), the codes of an image a randomly shifted lattice: the n_samples captions of an image are
+    stratified, each still an exact draw.  With share_latent=True all samples of an image are given the noise (eps0, eps and a
+    prefix's) of its sample 0 - contiguous copies made here - and differ by their codes alone.  ValueError naming the decoder with
+    any decoder but a word sampler, NotImplementedError with an ensemble.  None: the call without it.  Composes with logit_rules,
+    truncation, contrast, mirostat, guide, prefix (the codes start at the continuation) and attention.
     prefix: a DecodePrefix (ssc_runtime.prefix) with one row per image - or per (image, sample) entry -, or None.  With it every
     caption starts with its image's prompt: the prompt is teacher-forced on the nimg * n_samples rows (DecodeEngine.prime), whichever
     decoder was chosen continues from there (start=) and the call returns the FULL captions (nimg, n_samples, Lp + steps) - the
@@ -142,6 +148,17 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         if other is not None:
             raise ValueError(f"Mirostat belongs to the word samplers: mirostat= needs a multinomial / top-k / top-p sampler, "
                              f"not {other}")
+    if arithmetic is not None:
+        if isinstance(dec, EnsembleDecodeEngine):
+            raise NotImplementedError("arithmetic sampling (arithmetic=) is not implemented for an ensemble (EnsembleDecodeEngine)")
+        other = ("the beam search under decode rules (rules)" if rules is not None and rules.active else
+                 "the diverse beam search (diverse_beam)" if diverse_beam is not None else
+                 "the sampled-node beam search (sampled_beam)" if sampled_beam else
+                 "the stochastic beam search (GumbelSampler)" if sampler is not None and sampler.beam_search else
+                 "the beam search" if sampler is None else None)
+        if other is not None:
+            raise ValueError(f"arithmetic sampling belongs to the word samplers: arithmetic= needs a multinomial / top-k / top-p "
+                             f"sampler, not {other}")
     if contrast is not None and not contrast.active:
         contrast = None
     if contrast_stats and contrast is None:
@@ -235,6 +252,15 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
     if prefix is not None and prefix_eps is None and eps_steps is not None:
         pseed = int(torch.randint(0, 2 ** 62, (1,)).item())   # (the prefix noise of a call whose search noise is the caller's)
 
+    share = arithmetic is not None and arithmetic.share_latent
+
+    def shared(x):
+        """noise (..., B, Z) -> every sample of an image given the noise of its sample 0 (share_latent), a contiguous copy"""
+        if not share:
+            return x
+        lead = x.shape[:-2]
+        return x.reshape(*lead, nimg, n_samples, d.Z)[..., :1, :].expand(*lead, nimg, n_samples, d.Z).reshape(*lead, B, d.Z).contiguous()
+
     def prime(gen):
         """-> the start= of this call's decoder: {} without a prefix"""
         if prefix is None:
@@ -253,6 +279,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
                     gen = torch.Generator(device=dev)
                     gen.manual_seed(pseed)
                 peps = torch.randn(ids.size(1), B, d.Z, device=dev, generator=gen)
+            peps = shared(peps)
             primed["ids"] = ids.to(dev)
             primed["start"] = dec.prime(ctx, sent_b, n_samples, primed["ids"], boundary_index, peps)
             if contrast is not None and contrast.steps_amateur:   # the amateur reads the same prompt under the same noise
@@ -278,6 +305,8 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
         rkw["mirostat"] = mirostat
         if mirostat_stats:
             rkw["mirostat_stats"] = True
+    if arithmetic is not None:
+        rkw["arithmetic"] = arithmetic
     stats = {}
     if contrast is not None:
         cgen = torch.Generator(device=dev)
@@ -328,6 +357,7 @@ def diverse_decode(dec: Union[DecodeEngine, EnsembleDecodeEngine], feats: torch.
             calls["k"] = beams.size(-1)
             return beams.view(B, 1, beam, -1), lps.view(B, 1, beam), rec
         if sampler is not None:
+            eps0, eps = shared(eps0), shared(eps)
             pred, lps, *rec = dec.sample(ctx, sent_b, n_samples, max_steps, boundary_index, eps0, eps, sampler,
                                          seed if sample_seed is None else sample_seed, early_stop=early_stop, attention=want_attn,
                                          **gkw, **rkw, **skw)

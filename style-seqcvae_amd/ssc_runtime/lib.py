@@ -260,6 +260,11 @@ class Mirostat(C.Structure):
     _fields_ = [("tau", C.c_float), ("eta", C.c_float), ("mu0", C.c_float), ("mu", vp), ("surprise", vp), ("kept", vp)]
 
 
+class Arith(C.Structure):
+    """ssc_arith: travels beside SampleOpts and Mirostat (ssc_decode_sample_arith); mode 0 is off."""
+    _fields_ = [("mode", C.c_int), ("code", vp)]
+
+
 class EvalRefs(C.Structure):
     _fields_ = [("I", C.c_int), ("nref", C.c_int), ("ntok", C.c_int), ("W", C.c_int), ("ref_offsets", vp), ("tok_offsets", vp),
                 ("tokens", vp), ("style", vp), ("state", vp), ("state_bytes", C.c_size_t)]
@@ -442,6 +447,12 @@ SYMBOLS = {
                                                          C.POINTER(Mirostat)]),
     "ssc_decode_sample_mirostat": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
                                         C.POINTER(SampleOpts), C.POINTER(Mirostat), vp, _sz, vp]),
+    "ssc_arith_codes": (_i, [C.c_uint64, _i, _i, vp, vp]),
+    "ssc_arith_rows": (_i, [vp, _i, _i, _i, C.POINTER(SamplerDesc), vp, vp, vp, _i, vp, vp, vp, vp, vp]),
+    "ssc_decode_sample_arith_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(SearchDesc), C.POINTER(SampleOpts),
+                                                      C.POINTER(Mirostat), C.POINTER(Arith)]),
+    "ssc_decode_sample_arith": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(SearchDesc), C.POINTER(SamplerDesc),
+                                     C.POINTER(SampleOpts), C.POINTER(Mirostat), C.POINTER(Arith), vp, _sz, vp]),
     "ssc_decode_prime_workspace_bytes": (_sz, [C.POINTER(ModelCfg), C.POINTER(PrimeDesc)]),
     "ssc_decode_prime": (_i, [C.POINTER(ModelCfg), C.POINTER(Params), C.POINTER(PrimeDesc), vp, _sz, vp]),
     "ssc_prefix_join": (_i, [vp, vp, _i, vp, vp, _i, vp, vp, _i, _i, _i, vp, vp, vp]),

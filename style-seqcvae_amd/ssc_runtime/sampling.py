@@ -30,6 +30,9 @@ MODEL.SAMPLER_TRUNCATION / SAMPLER_TRUNCATION_VALUE).  The samplers themselves a
 
 Mirostat is the one control with state: a surprise target held by feedback, a cut behind the truncation and an update behind the draw
 (DecodeEngine.sample(mirostat=) / ssc_decode_sample_mirostat, MODEL.SAMPLER_MIROSTAT_TAU / SAMPLER_MIROSTAT_ETA).
+
+Arithmetic replaces the draw itself: every caption decodes along a code point, the codes of an image form a randomly shifted lattice
+(DecodeEngine.sample(arithmetic=) / ssc_decode_sample_arith, MODEL.SAMPLER_ARITHMETIC / SAMPLER_ARITHMETIC_SHARE_LATENT).
 """
 import math
 
@@ -612,6 +615,72 @@ def mirostat_from_config(model_cfg):
     return m
 
 
+class Arithmetic:
+    """Arithmetic sampling for the word samplers (ssc_arith in include/ssc.h; Vilnis et al., ICML 2023): every caption decodes along
+    a code point in [0, 1) by inverse CDF in vocabulary order, the code renormalised into the chosen word's interval after every
+    step (DecodeEngine.sample(arithmetic=) / ssc_decode_sample_arith).  It replaces only the draw: each caption is on its own an
+    exact draw from the sampler's distribution, every edit in front of the draw works as before.
+    codes: "lattice" (the default) - the N codes of an image are a lattice of spacing 1 / N shifted by a random offset per image
+    that the sampler's seed decides (ssc_arith_codes), so the set of an image is stratified -, or a tensor of B = images x samples
+    codes, torch.uint64 (or int64 holding the same bits), code c meaning c / 2^64.
+    share_latent: diverse_decode gives all samples of an image the latent noise of its sample 0, so that the N captions of an image
+    differ by their codes alone (DecodeEngine.sample, which is handed its noise, does not read it)."""
+
+    def __init__(self, codes="lattice", share_latent: bool = False) -> None:
+        import torch
+        if isinstance(codes, str):
+            if codes != "lattice":
+                raise ValueError(f'the arithmetic codes must be "lattice" or a uint64 tensor (B,), got {codes!r}')
+        elif not isinstance(codes, torch.Tensor):
+            raise ValueError(f'the arithmetic codes must be "lattice" or a uint64 tensor (B,), got {type(codes).__name__}')
+        elif codes.dtype not in (torch.uint64, torch.int64) or codes.dim() != 1:
+            raise ValueError(f"the arithmetic codes must be a uint64 (or int64) tensor of shape (B,), got {codes.dtype} "
+                             f"{tuple(codes.shape)}")
+        if not isinstance(share_latent, bool):
+            raise ValueError(f"share_latent must be a bool, got {share_latent!r}")
+        self.codes, self.share_latent = codes, share_latent
+
+    @property
+    def lattice(self) -> bool:
+        return isinstance(self.codes, str)
+
+    def desc(self, code) -> "_lib.Arith":
+        """The C struct ssc_arith over the call's (max_steps + 1, B) int64 block `code`; given codes are copied into its slab 0."""
+        import torch
+        d = _lib.Arith()
+        d.mode = 1 if self.lattice else 2
+        if not self.lattice:
+            if self.codes.numel() != code.size(1):
+                raise ValueError(f"the arithmetic codes hold {self.codes.numel()} entries for {code.size(1)} rows")
+            code[0].copy_(self.codes.view(torch.int64))
+        d.code = code.data_ptr()
+        return d
+
+    def __repr__(self):
+        return f"{type(self).__name__}(codes={'lattice' if self.lattice else 'tensor'!r}, share_latent={self.share_latent})"
+
+
+def arithmetic_from_config(model_cfg):
+    """MODEL.SAMPLER_ARITHMETIC / SAMPLER_ARITHMETIC_SHARE_LATENT -> Arithmetic, or None when off (no new code path runs then).
+    Arithmetic sampling belongs to the word samplers: DECODE_SAMPLER multinomial / top-k / top-p, SAMPLED_BEAM_SEARCH and
+    STOCHASTIC_BEAM_SEARCH False."""
+    on = bool(getattr(model_cfg, "SAMPLER_ARITHMETIC", False))
+    share = bool(getattr(model_cfg, "SAMPLER_ARITHMETIC_SHARE_LATENT", False))
+    if not on:
+        if share:
+            raise ValueError("MODEL.SAMPLER_ARITHMETIC_SHARE_LATENT needs MODEL.SAMPLER_ARITHMETIC True")
+        return None
+    kind = str(model_cfg.DECODE_SAMPLER).strip().lower()
+    if kind not in KINDS:
+        raise ValueError(f"MODEL.SAMPLER_ARITHMETIC needs MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p', got "
+                         f"{model_cfg.DECODE_SAMPLER!r} (arithmetic sampling belongs to the word samplers)")
+    for other in ("SAMPLED_BEAM_SEARCH", "STOCHASTIC_BEAM_SEARCH"):
+        if bool(getattr(model_cfg, other, False)):
+            raise ValueError(f"MODEL.SAMPLER_ARITHMETIC and MODEL.{other} exclude each other (arithmetic sampling belongs to the "
+                             "word-sampled decode)")
+    return Arithmetic("lattice", share_latent=share)
+
+
 def from_config(model_cfg):
     """The sampler the MODEL keys DECODE_SAMPLER / SAMPLER_TOP_K / SAMPLER_TOP_P / SAMPLER_TEMPERATURE / SAMPLER_WITH_REPLACEMENT /
     STOCHASTIC_BEAM_SEARCH describe, or None for "beam" (beam search, the default).  STOCHASTIC_BEAM_SEARCH with DECODE_SAMPLER
@@ -627,6 +696,7 @@ def from_config(model_cfg):
     logit_rules_from_config(model_cfg)
     truncation_from_config(model_cfg)
     mirostat_from_config(model_cfg)
+    arithmetic_from_config(model_cfg)
     from .contrast import contrast_from_config
     contrast_from_config(model_cfg)
     if sbs and kind != "beam":

@@ -196,6 +196,7 @@ class UpDownCaptioner(nn.Module):
         self._logit_rules = None       # logit_rules(): sampling.LogitRules the NEXT eval forwards of a word sampler draw under
         self._truncation = None        # truncation(): sampling.Truncation the NEXT eval forwards of a word sampler cut their steps with
         self._mirostat = None          # mirostat(): sampling.Mirostat the NEXT eval forwards of a word sampler hold their surprise with
+        self._arithmetic = None        # arithmetic(): sampling.Arithmetic the NEXT eval forwards of a word sampler draw their words along
         self._contrast = None          # contrast():contrast.Contrast the NEXT eval forwards of a word sampler decode against an amateur with
         self._decode_prefix = None     # decode_prefix(): a DecodePrefix every caption of the NEXT eval forwards starts with
 
@@ -230,6 +231,7 @@ class UpDownCaptioner(nn.Module):
             model.logit_rules(sampling.logit_rules_from_config(_C.MODEL, vocabulary))
             model.truncation(sampling.truncation_from_config(_C.MODEL))
             model.mirostat(sampling.mirostat_from_config(_C.MODEL))
+            model.arithmetic(sampling.arithmetic_from_config(_C.MODEL))
             from ssc_runtime.contrast import contrast_from_config
             model.contrast(contrast_from_config(_C.MODEL))
         if str(_C.MODEL.DECODE_PREFIX).strip():
@@ -538,6 +540,7 @@ class UpDownCaptioner(nn.Module):
                              logit_rules=self._logit_rules if words else None, prefix=DecodePrefix(ids),
                              **({"truncation": self._truncation} if words and self._truncation is not None else {}),
                              **({"mirostat": self._mirostat} if words and self._mirostat is not None else {}),
+                             **({"arithmetic": self._arithmetic} if words and self._arithmetic is not None else {}),
                              **({"contrast": self._contrast} if words and self._contrast is not None else {}))
         return {"predictions": out[0][:, 0, :]}
 
@@ -589,6 +592,19 @@ class UpDownCaptioner(nn.Module):
             if not mirostat.active:
                 mirostat = None
         self._mirostat = mirostat
+
+    def arithmetic(self, arithmetic):
+        """Arithmetic sampling for the NEXT eval forwards of a word sampler (ssc_runtime.sampling.Arithmetic; include/ssc.h:
+        ssc_arith): every step's draw is made by inverse CDF along a code point per caption, the codes of an image a randomly
+        shifted lattice.  None (the default state): off, the forward is what it is without.  ValueError without a word sampler.
+        Training forwards, scst_step, score_captions and every beam search never read it."""
+        if arithmetic is not None:
+            if not isinstance(arithmetic, sampling.Arithmetic):
+                raise ValueError(f"arithmetic takes a ssc_runtime.sampling.Arithmetic or None, got {type(arithmetic).__name__}")
+            if self.sampler is None or self.sampler.beam_search or self.sampled_beam:
+                raise ValueError("arithmetic needs a word sampler (MODEL.DECODE_SAMPLER 'multinomial', 'top-k' or 'top-p' without "
+                                 "MODEL.SAMPLED_BEAM_SEARCH): arithmetic sampling belongs to the word-sampled decode")
+        self._arithmetic = arithmetic
 
     def contrast(self, contrast):
         """A contrast for the NEXT eval forwards of a word sampler (ssc_runtime.contrast.Contrast; include/ssc.h: ssc_contrast):
@@ -755,6 +771,7 @@ class UpDownCaptioner(nn.Module):
                                          **({"logit_rules": self._logit_rules} if self._logit_rules is not None else {}),
                                          **({"truncation": self._truncation} if self._truncation is not None else {}),
                                          **({"mirostat": self._mirostat} if self._mirostat is not None else {}),
+                                         **({"arithmetic": self._arithmetic} if self._arithmetic is not None else {}),
                                          **({"contrast": self._contrast} if self._contrast is not None else {}))
         return self._traced(pred, rec, torch.arange(B, device=dev))
 
