@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB = os.path.join(HERE, "libssc_hip.so")
-SOURCES = ["gemm.hip", "pointwise.hip", "lstm.hip", "attention.hip", "sequence.hip", "decode.hip", "fsm.hip", "search.hip", "ensemble.hip", "distill.hip", "unlikelihood.hip", "sample.hip", "sched_sampling.hip", "score.hip", "prefix.hip", "latent_guide.hip", "attn_trace.hip", "sbs.hip", "sampled_beam.hip", "diverse_beam.hip", "rules_beam.hip", "logit_rules.hip", "truncation.hip", "mirostat.hip", "arith.hip", "contrast.hip", "caption_eval.hip", "consensus.hip", "caption_select.hip", "scst.hip", "collective.hip"]
+SOURCES = ["gemm.hip", "pointwise.hip", "cross_entropy.hip", "lstm.hip", "attention.hip", "sequence.hip", "decode.hip", "fsm.hip", "search.hip", "ensemble.hip", "sample.hip", "sched_sampling.hip", "score.hip", "prefix.hip", "latent_guide.hip", "attn_trace.hip", "sbs.hip", "sampled_beam.hip", "diverse_beam.hip", "rules_beam.hip", "logit_rules.hip", "truncation.hip", "mirostat.hip", "arith.hip", "contrast.hip", "caption_eval.hip", "consensus.hip", "caption_select.hip", "scst.hip", "collective.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-ffp-contract=off", "-fno-slp-vectorize", "-I" + INCLUDE, "-I" + CSRC]
 
 

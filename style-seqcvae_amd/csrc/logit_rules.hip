@@ -4,8 +4,8 @@
 // one step; ssc_decode_sample_opts (sample.hip) issues it between each step's decode step and its draw.
 // Two forms, chosen on the host:
 //   (A) with a bias, one workgroup of 256 per row streams the row once, x += bias: 16 bytes per lane where both rows share one
-//       misalignment and both leading dimensions are multiples of 4 (scalar head / float4 bulk / scalar tail, as distill.hip's
-//       kd_scan), scalar accesses throughout otherwise.  One fp32 add per element either way.  A workgroup barrier, then the sparse
+//       misalignment and both leading dimensions are multiples of 4 (scalar head / float4 bulk / scalar tail, as cross_entropy.hip's
+//       ce_pair_scan), scalar accesses throughout otherwise.  One fp32 add per element either way.  A workgroup barrier, then the sparse
 //       edits by the first wave.
 //   (B) without a bias no thread walks the row: one wave per row, LOGIT_RULES_ROWS rows per workgroup, at most t + n_suppress + 1
 //       elements touched per row.

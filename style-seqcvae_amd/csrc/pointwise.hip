@@ -378,168 +378,8 @@ __global__ void latent_bwd_kernel(const ssc_latent_bwd_desc d, const ssc_free_bi
 
 
 // ---------------------------------------------------------------------------------------------
-// cross entropy over the vocabulary
+// log-softmax over the vocabulary
 // ---------------------------------------------------------------------------------------------
-__global__ void ce_fwd_kernel(const float* __restrict__ logits, int ldl, const int64_t* __restrict__ targets,
-                              const float* __restrict__ w, int V, float* __restrict__ lse, float* __restrict__ nllw) {
-  __shared__ float sh[16];
-  int row = blockIdx.x;
-  if (w[row] == 0.f) {  // padded target: no loss, and its logits row may not have been computed at all
-    if (threadIdx.x == 0) { lse[row] = 0.f; nllw[row] = 0.f; }
-    return;
-  }
-  const float* p = logits + (size_t)row * ldl;
-  float mx = -INFINITY;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) mx = fmaxf(mx, p[v]);
-  mx = ssc_block_reduce(mx, sh, true);
-  float s = 0.f;
-  for (int v = threadIdx.x; v < V; v += blockDim.x) s += expf(p[v] - mx);
-  s = ssc_block_reduce(s, sh, false);
-  if (threadIdx.x == 0) {
-    float l = mx + logf(s);
-    lse[row] = l;
-    nllw[row] = w[row] * (l - p[targets[row]]);
-  }
-}
-
-// loss[b] from the [w*row(eps)] block.  nllw0 (optional) is the [w*row(0)] block behind it: same = 1 (eps = 0, the two blocks are
-// one) writes it as a copy of nllw, same = 0 reads it; nll[b] (optional) is the unsmoothed loss of the same forward.
-// One lane per caption, eight of its T loads in flight, summed in step order.
-__global__ void ce_loss_kernel(const float* __restrict__ nllw, float* __restrict__ nllw0, int same,
-                               const float* __restrict__ nvalid, int T, int B, float* __restrict__ loss,
-                               float* __restrict__ nll) {
-  int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const bool read0 = nllw0 && !same, copy0 = nllw0 && same;
-  float s = 0.f, s0 = 0.f;
-  for (int t = 0; t < T; t += 8) {
-    float x[8], x0[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const size_t i = (size_t)min(t + u, T - 1) * B + b;
-      x[u] = nllw[i];
-      x0[u] = read0 ? nllw0[i] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (t + u < T) {
-        s += x[u];
-        s0 += x0[u];
-        if (copy0) nllw0[(size_t)(t + u) * B + b] = x[u];
-      }
-    }
-  }
-  float n = nvalid[b];
-  const float l = n * (s / (n + 1e-13f));
-  loss[b] = l;
-  if (nll) nll[b] = read0 ? n * (s0 / (n + 1e-13f)) : l;
-}
-
-__global__ void ce_bwd_kernel(float* __restrict__ logits, int ldl, const int64_t* __restrict__ targets,
-                              const float* __restrict__ w, const float* __restrict__ nvalid, const float* __restrict__ lse,
-                              const float* __restrict__ gl, int B, int V) {
-  int row = blockIdx.x;
-  int b = row % B;
-  float n = nvalid[b];
-  float coef = gl[b] * w[row] * (n / (n + 1e-13f));
-  float* p = logits + (size_t)row * ldl;
-  float l = lse[row];
-  int tgt = (int)targets[row];
-  if (coef == 0.f) {
-    for (int v = threadIdx.x; v < V; v += blockDim.x) p[v] = 0.f;
-    return;
-  }
-  for (int v = threadIdx.x; v < V; v += blockDim.x) {
-    float sm = expf(p[v] - l);
-    p[v] = (sm - (v == tgt ? 1.f : 0.f)) * coef;
-  }
-}
-
-// ---- label smoothing (ssc.h "Label-smoothed vocabulary cross-entropy") ---------------------------------------------
-// row(eps) = lse - (1-eps) x[y] - (eps/V) sum_v x[v] = (lse - x[y]) - (eps/V) sum_v (x[v] - x[y]): the unsmoothed NLL of the row
-// and one extra sum, taken relative to the target logit so that no large lse - mean(x) difference is ever formed.
-// Elements [0, head) and [head + 4 * n4, V) of a row go one by one, the n4 groups of four in between as 16-byte accesses (the
-// host splits the row: with ldl % 4 == 0 every row shares the misalignment of the first; head = V, n4 = 0 is the scalar path
-// throughout).  Columns V .. ldl-1 are never touched.
-__device__ __forceinline__ void ce_online(float x, float r, float& m, float& s, float& d) {
-  if (x > m) { s *= expf(m - x); m = x; }
-  s += expf(x - m);
-  d += x - r;
-}
-
-// one scan of the row: running max m, sum of exp(x - m) rescaled when m moves, and the sum of x - x[y]
-__global__ __launch_bounds__(256) void ce_fwd_smooth_kernel(const float* __restrict__ logits, int ldl,
-                                                            const int64_t* __restrict__ targets, const float* __restrict__ w,
-                                                            int V, int head, int n4, float eps_over_v, float* __restrict__ lse,
-                                                            float* __restrict__ nllw, float* __restrict__ nllw0) {
-  __shared__ float sh[16];
-  const int row = blockIdx.x;
-  const float wr = w[row];
-  if (wr == 0.f) {  // padded target: no loss, and its logits row may not have been computed at all
-    if (threadIdx.x == 0) { lse[row] = 0.f; nllw[row] = 0.f; nllw0[row] = 0.f; }
-    return;
-  }
-  const float* p = logits + (size_t)row * ldl;
-  const float r = p[targets[row]];
-  float m = -INFINITY, s = 0.f, d = 0.f;
-  const float4* p4 = reinterpret_cast<const float4*>(p + head);
-#pragma unroll 2
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    const float4 x = p4[i];
-    const float mx = fmaxf(fmaxf(x.x, x.y), fmaxf(x.z, x.w));
-    if (mx > m) { s *= expf(m - mx); m = mx; }
-    s += (expf(x.x - m) + expf(x.y - m)) + (expf(x.z - m) + expf(x.w - m));
-    d += ((x.x - r) + (x.y - r)) + ((x.z - r) + (x.w - r));
-  }
-  const int tail = head + (n4 << 2), ns = head + (V - tail);
-  for (int k = threadIdx.x; k < ns; k += 256) ce_online(p[ssc_row_split_col(k, head, tail)], r, m, s, d);
-  const float M = ssc_block_reduce(m, sh, true);
-  s = ssc_block_reduce(s * expf(m - M), sh, false);   // a thread without elements: m = -inf, s = 0 -> 0
-  d = ssc_block_reduce(d, sh, false);
-  if (threadIdx.x == 0) {
-    const float l = M + logf(s);
-    const float nll = l - r;
-    lse[row] = l;
-    nllw[row] = wr * (nll - eps_over_v * d);
-    nllw0[row] = wr * nll;
-  }
-}
-
-// in place: x <- (softmax(x) - keep [v == y] - eps/V) * coef, keep = 1 - eps
-__global__ __launch_bounds__(256) void ce_bwd_smooth_kernel(float* __restrict__ logits, int ldl, const int64_t* __restrict__ targets,
-                                                            const float* __restrict__ w, const float* __restrict__ nvalid,
-                                                            const float* __restrict__ lse, const float* __restrict__ gl, int B,
-                                                            int V, int head, int n4, float keep, float eps_over_v) {
-  const int row = blockIdx.x;
-  const int b = row % B;
-  const float n = nvalid[b];
-  const float coef = gl[b] * w[row] * (n / (n + 1e-13f));
-  float* p = logits + (size_t)row * ldl;
-  float4* p4 = reinterpret_cast<float4*>(p + head);
-  const int tail = head + (n4 << 2), ns = head + (V - tail);
-  if (coef == 0.f) {  // never reads the row: a padded target's logits may hold anything
-    for (int i = threadIdx.x; i < n4; i += 256) p4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = threadIdx.x; k < ns; k += 256) p[ssc_row_split_col(k, head, tail)] = 0.f;
-    return;
-  }
-  const float l = lse[row];
-  const int tgt = (int)targets[row];
-#pragma unroll 2
-  for (int i = threadIdx.x; i < n4; i += 256) {
-    float4 x = p4[i];
-    const int v = head + (i << 2);
-    x.x = (expf(x.x - l) - (v == tgt ? keep : 0.f) - eps_over_v) * coef;
-    x.y = (expf(x.y - l) - (v + 1 == tgt ? keep : 0.f) - eps_over_v) * coef;
-    x.z = (expf(x.z - l) - (v + 2 == tgt ? keep : 0.f) - eps_over_v) * coef;
-    x.w = (expf(x.w - l) - (v + 3 == tgt ? keep : 0.f) - eps_over_v) * coef;
-    p4[i] = x;
-  }
-  for (int k = threadIdx.x; k < ns; k += 256) {
-    const int v = ssc_row_split_col(k, head, tail);
-    p[v] = (expf(p[v] - l) - (v == tgt ? keep : 0.f) - eps_over_v) * coef;
-  }
-}
-
 __global__ void log_softmax_kernel(const float* __restrict__ logits, int ldl, int V, float* __restrict__ out, int ldo) {
   __shared__ float sh[16];
   int row = blockIdx.x;
@@ -903,77 +743,6 @@ extern "C" int ssc_latent_prior_sample_pm(const float* eps, int ldeps, const flo
   if (!eps || !z || G <= 0 || Z <= 0 || ldeps < Z || (pm && ldpm < Z) || (pv && ldpv < Z) || ldz < Z) return SSC_EINVAL;
   SSC_LAUNCH(latent_prior_sample_pm_kernel, dim3(ssc_cdiv((Z + 3) & ~3, 64), G), dim3(64), 0, S(stream), eps, ldeps, pm, ldpm, pv, ldpv, sent,
              pm_scale, sqrtf(prior_var), G, Z, z, ldz);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-
-// lse must hold 2*T*B floats: [lse | w*nll]
-extern "C" int ssc_ce_fwd(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T,
-                          int B, int V, float* lse, float* loss, void* stream) {
-  if (!logits || !targets || !w || !nvalid || !lse || !loss || T <= 0 || B <= 0 || V <= 0 || ldl < V) return SSC_EINVAL;
-  int rows = T * B;
-  SSC_LAUNCH(ce_fwd_kernel, dim3(rows), dim3(256), 0, S(stream), logits, ldl, targets, w, V, lse, lse + rows);
-  SSC_CHECK_LAUNCH();
-  SSC_LAUNCH(ce_loss_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, S(stream), lse + rows, (float*)nullptr, 0, nvalid, T, B, loss,
-             (float*)nullptr);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-extern "C" int ssc_ce_bwd(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid,
-                          const float* lse, const float* gl, int T, int B, int V, void* stream) {
-  if (!logits || !targets || !w || !nvalid || !lse || !gl || T <= 0 || B <= 0 || V <= 0 || ldl < V) return SSC_EINVAL;
-  SSC_LAUNCH(ce_bwd_kernel, dim3(T * B), dim3(256), 0, S(stream), logits, ldl, targets, w, nvalid, lse, gl, B, V);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-// the three blocks [lse], [w*row(eps)], [w*row(0)] (T*B floats each) given one by one
-int ssc_ce_fwd_smooth_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
-                             int V, float eps, float* lse, float* nllw, float* nllw0, float* loss, float* nll, hipStream_t st) {
-  if (!logits || !targets || !w || !nvalid || !lse || !nllw || !nllw0 || !loss || T <= 0 || B <= 0 || V <= 0 || ldl < V ||
-      !ssc_ce_eps_ok(eps))
-    return SSC_EINVAL;
-  if (((uintptr_t)logits & 3u) != 0) return SSC_EALIGN;
-  const int rows = T * B;
-  if (eps == 0.f) {  // the kernels of ssc_ce_fwd; the [w*row(0)] block is a copy of the [w*row(eps)] block
-    SSC_LAUNCH(ce_fwd_kernel, dim3(rows), dim3(256), 0, st, logits, ldl, targets, w, V, lse, nllw);
-    SSC_CHECK_LAUNCH();
-  } else {
-    int head, n4;
-    ssc_row_split(logits, ldl, nullptr, 0, V, &head, &n4);
-    SSC_LAUNCH(ce_fwd_smooth_kernel, dim3(rows), dim3(256), 0, st, logits, ldl, targets, w, V, head, n4,
-               (float)((double)eps / V), lse, nllw, nllw0);
-    SSC_CHECK_LAUNCH();
-  }
-  SSC_LAUNCH(ce_loss_kernel, dim3(ssc_cdiv(B, 64)), dim3(64), 0, st, nllw, nllw0, eps == 0.f ? 1 : 0, nvalid, T, B, loss, nll);
-  SSC_CHECK_LAUNCH();
-  return SSC_OK;
-}
-
-// lse must hold 3*T*B floats: [lse | w*row(eps) | w*row(0)]
-extern "C" int ssc_ce_fwd_smooth(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid,
-                                 int T, int B, int V, float eps, float* lse, float* loss, float* nll, void* stream) {
-  if (!lse || T <= 0 || B <= 0) return SSC_EINVAL;
-  const size_t rows = (size_t)T * B;
-  return ssc_ce_fwd_smooth_blocks(logits, ldl, targets, w, nvalid, T, B, V, eps, lse, lse + rows, lse + 2 * rows, loss, nll,
-                                  S(stream));
-}
-
-extern "C" int ssc_ce_bwd_smooth(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid,
-                                 const float* lse, const float* gl, int T, int B, int V, float eps, void* stream) {
-  if (!logits || !targets || !w || !nvalid || !lse || !gl || T <= 0 || B <= 0 || V <= 0 || ldl < V || !ssc_ce_eps_ok(eps))
-    return SSC_EINVAL;
-  if (((uintptr_t)logits & 3u) != 0) return SSC_EALIGN;
-  if (eps == 0.f) {
-    SSC_LAUNCH(ce_bwd_kernel, dim3(T * B), dim3(256), 0, S(stream), logits, ldl, targets, w, nvalid, lse, gl, B, V);
-  } else {
-    int head, n4;
-    ssc_row_split(logits, ldl, nullptr, 0, V, &head, &n4);
-    SSC_LAUNCH(ce_bwd_smooth_kernel, dim3(T * B), dim3(256), 0, S(stream), logits, ldl, targets, w, nvalid, lse, gl, B, V, head,
-               n4, 1.f - eps, (float)((double)eps / V));
-  }
   SSC_CHECK_LAUNCH();
   return SSC_OK;
 }

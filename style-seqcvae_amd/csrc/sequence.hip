@@ -580,15 +580,15 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   SSC_TRY(resolve_train_opts(opts, ul, cfg, &ro));
   const ssc_train_opts& o = ro.o;
   const bool fb_on = ro.fb_on, ss_on = ro.ss_on;   // (fb_on: a free-bits floor on the KL, the _fb kernels of the latent head)
-  bool kd_on = ro.kd_on, ul_on = ro.ul_on;
   if (!workspace || !loss || !kld) return SSC_EINVAL;
   if (!ssc_aligned16(workspace)) return SSC_EALIGN;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
   // (the teacher's rows may not meet the logits block the backward overwrites: checked here, ahead of the first launch)
-  if (kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
-  if (ul_on) SSC_TRY(ssc_unlike_check(ro.ul, l.T, &ul_on));
+  bool on;
+  if (ro.kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &on));
+  if (ro.ul_on) SSC_TRY(ssc_unlike_check(ro.ul, l.T, &on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -805,16 +805,10 @@ static int train_fwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   } else {
     SSC_TRY(gemm_rows(c, true, {{hd_all, l.Hp, p->out_w, p->ld_out_w, H}}, TB, V, W + l.logits, l.Vp, p->out_b));
   }
-  // label_smoothing 0 launches the kernels of ssc_ce_fwd; the unsmoothed loss of this forward lands in l.nll either way
-  if (kd_on)   // the soft targets of a teacher beside the (smoothed) hard loss: distill.hip
-    return ssc_ce_fwd_distill_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, o.distill, W + l.lse,
-                                     W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
-  if (ul_on)   // the words the caption has already used are pushed down beside the (smoothed) hard loss: unlikelihood.hip
-    return ssc_ce_fwd_unlike_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, ro.ul,
-                                    W + l.lse, W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
-  SSC_TRY(ssc_ce_fwd_smooth_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, W + l.lse,
-                                   W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st));
-  return SSC_OK;
+  // label_smoothing 0 launches the kernels of ssc_ce_fwd; the unsmoothed loss of this forward lands in l.nll either way.  Beside the
+  // (smoothed) hard loss: the soft targets of a teacher (o.distill), or the words the caption has already used pushed down (ro.ul)
+  return ssc_ce_fwd_blocks(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, T, B, V, cfg->label_smoothing, o.distill, ro.ul, W + l.lse,
+                           W + l.lse + TB, W + l.nllw0, loss, W + l.nll, st);
 }
 
 extern "C" int ssc_train_fwd_opts(const ssc_model_cfg* cfg, const ssc_params* p, const ssc_batch* bt, void* workspace,
@@ -958,15 +952,15 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
   TrainOpts ro;   // the opts of the forward: its gates (free bits), its fed ids (sched on), its teacher and row sums (distill), its rows' G (unlikelihood)
   SSC_TRY(resolve_train_opts(opts, ul, cfg, &ro));
   const ssc_train_opts& o = ro.o;
-  bool kd_on = ro.kd_on, ul_on = ro.ul_on;
   if (phases == 0 || phases > 255u) return SSC_EINVAL;
   if (phases & 2u) phases |= 64u | 128u;   // 2 = both halves of the embedding / attention-LSTM / attention phase
   if (!workspace || !gl || !gk || !g) return SSC_EINVAL;
   const Layout l = make_layout(cfg, bt->B, bt->R, bt->L);
   if (workspace_bytes < l.total * sizeof(float)) return SSC_EWORKSPACE;
   float* W = (float*)workspace;
-  if (kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &kd_on));
-  if (ul_on) SSC_TRY(ssc_unlike_check(ro.ul, l.T, &ul_on));
+  bool on;
+  if (ro.kd_on) SSC_TRY(ssc_distill_check(o.distill, W + l.logits, l.Vp, (size_t)l.T * l.B, l.V, &on));
+  if (ro.ul_on) SSC_TRY(ssc_unlike_check(ro.ul, l.T, &on));
   hipStream_t st = (hipStream_t)stream;
   Ctx c{st, W + l.slabs, l.slab_floats};
   const int B = l.B, R = l.R, T = l.T, E = l.E, H = l.H, A = l.A, F = l.F, Z = l.Z, S = l.S, V = l.V, H4 = l.H4;
@@ -985,12 +979,9 @@ static int train_bwd_impl(const ssc_model_cfg* cfg, const ssc_params* p, const s
 
   if (phases & (1u | 16u)) {
   // ---- vocabulary head ------------------------------------------------------------------------------
-  if (kd_on)   // (the forward of this minibatch left the rows' log-sum-exps in kd->rows)
-    SSC_TRY(ssc_ce_bwd_distill(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, o.distill, st));
-  else if (ul_on)   // (the forward of this minibatch left the rows' G in ul->rows)
-    SSC_TRY(ssc_ce_bwd_unlike(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, ro.ul, st));
-  else
-    SSC_TRY(ssc_ce_bwd_smooth(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, st));
+  // (the forward of this minibatch left the rows' log-sum-exps in kd->rows, or the rows' G in ul->rows)
+  SSC_TRY(ssc_ce_bwd_terms(W + l.logits, l.Vp, tok + B, W + l.w, W + l.nvalid, W + l.lse, gl, T, B, V, cfg->label_smoothing, o.distill, ro.ul,
+                           st));
   const float* dlog = W + l.logits;
   {  // every zero-initialised buffer of this phase in one launch
     FillList f;

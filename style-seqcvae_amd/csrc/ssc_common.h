@@ -74,8 +74,8 @@ __device__ __forceinline__ float ssc_block_reduce(float v, float* sh, bool is_ma
   return r;
 }
 
-// How the cross-entropy kernels that stream a row (pointwise.hip: label smoothing, distill.hip: with a teacher's row b beside it)
-// walk it: elements [0, head) and [head + 4 * n4, V) one by one, the n4 groups of four in between as 16-byte accesses.  With
+// How the cross-entropy kernels that stream a row (cross_entropy.hip: every form but the plain pair; distillation with a teacher's
+// row b beside it) walk it: elements [0, head) and [head + 4 * n4, V) one by one, the n4 groups of four in between as 16-byte accesses.  With
 // leading dimensions that are multiples of 4 every row shares the first row's misalignment; a second matrix must share it too.
 // head = V, n4 = 0 is the scalar path throughout.
 static inline void ssc_row_split(const float* a, int lda, const float* b, int ldb, int V, int* head, int* n4) {
@@ -151,25 +151,19 @@ int ssc_beam_rows_dense(bool norm, const float* lp, int ldlp, const uint8_t* fsm
 int ssc_beam_merge(const float* sval, const int64_t* sidx, const float* last_lp, int B, int S, int beam, int per_node,
                    int64_t* pred, float* lp_out, int64_t* backptr, int end_index, int* ctl, int step_index, int max_steps,
                    int* host_flag, hipStream_t st);
-// ssc_ce_fwd_smooth (pointwise.hip) with its three blocks given one by one: the train workspace keeps the [w*row(0)] block apart from
-// the first two, whose place - and with it every other buffer's - is what it was before the third block existed
-int ssc_ce_fwd_smooth_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
-                             int V, float eps, float* lse, float* nllw, float* nllw0, float* loss, float* nll, hipStream_t st);
-// distillation (distill.hip, include/ssc.h: ssc_distill): the descriptor's refusals - *on = kd != NULL and alpha > 0; logits NULL
-// leaves the overlap test to a later call -, and ssc_ce_fwd_distill with its three blocks given one by one
+// The cross-entropy of the train step (cross_entropy.hip).  The descriptors' refusals (include/ssc.h: ssc_distill, ssc_unlikelihood):
+// *on = the descriptor is there and its alpha > 0; logits NULL leaves distillation's overlap test, T = 0 unlikelihood's limit on the
+// steps to a later call.
 int ssc_distill_check(const ssc_distill* kd, const float* logits, int ldl, size_t rows, int V, bool* on);
-int ssc_ce_fwd_distill_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
-                              int V, float eps, const ssc_distill* kd, float* lse, float* nllw, float* nllw0, float* loss, float* nll,
-                              hipStream_t st);
-// the per-caption sums of three row blocks in one launch (distill.hip: kd_loss_kernel), shared by distillation and unlikelihood training
-int ssc_ce_loss3(const float* nllw, const float* nllw0, const float* termw, const float* nvalid, int T, int B, float* loss, float* nll,
-                 float* term, hipStream_t st);
-// unlikelihood training (unlikelihood.hip, include/ssc.h: ssc_unlikelihood): the descriptor's refusals - *on = ul != NULL and
-// alpha > 0; T = 0 leaves the limit on the steps to a later call -, and ssc_ce_fwd_unlike with its three blocks given one by one
 int ssc_unlike_check(const ssc_unlikelihood* ul, int T, bool* on);
-int ssc_ce_fwd_unlike_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B,
-                             int V, float eps, const ssc_unlikelihood* ul, float* lse, float* nllw, float* nllw0, float* loss,
-                             float* nll, hipStream_t st);
+// ssc_ce_fwd_smooth / _distill / _unlike (kd, ul: optional, at most one of them on) with the three blocks [lse], [w*row(eps)],
+// [w*row(0)] given one by one: the train workspace keeps the third apart from the first two, whose place - and with it every other
+// buffer's - is what it was before the third block existed.  ssc_ce_bwd_terms: the backward of that forward.
+int ssc_ce_fwd_blocks(const float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, int T, int B, int V,
+                      float eps, const ssc_distill* kd, const ssc_unlikelihood* ul, float* lse, float* nllw, float* nllw0, float* loss,
+                      float* nll, hipStream_t st);
+int ssc_ce_bwd_terms(float* logits, int ldl, const int64_t* targets, const float* w, const float* nvalid, const float* lse,
+                     const float* gl, int T, int B, int V, float eps, const ssc_distill* kd, const ssc_unlikelihood* ul, hipStream_t st);
 int ssc_decode_att_table_enabled();   // the "dec_att_table" switch (decode.hip)
 // the start of a one-call decode with the early-stop protocol (search.hip): ctl[0] = max_steps, the counters behind it zero;
 // tokens0 (B) = end_index, the token the first step feeds - or, with a start state (ssc_start_state), its tokens, an id outside

@@ -178,17 +178,18 @@ def dump(path):
     torch.save(out, path)
 
 
-def main():
-    if sys.argv[1] == "--dump":
-        return dump(sys.argv[2])
-    variant = os.path.join(PKG, sys.argv[1], "libssc_hip.so")
+def compare(script, variant_dir):
+    """The two-process driver (shared with tools/ce_bits_ab.py): `script --dump PATH` - which saves a dict name -> int32 tensor - runs
+    once against the in-tree library and once against style-seqcvae_amd/<variant_dir>/libssc_hip.so, each a fresh child process; prints
+    the JSON line and exits 1 if any tensor differs."""
+    variant = os.path.join(PKG, variant_dir, "libssc_hip.so")
     assert os.path.exists(variant), variant
     import torch
     with tempfile.TemporaryDirectory() as td:
         got = {}
         for name, env in (("tree", {}), ("variant", {"SSC_DEBUG": "1", "SSC_LIB_PATH": variant})):
             path = os.path.join(td, name + ".pt")
-            subprocess.run([sys.executable, os.path.abspath(__file__), "--dump", path], env={**os.environ, **env}, check=True, timeout=900)
+            subprocess.run([sys.executable, os.path.abspath(script), "--dump", path], env={**os.environ, **env}, check=True, timeout=900)
             got[name] = torch.load(path)
     a, b = got["tree"], got["variant"]
     assert list(a) == list(b)
@@ -196,10 +197,16 @@ def main():
     groups = {}
     for k in a:
         groups[k.split("/")[0]] = groups.get(k.split("/")[0], 0) + 1
-    print(json.dumps({"variant": sys.argv[1], "tensors": len(a), "words": int(sum(t.numel() for t in a.values())), "by_entry": groups,
+    print(json.dumps({"variant": variant_dir, "tensors": len(a), "words": int(sum(t.numel() for t in a.values())), "by_entry": groups,
                       "differ": differ}))
     sys.exit(1 if differ else 0)
 
 
+def main(dump):
+    if sys.argv[1] == "--dump":
+        return dump(sys.argv[2])
+    compare(sys.argv[0], sys.argv[1])
+
+
 if __name__ == "__main__":
-    main()
+    main(dump)
